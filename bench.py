@@ -10,10 +10,14 @@ One "step" = one ``IPSNet.ips(patches)`` call (no-grad, eval, eager loading: the
 tensor is resident in HBM when the timed region starts): embed every patch, score,
 run the whole selection loop, gather the M winners.
 
-``value`` follows SURVEY.md 8 d-1: each of the K timed calls is bracketed by barrier + device
+``value`` follows SURVEY.md 8 d-1: each of the K = --steps timed calls is bracketed by barrier + device
 sync, a call's time is the max over ranks, ``value`` = patches per call / the MEDIAN call time
-(``ms_per_step``).  ``value_pipelined`` is the same K calls enqueued back to back between two
-fences (what a training loop sees when the host runs ahead).  The default single-GPU run also
+(``ms_per_step``).  A plain run does only that: set up, W warm-up calls, the K timed calls, the line.
+``--dump-outputs DIR`` then writes what the last timed call returned (DIR/mem_patch.npy, mem_pos.npy,
+mem_idx.npy; float32 / float64, at most 64 MB in all) so that two builds can be compared output for output.
+
+Everything below is measured with ``--full`` only.  ``value_pipelined`` is the same K calls enqueued back
+to back between two fences (what a training loop sees when the host runs ahead).  The full single-GPU run also
 times every other BASELINE configuration that fits one GPU into ``also_measured`` (b1 = d-1's
 primary shape, mnist3000 = configs[2], cam / cam_x16 = configs[3], cam_native = the reference's
 shipped CAMELYON sizes, traffic = configs[0]'s model on the GPU, native50 = the reference's shipped
@@ -30,7 +34,7 @@ Workloads (``ips_amd.synth.BENCH_WORKLOADS``; weights seed 7, patches seed 21):
   ``python bench.py --gpus N`` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself
   (a child ``python -m torch.distributed.run``; the parent never touches the GPU) and relays rank 0's line.
 
-Every line carries
+Every ``--full`` line carries
   parity        ``net.last_mem_idx`` after the timed loop against the REFERENCE's selection on the same
                 inputs (tests/golden/bench_<workload>.npz, recorded by running the imported reference in the
                 build container, tools/gen_golden_bench.py) - on every rank;
@@ -78,10 +82,17 @@ LABEL = {
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed calls (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: value_pipelined, encoder roofline (HIP events "
+                         "around the launches), parity against the reference fixtures, the other precisions and BASELINE "
+                         "configurations, rank_shard_model, the N > 1 extras and cpu_baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed calls, write what the last one returned as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed, seeded sample of larger outputs)")
     ap.add_argument("--batch", type=int, default=None, help="images per step (default: the workload's, 16 / 1)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget of the cpu_baseline leg (0 = skip)")
     ap.add_argument("--dedup-blank", action="store_true",
                     help="secondary measurement: exact blank-patch deduplication in front of the encoder "
                          "(IPSX_DEDUP_BLANK=1; the encoder then runs on the ~7 %% non-blank patches only, so the "
@@ -96,26 +107,39 @@ def parse():
                     help="secondary measurement: lazy loading - the patch tensor starts in pinned HOST memory and "
                          "is streamed over PCIe inside every step (the PCIe-inclusive rate; never the headline)")
     ap.add_argument("--no-kernel-events", action="store_true",
-                    help="do not bracket the encoder launches with HIP events (no `roofline.achieved`): what the events themselves "
+                    help="--full: do not bracket the encoder launches with HIP events (no `roofline.achieved`): what the events themselves "
                          "cost - at one image per call they move the dispatcher's placement of the loop's workgroup, DESIGN 6")
     ap.add_argument("--config", default=None, choices=sorted(FLOP_PER_PATCH),
                     help="default: mnist at every --gpus N (the headline, BASELINE configs[1], B=16; patch-sharded at N > 1, "
                          "where mnist3000 = configs[2] is also allowed); the others are secondary single-GPU measurements: b1 "
                          "(headline image 0 alone), native50, traffic, cam, cam_native (the reference's shipped M = I = 5000)")
     ap.add_argument("--also", default="all",
-                    help="default run only: which other BASELINE configurations are timed into `also_measured` ('all', 'none', "
+                    help="--full default run only: which other BASELINE configurations are timed into `also_measured` ('all', 'none', "
                          "or a comma list of b1,mnist3000,cam,cam_x16,cam_native,traffic,native50,rank_shard_model; at N > 1 only mnist3000 - "
                          "configs[2], sharded - and the single-rank time of the headline, `n1_value_same_workload`)")
     ap.add_argument("--also-steps", type=int, default=0,
-                    help="timed calls per `also_measured` leg, each way (0 = sized per leg: ~0.3 s of calls, 10 to 40)")
-    ap.add_argument("--leg-timeout", type=int, default=120, help="seconds an `also_measured` leg may take before the line is "
+                    help="--full: timed calls per `also_measured` leg, each way (0 = sized per leg: ~0.3 s of calls, 10 to 40)")
+    ap.add_argument("--leg-timeout", type=int, default=120, help="--full: seconds an `also_measured` leg may take before the line is "
                     "printed without it")
     ap.add_argument("--watchdog", type=int, default=600, help="seconds the headline measurement may take before every thread's "
                     "stack is dumped to stderr and the run exits")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="strong (default): BASELINE configs[1], the same 16 x 2500 patches at every N, patch axis sharded over "
                          "the ranks; weak: 2500 patches of every image per GPU (the image grows with N; N = 4 is configs[2])")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # these shape what only a --full run measures: set without it, the caller would lose that record unknowingly
+        moot = ["--" + k.replace("_", "-") for k in FULL_ONLY_OPTIONS if getattr(args, k) != ap.get_default(k)]
+        launcher = args.gpus > 1 and "WORLD_SIZE" not in os.environ     # (its rank 0 says it)
+        if moot and not launcher and os.environ.get("RANK", "0") == "0":
+            print("bench.py: ignored without --full (a plain run does not measure what they set): %s" % ", ".join(moot),
+                  file=sys.stderr)
+    return args
+
+
+FULL_ONLY_OPTIONS = ("cpu_seconds", "also", "also_steps", "leg_timeout", "no_kernel_events")
 
 
 def host_description():
@@ -410,6 +434,33 @@ class Ctx:
     def __init__(self, world, rank, dev, share):
         self.world, self.rank, self.dev, self.share = world, rank, dev, share
         self.cpu_job = None
+        self.outputs = None                                     # --dump-outputs: the last timed call's results (host)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def host_outputs(mem_patch, mem_pos, mem_idx):
+    """What a caller of ``ips()`` receives - the M selected patches, their positional rows - and the selected indices,
+    as host arrays: float32 (half-precision patch storage widened), the indices as float64 (exact)."""
+    arrays = {"mem_patch": mem_patch.float().cpu().numpy()}
+    if mem_pos is not None:
+        arrays["mem_pos"] = mem_pos.float().cpu().numpy()
+    if mem_idx is not None:
+        arrays["mem_idx"] = mem_idx.cpu().numpy().astype(np.float64)
+    return arrays
+
+
+def dump_outputs(arrays, path):
+    """DIR/<name>.npy per array; beyond DUMP_LIMIT_BYTES in all, every array keeps the same share of its elements, a
+    fixed seeded sample (flattened, in index order) - the same elements on every run of the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, a.size * DUMP_LIMIT_BYTES // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # Driver-run coverage (VERDICT r03 item 1): the default single-GPU invocation times the headline AND every other BASELINE
@@ -435,9 +486,10 @@ def make_input(conf, name, B, batch, dev_for_extra):
 
 
 def measure(args, ctx, name, batch=None, steps=20, warmup=5, cpu_seconds=0.0, headline=True):
-    """One workload: build it, warm up, time it both ways (SURVEY d-1: device sync around every call, median = `value`;
-    and the same K calls back to back between two fences = `value_pipelined`), check the selection against the
-    reference-recorded fixture, price the encoder launches.  Returns the JSON object on rank 0 (None elsewhere)."""
+    """One workload: build it, warm up, time the K calls (SURVEY d-1: device sync around every call, median = `value`).
+    With --full also, before those: the same K calls back to back between two fences = `value_pipelined`, with the
+    encoder launches bracketed by HIP events (the roofline), and the selection checked against the reference-recorded
+    fixture.  Returns the JSON object on rank 0 (None elsewhere)."""
     world, rank, dev, share = ctx.world, ctx.rank, ctx.dev, ctx.share
     from ips_amd import hip, synth
     from ips_amd import dist as ipsd
@@ -483,7 +535,7 @@ def measure(args, ctx, name, batch=None, steps=20, warmup=5, cpu_seconds=0.0, he
         x = torch.cat((x, more), 0)
         del more
 
-    timings = [] if world > 1 else None
+    timings = [] if world > 1 and args.full else None
     if world == 1:
         def step():
             return net.ips(x)
@@ -520,7 +572,7 @@ def measure(args, ctx, name, batch=None, steps=20, warmup=5, cpu_seconds=0.0, he
         return wrapper
 
     native_slots = []                                           # (slot, rows) of calls the library enqueued whole (csrc/call.hip)
-    if not args.no_kernel_events:
+    if args.full and not args.no_kernel_events:
         # calls with a resident loop are enqueued by ONE library call: the producer's launch is bracketed by an event pair the
         # library owns (ipsx_ips_call_run's timing_slot), read back after the timed region
         def hook(rows):
@@ -552,61 +604,68 @@ def measure(args, ctx, name, batch=None, steps=20, warmup=5, cpu_seconds=0.0, he
     import gc
     gc.collect()
     gc.freeze()
-    fence()
-    t0 = time.perf_counter()
-    per_step = []
-    prof = None
-    if os.environ.get("IPSX_BENCH_DEBUG") == "2":
-        import cProfile
-        prof = cProfile.Profile()
-        prof.enable()
-    for _ in range(steps):
-        h0 = time.perf_counter()
-        step()
-        per_step.append(time.perf_counter() - h0)
-    host_enqueue = time.perf_counter() - t0                     # the host's share: how long it took to ENQUEUE the steps
-    if prof is not None:
-        import pstats
-        prof.disable()
-        pstats.Stats(prof, stream=sys.stderr).sort_stats("tottime").print_stats(12)
-    if os.environ.get("IPSX_BENCH_DEBUG") and rank == 0:
-        print("host ms per step:", " ".join("%.2f" % (1e3 * v) for v in per_step), file=sys.stderr)
-    fence()
-    elapsed = time.perf_counter() - t0
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if share else dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
+    par = None
+    if args.full:                                               # the same K calls back to back, roofline, parity
+        fence()
+        t0 = time.perf_counter()
+        per_step = []
+        prof = None
+        if os.environ.get("IPSX_BENCH_DEBUG") == "2":
+            import cProfile
+            prof = cProfile.Profile()
+            prof.enable()
+        for _ in range(steps):
+            h0 = time.perf_counter()
+            step()
+            per_step.append(time.perf_counter() - h0)
+        host_enqueue = time.perf_counter() - t0                 # the host's share: how long it took to ENQUEUE the steps
+        if prof is not None:
+            import pstats
+            prof.disable()
+            pstats.Stats(prof, stream=sys.stderr).sort_stats("tottime").print_stats(12)
+        if os.environ.get("IPSX_BENCH_DEBUG") and rank == 0:
+            print("host ms per step:", " ".join("%.2f" % (1e3 * v) for v in per_step), file=sys.stderr)
+        fence()
+        elapsed = time.perf_counter() - t0
+        if world > 1:
+            t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if share else dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = float(t.item())
 
-    enc_ms = sum(a.elapsed_time(b) for a, b, _ in enc_events)
-    enc_patches = sum(n for _, _, n in enc_events)
-    n_launch = max(len(enc_events), 1)
-    if native_slots:                                            # the last <= 64 calls' producer launches (the slots are a ring)
-        import ctypes as C
-        ms = C.c_float()
-        last = native_slots[-64:]
-        for slot, rows in last:
-            hip._ck(hip.lib().ipsx_ips_call_elapsed(slot, C.byref(ms)), "ipsx_ips_call_elapsed")
-            enc_ms += ms.value
-            enc_patches += rows
-        n_launch = len(enc_events) + len(last)
-        streamed.append(2 if name in ("b1",) or conf.is_image else 1)
-    net.selection.timing_hook = None
-    achieved = enc_patches * FLOP_PER_PATCH[name] / (enc_ms * 1e-3) / 1e12 if enc_ms else 0.0       # (0: --no-kernel-events)
-    phases = ipsd.phase_ms(timings) if timings else None
-    # (more images than the fixture holds, --batch: its images are the first of the batch - the generator draws image by image)
-    par = parity(fixture, net.last_mem_idx[:B] if (world == 1 and batch > B) else net.last_mem_idx, images) if fixture else None
+        enc_ms = sum(a.elapsed_time(b) for a, b, _ in enc_events)
+        enc_patches = sum(n for _, _, n in enc_events)
+        n_launch = max(len(enc_events), 1)
+        if native_slots:                                        # the last <= 64 calls' producer launches (the slots are a ring)
+            import ctypes as C
+            ms = C.c_float()
+            last = native_slots[-64:]
+            for slot, rows in last:
+                hip._ck(hip.lib().ipsx_ips_call_elapsed(slot, C.byref(ms)), "ipsx_ips_call_elapsed")
+                enc_ms += ms.value
+                enc_patches += rows
+            n_launch = len(enc_events) + len(last)
+            streamed.append(2 if name in ("b1",) or conf.is_image else 1)
+        net.selection.timing_hook = None
+        achieved = enc_patches * FLOP_PER_PATCH[name] / (enc_ms * 1e-3) / 1e12 if enc_ms else 0.0       # (0: --no-kernel-events)
+        phases = ipsd.phase_ms(timings) if timings else None
+        # (more images than the fixture holds, --batch: its images are the first of the batch - the generator draws image by image)
+        par = parity(fixture, net.last_mem_idx[:B] if (world == 1 and batch > B) else net.last_mem_idx, images) if fixture else None
 
     # SURVEY d-1's protocol - the line's `value`: every one of the K calls bracketed by a fence (barrier + device sync) in
     # front and a device sync behind, the MAX over ranks of each call's time, the median over the K calls
     lat = []
-    for _ in range(steps):
+    for i in range(steps):
         fence()
         c0 = time.perf_counter()
-        step()
+        res = step()
         torch.cuda.synchronize()
         lat.append(1e3 * (time.perf_counter() - c0))
+        last = res if i == steps - 1 else None                  # (earlier calls' outputs are freed as they were)
+        del res
     fence()
+    if headline and rank == 0 and args.dump_outputs:            # to the host now: a later call may reuse the buffers
+        ctx.outputs = host_outputs(last[0], last[1], net.last_mem_idx)
+    del last
     if world > 1:
         t = torch.tensor(lat, dtype=torch.float64, device="cpu" if share else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -615,19 +674,20 @@ def measure(args, ctx, name, batch=None, steps=20, warmup=5, cpu_seconds=0.0, he
     med_ms = statistics.median(lat)
 
     if world > 1:                                               # every rank's verdict and phase times travel to rank 0
-        mine_rec = {"rank": rank, "patches_per_image": n_mine, "phases": phases,
+        mine_rec = {"rank": rank, "patches_per_image": n_mine, "phases": phases if args.full else None,
                     "indices_equal": par["indices_equal"] if par else None,
                     "device_index": dev.index, "device": torch.cuda.get_device_name(dev)}
         recs = [None] * world
         dist.all_gather_object(recs, mine_rec)
-    kernel_name = hip.encoder_kernel_name(net._plan)
-    if streamed and streamed[0] == 2:
-        kernel_name = "fused_trunk_stream_kernel (the fused trunk + logits, four / two patches per pull, patches published as they complete)"
-    elif streamed:
-        kernel_name = "projector_stream_kernel (row moments + Linear + BatchNorm + ReLU + logits per tile, rows published as they complete)"
-    traffic, traffic_note = pmc_traffic(name, kernel_name, enc_patches, n_launch)
-    if not (args.precision == "fp32" and not args.dedup_blank and not args.lazy and world == 1 and batch == (1 if name == "b1" else B)):
-        traffic = None
+    if args.full:
+        kernel_name = hip.encoder_kernel_name(net._plan)
+        if streamed and streamed[0] == 2:
+            kernel_name = "fused_trunk_stream_kernel (the fused trunk + logits, four / two patches per pull, patches published as they complete)"
+        elif streamed:
+            kernel_name = "projector_stream_kernel (row moments + Linear + BatchNorm + ReLU + logits per tile, rows published as they complete)"
+        traffic, traffic_note = pmc_traffic(name, kernel_name, enc_patches, n_launch)
+        if not (args.precision == "fp32" and not args.dedup_blank and not args.lazy and world == 1 and batch == (1 if name == "b1" else B)):
+            traffic = None
 
     out = None
     if rank == 0:
@@ -660,12 +720,24 @@ def measure(args, ctx, name, batch=None, steps=20, warmup=5, cpu_seconds=0.0, he
                        "loop_workgroups_per_image": hip.scan_workgroups_per_image(batch, conf.M, conf.I, net.transf.crs_attn.H,
                                                                                    conf.n_token)},
             "timing": "value = patches per call / median over the %d timed calls, each bracketed by barrier + device sync "
-                      "(SURVEY d-1; max over ranks per call); value_pipelined = the same %d calls enqueued back to back "
-                      "between two fences" % (steps, steps),
-            "value_pipelined": patches_per_step * steps / elapsed,
-            "ms_per_step_pipelined": 1e3 * elapsed / steps,
+                      "(SURVEY d-1; max over ranks per call)" % steps,
             "ms_per_call_median_synced": med_ms,
             "ms_per_call_min_synced": min(lat),
+        }
+        if n_extra:
+            out["config"]["workload"] += " (slide 0 = the fixture's, the other %d drawn on the device: relu(N(0,1)))" % n_extra
+        if world > 1:
+            paid, ideal = shard.rounds(0)
+            out["shard_plan"] = {"first_iteration_of_every_part": shard.its, "rank0_launch_patches": shard.launches(0),
+                                 "rounds_paid": paid, "rounds_ideal_one_launch": ideal, "model": shard.model.kind}
+            out["distributed"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
+                                  "devices": [r["device"] for r in recs], "one_gpu_per_rank": not share}
+        out["host"] = host_description()
+    if rank == 0 and args.full:
+        out["timing"] += "; value_pipelined = the same %d calls enqueued back to back between two fences" % steps
+        out.update({
+            "value_pipelined": patches_per_step * steps / elapsed,
+            "ms_per_step_pipelined": 1e3 * elapsed / steps,
             "host_enqueue_ms_per_step": 1e3 * host_enqueue / steps,
             "parity": par,
             "roofline": {"bound": "mfma", "achieved": achieved, "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
@@ -675,17 +747,10 @@ def measure(args, ctx, name, batch=None, steps=20, warmup=5, cpu_seconds=0.0, he
                          "kernel": kernel_name,
                          "launch_ms": enc_ms / n_launch,
                          "patches_per_launch": enc_patches / n_launch},
-        }
-        if n_extra:
-            out["config"]["workload"] += " (slide 0 = the fixture's, the other %d drawn on the device: relu(N(0,1)))" % n_extra
+        })
         if world > 1:
             out["parity_all_ranks"] = all(r["indices_equal"] for r in recs) if par else None
-            paid, ideal = shard.rounds(0)
-            out["shard_plan"] = {"first_iteration_of_every_part": shard.its, "rank0_launch_patches": shard.launches(0),
-                                 "rounds_paid": paid, "rounds_ideal_one_launch": ideal, "model": shard.model.kind}
             out["per_rank"] = recs
-            out["distributed"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
-                                  "devices": [r["device"] for r in recs], "one_gpu_per_rank": not share}
         # the WHOLE call priced against the work it executes: encoder FLOP + the logits' folded-query contraction
         # (2 * D * H * n_token per patch - the reference's per-iteration K projection is not executed here)
         call_flop = FLOP_PER_PATCH[name] + 2 * conf.D * conf.H * conf.n_token
@@ -718,7 +783,6 @@ def measure(args, ctx, name, batch=None, steps=20, warmup=5, cpu_seconds=0.0, he
             out["also_measured"]["bf16_f16"] = measure_precision(net, x, steps, "bf16", fixture, storage="f16")
         if world == 1 and cpu_seconds > 0:
             ctx.cpu_job = (conf, x_host, cpu_seconds)           # timed by main(), last and under a guard (see there)
-        out["host"] = host_description()
     del net, x, x_host
     torch.cuda.empty_cache()
     return out
@@ -815,12 +879,16 @@ def main():
     # reproduced on the next two boxes
     import faulthandler
     faulthandler.dump_traceback_later(args.watchdog, exit=True)
-    out = measure(args, ctx, name, batch=args.batch, steps=args.steps, warmup=args.warmup, cpu_seconds=args.cpu_seconds, headline=True)
+    out = measure(args, ctx, name, batch=args.batch, steps=args.steps, warmup=args.warmup,
+                  cpu_seconds=args.cpu_seconds if args.full else 0.0, headline=True)
     faulthandler.cancel_dump_traceback_later()
+    if ctx.outputs is not None:
+        dump_outputs(ctx.outputs, args.dump_outputs)
+        ctx.outputs = None
     plain = (args.config is None and args.batch is None and args.precision == "fp32"
              and args.storage == "f32" and not (args.dedup_blank or args.lazy or args.no_kernel_events))
-    default_run = world == 1 and plain
-    if world > 1 and plain and args.scaling == "strong":
+    default_run = world == 1 and plain and args.full
+    if world > 1 and plain and args.full and args.scaling == "strong":
         # the first point of the curve, measured in THIS run on THIS box: rank 0 alone, the same 16 x 2500 patches, the
         # single-GPU path (the other ranks wait at the barrier); then configs[2] sharded the same way
         faulthandler.dump_traceback_later(args.watchdog, exit=True)

@@ -367,8 +367,8 @@ def test_sharded_path_over_rccl_one_gpu_per_rank():
         assert out.stdout.count(" ok") == 3 * world and "MISMATCH" not in out.stdout
     # both ways a caller may start it: under the launcher, and bare (bench.py then starts its own ranks)
     for cmd in ([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                 "--master-port", "29559", os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
-                [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]):
+                 "--master-port", "29559", os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
+                [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"]):
         clean = {k: v for k, v in env.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
         out = subprocess.run(cmd, cwd=repo, env=clean, capture_output=True, text=True, timeout=900)
         assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
@@ -392,7 +392,7 @@ def test_bench_py_starts_its_own_ranks():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["IPSX_BENCH_SHARE_GPU"] = "1"
-    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"]
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"]
     out = subprocess.run(cmd, cwd=repo, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

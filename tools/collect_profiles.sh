@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 bash tools/bench_all.sh > "$OUT/bench_all.jsonl" 2> "$OUT/bench_all.err"
 for c in mnist cam native50 cam_native; do
   rm -rf /tmp/ks_$c
-  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$c -o ks -- python3 "$OLDPWD/bench.py" --config $c --steps 10 --warmup 3 --cpu-seconds 0 > "$OLDPWD/$OUT/bench_${c}_profiled.json" 2>/dev/null)
+  (cd "$TMPDIR" && rocprofv3 --kernel-trace --stats --output-format csv -d "$TMPDIR"/ks_$c -o ks -- python3 "$OLDPWD/bench.py" --full --config $c --steps 10 --warmup 3 --cpu-seconds 0 > "$OLDPWD/$OUT/bench_${c}_profiled.json" 2>/dev/null)
   cp $(find /tmp/ks_$c -name "*kernel_stats.csv" | head -1) "$OUT/${c}_kernel_stats.csv" 2>/dev/null
 done
 for ctr in FETCH_SIZE WRITE_SIZE; do            # the projector stream alone (inside ips() counter collection would serialise it away)
@@ -21,7 +21,7 @@ done
 for c in mnist cam native50 traffic; do
   for ctr in FETCH_SIZE WRITE_SIZE; do
     rm -rf /tmp/pmc_${c}_$ctr
-    (cd /tmp && rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d /tmp/pmc_${c}_$ctr -o pmc -- python3 "$OLDPWD/bench.py" --config $c --steps 3 --warmup 1 --cpu-seconds 0 > /dev/null 2>&1)
+    (cd "$TMPDIR" && rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d "$TMPDIR"/pmc_${c}_$ctr -o pmc -- python3 "$OLDPWD/bench.py" --full --config $c --steps 3 --warmup 1 --cpu-seconds 0 > /dev/null 2>&1)
   done
 done
 cp profiles/pmc_traffic.json "$OUT/pmc_traffic_before.json"
@@ -52,11 +52,11 @@ python tools/scan_beside.py > "$OUT/scan_beside.txt" 2>&1
 python -m pytest tests/test_bench_parity.py tests/test_seed_sweep.py -q -m gpu -s 2>&1 | grep -v "amdgpu.ids" > "$OUT/parity_rates.txt"
 # round 5: the default bench line as the driver runs it, kernel timelines of one-image / one-slide calls, the tie orders on the
 # shipped CAMELYON sizes, per-layer rates of the 50-px trunk, the compiler's resource table, the stream's launch-time spread, soak
-python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 for c in b1 cam cam_native; do bash tools/trace_step.sh $c 12 2>&1 | grep -v "amdgpu.ids" > "$OUT/${c}_timeline.txt"; done
 { for m in torch torch_all canonical; do
-    echo "IPSX_TIE_ORDER=$m python bench.py --config cam_native:"
-    IPSX_TIE_ORDER=$m python bench.py --config cam_native --cpu-seconds 0 2>/dev/null | python -c "
+    echo "IPSX_TIE_ORDER=$m python bench.py --full --config cam_native:"
+    IPSX_TIE_ORDER=$m python bench.py --full --config cam_native --cpu-seconds 0 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); p = d['parity']
 print('   %.2f M patches/s, %.3f ms per call; same SET as the reference every image: %s, slots_equal %.4f, selected_in_common %.4f' % (d['value'] / 1e6, d['ms_per_step'], p['selected_in_common'] == 1.0, p['slots_equal'], p['selected_in_common']))"

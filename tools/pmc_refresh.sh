@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 for c in "$@"; do
   for ctr in FETCH_SIZE WRITE_SIZE; do
     rm -rf /tmp/pmc_${c}_$ctr
-    (cd /tmp && rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d /tmp/pmc_${c}_$ctr -o pmc -- python3 "$OLDPWD/bench.py" --config $c --steps 3 --warmup 1 --cpu-seconds 0 > /dev/null 2>&1)
+    (cd "$TMPDIR" && rocprofv3 --kernel-trace --pmc $ctr --output-format csv -d "$TMPDIR"/pmc_${c}_$ctr -o pmc -- python3 "$OLDPWD/bench.py" --full --config $c --steps 3 --warmup 1 --cpu-seconds 0 > /dev/null 2>&1)
   done
   case $c in
     mnist) python tools/pmc_traffic.py /tmp/pmc_mnist_FETCH_SIZE /tmp/pmc_mnist_WRITE_SIZE mnist 8 fused_trunk.hip,fused_trunk_pair.h "fused_trunk_kernel|fused_trunk_pair_kernel" 10000 > "$OUT/pmc_mnist.json" 2> "$OUT/pmc_mnist.err";;

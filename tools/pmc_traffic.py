@@ -7,7 +7,7 @@ gfx950: FETCH_SIZE reports half of a wide coalesced read stream -> x2; WRITE_SIZ
                          [<dominant kernel substring(s), '|' separated> <patches per launch>]
 
 With a dominant kernel (the fused trunk: the encoder IS one kernel) the record holds bytes per launch of that kernel;
-otherwise bytes per step summed over every kernel of the run (calls = 1 + warmup + 2 * steps of bench.py: the first
+otherwise bytes per step summed over every kernel of the run (calls = 1 + warmup + 2 * steps of bench.py --full: the first
 call, the warm-up, the timed loop and the synchronised-latency loop).  The record carries a hash of the kernel sources;
 bench.py reports `traffic` only while they are unchanged.
 """
@@ -43,7 +43,7 @@ def main():
         h.update(open(os.path.join(REPO, "ips_amd", "csrc", src), "rb").read())
     rec = {"correction": "FETCH_SIZE x2 (gfx950 reports half of a wide coalesced read), WRITE_SIZE x1, KB = 1024 B",
            "source": sources, "source_sha16": h.hexdigest()[:16],
-           "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE -- python3 bench.py --config %s --steps 3 --warmup 1 --cpu-seconds 0" % workload}
+           "command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE|WRITE_SIZE -- python3 bench.py --full --config %s --steps 3 --warmup 1 --cpu-seconds 0" % workload}
     if dominant:
         names = dominant.split("|")                # e.g. the fused trunk's two exact kernels (whole rounds | remainder)
         fk = [v for k, v in fetch.items() if any(n in k for n in names)]
