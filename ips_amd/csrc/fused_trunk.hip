@@ -474,20 +474,110 @@ __device__ __forceinline__ void store_l2(float* lds, const f32x16 (&v)[2], int l
 }
 
 // STAMP = true is the diagnostic build: every wavefront records s_memtime at its phase boundaries
-// into a buffer of its own (never into an output); the product launches STAMP = false.
+// into a buffer of its own (never into an output), row blockIdx.x * WPB + wave (WPB: wavefronts per
+// workgroup - four unless a kernel declares its own); the product launches STAMP = false.
+constexpr int WPB = 4;
 #define IPSX_STAMP(k)                                                                      \
     do {                                                                                   \
         if (STAMP) {                                                                       \
             __builtin_amdgcn_sched_barrier(0);                                             \
             const unsigned long long t_ = __builtin_amdgcn_s_memtime();                    \
-            if (lane == 0) stamps[((size_t)blockIdx.x * 4 + wave) * 16 + (k)] = t_;        \
+            if (lane == 0) stamps[((size_t)blockIdx.x * WPB + wave) * 16 + (k)] = t_;      \
             __builtin_amdgcn_sched_barrier(0);                                             \
         }                                                                                  \
     } while (0)
 
-// four patches p_first .. p_first + 3 by the workgroup's four wavefronts (the body of fused_trunk_kernel); KEEP: the four
-// embeddings are also left in lds[0 .. 511] (behind a barrier) for a caller that goes on with them
-// (fused_trunk_stream_kernel: the logits)
+// one patch by one wavefront on its own slab S: the input load, the stem + pool and layer1, whose output is left in the
+// slab in the 8x8 stage's layout, behind a workgroup barrier (layer2 reads every slab) - the front of fused_trunk_kernel.
+// trunk_quad_tile below is the same with one more barrier after layer1's first block; that one orders nothing (the slab is
+// the wave's own until the end of layer1), and here it would make eight wavefronts wait for each other in mid-stage.
+template <bool STAMP, int WPB>
+__device__ __forceinline__ void trunk_front(const FusedArgs& a, long long pi, float* S, int lane, int wave,
+                                            unsigned long long* stamps) {
+    const int i = lane & 31;
+    IPSX_STAMP(0);
+
+    // ---- input patch -> slab as a zero-padded 38x38 image (coalesced 16 B global loads)
+    {
+        const float4* src = reinterpret_cast<const float4*>(a.patches + (size_t)pi * 1024);
+        float4 px[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) px[k] = src[k * 64 + lane];
+        for (int z = lane; z < (PW * PW + 3) / 4; z += 64) reinterpret_cast<float4*>(S)[z] = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int z = lane; z < PS1; z += 64) S[ZP1 * PS1 + z] = 0.0f;          // zero pixel row of the 8x8 stage
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int e = (k * 64 + lane) * 4, y = e >> 5, x = e & 31;       // 4 pixels of row y starting at x
+            float* d = S + (y + 3) * PW + x + 3;
+            d[0] = px[k].x; d[1] = px[k].y; d[2] = px[k].z; d[3] = px[k].w;
+        }
+    }
+    wave_fence();
+
+    // ---- stem + pool: result in registers = identity of block 1
+    f32x16 idn[2][2], acc[2][2];
+    IPSX_STAMP(1);
+    stem_pool<0>(a, S, idn, lane);
+    IPSX_STAMP(2);
+    wave_fence();                                                      // the input is dead
+    store_l1(S, idn, lane);
+    wave_fence();
+
+    // ---- layer1: two BasicBlocks at 8x8, wave = patch
+#pragma unroll 1
+    for (int blk = 0; blk < 2; ++blk) {
+        // conv1 -> BN -> ReLU, written over its own input (identity is in registers)
+        conv_l1(a.w[2 * blk], S, acc, lane);
+        IPSX_STAMP(3 + 4 * blk);
+        {
+            const float* al = a.al[2 * blk];
+            const float* sh = a.sh[2 * blk];
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+                const float A = al[nt * 32 + i], B = sh[nt * 32 + i];
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float v = __builtin_fmaf(acc[mt][nt][r], A, B);
+                        acc[mt][nt][r] = v > 0.0f ? v : 0.0f;
+                    }
+            }
+        }
+        wave_fence();
+        store_l1(S, acc, lane);
+        wave_fence();
+        IPSX_STAMP(4 + 4 * blk);
+        // conv2 -> BN -> += identity -> ReLU
+        conv_l1(a.w[2 * blk + 1], S, acc, lane);
+        IPSX_STAMP(5 + 4 * blk);
+        {
+            const float* al = a.al[2 * blk + 1];
+            const float* sh = a.sh[2 * blk + 1];
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+                const float A = al[nt * 32 + i], B = sh[nt * 32 + i];
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        float v = __builtin_fmaf(acc[mt][nt][r], A, B);
+                        v = v + idn[mt][nt][r];
+                        idn[mt][nt][r] = v > 0.0f ? v : 0.0f;
+                    }
+            }
+        }
+        wave_fence();
+        store_l1(S, idn, lane);
+        if (blk == 1) __syncthreads();                                    // layer2 reads every slab
+        else wave_fence();
+        IPSX_STAMP(6 + 4 * blk);
+    }
+}
+
+// four patches p_first .. p_first + 3 by the workgroup's four wavefronts (fused_trunk_stream_kernel and the pair kernel's
+// quads, fused_trunk_pair.h; fused_trunk_kernel runs eight, below); KEEP: the four embeddings are also left in
+// lds[0 .. 511] (behind a barrier) for a caller that goes on with them (fused_trunk_stream_kernel: the logits)
 template <bool STAMP, bool KEEP>
 __device__ __forceinline__ void trunk_quad_tile(const FusedArgs& a, long long p_first, long long n_valid, float* lds,
                                                 unsigned long long* stamps) {
@@ -640,13 +730,254 @@ __device__ __forceinline__ void trunk_quad_tile(const FusedArgs& a, long long p_
     IPSX_STAMP(15);
 }
 
+// ------------------------------------------------------------------ fused_trunk_kernel: eight patches per workgroup
+// One workgroup = 8 wavefronts = 8 patches, one workgroup per compute unit: still 2 wavefronts per SIMD of 256 registers
+// and 8 patches per unit per round, as two workgroups of four were.  Stem and layer1 are trunk_front (wave = patch, its
+// own slab).  The 4x4 stage is tiled by POSITION across the eight patches: row i of an M-tile = patch i >> 2, output
+// column i & 3 of ONE output row oy, so a tile is one output row of all eight patches; N = 4 tiles of 32 channels.
+// Wave w owns channels 32 (w & 3) .. 32 (w & 3) + 31 and two tiles: waves 0-3 the top row (oy 0) and oy 1, waves 4-7 the
+// bottom row (oy 3) and oy 2; waves w and w + 4 share a SIMD, so every SIMD issues the same MFMAs.
+// For the edge tile a whole row of taps reads the zero padding in all 32 rows - ky = 0 for the top row (both 3x3 shapes),
+// ky = 2 for the bottom row (the stride-1 convolutions) - and those taps' MFMAs and A-operand loads are left out: in code
+// (loops of their own over the taps), not by a branch.  That changes no bit (an accumulation chain that starts
+// at +0 is not changed by adding fma(0, w, .) for a finite w) and leaves 8,480 of the 9,104 MFMAs per patch.
+constexpr int SLAB8 = SLAB + 12;      // floats per slab here: 4432 = 16 (mod 64 banks), so the 4 patches x 4 columns of the 16
+                                      // lanes of one ds_read_b128 pass fall on 16 different 4-bank groups (SLAB: 1 - 4-way)
+
+template <int WIN, int PS, int ZP, int STRIDE, int KS>
+__device__ __forceinline__ L2Tap l8_tap(int tap, const float* S0, int oy0, int oy1, int ox) {
+    constexpr int PAD = KS / 2;
+    const int ky = tap / KS, kx = tap - ky * KS;
+    const int ix = ox * STRIDE + kx - PAD, iy0 = oy0 * STRIDE + ky - PAD, iy1 = oy1 * STRIDE + ky - PAD;
+    const bool okx = (unsigned)ix < (unsigned)WIN;
+    L2Tap d;
+    d.s0 = S0 + (okx && (unsigned)iy0 < (unsigned)WIN ? iy0 * WIN + ix : ZP) * PS;
+    d.s1 = S0 + (okx && (unsigned)iy1 < (unsigned)WIN ? iy1 * WIN + ix : ZP) * PS;
+    return d;
+}
+
+// SK0: tile 0 reads only padding at this tap - its loads and MFMAs are left out
+template <int C2, bool SK0>
+__device__ __forceinline__ void l8_load(L2Stage& st, const L2Tap& d) {
+    if (!SK0) {
+        st.a[0][0] = *reinterpret_cast<const float4*>(d.s0 + C2 * 16);
+        st.a[0][1] = *reinterpret_cast<const float4*>(d.s0 + C2 * 16 + 8);
+    }
+    st.a[1][0] = *reinterpret_cast<const float4*>(d.s1 + C2 * 16);
+    st.a[1][1] = *reinterpret_cast<const float4*>(d.s1 + C2 * 16 + 8);
+}
+
+template <bool SK0>
+__device__ __forceinline__ void l8_mma(const L2Stage& st, const float4 (&b)[2], f32x16 (&acc)[2]) {
+    if (!SK0) {
+        l2_mma(st, b, acc);
+        return;
+    }
+    const float a1[8] = {st.a[1][0].x, st.a[1][0].y, st.a[1][0].z, st.a[1][0].w,
+                         st.a[1][1].x, st.a[1][1].y, st.a[1][1].z, st.a[1][1].w};
+    const float bb[8] = {b[0].x, b[0].y, b[0].z, b[0].w, b[1].x, b[1].y, b[1].z, b[1].w};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[1] = MFMA(a1[j], bb[j], acc[1]);
+}
+
+// a stage's interleave of NM MFMAs with its NL LDS reads and 2 weight loads: L2_POST's spacing when both tiles are live;
+// with tile 0 out, 8 MFMAs (the stage's own) and 2 LDS reads (the next stage's tile 1 only)
+template <int NM, int NL>
+__device__ __forceinline__ void l8_post() {
+#if IPSX_SPREAD
+    if constexpr (NM == 16 && NL == 4) {
+        L2_POST();
+    } else if constexpr (NM == 16) {
+        SG_MFMA(3); SG_LDS(1); SG_MFMA(3); SG_VMEM(1); SG_MFMA(3); SG_LDS(1); SG_MFMA(3); SG_VMEM(1); SG_MFMA(4); SB();
+    } else if constexpr (NL == 4) {
+        SG_MFMA(1); SG_LDS(1); SG_MFMA(1); SG_LDS(1); SG_MFMA(1); SG_VMEM(1); SG_MFMA(1); SG_LDS(1); SG_MFMA(1); SG_LDS(1);
+        SG_MFMA(1); SG_VMEM(1); SG_MFMA(2); SB();
+    } else {
+        SG_MFMA(1); SG_LDS(1); SG_MFMA(2); SG_VMEM(1); SG_MFMA(1); SG_LDS(1); SG_MFMA(2); SG_VMEM(1); SG_MFMA(1); SB();
+    }
+#else
+    SB();
+#endif
+}
+
+// one tap of conv_l8: conv_l2's stages and weight ring; SK: tile 0 is out at this tap, SKN: at the next one
+template <int PER_TAP, int G2, bool SK, bool SKN>
+__device__ __forceinline__ void l8_tap_stages(const L2Tap& cur, const L2Tap& nxt, L2Stage& sa, L2Stage& sb, float4 (&b0)[2],
+                                              float4 (&b1)[2], float4 (&b2)[2], float4 (&b3)[2], const char* w, unsigned lo,
+                                              int g, f32x16 (&acc)[2]) {
+    constexpr int NM = SK ? 8 : 16, NL = SK ? 2 : 4, NLN = SKN ? 2 : 4;
+    if constexpr (PER_TAP == 8) {
+        l8_load<1, SK>(sb, cur); l2_loadb<G2>(b2, w, lo, g + 2); L2_PRE(); l8_mma<SK>(sa, b0, acc); l8_post<NM, NL>();
+        l8_load<2, SK>(sa, cur); l2_loadb<G2>(b3, w, lo, g + 3); L2_PRE(); l8_mma<SK>(sb, b1, acc); l8_post<NM, NL>();
+        l8_load<3, SK>(sb, cur); l2_loadb<G2>(b0, w, lo, g + 4); L2_PRE(); l8_mma<SK>(sa, b2, acc); l8_post<NM, NL>();
+        l8_load<4, SK>(sa, cur); l2_loadb<G2>(b1, w, lo, g + 5); L2_PRE(); l8_mma<SK>(sb, b3, acc); l8_post<NM, NL>();
+        l8_load<5, SK>(sb, cur); l2_loadb<G2>(b2, w, lo, g + 6); L2_PRE(); l8_mma<SK>(sa, b0, acc); l8_post<NM, NL>();
+        l8_load<6, SK>(sa, cur); l2_loadb<G2>(b3, w, lo, g + 7); L2_PRE(); l8_mma<SK>(sb, b1, acc); l8_post<NM, NL>();
+        l8_load<7, SK>(sb, cur); l2_loadb<G2>(b0, w, lo, g + 8); L2_PRE(); l8_mma<SK>(sa, b2, acc); l8_post<NM, NL>();
+        l8_load<0, SKN>(sa, nxt); l2_loadb<G2>(b1, w, lo, g + 9); L2_PRE(); l8_mma<SK>(sb, b3, acc); l8_post<NM, NLN>();
+    } else {
+        l8_load<1, SK>(sb, cur); l2_loadb<G2>(b2, w, lo, g + 2); L2_PRE(); l8_mma<SK>(sa, b0, acc); l8_post<NM, NL>();
+        l8_load<2, SK>(sa, cur); l2_loadb<G2>(b3, w, lo, g + 3); L2_PRE(); l8_mma<SK>(sb, b1, acc); l8_post<NM, NL>();
+        l8_load<3, SK>(sb, cur); l2_loadb<G2>(b0, w, lo, g + 4); L2_PRE(); l8_mma<SK>(sa, b2, acc); l8_post<NM, NL>();
+        l8_load<0, SKN>(sa, nxt); l2_loadb<G2>(b1, w, lo, g + 5); L2_PRE(); l8_mma<SK>(sb, b3, acc); l8_post<NM, NLN>();
+    }
+}
+
+// conv_l2 over the eight patches of fused_trunk_kernel: acc[0] = output row OY0 (0 top, 3 bottom), acc[1] = the row next to it
+// (1, 2), channels 32 nw .. 32 nw + 31.  The same k order and weight stream as conv_l2; the taps whose every row of tile 0 is
+// padding run without tile 0 - for the top row the first row of taps, for the bottom row the last, when it lies off the map.
+template <int CIN, int WIN, int PS, int ZP, int STRIDE, int KS, int OY0>
+__device__ __forceinline__ void conv_l8(const float* __restrict__ wp, const float* lds, f32x16 (&acc)[2], int lane, int nw) {
+    constexpr int KGS = KS * KS * CIN / 8, G2 = KGS / 2, PER_TAP = CIN / 16, TAPS = KS * KS, PAD = KS / 2;
+    static_assert(PER_TAP == 4 || PER_TAP == 8, "stage schedule is written for 64 or 128 input channels");
+    static_assert(OY0 == 0 || OY0 == 3, "tile 0 is the top or the bottom output row");
+    constexpr int OY1 = OY0 == 0 ? 1 : 2;
+    constexpr bool SKIP_FIRST = OY0 * STRIDE - PAD < 0;                    // tap row ky = 0 above the map for all of tile 0
+    constexpr bool SKIP_LAST = OY0 * STRIDE + KS - 1 - PAD >= WIN;         // tap row ky = KS - 1 below it
+    static_assert(!(SKIP_FIRST && SKIP_LAST), "one edge per tile");
+    const int i = lane & 31, half = lane >> 5;
+    const int ox = i & 3;
+    const float* S0 = lds + (i >> 2) * SLAB8 + 4 * half;
+    const char* w = reinterpret_cast<const char*>(wp) + (size_t)__builtin_amdgcn_readfirstlane(nw) * KGS * 1024;
+    const unsigned lo = lane * 16;
+    zero(acc[0]); zero(acc[1]);
+    L2Tap cur = l8_tap<WIN, PS, ZP, STRIDE, KS>(0, S0, OY0, OY1, ox);
+    L2Stage sa, sb;
+    float4 b0[2], b1[2], b2[2], b3[2];
+    l2_loadb<G2>(b0, w, lo, 0);
+    l2_loadb<G2>(b1, w, lo, 1);
+    l8_load<0, SKIP_FIRST>(sa, cur);
+    auto tap_at = [&](int t) { return l8_tap<WIN, PS, ZP, STRIDE, KS>(t < TAPS - 1 ? t + 1 : TAPS - 1, S0, OY0, OY1, ox); };
+    int tap = 0;
+    if constexpr (SKIP_FIRST) {
+#pragma unroll 1
+        for (; tap < KS - 1; ++tap) {
+            const L2Tap nxt = tap_at(tap);
+            l8_tap_stages<PER_TAP, G2, true, true>(cur, nxt, sa, sb, b0, b1, b2, b3, w, lo, tap * PER_TAP, acc);
+            cur = nxt;
+        }
+        const L2Tap nxt = tap_at(tap);
+        l8_tap_stages<PER_TAP, G2, true, false>(cur, nxt, sa, sb, b0, b1, b2, b3, w, lo, tap * PER_TAP, acc);
+        cur = nxt;
+        ++tap;
+    }
+    constexpr int END = SKIP_LAST ? TAPS - KS : TAPS;                       // the taps with both tiles: [tap, END)
+#pragma unroll 1
+    for (; tap < END - (SKIP_LAST ? 1 : 0); ++tap) {
+        const L2Tap nxt = tap_at(tap);
+        l8_tap_stages<PER_TAP, G2, false, false>(cur, nxt, sa, sb, b0, b1, b2, b3, w, lo, tap * PER_TAP, acc);
+        cur = nxt;
+    }
+    if constexpr (SKIP_LAST) {
+        {
+            const L2Tap nxt = tap_at(tap);
+            l8_tap_stages<PER_TAP, G2, false, true>(cur, nxt, sa, sb, b0, b1, b2, b3, w, lo, tap * PER_TAP, acc);
+            cur = nxt;
+            ++tap;
+        }
+#pragma unroll 1
+        for (; tap < TAPS; ++tap) {
+            const L2Tap nxt = tap_at(tap);
+            l8_tap_stages<PER_TAP, G2, true, true>(cur, nxt, sa, sb, b0, b1, b2, b3, w, lo, tap * PER_TAP, acc);
+            cur = nxt;
+        }
+    }
+}
+
+// the wave's edge-row or inner-row tiles, by a wave-uniform branch
+template <int CIN, int WIN, int PS, int ZP, int STRIDE, int KS>
+__device__ __forceinline__ void conv_l8_rows(const float* __restrict__ wp, const float* lds, f32x16 (&acc)[2], int lane, int nw,
+                                             bool bottom) {
+    if (bottom) conv_l8<CIN, WIN, PS, ZP, STRIDE, KS, 3>(wp, lds, acc, lane, nw);
+    else conv_l8<CIN, WIN, PS, ZP, STRIDE, KS, 0>(wp, lds, acc, lane, nw);
+}
+
+// write the wave's 2 tiles in the 4x4 stage's layout: C reg r is tile row (r & 3) + 4 half + 8 (r >> 2), i.e. patch
+// 2 (r >> 2) + half, column r & 3
+__device__ __forceinline__ void store_l8(float* lds, const f32x16 (&v)[2], int lane, int nw, int oy0, int oy1) {
+    const int i = lane & 31, half = lane >> 5;
+    const int n = 32 * nw + i;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int pl = 2 * (r >> 2) + half, pix = (mt ? oy1 : oy0) * 4 + (r & 3);
+            lds[pl * SLAB8 + pix * PS2 + n] = v[mt][r];
+        }
+}
+
 template <bool STAMP>
-__global__ __launch_bounds__(256, 2) void fused_trunk_kernel(FusedArgs a, unsigned long long* stamps) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];          // 4 slabs
-    const long long p_first = (long long)blockIdx.x * 4;
+__global__ __launch_bounds__(512, 1) void fused_trunk_kernel(FusedArgs a, unsigned long long* stamps) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];          // 8 slabs of SLAB8
+    constexpr int WPB = 8;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = lane & 31;
+    const long long p_first = (long long)blockIdx.x * 8;
     const long long n_valid = a.count ? (long long)*a.count : a.n;        // compacted launches read their length on device
     if (p_first >= n_valid) return;                                       // workgroup-uniform
-    trunk_quad_tile<STAMP, false>(a, p_first, n_valid, lds, stamps);
+    long long pi = p_first + wave;
+    if (pi >= n_valid) pi = n_valid - 1;                                  // tail: recompute a valid patch, store nothing
+    if (a.index) pi = a.index[pi];
+    trunk_front<STAMP, WPB>(a, pi, lds + wave * SLAB8, lane, wave, stamps);
+
+    // ---- layer2 block 0: conv3x3/2 (64->128) and the 1x1/2 projection read the 8x8 stage
+    const int nw = wave & 3;
+    const bool bottom = __builtin_amdgcn_readfirstlane(wave) >= 4;        // wave-uniform: tiles oy 3 + 2, else 0 + 1
+    const int oy0 = bottom ? 3 : 0, oy1 = bottom ? 2 : 1;
+    const int n2 = 32 * nw + i;
+    f32x16 t2[2], id2[2];
+    conv_l8_rows<64, 8, PS1, ZP1, 2, 3>(a.w[4], lds, t2, lane, nw, bottom);
+    conv_l8_rows<64, 8, PS1, ZP1, 2, 1>(a.w_down, lds, id2, lane, nw, bottom);
+    IPSX_STAMP(11);
+    {
+        const float A = a.al[4][n2], B = a.sh[4][n2], Ad = a.a_down[n2], Bd = a.s_down[n2];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float v = __builtin_fmaf(t2[mt][r], A, B);
+                t2[mt][r] = v > 0.0f ? v : 0.0f;
+                id2[mt][r] = __builtin_fmaf(id2[mt][r], Ad, Bd);
+            }
+    }
+    __syncthreads();
+    store_l8(lds, t2, lane, nw, oy0, oy1);
+    for (int z = lane; z < PS2; z += 64) lds[wave * SLAB8 + ZP2 * PS2 + z] = 0.0f;  // zero pixel row of the 4x4 stage
+    __syncthreads();
+    // conv2 of block 0, then block 1 (conv1, conv2), all 128->128 at 4x4
+#pragma unroll 1
+    for (int cv = 5; cv < 8; ++cv) {
+        conv_l8_rows<128, 4, PS2, ZP2, 1, 3>(a.w[cv], lds, t2, lane, nw, bottom);
+        const float A = a.al[cv][n2], B = a.sh[cv][n2];
+        const bool plain = (cv == 6);                                     // block 1 conv1: BN + ReLU only
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float v = __builtin_fmaf(t2[mt][r], A, B);
+                if (!plain) v = v + id2[mt][r];
+                v = v > 0.0f ? v : 0.0f;
+                t2[mt][r] = v;
+                if (!plain) id2[mt][r] = v;
+            }
+        __syncthreads();
+        store_l8(lds, t2, lane, nw, oy0, oy1);
+        __syncthreads();
+        IPSX_STAMP(7 + cv);
+    }
+
+    // ---- global average pool over the 16 pixels, sequential order
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int o = threadIdx.x + 512 * h;
+        const int pl = o >> 7, n = o & 127;
+        const float* s = lds + pl * SLAB8 + n;
+        float sum = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) sum = sum + s[k * PS2];
+        if (p_first + pl < n_valid) a.emb[(size_t)(p_first + pl) * 128 + n] = sum / 16.0f;
+    }
+    IPSX_STAMP(15);
 }
 
 #include "fused_trunk_split.h"
@@ -907,7 +1238,7 @@ static int fused_launch(const ipsx_trunk* t, const float* patches, int64_t n, fl
         else fused_trunk_bf16_kernel<false><<<grid, block, ldsx, s>>>(a, nullptr);
         return launched(x3 ? "fused_trunk_x3" : "fused_trunk_bf16");
     }
-    const size_t lds = (size_t)4 * SLAB * sizeof(float);
+    const size_t lds = (size_t)8 * SLAB8 * sizeof(float);              // 141,824 B: one workgroup of eight per CU
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_kernel<false>),
@@ -932,15 +1263,15 @@ static int fused_launch(const ipsx_trunk* t, const float* patches, int64_t n, fl
     const int64_t n_full = n - rest;
     a.n = n_full;
     if (stamps)
-        fused_trunk_kernel<true><<<dim3((unsigned)cdiv(n, 4)), dim3(256), lds, s>>>(a, stamps);
+        fused_trunk_kernel<true><<<dim3((unsigned)cdiv(n, 8)), dim3(512), lds, s>>>(a, stamps);
     else if (n_full)
-        fused_trunk_kernel<false><<<dim3((unsigned)cdiv(n_full, 4)), dim3(256), lds, s>>>(a, nullptr);
+        fused_trunk_kernel<false><<<dim3((unsigned)cdiv(n_full, 8)), dim3(512), lds, s>>>(a, nullptr);
     if (rest) {
         a.n = rest;
         if (index) a.index = index + n_full;
         else a.patches = patches + (size_t)n_full * 1024;
         a.emb = emb + (size_t)n_full * 128;
-        fused_trunk_pair_kernel<<<dim3((unsigned)cdiv(rest, 2)), dim3(256), lds / 2, s>>>(a);
+        fused_trunk_pair_kernel<<<dim3((unsigned)cdiv(rest, 2)), dim3(256), (size_t)2 * SLAB * sizeof(float), s>>>(a);
     }
     return launched("fused_trunk");
 }

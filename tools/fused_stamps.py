@@ -51,6 +51,14 @@ if prec == "fp32x3":      # bf16 MFMAs of 32 cycles, 6 per 8 fp32 MFMAs of 64 ->
     mfma = [(8 * 2 * 4 * 6 / 2) if k == 1 else m * 6 / 16 for k, m in enumerate(mfma)]
 if prec == "bf16":        # one bf16 MFMA of 32 cycles per 8 fp32 MFMAs of 64: x 1/16 (stem: 4 K-steps x 2 n-tiles x 8 tiles)
     mfma = [(8 * 2 * 4 / 2) if k == 1 else m / 16 for k, m in enumerate(mfma)]
+groups = None
+if prec == "fp32":
+    # fused_trunk_kernel: eight wavefronts per workgroup (row = 8 * workgroup + wave).  In the 4x4 stage a wave's MFMAs are
+    # those of its two output rows for 32 channels, less the padded taps of its edge row: waves 0-3 (rows 0 + 1) 544 in
+    # l2.0.c1+down and 960 per 128->128 convolution, waves 4-7 (rows 3 + 2) 640 and 960; the table holds their mean
+    wave = np.arange(len(s)) % 8
+    groups = [("waves 0-3", wave < 4, [544, 960, 960, 960]), ("waves 4-7", wave >= 4, [640, 960, 960, 960])]
+    mfma = mfma[:10] + [592, 960, 960, 960, 0]
 # stamps: 0 start,1 loaded,2 stem,3 c1,4 epi,5 c2,6 epi(+barrier),7..10 block 1,11 l2.0 c1+down,12 cv5,13 cv6,14 cv7,15 end
 life = s[:, 15] - s[:, 0]
 print("waves %d  median life %d cycles  (matrix-pipe cycles alone: %d)" % (len(s), np.median(life), sum(mfma) * 64))
@@ -59,6 +67,10 @@ for k in range(15):
     print("%-14s median %8d  p10 %8d  p90 %8d   mfma-alone %7d  ratio %.2f" % (
         names[k], np.median(d), np.percentile(d, 10), np.percentile(d, 90), mfma[k] * 64,
         (np.median(d) / (mfma[k] * 64)) if mfma[k] else float("nan")))
+for label, rows, counts in groups or []:
+    for k, m in zip(range(10, 14), counts):
+        d = s[rows, k + 1] - s[rows, k]
+        print("%-14s %s median %8d   mfma-alone %7d  ratio %.2f" % (names[k], label, np.median(d), m * 64, np.median(d) / (m * 64)))
 span = s[:, 15].max() - s[:, 0].min()
 print("kernel span %d cycles; sum of MFMA cycles per SIMD %d -> pipe utilisation %.3f" % (
     span, int(len(s) * sum(mfma) * 64 / 1024), len(s) * sum(mfma) * 64 / 1024 / span))
