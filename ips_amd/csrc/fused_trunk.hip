@@ -29,6 +29,7 @@
 //             exactly the register layout of the 8x8 stage's MFMA C tile - the first block's identity.
 //   layer1    wave = patch: 64 px x 64 ch = 2x2 accumulators, no workgroup barriers (the slab is
 //             wave-private).  conv1 output overwrites the slab in place (the identity lives in registers).
+//             fused_trunk_kernel (eight patches) tiles layer1 by position instead, as its 4x4 stage: conv_p1.
 //   layer2    the 4 waves share the 4 patches: M = 4 x 16 px = 2 tiles, wave w owns output
 //             channels 32w..32w+31, so each weight is fetched once per workgroup.
 //   avgpool   sequential 16-term sums from the slab (the oracle's order).
@@ -487,14 +488,11 @@ constexpr int WPB = 4;
         }                                                                                  \
     } while (0)
 
-// one patch by one wavefront on its own slab S: the input load, the stem + pool and layer1, whose output is left in the
-// slab in the 8x8 stage's layout, behind a workgroup barrier (layer2 reads every slab) - the front of fused_trunk_kernel.
-// trunk_quad_tile below is the same with one more barrier after layer1's first block; that one orders nothing (the slab is
-// the wave's own until the end of layer1), and here it would make eight wavefronts wait for each other in mid-stage.
+// one patch by one wavefront on its own slab S: the input load and the stem + pool, whose output is left in the slab in
+// the 8x8 stage's layout, behind a workgroup barrier (layer1 reads every slab) - the front of fused_trunk_kernel
 template <bool STAMP, int WPB>
 __device__ __forceinline__ void trunk_front(const FusedArgs& a, long long pi, float* S, int lane, int wave,
                                             unsigned long long* stamps) {
-    const int i = lane & 31;
     IPSX_STAMP(0);
 
     // ---- input patch -> slab as a zero-padded 38x38 image (coalesced 16 B global loads)
@@ -514,65 +512,14 @@ __device__ __forceinline__ void trunk_front(const FusedArgs& a, long long pi, fl
     }
     wave_fence();
 
-    // ---- stem + pool: result in registers = identity of block 1
-    f32x16 idn[2][2], acc[2][2];
+    // ---- stem + pool -> the slab, the input of layer1
+    f32x16 idn[2][2];
     IPSX_STAMP(1);
     stem_pool<0>(a, S, idn, lane);
     IPSX_STAMP(2);
     wave_fence();                                                      // the input is dead
     store_l1(S, idn, lane);
-    wave_fence();
-
-    // ---- layer1: two BasicBlocks at 8x8, wave = patch
-#pragma unroll 1
-    for (int blk = 0; blk < 2; ++blk) {
-        // conv1 -> BN -> ReLU, written over its own input (identity is in registers)
-        conv_l1(a.w[2 * blk], S, acc, lane);
-        IPSX_STAMP(3 + 4 * blk);
-        {
-            const float* al = a.al[2 * blk];
-            const float* sh = a.sh[2 * blk];
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                const float A = al[nt * 32 + i], B = sh[nt * 32 + i];
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const float v = __builtin_fmaf(acc[mt][nt][r], A, B);
-                        acc[mt][nt][r] = v > 0.0f ? v : 0.0f;
-                    }
-            }
-        }
-        wave_fence();
-        store_l1(S, acc, lane);
-        wave_fence();
-        IPSX_STAMP(4 + 4 * blk);
-        // conv2 -> BN -> += identity -> ReLU
-        conv_l1(a.w[2 * blk + 1], S, acc, lane);
-        IPSX_STAMP(5 + 4 * blk);
-        {
-            const float* al = a.al[2 * blk + 1];
-            const float* sh = a.sh[2 * blk + 1];
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                const float A = al[nt * 32 + i], B = sh[nt * 32 + i];
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        float v = __builtin_fmaf(acc[mt][nt][r], A, B);
-                        v = v + idn[mt][nt][r];
-                        idn[mt][nt][r] = v > 0.0f ? v : 0.0f;
-                    }
-            }
-        }
-        wave_fence();
-        store_l1(S, idn, lane);
-        if (blk == 1) __syncthreads();                                    // layer2 reads every slab
-        else wave_fence();
-        IPSX_STAMP(6 + 4 * blk);
-    }
+    __syncthreads();                                                   // layer1 reads every slab
 }
 
 // four patches p_first .. p_first + 3 by the workgroup's four wavefronts (fused_trunk_stream_kernel and the pair kernel's
@@ -732,8 +679,8 @@ __device__ __forceinline__ void trunk_quad_tile(const FusedArgs& a, long long p_
 
 // ------------------------------------------------------------------ fused_trunk_kernel: eight patches per workgroup
 // One workgroup = 8 wavefronts = 8 patches, one workgroup per compute unit: still 2 wavefronts per SIMD of 256 registers
-// and 8 patches per unit per round, as two workgroups of four were.  Stem and layer1 are trunk_front (wave = patch, its
-// own slab).  The 4x4 stage is tiled by POSITION across the eight patches: row i of an M-tile = patch i >> 2, output
+// and 8 patches per unit per round, as two workgroups of four were.  The stem is trunk_front (wave = patch, its own
+// slab); layer1 is tiled by position (conv_p1, below).  The 4x4 stage is tiled by POSITION across the eight patches: row i of an M-tile = patch i >> 2, output
 // column i & 3 of ONE output row oy, so a tile is one output row of all eight patches; N = 4 tiles of 32 channels.
 // Wave w owns channels 32 (w & 3) .. 32 (w & 3) + 31 and two tiles: waves 0-3 the top row (oy 0) and oy 1, waves 4-7 the
 // bottom row (oy 3) and oy 2; waves w and w + 4 share a SIMD, so every SIMD issues the same MFMAs.
@@ -906,6 +853,269 @@ __device__ __forceinline__ void store_l8(float* lds, const f32x16 (&v)[2], int l
         }
 }
 
+// ------------------------------------------------------------------ fused_trunk_kernel's layer1: tiled by position
+// The 8x8 stage over the eight patches, tiled as the 4x4 stage is: row m of an M-tile = patch m >> 2, position slot m & 3,
+// so a tile is four pixel positions of all eight patches.  The 64 positions make 16 tiles (slot s -> pixel
+// pix0 + (s & 1) s1 + (s >> 1) s2):
+//   T0 T1   row 0, columns 0-3 / 4-7          leave out ky = 0 (taps 0 1 2): those rows read only the zero padding
+//   B0 B1   row 7, columns 0-3 / 4-7          leave out ky = 2 (taps 6 7 8)
+//   L       column 0, rows 1-4                leave out kx = 0 (taps 0 3 6)
+//   R       column 7, rows 1-4                leave out kx = 2 (taps 2 5 8)
+//   M50 M54 M60 M64   rows 5 and 6, columns 0-3 / 4-7     every tap (one column of lanes reads the padding at kx 0 or 2)
+//   I1-I4   rows 1-4, columns 1-4;  J1 J2  rows 1-2 / 3-4, columns 5-6   interior: no tap leaves the map
+// Wave w computes the 32 channels of N-tile w >> 2 for the four M-tiles of set (w + 2 (w >> 2)) & 3: T {T0 T1 I1 I2},
+// B {B0 B1 I3 I4}, L {L M50 M54 J1}, R {R M60 M64 J2}.  Waves w and w + 4 share a SIMD and hold T + L, B + R, L + T or
+// R + B: 960 + 1,056 MFMAs per convolution on every SIMD, 1,008 per patch where wave = patch needed 1,152.  The taps a
+// tile leaves out are left out in code, by a row loop whose bodies know the live tiles of each tap at compile time; that
+// changes no bit.  LDS banks (ds_read_b128 takes 16 lanes = 4 patches x 4 slots at a time, and the patches
+// lie 16 banks apart): the row tiles' four columns fall on four different 4-bank groups, J1 J2 two ways, L and R
+// (one column) four ways - one of the wave's four operand reads per stage, prefetched a stage ahead.
+enum : int { P1_ALL, P1_KY0, P1_KY2, P1_KX0, P1_KX2 };
+struct P1Tile {
+    int pix0, s1, s2, skip;
+    bool x0, x7;          // some lanes sit in column 0 / 7 and read the zero row at kx = 0 / 2
+};
+
+__host__ __device__ constexpr P1Tile p1_tile(int set, int t) {
+    constexpr P1Tile tiles[4][4] = {
+        {{0, 1, 2, P1_KY0, true, false}, {4, 1, 2, P1_KY0, false, true}, {9, 1, 2, P1_ALL, false, false}, {17, 1, 2, P1_ALL, false, false}},
+        {{56, 1, 2, P1_KY2, true, false}, {60, 1, 2, P1_KY2, false, true}, {25, 1, 2, P1_ALL, false, false}, {33, 1, 2, P1_ALL, false, false}},
+        {{8, 8, 16, P1_KX0, true, false}, {40, 1, 2, P1_ALL, true, false}, {44, 1, 2, P1_ALL, false, true}, {13, 1, 8, P1_ALL, false, false}},
+        {{15, 8, 16, P1_KX2, false, true}, {48, 1, 2, P1_ALL, true, false}, {52, 1, 2, P1_ALL, false, true}, {29, 1, 8, P1_ALL, false, false}}};
+    return tiles[set][t];
+}
+
+__host__ __device__ constexpr int p1_pix(int set, int t, int slot) {
+    return p1_tile(set, t).pix0 + (slot & 1) * p1_tile(set, t).s1 + (slot >> 1) * p1_tile(set, t).s2;
+}
+
+// the set's live tiles at column kx of a tap row (bit t); EDGE: this is the row the set's T or B tiles leave out
+__host__ __device__ constexpr int p1_live(int set, bool edge, int kx) {
+    int m = 0;
+    for (int t = 0; t < 4; ++t) {
+        const int k = p1_tile(set, t).skip;
+        const bool out = ((k == P1_KY0 || k == P1_KY2) && edge) || (k == P1_KX0 && kx == 0) || (k == P1_KX2 && kx == 2);
+        if (!out) m |= 1 << t;
+    }
+    return m;
+}
+
+__host__ __device__ constexpr int p1_count(int m) { return (m & 1) + (m >> 1 & 1) + (m >> 2 & 1) + (m >> 3 & 1); }
+
+// the operand pointers of one tap row ky: p = pixel (y + ky - 1, x) for tiles with a column-0 lane, else (y + ky - 1, x - 1),
+// so that the other taps of the row are p plus an immediate; e = the one tap whose column leaves the map for some lanes
+// (kx = 0 for column-0 tiles, 2 for column-7 tiles), the zero row for those lanes
+struct P1Row {
+    const float* p[4];
+    const float* e[4];
+};
+
+template <int SET>
+__device__ __forceinline__ P1Row p1_row(const float* const (&P)[4], const float* Z, const bool (&ok)[4], int ky) {
+    P1Row r;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const P1Tile d = p1_tile(SET, t);
+        const float* c = P[t] + (ky - 1) * 8 * PS1;
+        r.p[t] = d.x0 ? c : c - PS1;
+        r.e[t] = d.x0 ? (ok[t] ? c - PS1 : Z) : (d.x7 ? (ok[t] ? c + PS1 : Z) : c);
+    }
+    return r;
+}
+
+template <int SET>
+__device__ __forceinline__ const float* p1_src(const P1Row& r, int t, int kx) {
+    const P1Tile d = p1_tile(SET, t);
+    if (d.x0) return kx == 0 ? r.e[t] : r.p[t] + (kx - 1) * PS1;
+    if (d.x7 && kx == 2) return r.e[t];
+    return r.p[t] + kx * PS1;
+}
+
+struct P1State {
+    f32x16 acc[4];
+    float4 a[2][4];     // [stage & 1][tile]: 4 consecutive k of this lane's half
+    float4 b[4];        // weight ring: slot = stage & 3, refilled 2 stages ahead
+};
+
+// a stage's interleave of NM MFMAs with its NL LDS reads and 1 weight load: the loads 2 MFMAs apart (1 when there are
+// more loads than that leaves room for), the weight load in the middle, 4 or more MFMAs at the end
+template <int G, int K, int NL>
+__device__ __forceinline__ void p1_groups() {
+#if IPSX_SPREAD
+    if constexpr (K <= NL) {
+        SG_MFMA(G);
+        if constexpr (K == NL / 2) SG_VMEM(1);
+        else SG_LDS(1);
+        p1_groups<G, K + 1, NL>();
+    }
+#endif
+}
+
+template <int NM, int NL>
+__device__ __forceinline__ void p1_post() {
+#if IPSX_SPREAD
+    constexpr int G = (NM - 4) / (NL + 1) > 0 ? (NM - 4) / (NL + 1) : 1;
+    p1_groups<G, 0, NL>();
+    SG_MFMA(NM - G * (NL + 1));
+#endif
+    SB();
+}
+
+// stage ST (= 8 kx + k-group) of tap row ky: prefetch the next stage's operands of its live tiles (the next row's first
+// when ST = 23) and the weights two stages on, then this stage's MFMAs - per tile the contract's k order, as conv_l1
+template <int SET, bool EDGE, bool EDGEN, int ST>
+__device__ __forceinline__ void p1_stages(P1State& s, const P1Row& cur, const P1Row& nxt, const char* w, unsigned lo, int g0) {
+    if constexpr (ST < 24) {
+        constexpr int KX = ST >> 3, LIVE = p1_live(SET, EDGE, KX);
+        constexpr bool LAST = ST == 23;
+        constexpr int NKX = LAST ? 0 : (ST + 1) >> 3, NCG = LAST ? 0 : (ST + 1) & 7;
+        constexpr int LIVEN = LAST ? p1_live(SET, EDGEN, 0) : p1_live(SET, EDGE, NKX);
+        constexpr int NB = (ST + 1) & 1;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            if (LIVEN >> t & 1)
+                s.a[NB][t] = *reinterpret_cast<const float4*>(p1_src<SET>(LAST ? nxt : cur, t, NKX) + NCG * 8);
+        {
+            int g = g0 + ST + 2;
+            g = g < 72 ? g : 71;
+            s.b[(ST + 2) & 3] = *reinterpret_cast<const float4*>(w + (size_t)g * 1024 + lo);
+        }
+        L1_PRE();
+        {
+            const float4& bq = s.b[ST & 3];
+            const float bb[4] = {bq.x, bq.y, bq.z, bq.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    if (LIVE >> t & 1) {
+                        const float4& aq = s.a[ST & 1][t];
+                        const float av[4] = {aq.x, aq.y, aq.z, aq.w};
+                        s.acc[t] = MFMA(av[j], bb[j], s.acc[t]);
+                    }
+        }
+        p1_post<4 * p1_count(LIVE), p1_count(LIVEN)>();
+        p1_stages<SET, EDGE, EDGEN, ST + 1>(s, cur, nxt, w, lo, g0);
+    }
+}
+
+// one tap row: its three taps x 8 k-groups; leaves cur = the next row's pointers (ky + 1, clamped: the last row's tail
+// prefetch re-reads its own first operands, as conv_l1's does)
+template <int SET, bool EDGE, bool EDGEN>
+__device__ __forceinline__ void p1_tap_row(P1State& s, P1Row& cur, const float* const (&P)[4], const float* Z,
+                                           const bool (&ok)[4], const char* w, unsigned lo, int ky) {
+    const P1Row nxt = p1_row<SET>(P, Z, ok, ky < 2 ? ky + 1 : 2);
+    p1_stages<SET, EDGE, EDGEN, 0>(s, cur, nxt, w, lo, ky * 24);
+    cur = nxt;
+}
+
+// conv3x3 (64 -> 64, stride 1, pad 1) of layer1 over the workgroup's eight slabs: acc[t] = tile t of the wave's set, channels
+// 32 nt .. 32 nt + 31.  Same k order and weight stream as conv_l1 (packed: 2 n-tiles x 72 k-groups of 1 KiB).
+template <int SET>
+__device__ __forceinline__ void conv_p1(const float* __restrict__ wp, const float* lds, f32x16 (&acc)[4], int lane, int nt) {
+    int i = lane & 31;
+    asm volatile("" : "+v"(i));            // the addresses below are computed per call, not kept live across layer1
+    const int half = lane >> 5, slot = i & 3;
+    const float* S0 = lds + (i >> 2) * SLAB8 + 4 * half;
+    const float* Z = S0 + ZP1 * PS1;
+    const float* P[4];
+    bool ok[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const P1Tile d = p1_tile(SET, t);
+        const int pix = d.pix0 + (slot & 1) * d.s1 + (slot >> 1) * d.s2;
+        P[t] = S0 + pix * PS1;
+        ok[t] = d.x0 ? (pix & 7) != 0 : (pix & 7) != 7;
+    }
+    const char* w = reinterpret_cast<const char*>(wp) + (size_t)__builtin_amdgcn_readfirstlane(nt) * 72 * 1024;
+    const unsigned lo = lane * 16;
+    P1State s;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) zero(s.acc[t]);
+    s.b[0] = *reinterpret_cast<const float4*>(w + lo);
+    s.b[1] = *reinterpret_cast<const float4*>(w + 1024 + lo);
+    P1Row cur = p1_row<SET>(P, Z, ok, 0);
+    constexpr int LIVE0 = p1_live(SET, SET == 0, 0);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        if (LIVE0 >> t & 1) s.a[0][t] = *reinterpret_cast<const float4*>(p1_src<SET>(cur, t, 0));
+    if constexpr (SET == 0) {                                               // T: row ky = 0 without T0 T1
+        p1_tap_row<SET, true, false>(s, cur, P, Z, ok, w, lo, 0);
+#pragma unroll 1
+        for (int ky = 1; ky < 3; ++ky) p1_tap_row<SET, false, false>(s, cur, P, Z, ok, w, lo, ky);
+    } else if constexpr (SET == 1) {                                        // B: row ky = 2 without B0 B1
+        p1_tap_row<SET, false, false>(s, cur, P, Z, ok, w, lo, 0);
+        p1_tap_row<SET, false, true>(s, cur, P, Z, ok, w, lo, 1);
+        p1_tap_row<SET, true, true>(s, cur, P, Z, ok, w, lo, 2);
+    } else {                                                                // L, R: a column of taps out in every row
+#pragma unroll 1
+        for (int ky = 0; ky < 3; ++ky) p1_tap_row<SET, false, false>(s, cur, P, Z, ok, w, lo, ky);
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[t] = s.acc[t];
+}
+
+// the wave's four tiles <-> the slabs' [pix][c] layout: C reg r is tile row (r & 3) + 4 half + 8 (r >> 2), i.e. patch
+// 2 (r >> 2) + half, slot r & 3
+template <int SET>
+__device__ __forceinline__ void store_p1(float* lds, const f32x16 (&v)[4], int lane, int nt) {
+    int o = (lane >> 5) * SLAB8 + 32 * nt + (lane & 31);
+    asm volatile("" : "+v"(o));            // as in conv_p1: addresses per call
+    float* base = lds + o;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) base[2 * (r >> 2) * SLAB8 + p1_pix(SET, t, r & 3) * PS1] = v[t][r];
+}
+
+template <int SET>
+__device__ __forceinline__ void load_p1(const float* lds, f32x16 (&v)[4], int lane, int nt) {
+    const float* base = lds + (lane >> 5) * SLAB8 + 32 * nt + (lane & 31);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) v[t][r] = base[2 * (r >> 2) * SLAB8 + p1_pix(SET, t, r & 3) * PS1];
+}
+
+// layer1 of fused_trunk_kernel (two BasicBlocks at 8x8) for the wave's set; the slabs hold the stem's output on entry and
+// layer1's on return.  Every convolution reads all eight slabs, so its epilogue writes in place between two barriers.
+template <bool STAMP, int SET>
+__device__ __forceinline__ void layer1_p1(const FusedArgs& a, float* lds, int lane, int wave, unsigned long long* stamps) {
+    constexpr int WPB = 8;                                                  // stamp rows: fused_trunk_kernel's eight waves
+    const int nt = wave >> 2, n = 32 * nt + (lane & 31);
+    f32x16 idn[4], acc[4];
+    load_p1<SET>(lds, idn, lane, nt);                                      // identity of block 1
+#pragma unroll 1
+    for (int cv = 0; cv < 4; ++cv) {
+        conv_p1<SET>(a.w[cv], lds, acc, lane, nt);
+        IPSX_STAMP(3 + 2 * cv);
+        const float A = a.al[cv][n], B = a.sh[cv][n];
+        if ((cv & 1) == 0) {                                                // conv1 -> BN -> ReLU
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float v = __builtin_fmaf(acc[t][r], A, B);
+                    acc[t][r] = v > 0.0f ? v : 0.0f;
+                }
+        } else {                                                            // conv2 -> BN -> += identity -> ReLU
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    float v = __builtin_fmaf(acc[t][r], A, B);
+                    v = v + idn[t][r];
+                    idn[t][r] = v > 0.0f ? v : 0.0f;
+                }
+        }
+        __syncthreads();                                                    // every wave has read this convolution's input
+        if (cv & 1) store_p1<SET>(lds, idn, lane, nt);
+        else store_p1<SET>(lds, acc, lane, nt);
+        __syncthreads();
+        IPSX_STAMP(4 + 2 * cv);
+    }
+}
+
 template <bool STAMP>
 __global__ __launch_bounds__(512, 1) void fused_trunk_kernel(FusedArgs a, unsigned long long* stamps) {
     extern __shared__ __attribute__((aligned(16))) float lds[];          // 8 slabs of SLAB8
@@ -919,6 +1129,12 @@ __global__ __launch_bounds__(512, 1) void fused_trunk_kernel(FusedArgs a, unsign
     if (pi >= n_valid) pi = n_valid - 1;                                  // tail: recompute a valid patch, store nothing
     if (a.index) pi = a.index[pi];
     trunk_front<STAMP, WPB>(a, pi, lds + wave * SLAB8, lane, wave, stamps);
+    switch (__builtin_amdgcn_readfirstlane((wave + 2 * (wave >> 2)) & 3)) {  // the wave's layer1 tile set, see conv_p1
+        case 0: layer1_p1<STAMP, 0>(a, lds, lane, wave, stamps); break;
+        case 1: layer1_p1<STAMP, 1>(a, lds, lane, wave, stamps); break;
+        case 2: layer1_p1<STAMP, 2>(a, lds, lane, wave, stamps); break;
+        default: layer1_p1<STAMP, 3>(a, lds, lane, wave, stamps); break;
+    }
 
     // ---- layer2 block 0: conv3x3/2 (64->128) and the 1x1/2 projection read the 8x8 stage
     const int nw = wave & 3;
