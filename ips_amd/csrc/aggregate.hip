@@ -212,6 +212,8 @@ __global__ __launch_bounds__(64) void head_kernel(const float* __restrict__ emb,
 int conv_nhwc_impl(const ipsx_conv* cv, const float* x, const float* residual, const float* row_stats, float* y,
                    int64_t n, int h, int w, int relu, void* stream, int* ready = nullptr, int ready_value = 0);
 
+constexpr size_t kAggLdsLimit = 160 * 1024;
+
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct AggLayout {
@@ -298,6 +300,11 @@ IPSX_API int ipsx_aggregate_packed(const ipsx_transf* t, const float* vq_packed,
     IPSX_REQUIRE(t && x && out && b > 0 && m > 0, "aggregate: bad arguments");
     IPSX_REQUIRE(t->q && t->wq && t->wk && t->wv && t->fc && t->ln1_g && t->ln1_b && t->w1 && t->b1 && t->w2 &&
                      t->b2 && t->ln2_g && t->ln2_b, "aggregate: missing weights");
+    // (refused before the first launch: the V projection's operand load needs D % 32 == 0, the tail keeps a workgroup's
+    // token state in LDS)
+    IPSX_REQUIRE(t->d % 32 == 0, "aggregate: D = %d is not a multiple of 32", t->d);
+    const size_t lds = ((size_t)t->n_token * (t->h * t->dv + 2 * t->d + t->d_inner)) * sizeof(float);
+    IPSX_REQUIRE(lds <= kAggLdsLimit, "aggregate: token state of %zu B exceeds the %zu B (160 KiB) of LDS", lds, kAggLdsLimit);
     const AggLayout L = agg_layout(t, b, m);
     if (!workspace || workspace_bytes < L.total)
         return fail(IPSX_EWORKSPACE, "aggregate: workspace %zu B < %zu B", workspace_bytes, L.total);
@@ -337,8 +344,6 @@ IPSX_API int ipsx_aggregate_packed(const ipsx_transf* t, const float* vq_packed,
 
     TailArgs ta;
     ta.ctx = ctx; ta.t = *t; ta.out = out;
-    const size_t lds = ((size_t)t->n_token * (hdv + 2 * t->d + t->d_inner)) * sizeof(float);
-    IPSX_REQUIRE(lds <= 160 * 1024, "aggregate: token state (%zu B) exceeds LDS", lds);
     if (lds > 64 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(transf_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     transf_tail_kernel<<<dim3((unsigned)b), dim3(256), lds, s>>>(ta);

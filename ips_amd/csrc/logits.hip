@@ -344,13 +344,15 @@ IPSX_API int ipsx_logits_stats(const float* emb, int64_t emb_bstride, const floa
 
 IPSX_API size_t ipsx_folded_query_bf16_bytes(int h, int n_token, int d) {
     if (h <= 0 || n_token <= 0 || d <= 0) return 0;
-    return (size_t)cdiv(h * n_token, 32) * (size_t)cdiv(d, 16) * 64 * 16;
+    const int nt = (int)cdiv(h * n_token, 32);
+    return (size_t)(nt == 3 ? 4 : nt) * (size_t)cdiv(d, 16) * 64 * 16;     // whole tiles of the kernel variant (zeros beyond R)
 }
 
 IPSX_API int ipsx_fold_query_bf16(const float* qs, const float* wk_packed, int h, int dk, int n_token, int d,
                                   void* v_packed_bf16, void* stream) {
     IPSX_REQUIRE(qs && wk_packed && v_packed_bf16 && h > 0 && dk > 0 && n_token > 0 && d > 0, "fold_query_bf16: bad arguments");
-    const int R = h * n_token, r_pad = (int)cdiv(R, 32) * 32, ksteps = (int)cdiv(d, 16), kgs = (int)cdiv(d, 8);
+    const int ksteps = (int)cdiv(d, 16), kgs = (int)cdiv(d, 8);
+    const int r_pad = (int)(ipsx_folded_query_bf16_bytes(h, n_token, d) / ((size_t)ksteps * 64 * 16)) * 32;
     const int total = r_pad * ksteps * 16;
     fold_query_bf16_kernel<<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, as_stream(stream)>>>(
         qs, wk_packed, h, dk, n_token, d, kgs, ksteps, r_pad, static_cast<unsigned short*>(v_packed_bf16));

@@ -3,9 +3,12 @@
 import math
 
 import numpy as np
+import pytest
 import torch
 
 from oracle import oracle as orc
+from tests.util import (HEAD_F64_BOUNDS, HEAD_SHAPES, f64_logits, head_shape_inputs, head_shape_net, head_shape_net64,
+                        head_shape_scores_lengths, rel_err)
 
 
 def test_det_expf_is_accurate_and_monotone():
@@ -179,3 +182,40 @@ def test_loop_tie_rule_sees_duplicates_across_a_colliding_row():
     s = base.copy(); s[11] = s[9]
     rows = lg.copy(); rows[11] = rows[9]
     assert np.array_equal(run(s, rows), canonical(s))
+
+
+@pytest.mark.parametrize("name", sorted(HEAD_SHAPES))
+def test_oracle_tracks_float64_at_head_shapes_no_config_uses(name):
+    """The yardstick of tests/test_head_shapes.py: at every configuration of HEAD_SHAPES (R = H * n_token up to 256,
+    D_k != D / H, D_v != D_k, D off the multiples of 128, n_class up to 130) the oracle's logits, scores, attention maps
+    and forward() predictions lie within HEAD_F64_BOUNDS of the same IPSNet run in float64 through its plain torch modules,
+    per element.  Measured (logits / scale, scores, attention, predictions; the bounds are 1e-6, 3e-5, 1e-4, 2e-5):
+        r33_d64      1.4e-7  5.4e-6  8.6e-6  2.2e-6        r128_d96     2.3e-7  3.7e-6  1.5e-5  2.0e-6
+        r40_d160     7.3e-8  2.9e-6  5.4e-6  1.9e-6        r256_d512    1.2e-7  1.6e-6  1.6e-5  4.3e-6
+        r64_d192     1.4e-7  7.3e-6  1.5e-5  1.8e-7        r32t1_d128   1.6e-7  5.3e-6  1.8e-5  1.3e-6
+        r96_d36      1.6e-7  2.6e-6  1.1e-5  1.6e-6        r32t2_mnist  9.8e-8  4.1e-6  8.5e-6  3.1e-6
+    A kernel that is bitwise equal to the oracle at these shapes is therefore right to within fp32 rounding."""
+    net, net64 = head_shape_net(name), head_shape_net64(name)
+    o = orc.Oracle(net)
+    inp = head_shape_inputs(name)
+    err = dict.fromkeys(HEAD_F64_BOUNDS, 0.0)
+    for b in range(2):
+        want, scale = f64_logits(net64, inp["x"][b], inp["pos"][b])
+        err["logits"] = max(err["logits"], float((np.abs(o.logits(inp["x"][b], inp["pos"][b]) - want) / scale).max()))
+    for L in head_shape_scores_lengths(name):
+        rows = inp["rows%d" % L]
+        with torch.no_grad():
+            s64 = net64.transf.get_scores(torch.from_numpy(rows).double()).numpy()
+            a64 = net64.transf.crs_attn.get_attn(torch.from_numpy(rows).double()).numpy()
+        for b in range(2):
+            sc, attn = o.scores(rows[b], want_attn=True)
+            err["scores"] = max(err["scores"], rel_err(sc, s64[b]))
+            err["attn"] = max(err["attn"], rel_err(attn, a64[b]))
+    preds = o.forward(inp["mem_patch"], inp["mem_pos"])
+    with torch.no_grad():
+        mem_pos = torch.from_numpy(inp["mem_pos"]).double() if inp["mem_pos"] is not None else None
+        p64 = net64(torch.from_numpy(inp["mem_patch"]).double(), mem_pos)
+    assert set(preds) == set(p64) == {"soft", "sig"}
+    err["preds"] = max(rel_err(preds[k], p64[k].numpy()) for k in preds)
+    print(name, {k: "%.1e" % v for k, v in err.items()})
+    assert all(err[k] <= HEAD_F64_BOUNDS[k] for k in err), err

@@ -67,3 +67,101 @@ def ulp_diff(a, b):
     a = np.where(a < 0, -(a & 0x7FFFFFFF), a)
     b = np.where(b < 0, -(b & 0x7FFFFFFF), b)
     return int(np.abs(a - b).max()) if a.size else 0
+
+
+# ---------------------------------------------------------------- head shapes no shipped configuration uses
+# Every fixture runs H = 8 (4), n_token <= 4, D in {32, 128, 512} and D_k = D / H, so R = H * n_token <= 32.  This table
+# reaches the kernels' other shape-picked paths (tests/test_head_shapes.py on the GPU; the oracle's float64 anchor at the
+# same shapes in tests/test_oracle_props.py):
+#   R = 33, 40, 64, 96, 128, 256: 2, 3, 4 and 8 column tiles of the logits, partial last tiles;
+#   R = 32 with n_token = 1 and 2: the generic selection loop instead of the LDS-resident one;
+#   D = 64 (8 k-groups: the logits' 8-group tail only), 96 (tail + scalar remainder), 160 (a 16-group trip + remainder),
+#   192 (trip + tail), 512 (trips only), 36 (D % 8 != 0: the masked scalar logits path - no aggregation, which needs
+#   D % 32 == 0);  D_k above and below D / H, D_v != D_k;  n_token = 8 at D = 512, D_inner = 2048 (112 KiB of token
+#   state: the aggregation's tail above 64 KiB of LDS);  n_class = 1, 10, 65 and 130 under softmax and sigmoid heads.
+def _heads(n_token):
+    """a softmax and a sigmoid task, on the first and the last token"""
+    return {'task0': {'id': 0, 'name': 'soft', 'act_fn': 'softmax', 'metric': 'accuracy'},
+            'task1': {'id': n_token - 1, 'name': 'sig', 'act_fn': 'sigmoid', 'metric': 'auc'}}
+
+
+def _feat(D, H, T, Dk, Dv, Di, n_class, use_pos=False, N=180, M=16, I=48):
+    return synth.camelyon_conf(N=N, M=M, I=I, n_chan_in=64, D=D, H=H, n_token=T, D_k=Dk, D_v=Dv, D_inner=Di,
+                               n_class=n_class, use_pos=use_pos, tasks=_heads(T))
+
+
+HEAD_SHAPES = {
+    # name: (configuration, weight seed, runs the aggregation)
+    "r33_d64": (_feat(64, 11, 3, 8, 12, 96, 65), 301, True),
+    "r40_d160": (_feat(160, 8, 5, 24, 16, 256, 130, use_pos=True), 302, True),
+    "r64_d192": (_feat(192, 16, 4, 8, 20, 128, 1), 303, True),
+    "r96_d36": (_feat(36, 12, 8, 5, 4, 64, 65), 304, False),
+    "r128_d96": (_feat(96, 32, 4, 4, 3, 64, 65, use_pos=True), 305, True),
+    "r256_d512": (_feat(512, 32, 8, 16, 16, 2048, 130), 306, True),
+    "r32t1_d128": (_feat(128, 32, 1, 6, 5, 160, 1), 307, True),
+    "r32t2_mnist": (synth.mnist_conf(N=100, M=8, I=40, H=16, n_token=2, D_k=12, D_v=10, D_inner=256, n_class=65,
+                                     tasks=_heads(2)), 308, True),
+}
+
+
+def head_shape_net(name, device="cpu"):
+    conf, seed, _ = HEAD_SHAPES[name]
+    net = IPSNet(torch.device(device), conf)
+    synth.fill_weights(net, seed)
+    return net.to(device).eval()
+
+
+def head_shape_net64(name):
+    """the same net in float64 on the CPU: its plain torch modules are the yardstick"""
+    return head_shape_net(name).double()
+
+
+def f64_logits(net64, x, pos=None):
+    """Attention logits (L, H*n_token) of rows x (+ pos) through the float64 net's q_w / k_w, and per element the scale
+    sum_c |x_c| sum_j |qs_j| |k_w[j, c]| that bounds the rounding of any fp32 order of the contraction."""
+    ca = net64.transf.crs_attn
+    H, T, Dk = ca.H, ca.n_token, ca.D_k
+    x = torch.as_tensor(np.asarray(x)).double()
+    if pos is not None:
+        x = x + torch.as_tensor(np.asarray(pos)).double()
+    with torch.no_grad():
+        qs = (ca.q_w(ca.q[0]) / ca.attention.temperature).view(T, H, Dk)
+        k = ca.k_w(x).view(-1, H, Dk)
+        lg = torch.einsum("thj,lhj->lht", qs, k).reshape(-1, H * T)
+        wk = ca.k_w.weight.view(H, Dk, -1)
+        absv = torch.einsum("thj,hjc->htc", qs.abs(), wk.abs()).reshape(H * T, -1)
+        scale = x.abs() @ absv.T
+    return lg.numpy(), scale.numpy()
+
+
+def rel_err(got, want, floor=0.0):
+    """largest per-element |got - want| / max(|want|, floor)"""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    return float((np.abs(got - want) / np.maximum(np.abs(want), floor)).max()) if want.size else 0.0
+
+
+# Bounds of the oracle (so of any kernel bitwise equal to it) against the float64 nets on head_shape_inputs, per element:
+# logits |err| / f64_logits' scale, scores / attention maps / predictions relative to the float64 value.  Measured worst
+# case over HEAD_SHAPES: 2.3e-7, 7.3e-6, 1.8e-5, 4.3e-6 (tests/test_oracle_props.py lists them per configuration).
+HEAD_F64_BOUNDS = {"logits": 1e-6, "scores": 3e-5, "attn": 1e-4, "preds": 2e-5}
+
+
+def head_shape_scores_lengths(name):
+    """53 candidates, and a candidate set past the 160 KiB LDS staging of the scores kernel (L (R + 1) 4 + 8 R bytes)"""
+    ca = HEAD_SHAPES[name][0]
+    R = ca.H * ca.n_token
+    return 53, (160 * 1024 - 8 * R) // ((R + 1) * 4) + 40
+
+
+def head_shape_inputs(name):
+    """Deterministic inputs of one configuration: logits rows x / pos (2, 333, D), scores rows per length, and a memory
+    (2, M, ...) with positional rows for forward()."""
+    conf, seed, _ = HEAD_SHAPES[name]
+    g = np.random.default_rng(seed)
+    D = conf.D
+    out = {"x": g.standard_normal((2, 333, D)).astype(np.float32), "pos": g.standard_normal((2, 333, D)).astype(np.float32)}
+    for L in head_shape_scores_lengths(name):
+        out["rows%d" % L] = g.standard_normal((2, L, D)).astype(np.float32)
+    out["mem_patch"] = synth.make_patches(conf, 2, seed=seed, N=conf.M, blank_frac=0.3).numpy()
+    out["mem_pos"] = (0.5 * g.standard_normal((2, conf.M, D))).astype(np.float32) if conf.use_pos else None
+    return out
