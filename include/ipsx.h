@@ -70,8 +70,10 @@ extern "C" {
  *         ipsx_maxpool_3x3s2_bwd_nhwc (+ _supported)
  *   3.02  round 6 (additions): ipsx_projector_stream_ctl_zero_words (the stream's control words were re-ordered: what must be
  *         zero comes first); ipsx_scan_workgroups_per_image - candidate sets beyond the LDS with 8 heads and one token run
- *         as a team of workgroups per image; ipsx_scan_workspace_bytes grew for those shapes */
-#define IPSX_VERSION 302
+ *         as a team of workgroups per image; ipsx_scan_workspace_bytes grew for those shapes
+ *   3.03  (additions only): ipsx_projector_stats_typed, ipsx_projector_apply_bf16, ipsx_projector_bf16_supported - the
+ *         feature projector on the bf16 matrix pipe, rows stored as float32 / bfloat16 / float16 */
+#define IPSX_VERSION 303
 
 #define IPSX_OK            0
 #define IPSX_EINVAL       -1      /* bad argument / unsupported shape */
@@ -298,6 +300,19 @@ int ipsx_projector_apply(const ipsx_conv* lin, const float* x, int64_t n, const 
  * pipeline that feeds ipsx_scan_persistent. */
 int ipsx_projector_apply_publish(const ipsx_conv* lin, const float* x, int64_t n, const float* stats, float* out,
                                  int32_t* ready, int32_t value, void* stream);
+
+/* The projector on the bf16 matrix pipe (3.03; IPSX_PRECISION=bf16 for feature nets): rows stored as
+ * dtype 0 = float32, 1 = bfloat16, 2 = float16.  ipsx_projector_stats_typed: the fp32 moments of the stored values widened
+ * exactly - dtype 0 is ipsx_projector_stats, a half-stored row gets the bits of the same values passed as float32.
+ * ipsx_projector_apply_bf16: out = ReLU(alpha * (|rstd| * sum_k bf16(x - mean) * bf16(W)) + shift), centred in fp32 and
+ * rounded to bf16 in the operand load, fp32 accumulation in one fixed k order; lin->w_packed_bf16 =
+ * ipsx_pack_conv_weight_bf16 of the (d, f) weights as a 1x1 convolution (lin->colsum is not read).  Needs f % 16 == 0,
+ * d % 32 == 0 (ipsx_projector_bf16_supported) and rows at 16-byte addresses.  ready (or NULL): what
+ * ipsx_projector_apply_publish does with it. */
+int ipsx_projector_stats_typed(const void* x, int dtype, int64_t n, int f, float ln_eps, float* stats, void* stream);
+int ipsx_projector_bf16_supported(const ipsx_conv* lin);
+int ipsx_projector_apply_bf16(const ipsx_conv* lin, const void* x, int dtype, int64_t n, const float* stats, float* out,
+                              int32_t* ready, int32_t ready_value, void* stream);
 
 /* ONE image's patches through the fused 1x32x32 trunk AND their logits as ONE persistent launch that feeds
  * ipsx_scan_persistent patch by patch (reference: self.encoder(...) chunk by chunk in IPSNet.ips, architecture/ips_net.py:

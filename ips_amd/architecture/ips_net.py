@@ -179,6 +179,8 @@ class IPSNet(nn.Module):
                 self._fused_train_ok = fused_encoder.supported(self.encoder)
             if self._fused_train_ok and fused_encoder.enabled():
                 return fused_encoder.encode(self.encoder, x)
+        if not self.is_image and x.dtype in (torch.float16, torch.bfloat16):
+            x = x.float()      # half-stored features (IPSX_PRECISION=bf16): the stock modules compute on the exact widening
         return self.encoder(x).flatten(1)
 
     # ---------------------------------------------------------------- IPS

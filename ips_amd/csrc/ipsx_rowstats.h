@@ -46,6 +46,20 @@ struct RowMoments {
     rm_f32x2 s01, s23, q01, q23;
 };
 
+// four consecutive stored values, widened exactly to fp32: the moments of a row stored as float16 / bfloat16 are those of
+// the same values passed as float32 (the typed statistics of the bf16 projector, projector_bf16.hip)
+typedef _Float16 rm_f16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned short rm_u16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ rm_f32x4 rm_load4(const float* p) { return *reinterpret_cast<const rm_f32x4*>(p); }
+__device__ __forceinline__ rm_f32x4 rm_load4(const _Float16* p) {
+    return __builtin_convertvector(*reinterpret_cast<const rm_f16x4*>(p), rm_f32x4);
+}
+__device__ __forceinline__ rm_f32x4 rm_load4(const __bf16* p) {
+    const rm_u16x4 u = *reinterpret_cast<const rm_u16x4*>(p);
+    return rm_f32x4{__uint_as_float((unsigned)u[0] << 16), __uint_as_float((unsigned)u[1] << 16),
+                    __uint_as_float((unsigned)u[2] << 16), __uint_as_float((unsigned)u[3] << 16)};
+}
+
 __device__ __forceinline__ void rm_zero(RowMoments& m) {
     m.s01 = rm_f32x2{0.0f, 0.0f}; m.s23 = m.s01; m.q01 = m.s01; m.q23 = m.s01;
 }
@@ -86,9 +100,9 @@ constexpr float RM_RECENTRE = 17.0f;
 // 2,048 additions of values that do not cancel - a constant row's residual d is exact, so mean' is the constant itself),
 // var = E[d^2] - E[d]^2, which no longer cancels.  NOT inlined - a rare path that must not cost the GEMM kernels around it
 // registers.  -> (mean', var)
-__device__ __attribute__((noinline)) float2 rm_recentred(const float* __restrict__ xr, bool centred, float mean, float var,
+template <typename T>
+__device__ __attribute__((noinline)) float2 rm_recentred(const T* __restrict__ xr, bool centred, float mean, float var,
                                                           int d, int lane) {
-    const rm_f32x4* p = reinterpret_cast<const rm_f32x4*>(xr);
     const rm_f32x4 mv = {mean, mean, mean, mean};
     rm_f32x4 q = {0.0f, 0.0f, 0.0f, 0.0f}, sd = q;
     const int kgs = d >> 3;
@@ -96,11 +110,11 @@ __device__ __attribute__((noinline)) float2 rm_recentred(const float* __restrict
     for (; g + 8 <= kgs; g += 8) {
         rm_f32x4 v[8];
 #pragma unroll
-        for (int w = 0; w < 8; ++w) v[w] = centred ? p[2 * (g + w)] : mv;
+        for (int w = 0; w < 8; ++w) v[w] = centred ? rm_load4(xr + 8 * (g + w)) : mv;
 #pragma unroll
         for (int w = 0; w < 8; ++w) { const rm_f32x4 c = v[w] - mv; sd = sd + c; q = __builtin_elementwise_fma(c, c, q); }
     }
-    for (; g < kgs; ++g) { const rm_f32x4 c = (centred ? p[2 * g] : mv) - mv; sd = sd + c; q = __builtin_elementwise_fma(c, c, q); }
+    for (; g < kgs; ++g) { const rm_f32x4 c = (centred ? rm_load4(xr + 8 * g) : mv) - mv; sd = sd + c; q = __builtin_elementwise_fma(c, c, q); }
     float s1 = (sd[0] + sd[1]) + (sd[2] + sd[3]);
     float s2 = (q[0] + q[1]) + (q[2] + q[3]);
     s1 = s1 + lane_xor_f32<32>(s1, lane);
@@ -113,7 +127,8 @@ __device__ __attribute__((noinline)) float2 rm_recentred(const float* __restrict
 
 // (mean, +-rstd) of the row whose halves lanes i and i + 32 hold - the same bits in both (a + b == b + a).  xr: this lane's
 // row + 4 * half (any readable row where there is none); wave-uniform control flow: every lane of the wave calls it.
-__device__ __forceinline__ float2 rm_finish(const RowMoments& m, int d, float eps, int lane, const float* __restrict__ xr) {
+template <typename T>
+__device__ __forceinline__ float2 rm_finish(const RowMoments& m, int d, float eps, int lane, const T* __restrict__ xr) {
     float t = (m.s01[0] + m.s01[1]) + (m.s23[0] + m.s23[1]);
     float u = (m.q01[0] + m.q01[1]) + (m.q23[0] + m.q23[1]);
     t = t + lane_xor_f32<32>(t, lane);
@@ -154,11 +169,12 @@ __device__ __forceinline__ float centred_row_dot(const float* __restrict__ xrow,
 }
 
 // the moments of rows row0 .. row0 + 31 (those below n) by one wavefront: lane l -> row row0 + (l & 31), half l >> 5;
-// d % 8 == 0.  Eight 16-byte loads in flight per lane.
-__device__ __forceinline__ float2 row_moments_wave32(const float* __restrict__ x, long long row0, long long n, int d, float eps,
+// d % 8 == 0.  Eight 16-byte (float) or 8-byte (float16 / bfloat16) loads in flight per lane.
+template <typename T>
+__device__ __forceinline__ float2 row_moments_wave32(const T* __restrict__ x, long long row0, long long n, int d, float eps,
                                                      int lane) {
     const long long row = row0 + (lane & 31);
-    const rm_f32x4* p = reinterpret_cast<const rm_f32x4*>(x + (size_t)(row < n ? row : n - 1) * d + 4 * (lane >> 5));
+    const T* p = x + (size_t)(row < n ? row : n - 1) * d + 4 * (lane >> 5);
     RowMoments m;
     rm_zero(m);
     const int kgs = d >> 3;
@@ -166,12 +182,12 @@ __device__ __forceinline__ float2 row_moments_wave32(const float* __restrict__ x
     for (; g + 8 <= kgs; g += 8) {
         rm_f32x4 v[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = p[2 * (g + u)];
+        for (int u = 0; u < 8; ++u) v[u] = rm_load4(p + 8 * (g + u));
 #pragma unroll
         for (int u = 0; u < 8; ++u) rm_add(m, v[u]);
     }
-    for (; g < kgs; ++g) rm_add(m, p[2 * g]);
-    return rm_finish(m, d, eps, lane, reinterpret_cast<const float*>(p));
+    for (; g < kgs; ++g) rm_add(m, rm_load4(p + 8 * g));
+    return rm_finish(m, d, eps, lane, p);
 }
 
 }  // namespace ipsx

@@ -36,7 +36,9 @@ def precision():
     """'fp32' (default: exact, reference parity), 'fp32x3' (every fp32 operand of the residual stages split exactly
     into three bf16 terms, six products on the bf16 matrix pipe, fp32 accumulation: fp32-grade accuracy but not
     bit-identical to the fp32 kernel) or 'bf16' (bf16 operands with fp32 accumulation; no reference behaviour
-    to match).  The last two exist for the fused 1x32x32 trunk."""
+    to match).  The last two exist for the fused 1x32x32 trunk.  A feature net under 'bf16' runs its projector on the
+    bf16 matrix pipe too (rows centred in fp32, then rounded) and reads feature rows stored as float16 /
+    bfloat16; under 'fp32x3' it keeps the fp32 projector and float32 features."""
     p = os.environ.get("IPSX_PRECISION", "fp32").lower()
     if p not in ("fp32", "fp32x3", "bf16"):
         raise ValueError("IPSX_PRECISION must be 'fp32', 'fp32x3' or 'bf16', got {!r}".format(p))
@@ -228,6 +230,10 @@ _EXPORTS = {
     "ipsx_projector_apply": (C.c_int, [C.POINTER(Conv), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ipsx_projector_apply_publish": (C.c_int, [C.POINTER(Conv), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_int32, C.c_void_p]),
+    "ipsx_projector_stats_typed": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "ipsx_projector_bf16_supported": (C.c_int, [C.POINTER(Conv)]),
+    "ipsx_projector_apply_bf16": (C.c_int, [C.POINTER(Conv), C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_int32, C.c_void_p]),
     "ipsx_trunk_stream_ctl_words": (C.c_size_t, [C.c_int64]),
     "ipsx_trunk_stream_supported": (C.c_int, [C.POINTER(Trunk), C.c_int, C.c_int]),
     "ipsx_trunk_stream": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,

@@ -64,6 +64,25 @@ class EncoderPlan:
         self._ws = None
         self._ws_small = 0
         self._held = 0
+        self.bf16 = False          # feature nets: the projector runs on the bf16 matrix pipe (IPSX_PRECISION=bf16)
+
+    def _features(self, x):
+        """Feature rows as the projector reads them: float32, or float16 / bfloat16 under the bf16 projector, which widens
+        them in its operand load.  Shapes the bf16 projector does not take raise here, before the first launch."""
+        if x.dtype in (torch.float16, torch.bfloat16):
+            if not self.bf16:
+                raise TypeError("{} features need IPSX_PRECISION=bf16 (the {} projector reads float32)".format(x.dtype, precision()))
+        else:
+            x = _f32(x)
+        if self.bf16 and not lib().ipsx_projector_bf16_supported(C.byref(self.lin)):
+            raise ValueError("the bf16 projector needs F % 16 == 0 and D % 32 == 0, got F = {}, D = {}".format(
+                self.lin.c_in, self.lin.c_out))
+        return x if x.is_contiguous() else x.contiguous()
+
+    def _stats(self, x, out):
+        _ck(lib().ipsx_projector_stats_typed(_p(x), _PATCH_DTYPES[x.dtype], x.shape[0], x.shape[1], C.c_float(self.ln_eps),
+                                             _p(out), _stream()), "ipsx_projector_stats_typed")
+        return out
 
     def _walk(self):
         """The module tree, flattened ONCE: every module's child dictionary (the structural fingerprint is the ids of their
@@ -169,7 +188,16 @@ class EncoderPlan:
             wf = _f32(w)
             _ck(lib().ipsx_weight_colsum(_p(wf), w.shape[0], w.shape[1], _p(colsum), _stream()), "ipsx_weight_colsum")
             self._keep += [packed, aff, colsum, wf]
-            self.lin = Conv(w.shape[1], w.shape[0], 1, 1, 1, 0, _p(packed), _p(aff[0]), _p(aff[1]), None, _p(colsum))
+            half = None
+            if precision() == "bf16":
+                # the bf16 projector's B operand (csrc/projector_bf16.hip): W rounded to bf16, viewed as a 1x1 convolution
+                half = torch.empty(lib().ipsx_packed_conv_weight_bf16_bytes(w.shape[0], w.shape[1], 1, 1), dtype=torch.uint8,
+                                   device=w.device)
+                _ck(lib().ipsx_pack_conv_weight_bf16(_p(wf), w.shape[0], w.shape[1], 1, 1, _p(half), _stream()),
+                    "ipsx_pack_conv_weight_bf16")
+                self._keep.append(half)
+            self.bf16 = half is not None
+            self.lin = Conv(w.shape[1], w.shape[0], 1, 1, 1, 0, _p(packed), _p(aff[0]), _p(aff[1]), _p(half), _p(colsum))
             self.ln_eps = float(ln.eps)
             self.d_out = w.shape[0]
 
@@ -267,12 +295,10 @@ class EncoderPlan:
         """(mean, rstd) of every feature row of ``x`` (P, F) -> (P, 2): the LayerNorm moments the projector's GEMM applies
         to its operand; for callers that run this HBM-bound pass ahead of / beside the GEMM (``encode(x, stats=...)``)."""
         self._refresh()
-        x = _f32(x)
+        x = self._features(x)
         if out is None:
             out = torch.empty((x.shape[0], 2), dtype=torch.float32, device=x.device)
-        _ck(lib().ipsx_projector_stats(_p(x), x.shape[0], x.shape[1], C.c_float(self.ln_eps), _p(out), _stream()),
-            "ipsx_projector_stats")
-        return out
+        return self._stats(x, out)
 
     def image_stream_supported(self, x_shape, D, R):
         """Can ``image_stream`` encode patches of this shape (the fused fp32 1x32x32 trunk, 128 features, R <= 32)?"""
@@ -302,14 +328,21 @@ class EncoderPlan:
         if self.is_image:
             return False
         self._refresh()
-        return bool(lib().ipsx_projector_stream_supported(C.byref(self.lin), int(n), int(R)))
+        return not self.bf16 and bool(lib().ipsx_projector_stream_supported(C.byref(self.lin), int(n), int(R)))
 
     def stream(self, x, vq, R, emb, logits, ctl, ready, workgroups=0, short_first=-1, slide_rows=None):
         """Projector + logits of the feature rows ``x`` (P, F) - one slide, or several one after the other, ``slide_rows``
         each - as one persistent launch that advances ``ready`` (the progress word(s) of ``scan_persistent``, one per
         slide) as rows complete: ``emb`` (P, 512) and ``logits`` (P, R) are the outputs, ``ctl`` =
-        ``torch.zeros(stream_ctl_words(P), int32)`` zeroed before every call, ``vq`` the folded query."""
+        ``torch.zeros(stream_ctl_words(P), int32)`` zeroed before every call, ``vq`` the folded query.  The fp32
+        projector only: float32 rows, and not under the bf16 projector (IPSX_PRECISION=bf16 runs ``encode`` launch by
+        launch) - both refused before the launch."""
         self._refresh()
+        if self.bf16:
+            raise TypeError("the projector stream runs the fp32 projector; under IPSX_PRECISION=bf16 the projector is "
+                            "encode()'s bf16 kernel")
+        if x.dtype in (torch.float16, torch.bfloat16):
+            raise TypeError("{} features need IPSX_PRECISION=bf16 (the projector stream reads float32)".format(x.dtype))
         x = _f32(x)
         _ck(lib().ipsx_projector_stream(C.byref(self.lin), _p(x), x.shape[0], int(slide_rows or x.shape[0]),
                                         C.c_float(self.ln_eps), _p(emb), _p(vq), int(R),
@@ -327,15 +360,17 @@ class EncoderPlan:
         return int(lib().ipsx_projector_stream_ctl_zero_words(int(n)))
 
     def encode(self, x, nonblank=None, stats=None, out=None, publish=None):
-        """(P, C, h, w) or (P, F) float32 on the GPU  ->  (P, D).
+        """(P, C, h, w) patches or (P, F) feature rows on the GPU  ->  (P, D) float32.  float32 input; patches also
+        float16 / bfloat16 under IPSX_PRECISION=bf16 or fp32x3 (``_patches``), feature rows also float16 / bfloat16
+        under IPSX_PRECISION=bf16, whose projector widens them in its operand load (``_features``).
 
         ``nonblank`` (P int32, 1 = the patch has a non-zero element; e.g. from ``patchify_sparse``) switches on
         the exact blank-patch dedup without the pass that looks for blank patches.  ``publish`` = (ready, value), with
         ``stats``: the GEMM launch also does ``publish_rows(ready, value)`` for what was enqueued before it."""
         self._refresh()
-        x = _patches(x) if self.is_image else _f32(x)
+        x = _patches(x) if self.is_image else self._features(x)
         n = x.shape[0]
-        if x.dtype != torch.float32 and (dedup_blank() or nonblank is not None):
+        if self.is_image and x.dtype != torch.float32 and (dedup_blank() or nonblank is not None):
             raise TypeError("blank-patch dedup reads float32 patches")
         if out is None:
             out = torch.empty((n, self.d_out), dtype=torch.float32, device=x.device)
@@ -377,6 +412,15 @@ class EncoderPlan:
                     self.n_encoded = torch.tensor(sel.numel(), dtype=torch.int32, device=x.device)
                     return out
             return self.encode_plain(x, out)
+        elif self.bf16:
+            if stats is None:
+                ws = self._workspace(lib().ipsx_projector_workspace_bytes(n), x.device)
+                stats = self._stats(x, ws[:8 * n].view(torch.float32).view(n, 2))
+            elif stats.shape != (n, 2) or stats.dtype != torch.float32 or not stats.is_contiguous():
+                raise ValueError("stats must be a contiguous (P, 2) float32 tensor")
+            ready, value = publish if publish is not None else (None, 0)
+            _ck(lib().ipsx_projector_apply_bf16(C.byref(self.lin), _p(x), _PATCH_DTYPES[x.dtype], n, _p(stats), _p(out), _p(ready),
+                                                int(value), _stream()), "ipsx_projector_apply_bf16")
         elif stats is not None:
             if stats.shape != (n, 2) or stats.dtype != torch.float32 or not stats.is_contiguous():
                 raise ValueError("stats must be a contiguous (P, 2) float32 tensor")
@@ -398,5 +442,7 @@ def encoder_kernel_name(plan):
     if plan is None or plan._sig is None:
         return None
     if not plan.is_image:
+        if plan.bf16:
+            return "row_moments_typed_kernel + projector_bf16_kernel (bf16 projector)"
         return "row_stats_kernel + conv_nhwc_kernel<NORM> (projector)"
     return lib().ipsx_trunk_kernel(C.byref(plan.trunk)).decode()
