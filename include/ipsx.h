@@ -72,7 +72,9 @@ extern "C" {
  *         zero comes first); ipsx_scan_workgroups_per_image - candidate sets beyond the LDS with 8 heads and one token run
  *         as a team of workgroups per image; ipsx_scan_workspace_bytes grew for those shapes
  *   3.03  (additions only): ipsx_projector_stats_typed, ipsx_projector_apply_bf16, ipsx_projector_bf16_supported - the
- *         feature projector on the bf16 matrix pipe, rows stored as float32 / bfloat16 / float16 */
+ *         feature projector on the bf16 matrix pipe, rows stored as float32 / bfloat16 / float16;
+ *         ipsx_conv2d_affine_nhwc_bf16 (+ _supported), ipsx_avgpool_nhwc_bf16 - the layer-by-layer trunk at precision 1:
+ *         ipsx_trunk_encode no longer refuses precision 1 on a trunk the fused kernel does not take */
 #define IPSX_VERSION 303
 
 #define IPSX_OK            0
@@ -164,10 +166,13 @@ typedef struct ipsx_trunk {
                                      residual stages; 2 = "fp32x3": every fp32 operand split exactly into three
                                      bf16 terms, the six significant products on the bf16 matrix pipe, fp32
                                      accumulate - fp32-grade accuracy, not bit-identical to precision 0.
-                                     1 and 2: fused 1x32x32 trunk only, need w_packed_bf16                */
+                                     1 and 2 need w_packed_bf16.  2: fused 1x32x32 trunk only.  1 on any other
+                                     trunk: stem + max-pool in fp32, the pooled map rounded once to bf16, every
+                                     convolution behind it ipsx_conv2d_affine_nhwc_bf16 on bf16 activations   */
     int patch_dtype;              /* storage type of the `patches` argument of the encode calls: 0 = float32
                                      (default), 1 = bfloat16, 2 = float16 (BASELINE configs[4]: half-precision patch
-                                     storage; precision 1 or 2 only - the exact path reads float32)        */
+                                     storage; fused 1x32x32 trunk at precision 1 or 2 only - the exact path and
+                                     the stems of the layer-by-layer trunks read float32)                   */
 } ipsx_trunk;
 
 /* y = act(affine(conv(x)) [+ residual]); x (n,c_in,h,w), y (n,c_out,ho,wo) NCHW */
@@ -181,6 +186,13 @@ int ipsx_conv2d_affine_to_nhwc(const ipsx_conv* cv, const float* x, const float*
  * This is the fast layer-by-layer path (16-byte operand loads); a Linear over rows is h = w = 1. */
 int ipsx_conv2d_affine_nhwc(const ipsx_conv* cv, const float* x, const float* residual,
                             float* y, int64_t n, int h, int w, int relu, void* stream);
+/* The same on the bf16 matrix pipe (3.03; the layer-by-layer trunk at precision 1): x, residual and y are bfloat16,
+ * channels-last, at 16-byte addresses; B operand cv->w_packed_bf16 (ipsx_pack_conv_weight_bf16), fp32 accumulation in one
+ * fixed k order per output, then in fp32 fma(acc, alpha, shift) [+ residual widened exactly] [ReLU] and ONE rounding to
+ * bfloat16 (nearest even).  Any kernel size, stride and padding; C_in % 16 == 0, C_out % 8 == 0 (_supported). */
+int ipsx_conv2d_affine_nhwc_bf16_supported(const ipsx_conv* cv);
+int ipsx_conv2d_affine_nhwc_bf16(const ipsx_conv* cv, const void* x, const void* residual, void* y, int64_t n, int h,
+                                 int w, int relu, void* stream);
 /* The fused trunk's stages as stand-alone plain convolutions of channels-last maps (training step: forward and data
  * gradient on the maps of 32-px patches, each layer's input read once and LDS-resident for all taps): 64 -> 64 3x3 on 8x8,
  * 128 -> 128 3x3 on 4x4, 64 -> 128 3x3 / 2 and 1x1 / 2 from 8x8 (ipsx_conv2d_lds_nhwc_supported).  cv: kernel, stride, pad and
@@ -229,6 +241,8 @@ int ipsx_maxpool_3x3s2_bwd_nhwc_supported(int c, int h, int w);
 int ipsx_maxpool_3x3s2_bwd_nhwc(const float* x, const float* dy, float* dx, int64_t n, int c, int h, int w, void* stream);
 /* (n,hw,c) -> (n,c) */
 int ipsx_avgpool_nhwc(const float* x, float* y, int64_t n, int c, int hw, void* stream);
+/* the same over a bfloat16 map: fp32 sum in the same order, same division, float32 out (3.03) */
+int ipsx_avgpool_nhwc_bf16(const void* x, float* y, int64_t n, int c, int hw, void* stream);
 /* nn.MaxPool2d(3, 2, 1) */
 int ipsx_maxpool_3x3s2(const float* x, float* y, int64_t n, int c, int h, int w, void* stream);
 /* nn.AdaptiveAvgPool2d(1): (n,c,hw) -> (n,c) */

@@ -5,6 +5,8 @@
 // Host-side runtime only: it sequences the kernels of conv.hip (or the fused
 // LDS-resident kernel of fused_trunk.hip when the trunk matches it) on the
 // caller's stream, in chunks of patches so the activation workspace stays bounded.
+// At precision 1 (bf16) a layer-by-layer trunk keeps its fp32 stem and max-pool, rounds the pooled map once to bf16 and
+// runs every convolution behind it through conv_nhwc_bf16.hip ("bf16 layered trunk").
 
 #include <algorithm>
 #include <cstdlib>
@@ -22,6 +24,8 @@ int fused_stage64(const ipsx_block* blocks, int n_block, const float* x, float* 
 int fused_stem_pool50(const ipsx_trunk* t, const float* patches, float* y, int64_t n, hipStream_t s);   // 1 = ran, 0 = other shape
 bool fused_stem_pool50_covers(const ipsx_trunk* t);
 bool fused_stem_pool100x3_covers(const ipsx_trunk* t);
+// conv_nhwc_bf16.hip: the pooled fp32 map rounded once to bf16 (count % 8 == 0)
+int round_to_bf16(const float* x, void* y, size_t count, hipStream_t s);
 // fused_trunk.hip
 bool fused_trunk_supported(const ipsx_trunk* t);
 int fused_trunk_encode(const ipsx_trunk* t, const float* patches, int64_t n, float* emb, hipStream_t s);
@@ -96,6 +100,22 @@ static int64_t trunk_chunk(const TrunkGeom& g, int64_t n) {
     return std::max<int64_t>(chunk_for(g, n, trunk_budget()), 1);
 }
 
+// precision 1 on a layer-by-layer trunk: every convolution behind the stem runs conv_nhwc_bf16_kernel
+static int layered_bf16_check(const ipsx_trunk* t) {
+    IPSX_REQUIRE(t->stem.c_out % 8 == 0, "trunk (bf16): the stem has %d output channels (need a multiple of 8)", t->stem.c_out);
+    for (int b = 0; b < t->n_block; ++b) {
+        const ipsx_block& B = t->blocks[b];
+        for (int j = 0; j < B.n_conv + (B.has_down ? 1 : 0); ++j) {
+            const ipsx_conv& cv = j < B.n_conv ? B.conv[j] : B.down;
+            const char* what = j < B.n_conv ? "conv" : "shortcut";
+            IPSX_REQUIRE(cv.w_packed_bf16, "trunk (bf16): block %d %s %d has no w_packed_bf16 (ipsx_pack_conv_weight_bf16)", b, what, j);
+            IPSX_REQUIRE(ipsx_conv2d_affine_nhwc_bf16_supported(&cv), "trunk (bf16): block %d %s %d, %d -> %d channels: the bf16 "
+                         "convolution needs C_in %% 16 == 0 and C_out %% 8 == 0", b, what, j, cv.c_in, cv.c_out);
+        }
+    }
+    return IPSX_OK;
+}
+
 }  // namespace ipsx
 
 using namespace ipsx;
@@ -112,9 +132,14 @@ IPSX_API const char* ipsx_trunk_kernel(const ipsx_trunk* t) {
         return t->precision == 2 ? "fused_trunk_x3_kernel" : (t->precision == 1 ? "fused_trunk_bf16_kernel" : "fused_trunk_kernel");
     if (t && t->n_block >= 2 && fused_stem_pool50_covers(t) &&
         fused_stage64_blocks(t->blocks, t->n_block, 13, 13) > 0)          // the reference's shipped 50-px Megapixel-MNIST trunk
-        return "stem_pool50_kernel + fused_stage64_kernel (layer1, LDS-resident) + conv_nhwc_kernel (layer2, layer by layer)";
+        return t->precision == 1 ? "stem_pool50_kernel + conv_nhwc_bf16_kernel (layer by layer, bf16)"
+                                 : "stem_pool50_kernel + fused_stage64_kernel (layer1, LDS-resident) + conv_nhwc_kernel (layer2, layer by layer)";
+    if (t && t->precision == 1 && fused_stem_pool50_covers(t))
+        return "stem_pool50_kernel + conv_nhwc_bf16_kernel (layer by layer, bf16)";
     if (t && fused_stem_pool100x3_covers(t))                               // the traffic-sign trunk: fused stem + pool, then layer by layer
-        return "stem_pool100x3_kernel + conv_nhwc_kernel (layer by layer)";
+        return t->precision == 1 ? "stem_pool100x3_kernel + conv_nhwc_bf16_kernel (layer by layer, bf16)"
+                                 : "stem_pool100x3_kernel + conv_nhwc_kernel (layer by layer)";
+    if (t && t->precision == 1) return "conv_any_kernel (stem) + conv_nhwc_bf16_kernel (layer by layer, bf16)";
     return "conv_nhwc_kernel (layer by layer)";
 }
 
@@ -123,11 +148,17 @@ IPSX_API int ipsx_trunk_encode(const ipsx_trunk* t, const float* patches, int64_
     TrunkGeom g;
     IPSX_TRY(trunk_geom(t, &g));
     IPSX_REQUIRE(patches && emb && n_patch >= 0, "trunk_encode: bad arguments");
-    IPSX_REQUIRE(t->precision == 0 || fused_trunk_supported(t), "trunk_encode: the bf16 / fp32x3 paths exist for the fused 1x32x32 trunk only");
-    IPSX_REQUIRE(t->patch_dtype == 0 || (fused_trunk_supported(t) && t->precision != 0),
-                 "trunk_encode: half-precision patch storage exists for the fused 1x32x32 trunk at precision 1 / 2 only");
+    const bool fused = fused_trunk_supported(t);
+    IPSX_REQUIRE(t->precision >= 0 && t->precision <= 2, "trunk_encode: precision %d", t->precision);
+    IPSX_REQUIRE(t->precision != 2 || fused, "trunk_encode: fp32x3 exists for the fused 1x32x32 trunk only");
+    IPSX_REQUIRE(t->patch_dtype == 0 || fused, "trunk_encode: the stem kernels of the layer-by-layer trunk (stem_pool50_kernel, "
+                 "stem_pool100x3_kernel, conv_any_kernel) read float32 patches; half-precision patch storage exists for the fused "
+                 "1x32x32 trunk at precision 1 / 2 only");
+    IPSX_REQUIRE(t->patch_dtype == 0 || t->precision != 0, "trunk_encode: half-precision patch storage needs precision 1 / 2");
+    const bool bf16 = t->precision == 1 && !fused;       // ("bf16 layered trunk")
+    if (bf16) IPSX_TRY(layered_bf16_check(t));
     if (n_patch == 0) return IPSX_OK;
-    if (fused_trunk_supported(t)) return fused_trunk_encode(t, patches, n_patch, emb, as_stream(stream));
+    if (fused) return fused_trunk_encode(t, patches, n_patch, emb, as_stream(stream));
 
     const int64_t chunk = workspace ? chunk_for(g, n_patch, workspace_bytes) : 0;      // chunks fit what the caller gave
     if (chunk < 1)
@@ -137,6 +168,11 @@ IPSX_API int ipsx_trunk_encode(const ipsx_trunk* t, const float* patches, int64_
     float* buf[4];
     for (int i = 0; i < 4; ++i) buf[i] = static_cast<float*>(workspace) + i * buf_elems;
     const size_t patch_elems = (size_t)t->c_in * t->h * t->w;
+    // bf16: the same workspace and the same chunks - four bf16 activation buffers in its first half, the fp32 stem output
+    // and pooled map in its second (2 + 2 + 4 + 4 bytes x chunk x max_elems of the 16 it has)
+    unsigned short* hb[4];
+    for (int i = 0; i < 4; ++i) hb[i] = static_cast<unsigned short*>(workspace) + i * buf_elems;
+    if (bf16) { buf[0] = static_cast<float*>(workspace) + 2 * buf_elems; buf[1] = buf[0] + buf_elems; }
 
     for (int64_t p0 = 0; p0 < n_patch; p0 += chunk) {
         const int64_t n = std::min(chunk, n_patch - p0);
@@ -151,6 +187,38 @@ IPSX_API int ipsx_trunk_encode(const ipsx_trunk* t, const float* patches, int64_
             IPSX_TRY(ipsx_maxpool_3x3s2_nhwc(buf[0], buf[1], n, c, h, w, stream));
         }
         h = conv_out(h, 3, 2, 1); w = conv_out(w, 3, 2, 1);
+        if (bf16) {
+            // the pooled map (the fp32 kernels' bits) rounded ONCE to bf16; from here on activations are bf16 in HBM
+            IPSX_TRY(round_to_bf16(buf[1], hb[1], (size_t)n * h * w * c, as_stream(stream)));
+            int cur = 1;
+            for (int b = 0; b < t->n_block; ++b) {
+                const ipsx_block& B = t->blocks[b];
+                int fr[3], k = 0;
+                for (int i = 0; i < 4; ++i) if (i != cur) fr[k++] = i;
+                const unsigned short* src = hb[cur];
+                int ch = h, cw = w, si = -1;
+                for (int j = 0; j < B.n_conv - 1; ++j) {   // conv -> BN -> ReLU
+                    const ipsx_conv& cv = B.conv[j];
+                    const int di = (si == fr[0]) ? fr[1] : fr[0];
+                    IPSX_TRY(ipsx_conv2d_affine_nhwc_bf16(&cv, src, nullptr, hb[di], n, ch, cw, 1, stream));
+                    ch = conv_out(ch, cv.kh, cv.stride, cv.pad); cw = conv_out(cw, cv.kw, cv.stride, cv.pad);
+                    src = hb[di]; si = di;
+                }
+                const ipsx_conv& last = B.conv[B.n_conv - 1];
+                const unsigned short* shortcut = hb[cur];  // the STORED bf16 block input (or projection output)
+                if (B.has_down) {
+                    IPSX_TRY(ipsx_conv2d_affine_nhwc_bf16(&B.down, hb[cur], nullptr, hb[fr[2]], n, h, w, 0, stream));
+                    shortcut = hb[fr[2]];
+                }
+                const int oi = (si == fr[0]) ? fr[1] : fr[0];
+                IPSX_TRY(ipsx_conv2d_affine_nhwc_bf16(&last, src, shortcut, hb[oi], n, ch, cw, 1, stream));
+                h = conv_out(ch, last.kh, last.stride, last.pad); w = conv_out(cw, last.kw, last.stride, last.pad);
+                c = last.c_out;
+                cur = oi;
+            }
+            IPSX_TRY(ipsx_avgpool_nhwc_bf16(hb[cur], emb + (size_t)p0 * g.d_out, n, c, h * w, stream));
+            continue;
+        }
         int cur = 1;                                   // buf[cur] holds the block input
         int b_first = 0;
         if (c == 64) {                                 // layer1 on a small map: all of its convolutions in one LDS-resident kernel

@@ -36,7 +36,9 @@ def precision():
     """'fp32' (default: exact, reference parity), 'fp32x3' (every fp32 operand of the residual stages split exactly
     into three bf16 terms, six products on the bf16 matrix pipe, fp32 accumulation: fp32-grade accuracy but not
     bit-identical to the fp32 kernel) or 'bf16' (bf16 operands with fp32 accumulation; no reference behaviour
-    to match).  The last two exist for the fused 1x32x32 trunk.  A feature net under 'bf16' runs its projector on the
+    to match).  'fp32x3' exists for the fused 1x32x32 trunk only.  'bf16' runs on every image encoder: the fused trunk
+    for 1x32x32 patches, and for every other trunk the stem and max-pool in fp32, then bf16 activations in memory and
+    every convolution on the bf16 matrix pipe ("bf16 layered trunk").  A feature net under 'bf16' runs its projector on the
     bf16 matrix pipe too (rows centred in fp32, then rounded) and reads feature rows stored as float16 /
     bfloat16; under 'fp32x3' it keeps the fp32 projector and float32 features."""
     p = os.environ.get("IPSX_PRECISION", "fp32").lower()
@@ -188,6 +190,9 @@ _EXPORTS = {
                                              C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ipsx_conv2d_affine_nhwc": (C.c_int, [C.POINTER(Conv), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "ipsx_conv2d_affine_nhwc_bf16_supported": (C.c_int, [C.POINTER(Conv)]),
+    "ipsx_conv2d_affine_nhwc_bf16": (C.c_int, [C.POINTER(Conv), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                               C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ipsx_conv2d_lds_nhwc_supported": (C.c_int, [C.c_int] * 7),
     "ipsx_conv2d_lds_nhwc": (C.c_int, [C.POINTER(Conv), C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "ipsx_conv2d_lds_nhwc_stats_slabs": (C.c_int64, [C.c_int64]),
@@ -207,6 +212,7 @@ _EXPORTS = {
     "ipsx_maxpool_3x3s2_bwd_nhwc_supported": (C.c_int, [C.c_int] * 3),
     "ipsx_maxpool_3x3s2_bwd_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ipsx_avgpool_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "ipsx_avgpool_nhwc_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "ipsx_maxpool_3x3s2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "ipsx_avgpool": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "ipsx_trunk_workspace_bytes": (C.c_size_t, [C.POINTER(Trunk), C.c_int64]),
@@ -826,6 +832,42 @@ def patchify_sparse(index, value, offsets, canvas, patch_size, patch_stride, fla
     _ck(lib().ipsx_patchify_sparse(_p(index), _p(value), _p(offsets), index.numel(), B, Cc, H, W, ph, pw, sh, sw,
                                    _p(out), _p(nb), _stream()), "ipsx_patchify_sparse")
     return (out, nb) if flags else out
+
+
+# ------------------------------------------------------------------ bf16 layer kernels (the layered trunk under IPSX_PRECISION=bf16)
+def conv2d_nhwc_bf16(x, weight, alpha, shift, stride, pad, residual=None, relu=True):
+    """One convolution of the bf16 layer-by-layer trunk (conv_nhwc_bf16_kernel): ``x`` (n, h, w, C_in) bfloat16, OIHW float32
+    ``weight`` (rounded to bf16 by the packing), float32 ``alpha`` / ``shift`` (C_out,) or None, ``residual``
+    (n, ho, wo, C_out) bfloat16 or None  ->  (n, ho, wo, C_out) bfloat16."""
+    if x.dim() != 4 or x.dtype != torch.bfloat16 or not x.is_contiguous():
+        raise ValueError("expected a contiguous bfloat16 (n, h, w, C) tensor")
+    w = _f32(weight.detach())
+    co, ci, kh, kw = w.shape
+    n, h, wd, _ = x.shape
+    half = torch.empty(lib().ipsx_packed_conv_weight_bf16_bytes(co, ci, kh, kw), dtype=torch.uint8, device=x.device)
+    _ck(lib().ipsx_pack_conv_weight_bf16(_p(w), co, ci, kh, kw, _p(half), _stream()), "ipsx_pack_conv_weight_bf16")
+    alpha, shift = (_f32(alpha) if alpha is not None else None), (_f32(shift) if shift is not None else None)
+    cv = Conv(ci, co, kh, kw, stride, pad, None, _p(alpha), _p(shift), _p(half))
+    if x.shape[3] != ci or not lib().ipsx_conv2d_affine_nhwc_bf16_supported(C.byref(cv)):
+        raise ValueError("the bf16 convolution needs C_in % 16 == 0 and C_out % 8 == 0, got {} -> {}".format(ci, co))
+    ho, wo = (h + 2 * pad - kh) // stride + 1, (wd + 2 * pad - kw) // stride + 1
+    if residual is not None and (residual.dtype != torch.bfloat16 or tuple(residual.shape) != (n, ho, wo, co) or
+                                 not residual.is_contiguous()):
+        raise ValueError("residual must be a contiguous bfloat16 (n, ho, wo, C_out) tensor")
+    y = torch.empty((n, ho, wo, co), dtype=torch.bfloat16, device=x.device)
+    _ck(lib().ipsx_conv2d_affine_nhwc_bf16(C.byref(cv), _p(x), _p(residual), _p(y), n, h, wd, int(bool(relu)), _stream()),
+        "ipsx_conv2d_affine_nhwc_bf16")
+    return y
+
+
+def avgpool_nhwc_bf16(x):
+    """(n, h, w, C) bfloat16 -> (n, C) float32: the fp32 sum over the pixels in memory order, divided by their number."""
+    if x.dim() != 4 or x.dtype != torch.bfloat16 or not x.is_contiguous():
+        raise ValueError("expected a contiguous bfloat16 (n, h, w, C) tensor")
+    n, h, w, c = x.shape
+    y = torch.empty((n, c), dtype=torch.float32, device=x.device)
+    _ck(lib().ipsx_avgpool_nhwc_bf16(_p(x), _p(y), n, c, h * w, _stream()), "ipsx_avgpool_nhwc_bf16")
+    return y
 
 
 # ------------------------------------------------------------------ aggregation
