@@ -74,8 +74,10 @@ extern "C" {
  *   3.03  (additions only): ipsx_projector_stats_typed, ipsx_projector_apply_bf16, ipsx_projector_bf16_supported - the
  *         feature projector on the bf16 matrix pipe, rows stored as float32 / bfloat16 / float16;
  *         ipsx_conv2d_affine_nhwc_bf16 (+ _supported), ipsx_avgpool_nhwc_bf16 - the layer-by-layer trunk at precision 1:
- *         ipsx_trunk_encode no longer refuses precision 1 on a trunk the fused kernel does not take */
-#define IPSX_VERSION 303
+ *         ipsx_trunk_encode no longer refuses precision 1 on a trunk the fused kernel does not take
+ *   3.04  (additions only): ipsx_projector_train_forward (+ _supported, _slabs), ipsx_projector_wgrad (+ _chunk_rows,
+ *         _max_rows, _workspace_bytes) - the feature projector of the training step, forward and weight gradient */
+#define IPSX_VERSION 304
 
 #define IPSX_OK            0
 #define IPSX_EINVAL       -1      /* bad argument / unsupported shape */
@@ -612,6 +614,31 @@ int ipsx_bn_train_forward_partials(const float* x, const float* residual, int64_
 int ipsx_bn_train_backward(const float* dy, const float* y, const float* x, int64_t rows, int c, const float* gamma,
                            const float* save_mean, const float* save_invstd, int relu, float* dx, float* dresidual,
                            float* dgamma, float* dbeta, float* workspace, void* stream);
+
+/* The feature projector of the training step (architecture/ips_net.py:54-60 under net.train() with autograd: LayerNorm
+ * without affine -> Linear -> BatchNorm1d -> ReLU; the features need no gradient).  x: (n, F) rows stored as dtype 0 =
+ * float32, 1 = bfloat16, 2 = float16 (widened exactly in the operand load: the bits of the same values passed as float32);
+ * stats: ipsx_projector_stats_typed of those rows (only |rstd| is used).  Both GEMMs run the RAW rows through the fp32
+ * matrix cores, centred in registers: the normalised rows never exist.  F a multiple of 32, D a power of two 32 .. 1024
+ * (ipsx_projector_train_supported).
+ * ipsx_projector_train_forward: z (n, D) = |rstd| * ((x - mean) W^T) + b - lin: the 1x1 Linear (w_packed:
+ * ipsx_pack_conv_weight, shift: its bias, alpha NULL), weight: the same (D, F) weights unpacked - and, off the accumulators,
+ * partial[slab][0 | 1][D] = sum (z - shift), sum (z - shift)^2 per slab of 64 rows (ipsx_projector_train_slabs(n) of them),
+ * shift (D floats, written by the call) = row 0 of z: what ipsx_bn_train_forward_partials takes.
+ * ipsx_projector_wgrad: dw (D, F) [+]= sum_r (dz[r, :] |rstd_r|)^T (x[r, :] - mean_r), db (D) [+]= sum_r dz[r, :]; the rows
+ * are cut into chunks of ipsx_projector_wgrad_chunk_rows() rows whose partial blocks are added in chunk order - on top of
+ * what dw / db hold when accumulate != 0.  One call takes at most ipsx_projector_wgrad_max_rows rows (activations below
+ * 2 GiB; a multiple of the chunk): more rows go slice by slice with accumulate = 1 from the second on, which gives the bits
+ * of one call whatever the slice (a multiple of the chunk).  workspace: ipsx_projector_wgrad_workspace_bytes(n, F, D). */
+int ipsx_projector_train_supported(int f, int d);
+int64_t ipsx_projector_train_slabs(int64_t n);
+int ipsx_projector_train_forward(const ipsx_conv* lin, const float* weight, const void* x, int dtype, int64_t n,
+                                 const float* stats, float* z, float* shift, float* partial, void* stream);
+int64_t ipsx_projector_wgrad_chunk_rows(void);
+int64_t ipsx_projector_wgrad_max_rows(int f, int d, int dtype);
+size_t ipsx_projector_wgrad_workspace_bytes(int64_t n, int f, int d);
+int ipsx_projector_wgrad(const void* x, int dtype, const float* dz, const float* stats, int64_t n, int f, int d, float* dw,
+                         float* db, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -179,6 +179,13 @@ class IPSNet(nn.Module):
                 self._fused_train_ok = fused_encoder.supported(self.encoder)
             if self._fused_train_ok and fused_encoder.enabled():
                 return fused_encoder.encode(self.encoder, x)
+        if hip.on_device(x) and self.encoder.training and not self.is_image and torch.is_grad_enabled():
+            # the same step of a feature net: LayerNorm + Linear + BatchNorm1d + ReLU as one node, half-stored rows read typed
+            from ..training import fused_projector
+            if getattr(self, "_fused_train_ok", None) is None:
+                self._fused_train_ok = fused_projector.supported(self.encoder)
+            if self._fused_train_ok and fused_projector.enabled() and x.dim() == 2 and x.shape[0] > 1 and not x.requires_grad:
+                return fused_projector.encode(self.encoder, x)
         if not self.is_image and x.dtype in (torch.float16, torch.bfloat16):
             x = x.float()      # half-stored features (IPSX_PRECISION=bf16): the stock modules compute on the exact widening
         return self.encoder(x).flatten(1)

@@ -1,14 +1,15 @@
 """The training step's kernels behind ``training/fused_encoder.py`` (reference training/iterative.py:158-163: the with-grad
 forward of the M selected patches and its backward): convolutions forward / data gradient / weight gradient, BatchNorm in
 batch-statistics mode, the max-pool - ctypes bindings of csrc/bn_train.hip, conv_wgrad.hip, dgrad_s2.hip, stem_train.hip,
-pool_train.hip (split out of ``hip.py`` in round 6; ``ips_amd.hip`` re-exports every public name)."""
+pool_train.hip (split out of ``hip.py`` in round 6; ``ips_amd.hip`` re-exports every public name) - and, behind
+``training/fused_projector.py``, the feature projector's two GEMMs (csrc/projector_train.hip)."""
 
 import ctypes as C
 import os
 
 import torch
 
-from .hip import (lib, _ck, _p, _f32, _stream, Conv)
+from .hip import (lib, _ck, _p, _f32, _stream, _PATCH_DTYPES, Conv)
 from .hip_encoder import _pack_conv
 
 
@@ -201,7 +202,9 @@ def conv2d_nhwc_wgrad(x, dy, weight_shape, stride, pad):
 
 
 def _rows_cl(t):
-    """(P, C, H, W) channels-last tensor -> (rows, C) of its memory."""
+    """(P, C, H, W) channels-last tensor, or (rows, C) rows as they lie (BatchNorm1d) -> (rows, C) of its memory."""
+    if t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous():
+        return t.shape[0], t.shape[1]
     if t.dim() != 4 or t.dtype != torch.float32 or not t.is_contiguous(memory_format=torch.channels_last):
         raise ValueError("expected a float32 channels-last (P, C, H, W) tensor")
     return t.shape[0] * t.shape[2] * t.shape[3], t.shape[1]
@@ -297,3 +300,80 @@ def bn_train_backward(dy, y, x, gamma, mean, invstd, relu, want_residual):
                                      _p(dx), _p(dres), _p(dgamma), _p(dbeta), _p(ws), _stream()),
         "ipsx_bn_train_backward")
     return dx, dres, dgamma, dbeta
+
+
+# ---------------------------------------------------------------- training step (with-grad feature projector)
+def projector_train_supported(f, d):
+    """Do ``projector_train_forward`` / ``projector_wgrad`` take a Linear(f, d) (F a multiple of 32; D a power of two
+    32 .. 1024, which is also what the BatchNorm kernels behind it take)?"""
+    return bool(lib().ipsx_projector_train_supported(f, d) and lib().ipsx_bn_train_supported(2, d))
+
+
+def _feature_rows(x, f):
+    if x.dim() != 2 or x.shape[1] != f or x.dtype not in _PATCH_DTYPES or not x.is_cuda:
+        raise ValueError("expected (rows, {}) float32 / bfloat16 / float16 feature rows on the GPU, got {} {}".format(
+            f, tuple(x.shape), x.dtype))
+    if x.shape[0] == 0:
+        raise ValueError("no rows")
+    return x if x.is_contiguous() else x.contiguous()
+
+
+def projector_train_forward(x, weight, bias, ln_eps):
+    """z = Linear(LayerNorm(x)) of (rows, F) feature rows (float32, or float16 / bfloat16 widened in the operand load) with
+    the (D, F) ``weight`` and ``bias``, for the BatchNorm1d behind it in batch-statistics mode:
+    -> (z, stats, partial, slabs, shift) - ``stats`` (rows, 2) the rows' (mean, rstd), all that backward needs of the
+    LayerNorm; ``partial`` (slabs, 2, D) the column sums of z around ``shift`` for ``bn_train_forward_partials``."""
+    d, f = weight.shape
+    if not projector_train_supported(f, d):
+        raise ValueError("the training projector takes F % 32 == 0 and D a power of two in 32 .. 1024, got F = {}, D = {}".format(f, d))
+    x = _feature_rows(x, f)
+    n = x.shape[0]
+    w = _f32(weight.detach())
+    b = _f32(bias.detach())
+    packed = _pack_conv(w.view(d, f, 1, 1))
+    lin = Conv(f, d, 1, 1, 1, 0, _p(packed), None, _p(b), None, None)
+    stats = torch.empty((n, 2), dtype=torch.float32, device=x.device)
+    _ck(lib().ipsx_projector_stats_typed(_p(x), _PATCH_DTYPES[x.dtype], n, f, C.c_float(ln_eps), _p(stats), _stream()),
+        "ipsx_projector_stats_typed")
+    slabs = int(lib().ipsx_projector_train_slabs(n))
+    z = torch.empty((n, d), dtype=torch.float32, device=x.device)
+    partial = torch.empty((slabs, 2, d), dtype=torch.float32, device=x.device)
+    shift = torch.empty(d, dtype=torch.float32, device=x.device)
+    _ck(lib().ipsx_projector_train_forward(C.byref(lin), _p(w), _p(x), _PATCH_DTYPES[x.dtype], n, _p(stats), _p(z), _p(shift),
+                                           _p(partial), _stream()), "ipsx_projector_train_forward")
+    return z, stats, partial, slabs, shift
+
+
+def _projector_wgrad_slice_rows(f, d, dtype):
+    """Rows of one ``ipsx_projector_wgrad`` call: what keeps either activation below 2 GiB, in whole chunks of the kernel's
+    row split.  ``IPSX_TRAIN_PROJECTOR_SLICE_ROWS`` lowers it (tests: the slicing at a small size), to whole chunks as well."""
+    chunk = int(lib().ipsx_projector_wgrad_chunk_rows())
+    step = int(lib().ipsx_projector_wgrad_max_rows(f, d, _PATCH_DTYPES[dtype]))
+    knob = os.environ.get("IPSX_TRAIN_PROJECTOR_SLICE_ROWS")
+    if knob:
+        step = min(step, max(chunk, int(knob) // chunk * chunk))
+    return step
+
+
+def projector_wgrad(x, dz, stats):
+    """The gradient of ``projector_train_forward``'s z w.r.t. weight and bias -> (dw (D, F), db (D,)): dw = sum over the rows
+    of (dz |rstd|)^T (x - mean), on the fp32 matrix cores from the raw rows.  Activations of 2 GiB and more go in slices of
+    whole rows, each call adding its chunks onto the result in order: the bits of one call (csrc/projector_train.hip)."""
+    n, d = dz.shape
+    f = x.shape[1]
+    x = _feature_rows(x, f)
+    if dz.dtype != torch.float32 or x.shape[0] != n or tuple(stats.shape) != (n, 2):
+        raise ValueError("dz: expected float32 ({}, D), statistics of the same rows".format(x.shape[0]))
+    if not projector_train_supported(f, d):
+        raise ValueError("the training projector takes F % 32 == 0 and D a power of two in 32 .. 1024, got F = {}, D = {}".format(f, d))
+    dz = dz if dz.is_contiguous() else dz.contiguous()
+    step = _projector_wgrad_slice_rows(f, d, x.dtype)
+    dw = torch.empty((d, f), dtype=torch.float32, device=x.device)
+    db = torch.empty(d, dtype=torch.float32, device=x.device)
+    nb = int(lib().ipsx_projector_wgrad_workspace_bytes(min(n, step), f, d))
+    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    for i0 in range(0, n, step):
+        cnt = min(step, n - i0)
+        _ck(lib().ipsx_projector_wgrad(_p(x[i0:i0 + cnt]), _PATCH_DTYPES[x.dtype], _p(dz[i0:i0 + cnt]), _p(stats[i0:i0 + cnt]), cnt, f, d,
+                                       _p(dw), _p(db), int(i0 > 0), _p(ws), nb, _stream()), "ipsx_projector_wgrad")
+    return dw, db
