@@ -76,8 +76,10 @@ extern "C" {
  *         ipsx_conv2d_affine_nhwc_bf16 (+ _supported), ipsx_avgpool_nhwc_bf16 - the layer-by-layer trunk at precision 1:
  *         ipsx_trunk_encode no longer refuses precision 1 on a trunk the fused kernel does not take
  *   3.04  (additions only): ipsx_projector_train_forward (+ _supported, _slabs), ipsx_projector_wgrad (+ _chunk_rows,
- *         _max_rows, _workspace_bytes) - the feature projector of the training step, forward and weight gradient */
-#define IPSX_VERSION 304
+ *         _max_rows, _workspace_bytes) - the feature projector of the training step, forward and weight gradient
+ *   3.05  (additions only): ipsx_attn_pool_forward, ipsx_attn_pool_backward (+ _supported, _workspace_bytes) - the
+ *         cross-attention aggregator of the training step on folded queries */
+#define IPSX_VERSION 305
 
 #define IPSX_OK            0
 #define IPSX_EINVAL       -1      /* bad argument / unsupported shape */
@@ -639,6 +641,26 @@ int64_t ipsx_projector_wgrad_max_rows(int f, int d, int dtype);
 size_t ipsx_projector_wgrad_workspace_bytes(int64_t n, int f, int d);
 int ipsx_projector_wgrad(const void* x, int dtype, const float* dz, const float* stats, int64_t n, int f, int d, float* dw,
                          float* db, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The cross-attention aggregator of the training step on folded queries (architecture/transformer.py:43-109 under
+ * autograd).  x: (B, M, D) float32 embeddings; A: (R, D) the scaled query folded into k_w, R = H * n_token rows in the order
+ * r = h * n_token + t (ipsx_fold_query's); keep: (B, R, M) attention-dropout factors (0 or 1 / (1 - p)) or NULL = ones.
+ *   forward   L[b, m, r] = x[b, m, :] . A[r, :],  P[b, r, :] = softmax_m L (max-subtracted),  P' = P * keep,
+ *             Z[b, r, :] = sum_m P'[b, r, m] x[b, m, :]                      -> Z (B, R, D), P (B, R, M)
+ *   backward  dP' = dZ . x,  dL = P * (keep * dP' - dZ[b, r, :] . Z[b, r, :]),
+ *             dx[b, m, :] = sum_r P' dZ[b, r, :] + dL A[r, :]  (dx NULL: not computed),  dA[r, :] = sum_b sum_m dL x[b, m, :]
+ * All contractions run on the fp32 matrix cores; no tensor of B x M x H x D_k elements exists.  Sums over workgroups (Z, dA)
+ * go through per-workgroup blocks in the workspace, added in ascending (b, row) order: the same bits every call, and an
+ * image's Z, P and dx do not depend on the rest of the batch.  R 1 .. 32, D a multiple of 32 up to 1024
+ * (ipsx_attn_pool_supported), any M >= 1, B <= 65535.  workspace: ipsx_attn_pool_workspace_bytes(B, M, R, D), either
+ * direction.  No allocation, no host synchronisation (graph-capturable). */
+int ipsx_attn_pool_supported(int R, int D);
+size_t ipsx_attn_pool_workspace_bytes(int64_t B, int64_t M, int R, int D);
+int ipsx_attn_pool_forward(const float* x, const float* A, const float* keep, int64_t B, int64_t M, int R, int D, float* Z,
+                           float* P, void* workspace, size_t workspace_bytes, void* stream);
+int ipsx_attn_pool_backward(const float* x, const float* A, const float* keep, const float* P, const float* Z, const float* dZ,
+                            int64_t B, int64_t M, int R, int D, float* dx, float* dA, void* workspace, size_t workspace_bytes,
+                            void* stream);
 
 #ifdef __cplusplus
 }

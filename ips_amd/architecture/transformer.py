@@ -5,12 +5,14 @@ names (``pos_enc_1d``, ``ScaledDotProductAttention``, ``MultiHeadCrossAttention`
 ``MLP``, ``Transformer``), constructor arguments, parameter names and shapes, so
 state-dicts interchange with the reference.
 
-Two execution paths live behind that interface:
+Three execution paths live behind that interface:
 
 * tensors on a ROCm device, autograd off  ->  the hand-written gfx950 kernels in
   ``ips_amd/csrc`` through the C ABI of ``include/ipsx.h`` (``ips_amd.hip``).
   There is no fallback: if ``libipsx.so`` is missing the call raises.
-* everything else (CPU tensors, or autograd on for the training ``forward``)
+* tensors on a ROCm device, autograd on, ``Transformer.forward``  ->  the attention pool on folded queries as one
+  autograd node (``ips_amd/training/fused_aggregator.py``, csrc/attn_pool_train.hip), the R-row rest on stock ops.
+* everything else (CPU tensors, ``get_scores`` / ``get_attn`` under autograd, ``IPSX_TRAIN_AGGREGATOR=0``)
   ->  stock ATen ops, which is what the reference itself dispatches.
 """
 
@@ -187,4 +189,13 @@ class Transformer(nn.Module):
         ca = self.crs_attn
         if _use_hip(x, *self.parameters()) and not self.training:
             return hip.aggregate(self, x)
+        if (x.is_cuda and x.dim() == 3 and x.dtype == torch.float32 and torch.is_grad_enabled() and hip.backend() == "hip"
+                and (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
+            # training step (reference training/iterative.py:158-163): the (B, M) part as one node on folded queries
+            from ..training import fused_aggregator
+            if fused_aggregator.enabled():
+                if getattr(self, "_fused_train_ok", None) is None:        # (the module tree does not change after construction)
+                    self._fused_train_ok = fused_aggregator.supported(self)
+                if self._fused_train_ok:
+                    return fused_aggregator.forward(self, x)
         return self.mlp(self.crs_attn(x))

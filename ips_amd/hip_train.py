@@ -2,7 +2,8 @@
 forward of the M selected patches and its backward): convolutions forward / data gradient / weight gradient, BatchNorm in
 batch-statistics mode, the max-pool - ctypes bindings of csrc/bn_train.hip, conv_wgrad.hip, dgrad_s2.hip, stem_train.hip,
 pool_train.hip (split out of ``hip.py`` in round 6; ``ips_amd.hip`` re-exports every public name) - and, behind
-``training/fused_projector.py``, the feature projector's two GEMMs (csrc/projector_train.hip)."""
+``training/fused_projector.py``, the feature projector's two GEMMs (csrc/projector_train.hip), and behind
+``training/fused_aggregator.py`` the attention pool on folded queries (csrc/attn_pool_train.hip)."""
 
 import ctypes as C
 import os
@@ -377,3 +378,67 @@ def projector_wgrad(x, dz, stats):
         _ck(lib().ipsx_projector_wgrad(_p(x[i0:i0 + cnt]), _PATCH_DTYPES[x.dtype], _p(dz[i0:i0 + cnt]), _p(stats[i0:i0 + cnt]), cnt, f, d,
                                        _p(dw), _p(db), int(i0 > 0), _p(ws), nb, _stream()), "ipsx_projector_wgrad")
     return dw, db
+
+
+# ---------------------------------------------------------------- training step (with-grad cross-attention aggregator)
+def attn_pool_supported(R, D):
+    """Do ``attn_pool_forward`` / ``attn_pool_backward`` take R = H * n_token folded query rows (1 .. 32) of D (a multiple of
+    32 up to 1024)?"""
+    return bool(lib().ipsx_attn_pool_supported(int(R), int(D)))
+
+
+def _attn_pool_args(x, A, keep):
+    """Checks (x (B, M, D), A (R, D), keep (B, R, M) | None) -> B, M, D, R."""
+    for name, t in (("x", x), ("A", A), ("keep", keep)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or not t.is_cuda:
+            raise ValueError("{}: expected float32 on the GPU, got {} on {}".format(name, t.dtype, t.device))
+        if not t.is_contiguous():
+            raise ValueError("{}: expected a contiguous tensor".format(name))
+    if x.dim() != 3 or A.dim() != 2 or A.shape[1] != x.shape[2]:
+        raise ValueError("expected x (B, M, D) and A (R, D), got {} and {}".format(tuple(x.shape), tuple(A.shape)))
+    B, M, D = x.shape
+    R = A.shape[0]
+    if B < 1 or M < 1:
+        raise ValueError("no rows")
+    if not attn_pool_supported(R, D):
+        raise ValueError("the attention pool takes R = H * n_token in 1 .. 32 and D a multiple of 32 up to 1024, got R = {}, D = {}".format(R, D))
+    if keep is not None and tuple(keep.shape) != (B, R, M):
+        raise ValueError("keep: expected {}, got {}".format((B, R, M), tuple(keep.shape)))
+    return B, M, D, R
+
+
+def _attn_pool_workspace(B, M, R, D, device):
+    nb = int(lib().ipsx_attn_pool_workspace_bytes(B, M, R, D))
+    if nb == 0:
+        raise ValueError("the attention pool takes B <= 65535 and M <= 2^30, got B = {}, M = {}".format(B, M))
+    return torch.empty(nb, dtype=torch.uint8, device=device), nb
+
+
+def attn_pool_forward(x, A, keep=None):
+    """Z[b, r] = sum_m P'[b, r, m] x[b, m] with P = softmax_m(x . A[r]), P' = P * keep, of float32 embeddings ``x`` (B, M, D),
+    the folded query ``A`` (R, D) and attention-dropout factors ``keep`` (B, R, M) or None: -> (Z (B, R, D), P (B, R, M))."""
+    B, M, D, R = _attn_pool_args(x, A, keep)
+    Z = torch.empty((B, R, D), dtype=torch.float32, device=x.device)
+    P = torch.empty((B, R, M), dtype=torch.float32, device=x.device)
+    ws, nb = _attn_pool_workspace(B, M, R, D, x.device)
+    _ck(lib().ipsx_attn_pool_forward(_p(x), _p(A), _p(keep), B, M, R, D, _p(Z), _p(P), _p(ws), nb, _stream()), "ipsx_attn_pool_forward")
+    return Z, P
+
+
+def attn_pool_backward(x, A, keep, P, Z, dZ, want_dx=True):
+    """The gradients of ``attn_pool_forward``'s Z: -> (dx (B, M, D) | None, dA (R, D)); ``P``, ``Z`` are what the forward
+    returned for the same ``x``, ``A``, ``keep``."""
+    B, M, D, R = _attn_pool_args(x, A, keep)
+    for name, t, shape in (("P", P, (B, R, M)), ("Z", Z, (B, R, D)), ("dZ", dZ, (B, R, D))):
+        if t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != shape:
+            raise ValueError("{}: expected float32 {} on the GPU, got {} {}".format(name, shape, t.dtype, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("{}: expected a contiguous tensor".format(name))
+    dx = torch.empty_like(x) if want_dx else None
+    dA = torch.empty((R, D), dtype=torch.float32, device=x.device)
+    ws, nb = _attn_pool_workspace(B, M, R, D, x.device)
+    _ck(lib().ipsx_attn_pool_backward(_p(x), _p(A), _p(keep), _p(P), _p(Z), _p(dZ), B, M, R, D, _p(dx), _p(dA), _p(ws), nb, _stream()),
+        "ipsx_attn_pool_backward")
+    return dx, dA
