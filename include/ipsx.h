@@ -626,7 +626,8 @@ int ipsx_bn_train_backward(const float* dy, const float* y, const float* x, int6
  * ipsx_projector_train_forward: z (n, D) = |rstd| * ((x - mean) W^T) + b - lin: the 1x1 Linear (w_packed:
  * ipsx_pack_conv_weight, shift: its bias, alpha NULL), weight: the same (D, F) weights unpacked - and, off the accumulators,
  * partial[slab][0 | 1][D] = sum (z - shift), sum (z - shift)^2 per slab of 64 rows (ipsx_projector_train_slabs(n) of them),
- * shift (D floats, written by the call) = row 0 of z: what ipsx_bn_train_forward_partials takes.
+ * shift (D floats, written by the call) = the column mean of the first min(n, 8) rows of z: what
+ * ipsx_bn_train_forward_partials takes.
  * ipsx_projector_wgrad: dw (D, F) [+]= sum_r (dz[r, :] |rstd_r|)^T (x[r, :] - mean_r), db (D) [+]= sum_r dz[r, :]; the rows
  * are cut into chunks of ipsx_projector_wgrad_chunk_rows() rows whose partial blocks are added in chunk order - on top of
  * what dw / db hold when accumulate != 0.  One call takes at most ipsx_projector_wgrad_max_rows rows (activations below

@@ -190,17 +190,42 @@ __global__ __launch_bounds__(256, 2) void projector_train_fwd_kernel(PtFwdArgs a
     }
 }
 
-// shift[o] = z[0, o]: the value the column sums are taken around (bn_reduce_kernel's rule: row 0 of the activation)
+// shift[o] = the mean of column o of z over its first k = min(n, PT_SHIFT_ROWS) rows: the value the column sums are taken
+// around.  bn_finalize_kernel takes any shift; the closer it is to the column mean, the less var = q / n - (s / n)^2
+// cancels.  Around row 0 alone (bn_reduce_kernel's rule) some column of 256 lies 3 sigma off, and the fp32 rounding of s
+// and q of a single slab came to 9e-7 of invstd at 65 rows, 6 x the stock error; around the mean of eight rows it lies
+// about 1 sigma off.  One wavefront per column, the lanes split F (coalesced reads of the row of W).
+constexpr int PT_SHIFT_ROWS = 8;
+
 template <typename T>
-__global__ void projector_train_shift_kernel(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                             const float2* __restrict__ stats, int c_in, int c_out, float* __restrict__ shift) {
-    const int o = blockIdx.x * blockDim.x + threadIdx.x;
-    if (o >= c_out) return;
-    const float mean = stats[0].x, rstd = __builtin_fabsf(stats[0].y);
+__global__ __launch_bounds__(256) void projector_train_shift_kernel(const T* __restrict__ x, const float* __restrict__ w,
+                                                                    const float* __restrict__ bias, const float2* __restrict__ stats, int k,
+                                                                    int c_in, int c_out, float* __restrict__ shift) {
+    const int lane = threadIdx.x & 63;
+    const int o = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
+    if (o >= c_out) return;                                         // wave-uniform; no barrier below
+    float mean[PT_SHIFT_ROWS], acc[PT_SHIFT_ROWS];
+    const T* xr[PT_SHIFT_ROWS];
+#pragma unroll
+    for (int u = 0; u < PT_SHIFT_ROWS; ++u) {                       // (a row that is not there repeats the last one; not added)
+        const int r = min(u, k - 1);
+        mean[u] = stats[r].x;
+        xr[u] = x + (size_t)r * c_in;
+        acc[u] = 0.0f;
+    }
     const float* wr = w + (size_t)o * c_in;
-    float acc = 0.0f;
-    for (int f = 0; f < c_in; ++f) acc = __builtin_fmaf((float)x[f] - mean, wr[f], acc);
-    shift[o] = acc * rstd + bias[o];
+    for (int f = lane; f < c_in; f += 64) {
+        const float wv = wr[f];
+#pragma unroll
+        for (int u = 0; u < PT_SHIFT_ROWS; ++u) acc[u] = __builtin_fmaf((float)xr[u][f] - mean[u], wv, acc[u]);
+    }
+    float s = 0.0f;
+#pragma unroll
+    for (int u = 0; u < PT_SHIFT_ROWS; ++u)
+        if (u < k) s = s + acc[u] * __builtin_fabsf(stats[u].y);
+    s = s + lane_xor_f32<32>(s, lane); s = s + lane_xor_f32<16>(s, lane); s = s + lane_xor_f32<8>(s, lane);
+    s = s + lane_xor_f32<4>(s, lane); s = s + lane_xor_f32<2>(s, lane); s = s + lane_xor_f32<1>(s, lane);
+    if (lane == 0) shift[o] = s / (float)k + bias[o];
 }
 
 // ------------------------------------------------------------------ weight gradient
@@ -379,10 +404,11 @@ IPSX_API int ipsx_projector_train_forward(const ipsx_conv* lin, const float* wei
     const int esize = dtype == 0 ? 4 : 2;
     hipStream_t s = as_stream(stream);
     const float2* st2 = reinterpret_cast<const float2*>(stats);
-    const dim3 sg((unsigned)cdiv(d, 64)), sb(64);
-    if (dtype == 0) projector_train_shift_kernel<float><<<sg, sb, 0, s>>>(static_cast<const float*>(x), weight, lin->shift, st2, f, d, shift);
-    else if (dtype == 1) projector_train_shift_kernel<__bf16><<<sg, sb, 0, s>>>(static_cast<const __bf16*>(x), weight, lin->shift, st2, f, d, shift);
-    else projector_train_shift_kernel<_Float16><<<sg, sb, 0, s>>>(static_cast<const _Float16*>(x), weight, lin->shift, st2, f, d, shift);
+    const dim3 sg((unsigned)cdiv(d, 4)), sb(256);
+    const int k = (int)std::min<int64_t>(n, PT_SHIFT_ROWS);
+    if (dtype == 0) projector_train_shift_kernel<float><<<sg, sb, 0, s>>>(static_cast<const float*>(x), weight, lin->shift, st2, k, f, d, shift);
+    else if (dtype == 1) projector_train_shift_kernel<__bf16><<<sg, sb, 0, s>>>(static_cast<const __bf16*>(x), weight, lin->shift, st2, k, f, d, shift);
+    else projector_train_shift_kernel<_Float16><<<sg, sb, 0, s>>>(static_cast<const _Float16*>(x), weight, lin->shift, st2, k, f, d, shift);
     IPSX_TRY(launched("projector_train_forward (shift)"));
     const int64_t per = pt_rows_per_launch(f, d, esize, 64);
     for (int64_t i0 = 0; i0 < n; i0 += per) {
