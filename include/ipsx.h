@@ -78,8 +78,11 @@ extern "C" {
  *   3.04  (additions only): ipsx_projector_train_forward (+ _supported, _slabs), ipsx_projector_wgrad (+ _chunk_rows,
  *         _max_rows, _workspace_bytes) - the feature projector of the training step, forward and weight gradient
  *   3.05  (additions only): ipsx_attn_pool_forward, ipsx_attn_pool_backward (+ _supported, _workspace_bytes) - the
- *         cross-attention aggregator of the training step on folded queries */
-#define IPSX_VERSION 305
+ *         cross-attention aggregator of the training step on folded queries
+ *   3.06  (additions only): ipsx_projector_stats_indexed, ipsx_projector_apply_indexed, ipsx_projector_apply_bf16_indexed,
+ *         ipsx_projector_stream_indexed, ipsx_ips_finish_indexed - the feature projector reading its rows through an index
+ *         (a shuffle applied as addressing, not as a copy of the patch tensor) and the end of such a call */
+#define IPSX_VERSION 306
 
 #define IPSX_OK            0
 #define IPSX_EINVAL       -1      /* bad argument / unsupported shape */
@@ -366,6 +369,22 @@ int ipsx_trunk_stream(const ipsx_trunk* t, const float* patches, int64_t n_patch
 size_t ipsx_projector_stream_ctl_words(int64_t n);
 size_t ipsx_projector_stream_ctl_zero_words(int64_t n);
 int ipsx_projector_stream_supported(const ipsx_conv* lin, int64_t n, int r);
+/* 3.06: the row-indexed feature producers.  Output row j (stats, out, emb, logits, the 32-row units and the `ready`
+ * progress, all in output order) is computed from source row index[j] of the (src_rows, F) tensor x: index is a flat
+ * int32 row number, the row base is computed in 64 bits (x may be many GB), a number outside [0, src_rows) is clamped
+ * into it.  Per-row arithmetic and k-order are those of the plain entry points - the results are the bits of the plain
+ * kernel run on the gathered tensor x[index] - and every other argument means what it means there (ready may be NULL
+ * in the two apply forms).  A feature row is 4-8 KB of contiguous memory: a gathered row costs no coalescing. */
+int ipsx_projector_stats_indexed(const void* x, int dtype, const int32_t* index, int64_t src_rows, int64_t n, int f,
+                                 float ln_eps, float* stats, void* stream);
+int ipsx_projector_apply_indexed(const ipsx_conv* lin, const float* x, const int32_t* index, int64_t src_rows, int64_t n,
+                                 const float* stats, float* out, int32_t* ready, int32_t value, void* stream);
+int ipsx_projector_apply_bf16_indexed(const ipsx_conv* lin, const void* x, int dtype, const int32_t* index, int64_t src_rows,
+                                      int64_t n, const float* stats, float* out, int32_t* ready, int32_t ready_value,
+                                      void* stream);
+int ipsx_projector_stream_indexed(const ipsx_conv* lin, const float* x, const int32_t* index, int64_t src_rows, int64_t n,
+                                  int64_t slide_rows, float ln_eps, float* emb, const float* v_packed, int r, float* logits,
+                                  int32_t* ctl, int32_t* ready, int workgroups, int short_first, void* stream);
 int ipsx_projector_stream(const ipsx_conv* lin, const float* x, int64_t n, int64_t slide_rows, float ln_eps, float* emb,
                           const float* v_packed, int r, float* logits, int32_t* ctl, int32_t* ready,
                           int workgroups, int short_first, void* stream);
@@ -535,6 +554,14 @@ int ipsx_ips_finish(const void* patches, int64_t patch_row_bytes, int64_t patch_
                     const void* pos, int64_t pos_row_bytes, int64_t pos_bstride_rows, const int64_t* mem_idx, int b, int m,
                     void* mem_patch, void* mem_pos, int64_t* mem_idx_out, const int32_t* status, int32_t* status_host,
                     void* stream);
+/* 3.06: ipsx_ips_finish after a selection that ran on a permuted NUMBERING of the patches (row-indexed producers below):
+ * mem_patch[b][j] = patches[b][order[b][mem_idx[b][j]]], read from the UNSHUFFLED tensor.  order: (b or 1, n_rows) int64,
+ * order_bstride = n_rows, or 0 for one permutation shared by every image.  pos (already in the loop's numbering), mem_pos
+ * and mem_idx_out: as in ipsx_ips_finish. */
+int ipsx_ips_finish_indexed(const void* patches, int64_t patch_row_bytes, int64_t patch_bstride_rows, int64_t n_rows,
+                            const void* pos, int64_t pos_row_bytes, int64_t pos_bstride_rows, const int64_t* mem_idx,
+                            const int64_t* order, int64_t order_bstride, int b, int m, void* mem_patch, void* mem_pos,
+                            int64_t* mem_idx_out, const int32_t* status, int32_t* status_host, void* stream);
 
 /* ONE IPSNet.ips call whose selection loop is resident (architecture/ips_net.py:169-262 for one image on the fused trunk,
  * or for feature slides through the projector), enqueued by ONE library call: fill of the control words, the loop on

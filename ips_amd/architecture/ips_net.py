@@ -32,7 +32,7 @@ import torch
 from torch import nn
 
 from .. import hip
-from ..shuffle import shuffle_batch, shuffle_instance
+from ..shuffle import draw_shuffle, shuffle_batch, shuffle_instance
 from .resnet import load_torchvision_checkpoint, resnet18_trunk, resnet50_trunk
 from .transformer import Transformer, pos_enc_1d
 
@@ -112,6 +112,7 @@ class IPSNet(nn.Module):
 
         # additions that do not change the drop-in surface
         self.last_mem_idx = None      # (B, M) int64 indices chosen by the last ips() call
+        self.last_shuffle = None      # (B, N) | (1, N) int64 permutation of the last shuffled ips() call (see ips), or None
         self._plan = None             # packed-weight cache of the HIP encoder
         self._emb_parts = None        # eval-mode embeddings of the last ips() call (see last_mem_emb)
         self._mem_emb = None
@@ -137,6 +138,34 @@ class IPSNet(nn.Module):
             if torch.is_tensor(pos_enc):
                 pos_enc, _ = shuffle_instance(pos_enc, 1, perm)
         return patches, pos_enc
+
+    def _shuffle_overridden(self):
+        """Has ``do_shuffle`` been replaced on this instance or in a subclass?  Then it is called as ever."""
+        return 'do_shuffle' in self.__dict__ or type(self).do_shuffle is not IPSNet.do_shuffle
+
+    def _shuffle(self, patches, pos_enc):
+        """``do_shuffle`` with the permutation kept (``last_shuffle``) and - where the selection can read the patches
+        through an index (device-resident, contiguous, a schedule that supports it; ``IPSX_SHUFFLE=copy`` switches it off) -
+        WITHOUT the permuted copy of the patch tensor.  The permutation is drawn by the calls ``do_shuffle`` makes, so the
+        RNG streams and the results are those of the copy.  ``pos_enc`` (a few hundred floats per patch) is shuffled by
+        copy either way.  -> (patches, pos_enc, order): ``order`` is the (B or 1, N) index when ``patches`` came back
+        unshuffled, else None."""
+        perm = draw_shuffle(patches, self.shuffle_style)
+        if perm is None:                   # an unknown style: do_shuffle leaves everything as it is
+            return patches, pos_enc, None
+        batch = self.shuffle_style == 'batch'
+        if torch.is_tensor(pos_enc):
+            pos_enc = shuffle_batch(pos_enc, perm)[0] if batch else shuffle_instance(pos_enc, 1, perm)[0]
+        by_index = (os.environ.get("IPSX_SHUFFLE", "index") != "copy" and hip.on_device(self.device) and patches.is_cuda
+                    and patches.is_contiguous() and self.selection.index_supported(patches))
+        order = (perm.unsqueeze(0) if batch else perm)
+        if by_index:
+            order = order.to(patches.device).contiguous()
+            self.last_shuffle = order
+            return patches, pos_enc, order
+        self.last_shuffle = order
+        patches = shuffle_batch(patches, perm)[0] if batch else shuffle_instance(patches, 1, perm)[0]
+        return patches, pos_enc, None
 
     def score_and_select(self, emb, emb_pos, M, idx):
         """Score ``L`` candidates, keep the top ``M`` (:136-155).
@@ -204,6 +233,7 @@ class IPSNet(nn.Module):
         B, N = patches.shape[:2]
 
         self._emb_parts = self._mem_emb = None
+        self.last_shuffle = None
         if M >= N:  # nothing to select (:185-188)
             self.last_mem_idx = None
             return patches.to(device), (pos_enc.expand(B, -1, -1) if self.use_pos else None)
@@ -215,27 +245,33 @@ class IPSNet(nn.Module):
         try:
             if self.use_pos:
                 pos_enc = pos_enc.expand(B, -1, -1)
-            if self.shuffle:
+            order = None
+            if self.shuffle and self._shuffle_overridden():
                 patches, pos_enc = self.do_shuffle(patches, pos_enc)
+            elif self.shuffle:
+                # (the encoder is in eval mode by now: the index path's own condition)
+                patches, pos_enc, order = self._shuffle(patches, pos_enc)
 
             if hip.on_device(device):
                 if self._plan is None:
                     self._plan = hip.EncoderPlan(self.encoder, self.is_image)
                 with self._plan.hold():            # weights cannot change inside a no-grad call: check them once
-                    mem_idx = self._select_hip(patches, pos_enc)
+                    mem_idx = self._select_hip(patches, pos_enc, order)
             else:
                 mem_idx = self._select_aten(patches, pos_enc)
 
             src = self._device_patches if self._device_patches is not None else patches
             self._device_patches = None
             sel = self._selection
-            done = sel.finish(src, pos_enc if self.use_pos else None) if sel is not None else None
+            done = sel.finish(src, pos_enc if self.use_pos else None, order) if sel is not None else None
             if done is not None:       # a resident loop's call ends in ONE launch: gathers, indices, status word (round 5)
                 mem_idx, mem_patch, mem_pos = done
             else:
                 if sel is not None:
                     mem_idx = sel.take_unfinished(mem_idx)
-                mem_patch = self._take(src, mem_idx).to(device)
+                # (through a shuffle index the patches are unshuffled: their rows are order[b, mem_idx[b, m]])
+                mem_patch = self._take(src, mem_idx if order is None else
+                                       torch.gather(order.expand(B, -1), 1, mem_idx)).to(device)
                 mem_pos = self._take(pos_enc, mem_idx) if self.use_pos else None
                 if sel is not None:
                     sel.after_call()
@@ -270,10 +306,10 @@ class IPSNet(nn.Module):
             self._selection = Selection(self)
         return self._selection
 
-    def _select_hip(self, patches, pos_enc):
+    def _select_hip(self, patches, pos_enc, order=None):
         """encode -> logits -> selection loop on the ROCm device (which producer, how the loop follows it: selection.py);
-        patches may still be on the host (lazy loading)."""
-        return self.selection.select(patches, pos_enc)
+        patches may still be on the host (lazy loading); ``order``: a shuffle applied as an index (``_shuffle``)."""
+        return self.selection.select(patches, pos_enc, order)
 
     def _select_aten(self, patches, pos_enc):
         """The reference's loop on stock ATen ops (CPU plumbing path)."""

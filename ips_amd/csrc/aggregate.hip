@@ -210,7 +210,8 @@ __global__ __launch_bounds__(64) void head_kernel(const float* __restrict__ emb,
 
 // conv_nhwc.hip
 int conv_nhwc_impl(const ipsx_conv* cv, const float* x, const float* residual, const float* row_stats, float* y,
-                   int64_t n, int h, int w, int relu, void* stream, int* ready = nullptr, int ready_value = 0);
+                   int64_t n, int h, int w, int relu, void* stream, int* ready = nullptr, int ready_value = 0,
+                   const int32_t* index = nullptr, int64_t src_rows = 0);
 
 constexpr size_t kAggLdsLimit = 160 * 1024;
 
@@ -267,6 +268,18 @@ IPSX_API int ipsx_projector_apply_publish(const ipsx_conv* lin, const float* x, 
     IPSX_REQUIRE(lin && x && out && stats && ready && n > 0 && lin->colsum, "projector_apply_publish: bad arguments");
     IPSX_REQUIRE(lin->kh == 1 && lin->kw == 1 && lin->stride == 1 && lin->pad == 0, "projector: lin must be 1x1");
     return conv_nhwc_impl(lin, x, nullptr, stats, out, n, 1, 1, 1, stream, ready, value);
+}
+
+// out[j] = the projector's row of source row index[j] of the (src_rows, F) tensor x; stats[j]: ipsx_projector_stats_indexed
+// through the same index.  ready (or NULL): as in ipsx_projector_apply_publish.
+IPSX_API int ipsx_projector_apply_indexed(const ipsx_conv* lin, const float* x, const int32_t* index, int64_t src_rows, int64_t n,
+                                          const float* stats, float* out, int32_t* ready, int32_t value, void* stream) {
+    IPSX_REQUIRE(lin && x && index && out && stats && src_rows > 0 && n >= 0 && (n > 0 || !ready) && lin->colsum,
+                 "projector_apply_indexed: bad arguments");
+    IPSX_REQUIRE(lin->kh == 1 && lin->kw == 1 && lin->stride == 1 && lin->pad == 0, "projector: lin must be 1x1");
+    IPSX_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0, "projector_apply_indexed: rows must start at 16-byte addresses");
+    if (n == 0) return IPSX_OK;
+    return conv_nhwc_impl(lin, x, nullptr, stats, out, n, 1, 1, 1, stream, ready, value, index, src_rows);
 }
 
 IPSX_API int ipsx_projector(const ipsx_conv* lin, const float* x, int64_t n, float ln_eps, float* out,

@@ -52,6 +52,8 @@ struct NhwcArgs {
     const float* colsum;   // NORM kernels: column sums of the weights, one per output channel (ipsx_weight_colsum)
     int* ready;            // NORM kernels, optional: *ready = ready_value by the first thread (see ipsx_projector_apply_publish)
     int ready_value;
+    const int* index;      // IDX kernels (NORM only): output row m reads source row index[m] of x; stats and y stay in output order
+    long long src_rows;
 };
 
 template <int NTW>
@@ -61,6 +63,13 @@ struct NhwcStage {
 
 __device__ __forceinline__ f32x4 bufload(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
+}
+
+// Row-indexed Linear kernels (IDX): a gathered row is 4-8 KB of contiguous memory, so only its BASE differs - but the rows
+// of one tile may lie anywhere in a tensor of many GB, beyond what one buffer descriptor's 32-bit offsets reach: the A
+// operand comes through a 64-bit pointer per lane (row base + this half's 16 bytes), the k-group offset is added per load.
+__device__ __forceinline__ f32x4 rowload(const float* rowp, int kgroup) {
+    return *reinterpret_cast<const f32x4*>(rowp + 8 * kgroup);
 }
 
 template <int NTW>
@@ -109,8 +118,9 @@ __device__ __forceinline__ unsigned nhwc_voff(const NhwcArgs& a, const NhwcPixel
 // NTW: n-tiles (32 output channels each) per wave - 2 (wave tile 64 x 64) or 4 (64 x 128: half the activation loads
 // and half the NORM arithmetic per MFMA, and with 4 waves along N a workgroup covers 512 output channels, so very
 // wide layers read every activation row once); 8 * NTW MFMAs and 2 + NTW loads per stage.
-template <int WM, int WN, bool NORM, int NTW>
+template <int WM, int WN, bool NORM, int NTW, bool IDX = false>
 __global__ __launch_bounds__(256, 2) void conv_nhwc_kernel(NhwcArgs a) {
+    static_assert(NORM || !IDX, "row-indexed: the Linear layers only");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5;
     const int wm = __builtin_amdgcn_readfirstlane(wave % WM), wn = __builtin_amdgcn_readfirstlane(wave / WM);
     if (NORM && a.ready && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
@@ -140,12 +150,20 @@ __global__ __launch_bounds__(256, 2) void conv_nhwc_kernel(NhwcArgs a) {
     // prefetch stream state: stage gp = (tap pt, k-group pc); pv0/pv1 = pixel offsets of tap pt
     int gp = 0, pt = 0, pc = 0;
     unsigned pv0 = nhwc_voff(a, p0, 0, half), pv1 = nhwc_voff(a, p1, 0, half);
+    // IDX: the source rows of this lane's two output rows (rows past the end read the last one's, are never stored)
+    const float* pa0 = a.x;
+    const float* pa1 = a.x;
+    if (IDX) {
+        const unsigned last = a.m_total - 1;
+        pa0 = a.x + (size_t)source_row(a.index, min(m_base + (lane & 31), last), a.src_rows) * a.c_in + 4 * half;
+        pa1 = a.x + (size_t)source_row(a.index, min(m_base + 32 + (lane & 31), last), a.src_rows) * a.c_in + 4 * half;
+    }
     NhwcStage<NTW> s0, s1, s2, s3;       // (s3: ring of 4 only)
 #define NHWC_ISSUE(S)                                                       \
     do {                                                                    \
         const unsigned ca = (unsigned)pc * 32u, cb = (unsigned)gp * 1024u;  \
-        S.a0 = bufload(rx, pv0, ca);                                        \
-        S.a1 = bufload(rx, pv1, ca);                                        \
+        S.a0 = IDX ? rowload(pa0, pc) : bufload(rx, pv0, ca);               \
+        S.a1 = IDX ? rowload(pa1, pc) : bufload(rx, pv1, ca);               \
         _Pragma("unroll") for (int t = 0; t < NTW; ++t) S.b[t] = bufload(rw, lb, wb[t] + cb); \
     } while (0)
 #define NHWC_ADVANCE()                                                      \
@@ -258,7 +276,8 @@ __global__ __launch_bounds__(256, 2) void conv_nhwc_kernel(NhwcArgs a) {
                 const int n = nt0 * 32 + c;
                 if (n >= a.c_out) continue;
                 const size_t idx = (size_t)m * a.c_out + n;
-                float v = centred_row_dot(a.x + (size_t)m * a.c_in, st.x, a.wp, a.kgs, n) * -st.y;
+                const size_t srow = IDX ? (size_t)source_row(a.index, m, a.src_rows) : (size_t)m;
+                float v = centred_row_dot(a.x + srow * a.c_in, st.x, a.wp, a.kgs, n) * -st.y;
                 if (a.alpha) v = __builtin_fmaf(v, a.alpha[n], a.shift ? a.shift[n] : 0.0f);
                 else if (a.shift) v = v + a.shift[n];
                 if (a.res) v = v + a.res[idx];
@@ -313,6 +332,8 @@ struct StreamArgs {
     int* ctl;                      // [0] next unit to hand out, [1] first unpublished unit; [2 ...] one flag per unit
     int* ready;                    // rows published, per slide (ipsx_scan_persistent's progress words)
     unsigned long long* stamps;    // diagnostic (ipsx_dbg_projector_stream_stamps): cycles per phase, summed by workgroup 0
+    const int* index;              // IDX kernels: row j of the stream is source row index[j] of x (emb, logits, units, ready: in j)
+    long long src_rows;
 };
 
 // The last few units of a launch - what is left when every workgroup has had its whole share: 2,048 units on 255 compute
@@ -347,16 +368,19 @@ __device__ __forceinline__ void bufstore(__amdgpu_buffer_rsrc_t r, f32x4 v, unsi
 
 // The rows of a tile that the statistics mark as centred (ipsx_rowstats.h), again, on the centred row: columns [c0, c0 +
 // ncol) into the LDS copy of the tile.  Not inlined: a rare path that must not cost the tile's GEMM registers.
+template <bool IDX>
 __device__ __attribute__((noinline)) void stream_centred_rows(const float* __restrict__ x, const float* __restrict__ wp,
                                                               const float* __restrict__ alpha, const float* __restrict__ shift,
                                                               int relu, int c_in, int kgs, unsigned n, unsigned row0, int c0,
                                                               int ncol, float* tile, const float2* s_stats,
-                                                              unsigned long long todo) {
+                                                              unsigned long long todo, const int* __restrict__ index = nullptr,
+                                                              long long src_rows = 0) {
     while (todo) {
         const int lr = __builtin_ctzll(todo);
         todo &= todo - 1;
         const float2 st = s_stats[lr];
-        const float* xrow = x + (size_t)min(row0 + (unsigned)lr, n - 1) * c_in;
+        const unsigned orow = min(row0 + (unsigned)lr, n - 1);
+        const float* xrow = x + (IDX ? (size_t)source_row(index, orow, src_rows) : (size_t)orow) * c_in;
         for (int c = threadIdx.x; c < ncol; c += 256) {
             const int nn = c0 + c;
             float v = centred_row_dot(xrow, st.x, wp, kgs, nn) * -st.y;
@@ -372,7 +396,7 @@ __device__ __attribute__((noinline)) void stream_centred_rows(const float* __res
 // through its MFMAs, so the 64-row tile's two blocks are shared out by wavefront parity (4 instead of 8 packed VALU
 // instructions per stage: each costs matrix-pipe time) and meet in the LDS; every row's sums are still ONE wavefront's
 // chains in the contract's order.
-template <int MT, int NTW, int MB, bool STAMP>
+template <int MT, int NTW, int MB, bool STAMP, bool IDX = false>
 __device__ __forceinline__ void stream_tile(const StreamArgs& a, unsigned row0, int part, unsigned split_unit, float* tile,
                                             float2* s_stats) {
     static_assert(NTW == 4 || MT == 1, "column parts are 32-row tiles");
@@ -397,6 +421,10 @@ __device__ __forceinline__ void stream_tile(const StreamArgs& a, unsigned row0, 
         const unsigned lr = mt * 32 + i, row = row0 + lr;
         pv[mt] = row < a.n ? (lr * (unsigned)a.c_in + 4u * half) * 4u : kOob;      // (no such row: zeros, never stored)
     }
+    const float* pa[MT];                                           // IDX: this lane's source rows (no such row: the last one's)
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+        pa[mt] = IDX ? a.x + (size_t)source_row(a.index, min(row0 + mt * 32u + (unsigned)i, a.n - 1), a.src_rows) * a.c_in + 4 * half : a.x;
     const unsigned lb = lane * 16u;
     unsigned wb[NTW];
 #pragma unroll
@@ -416,7 +444,7 @@ __device__ __forceinline__ void stream_tile(const StreamArgs& a, unsigned row0, 
 #define ST_ISSUE(S)                                                                        \
     do {                                                                                   \
         const unsigned ca = (unsigned)gp * 32u, cb = (unsigned)gp * 1024u;                 \
-        _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) S.a[mt] = bufload(rx, pv[mt], ca); \
+        _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) S.a[mt] = IDX ? rowload(pa[mt], gp) : bufload(rx, pv[mt], ca); \
         _Pragma("unroll") for (int t = 0; t < NTW; ++t) S.b[t] = bufload(rw, lb, wb[t] + cb); \
         if (gp + 1 < total) ++gp;                                                          \
     } while (0)
@@ -465,7 +493,7 @@ __device__ __forceinline__ void stream_tile(const StreamArgs& a, unsigned row0, 
     //  on the centred row below - ipsx_rowstats.h; never on well-conditioned features)
     {
         const unsigned mrow = min(row0 + MB * 32u + (unsigned)i, a.n - 1);
-        const float2 st = rm_finish(mom, a.c_in, a.eps, lane, a.x + (size_t)mrow * a.c_in + 4 * half);
+        const float2 st = rm_finish(mom, a.c_in, a.eps, lane, IDX ? pa[MB] : a.x + (size_t)mrow * a.c_in + 4 * half);
         if (lane < 32) s_stats[MB * 32 + i] = st;
     }
     __syncthreads();
@@ -506,8 +534,8 @@ __device__ __forceinline__ void stream_tile(const StreamArgs& a, unsigned row0, 
     }
     __syncthreads();
     if (centred_rows != 0ull) {                                    // workgroup-uniform (every wave read the same statistics); rare
-        stream_centred_rows(a.x, a.wp, a.alpha, a.shift, a.relu, a.c_in, a.kgs, a.n, row0, part * (16 / P) * 32, 4 * NTW * 32,
-                            tile, s_stats, centred_rows);
+        stream_centred_rows<IDX>(a.x, a.wp, a.alpha, a.shift, a.relu, a.c_in, a.kgs, a.n, row0, part * (16 / P) * 32, 4 * NTW * 32,
+                                 tile, s_stats, centred_rows, a.index, a.src_rows);
         __syncthreads();
     }
     ST_STAMP(3);
@@ -592,7 +620,7 @@ __device__ __forceinline__ void stream_tile(const StreamArgs& a, unsigned row0, 
     ST_STAMP(4);
 }
 
-template <bool STAMP>
+template <bool STAMP, bool IDX = false>
 __global__ __launch_bounds__(256, 1) void projector_stream_kernel(StreamArgs a) {
     extern __shared__ __attribute__((aligned(16))) float st_lds[];
     float* tile = st_lds;
@@ -635,11 +663,11 @@ __global__ __launch_bounds__(256, 1) void projector_stream_kernel(StreamArgs a) 
         if (u0 >= a.n_units) break;                                 // workgroup-uniform
         const int units = (take == 2 && u0 + 1 < a.n_units) ? 2 : 1;
         if (part >= 0)      // (hand-over slots: the last units' [0, SPLIT_TAIL), the first units' behind them)
-            stream_tile<1, 4 / SPLIT_P, 0, STAMP>(a, u0 * 32u, part, u0 >= a.split_start ? u0 - a.split_start : SPLIT_TAIL + u0, tile, s_stats);
+            stream_tile<1, 4 / SPLIT_P, 0, STAMP, IDX>(a, u0 * 32u, part, u0 >= a.split_start ? u0 - a.split_start : SPLIT_TAIL + u0, tile, s_stats);
         else if (units == 2) {
-            if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) stream_tile<2, 4, 1, STAMP>(a, u0 * 32u, 0, 0u, tile, s_stats);
-            else stream_tile<2, 4, 0, STAMP>(a, u0 * 32u, 0, 0u, tile, s_stats);
-        } else stream_tile<1, 4, 0, STAMP>(a, u0 * 32u, 0, 0u, tile, s_stats);
+            if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) stream_tile<2, 4, 1, STAMP, IDX>(a, u0 * 32u, 0, 0u, tile, s_stats);
+            else stream_tile<2, 4, 0, STAMP, IDX>(a, u0 * 32u, 0, 0u, tile, s_stats);
+        } else stream_tile<1, 4, 0, STAMP, IDX>(a, u0 * 32u, 0, 0u, tile, s_stats);
         // ---- publish: the tile's logits have been written through (stream_tile); one release fence, then relaxed atomics.
         // (The embeddings are ordinary stores: nothing reads them before the launch is over.)  The first wavefront sets
         // the flags of this tile's units, reads the cursor - the first unpublished unit - and the 64 flags from there on
@@ -735,7 +763,8 @@ using namespace ipsx;
 
 namespace ipsx {
 int conv_nhwc_impl(const ipsx_conv* cv, const float* x, const float* residual, const float* row_stats, float* y,
-                   int64_t n, int h, int w, int relu, void* stream, int* ready = nullptr, int ready_value = 0);
+                   int64_t n, int h, int w, int relu, void* stream, int* ready = nullptr, int ready_value = 0,
+                   const int32_t* index = nullptr, int64_t src_rows = 0);
 }
 
 IPSX_API int ipsx_conv2d_affine_nhwc(const ipsx_conv* cv, const float* x, const float* residual, float* y,
@@ -745,11 +774,13 @@ IPSX_API int ipsx_conv2d_affine_nhwc(const ipsx_conv* cv, const float* x, const 
 
 // row_stats != null: the LayerNorm of the x rows is folded into the epilogue ((mean, rstd) per row; 1x1 convolution on 1x1 maps)
 int ipsx::conv_nhwc_impl(const ipsx_conv* cv, const float* x, const float* residual, const float* row_stats, float* y,
-                         int64_t n, int h, int w, int relu, void* stream, int* ready, int ready_value) {
+                         int64_t n, int h, int w, int relu, void* stream, int* ready, int ready_value, const int32_t* index,
+                         int64_t src_rows) {
     IPSX_REQUIRE(cv && cv->w_packed && x && y && n >= 0 && h > 0 && w > 0, "conv2d_affine_nhwc: bad arguments");
     IPSX_REQUIRE(!row_stats || (cv->kh == 1 && cv->kw == 1 && cv->pad == 0 && cv->stride == 1 && h == 1 && w == 1 && cv->colsum),
                  "conv2d_affine_nhwc: row statistics go with a Linear layer (1x1 convolution on rows) that carries its column sums");
     IPSX_REQUIRE(cv->c_in % 32 == 0, "conv2d_affine_nhwc: C_in = %d is not a multiple of 32", cv->c_in);
+    IPSX_REQUIRE(!index || (row_stats && src_rows > 0), "conv2d_affine_nhwc: a row index goes with a Linear layer's row statistics");
     if (n == 0) return IPSX_OK;
     const int ho = conv_out(h, cv->kh, cv->stride, cv->pad), wo = conv_out(w, cv->kw, cv->stride, cv->pad);
     IPSX_REQUIRE(ho > 0 && wo > 0, "conv2d_affine_nhwc: empty output");
@@ -764,7 +795,10 @@ int ipsx::conv_nhwc_impl(const ipsx_conv* cv, const float* x, const float* resid
     for (int64_t i0 = 0; i0 < n; i0 += per) {
         const int64_t cnt = std::min(per, n - i0);
         NhwcArgs a;
-        a.x = x + (size_t)i0 * h * w * cv->c_in;
+        // (row-indexed: every launch reads the WHOLE source tensor through its own part of the index - 64-bit row bases)
+        a.x = index ? x : x + (size_t)i0 * h * w * cv->c_in;
+        a.index = index ? index + i0 : nullptr;
+        a.src_rows = src_rows;
         a.y = y + (size_t)i0 * howo * cv->c_out;
         a.res = residual ? residual + (size_t)i0 * howo * cv->c_out : nullptr;
         a.wp = cv->w_packed; a.alpha = cv->alpha; a.shift = cv->shift;
@@ -781,7 +815,24 @@ int ipsx::conv_nhwc_impl(const ipsx_conv* cv, const float* x, const float* resid
         const unsigned mt64 = (unsigned)cdiv(a.m_total, 64), nt64 = (unsigned)cdiv(cv->c_out, 64);
         hipStream_t s = as_stream(stream);
         const unsigned nt128 = (unsigned)cdiv(cv->c_out, 128);
-        if (row_stats) {
+        if (row_stats && index) {
+            // the row-indexed projector: the three shapes of the plain one below, the same choice for the same row count
+            const size_t lds_pad = 96 * 1024;
+            const bool big = cv->c_out >= 512 && mt64 > 127;
+            const unsigned wgs = big ? mt64 * (unsigned)cdiv(nt128, 4) : mt64 * (unsigned)cdiv(nt64, 4);
+            const size_t lds = (cv->c_out >= 256 && wgs <= 256) ? lds_pad : 0;
+            if (big) {
+                if (lds) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_nhwc_kernel<1, 4, true, 4, true>),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pad);
+                conv_nhwc_kernel<1, 4, true, 4, true><<<dim3(mt64, (unsigned)cdiv(nt128, 4)), dim3(256), lds, s>>>(a);
+            } else if (cv->c_out >= 256) {
+                if (lds) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_nhwc_kernel<1, 4, true, 2, true>),
+                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pad);
+                conv_nhwc_kernel<1, 4, true, 2, true><<<dim3(mt64, (unsigned)cdiv(nt64, 4)), dim3(256), lds, s>>>(a);
+            }
+            else
+                conv_nhwc_kernel<2, 2, true, 2, true><<<dim3((unsigned)cdiv(mt64, 2), (unsigned)cdiv(nt64, 2)), dim3(256), 0, s>>>(a);
+        } else if (row_stats) {
             // Linear layers with LayerNorm in the operand load (projector): wave tile 64 x 128, a workgroup = 64 rows x 512
             // columns.  A launch is as long as ONE workgroup takes, however few there are: one that would leave half the
             // compute units idle anyway (<= 127 row tiles) runs as twice as many workgroups of 64 rows x 256 columns (wave
@@ -870,9 +921,9 @@ IPSX_API int ipsx_projector_stream_supported(const ipsx_conv* lin, int64_t n, in
     return n < ((int64_t)1 << 31) - 64 ? 1 : 0;
 }
 
-IPSX_API int ipsx_projector_stream(const ipsx_conv* lin, const float* x, int64_t n, int64_t slide_rows, float ln_eps, float* emb,
-                                   const float* v_packed, int r, float* logits, int32_t* ctl, int32_t* ready,
-                                   int workgroups, int short_first, void* stream) {
+static int projector_stream_impl(const ipsx_conv* lin, const float* x, const int32_t* index, int64_t src_rows, int64_t n,
+                                 int64_t slide_rows, float ln_eps, float* emb, const float* v_packed, int r, float* logits,
+                                 int32_t* ctl, int32_t* ready, int workgroups, int short_first, void* stream) {
     IPSX_REQUIRE(lin && x && emb && v_packed && logits && ctl && ready, "projector_stream: bad arguments");
     IPSX_REQUIRE(slide_rows > 0 && n % slide_rows == 0 && (n == slide_rows || slide_rows % 32 == 0),
                  "projector_stream: %lld rows are not whole slides of %lld rows (a multiple of 32 when there are several)",
@@ -887,7 +938,8 @@ IPSX_API int ipsx_projector_stream(const ipsx_conv* lin, const float* x, int64_t
     a.c_in = lin->c_in; a.c_out = lin->c_out; a.eps = ln_eps;
     a.emb = emb; a.vp = v_packed; a.R = r; a.vkgs = lin->c_out / 8; a.logits = logits;
     a.n = (unsigned)n; a.n_units = (unsigned)ipsx::cdiv(n, 32); a.slide_rows = (unsigned)slide_rows;
-    a.ctl = ctl; a.ready = ready; a.stamps = g_stream_stamps;
+    a.ctl = ctl; a.ready = ready; a.stamps = index ? nullptr : g_stream_stamps;      // (the phase stamps: the plain kernel's diagnostic)
+    a.index = index; a.src_rows = src_rows;
     int cus = 256, dev = 0;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
     // 7 of the 8 compute units of every shader engine: the resident loop's unit is then free wherever the dispatcher
@@ -934,11 +986,32 @@ IPSX_API int ipsx_projector_stream(const ipsx_conv* lin, const float* x, int64_t
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)ipsx::ST_LDS);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ipsx::projector_stream_kernel<true>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)ipsx::ST_LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ipsx::projector_stream_kernel<false, true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)ipsx::ST_LDS);
         attr = true;
     }
-    if (a.stamps)
+    if (index)
+        ipsx::projector_stream_kernel<false, true><<<dim3((unsigned)wgs), dim3(256), ipsx::ST_LDS, ipsx::as_stream(stream)>>>(a);
+    else if (a.stamps)
         ipsx::projector_stream_kernel<true><<<dim3((unsigned)wgs), dim3(256), ipsx::ST_LDS, ipsx::as_stream(stream)>>>(a);
     else
         ipsx::projector_stream_kernel<false><<<dim3((unsigned)wgs), dim3(256), ipsx::ST_LDS, ipsx::as_stream(stream)>>>(a);
     return ipsx::launched("projector_stream");
+}
+
+IPSX_API int ipsx_projector_stream(const ipsx_conv* lin, const float* x, int64_t n, int64_t slide_rows, float ln_eps, float* emb,
+                                   const float* v_packed, int r, float* logits, int32_t* ctl, int32_t* ready,
+                                   int workgroups, int short_first, void* stream) {
+    return projector_stream_impl(lin, x, nullptr, 0, n, slide_rows, ln_eps, emb, v_packed, r, logits, ctl, ready, workgroups,
+                                 short_first, stream);
+}
+
+// Row j of the stream is source row index[j] of the (src_rows, c_in) tensor x: the bits of ipsx_projector_stream run on x[index]
+IPSX_API int ipsx_projector_stream_indexed(const ipsx_conv* lin, const float* x, const int32_t* index, int64_t src_rows, int64_t n,
+                                           int64_t slide_rows, float ln_eps, float* emb, const float* v_packed, int r,
+                                           float* logits, int32_t* ctl, int32_t* ready, int workgroups, int short_first,
+                                           void* stream) {
+    IPSX_REQUIRE(index && src_rows > 0, "projector_stream_indexed: an index into src_rows > 0 source rows is needed");
+    return projector_stream_impl(lin, x, index, src_rows, n, slide_rows, ln_eps, emb, v_packed, r, logits, ctl, ready, workgroups,
+                                 short_first, stream);
 }

@@ -31,13 +31,23 @@ struct FinishArgs {
     uint4* out_patch; uint4* out_pos;
     const int* status; int* status_host;
     int m;
+    const long long* order; long long order_bstride;      // ORDER kernels: patch row r of image b is source row order[b][r]
 };
 
+// ORDER: the selection ran on a permuted NUMBERING of the patches (a shuffle applied as an index, not as a copy): the patch
+// row comes from the unshuffled tensor through the permutation; the positional rows (shuffled by copy) and the returned
+// indices stay in the loop's numbering.
+template <bool ORDER>
 __global__ __launch_bounds__(256) void ips_finish_kernel(FinishArgs a) {
     const int j = blockIdx.x, b = blockIdx.y;
     const long long raw = a.idx[(size_t)b * a.m + j];
     const long long r = raw < 0 ? 0 : (raw >= a.n_rows ? a.n_rows - 1 : raw);         // never read out of bounds
-    const uint4* s = a.patches + ((size_t)b * a.patch_bstride_rows + (size_t)r) * a.patch_units;
+    long long rs = r;
+    if (ORDER) {
+        rs = a.order[(size_t)b * a.order_bstride + r];
+        rs = rs < 0 ? 0 : (rs >= a.n_rows ? a.n_rows - 1 : rs);
+    }
+    const uint4* s = a.patches + ((size_t)b * a.patch_bstride_rows + (size_t)rs) * a.patch_units;
     uint4* d = a.out_patch + ((size_t)b * a.m + j) * a.patch_units;
     for (long long i = threadIdx.x; i < a.patch_units; i += 256) d[i] = s[i];
     if (a.pos) {
@@ -57,10 +67,10 @@ __global__ __launch_bounds__(256) void ips_finish_kernel(FinishArgs a) {
 
 using namespace ipsx;
 
-IPSX_API int ipsx_ips_finish(const void* patches, int64_t patch_row_bytes, int64_t patch_bstride_rows, int64_t n_rows,
-                             const void* pos, int64_t pos_row_bytes, int64_t pos_bstride_rows, const int64_t* mem_idx, int b, int m,
-                             void* mem_patch, void* mem_pos, int64_t* mem_idx_out, const int32_t* status, int32_t* status_host,
-                             void* stream) {
+static int ips_finish_impl(const void* patches, int64_t patch_row_bytes, int64_t patch_bstride_rows, int64_t n_rows,
+                           const void* pos, int64_t pos_row_bytes, int64_t pos_bstride_rows, const int64_t* mem_idx, int b, int m,
+                           void* mem_patch, void* mem_pos, int64_t* mem_idx_out, const int32_t* status, int32_t* status_host,
+                           const int64_t* order, int64_t order_bstride, void* stream) {
     IPSX_REQUIRE(patches && mem_idx && mem_patch && mem_idx_out && b > 0 && m > 0 && n_rows > 0, "ips_finish: bad arguments");
     IPSX_REQUIRE(patch_row_bytes > 0 && patch_row_bytes % 16 == 0 && (reinterpret_cast<uintptr_t>(patches) & 15) == 0 &&
                  (reinterpret_cast<uintptr_t>(mem_patch) & 15) == 0, "ips_finish: patch rows of 16-byte units at 16-byte addresses");
@@ -74,8 +84,30 @@ IPSX_API int ipsx_ips_finish(const void* patches, int64_t patch_row_bytes, int64
     a.idx = reinterpret_cast<const long long*>(mem_idx); a.idx_out = reinterpret_cast<long long*>(mem_idx_out);
     a.out_patch = static_cast<uint4*>(mem_patch); a.out_pos = static_cast<uint4*>(mem_pos);
     a.status = status; a.status_host = status_host; a.m = m;
-    ips_finish_kernel<<<dim3((unsigned)m, (unsigned)b), dim3(256), 0, as_stream(stream)>>>(a);
+    a.order = reinterpret_cast<const long long*>(order); a.order_bstride = order_bstride;
+    if (order) ips_finish_kernel<true><<<dim3((unsigned)m, (unsigned)b), dim3(256), 0, as_stream(stream)>>>(a);
+    else ips_finish_kernel<false><<<dim3((unsigned)m, (unsigned)b), dim3(256), 0, as_stream(stream)>>>(a);
     return launched("ips_finish");
+}
+
+IPSX_API int ipsx_ips_finish(const void* patches, int64_t patch_row_bytes, int64_t patch_bstride_rows, int64_t n_rows,
+                             const void* pos, int64_t pos_row_bytes, int64_t pos_bstride_rows, const int64_t* mem_idx, int b, int m,
+                             void* mem_patch, void* mem_pos, int64_t* mem_idx_out, const int32_t* status, int32_t* status_host,
+                             void* stream) {
+    return ips_finish_impl(patches, patch_row_bytes, patch_bstride_rows, n_rows, pos, pos_row_bytes, pos_bstride_rows, mem_idx, b, m,
+                           mem_patch, mem_pos, mem_idx_out, status, status_host, nullptr, 0, stream);
+}
+
+// ipsx_ips_finish after a selection on shuffled NUMBERING: mem_patch[b][j] = patches[b][order[b][mem_idx[b][j]]] from the
+// UNSHUFFLED tensor (order: (b or 1, n_rows) int64, order_bstride = n_rows or 0 for one permutation shared by every image);
+// mem_pos and mem_idx_out as in ipsx_ips_finish.
+IPSX_API int ipsx_ips_finish_indexed(const void* patches, int64_t patch_row_bytes, int64_t patch_bstride_rows, int64_t n_rows,
+                                     const void* pos, int64_t pos_row_bytes, int64_t pos_bstride_rows, const int64_t* mem_idx,
+                                     const int64_t* order, int64_t order_bstride, int b, int m, void* mem_patch, void* mem_pos,
+                                     int64_t* mem_idx_out, const int32_t* status, int32_t* status_host, void* stream) {
+    IPSX_REQUIRE(order && (order_bstride == 0 || order_bstride == n_rows), "ips_finish_indexed: order is (b or 1, n_rows)");
+    return ips_finish_impl(patches, patch_row_bytes, patch_bstride_rows, n_rows, pos, pos_row_bytes, pos_bstride_rows, mem_idx, b, m,
+                           mem_patch, mem_pos, mem_idx_out, status, status_host, order, order_bstride, stream);
 }
 
 IPSX_API int ipsx_gather_rows(const void* src, const int64_t* idx, void* dst, int b, int64_t n_rows, int m,

@@ -38,6 +38,13 @@ __device__ __forceinline__ float2 row_stats_wave(const float* __restrict__ xr, i
     return make_float2(mean, rstd);
 }
 
+// Row-indexed projector kernels (output row j is computed from source row index[j]): the source row, clamped into the
+// tensor - a bad index never reads out of bounds.  Callers multiply by the row length in 64 bits.
+__device__ __forceinline__ long long source_row(const int* __restrict__ index, long long j, long long src_rows) {
+    const long long r = index[j];
+    return r < 0 ? 0 : (r >= src_rows ? src_rows - 1 : r);
+}
+
 // ---- the projector's moments (see the header comment): per lane the four j-chains of its half of the row
 typedef float rm_f32x2 __attribute__((ext_vector_type(2)));
 typedef float rm_f32x4 __attribute__((ext_vector_type(4)));
@@ -168,13 +175,10 @@ __device__ __forceinline__ float centred_row_dot(const float* __restrict__ xrow,
     return acc;
 }
 
-// the moments of rows row0 .. row0 + 31 (those below n) by one wavefront: lane l -> row row0 + (l & 31), half l >> 5;
-// d % 8 == 0.  Eight 16-byte (float) or 8-byte (float16 / bfloat16) loads in flight per lane.
+// the moments of ONE row by the two lanes that hold its halves: p = the row + 4 * half (row_moments_wave32 below: rows in
+// order; the row-indexed projector kernels: any row of the source tensor - only the row base differs)
 template <typename T>
-__device__ __forceinline__ float2 row_moments_wave32(const T* __restrict__ x, long long row0, long long n, int d, float eps,
-                                                     int lane) {
-    const long long row = row0 + (lane & 31);
-    const T* p = x + (size_t)(row < n ? row : n - 1) * d + 4 * (lane >> 5);
+__device__ __forceinline__ float2 row_moments_at(const T* __restrict__ p, int d, float eps, int lane) {
     RowMoments m;
     rm_zero(m);
     const int kgs = d >> 3;
@@ -188,6 +192,15 @@ __device__ __forceinline__ float2 row_moments_wave32(const T* __restrict__ x, lo
     }
     for (; g < kgs; ++g) rm_add(m, rm_load4(p + 8 * g));
     return rm_finish(m, d, eps, lane, p);
+}
+
+// the moments of rows row0 .. row0 + 31 (those below n) by one wavefront: lane l -> row row0 + (l & 31), half l >> 5;
+// d % 8 == 0.  Eight 16-byte (float) or 8-byte (float16 / bfloat16) loads in flight per lane.
+template <typename T>
+__device__ __forceinline__ float2 row_moments_wave32(const T* __restrict__ x, long long row0, long long n, int d, float eps,
+                                                     int lane) {
+    const long long row = row0 + (lane & 31);
+    return row_moments_at(x + (size_t)(row < n ? row : n - 1) * d + 4 * (lane >> 5), d, eps, lane);
 }
 
 }  // namespace ipsx

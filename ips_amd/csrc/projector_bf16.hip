@@ -45,6 +45,22 @@ __global__ __launch_bounds__(256) void row_moments_typed_kernel(const T* __restr
     if (lane < 32 && row0 + lane < n) stats[row0 + lane] = st;
 }
 
+// Row-indexed form (ipsx_projector_stats_indexed): stats[j] = the moments of source row index[j] - the bits of
+// row_moments_typed_kernel run on x[index]; only the row base differs, computed in 64 bits (a row number outside the
+// source tensor is clamped into it: never read out of bounds).
+template <typename T>
+__global__ __launch_bounds__(256) void row_moments_indexed_kernel(const T* __restrict__ x, const int* __restrict__ index,
+                                                                  long long src_rows, long long n, int d, float eps,
+                                                                  float2* __restrict__ stats) {
+    const int lane = threadIdx.x & 63;
+    const long long row0 = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 32;
+    if (row0 >= n) return;
+    const long long row = row0 + (lane & 31);
+    const long long src = source_row(index, row < n ? row : n - 1, src_rows);
+    const float2 st = row_moments_at(x + (size_t)src * d + 4 * (lane >> 5), d, eps, lane);
+    if (lane < 32 && row0 + lane < n) stats[row0 + lane] = st;
+}
+
 // eight consecutive stored values of one row, as loaded (widened at use, so the loads of the next k-step are in flight
 // while this one's MFMAs run)
 template <typename T> struct Raw8 { uint4 a; };
@@ -86,9 +102,11 @@ struct ProjBf16Args {
     float* out;                // (n, d)
     int* ready;                // optional: *ready = ready_value by the first thread (ipsx_projector_apply_publish)
     int ready_value;
+    const int* index;          // IDX kernels: output row j reads source row index[j] of x (stats and out stay in output order)
+    long long src_rows;
 };
 
-template <typename T, int NT, int MT>
+template <typename T, int NT, int MT, bool IDX>
 __global__ __launch_bounds__(256) void projector_bf16_kernel(ProjBf16Args a) {
     // (everything enqueued before this launch has completed and is visible - the stream order of two kernels - so the
     //  first thread can say so on behalf of a launch of its own)
@@ -105,7 +123,7 @@ __global__ __launch_bounds__(256) void projector_bf16_kernel(ProjBf16Args a) {
     for (int m = 0; m < MT; ++m) {
         const long long row = r0 + 32 * m + (lane & 31);
         const long long rc = row < a.n ? row : a.n - 1;             // rows past the end read the last one, write nothing
-        xp[m] = x + (size_t)rc * a.f + 8 * half;
+        xp[m] = x + (size_t)(IDX ? source_row(a.index, rc, a.src_rows) : rc) * a.f + 8 * half;
         mean[m] = a.stats[rc].x;
     }
     const uint4* wp = a.wp + (size_t)t0 * a.ksteps * 64 + lane;
@@ -172,14 +190,14 @@ __global__ __launch_bounds__(256) void projector_bf16_kernel(ProjBf16Args a) {
         }
 }
 
-template <typename T>
+template <typename T, bool IDX>
 static int launch_projector_bf16(const ProjBf16Args& a, hipStream_t s) {
     const int tiles = a.d / 32;
     const int nt = tiles % 4 == 0 ? 4 : (tiles % 2 == 0 ? 2 : 1);
     const dim3 block(256);
-    if (nt == 4) projector_bf16_kernel<T, 4, 2><<<dim3((unsigned)cdiv(a.n, 64), (unsigned)cdiv(tiles, 16)), block, 0, s>>>(a);
-    else if (nt == 2) projector_bf16_kernel<T, 2, 2><<<dim3((unsigned)cdiv(a.n, 64), (unsigned)cdiv(tiles, 8)), block, 0, s>>>(a);
-    else projector_bf16_kernel<T, 1, 2><<<dim3((unsigned)cdiv(a.n, 64), (unsigned)cdiv(tiles, 4)), block, 0, s>>>(a);
+    if (nt == 4) projector_bf16_kernel<T, 4, 2, IDX><<<dim3((unsigned)cdiv(a.n, 64), (unsigned)cdiv(tiles, 16)), block, 0, s>>>(a);
+    else if (nt == 2) projector_bf16_kernel<T, 2, 2, IDX><<<dim3((unsigned)cdiv(a.n, 64), (unsigned)cdiv(tiles, 8)), block, 0, s>>>(a);
+    else projector_bf16_kernel<T, 1, 2, IDX><<<dim3((unsigned)cdiv(a.n, 64), (unsigned)cdiv(tiles, 4)), block, 0, s>>>(a);
     return launched("projector_bf16");
 }
 
@@ -200,13 +218,29 @@ IPSX_API int ipsx_projector_stats_typed(const void* x, int dtype, int64_t n, int
     return launched("projector row moments (typed)");
 }
 
+IPSX_API int ipsx_projector_stats_indexed(const void* x, int dtype, const int32_t* index, int64_t src_rows, int64_t n, int f,
+                                          float ln_eps, float* stats, void* stream) {
+    IPSX_REQUIRE(dtype >= 0 && dtype <= 2, "projector_stats_indexed: dtype %d is not 0 (float32), 1 (bfloat16) or 2 (float16)", dtype);
+    IPSX_REQUIRE(x && index && stats && src_rows > 0 && n >= 0 && f > 0 && f % 8 == 0,
+                 "projector_stats_indexed: bad arguments (the row length is a multiple of 8)");
+    IPSX_REQUIRE(((uintptr_t)x & (dtype == 0 ? 15 : 7)) == 0, "projector_stats_indexed: rows must start at %d-byte addresses", dtype == 0 ? 16 : 8);
+    if (n == 0) return IPSX_OK;
+    const dim3 grid((unsigned)cdiv(n, 128)), block(256);
+    float2* st = reinterpret_cast<float2*>(stats);
+    hipStream_t s = as_stream(stream);
+    if (dtype == 0) row_moments_indexed_kernel<float><<<grid, block, 0, s>>>(static_cast<const float*>(x), index, src_rows, n, f, ln_eps, st);
+    else if (dtype == 1) row_moments_indexed_kernel<__bf16><<<grid, block, 0, s>>>(static_cast<const __bf16*>(x), index, src_rows, n, f, ln_eps, st);
+    else row_moments_indexed_kernel<_Float16><<<grid, block, 0, s>>>(static_cast<const _Float16*>(x), index, src_rows, n, f, ln_eps, st);
+    return launched("projector row moments (indexed)");
+}
+
 IPSX_API int ipsx_projector_bf16_supported(const ipsx_conv* lin) {
     return lin && lin->kh == 1 && lin->kw == 1 && lin->stride == 1 && lin->pad == 0 && lin->c_in > 0 && lin->c_in % 16 == 0 &&
            lin->c_out > 0 && lin->c_out % 32 == 0;
 }
 
-IPSX_API int ipsx_projector_apply_bf16(const ipsx_conv* lin, const void* x, int dtype, int64_t n, const float* stats, float* out,
-                                       int32_t* ready, int32_t ready_value, void* stream) {
+static int projector_apply_bf16_impl(const ipsx_conv* lin, const void* x, int dtype, const int32_t* index, int64_t src_rows,
+                                     int64_t n, const float* stats, float* out, int32_t* ready, int32_t ready_value, void* stream) {
     IPSX_REQUIRE(lin && x && out && stats && n >= 0 && (n > 0 || !ready), "projector_apply_bf16: bad arguments");
     IPSX_REQUIRE(dtype >= 0 && dtype <= 2, "projector_apply_bf16: dtype %d is not 0 (float32), 1 (bfloat16) or 2 (float16)", dtype);
     IPSX_REQUIRE(lin->kh == 1 && lin->kw == 1 && lin->stride == 1 && lin->pad == 0, "projector_apply_bf16: lin must be 1x1");
@@ -224,8 +258,26 @@ IPSX_API int ipsx_projector_apply_bf16(const ipsx_conv* lin, const void* x, int 
     a.stats = reinterpret_cast<const float2*>(stats);
     a.alpha = lin->alpha; a.shift = lin->shift; a.out = out;
     a.ready = ready; a.ready_value = ready_value;
+    a.index = index; a.src_rows = src_rows;
     hipStream_t s = as_stream(stream);
-    if (dtype == 0) return launch_projector_bf16<float>(a, s);
-    if (dtype == 1) return launch_projector_bf16<__bf16>(a, s);
-    return launch_projector_bf16<_Float16>(a, s);
+    if (index) {
+        if (dtype == 0) return launch_projector_bf16<float, true>(a, s);
+        if (dtype == 1) return launch_projector_bf16<__bf16, true>(a, s);
+        return launch_projector_bf16<_Float16, true>(a, s);
+    }
+    if (dtype == 0) return launch_projector_bf16<float, false>(a, s);
+    if (dtype == 1) return launch_projector_bf16<__bf16, false>(a, s);
+    return launch_projector_bf16<_Float16, false>(a, s);
+}
+
+IPSX_API int ipsx_projector_apply_bf16(const ipsx_conv* lin, const void* x, int dtype, int64_t n, const float* stats, float* out,
+                                       int32_t* ready, int32_t ready_value, void* stream) {
+    return projector_apply_bf16_impl(lin, x, dtype, nullptr, 0, n, stats, out, ready, ready_value, stream);
+}
+
+IPSX_API int ipsx_projector_apply_bf16_indexed(const ipsx_conv* lin, const void* x, int dtype, const int32_t* index, int64_t src_rows,
+                                               int64_t n, const float* stats, float* out, int32_t* ready, int32_t ready_value,
+                                               void* stream) {
+    IPSX_REQUIRE(index && src_rows > 0, "projector_apply_bf16_indexed: an index into src_rows > 0 source rows is needed");
+    return projector_apply_bf16_impl(lin, x, dtype, index, src_rows, n, stats, out, ready, ready_value, stream);
 }

@@ -240,6 +240,15 @@ _EXPORTS = {
     "ipsx_projector_bf16_supported": (C.c_int, [C.POINTER(Conv)]),
     "ipsx_projector_apply_bf16": (C.c_int, [C.POINTER(Conv), C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_int32, C.c_void_p]),
+    "ipsx_projector_stats_indexed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_float, C.c_void_p,
+                                               C.c_void_p]),
+    "ipsx_projector_apply_indexed": (C.c_int, [C.POINTER(Conv), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_int32, C.c_void_p]),
+    "ipsx_projector_apply_bf16_indexed": (C.c_int, [C.POINTER(Conv), C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ipsx_projector_stream_indexed": (C.c_int, [C.POINTER(Conv), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_float,
+                                                C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                C.c_void_p]),
     "ipsx_trunk_stream_ctl_words": (C.c_size_t, [C.c_int64]),
     "ipsx_trunk_stream_supported": (C.c_int, [C.POINTER(Trunk), C.c_int, C.c_int]),
     "ipsx_trunk_stream": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -301,6 +310,9 @@ _EXPORTS = {
     "ipsx_ips_call_elapsed": (C.c_int, [C.c_int, C.POINTER(C.c_float)]),
     "ipsx_ips_finish": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int,
                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ipsx_ips_finish_indexed": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                          C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
     "ipsx_aggregate_workspace_bytes": (C.c_size_t, [C.POINTER(Transf), C.c_int, C.c_int]),
     "ipsx_aggregate": (C.c_int, [C.POINTER(Transf), C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                  C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -792,9 +804,11 @@ def ips_finish_supported(src, pos):
     return p1.is_contiguous() and (pos.shape[2] * pos.element_size()) % 16 == 0 and pos.data_ptr() % 16 == 0
 
 
-def ips_finish(src, pos, idx_buf, status, status_host):
+def ips_finish(src, pos, idx_buf, status, status_host, order=None):
     """The end of an ``ips()`` call whose loop ran resident, ONE launch: ``src[b, idx[b, m]]``, ``pos[b, idx[b, m]]`` (or None),
     a fresh copy of the loop's index buffer, the loop's status word to its pinned host mirror (``ipsx_ips_finish``).
+    ``order`` ((B or 1, N) int64, contiguous, on the device): the loop ran on shuffled numbering - the patch rows are
+    ``src[b, order[b, idx[b, m]]]`` of the UNSHUFFLED ``src`` (``ipsx_ips_finish_indexed``), ``pos`` and the indices as before.
     -> (mem_idx, mem_patch, mem_pos)"""
     B, M = idx_buf.shape
     N = src.shape[1]
@@ -807,6 +821,14 @@ def ips_finish(src, pos, idx_buf, status, status_host):
         pos_bs = 0 if (pos.stride(0) == 0 or pos.shape[0] == 1) else pos.shape[1]
         pos_bytes = pos.shape[2] * pos.element_size()
         out_pos = torch.empty((B, M, pos.shape[2]), dtype=pos.dtype, device=pos.device)
+    if order is not None:
+        if order.dtype != torch.int64 or order.dim() != 2 or order.shape[1] != N or order.shape[0] not in (1, B) or \
+                not order.is_contiguous() or order.device != src.device:
+            raise ValueError("order must be a contiguous (B or 1, N) int64 tensor on the patches' device")
+        _ck(lib().ipsx_ips_finish_indexed(_p(src), row_bytes, N if src.shape[0] > 1 else 0, N, _p(pos), pos_bytes, pos_bs, _p(idx_buf),
+                                          _p(order), N if order.shape[0] > 1 else 0, B, M, _p(out), _p(out_pos), _p(idx), _p(status),
+                                          _p(status_host), _stream()), "ipsx_ips_finish_indexed")
+        return idx, out, out_pos
     _ck(lib().ipsx_ips_finish(_p(src), row_bytes, N if src.shape[0] > 1 else 0, N, _p(pos), pos_bytes, pos_bs, _p(idx_buf), B, M,
                               _p(out), _p(out_pos), _p(idx), _p(status), _p(status_host), _stream()), "ipsx_ips_finish")
     return idx, out, out_pos

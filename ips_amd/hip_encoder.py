@@ -79,7 +79,18 @@ class EncoderPlan:
                 self.lin.c_in, self.lin.c_out))
         return x if x.is_contiguous() else x.contiguous()
 
-    def _stats(self, x, out):
+    @staticmethod
+    def _index(index, x):
+        """A row index of the projector's indexed entry points: flat int32 row numbers into ``x`` (P, F), contiguous, on its device."""
+        if index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous() or index.device != x.device:
+            raise ValueError("index must be a contiguous 1-d int32 tensor on the rows' device")
+        return index
+
+    def _stats(self, x, out, index=None):
+        if index is not None:
+            _ck(lib().ipsx_projector_stats_indexed(_p(x), _PATCH_DTYPES[x.dtype], _p(index), x.shape[0], index.numel(), x.shape[1],
+                                                   C.c_float(self.ln_eps), _p(out), _stream()), "ipsx_projector_stats_indexed")
+            return out
         _ck(lib().ipsx_projector_stats_typed(_p(x), _PATCH_DTYPES[x.dtype], x.shape[0], x.shape[1], C.c_float(self.ln_eps),
                                              _p(out), _stream()), "ipsx_projector_stats_typed")
         return out
@@ -291,14 +302,18 @@ class EncoderPlan:
             self.trunk.patch_dtype = 0
         return out
 
-    def row_stats(self, x, out=None):
+    def row_stats(self, x, out=None, index=None):
         """(mean, rstd) of every feature row of ``x`` (P, F) -> (P, 2): the LayerNorm moments the projector's GEMM applies
-        to its operand; for callers that run this HBM-bound pass ahead of / beside the GEMM (``encode(x, stats=...)``)."""
+        to its operand; for callers that run this HBM-bound pass ahead of / beside the GEMM (``encode(x, stats=...)``).
+        ``index`` (n int32): of the rows ``x[index]`` -> (n, 2), read through the index - nothing is gathered."""
         self._refresh()
         x = self._features(x)
+        n = x.shape[0]
+        if index is not None:
+            n = self._index(index, x).numel()
         if out is None:
-            out = torch.empty((x.shape[0], 2), dtype=torch.float32, device=x.device)
-        return self._stats(x, out)
+            out = torch.empty((n, 2), dtype=torch.float32, device=x.device)
+        return self._stats(x, out, index)
 
     def image_stream_supported(self, x_shape, D, R):
         """Can ``image_stream`` encode patches of this shape (the fused fp32 1x32x32 trunk, 128 features, R <= 32)?"""
@@ -330,7 +345,7 @@ class EncoderPlan:
         self._refresh()
         return not self.bf16 and bool(lib().ipsx_projector_stream_supported(C.byref(self.lin), int(n), int(R)))
 
-    def stream(self, x, vq, R, emb, logits, ctl, ready, workgroups=0, short_first=-1, slide_rows=None):
+    def stream(self, x, vq, R, emb, logits, ctl, ready, workgroups=0, short_first=-1, slide_rows=None, index=None):
         """Projector + logits of the feature rows ``x`` (P, F) - one slide, or several one after the other, ``slide_rows``
         each - as one persistent launch that advances ``ready`` (the progress word(s) of ``scan_persistent``, one per
         slide) as rows complete: ``emb`` (P, 512) and ``logits`` (P, R) are the outputs, ``ctl`` =
@@ -344,6 +359,14 @@ class EncoderPlan:
         if x.dtype in (torch.float16, torch.bfloat16):
             raise TypeError("{} features need IPSX_PRECISION=bf16 (the projector stream reads float32)".format(x.dtype))
         x = _f32(x)
+        if index is not None:
+            # row j of the stream is x[index[j]] (``emb``, ``logits``, ``ready``: in j) - the bits of stream(x[index], ...)
+            n = self._index(index, x).numel()
+            x = x if x.is_contiguous() else x.contiguous()
+            _ck(lib().ipsx_projector_stream_indexed(C.byref(self.lin), _p(x), _p(index), x.shape[0], n, int(slide_rows or n),
+                                                    C.c_float(self.ln_eps), _p(emb), _p(vq), int(R), _p(logits), _p(ctl), _p(ready),
+                                                    int(workgroups), int(short_first), _stream()), "ipsx_projector_stream_indexed")
+            return emb
         _ck(lib().ipsx_projector_stream(C.byref(self.lin), _p(x), x.shape[0], int(slide_rows or x.shape[0]),
                                         C.c_float(self.ln_eps), _p(emb), _p(vq), int(R),
                                         _p(logits), _p(ctl), _p(ready), int(workgroups), int(short_first), _stream()),
@@ -359,17 +382,25 @@ class EncoderPlan:
         """... of which only the first this many have to be zero when a call starts."""
         return int(lib().ipsx_projector_stream_ctl_zero_words(int(n)))
 
-    def encode(self, x, nonblank=None, stats=None, out=None, publish=None):
+    def encode(self, x, nonblank=None, stats=None, out=None, publish=None, index=None):
         """(P, C, h, w) patches or (P, F) feature rows on the GPU  ->  (P, D) float32.  float32 input; patches also
         float16 / bfloat16 under IPSX_PRECISION=bf16 or fp32x3 (``_patches``), feature rows also float16 / bfloat16
         under IPSX_PRECISION=bf16, whose projector widens them in its operand load (``_features``).
 
         ``nonblank`` (P int32, 1 = the patch has a non-zero element; e.g. from ``patchify_sparse``) switches on
         the exact blank-patch dedup without the pass that looks for blank patches.  ``publish`` = (ready, value), with
-        ``stats``: the GEMM launch also does ``publish_rows(ready, value)`` for what was enqueued before it."""
+        ``stats``: the GEMM launch also does ``publish_rows(ready, value)`` for what was enqueued before it.
+
+        ``index`` (n int32, feature rows only): the embeddings of ``x[index]`` -> (n, D), read through the index by the
+        row-indexed kernels (``stats``, ``out`` and the result are in the index's order) - the bits of ``encode(x[index])``
+        without the gathered copy."""
         self._refresh()
         x = _patches(x) if self.is_image else self._features(x)
         n = x.shape[0]
+        if index is not None:
+            if self.is_image:
+                raise TypeError("a row index goes with feature rows (patches: encode_indexed)")
+            n = self._index(index, x).numel()
         if self.is_image and x.dtype != torch.float32 and (dedup_blank() or nonblank is not None):
             raise TypeError("blank-patch dedup reads float32 patches")
         if out is None:
@@ -415,12 +446,26 @@ class EncoderPlan:
         elif self.bf16:
             if stats is None:
                 ws = self._workspace(lib().ipsx_projector_workspace_bytes(n), x.device)
-                stats = self._stats(x, ws[:8 * n].view(torch.float32).view(n, 2))
+                stats = self._stats(x, ws[:8 * n].view(torch.float32).view(n, 2), index)
             elif stats.shape != (n, 2) or stats.dtype != torch.float32 or not stats.is_contiguous():
                 raise ValueError("stats must be a contiguous (P, 2) float32 tensor")
             ready, value = publish if publish is not None else (None, 0)
+            if index is not None:
+                _ck(lib().ipsx_projector_apply_bf16_indexed(C.byref(self.lin), _p(x), _PATCH_DTYPES[x.dtype], _p(index), x.shape[0], n,
+                                                            _p(stats), _p(out), _p(ready), int(value), _stream()),
+                    "ipsx_projector_apply_bf16_indexed")
+                return out
             _ck(lib().ipsx_projector_apply_bf16(C.byref(self.lin), _p(x), _PATCH_DTYPES[x.dtype], n, _p(stats), _p(out), _p(ready),
                                                 int(value), _stream()), "ipsx_projector_apply_bf16")
+        elif index is not None:
+            if stats is None:
+                ws = self._workspace(lib().ipsx_projector_workspace_bytes(n), x.device)
+                stats = self._stats(x, ws[:8 * n].view(torch.float32).view(n, 2), index)
+            elif stats.shape != (n, 2) or stats.dtype != torch.float32 or not stats.is_contiguous():
+                raise ValueError("stats must be a contiguous (P, 2) float32 tensor")
+            ready, value = publish if publish is not None else (None, 0)
+            _ck(lib().ipsx_projector_apply_indexed(C.byref(self.lin), _p(x), _p(index), x.shape[0], n, _p(stats), _p(out), _p(ready),
+                                                   int(value), _stream()), "ipsx_projector_apply_indexed")
         elif stats is not None:
             if stats.shape != (n, 2) or stats.dtype != torch.float32 or not stats.is_contiguous():
                 raise ValueError("stats must be a contiguous (P, 2) float32 tensor")

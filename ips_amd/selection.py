@@ -78,6 +78,12 @@ class Selection:
         self._calls = {}                           # hip.IpsCall structures, per pipeline
         self.timing_hook = None                    # callable(rows) -> slot of a library-owned event pair around the producer, or None
         self._part_index = None
+        self._order = None                         # the permutation this call selects through (an index, not a copy), or None
+        self._flat = None                          # ... as flat int32 row numbers b * N + perm[b, j], (B, N)
+        self._flat_key = None
+        self._flat_base = None
+        self._part_map = None                      # parts_with_ranges: where the parts' index lists lie in the flat (B, N) index
+        self.index_calls = 0                       # select() calls that read the patches through a shuffle index
 
     # ------------------------------------------------------------------ small helpers
     def plan(self):
@@ -163,11 +169,12 @@ class Selection:
         self._unfinished = mem_idx_buf
         return mem_idx_buf
 
-    def finish(self, src, pos):
+    def finish(self, src, pos, order=None):
         """The end of an ``ips()`` call whose loop ran resident, as ONE launch (``hip.ips_finish``: both gathers, a fresh copy
         of the selected indices, the loop's status word to its pinned host mirror) -> (mem_idx, mem_patch, mem_pos), or None
         when this call has nothing of the kind pending or the tensors' rows are not whole 16-byte units (the caller then
-        gathers itself and ``after_call`` mirrors the status word)."""
+        gathers itself and ``after_call`` mirrors the status word).  ``order``: the call selected through a shuffle index -
+        the patch rows come from the unshuffled ``src`` through it."""
         done, self._done = self._done, None
         if done is not None:
             return done
@@ -181,7 +188,7 @@ class Selection:
         if self.scan_status_host is None:
             self.scan_status_host = torch.zeros((1,), dtype=torch.int32).pin_memory()
         self._mirror_pending = None
-        return hip.ips_finish(src, pos, buf, status, self.scan_status_host)
+        return hip.ips_finish(src, pos, buf, status, self.scan_status_host, order=order)
 
     def take_unfinished(self, mem_idx):
         """``mem_idx`` as a tensor of the caller's own (the loop's buffer is overwritten by the next call)."""
@@ -272,11 +279,20 @@ class Selection:
             self.scan_status_host.copy_(status, non_blocking=True)
 
     # ------------------------------------------------------------------ which pipeline
-    def select(self, patches, pos_enc):
-        """(B, N, ...) patches (device, or host for lazy loading) -> mem_idx (B, M) int64 on the device."""
+    def select(self, patches, pos_enc, order=None):
+        """(B, N, ...) patches (device, or host for lazy loading) -> mem_idx (B, M) int64 on the device.
+
+        ``order`` ((B or 1, N) int64 on the device; only where ``index_supported``): select as if the patch axis had been
+        permuted by it - ``patches`` is the UNSHUFFLED tensor, the encoders read row ``order[b, j]`` where they would read
+        row j of the shuffled copy, and everything behind that first read (``pos_enc``, which IS shuffled, embeddings,
+        logits, the loops, ``mem_idx``) is in shuffled numbering."""
         net = self.net
         net._device_patches = None
         self._done = self._unfinished = None       # (whatever a call that raised half-way left behind)
+        self._order = self._flat = None
+        if order is not None:
+            self._order, self._flat = order, self.flat_index(order, patches.shape[0], patches.shape[1])
+            self.index_calls += 1
         if patches.is_cuda and self.can_stream_image(patches):
             return self.image_stream(patches, pos_enc)
         if patches.is_cuda and self.can_overlap(patches):
@@ -287,6 +303,40 @@ class Selection:
                 return self.features_persistent(patches, pos_enc)
             return self.parts_with_ranges(patches, pos_enc)
         return self.slabs(patches, pos_enc)
+
+    def index_supported(self, patches):
+        """Can the schedule ``select`` picks for these patches read them through a shuffle index?  Device-resident,
+        contiguous patches on: every feature pipeline (the row-indexed projector kernels) and the fused 1x32x32 trunk in
+        parts (its index list).  Not: lazy patches, the one-image trunk stream, the small-batch split, layer-by-layer trunks,
+        blank-patch dedup (those shuffle by copy)."""
+        net = self.net
+        if not (patches.is_cuda and patches.is_contiguous()) or hip.dedup_blank() or net.encoder.training:
+            return False
+        if not net.is_image:
+            return patches.dim() == 3 and patches.dtype in (torch.float32, torch.float16, torch.bfloat16)
+        if self.can_stream_image(patches) or not self.can_overlap(patches):
+            return False
+        B, N = patches.shape[:2]
+        if B * N < self.small_batch_limit(patches.device) and self.n_iter(N) < 100:
+            return False
+        return bool(self.plan().fused(patches.shape))
+
+    def flat_index(self, order, B, N):
+        """(B or 1, N) int64 permutation -> (B, N) int32 flat row numbers b * N + order[b, j], composed once per call (one
+        permutation for the whole batch: kept as long as the permutation tensor is the same)."""
+        shared = order.shape[0] == 1
+        key = (id(order), order._version, B, N) if shared else None
+        if shared and self._flat_key is not None and self._flat_key[0] == key and self._flat_key[1] is order:
+            return self._flat_key[2]
+        # (host work in front of the call's first launch: one conversion, and one addition when there are several images -
+        #  the images' first rows b * N are kept between calls)
+        flat = order.to(torch.int32)
+        if B > 1:
+            if self._flat_base is None or self._flat_base[0] != (B, N, order.device):
+                self._flat_base = ((B, N, order.device), (torch.arange(B, device=order.device, dtype=torch.int32) * N).unsqueeze(1))
+            flat = flat + self._flat_base[1]
+        self._flat_key = (key, order, flat) if shared else None
+        return flat
 
     def can_overlap(self, patches):
         """Does the loop run beside the encoder (parts + ranges, or a persistent loop)?"""
@@ -450,7 +500,9 @@ class Selection:
         # (candidate sets beyond the LDS - the shipped M = I = 5000 - run as a TEAM of workgroups per slide, csrc/scan_large_team.h:
         #  each of them keeps a compute unit)
         team = hip.scan_workgroups_per_image(B, M, I, ca.H, ca.n_token)
-        if streamed and patches.dtype == torch.float32 and self.native_ok(patches, None):
+        # (a shuffle index: the launches one by one - the library's one-call path carries no order)
+        fidx = self._flat.view(-1) if self._flat is not None else None
+        if streamed and patches.dtype == torch.float32 and fidx is None and self.native_ok(patches, None):
             free = hip.device_geometry(dev).cus - loops * team
             wgs = int(os.environ.get("IPSX_CAM_WGS", "0")) or free
             # (a team's iteration is ~55 us and the last TWO of them run behind the producer - the rows of the last chunk all
@@ -472,7 +524,8 @@ class Selection:
                 free = hip.device_geometry(dev).cus - loops * team
                 wgs = int(os.environ.get("IPSX_CAM_WGS", "0")) or free
                 short = int(os.environ.get("IPSX_CAM_SHORT", "0")) or (-11 if B == 1 else -1)
-                plan.stream(xf, vq, R, ef, logits.view(B * N, R), ctl, ready, workgroups=wgs, slide_rows=N, short_first=short)
+                plan.stream(xf, vq, R, ef, logits.view(B * N, R), ctl, ready, workgroups=wgs, slide_rows=N, short_first=short,
+                            index=fidx)
                 # (whatever two simultaneous finishers leave to each other is published by the last workgroup out: round 5 -
                 #  it was one publish_rows launch per slide behind the stream)
             else:
@@ -480,20 +533,28 @@ class Selection:
                 edges = [0] + [min(N, M + it * I) for it in its[1:]]
                 edges[-1] = N
                 launches = self.feature_launches(B, N, edges, dev, loops * team)
+                # (through a shuffle index the launches read the whole tensor xf through their rows of the index)
+                src_of = (lambda r0, r1: (xf, fidx[r0:r1])) if fidx is not None else (lambda r0, r1: (xf[r0:r1], None))
                 if fused2:
-                    plan.row_stats(xf[launches[0][0]:launches[0][1]], out=stats[launches[0][0]:launches[0][1]])
+                    x0, i0 = src_of(launches[0][0], launches[0][1])
+                    plan.row_stats(x0, out=stats[launches[0][0]:launches[0][1]], index=i0)
                 published = None                       # (slide, rows) whose publication rides on the next GEMM launch
                 for n_step, (r0, r1, pubs) in enumerate(launches):
+                    xk, ik = src_of(r0, r1)
                     if not fused2:
-                        plan.row_stats(xf[r0:r1], out=stats[r0:r1])
-                    emb = plan.encode(xf[r0:r1], stats=stats[r0:r1], out=ef[r0:r1],
+                        plan.row_stats(xk, out=stats[r0:r1], index=ik)
+                    emb = plan.encode(xk, stats=stats[r0:r1], out=ef[r0:r1], index=ik,
                                       publish=(ready[published[0]:published[0] + 1], published[1]) if published else None)
                     published = None
                     emb = emb.view(1, r1 - r0, -1)
                     pos = pos_enc[r0 // N:r0 // N + 1, r0 % N:r0 % N + (r1 - r0)] if net.use_pos else None
                     nxt = launches[n_step + 1] if n_step + 1 < len(launches) else None
                     if fused2 and nxt is not None:
-                        hip.logits_stats(emb, pos, vq, R, lf[:, r0:r1], xf[nxt[0]:nxt[1]], stats[nxt[0]:nxt[1]], plan.ln_eps)
+                        if fidx is not None:           # the next part's moments as a launch of their own, through the index
+                            hip.logits(emb, pos, vq, R, out=lf[:, r0:r1])
+                            plan.row_stats(xf, out=stats[nxt[0]:nxt[1]], index=fidx[nxt[0]:nxt[1]])
+                        else:
+                            hip.logits_stats(emb, pos, vq, R, lf[:, r0:r1], xf[nxt[0]:nxt[1]], stats[nxt[0]:nxt[1]], plan.ln_eps)
                         for b_, rows in pubs[:-1]:     # (a launch across a slide's end: the finished slide is published at once)
                             hip.publish_rows(ready[b_:b_ + 1], rows)
                         published = pubs[-1]
@@ -573,7 +634,16 @@ class Selection:
             self._part_index = (key, [(rows + torch.arange(edges[k], edges[k + 1], device=dev, dtype=torch.int32)).reshape(-1)
                                       for k in range(P)])
         side, main = self.streams(dev)
-        flat = patches.reshape(B * N, *patches.shape[2:]) if indexed else None
+        flat = patches.reshape(B * N, *patches.shape[2:]) if indexed or self._flat is not None else None
+        part_index = self._part_index[1] if indexed else None
+        if self._flat is not None:
+            # a shuffle index: composed into the parts' index lists, per call, by ONE gather (the map - part k's (B, rows)
+            # block of the (B, N) index, one after the other - is kept with the parts)
+            if self._part_map is None or self._part_map[0] != key:
+                pos = torch.arange(B * N, device=dev).view(B, N)
+                self._part_map = (key, torch.cat([pos[:, edges[k]:edges[k + 1]].reshape(-1) for k in range(P)]))
+            every = torch.index_select(self._flat.reshape(-1), 0, self._part_map[1])
+            part_index = [every[B * edges[k]:B * edges[k + 1]] for k in range(P)]
         logits, mem_idx_buf, tie, scan_ws = self.buffers(
             "parts", (B, N, M, I, R, str(dev)),
             lambda: (torch.empty((B, N, R), dtype=torch.float32, device=dev),
@@ -586,7 +656,9 @@ class Selection:
         for k in range(P):
             lo, hi = edges[k], edges[k + 1]
             if indexed:
-                emb = plan.encode_indexed(flat, self._part_index[1][k]).view(B, hi - lo, -1)
+                emb = plan.encode_indexed(flat, part_index[k]).view(B, hi - lo, -1)
+            elif self._flat is not None:           # feature rows through the shuffle index
+                emb = plan.encode(flat, index=part_index[k]).view(B, hi - lo, -1)
             else:
                 emb = net._embed(patches[:, lo:hi].reshape(-1, *patches.shape[2:])).view(B, hi - lo, -1)
             parts.append(emb)
@@ -638,7 +710,10 @@ class Selection:
         parts = []
         for k, (lo, hi) in enumerate(spans):
             part = fetch(k)
-            emb = net._embed(part.reshape(-1, *patches.shape[2:])).view(B, hi - lo, -1)
+            if self._flat is not None:             # (device-resident feature rows, one span) through the shuffle index
+                emb = self.plan().encode(part.reshape(B * N, -1), index=self._flat.view(-1)).view(B, N, -1)
+            else:
+                emb = net._embed(part.reshape(-1, *patches.shape[2:])).view(B, hi - lo, -1)
             hip.logits(emb, pos_enc[:, lo:hi] if net.use_pos else None, vq, R, out=logits[:, lo:hi])
             prefetch(k + 1)          # after the encoder is enqueued: a pageable-memory copy blocks the host, not the GPU
             parts.append(emb)

@@ -25,3 +25,16 @@ def shuffle_instance(x, axis, shuffle_idx=None):
     take = shuffle_idx.to(x.device)
     take = take.reshape(*take.shape, *(1,) * (x.ndim - axis - 1)).expand(*x.shape[:axis + 1], *x.shape[axis + 1:])
     return x.gather(axis, take), shuffle_idx
+
+
+def draw_shuffle(patches, style):
+    """DRAW the permutation ``IPSNet.do_shuffle`` would apply to ``patches`` (B, N, ...) without applying it: the same
+    calls, in the same order and with the same shapes, as ``shuffle_batch`` / ``shuffle_instance`` make, so torch's RNG
+    streams are consumed identically and ``x[:, perm]`` / ``x.gather(1, perm...)`` is their result.  ``'batch'``: (N,)
+    on the host (the CPU generator); ``'instance'``: (B, N) on the patches' device; any other style: None, as
+    ``do_shuffle`` leaves the patches alone.  Lets ``IPSNet.ips`` select through an index instead of a permuted copy."""
+    if style == 'batch':
+        return torch.randperm(patches.shape[1])
+    if style == 'instance':
+        return torch.rand(patches.shape[:2], device=patches.device).argsort(1)
+    return None
