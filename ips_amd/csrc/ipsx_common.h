@@ -26,7 +26,9 @@ static inline int launched(const char* what) {
 }
 
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-static inline int conv_out(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
+// (a padded map smaller than the kernel has NO output: C's division rounds (in + 2p - k) / s towards zero, which made it 1
+//  under stride >= 2 - a window hanging over the far edge, accepted by every "empty output" gate)
+static inline int conv_out(int in, int k, int s, int p) { return in + 2 * p < k ? 0 : (in + 2 * p - k) / s + 1; }
 
 }  // namespace ipsx
 

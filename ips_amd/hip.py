@@ -872,10 +872,10 @@ def patchify_sparse(index, value, offsets, canvas, patch_size, patch_stride, fla
 
 
 # ------------------------------------------------------------------ bf16 layer kernels (the layered trunk under IPSX_PRECISION=bf16)
-def conv2d_nhwc_bf16(x, weight, alpha, shift, stride, pad, residual=None, relu=True):
+def conv2d_nhwc_bf16(x, weight, alpha, shift, stride, pad, residual=None, relu=True, out=None):
     """One convolution of the bf16 layer-by-layer trunk (conv_nhwc_bf16_kernel): ``x`` (n, h, w, C_in) bfloat16, OIHW float32
     ``weight`` (rounded to bf16 by the packing), float32 ``alpha`` / ``shift`` (C_out,) or None, ``residual``
-    (n, ho, wo, C_out) bfloat16 or None  ->  (n, ho, wo, C_out) bfloat16."""
+    (n, ho, wo, C_out) bfloat16 or None  ->  (n, ho, wo, C_out) bfloat16 (written into ``out`` where one is given)."""
     if x.dim() != 4 or x.dtype != torch.bfloat16 or not x.is_contiguous():
         raise ValueError("expected a contiguous bfloat16 (n, h, w, C) tensor")
     w = _f32(weight.detach())
@@ -891,7 +891,10 @@ def conv2d_nhwc_bf16(x, weight, alpha, shift, stride, pad, residual=None, relu=T
     if residual is not None and (residual.dtype != torch.bfloat16 or tuple(residual.shape) != (n, ho, wo, co) or
                                  not residual.is_contiguous()):
         raise ValueError("residual must be a contiguous bfloat16 (n, ho, wo, C_out) tensor")
-    y = torch.empty((n, ho, wo, co), dtype=torch.bfloat16, device=x.device)
+    if out is not None and (out.dtype != torch.bfloat16 or tuple(out.shape) != (n, ho, wo, co) or not out.is_contiguous() or
+                            out.device != x.device):
+        raise ValueError("out must be a contiguous bfloat16 (n, ho, wo, C_out) tensor on the device of x")
+    y = out if out is not None else torch.empty((n, ho, wo, co), dtype=torch.bfloat16, device=x.device)
     _ck(lib().ipsx_conv2d_affine_nhwc_bf16(C.byref(cv), _p(x), _p(residual), _p(y), n, h, wd, int(bool(relu)), _stream()),
         "ipsx_conv2d_affine_nhwc_bf16")
     return y

@@ -123,7 +123,9 @@ struct orc_conv {
     const float* shift;   // c_out or NULL
 };
 
-static inline int out_dim(int in, int k, int s, int p) { return (in + 2 * p - k) / s + 1; }
+// (a padded map smaller than the kernel has no output - the library's conv_out, csrc/ipsx_common.h; C's division would
+//  round (in + 2p - k) / s towards zero and make it one under stride >= 2)
+static inline int out_dim(int in, int k, int s, int p) { return in + 2 * p < k ? 0 : (in + 2 * p - k) / s + 1; }
 
 // nn.Conv2d(bias=False) -> BatchNorm(eval) [-> += identity] [-> ReLU]
 // (torchvision BasicBlock.forward as composed by ips_net.py:35-50).

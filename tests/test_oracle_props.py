@@ -7,8 +7,9 @@ import pytest
 import torch
 
 from oracle import oracle as orc
-from tests.util import (HEAD_F64_BOUNDS, HEAD_SHAPES, f64_logits, head_shape_inputs, head_shape_net, head_shape_net64,
-                        head_shape_scores_lengths, rel_err)
+from tests.util import (CONV_LATTICE_NCHW, CONV_LATTICE_NHWC, HEAD_F64_BOUNDS, HEAD_SHAPES, conv_bound_ratio, conv_case_f64,
+                        conv_case_id, conv_case_inputs, conv_case_oracle, conv_case_out, conv_padding_only_value, f64_logits,
+                        head_shape_inputs, head_shape_net, head_shape_net64, head_shape_scores_lengths, rel_err)
 
 
 def test_det_expf_is_accurate_and_monotone():
@@ -219,3 +220,55 @@ def test_oracle_tracks_float64_at_head_shapes_no_config_uses(name):
     err["preds"] = max(rel_err(preds[k], p64[k].numpy()) for k in preds)
     print(name, {k: "%.1e" % v for k, v in err.items()})
     assert all(err[k] <= HEAD_F64_BOUNDS[k] for k in err), err
+
+
+# ---------------------------------------------------------------- the convolution lattices (tests/util.py), oracle alone
+# What tests/test_conv_lattice.py holds the HIP kernels to bit for bit is held to float64 here, without a GPU: the bound
+# 1.01 (K + 3) 2^-24 (|alpha| conv(|x|, |w|) + |shift| + |res|) per element is the first-order bound of a K-term fp32 fma
+# chain plus the two roundings of the epilogue - derived, not measured.  Worst |error| / bound over the lattices: 0.463
+# (NCHW), 0.115 (NHWC).
+CONV_LATTICES = [("nchw", i, c) for i, c in enumerate(CONV_LATTICE_NCHW)] + [("nhwc", i, c) for i, c in enumerate(CONV_LATTICE_NHWC)]
+
+
+@pytest.mark.parametrize("which,i,case", CONV_LATTICES, ids=["%s%02d_%s" % (w, i, conv_case_id(c)) for w, i, c in CONV_LATTICES])
+def test_conv_oracle_within_the_float64_bound_on_the_lattices(which, i, case):
+    x, wt, alpha, shift, r = conv_case_inputs(case, (100 if which == "nchw" else 200) + i)
+    want = conv_case_oracle(case, x, wt, alpha, shift, r)
+    e, bound, A = conv_case_f64(case, x, wt, alpha, shift, r)
+    assert want.shape == e.shape and np.isfinite(want).all()
+    ratio = conv_bound_ratio(want, e, bound)
+    print("\n  %s %s: worst |oracle - float64| / bound %.3f" % (which, conv_case_id(case), ratio))
+    assert ratio <= 1.0, ratio
+    pad_only, v = conv_padding_only_value(case, shift, r, A)
+    assert np.array_equal(want[pad_only], v[pad_only]), "a window wholly in padding is not exactly shift + res"
+
+
+def test_conv_lattices_reach_the_seams_they_are_there_for():
+    def totals(cases, pick=lambda c: True):
+        return {c.n * conv_case_out(c)[0] * conv_case_out(c)[1] for c in cases if pick(c)}
+
+    def vec4(c):
+        return conv_case_out(c)[0] * conv_case_out(c)[1] % 4 == 0
+
+    nchw, nhwc = CONV_LATTICE_NCHW, CONV_LATTICE_NHWC
+    for c in nchw + nhwc:
+        assert min(conv_case_out(c)) >= 1 and max(c.h, c.w) <= 13 and max(conv_case_out(c)) <= 17, c
+    assert {c.c_in for c in nchw} >= {1, 2, 3, 5, 8, 12, 33} and {c.c_out for c in nchw} >= {1, 31, 32, 33, 64, 65, 100}
+    kernels = {(1, 1), (2, 2), (3, 3), (1, 3), (3, 1), (5, 3), (7, 7)}
+    for cases in (nchw, nhwc):
+        assert {(c.kh, c.kw) for c in cases} >= kernels and {c.stride for c in cases} >= {1, 2, 3}
+        assert {c.affine for c in cases} == {"as", "a", "s", "-"}
+        assert {(c.res, c.relu) for c in cases} == {(False, False), (False, True), (True, False), (True, True)}
+        for k in (2, 3):        # pad 0, (k-1)/2, k-1, k+1 under a square kernel
+            assert {c.pad for c in cases if c.kh == c.kw == k} >= {0, (k - 1) // 2, k - 1, k + 1}, k
+        assert any(c.h < c.kh or c.w < c.kw for c in cases) and any(c.pad >= max(c.kh, c.kw) for c in cases)
+    assert totals(nchw) >= {1, 31, 32, 33, 63, 64, 65, 255, 256, 257}
+    assert totals(nchw, vec4) >= {32, 64, 256} and totals(nchw, lambda c: not vec4(c)) >= {32, 64, 256}
+    assert any(vec4(c) and c.n * conv_case_out(c)[0] * conv_case_out(c)[1] % 256 not in range(0, 256, 64) for c in nchw)
+    assert any(c.kh == 31 and c.kw == 31 for c in nchw)
+    assert any((c.kh * c.kw * c.c_in) % 8 and c.c_out % 32 for c in nchw)
+    assert {c.c_in for c in nhwc} >= {32, 64, 96, 160} and {c.c_out for c in nhwc} >= {8, 32, 33, 64, 65, 96, 160, 255, 256, 264, 288, 544}
+    assert {c.kh * c.kw * c.c_in // 8 for c in nhwc} >= {4, 8, 12, 180}
+    assert totals(nhwc, lambda c: c.c_out <= 64) >= {255, 256, 257}
+    assert totals(nhwc, lambda c: 64 < c.c_out < 256) >= {127, 128, 129}
+    assert totals(nhwc, lambda c: c.c_out >= 256) >= {63, 64, 65}

@@ -27,7 +27,7 @@ import torch.nn.functional as F
 
 from ips_amd import hip, synth
 from ips_amd.architecture import IPSNet
-from tests.util import Golden
+from tests.util import Golden, bf16_conv_emulation, r16
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -36,10 +36,6 @@ C = hip.C
 EMU_BOUND = 3e-3
 FP32_BOUND = 3e-2
 FLIP_CAP = 1e-3
-
-
-def r16(t):
-    return t.float().to(torch.bfloat16).double()
 
 
 def bf16_env(monkeypatch):
@@ -75,12 +71,7 @@ def test_one_convolution_against_the_emulation(c_in, c_out, k, stride, pad, h, w
                                r.to(DEV) if res else None, relu)
     assert got.dtype == torch.bfloat16 and tuple(got.shape) == (n, ho, wo, c_out)
     got = got.cpu().double()
-    e = F.conv2d(x.double().permute(0, 3, 1, 2), r16(wt), None, stride, pad).permute(0, 2, 3, 1)
-    e = e * alpha.double() + shift.double()
-    if res:
-        e = e + r.double()
-    if relu:
-        e = torch.relu(e)
+    e = bf16_conv_emulation(x, wt, alpha, shift, stride, pad, r, relu)
     s = float(e.abs().max())
     assert torch.isfinite(got).all()
     excess = float(((got - e).abs() - (2.0 ** -8 * e.abs() + 1e-5 * s)).max())
