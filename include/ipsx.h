@@ -81,7 +81,9 @@ extern "C" {
  *         cross-attention aggregator of the training step on folded queries
  *   3.06  (additions only): ipsx_projector_stats_indexed, ipsx_projector_apply_indexed, ipsx_projector_apply_bf16_indexed,
  *         ipsx_projector_stream_indexed, ipsx_ips_finish_indexed - the feature projector reading its rows through an index
- *         (a shuffle applied as addressing, not as a copy of the patch tensor) and the end of such a call */
+ *         (a shuffle applied as addressing, not as a copy of the patch tensor) and the end of such a call;
+ *         ipsx_trunk_encode_u8, ipsx_trunk_encode_indexed_u8, ipsx_dequant_patches - uint8 patch storage: the stems of the
+ *         exact fp32 trunks read bytes and look their float32 values up in a per-channel table */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -267,6 +269,21 @@ int ipsx_trunk_encode(const ipsx_trunk* t, const float* patches, int64_t n_patch
  * encode a strided subset (e.g. columns lo..hi of a (B, N, ...) tensor) without copying it.  Fused trunk only. */
 int ipsx_trunk_encode_indexed(const ipsx_trunk* t, const float* patches, const int32_t* index,
                               int64_t n_index, float* emb, void* stream);
+
+/* 3.06: uint8 patch storage.  `patches` holds the pixels as bytes, `table` (c_in x 256 floats, device) the float32 value of
+ * every byte per channel - e.g. byte / 255, or (byte / 255 - mean[c]) / std[c], filled by the host with the very tensor ops
+ * the dataset would have run.  The stem looks each pixel up while it stages the patch (the zero padding stays 0.0f) and
+ * everything behind that load is the float32 code: emb is bit for bit ipsx_trunk_encode of the expanded tensor
+ * x[p][c][..] = table[c][patches[p][c][..]].  The exact path only (precision 0, patch_dtype 0; anything else: IPSX_EINVAL);
+ * ipsx_trunk_kernel and ipsx_trunk_workspace_bytes serve both.  Addresses: table 16-byte aligned; patches 16-byte aligned
+ * for the fused 1x32x32 and the 3x100x100 stem, 4-byte aligned for the 1x50x50 stem, any for other shapes.
+ * ipsx_dequant_patches: q (n_patch, c, hw) bytes -> out (n_patch, c, hw) floats, out = table[c][q] - for the M patches a
+ * selection keeps. */
+int ipsx_trunk_encode_u8(const ipsx_trunk* t, const uint8_t* patches, const float* table, int64_t n_patch,
+                         float* emb, void* workspace, size_t workspace_bytes, void* stream);
+int ipsx_trunk_encode_indexed_u8(const ipsx_trunk* t, const uint8_t* patches, const float* table, const int32_t* index,
+                                 int64_t n_index, float* emb, void* stream);
+int ipsx_dequant_patches(const uint8_t* q, const float* table, float* out, int64_t n_patch, int c, int hw, void* stream);
 
 /* Same result as ipsx_trunk_encode, with exact blank-patch deduplication (all-zero patches share one
  * embedding in eval mode; ~93 % of Megapixel-MNIST patches): only the non-blank patches and one blank

@@ -118,6 +118,9 @@ class IPSNet(nn.Module):
         self._mem_emb = None
         self._selection = None        # the HIP selection pipelines (ips_amd/selection.py), built on first use
         self._device_patches = None   # lazy loading: the device copy of the host tensor, when it is kept
+        # uint8 patch storage (ips_amd/quant.py): the (n_chan, 256) float32 table of set_patch_table - a plain tensor
+        # attribute like pos_enc, not a buffer (state dicts stay those of the reference)
+        self.patch_table = None
         if self.is_image and hip.on_device(device):
             # the training step's convolutions run channels-last (training/fused_encoder.py): weights stored that way
             # from the start (before any optimizer state exists) are not re-laid-out in every step.  Shapes, names and
@@ -125,6 +128,55 @@ class IPSNet(nn.Module):
             from ..training import fused_encoder
             if fused_encoder.enabled() and fused_encoder.supported(self.encoder):
                 self.encoder.to(memory_format=torch.channels_last)
+
+    # ---------------------------------------------------------------- uint8 patch storage
+    def set_patch_table(self, table):
+        """Let ``ips()`` take uint8 patches: ``table`` ((n_chan, 256) float32, finite; ``ips_amd.quant.patch_table`` builds
+        the datasets' own) gives the float32 value of every byte per channel.  The encoders' stems look the pixels up as
+        they stage a patch, so the selection is that of the expanded float32 tensor ``table[c][patches]`` bit for bit, and
+        ``ips()`` returns ``mem_patch`` as float32 (the selected bytes dequantised) - ``forward()`` and the training step
+        see what they always saw.  ``None`` removes the table.  Kept on ``self.device``; not part of the state dict."""
+        if table is None:
+            self.patch_table = None
+            return self
+        if not self.is_image:
+            raise TypeError("a patch table goes with an image encoder (feature rows are stored as float16 / bfloat16)")
+        from ..quant import check_table
+        n_chan = next(self.encoder.children()).in_channels
+        check_table(table, n_chan)
+        if not bool(torch.isfinite(table).all()):
+            raise ValueError("the patch table must be finite")
+        self.patch_table = table.detach().to(self.device).contiguous()
+        return self
+
+    def _table_for(self, x):
+        """The table that goes with patches ``x`` - None unless they are uint8; uint8 without a table is an error."""
+        if x.dtype != torch.uint8:
+            return None
+        if self.patch_table is None:
+            raise TypeError("uint8 patches need a dequantisation table: call IPSNet.set_patch_table(ips_amd.quant.patch_table(...)) first")
+        return self.patch_table
+
+    def _dequant(self, q):
+        """float32 ``patch_table[c][q]`` of uint8 patches on ``self.device`` (the HIP kernel there, else by indexing)."""
+        table = self._table_for(q)
+        if hip.on_device(q):
+            return hip.dequant_patches(q, table)
+        from ..quant import dequant
+        return dequant(q, table)
+
+    def _check_u8(self, patches):
+        """uint8 patches: everything that refuses them does so here, before the first launch of the call."""
+        if not self.is_image or patches.dim() != 5:
+            raise TypeError("uint8 input goes with (B, N, C, h, w) image patches")
+        table = self._table_for(patches)
+        if table.shape[0] != patches.shape[2]:
+            raise ValueError("the patch table has {} rows, the patches {} channels".format(table.shape[0], patches.shape[2]))
+        if hip.on_device(self.device):
+            if hip.precision() != "fp32":
+                raise TypeError("uint8 patches go with the exact trunk (IPSX_PRECISION=fp32), not {}".format(hip.precision()))
+            if hip.dedup_blank():
+                raise TypeError("blank-patch dedup reads float32 patches (IPSX_DEDUP_BLANK=1 with uint8 patches)")
 
     # ---------------------------------------------------------------- small pieces
     def do_shuffle(self, patches, pos_enc):
@@ -200,7 +252,10 @@ class IPSNet(nn.Module):
                 torch.is_grad_enabled() and any(p.requires_grad for p in self.encoder.parameters())):
             if self._plan is None:
                 self._plan = hip.EncoderPlan(self.encoder, self.is_image)
-            return self._plan.encode(x)
+            return self._plan.encode(x, table=self._table_for(x))
+        if x.dtype == torch.uint8:
+            # the stock modules (CPU / ATen path, or an encoder in training mode) compute on the dequantised pixels
+            x = self._dequant(x)
         if hip.on_device(x) and self.encoder.training and self.is_image and torch.is_grad_enabled():
             # training step (reference training/iterative.py:158-163): same modules, BatchNorm + add + ReLU fused
             from ..training import fused_encoder
@@ -228,15 +283,22 @@ class IPSNet(nn.Module):
         (eager loading) or on the host (lazy loading).  Returns the M selected
         patches ``(B, M, ...)`` and their positional encodings ``(B, M, D)`` (or
         ``None``), both on ``self.device``, ordered by score of the last round.
+
+        uint8 image patches (after ``set_patch_table``): the same selection on a quarter of the bytes; ``mem_patch``
+        comes back float32 - the selected bytes dequantised, bit for bit what the call returns for the expanded tensor.
         """
         M, device, pos_enc = self.M, self.device, self.pos_enc
         B, N = patches.shape[:2]
+        u8 = patches.dtype == torch.uint8
+        if u8:
+            self._check_u8(patches)
 
         self._emb_parts = self._mem_emb = None
         self.last_shuffle = None
         if M >= N:  # nothing to select (:185-188)
             self.last_mem_idx = None
-            return patches.to(device), (pos_enc.expand(B, -1, -1) if self.use_pos else None)
+            mem_patch = patches.to(device)
+            return (self._dequant(mem_patch) if u8 else mem_patch), (pos_enc.expand(B, -1, -1) if self.use_pos else None)
 
         was_training = self.training
         if was_training:  # IPS always scores with running BN statistics and no dropout
@@ -275,6 +337,8 @@ class IPSNet(nn.Module):
                 mem_pos = self._take(pos_enc, mem_idx) if self.use_pos else None
                 if sel is not None:
                     sel.after_call()
+            if u8:                     # the M selected patches leave as float32 (forward / fill_batch read float32)
+                mem_patch = self._dequant(mem_patch)
         finally:
             if was_training:
                 self.encoder.train()

@@ -216,7 +216,11 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[2
 // Any C_in (the 1- and 3-channel stems, and the public NCHW entry point).  The (channel, ky, kx) of every k is decoded ONCE per workgroup into an LDS
 // table (offset inside the image, tap position), so the inner loop has no integer divisions: per element one table
 // read (the lanes of a half share the address), the bounds test, the gather.
-__global__ __launch_bounds__(256) void conv_any_kernel(ConvArgs a) {
+// U8 (the stem of a trunk on uint8 patches, ipsx_trunk_encode_u8): a.x holds bytes and an operand element is
+// table[c][byte] (table: c_in x 256 floats in global memory - 1 KB per channel, cache-resident); the table entry carries the
+// channel in bits 24.. for it.  Elements outside the image stay 0.0f - they never go through the table.
+template <bool U8>
+__device__ __forceinline__ void conv_any_body(const ConvArgs& a, const float* table) {
     extern __shared__ __attribute__((aligned(16))) int ktab[];     // [kgs*8][2]: {c*hw + ky*w + kx, ky | kx << 8 | valid << 16}
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, half = lane >> 5;
     const int hw = a.h * a.w;
@@ -227,7 +231,7 @@ __global__ __launch_bounds__(256) void conv_any_kernel(ConvArgs a) {
         const int tap = kk / a.c_in, c = kk - tap * a.c_in;
         const int ky = tap / a.kw, kx = tap - ky * a.kw;
         ktab[2 * k] = c * hw + ky * a.w + kx;
-        ktab[2 * k + 1] = ky | (kx << 8) | ((kin ? 1 : 0) << 16);
+        ktab[2 * k + 1] = ky | (kx << 8) | ((kin ? 1 : 0) << 16) | (U8 ? c << 24 : 0);
     }
     __syncthreads();
     const unsigned m_base = blockIdx.x * 256u + wave * 64u;
@@ -273,12 +277,23 @@ __global__ __launch_bounds__(256) void conv_any_kernel(ConvArgs a) {
         float a0[4], a1[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const unsigned ky = (unsigned)pk[j] & 0xFFu, kx = ((unsigned)pk[j] >> 8) & 0xFFu, kin = (unsigned)pk[j] >> 16;
+            const unsigned ky = (unsigned)pk[j] & 0xFFu, kx = ((unsigned)pk[j] >> 8) & 0xFFu;
+            const unsigned kin = U8 ? ((unsigned)pk[j] >> 16) & 1u : (unsigned)pk[j] >> 16;
             const bool ok0 = ((rm0 >> ky) & (cm0 >> kx) & kin) != 0u;
             const bool ok1 = ((rm1 >> ky) & (cm1 >> kx) & kin) != 0u;
-            const float v0 = p0.base[ok0 ? o0 + off[j] : 0], v1 = p1.base[ok1 ? o1 + off[j] : 0];
-            a0[j] = ok0 ? v0 : 0.0f;
-            a1[j] = ok1 ? v1 : 0.0f;
+            if constexpr (U8) {
+                // (p.base counts float elements from a.x; the same element offsets address the bytes)
+                const unsigned char* q0 = reinterpret_cast<const unsigned char*>(a.x) + (p0.base - a.x);
+                const unsigned char* q1 = reinterpret_cast<const unsigned char*>(a.x) + (p1.base - a.x);
+                const float* tc = table + 256 * ((unsigned)pk[j] >> 24);
+                const float v0 = tc[q0[ok0 ? o0 + off[j] : 0]], v1 = tc[q1[ok1 ? o1 + off[j] : 0]];
+                a0[j] = ok0 ? v0 : 0.0f;
+                a1[j] = ok1 ? v1 : 0.0f;
+            } else {
+                const float v0 = p0.base[ok0 ? o0 + off[j] : 0], v1 = p1.base[ok1 ? o1 + off[j] : 0];
+                a0[j] = ok0 ? v0 : 0.0f;
+                a1[j] = ok1 ? v1 : 0.0f;
+            }
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -290,6 +305,9 @@ __global__ __launch_bounds__(256) void conv_any_kernel(ConvArgs a) {
     }
     conv_epilogue(a, acc, m_base, n_base, lane);
 }
+
+__global__ __launch_bounds__(256) void conv_any_kernel(ConvArgs a) { conv_any_body<false>(a, nullptr); }
+__global__ __launch_bounds__(256) void conv_any_u8_kernel(ConvArgs a, const float* table) { conv_any_body<true>(a, table); }
 
 // ------------------------------------------------------------------ pooling
 __global__ void maxpool_3x3s2_kernel(const float* __restrict__ x, float* __restrict__ y, size_t total, int h,
@@ -388,7 +406,7 @@ IPSX_API int ipsx_bn_affine(const float* gamma, const float* beta, const float* 
 
 namespace ipsx {
 int conv2d_affine_impl(const ipsx_conv* cv, const float* x, const float* residual, float* y, int64_t n, int h,
-                       int w, int relu, int out_nhwc, void* stream);
+                       int w, int relu, int out_nhwc, void* stream, const float* table = nullptr);
 }
 
 IPSX_API int ipsx_conv2d_affine(const ipsx_conv* cv, const float* x, const float* residual, float* y,
@@ -401,9 +419,11 @@ IPSX_API int ipsx_conv2d_affine_to_nhwc(const ipsx_conv* cv, const float* x, con
     return conv2d_affine_impl(cv, x, residual, y, n, h, w, relu, 1, stream);
 }
 
+// table != nullptr: x holds uint8 elements (n, c_in, h, w) and an element's value is table[c][byte] (conv_any_u8_kernel)
 int ipsx::conv2d_affine_impl(const ipsx_conv* cv, const float* x, const float* residual, float* y, int64_t n,
-                             int h, int w, int relu, int out_nhwc, void* stream) {
+                             int h, int w, int relu, int out_nhwc, void* stream, const float* table) {
     IPSX_TRY(check_conv(cv));
+    IPSX_REQUIRE(!table || cv->c_in <= 127, "conv2d_affine: uint8 input with %d channels (at most 127)", cv->c_in);
     IPSX_REQUIRE(x && y && n >= 0 && h > 0 && w > 0, "conv2d_affine: bad arguments");
     if (n == 0) return IPSX_OK;
     const int ho = conv_out(h, cv->kh, cv->stride, cv->pad), wo = conv_out(w, cv->kw, cv->stride, cv->pad);
@@ -415,7 +435,8 @@ int ipsx::conv2d_affine_impl(const ipsx_conv* cv, const float* x, const float* r
     for (int64_t i0 = 0; i0 < n; i0 += per) {
         const int64_t cnt = std::min(per, n - i0);
         ConvArgs a;
-        a.x = x + (size_t)i0 * cv->c_in * h * w;
+        a.x = table ? reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(x) + (size_t)i0 * cv->c_in * h * w)
+                    : x + (size_t)i0 * cv->c_in * h * w;
         a.y = y + (size_t)i0 * cv->c_out * howo;
         a.res = residual ? residual + (size_t)i0 * cv->c_out * howo : nullptr;
         a.wp = cv->w_packed; a.alpha = cv->alpha; a.shift = cv->shift;
@@ -425,9 +446,10 @@ int ipsx::conv2d_affine_impl(const ipsx_conv* cv, const float* x, const float* r
         a.kgs = (int)cdiv((int64_t)cv->kh * cv->kw * cv->c_in, 8);
         a.out_nhwc = out_nhwc;
         dim3 grid((unsigned)cdiv(a.m_total, 256), (unsigned)cdiv(cv->c_out, 64));
-        const size_t table = (size_t)a.kgs * 8 * 2 * sizeof(int);
-        IPSX_REQUIRE(table <= 64 * 1024, "conv2d_affine: K = %d does not fit the k table", a.kgs * 8);
-        conv_any_kernel<<<grid, dim3(256), table, as_stream(stream)>>>(a);
+        const size_t ktab_bytes = (size_t)a.kgs * 8 * 2 * sizeof(int);
+        IPSX_REQUIRE(ktab_bytes <= 64 * 1024, "conv2d_affine: K = %d does not fit the k table", a.kgs * 8);
+        if (table) conv_any_u8_kernel<<<grid, dim3(256), ktab_bytes, as_stream(stream)>>>(a, table);
+        else conv_any_kernel<<<grid, dim3(256), ktab_bytes, as_stream(stream)>>>(a);
         IPSX_TRY(launched("conv2d_affine"));
     }
     return IPSX_OK;

@@ -294,18 +294,44 @@ constexpr int SP_SLAB = SPW * SPW + 64;   // floats per wave (+ slack: lanes 25.
 
 __device__ __forceinline__ float fs_max3(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
 
-__global__ __launch_bounds__(256, 2) void stem_pool50_kernel(StemArgs a) {
+// U8: a.patches holds uint8 pixels (2,500 B per patch: 4-byte aligned, dword loads) and `table` (256 floats, device) their
+// float32 values; each wavefront keeps a copy of the table behind its slab (SP_SLAB_U8) and stages the image's pixels - not
+// the padding, which stays 0.0f - through it.  Everything behind the staged image is the float32 kernel.
+constexpr int SP_SLAB_U8 = SP_SLAB + 256;
+
+template <bool U8>
+__device__ __forceinline__ void stem_pool50_body(const StemArgs& a, const float* table) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, half = lane >> 5;
     long long p = (long long)blockIdx.x * 4 + wave;
     const bool live = p < a.n;
     if (!live) p = a.n - 1;                                  // tail: recompute the last patch, store nothing
-    float* S = lds + wave * SP_SLAB;
+    float* S = lds + wave * (U8 ? SP_SLAB_U8 : SP_SLAB);
     // ---- the patch -> LDS, zero-padded (image at rows / columns 3..52)
     for (int z = lane; z < SP_SLAB / 4; z += 64) reinterpret_cast<float4*>(S)[z] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (U8) reinterpret_cast<float4*>(S + SP_SLAB)[lane] = reinterpret_cast<const float4*>(table)[lane];
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    {
+    if constexpr (U8) {
+        const float* tab = S + SP_SLAB;
+        const unsigned* src = reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(a.patches) + (size_t)p * 2500);
+        for (int e0 = lane; e0 < 625; e0 += 64 * 5) {
+            unsigned v[5];
+#pragma unroll
+            for (int u = 0; u < 5; ++u) v[u] = src[e0 + 64 * u < 625 ? e0 + 64 * u : e0];
+#pragma unroll
+            for (int u = 0; u < 5; ++u) {
+                const int e = e0 + 64 * u;
+                if (e < 625) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {                    // a dword may straddle two image rows (50 B each)
+                        const int b = 4 * e + j, yy = b / 50, xx = b - yy * 50;
+                        S[(yy + 3) * SPW + xx + 3] = tab[(v[u] >> (8 * j)) & 0xFFu];
+                    }
+                }
+            }
+        }
+    } else {
         const float2* src = reinterpret_cast<const float2*>(a.patches + (size_t)p * 2500);
         for (int e0 = lane; e0 < 1250; e0 += 64 * 5) {
             float2 v[5];
@@ -412,6 +438,9 @@ __global__ __launch_bounds__(256, 2) void stem_pool50_kernel(StemArgs a) {
     }
 }
 
+__global__ __launch_bounds__(256, 2) void stem_pool50_kernel(StemArgs a) { stem_pool50_body<false>(a, nullptr); }
+__global__ __launch_bounds__(256, 2) void stem_pool50_u8_kernel(StemArgs a, const float* table) { stem_pool50_body<true>(a, table); }
+
 // ------------------------------------------------------------------------------------------------ stem + max-pool, 3 x 100 px
 // The traffic-sign configuration's stem (config/traffic_config.yml: 3x100x100 patches -> 50x50x64 -> 25x25x64 pooled), same
 // scheme as stem_pool50_kernel with three input planes: ONE patch per workgroup (the zero-padded 3 x 106 x 106 image fills
@@ -435,15 +464,47 @@ __host__ __device__ constexpr int s3_off(int k) {
     return k >= 147 ? 0 : (k % 3) * S3PLANE + ((k / 3) / 7) * S3W + (k / 3) % 7;
 }
 
-__global__ __launch_bounds__(256, 1) void stem_pool100x3_kernel(Stem3Args a) {
+// U8: a.patches holds uint8 pixels (30,000 B per patch: 16-byte aligned, 16-byte loads) and `table` (3 x 256 floats, device)
+// their float32 values per channel; the workgroup's copy of the table lies behind the padded planes (S3_FLOATS_U8).  Only
+// the image's pixels go through the table; the padding stays 0.0f.
+constexpr int S3_FLOATS_U8 = S3_FLOATS + 3 * 256;
+
+template <bool U8>
+__device__ __forceinline__ void stem_pool100x3_body(const Stem3Args& a, const float* table) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, half = lane >> 5;
     const long long p = blockIdx.x;
     float* S = lds;
     for (int z = threadIdx.x; z < S3_FLOATS / 4; z += 256) reinterpret_cast<float4*>(S)[z] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (U8) {
+        if (threadIdx.x < 192) reinterpret_cast<float4*>(S + S3_FLOATS)[threadIdx.x] = reinterpret_cast<const float4*>(table)[threadIdx.x];
+    }
     __syncthreads();
-    {   // 3 x 100 x 100 floats, rows of 25 float4 -> image at rows / columns 3..102 of every plane
+    if constexpr (U8) {   // 3 x 100 x 100 bytes as 1,875 16-byte units; a dword (4 pixels) lies inside one image row (25 per row)
+        const float* tab = S + S3_FLOATS;
+        const uint4* src = reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(a.patches) + (size_t)p * 30000);
+        for (int e0 = threadIdx.x; e0 < 1875; e0 += 256 * 4) {
+            uint4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = src[e0 + 256 * u < 1875 ? e0 + 256 * u : e0];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int e = e0 + 256 * u;
+                if (e < 1875) {
+                    const unsigned w[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int dw = 4 * e + k, c = dw / 2500, rem = dw - c * 2500, yy = rem / 25, xx = 4 * (rem - yy * 25);
+                        float* d = S + c * S3PLANE + (yy + 3) * S3W + xx + 3;
+                        const float* tc = tab + 256 * c;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) d[j] = tc[(w[k] >> (8 * j)) & 0xFFu];
+                    }
+                }
+            }
+        }
+    } else {   // 3 x 100 x 100 floats, rows of 25 float4 -> image at rows / columns 3..102 of every plane
         const float4* src = reinterpret_cast<const float4*>(a.patches + (size_t)p * 30000);
         for (int e0 = threadIdx.x; e0 < 7500; e0 += 256 * 8) {
             float4 v[8];
@@ -589,6 +650,9 @@ __global__ __launch_bounds__(256, 1) void stem_pool100x3_kernel(Stem3Args a) {
     }
 }
 
+__global__ __launch_bounds__(256, 1) void stem_pool100x3_kernel(Stem3Args a) { stem_pool100x3_body<false>(a, nullptr); }
+__global__ __launch_bounds__(256, 1) void stem_pool100x3_u8_kernel(Stem3Args a, const float* table) { stem_pool100x3_body<true>(a, table); }
+
 static bool stem_pool100x3_supported(const ipsx_trunk* t) {
     const char* e = getenv("IPSX_NO_FUSED");
     if (e && e[0] == '1') return false;
@@ -609,7 +673,8 @@ bool fused_stem_pool50_covers(const ipsx_trunk* t) { return t && stem_pool50_sup
 bool fused_stem_pool100x3_covers(const ipsx_trunk* t) { return t && stem_pool100x3_supported(t); }
 
 // stem + max-pool of 1x50x50 patches -> (n, 13, 13, 64) channels-last; returns 1 when it ran, 0 when the trunk is another shape
-int fused_stem_pool50(const ipsx_trunk* t, const float* patches, float* y, int64_t n, hipStream_t s) {
+// table != nullptr: `patches` holds uint8 pixels, table (c_in x 256 floats, device, 16-byte aligned) their float32 values
+int fused_stem_pool50(const ipsx_trunk* t, const float* patches, float* y, int64_t n, hipStream_t s, const float* table) {
     if (t && stem_pool100x3_supported(t)) {                            // the traffic-sign stem: one patch per workgroup
         if (n <= 0) return 1;
         Stem3Args a3;
@@ -619,9 +684,19 @@ int fused_stem_pool50(const ipsx_trunk* t, const float* patches, float* y, int64
         if (!attr3) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem_pool100x3_kernel),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S3_FLOATS * sizeof(float)));
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem_pool100x3_u8_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S3_FLOATS_U8 * sizeof(float)));
             attr3 = true;
         }
-        stem_pool100x3_kernel<<<dim3((unsigned)n), dim3(256), S3_FLOATS * sizeof(float), s>>>(a3);
+        if (table) {
+            if (reinterpret_cast<uintptr_t>(patches) % 16 || reinterpret_cast<uintptr_t>(table) % 16) {
+                fail(IPSX_EINVAL, "stem_pool100x3: uint8 patches and their table must lie at 16-byte addresses");
+                return -1;
+            }
+            stem_pool100x3_u8_kernel<<<dim3((unsigned)n), dim3(256), S3_FLOATS_U8 * sizeof(float), s>>>(a3, table);
+        } else {
+            stem_pool100x3_kernel<<<dim3((unsigned)n), dim3(256), S3_FLOATS * sizeof(float), s>>>(a3);
+        }
         return launched("stem_pool100x3") == IPSX_OK ? 1 : -1;
     }
     if (!t || !stem_pool50_supported(t)) return 0;
@@ -629,7 +704,15 @@ int fused_stem_pool50(const ipsx_trunk* t, const float* patches, float* y, int64
     StemArgs a;
     a.patches = patches; a.y = y; a.n = n;
     a.w = t->stem.w_packed; a.al = t->stem.alpha; a.sh = t->stem.shift;
-    stem_pool50_kernel<<<dim3((unsigned)cdiv(n, 4)), dim3(256), 4 * SP_SLAB * sizeof(float), s>>>(a);
+    if (table) {
+        if (reinterpret_cast<uintptr_t>(patches) % 4 || reinterpret_cast<uintptr_t>(table) % 16) {
+            fail(IPSX_EINVAL, "stem_pool50: uint8 patches must lie at a 4-byte address, their table at a 16-byte address");
+            return -1;
+        }
+        stem_pool50_u8_kernel<<<dim3((unsigned)cdiv(n, 4)), dim3(256), 4 * SP_SLAB_U8 * sizeof(float), s>>>(a, table);
+    } else {
+        stem_pool50_kernel<<<dim3((unsigned)cdiv(n, 4)), dim3(256), 4 * SP_SLAB * sizeof(float), s>>>(a);
+    }
     return launched("stem_pool50") == IPSX_OK ? 1 : -1;
 }
 

@@ -488,15 +488,41 @@ constexpr int WPB = 4;
         }                                                                                  \
     } while (0)
 
+// uint8 patches: byte b of channel c stands for table[c][b] (ipsx_trunk_encode_u8).  A wavefront's copy of the 256-entry
+// table sits in its slab BEHIND the padded 38x38 image (floats U8_TAB ..), which the stem never reads and store_l1 overwrites
+// once the image is dead - no LDS beyond the slab, no workgroup barrier.  Only the image's pixels go through the table: the
+// padding stays 0.0f.
+constexpr int U8_TAB = 1448;         // >= 38 * 38, a multiple of 4; U8_TAB + 2 * 256 <= ZP1 * PS1 (the pair kernel keeps two copies)
+
+// this lane's 16 consecutive bytes of a 1x32x32 uint8 patch (ONE 16-byte load: pixels 16 lane .. 16 lane + 15, half an image
+// row) -> the padded image in S through the table copy `tab` (LDS)
+__device__ __forceinline__ void stage_u8_row16(const uint4 q, const float* tab, float* S, int lane) {
+    const unsigned w[4] = {q.x, q.y, q.z, q.w};
+    float* d = S + ((lane >> 1) + 3) * PW + 16 * (lane & 1) + 3;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) d[4 * k + j] = tab[(w[k] >> (8 * j)) & 0xFFu];
+}
+
 // one patch by one wavefront on its own slab S: the input load and the stem + pool, whose output is left in the slab in
 // the 8x8 stage's layout, behind a workgroup barrier (layer1 reads every slab) - the front of fused_trunk_kernel
-template <bool STAMP, int WPB>
+// U8: a.patches holds uint8 pixels, `table` (256 floats, device) their float32 values
+template <bool STAMP, int WPB, bool U8 = false>
 __device__ __forceinline__ void trunk_front(const FusedArgs& a, long long pi, float* S, int lane, int wave,
-                                            unsigned long long* stamps) {
+                                            unsigned long long* stamps, const float* table = nullptr) {
     IPSX_STAMP(0);
 
     // ---- input patch -> slab as a zero-padded 38x38 image (coalesced 16 B global loads)
-    {
+    if constexpr (U8) {
+        const uint4 q = reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(a.patches) + (size_t)pi * 1024)[lane];
+        const float4 tv = reinterpret_cast<const float4*>(table)[lane];
+        for (int z = lane; z < (PW * PW + 3) / 4; z += 64) reinterpret_cast<float4*>(S)[z] = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int z = lane; z < PS1; z += 64) S[ZP1 * PS1 + z] = 0.0f;          // zero pixel row of the 8x8 stage
+        reinterpret_cast<float4*>(S + U8_TAB)[lane] = tv;
+        wave_fence();                                                      // the table copy is whole before any lane reads it
+        stage_u8_row16(q, S + U8_TAB, S, lane);
+    } else {
         const float4* src = reinterpret_cast<const float4*>(a.patches + (size_t)pi * 1024);
         float4 px[4];
 #pragma unroll
@@ -1116,8 +1142,8 @@ __device__ __forceinline__ void layer1_p1(const FusedArgs& a, float* lds, int la
     }
 }
 
-template <bool STAMP>
-__global__ __launch_bounds__(512, 1) void fused_trunk_kernel(FusedArgs a, unsigned long long* stamps) {
+template <bool STAMP, bool U8>
+__device__ __forceinline__ void fused_trunk_body(const FusedArgs& a, unsigned long long* stamps, const float* table) {
     extern __shared__ __attribute__((aligned(16))) float lds[];          // 8 slabs of SLAB8
     constexpr int WPB = 8;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1128,7 +1154,7 @@ __global__ __launch_bounds__(512, 1) void fused_trunk_kernel(FusedArgs a, unsign
     long long pi = p_first + wave;
     if (pi >= n_valid) pi = n_valid - 1;                                  // tail: recompute a valid patch, store nothing
     if (a.index) pi = a.index[pi];
-    trunk_front<STAMP, WPB>(a, pi, lds + wave * SLAB8, lane, wave, stamps);
+    trunk_front<STAMP, WPB, U8>(a, pi, lds + wave * SLAB8, lane, wave, stamps, table);
     switch (__builtin_amdgcn_readfirstlane((wave + 2 * (wave >> 2)) & 3)) {  // the wave's layer1 tile set, see conv_p1
         case 0: layer1_p1<STAMP, 0>(a, lds, lane, wave, stamps); break;
         case 1: layer1_p1<STAMP, 1>(a, lds, lane, wave, stamps); break;
@@ -1194,6 +1220,16 @@ __global__ __launch_bounds__(512, 1) void fused_trunk_kernel(FusedArgs a, unsign
         if (p_first + pl < n_valid) a.emb[(size_t)(p_first + pl) * 128 + n] = sum / 16.0f;
     }
     IPSX_STAMP(15);
+}
+
+template <bool STAMP>
+__global__ __launch_bounds__(512, 1) void fused_trunk_kernel(FusedArgs a, unsigned long long* stamps) {
+    fused_trunk_body<STAMP, false>(a, stamps, nullptr);
+}
+
+// the same on uint8 patches (a.patches: bytes; table: 256 floats) - only the input load differs (trunk_front)
+__global__ __launch_bounds__(512, 1) void fused_trunk_u8_kernel(FusedArgs a, const float* table) {
+    fused_trunk_body<false, true>(a, nullptr, table);
 }
 
 #include "fused_trunk_split.h"
@@ -1371,12 +1407,20 @@ static int device_cus() {
     return cus[dev];
 }
 
+// table != nullptr: `patches` holds uint8 pixels (at a 16-byte address) and table[b] is the float32 value of byte b - the
+// exact fp32 trunk only, no stamps, no device-side count (ipsx_trunk_encode_u8 / _indexed_u8)
 static int fused_launch(const ipsx_trunk* t, const float* patches, int64_t n, float* emb,
                         unsigned long long* stamps, hipStream_t s, const int* index = nullptr,
-                        const int* count = nullptr) {
+                        const int* count = nullptr, const float* table = nullptr) {
     FusedArgs a;
     a.patches = patches; a.emb = emb; a.n = n; a.index = index; a.count = count;
     a.in_dtype = t->patch_dtype;
+    if (table) {
+        if (t->precision != 0 || t->patch_dtype != 0 || stamps || count)
+            return fail(IPSX_EINVAL, "fused trunk: uint8 patches go with the exact fp32 trunk (precision 0, patch_dtype 0) only");
+        if (reinterpret_cast<uintptr_t>(patches) % 16 || reinterpret_cast<uintptr_t>(table) % 16)
+            return fail(IPSX_EINVAL, "fused trunk: uint8 patches and their table must lie at 16-byte addresses");
+    }
     if (t->patch_dtype != 0 && !(t->precision == 1 || t->precision == 2))
         return fail(IPSX_EINVAL, "fused trunk: half-precision patch storage goes with precision 1 (bf16) or 2 (fp32x3)");
     if (t->patch_dtype < 0 || t->patch_dtype > 2) return fail(IPSX_EINVAL, "fused trunk: patch_dtype %d", t->patch_dtype);
@@ -1478,6 +1522,23 @@ static int fused_launch(const ipsx_trunk* t, const float* patches, int64_t n, fl
     }
     const int64_t n_full = n - rest;
     a.n = n_full;
+    if (table) {
+        static bool attr_u8 = false;
+        if (!attr_u8) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_u8_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            attr_u8 = true;
+        }
+        if (n_full) fused_trunk_u8_kernel<<<dim3((unsigned)cdiv(n_full, 8)), dim3(512), lds, s>>>(a, table);
+        if (rest) {
+            a.n = rest;
+            if (index) a.index = index + n_full;
+            else a.patches = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(patches) + (size_t)n_full * 1024);
+            a.emb = emb + (size_t)n_full * 128;
+            fused_trunk_pair_u8_kernel<<<dim3((unsigned)cdiv(rest, 2)), dim3(256), (size_t)2 * SLAB * sizeof(float), s>>>(a, table);
+        }
+        return launched("fused_trunk_u8");
+    }
     if (stamps)
         fused_trunk_kernel<true><<<dim3((unsigned)cdiv(n, 8)), dim3(512), lds, s>>>(a, stamps);
     else if (n_full)
@@ -1541,6 +1602,12 @@ int fused_trunk_encode(const ipsx_trunk* t, const float* patches, int64_t n, flo
 int fused_trunk_encode_indexed(const ipsx_trunk* t, const float* patches, int64_t n_max, const int* index,
                                const int* count, float* emb, hipStream_t s) {
     return fused_launch(t, patches, n_max, emb, nullptr, s, index, count);
+}
+
+// uint8 patches through table (256 floats, device); index: optional int32 patch numbers (nullptr: patches 0 .. n - 1)
+int fused_trunk_encode_u8(const ipsx_trunk* t, const unsigned char* patches, const float* table, int64_t n, const int* index,
+                          float* emb, hipStream_t s) {
+    return fused_launch(t, reinterpret_cast<const float*>(patches), n, emb, nullptr, s, index, nullptr, table);
 }
 
 }  // namespace ipsx

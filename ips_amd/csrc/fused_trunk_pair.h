@@ -223,8 +223,10 @@ __device__ __forceinline__ void store_l2_pair(float* lds, const f32x16& v, int l
 
 // two patches p_first, p_first + 1 by the workgroup's four wavefronts; KEEP: the two embeddings are also left in
 // lds[0 .. 255] (behind a barrier) for a caller that goes on with them (fused_trunk_stream_kernel: the logits)
-template <bool KEEP>
-__device__ __forceinline__ void trunk_pair_tile(const FusedArgs& a, long long p_first, float* lds) {
+// U8: a.patches holds uint8 pixels, `table` (256 floats, device) their float32 values - each wavefront of a pair keeps its
+// own copy of the table behind the padded image (U8_TAB, fused_trunk.hip) and stages its half of the patch through it
+template <bool KEEP, bool U8 = false>
+__device__ __forceinline__ void trunk_pair_tile(const FusedArgs& a, long long p_first, float* lds, const float* table = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ps = wave >> 1, nh = wave & 1;                              // patch slot of the workgroup, n-tile of the pair
     const int i = lane & 31;
@@ -234,7 +236,23 @@ __device__ __forceinline__ void trunk_pair_tile(const FusedArgs& a, long long p_
     float* S = lds + ps * SLAB;
 
     // ---- input patch -> slab as a zero-padded 38x38 image, half of it per wavefront
-    {
+    if constexpr (U8) {
+        // 8 bytes per lane: pixels 512 nh + 8 lane .. + 7 (a quarter of an image row)
+        const uint2 q = reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned char*>(a.patches) + (size_t)pi * 1024)[64 * nh + lane];
+        const float4 tv = reinterpret_cast<const float4*>(table)[lane];
+        float* tab = S + U8_TAB + 256 * nh;
+        for (int z = lane + 64 * nh; z < (PW * PW + 3) / 4; z += 128) reinterpret_cast<float4*>(S)[z] = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int z = lane + 64 * nh; z < PS1; z += 128) S[ZP1 * PS1 + z] = 0.0f;
+        reinterpret_cast<float4*>(tab)[lane] = tv;
+        __syncthreads();                                                  // the padding is laid by both waves of the pair
+        const int e = (64 * nh + lane) * 8, y = e >> 5, x = e & 31;
+        float* d = S + (y + 3) * PW + x + 3;
+        const unsigned w[2] = {q.x, q.y};
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) d[4 * k + j] = tab[(w[k] >> (8 * j)) & 0xFFu];
+    } else {
         const float4* src = reinterpret_cast<const float4*>(a.patches + (size_t)pi * 1024);
         float4 px[2];
 #pragma unroll
@@ -348,6 +366,12 @@ __device__ __forceinline__ void trunk_pair_tile(const FusedArgs& a, long long p_
 __global__ __launch_bounds__(256, 2) void fused_trunk_pair_kernel(FusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];          // 2 slabs
     trunk_pair_tile<false>(a, (long long)blockIdx.x * 2, lds);
+}
+
+// the same on uint8 patches (a.patches: bytes; table: 256 floats)
+__global__ __launch_bounds__(256, 2) void fused_trunk_pair_u8_kernel(FusedArgs a, const float* table) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];          // 2 slabs
+    trunk_pair_tile<false, true>(a, (long long)blockIdx.x * 2, lds, table);
 }
 
 // ------------------------------------------------------------------ one image as ONE persistent launch

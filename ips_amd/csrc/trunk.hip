@@ -17,11 +17,12 @@ namespace ipsx {
 
 // conv.hip
 int conv2d_affine_impl(const ipsx_conv* cv, const float* x, const float* residual, float* y, int64_t n, int h,
-                       int w, int relu, int out_nhwc, void* stream);
+                       int w, int relu, int out_nhwc, void* stream, const float* table = nullptr);   // table: x holds uint8
 // fused_stage.hip: the leading 64 -> 64 BasicBlocks on a small map, LDS-resident (50-px patches: 13x13)
 int fused_stage64_blocks(const ipsx_block* blocks, int n_block, int h, int w);
 int fused_stage64(const ipsx_block* blocks, int n_block, const float* x, float* y, int64_t n, int h, int w, hipStream_t s);
-int fused_stem_pool50(const ipsx_trunk* t, const float* patches, float* y, int64_t n, hipStream_t s);   // 1 = ran, 0 = other shape
+int fused_stem_pool50(const ipsx_trunk* t, const float* patches, float* y, int64_t n, hipStream_t s,
+                      const float* table = nullptr);   // 1 = ran, 0 = other shape; table: patches holds uint8
 bool fused_stem_pool50_covers(const ipsx_trunk* t);
 bool fused_stem_pool100x3_covers(const ipsx_trunk* t);
 // conv_nhwc_bf16.hip: the pooled fp32 map rounded once to bf16 (count % 8 == 0)
@@ -29,6 +30,8 @@ int round_to_bf16(const float* x, void* y, size_t count, hipStream_t s);
 // fused_trunk.hip
 bool fused_trunk_supported(const ipsx_trunk* t);
 int fused_trunk_encode(const ipsx_trunk* t, const float* patches, int64_t n, float* emb, hipStream_t s);
+int fused_trunk_encode_u8(const ipsx_trunk* t, const unsigned char* patches, const float* table, int64_t n, const int* index,
+                          float* emb, hipStream_t s);
 int fused_trunk_stream(const ipsx_trunk* t, const float* patches, int64_t n, float* emb, const float* pos, const float* v_packed,
                        int r, float* logits, int32_t* ctl, int32_t* ready, int workgroups, int quad_pulls, hipStream_t s);
 
@@ -143,11 +146,17 @@ IPSX_API const char* ipsx_trunk_kernel(const ipsx_trunk* t) {
     return "conv_nhwc_kernel (layer by layer)";
 }
 
-IPSX_API int ipsx_trunk_encode(const ipsx_trunk* t, const float* patches, int64_t n_patch, float* emb,
-                               void* workspace, size_t workspace_bytes, void* stream) {
+// ipsx_trunk_encode and ipsx_trunk_encode_u8: table == nullptr - `patches_v` holds float32 (or, fused split trunks,
+// t->patch_dtype) elements; else uint8 elements whose values are table[channel][byte] - only the stem's load differs
+static int trunk_encode(const ipsx_trunk* t, const void* patches_v, const float* table, int64_t n_patch, float* emb,
+                        void* workspace, size_t workspace_bytes, void* stream) {
     TrunkGeom g;
     IPSX_TRY(trunk_geom(t, &g));
+    const float* patches = static_cast<const float*>(patches_v);
+    const unsigned char* patches_u8 = static_cast<const unsigned char*>(patches_v);
     IPSX_REQUIRE(patches && emb && n_patch >= 0, "trunk_encode: bad arguments");
+    IPSX_REQUIRE(!table || (t->precision == 0 && t->patch_dtype == 0), "trunk_encode_u8: uint8 patches go with the exact fp32 "
+                 "trunk only (precision 0, patch_dtype 0), got precision %d, patch_dtype %d", t->precision, t->patch_dtype);
     const bool fused = fused_trunk_supported(t);
     IPSX_REQUIRE(t->precision >= 0 && t->precision <= 2, "trunk_encode: precision %d", t->precision);
     IPSX_REQUIRE(t->precision != 2 || fused, "trunk_encode: fp32x3 exists for the fused 1x32x32 trunk only");
@@ -158,6 +167,7 @@ IPSX_API int ipsx_trunk_encode(const ipsx_trunk* t, const float* patches, int64_
     const bool bf16 = t->precision == 1 && !fused;       // ("bf16 layered trunk")
     if (bf16) IPSX_TRY(layered_bf16_check(t));
     if (n_patch == 0) return IPSX_OK;
+    if (fused && table) return fused_trunk_encode_u8(t, patches_u8, table, n_patch, nullptr, emb, as_stream(stream));
     if (fused) return fused_trunk_encode(t, patches, n_patch, emb, as_stream(stream));
 
     const int64_t chunk = workspace ? chunk_for(g, n_patch, workspace_bytes) : 0;      // chunks fit what the caller gave
@@ -180,10 +190,11 @@ IPSX_API int ipsx_trunk_encode(const ipsx_trunk* t, const float* patches, int64_
         int w = conv_out(t->w, t->stem.kw, t->stem.stride, t->stem.pad);
         int c = t->stem.c_out;
         // stem reads the NCHW patches and writes channels-last; everything after it is channels-last
-        const int fused_stem = fused_stem_pool50(t, patches + p0 * patch_elems, buf[1], n, as_stream(stream));
+        const float* chunk_in = table ? reinterpret_cast<const float*>(patches_u8 + p0 * patch_elems) : patches + p0 * patch_elems;
+        const int fused_stem = fused_stem_pool50(t, chunk_in, buf[1], n, as_stream(stream), table);
         if (fused_stem < 0) return IPSX_EHIP;
         if (!fused_stem) {
-            IPSX_TRY(conv2d_affine_impl(&t->stem, patches + p0 * patch_elems, nullptr, buf[0], n, t->h, t->w, 1, 1, stream));
+            IPSX_TRY(conv2d_affine_impl(&t->stem, chunk_in, nullptr, buf[0], n, t->h, t->w, 1, 1, stream, table));
             IPSX_TRY(ipsx_maxpool_3x3s2_nhwc(buf[0], buf[1], n, c, h, w, stream));
         }
         h = conv_out(h, 3, 2, 1); w = conv_out(w, 3, 2, 1);
@@ -259,6 +270,26 @@ IPSX_API int ipsx_trunk_encode(const ipsx_trunk* t, const float* patches, int64_
         IPSX_TRY(ipsx_avgpool_nhwc(buf[cur], emb + (size_t)p0 * g.d_out, n, c, h * w, stream));
     }
     return IPSX_OK;
+}
+
+IPSX_API int ipsx_trunk_encode(const ipsx_trunk* t, const float* patches, int64_t n_patch, float* emb,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+    return trunk_encode(t, patches, nullptr, n_patch, emb, workspace, workspace_bytes, stream);
+}
+
+IPSX_API int ipsx_trunk_encode_u8(const ipsx_trunk* t, const uint8_t* patches, const float* table, int64_t n_patch, float* emb,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    IPSX_REQUIRE(table, "trunk_encode_u8: no table");
+    return trunk_encode(t, patches, table, n_patch, emb, workspace, workspace_bytes, stream);
+}
+
+IPSX_API int ipsx_trunk_encode_indexed_u8(const ipsx_trunk* t, const uint8_t* patches, const float* table, const int32_t* index,
+                                          int64_t n_index, float* emb, void* stream) {
+    IPSX_REQUIRE(t && patches && table && index && emb && n_index >= 0, "trunk_encode_indexed_u8: bad arguments");
+    IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_indexed_u8: only the fused 1x32x32 trunk is supported");
+    IPSX_REQUIRE(t->precision == 0 && t->patch_dtype == 0, "trunk_encode_indexed_u8: uint8 patches go with the exact fp32 trunk only");
+    if (n_index == 0) return IPSX_OK;
+    return fused_trunk_encode_u8(t, patches, table, n_index, index, emb, as_stream(stream));
 }
 
 // One image: trunk AND logits of its patches as ONE persistent launch that feeds ipsx_scan_persistent patch by patch

@@ -375,6 +375,8 @@ def ips_sharded(net, local_patches, N, group=None, timings=None, plan=None):
     ``timings`` (GPU path only): a list that receives one dict of HIP events per call - see ``phase_ms`` - so that a
     run can say where a rank's time went (encoder, exchange, loop, what of the loop stayed exposed).
     """
+    if local_patches.dtype == torch.uint8:
+        raise TypeError("sharded IPS reads float32 patches (uint8 patch storage: IPSNet.ips on one device)")
     world, rank = _world_rank(group)
     M, I, D = net.M, net.I, net.D
     if M >= N:

@@ -299,6 +299,11 @@ _EXPORTS = {
     "ipsx_set_persistent_wait_ms": (C.c_int, [C.c_int]),
     "ipsx_scan_gate": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ipsx_trunk_encode_indexed": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ipsx_trunk_encode_u8": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                       C.c_size_t, C.c_void_p]),
+    "ipsx_trunk_encode_indexed_u8": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                               C.c_void_p]),
+    "ipsx_dequant_patches": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "ipsx_scores_workspace_bytes": (C.c_size_t, [C.c_int] * 5),
     "ipsx_scores": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 +
                     [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -414,9 +419,31 @@ def _f32(t):
 _PATCH_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
-def _patches(t):
+def _patch_table(table, n_chan, device):
+    """A dequantisation table as the uint8 entry points take it: (n_chan, 256) float32, contiguous, on ``device``."""
+    from .quant import check_table
+    check_table(table, n_chan)
+    if table.device != device:
+        raise ValueError("the patch table lies on {}, the patches on {}".format(table.device, device))
+    return table if table.is_contiguous() else table.contiguous()
+
+
+def _patches(t, table=None):
     """Patch tensors may be stored in bfloat16 / float16 (BASELINE configs[4]); only the reduced-precision fused trunks
-    read those (the exact path's contract is float32 in)."""
+    read those (the exact path's contract is float32 in).  uint8 patches go with a ``table`` (n_chan, 256) on the exact
+    path only: its stems look every byte up (``ips_amd.quant``); everything is checked here, before the first launch."""
+    if t.dtype == torch.uint8:
+        if table is None:
+            raise TypeError("uint8 patches need a dequantisation table: IPSNet.set_patch_table(ips_amd.quant.patch_table(...)) "
+                            "(EncoderPlan.encode(..., table=))")
+        if precision() != "fp32":
+            raise TypeError("uint8 patches go with the exact trunk (IPSX_PRECISION=fp32), not {}".format(precision()))
+        if dedup_blank():
+            raise TypeError("blank-patch dedup reads float32 patches (IPSX_DEDUP_BLANK=1 with uint8 patches)")
+        _patch_table(table, t.shape[-3], t.device)
+        return t if t.is_contiguous() else t.contiguous()
+    if table is not None:
+        raise TypeError("a patch table goes with uint8 patches, got {}".format(t.dtype))
     if t.dtype not in _PATCH_DTYPES:
         raise TypeError("patches must be float32, bfloat16 or float16, got {}".format(t.dtype))
     if t.dtype != torch.float32 and precision() == "fp32":
@@ -787,6 +814,20 @@ def gather_rows(src, idx):
     bstride = N if src.shape[0] > 1 else 0
     _ck(lib().ipsx_gather_rows(_p(src), _p(idx), _p(out), B, N, M, row_bytes, bstride, _stream()),
         "ipsx_gather_rows")
+    return out
+
+
+def dequant_patches(q, table):
+    """uint8 patches (..., C, h, w) on the GPU -> float32 of the same shape, ``table[c][q]`` (``table``: (C, 256) float32,
+    ``ips_amd.quant.patch_table``).  For the M patches a selection keeps: what leaves ``ips()`` is float32."""
+    if q.dtype != torch.uint8 or q.dim() < 3:
+        raise TypeError("expected uint8 (..., C, h, w) patches, got {} {}".format(q.dtype, tuple(q.shape)))
+    table = _patch_table(table, q.shape[-3], q.device)
+    q = q if q.is_contiguous() else q.contiguous()
+    out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+    c, hw = q.shape[-3], q.shape[-2] * q.shape[-1]
+    _ck(lib().ipsx_dequant_patches(_p(q), _p(table), _p(out), q.numel() // max(1, c * hw), c, hw, _stream()),
+        "ipsx_dequant_patches")
     return out
 
 

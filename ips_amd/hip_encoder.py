@@ -9,7 +9,7 @@ import os
 
 import torch
 
-from .hip import (lib, _ck, _p, _f32, _stream, _patches, _PATCH_DTYPES, Conv, Block, Trunk, precision, dedup_blank, weights_generation)
+from .hip import (lib, _ck, _p, _f32, _stream, _patches, _patch_table, _PATCH_DTYPES, Conv, Block, Trunk, precision, dedup_blank, weights_generation)
 
 
 # ------------------------------------------------------------------ encoder plan
@@ -245,12 +245,17 @@ class EncoderPlan:
         self.trunk.h, self.trunk.w = x_shape[-2], x_shape[-1]
         return x_shape[-3] == self.trunk.c_in and lib().ipsx_trunk_kernel(C.byref(self.trunk)).startswith(b"fused")
 
-    def encode_indexed(self, flat, index):
-        """flat (P, C, h, w) contiguous on the GPU, index (n,) int32 -> (n, D) embeddings of flat[index]."""
+    def encode_indexed(self, flat, index, table=None):
+        """flat (P, C, h, w) contiguous on the GPU, index (n,) int32 -> (n, D) embeddings of flat[index].  uint8 ``flat``
+        with its ``table`` (C, 256): the embeddings of ``table[c][flat]`` (``ipsx_trunk_encode_indexed_u8``)."""
         self._refresh()
-        flat = _patches(flat)
-        self.trunk.patch_dtype = _PATCH_DTYPES[flat.dtype]
+        flat = _patches(flat, table)
         out = torch.empty((index.numel(), self.d_out), dtype=torch.float32, device=flat.device)
+        if table is not None:
+            _ck(lib().ipsx_trunk_encode_indexed_u8(C.byref(self.trunk), _p(flat), _p(_patch_table(table, flat.shape[1], flat.device)),
+                                                   _p(index), index.numel(), _p(out), _stream()), "ipsx_trunk_encode_indexed_u8")
+            return out
+        self.trunk.patch_dtype = _PATCH_DTYPES[flat.dtype]
         try:
             _ck(lib().ipsx_trunk_encode_indexed(C.byref(self.trunk), _p(flat), _p(index), index.numel(), _p(out),
                                                 _stream()), "ipsx_trunk_encode_indexed")
@@ -258,13 +263,23 @@ class EncoderPlan:
             self.trunk.patch_dtype = 0
         return out
 
-    def encode_plain(self, x, out=None):
-        """The image trunk on every patch of ``x`` (no dedup)."""
-        x = _patches(x)
+    def encode_plain(self, x, out=None, table=None):
+        """The image trunk on every patch of ``x`` (no dedup).  uint8 ``x`` with its ``table`` (C, 256): the same calls
+        through ``ipsx_trunk_encode_u8``, whose stems look the bytes up."""
+        x = _patches(x, table)
         n = x.shape[0]
         if out is None:
             out = torch.empty((n, self.d_out), dtype=torch.float32, device=x.device)
-        self.trunk.patch_dtype = _PATCH_DTYPES[x.dtype]
+        if table is not None:
+            tab = _p(_patch_table(table, x.shape[1], x.device))
+
+            def run(xs, cnt, outs, ws, nb):
+                _ck(lib().ipsx_trunk_encode_u8(C.byref(self.trunk), _p(xs), tab, cnt, _p(outs), _p(ws), nb, _stream()),
+                    "ipsx_trunk_encode_u8")
+        else:
+            def run(xs, cnt, outs, ws, nb):
+                _ck(lib().ipsx_trunk_encode(C.byref(self.trunk), _p(xs), cnt, _p(outs), _p(ws), nb, _stream()), "ipsx_trunk_encode")
+        self.trunk.patch_dtype = 0 if table is not None else _PATCH_DTYPES[x.dtype]
         try:
             # Layer-by-layer trunks: the batch goes through in two halves on two streams.  The stem and the max-pool are
             # HBM-bound (together 11-13 % of the trunk's time for 1 % of its arithmetic), the residual stages MFMA-bound:
@@ -288,16 +303,14 @@ class EncoderPlan:
                     st = self._sides[k - 1]
                     st.wait_stream(main)
                     with torch.cuda.stream(st):
-                        _ck(lib().ipsx_trunk_encode(C.byref(self.trunk), _p(x[cuts[k]:cuts[k + 1]]), cuts[k + 1] - cuts[k],
-                                                    _p(out[cuts[k]:cuts[k + 1]]), _p(ws[k * nb:]), nb, _stream()), "ipsx_trunk_encode")
-                _ck(lib().ipsx_trunk_encode(C.byref(self.trunk), _p(x[:cuts[1]]), cuts[1], _p(out[:cuts[1]]), _p(ws[:nb]), nb, _stream()),
-                    "ipsx_trunk_encode")
+                        run(x[cuts[k]:cuts[k + 1]], cuts[k + 1] - cuts[k], out[cuts[k]:cuts[k + 1]], ws[k * nb:], nb)
+                run(x[:cuts[1]], cuts[1], out[:cuts[1]], ws[:nb], nb)
                 for st in self._sides[:ns - 1]:
                     main.wait_stream(st)
                 return out
             nb = lib().ipsx_trunk_workspace_bytes(C.byref(self.trunk), n)
             ws = self._workspace(nb, x.device)
-            _ck(lib().ipsx_trunk_encode(C.byref(self.trunk), _p(x), n, _p(out), _p(ws), nb, _stream()), "ipsx_trunk_encode")
+            run(x, n, out, ws, nb)
         finally:
             self.trunk.patch_dtype = 0
         return out
@@ -382,10 +395,12 @@ class EncoderPlan:
         """... of which only the first this many have to be zero when a call starts."""
         return int(lib().ipsx_projector_stream_ctl_zero_words(int(n)))
 
-    def encode(self, x, nonblank=None, stats=None, out=None, publish=None, index=None):
+    def encode(self, x, nonblank=None, stats=None, out=None, publish=None, index=None, table=None):
         """(P, C, h, w) patches or (P, F) feature rows on the GPU  ->  (P, D) float32.  float32 input; patches also
         float16 / bfloat16 under IPSX_PRECISION=bf16 or fp32x3 (``_patches``), feature rows also float16 / bfloat16
-        under IPSX_PRECISION=bf16, whose projector widens them in its operand load (``_features``).
+        under IPSX_PRECISION=bf16, whose projector widens them in its operand load (``_features``).  uint8 patches with
+        their ``table`` ((C, 256) float32, ``ips_amd.quant``): the embeddings of ``table[c][x]``, bit for bit, on the exact
+        path only - no reduced precision, no blank-patch dedup (both refused before the first launch).
 
         ``nonblank`` (P int32, 1 = the patch has a non-zero element; e.g. from ``patchify_sparse``) switches on
         the exact blank-patch dedup without the pass that looks for blank patches.  ``publish`` = (ready, value), with
@@ -395,7 +410,11 @@ class EncoderPlan:
         row-indexed kernels (``stats``, ``out`` and the result are in the index's order) - the bits of ``encode(x[index])``
         without the gathered copy."""
         self._refresh()
-        x = _patches(x) if self.is_image else self._features(x)
+        if table is not None and not self.is_image:
+            raise TypeError("a patch table goes with uint8 patches of an image encoder")
+        if self.is_image and x.dtype == torch.uint8 and nonblank is not None:
+            raise TypeError("blank-patch dedup reads float32 patches")
+        x = _patches(x, table) if self.is_image else self._features(x)
         n = x.shape[0]
         if index is not None:
             if self.is_image:
@@ -442,7 +461,7 @@ class EncoderPlan:
                     out[blank] = uniq[keep.numel():keep.numel() + 1]
                     self.n_encoded = torch.tensor(sel.numel(), dtype=torch.int32, device=x.device)
                     return out
-            return self.encode_plain(x, out)
+            return self.encode_plain(x, out, table)
         elif self.bf16:
             if stats is None:
                 ws = self._workspace(lib().ipsx_projector_workspace_bytes(n), x.device)

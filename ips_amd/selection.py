@@ -182,7 +182,7 @@ class Selection:
         if buf is None:
             return None
         status = self._mirror_pending
-        if status is None or not hip.ips_finish_supported(src, pos):
+        if status is None or src.dtype == torch.uint8 or not hip.ips_finish_supported(src, pos):     # (uint8: gather, then dequantise)
             self._unfinished = buf
             return None
         if self.scan_status_host is None:
@@ -197,7 +197,7 @@ class Selection:
 
     def native_ok(self, src, pos):
         """Can the library enqueue this call whole (``ipsx_ips_call_run``)?  Needs what ``ips_finish`` needs of the tensors."""
-        return _env_on("IPSX_NATIVE_CALL") and hip.ips_finish_supported(src, pos)
+        return _env_on("IPSX_NATIVE_CALL") and src.dtype != torch.uint8 and hip.ips_finish_supported(src, pos)
 
     def native_call(self, name, patches, pos_enc, logits, mem_idx_buf, zeroed, emb_buf, scan_ws, loops, wgs, trunk_pos=None,
                     quad_pulls=-1, short_first=-1):
@@ -308,7 +308,8 @@ class Selection:
         """Can the schedule ``select`` picks for these patches read them through a shuffle index?  Device-resident,
         contiguous patches on: every feature pipeline (the row-indexed projector kernels) and the fused 1x32x32 trunk in
         parts (its index list).  Not: lazy patches, the one-image trunk stream, the small-batch split, layer-by-layer trunks,
-        blank-patch dedup (those shuffle by copy)."""
+        blank-patch dedup (those shuffle by copy).  uint8 patches: where float32 patches are (the index list
+        addresses bytes; the gather at the end of the call reads them through the order, then dequantises)."""
         net = self.net
         if not (patches.is_cuda and patches.is_contiguous()) or hip.dedup_blank() or net.encoder.training:
             return False
@@ -359,7 +360,8 @@ class Selection:
         """ONE image on the fused fp32 1x32x32 trunk: trunk + logits as one persistent launch beside a resident loop."""
         net = self.net
         if (not net.is_image or patches.shape[0] != 1 or net.encoder.training or not patches.is_contiguous()
-                or not _env_on("IPSX_IMAGE_STREAM") or patches.shape[1] < net.M + 2 * net.I):
+                or not _env_on("IPSX_IMAGE_STREAM") or patches.shape[1] < net.M + 2 * net.I
+                or patches.dtype == torch.uint8):          # (the stream kernel reads float32: uint8 goes through the parts)
             return False
         ca = net.transf.crs_attn
         return (self.persistent_allowed(patches.device, net.M, net.I, ca.H, ca.n_token)
@@ -656,7 +658,7 @@ class Selection:
         for k in range(P):
             lo, hi = edges[k], edges[k + 1]
             if indexed:
-                emb = plan.encode_indexed(flat, part_index[k]).view(B, hi - lo, -1)
+                emb = plan.encode_indexed(flat, part_index[k], table=net._table_for(flat)).view(B, hi - lo, -1)
             elif self._flat is not None:           # feature rows through the shuffle index
                 emb = plan.encode(flat, index=part_index[k]).view(B, hi - lo, -1)
             else:
