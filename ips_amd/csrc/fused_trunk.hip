@@ -1233,8 +1233,7 @@ __global__ __launch_bounds__(512, 1) void fused_trunk_u8_kernel(FusedArgs a, con
 }
 
 #include "fused_trunk_split.h"
-#include "fused_trunk_bf16v2.h"
-#include "fused_trunk_bf16v3.h"
+#include "fused_trunk_bf16.h"
 #include "fused_trunk_pair.h"
 
 // ------------------------------------------------------------------ the stages as stand-alone convolutions (training step)
@@ -1393,7 +1392,6 @@ bool fused_trunk_supported(const ipsx_trunk* t) {
     return !(off && off[0] == '1');
 }
 
-static int g_bf16_build = 0;      // diagnostic (ipsx_dbg_bf16_build): 0 the default build of the bf16 trunk (the third), 1 / 2 / 3 that build
 static int g_pair_mode = 0;       // diagnostic (ipsx_dbg_fused_trunk_pair): 0 the rule below, 1 never, 2 every patch through the pair kernel
 
 static int device_cus() {
@@ -1405,6 +1403,21 @@ static int device_cus() {
         cus[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
     }
     return cus[dev];
+}
+
+// the trunk's weights and BatchNorm affines; with_bf16: also the bf16 operand streams (null pointers otherwise)
+static void fill_fused_args(FusedArgs& a, const ipsx_trunk* t, bool with_bf16) {
+    a.w_stem = t->stem.w_packed; a.a_stem = t->stem.alpha; a.s_stem = t->stem.shift;
+    for (int k = 0; k < 4; ++k)
+        for (int j = 0; j < 2; ++j) {
+            a.w[2 * k + j] = t->blocks[k].conv[j].w_packed;
+            a.al[2 * k + j] = t->blocks[k].conv[j].alpha;
+            a.sh[2 * k + j] = t->blocks[k].conv[j].shift;
+            a.wh[2 * k + j] = with_bf16 ? t->blocks[k].conv[j].w_packed_bf16 : nullptr;
+        }
+    a.w_down = t->blocks[2].down.w_packed; a.a_down = t->blocks[2].down.alpha; a.s_down = t->blocks[2].down.shift;
+    a.wh_down = with_bf16 ? t->blocks[2].down.w_packed_bf16 : nullptr;
+    a.wh_stem = with_bf16 ? t->stem.w_packed_bf16 : nullptr;
 }
 
 // table != nullptr: `patches` holds uint8 pixels (at a 16-byte address) and table[b] is the float32 value of byte b - the
@@ -1424,79 +1437,35 @@ static int fused_launch(const ipsx_trunk* t, const float* patches, int64_t n, fl
     if (t->patch_dtype != 0 && !(t->precision == 1 || t->precision == 2))
         return fail(IPSX_EINVAL, "fused trunk: half-precision patch storage goes with precision 1 (bf16) or 2 (fp32x3)");
     if (t->patch_dtype < 0 || t->patch_dtype > 2) return fail(IPSX_EINVAL, "fused trunk: patch_dtype %d", t->patch_dtype);
-    a.w_stem = t->stem.w_packed; a.a_stem = t->stem.alpha; a.s_stem = t->stem.shift;
-    for (int k = 0; k < 4; ++k)
-        for (int j = 0; j < 2; ++j) {
-            a.w[2 * k + j] = t->blocks[k].conv[j].w_packed;
-            a.al[2 * k + j] = t->blocks[k].conv[j].alpha;
-            a.sh[2 * k + j] = t->blocks[k].conv[j].shift;
-        }
-    a.w_down = t->blocks[2].down.w_packed; a.a_down = t->blocks[2].down.alpha; a.s_down = t->blocks[2].down.shift;
-    bool bf16 = t->precision != 0;
-    for (int k = 0; k < 4; ++k)
-        for (int j = 0; j < 2; ++j) {
-            a.wh[2 * k + j] = t->blocks[k].conv[j].w_packed_bf16;
-            bf16 = bf16 && a.wh[2 * k + j];
-        }
-    a.wh_down = t->blocks[2].down.w_packed_bf16;
-    a.wh_stem = t->stem.w_packed_bf16;
-    bf16 = bf16 && a.wh_down && a.wh_stem;
+    fill_fused_args(a, t, true);
+    bool bf16 = t->precision != 0 && a.wh_down && a.wh_stem;
+    for (int k = 0; k < 8; ++k) bf16 = bf16 && a.wh[k];
     if (t->precision != 0 && !bf16) return fail(IPSX_EINVAL, "fused trunk: precision %d needs w_packed_bf16 on the stem (ipsx_pack_stem_weight_split) and every block conv", t->precision);
-    if (t->precision == 2 || t->precision == 1) {      // the split trunks on the bf16 matrix pipe (fused_trunk_split.h)
-        const bool x3 = t->precision == 2;
-        const size_t ldsx = (size_t)4 * (x3 ? XL<3>::SLAB : XL<1>::SLAB);
+    if (t->precision == 2 || t->precision == 1) {      // the trunks on the bf16 matrix pipe (fused_trunk_split.h, fused_trunk_bf16.h)
         static bool attr_split = false;
         if (!attr_split) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_x3_kernel<false>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 4 * XL<3>::SLAB);
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_x3_kernel<true>),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, 4 * XL<3>::SLAB);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_bf16_kernel<false>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, BF16_LDS);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_bf16_kernel<true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, BF16_LDS);
             attr_split = true;
         }
-        const dim3 grid((unsigned)cdiv(n, 4)), block(256);
-        // the bf16 trunk's builds (round 6): IPSX_BF16_BUILD = 1 first (fused_trunk_split.h), 2 second, 3 third (default)
-        static const int bf16_env = [] { const char* e = getenv("IPSX_BF16_BUILD"); return e && e[0] >= '1' && e[0] <= '3' ? e[0] - '0' : 0; }();
-        const int bf16_build = g_bf16_build ? g_bf16_build : (bf16_env ? bf16_env : 3);
-        if (!x3 && bf16_build == 3) {
-            // the third build (fused_trunk_bf16v3.h): eight patches per workgroup, the 4x4 stage once over all eight
-            static bool attr_v3 = false;
-            if (!attr_v3) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_bf16v3_kernel<false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, V3_LDS);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_bf16v3_kernel<true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, V3_LDS);
-                attr_v3 = true;
-            }
-            if (stamps) fused_trunk_bf16v3_kernel<true><<<dim3((unsigned)cdiv(n, 8)), block, V3_LDS, s>>>(a, stamps);
-            else fused_trunk_bf16v3_kernel<false><<<dim3((unsigned)cdiv(n, 8)), block, V3_LDS, s>>>(a, nullptr);
-            return launched("fused_trunk_bf16v3");
+        const dim3 block(256);
+        if (t->precision == 2) {                       // fp32x3: four patches per workgroup
+            const dim3 grid((unsigned)cdiv(n, 4));
+            const size_t ldsx = (size_t)4 * XL<3>::SLAB;
+            if (stamps) fused_trunk_x3_kernel<true><<<grid, block, ldsx, s>>>(a, stamps);
+            else fused_trunk_x3_kernel<false><<<grid, block, ldsx, s>>>(a, nullptr);
+            return launched("fused_trunk_x3");
         }
-        if (!x3 && bf16_build != 1) {
-            static bool attr_v2 = false;
-            if (!attr_v2) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_bf16v2_kernel<false>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_bf16v2_kernel<true>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-                attr_v2 = true;
-            }
-            // One workgroup per quad by default.  IPSX_BF16_PERSIST=1: two workgroups per unit take the launch's quads in
-            // turn (no dispatch gap between quads, the next quad's pixels prefetched) - faster alone (+5 %), but a selection
-            // loop that is to run BESIDE the launch needs a whole unit's registers (16 waves of 128) and finds none until the
-            // launch is over: measured inside ips() 26.5 -> 22.2 M patches/s, so it is not the default
-            static const bool persist = [] { const char* e = getenv("IPSX_BF16_PERSIST"); return e && e[0] == '1'; }();
-            const dim3 pgrid((unsigned)(persist ? std::min<int64_t>(cdiv(n, 4), 2 * (int64_t)device_cus()) : cdiv(n, 4)));
-            // (diagnostic: IPSX_BF16_ONE_WG=1 asks for more LDS than two workgroups get - ONE workgroup, one wave per SIMD)
-            static const size_t lds_v2 = [] { const char* e = getenv("IPSX_BF16_ONE_WG"); return (size_t)(e && e[0] == '1' ? 100 * 1024 : V2_LDS); }();
-            if (stamps) fused_trunk_bf16v2_kernel<true><<<pgrid, block, lds_v2, s>>>(a, stamps);
-            else fused_trunk_bf16v2_kernel<false><<<pgrid, block, lds_v2, s>>>(a, nullptr);
-            return launched("fused_trunk_bf16v2");
-        }
-        if (x3 && stamps) fused_trunk_x3_kernel<true><<<grid, block, ldsx, s>>>(a, stamps);
-        else if (x3) fused_trunk_x3_kernel<false><<<grid, block, ldsx, s>>>(a, nullptr);
-        else if (stamps) fused_trunk_bf16_kernel<true><<<grid, block, ldsx, s>>>(a, stamps);
-        else fused_trunk_bf16_kernel<false><<<grid, block, ldsx, s>>>(a, nullptr);
-        return launched(x3 ? "fused_trunk_x3" : "fused_trunk_bf16");
+        const dim3 grid((unsigned)cdiv(n, 8));         // bf16: eight patches per workgroup
+        if (stamps) fused_trunk_bf16_kernel<true><<<grid, block, BF16_LDS, s>>>(a, stamps);
+        else fused_trunk_bf16_kernel<false><<<grid, block, BF16_LDS, s>>>(a, nullptr);
+        return launched("fused_trunk_bf16");
     }
     const size_t lds = (size_t)8 * SLAB8 * sizeof(float);              // 141,824 B: one workgroup of eight per CU
     static bool attr_set = false;
@@ -1560,16 +1529,7 @@ int fused_trunk_stream(const ipsx_trunk* t, const float* patches, int64_t n, flo
     if (t->precision != 0 || t->patch_dtype != 0) return fail(IPSX_EINVAL, "trunk_stream: the exact fp32 trunk only");
     TrunkStreamArgs a;
     a.f.patches = patches; a.f.emb = emb; a.f.n = n; a.f.index = nullptr; a.f.count = nullptr; a.f.in_dtype = 0;
-    a.f.w_stem = t->stem.w_packed; a.f.a_stem = t->stem.alpha; a.f.s_stem = t->stem.shift;
-    for (int k = 0; k < 4; ++k)
-        for (int j = 0; j < 2; ++j) {
-            a.f.w[2 * k + j] = t->blocks[k].conv[j].w_packed;
-            a.f.al[2 * k + j] = t->blocks[k].conv[j].alpha;
-            a.f.sh[2 * k + j] = t->blocks[k].conv[j].shift;
-            a.f.wh[2 * k + j] = nullptr;
-        }
-    a.f.w_down = t->blocks[2].down.w_packed; a.f.a_down = t->blocks[2].down.alpha; a.f.s_down = t->blocks[2].down.shift;
-    a.f.wh_down = nullptr; a.f.wh_stem = nullptr;
+    fill_fused_args(a.f, t, false);
     a.pos = pos; a.vp = v_packed; a.R = r; a.logits = logits; a.ctl = ctl; a.ready = ready;
     a.n_pairs = (unsigned)cdiv(n, 2);
     // Four patches per pull run at the trunk's full rate (0.29 ms per pull at one workgroup per unit), two per pull at 0.84 of
@@ -1707,9 +1667,6 @@ IPSX_API int ipsx_pack_stem_weight_split(const float* w, int c_out, int planes, 
 // Diagnostic switch (not part of include/ipsx.h; tests/test_hip_kernels.py, tools): which of the two exact fp32 kernels
 // encodes - 0 the product's rule, 1 fused_trunk_kernel only, 2 fused_trunk_pair_kernel only.
 extern "C" __attribute__((visibility("default"))) void ipsx_dbg_fused_trunk_pair(int mode) { ipsx::g_pair_mode = mode; }
-// which build of the bf16 trunk IPSX_PRECISION=bf16 launches: 0 the default (the third, fused_trunk_bf16v3.h), 1 the first
-// (fused_trunk_split.h), 2 the second (fused_trunk_bf16v2.h), 3 the third
-extern "C" __attribute__((visibility("default"))) void ipsx_dbg_bf16_build(int build) { ipsx::g_bf16_build = build; }
 
 // Diagnostic entry point (not part of include/ipsx.h): the fused trunk with s_memtime stamps,
 // 16 x uint64 per wavefront = per patch, in launch order.  Used by tools/fused_stamps.py only.

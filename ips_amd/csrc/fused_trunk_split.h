@@ -1,5 +1,6 @@
-// fused_trunk_split.h - the fused trunk on the bf16 matrix pipe (included by fused_trunk.hip), in two flavours of one
-// template:
+// fused_trunk_split.h - the fused trunk on the bf16 matrix pipe (included by fused_trunk.hip).  The templates take the number
+// of bf16 planes PL an operand is carried as; fused_trunk_x3_kernel, below, is PL = 3, and fused_trunk_bf16_kernel
+// (fused_trunk_bf16.h) builds on the PL = 1 stem, image layout and epilogue helpers:
 //
 //   PL = 3, precision 2 "fp32x3": every fp32 operand of the residual stages is carried as THREE bf16 terms.
 //     The fp32 matrix pipe tops out at 157 TFLOP/s, the bf16 pipe at 2.5 PFLOP/s.  A float splits EXACTLY into
@@ -13,7 +14,7 @@
 //     reference has no reduced-precision path; this one is tolerance-tested against the fp32 kernel and a float64
 //     emulation that rounds at the same places.
 //
-// Structure = the fp32 kernel's (wave = patch in the 8x8 stage, 4 waves x 4 patches in the 4x4 stage; the stem runs on
+// Structure of fused_trunk_split_body = the fp32 kernel's (wave = patch in the 8x8 stage, 4 waves x 4 patches in the 4x4 stage; the stem runs on
 // the same pipe with a row-padded K, see stem_pool; identity and BatchNorm / residual / ReLU in fp32 registers), with
 // the contraction of the residual stages TRANSPOSED: weights are the
 // A operand (rows = output channels), activations the B operand (columns = pixels).  A lane then owns one pixel and 4
@@ -23,7 +24,7 @@
 //   stage       one K-step of 16 in the 8x8 stage: 2 PL ds_read_b128 + 2 PL global_load_dwordx4 + 4 NP MFMA (NP = 6 or
 //               1 products), the loads of the following stage spread between the MFMAs with sched_group_barrier
 //               (tools/ubench/x3_stage.hip: 833-843 cycles per stage against 768 of pure pipe time; 901 in front)
-// LDS per workgroup: 112 KB (PL = 3: one workgroup = one wave per SIMD per CU) / 37 KB (PL = 1).
+// LDS per workgroup: 112 KB (PL = 3: one workgroup = one wave per SIMD per CU).
 
 constexpr int XP1 = 144, XZ1 = 64;                    // 8x8 stage: bytes per plane per pixel row (64 bf16 + 8 pad); zero row
 constexpr int XP2 = 272, XZ2 = 16;                    // 4x4 stage
@@ -483,12 +484,6 @@ template <bool STAMP>
 __global__ __launch_bounds__(256, 1) void fused_trunk_x3_kernel(FusedArgs a, unsigned long long* stamps) {
     extern __shared__ __attribute__((aligned(16))) char ldsx[];           // 4 slabs of XL<3>::SLAB bytes
     fused_trunk_split_body<3, STAMP>(a, stamps, ldsx);
-}
-
-template <bool STAMP>
-__global__ __launch_bounds__(256, 2) void fused_trunk_bf16_kernel(FusedArgs a, unsigned long long* stamps) {
-    extern __shared__ __attribute__((aligned(16))) char ldsx[];           // 4 slabs of XL<1>::SLAB bytes
-    fused_trunk_split_body<1, STAMP>(a, stamps, ldsx);
 }
 
 // OIHW fp32 -> bf16 A-operand stream [C_out/32][K/16][plane][64 lanes][8] with PL planes: element j of lane l holds term

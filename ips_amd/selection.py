@@ -616,7 +616,7 @@ class Selection:
         if net.is_image and B * N < self.small_batch_limit(dev) and n_iter < 100:
             edges, its = self.small_batch_split(B, N, dev)
         elif net.is_image and indexed and hip.precision() == "bf16":
-            # the bf16 trunk's workgroups take EIGHT patches (fused_trunk_bf16v3.h): a round is 16 patches per unit, and the
+            # the bf16 trunk's workgroups take EIGHT patches (fused_trunk_bf16.h): a round is 16 patches per unit, and the
             # fixed 50 / 30 / 15 / 5 % cut of a 40,000-patch batch is 12 rounds of work for 9.8 - every part a whole number of
             # rounds instead (dist.plan_iterations: the sharded path's planner, one rank)
             from .dist import launch_model, plan_iterations

@@ -7,6 +7,7 @@ chain; own exp; wave-order sums), so floating-point results are compared BIT FOR
 """
 
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -14,7 +15,7 @@ import torch
 
 from ips_amd import hip, synth
 from oracle import oracle as orc
-from tests.util import Golden, ulp_diff
+from tests.util import GOLDEN_DIR, Golden, row_digests, ulp_diff
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -569,39 +570,42 @@ def test_bf16_trunk_tracks_fp32_within_tolerance(monkeypatch):
     assert float(err) < 3e-3, float(err)      # a bf16 rounding flip of one activation is 4e-3 of that activation
 
 
+def _row_mismatches(got, want_rows, want_digest):
+    """rows of `got` (n, 128) whose bytes differ from the recorded rows (the first len(want_rows)) / whose blake2b-16 digest
+    differs from the recorded one"""
+    got = np.ascontiguousarray(got.cpu().numpy(), dtype="<f4")
+    k = min(got.shape[0], want_rows.shape[0])
+    rows = np.flatnonzero((got[:k].view(np.uint32) != np.ascontiguousarray(want_rows[:k], dtype="<f4").view(np.uint32)).any(1))
+    dig = np.flatnonzero((row_digests(got) != want_digest).any(1))
+    return rows[:8].tolist(), dig[:8].tolist()
+
+
 @pytest.mark.parametrize("storage", [torch.float32, torch.float16])
-def test_bf16_trunk_builds_agree(monkeypatch, storage):
-    """Round 6: the bf16 trunk's second and third builds (csrc/fused_trunk_bf16v2.h: 8x8 stage by channel tile x patch pair,
-    deep operand rings; fused_trunk_bf16v3.h, the default: eight patches per workgroup, the 4x4 stage once over all eight)
-    do the FIRST build's arithmetic - same operand rounding, same products in the same order, fp32 identity: the embeddings
-    are bit-identical, whole workgroups and ragged ends (1 .. 17 patches: every remainder of 4 and of 8), an index list,
-    half-stored patches."""
+def test_bf16_trunk_matches_recorded_first_build(monkeypatch, storage):
+    """The bf16 trunk (csrc/fused_trunk_bf16.h: eight patches per workgroup, the 8x8 stage by channel tile x patch pair, the
+    4x4 stage once over all eight) does the arithmetic of the trunk's FIRST build (wave = patch) - same operand rounding,
+    same products in the same order, fp32 identity.  That build is gone; what it computed on these inputs was recorded
+    while it could still run (tests/golden/bf16_trunk.npz, tools/gen_golden_bf16_trunk.py: the first 24 rows and a
+    blake2b-16 digest of every row), and the embeddings are held to the record BYTE for byte: whole workgroups and ragged
+    ends (1 .. 17 patches: every remainder of 4 and of 8), an index list, half-stored patches."""
+    tag = {torch.float32: "f32", torch.float16: "f16"}[storage]
+    z = np.load(os.path.join(GOLDEN_DIR, "bf16_trunk.npz"))
+    want_rows, want_digest = z["rows_" + tag], z["digest_" + tag]
     g = Golden("mnist_full")
     net = g.net(DEV)
     plan = hip.EncoderPlan(net.encoder, True)
-    fn = hip.lib().ipsx_dbg_bf16_build
-    fn.restype, fn.argtypes = None, [C.c_int]
     x_all = g.patches()[0, :1203].to(DEV).to(storage)
     monkeypatch.setenv("IPSX_PRECISION", "bf16")
-    try:
-        for n in (1, 2, 3, 4, 5, 7, 8, 9, 12, 13, 15, 16, 17, 203, 1203):
-            x = x_all[:n].contiguous()
-            fn(1)
-            first = plan.encode(x)
-            fn(2)
-            second = plan.encode(x)
-            fn(3)
-            third = plan.encode(x)
-            assert torch.isfinite(second).all() and torch.equal(first, second), n
-            assert torch.isfinite(third).all() and torch.equal(first, third), n
-        idx = torch.randperm(1203, generator=torch.Generator().manual_seed(5))[:333].to(torch.int32).to(DEV)
-        outs = []
-        for b in (1, 2, 3, 0):
-            fn(b)
-            outs.append(plan.encode_indexed(x_all, idx))
-        assert all(torch.equal(outs[0], o) for o in outs[1:]) and torch.equal(outs[0], plan.encode(x_all[idx.long()].contiguous()))
-    finally:
-        fn(0)
+    for n in (1, 2, 3, 4, 5, 7, 8, 9, 12, 13, 15, 16, 17, 203, 1203):
+        got = plan.encode(x_all[:n].contiguous())
+        assert got.shape == (n, 128) and torch.isfinite(got).all(), n
+        rows, dig = _row_mismatches(got, want_rows, want_digest[:n])
+        assert not rows and not dig, "n = %d: rows %s differ from the recorded rows, rows %s from the recorded digests" % (n, rows, dig)
+    idx = torch.randperm(1203, generator=torch.Generator().manual_seed(5))[:333].to(torch.int32).to(DEV)
+    got = plan.encode_indexed(x_all, idx)
+    assert torch.equal(got, plan.encode(x_all[idx.long()].contiguous()))
+    _, dig = _row_mismatches(got, want_rows[:0], want_digest[idx.cpu().numpy()])
+    assert not dig, "index list: entries %s differ from the recorded digests" % dig
 
 
 def test_fp32x3_trunk_has_fp32_accuracy(monkeypatch):

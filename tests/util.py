@@ -1,6 +1,7 @@
 """Shared helpers of the test-suite: golden fixtures, deterministic nets and inputs."""
 
 import collections
+import hashlib
 import json
 import os
 
@@ -13,7 +14,7 @@ from ips_amd.architecture import IPSNet
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 GOLDEN_CASES = sorted(f[:-4] for f in os.listdir(GOLDEN_DIR)
-                      if f.endswith(".npz") and not f.startswith(("loop_", "bench_", "seeds_", "margin")))
+                      if f.endswith(".npz") and not f.startswith(("loop_", "bench_", "seeds_", "margin", "bf16_trunk")))
 # what the CPU oracle replays in seconds (the rest is checked on the GPU only)
 ORACLE_FAST_CASES = [c for c in GOLDEN_CASES if c not in ("traffic_full", "mnist_native50")]
 
@@ -54,6 +55,16 @@ class Golden:
             return x
         take = torch.from_numpy(self.perm).view(x.shape[0], -1, *(1,) * (x.dim() - 2)).expand_as(x)
         return torch.gather(x, 1, take)
+
+
+def row_digests(rows):
+    """(n, 16) uint8: blake2b-16 of every row's bytes (C order, little-endian float32) - bytewise identity of a row, so
+    -0.0 and +0.0 differ (tests/golden/bf16_trunk.npz, tools/gen_golden_bf16_trunk.py)"""
+    rows = np.ascontiguousarray(rows, dtype="<f4")
+    out = np.empty((rows.shape[0], 16), dtype=np.uint8)
+    for k, r in enumerate(rows):
+        out[k] = np.frombuffer(hashlib.blake2b(r.tobytes(), digest_size=16).digest(), dtype=np.uint8)
+    return out
 
 
 def max_rel(a, b):

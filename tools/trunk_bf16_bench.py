@@ -1,8 +1,8 @@
 #!/usr/bin/env python
-"""The bf16 trunk's three builds ALONE (no selection loop beside them): patches/s of plan.encode at whole rounds of each
-build (a round = 8 patches per unit for builds 1 and 2, 16 for build 3) and at the headline's part sizes.
+"""The bf16 trunk ALONE (no selection loop beside it): patches/s of plan.encode at whole rounds of the chip (a round = 16
+patches per unit: two workgroups of eight) and at the headline's part sizes.  Per size: 3 warm-up calls, then five
+batches of 10 calls between two syncs; the median batch with the fastest and the slowest beside it.
     python tools/trunk_bf16_bench.py"""
-import ctypes as C
 import os
 import sys
 import time
@@ -19,22 +19,21 @@ conf = synth.mnist_conf(N=2500)
 net = synth.fill_weights(IPSNet(dev, conf), 7).to(dev).eval()
 x = synth.make_patches(conf, 20, seed=21).reshape(-1, 1, 32, 32).contiguous().to(dev)
 plan = hip.EncoderPlan(net.encoder, True)
-fn = hip.lib().ipsx_dbg_bf16_build
-fn.restype, fn.argtypes = None, [C.c_int]
 units = hip.device_geometry(dev).cus
+for _ in range(60):                     # clocks up before the first size
+    plan.encode(x[:8 * units * 10])
 for n in (8 * units * 10, 16 * units * 5, 21504, 11264, 6144, 40000):
-    row = []
-    for b in (1, 2, 3):
-        fn(b)
-        xs = x[:n]
-        for _ in range(3):
-            plan.encode(xs)
-        torch.cuda.synchronize()
+    xs = x[:n]
+    for _ in range(3):
+        plan.encode(xs)
+    torch.cuda.synchronize()
+    dts = []
+    for _ in range(5):
         t0 = time.perf_counter()
         for _ in range(10):
             plan.encode(xs)
         torch.cuda.synchronize()
-        dt = (time.perf_counter() - t0) / 10
-        row.append("build %d: %6.1f us  %5.2f M patches/s" % (b, dt * 1e6, n / dt / 1e6))
-    print("%6d patches   " % n + "   ".join(row))
-fn(0)
+        dts.append((time.perf_counter() - t0) / 10)
+    dts.sort()
+    print("%6d patches   %6.1f us  %5.2f M patches/s   (fastest %6.1f us, slowest %6.1f us)"
+          % (n, dts[2] * 1e6, n / dts[2] / 1e6, dts[0] * 1e6, dts[-1] * 1e6))
