@@ -83,7 +83,10 @@ extern "C" {
  *         ipsx_projector_stream_indexed, ipsx_ips_finish_indexed - the feature projector reading its rows through an index
  *         (a shuffle applied as addressing, not as a copy of the patch tensor) and the end of such a call;
  *         ipsx_trunk_encode_u8, ipsx_trunk_encode_indexed_u8, ipsx_dequant_patches - uint8 patch storage: the stems of the
- *         exact fp32 trunks read bytes and look their float32 values up in a per-channel table */
+ *         exact fp32 trunks read bytes and look their float32 values up in a per-channel table;
+ *         ipsx_trunk_encode_parts, ipsx_part_wait, ipsx_logits_if - every part of a call through the fused fp32 trunk as
+ *         ONE launch that counts each part's finished patches, the one-wave kernel that holds another stream until a part
+ *         is complete, and the conditional logits of its recovery */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -285,6 +288,22 @@ int ipsx_trunk_encode_indexed_u8(const ipsx_trunk* t, const uint8_t* patches, co
                                  int64_t n_index, float* emb, void* stream);
 int ipsx_dequant_patches(const uint8_t* q, const float* table, float* out, int64_t n_patch, int c, int hw, void* stream);
 
+/* 3.06: the parts of a call in ONE launch.  index (n_index int32, device): the parts' index lists one after the other; emb row
+ * j belongs to list entry j, so a part's embeddings are one contiguous block, bit for bit ipsx_trunk_encode_indexed of its
+ * list.  part_end (n_parts values on the HOST): the exclusive prefix ends of the parts in list entries, increasing, the last
+ * one n_index.  done (n_parts int32, device, ZEROED by the caller on the same stream in front of the call): done[k] counts
+ * the patches of part k whose embeddings are written and visible device-wide; it ends on the part's size.  The exact fp32
+ * fused 1x32x32 trunk on float32 patches only (precision 0, patch_dtype 0) and n_parts <= 16; anything else: IPSX_EINVAL,
+ * nothing launched.
+ * ipsx_part_wait: a one-wavefront kernel that holds `stream` until *done >= want, so that kernels behind it in that stream
+ * may read the part's embeddings while the trunk launch is still running on another stream.  It gives up after
+ * ipsx_set_persistent_wait_ms WITHOUT PROGRESS of the counter (never unbounded) and then ORs `bit` into *status (device
+ * int32, zeroed by the caller): what followed it has to be redone (ipsx_logits_if, ipsx_scan_range_if on that word).
+ * Enqueue the trunk launch BEFORE the waits. */
+int ipsx_trunk_encode_parts(const ipsx_trunk* t, const float* patches, const int32_t* index, int64_t n_index,
+                            float* emb, const int64_t* part_end, int n_parts, int32_t* done, void* stream);
+int ipsx_part_wait(const int32_t* done, int32_t want, int32_t* status, int32_t bit, void* stream);
+
 /* Same result as ipsx_trunk_encode, with exact blank-patch deduplication (all-zero patches share one
  * embedding in eval mode; ~93 % of Megapixel-MNIST patches): only the non-blank patches and one blank
  * are encoded, everything on the device.  Fused 1x32x32 trunk only.  n_encoded (device int32, or NULL)
@@ -433,6 +452,11 @@ int ipsx_logits(const float* emb, int64_t emb_bstride,
                 const float* v_packed,
                 int b, int64_t n, int d, int r,
                 float* logits, int64_t logits_bstride, void* stream);
+
+/* 3.06: ipsx_logits as a conditional launch - every workgroup returns at once unless (*cond & cond_mask) != 0 (device int32) */
+int ipsx_logits_if(const float* emb, int64_t emb_bstride, const float* pos, int64_t pos_bstride,
+                   const float* v_packed, int b, int64_t n, int d, int r,
+                   float* logits, int64_t logits_bstride, const int32_t* cond, int32_t cond_mask, void* stream);
 
 /* BASELINE configs[4]: the same logits on the bf16 matrix pipe - x = emb (+ pos) rounded to bfloat16, the folded query
  * rounded to bfloat16 (ipsx_fold_query_bf16: ipsx_folded_query_bf16_bytes(h, n_token, d) bytes, from the float32 folded

@@ -20,6 +20,9 @@ bool fused_trunk_supported(const ipsx_trunk* t);
 int fused_trunk_encode_indexed(const ipsx_trunk* t, const float* patches, int64_t n_max, const int* index,
                                const int* count, float* emb, hipStream_t s);
 
+int fused_trunk_encode_parts(const ipsx_trunk* t, const float* patches, const int* index, int64_t n, float* emb,
+                             const int64_t* part_end, int parts, int* done, hipStream_t s);
+
 __global__ __launch_bounds__(256) void blank_flags_kernel(const float* __restrict__ x, long long n, int elems4,
                                                           int* __restrict__ nonblank) {
     const int lane = threadIdx.x & 63;
@@ -87,6 +90,13 @@ IPSX_API int ipsx_trunk_encode_indexed(const ipsx_trunk* t, const float* patches
     IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_indexed: only the fused 1x32x32 trunk is supported");
     if (n_index == 0) return IPSX_OK;
     return fused_trunk_encode_indexed(t, patches, n_index, index, nullptr, emb, as_stream(stream));
+}
+
+IPSX_API int ipsx_trunk_encode_parts(const ipsx_trunk* t, const float* patches, const int32_t* index, int64_t n_index,
+                                     float* emb, const int64_t* part_end, int n_parts, int32_t* done, void* stream) {
+    IPSX_REQUIRE(t && patches && index && emb && part_end && done, "trunk_encode_parts: null pointer");
+    IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_parts: only the fused 1x32x32 trunk is supported");
+    return fused_trunk_encode_parts(t, patches, index, n_index, emb, part_end, n_parts, done, as_stream(stream));
 }
 
 IPSX_API size_t ipsx_trunk_dedup_workspace_bytes(const ipsx_trunk* t, int64_t n_patch) {

@@ -172,6 +172,14 @@ __device__ __forceinline__ void logits_wave(const LogitsArgs& a, unsigned bx, in
 template <int NT>
 __global__ __launch_bounds__(256) void logits_kernel(LogitsArgs a) { logits_wave<NT>(a, blockIdx.x, (int)blockIdx.y); }
 
+// conditional launch (ipsx_logits_if): every workgroup returns at once unless (*cond & mask) != 0 - the redo of logits that
+// may have read embeddings too early (a part wait that gave up, ipsx_part_wait)
+template <int NT>
+__global__ __launch_bounds__(256) void logits_if_kernel(LogitsArgs a, const int* cond, int mask) {
+    if ((__hip_atomic_load(cond, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & mask) == 0) return;
+    logits_wave<NT>(a, blockIdx.x, (int)blockIdx.y);
+}
+
 // The same logits and, in the same launch (workgroups beyond the logits'), the LayerNorm row moments of the NEXT slab of
 // feature rows: two short, latency-bound kernels of the CAMELYON pipeline that sat one after the other between two GEMM
 // parts.  No publication in here (a device-wide release per workgroup costs more than the launch it would save: the next
@@ -264,10 +272,17 @@ __global__ __launch_bounds__(256) void logits_bf16_kernel(LogitsArgs a, const ui
     }
 }
 
-static int launch_logits(const LogitsArgs& a, int b, hipStream_t s) {
+static int launch_logits(const LogitsArgs& a, int b, hipStream_t s, const int* cond = nullptr, int mask = 0) {
     const int nt = (a.R + 31) / 32;
     IPSX_REQUIRE(nt <= 8, "logits: H * n_token = %d > 256 not supported", a.R);
     dim3 grid((unsigned)cdiv(a.n, 128), (unsigned)b);
+    if (cond) {
+        if (nt == 1) logits_if_kernel<1><<<grid, dim3(256), 0, s>>>(a, cond, mask);
+        else if (nt == 2) logits_if_kernel<2><<<grid, dim3(256), 0, s>>>(a, cond, mask);
+        else if (nt <= 4) logits_if_kernel<4><<<grid, dim3(256), 0, s>>>(a, cond, mask);
+        else logits_if_kernel<8><<<grid, dim3(256), 0, s>>>(a, cond, mask);
+        return launched("logits_if");
+    }
     if (nt == 1) logits_kernel<1><<<grid, dim3(256), 0, s>>>(a);
     else if (nt == 2) logits_kernel<2><<<grid, dim3(256), 0, s>>>(a);
     else if (nt <= 4) logits_kernel<4><<<grid, dim3(256), 0, s>>>(a);
@@ -315,6 +330,21 @@ IPSX_API int ipsx_logits(const float* emb, int64_t emb_bstride, const float* pos
     a.kgs = (int)cdiv(d, 8);
     a.out = logits; a.out_bs = logits_bstride;
     return launch_logits(a, b, as_stream(stream));
+}
+
+IPSX_API int ipsx_logits_if(const float* emb, int64_t emb_bstride, const float* pos, int64_t pos_bstride,
+                            const float* v_packed, int b, int64_t n, int d, int r, float* logits,
+                            int64_t logits_bstride, const int32_t* cond, int32_t cond_mask, void* stream) {
+    IPSX_REQUIRE(emb && v_packed && logits, "logits_if: null pointer");
+    IPSX_REQUIRE(cond && cond_mask, "logits_if: needs the condition word and a mask");
+    IPSX_REQUIRE(b > 0 && n >= 0 && d > 0 && r > 0, "logits_if: bad sizes");
+    if (n == 0) return IPSX_OK;
+    LogitsArgs a;
+    a.emb = emb; a.emb_bs = emb_bstride; a.pos = pos; a.pos_bs = pos_bstride;
+    a.vp = v_packed; a.n = n; a.d = d; a.R = r;
+    a.kgs = (int)cdiv(d, 8);
+    a.out = logits; a.out_bs = logits_bstride;
+    return launch_logits(a, b, as_stream(stream), cond, cond_mask);
 }
 
 IPSX_API int ipsx_logits_stats(const float* emb, int64_t emb_bstride, const float* pos, int64_t pos_bstride,

@@ -175,6 +175,33 @@ IPSX_API int ipsx_scan_gate(const int32_t* status, void* stream) {
     return launched("scan_gate");
 }
 
+// One wavefront that holds its stream until a part of a counted trunk launch (ipsx_trunk_encode_parts) is complete:
+// *done >= want.  Relaxed polls with a sleep between them, ONE acquire at the end.  Bounded WITHOUT PROGRESS: the clock
+// restarts whenever the counter has moved, and a wait that sees none for wait_ticks sets `bit` in *status and returns - the
+// caller's conditional launches (ipsx_logits_if, ipsx_scan_range_if) then redo what ran too early.
+__global__ void part_wait_kernel(const int* done, int want, int* status, int bit, unsigned long long wait_ticks) {
+    unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    int last = __hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    while (last < want) {
+        __builtin_amdgcn_s_sleep(32);
+        const int v = __hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long t = __builtin_amdgcn_s_memrealtime();
+        if (v != last) { last = v; t0 = t; }
+        else if (t - t0 > wait_ticks) {
+            __hip_atomic_fetch_or(status, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            break;
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+}
+
+IPSX_API int ipsx_part_wait(const int32_t* done, int32_t want, int32_t* status, int32_t bit, void* stream) {
+    IPSX_REQUIRE(done && status && bit, "part_wait: needs the counter, the status word and a bit");
+    part_wait_kernel<<<dim3(1), dim3(1), 0, as_stream(stream)>>>(done, want, status, bit,
+                                                                 (unsigned long long)g_persist_wait_ms * 100000ull);
+    return launched("part_wait");
+}
+
 IPSX_API int ipsx_publish_rows(int32_t* ready, int32_t value, void* stream) {
     IPSX_REQUIRE(ready, "publish_rows: null pointer");
     publish_rows_kernel<<<dim3(1), dim3(1), 0, as_stream(stream)>>>(ready, value);

@@ -299,6 +299,11 @@ _EXPORTS = {
     "ipsx_set_persistent_wait_ms": (C.c_int, [C.c_int]),
     "ipsx_scan_gate": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ipsx_trunk_encode_indexed": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ipsx_trunk_encode_parts": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                          C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p]),
+    "ipsx_part_wait": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ipsx_logits_if": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
+                                 C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
     "ipsx_trunk_encode_u8": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                        C.c_size_t, C.c_void_p]),
     "ipsx_trunk_encode_indexed_u8": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
@@ -486,9 +491,10 @@ def fold_query_bf16(qs, wk_weight, H, Dk, T):
     return out
 
 
-def logits(emb, pos, vq, R, out=None):
+def logits(emb, pos, vq, R, out=None, cond=None, mask=1):
     """Per-patch attention logits (B, n, R = H*T) from the folded query ``vq``; ``out`` may be a column slice of
-    (B, N, R).  A bfloat16 folded query (``fold_query_bf16``) selects the bf16 matrix pipe."""
+    (B, N, R).  A bfloat16 folded query (``fold_query_bf16``) selects the bf16 matrix pipe.  ``cond`` (int32 device
+    scalar; fp32 folded query only): a conditional launch that does nothing unless a bit of ``mask`` is set in it."""
     B, n, D = emb.shape
     emb = _f32(emb)
     if out is None:
@@ -501,12 +507,24 @@ def logits(emb, pos, vq, R, out=None):
             pos = pos.contiguous()
         pos_bs = pos.stride(0) if pos.shape[0] > 1 else 0
     if vq.dtype == torch.uint8:
+        if cond is not None:
+            raise ValueError("conditional logits: fp32 folded query only")
         _ck(lib().ipsx_logits_bf16(_p(emb), n * D, _p(pos), pos_bs, _p(vq), B, n, D, R, _p(out), out.stride(0), _stream()),
             "ipsx_logits_bf16")
+        return out
+    if cond is not None:
+        _ck(lib().ipsx_logits_if(_p(emb), n * D, _p(pos), pos_bs, _p(vq), B, n, D, R, _p(out), out.stride(0), _p(cond), mask,
+                                 _stream()), "ipsx_logits_if")
         return out
     _ck(lib().ipsx_logits(_p(emb), n * D, _p(pos), pos_bs, _p(vq), B, n, D, R, _p(out), out.stride(0), _stream()),
         "ipsx_logits")
     return out
+
+
+def part_wait(done, want, status, bit=1):
+    """Hold the current stream until the counter ``done`` (int32 device scalar, a part of ``EncoderPlan.encode_indexed``'s
+    one launch) has reached ``want``; a wait without progress for ``persistent_wait_ms`` sets ``bit`` in ``status``."""
+    _ck(lib().ipsx_part_wait(_p(done), int(want), _p(status), int(bit), _stream()), "ipsx_part_wait")
 
 
 def logits_stats(emb, pos, vq, R, out, stats_x, stats_out, ln_eps):

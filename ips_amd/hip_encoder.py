@@ -245,12 +245,24 @@ class EncoderPlan:
         self.trunk.h, self.trunk.w = x_shape[-2], x_shape[-1]
         return x_shape[-3] == self.trunk.c_in and lib().ipsx_trunk_kernel(C.byref(self.trunk)).startswith(b"fused")
 
-    def encode_indexed(self, flat, index, table=None):
+    def encode_indexed(self, flat, index, table=None, parts=None):
         """flat (P, C, h, w) contiguous on the GPU, index (n,) int32 -> (n, D) embeddings of flat[index].  uint8 ``flat``
-        with its ``table`` (C, 256): the embeddings of ``table[c][flat]`` (``ipsx_trunk_encode_indexed_u8``)."""
+        with its ``table`` (C, 256): the embeddings of ``table[c][flat]`` (``ipsx_trunk_encode_indexed_u8``).
+        ``parts`` = (part_end, done): ``index`` is the index lists of several parts one after the other, ending at the
+        list entries ``part_end`` (ints), encoded as ONE launch that counts part k's finished patches into ``done[k]``
+        (int32 on the GPU, zeroed by the caller on this stream) - ``ipsx_trunk_encode_parts``: float32 patches on the exact
+        fp32 fused trunk only."""
         self._refresh()
         flat = _patches(flat, table)
         out = torch.empty((index.numel(), self.d_out), dtype=torch.float32, device=flat.device)
+        if parts is not None:
+            if table is not None or flat.dtype != torch.float32:
+                raise TypeError("encode_indexed(parts=...): float32 patches only")
+            ends, done = parts
+            _ck(lib().ipsx_trunk_encode_parts(C.byref(self.trunk), _p(flat), _p(index), index.numel(), _p(out),
+                                              (C.c_int64 * len(ends))(*ends), len(ends), _p(done), _stream()),
+                "ipsx_trunk_encode_parts")
+            return out
         if table is not None:
             _ck(lib().ipsx_trunk_encode_indexed_u8(C.byref(self.trunk), _p(flat), _p(_patch_table(table, flat.shape[1], flat.device)),
                                                    _p(index), index.numel(), _p(out), _stream()), "ipsx_trunk_encode_indexed_u8")

@@ -596,6 +596,86 @@ class Selection:
         net._emb_parts = [emb_buf]
         return self.persistent_end(logits, mem_idx_buf, tie, status, self.n_iter(N), dev)
 
+    # ------------------------------------------------------------------ the parts' index lists
+    @staticmethod
+    def part_lists(B, N, edges, dev):
+        """int32 patch numbers b * N + j of every part: part k is rows edges[k] .. edges[k + 1] of every image, image-major."""
+        rows = torch.arange(B, device=dev, dtype=torch.int32).unsqueeze(1) * N
+        return [(rows + torch.arange(edges[k], edges[k + 1], device=dev, dtype=torch.int32)).reshape(-1)
+                for k in range(len(edges) - 1)]
+
+    @staticmethod
+    def part_map(B, N, edges, dev):
+        """Where the parts' lists lie in a flat (B, N) index: part k's (B, rows) block, one after the other."""
+        pos = torch.arange(B * N, device=dev).view(B, N)
+        return torch.cat([pos[:, edges[k]:edges[k + 1]].reshape(-1) for k in range(len(edges) - 1)])
+
+    @staticmethod
+    def part_ends(B, edges):
+        """Exclusive prefix ends of the parts in entries of the joined list."""
+        return [B * e for e in edges[1:]]
+
+    def one_launch_ok(self, patches, indexed, small, vq, P):
+        """Every part of the call as ONE launch of the fused fp32 trunk (``ipsx_trunk_encode_parts``), the parts' logits and
+        iterations let go by wait kernels on the side stream: the exact fp32 trunk on float32 patches, cut by the loop's
+        chunk boundaries (not the small-batch split), where kernels of different streams have been SEEN to run side by side."""
+        return (indexed and not small and 2 <= P <= 16 and patches.dtype == torch.float32 and hip.precision() == "fp32"
+                and vq.dtype == torch.float32 and patches.shape[0] * patches.shape[1] < (1 << 31) - 16
+                and _env_on("IPSX_ONE_LAUNCH") and hip.persistent_ok(patches.device))
+
+    def parts_one_launch(self, flat, every, edges, its, pos_enc, vq, R):
+        """``parts_with_ranges`` without the trunk's launch boundaries: ``every`` is the parts' index lists
+        joined.  The trunk launch goes to the main stream FIRST - a runtime that runs the two streams one after the other
+        then finds every counter full - and for each part but the last the side stream gets a wait on the part's counter,
+        the part's logits and its iterations.  A wait that gave up (no progress for hip.persistent_wait_ms) sets the status
+        word; the conditional launches at the end then redo the early parts' logits and the whole loop in this call, and
+        the host, which reads the word one call later, counts the event as the persistent pipelines do."""
+        net, plan = self.net, self.plan()
+        N = edges[-1]
+        B = every.numel() // N
+        M, I, dev = net.M, net.I, flat.device
+        ca = net.transf.crs_attn
+        P = len(its) - 1
+        hip._PERSIST_CALLS += 1                    # (the window of hip.persistent_timed_out is counted in such calls)
+        mirror = self.scan_status_host
+        if mirror is not None and int(mirror.item()) & 1:
+            mirror.zero_()
+            hip.persistent_timed_out(dev)          # (self-test again; off for the process only after repeated events)
+        side, main = self.streams(dev)
+        logits, mem_idx_buf, words, scan_ws = self.buffers(
+            "parts1", (B, N, M, I, R, P, str(dev)),
+            lambda: (torch.empty((B, N, R), dtype=torch.float32, device=dev),
+                     torch.empty((B, M), dtype=torch.int64, device=dev),
+                     torch.zeros((-(-(B + P + 1) // 4) * 4,), dtype=torch.int32, device=dev),   # tie flags | counters | status
+                     hip.scan_workspace(B, M, I, ca.H, ca.n_token, dev)))
+        tie, done, status = words[:B], words[B:B + P], words[B + P:B + P + 1]
+        words.zero_()
+        zeroed = torch.cuda.Event()
+        zeroed.record(main)
+        ends = self.part_ends(B, edges)
+        emb_all = plan.encode_indexed(flat, every, parts=(ends, done))
+        emb_all.record_stream(side)
+        starts = [0] + ends[:-1]
+        net._emb_parts = parts = [emb_all[starts[k]:ends[k]].view(B, edges[k + 1] - edges[k], -1) for k in range(P)]
+        pos = [pos_enc[:, edges[k]:edges[k + 1]] if net.use_pos else None for k in range(P)]
+        with torch.cuda.stream(side):
+            side.wait_event(zeroed)                # (previous readers of the buffers are done, the counters are zero)
+            for k in range(P - 1):
+                hip.part_wait(done[k:k + 1], ends[k] - starts[k], status)
+                hip.logits(parts[k], pos[k], vq, R, out=logits[:, edges[k]:edges[k + 1]])
+                hip.scan_range(logits, M, I, ca.H, ca.n_token, its[k], its[k + 1], mem_idx_buf, tie, scan_ws)
+        main.wait_stream(side)
+        k = P - 1
+        hip.logits(parts[k], pos[k], vq, R, out=logits[:, edges[k]:edges[k + 1]])
+        hip.scan_range(logits, M, I, ca.H, ca.n_token, its[k], its[k + 1], mem_idx_buf, tie, scan_ws)
+        # recovery, no-ops unless a wait gave up: behind the trunk launch every embedding is there
+        for k in range(P - 1):
+            hip.logits(parts[k], pos[k], vq, R, out=logits[:, edges[k]:edges[k + 1]], cond=status)
+        hip.scan_range_if(logits, M, I, ca.H, ca.n_token, 0, its[P], mem_idx_buf, tie, status, 1, workspace=scan_ws)
+        self._mirror_pending = status              # (copied to the host by after_call: behind the call's gathers)
+        hip.scan.last_tie = tie
+        return mem_idx_buf.clone()                 # the buffer is overwritten by the next call
+
     # ------------------------------------------------------------------ pipeline: parts, the loop in ranges beside them
     def parts_with_ranges(self, patches, pos_enc):
         """The patch axis in parts cut at chunk boundaries; part k is encoded (the fused trunk through an index list -
@@ -612,9 +692,10 @@ class Selection:
         n_iter = self.n_iter(N)
         from .dist import part_iterations
         indexed = net.is_image and patches.is_contiguous() and plan.fused(patches.shape)
-        edges = None
+        edges, small = None, False
         if net.is_image and B * N < self.small_batch_limit(dev) and n_iter < 100:
             edges, its = self.small_batch_split(B, N, dev)
+            small = True
         elif net.is_image and indexed and hip.precision() == "bf16":
             # the bf16 trunk's workgroups take EIGHT patches (fused_trunk_bf16.h): a round is 16 patches per unit, and the
             # fixed 50 / 30 / 15 / 5 % cut of a 40,000-patch batch is 12 rounds of work for 9.8 - every part a whole number of
@@ -632,20 +713,21 @@ class Selection:
             edges[-1] = N
         key = (B, N, tuple(edges), str(dev))
         if indexed and (self._part_index is None or self._part_index[0] != key):      # int32 patch indices of every part, cached
-            rows = torch.arange(B, device=dev, dtype=torch.int32).unsqueeze(1) * N
-            self._part_index = (key, [(rows + torch.arange(edges[k], edges[k + 1], device=dev, dtype=torch.int32)).reshape(-1)
-                                      for k in range(P)])
+            lists = self.part_lists(B, N, edges, dev)
+            self._part_index = (key, lists, torch.cat(lists))                         # (and joined: the one-launch route)
         side, main = self.streams(dev)
         flat = patches.reshape(B * N, *patches.shape[2:]) if indexed or self._flat is not None else None
         part_index = self._part_index[1] if indexed else None
+        every = self._part_index[2] if indexed else None
         if self._flat is not None:
             # a shuffle index: composed into the parts' index lists, per call, by ONE gather (the map - part k's (B, rows)
             # block of the (B, N) index, one after the other - is kept with the parts)
             if self._part_map is None or self._part_map[0] != key:
-                pos = torch.arange(B * N, device=dev).view(B, N)
-                self._part_map = (key, torch.cat([pos[:, edges[k]:edges[k + 1]].reshape(-1) for k in range(P)]))
+                self._part_map = (key, self.part_map(B, N, edges, dev))
             every = torch.index_select(self._flat.reshape(-1), 0, self._part_map[1])
             part_index = [every[B * edges[k]:B * edges[k + 1]] for k in range(P)]
+        if self.one_launch_ok(patches, indexed, small, vq, P):
+            return self.parts_one_launch(flat, every, edges, its, pos_enc, vq, R)
         logits, mem_idx_buf, tie, scan_ws = self.buffers(
             "parts", (B, N, M, I, R, str(dev)),
             lambda: (torch.empty((B, N, R), dtype=torch.float32, device=dev),
