@@ -86,7 +86,10 @@ extern "C" {
  *         exact fp32 trunks read bytes and look their float32 values up in a per-channel table;
  *         ipsx_trunk_encode_parts, ipsx_part_wait, ipsx_logits_if - every part of a call through the fused fp32 trunk as
  *         ONE launch that counts each part's finished patches, the one-wave kernel that holds another stream until a part
- *         is complete, and the conditional logits of its recovery */
+ *         is complete, and the conditional logits of its recovery;
+ *         ipsx_patch_view (struct), ipsx_patch_view_offset, ipsx_trunk_view_supported, ipsx_trunk_encode_view,
+ *         ipsx_trunk_encode_parts_view, ipsx_gather_patches_view - the patch-grid view: the LDS-staging stems of the exact
+ *         fp32 trunks read their patches straight from the (b, c, h, w) images, no (b, n, c, ph, pw) tensor exists */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -303,6 +306,41 @@ int ipsx_dequant_patches(const uint8_t* q, const float* table, float* out, int64
 int ipsx_trunk_encode_parts(const ipsx_trunk* t, const float* patches, const int32_t* index, int64_t n_index,
                             float* emb, const int64_t* part_end, int n_parts, int32_t* done, void* stream);
 int ipsx_part_wait(const int32_t* done, int32_t want, int32_t* status, int32_t bit, void* stream);
+
+/* 3.06: the patch-grid view.  The patches of a batch of whole images, addressed where they lie: no patch tensor.
+ * images: float32 (b, c, h, w), contiguous; patch p = (bi * ny + py) * nx + px, ny = (h - ph) / sh + 1, nx = (w - pw) / sw + 1
+ * (the order of the reference's unfold, data/megapixel_mnist/mnist_dataset.py:44-51, image-major: the numbering of
+ * ipsx_patchify's output), starts at element ((bi * c) * h + py * sh) * w + px * sw; its row pitch is w, its channel pitch
+ * h * w.  A geometry is valid when every field is positive, ph <= h, pw <= w and b * ny * nx < 2^31. */
+typedef struct ipsx_patch_view {   /* float32 images (b, c, h, w), contiguous; patches numbered (bi*ny + py)*nx + px, */
+    int b, c, h, w;                /* ny = (h-ph)/sh + 1, nx = (w-pw)/sw + 1: the order of the reference's unfold       */
+    int ph, pw, sh, sw;
+} ipsx_patch_view;
+
+/* host: element offset of patch p's (0,0,0) inside the images; -1 for an invalid geometry or a p outside the grid */
+int64_t ipsx_patch_view_offset(const ipsx_patch_view* v, int64_t p);
+/* 1 when ipsx_trunk_encode_view takes this trunk and view: the exact path (precision 0, patch_dtype 0), a valid geometry
+ * whose (c, ph, pw) is the trunk's patch shape, and a stem that stages its patch into LDS - the fused 1x32x32 trunk,
+ * stem_pool50_kernel (1x50x50) or stem_pool100x3_kernel (3x100x100).  0 otherwise (the generic stem, bf16 / fp32x3). */
+int ipsx_trunk_view_supported(const ipsx_trunk* t, const ipsx_patch_view* v);
+/* emb row j (j < n) = the embedding of grid patch index[j] (device int32), or of patch first + j when index is NULL: bit for
+ * bit ipsx_trunk_encode of those patches copied out of the images (ipsx_patchify) - only the stem's input load differs.  A
+ * list entry outside the grid reads patch 0.  The load width is picked per launch: 16-byte loads (8-byte for the 50-px
+ * stem) when `images` lies at a multiple of the width and w and sw are multiples of 4 (2) floats, dword loads otherwise.
+ * workspace: as ipsx_trunk_encode (ipsx_trunk_workspace_bytes; none for the fused trunk). */
+int ipsx_trunk_encode_view(const ipsx_trunk* t, const float* images, const ipsx_patch_view* v,
+                           const int32_t* index /* NULL: patches first .. first+n-1 */, int64_t first, int64_t n,
+                           float* emb, void* workspace, size_t workspace_bytes, void* stream);
+/* ipsx_trunk_encode_parts (below) with (images, view) in place of patches: index holds grid patch numbers */
+int ipsx_trunk_encode_parts_view(const ipsx_trunk* t, const float* images, const ipsx_patch_view* v, const int32_t* index,
+                                 int64_t n_index, float* emb, const int64_t* part_end, int n_parts, int32_t* done,
+                                 void* stream);
+/* out[bi][j] = patch idx[bi][j] of image bi (idx: (b, m) int64 on the device, patch numbers INSIDE an image, py * nx + px;
+ * a number outside [0, ny * nx) reads patch 0), out (b, m, c, ph, pw): the M patches a selection keeps, copied out of the
+ * images (ips_net.py:245-247 on a tensor that does not exist).  One thread per output float, or per 16 bytes when the
+ * addresses allow. */
+int ipsx_gather_patches_view(const float* images, const ipsx_patch_view* v, const int64_t* idx /* (b, m), per image */,
+                             int m, float* out /* (b, m, c, ph, pw) */, void* stream);
 
 /* Same result as ipsx_trunk_encode, with exact blank-patch deduplication (all-zero patches share one
  * embedding in eval mode; ~93 % of Megapixel-MNIST patches): only the non-blank patches and one blank

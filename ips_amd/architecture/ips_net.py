@@ -347,6 +347,91 @@ class IPSNet(nn.Module):
         self.last_mem_idx = mem_idx
         return mem_patch, mem_pos
 
+    @staticmethod
+    def _unfold_images(images, patch_size, patch_stride):
+        """(B, C, H, W) -> (B, N, C, ph, pw): the reference datasets' unfold (mnist_dataset.py:44-51), batched, on any device."""
+        (ph, pw), (sh, sw) = patch_size, patch_stride
+        if ph > images.shape[2] or pw > images.shape[3] or min(ph, pw, sh, sw) <= 0:
+            raise ValueError("patch {}x{} / stride {}x{} does not fit a {}x{} image".format(ph, pw, sh, sw, *images.shape[2:]))
+        p = images.unfold(2, ph, sh).unfold(3, pw, sw).permute(0, 2, 3, 1, 4, 5)
+        return p.reshape(images.shape[0], -1, images.shape[1], ph, pw)
+
+    def _materialise(self, images, patch_size, patch_stride):
+        """The patch tensor of ``images``, where ``ips_image`` cannot read them through a view."""
+        if hip.on_device(self.device):
+            images = images.to(self.device)
+            if images.dtype == torch.float32:
+                return hip.patchify(images, patch_size, patch_stride)
+        return self._unfold_images(images, patch_size, patch_stride).contiguous()
+
+    @torch.no_grad()
+    def ips_image(self, images, patch_size, patch_stride):
+        """``ips()`` on a batch of whole images: ``images`` (B, C, H, W) float32, on the device or on the host (copied
+        whole) -> (mem_patch (B, M, C, ph, pw), mem_pos).  Everything ``ips(hip.patchify(images, patch_size, patch_stride))``
+        returns and leaves behind (``last_mem_idx``, ``last_mem_emb``, ``last_shuffle``), bit for bit - but the stems of
+        the exact fp32 trunks read their patches straight from the image grid (``hip.PatchView``): the
+        (B, N, C, ph, pw) tensor, a multiple of the images when patches overlap, is never made.  Where the view is not
+        supported (other stems and precisions, blank-patch dedup, a CPU device, an encoder in training mode, an overridden
+        ``do_shuffle``, non-float32 images, M >= N) the patch tensor is materialised and ``ips()`` runs as ever."""
+        if not self.is_image or images.dim() != 4:
+            raise TypeError("ips_image takes (B, C, H, W) images of an image encoder")
+        if images.dtype == torch.uint8:
+            self._table_for(images)        # (no table: the error uint8 patches raise)
+            raise TypeError("ips_image reads float32 images; uint8 storage goes with patch tensors (ips())")
+        view = None
+        if (hip.on_device(self.device) and images.dtype == torch.float32 and not hip.dedup_blank()
+                and not (self.encoder.training and not self.training)       # (ips() itself puts a training NET into eval mode)
+                and not (self.shuffle and self._shuffle_overridden())):
+            view = hip.PatchView(images.shape, patch_size, patch_stride)
+            if self._plan is None:
+                self._plan = hip.EncoderPlan(self.encoder, self.is_image)
+            if self.M >= view.per_image or not self._plan.view_supported(view):
+                view = None
+        if view is None:
+            return self.ips(self._materialise(images, patch_size, patch_stride))
+
+        from ..selection import ViewedPatches
+        M, device, pos_enc = self.M, self.device, self.pos_enc
+        images = view.check(images.to(device))
+        B, N = view.image_shape[0], view.per_image
+        self._emb_parts = self._mem_emb = None
+        self.last_shuffle = None
+        was_training = self.training
+        if was_training:
+            self.encoder.eval()
+            self.transf.eval()
+        try:
+            if self.use_pos:
+                pos_enc = pos_enc.expand(B, -1, -1)
+            order = None
+            if self.shuffle:
+                # the draws do_shuffle would make on the (B, N, ...) tensor; the view always selects through the index
+                like = ViewedPatches(images, view)
+                perm = draw_shuffle(like, self.shuffle_style)
+                if perm is not None:
+                    batch = self.shuffle_style == 'batch'
+                    if torch.is_tensor(pos_enc):
+                        pos_enc = shuffle_batch(pos_enc, perm)[0] if batch else shuffle_instance(pos_enc, 1, perm)[0]
+                    kept = perm.unsqueeze(0) if batch else perm
+                    order = kept.to(device).contiguous()
+                    # (what ips() keeps: the device copy where it would have selected through the index itself)
+                    self.last_shuffle = order if (os.environ.get("IPSX_SHUFFLE", "index") != "copy"
+                                                  and self.selection.index_supported(like)) else kept
+            with self._plan.hold():
+                mem_idx = self.selection.select_view(images, view, pos_enc, order)
+            sel = self.selection
+            mem_idx = sel.take_unfinished(mem_idx)
+            mem_patch = hip.gather_patches_view(images, view, mem_idx if order is None else
+                                                torch.gather(order.expand(B, -1), 1, mem_idx))
+            mem_pos = self._take(pos_enc, mem_idx) if self.use_pos else None
+            sel.after_call()
+        finally:
+            if was_training:
+                self.encoder.train()
+                self.transf.train()
+        self.last_mem_idx = mem_idx
+        return mem_patch, mem_pos
+
     def _chunks(self, N):
         """[0, M) then ceil((N-M)/I) chunks of I (last one ragged) - reference :206,217-221."""
         yield 0, self.M

@@ -21,7 +21,7 @@ int fused_trunk_encode_indexed(const ipsx_trunk* t, const float* patches, int64_
                                const int* count, float* emb, hipStream_t s);
 
 int fused_trunk_encode_parts(const ipsx_trunk* t, const float* patches, const int* index, int64_t n, float* emb,
-                             const int64_t* part_end, int parts, int* done, hipStream_t s);
+                             const int64_t* part_end, int parts, int* done, hipStream_t s, const ViewArgs* view = nullptr);
 
 __global__ __launch_bounds__(256) void blank_flags_kernel(const float* __restrict__ x, long long n, int elems4,
                                                           int* __restrict__ nonblank) {

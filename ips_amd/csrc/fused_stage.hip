@@ -299,8 +299,10 @@ __device__ __forceinline__ float fs_max3(float a, float b, float c) { return __b
 // the padding, which stays 0.0f - through it.  Everything behind the staged image is the float32 kernel.
 constexpr int SP_SLAB_U8 = SP_SLAB + 256;
 
-template <bool U8>
-__device__ __forceinline__ void stem_pool50_body(const StemArgs& a, const float* table) {
+// VIEW: a.patches holds whole images and patch p of the launch is grid patch va->index[p] (or va->first + p) of the
+// ipsx_patch_view in `va`: the same float2 units off the image's rows (row pitch w; 8-byte loads when va->wide, else dwords)
+template <bool U8, bool VIEW = false>
+__device__ __forceinline__ void stem_pool50_body(const StemArgs& a, const float* table, const ViewArgs* va = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, half = lane >> 5;
@@ -333,10 +335,29 @@ __device__ __forceinline__ void stem_pool50_body(const StemArgs& a, const float*
         }
     } else {
         const float2* src = reinterpret_cast<const float2*>(a.patches + (size_t)p * 2500);
+        const float* img = nullptr;
+        if constexpr (VIEW) img = a.patches + view_base(*va, va->index ? (long long)va->index[p] : va->first + p);
         for (int e0 = lane; e0 < 1250; e0 += 64 * 5) {
             float2 v[5];
+            if constexpr (VIEW) {
+                if (va->wide) {
 #pragma unroll
-            for (int u = 0; u < 5; ++u) v[u] = src[e0 + 64 * u < 1250 ? e0 + 64 * u : e0];
+                    for (int u = 0; u < 5; ++u) {
+                        const int e = e0 + 64 * u < 1250 ? e0 + 64 * u : e0, yy = e / 25;
+                        v[u] = *reinterpret_cast<const float2*>(img + (long long)yy * va->v.w + 2 * (e - yy * 25));
+                    }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < 5; ++u) {
+                        const int e = e0 + 64 * u < 1250 ? e0 + 64 * u : e0, yy = e / 25;
+                        const float* q = img + (long long)yy * va->v.w + 2 * (e - yy * 25);
+                        v[u] = make_float2(q[0], q[1]);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < 5; ++u) v[u] = src[e0 + 64 * u < 1250 ? e0 + 64 * u : e0];
+            }
 #pragma unroll
             for (int u = 0; u < 5; ++u) {
                 const int e = e0 + 64 * u;
@@ -440,6 +461,7 @@ __device__ __forceinline__ void stem_pool50_body(const StemArgs& a, const float*
 
 __global__ __launch_bounds__(256, 2) void stem_pool50_kernel(StemArgs a) { stem_pool50_body<false>(a, nullptr); }
 __global__ __launch_bounds__(256, 2) void stem_pool50_u8_kernel(StemArgs a, const float* table) { stem_pool50_body<true>(a, table); }
+__global__ __launch_bounds__(256, 2) void stem_pool50_view_kernel(StemArgs a, ViewArgs va) { stem_pool50_body<false, true>(a, nullptr, &va); }
 
 // ------------------------------------------------------------------------------------------------ stem + max-pool, 3 x 100 px
 // The traffic-sign configuration's stem (config/traffic_config.yml: 3x100x100 patches -> 50x50x64 -> 25x25x64 pooled), same
@@ -469,8 +491,10 @@ __host__ __device__ constexpr int s3_off(int k) {
 // the image's pixels go through the table; the padding stays 0.0f.
 constexpr int S3_FLOATS_U8 = S3_FLOATS + 3 * 256;
 
-template <bool U8>
-__device__ __forceinline__ void stem_pool100x3_body(const Stem3Args& a, const float* table) {
+// VIEW: a.patches holds whole images, patch p of the launch is grid patch va->index[p] (or va->first + p): the same float4
+// units off the image's planes (row pitch w, plane pitch h * w; 16-byte loads when va->wide, else dwords)
+template <bool U8, bool VIEW = false>
+__device__ __forceinline__ void stem_pool100x3_body(const Stem3Args& a, const float* table, const ViewArgs* va = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, half = lane >> 5;
@@ -506,10 +530,33 @@ __device__ __forceinline__ void stem_pool100x3_body(const Stem3Args& a, const fl
         }
     } else {   // 3 x 100 x 100 floats, rows of 25 float4 -> image at rows / columns 3..102 of every plane
         const float4* src = reinterpret_cast<const float4*>(a.patches + (size_t)p * 30000);
+        const float* img = nullptr;
+        long long plane = 0;
+        if constexpr (VIEW) {
+            img = a.patches + view_base(*va, va->index ? (long long)va->index[p] : va->first + p);
+            plane = (long long)va->v.h * va->v.w;
+        }
         for (int e0 = threadIdx.x; e0 < 7500; e0 += 256 * 8) {
             float4 v[8];
+            if constexpr (VIEW) {
+                if (va->wide) {
 #pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = src[e0 + 256 * u < 7500 ? e0 + 256 * u : e0];
+                    for (int u = 0; u < 8; ++u) {
+                        const int e = e0 + 256 * u < 7500 ? e0 + 256 * u : e0, c = e / 2500, rem = e - c * 2500, yy = rem / 25;
+                        v[u] = *reinterpret_cast<const float4*>(img + c * plane + (long long)yy * va->v.w + 4 * (rem - yy * 25));
+                    }
+                } else {
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        const int e = e0 + 256 * u < 7500 ? e0 + 256 * u : e0, c = e / 2500, rem = e - c * 2500, yy = rem / 25;
+                        const float* q = img + c * plane + (long long)yy * va->v.w + 4 * (rem - yy * 25);
+                        v[u] = make_float4(q[0], q[1], q[2], q[3]);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = src[e0 + 256 * u < 7500 ? e0 + 256 * u : e0];
+            }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const int e = e0 + 256 * u;
@@ -652,6 +699,7 @@ __device__ __forceinline__ void stem_pool100x3_body(const Stem3Args& a, const fl
 
 __global__ __launch_bounds__(256, 1) void stem_pool100x3_kernel(Stem3Args a) { stem_pool100x3_body<false>(a, nullptr); }
 __global__ __launch_bounds__(256, 1) void stem_pool100x3_u8_kernel(Stem3Args a, const float* table) { stem_pool100x3_body<true>(a, table); }
+__global__ __launch_bounds__(256, 1) void stem_pool100x3_view_kernel(Stem3Args a, ViewArgs va) { stem_pool100x3_body<false, true>(a, nullptr, &va); }
 
 static bool stem_pool100x3_supported(const ipsx_trunk* t) {
     const char* e = getenv("IPSX_NO_FUSED");
@@ -674,7 +722,13 @@ bool fused_stem_pool100x3_covers(const ipsx_trunk* t) { return t && stem_pool100
 
 // stem + max-pool of 1x50x50 patches -> (n, 13, 13, 64) channels-last; returns 1 when it ran, 0 when the trunk is another shape
 // table != nullptr: `patches` holds uint8 pixels, table (c_in x 256 floats, device, 16-byte aligned) their float32 values
-int fused_stem_pool50(const ipsx_trunk* t, const float* patches, float* y, int64_t n, hipStream_t s, const float* table) {
+// view != nullptr: `patches` holds whole images, the launch's patches are view->index[0 .. n) or view->first .. + n - 1
+int fused_stem_pool50(const ipsx_trunk* t, const float* patches, float* y, int64_t n, hipStream_t s, const float* table,
+                      const ViewArgs* view) {
+    if (view && table) {
+        fail(IPSX_EINVAL, "stem_pool: a patch view reads float32 images");
+        return -1;
+    }
     if (t && stem_pool100x3_supported(t)) {                            // the traffic-sign stem: one patch per workgroup
         if (n <= 0) return 1;
         Stem3Args a3;
@@ -686,9 +740,15 @@ int fused_stem_pool50(const ipsx_trunk* t, const float* patches, float* y, int64
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S3_FLOATS * sizeof(float)));
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem_pool100x3_u8_kernel),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S3_FLOATS_U8 * sizeof(float)));
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem_pool100x3_view_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S3_FLOATS * sizeof(float)));
             attr3 = true;
         }
-        if (table) {
+        if (view) {
+            ViewArgs va = *view;
+            va.wide = view_wide(patches, va.v, 4);
+            stem_pool100x3_view_kernel<<<dim3((unsigned)n), dim3(256), S3_FLOATS * sizeof(float), s>>>(a3, va);
+        } else if (table) {
             if (reinterpret_cast<uintptr_t>(patches) % 16 || reinterpret_cast<uintptr_t>(table) % 16) {
                 fail(IPSX_EINVAL, "stem_pool100x3: uint8 patches and their table must lie at 16-byte addresses");
                 return -1;
@@ -704,7 +764,11 @@ int fused_stem_pool50(const ipsx_trunk* t, const float* patches, float* y, int64
     StemArgs a;
     a.patches = patches; a.y = y; a.n = n;
     a.w = t->stem.w_packed; a.al = t->stem.alpha; a.sh = t->stem.shift;
-    if (table) {
+    if (view) {
+        ViewArgs va = *view;
+        va.wide = view_wide(patches, va.v, 2);
+        stem_pool50_view_kernel<<<dim3((unsigned)cdiv(n, 4)), dim3(256), 4 * SP_SLAB * sizeof(float), s>>>(a, va);
+    } else if (table) {
         if (reinterpret_cast<uintptr_t>(patches) % 4 || reinterpret_cast<uintptr_t>(table) % 16) {
             fail(IPSX_EINVAL, "stem_pool50: uint8 patches must lie at a 4-byte address, their table at a 16-byte address");
             return -1;

@@ -505,12 +505,36 @@ __device__ __forceinline__ void stage_u8_row16(const uint4 q, const float* tab, 
         for (int j = 0; j < 4; ++j) d[4 * k + j] = tab[(w[k] >> (8 * j)) & 0xFFu];
 }
 
+// patch-grid view: the NK float4 units k0 .. k0 + NK - 1 (unit k: pixels 4 (64 k + lane) .. + 3 of the 1x32x32 patch) that
+// this lane stages, read from the image rows at `src` (the patch's first pixel; row pitch w floats).  wide (launch-uniform):
+// 16-byte loads - src and every row start are 16-byte aligned - else four dword loads.
+template <int NK>
+__device__ __forceinline__ void view_load_32(const float* src, int w, int wide, int lane, int k0, float4 (&px)[NK]) {
+    if (wide) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int e = ((k0 + k) * 64 + lane) * 4;
+            px[k] = *reinterpret_cast<const float4*>(src + (long long)(e >> 5) * w + (e & 31));
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int e = ((k0 + k) * 64 + lane) * 4;
+            const float* q = src + (long long)(e >> 5) * w + (e & 31);
+            px[k] = make_float4(q[0], q[1], q[2], q[3]);
+        }
+    }
+}
+
 // one patch by one wavefront on its own slab S: the input load and the stem + pool, whose output is left in the slab in
 // the 8x8 stage's layout, behind a workgroup barrier (layer1 reads every slab) - the front of fused_trunk_kernel
 // U8: a.patches holds uint8 pixels, `table` (256 floats, device) their float32 values
-template <bool STAMP, int WPB, bool U8 = false>
+// VIEW: a.patches holds whole images and `pi` is a patch of the grid `va` describes (ipsx_patch_view): the same 16 floats per
+// lane from the image's rows (row pitch w), staged in the same order
+template <bool STAMP, int WPB, bool U8 = false, bool VIEW = false>
 __device__ __forceinline__ void trunk_front(const FusedArgs& a, long long pi, float* S, int lane, int wave,
-                                            unsigned long long* stamps, const float* table = nullptr) {
+                                            unsigned long long* stamps, const float* table = nullptr,
+                                            const ViewArgs* va = nullptr) {
     IPSX_STAMP(0);
 
     // ---- input patch -> slab as a zero-padded 38x38 image (coalesced 16 B global loads)
@@ -523,10 +547,14 @@ __device__ __forceinline__ void trunk_front(const FusedArgs& a, long long pi, fl
         wave_fence();                                                      // the table copy is whole before any lane reads it
         stage_u8_row16(q, S + U8_TAB, S, lane);
     } else {
-        const float4* src = reinterpret_cast<const float4*>(a.patches + (size_t)pi * 1024);
         float4 px[4];
+        if constexpr (VIEW) {
+            view_load_32(a.patches + view_base(*va, pi), va->v.w, va->wide, lane, 0, px);
+        } else {
+            const float4* src = reinterpret_cast<const float4*>(a.patches + (size_t)pi * 1024);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) px[k] = src[k * 64 + lane];
+            for (int k = 0; k < 4; ++k) px[k] = src[k * 64 + lane];
+        }
         for (int z = lane; z < (PW * PW + 3) / 4; z += 64) reinterpret_cast<float4*>(S)[z] = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int z = lane; z < PS1; z += 64) S[ZP1 * PS1 + z] = 0.0f;          // zero pixel row of the 8x8 stage
 #pragma unroll
@@ -1176,9 +1204,9 @@ __device__ __forceinline__ void parts_count(const PartsArgs& pa, int lo, int hi)
     }
 }
 
-template <bool STAMP, bool U8, bool PARTS = false>
+template <bool STAMP, bool U8, bool PARTS = false, bool VIEW = false>
 __device__ __forceinline__ void fused_trunk_body(const FusedArgs& a, unsigned long long* stamps, const float* table,
-                                                 const PartsArgs* pa = nullptr) {
+                                                 const PartsArgs* pa = nullptr, const ViewArgs* va = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float lds[];          // 8 slabs of SLAB8
     constexpr int WPB = 8;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1189,7 +1217,8 @@ __device__ __forceinline__ void fused_trunk_body(const FusedArgs& a, unsigned lo
     long long pi = p_first + wave;
     if (pi >= n_valid) pi = n_valid - 1;                                  // tail: recompute a valid patch, store nothing
     if (a.index) pi = a.index[pi];
-    trunk_front<STAMP, WPB, U8>(a, pi, lds + wave * SLAB8, lane, wave, stamps, table);
+    else if constexpr (VIEW) pi += va->first;
+    trunk_front<STAMP, WPB, U8, VIEW>(a, pi, lds + wave * SLAB8, lane, wave, stamps, table, va);
     switch (__builtin_amdgcn_readfirstlane((wave + 2 * (wave >> 2)) & 3)) {  // the wave's layer1 tile set, see conv_p1
         case 0: layer1_p1<STAMP, 0>(a, lds, lane, wave, stamps); break;
         case 1: layer1_p1<STAMP, 1>(a, lds, lane, wave, stamps); break;
@@ -1274,6 +1303,15 @@ __global__ __launch_bounds__(512, 1) void fused_trunk_parts_kernel(FusedArgs a, 
 // the same on uint8 patches (a.patches: bytes; table: 256 floats) - only the input load differs (trunk_front)
 __global__ __launch_bounds__(512, 1) void fused_trunk_u8_kernel(FusedArgs a, const float* table) {
     fused_trunk_body<false, true>(a, nullptr, table);
+}
+
+// the same reading its patches through a patch-grid view (a.patches: whole images) - only the input load differs (trunk_front)
+__global__ __launch_bounds__(512, 1) void fused_trunk_view_kernel(FusedArgs a, ViewArgs va) {
+    fused_trunk_body<false, false, false, true>(a, nullptr, nullptr, nullptr, &va);
+}
+
+__global__ __launch_bounds__(512, 1) void fused_trunk_parts_view_kernel(FusedArgs a, PartsArgs pa, ViewArgs va) {
+    fused_trunk_body<false, false, true, true>(a, nullptr, nullptr, &pa, &va);
 }
 
 #include "fused_trunk_split.h"
@@ -1466,9 +1504,11 @@ static void fill_fused_args(FusedArgs& a, const ipsx_trunk* t, bool with_bf16) {
 
 // table != nullptr: `patches` holds uint8 pixels (at a 16-byte address) and table[b] is the float32 value of byte b - the
 // exact fp32 trunk only, no stamps, no device-side count (ipsx_trunk_encode_u8 / _indexed_u8)
+// view != nullptr: `patches` holds whole images and the launch's patches are grid patches of *view (index, or first ..) -
+// the exact fp32 trunk only, no stamps, no device-side count (ipsx_trunk_encode_view)
 static int fused_launch(const ipsx_trunk* t, const float* patches, int64_t n, float* emb,
                         unsigned long long* stamps, hipStream_t s, const int* index = nullptr,
-                        const int* count = nullptr, const float* table = nullptr) {
+                        const int* count = nullptr, const float* table = nullptr, const ViewArgs* view = nullptr) {
     FusedArgs a;
     a.patches = patches; a.emb = emb; a.n = n; a.index = index; a.count = count;
     a.in_dtype = t->patch_dtype;
@@ -1478,6 +1518,8 @@ static int fused_launch(const ipsx_trunk* t, const float* patches, int64_t n, fl
         if (reinterpret_cast<uintptr_t>(patches) % 16 || reinterpret_cast<uintptr_t>(table) % 16)
             return fail(IPSX_EINVAL, "fused trunk: uint8 patches and their table must lie at 16-byte addresses");
     }
+    if (view && (t->precision != 0 || t->patch_dtype != 0 || stamps || count || table))
+        return fail(IPSX_EINVAL, "fused trunk: a patch view goes with the exact fp32 trunk on float32 images only");
     if (t->patch_dtype != 0 && !(t->precision == 1 || t->precision == 2))
         return fail(IPSX_EINVAL, "fused trunk: half-precision patch storage goes with precision 1 (bf16) or 2 (fp32x3)");
     if (t->patch_dtype < 0 || t->patch_dtype > 2) return fail(IPSX_EINVAL, "fused trunk: patch_dtype %d", t->patch_dtype);
@@ -1552,6 +1594,25 @@ static int fused_launch(const ipsx_trunk* t, const float* patches, int64_t n, fl
         }
         return launched("fused_trunk_u8");
     }
+    if (view) {
+        static bool attr_view = false;
+        if (!attr_view) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_view_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            attr_view = true;
+        }
+        ViewArgs va = *view;
+        va.index = nullptr;                                           // (the list travels in a.index, as ever)
+        if (n_full) fused_trunk_view_kernel<<<dim3((unsigned)cdiv(n_full, 8)), dim3(512), lds, s>>>(a, va);
+        if (rest) {
+            a.n = rest;
+            if (index) a.index = index + n_full;
+            else va.first += n_full;
+            a.emb = emb + (size_t)n_full * 128;
+            fused_trunk_pair_view_kernel<<<dim3((unsigned)cdiv(rest, 2)), dim3(256), (size_t)2 * SLAB * sizeof(float), s>>>(a, va);
+        }
+        return launched("fused_trunk_view");
+    }
     if (stamps)
         fused_trunk_kernel<true><<<dim3((unsigned)cdiv(n, 8)), dim3(512), lds, s>>>(a, stamps);
     else if (n_full)
@@ -1570,7 +1631,7 @@ static int fused_launch(const ipsx_trunk* t, const float* patches, int64_t n, fl
 // as their workgroups finish.  The eight-patch kernel takes the whole list.  (The pair kernel for the tail, as fused_launch
 // does it, is a second launch: 9.42 against 9.45 ms at 40,000 patches, 0.3 % - not kept)
 int fused_trunk_encode_parts(const ipsx_trunk* t, const float* patches, const int* index, int64_t n, float* emb,
-                             const int64_t* part_end, int parts, int* done, hipStream_t s) {
+                             const int64_t* part_end, int parts, int* done, hipStream_t s, const ViewArgs* view) {
     if (t->precision != 0 || t->patch_dtype != 0)
         return fail(IPSX_EINVAL, "trunk_encode_parts: the exact fp32 trunk on float32 patches only (precision %d, patch_dtype %d)",
                     t->precision, t->patch_dtype);
@@ -1594,7 +1655,15 @@ int fused_trunk_encode_parts(const ipsx_trunk* t, const float* patches, const in
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_parts_kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_parts_view_kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         attr_set = true;
+    }
+    if (view) {                                                       // `patches`: whole images, the list: grid patches
+        ViewArgs va = *view;
+        va.index = nullptr; va.first = 0;
+        fused_trunk_parts_view_kernel<<<dim3((unsigned)cdiv(n, 8)), dim3(512), lds, s>>>(a, pa, va);
+        return launched("fused_trunk_parts_view");
     }
     fused_trunk_parts_kernel<<<dim3((unsigned)cdiv(n, 8)), dim3(512), lds, s>>>(a, pa);
     return launched("fused_trunk_parts");
@@ -1640,6 +1709,11 @@ int fused_trunk_encode(const ipsx_trunk* t, const float* patches, int64_t n, flo
 int fused_trunk_encode_indexed(const ipsx_trunk* t, const float* patches, int64_t n_max, const int* index,
                                const int* count, float* emb, hipStream_t s) {
     return fused_launch(t, patches, n_max, emb, nullptr, s, index, count);
+}
+
+// grid patches of whole images (view->index, or view->first .. + n - 1) - ipsx_trunk_encode_view
+int fused_trunk_encode_view(const ipsx_trunk* t, const float* images, const ViewArgs* view, int64_t n, float* emb, hipStream_t s) {
+    return fused_launch(t, images, n, emb, nullptr, s, view->index, nullptr, nullptr, view);
 }
 
 // uint8 patches through table (256 floats, device); index: optional int32 patch numbers (nullptr: patches 0 .. n - 1)

@@ -225,14 +225,17 @@ __device__ __forceinline__ void store_l2_pair(float* lds, const f32x16& v, int l
 // lds[0 .. 255] (behind a barrier) for a caller that goes on with them (fused_trunk_stream_kernel: the logits)
 // U8: a.patches holds uint8 pixels, `table` (256 floats, device) their float32 values - each wavefront of a pair keeps its
 // own copy of the table behind the padded image (U8_TAB, fused_trunk.hip) and stages its half of the patch through it
-template <bool KEEP, bool U8 = false>
-__device__ __forceinline__ void trunk_pair_tile(const FusedArgs& a, long long p_first, float* lds, const float* table = nullptr) {
+// VIEW: a.patches holds whole images, the patch is one of the grid `va` describes - the same 8 floats per lane off its rows
+template <bool KEEP, bool U8 = false, bool VIEW = false>
+__device__ __forceinline__ void trunk_pair_tile(const FusedArgs& a, long long p_first, float* lds, const float* table = nullptr,
+                                                const ViewArgs* va = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ps = wave >> 1, nh = wave & 1;                              // patch slot of the workgroup, n-tile of the pair
     const int i = lane & 31;
     long long pi = p_first + ps;
     if (pi >= a.n) pi = a.n - 1;                                          // odd tail: recompute a valid patch, store nothing
     if (a.index) pi = a.index[pi];
+    else if constexpr (VIEW) pi += va->first;
     float* S = lds + ps * SLAB;
 
     // ---- input patch -> slab as a zero-padded 38x38 image, half of it per wavefront
@@ -253,10 +256,14 @@ __device__ __forceinline__ void trunk_pair_tile(const FusedArgs& a, long long p_
 #pragma unroll
             for (int j = 0; j < 4; ++j) d[4 * k + j] = tab[(w[k] >> (8 * j)) & 0xFFu];
     } else {
-        const float4* src = reinterpret_cast<const float4*>(a.patches + (size_t)pi * 1024);
         float4 px[2];
+        if constexpr (VIEW) {
+            view_load_32(a.patches + view_base(*va, pi), va->v.w, va->wide, lane, 2 * nh, px);
+        } else {
+            const float4* src = reinterpret_cast<const float4*>(a.patches + (size_t)pi * 1024);
 #pragma unroll
-        for (int k = 0; k < 2; ++k) px[k] = src[(2 * nh + k) * 64 + lane];
+            for (int k = 0; k < 2; ++k) px[k] = src[(2 * nh + k) * 64 + lane];
+        }
         for (int z = lane + 64 * nh; z < (PW * PW + 3) / 4; z += 128) reinterpret_cast<float4*>(S)[z] = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int z = lane + 64 * nh; z < PS1; z += 128) S[ZP1 * PS1 + z] = 0.0f;
         __syncthreads();                                                  // the padding is laid by both waves of the pair
@@ -372,6 +379,12 @@ __global__ __launch_bounds__(256, 2) void fused_trunk_pair_kernel(FusedArgs a) {
 __global__ __launch_bounds__(256, 2) void fused_trunk_pair_u8_kernel(FusedArgs a, const float* table) {
     extern __shared__ __attribute__((aligned(16))) float lds[];          // 2 slabs
     trunk_pair_tile<false, true>(a, (long long)blockIdx.x * 2, lds, table);
+}
+
+// the same reading its patches through a patch-grid view (a.patches: whole images)
+__global__ __launch_bounds__(256, 2) void fused_trunk_pair_view_kernel(FusedArgs a, ViewArgs va) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];          // 2 slabs
+    trunk_pair_tile<false, false, true>(a, (long long)blockIdx.x * 2, lds, nullptr, &va);
 }
 
 // ------------------------------------------------------------------ one image as ONE persistent launch

@@ -30,9 +30,42 @@ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 //  under stride >= 2 - a window hanging over the far edge, accepted by every "empty output" gate)
 static inline int conv_out(int in, int k, int s, int p) { return in + 2 * p < k ? 0 : (in + 2 * p - k) / s + 1; }
 
+// ---- patch-grid view (ipsx_patch_view): the stems read their patches straight from the (b, c, h, w) images
+// Element offset of patch p's (channel 0, row 0, column 0) inside the images; -1 for a geometry that has no patches, more than
+// 2^31 - 1 of them, or a p outside [0, b * ny * nx).  ONE definition for the host export ipsx_patch_view_offset and the
+// kernels' address arithmetic.  Element (ch, y, x) of the patch lies at offset + (ch * h + y) * w + x.
+__host__ __device__ inline long long patch_view_offset(const ipsx_patch_view& v, long long p) {
+    if (v.b <= 0 || v.c <= 0 || v.ph <= 0 || v.pw <= 0 || v.sh <= 0 || v.sw <= 0 || v.ph > v.h || v.pw > v.w) return -1;
+    const unsigned ny = (unsigned)((v.h - v.ph) / v.sh + 1), nx = (unsigned)((v.w - v.pw) / v.sw + 1);
+    const unsigned long long total = (unsigned long long)v.b * ny * nx;
+    if (total > 0x7FFFFFFFull || p < 0 || (unsigned long long)p >= total) return -1;
+    const unsigned up = (unsigned)p, r = up / nx, px = up - r * nx, bi = r / ny, py = r - bi * ny;
+    return (((long long)bi * v.c) * v.h + (long long)py * v.sh) * v.w + (long long)px * v.sw;
+}
+
+// what a view kernel gets beside its usual arguments: patch j of the launch is grid patch index[j] (index: device int32) or
+// first + j; wide: the launch's load width, picked by the host (view_wide)
+struct ViewArgs {
+    ipsx_patch_view v;
+    const int* index;
+    long long first;
+    int wide;
+};
+
+// a patch number that is no patch of the grid (a bad index list) reads patch 0: never outside the images
+__device__ __forceinline__ long long view_base(const ViewArgs& va, long long p) {
+    const long long off = patch_view_offset(va.v, p);
+    return off < 0 ? 0 : off;
+}
+
+// wide loads of `elems` floats (4: 16 bytes, 2: 8 bytes): every patch row starts at a multiple of the load width
+static inline int view_wide(const float* images, const ipsx_patch_view& v, int elems) {
+    return reinterpret_cast<uintptr_t>(images) % (elems * sizeof(float)) == 0 && v.w % elems == 0 && v.sw % elems == 0 ? 1 : 0;
+}
+
 }  // namespace ipsx
 
-#define IPSX_REQUIRE(cond, ...)                                   \
+#define IPSX_REQUIRE(cond, ...)                                  \
     do {                                                          \
         if (!(cond)) return ipsx::fail(IPSX_EINVAL, __VA_ARGS__); \
     } while (0)

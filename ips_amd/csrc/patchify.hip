@@ -40,6 +40,28 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
     out[e] = *reinterpret_cast<const V*>(img + src);
 }
 
+// ipsx_gather_patches_view: out[bi][j] = patch idx[bi][j] of image bi, copied out of the images - one thread per V (float or
+// float4) of the output; a patch number outside the image's grid reads patch 0
+template <typename V, int VW>
+__global__ __launch_bounds__(256) void gather_patches_view_kernel(const float* __restrict__ img, ipsx_patch_view v, int m,
+                                                                  const long long* __restrict__ idx, long long total,
+                                                                  V* __restrict__ out) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int rowv = v.pw / VW;
+    long long r = e;
+    const int xv = (int)(r % rowv); r /= rowv;
+    const int y = (int)(r % v.ph); r /= v.ph;
+    const int c = (int)(r % v.c); r /= v.c;          // r = bi * m + j
+    const long long bi = r / m;
+    const long long per = (long long)((v.h - v.ph) / v.sh + 1) * ((v.w - v.pw) / v.sw + 1);
+    long long q = idx[r];
+    if (q < 0 || q >= per) q = 0;
+    long long off = patch_view_offset(v, bi * per + q);
+    if (off < 0) off = 0;
+    out[e] = *reinterpret_cast<const V*>(img + off + ((long long)c * v.h + y) * v.w + (long long)xv * VW);
+}
+
 // one thread per non-zero; the image of a non-zero is found by bisection of the (B+1) offsets
 __global__ __launch_bounds__(256) void patchify_sparse_kernel(const long long* __restrict__ index,
                                                               const float* __restrict__ value,
@@ -127,4 +149,27 @@ IPSX_API int ipsx_patchify_sparse(const int64_t* index, const float* value, cons
         reinterpret_cast<const long long*>(index), value, reinterpret_cast<const long long*>(offsets), b, g, patches,
         reinterpret_cast<int*>(nonblank));
     return launched("patchify_sparse");
+}
+
+IPSX_API int ipsx_gather_patches_view(const float* images, const ipsx_patch_view* v, const int64_t* idx, int m, float* out,
+                                      void* stream) {
+    IPSX_REQUIRE(images && v && idx && out && m >= 0, "gather_patches_view: bad arguments");
+    IPSX_REQUIRE(patch_view_offset(*v, 0) >= 0, "gather_patches_view: images %dx%dx%dx%d, patch %dx%d, stride %dx%d", v->b, v->c,
+                 v->h, v->w, v->ph, v->pw, v->sh, v->sw);
+    IPSX_REQUIRE(reinterpret_cast<uintptr_t>(images) % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0,
+                 "gather_patches_view: images and out must lie at 4-byte addresses");
+    const long long elems = (long long)v->b * m * v->c * v->ph * v->pw;
+    if (elems == 0) return IPSX_OK;
+    const bool v4 = v->pw % 4 == 0 && v->w % 4 == 0 && v->sw % 4 == 0 && (reinterpret_cast<uintptr_t>(images) & 15) == 0 &&
+                    (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    const long long* ix = reinterpret_cast<const long long*>(idx);
+    if (v4) {
+        const long long total = elems / 4;
+        gather_patches_view_kernel<float4, 4><<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, as_stream(stream)>>>(
+            images, *v, m, ix, total, reinterpret_cast<float4*>(out));
+    } else {
+        gather_patches_view_kernel<float, 1><<<dim3((unsigned)cdiv(elems, 256)), dim3(256), 0, as_stream(stream)>>>(
+            images, *v, m, ix, elems, out);
+    }
+    return launched("gather_patches_view");
 }

@@ -22,7 +22,8 @@ int conv2d_affine_impl(const ipsx_conv* cv, const float* x, const float* residua
 int fused_stage64_blocks(const ipsx_block* blocks, int n_block, int h, int w);
 int fused_stage64(const ipsx_block* blocks, int n_block, const float* x, float* y, int64_t n, int h, int w, hipStream_t s);
 int fused_stem_pool50(const ipsx_trunk* t, const float* patches, float* y, int64_t n, hipStream_t s,
-                      const float* table = nullptr);   // 1 = ran, 0 = other shape; table: patches holds uint8
+                      const float* table = nullptr,    // 1 = ran, 0 = other shape; table: patches holds uint8
+                      const ViewArgs* view = nullptr); // view: patches holds whole images (ipsx_trunk_encode_view)
 bool fused_stem_pool50_covers(const ipsx_trunk* t);
 bool fused_stem_pool100x3_covers(const ipsx_trunk* t);
 // conv_nhwc_bf16.hip: the pooled fp32 map rounded once to bf16 (count % 8 == 0)
@@ -32,6 +33,9 @@ bool fused_trunk_supported(const ipsx_trunk* t);
 int fused_trunk_encode(const ipsx_trunk* t, const float* patches, int64_t n, float* emb, hipStream_t s);
 int fused_trunk_encode_u8(const ipsx_trunk* t, const unsigned char* patches, const float* table, int64_t n, const int* index,
                           float* emb, hipStream_t s);
+int fused_trunk_encode_view(const ipsx_trunk* t, const float* images, const ViewArgs* view, int64_t n, float* emb, hipStream_t s);
+int fused_trunk_encode_parts(const ipsx_trunk* t, const float* patches, const int* index, int64_t n, float* emb,
+                             const int64_t* part_end, int parts, int* done, hipStream_t s, const ViewArgs* view);
 int fused_trunk_stream(const ipsx_trunk* t, const float* patches, int64_t n, float* emb, const float* pos, const float* v_packed,
                        int r, float* logits, int32_t* ctl, int32_t* ready, int workgroups, int quad_pulls, hipStream_t s);
 
@@ -148,8 +152,10 @@ IPSX_API const char* ipsx_trunk_kernel(const ipsx_trunk* t) {
 
 // ipsx_trunk_encode and ipsx_trunk_encode_u8: table == nullptr - `patches_v` holds float32 (or, fused split trunks,
 // t->patch_dtype) elements; else uint8 elements whose values are table[channel][byte] - only the stem's load differs
+// ipsx_trunk_encode_view: view != nullptr - `patches_v` holds whole float32 images and patch j of the call is grid patch
+// view->index[j] (or view->first + j) of view->v; the caller has checked ipsx_trunk_view_supported
 static int trunk_encode(const ipsx_trunk* t, const void* patches_v, const float* table, int64_t n_patch, float* emb,
-                        void* workspace, size_t workspace_bytes, void* stream) {
+                        void* workspace, size_t workspace_bytes, void* stream, const ViewArgs* view = nullptr) {
     TrunkGeom g;
     IPSX_TRY(trunk_geom(t, &g));
     const float* patches = static_cast<const float*>(patches_v);
@@ -168,6 +174,11 @@ static int trunk_encode(const ipsx_trunk* t, const void* patches_v, const float*
     if (bf16) IPSX_TRY(layered_bf16_check(t));
     if (n_patch == 0) return IPSX_OK;
     if (fused && table) return fused_trunk_encode_u8(t, patches_u8, table, n_patch, nullptr, emb, as_stream(stream));
+    if (fused && view) {
+        ViewArgs va = *view;
+        va.wide = view_wide(patches, va.v, 4);
+        return fused_trunk_encode_view(t, patches, &va, n_patch, emb, as_stream(stream));
+    }
     if (fused) return fused_trunk_encode(t, patches, n_patch, emb, as_stream(stream));
 
     const int64_t chunk = workspace ? chunk_for(g, n_patch, workspace_bytes) : 0;      // chunks fit what the caller gave
@@ -191,8 +202,15 @@ static int trunk_encode(const ipsx_trunk* t, const void* patches_v, const float*
         int c = t->stem.c_out;
         // stem reads the NCHW patches and writes channels-last; everything after it is channels-last
         const float* chunk_in = table ? reinterpret_cast<const float*>(patches_u8 + p0 * patch_elems) : patches + p0 * patch_elems;
-        const int fused_stem = fused_stem_pool50(t, chunk_in, buf[1], n, as_stream(stream), table);
+        ViewArgs va;
+        if (view) {                                    // the chunk's patches: the list's entries p0 .. or the grid's first + p0 ..
+            va = *view;
+            if (va.index) va.index += p0;
+            else va.first += p0;
+        }
+        const int fused_stem = fused_stem_pool50(t, view ? patches : chunk_in, buf[1], n, as_stream(stream), table, view ? &va : nullptr);
         if (fused_stem < 0) return IPSX_EHIP;
+        IPSX_REQUIRE(fused_stem || !view, "trunk_encode_view: this trunk's stem does not read through a view");
         if (!fused_stem) {
             IPSX_TRY(conv2d_affine_impl(&t->stem, chunk_in, nullptr, buf[0], n, t->h, t->w, 1, 1, stream, table));
             IPSX_TRY(ipsx_maxpool_3x3s2_nhwc(buf[0], buf[1], n, c, h, w, stream));
@@ -290,6 +308,45 @@ IPSX_API int ipsx_trunk_encode_indexed_u8(const ipsx_trunk* t, const uint8_t* pa
     IPSX_REQUIRE(t->precision == 0 && t->patch_dtype == 0, "trunk_encode_indexed_u8: uint8 patches go with the exact fp32 trunk only");
     if (n_index == 0) return IPSX_OK;
     return fused_trunk_encode_u8(t, patches, table, n_index, index, emb, as_stream(stream));
+}
+
+// ---- the patch-grid view (3.06): whole images in place of the patch tensor
+IPSX_API int64_t ipsx_patch_view_offset(const ipsx_patch_view* v, int64_t p) { return v ? patch_view_offset(*v, p) : -1; }
+
+IPSX_API int ipsx_trunk_view_supported(const ipsx_trunk* t, const ipsx_patch_view* v) {
+    if (!t || !v || patch_view_offset(*v, 0) < 0) return 0;
+    if (t->precision != 0 || t->patch_dtype != 0) return 0;
+    if (v->c != t->c_in || v->ph != t->h || v->pw != t->w) return 0;
+    return fused_trunk_supported(t) || fused_stem_pool50_covers(t) || fused_stem_pool100x3_covers(t) ? 1 : 0;
+}
+
+static int64_t view_patches(const ipsx_patch_view& v) {
+    return (int64_t)v.b * ((v.h - v.ph) / v.sh + 1) * ((v.w - v.pw) / v.sw + 1);
+}
+
+IPSX_API int ipsx_trunk_encode_view(const ipsx_trunk* t, const float* images, const ipsx_patch_view* v, const int32_t* index,
+                                    int64_t first, int64_t n, float* emb, void* workspace, size_t workspace_bytes, void* stream) {
+    IPSX_REQUIRE(t && images && v && emb && n >= 0 && first >= 0, "trunk_encode_view: bad arguments");
+    IPSX_REQUIRE(reinterpret_cast<uintptr_t>(images) % 4 == 0, "trunk_encode_view: images must lie at a 4-byte address");
+    IPSX_REQUIRE(ipsx_trunk_view_supported(t, v), "trunk_encode_view: the exact fp32 trunks whose stem stages its patch into LDS "
+                 "(1x32x32 fused, 1x50x50, 3x100x100) on a valid view of their patch shape (ipsx_trunk_view_supported)");
+    IPSX_REQUIRE(index || first + n <= view_patches(*v), "trunk_encode_view: patches %lld .. %lld of a grid of %lld",
+                 (long long)first, (long long)(first + n), (long long)view_patches(*v));
+    ViewArgs va;
+    va.v = *v; va.index = index; va.first = index ? 0 : first; va.wide = 0;
+    return trunk_encode(t, images, nullptr, n, emb, workspace, workspace_bytes, stream, &va);
+}
+
+IPSX_API int ipsx_trunk_encode_parts_view(const ipsx_trunk* t, const float* images, const ipsx_patch_view* v, const int32_t* index,
+                                          int64_t n_index, float* emb, const int64_t* part_end, int n_parts, int32_t* done,
+                                          void* stream) {
+    IPSX_REQUIRE(t && images && v && index && emb && part_end && done, "trunk_encode_parts_view: null pointer");
+    IPSX_REQUIRE(reinterpret_cast<uintptr_t>(images) % 4 == 0, "trunk_encode_parts_view: images must lie at a 4-byte address");
+    IPSX_REQUIRE(fused_trunk_supported(t) && ipsx_trunk_view_supported(t, v),
+                 "trunk_encode_parts_view: the fused fp32 1x32x32 trunk on a valid view of 1x32x32 patches only");
+    ViewArgs va;
+    va.v = *v; va.index = nullptr; va.first = 0; va.wide = view_wide(images, *v, 4);
+    return fused_trunk_encode_parts(t, images, index, n_index, emb, part_end, n_parts, done, as_stream(stream), &va);
 }
 
 // One image: trunk AND logits of its patches as ONE persistent launch that feeds ipsx_scan_persistent patch by patch

@@ -44,6 +44,11 @@ class SparseImages:
     def pin_memory(self):
         return SparseImages(self.index.pin_memory(), self.value.pin_memory(), self.offsets.pin_memory(), self.canvas)
 
+    def image(self):
+        """The dense (B, C, H, W) canvases - ``patches`` with one patch, the canvas itself: what ``IPSNet.ips_image`` takes."""
+        H, W, Cc = self.canvas
+        return self.patches((H, W), (H, W)).reshape(len(self), Cc, H, W)
+
     def patches(self, patch_size, patch_stride, flags=False):
         """(B, N, C, ph, pw) patch tensor.  On the GPU one scatter kernel; on the CPU densify + unfold (ATen)."""
         if hip.on_device(self.index):
@@ -59,6 +64,9 @@ class SparseImages:
         if flags:
             return out, (out.flatten(2) != 0).any(-1).reshape(-1).to(torch.int32)
         return out
+
+
+SparseBatch = SparseImages      # (the batch of a DataLoader with collate_sparse)
 
 
 def _unfold(img, patch_size, patch_stride):

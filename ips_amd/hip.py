@@ -144,6 +144,12 @@ class Trunk(C.Structure):
                 ("n_block", C.c_int), ("blocks", C.POINTER(Block)), ("precision", C.c_int), ("patch_dtype", C.c_int)]
 
 
+class PatchViewStruct(C.Structure):
+    """``ipsx_patch_view``: float32 images (b, c, h, w) and the patch grid laid over them."""
+    _fields_ = [("b", C.c_int), ("c", C.c_int), ("h", C.c_int), ("w", C.c_int),
+                ("ph", C.c_int), ("pw", C.c_int), ("sh", C.c_int), ("sw", C.c_int)]
+
+
 class IpsCall(C.Structure):
     """include/ipsx.h ``ipsx_ips_call``: one ips() call with a resident loop, enqueued by ONE library call."""
     _fields_ = [("b", C.c_int), ("n", C.c_int64), ("m", C.c_int), ("i", C.c_int), ("h", C.c_int), ("n_token", C.c_int),
@@ -219,6 +225,13 @@ _EXPORTS = {
     "ipsx_trunk_kernel": (C.c_char_p, [C.POINTER(Trunk)]),
     "ipsx_trunk_encode": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                     C.c_size_t, C.c_void_p]),
+    "ipsx_patch_view_offset": (C.c_int64, [C.POINTER(PatchViewStruct), C.c_int64]),
+    "ipsx_trunk_view_supported": (C.c_int, [C.POINTER(Trunk), C.POINTER(PatchViewStruct)]),
+    "ipsx_trunk_encode_view": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.POINTER(PatchViewStruct), C.c_void_p, C.c_int64,
+                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ipsx_trunk_encode_parts_view": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.POINTER(PatchViewStruct), C.c_void_p, C.c_int64,
+                                               C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p]),
+    "ipsx_gather_patches_view": (C.c_int, [C.c_void_p, C.POINTER(PatchViewStruct), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ipsx_trunk_dedup_workspace_bytes": (C.c_size_t, [C.POINTER(Trunk), C.c_int64]),
     "ipsx_trunk_encode_dedup": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -905,6 +918,58 @@ def patchify(img, patch_size, patch_stride):
         raise ValueError("patch {}x{} / stride {}x{} does not fit a {}x{} image".format(ph, pw, sh, sw, H, W))
     out = torch.empty((B, n, Cc, ph, pw), dtype=torch.float32, device=img.device)
     _ck(lib().ipsx_patchify(_p(img), B, Cc, H, W, ph, pw, sh, sw, _p(out), _stream()), "ipsx_patchify")
+    return out
+
+
+class PatchView:
+    """The patch grid of a batch of whole images, as addresses (``ipsx_patch_view``): what
+    ``patchify(images, patch_size, patch_stride)`` would copy out, patch ``p = (b * ny + py) * nx + px`` in the order of the
+    reference's ``unfold`` - never materialised.  ``image_shape`` = (B, C, H, W)."""
+
+    def __init__(self, image_shape, patch_size, patch_stride):
+        B, Cc, H, W = (int(v) for v in image_shape)
+        (ph, pw), (sh, sw) = (int(v) for v in patch_size), (int(v) for v in patch_stride)
+        self.struct = PatchViewStruct(B, Cc, H, W, ph, pw, sh, sw)
+        if min(B, Cc, H, W, ph, pw, sh, sw) <= 0 or ph > H or pw > W:
+            raise ValueError("patch {}x{} / stride {}x{} does not fit {} images of {}x{}x{}".format(ph, pw, sh, sw, B, Cc, H, W))
+        self.ny, self.nx = (H - ph) // sh + 1, (W - pw) // sw + 1
+        if B * self.ny * self.nx >= 1 << 31:
+            raise ValueError("a view of {} patches (the limit is 2^31 - 1)".format(B * self.ny * self.nx))
+        self.image_shape, self.patch_size, self.patch_stride = (B, Cc, H, W), (ph, pw), (sh, sw)
+        self.per_image = self.ny * self.nx         # N of the (B, N, C, ph, pw) tensor that does not exist
+        self.count = B * self.per_image
+        self.patch_shape = (Cc, ph, pw)
+
+    def origin(self, p):
+        """Element offset of patch ``p``'s (channel 0, row 0, column 0) inside the contiguous images, or -1 when ``p`` is
+        no patch of the grid.  Element (c, y, x) of the patch lies ``(c * H + y) * W + x`` further."""
+        _, Cc, H, W = self.image_shape
+        if not 0 <= p < self.count:
+            return -1
+        r, px = divmod(int(p), self.nx)
+        b, py = divmod(r, self.ny)
+        return ((b * Cc) * H + py * self.patch_stride[0]) * W + px * self.patch_stride[1]
+
+    def check(self, images):
+        """``images`` as the view kernels read them: float32, this view's shape, contiguous."""
+        if images.dtype != torch.float32:
+            raise TypeError("a patch view reads float32 images, got {}".format(images.dtype))
+        if tuple(images.shape) != self.image_shape:
+            raise ValueError("images are {}, the view was made for {}".format(tuple(images.shape), self.image_shape))
+        return images if images.is_contiguous() else images.contiguous()
+
+
+def gather_patches_view(images, view, idx):
+    """images (B, C, H, W) float32 on the GPU, idx (B, M) int64 patch numbers inside each image (py * nx + px) ->
+    (B, M, C, ph, pw): ``patchify(images, ...)[b, idx[b, m]]`` copied straight out of the images."""
+    images = view.check(images)
+    if idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] != view.image_shape[0] or idx.device != images.device:
+        raise ValueError("idx must be a (B, M) int64 tensor on the images' device")
+    idx = idx if idx.is_contiguous() else idx.contiguous()
+    M = idx.shape[1]
+    out = torch.empty((idx.shape[0], M) + view.patch_shape, dtype=torch.float32, device=images.device)
+    _ck(lib().ipsx_gather_patches_view(_p(images), C.byref(view.struct), _p(idx), M, _p(out), _stream()),
+        "ipsx_gather_patches_view")
     return out
 
 

@@ -275,6 +275,82 @@ class EncoderPlan:
             self.trunk.patch_dtype = 0
         return out
 
+    def view_supported(self, view):
+        """Can ``encode_view`` read the patches of this ``hip.PatchView``?  The exact fp32 trunks whose stem stages its
+        patch into LDS (1x32x32 fused, 1x50x50, 3x100x100) on a view of their patch shape (``ipsx_trunk_view_supported``)."""
+        if not self.is_image:
+            return False
+        self._refresh()
+        self.trunk.h, self.trunk.w = view.patch_size
+        return bool(lib().ipsx_trunk_view_supported(C.byref(self.trunk), C.byref(view.struct)))
+
+    def view_kernel_name(self, view):
+        """The kernel that reads the images for this view (None: not supported)."""
+        if not self.view_supported(view):
+            return None
+        name = lib().ipsx_trunk_kernel(C.byref(self.trunk)).decode()
+        return "fused_trunk_view_kernel" if name.startswith("fused") else name.split(" ")[0].replace("_kernel", "_view_kernel")
+
+    def encode_view(self, images, view, index=None, first=0, n=None, parts=None):
+        """images (B, C, H, W) float32 on the GPU + their ``hip.PatchView`` -> (n, D) embeddings of grid patches
+        ``index`` (int32, device) or ``first .. first + n - 1`` (default: every patch): the bits of ``encode`` on the same
+        patches of ``hip.patchify(images, ...)`` - the stems read the images, no patch tensor exists
+        (``ipsx_trunk_encode_view``).  ``parts`` = (part_end, done): as ``encode_indexed(parts=...)``, fused trunk only."""
+        if not self.view_supported(view):
+            raise ValueError("this encoder does not read patches through a view (EncoderPlan.view_supported)")
+        images = view.check(images)
+        if index is not None:
+            if index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous() or index.device != images.device:
+                raise ValueError("index must be a contiguous 1-d int32 tensor on the images' device")
+            first, n = 0, index.numel()
+        elif n is None:
+            n = view.count - first
+        if first < 0 or n < 0 or (index is None and first + n > view.count):
+            raise ValueError("patches {} .. {} of a view of {}".format(first, first + n, view.count))
+        out = torch.empty((n, self.d_out), dtype=torch.float32, device=images.device)
+        if n == 0:
+            return out
+        vs = C.byref(view.struct)
+        if parts is not None:
+            if index is None:
+                raise ValueError("encode_view(parts=...) takes the parts' index lists")
+            ends, done = parts
+            _ck(lib().ipsx_trunk_encode_parts_view(C.byref(self.trunk), _p(images), vs, _p(index), n, _p(out),
+                                                   (C.c_int64 * len(ends))(*ends), len(ends), _p(done), _stream()),
+                "ipsx_trunk_encode_parts_view")
+            return out
+
+        def run(lo, cnt, ws, nb):
+            ix = C.c_void_p(index.data_ptr() + 4 * lo) if index is not None else C.c_void_p(0)
+            _ck(lib().ipsx_trunk_encode_view(C.byref(self.trunk), _p(images), vs, ix, first + lo if index is None else 0, cnt,
+                                             _p(out[lo:lo + cnt]), _p(ws), nb, _stream()), "ipsx_trunk_encode_view")
+
+        # (layer-by-layer trunks: two halves on two streams, as encode_plain runs them)
+        ns = int(os.environ.get("IPSX_LAYERED_STREAMS", "2"))
+        if ns > 1 and n >= 1024 and not lib().ipsx_trunk_kernel(C.byref(self.trunk)).startswith(b"fused"):
+            cuts = [n * k // ns for k in range(ns + 1)]
+            nb = lib().ipsx_trunk_workspace_bytes(C.byref(self.trunk), max(cuts[k + 1] - cuts[k] for k in range(ns)))
+            budget = lib().ipsx_trunk_workspace_bytes(C.byref(self.trunk), 1 << 40)
+            nb = min(nb, max(budget // ns, lib().ipsx_trunk_workspace_bytes(C.byref(self.trunk), 1)))
+            nb -= nb % 256
+            ws = self._workspace(ns * nb, images.device)
+            if len(getattr(self, "_sides", [])) < ns - 1:
+                self._sides = [torch.cuda.Stream(device=images.device) for _ in range(ns - 1)]
+            main = torch.cuda.current_stream(images.device)
+            for k in range(1, ns):
+                st = self._sides[k - 1]
+                st.wait_stream(main)
+                with torch.cuda.stream(st):
+                    run(cuts[k], cuts[k + 1] - cuts[k], ws[k * nb:], nb)
+            run(0, cuts[1], ws[:nb], nb)
+            for st in self._sides[:ns - 1]:
+                main.wait_stream(st)
+            return out
+        nb = lib().ipsx_trunk_workspace_bytes(C.byref(self.trunk), n)
+        ws = self._workspace(nb, images.device)
+        run(0, n, ws, nb)
+        return out
+
     def encode_plain(self, x, out=None, table=None):
         """The image trunk on every patch of ``x`` (no dedup).  uint8 ``x`` with its ``table`` (C, 256): the same calls
         through ``ipsx_trunk_encode_u8``, whose stems look the bytes up."""

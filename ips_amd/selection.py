@@ -57,6 +57,26 @@ def _env_on(name):
     return os.environ.get(name, "1") != "0"
 
 
+class ViewedPatches:
+    """(images, view) standing where the (B, N, C, ph, pw) patch tensor stands in the schedules: the shape, type and device
+    of the tensor ``hip.patchify(images, ...)`` would make, which is never made - the encoders read ``images`` through
+    ``view`` (a ``hip.PatchView``)."""
+
+    is_cuda = True
+    dtype = torch.float32
+
+    def __init__(self, images, view):
+        self.images, self.view = images, view
+        self.shape = torch.Size((view.image_shape[0], view.per_image) + view.patch_shape)
+        self.device = images.device
+
+    def dim(self):
+        return 5
+
+    def is_contiguous(self):
+        return True
+
+
 class Selection:
     """The selection pipelines of one ``IPSNet`` (buffers and streams are kept between calls of the same shape: a buffer
     that a side stream has used cannot be recycled by the allocator until that stream's work is known to be over, and
@@ -84,6 +104,7 @@ class Selection:
         self._flat_base = None
         self._part_map = None                      # parts_with_ranges: where the parts' index lists lie in the flat (B, N) index
         self.index_calls = 0                       # select() calls that read the patches through a shuffle index
+        self.view_calls = 0                        # select_view() calls: the patches read through a patch-grid view
 
     # ------------------------------------------------------------------ small helpers
     def plan(self):
@@ -301,6 +322,27 @@ class Selection:
                     and self.persistent_allowed(patches.device, net.M, net.I, ca.H, ca.n_token, self.feature_loops(patches.shape[0]),
                                                 large=_env_on("IPSX_LARGE_PERSIST"))):
                 return self.features_persistent(patches, pos_enc)
+            return self.parts_with_ranges(patches, pos_enc)
+        return self.slabs(patches, pos_enc)
+
+    def select_view(self, images, view, pos_enc, order=None):
+        """``select`` on the patches of whole images (B, C, H, W) on the device, read through ``view`` (a ``hip.PatchView``
+        the plan supports: ``EncoderPlan.view_supported``) - no (B, N, ...) tensor exists.  The schedules are those of
+        ``select`` with (images, view) where they hold the flat patch tensor: the parts beside the loop's ranges (every part
+        an index list of grid patches - the fused trunk's one launch, the small-batch split, layered trunks too) or, for a
+        short loop, one piece.  Patch numbers are those of the tensor ``hip.patchify`` would make, so ``order``, ``pos_enc``
+        and ``mem_idx`` mean what they mean in ``select``.  The one-image stream and the native one-call route read patch
+        tensors: a single image takes the parts."""
+        net = self.net
+        net._device_patches = None
+        self._done = self._unfinished = None
+        self._order = self._flat = None
+        patches = ViewedPatches(images, view)
+        if order is not None:
+            self._order, self._flat = order, self.flat_index(order, patches.shape[0], patches.shape[1])
+            self.index_calls += 1
+        self.view_calls += 1
+        if self.can_overlap(patches):
             return self.parts_with_ranges(patches, pos_enc)
         return self.slabs(patches, pos_enc)
 
@@ -621,7 +663,8 @@ class Selection:
         chunk boundaries (not the small-batch split), where kernels of different streams have been SEEN to run side by side."""
         return (indexed and not small and 2 <= P <= 16 and patches.dtype == torch.float32 and hip.precision() == "fp32"
                 and vq.dtype == torch.float32 and patches.shape[0] * patches.shape[1] < (1 << 31) - 16
-                and _env_on("IPSX_ONE_LAUNCH") and hip.persistent_ok(patches.device))
+                and _env_on("IPSX_ONE_LAUNCH") and hip.persistent_ok(patches.device)
+                and (not isinstance(patches, ViewedPatches) or bool(self.plan().fused(patches.shape))))   # (a view's lists serve layered trunks too)
 
     def parts_one_launch(self, flat, every, edges, its, pos_enc, vq, R):
         """``parts_with_ranges`` without the trunk's launch boundaries: ``every`` is the parts' index lists
@@ -653,7 +696,10 @@ class Selection:
         zeroed = torch.cuda.Event()
         zeroed.record(main)
         ends = self.part_ends(B, edges)
-        emb_all = plan.encode_indexed(flat, every, parts=(ends, done))
+        if isinstance(flat, ViewedPatches):
+            emb_all = plan.encode_view(flat.images, flat.view, index=every, parts=(ends, done))
+        else:
+            emb_all = plan.encode_indexed(flat, every, parts=(ends, done))
         emb_all.record_stream(side)
         starts = [0] + ends[:-1]
         net._emb_parts = parts = [emb_all[starts[k]:ends[k]].view(B, edges[k + 1] - edges[k], -1) for k in range(P)]
@@ -691,7 +737,8 @@ class Selection:
         vq, R = ca.folded_query(), ca.H * ca.n_token
         n_iter = self.n_iter(N)
         from .dist import part_iterations
-        indexed = net.is_image and patches.is_contiguous() and plan.fused(patches.shape)
+        viewed = isinstance(patches, ViewedPatches)         # (whole images: every encoder takes its parts as index lists)
+        indexed = net.is_image and patches.is_contiguous() and (viewed or plan.fused(patches.shape))
         edges, small = None, False
         if net.is_image and B * N < self.small_batch_limit(dev) and n_iter < 100:
             edges, its = self.small_batch_split(B, N, dev)
@@ -716,7 +763,10 @@ class Selection:
             lists = self.part_lists(B, N, edges, dev)
             self._part_index = (key, lists, torch.cat(lists))                         # (and joined: the one-launch route)
         side, main = self.streams(dev)
-        flat = patches.reshape(B * N, *patches.shape[2:]) if indexed or self._flat is not None else None
+        if viewed:
+            flat = patches
+        else:
+            flat = patches.reshape(B * N, *patches.shape[2:]) if indexed or self._flat is not None else None
         part_index = self._part_index[1] if indexed else None
         every = self._part_index[2] if indexed else None
         if self._flat is not None:
@@ -739,7 +789,9 @@ class Selection:
         side.wait_stream(main)
         for k in range(P):
             lo, hi = edges[k], edges[k + 1]
-            if indexed:
+            if viewed:
+                emb = plan.encode_view(patches.images, patches.view, index=part_index[k]).view(B, hi - lo, -1)
+            elif indexed:
                 emb = plan.encode_indexed(flat, part_index[k], table=net._table_for(flat)).view(B, hi - lo, -1)
             elif self._flat is not None:           # feature rows through the shuffle index
                 emb = plan.encode(flat, index=part_index[k]).view(B, hi - lo, -1)
@@ -794,7 +846,10 @@ class Selection:
         parts = []
         for k, (lo, hi) in enumerate(spans):
             part = fetch(k)
-            if self._flat is not None:             # (device-resident feature rows, one span) through the shuffle index
+            if isinstance(part, ViewedPatches):    # whole images, one span: every grid patch, or those the shuffle index names
+                emb = self.plan().encode_view(part.images, part.view,
+                                              index=self._flat.reshape(-1) if self._flat is not None else None).view(B, N, -1)
+            elif self._flat is not None:           # (device-resident feature rows, one span) through the shuffle index
                 emb = self.plan().encode(part.reshape(B * N, -1), index=self._flat.view(-1)).view(B, N, -1)
             else:
                 emb = net._embed(part.reshape(-1, *patches.shape[2:])).view(B, hi - lo, -1)
