@@ -390,7 +390,6 @@ class IPSNet(nn.Module):
         if view is None:
             return self.ips(self._materialise(images, patch_size, patch_stride))
 
-        from ..selection import ViewedPatches
         M, device, pos_enc = self.M, self.device, self.pos_enc
         images = view.check(images.to(device))
         B, N = view.image_shape[0], view.per_image
@@ -406,7 +405,7 @@ class IPSNet(nn.Module):
             order = None
             if self.shuffle:
                 # the draws do_shuffle would make on the (B, N, ...) tensor; the view always selects through the index
-                like = ViewedPatches(images, view)
+                like = hip.PatchSource(images=images, view=view)
                 perm = draw_shuffle(like, self.shuffle_style)
                 if perm is not None:
                     batch = self.shuffle_style == 'batch'

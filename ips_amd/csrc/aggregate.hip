@@ -11,7 +11,7 @@
 //  * ipsx_head: Linear -> softmax | sigmoid (ips_net.py:72-81).
 // Arithmetic order: oracle/ips_oracle.cpp orc_projector / orc_aggregate / orc_head.
 
-#include "ipsx_common.h"
+#include "ipsx_internal.h"
 #include "ipsx_math.h"
 #include "ipsx_rowstats.h"
 
@@ -207,11 +207,6 @@ __global__ __launch_bounds__(64) void head_kernel(const float* __restrict__ emb,
         }
     }
 }
-
-// conv_nhwc.hip
-int conv_nhwc_impl(const ipsx_conv* cv, const float* x, const float* residual, const float* row_stats, float* y,
-                   int64_t n, int h, int w, int relu, void* stream, int* ready = nullptr, int ready_value = 0,
-                   const int32_t* index = nullptr, int64_t src_rows = 0);
 
 constexpr size_t kAggLdsLimit = 160 * 1024;
 

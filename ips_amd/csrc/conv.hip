@@ -22,7 +22,7 @@
 
 #include <algorithm>
 
-#include "ipsx_common.h"
+#include "ipsx_internal.h"
 #include "ipsx_math.h"
 
 namespace ipsx {
@@ -402,11 +402,6 @@ IPSX_API int ipsx_bn_affine(const float* gamma, const float* beta, const float* 
     bn_affine_kernel<<<dim3((unsigned)cdiv(c, 256)), dim3(256), 0, as_stream(stream)>>>(
         gamma, beta, mean, var, lin_bias, eps, c, alpha, shift);
     return launched("bn_affine");
-}
-
-namespace ipsx {
-int conv2d_affine_impl(const ipsx_conv* cv, const float* x, const float* residual, float* y, int64_t n, int h,
-                       int w, int relu, int out_nhwc, void* stream, const float* table = nullptr);
 }
 
 IPSX_API int ipsx_conv2d_affine(const ipsx_conv* cv, const float* x, const float* residual, float* y,

@@ -21,7 +21,7 @@
 
 #include <algorithm>
 
-#include "ipsx_common.h"
+#include "ipsx_internal.h"
 #include "ipsx_math.h"
 #include "ipsx_rowstats.h"
 
@@ -760,12 +760,6 @@ __global__ void avgpool_nhwc_kernel(const float* __restrict__ x, float* __restri
 }  // namespace ipsx
 
 using namespace ipsx;
-
-namespace ipsx {
-int conv_nhwc_impl(const ipsx_conv* cv, const float* x, const float* residual, const float* row_stats, float* y,
-                   int64_t n, int h, int w, int relu, void* stream, int* ready = nullptr, int ready_value = 0,
-                   const int32_t* index = nullptr, int64_t src_rows = 0);
-}
 
 IPSX_API int ipsx_conv2d_affine_nhwc(const ipsx_conv* cv, const float* x, const float* residual, float* y,
                                      int64_t n, int h, int w, int relu, void* stream) {

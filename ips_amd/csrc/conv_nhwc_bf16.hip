@@ -24,7 +24,7 @@
 
 #include <algorithm>
 
-#include "ipsx_common.h"
+#include "ipsx_internal.h"
 #include "ipsx_math.h"
 
 namespace ipsx {

@@ -12,16 +12,9 @@
 //   fused trunk          launched for the worst case, workgroups beyond the device-side count exit at once
 //   scatter_rows_kernel  emb[j] = emb_unique[slot[j]]
 
-#include "ipsx_common.h"
+#include "ipsx_internal.h"
 
 namespace ipsx {
-
-bool fused_trunk_supported(const ipsx_trunk* t);
-int fused_trunk_encode_indexed(const ipsx_trunk* t, const float* patches, int64_t n_max, const int* index,
-                               const int* count, float* emb, hipStream_t s);
-
-int fused_trunk_encode_parts(const ipsx_trunk* t, const float* patches, const int* index, int64_t n, float* emb,
-                             const int64_t* part_end, int parts, int* done, hipStream_t s, const ViewArgs* view = nullptr);
 
 __global__ __launch_bounds__(256) void blank_flags_kernel(const float* __restrict__ x, long long n, int elems4,
                                                           int* __restrict__ nonblank) {
@@ -88,15 +81,18 @@ IPSX_API int ipsx_trunk_encode_indexed(const ipsx_trunk* t, const float* patches
                                        int64_t n_index, float* emb, void* stream) {
     IPSX_REQUIRE(t && patches && index && emb && n_index >= 0, "trunk_encode_indexed: bad arguments");
     IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_indexed: only the fused 1x32x32 trunk is supported");
+    const PatchSrc src{patches, nullptr, nullptr, index, 0};
+    IPSX_TRY(patch_src_check(t, src, n_index, true, "trunk_encode_indexed"));
     if (n_index == 0) return IPSX_OK;
-    return fused_trunk_encode_indexed(t, patches, n_index, index, nullptr, emb, as_stream(stream));
+    return fused_launch(t, src, n_index, emb, as_stream(stream));
 }
 
 IPSX_API int ipsx_trunk_encode_parts(const ipsx_trunk* t, const float* patches, const int32_t* index, int64_t n_index,
                                      float* emb, const int64_t* part_end, int n_parts, int32_t* done, void* stream) {
     IPSX_REQUIRE(t && patches && index && emb && part_end && done, "trunk_encode_parts: null pointer");
     IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_parts: only the fused 1x32x32 trunk is supported");
-    return fused_trunk_encode_parts(t, patches, index, n_index, emb, part_end, n_parts, done, as_stream(stream));
+    return fused_trunk_encode_parts(t, PatchSrc{patches, nullptr, nullptr, index, 0}, n_index, emb, part_end, n_parts, done,
+                                    as_stream(stream));
 }
 
 IPSX_API size_t ipsx_trunk_dedup_workspace_bytes(const ipsx_trunk* t, int64_t n_patch) {
@@ -110,6 +106,7 @@ static int encode_dedup(const ipsx_trunk* t, const float* patches, int64_t n_pat
     IPSX_REQUIRE(t && patches && emb && n_patch >= 0, "trunk_encode_dedup: bad arguments");
     IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_dedup: only the fused 1x32x32 trunk is supported");
     IPSX_REQUIRE(n_patch < ((int64_t)1 << 31), "trunk_encode_dedup: too many patches");
+    IPSX_TRY(patch_src_check(t, PatchSrc{patches, nullptr, nullptr, nullptr, 0}, n_patch, true, "trunk_encode_dedup"));
     if (n_patch == 0) return IPSX_OK;
     const size_t need = ipsx_trunk_dedup_workspace_bytes(t, n_patch);
     if (!workspace || workspace_bytes < need)
@@ -129,7 +126,7 @@ static int encode_dedup(const ipsx_trunk* t, const float* patches, int64_t n_pat
     compact_kernel<<<dim3(1), dim3(1024), 0, s>>>(flags ? reinterpret_cast<const int*>(flags) : nonblank, (int)n_patch,
                                                   index, slot, count);
     IPSX_TRY(launched("compact"));
-    IPSX_TRY(fused_trunk_encode_indexed(t, patches, n_patch, index, count, emb_u, s));
+    IPSX_TRY(fused_launch(t, PatchSrc{patches, nullptr, nullptr, index, 0}, n_patch, emb_u, s, count));
     scatter_rows_kernel<<<dim3((unsigned)cdiv(n_patch * 32, 256)), dim3(256), 0, s>>>(
         reinterpret_cast<const float4*>(emb_u), slot, reinterpret_cast<float4*>(emb), n_patch, 32);
     IPSX_TRY(launched("scatter_rows"));

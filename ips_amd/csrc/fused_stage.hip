@@ -23,7 +23,7 @@
 // contribute fma(0, w, acc), BatchNorm = fma(acc, alpha, shift), + identity, ReLU - bit-identical to conv_nhwc.hip and to
 // the oracle.  Algorithmic work: 4 x 169 x 576 x 64 MAC per patch; bytes 43 KB in + 43 KB out per patch.
 
-#include "ipsx_common.h"
+#include "ipsx_internal.h"
 #include "ipsx_math.h"
 
 namespace ipsx {
@@ -720,16 +720,12 @@ static bool stem_pool50_supported(const ipsx_trunk* t) {
 bool fused_stem_pool50_covers(const ipsx_trunk* t) { return t && stem_pool50_supported(t); }
 bool fused_stem_pool100x3_covers(const ipsx_trunk* t) { return t && stem_pool100x3_supported(t); }
 
-// stem + max-pool of 1x50x50 patches -> (n, 13, 13, 64) channels-last; returns 1 when it ran, 0 when the trunk is another shape
-// table != nullptr: `patches` holds uint8 pixels, table (c_in x 256 floats, device, 16-byte aligned) their float32 values
-// view != nullptr: `patches` holds whole images, the launch's patches are view->index[0 .. n) or view->first .. + n - 1
-int fused_stem_pool50(const ipsx_trunk* t, const float* patches, float* y, int64_t n, hipStream_t s, const float* table,
-                      const ViewArgs* view) {
-    if (view && table) {
-        fail(IPSX_EINVAL, "stem_pool: a patch view reads float32 images");
-        return -1;
-    }
-    if (t && stem_pool100x3_supported(t)) {                            // the traffic-sign stem: one patch per workgroup
+// stem + max-pool of `n` patches of `src` (checked by the entry: patch_src_check), 3x100x100 one patch per workgroup or 1x50x50
+// four; returns 1 when it ran, 0 when the trunk is another shape.  The storage kinds differ in the kernels' last argument
+// only (nothing, the table, the view at the kernel's load width) and in the LDS the bytes' staging takes.
+int fused_stem_pool50(const ipsx_trunk* t, const PatchSrc& src, float* y, int64_t n, hipStream_t s) {
+    const float* patches = static_cast<const float*>(src.base);
+    if (t && stem_pool100x3_supported(t)) {                            // the traffic-sign stem
         if (n <= 0) return 1;
         Stem3Args a3;
         a3.patches = patches; a3.y = y; a3.n = n;
@@ -744,19 +740,10 @@ int fused_stem_pool50(const ipsx_trunk* t, const float* patches, float* y, int64
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S3_FLOATS * sizeof(float)));
             attr3 = true;
         }
-        if (view) {
-            ViewArgs va = *view;
-            va.wide = view_wide(patches, va.v, 4);
-            stem_pool100x3_view_kernel<<<dim3((unsigned)n), dim3(256), S3_FLOATS * sizeof(float), s>>>(a3, va);
-        } else if (table) {
-            if (reinterpret_cast<uintptr_t>(patches) % 16 || reinterpret_cast<uintptr_t>(table) % 16) {
-                fail(IPSX_EINVAL, "stem_pool100x3: uint8 patches and their table must lie at 16-byte addresses");
-                return -1;
-            }
-            stem_pool100x3_u8_kernel<<<dim3((unsigned)n), dim3(256), S3_FLOATS_U8 * sizeof(float), s>>>(a3, table);
-        } else {
-            stem_pool100x3_kernel<<<dim3((unsigned)n), dim3(256), S3_FLOATS * sizeof(float), s>>>(a3);
-        }
+        const dim3 grid((unsigned)n), block(256);
+        if (src.view) stem_pool100x3_view_kernel<<<grid, block, S3_FLOATS * sizeof(float), s>>>(a3, view_args(src, 4));
+        else if (src.table) stem_pool100x3_u8_kernel<<<grid, block, S3_FLOATS_U8 * sizeof(float), s>>>(a3, src.table);
+        else stem_pool100x3_kernel<<<grid, block, S3_FLOATS * sizeof(float), s>>>(a3);
         return launched("stem_pool100x3") == IPSX_OK ? 1 : -1;
     }
     if (!t || !stem_pool50_supported(t)) return 0;
@@ -764,19 +751,10 @@ int fused_stem_pool50(const ipsx_trunk* t, const float* patches, float* y, int64
     StemArgs a;
     a.patches = patches; a.y = y; a.n = n;
     a.w = t->stem.w_packed; a.al = t->stem.alpha; a.sh = t->stem.shift;
-    if (view) {
-        ViewArgs va = *view;
-        va.wide = view_wide(patches, va.v, 2);
-        stem_pool50_view_kernel<<<dim3((unsigned)cdiv(n, 4)), dim3(256), 4 * SP_SLAB * sizeof(float), s>>>(a, va);
-    } else if (table) {
-        if (reinterpret_cast<uintptr_t>(patches) % 4 || reinterpret_cast<uintptr_t>(table) % 16) {
-            fail(IPSX_EINVAL, "stem_pool50: uint8 patches must lie at a 4-byte address, their table at a 16-byte address");
-            return -1;
-        }
-        stem_pool50_u8_kernel<<<dim3((unsigned)cdiv(n, 4)), dim3(256), 4 * SP_SLAB_U8 * sizeof(float), s>>>(a, table);
-    } else {
-        stem_pool50_kernel<<<dim3((unsigned)cdiv(n, 4)), dim3(256), 4 * SP_SLAB * sizeof(float), s>>>(a);
-    }
+    const dim3 grid((unsigned)cdiv(n, 4)), block(256);
+    if (src.view) stem_pool50_view_kernel<<<grid, block, 4 * SP_SLAB * sizeof(float), s>>>(a, view_args(src, 2));
+    else if (src.table) stem_pool50_u8_kernel<<<grid, block, 4 * SP_SLAB_U8 * sizeof(float), s>>>(a, src.table);
+    else stem_pool50_kernel<<<grid, block, 4 * SP_SLAB * sizeof(float), s>>>(a);
     return launched("stem_pool50") == IPSX_OK ? 1 : -1;
 }
 

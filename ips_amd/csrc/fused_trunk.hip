@@ -39,7 +39,7 @@
 
 #include <algorithm>
 
-#include "ipsx_common.h"
+#include "ipsx_internal.h"
 #include "ipsx_math.h"
 
 namespace ipsx {
@@ -1487,8 +1487,12 @@ static int device_cus() {
     return cus[dev];
 }
 
-// the trunk's weights and BatchNorm affines; with_bf16: also the bf16 operand streams (null pointers otherwise)
-static void fill_fused_args(FusedArgs& a, const ipsx_trunk* t, bool with_bf16) {
+// The kernels' common arguments, assembled HERE for every launch: the trunk's weights and BatchNorm affines (with_bf16: also
+// the bf16 operand streams, null pointers otherwise) and `n` patches of `src` -> rows of `emb`
+static FusedArgs fused_args(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, bool with_bf16) {
+    FusedArgs a;
+    a.patches = static_cast<const float*>(src.base); a.emb = emb; a.n = n; a.index = src.index; a.count = nullptr;
+    a.in_dtype = t->patch_dtype;
     a.w_stem = t->stem.w_packed; a.a_stem = t->stem.alpha; a.s_stem = t->stem.shift;
     for (int k = 0; k < 4; ++k)
         for (int j = 0; j < 2; ++j) {
@@ -1500,46 +1504,45 @@ static void fill_fused_args(FusedArgs& a, const ipsx_trunk* t, bool with_bf16) {
     a.w_down = t->blocks[2].down.w_packed; a.a_down = t->blocks[2].down.alpha; a.s_down = t->blocks[2].down.shift;
     a.wh_down = with_bf16 ? t->blocks[2].down.w_packed_bf16 : nullptr;
     a.wh_stem = with_bf16 ? t->stem.w_packed_bf16 : nullptr;
+    return a;
 }
 
-// table != nullptr: `patches` holds uint8 pixels (at a 16-byte address) and table[b] is the float32 value of byte b - the
-// exact fp32 trunk only, no stamps, no device-side count (ipsx_trunk_encode_u8 / _indexed_u8)
-// view != nullptr: `patches` holds whole images and the launch's patches are grid patches of *view (index, or first ..) -
-// the exact fp32 trunk only, no stamps, no device-side count (ipsx_trunk_encode_view)
-static int fused_launch(const ipsx_trunk* t, const float* patches, int64_t n, float* emb,
-                        unsigned long long* stamps, hipStream_t s, const int* index = nullptr,
-                        const int* count = nullptr, const float* table = nullptr, const ViewArgs* view = nullptr) {
-    FusedArgs a;
-    a.patches = patches; a.emb = emb; a.n = n; a.index = index; a.count = count;
-    a.in_dtype = t->patch_dtype;
-    if (table) {
-        if (t->precision != 0 || t->patch_dtype != 0 || stamps || count)
-            return fail(IPSX_EINVAL, "fused trunk: uint8 patches go with the exact fp32 trunk (precision 0, patch_dtype 0) only");
-        if (reinterpret_cast<uintptr_t>(patches) % 16 || reinterpret_cast<uintptr_t>(table) % 16)
-            return fail(IPSX_EINVAL, "fused trunk: uint8 patches and their table must lie at 16-byte addresses");
-    }
-    if (view && (t->precision != 0 || t->patch_dtype != 0 || stamps || count || table))
-        return fail(IPSX_EINVAL, "fused trunk: a patch view goes with the exact fp32 trunk on float32 images only");
-    if (t->patch_dtype != 0 && !(t->precision == 1 || t->precision == 2))
-        return fail(IPSX_EINVAL, "fused trunk: half-precision patch storage goes with precision 1 (bf16) or 2 (fp32x3)");
-    if (t->patch_dtype < 0 || t->patch_dtype > 2) return fail(IPSX_EINVAL, "fused trunk: patch_dtype %d", t->patch_dtype);
-    fill_fused_args(a, t, true);
+// what the fused view kernels get beside FusedArgs (the list travels in FusedArgs::index, as ever); 16-byte loads
+static ViewArgs fused_view_args(const PatchSrc& src) {
+    ViewArgs va = view_args(src, 4);
+    va.index = nullptr;
+    return va;
+}
+
+static const size_t FUSED_LDS = (size_t)8 * SLAB8 * sizeof(float);    // 141,824 B: one workgroup of eight per CU
+
+// `n` patches of `src` (checked by the entry: patch_src_check) -> emb.  A table or a view: the exact fp32 trunk only, no
+// stamps, no device-side count.
+int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, hipStream_t s, const int* count,
+                 unsigned long long* stamps) {
+    if ((src.table || src.view) && (stamps || count))
+        return fail(IPSX_EINVAL, "fused trunk: uint8 patches and patch views go without stamps and device-side counts");
+    FusedArgs a = fused_args(t, src, n, emb, true);
+    a.count = count;
     bool bf16 = t->precision != 0 && a.wh_down && a.wh_stem;
     for (int k = 0; k < 8; ++k) bf16 = bf16 && a.wh[k];
     if (t->precision != 0 && !bf16) return fail(IPSX_EINVAL, "fused trunk: precision %d needs w_packed_bf16 on the stem (ipsx_pack_stem_weight_split) and every block conv", t->precision);
+    static bool attr_set = false;
+    if (!attr_set) {
+        const auto lds_of = [](const void* kernel, size_t bytes) {
+            (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        };
+        lds_of(reinterpret_cast<const void*>(fused_trunk_x3_kernel<false>), 4 * XL<3>::SLAB);
+        lds_of(reinterpret_cast<const void*>(fused_trunk_x3_kernel<true>), 4 * XL<3>::SLAB);
+        lds_of(reinterpret_cast<const void*>(fused_trunk_bf16_kernel<false>), BF16_LDS);
+        lds_of(reinterpret_cast<const void*>(fused_trunk_bf16_kernel<true>), BF16_LDS);
+        lds_of(reinterpret_cast<const void*>(fused_trunk_kernel<false>), FUSED_LDS);
+        lds_of(reinterpret_cast<const void*>(fused_trunk_kernel<true>), FUSED_LDS);
+        lds_of(reinterpret_cast<const void*>(fused_trunk_u8_kernel), FUSED_LDS);
+        lds_of(reinterpret_cast<const void*>(fused_trunk_view_kernel), FUSED_LDS);
+        attr_set = true;
+    }
     if (t->precision == 2 || t->precision == 1) {      // the trunks on the bf16 matrix pipe (fused_trunk_split.h, fused_trunk_bf16.h)
-        static bool attr_split = false;
-        if (!attr_split) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_x3_kernel<false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 4 * XL<3>::SLAB);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_x3_kernel<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 4 * XL<3>::SLAB);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_bf16_kernel<false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, BF16_LDS);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_bf16_kernel<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, BF16_LDS);
-            attr_split = true;
-        }
         const dim3 block(256);
         if (t->precision == 2) {                       // fp32x3: four patches per workgroup
             const dim3 grid((unsigned)cdiv(n, 4));
@@ -1552,15 +1555,6 @@ static int fused_launch(const ipsx_trunk* t, const float* patches, int64_t n, fl
         if (stamps) fused_trunk_bf16_kernel<true><<<grid, block, BF16_LDS, s>>>(a, stamps);
         else fused_trunk_bf16_kernel<false><<<grid, block, BF16_LDS, s>>>(a, nullptr);
         return launched("fused_trunk_bf16");
-    }
-    const size_t lds = (size_t)8 * SLAB8 * sizeof(float);              // 141,824 B: one workgroup of eight per CU
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_kernel<false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_kernel<true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_set = true;
     }
     const int cus = device_cus();
     // What is left over after the whole rounds (8 patches per CU) goes to the two-wavefronts-per-patch kernel when that takes
@@ -1575,64 +1569,37 @@ static int fused_launch(const ipsx_trunk* t, const float* patches, int64_t n, fl
         // (three workgroups per CU), 2048 0.57
         if (g_pair_mode != 2 && !(rest <= round / 4 || (rest > round / 2 && rest <= 3 * round / 4))) rest = 0;
     }
+    // patches 0 .. n_full through the eight-patch kernel, patches n_full .. through the pair kernel: the same source, advanced.
+    // The three storage kinds differ in the kernels' last argument only (the table, the view, nothing).
     const int64_t n_full = n - rest;
     a.n = n_full;
-    if (table) {
-        static bool attr_u8 = false;
-        if (!attr_u8) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_u8_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_u8 = true;
-        }
-        if (n_full) fused_trunk_u8_kernel<<<dim3((unsigned)cdiv(n_full, 8)), dim3(512), lds, s>>>(a, table);
-        if (rest) {
-            a.n = rest;
-            if (index) a.index = index + n_full;
-            else a.patches = reinterpret_cast<const float*>(reinterpret_cast<const unsigned char*>(patches) + (size_t)n_full * 1024);
-            a.emb = emb + (size_t)n_full * 128;
-            fused_trunk_pair_u8_kernel<<<dim3((unsigned)cdiv(rest, 2)), dim3(256), (size_t)2 * SLAB * sizeof(float), s>>>(a, table);
-        }
+    const PatchSrc tail = patch_src_from(t, src, n_full);
+    const FusedArgs b = fused_args(t, tail, rest, emb + (size_t)n_full * 128, true);
+    const dim3 grid8((unsigned)cdiv(stamps ? n : n_full, 8)), grid2((unsigned)cdiv(rest, 2));
+    const size_t lds2 = (size_t)2 * SLAB * sizeof(float);
+    if (src.table) {
+        if (n_full) fused_trunk_u8_kernel<<<grid8, dim3(512), FUSED_LDS, s>>>(a, src.table);
+        if (rest) fused_trunk_pair_u8_kernel<<<grid2, dim3(256), lds2, s>>>(b, src.table);
         return launched("fused_trunk_u8");
     }
-    if (view) {
-        static bool attr_view = false;
-        if (!attr_view) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_view_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_view = true;
-        }
-        ViewArgs va = *view;
-        va.index = nullptr;                                           // (the list travels in a.index, as ever)
-        if (n_full) fused_trunk_view_kernel<<<dim3((unsigned)cdiv(n_full, 8)), dim3(512), lds, s>>>(a, va);
-        if (rest) {
-            a.n = rest;
-            if (index) a.index = index + n_full;
-            else va.first += n_full;
-            a.emb = emb + (size_t)n_full * 128;
-            fused_trunk_pair_view_kernel<<<dim3((unsigned)cdiv(rest, 2)), dim3(256), (size_t)2 * SLAB * sizeof(float), s>>>(a, va);
-        }
+    if (src.view) {
+        if (n_full) fused_trunk_view_kernel<<<grid8, dim3(512), FUSED_LDS, s>>>(a, fused_view_args(src));
+        if (rest) fused_trunk_pair_view_kernel<<<grid2, dim3(256), lds2, s>>>(b, fused_view_args(tail));
         return launched("fused_trunk_view");
     }
-    if (stamps)
-        fused_trunk_kernel<true><<<dim3((unsigned)cdiv(n, 8)), dim3(512), lds, s>>>(a, stamps);
-    else if (n_full)
-        fused_trunk_kernel<false><<<dim3((unsigned)cdiv(n_full, 8)), dim3(512), lds, s>>>(a, nullptr);
-    if (rest) {
-        a.n = rest;
-        if (index) a.index = index + n_full;
-        else a.patches = patches + (size_t)n_full * 1024;
-        a.emb = emb + (size_t)n_full * 128;
-        fused_trunk_pair_kernel<<<dim3((unsigned)cdiv(rest, 2)), dim3(256), (size_t)2 * SLAB * sizeof(float), s>>>(a);
-    }
+    if (stamps) fused_trunk_kernel<true><<<grid8, dim3(512), FUSED_LDS, s>>>(a, stamps);
+    else if (n_full) fused_trunk_kernel<false><<<grid8, dim3(512), FUSED_LDS, s>>>(a, nullptr);
+    if (rest) fused_trunk_pair_kernel<<<grid2, dim3(256), lds2, s>>>(b);
     return launched("fused_trunk");
 }
 
 // Every part of a call in ONE launch (ipsx_trunk_encode_parts): list entry j -> emb row j, done[k] += the patches of part k
 // as their workgroups finish.  The eight-patch kernel takes the whole list.  (The pair kernel for the tail, as fused_launch
 // does it, is a second launch: 9.42 against 9.45 ms at 40,000 patches, 0.3 % - not kept)
-int fused_trunk_encode_parts(const ipsx_trunk* t, const float* patches, const int* index, int64_t n, float* emb,
-                             const int64_t* part_end, int parts, int* done, hipStream_t s, const ViewArgs* view) {
-    if (t->precision != 0 || t->patch_dtype != 0)
+// src: float32 patches or a view, with the parts' joined index lists (checked by the entry: patch_src_check)
+int fused_trunk_encode_parts(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, const int64_t* part_end, int parts,
+                             int* done, hipStream_t s) {
+    if (t->precision != 0 || t->patch_dtype != 0 || src.table)
         return fail(IPSX_EINVAL, "trunk_encode_parts: the exact fp32 trunk on float32 patches only (precision %d, patch_dtype %d)",
                     t->precision, t->patch_dtype);
     if (parts < 1 || parts > 16) return fail(IPSX_EINVAL, "trunk_encode_parts: %d parts (1 .. 16)", parts);
@@ -1647,25 +1614,21 @@ int fused_trunk_encode_parts(const ipsx_trunk* t, const float* patches, const in
         pa.part_end[k] = (int)(before = part_end[k]);
     }
     if (before != n) return fail(IPSX_EINVAL, "trunk_encode_parts: part_end must increase and end on the list's length");
-    FusedArgs a;
-    a.patches = patches; a.emb = emb; a.n = n; a.index = index; a.count = nullptr; a.in_dtype = 0;
-    fill_fused_args(a, t, false);
-    const size_t lds = (size_t)8 * SLAB8 * sizeof(float);
+    const FusedArgs a = fused_args(t, src, n, emb, false);
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_parts_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_parts_view_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS);
         attr_set = true;
     }
-    if (view) {                                                       // `patches`: whole images, the list: grid patches
-        ViewArgs va = *view;
-        va.index = nullptr; va.first = 0;
-        fused_trunk_parts_view_kernel<<<dim3((unsigned)cdiv(n, 8)), dim3(512), lds, s>>>(a, pa, va);
+    const dim3 grid((unsigned)cdiv(n, 8));
+    if (src.view) {                                                   // whole images, the list: grid patches
+        fused_trunk_parts_view_kernel<<<grid, dim3(512), FUSED_LDS, s>>>(a, pa, fused_view_args(src));
         return launched("fused_trunk_parts_view");
     }
-    fused_trunk_parts_kernel<<<dim3((unsigned)cdiv(n, 8)), dim3(512), lds, s>>>(a, pa);
+    fused_trunk_parts_kernel<<<grid, dim3(512), FUSED_LDS, s>>>(a, pa);
     return launched("fused_trunk_parts");
 }
 
@@ -1675,8 +1638,7 @@ int fused_trunk_stream(const ipsx_trunk* t, const float* patches, int64_t n, flo
                        int r, float* logits, int32_t* ctl, int32_t* ready, int workgroups, int quad_pulls, hipStream_t s) {
     if (t->precision != 0 || t->patch_dtype != 0) return fail(IPSX_EINVAL, "trunk_stream: the exact fp32 trunk only");
     TrunkStreamArgs a;
-    a.f.patches = patches; a.f.emb = emb; a.f.n = n; a.f.index = nullptr; a.f.count = nullptr; a.f.in_dtype = 0;
-    fill_fused_args(a.f, t, false);
+    a.f = fused_args(t, PatchSrc{patches, nullptr, nullptr, nullptr, 0}, n, emb, false);
     a.pos = pos; a.vp = v_packed; a.R = r; a.logits = logits; a.ctl = ctl; a.ready = ready;
     a.n_pairs = (unsigned)cdiv(n, 2);
     // Four patches per pull run at the trunk's full rate (0.29 ms per pull at one workgroup per unit), two per pull at 0.84 of
@@ -1700,26 +1662,6 @@ int fused_trunk_stream(const ipsx_trunk* t, const float* patches, int64_t n, flo
     const int wgs = workgroups > 0 ? workgroups : device_cus() + 8;
     fused_trunk_stream_kernel<<<dim3((unsigned)wgs), dim3(256), lds, s>>>(a);
     return launched("fused_trunk_stream");
-}
-
-int fused_trunk_encode(const ipsx_trunk* t, const float* patches, int64_t n, float* emb, hipStream_t s) {
-    return fused_launch(t, patches, n, emb, nullptr, s);
-}
-
-int fused_trunk_encode_indexed(const ipsx_trunk* t, const float* patches, int64_t n_max, const int* index,
-                               const int* count, float* emb, hipStream_t s) {
-    return fused_launch(t, patches, n_max, emb, nullptr, s, index, count);
-}
-
-// grid patches of whole images (view->index, or view->first .. + n - 1) - ipsx_trunk_encode_view
-int fused_trunk_encode_view(const ipsx_trunk* t, const float* images, const ViewArgs* view, int64_t n, float* emb, hipStream_t s) {
-    return fused_launch(t, images, n, emb, nullptr, s, view->index, nullptr, nullptr, view);
-}
-
-// uint8 patches through table (256 floats, device); index: optional int32 patch numbers (nullptr: patches 0 .. n - 1)
-int fused_trunk_encode_u8(const ipsx_trunk* t, const unsigned char* patches, const float* table, int64_t n, const int* index,
-                          float* emb, hipStream_t s) {
-    return fused_launch(t, reinterpret_cast<const float*>(patches), n, emb, nullptr, s, index, nullptr, table);
 }
 
 }  // namespace ipsx
@@ -1825,5 +1767,7 @@ extern "C" __attribute__((visibility("default"))) void ipsx_dbg_fused_trunk_pair
 extern "C" __attribute__((visibility("default"))) int ipsx_dbg_fused_trunk_stamps(
     const ipsx_trunk* t, const float* patches, int64_t n, float* emb, unsigned long long* stamps, void* stream) {
     if (!ipsx::fused_trunk_supported(t)) return ipsx::fail(IPSX_EINVAL, "trunk is not the fused shape");
-    return ipsx::fused_launch(t, patches, n, emb, stamps, ipsx::as_stream(stream));
+    const ipsx::PatchSrc src{patches, nullptr, nullptr, nullptr, 0};
+    IPSX_TRY(ipsx::patch_src_check(t, src, n, true, "fused trunk"));
+    return ipsx::fused_launch(t, src, n, emb, ipsx::as_stream(stream), nullptr, stamps);
 }

@@ -44,7 +44,7 @@ __host__ __device__ inline long long patch_view_offset(const ipsx_patch_view& v,
 }
 
 // what a view kernel gets beside its usual arguments: patch j of the launch is grid patch index[j] (index: device int32) or
-// first + j; wide: the launch's load width, picked by the host (view_wide)
+// first + j; wide: the launch's load width, picked by the host (view_args, ipsx_internal.h)
 struct ViewArgs {
     ipsx_patch_view v;
     const int* index;
@@ -56,11 +56,6 @@ struct ViewArgs {
 __device__ __forceinline__ long long view_base(const ViewArgs& va, long long p) {
     const long long off = patch_view_offset(va.v, p);
     return off < 0 ? 0 : off;
-}
-
-// wide loads of `elems` floats (4: 16 bytes, 2: 8 bytes): every patch row starts at a multiple of the load width
-static inline int view_wide(const float* images, const ipsx_patch_view& v, int elems) {
-    return reinterpret_cast<uintptr_t>(images) % (elems * sizeof(float)) == 0 && v.w % elems == 0 && v.sw % elems == 0 ? 1 : 0;
 }
 
 }  // namespace ipsx

@@ -1,0 +1,72 @@
+// ipsx_internal.h - what the translation units of libipsx call in each other (none of it is part of include/ipsx.h), and
+// PatchSrc: the ONE description of where the patches of an image-encoder launch lie.
+#pragma once
+
+#include "ipsx_common.h"
+
+namespace ipsx {
+
+// ---- where the patches of a launch lie.  Patch j of the launch is patch index[j], or first + j, of
+//   the patch tensor at `base`: float32, t->patch_dtype (fused split trunks) or - with `table` - uint8 whose values are
+//   table[channel][byte]; or
+//   the grid of `view` over the whole float32 images at `base`.
+// A tensor that is read from patch k on has its base moved (`first` stays 0); only a view counts in `first`.
+struct PatchSrc {
+    const void* base;
+    const float* table;
+    const ipsx_patch_view* view;
+    const int* index;
+    long long first;
+};
+
+// the source of patches k .. of this source - the remainder of a launch, a chunk, the second half of a call
+static inline PatchSrc patch_src_from(const ipsx_trunk* t, PatchSrc s, int64_t k) {
+    if (s.index) s.index += k;
+    else if (s.view) s.first += k;
+    else s.base = static_cast<const unsigned char*>(s.base) +
+                  (size_t)k * t->c_in * t->h * t->w * (s.table ? 1 : (t->patch_dtype ? 2 : sizeof(float)));
+    return s;
+}
+
+// what a view kernel gets beside its usual arguments, made by the launcher that knows its kernel's load width: wide loads of
+// `elems` floats (4: 16 bytes, 2: 8 bytes) when every patch row starts at a multiple of that width
+static inline ViewArgs view_args(const PatchSrc& s, int elems) {
+    const ipsx_patch_view& v = *s.view;
+    ViewArgs va;
+    va.v = v; va.index = s.index; va.first = s.first;
+    va.wide = reinterpret_cast<uintptr_t>(s.base) % (elems * sizeof(float)) == 0 && v.w % elems == 0 && v.sw % elems == 0 ? 1 : 0;
+    return va;
+}
+
+static inline bool at_multiple(const void* p, uintptr_t bytes) { return reinterpret_cast<uintptr_t>(p) % bytes == 0; }
+
+// conv.hip (table: x holds uint8 elements)
+int conv2d_affine_impl(const ipsx_conv* cv, const float* x, const float* residual, float* y, int64_t n, int h,
+                       int w, int relu, int out_nhwc, void* stream, const float* table = nullptr);
+// conv_nhwc.hip
+int conv_nhwc_impl(const ipsx_conv* cv, const float* x, const float* residual, const float* row_stats, float* y,
+                   int64_t n, int h, int w, int relu, void* stream, int* ready = nullptr, int ready_value = 0,
+                   const int32_t* index = nullptr, int64_t src_rows = 0);
+// conv_nhwc_bf16.hip: the pooled fp32 map rounded once to bf16 (count % 8 == 0)
+int round_to_bf16(const float* x, void* y, size_t count, hipStream_t s);
+// fused_stage.hip: the leading 64 -> 64 BasicBlocks on a small map, LDS-resident (50-px patches: 13x13)
+int fused_stage64_blocks(const ipsx_block* blocks, int n_block, int h, int w);
+int fused_stage64(const ipsx_block* blocks, int n_block, const float* x, float* y, int64_t n, int h, int w, hipStream_t s);
+// ... and stem + max-pool of 1x50x50 / 3x100x100 patches -> (n, 13, 13, 64) / (n, 25, 25, 64) channels-last:
+// 1 = ran, 0 = the trunk is another shape, -1 = failed
+int fused_stem_pool50(const ipsx_trunk* t, const PatchSrc& src, float* y, int64_t n, hipStream_t s);
+bool fused_stem_pool50_covers(const ipsx_trunk* t);
+bool fused_stem_pool100x3_covers(const ipsx_trunk* t);
+// fused_trunk.hip; count: a device-side number of patches (blank-patch dedup), stamps: diagnostic clocks per patch
+bool fused_trunk_supported(const ipsx_trunk* t);
+int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, hipStream_t s, const int* count = nullptr,
+                 unsigned long long* stamps = nullptr);
+int fused_trunk_encode_parts(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, const int64_t* part_end, int parts,
+                             int* done, hipStream_t s);
+int fused_trunk_stream(const ipsx_trunk* t, const float* patches, int64_t n, float* emb, const float* pos, const float* v_packed,
+                       int r, float* logits, int32_t* ctl, int32_t* ready, int workgroups, int quad_pulls, hipStream_t s);
+// trunk.hip: a source of `n` patches against a trunk, once per entry (`what`: the entry's name in the message; `fused`:
+// fused_trunk_supported(t))
+int patch_src_check(const ipsx_trunk* t, const PatchSrc& src, int64_t n, bool fused, const char* what);
+
+}  // namespace ipsx

@@ -11,33 +11,9 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "ipsx_common.h"
+#include "ipsx_internal.h"
 
 namespace ipsx {
-
-// conv.hip
-int conv2d_affine_impl(const ipsx_conv* cv, const float* x, const float* residual, float* y, int64_t n, int h,
-                       int w, int relu, int out_nhwc, void* stream, const float* table = nullptr);   // table: x holds uint8
-// fused_stage.hip: the leading 64 -> 64 BasicBlocks on a small map, LDS-resident (50-px patches: 13x13)
-int fused_stage64_blocks(const ipsx_block* blocks, int n_block, int h, int w);
-int fused_stage64(const ipsx_block* blocks, int n_block, const float* x, float* y, int64_t n, int h, int w, hipStream_t s);
-int fused_stem_pool50(const ipsx_trunk* t, const float* patches, float* y, int64_t n, hipStream_t s,
-                      const float* table = nullptr,    // 1 = ran, 0 = other shape; table: patches holds uint8
-                      const ViewArgs* view = nullptr); // view: patches holds whole images (ipsx_trunk_encode_view)
-bool fused_stem_pool50_covers(const ipsx_trunk* t);
-bool fused_stem_pool100x3_covers(const ipsx_trunk* t);
-// conv_nhwc_bf16.hip: the pooled fp32 map rounded once to bf16 (count % 8 == 0)
-int round_to_bf16(const float* x, void* y, size_t count, hipStream_t s);
-// fused_trunk.hip
-bool fused_trunk_supported(const ipsx_trunk* t);
-int fused_trunk_encode(const ipsx_trunk* t, const float* patches, int64_t n, float* emb, hipStream_t s);
-int fused_trunk_encode_u8(const ipsx_trunk* t, const unsigned char* patches, const float* table, int64_t n, const int* index,
-                          float* emb, hipStream_t s);
-int fused_trunk_encode_view(const ipsx_trunk* t, const float* images, const ViewArgs* view, int64_t n, float* emb, hipStream_t s);
-int fused_trunk_encode_parts(const ipsx_trunk* t, const float* patches, const int* index, int64_t n, float* emb,
-                             const int64_t* part_end, int parts, int* done, hipStream_t s, const ViewArgs* view);
-int fused_trunk_stream(const ipsx_trunk* t, const float* patches, int64_t n, float* emb, const float* pos, const float* v_packed,
-                       int r, float* logits, int32_t* ctl, int32_t* ready, int workgroups, int quad_pulls, hipStream_t s);
 
 struct TrunkGeom {
     size_t max_elems;   // largest per-patch activation (floats) of any layer
@@ -123,6 +99,42 @@ static int layered_bf16_check(const ipsx_trunk* t) {
     return IPSX_OK;
 }
 
+static int64_t view_patches(const ipsx_patch_view& v) {
+    return (int64_t)v.b * ((v.h - v.ph) / v.sh + 1) * ((v.w - v.pw) / v.sw + 1);
+}
+
+// Is `src` a source this trunk can encode `n` patches from?  Asked ONCE, by every entry, before its first launch.
+int patch_src_check(const ipsx_trunk* t, const PatchSrc& src, int64_t n, bool fused, const char* what) {
+    IPSX_REQUIRE(t->precision >= 0 && t->precision <= 2, "%s: precision %d", what, t->precision);
+    IPSX_REQUIRE(t->patch_dtype >= 0 && t->patch_dtype <= 2, "%s: patch_dtype %d", what, t->patch_dtype);
+    IPSX_REQUIRE(t->precision != 2 || fused, "%s: fp32x3 exists for the fused 1x32x32 trunk only", what);
+    IPSX_REQUIRE(t->patch_dtype == 0 || (fused && t->precision != 0), "%s: the stem kernels of the layer-by-layer trunk "
+                 "(stem_pool50_kernel, stem_pool100x3_kernel, conv_any_kernel) read float32 patches; half-precision patch storage "
+                 "exists for the fused 1x32x32 trunk at precision 1 (bf16) / 2 (fp32x3) only", what);
+    IPSX_REQUIRE(!(src.table && src.view), "%s: a patch view reads float32 images", what);
+    if (src.table) {
+        IPSX_REQUIRE(t->precision == 0 && t->patch_dtype == 0, "%s: uint8 patches go with the exact fp32 trunk only (precision 0, "
+                     "patch_dtype 0), got precision %d, patch_dtype %d", what, t->precision, t->patch_dtype);
+        // what each stem's byte loads need (the generic stem gathers byte by byte); the layered stems' codes are those
+        // their launcher used to hand up
+        if (fused)
+            IPSX_REQUIRE(at_multiple(src.base, 16) && at_multiple(src.table, 16),
+                         "fused trunk: uint8 patches and their table must lie at 16-byte addresses");
+        else if (fused_stem_pool100x3_covers(t) && !(at_multiple(src.base, 16) && at_multiple(src.table, 16)))
+            return fail(IPSX_EHIP, "stem_pool100x3: uint8 patches and their table must lie at 16-byte addresses");
+        else if (fused_stem_pool50_covers(t) && !(at_multiple(src.base, 4) && at_multiple(src.table, 16)))
+            return fail(IPSX_EHIP, "stem_pool50: uint8 patches must lie at a 4-byte address, their table at a 16-byte address");
+    }
+    if (src.view) {
+        IPSX_REQUIRE(at_multiple(src.base, 4), "%s: images must lie at a 4-byte address", what);
+        IPSX_REQUIRE(ipsx_trunk_view_supported(t, src.view), "%s: the exact fp32 trunks whose stem stages its patch into LDS "
+                     "(1x32x32 fused, 1x50x50, 3x100x100) on a valid view of their patch shape (ipsx_trunk_view_supported)", what);
+        IPSX_REQUIRE(src.index || src.first + n <= view_patches(*src.view), "%s: patches %lld .. %lld of a grid of %lld", what,
+                     src.first, (long long)(src.first + n), (long long)view_patches(*src.view));
+    }
+    return IPSX_OK;
+}
+
 }  // namespace ipsx
 
 using namespace ipsx;
@@ -150,36 +162,18 @@ IPSX_API const char* ipsx_trunk_kernel(const ipsx_trunk* t) {
     return "conv_nhwc_kernel (layer by layer)";
 }
 
-// ipsx_trunk_encode and ipsx_trunk_encode_u8: table == nullptr - `patches_v` holds float32 (or, fused split trunks,
-// t->patch_dtype) elements; else uint8 elements whose values are table[channel][byte] - only the stem's load differs
-// ipsx_trunk_encode_view: view != nullptr - `patches_v` holds whole float32 images and patch j of the call is grid patch
-// view->index[j] (or view->first + j) of view->v; the caller has checked ipsx_trunk_view_supported
-static int trunk_encode(const ipsx_trunk* t, const void* patches_v, const float* table, int64_t n_patch, float* emb,
-                        void* workspace, size_t workspace_bytes, void* stream, const ViewArgs* view = nullptr) {
+// The one path behind ipsx_trunk_encode, _u8 and _view: `n_patch` patches of `src` -> emb; only the stem's load differs
+static int trunk_encode(const ipsx_trunk* t, const PatchSrc& src, int64_t n_patch, float* emb, void* workspace,
+                        size_t workspace_bytes, void* stream, const char* what) {
     TrunkGeom g;
     IPSX_TRY(trunk_geom(t, &g));
-    const float* patches = static_cast<const float*>(patches_v);
-    const unsigned char* patches_u8 = static_cast<const unsigned char*>(patches_v);
-    IPSX_REQUIRE(patches && emb && n_patch >= 0, "trunk_encode: bad arguments");
-    IPSX_REQUIRE(!table || (t->precision == 0 && t->patch_dtype == 0), "trunk_encode_u8: uint8 patches go with the exact fp32 "
-                 "trunk only (precision 0, patch_dtype 0), got precision %d, patch_dtype %d", t->precision, t->patch_dtype);
+    IPSX_REQUIRE(src.base && emb && n_patch >= 0, "%s: bad arguments", what);
     const bool fused = fused_trunk_supported(t);
-    IPSX_REQUIRE(t->precision >= 0 && t->precision <= 2, "trunk_encode: precision %d", t->precision);
-    IPSX_REQUIRE(t->precision != 2 || fused, "trunk_encode: fp32x3 exists for the fused 1x32x32 trunk only");
-    IPSX_REQUIRE(t->patch_dtype == 0 || fused, "trunk_encode: the stem kernels of the layer-by-layer trunk (stem_pool50_kernel, "
-                 "stem_pool100x3_kernel, conv_any_kernel) read float32 patches; half-precision patch storage exists for the fused "
-                 "1x32x32 trunk at precision 1 / 2 only");
-    IPSX_REQUIRE(t->patch_dtype == 0 || t->precision != 0, "trunk_encode: half-precision patch storage needs precision 1 / 2");
+    IPSX_TRY(patch_src_check(t, src, n_patch, fused, what));
     const bool bf16 = t->precision == 1 && !fused;       // ("bf16 layered trunk")
     if (bf16) IPSX_TRY(layered_bf16_check(t));
     if (n_patch == 0) return IPSX_OK;
-    if (fused && table) return fused_trunk_encode_u8(t, patches_u8, table, n_patch, nullptr, emb, as_stream(stream));
-    if (fused && view) {
-        ViewArgs va = *view;
-        va.wide = view_wide(patches, va.v, 4);
-        return fused_trunk_encode_view(t, patches, &va, n_patch, emb, as_stream(stream));
-    }
-    if (fused) return fused_trunk_encode(t, patches, n_patch, emb, as_stream(stream));
+    if (fused) return fused_launch(t, src, n_patch, emb, as_stream(stream));
 
     const int64_t chunk = workspace ? chunk_for(g, n_patch, workspace_bytes) : 0;      // chunks fit what the caller gave
     if (chunk < 1)
@@ -188,7 +182,6 @@ static int trunk_encode(const ipsx_trunk* t, const void* patches_v, const float*
     const size_t buf_elems = (size_t)chunk * g.max_elems;
     float* buf[4];
     for (int i = 0; i < 4; ++i) buf[i] = static_cast<float*>(workspace) + i * buf_elems;
-    const size_t patch_elems = (size_t)t->c_in * t->h * t->w;
     // bf16: the same workspace and the same chunks - four bf16 activation buffers in its first half, the fp32 stem output
     // and pooled map in its second (2 + 2 + 4 + 4 bytes x chunk x max_elems of the 16 it has)
     unsigned short* hb[4];
@@ -200,19 +193,14 @@ static int trunk_encode(const ipsx_trunk* t, const void* patches_v, const float*
         int h = conv_out(t->h, t->stem.kh, t->stem.stride, t->stem.pad);
         int w = conv_out(t->w, t->stem.kw, t->stem.stride, t->stem.pad);
         int c = t->stem.c_out;
-        // stem reads the NCHW patches and writes channels-last; everything after it is channels-last
-        const float* chunk_in = table ? reinterpret_cast<const float*>(patches_u8 + p0 * patch_elems) : patches + p0 * patch_elems;
-        ViewArgs va;
-        if (view) {                                    // the chunk's patches: the list's entries p0 .. or the grid's first + p0 ..
-            va = *view;
-            if (va.index) va.index += p0;
-            else va.first += p0;
-        }
-        const int fused_stem = fused_stem_pool50(t, view ? patches : chunk_in, buf[1], n, as_stream(stream), table, view ? &va : nullptr);
+        // stem reads the NCHW patches (the chunk's: the source from patch p0 on) and writes channels-last; everything after
+        // it is channels-last
+        const PatchSrc chunk_src = patch_src_from(t, src, p0);
+        const int fused_stem = fused_stem_pool50(t, chunk_src, buf[1], n, as_stream(stream));
         if (fused_stem < 0) return IPSX_EHIP;
-        IPSX_REQUIRE(fused_stem || !view, "trunk_encode_view: this trunk's stem does not read through a view");
         if (!fused_stem) {
-            IPSX_TRY(conv2d_affine_impl(&t->stem, chunk_in, nullptr, buf[0], n, t->h, t->w, 1, 1, stream, table));
+            IPSX_TRY(conv2d_affine_impl(&t->stem, static_cast<const float*>(chunk_src.base), nullptr, buf[0], n, t->h, t->w, 1, 1,
+                                        stream, src.table));
             IPSX_TRY(ipsx_maxpool_3x3s2_nhwc(buf[0], buf[1], n, c, h, w, stream));
         }
         h = conv_out(h, 3, 2, 1); w = conv_out(w, 3, 2, 1);
@@ -292,22 +280,25 @@ static int trunk_encode(const ipsx_trunk* t, const void* patches_v, const float*
 
 IPSX_API int ipsx_trunk_encode(const ipsx_trunk* t, const float* patches, int64_t n_patch, float* emb,
                                void* workspace, size_t workspace_bytes, void* stream) {
-    return trunk_encode(t, patches, nullptr, n_patch, emb, workspace, workspace_bytes, stream);
+    return trunk_encode(t, PatchSrc{patches, nullptr, nullptr, nullptr, 0}, n_patch, emb, workspace, workspace_bytes, stream,
+                        "trunk_encode");
 }
 
 IPSX_API int ipsx_trunk_encode_u8(const ipsx_trunk* t, const uint8_t* patches, const float* table, int64_t n_patch, float* emb,
                                   void* workspace, size_t workspace_bytes, void* stream) {
     IPSX_REQUIRE(table, "trunk_encode_u8: no table");
-    return trunk_encode(t, patches, table, n_patch, emb, workspace, workspace_bytes, stream);
+    return trunk_encode(t, PatchSrc{patches, table, nullptr, nullptr, 0}, n_patch, emb, workspace, workspace_bytes, stream,
+                        "trunk_encode_u8");
 }
 
 IPSX_API int ipsx_trunk_encode_indexed_u8(const ipsx_trunk* t, const uint8_t* patches, const float* table, const int32_t* index,
                                           int64_t n_index, float* emb, void* stream) {
     IPSX_REQUIRE(t && patches && table && index && emb && n_index >= 0, "trunk_encode_indexed_u8: bad arguments");
     IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_indexed_u8: only the fused 1x32x32 trunk is supported");
-    IPSX_REQUIRE(t->precision == 0 && t->patch_dtype == 0, "trunk_encode_indexed_u8: uint8 patches go with the exact fp32 trunk only");
+    const PatchSrc src{patches, table, nullptr, index, 0};
+    IPSX_TRY(patch_src_check(t, src, n_index, true, "trunk_encode_indexed_u8"));
     if (n_index == 0) return IPSX_OK;
-    return fused_trunk_encode_u8(t, patches, table, n_index, index, emb, as_stream(stream));
+    return fused_launch(t, src, n_index, emb, as_stream(stream));
 }
 
 // ---- the patch-grid view (3.06): whole images in place of the patch tensor
@@ -320,33 +311,21 @@ IPSX_API int ipsx_trunk_view_supported(const ipsx_trunk* t, const ipsx_patch_vie
     return fused_trunk_supported(t) || fused_stem_pool50_covers(t) || fused_stem_pool100x3_covers(t) ? 1 : 0;
 }
 
-static int64_t view_patches(const ipsx_patch_view& v) {
-    return (int64_t)v.b * ((v.h - v.ph) / v.sh + 1) * ((v.w - v.pw) / v.sw + 1);
-}
-
 IPSX_API int ipsx_trunk_encode_view(const ipsx_trunk* t, const float* images, const ipsx_patch_view* v, const int32_t* index,
                                     int64_t first, int64_t n, float* emb, void* workspace, size_t workspace_bytes, void* stream) {
     IPSX_REQUIRE(t && images && v && emb && n >= 0 && first >= 0, "trunk_encode_view: bad arguments");
-    IPSX_REQUIRE(reinterpret_cast<uintptr_t>(images) % 4 == 0, "trunk_encode_view: images must lie at a 4-byte address");
-    IPSX_REQUIRE(ipsx_trunk_view_supported(t, v), "trunk_encode_view: the exact fp32 trunks whose stem stages its patch into LDS "
-                 "(1x32x32 fused, 1x50x50, 3x100x100) on a valid view of their patch shape (ipsx_trunk_view_supported)");
-    IPSX_REQUIRE(index || first + n <= view_patches(*v), "trunk_encode_view: patches %lld .. %lld of a grid of %lld",
-                 (long long)first, (long long)(first + n), (long long)view_patches(*v));
-    ViewArgs va;
-    va.v = *v; va.index = index; va.first = index ? 0 : first; va.wide = 0;
-    return trunk_encode(t, images, nullptr, n, emb, workspace, workspace_bytes, stream, &va);
+    return trunk_encode(t, PatchSrc{images, nullptr, v, index, index ? 0 : first}, n, emb, workspace, workspace_bytes, stream,
+                        "trunk_encode_view");
 }
 
 IPSX_API int ipsx_trunk_encode_parts_view(const ipsx_trunk* t, const float* images, const ipsx_patch_view* v, const int32_t* index,
                                           int64_t n_index, float* emb, const int64_t* part_end, int n_parts, int32_t* done,
                                           void* stream) {
     IPSX_REQUIRE(t && images && v && index && emb && part_end && done, "trunk_encode_parts_view: null pointer");
-    IPSX_REQUIRE(reinterpret_cast<uintptr_t>(images) % 4 == 0, "trunk_encode_parts_view: images must lie at a 4-byte address");
-    IPSX_REQUIRE(fused_trunk_supported(t) && ipsx_trunk_view_supported(t, v),
-                 "trunk_encode_parts_view: the fused fp32 1x32x32 trunk on a valid view of 1x32x32 patches only");
-    ViewArgs va;
-    va.v = *v; va.index = nullptr; va.first = 0; va.wide = view_wide(images, *v, 4);
-    return fused_trunk_encode_parts(t, images, index, n_index, emb, part_end, n_parts, done, as_stream(stream), &va);
+    IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_parts_view: the fused fp32 1x32x32 trunk on a valid view of 1x32x32 patches only");
+    const PatchSrc src{images, nullptr, v, index, 0};
+    IPSX_TRY(patch_src_check(t, src, n_index, true, "trunk_encode_parts_view"));
+    return fused_trunk_encode_parts(t, src, n_index, emb, part_end, n_parts, done, as_stream(stream));
 }
 
 // One image: trunk AND logits of its patches as ONE persistent launch that feeds ipsx_scan_persistent patch by patch

@@ -959,6 +959,39 @@ class PatchView:
         return images if images.is_contiguous() else images.contiguous()
 
 
+class PatchSource:
+    """Where the patches of an image-encoder call lie - what ``EncoderPlan.encode_source`` reads.  Either a patch tensor
+    ``PatchSource(patches, table=None)``: (P, C, h, w) or (B, N, C, h, w) on the GPU, float32, float16 / bfloat16 under
+    IPSX_PRECISION=bf16 / fp32x3, or uint8 with its ``table`` (C, 256); or whole images read through a patch grid
+    ``PatchSource(images=..., view=...)`` (``PatchView``), whose patch tensor is never made.  Everything that
+    refuses a storage kind does so here, once, before the first launch; what is kept is contiguous.  ``shape`` is that of
+    the patch tensor (for a view: the one ``patchify`` would make), ``count`` its number of patches."""
+
+    __slots__ = ("patches", "table", "images", "view", "shape", "dtype", "device", "count")
+
+    def __init__(self, patches=None, table=None, images=None, view=None):
+        self.patches = self.table = self.images = self.view = None
+        if view is not None:
+            self.images, self.view = view.check(images), view
+            self.shape = torch.Size((view.image_shape[0], view.per_image) + view.patch_shape)
+            self.dtype, self.device, self.count = torch.float32, images.device, view.count
+            return
+        self.patches = patches = _patches(patches, table)
+        if table is not None:
+            self.table = _patch_table(table, patches.shape[-3], patches.device)
+        self.shape, self.dtype, self.device = patches.shape, patches.dtype, patches.device
+        self.count = patches.shape[:-3].numel()
+
+    @property
+    def is_view(self):
+        return self.view is not None
+
+    @property
+    def base(self):
+        """The tensor the kernels' base pointer points into."""
+        return self.images if self.view is not None else self.patches
+
+
 def gather_patches_view(images, view, idx):
     """images (B, C, H, W) float32 on the GPU, idx (B, M) int64 patch numbers inside each image (py * nx + px) ->
     (B, M, C, ph, pw): ``patchify(images, ...)[b, idx[b, m]]`` copied straight out of the images."""

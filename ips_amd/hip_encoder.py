@@ -9,7 +9,7 @@ import os
 
 import torch
 
-from .hip import (lib, _ck, _p, _f32, _stream, _patches, _patch_table, _PATCH_DTYPES, Conv, Block, Trunk, precision, dedup_blank, weights_generation)
+from .hip import (lib, _ck, _p, _f32, _stream, _patches, PatchSource, _PATCH_DTYPES, Conv, Block, Trunk, precision, dedup_blank, weights_generation)
 
 
 # ------------------------------------------------------------------ encoder plan
@@ -242,101 +242,95 @@ class EncoderPlan:
         if not self.is_image:
             return False
         self._refresh()
-        self.trunk.h, self.trunk.w = x_shape[-2], x_shape[-1]
-        return x_shape[-3] == self.trunk.c_in and lib().ipsx_trunk_kernel(C.byref(self.trunk)).startswith(b"fused")
+        t = self._describe(x_shape)
+        return x_shape[-3] == t.c_in and lib().ipsx_trunk_kernel(C.byref(t)).startswith(b"fused")
 
-    def encode_indexed(self, flat, index, table=None, parts=None):
-        """flat (P, C, h, w) contiguous on the GPU, index (n,) int32 -> (n, D) embeddings of flat[index].  uint8 ``flat``
-        with its ``table`` (C, 256): the embeddings of ``table[c][flat]`` (``ipsx_trunk_encode_indexed_u8``).
+    def _describe(self, patch_shape, patch_dtype=0):
+        """The trunk struct, told the (..., C, h, w) patches and storage type the next library call is about.  Every
+        question and every encode call says this itself; none relies on what an earlier one wrote."""
+        t = self.trunk
+        t.h, t.w, t.patch_dtype = patch_shape[-2], patch_shape[-1], patch_dtype
+        return t
+
+    def encode_source(self, src, index=None, first=0, n=None, parts=None, out=None):
+        """The image trunk on patches of ``src`` (a ``hip.PatchSource``) -> (n, D) embeddings: of its patches ``index``
+        (int32 numbers, on the device), or ``first .. first + n - 1`` (default: all from ``first`` on).  The ONE way into the
+        ``ipsx_trunk_encode*`` family; which export runs follows from the source (float32 / half / uint8 patches, a view)
+        and from how it is addressed.  An index list: the fused 1x32x32 trunk, or a view on any trunk that reads one.
         ``parts`` = (part_end, done): ``index`` is the index lists of several parts one after the other, ending at the
         list entries ``part_end`` (ints), encoded as ONE launch that counts part k's finished patches into ``done[k]``
-        (int32 on the GPU, zeroed by the caller on this stream) - ``ipsx_trunk_encode_parts``: float32 patches on the exact
-        fp32 fused trunk only."""
+        (int32 on the GPU, zeroed by the caller on this stream) - float32 patches or a view on the exact fp32 fused trunk."""
         self._refresh()
-        flat = _patches(flat, table)
-        out = torch.empty((index.numel(), self.d_out), dtype=torch.float32, device=flat.device)
-        if parts is not None:
-            if table is not None or flat.dtype != torch.float32:
-                raise TypeError("encode_indexed(parts=...): float32 patches only")
-            ends, done = parts
-            _ck(lib().ipsx_trunk_encode_parts(C.byref(self.trunk), _p(flat), _p(index), index.numel(), _p(out),
-                                              (C.c_int64 * len(ends))(*ends), len(ends), _p(done), _stream()),
-                "ipsx_trunk_encode_parts")
-            return out
-        if table is not None:
-            _ck(lib().ipsx_trunk_encode_indexed_u8(C.byref(self.trunk), _p(flat), _p(_patch_table(table, flat.shape[1], flat.device)),
-                                                   _p(index), index.numel(), _p(out), _stream()), "ipsx_trunk_encode_indexed_u8")
-            return out
-        self.trunk.patch_dtype = _PATCH_DTYPES[flat.dtype]
-        try:
-            _ck(lib().ipsx_trunk_encode_indexed(C.byref(self.trunk), _p(flat), _p(index), index.numel(), _p(out),
-                                                _stream()), "ipsx_trunk_encode_indexed")
-        finally:
-            self.trunk.patch_dtype = 0
-        return out
-
-    def view_supported(self, view):
-        """Can ``encode_view`` read the patches of this ``hip.PatchView``?  The exact fp32 trunks whose stem stages its
-        patch into LDS (1x32x32 fused, 1x50x50, 3x100x100) on a view of their patch shape (``ipsx_trunk_view_supported``)."""
-        if not self.is_image:
-            return False
-        self._refresh()
-        self.trunk.h, self.trunk.w = view.patch_size
-        return bool(lib().ipsx_trunk_view_supported(C.byref(self.trunk), C.byref(view.struct)))
-
-    def view_kernel_name(self, view):
-        """The kernel that reads the images for this view (None: not supported)."""
-        if not self.view_supported(view):
-            return None
-        name = lib().ipsx_trunk_kernel(C.byref(self.trunk)).decode()
-        return "fused_trunk_view_kernel" if name.startswith("fused") else name.split(" ")[0].replace("_kernel", "_view_kernel")
-
-    def encode_view(self, images, view, index=None, first=0, n=None, parts=None):
-        """images (B, C, H, W) float32 on the GPU + their ``hip.PatchView`` -> (n, D) embeddings of grid patches
-        ``index`` (int32, device) or ``first .. first + n - 1`` (default: every patch): the bits of ``encode`` on the same
-        patches of ``hip.patchify(images, ...)`` - the stems read the images, no patch tensor exists
-        (``ipsx_trunk_encode_view``).  ``parts`` = (part_end, done): as ``encode_indexed(parts=...)``, fused trunk only."""
-        if not self.view_supported(view):
+        # the trunk struct describes THIS call's patches: nothing an earlier call or question left in it is read
+        t, L = self._describe(src.shape, 0 if src.table is not None else _PATCH_DTYPES[src.dtype]), lib()
+        if src.shape[-3] != t.c_in:
+            raise ValueError("patches have {} channels, encoder expects {}".format(src.shape[-3], t.c_in))
+        if src.is_view and not L.ipsx_trunk_view_supported(C.byref(t), C.byref(src.view.struct)):
             raise ValueError("this encoder does not read patches through a view (EncoderPlan.view_supported)")
-        images = view.check(images)
         if index is not None:
-            if index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous() or index.device != images.device:
-                raise ValueError("index must be a contiguous 1-d int32 tensor on the images' device")
+            if index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous() or index.device != src.device:
+                raise ValueError("index must be a contiguous 1-d int32 tensor on the patches' device")
             first, n = 0, index.numel()
         elif n is None:
-            n = view.count - first
-        if first < 0 or n < 0 or (index is None and first + n > view.count):
-            raise ValueError("patches {} .. {} of a view of {}".format(first, first + n, view.count))
-        out = torch.empty((n, self.d_out), dtype=torch.float32, device=images.device)
+            n = src.count - first
+        if first < 0 or n < 0 or (index is None and first + n > src.count):
+            raise ValueError("patches {} .. {} of a source of {}".format(first, first + n, src.count))
+        if out is None:
+            out = torch.empty((n, self.d_out), dtype=torch.float32, device=src.device)
         if n == 0:
             return out
-        vs = C.byref(view.struct)
+        tr, vs = C.byref(t), C.byref(src.view.struct) if src.is_view else None
+        tab, base = _p(src.table), src.base
         if parts is not None:
-            if index is None:
-                raise ValueError("encode_view(parts=...) takes the parts' index lists")
-            ends, done = parts
-            _ck(lib().ipsx_trunk_encode_parts_view(C.byref(self.trunk), _p(images), vs, _p(index), n, _p(out),
-                                                   (C.c_int64 * len(ends))(*ends), len(ends), _p(done), _stream()),
-                "ipsx_trunk_encode_parts_view")
+            if index is None or tab.value or src.dtype != torch.float32:
+                raise TypeError("parts=(part_end, done) take float32 patches and the parts' index lists")
+            ends, done = (C.c_int64 * len(parts[0]))(*parts[0]), _p(parts[1])
+            if vs is not None:
+                _ck(L.ipsx_trunk_encode_parts_view(tr, _p(base), vs, _p(index), n, _p(out), ends, len(ends), done, _stream()),
+                    "ipsx_trunk_encode_parts_view")
+            else:
+                _ck(L.ipsx_trunk_encode_parts(tr, _p(base), _p(index), n, _p(out), ends, len(ends), done, _stream()),
+                    "ipsx_trunk_encode_parts")
             return out
+        if index is not None and vs is None:               # a patch tensor through an index list: the fused trunk
+            if tab.value:
+                _ck(L.ipsx_trunk_encode_indexed_u8(tr, _p(base), tab, _p(index), n, _p(out), _stream()), "ipsx_trunk_encode_indexed_u8")
+            else:
+                _ck(L.ipsx_trunk_encode_indexed(tr, _p(base), _p(index), n, _p(out), _stream()), "ipsx_trunk_encode_indexed")
+            return out
+        flat = base if vs is not None else base.view(-1, *src.shape[-3:])
 
         def run(lo, cnt, ws, nb):
-            ix = C.c_void_p(index.data_ptr() + 4 * lo) if index is not None else C.c_void_p(0)
-            _ck(lib().ipsx_trunk_encode_view(C.byref(self.trunk), _p(images), vs, ix, first + lo if index is None else 0, cnt,
-                                             _p(out[lo:lo + cnt]), _p(ws), nb, _stream()), "ipsx_trunk_encode_view")
+            """Patches lo .. lo + cnt of the call - the library's own rule for "the source from patch lo on": the index is
+            advanced, else the view's first patch, else the tensor."""
+            outs = _p(out[lo:lo + cnt])
+            if vs is not None:
+                _ck(L.ipsx_trunk_encode_view(tr, _p(flat), vs, _p(index[lo:]) if index is not None else None,
+                                             0 if index is not None else first + lo, cnt, outs, _p(ws), nb, _stream()),
+                    "ipsx_trunk_encode_view")
+            elif tab.value:
+                _ck(L.ipsx_trunk_encode_u8(tr, _p(flat[first + lo:]), tab, cnt, outs, _p(ws), nb, _stream()), "ipsx_trunk_encode_u8")
+            else:
+                _ck(L.ipsx_trunk_encode(tr, _p(flat[first + lo:]), cnt, outs, _p(ws), nb, _stream()), "ipsx_trunk_encode")
 
-        # (layer-by-layer trunks: two halves on two streams, as encode_plain runs them)
+        # Layer-by-layer trunks: the batch goes through in two halves on two streams.  The stem and the max-pool are
+        # HBM-bound (together 11-13 % of the trunk's time for 1 % of its arithmetic), the residual stages MFMA-bound:
+        # side by side, one half's stem / pool / epilogues fill what the other half's convolutions leave idle
+        # (50-px MNIST 14.25 -> 13.89 ms, traffic signs 22.75 -> 22.11 ms; three streams gain less).  Same kernels on
+        # the same patches: results are unchanged.  IPSX_LAYERED_STREAMS=1 switches it off.
         ns = int(os.environ.get("IPSX_LAYERED_STREAMS", "2"))
-        if ns > 1 and n >= 1024 and not lib().ipsx_trunk_kernel(C.byref(self.trunk)).startswith(b"fused"):
+        if ns > 1 and n >= 1024 and not L.ipsx_trunk_kernel(tr).startswith(b"fused"):
             cuts = [n * k // ns for k in range(ns + 1)]
-            nb = lib().ipsx_trunk_workspace_bytes(C.byref(self.trunk), max(cuts[k + 1] - cuts[k] for k in range(ns)))
-            budget = lib().ipsx_trunk_workspace_bytes(C.byref(self.trunk), 1 << 40)
-            nb = min(nb, max(budget // ns, lib().ipsx_trunk_workspace_bytes(C.byref(self.trunk), 1)))
+            nb = L.ipsx_trunk_workspace_bytes(tr, max(cuts[k + 1] - cuts[k] for k in range(ns)))
+            # the library's budget (a share of the free memory) is per CALL: the ns concurrent calls split it - each
+            # chunks its part of the batch to the workspace it is given
+            budget = L.ipsx_trunk_workspace_bytes(tr, 1 << 40)
+            nb = min(nb, max(budget // ns, L.ipsx_trunk_workspace_bytes(tr, 1)))
             nb -= nb % 256
-            ws = self._workspace(ns * nb, images.device)
+            ws = self._workspace(ns * nb, src.device)
             if len(getattr(self, "_sides", [])) < ns - 1:
-                self._sides = [torch.cuda.Stream(device=images.device) for _ in range(ns - 1)]
-            main = torch.cuda.current_stream(images.device)
+                self._sides = [torch.cuda.Stream(device=src.device) for _ in range(ns - 1)]
+            main = torch.cuda.current_stream(src.device)
             for k in range(1, ns):
                 st = self._sides[k - 1]
                 st.wait_stream(main)
@@ -346,62 +340,40 @@ class EncoderPlan:
             for st in self._sides[:ns - 1]:
                 main.wait_stream(st)
             return out
-        nb = lib().ipsx_trunk_workspace_bytes(C.byref(self.trunk), n)
-        ws = self._workspace(nb, images.device)
-        run(0, n, ws, nb)
+        nb = L.ipsx_trunk_workspace_bytes(tr, n)
+        run(0, n, self._workspace(nb, src.device), nb)
         return out
+
+    # ---- the entry points of old, each a source and the one call
+    def encode_indexed(self, flat, index, table=None, parts=None):
+        """flat (P, C, h, w) contiguous on the GPU (uint8: with its ``table`` (C, 256)), index (n,) int32 -> (n, D)
+        embeddings of flat[index]; ``parts``: as ``encode_source``."""
+        return self.encode_source(PatchSource(flat, table), index=index, parts=parts)
+
+    def encode_view(self, images, view, index=None, first=0, n=None, parts=None):
+        """images (B, C, H, W) float32 on the GPU + their ``hip.PatchView`` -> (n, D) embeddings of grid patches
+        ``index`` (int32, device) or ``first .. first + n - 1`` (default: every patch): the bits of ``encode`` on the same
+        patches of ``hip.patchify(images, ...)`` - the stems read the images, no patch tensor exists."""
+        return self.encode_source(PatchSource(images=images, view=view), index=index, first=first, n=n, parts=parts)
 
     def encode_plain(self, x, out=None, table=None):
-        """The image trunk on every patch of ``x`` (no dedup).  uint8 ``x`` with its ``table`` (C, 256): the same calls
-        through ``ipsx_trunk_encode_u8``, whose stems look the bytes up."""
-        x = _patches(x, table)
-        n = x.shape[0]
-        if out is None:
-            out = torch.empty((n, self.d_out), dtype=torch.float32, device=x.device)
-        if table is not None:
-            tab = _p(_patch_table(table, x.shape[1], x.device))
+        """The image trunk on every patch of ``x`` (no dedup); uint8 ``x`` with its ``table`` (C, 256)."""
+        return self.encode_source(PatchSource(x, table), out=out)
 
-            def run(xs, cnt, outs, ws, nb):
-                _ck(lib().ipsx_trunk_encode_u8(C.byref(self.trunk), _p(xs), tab, cnt, _p(outs), _p(ws), nb, _stream()),
-                    "ipsx_trunk_encode_u8")
-        else:
-            def run(xs, cnt, outs, ws, nb):
-                _ck(lib().ipsx_trunk_encode(C.byref(self.trunk), _p(xs), cnt, _p(outs), _p(ws), nb, _stream()), "ipsx_trunk_encode")
-        self.trunk.patch_dtype = 0 if table is not None else _PATCH_DTYPES[x.dtype]
-        try:
-            # Layer-by-layer trunks: the batch goes through in two halves on two streams.  The stem and the max-pool are
-            # HBM-bound (together 11-13 % of the trunk's time for 1 % of its arithmetic), the residual stages MFMA-bound:
-            # side by side, one half's stem / pool / epilogues fill what the other half's convolutions leave idle
-            # (50-px MNIST 14.25 -> 13.89 ms, traffic signs 22.75 -> 22.11 ms; three streams gain less).  Same kernels on
-            # the same patches: results are unchanged.  IPSX_LAYERED_STREAMS=1 switches it off.
-            ns = int(os.environ.get("IPSX_LAYERED_STREAMS", "2"))
-            if ns > 1 and n >= 1024 and not lib().ipsx_trunk_kernel(C.byref(self.trunk)).startswith(b"fused"):
-                cuts = [n * k // ns for k in range(ns + 1)]
-                nb = lib().ipsx_trunk_workspace_bytes(C.byref(self.trunk), max(cuts[k + 1] - cuts[k] for k in range(ns)))
-                # the library's budget (a share of the free memory) is per CALL: the ns concurrent calls split it - each
-                # chunks its part of the batch to the workspace it is given
-                budget = lib().ipsx_trunk_workspace_bytes(C.byref(self.trunk), 1 << 40)
-                nb = min(nb, max(budget // ns, lib().ipsx_trunk_workspace_bytes(C.byref(self.trunk), 1)))
-                nb -= nb % 256
-                ws = self._workspace(ns * nb, x.device)
-                if len(getattr(self, "_sides", [])) < ns - 1:
-                    self._sides = [torch.cuda.Stream(device=x.device) for _ in range(ns - 1)]
-                main = torch.cuda.current_stream(x.device)
-                for k in range(1, ns):
-                    st = self._sides[k - 1]
-                    st.wait_stream(main)
-                    with torch.cuda.stream(st):
-                        run(x[cuts[k]:cuts[k + 1]], cuts[k + 1] - cuts[k], out[cuts[k]:cuts[k + 1]], ws[k * nb:], nb)
-                run(x[:cuts[1]], cuts[1], out[:cuts[1]], ws[:nb], nb)
-                for st in self._sides[:ns - 1]:
-                    main.wait_stream(st)
-                return out
-            nb = lib().ipsx_trunk_workspace_bytes(C.byref(self.trunk), n)
-            ws = self._workspace(nb, x.device)
-            run(x, n, out, ws, nb)
-        finally:
-            self.trunk.patch_dtype = 0
-        return out
+    def view_supported(self, view):
+        """Can ``encode_view`` read the patches of this ``hip.PatchView``?  The exact fp32 trunks whose stem stages its
+        patch into LDS (1x32x32 fused, 1x50x50, 3x100x100) on a view of their patch shape (``ipsx_trunk_view_supported``)."""
+        if not self.is_image:
+            return False
+        self._refresh()
+        return bool(lib().ipsx_trunk_view_supported(C.byref(self._describe(view.patch_size)), C.byref(view.struct)))
+
+    def view_kernel_name(self, view):
+        """The kernel that reads the images for this view (None: not supported)."""
+        if not self.view_supported(view):
+            return None
+        name = lib().ipsx_trunk_kernel(C.byref(self.trunk)).decode()
+        return "fused_trunk_view_kernel" if name.startswith("fused") else name.split(" ")[0].replace("_kernel", "_view_kernel")
 
     def row_stats(self, x, out=None, index=None):
         """(mean, rstd) of every feature row of ``x`` (P, F) -> (P, 2): the LayerNorm moments the projector's GEMM applies
@@ -429,6 +401,7 @@ class EncoderPlan:
         ``torch.zeros(image_stream_ctl_words(P), int32)`` zeroed before every call, ``vq`` the folded query."""
         self._refresh()
         x = _patches(x)
+        self._describe(x.shape)
         if pos is not None and (pos.stride(-1) != 1 or pos.stride(-2) != pos.shape[-1]):
             pos = pos.contiguous()
         _ck(lib().ipsx_trunk_stream(C.byref(self.trunk), _p(x), x.shape[0], _p(emb), _p(pos), _p(vq), int(R), _p(logits),
@@ -502,7 +475,8 @@ class EncoderPlan:
             raise TypeError("a patch table goes with uint8 patches of an image encoder")
         if self.is_image and x.dtype == torch.uint8 and nonblank is not None:
             raise TypeError("blank-patch dedup reads float32 patches")
-        x = _patches(x, table) if self.is_image else self._features(x)
+        src = PatchSource(x, table) if self.is_image else None
+        x = src.patches if self.is_image else self._features(x)
         n = x.shape[0]
         if index is not None:
             if self.is_image:
@@ -517,7 +491,7 @@ class EncoderPlan:
         if n == 0:
             return out
         if self.is_image:
-            self.trunk.h, self.trunk.w = x.shape[2], x.shape[3]
+            self._describe(x.shape)                        # (the dedup entries read float32 patches)
             if x.shape[1] != self.trunk.c_in:
                 raise ValueError("patches have {} channels, encoder expects {}".format(x.shape[1], self.trunk.c_in))
             if (dedup_blank() or nonblank is not None) and \
@@ -549,7 +523,7 @@ class EncoderPlan:
                     out[blank] = uniq[keep.numel():keep.numel() + 1]
                     self.n_encoded = torch.tensor(sel.numel(), dtype=torch.int32, device=x.device)
                     return out
-            return self.encode_plain(x, out, table)
+            return self.encode_source(src, out=out)
         elif self.bf16:
             if stats is None:
                 ws = self._workspace(lib().ipsx_projector_workspace_bytes(n), x.device)

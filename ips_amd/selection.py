@@ -57,26 +57,6 @@ def _env_on(name):
     return os.environ.get(name, "1") != "0"
 
 
-class ViewedPatches:
-    """(images, view) standing where the (B, N, C, ph, pw) patch tensor stands in the schedules: the shape, type and device
-    of the tensor ``hip.patchify(images, ...)`` would make, which is never made - the encoders read ``images`` through
-    ``view`` (a ``hip.PatchView``)."""
-
-    is_cuda = True
-    dtype = torch.float32
-
-    def __init__(self, images, view):
-        self.images, self.view = images, view
-        self.shape = torch.Size((view.image_shape[0], view.per_image) + view.patch_shape)
-        self.device = images.device
-
-    def dim(self):
-        return 5
-
-    def is_contiguous(self):
-        return True
-
-
 class Selection:
     """The selection pipelines of one ``IPSNet`` (buffers and streams are kept between calls of the same shape: a buffer
     that a side stream has used cannot be recycled by the allocator until that stream's work is known to be over, and
@@ -300,8 +280,19 @@ class Selection:
             self.scan_status_host.copy_(status, non_blocking=True)
 
     # ------------------------------------------------------------------ which pipeline
+    def source(self, patches):
+        """The ``hip.PatchSource`` the parts of a call are index lists into: the one ``select`` was handed, or - image
+        patches that are device-resident and contiguous - built here, ONCE per call, with the net's table for bytes; else
+        None (feature rows, strided patches)."""
+        if not torch.is_tensor(patches):
+            return patches
+        if self.net.is_image and patches.is_cuda and patches.is_contiguous():
+            return hip.PatchSource(patches, self.net._table_for(patches))
+        return None
+
     def select(self, patches, pos_enc, order=None):
-        """(B, N, ...) patches (device, or host for lazy loading) -> mem_idx (B, M) int64 on the device.
+        """(B, N, ...) patches (device, or host for lazy loading) -> mem_idx (B, M) int64 on the device.  Image nets also
+        take a ``hip.PatchSource``: with a view, whole images whose patch tensor is never made (``select_view``).
 
         ``order`` ((B or 1, N) int64 on the device; only where ``index_supported``): select as if the patch axis had been
         permuted by it - ``patches`` is the UNSHUFFLED tensor, the encoders read row ``order[b, j]`` where they would read
@@ -314,7 +305,13 @@ class Selection:
         if order is not None:
             self._order, self._flat = order, self.flat_index(order, patches.shape[0], patches.shape[1])
             self.index_calls += 1
-        if patches.is_cuda and self.can_stream_image(patches):
+        if not torch.is_tensor(patches):
+            # the one-image stream and the native one-call route read patch tensors: a view takes the parts (every part an
+            # index list of grid patches - the fused trunk's one launch, the small-batch split, layered trunks too) or, for
+            # a short loop, one piece
+            self.view_calls += patches.is_view
+            return self.parts_with_ranges(patches, pos_enc) if self.can_overlap(patches) else self.slabs(patches, pos_enc)
+        if patches.is_cuda and patches.is_contiguous() and self.can_stream_image(patches):
             return self.image_stream(patches, pos_enc)
         if patches.is_cuda and self.can_overlap(patches):
             ca = net.transf.crs_attn
@@ -327,24 +324,9 @@ class Selection:
 
     def select_view(self, images, view, pos_enc, order=None):
         """``select`` on the patches of whole images (B, C, H, W) on the device, read through ``view`` (a ``hip.PatchView``
-        the plan supports: ``EncoderPlan.view_supported``) - no (B, N, ...) tensor exists.  The schedules are those of
-        ``select`` with (images, view) where they hold the flat patch tensor: the parts beside the loop's ranges (every part
-        an index list of grid patches - the fused trunk's one launch, the small-batch split, layered trunks too) or, for a
-        short loop, one piece.  Patch numbers are those of the tensor ``hip.patchify`` would make, so ``order``, ``pos_enc``
-        and ``mem_idx`` mean what they mean in ``select``.  The one-image stream and the native one-call route read patch
-        tensors: a single image takes the parts."""
-        net = self.net
-        net._device_patches = None
-        self._done = self._unfinished = None
-        self._order = self._flat = None
-        patches = ViewedPatches(images, view)
-        if order is not None:
-            self._order, self._flat = order, self.flat_index(order, patches.shape[0], patches.shape[1])
-            self.index_calls += 1
-        self.view_calls += 1
-        if self.can_overlap(patches):
-            return self.parts_with_ranges(patches, pos_enc)
-        return self.slabs(patches, pos_enc)
+        the plan supports: ``EncoderPlan.view_supported``).  Patch numbers are those of the tensor ``hip.patchify`` would
+        make, so ``order``, ``pos_enc`` and ``mem_idx`` mean what they mean in ``select``."""
+        return self.select(hip.PatchSource(images=images, view=view), pos_enc, order)
 
     def index_supported(self, patches):
         """Can the schedule ``select`` picks for these patches read them through a shuffle index?  Device-resident,
@@ -353,7 +335,8 @@ class Selection:
         blank-patch dedup (those shuffle by copy).  uint8 patches: where float32 patches are (the index list
         addresses bytes; the gather at the end of the call reads them through the order, then dequantises)."""
         net = self.net
-        if not (patches.is_cuda and patches.is_contiguous()) or hip.dedup_blank() or net.encoder.training:
+        # (a hip.PatchSource is device-resident and contiguous by construction)
+        if (torch.is_tensor(patches) and not (patches.is_cuda and patches.is_contiguous())) or hip.dedup_blank() or net.encoder.training:
             return False
         if not net.is_image:
             return patches.dim() == 3 and patches.dtype in (torch.float32, torch.float16, torch.bfloat16)
@@ -399,9 +382,10 @@ class Selection:
         return n_iter >= (2 * self.OVERLAP_PARTS if net.is_image else 3)
 
     def can_stream_image(self, patches):
-        """ONE image on the fused fp32 1x32x32 trunk: trunk + logits as one persistent launch beside a resident loop."""
+        """ONE image on the fused fp32 1x32x32 trunk: trunk + logits as one persistent launch beside a resident loop
+        (contiguous patches: the caller's to check)."""
         net = self.net
-        if (not net.is_image or patches.shape[0] != 1 or net.encoder.training or not patches.is_contiguous()
+        if (not net.is_image or patches.shape[0] != 1 or net.encoder.training
                 or not _env_on("IPSX_IMAGE_STREAM") or patches.shape[1] < net.M + 2 * net.I
                 or patches.dtype == torch.uint8):          # (the stream kernel reads float32: uint8 goes through the parts)
             return False
@@ -657,16 +641,16 @@ class Selection:
         """Exclusive prefix ends of the parts in entries of the joined list."""
         return [B * e for e in edges[1:]]
 
-    def one_launch_ok(self, patches, indexed, small, vq, P):
+    def one_launch_ok(self, src, fused, small, vq, P):
         """Every part of the call as ONE launch of the fused fp32 trunk (``ipsx_trunk_encode_parts``), the parts' logits and
-        iterations let go by wait kernels on the side stream: the exact fp32 trunk on float32 patches, cut by the loop's
-        chunk boundaries (not the small-batch split), where kernels of different streams have been SEEN to run side by side."""
-        return (indexed and not small and 2 <= P <= 16 and patches.dtype == torch.float32 and hip.precision() == "fp32"
-                and vq.dtype == torch.float32 and patches.shape[0] * patches.shape[1] < (1 << 31) - 16
-                and _env_on("IPSX_ONE_LAUNCH") and hip.persistent_ok(patches.device)
-                and (not isinstance(patches, ViewedPatches) or bool(self.plan().fused(patches.shape))))   # (a view's lists serve layered trunks too)
+        iterations let go by wait kernels on the side stream: the exact fp32 trunk (a view's lists serve layered trunks too)
+        on float32 patches, cut by the loop's chunk boundaries (not the small-batch split), where kernels of different
+        streams have been SEEN to run side by side."""
+        return (src is not None and fused and not small and 2 <= P <= 16 and src.dtype == torch.float32 and hip.precision() == "fp32"
+                and vq.dtype == torch.float32 and src.count < (1 << 31) - 16
+                and _env_on("IPSX_ONE_LAUNCH") and hip.persistent_ok(src.device))
 
-    def parts_one_launch(self, flat, every, edges, its, pos_enc, vq, R):
+    def parts_one_launch(self, src, every, edges, its, pos_enc, vq, R):
         """``parts_with_ranges`` without the trunk's launch boundaries: ``every`` is the parts' index lists
         joined.  The trunk launch goes to the main stream FIRST - a runtime that runs the two streams one after the other
         then finds every counter full - and for each part but the last the side stream gets a wait on the part's counter,
@@ -676,7 +660,7 @@ class Selection:
         net, plan = self.net, self.plan()
         N = edges[-1]
         B = every.numel() // N
-        M, I, dev = net.M, net.I, flat.device
+        M, I, dev = net.M, net.I, src.device
         ca = net.transf.crs_attn
         P = len(its) - 1
         hip._PERSIST_CALLS += 1                    # (the window of hip.persistent_timed_out is counted in such calls)
@@ -696,10 +680,7 @@ class Selection:
         zeroed = torch.cuda.Event()
         zeroed.record(main)
         ends = self.part_ends(B, edges)
-        if isinstance(flat, ViewedPatches):
-            emb_all = plan.encode_view(flat.images, flat.view, index=every, parts=(ends, done))
-        else:
-            emb_all = plan.encode_indexed(flat, every, parts=(ends, done))
+        emb_all = plan.encode_source(src, index=every, parts=(ends, done))
         emb_all.record_stream(side)
         starts = [0] + ends[:-1]
         net._emb_parts = parts = [emb_all[starts[k]:ends[k]].view(B, edges[k + 1] - edges[k], -1) for k in range(P)]
@@ -737,8 +718,10 @@ class Selection:
         vq, R = ca.folded_query(), ca.H * ca.n_token
         n_iter = self.n_iter(N)
         from .dist import part_iterations
-        viewed = isinstance(patches, ViewedPatches)         # (whole images: every encoder takes its parts as index lists)
-        indexed = net.is_image and patches.is_contiguous() and (viewed or plan.fused(patches.shape))
+        # parts as index lists into the call's source: the fused trunk, and - whole images - every encoder that reads a view
+        src = self.source(patches)
+        fused = src is not None and bool(plan.fused(src.shape))
+        indexed = fused or (src is not None and src.is_view)
         edges, small = None, False
         if net.is_image and B * N < self.small_batch_limit(dev) and n_iter < 100:
             edges, its = self.small_batch_split(B, N, dev)
@@ -763,10 +746,7 @@ class Selection:
             lists = self.part_lists(B, N, edges, dev)
             self._part_index = (key, lists, torch.cat(lists))                         # (and joined: the one-launch route)
         side, main = self.streams(dev)
-        if viewed:
-            flat = patches
-        else:
-            flat = patches.reshape(B * N, *patches.shape[2:]) if indexed or self._flat is not None else None
+        flat = patches.reshape(B * N, *patches.shape[2:]) if self._flat is not None and not indexed else None   # (feature rows)
         part_index = self._part_index[1] if indexed else None
         every = self._part_index[2] if indexed else None
         if self._flat is not None:
@@ -776,8 +756,8 @@ class Selection:
                 self._part_map = (key, self.part_map(B, N, edges, dev))
             every = torch.index_select(self._flat.reshape(-1), 0, self._part_map[1])
             part_index = [every[B * edges[k]:B * edges[k + 1]] for k in range(P)]
-        if self.one_launch_ok(patches, indexed, small, vq, P):
-            return self.parts_one_launch(flat, every, edges, its, pos_enc, vq, R)
+        if self.one_launch_ok(src, fused, small, vq, P):
+            return self.parts_one_launch(src, every, edges, its, pos_enc, vq, R)
         logits, mem_idx_buf, tie, scan_ws = self.buffers(
             "parts", (B, N, M, I, R, str(dev)),
             lambda: (torch.empty((B, N, R), dtype=torch.float32, device=dev),
@@ -789,10 +769,8 @@ class Selection:
         side.wait_stream(main)
         for k in range(P):
             lo, hi = edges[k], edges[k + 1]
-            if viewed:
-                emb = plan.encode_view(patches.images, patches.view, index=part_index[k]).view(B, hi - lo, -1)
-            elif indexed:
-                emb = plan.encode_indexed(flat, part_index[k], table=net._table_for(flat)).view(B, hi - lo, -1)
+            if indexed:
+                emb = plan.encode_source(src, index=part_index[k]).view(B, hi - lo, -1)
             elif self._flat is not None:           # feature rows through the shuffle index
                 emb = plan.encode(flat, index=part_index[k]).view(B, hi - lo, -1)
             else:
@@ -828,7 +806,8 @@ class Selection:
         ca = net.transf.crs_attn
         vq, R = ca.folded_query(), ca.H * ca.n_token
         logits = torch.empty((B, N, R), dtype=torch.float32, device=dev)
-        if patches.is_cuda:
+        viewed = not torch.is_tensor(patches)                    # a hip.PatchSource (select_view: whole images), one span
+        if viewed or patches.is_cuda:
             spans, fetch, prefetch = [(0, N)], lambda k: patches, lambda k: None
         else:
             spans, fetch, prefetch = self.lazy_slabs(patches)
@@ -846,9 +825,8 @@ class Selection:
         parts = []
         for k, (lo, hi) in enumerate(spans):
             part = fetch(k)
-            if isinstance(part, ViewedPatches):    # whole images, one span: every grid patch, or those the shuffle index names
-                emb = self.plan().encode_view(part.images, part.view,
-                                              index=self._flat.reshape(-1) if self._flat is not None else None).view(B, N, -1)
+            if viewed:                             # every grid patch, or those the shuffle index names
+                emb = self.plan().encode_source(part, index=self._flat.reshape(-1) if self._flat is not None else None).view(B, N, -1)
             elif self._flat is not None:           # (device-resident feature rows, one span) through the shuffle index
                 emb = self.plan().encode(part.reshape(B * N, -1), index=self._flat.view(-1)).view(B, N, -1)
             else:

@@ -171,8 +171,8 @@ def test_ips_selects_the_same_bits_on_both_routes(B, shuffle, monkeypatch):
     x = x[:B].contiguous()
     launches = []
     plan = net.selection.plan()
-    inner = plan.encode_indexed
-    monkeypatch.setattr(plan, "encode_indexed", lambda *a, **kw: (launches.append(kw.get("parts")), inner(*a, **kw))[1], raising=False)
+    inner = plan.encode_source
+    monkeypatch.setattr(plan, "encode_source", lambda *a, **kw: (launches.append(kw.get("parts")), inner(*a, **kw))[1], raising=False)
     index_calls = net.selection.index_calls
     want = call(net, x, monkeypatch, "0")
     assert len(launches) == 4 and not any(launches)
@@ -194,7 +194,7 @@ def test_default_route_is_one_trunk_launch_per_call(monkeypatch):
     assert hip.persistent_ok(DEV)
     counts = {"trunk": 0, "wait": 0}
     plan = net.selection.plan()
-    inner, inner_wait = plan.encode_indexed, hip.part_wait
+    inner, inner_wait = plan.encode_source, hip.part_wait
 
     def encode(*a, **kw):
         counts["trunk"] += 1
@@ -204,7 +204,7 @@ def test_default_route_is_one_trunk_launch_per_call(monkeypatch):
         counts["wait"] += 1
         return inner_wait(*a, **kw)
 
-    monkeypatch.setattr(plan, "encode_indexed", encode, raising=False)
+    monkeypatch.setattr(plan, "encode_source", encode, raising=False)
     monkeypatch.setattr(hip, "part_wait", wait)
     net.ips(x)
     assert counts == {"trunk": 1, "wait": 3}
