@@ -89,7 +89,9 @@ extern "C" {
  *         is complete, and the conditional logits of its recovery;
  *         ipsx_patch_view (struct), ipsx_patch_view_offset, ipsx_trunk_view_supported, ipsx_trunk_encode_view,
  *         ipsx_trunk_encode_parts_view, ipsx_gather_patches_view - the patch-grid view: the LDS-staging stems of the exact
- *         fp32 trunks read their patches straight from the (b, c, h, w) images, no (b, n, c, ph, pw) tensor exists */
+ *         fp32 trunks read their patches straight from the (b, c, h, w) images, no (b, n, c, ph, pw) tensor exists;
+ *         ipsx_trunk_encode_view_u8, ipsx_gather_patches_view_u8 - the view over whole uint8 images: the same stems stage
+ *         table[c][byte] off the image grid, neither float32 images nor a patch tensor exist */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -312,7 +314,7 @@ int ipsx_part_wait(const int32_t* done, int32_t want, int32_t* status, int32_t b
  * (the order of the reference's unfold, data/megapixel_mnist/mnist_dataset.py:44-51, image-major: the numbering of
  * ipsx_patchify's output), starts at element ((bi * c) * h + py * sh) * w + px * sw; its row pitch is w, its channel pitch
  * h * w.  A geometry is valid when every field is positive, ph <= h, pw <= w and b * ny * nx < 2^31. */
-typedef struct ipsx_patch_view {   /* float32 images (b, c, h, w), contiguous; patches numbered (bi*ny + py)*nx + px, */
+typedef struct ipsx_patch_view {   /* images (b, c, h, w), contiguous;         patches numbered (bi*ny + py)*nx + px, */
     int b, c, h, w;                /* ny = (h-ph)/sh + 1, nx = (w-pw)/sw + 1: the order of the reference's unfold       */
     int ph, pw, sh, sw;
 } ipsx_patch_view;
@@ -341,6 +343,21 @@ int ipsx_trunk_encode_parts_view(const ipsx_trunk* t, const float* images, const
  * addresses allow. */
 int ipsx_gather_patches_view(const float* images, const ipsx_patch_view* v, const int64_t* idx /* (b, m), per image */,
                              int m, float* out /* (b, m, c, ph, pw) */, void* stream);
+
+/* 3.06: the patch-grid view over uint8 images.  `images` holds the pixels of the (b, c, h, w) images as bytes, `table` (c x 256
+ * floats, device, 16-byte aligned) their float32 values per channel as for ipsx_trunk_encode_u8; ipsx_patch_view keeps its
+ * layout and its offsets are the same in bytes, an element being one byte.  emb is bit for bit ipsx_trunk_encode_view of the
+ * expanded images x[b][c][y][x] = table[c][images[b][c][y][x]]: a stem stages table[c][byte] where its float32 twin stages the
+ * float it loaded, and the padding stays 0.0f.  The same trunks as ipsx_trunk_view_supported.  `images` may lie at ANY
+ * address: the load width is picked per launch as the widest of the kernel's list at which images, w and sw are all multiples
+ * of it - fused 1x32x32 trunk 16 / 4 / 1 bytes (its pair kernel 8 / 4 / 1), 1x50x50 stem 2 / 1, 3x100x100 stem 4 / 1.
+ * ipsx_gather_patches_view_u8: ipsx_gather_patches_view out of such images, out (float32) = table[c][byte]. */
+int ipsx_trunk_encode_view_u8(const ipsx_trunk* t, const uint8_t* images, const float* table, const ipsx_patch_view* v,
+                              const int32_t* index /* NULL: patches first .. first+n-1 */, int64_t first, int64_t n,
+                              float* emb, void* workspace, size_t workspace_bytes, void* stream);
+int ipsx_gather_patches_view_u8(const uint8_t* images, const float* table, const ipsx_patch_view* v,
+                                const int64_t* idx /* (b, m), per image */, int m, float* out /* (b, m, c, ph, pw) */,
+                                void* stream);
 
 /* Same result as ipsx_trunk_encode, with exact blank-patch deduplication (all-zero patches share one
  * embedding in eval mode; ~93 % of Megapixel-MNIST patches): only the non-blank patches and one blank
@@ -619,7 +636,7 @@ size_t ipsx_topm_workspace_bytes(int b, int l, int m);
 
 /* ------------------------------------------------------------------- gather
  * Replaces the torch.gather calls of ips_net.py:245-250: dst[b][j] = src[b][idx[b][j]]
- * for rows of row_bytes bytes (multiple of 4).  src_bstride_rows = rows between
+ * for rows of row_bytes bytes (16 / 4 per lane where size and addresses allow, else by bytes).  src_bstride_rows = rows between
  * batches of src (0 = one table shared by all batches).                       */
 int ipsx_gather_rows(const void* src, const int64_t* idx, void* dst,
                      int b, int64_t n_rows, int m, int64_t row_bytes,

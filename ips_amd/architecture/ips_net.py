@@ -366,20 +366,21 @@ class IPSNet(nn.Module):
 
     @torch.no_grad()
     def ips_image(self, images, patch_size, patch_stride):
-        """``ips()`` on a batch of whole images: ``images`` (B, C, H, W) float32, on the device or on the host (copied
-        whole) -> (mem_patch (B, M, C, ph, pw), mem_pos).  Everything ``ips(hip.patchify(images, patch_size, patch_stride))``
+        """``ips()`` on a batch of whole images: ``images`` (B, C, H, W) float32 - or uint8 after ``set_patch_table``, the
+        bytes a dataset stores: everything below as for the float32 images ``patch_table[c][images]``, which are never made,
+        ``mem_patch`` float32 -, on the device or on the host (copied whole, as stored)
+        -> (mem_patch (B, M, C, ph, pw), mem_pos).  Everything ``ips(hip.patchify(images, patch_size, patch_stride))``
         returns and leaves behind (``last_mem_idx``, ``last_mem_emb``, ``last_shuffle``), bit for bit - but the stems of
         the exact fp32 trunks read their patches straight from the image grid (``hip.PatchView``): the
         (B, N, C, ph, pw) tensor, a multiple of the images when patches overlap, is never made.  Where the view is not
         supported (other stems and precisions, blank-patch dedup, a CPU device, an encoder in training mode, an overridden
-        ``do_shuffle``, non-float32 images, M >= N) the patch tensor is materialised and ``ips()`` runs as ever."""
+        ``do_shuffle``, other image types, M >= N) the patch tensor is materialised - uint8 images: as uint8 patches - and
+        ``ips()`` runs as ever, refusing what it refuses."""
         if not self.is_image or images.dim() != 4:
             raise TypeError("ips_image takes (B, C, H, W) images of an image encoder")
-        if images.dtype == torch.uint8:
-            self._table_for(images)        # (no table: the error uint8 patches raise)
-            raise TypeError("ips_image reads float32 images; uint8 storage goes with patch tensors (ips())")
+        table = self._table_for(images)    # (uint8 without a table: the error uint8 patches raise)
         view = None
-        if (hip.on_device(self.device) and images.dtype == torch.float32 and not hip.dedup_blank()
+        if (hip.on_device(self.device) and images.dtype in (torch.float32, torch.uint8) and not hip.dedup_blank()
                 and not (self.encoder.training and not self.training)       # (ips() itself puts a training NET into eval mode)
                 and not (self.shuffle and self._shuffle_overridden())):
             view = hip.PatchView(images.shape, patch_size, patch_stride)
@@ -391,7 +392,8 @@ class IPSNet(nn.Module):
             return self.ips(self._materialise(images, patch_size, patch_stride))
 
         M, device, pos_enc = self.M, self.device, self.pos_enc
-        images = view.check(images.to(device))
+        src = hip.PatchSource(images=images.to(device), view=view, table=table)
+        images = src.images
         B, N = view.image_shape[0], view.per_image
         self._emb_parts = self._mem_emb = None
         self.last_shuffle = None
@@ -405,8 +407,7 @@ class IPSNet(nn.Module):
             order = None
             if self.shuffle:
                 # the draws do_shuffle would make on the (B, N, ...) tensor; the view always selects through the index
-                like = hip.PatchSource(images=images, view=view)
-                perm = draw_shuffle(like, self.shuffle_style)
+                perm = draw_shuffle(src, self.shuffle_style)
                 if perm is not None:
                     batch = self.shuffle_style == 'batch'
                     if torch.is_tensor(pos_enc):
@@ -415,13 +416,13 @@ class IPSNet(nn.Module):
                     order = kept.to(device).contiguous()
                     # (what ips() keeps: the device copy where it would have selected through the index itself)
                     self.last_shuffle = order if (os.environ.get("IPSX_SHUFFLE", "index") != "copy"
-                                                  and self.selection.index_supported(like)) else kept
+                                                  and self.selection.index_supported(src)) else kept
             with self._plan.hold():
-                mem_idx = self.selection.select_view(images, view, pos_enc, order)
+                mem_idx = self.selection.select(src, pos_enc, order)
             sel = self.selection
             mem_idx = sel.take_unfinished(mem_idx)
             mem_patch = hip.gather_patches_view(images, view, mem_idx if order is None else
-                                                torch.gather(order.expand(B, -1), 1, mem_idx))
+                                                torch.gather(order.expand(B, -1), 1, mem_idx), table)
             mem_pos = self._take(pos_enc, mem_idx) if self.use_pos else None
             sel.after_call()
         finally:

@@ -301,6 +301,8 @@ constexpr int SP_SLAB_U8 = SP_SLAB + 256;
 
 // VIEW: a.patches holds whole images and patch p of the launch is grid patch va->index[p] (or va->first + p) of the
 // ipsx_patch_view in `va`: the same float2 units off the image's rows (row pitch w; 8-byte loads when va->wide, else dwords)
+// U8 and VIEW: whole uint8 images.  The patch kernel's dwords cross row ends, which an image does not allow: the float view's
+// 1,250 two-pixel units instead, 2 bytes each (va->wide: one 2-byte load or two single bytes), through the table copy
 template <bool U8, bool VIEW = false>
 __device__ __forceinline__ void stem_pool50_body(const StemArgs& a, const float* table, const ViewArgs* va = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -314,7 +316,30 @@ __device__ __forceinline__ void stem_pool50_body(const StemArgs& a, const float*
     for (int z = lane; z < SP_SLAB / 4; z += 64) reinterpret_cast<float4*>(S)[z] = make_float4(0.f, 0.f, 0.f, 0.f);
     if constexpr (U8) reinterpret_cast<float4*>(S + SP_SLAB)[lane] = reinterpret_cast<const float4*>(table)[lane];
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if constexpr (U8) {
+    if constexpr (U8 && VIEW) {
+        const float* tab = S + SP_SLAB;
+        const unsigned char* img = reinterpret_cast<const unsigned char*>(a.patches) +
+                                   view_base(*va, va->index ? (long long)va->index[p] : va->first + p);
+        for (int e0 = lane; e0 < 1250; e0 += 64 * 5) {
+            unsigned v[5];
+#pragma unroll
+            for (int u = 0; u < 5; ++u) {
+                const int e = e0 + 64 * u < 1250 ? e0 + 64 * u : e0, yy = e / 25;
+                const unsigned char* q = img + (long long)yy * va->v.w + 2 * (e - yy * 25);
+                if (va->wide == 2) v[u] = *reinterpret_cast<const unsigned short*>(q);
+                else v[u] = (unsigned)q[0] | ((unsigned)q[1] << 8);
+            }
+#pragma unroll
+            for (int u = 0; u < 5; ++u) {
+                const int e = e0 + 64 * u;
+                if (e < 1250) {
+                    const int yy = e / 25, xx = 2 * (e - yy * 25);
+                    S[(yy + 3) * SPW + xx + 3] = tab[v[u] & 0xFFu];
+                    S[(yy + 3) * SPW + xx + 4] = tab[(v[u] >> 8) & 0xFFu];
+                }
+            }
+        }
+    } else if constexpr (U8) {
         const float* tab = S + SP_SLAB;
         const unsigned* src = reinterpret_cast<const unsigned*>(reinterpret_cast<const unsigned char*>(a.patches) + (size_t)p * 2500);
         for (int e0 = lane; e0 < 625; e0 += 64 * 5) {
@@ -462,6 +487,7 @@ __device__ __forceinline__ void stem_pool50_body(const StemArgs& a, const float*
 __global__ __launch_bounds__(256, 2) void stem_pool50_kernel(StemArgs a) { stem_pool50_body<false>(a, nullptr); }
 __global__ __launch_bounds__(256, 2) void stem_pool50_u8_kernel(StemArgs a, const float* table) { stem_pool50_body<true>(a, table); }
 __global__ __launch_bounds__(256, 2) void stem_pool50_view_kernel(StemArgs a, ViewArgs va) { stem_pool50_body<false, true>(a, nullptr, &va); }
+__global__ __launch_bounds__(256, 2) void stem_pool50_view_u8_kernel(StemArgs a, const float* table, ViewArgs va) { stem_pool50_body<true, true>(a, table, &va); }
 
 // ------------------------------------------------------------------------------------------------ stem + max-pool, 3 x 100 px
 // The traffic-sign configuration's stem (config/traffic_config.yml: 3x100x100 patches -> 50x50x64 -> 25x25x64 pooled), same
@@ -493,6 +519,8 @@ constexpr int S3_FLOATS_U8 = S3_FLOATS + 3 * 256;
 
 // VIEW: a.patches holds whole images, patch p of the launch is grid patch va->index[p] (or va->first + p): the same float4
 // units off the image's planes (row pitch w, plane pitch h * w; 16-byte loads when va->wide, else dwords)
+// U8 and VIEW: whole uint8 images.  The patch kernel's 16-byte units cross row and plane ends: the float view's 7,500
+// four-pixel units instead, a dword each (va->wide: one dword load or four single bytes), through the channel's table copy
 template <bool U8, bool VIEW = false>
 __device__ __forceinline__ void stem_pool100x3_body(const Stem3Args& a, const float* table, const ViewArgs* va = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -505,7 +533,33 @@ __device__ __forceinline__ void stem_pool100x3_body(const Stem3Args& a, const fl
         if (threadIdx.x < 192) reinterpret_cast<float4*>(S + S3_FLOATS)[threadIdx.x] = reinterpret_cast<const float4*>(table)[threadIdx.x];
     }
     __syncthreads();
-    if constexpr (U8) {   // 3 x 100 x 100 bytes as 1,875 16-byte units; a dword (4 pixels) lies inside one image row (25 per row)
+    if constexpr (U8 && VIEW) {
+        const float* tab = S + S3_FLOATS;
+        const unsigned char* img = reinterpret_cast<const unsigned char*>(a.patches) +
+                                   view_base(*va, va->index ? (long long)va->index[p] : va->first + p);
+        const long long plane = (long long)va->v.h * va->v.w;
+        for (int e0 = threadIdx.x; e0 < 7500; e0 += 256 * 8) {
+            unsigned v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int e = e0 + 256 * u < 7500 ? e0 + 256 * u : e0, c = e / 2500, rem = e - c * 2500, yy = rem / 25;
+                unsigned w1[1];
+                view_load_u8<1>(img + c * plane + (long long)yy * va->v.w + 4 * (rem - yy * 25), va->wide, w1);
+                v[u] = w1[0];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int e = e0 + 256 * u;
+                if (e < 7500) {
+                    const int c = e / 2500, rem = e - c * 2500, yy = rem / 25, xx = 4 * (rem - yy * 25);
+                    float* d = S + c * S3PLANE + (yy + 3) * S3W + xx + 3;
+                    const float* tc = tab + 256 * c;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) d[j] = tc[(v[u] >> (8 * j)) & 0xFFu];
+                }
+            }
+        }
+    } else if constexpr (U8) {   // 3 x 100 x 100 bytes as 1,875 16-byte units; a dword (4 pixels) lies inside one image row (25 per row)
         const float* tab = S + S3_FLOATS;
         const uint4* src = reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(a.patches) + (size_t)p * 30000);
         for (int e0 = threadIdx.x; e0 < 1875; e0 += 256 * 4) {
@@ -700,6 +754,7 @@ __device__ __forceinline__ void stem_pool100x3_body(const Stem3Args& a, const fl
 __global__ __launch_bounds__(256, 1) void stem_pool100x3_kernel(Stem3Args a) { stem_pool100x3_body<false>(a, nullptr); }
 __global__ __launch_bounds__(256, 1) void stem_pool100x3_u8_kernel(Stem3Args a, const float* table) { stem_pool100x3_body<true>(a, table); }
 __global__ __launch_bounds__(256, 1) void stem_pool100x3_view_kernel(Stem3Args a, ViewArgs va) { stem_pool100x3_body<false, true>(a, nullptr, &va); }
+__global__ __launch_bounds__(256, 1) void stem_pool100x3_view_u8_kernel(Stem3Args a, const float* table, ViewArgs va) { stem_pool100x3_body<true, true>(a, table, &va); }
 
 static bool stem_pool100x3_supported(const ipsx_trunk* t) {
     const char* e = getenv("IPSX_NO_FUSED");
@@ -722,7 +777,7 @@ bool fused_stem_pool100x3_covers(const ipsx_trunk* t) { return t && stem_pool100
 
 // stem + max-pool of `n` patches of `src` (checked by the entry: patch_src_check), 3x100x100 one patch per workgroup or 1x50x50
 // four; returns 1 when it ran, 0 when the trunk is another shape.  The storage kinds differ in the kernels' last argument
-// only (nothing, the table, the view at the kernel's load width) and in the LDS the bytes' staging takes.
+// only (nothing, the table, the view with the kernel's load widths, table and view) and in the LDS the bytes' staging takes.
 int fused_stem_pool50(const ipsx_trunk* t, const PatchSrc& src, float* y, int64_t n, hipStream_t s) {
     const float* patches = static_cast<const float*>(src.base);
     if (t && stem_pool100x3_supported(t)) {                            // the traffic-sign stem
@@ -738,10 +793,14 @@ int fused_stem_pool50(const ipsx_trunk* t, const PatchSrc& src, float* y, int64_
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S3_FLOATS_U8 * sizeof(float)));
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem_pool100x3_view_kernel),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S3_FLOATS * sizeof(float)));
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem_pool100x3_view_u8_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S3_FLOATS_U8 * sizeof(float)));
             attr3 = true;
         }
         const dim3 grid((unsigned)n), block(256);
-        if (src.view) stem_pool100x3_view_kernel<<<grid, block, S3_FLOATS * sizeof(float), s>>>(a3, view_args(src, 4));
+        if (src.view && src.table)
+            stem_pool100x3_view_u8_kernel<<<grid, block, S3_FLOATS_U8 * sizeof(float), s>>>(a3, src.table, view_args(src, {4, 1}));
+        else if (src.view) stem_pool100x3_view_kernel<<<grid, block, S3_FLOATS * sizeof(float), s>>>(a3, view_args(src, {16}));
         else if (src.table) stem_pool100x3_u8_kernel<<<grid, block, S3_FLOATS_U8 * sizeof(float), s>>>(a3, src.table);
         else stem_pool100x3_kernel<<<grid, block, S3_FLOATS * sizeof(float), s>>>(a3);
         return launched("stem_pool100x3") == IPSX_OK ? 1 : -1;
@@ -752,7 +811,9 @@ int fused_stem_pool50(const ipsx_trunk* t, const PatchSrc& src, float* y, int64_
     a.patches = patches; a.y = y; a.n = n;
     a.w = t->stem.w_packed; a.al = t->stem.alpha; a.sh = t->stem.shift;
     const dim3 grid((unsigned)cdiv(n, 4)), block(256);
-    if (src.view) stem_pool50_view_kernel<<<grid, block, 4 * SP_SLAB * sizeof(float), s>>>(a, view_args(src, 2));
+    if (src.view && src.table)
+        stem_pool50_view_u8_kernel<<<grid, block, 4 * SP_SLAB_U8 * sizeof(float), s>>>(a, src.table, view_args(src, {2, 1}));
+    else if (src.view) stem_pool50_view_kernel<<<grid, block, 4 * SP_SLAB * sizeof(float), s>>>(a, view_args(src, {8}));
     else if (src.table) stem_pool50_u8_kernel<<<grid, block, 4 * SP_SLAB_U8 * sizeof(float), s>>>(a, src.table);
     else stem_pool50_kernel<<<grid, block, 4 * SP_SLAB * sizeof(float), s>>>(a);
     return launched("stem_pool50") == IPSX_OK ? 1 : -1;

@@ -531,6 +531,8 @@ __device__ __forceinline__ void view_load_32(const float* src, int w, int wide, 
 // U8: a.patches holds uint8 pixels, `table` (256 floats, device) their float32 values
 // VIEW: a.patches holds whole images and `pi` is a patch of the grid `va` describes (ipsx_patch_view): the same 16 floats per
 // lane from the image's rows (row pitch w), staged in the same order
+// U8 and VIEW: whole uint8 images - the lane's 16 bytes are half a patch row, contiguous in the image too (va->wide: 16, 4 or 1
+// bytes per load), staged by stage_u8_row16 as the uint8 patch kernel's
 template <bool STAMP, int WPB, bool U8 = false, bool VIEW = false>
 __device__ __forceinline__ void trunk_front(const FusedArgs& a, long long pi, float* S, int lane, int wave,
                                             unsigned long long* stamps, const float* table = nullptr,
@@ -539,7 +541,15 @@ __device__ __forceinline__ void trunk_front(const FusedArgs& a, long long pi, fl
 
     // ---- input patch -> slab as a zero-padded 38x38 image (coalesced 16 B global loads)
     if constexpr (U8) {
-        const uint4 q = reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(a.patches) + (size_t)pi * 1024)[lane];
+        uint4 q;
+        if constexpr (VIEW) {
+            unsigned w[4];
+            view_load_u8<4>(reinterpret_cast<const unsigned char*>(a.patches) + view_base(*va, pi) + (long long)(lane >> 1) * va->v.w +
+                            16 * (lane & 1), va->wide, w);
+            q = make_uint4(w[0], w[1], w[2], w[3]);
+        } else {
+            q = reinterpret_cast<const uint4*>(reinterpret_cast<const unsigned char*>(a.patches) + (size_t)pi * 1024)[lane];
+        }
         const float4 tv = reinterpret_cast<const float4*>(table)[lane];
         for (int z = lane; z < (PW * PW + 3) / 4; z += 64) reinterpret_cast<float4*>(S)[z] = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int z = lane; z < PS1; z += 64) S[ZP1 * PS1 + z] = 0.0f;          // zero pixel row of the 8x8 stage
@@ -1310,6 +1320,11 @@ __global__ __launch_bounds__(512, 1) void fused_trunk_view_kernel(FusedArgs a, V
     fused_trunk_body<false, false, false, true>(a, nullptr, nullptr, nullptr, &va);
 }
 
+// ... through a view of whole uint8 images (a.patches: bytes; table: 256 floats)
+__global__ __launch_bounds__(512, 1) void fused_trunk_view_u8_kernel(FusedArgs a, const float* table, ViewArgs va) {
+    fused_trunk_body<false, true, false, true>(a, nullptr, table, nullptr, &va);
+}
+
 __global__ __launch_bounds__(512, 1) void fused_trunk_parts_view_kernel(FusedArgs a, PartsArgs pa, ViewArgs va) {
     fused_trunk_body<false, false, true, true>(a, nullptr, nullptr, &pa, &va);
 }
@@ -1507,9 +1522,10 @@ static FusedArgs fused_args(const ipsx_trunk* t, const PatchSrc& src, int64_t n,
     return a;
 }
 
-// what the fused view kernels get beside FusedArgs (the list travels in FusedArgs::index, as ever); 16-byte loads
-static ViewArgs fused_view_args(const PatchSrc& src) {
-    ViewArgs va = view_args(src, 4);
+// what the fused view kernels get beside FusedArgs (the list travels in FusedArgs::index, as ever): `widest`-byte loads
+// (16; the pair kernel's 8 bytes per lane of uint8 images: 8), dwords, or - bytes only - single bytes
+static ViewArgs fused_view_args(const PatchSrc& src, int widest = 16) {
+    ViewArgs va = src.table ? view_args(src, {widest, 4, 1}) : view_args(src, {widest});
     va.index = nullptr;
     return va;
 }
@@ -1540,6 +1556,7 @@ int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb
         lds_of(reinterpret_cast<const void*>(fused_trunk_kernel<true>), FUSED_LDS);
         lds_of(reinterpret_cast<const void*>(fused_trunk_u8_kernel), FUSED_LDS);
         lds_of(reinterpret_cast<const void*>(fused_trunk_view_kernel), FUSED_LDS);
+        lds_of(reinterpret_cast<const void*>(fused_trunk_view_u8_kernel), FUSED_LDS);
         attr_set = true;
     }
     if (t->precision == 2 || t->precision == 1) {      // the trunks on the bf16 matrix pipe (fused_trunk_split.h, fused_trunk_bf16.h)
@@ -1570,13 +1587,18 @@ int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb
         if (g_pair_mode != 2 && !(rest <= round / 4 || (rest > round / 2 && rest <= 3 * round / 4))) rest = 0;
     }
     // patches 0 .. n_full through the eight-patch kernel, patches n_full .. through the pair kernel: the same source, advanced.
-    // The three storage kinds differ in the kernels' last argument only (the table, the view, nothing).
+    // The storage kinds differ in the kernels' last arguments only (the table, the view, both, nothing).
     const int64_t n_full = n - rest;
     a.n = n_full;
     const PatchSrc tail = patch_src_from(t, src, n_full);
     const FusedArgs b = fused_args(t, tail, rest, emb + (size_t)n_full * 128, true);
     const dim3 grid8((unsigned)cdiv(stamps ? n : n_full, 8)), grid2((unsigned)cdiv(rest, 2));
     const size_t lds2 = (size_t)2 * SLAB * sizeof(float);
+    if (src.table && src.view) {
+        if (n_full) fused_trunk_view_u8_kernel<<<grid8, dim3(512), FUSED_LDS, s>>>(a, src.table, fused_view_args(src));
+        if (rest) fused_trunk_pair_view_u8_kernel<<<grid2, dim3(256), lds2, s>>>(b, src.table, fused_view_args(tail, 8));
+        return launched("fused_trunk_view_u8");
+    }
     if (src.table) {
         if (n_full) fused_trunk_u8_kernel<<<grid8, dim3(512), FUSED_LDS, s>>>(a, src.table);
         if (rest) fused_trunk_pair_u8_kernel<<<grid2, dim3(256), lds2, s>>>(b, src.table);

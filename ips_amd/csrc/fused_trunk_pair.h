@@ -226,6 +226,7 @@ __device__ __forceinline__ void store_l2_pair(float* lds, const f32x16& v, int l
 // U8: a.patches holds uint8 pixels, `table` (256 floats, device) their float32 values - each wavefront of a pair keeps its
 // own copy of the table behind the padded image (U8_TAB, fused_trunk.hip) and stages its half of the patch through it
 // VIEW: a.patches holds whole images, the patch is one of the grid `va` describes - the same 8 floats per lane off its rows
+// U8 and VIEW: whole uint8 images - the lane's 8 bytes are a quarter of a patch row (va->wide: 8, 4 or 1 bytes per load)
 template <bool KEEP, bool U8 = false, bool VIEW = false>
 __device__ __forceinline__ void trunk_pair_tile(const FusedArgs& a, long long p_first, float* lds, const float* table = nullptr,
                                                 const ViewArgs* va = nullptr) {
@@ -241,16 +242,22 @@ __device__ __forceinline__ void trunk_pair_tile(const FusedArgs& a, long long p_
     // ---- input patch -> slab as a zero-padded 38x38 image, half of it per wavefront
     if constexpr (U8) {
         // 8 bytes per lane: pixels 512 nh + 8 lane .. + 7 (a quarter of an image row)
-        const uint2 q = reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned char*>(a.patches) + (size_t)pi * 1024)[64 * nh + lane];
+        const int e = (64 * nh + lane) * 8, y = e >> 5, x = e & 31;
+        unsigned w[2];
+        if constexpr (VIEW) {
+            view_load_u8<2>(reinterpret_cast<const unsigned char*>(a.patches) + view_base(*va, pi) + (long long)y * va->v.w + x,
+                            va->wide, w);
+        } else {
+            const uint2 q = reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned char*>(a.patches) + (size_t)pi * 1024)[64 * nh + lane];
+            w[0] = q.x; w[1] = q.y;
+        }
         const float4 tv = reinterpret_cast<const float4*>(table)[lane];
         float* tab = S + U8_TAB + 256 * nh;
         for (int z = lane + 64 * nh; z < (PW * PW + 3) / 4; z += 128) reinterpret_cast<float4*>(S)[z] = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int z = lane + 64 * nh; z < PS1; z += 128) S[ZP1 * PS1 + z] = 0.0f;
         reinterpret_cast<float4*>(tab)[lane] = tv;
         __syncthreads();                                                  // the padding is laid by both waves of the pair
-        const int e = (64 * nh + lane) * 8, y = e >> 5, x = e & 31;
         float* d = S + (y + 3) * PW + x + 3;
-        const unsigned w[2] = {q.x, q.y};
 #pragma unroll
         for (int k = 0; k < 2; ++k)
 #pragma unroll
@@ -385,6 +392,12 @@ __global__ __launch_bounds__(256, 2) void fused_trunk_pair_u8_kernel(FusedArgs a
 __global__ __launch_bounds__(256, 2) void fused_trunk_pair_view_kernel(FusedArgs a, ViewArgs va) {
     extern __shared__ __attribute__((aligned(16))) float lds[];          // 2 slabs
     trunk_pair_tile<false, false, true>(a, (long long)blockIdx.x * 2, lds, nullptr, &va);
+}
+
+// ... through a view of whole uint8 images (a.patches: bytes; table: 256 floats)
+__global__ __launch_bounds__(256, 2) void fused_trunk_pair_view_u8_kernel(FusedArgs a, const float* table, ViewArgs va) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];          // 2 slabs
+    trunk_pair_tile<false, true, true>(a, (long long)blockIdx.x * 2, lds, table, &va);
 }
 
 // ------------------------------------------------------------------ one image as ONE persistent launch

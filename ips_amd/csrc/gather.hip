@@ -113,7 +113,7 @@ IPSX_API int ipsx_ips_finish_indexed(const void* patches, int64_t patch_row_byte
 IPSX_API int ipsx_gather_rows(const void* src, const int64_t* idx, void* dst, int b, int64_t n_rows, int m,
                               int64_t row_bytes, int64_t src_bstride_rows, void* stream) {
     IPSX_REQUIRE(src && idx && dst && b > 0 && n_rows > 0 && m > 0, "gather_rows: bad arguments");
-    IPSX_REQUIRE(row_bytes > 0 && row_bytes % 4 == 0, "gather_rows: row of %lld bytes", (long long)row_bytes);
+    IPSX_REQUIRE(row_bytes > 0, "gather_rows: row of %lld bytes", (long long)row_bytes);
     dim3 grid((unsigned)m, (unsigned)b);
     const bool a16 = row_bytes % 16 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
                      (reinterpret_cast<uintptr_t>(dst) & 15) == 0;
@@ -121,6 +121,11 @@ IPSX_API int ipsx_gather_rows(const void* src, const int64_t* idx, void* dst, in
         gather_rows_kernel<uint4><<<grid, dim3(256), 0, as_stream(stream)>>>(
             static_cast<const uint4*>(src), reinterpret_cast<const long long*>(idx), static_cast<uint4*>(dst),
             n_rows, m, row_bytes / 16, src_bstride_rows);
+    else if (row_bytes % 4 != 0 || (reinterpret_cast<uintptr_t>(src) & 3) != 0 || (reinterpret_cast<uintptr_t>(dst) & 3) != 0)
+        // rows of any size, byte by byte: uint8 patches whose C * h * w is no multiple of 4 (3 x 37 x 45)
+        gather_rows_kernel<unsigned char><<<grid, dim3(256), 0, as_stream(stream)>>>(
+            static_cast<const unsigned char*>(src), reinterpret_cast<const long long*>(idx),
+            static_cast<unsigned char*>(dst), n_rows, m, row_bytes, src_bstride_rows);
     else
         gather_rows_kernel<uint32_t><<<grid, dim3(256), 0, as_stream(stream)>>>(
             static_cast<const uint32_t*>(src), reinterpret_cast<const long long*>(idx),

@@ -44,7 +44,8 @@ __host__ __device__ inline long long patch_view_offset(const ipsx_patch_view& v,
 }
 
 // what a view kernel gets beside its usual arguments: patch j of the launch is grid patch index[j] (index: device int32) or
-// first + j; wide: the launch's load width, picked by the host (view_args, ipsx_internal.h)
+// first + j; wide: the launch's load width in bytes, picked by the host (view_args, ipsx_internal.h) - 0 where no width of
+// the kernel's list fits (the float kernels' dword loads)
 struct ViewArgs {
     ipsx_patch_view v;
     const int* index;
@@ -57,6 +58,29 @@ __device__ __forceinline__ long long view_base(const ViewArgs& va, long long p) 
     const long long off = patch_view_offset(va.v, p);
     return off < 0 ? 0 : off;
 }
+
+#ifdef __HIPCC__
+// uint8 images: the 4 NW consecutive bytes at q (inside one image row) as NW little-endian dwords, by loads of `width` bytes
+// (launch-uniform, every load naturally aligned): ONE load of 4 NW bytes, NW dwords, or 4 NW single bytes put together -
+// the same registers whatever the width, so a kernel's staging code has one form
+template <int NW>
+__device__ __forceinline__ void view_load_u8(const unsigned char* q, int width, unsigned (&w)[NW]) {
+    if (NW == 4 && width == 16) {
+        const uint4 v = *reinterpret_cast<const uint4*>(q);
+        w[0] = v.x; w[1 % NW] = v.y; w[2 % NW] = v.z; w[3 % NW] = v.w;
+    } else if (NW == 2 && width == 8) {
+        const uint2 v = *reinterpret_cast<const uint2*>(q);
+        w[0] = v.x; w[1 % NW] = v.y;
+    } else if (width >= 4) {
+#pragma unroll
+        for (int k = 0; k < NW; ++k) w[k] = reinterpret_cast<const unsigned*>(q)[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < NW; ++k)
+            w[k] = (unsigned)q[4 * k] | ((unsigned)q[4 * k + 1] << 8) | ((unsigned)q[4 * k + 2] << 16) | ((unsigned)q[4 * k + 3] << 24);
+    }
+}
+#endif
 
 }  // namespace ipsx
 

@@ -2,6 +2,8 @@
 // PatchSrc: the ONE description of where the patches of an image-encoder launch lie.
 #pragma once
 
+#include <initializer_list>
+
 #include "ipsx_common.h"
 
 namespace ipsx {
@@ -9,7 +11,7 @@ namespace ipsx {
 // ---- where the patches of a launch lie.  Patch j of the launch is patch index[j], or first + j, of
 //   the patch tensor at `base`: float32, t->patch_dtype (fused split trunks) or - with `table` - uint8 whose values are
 //   table[channel][byte]; or
-//   the grid of `view` over the whole float32 images at `base`.
+//   the grid of `view` over the whole images at `base`: float32, or - with `table` - uint8 through the table.
 // A tensor that is read from patch k on has its base moved (`first` stays 0); only a view counts in `first`.
 struct PatchSrc {
     const void* base;
@@ -28,13 +30,20 @@ static inline PatchSrc patch_src_from(const ipsx_trunk* t, PatchSrc s, int64_t k
     return s;
 }
 
-// what a view kernel gets beside its usual arguments, made by the launcher that knows its kernel's load width: wide loads of
-// `elems` floats (4: 16 bytes, 2: 8 bytes) when every patch row starts at a multiple of that width
-static inline ViewArgs view_args(const PatchSrc& s, int elems) {
-    const ipsx_patch_view& v = *s.view;
+// the widest of `widths` (bytes per load, widest first) at which every patch row of the view starts: the images, their row
+// pitch and the patches' column stride are all multiples of it; 0 when none is.  elem: bytes per pixel (4, or 1 with a table)
+static inline int view_load_width(const void* base, const ipsx_patch_view& v, size_t elem, std::initializer_list<int> widths) {
+    for (const int wd : widths)
+        if (reinterpret_cast<uintptr_t>(base) % wd == 0 && (v.w * elem) % wd == 0 && (v.sw * elem) % wd == 0) return wd;
+    return 0;
+}
+
+// what a view kernel gets beside its usual arguments, made by the launcher that knows its kernel's load widths (bytes, widest
+// first).  float32 images: the one wide load, else 0 = dwords; uint8 images: a list that ends on 1, which always fits
+static inline ViewArgs view_args(const PatchSrc& s, std::initializer_list<int> widths) {
     ViewArgs va;
-    va.v = v; va.index = s.index; va.first = s.first;
-    va.wide = reinterpret_cast<uintptr_t>(s.base) % (elems * sizeof(float)) == 0 && v.w % elems == 0 && v.sw % elems == 0 ? 1 : 0;
+    va.v = *s.view; va.index = s.index; va.first = s.first;
+    va.wide = view_load_width(s.base, *s.view, s.table ? 1 : sizeof(float), widths);
     return va;
 }
 

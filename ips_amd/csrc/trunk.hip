@@ -111,8 +111,12 @@ int patch_src_check(const ipsx_trunk* t, const PatchSrc& src, int64_t n, bool fu
     IPSX_REQUIRE(t->patch_dtype == 0 || (fused && t->precision != 0), "%s: the stem kernels of the layer-by-layer trunk "
                  "(stem_pool50_kernel, stem_pool100x3_kernel, conv_any_kernel) read float32 patches; half-precision patch storage "
                  "exists for the fused 1x32x32 trunk at precision 1 (bf16) / 2 (fp32x3) only", what);
-    IPSX_REQUIRE(!(src.table && src.view), "%s: a patch view reads float32 images", what);
-    if (src.table) {
+    if (src.table && src.view) {
+        // whole uint8 images: the byte tier of the view kernels takes any image address (view_args), the table copy is 16-byte loads
+        IPSX_REQUIRE(t->precision == 0 && t->patch_dtype == 0, "%s: uint8 images go with the exact fp32 trunk only (precision 0, "
+                     "patch_dtype 0), got precision %d, patch_dtype %d", what, t->precision, t->patch_dtype);
+        IPSX_REQUIRE(at_multiple(src.table, 16), "%s: the table of uint8 images must lie at a 16-byte address", what);
+    } else if (src.table) {
         IPSX_REQUIRE(t->precision == 0 && t->patch_dtype == 0, "%s: uint8 patches go with the exact fp32 trunk only (precision 0, "
                      "patch_dtype 0), got precision %d, patch_dtype %d", what, t->precision, t->patch_dtype);
         // what each stem's byte loads need (the generic stem gathers byte by byte); the layered stems' codes are those
@@ -126,7 +130,7 @@ int patch_src_check(const ipsx_trunk* t, const PatchSrc& src, int64_t n, bool fu
             return fail(IPSX_EHIP, "stem_pool50: uint8 patches must lie at a 4-byte address, their table at a 16-byte address");
     }
     if (src.view) {
-        IPSX_REQUIRE(at_multiple(src.base, 4), "%s: images must lie at a 4-byte address", what);
+        IPSX_REQUIRE(src.table || at_multiple(src.base, 4), "%s: images must lie at a 4-byte address", what);
         IPSX_REQUIRE(ipsx_trunk_view_supported(t, src.view), "%s: the exact fp32 trunks whose stem stages its patch into LDS "
                      "(1x32x32 fused, 1x50x50, 3x100x100) on a valid view of their patch shape (ipsx_trunk_view_supported)", what);
         IPSX_REQUIRE(src.index || src.first + n <= view_patches(*src.view), "%s: patches %lld .. %lld of a grid of %lld", what,
@@ -162,7 +166,7 @@ IPSX_API const char* ipsx_trunk_kernel(const ipsx_trunk* t) {
     return "conv_nhwc_kernel (layer by layer)";
 }
 
-// The one path behind ipsx_trunk_encode, _u8 and _view: `n_patch` patches of `src` -> emb; only the stem's load differs
+// The one path behind ipsx_trunk_encode, _u8, _view and _view_u8: `n_patch` patches of `src` -> emb; only the stem's load differs
 static int trunk_encode(const ipsx_trunk* t, const PatchSrc& src, int64_t n_patch, float* emb, void* workspace,
                         size_t workspace_bytes, void* stream, const char* what) {
     TrunkGeom g;
@@ -326,6 +330,14 @@ IPSX_API int ipsx_trunk_encode_parts_view(const ipsx_trunk* t, const float* imag
     const PatchSrc src{images, nullptr, v, index, 0};
     IPSX_TRY(patch_src_check(t, src, n_index, true, "trunk_encode_parts_view"));
     return fused_trunk_encode_parts(t, src, n_index, emb, part_end, n_parts, done, as_stream(stream));
+}
+
+IPSX_API int ipsx_trunk_encode_view_u8(const ipsx_trunk* t, const uint8_t* images, const float* table, const ipsx_patch_view* v,
+                                       const int32_t* index, int64_t first, int64_t n, float* emb, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    IPSX_REQUIRE(t && images && table && v && emb && n >= 0 && first >= 0, "trunk_encode_view_u8: bad arguments");
+    return trunk_encode(t, PatchSrc{images, table, v, index, index ? 0 : first}, n, emb, workspace, workspace_bytes, stream,
+                        "trunk_encode_view_u8");
 }
 
 // One image: trunk AND logits of its patches as ONE persistent launch that feeds ipsx_scan_persistent patch by patch

@@ -232,6 +232,10 @@ _EXPORTS = {
     "ipsx_trunk_encode_parts_view": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.POINTER(PatchViewStruct), C.c_void_p, C.c_int64,
                                                C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p]),
     "ipsx_gather_patches_view": (C.c_int, [C.c_void_p, C.POINTER(PatchViewStruct), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "ipsx_trunk_encode_view_u8": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.POINTER(PatchViewStruct), C.c_void_p,
+                                            C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ipsx_gather_patches_view_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PatchViewStruct), C.c_void_p, C.c_int, C.c_void_p,
+                                              C.c_void_p]),
     "ipsx_trunk_dedup_workspace_bytes": (C.c_size_t, [C.POINTER(Trunk), C.c_int64]),
     "ipsx_trunk_encode_dedup": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                           C.c_size_t, C.c_void_p, C.c_void_p]),
@@ -838,9 +842,7 @@ def gather_rows(src, idx):
     src = src if src.is_contiguous() else src.contiguous()
     idx = idx if idx.is_contiguous() else idx.contiguous()
     N = src.shape[1]
-    row_bytes = src[0, 0].numel() * src.element_size()
-    if row_bytes % 4:
-        raise ValueError("row size must be a multiple of 4 bytes")
+    row_bytes = src[0, 0].numel() * src.element_size()       # (no multiple of 4: uint8 rows of an odd size, copied by bytes)
     out = torch.empty((B, M) + tuple(src.shape[2:]), dtype=src.dtype, device=src.device)
     bstride = N if src.shape[0] > 1 else 0
     _ck(lib().ipsx_gather_rows(_p(src), _p(idx), _p(out), B, N, M, row_bytes, bstride, _stream()),
@@ -950,20 +952,37 @@ class PatchView:
         b, py = divmod(r, self.ny)
         return ((b * Cc) * H + py * self.patch_stride[0]) * W + px * self.patch_stride[1]
 
-    def check(self, images):
-        """``images`` as the view kernels read them: float32, this view's shape, contiguous."""
+    def check(self, images, table=None):
+        """``images`` as the view kernels read them: float32, or uint8 with their ``table`` (C, 256) - refused where uint8
+        patches are (``_patches``) -, this view's shape, contiguous."""
+        if images.dtype == torch.uint8 or table is not None:
+            if tuple(images.shape) != self.image_shape:
+                raise ValueError("images are {}, the view was made for {}".format(tuple(images.shape), self.image_shape))
+            return _patches(images, table)
         if images.dtype != torch.float32:
-            raise TypeError("a patch view reads float32 images, got {}".format(images.dtype))
+            raise TypeError("a patch view reads float32 or uint8 images, got {}".format(images.dtype))
         if tuple(images.shape) != self.image_shape:
             raise ValueError("images are {}, the view was made for {}".format(tuple(images.shape), self.image_shape))
         return images if images.is_contiguous() else images.contiguous()
+
+    def load_bytes(self, images, widths):
+        """The launcher's rule for a view kernel's load width (``view_args``, csrc/ipsx_internal.h): the first of ``widths``
+        (bytes, widest first) of which the images' address, their row pitch and the patches' column stride in bytes are
+        all multiples; 0 when none is.  fused 1x32x32: float32 (16,), uint8 (16, 4, 1), its pair kernel (8, 4, 1); 1x50x50:
+        (8,) / (2, 1); 3x100x100: (16,) / (4, 1)."""
+        e = images.element_size()
+        for wd in widths:
+            if images.data_ptr() % wd == 0 and self.image_shape[3] * e % wd == 0 and self.patch_stride[1] * e % wd == 0:
+                return wd
+        return 0
 
 
 class PatchSource:
     """Where the patches of an image-encoder call lie - what ``EncoderPlan.encode_source`` reads.  Either a patch tensor
     ``PatchSource(patches, table=None)``: (P, C, h, w) or (B, N, C, h, w) on the GPU, float32, float16 / bfloat16 under
     IPSX_PRECISION=bf16 / fp32x3, or uint8 with its ``table`` (C, 256); or whole images read through a patch grid
-    ``PatchSource(images=..., view=...)`` (``PatchView``), whose patch tensor is never made.  Everything that
+    ``PatchSource(images=..., view=..., table=None)`` (``PatchView``, DESIGN 2.3: float32 images, or uint8 images with
+    their ``table``), whose patch tensor is never made.  Everything that
     refuses a storage kind does so here, once, before the first launch; what is kept is contiguous.  ``shape`` is that of
     the patch tensor (for a view: the one ``patchify`` would make), ``count`` its number of patches."""
 
@@ -972,9 +991,11 @@ class PatchSource:
     def __init__(self, patches=None, table=None, images=None, view=None):
         self.patches = self.table = self.images = self.view = None
         if view is not None:
-            self.images, self.view = view.check(images), view
+            self.images, self.view = view.check(images, table), view
+            if table is not None:
+                self.table = _patch_table(table, images.shape[-3], images.device)
             self.shape = torch.Size((view.image_shape[0], view.per_image) + view.patch_shape)
-            self.dtype, self.device, self.count = torch.float32, images.device, view.count
+            self.dtype, self.device, self.count = images.dtype, images.device, view.count
             return
         self.patches = patches = _patches(patches, table)
         if table is not None:
@@ -992,15 +1013,21 @@ class PatchSource:
         return self.images if self.view is not None else self.patches
 
 
-def gather_patches_view(images, view, idx):
+def gather_patches_view(images, view, idx, table=None):
     """images (B, C, H, W) float32 on the GPU, idx (B, M) int64 patch numbers inside each image (py * nx + px) ->
-    (B, M, C, ph, pw): ``patchify(images, ...)[b, idx[b, m]]`` copied straight out of the images."""
-    images = view.check(images)
+    (B, M, C, ph, pw): ``patchify(images, ...)[b, idx[b, m]]`` copied straight out of the images.  uint8 images with
+    their ``table`` (C, 256): float32 all the same, ``table[c][byte]``."""
+    images = view.check(images, table)
     if idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] != view.image_shape[0] or idx.device != images.device:
         raise ValueError("idx must be a (B, M) int64 tensor on the images' device")
     idx = idx if idx.is_contiguous() else idx.contiguous()
     M = idx.shape[1]
     out = torch.empty((idx.shape[0], M) + view.patch_shape, dtype=torch.float32, device=images.device)
+    if table is not None:
+        table = _patch_table(table, images.shape[-3], images.device)
+        _ck(lib().ipsx_gather_patches_view_u8(_p(images), _p(table), C.byref(view.struct), _p(idx), M, _p(out), _stream()),
+            "ipsx_gather_patches_view_u8")
+        return out
     _ck(lib().ipsx_gather_patches_view(_p(images), C.byref(view.struct), _p(idx), M, _p(out), _stream()),
         "ipsx_gather_patches_view")
     return out

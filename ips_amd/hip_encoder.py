@@ -255,7 +255,8 @@ class EncoderPlan:
     def encode_source(self, src, index=None, first=0, n=None, parts=None, out=None):
         """The image trunk on patches of ``src`` (a ``hip.PatchSource``) -> (n, D) embeddings: of its patches ``index``
         (int32 numbers, on the device), or ``first .. first + n - 1`` (default: all from ``first`` on).  The ONE way into the
-        ``ipsx_trunk_encode*`` family; which export runs follows from the source (float32 / half / uint8 patches, a view)
+        ``ipsx_trunk_encode*`` family; which export runs follows from the source (float32 / half / uint8 patches, a view
+        of float32 or uint8 images)
         and from how it is addressed.  An index list: the fused 1x32x32 trunk, or a view on any trunk that reads one.
         ``parts`` = (part_end, done): ``index`` is the index lists of several parts one after the other, ending at the
         list entries ``part_end`` (ints), encoded as ONE launch that counts part k's finished patches into ``done[k]``
@@ -305,9 +306,13 @@ class EncoderPlan:
             advanced, else the view's first patch, else the tensor."""
             outs = _p(out[lo:lo + cnt])
             if vs is not None:
-                _ck(L.ipsx_trunk_encode_view(tr, _p(flat), vs, _p(index[lo:]) if index is not None else None,
-                                             0 if index is not None else first + lo, cnt, outs, _p(ws), nb, _stream()),
-                    "ipsx_trunk_encode_view")
+                ix, lo1 = (_p(index[lo:]), 0) if index is not None else (None, first + lo)
+                if tab.value:                              # whole uint8 images
+                    _ck(L.ipsx_trunk_encode_view_u8(tr, _p(flat), tab, vs, ix, lo1, cnt, outs, _p(ws), nb, _stream()),
+                        "ipsx_trunk_encode_view_u8")
+                else:
+                    _ck(L.ipsx_trunk_encode_view(tr, _p(flat), vs, ix, lo1, cnt, outs, _p(ws), nb, _stream()),
+                        "ipsx_trunk_encode_view")
             elif tab.value:
                 _ck(L.ipsx_trunk_encode_u8(tr, _p(flat[first + lo:]), tab, cnt, outs, _p(ws), nb, _stream()), "ipsx_trunk_encode_u8")
             else:
@@ -350,11 +355,12 @@ class EncoderPlan:
         embeddings of flat[index]; ``parts``: as ``encode_source``."""
         return self.encode_source(PatchSource(flat, table), index=index, parts=parts)
 
-    def encode_view(self, images, view, index=None, first=0, n=None, parts=None):
+    def encode_view(self, images, view, index=None, first=0, n=None, parts=None, table=None):
         """images (B, C, H, W) float32 on the GPU + their ``hip.PatchView`` -> (n, D) embeddings of grid patches
         ``index`` (int32, device) or ``first .. first + n - 1`` (default: every patch): the bits of ``encode`` on the same
-        patches of ``hip.patchify(images, ...)`` - the stems read the images, no patch tensor exists."""
-        return self.encode_source(PatchSource(images=images, view=view), index=index, first=first, n=n, parts=parts)
+        patches of ``hip.patchify(images, ...)`` - the stems read the images, no patch tensor exists.  uint8 images with
+        their ``table`` (C, 256): the bits of the float32 images ``table[c][images]``, which do not exist either."""
+        return self.encode_source(PatchSource(images=images, view=view, table=table), index=index, first=first, n=n, parts=parts)
 
     def encode_plain(self, x, out=None, table=None):
         """The image trunk on every patch of ``x`` (no dedup); uint8 ``x`` with its ``table`` (C, 256)."""
@@ -368,12 +374,13 @@ class EncoderPlan:
         self._refresh()
         return bool(lib().ipsx_trunk_view_supported(C.byref(self._describe(view.patch_size)), C.byref(view.struct)))
 
-    def view_kernel_name(self, view):
-        """The kernel that reads the images for this view (None: not supported)."""
+    def view_kernel_name(self, view, u8=False):
+        """The kernel that reads the images for this view (None: not supported); ``u8``: uint8 images."""
         if not self.view_supported(view):
             return None
         name = lib().ipsx_trunk_kernel(C.byref(self.trunk)).decode()
-        return "fused_trunk_view_kernel" if name.startswith("fused") else name.split(" ")[0].replace("_kernel", "_view_kernel")
+        kind = "_view_u8_kernel" if u8 else "_view_kernel"
+        return "fused_trunk" + kind if name.startswith("fused") else name.split(" ")[0].replace("_kernel", kind)
 
     def row_stats(self, x, out=None, index=None):
         """(mean, rstd) of every feature row of ``x`` (P, F) -> (P, 2): the LayerNorm moments the projector's GEMM applies

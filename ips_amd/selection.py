@@ -322,11 +322,12 @@ class Selection:
             return self.parts_with_ranges(patches, pos_enc)
         return self.slabs(patches, pos_enc)
 
-    def select_view(self, images, view, pos_enc, order=None):
-        """``select`` on the patches of whole images (B, C, H, W) on the device, read through ``view`` (a ``hip.PatchView``
-        the plan supports: ``EncoderPlan.view_supported``).  Patch numbers are those of the tensor ``hip.patchify`` would
-        make, so ``order``, ``pos_enc`` and ``mem_idx`` mean what they mean in ``select``."""
-        return self.select(hip.PatchSource(images=images, view=view), pos_enc, order)
+    def select_view(self, images, view, pos_enc, order=None, table=None):
+        """``select`` on the patches of whole images (B, C, H, W) on the device - float32, or uint8 with their ``table`` -
+        read through ``view`` (a ``hip.PatchView`` the plan supports: ``EncoderPlan.view_supported``).  Patch numbers are
+        those of the tensor ``hip.patchify`` would make, so ``order``, ``pos_enc`` and ``mem_idx`` mean what they mean in
+        ``select``.  uint8 images take the schedules float32 images take but the one counted launch (``one_launch_ok``)."""
+        return self.select(hip.PatchSource(images=images, view=view, table=table), pos_enc, order)
 
     def index_supported(self, patches):
         """Can the schedule ``select`` picks for these patches read them through a shuffle index?  Device-resident,
