@@ -91,7 +91,10 @@ extern "C" {
  *         ipsx_trunk_encode_parts_view, ipsx_gather_patches_view - the patch-grid view: the LDS-staging stems of the exact
  *         fp32 trunks read their patches straight from the (b, c, h, w) images, no (b, n, c, ph, pw) tensor exists;
  *         ipsx_trunk_encode_view_u8, ipsx_gather_patches_view_u8 - the view over whole uint8 images: the same stems stage
- *         table[c][byte] off the image grid, neither float32 images nor a patch tensor exist */
+ *         table[c][byte] off the image grid, neither float32 images nor a patch tensor exist;
+ *         ipsx_scan_range_strided, ipsx_stream_commit (+ struct ipsx_stream_table) - IPS over patches fed in pieces: the
+ *         loop on logits that sit in a candidate table of fixed capacity, and the launch that carries a stream's state
+ *         (the m winners in rank order, then the not yet scored tail) forward without joining or copying the piece */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -566,6 +569,14 @@ int ipsx_scan_workgroups_per_image(int b, int m, int i, int h, int n_token);
 int ipsx_scan_range(const float* logits, int b, int64_t n, int m, int i, int h, int n_token,
                     int64_t it_begin, int64_t it_end, int64_t* mem_idx, float* mem_score,
                     int32_t* tie_flag, void* workspace, size_t workspace_bytes, void* stream);
+/* 3.06: ipsx_scan_range on logits that sit in a table of fixed capacity - image k's rows start k * logits_bstride_rows rows
+ * behind image 0's (>= n), the first n of them are the candidates.  ipsx_scan_range is this call with
+ * logits_bstride_rows = n: same kernels, same launch shapes, same results.  A stream's candidate table (IPSNet.ips_stream:
+ * the memory's m rows in rank order, then the carried rows, then the fed piece's) is scanned this way from it_begin = 0:
+ * mem_idx then holds row numbers of that table. */
+int ipsx_scan_range_strided(const float* logits, int64_t logits_bstride_rows, int b, int64_t n, int m, int i, int h,
+                            int n_token, int64_t it_begin, int64_t it_end, int64_t* mem_idx, float* mem_score,
+                            int32_t* tie_flag, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The whole loop as ONE launch that may start before any logits exist (overlap with the encoder without re-launching
  * per part): the kernel waits until *ready (device int32, written with ipsx_publish_rows on another stream after the
@@ -658,6 +669,29 @@ int ipsx_ips_finish_indexed(const void* patches, int64_t patch_row_bytes, int64_
                             const void* pos, int64_t pos_row_bytes, int64_t pos_bstride_rows, const int64_t* mem_idx,
                             const int64_t* order, int64_t order_bstride, int b, int m, void* mem_patch, void* mem_pos,
                             int64_t* mem_idx_out, const int32_t* status, int32_t* status_host, void* stream);
+
+/* 3.06: the state update of a stream (IPSNet.ips_stream) as ONE launch, for up to four tables at once (patch rows,
+ * embeddings, logits, global ids).  The n_cand candidates of a table are two segments that are never joined: its first
+ * held_rows rows lie in `held` ((b, held_bstride_rows, row_bytes)), the rest in `piece` - the caller's tensor, which may be
+ * a slice: image k's rows start piece_bstride_bytes * k bytes behind `piece` (0: one piece shared by every image).
+ *   sel != NULL ((b, m) candidate rows, e.g. what ipsx_scan_range_strided left in mem_idx; clamped into the candidates):
+ *       dst[k][j] = cand[k][sel[k][j]] for j < m, dst[k][m + r] = cand[k][tail_first + r] for the n_cand - tail_first
+ *       candidates no iteration has consumed; dst is another buffer than held.
+ *   sel == NULL (the memory is unchanged - a feed that completes no chunk): dst[k][held_rows + r] = piece[k][r], the rows
+ *       in front of them are not touched (dst is normally the buffer `held` points into; tail_first is ignored).
+ * Rows are copied 16 / 4 / 1 bytes per lane, chosen per table from row size, addresses and the piece's batch stride.
+ * dst_rows: rows per image dst has room for - a call that would write more is refused. */
+typedef struct ipsx_stream_table {
+    const void* held;
+    int64_t held_rows, held_bstride_rows;
+    const void* piece;
+    int64_t piece_bstride_bytes;
+    void* dst;
+    int64_t dst_rows, dst_bstride_rows;
+    int64_t row_bytes;
+} ipsx_stream_table;
+int ipsx_stream_commit(const ipsx_stream_table* tables, int n_tables, const int64_t* sel, int b, int m, int64_t n_cand,
+                       int64_t tail_first, void* stream);
 
 /* ONE IPSNet.ips call whose selection loop is resident (architecture/ips_net.py:169-262 for one image on the fused trunk,
  * or for feature slides through the projector), enqueued by ONE library call: fill of the control words, the loop on

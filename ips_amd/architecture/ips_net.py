@@ -432,6 +432,15 @@ class IPSNet(nn.Module):
         self.last_mem_idx = mem_idx
         return mem_patch, mem_pos
 
+    def ips_stream(self):
+        """``ips()`` over patches that arrive in pieces -> ``ips_amd.stream.IPSStream``: ``feed(piece)`` takes
+        (B, n, C, h, w) | (B, n, F) pieces of any length, on the device or the host, ``finish()`` returns what
+        ``ips(torch.cat(pieces, 1))`` returns with ``shuffle`` off, bit for bit, and sets ``last_mem_idx`` /
+        ``last_mem_emb``.  The state is M + I - 1 rows per image whatever N turns out to be.  The stream
+        never shuffles (the permutation needs N): feed in random order for randomised ties."""
+        from ..stream import IPSStream
+        return IPSStream(self)
+
     def _chunks(self, N):
         """[0, M) then ceil((N-M)/I) chunks of I (last one ragged) - reference :206,217-221."""
         yield 0, self.M

@@ -99,7 +99,7 @@ __device__ __forceinline__ void search_run_u32_x2(const uint32_t* runA, uint32_t
     cB = (int)(loB + key_gt(lastB, mB));
 }
 
-template <bool STAMP, bool PERSIST>
+template <bool STAMP, bool PERSIST, bool STRIDED = false>      // (STRIDED: see scan_fast_kernel)
 __global__ __launch_bounds__(cam::NT) void scan_cam_kernel(ScanArgs a, unsigned long long* stamps) {
     using namespace cam;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(cam::NT) void scan_cam_kernel(ScanArgs a, unsigned 
     // after the other - the producer works through the slides in that order, and a loop is faster than its slide's
     // projector, so two resident loops follow 16 slides and the projector keeps the other 14 compute units.
     for (int b = blockIdx.x; b < a.slides; b += (int)gridDim.x) {
-    const float* lg = a.lg + (size_t)b * a.n * R;
+    const float* lg = a.lg + (size_t)b * (STRIDED ? a.lg_bs : a.n) * R;
 #pragma unroll
     for (int k = 0; k < 8; ++k) tacc[k] = 0;
     if (STAMP) tlast = __builtin_amdgcn_s_memtime();
@@ -511,7 +511,7 @@ int launch_scan_cam(const ScanCall& c) {
     void* const stream = c.stream;
     ScanArgs a;
     a.plog = persist_log();
-    a.lg = c.logits; a.n = c.n; a.m = c.m; a.i = c.i; a.h = c.h; a.T = c.n_token; a.n2 = next_pow2(c.m + c.i);
+    a.lg = c.logits; a.n = c.n; a.lg_bs = c.logits_bstride_rows; a.m = c.m; a.i = c.i; a.h = c.h; a.T = c.n_token; a.n2 = next_pow2(c.m + c.i);
     a.it0 = c.it_begin; a.it1 = c.it_end;
     a.mem_idx = reinterpret_cast<long long*>(c.mem_idx); a.mem_score = c.mem_score; a.tie = c.tie_flag;
     a.ready = c.ready; a.status = c.status; a.ready_stride = c.ready_stride;
@@ -534,6 +534,12 @@ int launch_scan_cam(const ScanCall& c) {
         scan_cam_kernel<S, P><<<dim3((unsigned)grid), dim3(cam::NT), cam::LDS_BYTES, as_stream(stream)>>>(a, st);   \
         return launched("scan");                                                                                    \
     } while (0)
+        if (!a.ready && c.logits_bstride_rows != c.n) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_cam_kernel<false, false, true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)cam::LDS_BYTES);
+            scan_cam_kernel<false, false, true><<<dim3((unsigned)grid), dim3(cam::NT), cam::LDS_BYTES, as_stream(stream)>>>(a, nullptr);
+            return launched("scan");
+        }
         if (st && a.ready) IPSX_LAUNCH_CAM(true, true);
         if (st) IPSX_LAUNCH_CAM(true, false);
         if (a.ready) IPSX_LAUNCH_CAM(false, true);

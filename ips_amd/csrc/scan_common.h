@@ -699,6 +699,7 @@ struct ScanArgs {
     int slides;            // images of the call; a launch of fewer workgroups (scan_cam_kernel) gives workgroup w the
                            // images w, w + gridDim.x, ... one after the other
     unsigned long long* plog;   // the resident loops' log (scorer.hip g_persist_log; diagnostic: ipsx_dbg_persist_log)
+    long long lg_bs;       // rows between the images' logits: read by the STRIDED instantiations only (ipsx_scan_range_strided)
 };
 
 // ipsx_scan_range_if: the recovery launch behind a persistent loop - every workgroup looks at the word the loop sets when
@@ -1046,6 +1047,7 @@ struct ScanCall {
     const int32_t* cond;
     int32_t cond_mask;
     int ready_stride, workgroups;
+    int64_t logits_bstride_rows;       // rows between the images' logits: n for every entry but ipsx_scan_range_strided
 };
 
 // Is this shape the LDS-resident loop's (scan_fast_kernel)?  Otherwise scan_large_kernel takes it (and needs a workspace).

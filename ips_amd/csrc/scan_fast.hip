@@ -9,7 +9,9 @@
 
 namespace ipsx {
 
-template <int R, int T, int EPT, int LCH, bool STAMP, bool PERSIST>
+// STRIDED: the images' logits lie a.lg_bs rows apart (ipsx_scan_range_strided) - an instantiation of its own, so that the
+// kernels every other entry launches are compiled from the code they always were
+template <int R, int T, int EPT, int LCH, bool STAMP, bool PERSIST, bool STRIDED = false>
 __global__ __launch_bounds__(SCAN_NT) void scan_fast_kernel(ScanArgs a, unsigned long long* stamps) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // prefetch registers per (prefetching) thread: 4, 5 for 32 rows x up to 512 candidates - the reference's shipped
@@ -52,7 +54,7 @@ __global__ __launch_bounds__(SCAN_NT) void scan_fast_kernel(ScanArgs a, unsigned
     float* eB = eA + (size_t)Lmax * ld;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x;
-    const float* lg = a.lg + (size_t)b * a.n * R;
+    const float* lg = a.lg + (size_t)b * (STRIDED ? a.lg_bs : a.n) * R;
     const int r = tid & (R - 1), lrow0 = tid >> log2R;
     constexpr int lstep = SCAN_NT >> log2R;
 
@@ -415,7 +417,7 @@ FastPlan scan_fast_plan(int m, int i, int h, int n_token) {
 
 static void fill_scan_args(ScanArgs& a, const ScanCall& c) {
     a.plog = persist_log();
-    a.lg = c.logits; a.n = c.n; a.m = c.m; a.i = c.i; a.h = c.h; a.T = c.n_token; a.n2 = next_pow2(c.m + c.i);
+    a.lg = c.logits; a.n = c.n; a.lg_bs = c.logits_bstride_rows; a.m = c.m; a.i = c.i; a.h = c.h; a.T = c.n_token; a.n2 = next_pow2(c.m + c.i);
     a.it0 = c.it_begin; a.it1 = c.it_end;
     a.mem_idx = reinterpret_cast<long long*>(c.mem_idx); a.mem_score = c.mem_score; a.tie = c.tie_flag;
     a.ready = c.ready; a.status = c.status; a.ready_stride = c.ready_stride;
@@ -436,12 +438,17 @@ int launch_scan_fast(const ScanCall& c, const FastPlan& fp) {
     const size_t fast = fp.lds;
     const int ept = fp.ept, lch = fp.lch;
     unsigned long long* st = g_scan_stamps;
+    const bool strided = c.logits_bstride_rows != c.n;
 #define IPSX_LAUNCH_FAST(RR, TT, E, C, S)                                                                           \
     do {                                                                                                            \
         if (a.ready) {                                                                                              \
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_fast_kernel<RR, TT, E, C, false, true>),   \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast);                       \
             scan_fast_kernel<RR, TT, E, C, false, true><<<dim3((unsigned)b), dim3(SCAN_NT), fast, as_stream(stream)>>>(a, nullptr); \
+        } else if (strided) {                                                                                       \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_fast_kernel<RR, TT, E, C, false, false, true>), \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast);                       \
+            scan_fast_kernel<RR, TT, E, C, false, false, true><<<dim3((unsigned)b), dim3(SCAN_NT), fast, as_stream(stream)>>>(a, nullptr); \
         } else {                                                                                                    \
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_fast_kernel<RR, TT, E, C, S, false>),      \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast);                       \

@@ -291,6 +291,8 @@ struct LargeArgs {
     int tie_order;
     int rstamp;            // 1: the replay's phase stamps are collected (ipsx_dbg_replay_stamps)
     int direct;            // 1: the register-resident passes for 8 heads x one token (diagnostic ipsx_dbg_scan_direct(0): off)
+    int lg_bs;             // rows between the images' logits, read by the STRIDED instantiations only (ScanArgs::lg_bs); it sits in
+                           // what was padding in front of `lg`: the struct's size and every other member's offset are unchanged
     const float* lg;       // (b, n, R)
     long long n;
     long long it0, it1;
@@ -329,7 +331,7 @@ constexpr int LARGE_U = 8;
         }                                                                          \
     } while (0)
 
-template <bool STAMP>
+template <bool STAMP, bool STRIDED = false>      // (STRIDED: see scan_fast_kernel)
 __global__ __launch_bounds__(LARGE_NT) void scan_large_kernel(LargeArgs a, unsigned long long* stamps) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int R = a.h * a.T, Lp = a.Lp, m = a.m;
@@ -339,7 +341,7 @@ __global__ __launch_bounds__(LARGE_NT) void scan_large_kernel(LargeArgs a, unsig
     const int tail = (a.n2 + (a.n2 >> 4)) * 8 + ((R + 1) & ~1) * 8;
     const int tid = threadIdx.x, b = blockIdx.x;
     constexpr int NW = LARGE_NT / 64;
-    const float* lg = a.lg + (size_t)b * a.n * R;
+    const float* lg = a.lg + (size_t)b * (STRIDED ? a.lg_bs : a.n) * R;
     long long* mem = a.mem_idx + (size_t)b * m;
     float* xT = reinterpret_cast<float*>(a.ws + (size_t)b * a.ws_per_image);
     int* lists = reinterpret_cast<int*>(xT + (size_t)R * Lp);
@@ -770,7 +772,7 @@ int launch_scan_large(const ScanCall& c) {
         la.tie_order = g_tie_order;
         la.direct = g_scan_direct ? 1 : 0;
         la.rstamp = g_replay_stamps_on ? 1 : 0;
-        la.lg = logits; la.n = n; la.it0 = it_begin; la.it1 = it_end;
+        la.lg = logits; la.n = n; la.lg_bs = (int)c.logits_bstride_rows; la.it0 = it_begin; la.it1 = it_end;
         la.m = m; la.i = i; la.h = h; la.T = n_token; la.n2 = n2; la.Lp = (Lmax + 63) & ~63;
         la.mem_idx = reinterpret_cast<long long*>(mem_idx); la.mem_score = mem_score; la.tie = tie_flag;
         la.ws = static_cast<unsigned char*>(workspace); la.ws_per_image = scan_large_ws_per_image(m, i, h, n_token);
@@ -782,6 +784,7 @@ int launch_scan_large(const ScanCall& c) {
         IPSX_REQUIRE(lds <= kLdsLimit, "scan: internal - %zu B of LDS", lds);
         // a team of workgroups per image (scan_large_team.h) - not the conditional recovery launch, which must not wait on anyone
         const int W = cond ? 1 : scan_large_team(b, m, i, h, n_token);
+        const bool strided = c.logits_bstride_rows != n && !ready && !cond;
         if (W > 1 && !(g_scan_stamps && n2 / (LARGE_NT * W) != 2)) {
             la.team_off = large_ws_base(m, i, h, n_token);
             la.team_ticks = la.wait_ticks * (ready ? 1ull : 20ull);
@@ -797,6 +800,23 @@ int launch_scan_large(const ScanCall& c) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                        \
         scan_large_team_kernel<CPT, ST><<<grid, block, lds, as_stream(stream)>>>(la, ST ? g_scan_stamps : nullptr);             \
     } while (0)
+#define IPSX_TEAM_LAUNCH_STRIDED(CPT)                                                                                          \
+    do {                                                                                                                        \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_large_team_kernel<CPT, false, true>),                      \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                        \
+        scan_large_team_kernel<CPT, false, true><<<grid, block, lds, as_stream(stream)>>>(la, nullptr);                         \
+    } while (0)
+            if (strided) {
+                switch (n2 / (LARGE_NT * W)) {
+                    case 1: IPSX_TEAM_LAUNCH_STRIDED(1); break;
+                    case 2: IPSX_TEAM_LAUNCH_STRIDED(2); break;
+                    case 4: IPSX_TEAM_LAUNCH_STRIDED(4); break;
+                    case 8: IPSX_TEAM_LAUNCH_STRIDED(8); break;
+                    default: return fail(IPSX_EINVAL, "scan: internal - team of %d workgroups for %d slots", W, n2);
+                }
+                return launched("scan");
+            }
+#undef IPSX_TEAM_LAUNCH_STRIDED
             switch (n2 / (LARGE_NT * W)) {
                 case 1: IPSX_TEAM_LAUNCH(1, false); break;
                 case 2: if (g_scan_stamps) IPSX_TEAM_LAUNCH(2, true); else IPSX_TEAM_LAUNCH(2, false); break;
@@ -805,6 +825,11 @@ int launch_scan_large(const ScanCall& c) {
                 default: return fail(IPSX_EINVAL, "scan: internal - team of %d workgroups for %d slots", W, n2);
             }
 #undef IPSX_TEAM_LAUNCH
+            return launched("scan");
+        }
+        if (strided) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_large_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            scan_large_kernel<false, true><<<dim3((unsigned)b), dim3(LARGE_NT), lds, as_stream(stream)>>>(la, nullptr);
             return launched("scan");
         }
         if (g_scan_stamps) {                                           // diagnostic build (tools/scan_stamps.py large)

@@ -305,7 +305,7 @@ __device__ __attribute__((noinline)) int team_redo(const LargeArgs& a, long long
 
 // CPT = candidates per thread: a workgroup's run is 1024 * CPT slots, the team W = n2 / (1024 * CPT) workgroups.
 // 8 heads, one token (R = 8) only - the shape scan_large_kernel's register-resident passes are written for.
-template <int CPT, bool STAMP>
+template <int CPT, bool STAMP, bool STRIDED = false>      // (STRIDED: see scan_fast_kernel)
 __global__ __launch_bounds__(LARGE_NT) void scan_large_team_kernel(LargeArgs a, unsigned long long* stamps) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int RUN = LARGE_NT * CPT;
@@ -316,7 +316,7 @@ __global__ __launch_bounds__(LARGE_NT) void scan_large_team_kernel(LargeArgs a, 
     const int tail = (a.n2 + (a.n2 >> 4)) * 8 + 8 * 8;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x / W, w = blockIdx.x - b * W;
-    const float* lg = a.lg + (size_t)b * a.n * 8;
+    const float* lg = a.lg + (size_t)b * (STRIDED ? a.lg_bs : a.n) * 8;
     long long* const mem_out = a.mem_idx + (size_t)b * m;
     unsigned char* wsb = a.ws + (size_t)b * a.ws_per_image;
     float* xT = reinterpret_cast<float*>(wsb);

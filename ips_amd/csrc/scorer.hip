@@ -74,13 +74,25 @@ static int scan_range_impl(const float* logits, int b, int64_t n, int m, int i, 
                            int64_t it_begin, int64_t it_end, int64_t* mem_idx, float* mem_score,
                            int32_t* tie_flag, const int32_t* ready, int32_t* status, void* workspace,
                            size_t workspace_bytes, void* stream, const int32_t* cond = nullptr, int32_t cond_mask = 0,
-                           int ready_stride = 0, int workgroups = 0);
+                           int ready_stride = 0, int workgroups = 0, int64_t logits_bstride_rows = -1);
 
 IPSX_API int ipsx_scan_range(const float* logits, int b, int64_t n, int m, int i, int h, int n_token,
                              int64_t it_begin, int64_t it_end, int64_t* mem_idx, float* mem_score,
                              int32_t* tie_flag, void* workspace, size_t workspace_bytes, void* stream) {
     return scan_range_impl(logits, b, n, m, i, h, n_token, it_begin, it_end, mem_idx, mem_score, tie_flag, nullptr, nullptr,
                            workspace, workspace_bytes, stream);
+}
+
+// ipsx_scan_range on logits that sit in a table of fixed capacity: image k's rows start k * logits_bstride_rows rows behind
+// image 0's, n of them are candidates (a stream's candidate table: n changes from feed to feed, the capacity does not).
+IPSX_API int ipsx_scan_range_strided(const float* logits, int64_t logits_bstride_rows, int b, int64_t n, int m, int i, int h,
+                                     int n_token, int64_t it_begin, int64_t it_end, int64_t* mem_idx, float* mem_score,
+                                     int32_t* tie_flag, void* workspace, size_t workspace_bytes, void* stream) {
+    IPSX_REQUIRE(logits_bstride_rows >= n && logits_bstride_rows < ((int64_t)1 << 31),
+                 "scan_range_strided: %lld rows between the images hold %lld candidates (fewer than 2^31)",
+                 (long long)logits_bstride_rows, (long long)n);
+    return scan_range_impl(logits, b, n, m, i, h, n_token, it_begin, it_end, mem_idx, mem_score, tie_flag, nullptr, nullptr,
+                           workspace, workspace_bytes, stream, nullptr, 0, 0, 0, logits_bstride_rows);
 }
 
 IPSX_API size_t ipsx_scan_workspace_bytes(int b, int m, int i, int h, int n_token) {
@@ -221,7 +233,7 @@ static int scan_range_impl(const float* logits, int b, int64_t n, int m, int i, 
                            int64_t it_begin, int64_t it_end, int64_t* mem_idx, float* mem_score,
                            int32_t* tie_flag, const int32_t* ready, int32_t* status, void* workspace,
                            size_t workspace_bytes, void* stream, const int32_t* cond, int32_t cond_mask, int ready_stride,
-                           int workgroups) {
+                           int workgroups, int64_t logits_bstride_rows) {
     IPSX_REQUIRE(logits && mem_idx, "scan: null pointer");
     IPSX_REQUIRE(b > 0 && m > 0 && i > 0 && h > 0 && n_token > 0, "scan: bad sizes");
     IPSX_REQUIRE(n > m, "scan: needs more patches (%lld) than memory slots (%d)", (long long)n, m);
@@ -231,7 +243,7 @@ static int scan_range_impl(const float* logits, int b, int64_t n, int m, int i, 
     if (it_begin == it_end) return IPSX_OK;
     const FastPlan fp = scan_fast_plan(m, i, h, n_token);
     ScanCall c = {logits, b, n, m, i, h, n_token, it_begin, it_end, mem_idx, mem_score, tie_flag, ready, status, workspace,
-                  workspace_bytes, stream, cond, cond_mask, ready_stride, workgroups};
+                  workspace_bytes, stream, cond, cond_mask, ready_stride, workgroups, logits_bstride_rows < 0 ? n : logits_bstride_rows};
     // every shape the LDS-resident loops do not cover - other head / token counts, candidate sets beyond the LDS (the
     // reference's shipped CAMELYON configuration: M = I = 5000): scan_large_kernel (forced generic: plain launches only)
     if (!fp.ok || (g_scan_generic && !ready && !cond)) return launch_scan_large(c);

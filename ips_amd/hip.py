@@ -164,6 +164,13 @@ class IpsCall(C.Structure):
                 ("timing_slot", C.c_int), ("stream", C.c_void_p), ("side_stream", C.c_void_p)]
 
 
+class StreamTable(C.Structure):
+    """include/ipsx.h ``ipsx_stream_table``: one table of a stream's state as ``ipsx_stream_commit`` moves it."""
+    _fields_ = [("held", C.c_void_p), ("held_rows", C.c_int64), ("held_bstride_rows", C.c_int64),
+                ("piece", C.c_void_p), ("piece_bstride_bytes", C.c_int64),
+                ("dst", C.c_void_p), ("dst_rows", C.c_int64), ("dst_bstride_rows", C.c_int64), ("row_bytes", C.c_int64)]
+
+
 class Transf(C.Structure):
     _fields_ = [("n_token", C.c_int), ("h", C.c_int), ("d", C.c_int), ("dk", C.c_int),
                 ("dv", C.c_int), ("d_inner", C.c_int)] + \
@@ -297,6 +304,10 @@ _EXPORTS = {
     "ipsx_scan_workgroups_per_image": (C.c_int, [C.c_int] * 5),
     "ipsx_scan_range": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ipsx_scan_range_strided": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
+                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ipsx_stream_commit": (C.c_int, [C.POINTER(StreamTable), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                     C.c_void_p]),
     "ipsx_scan_range_if": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "ipsx_scan_persistent_supported": (C.c_int, [C.c_int] * 4),
@@ -602,6 +613,68 @@ def scan_range(lg, M, I, H, T, it_begin, it_end, mem_idx, tie, workspace=None):
     _ck(lib().ipsx_scan_range(_p(lg), B, N, M, I, H, T, it_begin, it_end, _p(mem_idx), None, _p(tie),
                               _p(ws), ws.numel() if ws is not None else 0, _stream()), "ipsx_scan_range")
     return mem_idx
+
+
+def scan_range_strided(lg, n, M, I, H, T, it_begin, it_end, mem_idx, tie, workspace=None):
+    """``scan_range`` on the first ``n`` rows per image of a (B, cap, H*T) logits table (``ipsx_scan_range_strided``): the
+    candidate table of ``IPSNet.ips_stream``, whose capacity stays while ``n`` changes from feed to feed.  From
+    ``it_begin = 0`` the memory is rows 0 .. M-1 and ``mem_idx`` comes back as row numbers of the table."""
+    B, cap = lg.shape[:2]
+    if lg.dtype != torch.float32 or lg.dim() != 3 or lg.stride(2) != 1 or lg.stride(1) != lg.shape[2] or (B > 1 and lg.stride(0) != cap * lg.shape[2]):
+        raise ValueError("scan_range_strided needs a row-contiguous float32 (B, cap, H*T) logits table")
+    if not 0 < n <= cap:
+        raise ValueError("{} candidates in a table of {} rows".format(n, cap))
+    ws = workspace if workspace is not None else scan_workspace(B, M, I, H, T, lg.device)
+    _ck(lib().ipsx_scan_range_strided(_p(lg), cap, B, n, M, I, H, T, it_begin, it_end, _p(mem_idx), None, _p(tie),
+                                      _p(ws), ws.numel() if ws is not None else 0, _stream()), "ipsx_scan_range_strided")
+    return mem_idx
+
+
+def stream_commit(tables, sel, M, n_cand, tail_first=0):
+    """The state update of a stream, ONE launch (``ipsx_stream_commit``).  ``tables``: up to four ``(held, held_rows, piece,
+    dst)`` - ``held`` (B, cap, ...) or None, of which the first ``held_rows`` rows per image are candidates; ``piece``
+    (B or 1, n_cand - held_rows, ...) the candidates behind them (or None), read where it lies: any batch stride, rows
+    contiguous; ``dst`` (B, cap', ...) contiguous.  ``sel`` (B, M) int64 candidate rows: ``dst[b, j] = cand[b, sel[b, j]]``,
+    ``dst[b, M + r] = cand[b, tail_first + r]``.  ``sel`` None: ``dst[b, held_rows + r] = piece[b, r]`` (append; the rows in
+    front stay as they are).  Everything is checked before the launch."""
+    if tables is None:
+        _ck(lib().ipsx_stream_commit(None, 0, None, 0, M, n_cand, tail_first, None), "ipsx_stream_commit")
+    arr = (StreamTable * max(1, len(tables)))()
+    B = None
+    for k, (held, held_rows, piece, dst) in enumerate(tables[:len(arr)]):
+        row_bytes = dst[0, 0].numel() * dst.element_size()
+        if not dst.is_contiguous():
+            raise ValueError("table {}: the destination must be contiguous".format(k))
+        B = dst.shape[0] if B is None else B
+        if dst.shape[0] != B:
+            raise ValueError("table {}: {} images, the first table has {}".format(k, dst.shape[0], B))
+        t = arr[k]
+        t.dst, t.dst_rows, t.dst_bstride_rows, t.row_bytes = dst.data_ptr(), dst.shape[1], dst.shape[1], row_bytes
+        t.held_rows = held_rows
+        if held is not None:
+            if not held.is_contiguous() or held.dtype != dst.dtype or held.shape[2:] != dst.shape[2:] or held.shape[0] != B \
+                    or held.device != dst.device:
+                raise ValueError("table {}: held rows must be a contiguous (B, cap, ...) tensor of the destination's kind".format(k))
+            if held_rows > held.shape[1]:
+                raise ValueError("table {}: {} held rows in a buffer of {}".format(k, held_rows, held.shape[1]))
+            t.held, t.held_bstride_rows = held.data_ptr(), held.shape[1]
+        elif held_rows:
+            raise ValueError("table {}: {} held rows but no buffer".format(k, held_rows))
+        if piece is not None:
+            if piece.dtype != dst.dtype or piece.shape[2:] != dst.shape[2:] or piece.shape[0] not in (1, B) or piece.device != dst.device:
+                raise ValueError("table {}: the piece must be a (B or 1, n, ...) tensor of the destination's kind".format(k))
+            if piece.shape[1] != n_cand - held_rows:
+                raise ValueError("table {}: a piece of {} rows behind {} held rows, {} candidates".format(k, piece.shape[1], held_rows, n_cand))
+            if piece.shape[1] and not piece[0].is_contiguous():
+                raise ValueError("table {}: the piece's rows must be contiguous inside an image".format(k))
+            bs = piece.stride(0) if piece.shape[0] > 1 else 0
+            if bs < 0:
+                raise ValueError("table {}: negative batch stride".format(k))
+            t.piece, t.piece_bstride_bytes = piece.data_ptr(), bs * piece.element_size()
+    if sel is not None and (sel.dtype != torch.int64 or tuple(sel.shape) != (B, M) or not sel.is_contiguous()):
+        raise ValueError("sel must be a contiguous (B, M) int64 tensor")
+    st = _stream() if len(tables) and tables[0][3].is_cuda else None       # (host tensors: refused by the library's own checks)
+    _ck(lib().ipsx_stream_commit(arr, len(tables), _p(sel), B or 0, M, n_cand, tail_first, st), "ipsx_stream_commit")
 
 
 def scan_range_if(lg, M, I, H, T, it_begin, it_end, mem_idx, tie, cond, mask=1, workspace=None):
