@@ -94,7 +94,9 @@ extern "C" {
  *         table[c][byte] off the image grid, neither float32 images nor a patch tensor exist;
  *         ipsx_scan_range_strided, ipsx_stream_commit (+ struct ipsx_stream_table) - IPS over patches fed in pieces: the
  *         loop on logits that sit in a candidate table of fixed capacity, and the launch that carries a stream's state
- *         (the m winners in rank order, then the not yet scored tail) forward without joining or copying the piece */
+ *         (the m winners in rank order, then the not yet scored tail) forward without joining or copying the piece;
+ *         ipsx_stream_commit_view - that launch for a stream fed pixel-row bands of whole images: the piece of the patch
+ *         table is read out of the images through an ipsx_patch_view, no patch tensor exists */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -692,6 +694,18 @@ typedef struct ipsx_stream_table {
 } ipsx_stream_table;
 int ipsx_stream_commit(const ipsx_stream_table* tables, int n_tables, const int64_t* sel, int b, int m, int64_t n_cand,
                        int64_t tail_first, void* stream);
+/* 3.06: ipsx_stream_commit for a stream fed pixel-row bands (IPSStream.feed_rows).  tables[0] is the patch table and has no
+ * `piece` pointer: its candidates behind the held rows are patches of `images` ((b, c, h, w), contiguous, elem_size 4: float32
+ * | 1: uint8) read through `v` - candidate held_rows + r of image k is grid patch k * ny * nx + r, i.e. c * ph segments of pw
+ * elements from element ipsx_patch_view_offset(v, .) + (ch * h + y) * w on, copied raw (bytes stay bytes); its row_bytes is
+ * c * ph * pw * elem_size and at most ny * nx candidates lie behind its held rows.  tables[1 ..] keep their contiguous
+ * pieces.  Both modes as above.  The patch table is copied 16 / 4 / 1 bytes per lane, ONE width for the launch: the widest of
+ * which images, dst, held and w, sw, pw in bytes are all multiples (*unit, when given, says which); no load touches a byte
+ * outside a patch row.  Refused before the launch: what ipsx_stream_commit refuses, a view that does not fit its images or
+ * has another b, another elem_size, a destination that overlaps the images. */
+int ipsx_stream_commit_view(const ipsx_stream_table* tables, int n_tables, const void* images, const ipsx_patch_view* v,
+                            int elem_size, const int64_t* sel, int b, int m, int64_t n_cand, int64_t tail_first, int* unit,
+                            void* stream);
 
 /* ONE IPSNet.ips call whose selection loop is resident (architecture/ips_net.py:169-262 for one image on the fused trunk,
  * or for feature slides through the projector), enqueued by ONE library call: fill of the control words, the loop on

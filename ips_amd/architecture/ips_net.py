@@ -432,14 +432,20 @@ class IPSNet(nn.Module):
         self.last_mem_idx = mem_idx
         return mem_patch, mem_pos
 
-    def ips_stream(self):
+    def ips_stream(self, patch_size=None, patch_stride=None):
         """``ips()`` over patches that arrive in pieces -> ``ips_amd.stream.IPSStream``: ``feed(piece)`` takes
         (B, n, C, h, w) | (B, n, F) pieces of any length, on the device or the host, ``finish()`` returns what
         ``ips(torch.cat(pieces, 1))`` returns with ``shuffle`` off, bit for bit, and sets ``last_mem_idx`` /
         ``last_mem_emb``.  The state is M + I - 1 rows per image whatever N turns out to be.  The stream
-        never shuffles (the permutation needs N): feed in random order for randomised ties."""
+        never shuffles (the permutation needs N): feed in random order for randomised ties.
+
+        With ``patch_size`` (ph, pw) and ``patch_stride`` (sh, sw), as ``ips_image`` takes them, the stream is a ROW stream
+        (DESIGN 2.5): ``feed_rows(band)`` takes the next pixel rows (B, C, h, W) of whole images - float32, or uint8 after
+        ``set_patch_table`` -, bands of any height, and ``finish()`` returns what
+        ``ips_image(torch.cat(bands, 2), patch_size, patch_stride)`` returns, bit for bit.  The stream carries the fewer than
+        ph rows a patch row straddling two bands needs; where ``ips_image`` reads a patch view no patch tensor is made."""
         from ..stream import IPSStream
-        return IPSStream(self)
+        return IPSStream(self, patch_size, patch_stride)
 
     def _chunks(self, N):
         """[0, M) then ceil((N-M)/I) chunks of I (last one ragged) - reference :206,217-221."""

@@ -4,6 +4,11 @@
 // joined: the rows the stream holds, then the caller's piece (its own base address and batch stride - a slice of a larger
 // tensor is read where it lies).  Pure HBM-bound copy like gather.hip: one workgroup per (row, image, table), 16 / 4 / 1
 // bytes per lane as row size and addresses allow, source rows clamped into the candidates.
+//
+// stream_commit_view_kernel (IPSStream.feed_rows) is the same update when the piece of the PATCH table is no
+// tensor at all: the candidates behind the held rows are patches of a (b, c, h, w) window of whole images, read through its
+// ipsx_patch_view - c * ph segments of pw elements each, copied raw (bytes stay bytes).  The other tables of the launch keep
+// their contiguous pieces.
 
 #include "ipsx_common.h"
 
@@ -59,6 +64,63 @@ __global__ __launch_bounds__(256) void stream_commit_kernel(CommitArgs a) {
     else copy_units<unsigned char>(s, d, t.row_bytes);
 }
 
+// the patch table of a row stream: table 0's piece is (images, view) - candidate held_rows + r of image b is grid patch
+// b * per_image + r.  unit: bytes per lane of THAT segment, uniform over the launch (host: images, w, sw, pw, dst, held).
+struct CommitViewArgs {
+    CommitArgs c;
+    const unsigned char* images;
+    ipsx_patch_view v;
+    int elem, unit;                                               // bytes per pixel (4 | 1); 16, 4 or 1 bytes per lane
+    long long per_image;                                          // ny * nx
+};
+
+// one patch out of the image grid: c * ph segments of seg_units lanes; no load leaves its patch row
+template <typename V>
+__device__ __forceinline__ void copy_patch_units(const unsigned char* s, unsigned char* d, const ipsx_patch_view& v, int elem) {
+    const unsigned seg_units = (unsigned)(v.pw * elem) / (unsigned)sizeof(V), total = (unsigned)(v.c * v.ph) * seg_units;
+    const long long pitch = (long long)v.w * elem;                // bytes between two rows of an image
+    V* dv = reinterpret_cast<V*>(d);
+    for (unsigned i = threadIdx.x; i < total; i += 256) {
+        const unsigned seg = i / seg_units, u = i - seg * seg_units, ch = seg / (unsigned)v.ph, y = seg - ch * (unsigned)v.ph;
+        dv[i] = *reinterpret_cast<const V*>(s + ((long long)ch * v.h + y) * pitch + (size_t)u * sizeof(V));
+    }
+}
+
+__global__ __launch_bounds__(256) void stream_commit_view_kernel(CommitViewArgs a) {
+    const CommitTable& t = a.c.t[blockIdx.z];
+    const long long j = blockIdx.x;
+    const int b = blockIdx.y;
+    long long r, out;                                             // as stream_commit_kernel
+    if (a.c.sel) {
+        if (j < a.c.m) {
+            r = a.c.sel[(size_t)b * a.c.m + j];
+            r = r < 0 ? 0 : (r >= a.c.n_cand ? a.c.n_cand - 1 : r);
+        } else {
+            r = a.c.tail_first + (j - a.c.m);
+        }
+        out = j;
+    } else {
+        r = t.held_rows + j;
+        if (r >= a.c.n_cand) return;
+        out = r;
+    }
+    unsigned char* d = t.dst + (size_t)b * t.dst_bs + (size_t)out * t.row_bytes;
+    if (blockIdx.z == 0 && r >= t.held_rows) {                    // a patch of the window (r - held_rows < per_image: host)
+        long long off = patch_view_offset(a.v, (long long)b * a.per_image + (r - t.held_rows));
+        if (off < 0) off = 0;
+        const unsigned char* s = a.images + off * a.elem;
+        if (a.unit == 16) copy_patch_units<uint4>(s, d, a.v, a.elem);
+        else if (a.unit == 4) copy_patch_units<uint32_t>(s, d, a.v, a.elem);
+        else copy_patch_units<unsigned char>(s, d, a.v, a.elem);
+        return;
+    }
+    const unsigned char* s = r < t.held_rows ? t.held + (size_t)b * t.held_bs + (size_t)r * t.row_bytes
+                                             : t.piece + (size_t)b * t.piece_bs + (size_t)(r - t.held_rows) * t.row_bytes;
+    if (t.unit == 16) copy_units<uint4>(s, d, t.row_bytes / 16);
+    else if (t.unit == 4) copy_units<uint32_t>(s, d, t.row_bytes / 4);
+    else copy_units<unsigned char>(s, d, t.row_bytes);
+}
+
 }  // namespace ipsx
 
 using namespace ipsx;
@@ -69,6 +131,46 @@ static bool overlaps(const void* p, long long p_bytes, const void* q, long long 
 }
 
 static bool multiple_of(const void* p, long long unit) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(unit - 1)) == 0; }
+
+// one table of a commit, checked and translated for the kernels.  rows: workgroups per image of a selection (m + tail).
+// view_piece: the candidates behind the held rows are no tensor (stream_commit_view's patch table) - `piece` stays null and
+// the caller picks the lane width.
+static int commit_table(const char* what, const ipsx_stream_table& s, int k, bool sel, int b, long long n_cand, long long rows,
+                        bool view_piece, CommitTable& t) {
+    IPSX_REQUIRE(s.dst && s.row_bytes > 0, "%s: table %d has no destination or no row size", what, k);
+    IPSX_REQUIRE(s.held_rows >= 0 && s.held_rows <= n_cand, "%s: table %d holds %lld of %lld candidates", what, k,
+                 (long long)s.held_rows, (long long)n_cand);
+    IPSX_REQUIRE(!view_piece || !s.piece, "%s: table %d: its piece is the patch view (no piece pointer)", what, k);
+    IPSX_REQUIRE(view_piece || s.held_rows == n_cand || s.piece, "%s: table %d has candidates behind its held rows but no piece", what, k);
+    IPSX_REQUIRE(!sel || s.held_rows == 0 || (s.held && s.held_bstride_rows >= s.held_rows),
+                 "%s: table %d: the held rows are missing or overlap the next image's", what, k);
+    const long long written = sel ? rows : n_cand;                // rows of dst this call may touch: [0, written)
+    if (sel) {          // workgroups read candidates while others write dst: the bytes written lie apart from every byte read
+        const long long dst_span = ((long long)(b - 1) * s.dst_bstride_rows + written) * s.row_bytes;
+        IPSX_REQUIRE(s.held_rows == 0 || !overlaps(s.dst, dst_span, s.held, ((long long)(b - 1) * s.held_bstride_rows + s.held_rows) * s.row_bytes),
+                     "%s: table %d is moved in place (a selection goes to the other buffer set)", what, k);
+        IPSX_REQUIRE(view_piece || s.held_rows == n_cand ||
+                         !overlaps(s.dst, dst_span, s.piece, (long long)(b - 1) * s.piece_bstride_bytes + (n_cand - s.held_rows) * s.row_bytes),
+                     "%s: table %d: the destination overlaps the piece", what, k);
+    }
+    IPSX_REQUIRE(s.dst_rows >= written && (b == 1 || s.dst_bstride_rows >= written),
+                 "%s: table %d: %lld rows do not fit the destination (%lld rows, %lld between the images)", what, k, written,
+                 (long long)s.dst_rows, (long long)s.dst_bstride_rows);
+    IPSX_REQUIRE(s.piece_bstride_bytes >= 0, "%s: table %d: negative batch stride of the piece", what, k);
+    t.held = static_cast<const unsigned char*>(s.held); t.held_rows = s.held_rows; t.held_bs = s.held_bstride_rows * s.row_bytes;
+    t.piece = static_cast<const unsigned char*>(s.piece); t.piece_bs = s.piece_bstride_bytes;
+    t.dst = static_cast<unsigned char*>(s.dst); t.dst_bs = s.dst_bstride_rows * s.row_bytes;
+    t.row_bytes = s.row_bytes;
+    t.unit = 1;
+    if (view_piece) return IPSX_OK;
+    for (long long u : {16ll, 4ll})
+        if (s.row_bytes % u == 0 && multiple_of(s.dst, u) && (!s.held || multiple_of(s.held, u)) &&
+            (!s.piece || (multiple_of(s.piece, u) && s.piece_bstride_bytes % u == 0))) {
+            t.unit = (int)u;
+            break;
+        }
+    return IPSX_OK;
+}
 
 IPSX_API int ipsx_stream_commit(const ipsx_stream_table* tables, int n_tables, const int64_t* sel, int b, int m, int64_t n_cand,
                                 int64_t tail_first, void* stream) {
@@ -82,43 +184,64 @@ IPSX_API int ipsx_stream_commit(const ipsx_stream_table* tables, int n_tables, c
     a.sel = reinterpret_cast<const long long*>(sel); a.m = m; a.n_cand = n_cand; a.tail_first = tail_first;
     long long rows = sel ? m + (n_cand - tail_first) : 0;         // workgroups per image and table
     for (int k = 0; k < n_tables; ++k) {
-        const ipsx_stream_table& s = tables[k];
-        IPSX_REQUIRE(s.dst && s.row_bytes > 0, "stream_commit: table %d has no destination or no row size", k);
-        IPSX_REQUIRE(s.held_rows >= 0 && s.held_rows <= n_cand, "stream_commit: table %d holds %lld of %lld candidates", k,
-                     (long long)s.held_rows, (long long)n_cand);
-        IPSX_REQUIRE(s.held_rows == n_cand || s.piece, "stream_commit: table %d has candidates behind its held rows but no piece", k);
-        IPSX_REQUIRE(!sel || s.held_rows == 0 || (s.held && s.held_bstride_rows >= s.held_rows),
-                     "stream_commit: table %d: the held rows are missing or overlap the next image's", k);
-        const long long written = sel ? rows : n_cand;            // rows of dst this call may touch: [0, written)
-        if (sel) {      // workgroups read candidates while others write dst: the bytes written lie apart from every byte read
-            const long long dst_span = ((long long)(b - 1) * s.dst_bstride_rows + written) * s.row_bytes;
-            IPSX_REQUIRE(s.held_rows == 0 || !overlaps(s.dst, dst_span, s.held, ((long long)(b - 1) * s.held_bstride_rows + s.held_rows) * s.row_bytes),
-                         "stream_commit: table %d is moved in place (a selection goes to the other buffer set)", k);
-            IPSX_REQUIRE(s.held_rows == n_cand || !overlaps(s.dst, dst_span, s.piece, (long long)(b - 1) * s.piece_bstride_bytes +
-                                                                                       (n_cand - s.held_rows) * s.row_bytes),
-                         "stream_commit: table %d: the destination overlaps the piece", k);
-        }
-        IPSX_REQUIRE(s.dst_rows >= written && (b == 1 || s.dst_bstride_rows >= written),
-                     "stream_commit: table %d: %lld rows do not fit the destination (%lld rows, %lld between the images)", k, written,
-                     (long long)s.dst_rows, (long long)s.dst_bstride_rows);
-        IPSX_REQUIRE(s.piece_bstride_bytes >= 0, "stream_commit: table %d: negative batch stride of the piece", k);
-        CommitTable& t = a.t[k];
-        t.held = static_cast<const unsigned char*>(s.held); t.held_rows = s.held_rows; t.held_bs = s.held_bstride_rows * s.row_bytes;
-        t.piece = static_cast<const unsigned char*>(s.piece); t.piece_bs = s.piece_bstride_bytes;
-        t.dst = static_cast<unsigned char*>(s.dst); t.dst_bs = s.dst_bstride_rows * s.row_bytes;
-        t.row_bytes = s.row_bytes;
-        t.unit = 1;
-        for (long long u : {16ll, 4ll})
-            if (s.row_bytes % u == 0 && multiple_of(s.dst, u) && (!s.held || multiple_of(s.held, u)) &&
-                (!s.piece || (multiple_of(s.piece, u) && s.piece_bstride_bytes % u == 0))) {
-                t.unit = (int)u;
-                break;
-            }
-        if (!sel) rows = std::max<long long>(rows, n_cand - s.held_rows);
+        IPSX_TRY(commit_table("stream_commit", tables[k], k, sel != nullptr, b, n_cand, rows, false, a.t[k]));
+        if (!sel) rows = std::max<long long>(rows, n_cand - tables[k].held_rows);
     }
     for (int k = n_tables; k < COMMIT_MAX_TABLES; ++k) a.t[k] = a.t[0];
     if (rows <= 0) return IPSX_OK;                                // nothing to append
     IPSX_REQUIRE(rows < ((int64_t)1 << 31) && b < 65536, "stream_commit: %lld rows x %d images in one launch", rows, b);
     stream_commit_kernel<<<dim3((unsigned)rows, (unsigned)b, (unsigned)n_tables), dim3(256), 0, as_stream(stream)>>>(a);
     return launched("stream_commit");
+}
+
+IPSX_API int ipsx_stream_commit_view(const ipsx_stream_table* tables, int n_tables, const void* images, const ipsx_patch_view* v,
+                                     int elem_size, const int64_t* sel, int b, int m, int64_t n_cand, int64_t tail_first,
+                                     int* unit, void* stream) {
+    const char* what = "stream_commit_view";
+    IPSX_REQUIRE(tables, "%s: null tables", what);
+    IPSX_REQUIRE(images && v, "%s: null images or view", what);
+    IPSX_REQUIRE(elem_size == 4 || elem_size == 1, "%s: an element of %d bytes (float32: 4, uint8: 1)", what, elem_size);
+    IPSX_REQUIRE(n_tables > 0 && n_tables <= COMMIT_MAX_TABLES, "%s: %d tables (1 .. %d in one launch)", what, n_tables, COMMIT_MAX_TABLES);
+    IPSX_REQUIRE(b > 0 && m > 0 && n_cand > 0, "%s: bad sizes (b = %d, m = %d, %lld candidates)", what, b, m, (long long)n_cand);
+    IPSX_REQUIRE(!sel || (tail_first >= 0 && tail_first <= n_cand), "%s: the tail starts at candidate %lld of %lld", what,
+                 (long long)tail_first, (long long)n_cand);
+    IPSX_REQUIRE(patch_view_offset(*v, 0) >= 0, "%s: the view does not fit its images (%dx%dx%dx%d, patch %dx%d, stride %dx%d)", what,
+                 v->b, v->c, v->h, v->w, v->ph, v->pw, v->sh, v->sw);
+    IPSX_REQUIRE(v->b == b, "%s: a view of %d images in a call of %d", what, v->b, b);
+    CommitViewArgs a;
+    a.c.sel = reinterpret_cast<const long long*>(sel); a.c.m = m; a.c.n_cand = n_cand; a.c.tail_first = tail_first;
+    a.images = static_cast<const unsigned char*>(images); a.v = *v; a.elem = elem_size;
+    a.per_image = (long long)((v->h - v->ph) / v->sh + 1) * ((v->w - v->pw) / v->sw + 1);
+    long long rows = sel ? m + (n_cand - tail_first) : 0;
+    for (int k = 0; k < n_tables; ++k) {
+        const ipsx_stream_table& s = tables[k];
+        IPSX_TRY(commit_table(what, s, k, sel != nullptr, b, n_cand, rows, k == 0, a.c.t[k]));
+        if (!sel) rows = std::max<long long>(rows, n_cand - s.held_rows);
+        if (k) continue;
+        // table 0: the patch table.  Its rows are whole patches of the view, its piece at most the view's patches per image,
+        // and nothing it writes lies inside the images (in EITHER mode: the images are read while dst is written)
+        const long long eb = elem_size, seg = (long long)v->pw * eb;
+        IPSX_REQUIRE(s.row_bytes == (long long)v->c * v->ph * seg, "%s: rows of %lld bytes, a %dx%dx%d patch of %d-byte elements has %lld",
+                     what, (long long)s.row_bytes, v->c, v->ph, v->pw, elem_size, (long long)v->c * v->ph * seg);
+        IPSX_REQUIRE(n_cand - s.held_rows <= a.per_image, "%s: %lld candidates behind the held rows, the view has %lld patches per image", what,
+                     (long long)(n_cand - s.held_rows), a.per_image);
+        const long long written = sel ? rows : n_cand;
+        IPSX_REQUIRE(!overlaps(s.dst, ((long long)(b - 1) * s.dst_bstride_rows + written) * s.row_bytes, images,
+                               (long long)v->b * v->c * v->h * v->w * eb),
+                     "%s: the destination overlaps the images", what);
+        a.unit = 1;
+        for (long long u : {16ll, 4ll})
+            if (seg % u == 0 && ((long long)v->w * eb) % u == 0 && ((long long)v->sw * eb) % u == 0 && multiple_of(images, u) &&
+                multiple_of(s.dst, u) && (!s.held || multiple_of(s.held, u))) {
+                a.unit = (int)u;
+                break;
+            }
+        a.c.t[0].unit = a.unit;                                   // (row_bytes is a multiple of seg: the held rows go the same width)
+    }
+    for (int k = n_tables; k < COMMIT_MAX_TABLES; ++k) a.c.t[k] = a.c.t[0];
+    if (unit) *unit = a.unit;
+    if (rows <= 0) return IPSX_OK;
+    IPSX_REQUIRE(rows < ((int64_t)1 << 31) && b < 65536, "%s: %lld rows x %d images in one launch", what, rows, b);
+    stream_commit_view_kernel<<<dim3((unsigned)rows, (unsigned)b, (unsigned)n_tables), dim3(256), 0, as_stream(stream)>>>(a);
+    return launched(what);
 }

@@ -308,6 +308,8 @@ _EXPORTS = {
                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ipsx_stream_commit": (C.c_int, [C.POINTER(StreamTable), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                      C.c_void_p]),
+    "ipsx_stream_commit_view": (C.c_int, [C.POINTER(StreamTable), C.c_int, C.c_void_p, C.POINTER(PatchViewStruct), C.c_int,
+                                          C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int), C.c_void_p]),
     "ipsx_scan_range_if": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "ipsx_scan_persistent_supported": (C.c_int, [C.c_int] * 4),
@@ -630,15 +632,9 @@ def scan_range_strided(lg, n, M, I, H, T, it_begin, it_end, mem_idx, tie, worksp
     return mem_idx
 
 
-def stream_commit(tables, sel, M, n_cand, tail_first=0):
-    """The state update of a stream, ONE launch (``ipsx_stream_commit``).  ``tables``: up to four ``(held, held_rows, piece,
-    dst)`` - ``held`` (B, cap, ...) or None, of which the first ``held_rows`` rows per image are candidates; ``piece``
-    (B or 1, n_cand - held_rows, ...) the candidates behind them (or None), read where it lies: any batch stride, rows
-    contiguous; ``dst`` (B, cap', ...) contiguous.  ``sel`` (B, M) int64 candidate rows: ``dst[b, j] = cand[b, sel[b, j]]``,
-    ``dst[b, M + r] = cand[b, tail_first + r]``.  ``sel`` None: ``dst[b, held_rows + r] = piece[b, r]`` (append; the rows in
-    front stay as they are).  Everything is checked before the launch."""
-    if tables is None:
-        _ck(lib().ipsx_stream_commit(None, 0, None, 0, M, n_cand, tail_first, None), "ipsx_stream_commit")
+def _stream_tables(tables, n_cand):
+    """``(held, held_rows, piece, dst)`` tuples -> (the ``ipsx_stream_table`` array, B); the checks a tensor allows before
+    the library's own."""
     arr = (StreamTable * max(1, len(tables)))()
     B = None
     for k, (held, held_rows, piece, dst) in enumerate(tables[:len(arr)]):
@@ -671,10 +667,54 @@ def stream_commit(tables, sel, M, n_cand, tail_first=0):
             if bs < 0:
                 raise ValueError("table {}: negative batch stride".format(k))
             t.piece, t.piece_bstride_bytes = piece.data_ptr(), bs * piece.element_size()
+    return arr, B
+
+
+def stream_commit(tables, sel, M, n_cand, tail_first=0):
+    """The state update of a stream, ONE launch (``ipsx_stream_commit``).  ``tables``: up to four ``(held, held_rows, piece,
+    dst)`` - ``held`` (B, cap, ...) or None, of which the first ``held_rows`` rows per image are candidates; ``piece``
+    (B or 1, n_cand - held_rows, ...) the candidates behind them (or None), read where it lies: any batch stride, rows
+    contiguous; ``dst`` (B, cap', ...) contiguous.  ``sel`` (B, M) int64 candidate rows: ``dst[b, j] = cand[b, sel[b, j]]``,
+    ``dst[b, M + r] = cand[b, tail_first + r]``.  ``sel`` None: ``dst[b, held_rows + r] = piece[b, r]`` (append; the rows in
+    front stay as they are).  Everything is checked before the launch."""
+    if tables is None:
+        _ck(lib().ipsx_stream_commit(None, 0, None, 0, M, n_cand, tail_first, None), "ipsx_stream_commit")
+    arr, B = _stream_tables(tables, n_cand)
     if sel is not None and (sel.dtype != torch.int64 or tuple(sel.shape) != (B, M) or not sel.is_contiguous()):
         raise ValueError("sel must be a contiguous (B, M) int64 tensor")
     st = _stream() if len(tables) and tables[0][3].is_cuda else None       # (host tensors: refused by the library's own checks)
     _ck(lib().ipsx_stream_commit(arr, len(tables), _p(sel), B or 0, M, n_cand, tail_first, st), "ipsx_stream_commit")
+
+
+def stream_commit_view(tables, images, view, sel, M, n_cand, tail_first=0):
+    """``stream_commit`` for a stream fed pixel-row bands, ONE launch (``ipsx_stream_commit_view``).
+    ``tables[0]`` is the patch table ``(held, held_rows, None, dst)`` with rows (C, ph, pw) of the images' dtype: its
+    candidates behind the held rows are the first ``n_cand - held_rows`` patches per image of ``images`` (B, C, H, W)
+    float32 | uint8 on the GPU, read through ``view`` (a ``PatchView``) where they lie - bytes are copied as bytes.  The other
+    tables are those of ``stream_commit``.  -> the bytes per lane the patch table was copied with (16, 4 or 1)."""
+    if tables is None:
+        _ck(lib().ipsx_stream_commit_view(None, 0, _p(images), C.byref(view.struct), images.element_size(), None, 0, M, n_cand,
+                                          tail_first, None, None), "ipsx_stream_commit_view")
+    if images.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("a patch view reads float32 or uint8 images, got {}".format(images.dtype))
+    if tuple(images.shape) != view.image_shape or not images.is_contiguous():
+        raise ValueError("images are {}{}, the view was made for {}".format(tuple(images.shape), "" if images.is_contiguous() else
+                                                                            " (not contiguous)", view.image_shape))
+    if len(tables):
+        held, held_rows, piece, dst = tables[0]
+        if piece is not None:
+            raise ValueError("table 0 is the patch table: its piece is the view (pass None)")
+        if dst.dtype != images.dtype or tuple(dst.shape[2:]) != view.patch_shape or dst.device != images.device:
+            raise ValueError("table 0: rows of {} {}, the view's patches are {} {}".format(
+                dst.dtype, tuple(dst.shape[2:]), images.dtype, view.patch_shape))
+    arr, B = _stream_tables(tables, n_cand)
+    if sel is not None and (sel.dtype != torch.int64 or tuple(sel.shape) != (B, M) or not sel.is_contiguous()):
+        raise ValueError("sel must be a contiguous (B, M) int64 tensor")
+    unit = C.c_int(0)
+    st = _stream() if images.is_cuda else None               # (host tensors: refused by the library's own checks)
+    _ck(lib().ipsx_stream_commit_view(arr, len(tables), _p(images), C.byref(view.struct), images.element_size(), _p(sel), B or 0,
+                                      M, n_cand, tail_first, C.byref(unit), st), "ipsx_stream_commit_view")
+    return unit.value
 
 
 def scan_range_if(lg, M, I, H, T, it_begin, it_end, mem_idx, tie, cond, mask=1, workspace=None):

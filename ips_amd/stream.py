@@ -25,6 +25,19 @@ numbers come back) and carries the state forward in one launch (``hip.stream_com
 own base address and batch stride - nothing is concatenated.  The logits table alone grows with the largest piece fed
 (H * n_token floats per row); everything else is M + I - 1 rows per image.  On a CPU device the same state machine runs
 on ATen ops, one ``score_and_select`` per iteration on the chunks ``IPSNet._select_aten`` would embed.
+
+A ROW stream (``net.ips_stream(patch_size, patch_stride)``) takes the pixel rows of whole images instead:
+
+    s = net.ips_stream(patch_size=(32, 32), patch_stride=(16, 16))
+    for band in reader:             # (B, C, h_k, W): the NEXT h_k pixel rows of every image, h_k >= 1 and arbitrary
+        s.feed_rows(band)
+    mem_patch, mem_pos = s.finish()
+
+and returns what ``net.ips_image(torch.cat(bands, 2), patch_size, patch_stride)`` returns, wherever the bands end.  The
+stream owns a window - the pixel rows from the first row of the next incomplete patch row on, fewer than ``ph`` of them
+(``BandGeometry``) - and puts every band behind it; the window's complete patch rows are the feed's piece.  Where the
+encoder reads a ``hip.PatchView`` that piece is never unfolded: the stems read the window, and ``hip.stream_commit_view``
+copies the kept patches out of it.  Everywhere else the piece is unfolded and takes ``feed()``'s path.
 """
 
 import torch
@@ -32,13 +45,71 @@ import torch
 from . import hip
 
 
+class BandGeometry:
+    """The integer bookkeeping of a row stream: patch rows of height ``ph`` every ``sh`` pixel rows, over bands of any
+    height.  ``take(h)`` says what a band of ``h`` rows does - nothing here touches a tensor.
+
+    ``carry``: rows of the window before the next band (< ph); ``skip``: rows of the coming bands that no patch row will ever
+    cover (``sh > ph`` only; ``carry`` is 0 then); ``rows``: pixel rows taken; ``patch_rows``: complete patch rows so far;
+    ``first_row``: the image row the window starts at (``patch_rows * sh`` whenever the window is not empty)."""
+
+    def __init__(self, ph, sh):
+        if ph < 1 or sh < 1:
+            raise ValueError("patch height {} / stride {}".format(ph, sh))
+        self.ph, self.sh = int(ph), int(sh)
+        self.rows = self.carry = self.skip = self.patch_rows = 0
+
+    @property
+    def first_row(self):
+        return self.rows - self.carry + self.skip
+
+    def plan(self, h):
+        """A band of ``h`` rows, without taking it -> (drop, window_rows, ny_w, carry, skip): its first ``drop`` rows are
+        skipped, the window then has ``window_rows`` rows (carried + kept), of which ``ny_w`` patch rows are complete -
+        window rows ``i * sh .. i * sh + ph - 1`` for i < ny_w -, and ``carry`` / ``skip`` afterwards."""
+        if h < 1:
+            raise ValueError("a band has at least one pixel row")
+        drop = min(self.skip, h)
+        rows = self.carry + h - drop
+        skip = self.skip - drop
+        if rows < self.ph:
+            return drop, rows, 0, rows, skip
+        ny_w = (rows - self.ph) // self.sh + 1
+        nxt = ny_w * self.sh                       # the window row the next patch row starts at
+        return drop, rows, ny_w, max(0, rows - nxt), max(0, nxt - rows)
+
+    def take(self, h):
+        out = self.plan(h)
+        self.rows += h
+        self.patch_rows += out[2]
+        self.carry, self.skip = out[3], out[4]
+        return out
+
+
 class IPSStream:
     """The state of one streamed selection.  ``fed``: patches per image so far; ``iterations``: completed iterations;
     ``mem_idx``: (B, M) int64 global patch numbers in the order of the last completed iteration (None until M patches
-    have arrived)."""
+    have arrived).  A row stream (``patch_size`` / ``patch_stride`` given) takes ``feed_rows(band)`` instead of ``feed``;
+    ``rows``: pixel rows taken so far, ``fed``: complete patch rows times ``nx``; ``view_feeds``: feeds whose piece was read
+    through a patch view (no patch tensor)."""
 
-    def __init__(self, net):
+    def __init__(self, net, patch_size=None, patch_stride=None):
         self.net = net
+        self._geom = None
+        if patch_size is not None or patch_stride is not None:
+            if patch_size is None or patch_stride is None:
+                raise ValueError("a row stream needs both patch_size and patch_stride")
+            if not net.is_image:
+                raise TypeError("a row stream takes bands of whole images: it goes with an image encoder")
+            (ph, pw), (sh, sw) = (int(v) for v in patch_size), (int(v) for v in patch_stride)
+            if min(ph, pw, sh, sw) <= 0:
+                raise ValueError("patch {}x{} / stride {}x{}".format(ph, pw, sh, sw))
+            self._patch_size, self._patch_stride = (ph, pw), (sh, sw)
+            self._geom = BandGeometry(ph, sh)
+            self._carry = None           # (B, C, carry, W) on net.device: the window before the next band
+            self._band_shape = None      # (B, C, W) of the first band
+            self._nx = 0
+        self.view_feeds = 0
         self.fed = 0
         self.iterations = 0
         self._finished = False
@@ -55,6 +126,11 @@ class IPSStream:
         self._pending = None         # (B, t, ...) rows no iteration has consumed
 
     # ------------------------------------------------------------------ observable state
+    @property
+    def rows(self):
+        """Pixel rows taken so far (a row stream)."""
+        return self._geom.rows if self._geom is not None else None
+
     @property
     def mem_idx(self):
         M = self.net.M
@@ -104,6 +180,8 @@ class IPSStream:
         """Take the next ``piece`` (B, n, ...) of every image.  Stream-ordered on the current stream: when the call
         returns, the caller may overwrite or free the piece with work on that stream.  Host pieces are copied to the
         device as they are."""
+        if self._geom is not None:
+            raise TypeError("this is a row stream (ips_stream(patch_size, patch_stride)): it takes feed_rows(band), not patches")
         self._check(piece)
         net = self.net
         if self._B is None:
@@ -125,6 +203,111 @@ class IPSStream:
                 net.encoder.train()
                 net.transf.train()
         self.fed += piece.shape[1]
+        return self
+
+    # ------------------------------------------------------------------ feed_rows
+    def _check_rows(self, band):
+        """Everything that refuses a band, before the first launch or allocation of the call -> the geometry's plan."""
+        net = self.net
+        if self._geom is None:
+            raise TypeError("this is a patch stream: feed_rows() goes with ips_stream(patch_size, patch_stride)")
+        self._check()
+        if not torch.is_tensor(band) or band.dim() != 4 or min(band.shape) < 1:
+            raise ValueError("a band is (B, C, h, W): the next h >= 1 pixel rows of every image")
+        (ph, pw), (sh, sw) = self._patch_size, self._patch_stride
+        B, Cc, h, W = band.shape
+        if self._band_shape is None:
+            if band.dtype == torch.uint8:
+                table = net._table_for(band)
+                if table.shape[0] != Cc:
+                    raise ValueError("the patch table has {} rows, the band {} channels".format(table.shape[0], Cc))
+                if self._on_device and hip.precision() != "fp32":
+                    raise TypeError("uint8 bands go with the exact trunk (IPSX_PRECISION=fp32), not {}".format(hip.precision()))
+            elif band.dtype != torch.float32:
+                raise TypeError("bands are float32, or uint8 after set_patch_table; got {}".format(band.dtype))
+            want = next(net.encoder.children()).in_channels
+            if Cc != want:
+                raise ValueError("a band of {} channels, the encoder expects {}".format(Cc, want))
+            if pw > W:
+                raise ValueError("patches of width {} do not fit rows of {} pixels".format(pw, W))
+        else:
+            if (B, Cc, W) != self._band_shape:
+                raise ValueError("a band of shape {} in a stream of (B = {}, C = {}, h, W = {})".format(
+                    tuple(band.shape), *self._band_shape))
+            if band.dtype != self._dtype:
+                raise TypeError("a {} band in a stream of {}".format(band.dtype, self._dtype))
+        plan = self._geom.plan(h)
+        n_k = plan[2] * ((W - pw) // sw + 1)
+        if net.use_pos and self.fed + n_k > net.pos_enc.shape[1]:
+            raise ValueError("{} patches per image pass the {} rows of the positional table (conf.N)".format(
+                self.fed + n_k, net.pos_enc.shape[1]))
+        return plan
+
+    def _window(self, band, drop, rows):
+        """The carried rows and the band's rows from ``drop`` on as ONE (B, C, rows, W) tensor on the net's device: the only
+        copy of pixels a feed makes - a host band's transfer lands in it."""
+        B, Cc, h, W = band.shape
+        carry = rows - (h - drop)
+        window = torch.empty((B, Cc, rows, W), dtype=band.dtype, device=self.net.device)
+        if carry:
+            window[:, :, :carry].copy_(self._carry)
+        if h > drop:
+            src, dst = band[:, :, drop:], window[:, :, carry:]
+            if src.device == window.device or (src.is_contiguous() and dst.is_contiguous()):
+                dst.copy_(src)
+            else:                        # host rows into a strided window: plane by plane, each transfer contiguous at both ends
+                for b in range(B):
+                    for c in range(Cc):
+                        dst[b, c].copy_(src[b, c])
+        return window
+
+    @torch.no_grad()
+    def feed_rows(self, band):
+        """Take the next pixel rows ``band`` (B, C, h, W) of every image - float32, or uint8 after ``set_patch_table``; on the
+        device or on the host.  The patch rows the band completes are this feed's piece (none: nothing is launched).
+        Stream-ordered like ``feed``: when the call returns, the caller may overwrite or free the band."""
+        drop, rows, ny_w, carry, _ = self._check_rows(band)
+        net = self.net
+        (ph, pw), (sh, sw) = self._patch_size, self._patch_stride
+        if self._band_shape is None:
+            B, Cc, _, W = band.shape
+            self._band_shape, self._nx = (B, Cc, W), (W - pw) // sw + 1
+            self._B, self._row_shape, self._dtype = B, (Cc, ph, pw), band.dtype
+        self._geom.take(band.shape[2])
+        if rows == 0:                    # every row of the band lies between two patch rows
+            return self
+        window = self._window(band, drop, rows)
+        self._carry = None
+        if ny_w:
+            n_k = ny_w * self._nx
+            was_training = net.training
+            if was_training:
+                net.encoder.eval()
+                net.transf.eval()
+            try:
+                view = None
+                if self._on_device and not net.encoder.training:
+                    view = hip.PatchView(window.shape, self._patch_size, self._patch_stride)
+                    if net._plan is None:
+                        net._plan = hip.EncoderPlan(net.encoder, net.is_image)
+                    if not net._plan.view_supported(view):
+                        view = None
+                if view is not None:
+                    self._feed_hip(window, view)
+                    self.view_feeds += 1
+                else:                    # the piece as a patch tensor, through feed()'s path
+                    piece = net._materialise(window[:, :, :(ny_w - 1) * sh + ph], self._patch_size, self._patch_stride)
+                    if self._on_device:
+                        self._feed_hip(piece)
+                    else:
+                        self._feed_aten(piece)
+            finally:
+                if was_training:
+                    net.encoder.train()
+                    net.transf.train()
+            self.fed += n_k
+        if carry:                        # (a copy: the window itself is released)
+            self._carry = window[:, :, rows - carry:].clone() if ny_w else window
         return self
 
     # ------------------------------------------------------------------ the ROCm device
@@ -180,28 +363,38 @@ class IPSStream:
                                self._scan_ws)
         hip.scan.last_tie = self._tie
 
-    def _feed_hip(self, piece):
+    def _feed_hip(self, piece, view=None):
+        """One feed on the device.  ``view``: ``piece`` is the window (B, C, rows, W) of a row stream and the feed's patches are
+        those of its ``hip.PatchView`` - encoded and committed where they lie, no patch tensor."""
         net = self.net
         M, I = net.M, net.I
-        n_k, held = piece.shape[1], self._held
+        n_k, held = piece.shape[1] if view is None else view.per_image, self._held
         if self._sets is None:
             self._allocate(piece)
         self._logits_room(held + n_k, piece.device)
         patch, emb, ids, lg = self._sets[self._cur]
-        emb_k = self._encode(piece)
+        if view is None:
+            emb_k = self._encode(piece)
+            commit = hip.stream_commit
+        else:                        # (the view numbers image-major: one launch for all images)
+            src = hip.PatchSource(images=piece, view=view, table=net._table_for(piece))
+            emb_k = net._plan.encode_source(src, first=0, n=view.count).view(self._B, n_k, -1)
+
+            def commit(tables, *args):          # the patch table's piece is (window, view)
+                hip.stream_commit_view([tables[0][:2] + (None,) + tables[0][3:]] + tables[1:], piece, view, *args)
         pos = net.pos_enc[:, self.fed:self.fed + n_k] if net.use_pos else None       # (shared by the images: batch stride 0)
         hip.logits(emb_k, pos, net.transf.crs_attn.folded_query(), self._R, out=lg[:, held:held + n_k])
         ids_k = torch.arange(self.fed, self.fed + n_k, dtype=torch.int64, device=piece.device).unsqueeze(0)
         total = held + n_k
         k = (total - M) // I if total > M else 0
         if k == 0:                   # no chunk is complete: the piece goes behind the held rows (its logits lie there already)
-            hip.stream_commit([(patch, held, piece, patch), (emb, held, emb_k, emb), (ids, held, ids_k, ids)], None, M, total)
+            commit([(patch, held, piece, patch), (emb, held, emb_k, emb), (ids, held, ids_k, ids)], None, M, total)
             self._held = total
             return
         self._scan(total, k)
         nxt = self._sets[self._cur ^ 1]
-        hip.stream_commit([(patch, held, piece, nxt[0]), (emb, held, emb_k, nxt[1]), (ids, held, ids_k, nxt[2]),
-                           (lg, total, None, nxt[3])], self._sel, M, total, M + k * I)
+        commit([(patch, held, piece, nxt[0]), (emb, held, emb_k, nxt[1]), (ids, held, ids_k, nxt[2]),
+                (lg, total, None, nxt[3])], self._sel, M, total, M + k * I)
         self._cur ^= 1
         self._held = total - k * I
         self.iterations += k
@@ -253,6 +446,8 @@ class IPSStream:
         net = self.net
         if self._B is None:
             raise RuntimeError("nothing was fed")
+        if self._geom is not None and self.fed == 0:
+            raise RuntimeError("the {} pixel rows fed complete no patch row of height {}".format(self.rows, self._patch_size[0]))
         M, B = net.M, self._B
         net._emb_parts = net._mem_emb = None
         net.last_shuffle = None
@@ -299,3 +494,5 @@ class IPSStream:
         self._finished, self._last_idx = True, mem_idx
         self._sets = self._sel = self._scan_ws = None
         self._mem_patch = self._mem_emb = self._mem_ids = self._pending = None
+        if self._geom is not None:
+            self._carry = None
