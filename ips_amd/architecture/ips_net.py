@@ -26,6 +26,7 @@ order per patch.  ``last_mem_idx`` exposes the selected indices (the reference
 only returns the gathered patches).
 """
 
+import contextlib
 import os
 
 import torch
@@ -200,22 +201,29 @@ class IPSNet(nn.Module):
         through an index (device-resident, contiguous, a schedule that supports it; ``IPSX_SHUFFLE=copy`` switches it off) -
         WITHOUT the permuted copy of the patch tensor.  The permutation is drawn by the calls ``do_shuffle`` makes, so the
         RNG streams and the results are those of the copy.  ``pos_enc`` (a few hundred floats per patch) is shuffled by
-        copy either way.  -> (patches, pos_enc, order): ``order`` is the (B or 1, N) index when ``patches`` came back
-        unshuffled, else None."""
+        copy either way.  ``patches`` may be a ``hip.PatchSource`` (``ips_image``): there is nothing to copy, so it always
+        selects through the index, and ``last_shuffle`` keeps what ``ips()`` keeps for the patch tensor - the device copy
+        where it would have selected through the index itself, else the permutation as drawn.  An overridden
+        ``do_shuffle`` is called as ever.  -> (patches, pos_enc, order): ``order`` is the (B or 1, N) index on the device
+        when ``patches`` came back unshuffled, else None."""
+        if self._shuffle_overridden():
+            return (*self.do_shuffle(patches, pos_enc), None)
         perm = draw_shuffle(patches, self.shuffle_style)
         if perm is None:                   # an unknown style: do_shuffle leaves everything as it is
             return patches, pos_enc, None
         batch = self.shuffle_style == 'batch'
         if torch.is_tensor(pos_enc):
             pos_enc = shuffle_batch(pos_enc, perm)[0] if batch else shuffle_instance(pos_enc, 1, perm)[0]
-        by_index = (os.environ.get("IPSX_SHUFFLE", "index") != "copy" and hip.on_device(self.device) and patches.is_cuda
-                    and patches.is_contiguous() and self.selection.index_supported(patches))
-        order = (perm.unsqueeze(0) if batch else perm)
-        if by_index:
-            order = order.to(patches.device).contiguous()
-            self.last_shuffle = order
+        source = not torch.is_tensor(patches)
+        by_index = (os.environ.get("IPSX_SHUFFLE", "index") != "copy"
+                    and (source or (hip.on_device(self.device) and patches.is_cuda and patches.is_contiguous()))
+                    and self.selection.index_supported(patches))
+        drawn = perm.unsqueeze(0) if batch else perm
+        if by_index or source:
+            order = drawn.to(patches.device).contiguous()
+            self.last_shuffle = order if by_index else drawn
             return patches, pos_enc, order
-        self.last_shuffle = order
+        self.last_shuffle = drawn
         patches = shuffle_batch(patches, perm)[0] if batch else shuffle_instance(patches, 1, perm)[0]
         return patches, pos_enc, None
 
@@ -250,9 +258,7 @@ class IPSNet(nn.Module):
         """(P, C, h, w) | (P, F)  ->  (P, D) with the encoder's CURRENT mode."""
         if hip.on_device(x) and not self.encoder.training and not (
                 torch.is_grad_enabled() and any(p.requires_grad for p in self.encoder.parameters())):
-            if self._plan is None:
-                self._plan = hip.EncoderPlan(self.encoder, self.is_image)
-            return self._plan.encode(x, table=self._table_for(x))
+            return self.plan.encode(x, table=self._table_for(x))
         if x.dtype == torch.uint8:
             # the stock modules (CPU / ATen path, or an encoder in training mode) compute on the dequantised pixels
             x = self._dequant(x)
@@ -287,37 +293,51 @@ class IPSNet(nn.Module):
         uint8 image patches (after ``set_patch_table``): the same selection on a quarter of the bytes; ``mem_patch``
         comes back float32 - the selected bytes dequantised, bit for bit what the call returns for the expanded tensor.
         """
-        M, device, pos_enc = self.M, self.device, self.pos_enc
         B, N = patches.shape[:2]
         u8 = patches.dtype == torch.uint8
         if u8:
             self._check_u8(patches)
+        if self.M >= N:  # nothing to select (:185-188)
+            self._emb_parts = self._mem_emb = self.last_shuffle = self.last_mem_idx = None
+            mem_patch = patches.to(self.device)
+            return (self._dequant(mem_patch) if u8 else mem_patch), (self.pos_enc.expand(B, -1, -1) if self.use_pos else None)
+        return self._call(patches)
 
-        self._emb_parts = self._mem_emb = None
-        self.last_shuffle = None
-        if M >= N:  # nothing to select (:185-188)
-            self.last_mem_idx = None
-            mem_patch = patches.to(device)
-            return (self._dequant(mem_patch) if u8 else mem_patch), (pos_enc.expand(B, -1, -1) if self.use_pos else None)
-
+    @contextlib.contextmanager
+    def _scoring(self):
+        """The frame of every selection (``ips``, ``ips_image``, streams, sharded calls): IPS always scores with running BN
+        statistics and no dropout, so a net in train mode has its encoder and transformer in eval mode inside the block
+        and both back in train mode behind it, also after an exception.  A net in eval mode is left alone."""
         was_training = self.training
-        if was_training:  # IPS always scores with running BN statistics and no dropout
+        if was_training:
             self.encoder.eval()
             self.transf.eval()
         try:
+            yield
+        finally:
+            if was_training:
+                self.encoder.train()
+                self.transf.train()
+
+    def _call(self, patches):
+        """One selection with N > M, the body of ``ips()`` ((B, N, ...) patches) and ``ips_image()`` (a ``hip.PatchSource``
+        with a view: whole images on the device) -> (mem_patch, mem_pos).  The two differ in the last gather alone."""
+        device, pos_enc = self.device, self.pos_enc
+        viewed = not torch.is_tensor(patches)
+        u8 = patches.dtype == torch.uint8
+        B = patches.shape[0]
+        self._emb_parts = self._mem_emb = None
+        self.last_shuffle = None
+        with self._scoring():
             if self.use_pos:
                 pos_enc = pos_enc.expand(B, -1, -1)
             order = None
-            if self.shuffle and self._shuffle_overridden():
-                patches, pos_enc = self.do_shuffle(patches, pos_enc)
-            elif self.shuffle:
+            if self.shuffle:
                 # (the encoder is in eval mode by now: the index path's own condition)
                 patches, pos_enc, order = self._shuffle(patches, pos_enc)
 
             if hip.on_device(device):
-                if self._plan is None:
-                    self._plan = hip.EncoderPlan(self.encoder, self.is_image)
-                with self._plan.hold():            # weights cannot change inside a no-grad call: check them once
+                with self.plan.hold():            # weights cannot change inside a no-grad call: check them once
                     mem_idx = self._select_hip(patches, pos_enc, order)
             else:
                 mem_idx = self._select_aten(patches, pos_enc)
@@ -325,6 +345,7 @@ class IPSNet(nn.Module):
             src = self._device_patches if self._device_patches is not None else patches
             self._device_patches = None
             sel = self._selection
+            # (a call on a source leaves nothing pending: finish returns None before it looks at ``src``)
             done = sel.finish(src, pos_enc if self.use_pos else None, order) if sel is not None else None
             if done is not None:       # a resident loop's call ends in ONE launch: gathers, indices, status word (round 5)
                 mem_idx, mem_patch, mem_pos = done
@@ -332,17 +353,16 @@ class IPSNet(nn.Module):
                 if sel is not None:
                     mem_idx = sel.take_unfinished(mem_idx)
                 # (through a shuffle index the patches are unshuffled: their rows are order[b, mem_idx[b, m]])
-                mem_patch = self._take(src, mem_idx if order is None else
-                                       torch.gather(order.expand(B, -1), 1, mem_idx)).to(device)
+                rows = mem_idx if order is None else torch.gather(order.expand(B, -1), 1, mem_idx)
+                if viewed:             # straight out of the images, float32 whatever they store
+                    mem_patch = hip.gather_patches_view(src.images, src.view, rows, self._table_for(src))
+                else:
+                    mem_patch = self._take(src, rows).to(device)
                 mem_pos = self._take(pos_enc, mem_idx) if self.use_pos else None
                 if sel is not None:
                     sel.after_call()
-            if u8:                     # the M selected patches leave as float32 (forward / fill_batch read float32)
+            if u8 and not viewed:      # the M selected patches leave as float32 (forward / fill_batch read float32)
                 mem_patch = self._dequant(mem_patch)
-        finally:
-            if was_training:
-                self.encoder.train()
-                self.transf.train()
 
         self.last_mem_idx = mem_idx
         return mem_patch, mem_pos
@@ -384,53 +404,11 @@ class IPSNet(nn.Module):
                 and not (self.encoder.training and not self.training)       # (ips() itself puts a training NET into eval mode)
                 and not (self.shuffle and self._shuffle_overridden())):
             view = hip.PatchView(images.shape, patch_size, patch_stride)
-            if self._plan is None:
-                self._plan = hip.EncoderPlan(self.encoder, self.is_image)
-            if self.M >= view.per_image or not self._plan.view_supported(view):
+            if self.M >= view.per_image or not self.plan.view_supported(view):
                 view = None
         if view is None:
             return self.ips(self._materialise(images, patch_size, patch_stride))
-
-        M, device, pos_enc = self.M, self.device, self.pos_enc
-        src = hip.PatchSource(images=images.to(device), view=view, table=table)
-        images = src.images
-        B, N = view.image_shape[0], view.per_image
-        self._emb_parts = self._mem_emb = None
-        self.last_shuffle = None
-        was_training = self.training
-        if was_training:
-            self.encoder.eval()
-            self.transf.eval()
-        try:
-            if self.use_pos:
-                pos_enc = pos_enc.expand(B, -1, -1)
-            order = None
-            if self.shuffle:
-                # the draws do_shuffle would make on the (B, N, ...) tensor; the view always selects through the index
-                perm = draw_shuffle(src, self.shuffle_style)
-                if perm is not None:
-                    batch = self.shuffle_style == 'batch'
-                    if torch.is_tensor(pos_enc):
-                        pos_enc = shuffle_batch(pos_enc, perm)[0] if batch else shuffle_instance(pos_enc, 1, perm)[0]
-                    kept = perm.unsqueeze(0) if batch else perm
-                    order = kept.to(device).contiguous()
-                    # (what ips() keeps: the device copy where it would have selected through the index itself)
-                    self.last_shuffle = order if (os.environ.get("IPSX_SHUFFLE", "index") != "copy"
-                                                  and self.selection.index_supported(src)) else kept
-            with self._plan.hold():
-                mem_idx = self.selection.select(src, pos_enc, order)
-            sel = self.selection
-            mem_idx = sel.take_unfinished(mem_idx)
-            mem_patch = hip.gather_patches_view(images, view, mem_idx if order is None else
-                                                torch.gather(order.expand(B, -1), 1, mem_idx), table)
-            mem_pos = self._take(pos_enc, mem_idx) if self.use_pos else None
-            sel.after_call()
-        finally:
-            if was_training:
-                self.encoder.train()
-                self.transf.train()
-        self.last_mem_idx = mem_idx
-        return mem_patch, mem_pos
+        return self._call(hip.PatchSource(images=images.to(self.device), view=view, table=table))
 
     def ips_stream(self, patch_size=None, patch_stride=None):
         """``ips()`` over patches that arrive in pieces -> ``ips_amd.stream.IPSStream``: ``feed(piece)`` takes
@@ -463,6 +441,13 @@ class IPSNet(nn.Module):
         return torch.gather(src.expand(idx.shape[0], *src.shape[1:]), 1, view)
 
     @property
+    def plan(self):
+        """The packed-weight plan of the HIP encoder (``hip.EncoderPlan``), built on first use and kept in ``_plan``."""
+        if self._plan is None:
+            self._plan = hip.EncoderPlan(self.encoder, self.is_image)
+        return self._plan
+
+    @property
     def selection(self):
         """The HIP selection pipelines of this net (ips_amd/selection.py), built on first use."""
         if self._selection is None:
@@ -474,6 +459,22 @@ class IPSNet(nn.Module):
         """encode -> logits -> selection loop on the ROCm device (which producer, how the loop follows it: selection.py);
         patches may still be on the host (lazy loading); ``order``: a shuffle applied as an index (``_shuffle``)."""
         return self.selection.select(patches, pos_enc, order)
+
+    def _iterate(self, mem_emb, mem_ids, emb, ids, pos_table, rows=False):
+        """One iteration of the reference's loop on stock ATen ops (:229-241): the memory first, the chunk ``emb`` / ``ids``
+        after, positions added through the ids (``pos_table``: (B, N, D), used with ``use_pos``), ``score_and_select``
+        -> (mem_emb, mem_ids, top).  ``rows``: ``top`` is the (B, M) compact candidate rows that were kept (a stream
+        gathers its patches with them), else None."""
+        cand_emb = torch.cat((mem_emb, emb), dim=1)
+        cand_ids = torch.cat((mem_ids, ids), dim=1)
+        cand_pos = None
+        if self.use_pos:
+            cand_pos = cand_emb + torch.gather(pos_table, 1, cand_ids.unsqueeze(-1).expand(-1, -1, self.D))
+        if not rows:
+            return (*self.score_and_select(cand_emb, cand_pos, self.M, cand_ids), None)
+        idx = torch.arange(cand_ids.shape[1], dtype=torch.int64, device=emb.device).unsqueeze(0).expand(emb.shape[0], -1)
+        mem_emb, top = self.score_and_select(cand_emb, cand_pos, self.M, idx)
+        return mem_emb, torch.gather(cand_ids, 1, top), top
 
     def _select_aten(self, patches, pos_enc):
         """The reference's loop on stock ATen ops (CPU plumbing path)."""
@@ -487,12 +488,7 @@ class IPSNet(nn.Module):
             if mem_emb is None:
                 mem_emb, mem_idx = emb, order[:, lo:hi]
                 continue
-            cand_emb = torch.cat((mem_emb, emb), dim=1)          # memory first, chunk after
-            cand_idx = torch.cat((mem_idx, order[:, lo:hi]), dim=1)
-            cand_pos = None
-            if self.use_pos:
-                cand_pos = cand_emb + torch.gather(pos_enc, 1, cand_idx.unsqueeze(-1).expand(-1, -1, D))
-            mem_emb, mem_idx = self.score_and_select(cand_emb, cand_pos, self.M, cand_idx)
+            mem_emb, mem_idx, _ = self._iterate(mem_emb, mem_idx, emb, order[:, lo:hi], pos_enc)
         self._mem_emb = mem_emb
         return mem_idx
 

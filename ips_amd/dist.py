@@ -404,10 +404,7 @@ def ips_sharded(net, local_patches, N, group=None, timings=None, plan=None):
             raise RuntimeError("ips_sharded: the ranks disagree on the partition (different GPUs per rank?) - pass the same plan= everywhere")
         net.__dict__["_shard_plan_checked"] = (plan.signature(), world)
     dev = local_patches.device
-    was_training = net.training
-    if was_training:
-        net.encoder.eval(); net.transf.eval()
-    try:
+    with net._scoring():
         ca = net.transf.crs_attn
         on_gpu = hip.on_device(dev)
         if on_gpu:
@@ -442,9 +439,7 @@ def ips_sharded(net, local_patches, N, group=None, timings=None, plan=None):
 
         indexed = False
         if on_gpu and net.is_image and not hip.dedup_blank() and local_patches.is_contiguous():
-            if net._plan is None:
-                net._plan = hip.EncoderPlan(net.encoder, net.is_image)
-            indexed = net._plan.fused(local_patches.shape)                 # encode a column range without copying it
+            indexed = net.plan.fused(local_patches.shape)                 # encode a column range without copying it
         if indexed:
             flat = local_patches.reshape(B * n_local, *local_patches.shape[2:])
             ikey = (plan.signature(), rank, str(dev))
@@ -518,23 +513,20 @@ def ips_sharded(net, local_patches, N, group=None, timings=None, plan=None):
         owned = owner[mem_idx] == rank
         local_idx = torch.where(owned, lpos[mem_idx], torch.zeros_like(mem_idx)).clamp_(0, max(n_local - 1, 0))
         if n_local > 0:
-            mem_patch = _take(local_patches, local_idx)
+            mem_patch = net._take(local_patches, local_idx)
             mem_patch = mem_patch * owned.view(B, M, *(1,) * (mem_patch.dim() - 2)).to(mem_patch.dtype)
         else:
             mem_patch = torch.zeros((B, M) + tuple(local_patches.shape[2:]), dtype=local_patches.dtype, device=dev)
         if isinstance(group, LoopbackGroup):
             # the all-reduce's stand-in: the rows other ranks own arrive by a device copy of the same size
-            others = _take(group.full_patches, mem_idx)
+            others = net._take(group.full_patches, mem_idx)
             mem_patch = torch.where(owned.view(B, M, *(1,) * (mem_patch.dim() - 2)), mem_patch, others)
         else:
             mem_patch = _all_reduce(mem_patch, group)
-        mem_pos = _take(net.pos_enc, mem_idx) if net.use_pos else None
+        mem_pos = net._take(net.pos_enc, mem_idx) if net.use_pos else None
         if on_gpu and ev is not None:
             ev["end"].record(main)
             timings.append(ev)
-    finally:
-        if was_training:
-            net.encoder.train(); net.transf.train()
     net.last_mem_idx = mem_idx
     return mem_patch, mem_pos, mem_idx
 
@@ -628,10 +620,7 @@ def ips_tournament(net, local_patches, N, group=None):
     B, n_local = local_patches.shape[:2]
     assert n_local == hi - lo, "rank %d expects %d patches, got %d" % (rank, hi - lo, n_local)
     dev = local_patches.device
-    was_training = net.training
-    if was_training:
-        net.encoder.eval(); net.transf.eval()
-    try:
+    with net._scoring():
         pos = net.pos_enc[:, lo:hi].expand(B, -1, -1) if net.use_pos else None
         k = min(M, n_local)                                      # a slab no larger than the memory keeps everything
         if n_local > M:
@@ -657,23 +646,13 @@ def ips_tournament(net, local_patches, N, group=None):
 
         owned = (mem_idx >= lo) & (mem_idx < hi)
         local_idx = torch.where(owned, mem_idx - lo, torch.zeros_like(mem_idx)).clamp_(0, max(n_local - 1, 0))
-        mem_patch = _take(local_patches, local_idx)
+        mem_patch = net._take(local_patches, local_idx)
         mem_patch = mem_patch * owned.view(B, M, *(1,) * (mem_patch.dim() - 2)).to(mem_patch.dtype)
         mem_patch = _all_reduce(mem_patch, group)
-        mem_pos = _take(net.pos_enc, mem_idx) if net.use_pos else None
-    finally:
-        if was_training:
-            net.encoder.train(); net.transf.train()
+        mem_pos = net._take(net.pos_enc, mem_idx) if net.use_pos else None
     net.last_mem_idx = mem_idx
     net._emb_parts = net._mem_emb = None
     return mem_patch, mem_pos, mem_idx
-
-
-def _take(src, idx):
-    if hip.on_device(src):
-        return hip.gather_rows(src, idx)
-    view = idx.view(*idx.shape, *(1,) * (src.dim() - 2)).expand(-1, -1, *src.shape[2:])
-    return torch.gather(src.expand(idx.shape[0], *src.shape[1:]), 1, view)
 
 
 def _scan_aten(net, emb):
@@ -685,8 +664,5 @@ def _scan_aten(net, emb):
     mem_emb, mem_idx = emb[:, :M], order[:, :M]
     for lo in range(M, N, I):
         hi = min(lo + I, N)
-        ce = torch.cat((mem_emb, emb[:, lo:hi]), 1)
-        ci = torch.cat((mem_idx, order[:, lo:hi]), 1)
-        cp = ce + torch.gather(pos, 1, ci.unsqueeze(-1).expand(-1, -1, D)) if net.use_pos else None
-        mem_emb, mem_idx = net.score_and_select(ce, cp, M, ci)
+        mem_emb, mem_idx, _ = net._iterate(mem_emb, mem_idx, emb[:, lo:hi], order[:, lo:hi], pos)
     return mem_idx

@@ -88,10 +88,22 @@ class Selection:
 
     # ------------------------------------------------------------------ small helpers
     def plan(self):
-        net = self.net
-        if net._plan is None:
-            net._plan = hip.EncoderPlan(net.encoder, net.is_image)
-        return net._plan
+        return self.net.plan
+
+    def status_mirror(self):
+        """The pinned host mirror of a resident loop's status word, made on first use."""
+        if self.scan_status_host is None:
+            self.scan_status_host = torch.zeros((1,), dtype=torch.int32).pin_memory()
+        return self.scan_status_host
+
+    def check_strike(self, dev):
+        """Look at the mirror of the PREVIOUS call's status word (it has long arrived): a loop or a wait that gave up
+        clears it and counts as an event (``hip.persistent_timed_out``: the device's self-test again; the persistent
+        pipelines go off for the process only after repeated events)."""
+        mirror = self.scan_status_host
+        if mirror is not None and int(mirror.item()) & 1:
+            mirror.zero_()
+            hip.persistent_timed_out(dev)
 
     def n_iter(self, N):
         return math.ceil((N - self.net.M) / self.net.I)
@@ -138,10 +150,7 @@ class Selection:
         hip._PERSIST_CALLS += 1
         net = self.net
         ca = net.transf.crs_attn
-        mirror = self.scan_status_host
-        if mirror is not None and int(mirror.item()) & 1:
-            mirror.zero_()
-            hip.persistent_timed_out(dev)          # (self-test again; off for the process only after repeated events)
+        self.check_strike(dev)
         side, main = self.streams(dev)
         tie, words, ctl = zeroed[:B], zeroed[B:2 * B + 1], zeroed[2 * B + 1:]
         ready, status = words[:B], words[B:B + 1]
@@ -186,10 +195,8 @@ class Selection:
         if status is None or src.dtype == torch.uint8 or not hip.ips_finish_supported(src, pos):     # (uint8: gather, then dequantise)
             self._unfinished = buf
             return None
-        if self.scan_status_host is None:
-            self.scan_status_host = torch.zeros((1,), dtype=torch.int32).pin_memory()
         self._mirror_pending = None
-        return hip.ips_finish(src, pos, buf, status, self.scan_status_host, order=order)
+        return hip.ips_finish(src, pos, buf, status, self.status_mirror(), order=order)
 
     def take_unfinished(self, mem_idx):
         """``mem_idx`` as a tensor of the caller's own (the loop's buffer is overwritten by the next call)."""
@@ -212,12 +219,8 @@ class Selection:
         dev = patches.device
         ca = net.transf.crs_attn
         vq, R = ca.folded_query(), ca.H * ca.n_token
-        mirror = self.scan_status_host
-        if mirror is None:
-            mirror = self.scan_status_host = torch.zeros((1,), dtype=torch.int32).pin_memory()
-        elif int(mirror.item()) & 1:
-            mirror.zero_()
-            hip.persistent_timed_out(dev)          # (self-test again; off for the process only after repeated events)
+        self.check_strike(dev)
+        mirror = self.status_mirror()
         hip._PERSIST_CALLS += 1
         side, _ = self.streams(dev)
         plan._refresh()
@@ -275,9 +278,7 @@ class Selection:
         status = self._mirror_pending
         if status is not None:
             self._mirror_pending = None
-            if self.scan_status_host is None:
-                self.scan_status_host = torch.zeros((1,), dtype=torch.int32).pin_memory()
-            self.scan_status_host.copy_(status, non_blocking=True)
+            self.status_mirror().copy_(status, non_blocking=True)
 
     # ------------------------------------------------------------------ which pipeline
     def source(self, patches):
@@ -665,10 +666,7 @@ class Selection:
         ca = net.transf.crs_attn
         P = len(its) - 1
         hip._PERSIST_CALLS += 1                    # (the window of hip.persistent_timed_out is counted in such calls)
-        mirror = self.scan_status_host
-        if mirror is not None and int(mirror.item()) & 1:
-            mirror.zero_()
-            hip.persistent_timed_out(dev)          # (self-test again; off for the process only after repeated events)
+        self.check_strike(dev)
         side, main = self.streams(dev)
         logits, mem_idx_buf, words, scan_ws = self.buffers(
             "parts1", (B, N, M, I, R, P, str(dev)),

@@ -165,14 +165,23 @@ class IPSStream:
                 if hip.precision() == "fp32" or (not net.is_image and hip.precision() != "bf16"):
                     raise TypeError("{} pieces need IPSX_PRECISION=bf16{}".format(piece.dtype, " or fp32x3" if net.is_image else ""))
         else:
-            if piece.shape[0] != self._B or tuple(piece.shape[2:]) != self._row_shape:
-                raise ValueError("a piece of shape {} in a stream of (B = {}, n, {})".format(
-                    tuple(piece.shape), self._B, ", ".join(str(v) for v in self._row_shape)))
-            if piece.dtype != self._dtype:
-                raise TypeError("a {} piece in a stream of {}".format(piece.dtype, self._dtype))
-        if net.use_pos and self.fed + piece.shape[1] > net.pos_enc.shape[1]:
+            self._check_like_first("piece", piece, piece.shape[0] == self._B and tuple(piece.shape[2:]) == self._row_shape,
+                                   lambda: "B = {}, n, {}".format(self._B, ", ".join(str(v) for v in self._row_shape)))
+        self._check_fits(piece.shape[1])
+
+    def _check_like_first(self, what, t, same_shape, layout):
+        """A later piece / band must look like the first (``layout()``: the shape the stream takes, for the message)."""
+        if not same_shape:
+            raise ValueError("a {} of shape {} in a stream of ({})".format(what, tuple(t.shape), layout()))
+        if t.dtype != self._dtype:
+            raise TypeError("a {} {} in a stream of {}".format(t.dtype, what, self._dtype))
+
+    def _check_fits(self, n):
+        """Do ``n`` more patches per image still fit the positional table?"""
+        net = self.net
+        if net.use_pos and self.fed + n > net.pos_enc.shape[1]:
             raise ValueError("{} patches per image pass the {} rows of the positional table (conf.N)".format(
-                self.fed + piece.shape[1], net.pos_enc.shape[1]))
+                self.fed + n, net.pos_enc.shape[1]))
 
     # ------------------------------------------------------------------ feed
     @torch.no_grad()
@@ -183,27 +192,25 @@ class IPSStream:
         if self._geom is not None:
             raise TypeError("this is a row stream (ips_stream(patch_size, patch_stride)): it takes feed_rows(band), not patches")
         self._check(piece)
-        net = self.net
         if self._B is None:
             self._B, self._row_shape, self._dtype = piece.shape[0], tuple(piece.shape[2:]), piece.dtype
-        was_training = net.training
-        if was_training:                 # IPS always scores with running BN statistics and no dropout
-            net.encoder.eval()
-            net.transf.eval()
-        try:
-            piece = piece.to(net.device)
-            if not piece[0].is_contiguous():      # rows strided inside an image (a crop, channels-last): one copy up front, as ips() makes
-                piece = piece.contiguous()
+        self._run(piece)
+        return self
+
+    def _run(self, piece, view=None):
+        """One feed's piece through the selection, in the scoring frame (``IPSNet._scoring``): on the device or on ATen
+        ops.  ``view``: ``piece`` is the window of a row stream, its patches those of the view (``_feed_hip``)."""
+        net = self.net
+        with net._scoring():
+            if view is None:
+                piece = piece.to(net.device)
+                if not piece[0].is_contiguous():  # rows strided inside an image (a crop, channels-last): one copy up front, as ips() makes
+                    piece = piece.contiguous()
             if self._on_device:
-                self._feed_hip(piece)
+                self._feed_hip(piece, view)
             else:
                 self._feed_aten(piece)
-        finally:
-            if was_training:
-                net.encoder.train()
-                net.transf.train()
-        self.fed += piece.shape[1]
-        return self
+        self.fed += piece.shape[1] if view is None else view.per_image
 
     # ------------------------------------------------------------------ feed_rows
     def _check_rows(self, band):
@@ -231,16 +238,10 @@ class IPSStream:
             if pw > W:
                 raise ValueError("patches of width {} do not fit rows of {} pixels".format(pw, W))
         else:
-            if (B, Cc, W) != self._band_shape:
-                raise ValueError("a band of shape {} in a stream of (B = {}, C = {}, h, W = {})".format(
-                    tuple(band.shape), *self._band_shape))
-            if band.dtype != self._dtype:
-                raise TypeError("a {} band in a stream of {}".format(band.dtype, self._dtype))
+            self._check_like_first("band", band, (B, Cc, W) == self._band_shape,
+                                   lambda: "B = {}, C = {}, h, W = {}".format(*self._band_shape))
         plan = self._geom.plan(h)
-        n_k = plan[2] * ((W - pw) // sw + 1)
-        if net.use_pos and self.fed + n_k > net.pos_enc.shape[1]:
-            raise ValueError("{} patches per image pass the {} rows of the positional table (conf.N)".format(
-                self.fed + n_k, net.pos_enc.shape[1]))
+        self._check_fits(plan[2] * ((W - pw) // sw + 1))
         return plan
 
     def _window(self, band, drop, rows):
@@ -279,33 +280,17 @@ class IPSStream:
         window = self._window(band, drop, rows)
         self._carry = None
         if ny_w:
-            n_k = ny_w * self._nx
-            was_training = net.training
-            if was_training:
-                net.encoder.eval()
-                net.transf.eval()
-            try:
-                view = None
-                if self._on_device and not net.encoder.training:
-                    view = hip.PatchView(window.shape, self._patch_size, self._patch_stride)
-                    if net._plan is None:
-                        net._plan = hip.EncoderPlan(net.encoder, net.is_image)
-                    if not net._plan.view_supported(view):
-                        view = None
-                if view is not None:
-                    self._feed_hip(window, view)
-                    self.view_feeds += 1
-                else:                    # the piece as a patch tensor, through feed()'s path
-                    piece = net._materialise(window[:, :, :(ny_w - 1) * sh + ph], self._patch_size, self._patch_stride)
-                    if self._on_device:
-                        self._feed_hip(piece)
-                    else:
-                        self._feed_aten(piece)
-            finally:
-                if was_training:
-                    net.encoder.train()
-                    net.transf.train()
-            self.fed += n_k
+            view = None
+            # (the frame puts a training NET into eval mode: an encoder that alone is in training mode stays there)
+            if self._on_device and not (net.encoder.training and not net.training):
+                view = hip.PatchView(window.shape, self._patch_size, self._patch_stride)
+                if not net.plan.view_supported(view):
+                    view = None
+            if view is not None:
+                self._run(window, view)
+                self.view_feeds += 1
+            else:                        # the piece as a patch tensor, through feed()'s path
+                self._run(net._materialise(window[:, :, :(ny_w - 1) * sh + ph], self._patch_size, self._patch_stride))
         if carry:                        # (a copy: the window itself is released)
             self._carry = window[:, :, rows - carry:].clone() if ny_w else window
         return self
@@ -346,13 +331,12 @@ class IPSStream:
             return net._embed(flat).view(B, n, -1)
         if net.encoder.training:                                     # the stock modules (ips() takes them there too)
             return torch.stack([net._embed(piece[b]) for b in range(B)])
-        if net._plan is None:
-            net._plan = hip.EncoderPlan(net.encoder, net.is_image)
+        plan = net.plan
         emb = torch.empty((B, n, net.D), dtype=torch.float32, device=piece.device)
         table = net._table_for(piece)
-        with net._plan.hold():
+        with plan.hold():
             for b in range(B):
-                net._plan.encode(piece[b], out=emb[b], table=table)
+                plan.encode(piece[b], out=emb[b], table=table)
         return emb
 
     def _scan(self, n, k):
@@ -372,31 +356,44 @@ class IPSStream:
         if self._sets is None:
             self._allocate(piece)
         self._logits_room(held + n_k, piece.device)
-        patch, emb, ids, lg = self._sets[self._cur]
         if view is None:
             emb_k = self._encode(piece)
-            commit = hip.stream_commit
         else:                        # (the view numbers image-major: one launch for all images)
             src = hip.PatchSource(images=piece, view=view, table=net._table_for(piece))
-            emb_k = net._plan.encode_source(src, first=0, n=view.count).view(self._B, n_k, -1)
-
-            def commit(tables, *args):          # the patch table's piece is (window, view)
-                hip.stream_commit_view([tables[0][:2] + (None,) + tables[0][3:]] + tables[1:], piece, view, *args)
+            emb_k = net.plan.encode_source(src, first=0, n=view.count).view(self._B, n_k, -1)
         pos = net.pos_enc[:, self.fed:self.fed + n_k] if net.use_pos else None       # (shared by the images: batch stride 0)
+        lg = self._sets[self._cur][3]
         hip.logits(emb_k, pos, net.transf.crs_attn.folded_query(), self._R, out=lg[:, held:held + n_k])
         ids_k = torch.arange(self.fed, self.fed + n_k, dtype=torch.int64, device=piece.device).unsqueeze(0)
         total = held + n_k
-        k = (total - M) // I if total > M else 0
-        if k == 0:                   # no chunk is complete: the piece goes behind the held rows (its logits lie there already)
-            commit([(patch, held, piece, patch), (emb, held, emb_k, emb), (ids, held, ids_k, ids)], None, M, total)
-            self._held = total
-            return
-        self._scan(total, k)
-        nxt = self._sets[self._cur ^ 1]
-        commit([(patch, held, piece, nxt[0]), (emb, held, emb_k, nxt[1]), (ids, held, ids_k, nxt[2]),
-                (lg, total, None, nxt[3])], self._sel, M, total, M + k * I)
-        self._cur ^= 1
-        self._held = total - k * I
+        self._advance((total - M) // I if total > M else 0, total, piece, emb_k, ids_k, view)
+
+    def _advance(self, k, total, piece=None, emb_k=None, ids_k=None, view=None):
+        """The state update behind ``total`` candidates per image - the held rows and, behind them, a feed's ``piece`` with
+        its embeddings and ids (none: the ragged last chunk of ``finish()``): scan ``k`` iterations of the current logits
+        table, commit the kept rows and the tail behind iteration k into the OTHER set (ONE launch), flip, count.  ``k`` = 0
+        (no chunk is complete): the piece goes behind the held rows of the current set - its logits lie there already.
+        ``view``: ``piece`` is a row stream's window, the patch table's piece its view (``hip.stream_commit_view``)."""
+        net = self.net
+        M, I, held = net.M, net.I, self._held
+        cur = self._sets[self._cur]
+        dst = self._sets[self._cur ^ 1] if k else cur
+        tables = [(cur[0], held, piece if view is None else None, dst[0]), (cur[1], held, emb_k, dst[1]),
+                  (cur[2], held, ids_k, dst[2])]
+        sel = None
+        if k:
+            self._scan(total, k)
+            sel = self._sel
+            if emb_k is not None:    # (finish() scans nothing after its chunk: the logits stay behind)
+                tables.append((cur[3], total, None, dst[3]))
+        tail_first = min(M + k * I, total) if k else 0
+        if view is None:
+            hip.stream_commit(tables, sel, M, total, tail_first)
+        else:
+            hip.stream_commit_view(tables, piece, view, sel, M, total, tail_first)
+        if k:
+            self._cur ^= 1
+        self._held = max(M, total - k * I) if k else total
         self.iterations += k
 
     # ------------------------------------------------------------------ the CPU device (ATen ops)
@@ -411,14 +408,8 @@ class IPSStream:
         if self._mem_emb is None:
             self._mem_emb, self._mem_ids, self._mem_patch = emb, ids, chunk.clone()      # (the caller's piece may be overwritten)
             return
-        cand_emb = torch.cat((self._mem_emb, emb), dim=1)
-        cand_ids = torch.cat((self._mem_ids, ids), dim=1)
-        cand_pos = None
-        if net.use_pos:
-            cand_pos = cand_emb + torch.gather(net.pos_enc.expand(B, -1, -1), 1, cand_ids.unsqueeze(-1).expand(-1, -1, D))
-        rows = torch.arange(cand_ids.shape[1], dtype=torch.int64, device=chunk.device).unsqueeze(0).expand(B, -1)
-        self._mem_emb, top = net.score_and_select(cand_emb, cand_pos, net.M, rows)      # (top: compact candidate rows)
-        self._mem_ids = torch.gather(cand_ids, 1, top)
+        pos = net.pos_enc.expand(B, -1, -1) if net.use_pos else None
+        self._mem_emb, self._mem_ids, top = net._iterate(self._mem_emb, self._mem_ids, emb, ids, pos, rows=True)
         self._mem_patch = net._take(torch.cat((self._mem_patch, chunk), dim=1), top)
         self.iterations += 1
 
@@ -459,20 +450,10 @@ class IPSStream:
             self._close(None)
             net.last_mem_idx = None
             return (net._dequant(mem_patch) if u8 else mem_patch), mem_pos
-        was_training = net.training
-        if was_training:
-            net.encoder.eval()
-            net.transf.eval()
-        try:
+        with net._scoring():
             if self._on_device:
                 if self._held > M:       # the ragged last chunk: one more iteration, no tail behind it
-                    self._scan(self._held, 1)
-                    cur, nxt = self._sets[self._cur], self._sets[self._cur ^ 1]
-                    hip.stream_commit([(cur[0], self._held, None, nxt[0]), (cur[1], self._held, None, nxt[1]),
-                                       (cur[2], self._held, None, nxt[2])], self._sel, M, self._held, self._held)
-                    self._cur ^= 1
-                    self._held = M
-                    self.iterations += 1
+                    self._advance(1, self._held)
                 patch, emb, ids, _ = self._sets[self._cur]
                 mem_patch, mem_emb, mem_idx = patch[:, :M].clone(), emb[:, :M].clone(), ids[:, :M].clone()
             else:
@@ -482,10 +463,6 @@ class IPSStream:
             mem_pos = net._take(net.pos_enc.expand(B, -1, -1), mem_idx) if net.use_pos else None
             if u8:                       # the M selected patches leave as float32
                 mem_patch = net._dequant(mem_patch)
-        finally:
-            if was_training:
-                net.encoder.train()
-                net.transf.train()
         self._close(mem_idx)
         net.last_mem_idx, net._mem_emb = mem_idx, mem_emb
         return mem_patch, mem_pos
