@@ -96,7 +96,10 @@ extern "C" {
  *         loop on logits that sit in a candidate table of fixed capacity, and the launch that carries a stream's state
  *         (the m winners in rank order, then the not yet scored tail) forward without joining or copying the piece;
  *         ipsx_stream_commit_view - that launch for a stream fed pixel-row bands of whole images: the piece of the patch
- *         table is read out of the images through an ipsx_patch_view, no patch tensor exists */
+ *         table is read out of the images through an ipsx_patch_view, no patch tensor exists;
+ *         ipsx_order_index, ipsx_trunk_stream_indexed, ipsx_ips_call_run_ordered (+ struct ipsx_call_order) - a shuffle
+ *         index on the one-call route: the launch that composes a permutation into flat int32 row numbers, the one-image
+ *         trunk stream reading its patches through such an index, and ipsx_ips_call_run with both inside it */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -445,6 +448,14 @@ int ipsx_trunk_stream_supported(const ipsx_trunk* t, int d, int r);
 int ipsx_trunk_stream(const ipsx_trunk* t, const float* patches, int64_t n_patch, float* emb, const float* pos,
                       const float* v_packed, int r, float* logits, int32_t* ctl, int32_t* ready, int workgroups,
                       int quad_pulls, void* stream);
+/* 3.06: ipsx_trunk_stream reading patch index[j] of `patches` (src_patches of them, float32) where it reads patch j;
+ * everything else (emb, pos, logits, ctl, ready: in OUTPUT numbering) as there - the bits of ipsx_trunk_stream on the
+ * gathered tensor patches[index].  index == NULL is ipsx_trunk_stream.  The tiles read index[j] as it is: every entry must
+ * lie in [0, src_patches) (ipsx_order_index composes such an index from any permutation).  Refused before the launch: what
+ * ipsx_trunk_stream refuses, src_patches < 1, an index with n_patch > 0x7FFFFFF0. */
+int ipsx_trunk_stream_indexed(const ipsx_trunk* t, const float* patches, const int32_t* index, int64_t src_patches,
+                              int64_t n_patch, float* emb, const float* pos, const float* v_packed, int r,
+                              float* logits, int32_t* ctl, int32_t* ready, int workgroups, int quad_pulls, void* stream);
 
 /* The projector AND the logits of one slide as ONE persistent launch that feeds ipsx_scan_persistent row by row
  * (reference: the projector of architecture/ips_net.py:60-66 applied chunk by chunk in IPSNet.ips :213-241, and
@@ -736,6 +747,25 @@ typedef struct ipsx_ips_call {
 } ipsx_ips_call;
 int ipsx_ips_call_run(const ipsx_ips_call* c);
 int ipsx_ips_call_elapsed(int slot, float* ms);
+
+/* 3.06: a permutation as the flat row index the row-indexed producers read through, ONE launch:
+ * index[bi * n + j] = bi * n + clamp(order[bi * order_bstride + j], 0, n - 1);  order: (b or 1, n) int64 on the device,
+ * order_bstride = n, or 0 for one permutation shared by every image; b * n <= 0x7FFFFFF0.  The clamp keeps whatever reads
+ * through the index inside image bi's rows, whatever the caller handed in. */
+int ipsx_order_index(const int64_t* order, int64_t order_bstride, int b, int64_t n, int32_t* index, void* stream);
+
+/* 3.06: ipsx_ips_call_run for a selection on a permuted NUMBERING of the patches (a shuffle applied as addressing).
+ * c->x and c->src are the UNSHUFFLED tensor; c->pos, c->pos_table, c->logits, c->emb, c->mem_idx are in shuffled
+ * numbering.  The call enqueues what ipsx_ips_call_run enqueues, with ipsx_order_index behind the fill of the control
+ * words - in front of the loop's launch: nothing sits between that and its producer's -, the producer reading through the
+ * index (ipsx_trunk_stream_indexed | ipsx_projector_stream_indexed) and ipsx_ips_finish_indexed as the end of the call.
+ * Refused before any launch: what ipsx_ips_call_run refuses, a null o, o->order or o->index, an order_bstride that is
+ * neither 0 nor c->n. */
+typedef struct ipsx_call_order {
+    const int64_t* order; int64_t order_bstride;   /* (b or 1, n) int64 on the device, as ipsx_ips_finish_indexed takes it */
+    int32_t* index;                                /* workspace, b * n int32 on the device: filled by the call */
+} ipsx_call_order;
+int ipsx_ips_call_run_ordered(const ipsx_ips_call* c, const ipsx_call_order* o);
 
 /* --------------------------------------------------------------- aggregation
  * Replaces Transformer.forward (transformer.py:85-109,122-132,150-152) and the

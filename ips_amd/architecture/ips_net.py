@@ -452,7 +452,7 @@ class IPSNet(nn.Module):
         """The HIP selection pipelines of this net (ips_amd/selection.py), built on first use."""
         if self._selection is None:
             from ..selection import Selection
-            self._selection = Selection(self)
+            self._selection = Selection(self, owned=True)
         return self._selection
 
     def _select_hip(self, patches, pos_enc, order=None):

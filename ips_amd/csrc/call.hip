@@ -4,7 +4,9 @@
 // feature slides (config/camelyon_config.yml).  The pieces are the library's own entry points - fill, the resident loop on
 // the side stream (ipsx_scan_persistent_ws), the gate, the producer (ipsx_trunk_stream | ipsx_projector_stream), the
 // conditional recovery launch (ipsx_scan_range_if_ws), the end of the call (ipsx_ips_finish) - and the two cross-stream
-// hand-overs between them.  Enqueued from Python they cost ~12 ctypes calls, two torch event objects and ~170 us of host
+// hand-overs between them.  With an order (ipsx_ips_call_run_ordered: a shuffle applied as addressing) the flat
+// row index is composed behind the fill (ipsx_order_index), the producers are the row-indexed ones and the end of the call
+// is ipsx_ips_finish_indexed.  Enqueued from Python they cost ~12 ctypes calls, two torch event objects and ~170 us of host
 // time per call, of which ~100 us sit IN FRONT of the producer's launch: a synchronised call of one image was 0.92 ms
 // around a 0.77 ms kernel.  Enqueued here the host's share is one call; and nothing of the interpreter - the
 // garbage collector, the allocator, another thread holding the GIL - can stall the host between the launch of the loop
@@ -59,9 +61,43 @@ DeviceEvents* device_events() {
 
 }  // namespace
 
+namespace ipsx {
+
+// index[bi * n + j] = bi * n + clamp(order[bi * bstride + j], 0, n - 1): a (b or 1, n) int64 permutation as the flat int32 row
+// numbers the row-indexed producers read through.  Grid-stride, one 8-byte load and one 4-byte store per entry; the clamp keeps
+// every reader behind it inside its own image's rows whatever the caller handed in.
+__global__ void __launch_bounds__(256) order_index_kernel(const int64_t* __restrict__ order, int64_t bstride, int64_t n, int64_t total,
+                                                          int32_t* __restrict__ index) {
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += step) {
+        const int64_t bi = t / n, j = t - bi * n;
+        int64_t v = order[bi * bstride + j];
+        v = v < 0 ? 0 : (v > n - 1 ? n - 1 : v);
+        index[t] = (int32_t)(bi * n + v);
+    }
+}
+
+}  // namespace ipsx
+
 using namespace ipsx;
 
-IPSX_API int ipsx_ips_call_run(const ipsx_ips_call* c) {
+IPSX_API int ipsx_order_index(const int64_t* order, int64_t order_bstride, int b, int64_t n, int32_t* index, void* stream) {
+    IPSX_REQUIRE(order && index, "order_index: null pointer");
+    IPSX_REQUIRE(b >= 1 && n >= 1 && (int64_t)b * n <= 0x7FFFFFF0ll, "order_index: %d x %lld rows (flat row numbers are int32)", b, (long long)n);
+    IPSX_REQUIRE(order_bstride == 0 || order_bstride == n, "order_index: order_bstride is n, or 0 for one permutation shared by every image");
+    const int64_t total = (int64_t)b * n;
+    const unsigned grid = (unsigned)std::min<int64_t>(cdiv(total, 256), 2048);
+    order_index_kernel<<<dim3(grid), dim3(256), 0, as_stream(stream)>>>(order, order_bstride, n, total, index);
+    return launched("order_index");
+}
+
+// The one body of ipsx_ips_call_run (o == NULL) and ipsx_ips_call_run_ordered
+static int ips_call_run(const ipsx_ips_call* c, const ipsx_call_order* o) {
+    if (o) {      // (refused before the first runtime call)
+        IPSX_REQUIRE(c, "ips_call: null pointer");
+        IPSX_REQUIRE(o->order && o->index, "ips_call: an order needs the permutation and the index workspace");
+        IPSX_REQUIRE(o->order_bstride == 0 || o->order_bstride == c->n, "ips_call: order_bstride is n, or 0 for one permutation shared by every image");
+    }
     IPSX_REQUIRE(c && c->logits && c->mem_idx && c->words && c->x && c->emb && c->v_packed && c->src && c->mem_patch && c->mem_idx_out,
                  "ips_call: null pointer");
     IPSX_REQUIRE(c->b > 0 && c->n > c->m && c->m > 0 && c->i > 0 && c->h > 0 && c->n_token > 0, "ips_call: bad sizes");
@@ -84,6 +120,8 @@ IPSX_API int ipsx_ips_call_run(const ipsx_ips_call* c) {
     const int64_t zero_words = c->lin ? std::min<int64_t>(c->words_total, 2 * (int64_t)c->b + 1 + (int64_t)ipsx_projector_stream_ctl_zero_words((int64_t)c->b * c->n))
                                       : c->words_total;
     IPSX_TRY(hip_ok(hipMemsetAsync(c->words, 0, (size_t)zero_words * sizeof(int32_t), main), "fill"));
+    // the index is composed BEFORE the loop is launched: nothing sits between the loop's launch and its producer's
+    if (o) IPSX_TRY(ipsx_order_index(o->order, o->order_bstride, c->b, c->n, o->index, main));
     IPSX_TRY(hip_ok(hipEventRecord(ev->fork, main), "event"));
     IPSX_TRY(hip_ok(hipStreamWaitEvent(side, ev->fork, 0), "wait"));
     const unsigned long long h0 = host_ns();
@@ -120,7 +158,14 @@ IPSX_API int ipsx_ips_call_run(const ipsx_ips_call* c) {
         }
         IPSX_TRY_JOINED(hip_ok(hipEventRecord(ev->t0[slot], main), "timing event"));
     }
-    if (c->trunk)
+    if (o && c->trunk)
+        IPSX_TRY_JOINED(ipsx_trunk_stream_indexed(c->trunk, static_cast<const float*>(c->x), o->index, c->n, c->n, c->emb, c->pos, c->v_packed,
+                                                  c->r, c->logits, ctl, ready, c->workgroups, c->quad_pulls, main));
+    else if (o)
+        IPSX_TRY_JOINED(ipsx_projector_stream_indexed(c->lin, static_cast<const float*>(c->x), o->index, (int64_t)c->b * c->n,
+                                                      (int64_t)c->b * c->n, c->n, c->ln_eps, c->emb, c->v_packed, c->r, c->logits, ctl, ready,
+                                                      c->workgroups, c->short_first, main));
+    else if (c->trunk)
         IPSX_TRY_JOINED(ipsx_trunk_stream(c->trunk, static_cast<const float*>(c->x), c->n, c->emb, c->pos, c->v_packed, c->r, c->logits, ctl,
                                           ready, c->workgroups, c->quad_pulls, main));
     else
@@ -140,8 +185,19 @@ IPSX_API int ipsx_ips_call_run(const ipsx_ips_call* c) {
     // a loop that gave up waiting is redone here, in the same call (a no-op otherwise)
     IPSX_TRY(ipsx_scan_range_if_ws(c->logits, c->b, c->n, c->m, c->i, c->h, c->n_token, 0, n_iter, c->mem_idx, nullptr, tie, status, 1,
                                    c->scan_workspace, c->scan_workspace_bytes, main));
+    if (o)       // the patch rows come from the UNSHUFFLED tensor through the permutation; everything else is in the loop's numbering
+        return ipsx_ips_finish_indexed(c->src, c->src_row_bytes, c->src_bstride_rows, c->n, c->pos_table, c->pos_row_bytes,
+                                       c->pos_bstride_rows, c->mem_idx, o->order, o->order_bstride, c->b, c->m, c->mem_patch, c->mem_pos,
+                                       c->mem_idx_out, status, c->status_host, main);
     return ipsx_ips_finish(c->src, c->src_row_bytes, c->src_bstride_rows, c->n, c->pos_table, c->pos_row_bytes, c->pos_bstride_rows,
                            c->mem_idx, c->b, c->m, c->mem_patch, c->mem_pos, c->mem_idx_out, status, c->status_host, main);
+}
+
+IPSX_API int ipsx_ips_call_run(const ipsx_ips_call* c) { return ips_call_run(c, nullptr); }
+
+IPSX_API int ipsx_ips_call_run_ordered(const ipsx_ips_call* c, const ipsx_call_order* o) {
+    IPSX_REQUIRE(o, "ips_call_run_ordered: no order (ipsx_ips_call_run is the plain call)");
+    return ips_call_run(c, o);
 }
 
 IPSX_API int ipsx_ips_call_elapsed(int slot, float* ms) {

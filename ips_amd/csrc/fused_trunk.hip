@@ -1655,12 +1655,14 @@ int fused_trunk_encode_parts(const ipsx_trunk* t, const PatchSrc& src, int64_t n
 }
 
 // One image through the fused trunk as ONE persistent launch that feeds a resident selection loop (fused_trunk_stream_kernel,
-// fused_trunk_pair.h).  workgroups <= 0: one per compute unit but the loop's and a few to spare.
+// fused_trunk_pair.h).  workgroups <= 0: one per compute unit but the loop's and a few to spare.  index (or NULL): patch j of
+// the stream is patch index[j] of `patches` (the tiles' own index read; outputs and publication stay in j).
 int fused_trunk_stream(const ipsx_trunk* t, const float* patches, int64_t n, float* emb, const float* pos, const float* v_packed,
-                       int r, float* logits, int32_t* ctl, int32_t* ready, int workgroups, int quad_pulls, hipStream_t s) {
+                       int r, float* logits, int32_t* ctl, int32_t* ready, int workgroups, int quad_pulls, hipStream_t s,
+                       const int32_t* index) {
     if (t->precision != 0 || t->patch_dtype != 0) return fail(IPSX_EINVAL, "trunk_stream: the exact fp32 trunk only");
     TrunkStreamArgs a;
-    a.f = fused_args(t, PatchSrc{patches, nullptr, nullptr, nullptr, 0}, n, emb, false);
+    a.f = fused_args(t, PatchSrc{patches, nullptr, nullptr, index, 0}, n, emb, false);
     a.pos = pos; a.vp = v_packed; a.R = r; a.logits = logits; a.ctl = ctl; a.ready = ready;
     a.n_pairs = (unsigned)cdiv(n, 2);
     // Four patches per pull run at the trunk's full rate (0.29 ms per pull at one workgroup per unit), two per pull at 0.84 of

@@ -73,7 +73,8 @@ int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb
 int fused_trunk_encode_parts(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, const int64_t* part_end, int parts,
                              int* done, hipStream_t s);
 int fused_trunk_stream(const ipsx_trunk* t, const float* patches, int64_t n, float* emb, const float* pos, const float* v_packed,
-                       int r, float* logits, int32_t* ctl, int32_t* ready, int workgroups, int quad_pulls, hipStream_t s);
+                       int r, float* logits, int32_t* ctl, int32_t* ready, int workgroups, int quad_pulls, hipStream_t s,
+                       const int32_t* index = nullptr);
 // trunk.hip: a source of `n` patches against a trunk, once per entry (`what`: the entry's name in the message; `fused`:
 // fused_trunk_supported(t))
 int patch_src_check(const ipsx_trunk* t, const PatchSrc& src, int64_t n, bool fused, const char* what);

@@ -356,3 +356,16 @@ IPSX_API int ipsx_trunk_stream(const ipsx_trunk* t, const float* patches, int64_
     return ipsx::fused_trunk_stream(t, patches, n_patch, emb, pos, v_packed, r, logits, ctl, ready, workgroups, quad_pulls,
                                     ipsx::as_stream(stream));
 }
+
+// 3.06: the stream reading patch index[j] of `patches` (src_patches of them) where it reads patch j.  The tiles read the
+// index as it is: whoever composes it keeps it inside [0, src_patches) (ipsx_order_index clamps).
+IPSX_API int ipsx_trunk_stream_indexed(const ipsx_trunk* t, const float* patches, const int32_t* index, int64_t src_patches,
+                                       int64_t n_patch, float* emb, const float* pos, const float* v_packed, int r, float* logits,
+                                       int32_t* ctl, int32_t* ready, int workgroups, int quad_pulls, void* stream) {
+    IPSX_REQUIRE(t && patches && emb && v_packed && logits && ctl && ready && n_patch > 0, "trunk_stream_indexed: bad arguments");
+    IPSX_REQUIRE(src_patches >= 1, "trunk_stream_indexed: a source of %lld patches", (long long)src_patches);
+    IPSX_REQUIRE(!index || n_patch <= 0x7FFFFFF0ll, "trunk_stream_indexed: %lld patches through an int32 index", (long long)n_patch);
+    IPSX_REQUIRE(ipsx_trunk_stream_supported(t, 128, r), "trunk_stream_indexed: the fused fp32 1x32x32 trunk with 128 features and at most 32 logits per patch");
+    return ipsx::fused_trunk_stream(t, patches, n_patch, emb, pos, v_packed, r, logits, ctl, ready, workgroups, quad_pulls,
+                                    ipsx::as_stream(stream), index);
+}

@@ -164,6 +164,12 @@ class IpsCall(C.Structure):
                 ("timing_slot", C.c_int), ("stream", C.c_void_p), ("side_stream", C.c_void_p)]
 
 
+class IpsCallOrder(C.Structure):
+    """include/ipsx.h ``ipsx_call_order``: the permutation an ``ipsx_ips_call_run_ordered`` selects through, and the
+    workspace the call composes its flat row index in."""
+    _fields_ = [("order", C.c_void_p), ("order_bstride", C.c_int64), ("index", C.c_void_p)]
+
+
 class StreamTable(C.Structure):
     """include/ipsx.h ``ipsx_stream_table``: one table of a stream's state as ``ipsx_stream_commit`` moves it."""
     _fields_ = [("held", C.c_void_p), ("held_rows", C.c_int64), ("held_bstride_rows", C.c_int64),
@@ -348,6 +354,10 @@ _EXPORTS = {
                                    C.c_int64, C.c_int64, C.c_void_p]),
     "ipsx_ips_call_run": (C.c_int, [C.POINTER(IpsCall)]),
     "ipsx_ips_call_elapsed": (C.c_int, [C.c_int, C.POINTER(C.c_float)]),
+    "ipsx_ips_call_run_ordered": (C.c_int, [C.POINTER(IpsCall), C.POINTER(IpsCallOrder)]),
+    "ipsx_order_index": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ipsx_trunk_stream_indexed": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ipsx_ips_finish": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int,
                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ipsx_ips_finish_indexed": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
@@ -1019,6 +1029,21 @@ def ips_finish(src, pos, idx_buf, status, status_host, order=None):
     _ck(lib().ipsx_ips_finish(_p(src), row_bytes, N if src.shape[0] > 1 else 0, N, _p(pos), pos_bytes, pos_bs, _p(idx_buf), B, M,
                               _p(out), _p(out_pos), _p(idx), _p(status), _p(status_host), _stream()), "ipsx_ips_finish")
     return idx, out, out_pos
+
+
+def order_index(order, B, N, out=None):
+    """``order`` ((B or 1, N) int64, contiguous, on the device) -> (B, N) int32 flat row numbers
+    ``b * N + clamp(order[b, j], 0, N - 1)`` - what the row-indexed producers read through - in ONE launch
+    (``ipsx_order_index``); ``out``: B * N int32 on the same device."""
+    if order.dtype != torch.int64 or order.dim() != 2 or order.shape[1] != N or order.shape[0] not in (1, B) or \
+            not order.is_contiguous() or not order.is_cuda:
+        raise ValueError("order must be a contiguous (B or 1, N) int64 tensor on the device")
+    if out is None:
+        out = torch.empty((B, N), dtype=torch.int32, device=order.device)
+    elif out.dtype != torch.int32 or out.numel() != B * N or not out.is_contiguous() or out.device != order.device:
+        raise ValueError("out must be B * N contiguous int32 on the order's device")
+    _ck(lib().ipsx_order_index(_p(order), N if order.shape[0] > 1 else 0, B, N, _p(out), _stream()), "ipsx_order_index")
+    return out.view(B, N)
 
 
 # ------------------------------------------------------------------ image -> patches

@@ -9,7 +9,7 @@ import os
 
 import torch
 
-from .hip import (lib, _ck, _p, _f32, _stream, _patches, PatchSource, _PATCH_DTYPES, Conv, Block, Trunk, precision, dedup_blank, weights_generation)
+from .hip import (lib, _ck, _p, _f32, _stream, _patches, PatchSource, PatchView, _PATCH_DTYPES, Conv, Block, Trunk, precision, dedup_blank, weights_generation)
 
 
 # ------------------------------------------------------------------ encoder plan
@@ -280,6 +280,13 @@ class EncoderPlan:
             out = torch.empty((n, self.d_out), dtype=torch.float32, device=src.device)
         if n == 0:
             return out
+        if index is not None and not src.is_view and not L.ipsx_trunk_kernel(C.byref(t)).startswith(b"fused"):
+            # a layer-by-layer trunk: its LDS-staging stems take an index list through a view - the patch tensor as
+            # src.count images of ONE patch each, grid patch p = patch p
+            view = self._rows_view(src.shape)
+            if not L.ipsx_trunk_view_supported(C.byref(t), C.byref(view.struct)):
+                raise ValueError("this encoder's stem takes no index list (EncoderPlan.index_list_supported)")
+            src = PatchSource(images=src.patches.view(-1, *src.shape[-3:]), view=view, table=src.table)
         tr, vs = C.byref(t), C.byref(src.view.struct) if src.is_view else None
         tab, base = _p(src.table), src.base
         if parts is not None:
@@ -349,6 +356,20 @@ class EncoderPlan:
         run(0, n, self._workspace(nb, src.device), nb)
         return out
 
+    @staticmethod
+    def _rows_view(patch_shape):
+        """A (..., C, h, w) patch tensor as a view: its patches are images of one patch each."""
+        c, h, w = (int(v) for v in patch_shape[-3:])
+        return PatchView((int(torch.Size(patch_shape[:-3]).numel()), c, h, w), (h, w), (h, w))
+
+    def index_list_supported(self, patch_shape):
+        """Does ``encode_source`` take an index list into a patch tensor of this (..., C, h, w)?  The fused 1x32x32 trunk
+        (``fused``), and the layer-by-layer trunks whose stem stages its patch into LDS (1x50x50, 3x100x100, exact fp32):
+        they read the list as they read a view's.  The generic stem (``conv_any_kernel``) takes none."""
+        if not self.is_image:
+            return False
+        return self.fused(patch_shape) or self.view_supported(self._rows_view(patch_shape))
+
     # ---- the entry points of old, each a source and the one call
     def encode_indexed(self, flat, index, table=None, parts=None):
         """flat (P, C, h, w) contiguous on the GPU (uint8: with its ``table`` (C, 256)), index (n,) int32 -> (n, D)
@@ -401,16 +422,25 @@ class EncoderPlan:
             return False
         return bool(lib().ipsx_trunk_stream_supported(C.byref(self.trunk), int(D), int(R)))
 
-    def image_stream(self, x, pos, vq, R, emb, logits, ctl, ready, workgroups=0, quad_pulls=-1):
+    def image_stream(self, x, pos, vq, R, emb, logits, ctl, ready, workgroups=0, quad_pulls=-1, index=None):
         """Trunk + logits of ONE image's patches ``x`` (P, 1, 32, 32) as one persistent launch that advances ``ready`` (the
         progress word of ``scan_persistent``) as patches complete: ``emb`` (P, 128) and ``logits`` (P, R) are the outputs,
         ``pos`` (P, 128) or None is added to the embeddings for the logits, ``ctl`` =
-        ``torch.zeros(image_stream_ctl_words(P), int32)`` zeroed before every call, ``vq`` the folded query."""
+        ``torch.zeros(image_stream_ctl_words(P), int32)`` zeroed before every call, ``vq`` the folded query.
+        ``index`` (n int32 patch numbers inside ``x``, every one in [0, P)): patch j of the stream is ``x[index[j]]`` -
+        the bits of ``image_stream(x[index], ...)``, outputs and ``pos`` in j (``ipsx_trunk_stream_indexed``)."""
         self._refresh()
         x = _patches(x)
         self._describe(x.shape)
         if pos is not None and (pos.stride(-1) != 1 or pos.stride(-2) != pos.shape[-1]):
             pos = pos.contiguous()
+        if index is not None:
+            if index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous() or index.device != x.device:
+                raise ValueError("index must be a contiguous 1-d int32 tensor on the patches' device")
+            _ck(lib().ipsx_trunk_stream_indexed(C.byref(self.trunk), _p(x), _p(index), x.shape[0], index.numel(), _p(emb), _p(pos),
+                                                _p(vq), int(R), _p(logits), _p(ctl), _p(ready), int(workgroups), int(quad_pulls),
+                                                _stream()), "ipsx_trunk_stream_indexed")
+            return emb
         _ck(lib().ipsx_trunk_stream(C.byref(self.trunk), _p(x), x.shape[0], _p(emb), _p(pos), _p(vq), int(R), _p(logits),
                                     _p(ctl), _p(ready), int(workgroups), int(quad_pulls), _stream()), "ipsx_trunk_stream")
         return emb

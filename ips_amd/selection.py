@@ -30,6 +30,7 @@ import ctypes as C
 import gc
 import math
 import os
+import weakref
 
 import torch
 
@@ -57,6 +58,19 @@ def _env_on(name):
     return os.environ.get(name, "1") != "0"
 
 
+# IPSX_NATIVE_ORDER when the environment does not set it.  Off: measured against the launches one by one, in one process,
+# the ordered one call of a lone slide is 0.006 - 0.016 ms faster, inside the quartiles of either (DESIGN 2.1,
+# profiles/shuffle_routes_native_order_ab.json) - not the margin that was asked of it
+NATIVE_ORDER_DEFAULT = "0"
+
+
+def _native_order_on():
+    """Feature slides that select through a shuffle index inside the library's one call (``ipsx_ips_call_run_ordered``,
+    DESIGN 2.1): ``IPSX_NATIVE_ORDER=1``.  Otherwise such a call enqueues its launches one by one.  (One image on the
+    fused trunk takes the ordered one call either way: its alternative is the copy.)"""
+    return os.environ.get("IPSX_NATIVE_ORDER", NATIVE_ORDER_DEFAULT) == "1"
+
+
 class Selection:
     """The selection pipelines of one ``IPSNet`` (buffers and streams are kept between calls of the same shape: a buffer
     that a side stream has used cannot be recycled by the allocator until that stream's work is known to be over, and
@@ -65,8 +79,10 @@ class Selection:
     OVERLAP_PARTS = 4
     LAZY_SLAB_BYTES = 48 << 20
 
-    def __init__(self, net):
-        self.net = net
+    def __init__(self, net, owned=False):
+        # ``owned``: built by ``IPSNet.selection`` and kept by the net - then the way back is a weak reference, so that a net
+        # nobody holds any more releases its call buffers at once and not when the cyclic collector next runs
+        self._net = weakref.ref(net) if owned else (lambda: net)
         self._bufs = {}
         self._side = None
         self._copy = None
@@ -79,16 +95,34 @@ class Selection:
         self.timing_hook = None                    # callable(rows) -> slot of a library-owned event pair around the producer, or None
         self._part_index = None
         self._order = None                         # the permutation this call selects through (an index, not a copy), or None
-        self._flat = None                          # ... as flat int32 row numbers b * N + perm[b, j], (B, N)
+        self._order_bn = None                      # ... its call's (B, N)
+        self._flat_made = None                     # ... as flat int32 row numbers b * N + perm[b, j], (B, N): made on first use
         self._flat_key = None
         self._flat_base = None
         self._part_map = None                      # parts_with_ranges: where the parts' index lists lie in the flat (B, N) index
+        self._one_piece_index = {}                 # index_supported: does a layered trunk's stem take an index list, per patch shape
         self.index_calls = 0                       # select() calls that read the patches through a shuffle index
         self.view_calls = 0                        # select_view() calls: the patches read through a patch-grid view
+        self.native_calls = 0                      # calls the library enqueued whole (ipsx_ips_call_run*)
+        self.native_ordered_calls = 0              # ... of which through a shuffle index (ipsx_ips_call_run_ordered)
 
     # ------------------------------------------------------------------ small helpers
+    @property
+    def net(self):
+        return self._net()
+
     def plan(self):
         return self.net.plan
+
+    @property
+    def _flat(self):
+        """The call's shuffle index as flat int32 row numbers (B, N), or None - composed on FIRST use: the ordered one-call
+        route never asks (the library composes its own, ``ipsx_order_index``)."""
+        if self._order is None:
+            return None
+        if self._flat_made is None:
+            self._flat_made = self.flat_index(self._order, *self._order_bn)
+        return self._flat_made
 
     def status_mirror(self):
         """The pinned host mirror of a resident loop's status word, made on first use."""
@@ -213,7 +247,10 @@ class Selection:
         gate, producer (the fused trunk for one image / the projector for feature slides), conditional recovery, and the end
         of the call (both gathers, indices, status word to the host).  Same kernels and results as the launches one by one
         (``IPSX_NATIVE_CALL=0``); the host's share of a call is one ctypes call, and nothing of the interpreter sits between
-        the loop's launch and its producer's.  -> mem_idx (fresh); ``finish`` hands out (mem_idx, mem_patch, mem_pos)."""
+        the loop's launch and its producer's.  A call that selects through a shuffle index (``self._order``): the same one
+        call with the order inside it (``ipsx_ips_call_run_ordered``: ``patches`` is the unshuffled tensor, the flat index is
+        composed by the library into a workspace kept with the pipeline's buffers, everything else is in shuffled
+        numbering).  -> mem_idx (fresh); ``finish`` hands out (mem_idx, mem_patch, mem_pos)."""
         net, plan = self.net, self.plan()
         B, N = patches.shape[:2]
         dev = patches.device
@@ -264,7 +301,19 @@ class Selection:
         call.mem_patch, call.mem_idx_out = mem_patch.data_ptr(), mem_idx.data_ptr()
         call.timing_slot = self.timing_hook(B * N) if self.timing_hook is not None else -1
         call.stream = hip._stream().value
-        hip._ck(hip.lib().ipsx_ips_call_run(C.byref(call)), "ipsx_ips_call_run")
+        order = self._order
+        if order is not None:
+            if order.dtype != torch.int64 or order.dim() != 2 or order.shape[1] != N or order.shape[0] not in (1, B) or \
+                    not order.is_contiguous() or order.device != dev:
+                raise ValueError("order must be a contiguous (B or 1, N) int64 tensor on the patches' device")
+            (index_ws,) = self.buffers(name + ".order", (B, N, str(dev)),
+                                       lambda: (torch.empty((B * N,), dtype=torch.int32, device=dev),))
+            o = hip.IpsCallOrder(order.data_ptr(), N if order.shape[0] > 1 else 0, index_ws.data_ptr())
+            hip._ck(hip.lib().ipsx_ips_call_run_ordered(C.byref(call), C.byref(o)), "ipsx_ips_call_run_ordered")
+            self.native_ordered_calls += 1
+        else:
+            hip._ck(hip.lib().ipsx_ips_call_run(C.byref(call)), "ipsx_ips_call_run")
+        self.native_calls += 1
         tie, status = zeroed[:B], zeroed[2 * B:2 * B + 1]
         self.scan_status = status
         hip.scan.last_tie = tie
@@ -302,9 +351,9 @@ class Selection:
         net = self.net
         net._device_patches = None
         self._done = self._unfinished = None       # (whatever a call that raised half-way left behind)
-        self._order = self._flat = None
+        self._order = self._order_bn = self._flat_made = None
         if order is not None:
-            self._order, self._flat = order, self.flat_index(order, patches.shape[0], patches.shape[1])
+            self._order, self._order_bn = order, (patches.shape[0], patches.shape[1])
             self.index_calls += 1
         if not torch.is_tensor(patches):
             # the one-image stream and the native one-call route read patch tensors: a view takes the parts (every part an
@@ -332,18 +381,29 @@ class Selection:
 
     def index_supported(self, patches):
         """Can the schedule ``select`` picks for these patches read them through a shuffle index?  Device-resident,
-        contiguous patches on: every feature pipeline (the row-indexed projector kernels) and the fused 1x32x32 trunk in
-        parts (its index list).  Not: lazy patches, the one-image trunk stream, the small-batch split, layer-by-layer trunks,
-        blank-patch dedup (those shuffle by copy).  uint8 patches: where float32 patches are (the index list
-        addresses bytes; the gather at the end of the call reads them through the order, then dequantises)."""
+        contiguous patches on: every feature pipeline (the row-indexed projector kernels), the fused 1x32x32 trunk in
+        parts (its index list) and as the one-image stream (the stream's tiles read the same list), and a layer-by-layer
+        trunk in one piece whose stem takes an index list (``EncoderPlan.index_list_supported``).  Not: lazy patches, the
+        small-batch split and the fused trunk in one piece, layer-by-layer trunks in parts, blank-patch dedup (DESIGN 2.1:
+        those shuffle by copy).  uint8 patches: where float32 patches are (the index list addresses bytes; the gather at
+        the end of the call reads them through the order, then dequantises) - the one-image stream reads float32."""
         net = self.net
         # (a hip.PatchSource is device-resident and contiguous by construction)
         if (torch.is_tensor(patches) and not (patches.is_cuda and patches.is_contiguous())) or hip.dedup_blank() or net.encoder.training:
             return False
         if not net.is_image:
             return patches.dim() == 3 and patches.dtype in (torch.float32, torch.float16, torch.bfloat16)
-        if self.can_stream_image(patches) or not self.can_overlap(patches):
-            return False
+        if self.can_stream_image(patches):
+            return patches.dtype == torch.float32
+        if not self.can_overlap(patches):
+            # one piece (``slabs``): a layered trunk reads float32 / uint8 patches through the list where its stem takes one;
+            # the fused trunk's small batches keep the copy
+            # (asked once per patch shape: the answer is the trunk's geometry, and asking walks the plan's weights)
+            key = (tuple(patches.shape[-3:]), hip.precision(), os.environ.get("IPSX_NO_FUSED"))
+            if key not in self._one_piece_index:
+                plan = self.plan()
+                self._one_piece_index[key] = not plan.fused(patches.shape) and plan.index_list_supported(patches.shape)
+            return patches.dtype in (torch.float32, torch.uint8) and self._one_piece_index[key]
         B, N = patches.shape[:2]
         if B * N < self.small_batch_limit(patches.device) and self.n_iter(N) < 100:
             return False
@@ -530,9 +590,10 @@ class Selection:
         # (candidate sets beyond the LDS - the shipped M = I = 5000 - run as a TEAM of workgroups per slide, csrc/scan_large_team.h:
         #  each of them keeps a compute unit)
         team = hip.scan_workgroups_per_image(B, M, I, ca.H, ca.n_token)
-        # (a shuffle index: the launches one by one - the library's one-call path carries no order)
-        fidx = self._flat.view(-1) if self._flat is not None else None
-        if streamed and patches.dtype == torch.float32 and fidx is None and self.native_ok(patches, None):
+        # (a shuffle index rides inside the library's one call, which composes its own flat index, under IPSX_NATIVE_ORDER=1;
+        #  by default such a call stays on the launches one by one: the one call measured no faster)
+        ordered = self._order is not None
+        if streamed and patches.dtype == torch.float32 and (not ordered or _native_order_on()) and self.native_ok(patches, None):
             free = hip.device_geometry(dev).cus - loops * team
             wgs = int(os.environ.get("IPSX_CAM_WGS", "0")) or free
             # (a team's iteration is ~55 us and the last TWO of them run behind the producer - the rows of the last chunk all
@@ -541,6 +602,7 @@ class Selection:
             short = int(os.environ.get("IPSX_CAM_SHORT", "0")) or ((-19 if team > 1 else -11) if B == 1 else -1)
             return self.native_call("features", patches, None, logits, mem_idx_buf, zeroed, emb_buf, scan_ws, loops, wgs,
                                     short_first=short)
+        fidx = self._flat.view(-1) if ordered else None       # (composed here: in front of the loop's launch)
         with _no_gc_pause():                       # from the loop's launch to its producers': no host stall
             tie, ready, status, ctl = self.persistent_begin(logits, mem_idx_buf, zeroed, B, dev, loops, scan_ws,
                                                             zero_words=2 * B + 1 + plan.stream_ctl_zero_words(B * N))
@@ -613,13 +675,16 @@ class Selection:
                      torch.empty((1, M), dtype=torch.int64, device=dev),
                      torch.empty((1, N, net.D), dtype=torch.float32, device=dev),
                      torch.zeros((3 + plan.image_stream_ctl_words(N),), dtype=torch.int32, device=dev)))
+        ordered = self._order is not None           # (a shuffle index: the tiles read patch index[j] where they read patch j)
         if patches.dtype == torch.float32 and self.native_ok(patches, pos_enc if net.use_pos else None):
             tp = (pos_enc[0] if pos_enc[0].is_contiguous() else pos_enc[0].contiguous()) if net.use_pos else None
             return self.native_call("image", patches, pos_enc if net.use_pos else None, logits, mem_idx_buf, zeroed, emb_buf, None, 0, 0,
                                     trunk_pos=tp, quad_pulls=-1)
+        fidx = self._flat.view(-1) if ordered else None       # (composed here: in front of the loop's launch)
         with _no_gc_pause():                       # from the loop's launch to its producer's: no host stall
             tie, ready, status, ctl = self.persistent_begin(logits, mem_idx_buf, zeroed, 1, dev)
-            plan.image_stream(patches[0], pos_enc[0] if net.use_pos else None, vq, R, emb_buf[0], logits[0], ctl, ready)
+            plan.image_stream(patches[0], pos_enc[0] if net.use_pos else None, vq, R, emb_buf[0], logits[0], ctl, ready,
+                              index=fidx)
         # (whatever two simultaneous finishers leave to each other is published by the last workgroup out: no launch for it)
         net._emb_parts = [emb_buf]
         return self.persistent_end(logits, mem_idx_buf, tie, status, self.n_iter(N), dev)
@@ -826,7 +891,9 @@ class Selection:
             part = fetch(k)
             if viewed:                             # every grid patch, or those the shuffle index names
                 emb = self.plan().encode_source(part, index=self._flat.reshape(-1) if self._flat is not None else None).view(B, N, -1)
-            elif self._flat is not None:           # (device-resident feature rows, one span) through the shuffle index
+            elif self._order is not None and net.is_image:       # (device-resident patches of a layered trunk, one span: the stem reads the list)
+                emb = self.plan().encode_source(self.source(part), index=self._flat.view(-1)).view(B, N, -1)
+            elif self._order is not None:          # (device-resident feature rows, one span) through the shuffle index
                 emb = self.plan().encode(part.reshape(B * N, -1), index=self._flat.view(-1)).view(B, N, -1)
             else:
                 emb = net._embed(part.reshape(-1, *patches.shape[2:])).view(B, hi - lo, -1)
