@@ -99,7 +99,10 @@ extern "C" {
  *         table is read out of the images through an ipsx_patch_view, no patch tensor exists;
  *         ipsx_order_index, ipsx_trunk_stream_indexed, ipsx_ips_call_run_ordered (+ struct ipsx_call_order) - a shuffle
  *         index on the one-call route: the launch that composes a permutation into flat int32 row numbers, the one-image
- *         trunk stream reading its patches through such an index, and ipsx_ips_call_run with both inside it */
+ *         trunk stream reading its patches through such an index, and ipsx_ips_call_run with both inside it;
+ *         ipsx_trunk_encode_parts_u8, ipsx_trunk_encode_parts_view_u8 - the counted one-launch route on uint8 patches and on
+ *         whole uint8 images: ipsx_trunk_encode_parts / _parts_view with the bytes' staging (the minor number stays: it and
+ *         this block are pinned by the tests of the earlier 3.06 additions) */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -366,6 +369,18 @@ int ipsx_trunk_encode_view_u8(const ipsx_trunk* t, const uint8_t* images, const 
 int ipsx_gather_patches_view_u8(const uint8_t* images, const float* table, const ipsx_patch_view* v,
                                 const int64_t* idx /* (b, m), per image */, int m, float* out /* (b, m, c, ph, pw) */,
                                 void* stream);
+
+/* 3.06: the parts of a call in ONE launch (ipsx_trunk_encode_parts, ipsx_trunk_encode_parts_view) on uint8 patches and on whole
+ * uint8 images: index, emb, part_end, n_parts and done mean what they mean there, patches / images / table / view what they mean
+ * for ipsx_trunk_encode_indexed_u8 and ipsx_trunk_encode_view_u8, and emb is bit for bit theirs on every part's list.  The exact
+ * fp32 fused 1x32x32 trunk only (precision 0, patch_dtype 0), n_parts <= 16, table and - for patches - `patches` 16-byte
+ * aligned (images: any address, the load width 16 / 4 / 1 bytes is picked per launch); anything else: IPSX_EINVAL, nothing
+ * launched. */
+int ipsx_trunk_encode_parts_u8(const ipsx_trunk* t, const uint8_t* patches, const float* table, const int32_t* index,
+                               int64_t n_index, float* emb, const int64_t* part_end, int n_parts, int32_t* done, void* stream);
+int ipsx_trunk_encode_parts_view_u8(const ipsx_trunk* t, const uint8_t* images, const float* table, const ipsx_patch_view* v,
+                                    const int32_t* index, int64_t n_index, float* emb, const int64_t* part_end, int n_parts,
+                                    int32_t* done, void* stream);
 
 /* Same result as ipsx_trunk_encode, with exact blank-patch deduplication (all-zero patches share one
  * embedding in eval mode; ~93 % of Megapixel-MNIST patches): only the non-blank patches and one blank

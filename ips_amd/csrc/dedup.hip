@@ -95,6 +95,16 @@ IPSX_API int ipsx_trunk_encode_parts(const ipsx_trunk* t, const float* patches, 
                                     as_stream(stream));
 }
 
+IPSX_API int ipsx_trunk_encode_parts_u8(const ipsx_trunk* t, const uint8_t* patches, const float* table, const int32_t* index,
+                                        int64_t n_index, float* emb, const int64_t* part_end, int n_parts, int32_t* done,
+                                        void* stream) {
+    IPSX_REQUIRE(t && patches && table && index && emb && part_end && done, "trunk_encode_parts_u8: null pointer");
+    IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_parts_u8: only the fused 1x32x32 trunk is supported");
+    const PatchSrc src{patches, table, nullptr, index, 0};
+    IPSX_TRY(patch_src_check(t, src, n_index, true, "trunk_encode_parts_u8"));
+    return fused_trunk_encode_parts(t, src, n_index, emb, part_end, n_parts, done, as_stream(stream));
+}
+
 IPSX_API size_t ipsx_trunk_dedup_workspace_bytes(const ipsx_trunk* t, int64_t n_patch) {
     if (!t || n_patch <= 0) return 0;
     // nonblank, index, slot (n ints each) + count + the compacted embeddings (n+1 rows of 128 floats)

@@ -1329,6 +1329,16 @@ __global__ __launch_bounds__(512, 1) void fused_trunk_parts_view_kernel(FusedArg
     fused_trunk_body<false, false, true, true>(a, nullptr, nullptr, &pa, &va);
 }
 
+// the counted launch on uint8 patches and on whole uint8 images: the uint8 kernels' staging, the parts' count at the end
+__global__ __launch_bounds__(512, 1) void fused_trunk_parts_u8_kernel(FusedArgs a, PartsArgs pa, const float* table) {
+    fused_trunk_body<false, true, true>(a, nullptr, table, &pa);
+}
+
+__global__ __launch_bounds__(512, 1) void fused_trunk_parts_view_u8_kernel(FusedArgs a, PartsArgs pa, const float* table,
+                                                                          ViewArgs va) {
+    fused_trunk_body<false, true, true, true>(a, nullptr, table, &pa, &va);
+}
+
 #include "fused_trunk_split.h"
 #include "fused_trunk_bf16.h"
 #include "fused_trunk_pair.h"
@@ -1618,12 +1628,14 @@ int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb
 // Every part of a call in ONE launch (ipsx_trunk_encode_parts): list entry j -> emb row j, done[k] += the patches of part k
 // as their workgroups finish.  The eight-patch kernel takes the whole list.  (The pair kernel for the tail, as fused_launch
 // does it, is a second launch: 9.42 against 9.45 ms at 40,000 patches, 0.3 % - not kept)
-// src: float32 patches or a view, with the parts' joined index lists (checked by the entry: patch_src_check)
+// src: float32 or uint8 (src.table) patches, or a view of float32 or uint8 images, with the parts' joined index lists (checked
+// by the entry: patch_src_check)
 int fused_trunk_encode_parts(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, const int64_t* part_end, int parts,
                              int* done, hipStream_t s) {
-    if (t->precision != 0 || t->patch_dtype != 0 || src.table)
-        return fail(IPSX_EINVAL, "trunk_encode_parts: the exact fp32 trunk on float32 patches only (precision %d, patch_dtype %d)",
-                    t->precision, t->patch_dtype);
+    if (t->precision != 0 || t->patch_dtype != 0)
+        return fail(IPSX_EINVAL, "trunk_encode_parts: the exact fp32 trunk on float32 or uint8 patches only (precision %d, "
+                    "patch_dtype %d)", t->precision, t->patch_dtype);
+    if (!src.index) return fail(IPSX_EINVAL, "trunk_encode_parts: the parts are index lists");
     if (parts < 1 || parts > 16) return fail(IPSX_EINVAL, "trunk_encode_parts: %d parts (1 .. 16)", parts);
     if (n <= 0 || n > 0x7FFFFFF0ll) return fail(IPSX_EINVAL, "trunk_encode_parts: %lld patches", (long long)n);
     PartsArgs pa;
@@ -1643,9 +1655,22 @@ int fused_trunk_encode_parts(const ipsx_trunk* t, const PatchSrc& src, int64_t n
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_parts_view_kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_parts_u8_kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_parts_view_u8_kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS);
         attr_set = true;
     }
     const dim3 grid((unsigned)cdiv(n, 8));
+    // the storage kinds differ in the kernels' last arguments only (the table, the view, both, nothing), as in fused_launch
+    if (src.table && src.view) {                                      // whole uint8 images
+        fused_trunk_parts_view_u8_kernel<<<grid, dim3(512), FUSED_LDS, s>>>(a, pa, src.table, fused_view_args(src));
+        return launched("fused_trunk_parts_view_u8");
+    }
+    if (src.table) {                                                  // uint8 patches
+        fused_trunk_parts_u8_kernel<<<grid, dim3(512), FUSED_LDS, s>>>(a, pa, src.table);
+        return launched("fused_trunk_parts_u8");
+    }
     if (src.view) {                                                   // whole images, the list: grid patches
         fused_trunk_parts_view_kernel<<<grid, dim3(512), FUSED_LDS, s>>>(a, pa, fused_view_args(src));
         return launched("fused_trunk_parts_view");

@@ -332,6 +332,16 @@ IPSX_API int ipsx_trunk_encode_parts_view(const ipsx_trunk* t, const float* imag
     return fused_trunk_encode_parts(t, src, n_index, emb, part_end, n_parts, done, as_stream(stream));
 }
 
+IPSX_API int ipsx_trunk_encode_parts_view_u8(const ipsx_trunk* t, const uint8_t* images, const float* table,
+                                             const ipsx_patch_view* v, const int32_t* index, int64_t n_index, float* emb,
+                                             const int64_t* part_end, int n_parts, int32_t* done, void* stream) {
+    IPSX_REQUIRE(t && images && table && v && index && emb && part_end && done, "trunk_encode_parts_view_u8: null pointer");
+    IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_parts_view_u8: the fused fp32 1x32x32 trunk on a valid view of 1x32x32 patches only");
+    const PatchSrc src{images, table, v, index, 0};
+    IPSX_TRY(patch_src_check(t, src, n_index, true, "trunk_encode_parts_view_u8"));
+    return fused_trunk_encode_parts(t, src, n_index, emb, part_end, n_parts, done, as_stream(stream));
+}
+
 IPSX_API int ipsx_trunk_encode_view_u8(const ipsx_trunk* t, const uint8_t* images, const float* table, const ipsx_patch_view* v,
                                        const int32_t* index, int64_t first, int64_t n, float* emb, void* workspace,
                                        size_t workspace_bytes, void* stream) {

@@ -247,6 +247,10 @@ _EXPORTS = {
     "ipsx_gather_patches_view": (C.c_int, [C.c_void_p, C.POINTER(PatchViewStruct), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "ipsx_trunk_encode_view_u8": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.POINTER(PatchViewStruct), C.c_void_p,
                                             C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ipsx_trunk_encode_parts_u8": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                             C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p]),
+    "ipsx_trunk_encode_parts_view_u8": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.POINTER(PatchViewStruct), C.c_void_p,
+                                                  C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p]),
     "ipsx_gather_patches_view_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PatchViewStruct), C.c_void_p, C.c_int, C.c_void_p,
                                               C.c_void_p]),
     "ipsx_trunk_dedup_workspace_bytes": (C.c_size_t, [C.POINTER(Trunk), C.c_int64]),

@@ -260,7 +260,8 @@ class EncoderPlan:
         and from how it is addressed.  An index list: the fused 1x32x32 trunk, or a view on any trunk that reads one.
         ``parts`` = (part_end, done): ``index`` is the index lists of several parts one after the other, ending at the
         list entries ``part_end`` (ints), encoded as ONE launch that counts part k's finished patches into ``done[k]``
-        (int32 on the GPU, zeroed by the caller on this stream) - float32 patches or a view on the exact fp32 fused trunk."""
+        (int32 on the GPU, zeroed by the caller on this stream) - float32 patches, uint8 patches with their table, or a view
+        of float32 or uint8 images, on the exact fp32 fused trunk."""
         self._refresh()
         # the trunk struct describes THIS call's patches: nothing an earlier call or question left in it is read
         t, L = self._describe(src.shape, 0 if src.table is not None else _PATCH_DTYPES[src.dtype]), lib()
@@ -290,10 +291,17 @@ class EncoderPlan:
         tr, vs = C.byref(t), C.byref(src.view.struct) if src.is_view else None
         tab, base = _p(src.table), src.base
         if parts is not None:
-            if index is None or tab.value or src.dtype != torch.float32:
-                raise TypeError("parts=(part_end, done) take float32 patches and the parts' index lists")
+            if index is None or not (src.dtype == torch.float32 or (src.dtype == torch.uint8 and tab.value)):
+                raise TypeError("parts=(part_end, done) take float32 patches, or uint8 patches with their table, and the "
+                                "parts' index lists")
             ends, done = (C.c_int64 * len(parts[0]))(*parts[0]), _p(parts[1])
-            if vs is not None:
+            if tab.value and vs is not None:               # whole uint8 images
+                _ck(L.ipsx_trunk_encode_parts_view_u8(tr, _p(base), tab, vs, _p(index), n, _p(out), ends, len(ends), done,
+                                                      _stream()), "ipsx_trunk_encode_parts_view_u8")
+            elif tab.value:
+                _ck(L.ipsx_trunk_encode_parts_u8(tr, _p(base), tab, _p(index), n, _p(out), ends, len(ends), done, _stream()),
+                    "ipsx_trunk_encode_parts_u8")
+            elif vs is not None:
                 _ck(L.ipsx_trunk_encode_parts_view(tr, _p(base), vs, _p(index), n, _p(out), ends, len(ends), done, _stream()),
                     "ipsx_trunk_encode_parts_view")
             else:

@@ -63,6 +63,13 @@ def _env_on(name):
 # profiles/shuffle_routes_native_order_ab.json) - not the margin that was asked of it
 NATIVE_ORDER_DEFAULT = "0"
 
+# IPSX_ONE_LAUNCH_U8 when the environment does not set it.  Off: the rule was "faster than the parent's uint8 median by more
+# than the parent's own max - min on all three shapes".  16 x 1600x1600 uint8 images met it twice (stride 32: 0.48 / 0.49 ms
+# against 0.11 / 0.13; stride 16: 0.93 / 0.85 against 0.44 / 0.23); 16 x 2,500 uint8 patches missed it in the first of two
+# sessions (0.45 ms against a max - min of 0.49) and met it in the second (0.49 against 0.34) - DESIGN 2.3,
+# profiles/parts_u8_view.json, profiles/uint8_patches{,_parent,_first,_first_parent}.json
+ONE_LAUNCH_U8_DEFAULT = "0"
+
 
 def _native_order_on():
     """Feature slides that select through a shuffle index inside the library's one call (``ipsx_ips_call_run_ordered``,
@@ -376,7 +383,8 @@ class Selection:
         """``select`` on the patches of whole images (B, C, H, W) on the device - float32, or uint8 with their ``table`` -
         read through ``view`` (a ``hip.PatchView`` the plan supports: ``EncoderPlan.view_supported``).  Patch numbers are
         those of the tensor ``hip.patchify`` would make, so ``order``, ``pos_enc`` and ``mem_idx`` mean what they mean in
-        ``select``.  uint8 images take the schedules float32 images take but the one counted launch (``one_launch_ok``)."""
+        ``select``.  uint8 images take the schedules float32 images take - the one counted launch (``one_launch_ok``) under
+        ``IPSX_ONE_LAUNCH_U8=1``."""
         return self.select(hip.PatchSource(images=images, view=view, table=table), pos_enc, order)
 
     def index_supported(self, patches):
@@ -386,7 +394,8 @@ class Selection:
         trunk in one piece whose stem takes an index list (``EncoderPlan.index_list_supported``).  Not: lazy patches, the
         small-batch split and the fused trunk in one piece, layer-by-layer trunks in parts, blank-patch dedup (DESIGN 2.1:
         those shuffle by copy).  uint8 patches: where float32 patches are (the index list addresses bytes; the gather at
-        the end of the call reads them through the order, then dequantises) - the one-image stream reads float32."""
+        the end of the call reads them through the order, then dequantises), the parts' one counted launch
+        (``IPSX_ONE_LAUNCH_U8=1``) included - the one-image stream reads float32."""
         net = self.net
         # (a hip.PatchSource is device-resident and contiguous by construction)
         if (torch.is_tensor(patches) and not (patches.is_cuda and patches.is_contiguous())) or hip.dedup_blank() or net.encoder.training:
@@ -709,11 +718,16 @@ class Selection:
         return [B * e for e in edges[1:]]
 
     def one_launch_ok(self, src, fused, small, vq, P):
-        """Every part of the call as ONE launch of the fused fp32 trunk (``ipsx_trunk_encode_parts``), the parts' logits and
-        iterations let go by wait kernels on the side stream: the exact fp32 trunk (a view's lists serve layered trunks too)
-        on float32 patches, cut by the loop's chunk boundaries (not the small-batch split), where kernels of different
-        streams have been SEEN to run side by side."""
-        return (src is not None and fused and not small and 2 <= P <= 16 and src.dtype == torch.float32 and hip.precision() == "fp32"
+        """Every part of the call as ONE launch of the fused fp32 trunk (``ipsx_trunk_encode_parts`` and its ``_u8`` /
+        ``_view`` / ``_view_u8`` twins), the parts' logits and iterations let go by wait kernels on the side stream: the
+        exact fp32 trunk (a view's lists serve layered trunks too) on float32 patches or images, or - under
+        ``IPSX_ONE_LAUNCH_U8=1`` (``ONE_LAUNCH_U8_DEFAULT``) - on uint8 ones with their table (``hip.PatchSource`` has checked
+        it), cut by the loop's chunk boundaries (not the small-batch split), where kernels of different streams have been
+        SEEN to run side by side."""
+        if src is not None and src.dtype == torch.uint8 and os.environ.get("IPSX_ONE_LAUNCH_U8", ONE_LAUNCH_U8_DEFAULT) == "0":
+            return False
+        return (src is not None and fused and not small and 2 <= P <= 16 and src.dtype in (torch.float32, torch.uint8)
+                and hip.precision() == "fp32"
                 and vq.dtype == torch.float32 and src.count < (1 << 31) - 16
                 and _env_on("IPSX_ONE_LAUNCH") and hip.persistent_ok(src.device))
 

@@ -8,7 +8,10 @@ and the peak of allocated device memory above what was resident before the call.
            residual blocks, ``stem_alone``), and the whole trunk on the same patches for scale
   lazy     ``ips`` on a HOST tensor of the 16 x 2,500 shape, pinned and pageable
 
-    python tools/uint8_patches_bench.py [--reps 30] [--out profiles/uint8_patches.json] [--only NAME]
+    python tools/uint8_patches_bench.py [--reps 30] [--out profiles/uint8_patches.json] [--only NAME] [--repo CHECKOUT]
+
+``--repo``: the checkout to import ``ips_amd`` from (default: this file's) - the same tool on a parent commit's build gives the
+baseline of a comparison; ``max_ms`` - ``min_ms`` of a row is that commit's own run-to-run spread.
 """
 
 import argparse
@@ -21,7 +24,10 @@ import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--repo" in sys.argv[1:-1]:                 # (read here: the imports below are the checkout's)
+    REPO = os.path.abspath(sys.argv[sys.argv.index("--repo") + 1])
+sys.path.insert(0, REPO)
 
 from ips_amd import hip, quant, synth         # noqa: E402
 from ips_amd.architecture import IPSNet       # noqa: E402
@@ -65,7 +71,8 @@ def timed(fn, dev):
 
 def quartiles(v):
     q = statistics.quantiles(v, n=4)
-    return {"median_ms": round(statistics.median(v), 4), "q1_ms": round(q[0], 4), "q3_ms": round(q[2], 4), "min_ms": round(min(v), 4)}
+    return {"median_ms": round(statistics.median(v), 4), "q1_ms": round(q[0], 4), "q3_ms": round(q[2], 4), "min_ms": round(min(v), 4),
+            "max_ms": round(max(v), 4), "spread_ms": round(max(v) - min(v), 4)}
 
 
 def alternate(calls, reps, warmup, dev):
@@ -119,6 +126,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=os.path.join("profiles", "uint8_patches.json"))
     ap.add_argument("--only", default=None)
+    ap.add_argument("--repo", default=REPO, help="checkout to import ips_amd from")
+    ap.add_argument("--label", default="head", help="what the figures belong to, e.g. the commit (stored in the JSON)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     rows = []
@@ -193,7 +202,7 @@ def main():
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as fh:
-            json.dump({"tool": "tools/uint8_patches_bench.py", "device": torch.cuda.get_device_name(dev), "rows": rows}, fh, indent=1)
+            json.dump({"tool": "tools/uint8_patches_bench.py", "label": args.label, "device": torch.cuda.get_device_name(dev), "rows": rows}, fh, indent=1)
             fh.write("\n")
 
 
