@@ -102,7 +102,10 @@ extern "C" {
  *         trunk stream reading its patches through such an index, and ipsx_ips_call_run with both inside it;
  *         ipsx_trunk_encode_parts_u8, ipsx_trunk_encode_parts_view_u8 - the counted one-launch route on uint8 patches and on
  *         whole uint8 images: ipsx_trunk_encode_parts / _parts_view with the bytes' staging (the minor number stays: it and
- *         this block are pinned by the tests of the earlier 3.06 additions) */
+ *         this block are pinned by the tests of the earlier 3.06 additions);
+ *         ipsx_pack_conv_weight_tile16 (+ ipsx_packed_conv_weight_tile16_elems) - the fused 1x32x32 trunk at precision 0 runs
+ *         its three 128 -> 128 convolutions on 16-row tiles and reads their weights in this packing from
+ *         ipsx_conv.w_packed_bf16, which precision 0 did not read before: a caller that left it NULL there is refused */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -145,6 +148,15 @@ size_t ipsx_packed_conv_weight_bf16_bytes(int c_out, int c_in, int kh, int kw);
 int ipsx_pack_conv_weight_bf16(const float* w_oihw, int c_out, int c_in, int kh, int kw,
                                void* packed, void* stream);
 
+/* fp32 B-operand stream of the fused 1x32x32 trunk's 16-row tiles (v_mfma_f32_16x16x4_f32), for its three 3x3 convolutions
+ * 128 -> 128 at precision 0: [C_out/32][K/16][2][64 lanes][4], tap-major K; component j of lane l holds output channel
+ * 32*tile + 16*half + (l&15) and, of the block's 16 k, the one at position 4*(l>>4) + j of the order
+ * 0 2 8 10 | 4 6 12 14 | 1 3 9 11 | 5 7 13 15.  C_out % 32 == 0 and C_in % 16 == 0 (elems: 0 otherwise).  Goes into
+ * ipsx_conv.w_packed_bf16 beside the ipsx_pack_conv_weight stream in w_packed, which every other kernel keeps reading. */
+size_t ipsx_packed_conv_weight_tile16_elems(int c_out, int c_in, int kh, int kw);
+int ipsx_pack_conv_weight_tile16(const float* w_oihw, int c_out, int c_in, int kh, int kw,
+                                 float* packed, void* stream);
+
 /* eval-mode BatchNorm (nn.BatchNorm2d/1d with running stats) -> per-channel affine.
  * lin_bias (or NULL): bias of a Linear feeding the BatchNorm, folded in as
  * shift = fma(lin_bias, alpha, shift)                                        */
@@ -170,7 +182,9 @@ typedef struct ipsx_conv {
     const float* alpha;           /* c_out, BatchNorm scale (or NULL = 1)    */
     const float* shift;           /* c_out, BatchNorm shift / bias (or NULL) */
     const void* w_packed_bf16;    /* bf16 operand stream for ipsx_trunk.precision: ipsx_pack_conv_weight_bf16
-                                     (precision 1) or ipsx_pack_conv_weight_x3 (precision 2); NULL = fp32 only */
+                                     (precision 1) or ipsx_pack_conv_weight_x3 (precision 2); NULL = fp32 only.
+                                     At precision 0, on a 3x3 convolution 128 -> 128 of stride 1:
+                                     ipsx_pack_conv_weight_tile16 (float32), read by the fused 1x32x32 trunk */
     const float* colsum;          /* c_out, sum over c_in of the weights (ipsx_weight_colsum): the projector's Linear
                                      only (ipsx_projector*: the folded LayerNorm's mean term); NULL elsewhere      */
 } ipsx_conv;

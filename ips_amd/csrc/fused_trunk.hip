@@ -8,7 +8,8 @@
 // bound is the fp32 matrix pipe (157 TFLOP/s), not HBM.
 //
 // One workgroup = 4 wavefronts = 4 patches, 69 KiB of LDS (one 17.3 KiB slab per patch), two
-// workgroups per CU.  Every contraction is v_mfma_f32_32x32x2_f32 in the contract's k order, so
+// workgroups per CU.  Every contraction is v_mfma_f32_32x32x2_f32 in the contract's k order (fused_trunk_kernel's 4x4 stage:
+// v_mfma_f32_16x16x4_f32 in the same order, conv_t16), so
 // the embeddings are bit-identical to the layer-by-layer kernels of conv.hip and to the oracle.
 //
 // What the instruction stream is shaped by (measured, tools/ubench): for the fp32 MFMA every
@@ -752,6 +753,8 @@ __device__ __forceinline__ void trunk_quad_tile(const FusedArgs& a, long long p_
 // ky = 2 for the bottom row (the stride-1 convolutions) - and those taps' MFMAs and A-operand loads are left out: in code
 // (loops of their own over the taps), not by a branch.  That changes no bit (an accumulation chain that starts
 // at +0 is not changed by adding fma(0, w, .) for a finite w) and leaves 8,480 of the 9,104 MFMAs per patch.
+// Of the 4x4 stage only the stride-2 convolution and the projection, which read the 8x8 image, still run so; the three
+// 128 -> 128 convolutions run on 16-row tiles (conv_t16, below), which leave out more.
 constexpr int SLAB8 = SLAB + 12;      // floats per slab here: 4432 = 16 (mod 64 banks), so the 4 patches x 4 columns of the 16
                                       // lanes of one ds_read_b128 pass fall on 16 different 4-bank groups (SLAB: 1 - 4-way)
 
@@ -903,11 +906,251 @@ __device__ __forceinline__ void conv_l8_rows(const float* __restrict__ wp, const
     else conv_l8<CIN, WIN, PS, ZP, STRIDE, KS, 0>(wp, lds, acc, lane, nw);
 }
 
-// write the wave's 2 tiles in the 4x4 stage's layout: C reg r is tile row (r & 3) + 4 half + 8 (r >> 2), i.e. patch
-// 2 (r >> 2) + half, column r & 3
-__device__ __forceinline__ void store_l8(float* lds, const f32x16 (&v)[2], int lane, int nw, int oy0, int oy1) {
+// ------------------------------------------------------------------ fused_trunk_kernel's 4x4 stage: 16-row tiles
+// The three stride-1 3x3 convolutions at 4x4 (128 -> 128) run on v_mfma_f32_16x16x4_f32: row m of an M-tile = patch m >> 1,
+// position slot m & 1, so a tile is TWO pixel positions of all eight patches and the 16 positions make eight tiles
+// (slot s -> pixel pix0 + s step):
+//   TL TR   row 0, columns 0-1 / 2-3          leave out ky = 0          BL BR   row 3, columns 0-1 / 2-3    leave out ky = 2
+//   LC      column 0, rows 1-2                leave out kx = 0          RC      column 3, rows 1-2          leave out kx = 2
+//   I1 I2   rows 1 / 2, columns 1-2           every tap
+// Wave w computes channels 32 (w & 3) .. + 31 as two 16-channel N-tiles, for set w >> 2: {TL TR LC I1} or {BL BR RC I2} -
+// 27 of 36 tile-taps each, 54 of 72 in all where one output row per tile ran 30 of 36 (960 -> 864 MFMA equivalents per
+// convolution and patch).  The instruction accumulates its four k slots as one fma chain in slot order (lane group
+// g = lane >> 4 is slot g; ipsx_dbg_mfma16_chain, tests/test_mfma16_chain.py), so the two instructions of an aligned 8-group
+// take k (0,4,1,5) and (2,6,3,7): the contract's order.  For a lane group's four k of two 8-groups to lie side by side - ONE
+// ds_read_b128 per tile and 16 k, one 16-byte weight load per N-tile and 16 k - the stage's LDS images keep their channels
+// permuted inside every aligned block of 16 (position t16_pos(c)); store_l8t, t16_store / t16_load and the average pool write and read
+// it so, and ipsx_pack_conv_weight_tile16 packs the weights to match.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+#define MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+
+enum : int { T16_ALL, T16_KY0, T16_KY2, T16_KX0, T16_KX2 };
+struct T16Tile {
+    int pix0, step, skip;
+    bool x0, x3;          // one slot sits in column 0 / 3 and reads the zero row at kx = 0 / 2
+};
+
+__host__ __device__ constexpr T16Tile t16_tile(int set, int t) {
+    constexpr T16Tile tiles[2][4] = {
+        {{0, 1, T16_KY0, true, false}, {2, 1, T16_KY0, false, true}, {4, 4, T16_KX0, true, false}, {5, 1, T16_ALL, false, false}},
+        {{12, 1, T16_KY2, true, false}, {14, 1, T16_KY2, false, true}, {7, 4, T16_KX2, false, true}, {9, 1, T16_ALL, false, false}}};
+    return tiles[set][t];
+}
+
+__host__ __device__ constexpr int t16_pix(int set, int t, int slot) { return t16_tile(set, t).pix0 + slot * t16_tile(set, t).step; }
+
+// the set's live tiles at tap (ky, kx) (bit t)
+__host__ __device__ constexpr int t16_live(int set, int ky, int kx) {
+    int m = 0;
+    for (int t = 0; t < 4; ++t) {
+        const int k = t16_tile(set, t).skip;
+        const bool out = (k == T16_KY0 && ky == 0) || (k == T16_KY2 && ky == 2) || (k == T16_KX0 && kx == 0) || (k == T16_KX2 && kx == 2);
+        if (!out) m |= 1 << t;
+    }
+    return m;
+}
+
+// where channel c (mod 16) lies inside its block of 16: lane group g = (k >> 2) + 2 (k & 1) of k = c & 7 holds it, as
+// component 2 (c >> 3) + ((k >> 1) & 1) of the group's float4 - [0 2 8 10 | 4 6 12 14 | 1 3 9 11 | 5 7 13 15]
+__host__ __device__ constexpr int t16_pos(int c) {
+    return 4 * (((c & 7) >> 2) + 2 * (c & 1)) + 2 * ((c >> 3) & 1) + ((c >> 1) & 1);
+}
+__host__ __device__ constexpr int t16_col(int n) { return (n & ~15) + t16_pos(n & 15); }
+
+constexpr int T16_ID = (ZP2 + 1) * PS2;     // floats into a slab: a second 4x4 image behind the stage's own (the identity's hand-over)
+static_assert(T16_ID + 16 * PS2 <= SLAB8, "the hand-over image fits the slab");
+
+// the operand pointers of one tap row ky, as conv_p1's: p = pixel (y + ky - 1, x) for tiles with a column-0 slot, else
+// (y + ky - 1, x - 1); e = the one tap whose column leaves the map for one slot, the zero row for its lanes
+struct T16Row {
+    const float* p[4];
+    const float* e[4];
+};
+
+template <int SET>
+__device__ __forceinline__ T16Row t16_row(const float* const (&P)[4], const float* Z, const bool (&ok)[4], int ky) {
+    T16Row r;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const T16Tile d = t16_tile(SET, t);
+        const float* c = P[t] + (ky - 1) * 4 * PS2;
+        r.p[t] = d.x0 ? c : c - PS2;
+        r.e[t] = d.x0 ? (ok[t] ? c - PS2 : Z) : (d.x3 ? (ok[t] ? c + PS2 : Z) : c);
+    }
+    return r;
+}
+
+template <int SET>
+__device__ __forceinline__ const float* t16_src(const T16Row& r, int t, int kx) {
+    const T16Tile d = t16_tile(SET, t);
+    if (d.x0) return kx == 0 ? r.e[t] : r.p[t] + (kx - 1) * PS2;
+    if (d.x3 && kx == 2) return r.e[t];
+    return r.p[t] + kx * PS2;
+}
+
+struct T16State {
+    f32x4 acc[4][2];    // [tile][N-tile]
+    float4 a[2][4];     // [stage & 1][tile]: the lane group's four k of 16
+    float4 b[4][2];     // weight ring: slot = stage & 3, refilled 2 stages ahead; [N-tile]
+};
+
+// a stage's interleave of NM MFMAs with its NL LDS reads and 2 weight loads: G MFMAs in front of every load, the weight
+// loads second and fourth (second and third when there are three loads), the rest of the MFMAs at the end
+template <int G, int K, int NL>
+__device__ __forceinline__ void t16_groups() {
+#if IPSX_SPREAD
+    if constexpr (K < NL + 2) {
+        SG_MFMA(G);
+        if constexpr (K == 1 || K == (NL + 1 < 3 ? NL + 1 : 3)) SG_VMEM(1);
+        else SG_LDS(1);
+        t16_groups<G, K + 1, NL>();
+    }
+#endif
+}
+
+template <int NM, int NL>
+__device__ __forceinline__ void t16_post() {
+#if IPSX_SPREAD
+    constexpr int G = (NM - 4) / (NL + 3) > 0 ? (NM - 4) / (NL + 3) : 1;
+    t16_groups<G, 0, NL>();
+    SG_MFMA(NM - G * (NL + 2));
+#endif
+    SB();
+}
+
+__host__ __device__ constexpr int t16_count(int m) { return (m & 1) + (m >> 1 & 1) + (m >> 2 & 1) + (m >> 3 & 1); }
+
+// stage ST (= 8 kx + block of 16 k) of tap row ky: prefetch the next stage's operands of its live tiles (the next row's first
+// when ST = 23: KYN) and the weights two stages on, then this stage's MFMAs - per (tile, N-tile) the four instructions of
+// its 16 k in order, the eight chains interleaved
+template <int SET, int KY, int KYN, int ST>
+__device__ __forceinline__ void t16_stages(T16State& s, const T16Row& cur, const T16Row& nxt, const char* w, unsigned lo, int g0) {
+    if constexpr (ST < 24) {
+        constexpr int KX = ST >> 3, LIVE = t16_live(SET, KY, KX);
+        constexpr bool LAST = ST == 23;
+        constexpr int NKX = LAST ? 0 : (ST + 1) >> 3, NCB = LAST ? 0 : (ST + 1) & 7;
+        constexpr int LIVEN = LAST ? t16_live(SET, KYN, 0) : t16_live(SET, KY, NKX);
+        constexpr int NB = (ST + 1) & 1;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+            if (LIVEN >> t & 1)
+                s.a[NB][t] = *reinterpret_cast<const float4*>(t16_src<SET>(LAST ? nxt : cur, t, NKX) + NCB * 16);
+        {
+            int g = g0 + ST + 2;
+            g = g < 72 ? g : 71;
+            s.b[(ST + 2) & 3][0] = *reinterpret_cast<const float4*>(w + (size_t)g * 2048 + lo);
+            s.b[(ST + 2) & 3][1] = *reinterpret_cast<const float4*>(w + (size_t)g * 2048 + 1024 + lo);
+        }
+        L1_PRE();
+        {
+            const float4 &b0 = s.b[ST & 3][0], &b1 = s.b[ST & 3][1];
+            const float bb[2][4] = {{b0.x, b0.y, b0.z, b0.w}, {b1.x, b1.y, b1.z, b1.w}};
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+                    if (LIVE >> t & 1) {
+                        const float4& aq = s.a[ST & 1][t];
+                        const float av[4] = {aq.x, aq.y, aq.z, aq.w};
+                        s.acc[t][0] = MFMA4(av[j], bb[0][j], s.acc[t][0]);
+                        s.acc[t][1] = MFMA4(av[j], bb[1][j], s.acc[t][1]);
+                    }
+        }
+        t16_post<8 * t16_count(LIVE), t16_count(LIVEN)>();
+        t16_stages<SET, KY, KYN, ST + 1>(s, cur, nxt, w, lo, g0);
+    }
+}
+
+// one tap row: its three taps x 8 blocks of 16 k; leaves cur = the next row's pointers (clamped: the last row's tail prefetch
+// re-reads its own first operands)
+template <int SET, int KY, int KYN>
+__device__ __forceinline__ void t16_tap_row(T16State& s, T16Row& cur, const float* const (&P)[4], const float* Z,
+                                            const bool (&ok)[4], const char* w, unsigned lo, int ky) {
+    const T16Row nxt = t16_row<SET>(P, Z, ok, ky < 2 ? ky + 1 : 2);
+    t16_stages<SET, KY, KYN, 0>(s, cur, nxt, w, lo, ky * 24);
+    cur = nxt;
+}
+
+// conv3x3 (128 -> 128, stride 1, pad 1) of the 4x4 stage over the workgroup's eight slabs: acc[t][h] = tile t of the wave's
+// set, channels 32 nw + 16 h .. + 15.  wp: ipsx_pack_conv_weight_tile16 - per wave 72 blocks of 16 k x 2 N-tiles of 1 KiB.
+template <int SET>
+__device__ __forceinline__ void conv_t16(const float* __restrict__ wp, const float* lds, f32x4 (&acc)[4][2], int lane, int nw) {
+    int m = lane & 15;
+    asm volatile("" : "+v"(m));            // the addresses below are computed per call, not kept live across the stage
+    const int slot = m & 1;
+    const float* S0 = lds + (m >> 1) * SLAB8 + 4 * (lane >> 4);
+    const float* Z = S0 + ZP2 * PS2;
+    const float* P[4];
+    bool ok[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const T16Tile d = t16_tile(SET, t);
+        const int pix = d.pix0 + slot * d.step;
+        P[t] = S0 + pix * PS2;
+        ok[t] = d.x0 ? (pix & 3) != 0 : (pix & 3) != 3;
+    }
+    const char* w = reinterpret_cast<const char*>(wp) + (size_t)__builtin_amdgcn_readfirstlane(nw) * 72 * 2048;
+    const unsigned lo = lane * 16;
+    T16State s;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s.acc[t][h][r] = 0.0f;
+    s.b[0][0] = *reinterpret_cast<const float4*>(w + lo);
+    s.b[0][1] = *reinterpret_cast<const float4*>(w + 1024 + lo);
+    s.b[1][0] = *reinterpret_cast<const float4*>(w + 2048 + lo);
+    s.b[1][1] = *reinterpret_cast<const float4*>(w + 3072 + lo);
+    T16Row cur = t16_row<SET>(P, Z, ok, 0);
+    constexpr int LIVE0 = t16_live(SET, 0, 0);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+        if (LIVE0 >> t & 1) s.a[0][t] = *reinterpret_cast<const float4*>(t16_src<SET>(cur, t, 0));
+    if constexpr (SET == 0) {                                               // rows ky = 1 and 2 alike
+        t16_tap_row<SET, 0, 1>(s, cur, P, Z, ok, w, lo, 0);
+#pragma unroll 1
+        for (int ky = 1; ky < 3; ++ky) t16_tap_row<SET, 1, 1>(s, cur, P, Z, ok, w, lo, ky);
+    } else {                         // rows ky = 0 and 1 alike: row 1's tail prefetches BL BR for row 2 too, unused (inside the slab)
+#pragma unroll 1
+        for (int ky = 0; ky < 2; ++ky) t16_tap_row<SET, 0, 0>(s, cur, P, Z, ok, w, lo, ky);
+        t16_tap_row<SET, 2, 2>(s, cur, P, Z, ok, w, lo, 2);
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) acc[t][h] = s.acc[t][h];
+}
+
+// the wave's four tiles <-> a 4x4 image at `lds` (+ T16_ID: the hand-over image), channels permuted: C reg r of a tile is
+// row 4 (lane >> 4) + r, i.e. patch 2 (lane >> 4) + (r >> 1), slot r & 1
+template <int SET>
+__device__ __forceinline__ void t16_store(float* lds, const f32x4 (&v)[4][2], int lane, int nw) {
+    float* base = lds + 2 * (lane >> 4) * SLAB8 + 32 * nw + t16_pos(lane & 15);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) base[(r >> 1) * SLAB8 + t16_pix(SET, t, r & 1) * PS2 + 16 * h] = v[t][h][r];
+}
+
+template <int SET>
+__device__ __forceinline__ void t16_load(const float* lds, f32x4 (&v)[4][2], int lane, int nw) {
+    const float* base = lds + 2 * (lane >> 4) * SLAB8 + 32 * nw + t16_pos(lane & 15);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[t][h][r] = base[(r >> 1) * SLAB8 + t16_pix(SET, t, r & 1) * PS2 + 16 * h];
+}
+
+// write conv_l8's 2 tiles as a 4x4 image of the 16-row stage (channels permuted), at `lds` or at lds + T16_ID: C reg r is
+// tile row (r & 3) + 4 half + 8 (r >> 2), i.e. patch 2 (r >> 2) + half, column r & 3
+__device__ __forceinline__ void store_l8t(float* lds, const f32x16 (&v)[2], int lane, int nw, int oy0, int oy1) {
     const int i = lane & 31, half = lane >> 5;
-    const int n = 32 * nw + i;
+    const int n = t16_col(32 * nw + i);
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -915,6 +1158,49 @@ __device__ __forceinline__ void store_l8(float* lds, const f32x16 (&v)[2], int l
             const int pl = 2 * (r >> 2) + half, pix = (mt ? oy1 : oy0) * 4 + (r & 3);
             lds[pl * SLAB8 + pix * PS2 + n] = v[mt][r];
         }
+}
+
+// block 0's second convolution and block 1 of layer2 for the wave's set: the slabs hold conv1's output (permuted) and the
+// projected identity at T16_ID on entry, layer2's output (permuted) on return
+template <bool STAMP, int SET>
+__device__ __forceinline__ void layer2_t16(const FusedArgs& a, float* lds, int lane, int wave, unsigned long long* stamps) {
+    constexpr int WPB = 8;
+    const int nw = wave & 3;
+    const int n0 = 32 * nw + (lane & 15);
+    f32x4 idn[4][2], acc[4][2];
+    t16_load<SET>(lds + T16_ID, idn, lane, nw);
+#pragma unroll 1
+    for (int cv = 5; cv < 8; ++cv) {
+        conv_t16<SET>(static_cast<const float*>(a.wh[cv]), lds, acc, lane, nw);
+        const float A[2] = {a.al[cv][n0], a.al[cv][n0 + 16]}, B[2] = {a.sh[cv][n0], a.sh[cv][n0 + 16]};
+        if (cv == 6) {                                                      // block 1 conv1: BN + ReLU only
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float v = __builtin_fmaf(acc[t][h][r], A[h], B[h]);
+                        acc[t][h][r] = v > 0.0f ? v : 0.0f;
+                    }
+        } else {                                                            // conv2 -> BN -> += identity -> ReLU
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float v = __builtin_fmaf(acc[t][h][r], A[h], B[h]);
+                        v = v + idn[t][h][r];
+                        idn[t][h][r] = v > 0.0f ? v : 0.0f;
+                    }
+        }
+        __syncthreads();                                                    // every wave has read this convolution's input
+        if (cv == 6) t16_store<SET>(lds, acc, lane, nw);
+        else t16_store<SET>(lds, idn, lane, nw);
+        __syncthreads();
+        IPSX_STAMP(7 + cv);
+    }
 }
 
 // ------------------------------------------------------------------ fused_trunk_kernel's layer1: tiled by position
@@ -1257,37 +1543,20 @@ __device__ __forceinline__ void fused_trunk_body(const FusedArgs& a, unsigned lo
             }
     }
     __syncthreads();
-    store_l8(lds, t2, lane, nw, oy0, oy1);
+    store_l8t(lds, t2, lane, nw, oy0, oy1);
+    store_l8t(lds + T16_ID, id2, lane, nw, oy0, oy1);                     // the identity, into the 16-row tiles' registers below
     for (int z = lane; z < PS2; z += 64) lds[wave * SLAB8 + ZP2 * PS2 + z] = 0.0f;  // zero pixel row of the 4x4 stage
     __syncthreads();
-    // conv2 of block 0, then block 1 (conv1, conv2), all 128->128 at 4x4
-#pragma unroll 1
-    for (int cv = 5; cv < 8; ++cv) {
-        conv_l8_rows<128, 4, PS2, ZP2, 1, 3>(a.w[cv], lds, t2, lane, nw, bottom);
-        const float A = a.al[cv][n2], B = a.sh[cv][n2];
-        const bool plain = (cv == 6);                                     // block 1 conv1: BN + ReLU only
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float v = __builtin_fmaf(t2[mt][r], A, B);
-                if (!plain) v = v + id2[mt][r];
-                v = v > 0.0f ? v : 0.0f;
-                t2[mt][r] = v;
-                if (!plain) id2[mt][r] = v;
-            }
-        __syncthreads();
-        store_l8(lds, t2, lane, nw, oy0, oy1);
-        __syncthreads();
-        IPSX_STAMP(7 + cv);
-    }
+    // conv2 of block 0, then block 1 (conv1, conv2), all 128->128 at 4x4, on 16-row tiles
+    if (bottom) layer2_t16<STAMP, 1>(a, lds, lane, wave, stamps);
+    else layer2_t16<STAMP, 0>(a, lds, lane, wave, stamps);
 
     // ---- global average pool over the 16 pixels, sequential order
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int o = threadIdx.x + 512 * h;
         const int pl = o >> 7, n = o & 127;
-        const float* s = lds + pl * SLAB8 + n;
+        const float* s = lds + pl * SLAB8 + t16_col(n);                   // the stage's channel permutation, undone
         float sum = 0.0f;
 #pragma unroll
         for (int k = 0; k < 16; ++k) sum = sum + s[k * PS2];
@@ -1478,6 +1747,53 @@ __global__ __launch_bounds__(256, 2) void conv_lds_l2_kernel(LdsConvArgs a) {
     }
 }
 
+// OIHW fp32 -> the B-operand stream of conv_t16: [C_out/32][K/16][2 N-tiles][64 lanes][4], tap-major K; component j of lane l
+// holds k = 16 block + (the channel at position 4 (l >> 4) + j of the block), output channel 32 wave + 16 N-tile + (l & 15)
+__global__ void pack_conv_weight_tile16_kernel(const float* __restrict__ w, int c_in, int taps, int blocks, size_t total,
+                                               float* __restrict__ packed) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int j = (int)(i & 3), lane = (int)((i >> 2) & 63), h = (int)((i >> 8) & 1);
+    const size_t q = i >> 9;               // wave * blocks + block
+    const int blk = (int)(q % blocks), nw = (int)(q / blocks);
+    const int n = 32 * nw + 16 * h + (lane & 15);
+    int c16 = 0;
+    for (int c = 0; c < 16; ++c)
+        if (t16_pos(c) == 4 * (lane >> 4) + j) c16 = c;
+    const int k = 16 * blk + c16, tap = k / c_in, c = k - tap * c_in;
+    packed[i] = w[((size_t)n * c_in + c) * taps + tap];
+}
+
+// ipsx_dbg_mfma16_chain: one wavefront, C (16 x 16) = A (16 x 8) B (8 x 16) from +0.  form 0: two v_mfma_f32_16x16x4_f32
+// with k slots (0,4,1,5) then (2,6,3,7); form 1: the same product as the 32x32x2 path computes it - four instructions,
+// lane half h holding k = 4 h + j at step j (rows and columns 16 .. 31 of the tile are zero operands)
+__global__ void mfma16_chain_kernel(const float* __restrict__ A, const float* __restrict__ B, float* __restrict__ Cm, int form) {
+    const int lane = threadIdx.x & 63;
+    if (form == 0) {
+        const int m = lane & 15, g = lane >> 4;
+        const int k0 = 4 * (g & 1) + (g >> 1), k1 = k0 + 2;          // slot g: k = {0,4,1,5}[g], then {2,6,3,7}[g]
+        f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+        acc = MFMA4(A[m * 8 + k0], B[k0 * 16 + m], acc);
+        acc = MFMA4(A[m * 8 + k1], B[k1 * 16 + m], acc);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Cm[(4 * g + r) * 16 + m] = acc[r];
+    } else {
+        const int i = lane & 31, half = lane >> 5;
+        f32x16 acc;
+        zero(acc);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = 4 * half + j;
+            acc = MFMA(i < 16 ? A[i * 8 + k] : 0.0f, i < 16 ? B[k * 16 + i] : 0.0f, acc);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+            if (row < 16 && i < 16) Cm[row * 16 + i] = acc[r];
+        }
+    }
+}
+
 static bool is_conv(const ipsx_conv& c, int ci, int co, int k, int s, int p) {
     return c.c_in == ci && c.c_out == co && c.kh == k && c.kw == k && c.stride == s && c.pad == p && c.w_packed &&
            c.alpha && c.shift;
@@ -1524,7 +1840,7 @@ static FusedArgs fused_args(const ipsx_trunk* t, const PatchSrc& src, int64_t n,
             a.w[2 * k + j] = t->blocks[k].conv[j].w_packed;
             a.al[2 * k + j] = t->blocks[k].conv[j].alpha;
             a.sh[2 * k + j] = t->blocks[k].conv[j].shift;
-            a.wh[2 * k + j] = with_bf16 ? t->blocks[k].conv[j].w_packed_bf16 : nullptr;
+            a.wh[2 * k + j] = with_bf16 || t->precision == 0 ? t->blocks[k].conv[j].w_packed_bf16 : nullptr;
         }
     a.w_down = t->blocks[2].down.w_packed; a.a_down = t->blocks[2].down.alpha; a.s_down = t->blocks[2].down.shift;
     a.wh_down = with_bf16 ? t->blocks[2].down.w_packed_bf16 : nullptr;
@@ -1583,6 +1899,9 @@ int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb
         else fused_trunk_bf16_kernel<false><<<grid, block, BF16_LDS, s>>>(a, nullptr);
         return launched("fused_trunk_bf16");
     }
+    if (!(a.wh[5] && a.wh[6] && a.wh[7]))
+        return fail(IPSX_EINVAL, "fused trunk: the exact fp32 trunk needs ipsx_pack_conv_weight_tile16 of its three 128 -> 128 "
+                    "convolutions in their w_packed_bf16");
     const int cus = device_cus();
     // What is left over after the whole rounds (8 patches per CU) goes to the two-wavefronts-per-patch kernel when that takes
     // fewer wavefront slots per SIMD: at most a quarter round (one workgroup per CU, one wavefront per SIMD, half a patch
@@ -1649,6 +1968,9 @@ int fused_trunk_encode_parts(const ipsx_trunk* t, const PatchSrc& src, int64_t n
     }
     if (before != n) return fail(IPSX_EINVAL, "trunk_encode_parts: part_end must increase and end on the list's length");
     const FusedArgs a = fused_args(t, src, n, emb, false);
+    if (!(a.wh[5] && a.wh[6] && a.wh[7]))
+        return fail(IPSX_EINVAL, "trunk_encode_parts: the exact fp32 trunk needs ipsx_pack_conv_weight_tile16 of its three "
+                    "128 -> 128 convolutions in their w_packed_bf16");
     static bool attr_set = false;
     if (!attr_set) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_parts_kernel),
@@ -1807,6 +2129,19 @@ IPSX_API int ipsx_pack_stem_weight_split(const float* w, int c_out, int planes, 
     return ipsx::launched("pack_stem_weight_split");
 }
 
+IPSX_API size_t ipsx_packed_conv_weight_tile16_elems(int c_out, int c_in, int kh, int kw) {
+    if (c_out <= 0 || c_in <= 0 || kh <= 0 || kw <= 0 || c_out % 32 || c_in % 16) return 0;
+    return (size_t)c_out * c_in * kh * kw;
+}
+
+IPSX_API int ipsx_pack_conv_weight_tile16(const float* w, int c_out, int c_in, int kh, int kw, float* packed, void* stream) {
+    const size_t total = ipsx_packed_conv_weight_tile16_elems(c_out, c_in, kh, kw);
+    IPSX_REQUIRE(w && packed && total, "pack_conv_weight_tile16: C_out a multiple of 32 and C_in a multiple of 16");
+    ipsx::pack_conv_weight_tile16_kernel<<<dim3((unsigned)ipsx::cdiv(total, 256)), dim3(256), 0, ipsx::as_stream(stream)>>>(
+        w, c_in, kh * kw, kh * kw * c_in / 16, total, packed);
+    return ipsx::launched("pack_conv_weight_tile16");
+}
+
 // Diagnostic switch (not part of include/ipsx.h; tests/test_hip_kernels.py, tools): which of the two exact fp32 kernels
 // encodes - 0 the product's rule, 1 fused_trunk_kernel only, 2 fused_trunk_pair_kernel only.
 extern "C" __attribute__((visibility("default"))) void ipsx_dbg_fused_trunk_pair(int mode) { ipsx::g_pair_mode = mode; }
@@ -1819,4 +2154,32 @@ extern "C" __attribute__((visibility("default"))) int ipsx_dbg_fused_trunk_stamp
     const ipsx::PatchSrc src{patches, nullptr, nullptr, nullptr, 0};
     IPSX_TRY(ipsx::patch_src_check(t, src, n, true, "fused trunk"));
     return ipsx::fused_launch(t, src, n, emb, ipsx::as_stream(stream), nullptr, stamps);
+}
+
+// Diagnostic entry points (not part of include/ipsx.h; tests/test_mfma16_chain.py, tests/test_tile16_layout_cpu.py).
+// ipsx_dbg_mfma16_chain: c (16 x 16, row-major) = a (16 x 8, row-major) b (8 x 16, row-major), device pointers - form 0 on
+// v_mfma_f32_16x16x4_f32 as conv_t16 issues it, form 1 on v_mfma_f32_32x32x2_f32 as every other convolution here does.
+extern "C" __attribute__((visibility("default"))) int ipsx_dbg_mfma16_chain(const float* a, const float* b, float* c, int form,
+                                                                             void* stream) {
+    IPSX_REQUIRE(a && b && c && (form == 0 || form == 1), "dbg_mfma16_chain: bad arguments");
+    ipsx::mfma16_chain_kernel<<<dim3(1), dim3(64), 0, ipsx::as_stream(stream)>>>(a, b, c, form);
+    return ipsx::launched("mfma16_chain");
+}
+
+// ipsx_dbg_tile16_layout (host only): the 4x4 stage's tiles as the kernel's tables have them - tiles[8][4] = (first pixel,
+// second pixel, skipped tap row ky or -1, skipped tap column kx or -1), tile 4 s + t = tile t of set s; wave_set[8] = the set
+// of wave w; live[2][9] = the set's live tiles at tap 3 ky + kx (bit t); pos[16] = position of channel c in its block of 16.
+extern "C" __attribute__((visibility("default"))) void ipsx_dbg_tile16_layout(int* tiles, int* wave_set, int* live, int* pos) {
+    for (int s = 0; s < 2; ++s)
+        for (int t = 0; t < 4; ++t) {
+            const ipsx::T16Tile d = ipsx::t16_tile(s, t);
+            int* o = tiles + 4 * (4 * s + t);
+            o[0] = ipsx::t16_pix(s, t, 0); o[1] = ipsx::t16_pix(s, t, 1);
+            o[2] = d.skip == ipsx::T16_KY0 ? 0 : d.skip == ipsx::T16_KY2 ? 2 : -1;
+            o[3] = d.skip == ipsx::T16_KX0 ? 0 : d.skip == ipsx::T16_KX2 ? 2 : -1;
+        }
+    for (int w = 0; w < 8; ++w) wave_set[w] = w >> 2;
+    for (int s = 0; s < 2; ++s)
+        for (int tap = 0; tap < 9; ++tap) live[9 * s + tap] = ipsx::t16_live(s, tap / 3, tap % 3);
+    for (int c = 0; c < 16; ++c) pos[c] = ipsx::t16_pos(c);
 }

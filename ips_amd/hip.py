@@ -198,6 +198,8 @@ _EXPORTS = {
     "ipsx_pack_conv_weights_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "ipsx_packed_conv_weight_bf16_bytes": (C.c_size_t, [C.c_int] * 4),
     "ipsx_pack_conv_weight_bf16": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "ipsx_packed_conv_weight_tile16_elems": (C.c_size_t, [C.c_int] * 4),
+    "ipsx_pack_conv_weight_tile16": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ipsx_packed_conv_weight_x3_bytes": (C.c_size_t, [C.c_int] * 4),
     "ipsx_pack_conv_weight_x3": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ipsx_packed_stem_weight_split_bytes": (C.c_size_t, [C.c_int, C.c_int]),

@@ -33,6 +33,12 @@ def _pack_conv(weight):
     return packed
 
 
+def _is_tile16(conv):
+    """A 3x3 convolution 128 -> 128 of stride 1 and pad 1: the 4x4 stage of the fused 1x32x32 trunk."""
+    return (conv.in_channels == 128 and conv.out_channels == 128 and tuple(conv.kernel_size) == (3, 3)
+            and tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (1, 1))
+
+
 class _PlanHold:
     """``EncoderPlan.hold()``: the plan's weight check runs on entry and is skipped until exit."""
     __slots__ = ("plan",)
@@ -156,6 +162,14 @@ class EncoderPlan:
                           (lib().ipsx_packed_conv_weight_x3_bytes, lib().ipsx_pack_conv_weight_x3))
             half = torch.empty(size(co, ci, kh, kw), dtype=torch.uint8, device=w.device)
             _ck(pack(_p(w), co, ci, kh, kw, _p(half), _stream()), "ipsx_pack_conv_weight_bf16/x3")
+            self._keep.append(half)
+        elif not stem and _is_tile16(conv):
+            # the fp32 fused trunk's 16-row tiles (csrc/fused_trunk.hip: conv_t16) read these three convolutions in a packing
+            # of their own, carried in the descriptor's second pointer, which nothing else reads at precision 0
+            w = _f32(conv.weight.detach())
+            co, ci, kh, kw = w.shape
+            half = torch.empty(lib().ipsx_packed_conv_weight_tile16_elems(co, ci, kh, kw), dtype=torch.float32, device=w.device)
+            _ck(lib().ipsx_pack_conv_weight_tile16(_p(w), co, ci, kh, kw, _p(half), _stream()), "ipsx_pack_conv_weight_tile16")
             self._keep.append(half)
         return Conv(conv.in_channels, conv.out_channels, conv.kernel_size[0], conv.kernel_size[1],
                     conv.stride[0], conv.padding[0], _p(packed), _p(aff[0]), _p(aff[1]), _p(half))

@@ -55,17 +55,18 @@ groups = None
 if prec == "fp32":
     # fused_trunk_kernel: eight wavefronts per workgroup (row = 8 * workgroup + wave).  In the 4x4 stage a wave's MFMAs are
     # those of its two output rows for 32 channels, less the padded taps of its edge row: waves 0-3 (rows 0 + 1) 544 in
-    # l2.0.c1+down and 960 per 128->128 convolution, waves 4-7 (rows 3 + 2) 640 and 960; the table holds their mean
+    # l2.0.c1+down, waves 4-7 (rows 3 + 2) 640; the table holds their mean.  The three 128->128 convolutions run on 16-row
+    # tiles (conv_t16): 27 tile-taps x 64 v_mfma_f32_16x16x4_f32 of 32 cycles per wave = 864 in this table's 64-cycle units
     # Layer1 is tiled by position too (conv_p1): a wave computes one N-tile of four M-tiles, the set (w + 2 (w >> 2)) & 3;
     # the sets T and B (waves 0 1 6 7) leave out 2 tiles x 3 taps, L and R (waves 2 3 4 5) 1 tile x 3 taps: 960 and 1,056
     # MFMAs per convolution, 1,008 on average (1,152 when wave = patch)
     wave = np.arange(len(s)) % 8
     tb = (((wave + 2 * (wave >> 2)) & 3) < 2)
-    groups = [("waves 0-3", wave < 4, range(10, 14), [544, 960, 960, 960]),
-              ("waves 4-7", wave >= 4, range(10, 14), [640, 960, 960, 960]),
+    groups = [("waves 0-3", wave < 4, range(10, 14), [544, 864, 864, 864]),
+              ("waves 4-7", wave >= 4, range(10, 14), [640, 864, 864, 864]),
               ("waves 0 1 6 7", tb, range(2, 10, 2), [960] * 4),
               ("waves 2 3 4 5", ~tb, range(2, 10, 2), [1056] * 4)]
-    mfma = mfma[:2] + [1008, 0, 1008, 0, 1008, 0, 1008, 0] + [592, 960, 960, 960, 0]
+    mfma = mfma[:2] + [1008, 0, 1008, 0, 1008, 0, 1008, 0] + [592, 864, 864, 864, 0]
 # stamps: 0 start,1 loaded,2 stem,3 c1,4 epi,5 c2,6 epi(+barrier),7..10 block 1,11 l2.0 c1+down,12 cv5,13 cv6,14 cv7,15 end
 life = s[:, 15] - s[:, 0]
 print("waves %d  median life %d cycles  (matrix-pipe cycles alone: %d)" % (len(s), np.median(life), sum(mfma) * 64))
