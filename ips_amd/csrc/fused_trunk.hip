@@ -1,21 +1,36 @@
-// fused_trunk.hip - the whole patch encoder of the Megapixel-MNIST configuration in ONE
-// kernel, activations resident in LDS.
+// fused_trunk.hip - the whole patch encoder of the Megapixel-MNIST configuration in ONE kernel, activations resident in LDS.
 //
-// Trunk (reference architecture/ips_net.py:17-52 with config/mnist_config.yml, 32-px
-// patches): conv7x7/2(1->64)+BN+ReLU -> maxpool3x3/2 -> 2 x BasicBlock(64) @8x8 ->
-// BasicBlock(64->128, /2, 1x1 projection) -> BasicBlock(128) @4x4 -> global average pool.
-// 18,628,608 MAC per patch; 4 KiB in, 512 B out: arithmetic intensity ~8 kFLOP/B, so the
-// bound is the fp32 matrix pipe (157 TFLOP/s), not HBM.
+// Trunk (reference architecture/ips_net.py:17-52 with config/mnist_config.yml, 32-px patches): conv7x7/2(1->64)+BN+ReLU ->
+// maxpool3x3/2 -> 2 x BasicBlock(64) @8x8 -> BasicBlock(64->128, /2, 1x1 projection) -> BasicBlock(128) @4x4 -> global
+// average pool.  18,628,608 MAC per patch; 4 KiB in, 512 B out: arithmetic intensity ~8 kFLOP/B, so the bound is the fp32
+// matrix pipe (157 TFLOP/s), not HBM.  No global-memory round trips between layers: HBM traffic is the patch, the 512 B
+// embedding and the L2-resident 2.7 MB of weights.
 //
-// One workgroup = 4 wavefronts = 4 patches, 69 KiB of LDS (one 17.3 KiB slab per patch), two
-// workgroups per CU.  Every contraction is v_mfma_f32_32x32x2_f32 in the contract's k order (fused_trunk_kernel's 4x4 stage:
-// v_mfma_f32_16x16x4_f32 in the same order, conv_t16), so
-// the embeddings are bit-identical to the layer-by-layer kernels of conv.hip and to the oracle.
+// What this translation unit holds:
+//   this file              the pieces every kernel shares - FusedArgs, the stem + max-pool (stem_pool), trunk_front (input
+//                          load + stem, wave = patch, into the wave's slab), the wave = patch 8x8 stage (conv_l1), the 32-row
+//                          4x4 stage (conv_l2), trunk_quad_tile (FOUR patches by four wavefronts: the stream kernel's and the
+//                          pair kernel's quads) - then, behind the headers, the stages as stand-alone convolutions for the
+//                          training step (conv_lds_*), the weight packers, the launchers (fused_launch,
+//                          fused_trunk_encode_parts, fused_trunk_stream) and the diagnostic exports
+//   fused_trunk_eight.h    fused_trunk_kernel, the exact fp32 kernel for whole rounds: EIGHT patches per workgroup of eight
+//                          wavefronts, one workgroup per CU, 139 KiB of LDS (a 17.3 KiB slab per patch).  The stem is
+//                          trunk_front; layer1 and the three 128 -> 128 convolutions at 4x4 run tiled by position across the
+//                          eight patches and leave out taps that read only padding - one stage over a geometry trait
+//                          (conv_p1, conv_t16); the two convolutions that read the 8x8 image run tiled by output row (conv_l8)
+//   fused_trunk_pair.h     the exact fp32 kernels for what does not fill a round (two wavefronts per patch) and for the
+//                          persistent one-image stream
+//   fused_trunk_split.h    the fp32x3 trunk on the bf16 matrix pipe (precision 2)
+//   fused_trunk_bf16.h     the bf16 trunk (precision 1)
+//
+// Every fp32 contraction is v_mfma_f32_32x32x2_f32 in the contract's k order (fused_trunk_kernel's 4x4 stage:
+// v_mfma_f32_16x16x4_f32 in the same order, conv_t16), so the embeddings are bit-identical to the layer-by-layer kernels of
+// conv.hip and to the oracle.
 //
 // What the instruction stream is shaped by (measured, tools/ubench): for the fp32 MFMA every
 // OTHER instruction a wave issues costs matrix-pipe time (~8-10 cycles each, wherever it is
 // placed), and a VALU write to a register that an MFMA issued just before reads as SrcA/B stalls
-// for that MFMA.  So the kernel minimises instructions per MFMA:
+// for that MFMA.  So the kernels minimise instructions per MFMA:
 //   * the LDS image of a stage is PIXEL-major, [pix][channel] with 4 floats of row padding, so a
 //     lane fetches the 4 consecutive k of its half of an 8-group with ONE ds_read_b128
 //     (that is why the contract's k order inside a group is 0,4,1,5,2,6,3,7);
@@ -28,15 +43,12 @@
 //             (32 px) x 64 channels; BN+ReLU in registers; the 3x3/2 max-pool is done ON the
 //             accumulators (one lane-half exchange of column maxima), and its output lands in
 //             exactly the register layout of the 8x8 stage's MFMA C tile - the first block's identity.
-//   layer1    wave = patch: 64 px x 64 ch = 2x2 accumulators, no workgroup barriers (the slab is
-//             wave-private).  conv1 output overwrites the slab in place (the identity lives in registers).
-//             fused_trunk_kernel (eight patches) tiles layer1 by position instead, as its 4x4 stage: conv_p1.
-//   layer2    the 4 waves share the 4 patches: M = 4 x 16 px = 2 tiles, wave w owns output
-//             channels 32w..32w+31, so each weight is fetched once per workgroup.
+//   layer1    trunk_quad_tile: wave = patch, 64 px x 64 ch = 2x2 accumulators, no workgroup barriers (the slab is
+//             wave-private); conv1's output overwrites the slab in place (the identity lives in registers).
+//             fused_trunk_kernel: tiled by position across its eight patches (conv_p1).
+//   layer2    trunk_quad_tile: the 4 waves share the 4 patches, M = 4 x 16 px = 2 tiles, wave w owns output channels
+//             32w..32w+31, so each weight is fetched once per workgroup.  fused_trunk_kernel: conv_l8, then conv_t16.
 //   avgpool   sequential 16-term sums from the slab (the oracle's order).
-//
-// No global-memory round trips between layers: HBM traffic is the 4 KiB patch, the 512 B
-// embedding and the L2-resident 2.7 MB of weights.
 
 #include <algorithm>
 
@@ -742,872 +754,7 @@ __device__ __forceinline__ void trunk_quad_tile(const FusedArgs& a, long long p_
     IPSX_STAMP(15);
 }
 
-// ------------------------------------------------------------------ fused_trunk_kernel: eight patches per workgroup
-// One workgroup = 8 wavefronts = 8 patches, one workgroup per compute unit: still 2 wavefronts per SIMD of 256 registers
-// and 8 patches per unit per round, as two workgroups of four were.  The stem is trunk_front (wave = patch, its own
-// slab); layer1 is tiled by position (conv_p1, below).  The 4x4 stage is tiled by POSITION across the eight patches: row i of an M-tile = patch i >> 2, output
-// column i & 3 of ONE output row oy, so a tile is one output row of all eight patches; N = 4 tiles of 32 channels.
-// Wave w owns channels 32 (w & 3) .. 32 (w & 3) + 31 and two tiles: waves 0-3 the top row (oy 0) and oy 1, waves 4-7 the
-// bottom row (oy 3) and oy 2; waves w and w + 4 share a SIMD, so every SIMD issues the same MFMAs.
-// For the edge tile a whole row of taps reads the zero padding in all 32 rows - ky = 0 for the top row (both 3x3 shapes),
-// ky = 2 for the bottom row (the stride-1 convolutions) - and those taps' MFMAs and A-operand loads are left out: in code
-// (loops of their own over the taps), not by a branch.  That changes no bit (an accumulation chain that starts
-// at +0 is not changed by adding fma(0, w, .) for a finite w) and leaves 8,480 of the 9,104 MFMAs per patch.
-// Of the 4x4 stage only the stride-2 convolution and the projection, which read the 8x8 image, still run so; the three
-// 128 -> 128 convolutions run on 16-row tiles (conv_t16, below), which leave out more.
-constexpr int SLAB8 = SLAB + 12;      // floats per slab here: 4432 = 16 (mod 64 banks), so the 4 patches x 4 columns of the 16
-                                      // lanes of one ds_read_b128 pass fall on 16 different 4-bank groups (SLAB: 1 - 4-way)
-
-template <int WIN, int PS, int ZP, int STRIDE, int KS>
-__device__ __forceinline__ L2Tap l8_tap(int tap, const float* S0, int oy0, int oy1, int ox) {
-    constexpr int PAD = KS / 2;
-    const int ky = tap / KS, kx = tap - ky * KS;
-    const int ix = ox * STRIDE + kx - PAD, iy0 = oy0 * STRIDE + ky - PAD, iy1 = oy1 * STRIDE + ky - PAD;
-    const bool okx = (unsigned)ix < (unsigned)WIN;
-    L2Tap d;
-    d.s0 = S0 + (okx && (unsigned)iy0 < (unsigned)WIN ? iy0 * WIN + ix : ZP) * PS;
-    d.s1 = S0 + (okx && (unsigned)iy1 < (unsigned)WIN ? iy1 * WIN + ix : ZP) * PS;
-    return d;
-}
-
-// SK0: tile 0 reads only padding at this tap - its loads and MFMAs are left out
-template <int C2, bool SK0>
-__device__ __forceinline__ void l8_load(L2Stage& st, const L2Tap& d) {
-    if (!SK0) {
-        st.a[0][0] = *reinterpret_cast<const float4*>(d.s0 + C2 * 16);
-        st.a[0][1] = *reinterpret_cast<const float4*>(d.s0 + C2 * 16 + 8);
-    }
-    st.a[1][0] = *reinterpret_cast<const float4*>(d.s1 + C2 * 16);
-    st.a[1][1] = *reinterpret_cast<const float4*>(d.s1 + C2 * 16 + 8);
-}
-
-template <bool SK0>
-__device__ __forceinline__ void l8_mma(const L2Stage& st, const float4 (&b)[2], f32x16 (&acc)[2]) {
-    if (!SK0) {
-        l2_mma(st, b, acc);
-        return;
-    }
-    const float a1[8] = {st.a[1][0].x, st.a[1][0].y, st.a[1][0].z, st.a[1][0].w,
-                         st.a[1][1].x, st.a[1][1].y, st.a[1][1].z, st.a[1][1].w};
-    const float bb[8] = {b[0].x, b[0].y, b[0].z, b[0].w, b[1].x, b[1].y, b[1].z, b[1].w};
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[1] = MFMA(a1[j], bb[j], acc[1]);
-}
-
-// a stage's interleave of NM MFMAs with its NL LDS reads and 2 weight loads: L2_POST's spacing when both tiles are live;
-// with tile 0 out, 8 MFMAs (the stage's own) and 2 LDS reads (the next stage's tile 1 only)
-template <int NM, int NL>
-__device__ __forceinline__ void l8_post() {
-#if IPSX_SPREAD
-    if constexpr (NM == 16 && NL == 4) {
-        L2_POST();
-    } else if constexpr (NM == 16) {
-        SG_MFMA(3); SG_LDS(1); SG_MFMA(3); SG_VMEM(1); SG_MFMA(3); SG_LDS(1); SG_MFMA(3); SG_VMEM(1); SG_MFMA(4); SB();
-    } else if constexpr (NL == 4) {
-        SG_MFMA(1); SG_LDS(1); SG_MFMA(1); SG_LDS(1); SG_MFMA(1); SG_VMEM(1); SG_MFMA(1); SG_LDS(1); SG_MFMA(1); SG_LDS(1);
-        SG_MFMA(1); SG_VMEM(1); SG_MFMA(2); SB();
-    } else {
-        SG_MFMA(1); SG_LDS(1); SG_MFMA(2); SG_VMEM(1); SG_MFMA(1); SG_LDS(1); SG_MFMA(2); SG_VMEM(1); SG_MFMA(1); SB();
-    }
-#else
-    SB();
-#endif
-}
-
-// one tap of conv_l8: conv_l2's stages and weight ring; SK: tile 0 is out at this tap, SKN: at the next one
-template <int PER_TAP, int G2, bool SK, bool SKN>
-__device__ __forceinline__ void l8_tap_stages(const L2Tap& cur, const L2Tap& nxt, L2Stage& sa, L2Stage& sb, float4 (&b0)[2],
-                                              float4 (&b1)[2], float4 (&b2)[2], float4 (&b3)[2], const char* w, unsigned lo,
-                                              int g, f32x16 (&acc)[2]) {
-    constexpr int NM = SK ? 8 : 16, NL = SK ? 2 : 4, NLN = SKN ? 2 : 4;
-    if constexpr (PER_TAP == 8) {
-        l8_load<1, SK>(sb, cur); l2_loadb<G2>(b2, w, lo, g + 2); L2_PRE(); l8_mma<SK>(sa, b0, acc); l8_post<NM, NL>();
-        l8_load<2, SK>(sa, cur); l2_loadb<G2>(b3, w, lo, g + 3); L2_PRE(); l8_mma<SK>(sb, b1, acc); l8_post<NM, NL>();
-        l8_load<3, SK>(sb, cur); l2_loadb<G2>(b0, w, lo, g + 4); L2_PRE(); l8_mma<SK>(sa, b2, acc); l8_post<NM, NL>();
-        l8_load<4, SK>(sa, cur); l2_loadb<G2>(b1, w, lo, g + 5); L2_PRE(); l8_mma<SK>(sb, b3, acc); l8_post<NM, NL>();
-        l8_load<5, SK>(sb, cur); l2_loadb<G2>(b2, w, lo, g + 6); L2_PRE(); l8_mma<SK>(sa, b0, acc); l8_post<NM, NL>();
-        l8_load<6, SK>(sa, cur); l2_loadb<G2>(b3, w, lo, g + 7); L2_PRE(); l8_mma<SK>(sb, b1, acc); l8_post<NM, NL>();
-        l8_load<7, SK>(sb, cur); l2_loadb<G2>(b0, w, lo, g + 8); L2_PRE(); l8_mma<SK>(sa, b2, acc); l8_post<NM, NL>();
-        l8_load<0, SKN>(sa, nxt); l2_loadb<G2>(b1, w, lo, g + 9); L2_PRE(); l8_mma<SK>(sb, b3, acc); l8_post<NM, NLN>();
-    } else {
-        l8_load<1, SK>(sb, cur); l2_loadb<G2>(b2, w, lo, g + 2); L2_PRE(); l8_mma<SK>(sa, b0, acc); l8_post<NM, NL>();
-        l8_load<2, SK>(sa, cur); l2_loadb<G2>(b3, w, lo, g + 3); L2_PRE(); l8_mma<SK>(sb, b1, acc); l8_post<NM, NL>();
-        l8_load<3, SK>(sb, cur); l2_loadb<G2>(b0, w, lo, g + 4); L2_PRE(); l8_mma<SK>(sa, b2, acc); l8_post<NM, NL>();
-        l8_load<0, SKN>(sa, nxt); l2_loadb<G2>(b1, w, lo, g + 5); L2_PRE(); l8_mma<SK>(sb, b3, acc); l8_post<NM, NLN>();
-    }
-}
-
-// conv_l2 over the eight patches of fused_trunk_kernel: acc[0] = output row OY0 (0 top, 3 bottom), acc[1] = the row next to it
-// (1, 2), channels 32 nw .. 32 nw + 31.  The same k order and weight stream as conv_l2; the taps whose every row of tile 0 is
-// padding run without tile 0 - for the top row the first row of taps, for the bottom row the last, when it lies off the map.
-template <int CIN, int WIN, int PS, int ZP, int STRIDE, int KS, int OY0>
-__device__ __forceinline__ void conv_l8(const float* __restrict__ wp, const float* lds, f32x16 (&acc)[2], int lane, int nw) {
-    constexpr int KGS = KS * KS * CIN / 8, G2 = KGS / 2, PER_TAP = CIN / 16, TAPS = KS * KS, PAD = KS / 2;
-    static_assert(PER_TAP == 4 || PER_TAP == 8, "stage schedule is written for 64 or 128 input channels");
-    static_assert(OY0 == 0 || OY0 == 3, "tile 0 is the top or the bottom output row");
-    constexpr int OY1 = OY0 == 0 ? 1 : 2;
-    constexpr bool SKIP_FIRST = OY0 * STRIDE - PAD < 0;                    // tap row ky = 0 above the map for all of tile 0
-    constexpr bool SKIP_LAST = OY0 * STRIDE + KS - 1 - PAD >= WIN;         // tap row ky = KS - 1 below it
-    static_assert(!(SKIP_FIRST && SKIP_LAST), "one edge per tile");
-    const int i = lane & 31, half = lane >> 5;
-    const int ox = i & 3;
-    const float* S0 = lds + (i >> 2) * SLAB8 + 4 * half;
-    const char* w = reinterpret_cast<const char*>(wp) + (size_t)__builtin_amdgcn_readfirstlane(nw) * KGS * 1024;
-    const unsigned lo = lane * 16;
-    zero(acc[0]); zero(acc[1]);
-    L2Tap cur = l8_tap<WIN, PS, ZP, STRIDE, KS>(0, S0, OY0, OY1, ox);
-    L2Stage sa, sb;
-    float4 b0[2], b1[2], b2[2], b3[2];
-    l2_loadb<G2>(b0, w, lo, 0);
-    l2_loadb<G2>(b1, w, lo, 1);
-    l8_load<0, SKIP_FIRST>(sa, cur);
-    auto tap_at = [&](int t) { return l8_tap<WIN, PS, ZP, STRIDE, KS>(t < TAPS - 1 ? t + 1 : TAPS - 1, S0, OY0, OY1, ox); };
-    int tap = 0;
-    if constexpr (SKIP_FIRST) {
-#pragma unroll 1
-        for (; tap < KS - 1; ++tap) {
-            const L2Tap nxt = tap_at(tap);
-            l8_tap_stages<PER_TAP, G2, true, true>(cur, nxt, sa, sb, b0, b1, b2, b3, w, lo, tap * PER_TAP, acc);
-            cur = nxt;
-        }
-        const L2Tap nxt = tap_at(tap);
-        l8_tap_stages<PER_TAP, G2, true, false>(cur, nxt, sa, sb, b0, b1, b2, b3, w, lo, tap * PER_TAP, acc);
-        cur = nxt;
-        ++tap;
-    }
-    constexpr int END = SKIP_LAST ? TAPS - KS : TAPS;                       // the taps with both tiles: [tap, END)
-#pragma unroll 1
-    for (; tap < END - (SKIP_LAST ? 1 : 0); ++tap) {
-        const L2Tap nxt = tap_at(tap);
-        l8_tap_stages<PER_TAP, G2, false, false>(cur, nxt, sa, sb, b0, b1, b2, b3, w, lo, tap * PER_TAP, acc);
-        cur = nxt;
-    }
-    if constexpr (SKIP_LAST) {
-        {
-            const L2Tap nxt = tap_at(tap);
-            l8_tap_stages<PER_TAP, G2, false, true>(cur, nxt, sa, sb, b0, b1, b2, b3, w, lo, tap * PER_TAP, acc);
-            cur = nxt;
-            ++tap;
-        }
-#pragma unroll 1
-        for (; tap < TAPS; ++tap) {
-            const L2Tap nxt = tap_at(tap);
-            l8_tap_stages<PER_TAP, G2, true, true>(cur, nxt, sa, sb, b0, b1, b2, b3, w, lo, tap * PER_TAP, acc);
-            cur = nxt;
-        }
-    }
-}
-
-// the wave's edge-row or inner-row tiles, by a wave-uniform branch
-template <int CIN, int WIN, int PS, int ZP, int STRIDE, int KS>
-__device__ __forceinline__ void conv_l8_rows(const float* __restrict__ wp, const float* lds, f32x16 (&acc)[2], int lane, int nw,
-                                             bool bottom) {
-    if (bottom) conv_l8<CIN, WIN, PS, ZP, STRIDE, KS, 3>(wp, lds, acc, lane, nw);
-    else conv_l8<CIN, WIN, PS, ZP, STRIDE, KS, 0>(wp, lds, acc, lane, nw);
-}
-
-// ------------------------------------------------------------------ fused_trunk_kernel's 4x4 stage: 16-row tiles
-// The three stride-1 3x3 convolutions at 4x4 (128 -> 128) run on v_mfma_f32_16x16x4_f32: row m of an M-tile = patch m >> 1,
-// position slot m & 1, so a tile is TWO pixel positions of all eight patches and the 16 positions make eight tiles
-// (slot s -> pixel pix0 + s step):
-//   TL TR   row 0, columns 0-1 / 2-3          leave out ky = 0          BL BR   row 3, columns 0-1 / 2-3    leave out ky = 2
-//   LC      column 0, rows 1-2                leave out kx = 0          RC      column 3, rows 1-2          leave out kx = 2
-//   I1 I2   rows 1 / 2, columns 1-2           every tap
-// Wave w computes channels 32 (w & 3) .. + 31 as two 16-channel N-tiles, for set w >> 2: {TL TR LC I1} or {BL BR RC I2} -
-// 27 of 36 tile-taps each, 54 of 72 in all where one output row per tile ran 30 of 36 (960 -> 864 MFMA equivalents per
-// convolution and patch).  The instruction accumulates its four k slots as one fma chain in slot order (lane group
-// g = lane >> 4 is slot g; ipsx_dbg_mfma16_chain, tests/test_mfma16_chain.py), so the two instructions of an aligned 8-group
-// take k (0,4,1,5) and (2,6,3,7): the contract's order.  For a lane group's four k of two 8-groups to lie side by side - ONE
-// ds_read_b128 per tile and 16 k, one 16-byte weight load per N-tile and 16 k - the stage's LDS images keep their channels
-// permuted inside every aligned block of 16 (position t16_pos(c)); store_l8t, t16_store / t16_load and the average pool write and read
-// it so, and ipsx_pack_conv_weight_tile16 packs the weights to match.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define MFMA4(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-
-enum : int { T16_ALL, T16_KY0, T16_KY2, T16_KX0, T16_KX2 };
-struct T16Tile {
-    int pix0, step, skip;
-    bool x0, x3;          // one slot sits in column 0 / 3 and reads the zero row at kx = 0 / 2
-};
-
-__host__ __device__ constexpr T16Tile t16_tile(int set, int t) {
-    constexpr T16Tile tiles[2][4] = {
-        {{0, 1, T16_KY0, true, false}, {2, 1, T16_KY0, false, true}, {4, 4, T16_KX0, true, false}, {5, 1, T16_ALL, false, false}},
-        {{12, 1, T16_KY2, true, false}, {14, 1, T16_KY2, false, true}, {7, 4, T16_KX2, false, true}, {9, 1, T16_ALL, false, false}}};
-    return tiles[set][t];
-}
-
-__host__ __device__ constexpr int t16_pix(int set, int t, int slot) { return t16_tile(set, t).pix0 + slot * t16_tile(set, t).step; }
-
-// the set's live tiles at tap (ky, kx) (bit t)
-__host__ __device__ constexpr int t16_live(int set, int ky, int kx) {
-    int m = 0;
-    for (int t = 0; t < 4; ++t) {
-        const int k = t16_tile(set, t).skip;
-        const bool out = (k == T16_KY0 && ky == 0) || (k == T16_KY2 && ky == 2) || (k == T16_KX0 && kx == 0) || (k == T16_KX2 && kx == 2);
-        if (!out) m |= 1 << t;
-    }
-    return m;
-}
-
-// where channel c (mod 16) lies inside its block of 16: lane group g = (k >> 2) + 2 (k & 1) of k = c & 7 holds it, as
-// component 2 (c >> 3) + ((k >> 1) & 1) of the group's float4 - [0 2 8 10 | 4 6 12 14 | 1 3 9 11 | 5 7 13 15]
-__host__ __device__ constexpr int t16_pos(int c) {
-    return 4 * (((c & 7) >> 2) + 2 * (c & 1)) + 2 * ((c >> 3) & 1) + ((c >> 1) & 1);
-}
-__host__ __device__ constexpr int t16_col(int n) { return (n & ~15) + t16_pos(n & 15); }
-
-constexpr int T16_ID = (ZP2 + 1) * PS2;     // floats into a slab: a second 4x4 image behind the stage's own (the identity's hand-over)
-static_assert(T16_ID + 16 * PS2 <= SLAB8, "the hand-over image fits the slab");
-
-// the operand pointers of one tap row ky, as conv_p1's: p = pixel (y + ky - 1, x) for tiles with a column-0 slot, else
-// (y + ky - 1, x - 1); e = the one tap whose column leaves the map for one slot, the zero row for its lanes
-struct T16Row {
-    const float* p[4];
-    const float* e[4];
-};
-
-template <int SET>
-__device__ __forceinline__ T16Row t16_row(const float* const (&P)[4], const float* Z, const bool (&ok)[4], int ky) {
-    T16Row r;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const T16Tile d = t16_tile(SET, t);
-        const float* c = P[t] + (ky - 1) * 4 * PS2;
-        r.p[t] = d.x0 ? c : c - PS2;
-        r.e[t] = d.x0 ? (ok[t] ? c - PS2 : Z) : (d.x3 ? (ok[t] ? c + PS2 : Z) : c);
-    }
-    return r;
-}
-
-template <int SET>
-__device__ __forceinline__ const float* t16_src(const T16Row& r, int t, int kx) {
-    const T16Tile d = t16_tile(SET, t);
-    if (d.x0) return kx == 0 ? r.e[t] : r.p[t] + (kx - 1) * PS2;
-    if (d.x3 && kx == 2) return r.e[t];
-    return r.p[t] + kx * PS2;
-}
-
-struct T16State {
-    f32x4 acc[4][2];    // [tile][N-tile]
-    float4 a[2][4];     // [stage & 1][tile]: the lane group's four k of 16
-    float4 b[4][2];     // weight ring: slot = stage & 3, refilled 2 stages ahead; [N-tile]
-};
-
-// a stage's interleave of NM MFMAs with its NL LDS reads and 2 weight loads: G MFMAs in front of every load, the weight
-// loads second and fourth (second and third when there are three loads), the rest of the MFMAs at the end
-template <int G, int K, int NL>
-__device__ __forceinline__ void t16_groups() {
-#if IPSX_SPREAD
-    if constexpr (K < NL + 2) {
-        SG_MFMA(G);
-        if constexpr (K == 1 || K == (NL + 1 < 3 ? NL + 1 : 3)) SG_VMEM(1);
-        else SG_LDS(1);
-        t16_groups<G, K + 1, NL>();
-    }
-#endif
-}
-
-template <int NM, int NL>
-__device__ __forceinline__ void t16_post() {
-#if IPSX_SPREAD
-    constexpr int G = (NM - 4) / (NL + 3) > 0 ? (NM - 4) / (NL + 3) : 1;
-    t16_groups<G, 0, NL>();
-    SG_MFMA(NM - G * (NL + 2));
-#endif
-    SB();
-}
-
-__host__ __device__ constexpr int t16_count(int m) { return (m & 1) + (m >> 1 & 1) + (m >> 2 & 1) + (m >> 3 & 1); }
-
-// stage ST (= 8 kx + block of 16 k) of tap row ky: prefetch the next stage's operands of its live tiles (the next row's first
-// when ST = 23: KYN) and the weights two stages on, then this stage's MFMAs - per (tile, N-tile) the four instructions of
-// its 16 k in order, the eight chains interleaved
-template <int SET, int KY, int KYN, int ST>
-__device__ __forceinline__ void t16_stages(T16State& s, const T16Row& cur, const T16Row& nxt, const char* w, unsigned lo, int g0) {
-    if constexpr (ST < 24) {
-        constexpr int KX = ST >> 3, LIVE = t16_live(SET, KY, KX);
-        constexpr bool LAST = ST == 23;
-        constexpr int NKX = LAST ? 0 : (ST + 1) >> 3, NCB = LAST ? 0 : (ST + 1) & 7;
-        constexpr int LIVEN = LAST ? t16_live(SET, KYN, 0) : t16_live(SET, KY, NKX);
-        constexpr int NB = (ST + 1) & 1;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-            if (LIVEN >> t & 1)
-                s.a[NB][t] = *reinterpret_cast<const float4*>(t16_src<SET>(LAST ? nxt : cur, t, NKX) + NCB * 16);
-        {
-            int g = g0 + ST + 2;
-            g = g < 72 ? g : 71;
-            s.b[(ST + 2) & 3][0] = *reinterpret_cast<const float4*>(w + (size_t)g * 2048 + lo);
-            s.b[(ST + 2) & 3][1] = *reinterpret_cast<const float4*>(w + (size_t)g * 2048 + 1024 + lo);
-        }
-        L1_PRE();
-        {
-            const float4 &b0 = s.b[ST & 3][0], &b1 = s.b[ST & 3][1];
-            const float bb[2][4] = {{b0.x, b0.y, b0.z, b0.w}, {b1.x, b1.y, b1.z, b1.w}};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    if (LIVE >> t & 1) {
-                        const float4& aq = s.a[ST & 1][t];
-                        const float av[4] = {aq.x, aq.y, aq.z, aq.w};
-                        s.acc[t][0] = MFMA4(av[j], bb[0][j], s.acc[t][0]);
-                        s.acc[t][1] = MFMA4(av[j], bb[1][j], s.acc[t][1]);
-                    }
-        }
-        t16_post<8 * t16_count(LIVE), t16_count(LIVEN)>();
-        t16_stages<SET, KY, KYN, ST + 1>(s, cur, nxt, w, lo, g0);
-    }
-}
-
-// one tap row: its three taps x 8 blocks of 16 k; leaves cur = the next row's pointers (clamped: the last row's tail prefetch
-// re-reads its own first operands)
-template <int SET, int KY, int KYN>
-__device__ __forceinline__ void t16_tap_row(T16State& s, T16Row& cur, const float* const (&P)[4], const float* Z,
-                                            const bool (&ok)[4], const char* w, unsigned lo, int ky) {
-    const T16Row nxt = t16_row<SET>(P, Z, ok, ky < 2 ? ky + 1 : 2);
-    t16_stages<SET, KY, KYN, 0>(s, cur, nxt, w, lo, ky * 24);
-    cur = nxt;
-}
-
-// conv3x3 (128 -> 128, stride 1, pad 1) of the 4x4 stage over the workgroup's eight slabs: acc[t][h] = tile t of the wave's
-// set, channels 32 nw + 16 h .. + 15.  wp: ipsx_pack_conv_weight_tile16 - per wave 72 blocks of 16 k x 2 N-tiles of 1 KiB.
-template <int SET>
-__device__ __forceinline__ void conv_t16(const float* __restrict__ wp, const float* lds, f32x4 (&acc)[4][2], int lane, int nw) {
-    int m = lane & 15;
-    asm volatile("" : "+v"(m));            // the addresses below are computed per call, not kept live across the stage
-    const int slot = m & 1;
-    const float* S0 = lds + (m >> 1) * SLAB8 + 4 * (lane >> 4);
-    const float* Z = S0 + ZP2 * PS2;
-    const float* P[4];
-    bool ok[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const T16Tile d = t16_tile(SET, t);
-        const int pix = d.pix0 + slot * d.step;
-        P[t] = S0 + pix * PS2;
-        ok[t] = d.x0 ? (pix & 3) != 0 : (pix & 3) != 3;
-    }
-    const char* w = reinterpret_cast<const char*>(wp) + (size_t)__builtin_amdgcn_readfirstlane(nw) * 72 * 2048;
-    const unsigned lo = lane * 16;
-    T16State s;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s.acc[t][h][r] = 0.0f;
-    s.b[0][0] = *reinterpret_cast<const float4*>(w + lo);
-    s.b[0][1] = *reinterpret_cast<const float4*>(w + 1024 + lo);
-    s.b[1][0] = *reinterpret_cast<const float4*>(w + 2048 + lo);
-    s.b[1][1] = *reinterpret_cast<const float4*>(w + 3072 + lo);
-    T16Row cur = t16_row<SET>(P, Z, ok, 0);
-    constexpr int LIVE0 = t16_live(SET, 0, 0);
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-        if (LIVE0 >> t & 1) s.a[0][t] = *reinterpret_cast<const float4*>(t16_src<SET>(cur, t, 0));
-    if constexpr (SET == 0) {                                               // rows ky = 1 and 2 alike
-        t16_tap_row<SET, 0, 1>(s, cur, P, Z, ok, w, lo, 0);
-#pragma unroll 1
-        for (int ky = 1; ky < 3; ++ky) t16_tap_row<SET, 1, 1>(s, cur, P, Z, ok, w, lo, ky);
-    } else {                         // rows ky = 0 and 1 alike: row 1's tail prefetches BL BR for row 2 too, unused (inside the slab)
-#pragma unroll 1
-        for (int ky = 0; ky < 2; ++ky) t16_tap_row<SET, 0, 0>(s, cur, P, Z, ok, w, lo, ky);
-        t16_tap_row<SET, 2, 2>(s, cur, P, Z, ok, w, lo, 2);
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int h = 0; h < 2; ++h) acc[t][h] = s.acc[t][h];
-}
-
-// the wave's four tiles <-> a 4x4 image at `lds` (+ T16_ID: the hand-over image), channels permuted: C reg r of a tile is
-// row 4 (lane >> 4) + r, i.e. patch 2 (lane >> 4) + (r >> 1), slot r & 1
-template <int SET>
-__device__ __forceinline__ void t16_store(float* lds, const f32x4 (&v)[4][2], int lane, int nw) {
-    float* base = lds + 2 * (lane >> 4) * SLAB8 + 32 * nw + t16_pos(lane & 15);
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) base[(r >> 1) * SLAB8 + t16_pix(SET, t, r & 1) * PS2 + 16 * h] = v[t][h][r];
-}
-
-template <int SET>
-__device__ __forceinline__ void t16_load(const float* lds, f32x4 (&v)[4][2], int lane, int nw) {
-    const float* base = lds + 2 * (lane >> 4) * SLAB8 + 32 * nw + t16_pos(lane & 15);
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[t][h][r] = base[(r >> 1) * SLAB8 + t16_pix(SET, t, r & 1) * PS2 + 16 * h];
-}
-
-// write conv_l8's 2 tiles as a 4x4 image of the 16-row stage (channels permuted), at `lds` or at lds + T16_ID: C reg r is
-// tile row (r & 3) + 4 half + 8 (r >> 2), i.e. patch 2 (r >> 2) + half, column r & 3
-__device__ __forceinline__ void store_l8t(float* lds, const f32x16 (&v)[2], int lane, int nw, int oy0, int oy1) {
-    const int i = lane & 31, half = lane >> 5;
-    const int n = t16_col(32 * nw + i);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int pl = 2 * (r >> 2) + half, pix = (mt ? oy1 : oy0) * 4 + (r & 3);
-            lds[pl * SLAB8 + pix * PS2 + n] = v[mt][r];
-        }
-}
-
-// block 0's second convolution and block 1 of layer2 for the wave's set: the slabs hold conv1's output (permuted) and the
-// projected identity at T16_ID on entry, layer2's output (permuted) on return
-template <bool STAMP, int SET>
-__device__ __forceinline__ void layer2_t16(const FusedArgs& a, float* lds, int lane, int wave, unsigned long long* stamps) {
-    constexpr int WPB = 8;
-    const int nw = wave & 3;
-    const int n0 = 32 * nw + (lane & 15);
-    f32x4 idn[4][2], acc[4][2];
-    t16_load<SET>(lds + T16_ID, idn, lane, nw);
-#pragma unroll 1
-    for (int cv = 5; cv < 8; ++cv) {
-        conv_t16<SET>(static_cast<const float*>(a.wh[cv]), lds, acc, lane, nw);
-        const float A[2] = {a.al[cv][n0], a.al[cv][n0 + 16]}, B[2] = {a.sh[cv][n0], a.sh[cv][n0 + 16]};
-        if (cv == 6) {                                                      // block 1 conv1: BN + ReLU only
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float v = __builtin_fmaf(acc[t][h][r], A[h], B[h]);
-                        acc[t][h][r] = v > 0.0f ? v : 0.0f;
-                    }
-        } else {                                                            // conv2 -> BN -> += identity -> ReLU
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        float v = __builtin_fmaf(acc[t][h][r], A[h], B[h]);
-                        v = v + idn[t][h][r];
-                        idn[t][h][r] = v > 0.0f ? v : 0.0f;
-                    }
-        }
-        __syncthreads();                                                    // every wave has read this convolution's input
-        if (cv == 6) t16_store<SET>(lds, acc, lane, nw);
-        else t16_store<SET>(lds, idn, lane, nw);
-        __syncthreads();
-        IPSX_STAMP(7 + cv);
-    }
-}
-
-// ------------------------------------------------------------------ fused_trunk_kernel's layer1: tiled by position
-// The 8x8 stage over the eight patches, tiled as the 4x4 stage is: row m of an M-tile = patch m >> 2, position slot m & 3,
-// so a tile is four pixel positions of all eight patches.  The 64 positions make 16 tiles (slot s -> pixel
-// pix0 + (s & 1) s1 + (s >> 1) s2):
-//   T0 T1   row 0, columns 0-3 / 4-7          leave out ky = 0 (taps 0 1 2): those rows read only the zero padding
-//   B0 B1   row 7, columns 0-3 / 4-7          leave out ky = 2 (taps 6 7 8)
-//   L       column 0, rows 1-4                leave out kx = 0 (taps 0 3 6)
-//   R       column 7, rows 1-4                leave out kx = 2 (taps 2 5 8)
-//   M50 M54 M60 M64   rows 5 and 6, columns 0-3 / 4-7     every tap (one column of lanes reads the padding at kx 0 or 2)
-//   I1-I4   rows 1-4, columns 1-4;  J1 J2  rows 1-2 / 3-4, columns 5-6   interior: no tap leaves the map
-// Wave w computes the 32 channels of N-tile w >> 2 for the four M-tiles of set (w + 2 (w >> 2)) & 3: T {T0 T1 I1 I2},
-// B {B0 B1 I3 I4}, L {L M50 M54 J1}, R {R M60 M64 J2}.  Waves w and w + 4 share a SIMD and hold T + L, B + R, L + T or
-// R + B: 960 + 1,056 MFMAs per convolution on every SIMD, 1,008 per patch where wave = patch needed 1,152.  The taps a
-// tile leaves out are left out in code, by a row loop whose bodies know the live tiles of each tap at compile time; that
-// changes no bit.  LDS banks (ds_read_b128 takes 16 lanes = 4 patches x 4 slots at a time, and the patches
-// lie 16 banks apart): the row tiles' four columns fall on four different 4-bank groups, J1 J2 two ways, L and R
-// (one column) four ways - one of the wave's four operand reads per stage, prefetched a stage ahead.
-enum : int { P1_ALL, P1_KY0, P1_KY2, P1_KX0, P1_KX2 };
-struct P1Tile {
-    int pix0, s1, s2, skip;
-    bool x0, x7;          // some lanes sit in column 0 / 7 and read the zero row at kx = 0 / 2
-};
-
-__host__ __device__ constexpr P1Tile p1_tile(int set, int t) {
-    constexpr P1Tile tiles[4][4] = {
-        {{0, 1, 2, P1_KY0, true, false}, {4, 1, 2, P1_KY0, false, true}, {9, 1, 2, P1_ALL, false, false}, {17, 1, 2, P1_ALL, false, false}},
-        {{56, 1, 2, P1_KY2, true, false}, {60, 1, 2, P1_KY2, false, true}, {25, 1, 2, P1_ALL, false, false}, {33, 1, 2, P1_ALL, false, false}},
-        {{8, 8, 16, P1_KX0, true, false}, {40, 1, 2, P1_ALL, true, false}, {44, 1, 2, P1_ALL, false, true}, {13, 1, 8, P1_ALL, false, false}},
-        {{15, 8, 16, P1_KX2, false, true}, {48, 1, 2, P1_ALL, true, false}, {52, 1, 2, P1_ALL, false, true}, {29, 1, 8, P1_ALL, false, false}}};
-    return tiles[set][t];
-}
-
-__host__ __device__ constexpr int p1_pix(int set, int t, int slot) {
-    return p1_tile(set, t).pix0 + (slot & 1) * p1_tile(set, t).s1 + (slot >> 1) * p1_tile(set, t).s2;
-}
-
-// the set's live tiles at column kx of a tap row (bit t); EDGE: this is the row the set's T or B tiles leave out
-__host__ __device__ constexpr int p1_live(int set, bool edge, int kx) {
-    int m = 0;
-    for (int t = 0; t < 4; ++t) {
-        const int k = p1_tile(set, t).skip;
-        const bool out = ((k == P1_KY0 || k == P1_KY2) && edge) || (k == P1_KX0 && kx == 0) || (k == P1_KX2 && kx == 2);
-        if (!out) m |= 1 << t;
-    }
-    return m;
-}
-
-__host__ __device__ constexpr int p1_count(int m) { return (m & 1) + (m >> 1 & 1) + (m >> 2 & 1) + (m >> 3 & 1); }
-
-// the operand pointers of one tap row ky: p = pixel (y + ky - 1, x) for tiles with a column-0 lane, else (y + ky - 1, x - 1),
-// so that the other taps of the row are p plus an immediate; e = the one tap whose column leaves the map for some lanes
-// (kx = 0 for column-0 tiles, 2 for column-7 tiles), the zero row for those lanes
-struct P1Row {
-    const float* p[4];
-    const float* e[4];
-};
-
-template <int SET>
-__device__ __forceinline__ P1Row p1_row(const float* const (&P)[4], const float* Z, const bool (&ok)[4], int ky) {
-    P1Row r;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const P1Tile d = p1_tile(SET, t);
-        const float* c = P[t] + (ky - 1) * 8 * PS1;
-        r.p[t] = d.x0 ? c : c - PS1;
-        r.e[t] = d.x0 ? (ok[t] ? c - PS1 : Z) : (d.x7 ? (ok[t] ? c + PS1 : Z) : c);
-    }
-    return r;
-}
-
-template <int SET>
-__device__ __forceinline__ const float* p1_src(const P1Row& r, int t, int kx) {
-    const P1Tile d = p1_tile(SET, t);
-    if (d.x0) return kx == 0 ? r.e[t] : r.p[t] + (kx - 1) * PS1;
-    if (d.x7 && kx == 2) return r.e[t];
-    return r.p[t] + kx * PS1;
-}
-
-struct P1State {
-    f32x16 acc[4];
-    float4 a[2][4];     // [stage & 1][tile]: 4 consecutive k of this lane's half
-    float4 b[4];        // weight ring: slot = stage & 3, refilled 2 stages ahead
-};
-
-// a stage's interleave of NM MFMAs with its NL LDS reads and 1 weight load: the loads 2 MFMAs apart (1 when there are
-// more loads than that leaves room for), the weight load in the middle, 4 or more MFMAs at the end
-template <int G, int K, int NL>
-__device__ __forceinline__ void p1_groups() {
-#if IPSX_SPREAD
-    if constexpr (K <= NL) {
-        SG_MFMA(G);
-        if constexpr (K == NL / 2) SG_VMEM(1);
-        else SG_LDS(1);
-        p1_groups<G, K + 1, NL>();
-    }
-#endif
-}
-
-template <int NM, int NL>
-__device__ __forceinline__ void p1_post() {
-#if IPSX_SPREAD
-    constexpr int G = (NM - 4) / (NL + 1) > 0 ? (NM - 4) / (NL + 1) : 1;
-    p1_groups<G, 0, NL>();
-    SG_MFMA(NM - G * (NL + 1));
-#endif
-    SB();
-}
-
-// stage ST (= 8 kx + k-group) of tap row ky: prefetch the next stage's operands of its live tiles (the next row's first
-// when ST = 23) and the weights two stages on, then this stage's MFMAs - per tile the contract's k order, as conv_l1
-template <int SET, bool EDGE, bool EDGEN, int ST>
-__device__ __forceinline__ void p1_stages(P1State& s, const P1Row& cur, const P1Row& nxt, const char* w, unsigned lo, int g0) {
-    if constexpr (ST < 24) {
-        constexpr int KX = ST >> 3, LIVE = p1_live(SET, EDGE, KX);
-        constexpr bool LAST = ST == 23;
-        constexpr int NKX = LAST ? 0 : (ST + 1) >> 3, NCG = LAST ? 0 : (ST + 1) & 7;
-        constexpr int LIVEN = LAST ? p1_live(SET, EDGEN, 0) : p1_live(SET, EDGE, NKX);
-        constexpr int NB = (ST + 1) & 1;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-            if (LIVEN >> t & 1)
-                s.a[NB][t] = *reinterpret_cast<const float4*>(p1_src<SET>(LAST ? nxt : cur, t, NKX) + NCG * 8);
-        {
-            int g = g0 + ST + 2;
-            g = g < 72 ? g : 71;
-            s.b[(ST + 2) & 3] = *reinterpret_cast<const float4*>(w + (size_t)g * 1024 + lo);
-        }
-        L1_PRE();
-        {
-            const float4& bq = s.b[ST & 3];
-            const float bb[4] = {bq.x, bq.y, bq.z, bq.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-                    if (LIVE >> t & 1) {
-                        const float4& aq = s.a[ST & 1][t];
-                        const float av[4] = {aq.x, aq.y, aq.z, aq.w};
-                        s.acc[t] = MFMA(av[j], bb[j], s.acc[t]);
-                    }
-        }
-        p1_post<4 * p1_count(LIVE), p1_count(LIVEN)>();
-        p1_stages<SET, EDGE, EDGEN, ST + 1>(s, cur, nxt, w, lo, g0);
-    }
-}
-
-// one tap row: its three taps x 8 k-groups; leaves cur = the next row's pointers (ky + 1, clamped: the last row's tail
-// prefetch re-reads its own first operands, as conv_l1's does)
-template <int SET, bool EDGE, bool EDGEN>
-__device__ __forceinline__ void p1_tap_row(P1State& s, P1Row& cur, const float* const (&P)[4], const float* Z,
-                                           const bool (&ok)[4], const char* w, unsigned lo, int ky) {
-    const P1Row nxt = p1_row<SET>(P, Z, ok, ky < 2 ? ky + 1 : 2);
-    p1_stages<SET, EDGE, EDGEN, 0>(s, cur, nxt, w, lo, ky * 24);
-    cur = nxt;
-}
-
-// conv3x3 (64 -> 64, stride 1, pad 1) of layer1 over the workgroup's eight slabs: acc[t] = tile t of the wave's set, channels
-// 32 nt .. 32 nt + 31.  Same k order and weight stream as conv_l1 (packed: 2 n-tiles x 72 k-groups of 1 KiB).
-template <int SET>
-__device__ __forceinline__ void conv_p1(const float* __restrict__ wp, const float* lds, f32x16 (&acc)[4], int lane, int nt) {
-    int i = lane & 31;
-    asm volatile("" : "+v"(i));            // the addresses below are computed per call, not kept live across layer1
-    const int half = lane >> 5, slot = i & 3;
-    const float* S0 = lds + (i >> 2) * SLAB8 + 4 * half;
-    const float* Z = S0 + ZP1 * PS1;
-    const float* P[4];
-    bool ok[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const P1Tile d = p1_tile(SET, t);
-        const int pix = d.pix0 + (slot & 1) * d.s1 + (slot >> 1) * d.s2;
-        P[t] = S0 + pix * PS1;
-        ok[t] = d.x0 ? (pix & 7) != 0 : (pix & 7) != 7;
-    }
-    const char* w = reinterpret_cast<const char*>(wp) + (size_t)__builtin_amdgcn_readfirstlane(nt) * 72 * 1024;
-    const unsigned lo = lane * 16;
-    P1State s;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) zero(s.acc[t]);
-    s.b[0] = *reinterpret_cast<const float4*>(w + lo);
-    s.b[1] = *reinterpret_cast<const float4*>(w + 1024 + lo);
-    P1Row cur = p1_row<SET>(P, Z, ok, 0);
-    constexpr int LIVE0 = p1_live(SET, SET == 0, 0);
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-        if (LIVE0 >> t & 1) s.a[0][t] = *reinterpret_cast<const float4*>(p1_src<SET>(cur, t, 0));
-    if constexpr (SET == 0) {                                               // T: row ky = 0 without T0 T1
-        p1_tap_row<SET, true, false>(s, cur, P, Z, ok, w, lo, 0);
-#pragma unroll 1
-        for (int ky = 1; ky < 3; ++ky) p1_tap_row<SET, false, false>(s, cur, P, Z, ok, w, lo, ky);
-    } else if constexpr (SET == 1) {                                        // B: row ky = 2 without B0 B1
-        p1_tap_row<SET, false, false>(s, cur, P, Z, ok, w, lo, 0);
-        p1_tap_row<SET, false, true>(s, cur, P, Z, ok, w, lo, 1);
-        p1_tap_row<SET, true, true>(s, cur, P, Z, ok, w, lo, 2);
-    } else {                                                                // L, R: a column of taps out in every row
-#pragma unroll 1
-        for (int ky = 0; ky < 3; ++ky) p1_tap_row<SET, false, false>(s, cur, P, Z, ok, w, lo, ky);
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) acc[t] = s.acc[t];
-}
-
-// the wave's four tiles <-> the slabs' [pix][c] layout: C reg r is tile row (r & 3) + 4 half + 8 (r >> 2), i.e. patch
-// 2 (r >> 2) + half, slot r & 3
-template <int SET>
-__device__ __forceinline__ void store_p1(float* lds, const f32x16 (&v)[4], int lane, int nt) {
-    int o = (lane >> 5) * SLAB8 + 32 * nt + (lane & 31);
-    asm volatile("" : "+v"(o));            // as in conv_p1: addresses per call
-    float* base = lds + o;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) base[2 * (r >> 2) * SLAB8 + p1_pix(SET, t, r & 3) * PS1] = v[t][r];
-}
-
-template <int SET>
-__device__ __forceinline__ void load_p1(const float* lds, f32x16 (&v)[4], int lane, int nt) {
-    const float* base = lds + (lane >> 5) * SLAB8 + 32 * nt + (lane & 31);
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) v[t][r] = base[2 * (r >> 2) * SLAB8 + p1_pix(SET, t, r & 3) * PS1];
-}
-
-// layer1 of fused_trunk_kernel (two BasicBlocks at 8x8) for the wave's set; the slabs hold the stem's output on entry and
-// layer1's on return.  Every convolution reads all eight slabs, so its epilogue writes in place between two barriers.
-template <bool STAMP, int SET>
-__device__ __forceinline__ void layer1_p1(const FusedArgs& a, float* lds, int lane, int wave, unsigned long long* stamps) {
-    constexpr int WPB = 8;                                                  // stamp rows: fused_trunk_kernel's eight waves
-    const int nt = wave >> 2, n = 32 * nt + (lane & 31);
-    f32x16 idn[4], acc[4];
-    load_p1<SET>(lds, idn, lane, nt);                                      // identity of block 1
-#pragma unroll 1
-    for (int cv = 0; cv < 4; ++cv) {
-        conv_p1<SET>(a.w[cv], lds, acc, lane, nt);
-        IPSX_STAMP(3 + 2 * cv);
-        const float A = a.al[cv][n], B = a.sh[cv][n];
-        if ((cv & 1) == 0) {                                                // conv1 -> BN -> ReLU
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float v = __builtin_fmaf(acc[t][r], A, B);
-                    acc[t][r] = v > 0.0f ? v : 0.0f;
-                }
-        } else {                                                            // conv2 -> BN -> += identity -> ReLU
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    float v = __builtin_fmaf(acc[t][r], A, B);
-                    v = v + idn[t][r];
-                    idn[t][r] = v > 0.0f ? v : 0.0f;
-                }
-        }
-        __syncthreads();                                                    // every wave has read this convolution's input
-        if (cv & 1) store_p1<SET>(lds, idn, lane, nt);
-        else store_p1<SET>(lds, acc, lane, nt);
-        __syncthreads();
-        IPSX_STAMP(4 + 2 * cv);
-    }
-}
-
-// PARTS (ipsx_trunk_encode_parts): ONE launch encodes the index lists of every part of a call, one after the other, and says
-// how far each part has come - done[k] counts the patches of part k whose embeddings are written AND visible to the whole
-// device, so that a one-wave wait kernel on another stream (part_wait_kernel, scorer.hip) can let the part's logits and loop
-// iterations go while later parts are still being encoded.  A launch boundary per part drains the chip.
-struct PartsArgs {
-    int* done;               // [parts] device counters, zeroed by the caller in front of the launch
-    int parts;
-    int part_end[16];        // exclusive prefix ends of the parts, in list entries
-};
-
-// Entries [lo, hi) of the list are stored by this workgroup: make them visible, then count them into their parts.
-// The hand-over: every storing wavefront drains its stores, the workgroup meets, ONE thread releases at agent scope (the
-// write-back of this XCD's L2 - per-XCD L2s are not coherent) and only then adds, relaxed, at agent scope.  The explicit
-// waits are inline assembly on purpose: the compiler may drop the wait behind the write-back when it believes the
-// wavefront's memory counter empty, and the add must not overtake it.
-__device__ __forceinline__ void parts_count(const PartsArgs& pa, int lo, int hi) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        int begin = 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {                                    // (constant indices: part_end stays in the kernel arguments)
-            if (k < pa.parts) {
-                const int end = pa.part_end[k];
-                const int c = (hi < end ? hi : end) - (lo > begin ? lo : begin);
-                if (c > 0) __hip_atomic_fetch_add(pa.done + k, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                begin = end;
-            }
-        }
-    }
-}
-
-template <bool STAMP, bool U8, bool PARTS = false, bool VIEW = false>
-__device__ __forceinline__ void fused_trunk_body(const FusedArgs& a, unsigned long long* stamps, const float* table,
-                                                 const PartsArgs* pa = nullptr, const ViewArgs* va = nullptr) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];          // 8 slabs of SLAB8
-    constexpr int WPB = 8;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i = lane & 31;
-    const long long p_first = (long long)blockIdx.x * 8;
-    const long long n_valid = a.count ? (long long)*a.count : a.n;        // compacted launches read their length on device
-    if (p_first >= n_valid) return;                                       // workgroup-uniform
-    long long pi = p_first + wave;
-    if (pi >= n_valid) pi = n_valid - 1;                                  // tail: recompute a valid patch, store nothing
-    if (a.index) pi = a.index[pi];
-    else if constexpr (VIEW) pi += va->first;
-    trunk_front<STAMP, WPB, U8, VIEW>(a, pi, lds + wave * SLAB8, lane, wave, stamps, table, va);
-    switch (__builtin_amdgcn_readfirstlane((wave + 2 * (wave >> 2)) & 3)) {  // the wave's layer1 tile set, see conv_p1
-        case 0: layer1_p1<STAMP, 0>(a, lds, lane, wave, stamps); break;
-        case 1: layer1_p1<STAMP, 1>(a, lds, lane, wave, stamps); break;
-        case 2: layer1_p1<STAMP, 2>(a, lds, lane, wave, stamps); break;
-        default: layer1_p1<STAMP, 3>(a, lds, lane, wave, stamps); break;
-    }
-
-    // ---- layer2 block 0: conv3x3/2 (64->128) and the 1x1/2 projection read the 8x8 stage
-    const int nw = wave & 3;
-    const bool bottom = __builtin_amdgcn_readfirstlane(wave) >= 4;        // wave-uniform: tiles oy 3 + 2, else 0 + 1
-    const int oy0 = bottom ? 3 : 0, oy1 = bottom ? 2 : 1;
-    const int n2 = 32 * nw + i;
-    f32x16 t2[2], id2[2];
-    conv_l8_rows<64, 8, PS1, ZP1, 2, 3>(a.w[4], lds, t2, lane, nw, bottom);
-    conv_l8_rows<64, 8, PS1, ZP1, 2, 1>(a.w_down, lds, id2, lane, nw, bottom);
-    IPSX_STAMP(11);
-    {
-        const float A = a.al[4][n2], B = a.sh[4][n2], Ad = a.a_down[n2], Bd = a.s_down[n2];
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float v = __builtin_fmaf(t2[mt][r], A, B);
-                t2[mt][r] = v > 0.0f ? v : 0.0f;
-                id2[mt][r] = __builtin_fmaf(id2[mt][r], Ad, Bd);
-            }
-    }
-    __syncthreads();
-    store_l8t(lds, t2, lane, nw, oy0, oy1);
-    store_l8t(lds + T16_ID, id2, lane, nw, oy0, oy1);                     // the identity, into the 16-row tiles' registers below
-    for (int z = lane; z < PS2; z += 64) lds[wave * SLAB8 + ZP2 * PS2 + z] = 0.0f;  // zero pixel row of the 4x4 stage
-    __syncthreads();
-    // conv2 of block 0, then block 1 (conv1, conv2), all 128->128 at 4x4, on 16-row tiles
-    if (bottom) layer2_t16<STAMP, 1>(a, lds, lane, wave, stamps);
-    else layer2_t16<STAMP, 0>(a, lds, lane, wave, stamps);
-
-    // ---- global average pool over the 16 pixels, sequential order
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int o = threadIdx.x + 512 * h;
-        const int pl = o >> 7, n = o & 127;
-        const float* s = lds + pl * SLAB8 + t16_col(n);                   // the stage's channel permutation, undone
-        float sum = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) sum = sum + s[k * PS2];
-        if (p_first + pl < n_valid) a.emb[(size_t)(p_first + pl) * 128 + n] = sum / 16.0f;
-    }
-    IPSX_STAMP(15);
-    if constexpr (PARTS) {
-        const long long p_end = p_first + 8 < n_valid ? p_first + 8 : n_valid;
-        parts_count(*pa, (int)p_first, (int)p_end);
-    }
-}
-
-template <bool STAMP>
-__global__ __launch_bounds__(512, 1) void fused_trunk_kernel(FusedArgs a, unsigned long long* stamps) {
-    fused_trunk_body<STAMP, false>(a, stamps, nullptr);
-}
-
-// the same, counting its patches into the parts of the call (PartsArgs)
-__global__ __launch_bounds__(512, 1) void fused_trunk_parts_kernel(FusedArgs a, PartsArgs pa) {
-    fused_trunk_body<false, false, true>(a, nullptr, nullptr, &pa);
-}
-
-// the same on uint8 patches (a.patches: bytes; table: 256 floats) - only the input load differs (trunk_front)
-__global__ __launch_bounds__(512, 1) void fused_trunk_u8_kernel(FusedArgs a, const float* table) {
-    fused_trunk_body<false, true>(a, nullptr, table);
-}
-
-// the same reading its patches through a patch-grid view (a.patches: whole images) - only the input load differs (trunk_front)
-__global__ __launch_bounds__(512, 1) void fused_trunk_view_kernel(FusedArgs a, ViewArgs va) {
-    fused_trunk_body<false, false, false, true>(a, nullptr, nullptr, nullptr, &va);
-}
-
-// ... through a view of whole uint8 images (a.patches: bytes; table: 256 floats)
-__global__ __launch_bounds__(512, 1) void fused_trunk_view_u8_kernel(FusedArgs a, const float* table, ViewArgs va) {
-    fused_trunk_body<false, true, false, true>(a, nullptr, table, nullptr, &va);
-}
-
-__global__ __launch_bounds__(512, 1) void fused_trunk_parts_view_kernel(FusedArgs a, PartsArgs pa, ViewArgs va) {
-    fused_trunk_body<false, false, true, true>(a, nullptr, nullptr, &pa, &va);
-}
-
-// the counted launch on uint8 patches and on whole uint8 images: the uint8 kernels' staging, the parts' count at the end
-__global__ __launch_bounds__(512, 1) void fused_trunk_parts_u8_kernel(FusedArgs a, PartsArgs pa, const float* table) {
-    fused_trunk_body<false, true, true>(a, nullptr, table, &pa);
-}
-
-__global__ __launch_bounds__(512, 1) void fused_trunk_parts_view_u8_kernel(FusedArgs a, PartsArgs pa, const float* table,
-                                                                          ViewArgs va) {
-    fused_trunk_body<false, true, true, true>(a, nullptr, table, &pa, &va);
-}
-
+#include "fused_trunk_eight.h"
 #include "fused_trunk_split.h"
 #include "fused_trunk_bf16.h"
 #include "fused_trunk_pair.h"
@@ -1858,6 +1005,29 @@ static ViewArgs fused_view_args(const PatchSrc& src, int widest = 16) {
 
 static const size_t FUSED_LDS = (size_t)8 * SLAB8 * sizeof(float);    // 141,824 B: one workgroup of eight per CU
 
+// every fused trunk kernel that asks for more dynamic LDS than the default limit, with what it asks for: set once
+static void fused_lds_attrs() {
+    static bool attr_set = false;
+    if (attr_set) return;
+    const struct { const void* kernel; size_t bytes; } list[] = {
+        {reinterpret_cast<const void*>(fused_trunk_x3_kernel<false>), 4 * XL<3>::SLAB},
+        {reinterpret_cast<const void*>(fused_trunk_x3_kernel<true>), 4 * XL<3>::SLAB},
+        {reinterpret_cast<const void*>(fused_trunk_bf16_kernel<false>), BF16_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_bf16_kernel<true>), BF16_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_kernel<false>), FUSED_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_kernel<true>), FUSED_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_u8_kernel), FUSED_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_view_kernel), FUSED_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_view_u8_kernel), FUSED_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_parts_kernel), FUSED_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_parts_view_kernel), FUSED_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_parts_u8_kernel), FUSED_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_parts_view_u8_kernel), FUSED_LDS},
+    };
+    for (const auto& e : list) (void)hipFuncSetAttribute(e.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e.bytes);
+    attr_set = true;
+}
+
 // `n` patches of `src` (checked by the entry: patch_src_check) -> emb.  A table or a view: the exact fp32 trunk only, no
 // stamps, no device-side count.
 int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, hipStream_t s, const int* count,
@@ -1869,22 +1039,7 @@ int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb
     bool bf16 = t->precision != 0 && a.wh_down && a.wh_stem;
     for (int k = 0; k < 8; ++k) bf16 = bf16 && a.wh[k];
     if (t->precision != 0 && !bf16) return fail(IPSX_EINVAL, "fused trunk: precision %d needs w_packed_bf16 on the stem (ipsx_pack_stem_weight_split) and every block conv", t->precision);
-    static bool attr_set = false;
-    if (!attr_set) {
-        const auto lds_of = [](const void* kernel, size_t bytes) {
-            (void)hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        };
-        lds_of(reinterpret_cast<const void*>(fused_trunk_x3_kernel<false>), 4 * XL<3>::SLAB);
-        lds_of(reinterpret_cast<const void*>(fused_trunk_x3_kernel<true>), 4 * XL<3>::SLAB);
-        lds_of(reinterpret_cast<const void*>(fused_trunk_bf16_kernel<false>), BF16_LDS);
-        lds_of(reinterpret_cast<const void*>(fused_trunk_bf16_kernel<true>), BF16_LDS);
-        lds_of(reinterpret_cast<const void*>(fused_trunk_kernel<false>), FUSED_LDS);
-        lds_of(reinterpret_cast<const void*>(fused_trunk_kernel<true>), FUSED_LDS);
-        lds_of(reinterpret_cast<const void*>(fused_trunk_u8_kernel), FUSED_LDS);
-        lds_of(reinterpret_cast<const void*>(fused_trunk_view_kernel), FUSED_LDS);
-        lds_of(reinterpret_cast<const void*>(fused_trunk_view_u8_kernel), FUSED_LDS);
-        attr_set = true;
-    }
+    fused_lds_attrs();
     if (t->precision == 2 || t->precision == 1) {      // the trunks on the bf16 matrix pipe (fused_trunk_split.h, fused_trunk_bf16.h)
         const dim3 block(256);
         if (t->precision == 2) {                       // fp32x3: four patches per workgroup
@@ -1971,18 +1126,7 @@ int fused_trunk_encode_parts(const ipsx_trunk* t, const PatchSrc& src, int64_t n
     if (!(a.wh[5] && a.wh[6] && a.wh[7]))
         return fail(IPSX_EINVAL, "trunk_encode_parts: the exact fp32 trunk needs ipsx_pack_conv_weight_tile16 of its three "
                     "128 -> 128 convolutions in their w_packed_bf16");
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_parts_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_parts_view_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_parts_u8_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fused_trunk_parts_view_u8_kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)FUSED_LDS);
-        attr_set = true;
-    }
+    fused_lds_attrs();
     const dim3 grid((unsigned)cdiv(n, 8));
     // the storage kinds differ in the kernels' last arguments only (the table, the view, both, nothing), as in fused_launch
     if (src.table && src.view) {                                      // whole uint8 images
@@ -2166,20 +1310,32 @@ extern "C" __attribute__((visibility("default"))) int ipsx_dbg_mfma16_chain(cons
     return ipsx::launched("mfma16_chain");
 }
 
-// ipsx_dbg_tile16_layout (host only): the 4x4 stage's tiles as the kernel's tables have them - tiles[8][4] = (first pixel,
-// second pixel, skipped tap row ky or -1, skipped tap column kx or -1), tile 4 s + t = tile t of set s; wave_set[8] = the set
-// of wave w; live[2][9] = the set's live tiles at tap 3 ky + kx (bit t); pos[16] = position of channel c in its block of 16.
-extern "C" __attribute__((visibility("default"))) void ipsx_dbg_tile16_layout(int* tiles, int* wave_set, int* live, int* pos) {
-    for (int s = 0; s < 2; ++s)
+// The position tiles as the kernel's tables have them (host only), for a trait G of S slots: tiles[4 sets][S + 2] = (the
+// tile's S pixels, skipped tap row ky or -1, skipped tap column kx or -1), tile 4 s + t = tile t of set s; wave_set[8] = the
+// set of wave w; live[sets][9] = the set's live tiles at tap 3 ky + kx (bit t).
+template <class G>
+static void dbg_tile_layout(int* tiles, int* wave_set, int* live) {
+    constexpr int S = 1 << G::SLOT_BITS;
+    for (int s = 0; s < G::SETS; ++s)
         for (int t = 0; t < 4; ++t) {
-            const ipsx::T16Tile d = ipsx::t16_tile(s, t);
-            int* o = tiles + 4 * (4 * s + t);
-            o[0] = ipsx::t16_pix(s, t, 0); o[1] = ipsx::t16_pix(s, t, 1);
-            o[2] = d.skip == ipsx::T16_KY0 ? 0 : d.skip == ipsx::T16_KY2 ? 2 : -1;
-            o[3] = d.skip == ipsx::T16_KX0 ? 0 : d.skip == ipsx::T16_KX2 ? 2 : -1;
+            const int skip = G::tile(s, t).skip;
+            int* o = tiles + (S + 2) * (4 * s + t);
+            for (int slot = 0; slot < S; ++slot) o[slot] = ipsx::pt_pix<G>(s, t, slot);
+            o[S] = skip == ipsx::PT_KY0 ? 0 : skip == ipsx::PT_KY2 ? 2 : -1;
+            o[S + 1] = skip == ipsx::PT_KX0 ? 0 : skip == ipsx::PT_KX2 ? 2 : -1;
         }
-    for (int w = 0; w < 8; ++w) wave_set[w] = w >> 2;
-    for (int s = 0; s < 2; ++s)
-        for (int tap = 0; tap < 9; ++tap) live[9 * s + tap] = ipsx::t16_live(s, tap / 3, tap % 3);
+    for (int w = 0; w < 8; ++w) wave_set[w] = G::set_of_wave(w);
+    for (int s = 0; s < G::SETS; ++s)
+        for (int tap = 0; tap < 9; ++tap) live[9 * s + tap] = ipsx::pt_live<G>(s, tap / 3, tap % 3);
+}
+
+// ipsx_dbg_tile16_layout: the 4x4 stage's (Geo4: tiles[8][4], live[2][9]) and pos[16] = position of channel c in its block of
+// 16; ipsx_dbg_layer1_layout: layer1's (Geo8: tiles[16][6], live[4][9]; tests/test_layer1_layout_cpu.py)
+extern "C" __attribute__((visibility("default"))) void ipsx_dbg_tile16_layout(int* tiles, int* wave_set, int* live, int* pos) {
+    dbg_tile_layout<ipsx::Geo4>(tiles, wave_set, live);
     for (int c = 0; c < 16; ++c) pos[c] = ipsx::t16_pos(c);
+}
+
+extern "C" __attribute__((visibility("default"))) void ipsx_dbg_layer1_layout(int* tiles, int* wave_set, int* live) {
+    dbg_tile_layout<ipsx::Geo8>(tiles, wave_set, live);
 }
