@@ -105,7 +105,10 @@ extern "C" {
  *         this block are pinned by the tests of the earlier 3.06 additions);
  *         ipsx_pack_conv_weight_tile16 (+ ipsx_packed_conv_weight_tile16_elems) - the fused 1x32x32 trunk at precision 0 runs
  *         its three 128 -> 128 convolutions on 16-row tiles and reads their weights in this packing from
- *         ipsx_conv.w_packed_bf16, which precision 0 did not read before: a caller that left it NULL there is refused */
+ *         ipsx_conv.w_packed_bf16, which precision 0 did not read before: a caller that left it NULL there is refused;
+ *         ipsx_trunk_encode_parts_dedup (+ ipsx_trunk_parts_dedup_workspace_bytes) - ipsx_trunk_encode_parts with exact
+ *         blank-patch dedup inside the counted launch (the minor number stays, as above: the tests of the earlier 3.06
+ *         additions pin it) */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -408,6 +411,20 @@ int ipsx_trunk_encode_dedup(const ipsx_trunk* t, const float* patches, int64_t n
 int ipsx_trunk_encode_dedup_flagged(const ipsx_trunk* t, const float* patches, int64_t n_patch,
                                     const int32_t* nonblank, float* emb, void* workspace,
                                     size_t workspace_bytes, int32_t* n_encoded, void* stream);
+
+/* ipsx_trunk_encode_parts with exact blank-patch dedup inside the one counted launch: emb, done[] and every argument they
+ * share mean what they mean there, and emb is bit for bit what that call writes WHEN blank_emb (128 floats on the device) is
+ * the embedding this trunk gives an all-zero patch - the caller computes it once per weight state, with
+ * ipsx_trunk_encode_parts on one zero patch.  A scan finds the all-zero list entries (-0.0 counts as zero; it stops reading a
+ * patch at the first KiB that holds a non-zero bit), writes blank_emb to their rows and counts them into done[]; an ordered
+ * compaction lists the others, and the trunk launch encodes only those, each to its own row, and counts them.  No copy of the
+ * embeddings, no host synchronisation.  n_encoded (device int32, or NULL) receives the number of entries encoded, the
+ * non-blank ones.  float32 patches, the exact fp32 fused 1x32x32 trunk (precision 0, patch_dtype 0), n_parts <= 16; anything
+ * else: IPSX_EINVAL, nothing launched.  workspace: ipsx_trunk_parts_dedup_workspace_bytes(t, n_index) bytes, 8-byte aligned. */
+size_t ipsx_trunk_parts_dedup_workspace_bytes(const ipsx_trunk* t, int64_t n_index);
+int ipsx_trunk_encode_parts_dedup(const ipsx_trunk* t, const float* patches, const int32_t* index, int64_t n_index, float* emb,
+                                  const int64_t* part_end, int n_parts, int32_t* done, const float* blank_emb, void* workspace,
+                                  size_t workspace_bytes, int32_t* n_encoded, void* stream);
 
 /* ---------------------------------------------------------- image -> patches
  * The step that feeds ips(): replaces, for a whole batch on the device,

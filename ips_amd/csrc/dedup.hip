@@ -5,7 +5,9 @@
 // function of the patch (reference architecture/ips_net.py:191-193), so all blank patches share ONE
 // embedding: encode the non-blank patches and a single blank one, then copy.  The result is
 // bit-identical to encoding every patch (same kernel, same inputs) - this is not an approximation.
-// Opt-in (ipsx_trunk_encode_dedup); everything stays on the device, no host synchronisation:
+// Two routes.  Inside the one counted launch of an image batch (ipsx_trunk_encode_parts_dedup, the default there: the second
+// half of this file).  And the explicit one for any call (ipsx_trunk_encode_dedup, IPSX_DEDUP_BLANK=1); everything stays on the
+// device, no host synchronisation:
 //   blank_flags_kernel   one wavefront per patch: is any element non-zero?        (HBM-bound, reads all patches once)
 //   compact_kernel       one workgroup: ordered list of the patches to encode (non-blank ones + the first
 //                        blank), its length, and for every patch the slot of its representative
@@ -71,6 +73,108 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(const float4* __restr
     const long long j = i / row4;
     const int c = (int)(i - j * row4);
     dst[i] = src[(size_t)slot[j] * row4 + c];
+}
+
+// ---- the same dedup inside the one counted launch (ipsx_trunk_encode_parts_dedup): no workspace of embeddings, no scatter
+//   blank_scan_parts_kernel     64 list entries per workgroup: blank or not (with an early exit), the blank entries' rows
+//                               written and counted into their parts, a mask and a count of the others
+//   blank_compact_kernel        many workgroups: the ordered list of the entries to encode, and its length
+//   fused_trunk_parts_dedup_kernel (fused_trunk_eight.h)   encodes those, each to its own row, and counts them
+constexpr int SCAN_ENT = 64;          // list entries per scan workgroup: 16 wavefronts x 4
+constexpr int PATCH_U4 = 256;         // a 1x32x32 float32 patch in 16-byte loads: 4 per lane
+
+__device__ __forceinline__ unsigned nonzero_bits(const uint4& v) { return (v.x | v.y | v.z | v.w) & 0x7FFFFFFFu; }   // -0.0 is zero
+__device__ __forceinline__ unsigned long long low_bits(int b) { return b >= 64 ? ~0ull : (1ull << b) - 1ull; }
+
+// List entry j is patch index[j].  A wavefront takes four entries: the first KiB of each (one 16-byte load per lane, the four
+// in flight together) and, only where that is all zero, the other three.  On data without blank patches a KiB per patch is
+// read.  Blank entry j: emb row j = blank_emb.  The hand-over of those rows is parts_count's (fused_trunk_eight.h): every
+// storing wavefront drained, the workgroup's barrier, one lane's agent-scope release, waited for, then relaxed agent-scope adds.
+__global__ __launch_bounds__(1024) void blank_scan_parts_kernel(const float* __restrict__ x, const int* __restrict__ index, int n,
+                                                                const float* __restrict__ blank_emb, float* __restrict__ emb,
+                                                                PartsArgs pa, unsigned long long* __restrict__ mask,
+                                                                int* __restrict__ cnt) {
+    __shared__ unsigned wbits[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lo = blockIdx.x * SCAN_ENT, j0 = lo + wave * 4;
+    const uint4* p[4];
+    uint4 v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        p[e] = reinterpret_cast<const uint4*>(x) + (size_t)(j0 + e < n ? index[j0 + e] : 0) * PATCH_U4 + lane;
+        v[e] = j0 + e < n ? p[e][0] : uint4{0u, 0u, 0u, 0u};
+    }
+    const float2 be = reinterpret_cast<const float2*>(blank_emb)[lane];
+    unsigned bits = 0;                                                    // the wavefront's non-blank entries
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (j0 + e >= n) break;                                           // wavefront-uniform
+        unsigned any = nonzero_bits(v[e]);
+        if (__ballot(any != 0) == 0ull) {
+            const uint4 a = p[e][64], b = p[e][128], c = p[e][192];
+            any = nonzero_bits(a) | nonzero_bits(b) | nonzero_bits(c);
+        }
+        if (__ballot(any != 0) != 0ull) bits |= 1u << e;
+        else reinterpret_cast<float2*>(emb + (size_t)(j0 + e) * 128)[lane] = be;
+    }
+    if (lane == 0) wbits[wave] = bits;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long m = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) m |= (unsigned long long)wbits[w] << (4 * w);
+        mask[blockIdx.x] = m;
+        cnt[blockIdx.x] = __popcll(m);
+        const unsigned long long blank = ~m & low_bits(n - lo);
+        if (blank) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            int begin = 0;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {                                // (constant indices: part_end stays in the kernel arguments)
+                if (k < pa.parts) {
+                    const int end = pa.part_end[k];
+                    const int b0 = begin - lo, b1 = end - lo;             // the part's entries in this workgroup: bits b0 .. b1 - 1
+                    const int c = b1 <= 0 || b0 >= SCAN_ENT ? 0 : __popcll(blank & low_bits(b1) & ~low_bits(b0 > 0 ? b0 : 0));
+                    if (c > 0) __hip_atomic_fetch_add(pa.done + k, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    begin = end;
+                }
+            }
+        }
+    }
+}
+
+// Ordered compaction with many workgroups: a workgroup takes four scan workgroups' masks (256 entries), sums the counts of the
+// scan workgroups in front of it and writes clist[p] = (j, index[j]) in list order - the trunk then has its patch number with
+// one load; the one that holds the last mask writes the length.
+// Sums of integers: the list depends on the data only, never on timing.
+__global__ __launch_bounds__(256) void blank_compact_kernel(const unsigned long long* __restrict__ mask,
+                                                            const int* __restrict__ cnt, int n_mask,
+                                                            const int* __restrict__ index, int2* __restrict__ clist,
+                                                            int* __restrict__ count, int* __restrict__ n_encoded) {
+    __shared__ int wsum[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int first = blockIdx.x * 4;
+    int sum = 0;
+    for (int i = threadIdx.x; i < first; i += 256) sum += cnt[i];
+#pragma unroll
+    for (int o = 32; o; o >>= 1) sum += __shfl_xor(sum, o);
+    if (lane == 0) wsum[wave] = sum;
+    __syncthreads();
+    const int s = first + wave;
+    if (s >= n_mask) return;
+    int base = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    for (int w = 0; w < wave; ++w) base += cnt[first + w];
+    const unsigned long long m = mask[s];
+    if (m >> lane & 1ull) {
+        const int j = s * SCAN_ENT + lane;
+        clist[base + __popcll(m & ((1ull << lane) - 1ull))] = int2{j, index[j]};
+    }
+    if (s == n_mask - 1 && lane == 0) {
+        *count = base + __popcll(m);
+        if (n_encoded) *n_encoded = base + __popcll(m);
+    }
 }
 
 }  // namespace ipsx
@@ -164,4 +268,41 @@ IPSX_API int ipsx_trunk_encode_dedup_flagged(const ipsx_trunk* t, const float* p
     IPSX_REQUIRE(nonblank, "trunk_encode_dedup_flagged: no flags");
     IPSX_TRY(dedup_needs_f32(t));
     return encode_dedup(t, patches, n_patch, nonblank, emb, workspace, workspace_bytes, n_encoded, stream);
+}
+
+// ---- exact blank-patch dedup inside the one counted launch
+static size_t parts_dedup_masks(int64_t n_index) { return (size_t)cdiv(n_index, (int64_t)SCAN_ENT); }
+
+IPSX_API size_t ipsx_trunk_parts_dedup_workspace_bytes(const ipsx_trunk* t, int64_t n_index) {
+    if (!t || n_index <= 0) return 0;
+    // the scan workgroups' masks (8 B) and counts, the length, the list of the entries to encode (8 B each)
+    return parts_dedup_masks(n_index) * 12 + 256 + (size_t)n_index * 8 + 256;
+}
+
+IPSX_API int ipsx_trunk_encode_parts_dedup(const ipsx_trunk* t, const float* patches, const int32_t* index, int64_t n_index,
+                                           float* emb, const int64_t* part_end, int n_parts, int32_t* done,
+                                           const float* blank_emb, void* workspace, size_t workspace_bytes, int32_t* n_encoded,
+                                           void* stream) {
+    IPSX_REQUIRE(t && patches && index && emb && part_end && done && blank_emb, "trunk_encode_parts_dedup: null pointer");
+    IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_parts_dedup: only the fused 1x32x32 trunk is supported");
+    IPSX_REQUIRE(t->precision == 0 && t->patch_dtype == 0 && t->c_in * t->h * t->w == PATCH_U4 * 4,
+                 "trunk_encode_parts_dedup: blank-patch detection reads float32 patches, on the exact fp32 trunk");
+    PartsArgs pa;
+    IPSX_TRY(parts_args(pa, n_index, part_end, n_parts, done, "trunk_encode_parts_dedup"));
+    IPSX_TRY(parts_trunk_check(t, "trunk_encode_parts_dedup"));          // everything the trunk launch refuses: before the scan
+    const size_t need = ipsx_trunk_parts_dedup_workspace_bytes(t, n_index);
+    if (!workspace || workspace_bytes < need || !at_multiple(workspace, 8))
+        return fail(IPSX_EWORKSPACE, "trunk_encode_parts_dedup: workspace %zu B < %zu B", workspace_bytes, need);
+    hipStream_t s = as_stream(stream);
+    const int n_mask = (int)parts_dedup_masks(n_index);
+    unsigned long long* mask = static_cast<unsigned long long*>(workspace);
+    int* cnt = reinterpret_cast<int*>(mask + n_mask);
+    int* count = reinterpret_cast<int*>(static_cast<unsigned char*>(workspace) + (((size_t)n_mask * 12 + 255) & ~(size_t)255));
+    int2* clist = reinterpret_cast<int2*>(count + 64);
+    blank_scan_parts_kernel<<<dim3((unsigned)n_mask), dim3(1024), 0, s>>>(patches, index, (int)n_index, blank_emb, emb, pa, mask, cnt);
+    IPSX_TRY(launched("blank_scan_parts"));
+    blank_compact_kernel<<<dim3((unsigned)cdiv(n_mask, 4)), dim3(256), 0, s>>>(mask, cnt, n_mask, index, clist, count, n_encoded);
+    IPSX_TRY(launched("blank_compact"));
+    return fused_trunk_encode_parts_compact(t, PatchSrc{patches, nullptr, nullptr, index, 0}, n_index, emb, part_end, n_parts, done,
+                                            clist, count, s);
 }

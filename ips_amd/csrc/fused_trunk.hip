@@ -1023,6 +1023,7 @@ static void fused_lds_attrs() {
         {reinterpret_cast<const void*>(fused_trunk_parts_view_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_parts_u8_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_parts_view_u8_kernel), FUSED_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_parts_dedup_kernel), FUSED_LDS},
     };
     for (const auto& e : list) (void)hipFuncSetAttribute(e.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e.bytes);
     attr_set = true;
@@ -1104,29 +1105,49 @@ int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb
 // does it, is a second launch: 9.42 against 9.45 ms at 40,000 patches, 0.3 % - not kept)
 // src: float32 or uint8 (src.table) patches, or a view of float32 or uint8 images, with the parts' joined index lists (checked
 // by the entry: patch_src_check)
-int fused_trunk_encode_parts(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, const int64_t* part_end, int parts,
-                             int* done, hipStream_t s) {
-    if (t->precision != 0 || t->patch_dtype != 0)
-        return fail(IPSX_EINVAL, "trunk_encode_parts: the exact fp32 trunk on float32 or uint8 patches only (precision %d, "
-                    "patch_dtype %d)", t->precision, t->patch_dtype);
-    if (!src.index) return fail(IPSX_EINVAL, "trunk_encode_parts: the parts are index lists");
-    if (parts < 1 || parts > 16) return fail(IPSX_EINVAL, "trunk_encode_parts: %d parts (1 .. 16)", parts);
-    if (n <= 0 || n > 0x7FFFFFF0ll) return fail(IPSX_EINVAL, "trunk_encode_parts: %lld patches", (long long)n);
-    PartsArgs pa;
+int parts_args(PartsArgs& pa, int64_t n, const int64_t* part_end, int parts, int* done, const char* what) {
+    if (parts < 1 || parts > 16) return fail(IPSX_EINVAL, "%s: %d parts (1 .. 16)", what, parts);
+    if (n <= 0 || n > 0x7FFFFFF0ll) return fail(IPSX_EINVAL, "%s: %lld patches", what, (long long)n);
     pa.done = done; pa.parts = parts;
     for (int k = 0; k < 16; ++k) pa.part_end[k] = 0;
     int64_t before = 0;
     for (int k = 0; k < parts; ++k) {
         if (part_end[k] <= before || part_end[k] > n)
-            return fail(IPSX_EINVAL, "trunk_encode_parts: part_end must increase and end on the list's length");
+            return fail(IPSX_EINVAL, "%s: part_end must increase and end on the list's length", what);
         pa.part_end[k] = (int)(before = part_end[k]);
     }
-    if (before != n) return fail(IPSX_EINVAL, "trunk_encode_parts: part_end must increase and end on the list's length");
-    const FusedArgs a = fused_args(t, src, n, emb, false);
-    if (!(a.wh[5] && a.wh[6] && a.wh[7]))
-        return fail(IPSX_EINVAL, "trunk_encode_parts: the exact fp32 trunk needs ipsx_pack_conv_weight_tile16 of its three "
-                    "128 -> 128 convolutions in their w_packed_bf16");
+    if (before != n) return fail(IPSX_EINVAL, "%s: part_end must increase and end on the list's length", what);
+    return IPSX_OK;
+}
+
+// what every counted launch asks of its trunk (`what`: the entry's name in the messages)
+int parts_trunk_check(const ipsx_trunk* t, const char* what) {
+    if (t->precision != 0 || t->patch_dtype != 0)
+        return fail(IPSX_EINVAL, "%s: the exact fp32 trunk on float32 or uint8 patches only (precision %d, "
+                    "patch_dtype %d)", what, t->precision, t->patch_dtype);
+    if (!(t->blocks[2].conv[1].w_packed_bf16 && t->blocks[3].conv[0].w_packed_bf16 && t->blocks[3].conv[1].w_packed_bf16))
+        return fail(IPSX_EINVAL, "%s: the exact fp32 trunk needs ipsx_pack_conv_weight_tile16 of its three "
+                    "128 -> 128 convolutions in their w_packed_bf16", what);
+    return IPSX_OK;
+}
+
+// ... and of its list, and its common arguments
+static int parts_launch_args(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, const int64_t* part_end, int parts,
+                             int* done, const char* what, FusedArgs& a, PartsArgs& pa) {
+    if (t->precision != 0 || t->patch_dtype != 0) return parts_trunk_check(t, what);       // (in front of the list's checks, as ever)
+    if (!src.index) return fail(IPSX_EINVAL, "%s: the parts are index lists", what);
+    IPSX_TRY(parts_args(pa, n, part_end, parts, done, what));
+    IPSX_TRY(parts_trunk_check(t, what));
+    a = fused_args(t, src, n, emb, false);
     fused_lds_attrs();
+    return IPSX_OK;
+}
+
+int fused_trunk_encode_parts(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, const int64_t* part_end, int parts,
+                             int* done, hipStream_t s) {
+    FusedArgs a;
+    PartsArgs pa;
+    IPSX_TRY(parts_launch_args(t, src, n, emb, part_end, parts, done, "trunk_encode_parts", a, pa));
     const dim3 grid((unsigned)cdiv(n, 8));
     // the storage kinds differ in the kernels' last arguments only (the table, the view, both, nothing), as in fused_launch
     if (src.table && src.view) {                                      // whole uint8 images
@@ -1143,6 +1164,20 @@ int fused_trunk_encode_parts(const ipsx_trunk* t, const PatchSrc& src, int64_t n
     }
     fused_trunk_parts_kernel<<<grid, dim3(512), FUSED_LDS, s>>>(a, pa);
     return launched("fused_trunk_parts");
+}
+
+// The counted launch behind the blank scan: the grid is sized for a list without a blank entry, and the workgroups beyond
+// *count return at once.  float32 patches through their index list only.
+int fused_trunk_encode_parts_compact(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, const int64_t* part_end,
+                                     int parts, int* done, const int2* clist, const int* count, hipStream_t s) {
+    FusedArgs a;
+    PartsArgs pa;
+    IPSX_TRY(parts_launch_args(t, src, n, emb, part_end, parts, done, "trunk_encode_parts_dedup", a, pa));
+    if (src.table || src.view || !clist || !count)
+        return fail(IPSX_EINVAL, "trunk_encode_parts_dedup: float32 patches through an index list, with the scan's list and count");
+    a.count = count;
+    fused_trunk_parts_dedup_kernel<<<dim3((unsigned)cdiv(n, 8)), dim3(512), FUSED_LDS, s>>>(a, pa, clist);
+    return launched("fused_trunk_parts_dedup");
 }
 
 // One image through the fused trunk as ONE persistent launch that feeds a resident selection loop (fused_trunk_stream_kernel,

@@ -4,7 +4,8 @@
 //   conv_l8                 the stride-2 3x3 convolution and the 1x1/2 projection from the 8x8 image, tiled by output row
 //   the position-tiled      ONE 3x3 / stride 1 stage over a geometry trait: conv_p1 (layer1, 8x8 map, Geo8) and conv_t16
 //   stage (pt_*)            (the three 128 -> 128 convolutions at 4x4, Geo4), with their epilogue loops layer1_p1, layer2_t16
-//   fused_trunk_body        the kernel, and its eight __global__ entry points (storage kinds x the parts' count)
+//   fused_trunk_body        the kernel, and its nine __global__ entry points (storage kinds x the parts' count, and the
+//                           counted launch behind the blank scan)
 #pragma once
 
 // ------------------------------------------------------------------ fused_trunk_kernel: eight patches per workgroup
@@ -605,16 +606,7 @@ __device__ __forceinline__ void layer1_p1(const FusedArgs& a, float* lds, int la
     }
 }
 
-// PARTS (ipsx_trunk_encode_parts): ONE launch encodes the index lists of every part of a call, one after the other, and says
-// how far each part has come - done[k] counts the patches of part k whose embeddings are written AND visible to the whole
-// device, so that a one-wave wait kernel on another stream (part_wait_kernel, scorer.hip) can let the part's logits and loop
-// iterations go while later parts are still being encoded.  A launch boundary per part drains the chip.
-struct PartsArgs {
-    int* done;               // [parts] device counters, zeroed by the caller in front of the launch
-    int parts;
-    int part_end[16];        // exclusive prefix ends of the parts, in list entries
-};
-
+// PARTS (ipsx_trunk_encode_parts; PartsArgs: ipsx_internal.h).
 // Entries [lo, hi) of the list are stored by this workgroup: make them visible, then count them into their parts.
 // The hand-over: every storing wavefront drains its stores, the workgroup meets, ONE thread releases at agent scope (the
 // write-back of this XCD's L2 - per-XCD L2s are not coherent) and only then adds, relaxed, at agent scope.  The explicit
@@ -639,9 +631,44 @@ __device__ __forceinline__ void parts_count(const PartsArgs& pa, int lo, int hi)
     }
 }
 
-template <bool STAMP, bool U8, bool PARTS = false, bool VIEW = false>
+// The same hand-over behind the blank scan (COMPACT): this workgroup stored the rows of the list entries js[0 .. 7] - increasing,
+// anywhere in the list, -1: none - and counts each into the part its ORIGINAL position lies in.
+__device__ __forceinline__ void parts_count_compact(const PartsArgs& pa, const int* js) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        int j[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) j[e] = js[e];
+        int begin = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {                                    // (constant indices: part_end stays in the kernel arguments)
+            if (k < pa.parts) {
+                const int end = pa.part_end[k];
+                int c = 0;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) c += j[e] >= begin && j[e] < end;
+                if (c > 0) __hip_atomic_fetch_add(pa.done + k, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                begin = end;
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ int* compact_rows() {
+    __shared__ int js[8];
+    return js;
+}
+
+// COMPACT (fused_trunk_parts_dedup_kernel only): workgroup b takes the entries clist[8 b .. 8 b + 7] below *a.count of the
+// call's list.  clist[p] = (j, a.index[j]): patch .y -> emb row j = .x.  The rows are kept in LDS (32 bytes beside the slabs)
+// for the store and the count at the end, so that nothing there waits for memory again.
+template <bool STAMP, bool U8, bool PARTS = false, bool VIEW = false, bool COMPACT = false>
 __device__ __forceinline__ void fused_trunk_body(const FusedArgs& a, unsigned long long* stamps, const float* table,
-                                                 const PartsArgs* pa = nullptr, const ViewArgs* va = nullptr) {
+                                                 const PartsArgs* pa = nullptr, const ViewArgs* va = nullptr,
+                                                 const int2* __restrict__ clist = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float lds[];          // 8 slabs of SLAB8
     constexpr int WPB = 8;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -651,7 +678,13 @@ __device__ __forceinline__ void fused_trunk_body(const FusedArgs& a, unsigned lo
     if (p_first >= n_valid) return;                                       // workgroup-uniform
     long long pi = p_first + wave;
     if (pi >= n_valid) pi = n_valid - 1;                                  // tail: recompute a valid patch, store nothing
-    if (a.index) pi = a.index[pi];
+    int* js = nullptr;                                                    // COMPACT: the eight rows this workgroup stores
+    if constexpr (COMPACT) {
+        js = compact_rows();
+        const int2 e = clist[pi];
+        if (lane == 0) js[wave] = p_first + wave < n_valid ? e.x : -1;    // (read behind layer1's barriers)
+        pi = e.y;
+    } else if (a.index) pi = a.index[pi];
     else if constexpr (VIEW) pi += va->first;
     trunk_front<STAMP, WPB, U8, VIEW>(a, pi, lds + wave * SLAB8, lane, wave, stamps, table, va);
     switch (__builtin_amdgcn_readfirstlane(Geo8::set_of_wave(wave))) {   // the wave's layer1 tile set, see Geo8
@@ -699,12 +732,17 @@ __device__ __forceinline__ void fused_trunk_body(const FusedArgs& a, unsigned lo
         float sum = 0.0f;
 #pragma unroll
         for (int k = 0; k < 16; ++k) sum = sum + s[k * PS2];
-        if (p_first + pl < n_valid) a.emb[(size_t)(p_first + pl) * 128 + n] = sum / 16.0f;
+        if constexpr (COMPACT) {
+            if (p_first + pl < n_valid) a.emb[(size_t)js[pl] * 128 + n] = sum / 16.0f;
+        } else {
+            if (p_first + pl < n_valid) a.emb[(size_t)(p_first + pl) * 128 + n] = sum / 16.0f;
+        }
     }
     IPSX_STAMP(15);
     if constexpr (PARTS) {
         const long long p_end = p_first + 8 < n_valid ? p_first + 8 : n_valid;
-        parts_count(*pa, (int)p_first, (int)p_end);
+        if constexpr (COMPACT) parts_count_compact(*pa, js);
+        else parts_count(*pa, (int)p_first, (int)p_end);
     }
 }
 
@@ -745,4 +783,9 @@ __global__ __launch_bounds__(512, 1) void fused_trunk_parts_u8_kernel(FusedArgs 
 __global__ __launch_bounds__(512, 1) void fused_trunk_parts_view_u8_kernel(FusedArgs a, PartsArgs pa, const float* table,
                                                                           ViewArgs va) {
     fused_trunk_body<false, true, true, true>(a, nullptr, table, &pa, &va);
+}
+
+// the counted launch behind the blank scan (dedup.hip): the entries clist[0 .. *a.count) of the list only
+__global__ __launch_bounds__(512, 1) void fused_trunk_parts_dedup_kernel(FusedArgs a, PartsArgs pa, const int2* clist) {
+    fused_trunk_body<false, false, true, false, true>(a, nullptr, nullptr, &pa, nullptr, clist);
 }

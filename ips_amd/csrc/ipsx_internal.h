@@ -47,6 +47,20 @@ static inline ViewArgs view_args(const PatchSrc& s, std::initializer_list<int> w
     return va;
 }
 
+// PARTS (ipsx_trunk_encode_parts): ONE launch encodes the index lists of every part of a call, one after the other, and says
+// how far each part has come - done[k] counts the patches of part k whose embeddings are written AND visible to the whole
+// device, so that a one-wave wait kernel on another stream (part_wait_kernel, scorer.hip) can let the part's logits and loop
+// iterations go while later parts are still being encoded.  A launch boundary per part drains the chip.
+struct PartsArgs {
+    int* done;               // [parts] device counters, zeroed by the caller in front of the launch
+    int parts;
+    int part_end[16];        // exclusive prefix ends of the parts, in list entries
+};
+// fused_trunk.hip: the checked PartsArgs of a list of n entries (`what`: the entry's name in the messages)
+int parts_args(PartsArgs& pa, int64_t n, const int64_t* part_end, int parts, int* done, const char* what);
+// ... and what a counted launch asks of its trunk: precision 0, patch_dtype 0, the tile16 packing of the 128 -> 128 convolutions
+int parts_trunk_check(const ipsx_trunk* t, const char* what);
+
 static inline bool at_multiple(const void* p, uintptr_t bytes) { return reinterpret_cast<uintptr_t>(p) % bytes == 0; }
 
 // conv.hip (table: x holds uint8 elements)
@@ -72,6 +86,10 @@ int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb
                  unsigned long long* stamps = nullptr);
 int fused_trunk_encode_parts(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, const int64_t* part_end, int parts,
                              int* done, hipStream_t s);
+// ... behind the blank scan (dedup.hip): only the list entries clist[0 .. *count) are encoded, clist[p] = (j, src.index[j]):
+// that patch to emb row j, counted into the part j lies in; the other rows, and their share of done[], are the scan's
+int fused_trunk_encode_parts_compact(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, const int64_t* part_end,
+                                     int parts, int* done, const int2* clist, const int* count, hipStream_t s);
 int fused_trunk_stream(const ipsx_trunk* t, const float* patches, int64_t n, float* emb, const float* pos, const float* v_packed,
                        int r, float* logits, int32_t* ctl, int32_t* ready, int workgroups, int quad_pulls, hipStream_t s,
                        const int32_t* index = nullptr);

@@ -71,8 +71,16 @@ def set_tie_order(mode):
 
 
 def dedup_blank():
-    """Opt-in exact blank-patch deduplication in front of the fused encoder (IPSX_DEDUP_BLANK=1)."""
-    return os.environ.get("IPSX_DEDUP_BLANK", "0") == "1"
+    """The explicit exact blank-patch deduplication in front of the fused encoder (IPSX_DEDUP_BLANK=1): every image-encoder
+    call through ``ipsx_trunk_encode_dedup``, and the routes that cannot take it refuse."""
+    return os.environ.get("IPSX_DEDUP_BLANK") == "1"
+
+
+def dedup_auto():
+    """IPSX_DEDUP_BLANK unset (or ``auto``): exact blank-patch dedup inside the one counted launch, where that route runs on
+    a float32 patch tensor (``selection.parts_one_launch``, ``ipsx_trunk_encode_parts_dedup``); every other route runs as
+    under ``0`` and refuses nothing.  ``0``: no dedup anywhere."""
+    return os.environ.get("IPSX_DEDUP_BLANK", "auto") == "auto"
 
 
 # Graph replays (training/graphed.py) update parameters and BatchNorm statistics without bumping tensor._version or
@@ -343,6 +351,10 @@ _EXPORTS = {
     "ipsx_trunk_encode_indexed": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "ipsx_trunk_encode_parts": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                           C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p]),
+    "ipsx_trunk_parts_dedup_workspace_bytes": (C.c_size_t, [C.POINTER(Trunk), C.c_int64]),
+    "ipsx_trunk_encode_parts_dedup": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                C.c_void_p, C.c_void_p]),
     "ipsx_part_wait": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "ipsx_logits_if": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),

@@ -70,6 +70,9 @@ class EncoderPlan:
         self._ws = None
         self._ws_small = 0
         self._held = 0
+        self.blank_emb = None      # the fused fp32 trunk's embedding of an all-zero patch, for this weight state
+        self._blank_ready = None   # (the stream it was made on, the event behind its launch)
+        self.n_encoded = None      # device int32: what the last dedup call really encoded
         self.bf16 = False          # feature nets: the projector runs on the bf16 matrix pipe (IPSX_PRECISION=bf16)
 
     def _features(self, x):
@@ -176,6 +179,7 @@ class EncoderPlan:
 
     def _rebuild(self):
         self._keep = []
+        self.blank_emb = None
         enc = self.encoder
         if self.is_image:
             mods = list(enc.children())
@@ -266,7 +270,26 @@ class EncoderPlan:
         t.h, t.w, t.patch_dtype = patch_shape[-2], patch_shape[-1], patch_dtype
         return t
 
-    def encode_source(self, src, index=None, first=0, n=None, parts=None, out=None):
+    def blank_embedding(self, src):
+        """(1, D) embedding of an all-zero patch of ``src``'s shape on the fused fp32 trunk, by the counted launch's own
+        kernel (``ipsx_trunk_encode_parts`` on one patch); kept until ``_refresh()`` sees the weights change (``_rebuild``
+        drops it).  One tiny launch per weight state, on the stream that is current then; a call on another stream waits for
+        that launch's event."""
+        if self.blank_emb is None or self.blank_emb.device != src.device:
+            dev = src.device
+            zero = torch.zeros((1,) + tuple(src.shape[-3:]), dtype=torch.float32, device=dev)
+            words = torch.zeros((2,), dtype=torch.int32, device=dev)       # the list [0] | the part's counter
+            out = torch.empty((1, self.d_out), dtype=torch.float32, device=dev)
+            _ck(lib().ipsx_trunk_encode_parts(C.byref(self._describe(zero.shape, 0)), _p(zero), _p(words[0:1]), 1, _p(out),
+                                              (C.c_int64 * 1)(1), 1, _p(words[1:2]), _stream()), "ipsx_trunk_encode_parts")
+            self.blank_emb = out
+            self._blank_ready = (torch.cuda.current_stream(dev), torch.cuda.Event())
+            self._blank_ready[1].record()
+        elif torch.cuda.current_stream(src.device) != self._blank_ready[0]:
+            torch.cuda.current_stream(src.device).wait_event(self._blank_ready[1])   # made on another stream: behind its launch
+        return self.blank_emb
+
+    def encode_source(self, src, index=None, first=0, n=None, parts=None, out=None, dedup=False):
         """The image trunk on patches of ``src`` (a ``hip.PatchSource``) -> (n, D) embeddings: of its patches ``index``
         (int32 numbers, on the device), or ``first .. first + n - 1`` (default: all from ``first`` on).  The ONE way into the
         ``ipsx_trunk_encode*`` family; which export runs follows from the source (float32 / half / uint8 patches, a view
@@ -275,7 +298,9 @@ class EncoderPlan:
         ``parts`` = (part_end, done): ``index`` is the index lists of several parts one after the other, ending at the
         list entries ``part_end`` (ints), encoded as ONE launch that counts part k's finished patches into ``done[k]``
         (int32 on the GPU, zeroed by the caller on this stream) - float32 patches, uint8 patches with their table, or a view
-        of float32 or uint8 images, on the exact fp32 fused trunk."""
+        of float32 or uint8 images, on the exact fp32 fused trunk.  ``dedup`` (with ``parts``, a float32 patch tensor): exact
+        blank-patch dedup inside that launch (``ipsx_trunk_encode_parts_dedup``) - the same bits, the all-zero entries'
+        rows written from ``blank_embedding``; ``n_encoded`` then holds the number of entries the trunk encoded."""
         self._refresh()
         # the trunk struct describes THIS call's patches: nothing an earlier call or question left in it is read
         t, L = self._describe(src.shape, 0 if src.table is not None else _PATCH_DTYPES[src.dtype]), lib()
@@ -318,6 +343,16 @@ class EncoderPlan:
             elif vs is not None:
                 _ck(L.ipsx_trunk_encode_parts_view(tr, _p(base), vs, _p(index), n, _p(out), ends, len(ends), done, _stream()),
                     "ipsx_trunk_encode_parts_view")
+            elif dedup:
+                # exact blank-patch dedup inside the launch: the blank embedding of this weight state goes in front
+                blank = self.blank_embedding(src)
+                self._describe(src.shape, 0)               # (blank_embedding described its own patch)
+                nb = L.ipsx_trunk_parts_dedup_workspace_bytes(tr, n)
+                if self.n_encoded is None or self.n_encoded.device != src.device:
+                    self.n_encoded = torch.zeros((), dtype=torch.int32, device=src.device)
+                _ck(L.ipsx_trunk_encode_parts_dedup(tr, _p(base), _p(index), n, _p(out), ends, len(ends), done, _p(blank),
+                                                    _p(self._workspace(nb, src.device)), nb, _p(self.n_encoded), _stream()),
+                    "ipsx_trunk_encode_parts_dedup")
             else:
                 _ck(L.ipsx_trunk_encode_parts(tr, _p(base), _p(index), n, _p(out), ends, len(ends), done, _stream()),
                     "ipsx_trunk_encode_parts")

@@ -758,7 +758,10 @@ class Selection:
         zeroed = torch.cuda.Event()
         zeroed.record(main)
         ends = self.part_ends(B, edges)
-        emb_all = plan.encode_source(src, index=every, parts=(ends, done))
+        # float32 patch tensors: blank entries are found, written and counted in front of the trunk launch, which encodes
+        # the others only (same bits; the waits below see done[k] fill as before)
+        dedup = hip.dedup_auto() and src.dtype == torch.float32 and not src.is_view and src.table is None
+        emb_all = plan.encode_source(src, index=every, parts=(ends, done), dedup=dedup)
         emb_all.record_stream(side)
         starts = [0] + ends[:-1]
         net._emb_parts = parts = [emb_all[starts[k]:ends[k]].view(B, edges[k + 1] - edges[k], -1) for k in range(P)]
