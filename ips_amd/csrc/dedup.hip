@@ -79,7 +79,9 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(const float4* __restr
 //   blank_scan_parts_kernel     64 list entries per workgroup: blank or not (with an early exit), the blank entries' rows
 //                               written and counted into their parts, a mask and a count of the others
 //   blank_compact_kernel        many workgroups: the ordered list of the entries to encode, and its length
-//   fused_trunk_parts_dedup_kernel (fused_trunk_eight.h)   encodes those, each to its own row, and counts them
+//   fused_trunk_parts_dedup_kernel (fused_trunk_eight.h)   encodes those, each to its own row, and counts them: the whole
+//                               rounds of the list, or all of it (trunk_split_n8 of the length, ipsx_internal.h)
+//   fused_trunk_pair_parts_dedup_kernel (fused_trunk_pair.h)   the same for the remainder of up to half a round
 constexpr int SCAN_ENT = 64;          // list entries per scan workgroup: 16 wavefronts x 4
 constexpr int PATCH_U4 = 256;         // a 1x32x32 float32 patch in 16-byte loads: 4 per lane
 

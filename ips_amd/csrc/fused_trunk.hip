@@ -1059,18 +1059,14 @@ int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb
         return fail(IPSX_EINVAL, "fused trunk: the exact fp32 trunk needs ipsx_pack_conv_weight_tile16 of its three 128 -> 128 "
                     "convolutions in their w_packed_bf16");
     const int cus = device_cus();
-    // What is left over after the whole rounds (8 patches per CU) goes to the two-wavefronts-per-patch kernel when that takes
-    // fewer wavefront slots per SIMD: at most a quarter round (one workgroup per CU, one wavefront per SIMD, half a patch
-    // each) or between a half and three quarters (three per SIMD) - fused_trunk_pair.h; a device-side count (blank-patch
-    // dedup) leaves the launch as it is.
+    // What is left over after the whole rounds (8 patches per CU) goes to the two-wavefronts-per-patch kernel when that is done
+    // with it well before the eight-patch kernel's started round: up to half a round (trunk_split_n8, ipsx_internal.h - the
+    // rule of the launches behind the blank scan, which split a device-side count on the device); a device-side count HERE
+    // (ipsx_trunk_encode_dedup) leaves the launch as it is.
+    // measured, patches -> ms (profiles/dedup_rounds_pair_table.txt): one wavefront per patch 0.45 for any part of a round; two
+    // per patch 512 0.16, 1024 0.29, 1536 0.42 (three workgroups per CU: no gain left beside a selection loop), 2048 0.56
     int64_t rest = 0;
-    if (!stamps && !count && g_pair_mode != 1) {
-        const int64_t round = 8 * (int64_t)cus;
-        rest = g_pair_mode == 2 ? n : n % round;
-        // measured, patches -> ms: one wavefront per patch 1024 0.29, 2048 0.54; two per patch 512 0.15, 1024 0.28, 1536 0.43
-        // (three workgroups per CU), 2048 0.57
-        if (g_pair_mode != 2 && !(rest <= round / 4 || (rest > round / 2 && rest <= 3 * round / 4))) rest = 0;
-    }
+    if (!stamps && !count) rest = n - trunk_split_n8(n, cus, g_pair_mode);
     // patches 0 .. n_full through the eight-patch kernel, patches n_full .. through the pair kernel: the same source, advanced.
     // The storage kinds differ in the kernels' last arguments only (the table, the view, both, nothing).
     const int64_t n_full = n - rest;
@@ -1166,8 +1162,12 @@ int fused_trunk_encode_parts(const ipsx_trunk* t, const PatchSrc& src, int64_t n
     return launched("fused_trunk_parts");
 }
 
-// The counted launch behind the blank scan: the grid is sized for a list without a blank entry, and the workgroups beyond
-// *count return at once.  float32 patches through their index list only.
+// The counted launch behind the blank scan, as TWO launches on the stream: the host does not know how many entries the scan
+// left, the device does, and both kernels split the list by the same function of it (trunk_split_n8, ipsx_internal.h) - whole
+// rounds through eight-patch workgroups, a remainder of up to half a round through pair workgroups, which are done with it
+// well before a started round would be (profiles/dedup_rounds_pair_table.txt).  The eight-patch grid is sized for a list
+// without a blank entry, the pair grid for the largest remainder the rule hands over; the workgroups beyond their share
+// return at once.  float32 patches through their index list only.
 int fused_trunk_encode_parts_compact(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, const int64_t* part_end,
                                      int parts, int* done, const int2* clist, const int* count, hipStream_t s) {
     FusedArgs a;
@@ -1176,8 +1176,13 @@ int fused_trunk_encode_parts_compact(const ipsx_trunk* t, const PatchSrc& src, i
     if (src.table || src.view || !clist || !count)
         return fail(IPSX_EINVAL, "trunk_encode_parts_dedup: float32 patches through an index list, with the scan's list and count");
     a.count = count;
-    fused_trunk_parts_dedup_kernel<<<dim3((unsigned)cdiv(n, 8)), dim3(512), FUSED_LDS, s>>>(a, pa, clist);
-    return launched("fused_trunk_parts_dedup");
+    const int cus = device_cus(), mode = g_pair_mode;
+    fused_trunk_parts_dedup_kernel<<<dim3((unsigned)cdiv(n, 8)), dim3(512), FUSED_LDS, s>>>(a, pa, clist, cus, mode);
+    IPSX_TRY(launched("fused_trunk_parts_dedup"));
+    const int64_t grid2 = trunk_split_pair_grid(n, cus, mode);
+    if (grid2 == 0) return IPSX_OK;                                   // (mode 1: the eight-patch launch takes every entry)
+    fused_trunk_pair_parts_dedup_kernel<<<dim3((unsigned)grid2), dim3(256), (size_t)2 * SLAB * sizeof(float), s>>>(a, pa, clist, cus, mode);
+    return launched("fused_trunk_pair_parts_dedup");
 }
 
 // One image through the fused trunk as ONE persistent launch that feeds a resident selection loop (fused_trunk_stream_kernel,
@@ -1324,6 +1329,30 @@ IPSX_API int ipsx_pack_conv_weight_tile16(const float* w, int c_out, int c_in, i
 // Diagnostic switch (not part of include/ipsx.h; tests/test_hip_kernels.py, tools): which of the two exact fp32 kernels
 // encodes - 0 the product's rule, 1 fused_trunk_kernel only, 2 fused_trunk_pair_kernel only.
 extern "C" __attribute__((visibility("default"))) void ipsx_dbg_fused_trunk_pair(int mode) { ipsx::g_pair_mode = mode; }
+
+// Diagnostic entry point (host only, not part of include/ipsx.h; tests/test_dedup_split_cpu.py, tests/test_dedup_rounds.py): the
+// split of a list between the two kernels as host and device compute it (trunk_split_n8, ipsx_internal.h) on `cus` units under
+// `mode` (-1: the mode ipsx_dbg_fused_trunk_pair has set).  Returns n8; *pair_grid (or NULL) = the pair workgroups a launch
+// gets for a list of at most `count` entries; thresholds (or NULL, room for `cap`): every remainder t in 1 .. 8 cus - 2 at
+// which the rule changes between t and t + 1, *n_thresholds their number.
+extern "C" __attribute__((visibility("default"))) long long ipsx_dbg_trunk_split(long long count, int cus, int mode,
+                                                                                  long long* pair_grid, long long* thresholds,
+                                                                                  int cap, int* n_thresholds) {
+    if (mode < 0) mode = ipsx::g_pair_mode;
+    if (cus <= 0) cus = ipsx::device_cus();
+    if (pair_grid) *pair_grid = ipsx::trunk_split_pair_grid(count, cus, mode);
+    if (n_thresholds) {
+        const long long round = 8ll * cus;
+        int found = 0;
+        for (long long t = 1; t <= round - 2; ++t)
+            if ((ipsx::trunk_split_n8(round + t, cus, mode) == round) != (ipsx::trunk_split_n8(round + t + 1, cus, mode) == round)) {
+                if (thresholds && found < cap) thresholds[found] = t;
+                ++found;
+            }
+        *n_thresholds = found;
+    }
+    return ipsx::trunk_split_n8(count, cus, mode);
+}
 
 // Diagnostic entry point (not part of include/ipsx.h): the fused trunk with s_memtime stamps,
 // 16 x uint64 per wavefront = per patch, in launch order.  Used by tools/fused_stamps.py only.

@@ -632,16 +632,18 @@ __device__ __forceinline__ void parts_count(const PartsArgs& pa, int lo, int hi)
 }
 
 // The same hand-over behind the blank scan (COMPACT): this workgroup stored the rows of the list entries js[0 .. 7] - increasing,
-// anywhere in the list, -1: none - and counts each into the part its ORIGINAL position lies in.
+// anywhere in the list, -1: none - and counts each into the part its ORIGINAL position lies in.  (E = 2: the pair workgroups of
+// fused_trunk_pair_parts_dedup_kernel, their two rows.)
+template <int E = 8>
 __device__ __forceinline__ void parts_count_compact(const PartsArgs& pa, const int* js) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        int j[8];
+        int j[E];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) j[e] = js[e];
+        for (int e = 0; e < E; ++e) j[e] = js[e];
         int begin = 0;
 #pragma unroll
         for (int k = 0; k < 16; ++k) {                                    // (constant indices: part_end stays in the kernel arguments)
@@ -649,7 +651,7 @@ __device__ __forceinline__ void parts_count_compact(const PartsArgs& pa, const i
                 const int end = pa.part_end[k];
                 int c = 0;
 #pragma unroll
-                for (int e = 0; e < 8; ++e) c += j[e] >= begin && j[e] < end;
+                for (int e = 0; e < E; ++e) c += j[e] >= begin && j[e] < end;
                 if (c > 0) __hip_atomic_fetch_add(pa.done + k, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 begin = end;
             }
@@ -664,18 +666,21 @@ __device__ __forceinline__ int* compact_rows() {
 
 // COMPACT (fused_trunk_parts_dedup_kernel only): workgroup b takes the entries clist[8 b .. 8 b + 7] below *a.count of the
 // call's list.  clist[p] = (j, a.index[j]): patch .y -> emb row j = .x.  The rows are kept in LDS (32 bytes beside the slabs)
-// for the store and the count at the end, so that nothing there waits for memory again.
+// for the store and the count at the end, so that nothing there waits for memory again.  Only the first n8 entries are this
+// launch's (trunk_split_n8 of the count, ipsx_internal.h: whole rounds, or all of them); the pair launch behind takes the rest.
 template <bool STAMP, bool U8, bool PARTS = false, bool VIEW = false, bool COMPACT = false>
 __device__ __forceinline__ void fused_trunk_body(const FusedArgs& a, unsigned long long* stamps, const float* table,
                                                  const PartsArgs* pa = nullptr, const ViewArgs* va = nullptr,
-                                                 const int2* __restrict__ clist = nullptr) {
+                                                 const int2* __restrict__ clist = nullptr, int cus = 0, int pair_mode = 0) {
     extern __shared__ __attribute__((aligned(16))) float lds[];          // 8 slabs of SLAB8
     constexpr int WPB = 8;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31;
     const long long p_first = (long long)blockIdx.x * 8;
     const long long n_valid = a.count ? (long long)*a.count : a.n;        // compacted launches read their length on device
-    if (p_first >= n_valid) return;                                       // workgroup-uniform
+    if constexpr (COMPACT) {
+        if (p_first >= trunk_split_n8(n_valid, cus, pair_mode)) return;   // workgroup-uniform
+    } else if (p_first >= n_valid) return;                                // workgroup-uniform
     long long pi = p_first + wave;
     if (pi >= n_valid) pi = n_valid - 1;                                  // tail: recompute a valid patch, store nothing
     int* js = nullptr;                                                    // COMPACT: the eight rows this workgroup stores
@@ -785,7 +790,8 @@ __global__ __launch_bounds__(512, 1) void fused_trunk_parts_view_u8_kernel(Fused
     fused_trunk_body<false, true, true, true>(a, nullptr, table, &pa, &va);
 }
 
-// the counted launch behind the blank scan (dedup.hip): the entries clist[0 .. *a.count) of the list only
-__global__ __launch_bounds__(512, 1) void fused_trunk_parts_dedup_kernel(FusedArgs a, PartsArgs pa, const int2* clist) {
-    fused_trunk_body<false, false, true, false, true>(a, nullptr, nullptr, &pa, nullptr, clist);
+// the counted launch behind the blank scan (dedup.hip): the entries clist[0 .. n8) of the list only, n8 <= *a.count
+__global__ __launch_bounds__(512, 1) void fused_trunk_parts_dedup_kernel(FusedArgs a, PartsArgs pa, const int2* clist, int cus,
+                                                                        int pair_mode) {
+    fused_trunk_body<false, false, true, false, true>(a, nullptr, nullptr, &pa, nullptr, clist, cus, pair_mode);
 }

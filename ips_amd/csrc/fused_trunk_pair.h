@@ -10,7 +10,7 @@
 // patches (one 32-row tile).  Every output's fma chain runs over k in the contract's order exactly as in
 // fused_trunk_kernel, so the embeddings are bit-identical to it (tests/test_hip_kernels.py); only the operand traffic per
 // MFMA differs (6 loads per 16 MFMAs at 8x8 instead of 4, 8 per 16 at 4x4 instead of 6), which is why this is the
-// kernel for a remainder of at most a quarter round (one workgroup per CU, one wavefront per SIMD) and not the kernel.
+// kernel for a remainder of at most half a round (two workgroups per CU; trunk_split_n8, ipsx_internal.h) and not the kernel.
 #pragma once
 
 // ------------------------------------------------------------------ stem + max-pool, one n-tile per wavefront
@@ -227,15 +227,28 @@ __device__ __forceinline__ void store_l2_pair(float* lds, const f32x16& v, int l
 // own copy of the table behind the padded image (U8_TAB, fused_trunk.hip) and stages its half of the patch through it
 // VIEW: a.patches holds whole images, the patch is one of the grid `va` describes - the same 8 floats per lane off its rows
 // U8 and VIEW: whole uint8 images - the lane's 8 bytes are a quarter of a patch row (va->wide: 8, 4 or 1 bytes per load)
-template <bool KEEP, bool U8 = false, bool VIEW = false>
+// COMPACT (fused_trunk_pair_parts_dedup_kernel only, as in fused_trunk_body): the two entries are clist[p_first], clist[p_first
+// + 1] below n_list, the list's device-side length; clist[p] = (j, a.index[j]): patch .y -> emb row j = .x, and the rows are
+// counted into their parts behind the stores (parts_count_compact<2>)
+template <bool KEEP, bool U8 = false, bool VIEW = false, bool COMPACT = false>
 __device__ __forceinline__ void trunk_pair_tile(const FusedArgs& a, long long p_first, float* lds, const float* table = nullptr,
-                                                const ViewArgs* va = nullptr) {
+                                                const ViewArgs* va = nullptr, const PartsArgs* pa = nullptr,
+                                                const int2* __restrict__ clist = nullptr, long long n_list = 0) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ps = wave >> 1, nh = wave & 1;                              // patch slot of the workgroup, n-tile of the pair
     const int i = lane & 31;
+    const long long n_valid = COMPACT ? n_list : a.n;
     long long pi = p_first + ps;
-    if (pi >= a.n) pi = a.n - 1;                                          // odd tail: recompute a valid patch, store nothing
-    if (a.index) pi = a.index[pi];
+    if (pi >= n_valid) pi = n_valid - 1;                                  // odd tail: recompute a valid patch, store nothing
+    int row = 0;                                                          // COMPACT: the row of this thread's patch slot
+    int* js = nullptr;                                                    // ... and both, for the count at the end
+    if constexpr (COMPACT) {
+        js = compact_rows();
+        const int2 e = clist[pi];
+        row = e.x;
+        if (lane == 0 && nh == 0) js[ps] = p_first + ps < n_valid ? e.x : -1;   // (read behind the trunk's barriers)
+        pi = e.y;
+    } else if (a.index) pi = a.index[pi];
     else if constexpr (VIEW) pi += va->first;
     float* S = lds + ps * SLAB;
 
@@ -368,13 +381,18 @@ __device__ __forceinline__ void trunk_pair_tile(const FusedArgs& a, long long p_
 #pragma unroll
         for (int k = 0; k < 16; ++k) sum = sum + s[k * PS2];
         const float e = sum / 16.0f;
-        if (p_first + pl < a.n) a.emb[(size_t)(p_first + pl) * 128 + n] = e;
+        if constexpr (COMPACT) {
+            if (p_first + pl < n_valid) a.emb[(size_t)row * 128 + n] = e;   // (pl == ps: the thread's own slot)
+        } else {
+            if (p_first + pl < a.n) a.emb[(size_t)(p_first + pl) * 128 + n] = e;
+        }
         if (KEEP) {
             __syncthreads();                                              // every sum has been read
             lds[threadIdx.x] = e;
             __syncthreads();
         }
     }
+    if constexpr (COMPACT) parts_count_compact<2>(*pa, js);
 }
 
 __global__ __launch_bounds__(256, 2) void fused_trunk_pair_kernel(FusedArgs a) {
@@ -398,6 +416,18 @@ __global__ __launch_bounds__(256, 2) void fused_trunk_pair_view_kernel(FusedArgs
 __global__ __launch_bounds__(256, 2) void fused_trunk_pair_view_u8_kernel(FusedArgs a, const float* table, ViewArgs va) {
     extern __shared__ __attribute__((aligned(16))) float lds[];          // 2 slabs
     trunk_pair_tile<false, true, true>(a, (long long)blockIdx.x * 2, lds, table, &va);
+}
+
+// the counted launch behind the blank scan, second half (dedup.hip; launched behind fused_trunk_parts_dedup_kernel on its
+// stream): the entries clist[n8 .. *a.count) that the eight-patch workgroups leave - trunk_split_n8 of the count, as there -
+// two per workgroup, each to its own row, counted into their parts
+__global__ __launch_bounds__(256, 2) void fused_trunk_pair_parts_dedup_kernel(FusedArgs a, PartsArgs pa, const int2* clist, int cus,
+                                                                             int pair_mode) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];          // 2 slabs
+    const long long n_list = *a.count;
+    const long long p_first = trunk_split_n8(n_list, cus, pair_mode) + (long long)blockIdx.x * 2;
+    if (p_first >= n_list) return;                                        // workgroup-uniform
+    trunk_pair_tile<false, false, false, true>(a, p_first, lds, nullptr, nullptr, &pa, clist, n_list);
 }
 
 // ------------------------------------------------------------------ one image as ONE persistent launch

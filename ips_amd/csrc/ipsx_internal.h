@@ -61,6 +61,30 @@ int parts_args(PartsArgs& pa, int64_t n, const int64_t* part_end, int parts, int
 // ... and what a counted launch asks of its trunk: precision 0, patch_dtype 0, the tile16 packing of the 128 -> 128 convolutions
 int parts_trunk_check(const ipsx_trunk* t, const char* what);
 
+// ---- the two exact fp32 trunk kernels share a list (fused_trunk.hip).  `count` entries on `cus` compute units: the first n8
+// go through eight-patch workgroups (one per unit and round: a started round costs a whole one, 0.45 ms), the other count - n8
+// through pair workgroups (fused_trunk_pair.h: a quarter round per unit each, 0.15 ms the layer).  n8 is the whole rounds when
+// the remainder r = count % (8 cus) is at most PAIR_REST_NUM / PAIR_REST_DEN of a round, and the whole list otherwise.
+// Measured (profiles/dedup_rounds_pair_table.txt): alone, the pair kernel is the faster one up to three quarters of a round
+// (0.42 against 0.45 ms); inside a call its third layer of workgroups slows the selection loop that runs beside it by more
+// than that, and only a remainder of up to half a round gains.  A pure function of the count: host (fused_launch) and device
+// (the launches behind the blank scan, which alone know the count) agree, and both kernels give the same bits.
+// mode (ipsx_dbg_fused_trunk_pair): 0 this rule, 1 n8 = count, 2 n8 = 0.
+constexpr int PAIR_REST_NUM = 1, PAIR_REST_DEN = 2;
+__host__ __device__ static inline long long trunk_pair_rest_max(int cus) { return 8ll * cus * PAIR_REST_NUM / PAIR_REST_DEN; }
+__host__ __device__ static inline long long trunk_split_n8(long long count, int cus, int mode) {
+    if (count <= 0 || mode == 2) return 0;
+    if (mode == 1 || count > 0x7FFFFFFFll) return count;
+    const unsigned r = (unsigned)count % (8u * (unsigned)cus);            // (32-bit: once per workgroup on the device)
+    return (long long)r <= trunk_pair_rest_max(cus) ? count - r : count;
+}
+// ... and the pair workgroups a launch needs for a list of at most n entries whose length only the device knows
+static inline long long trunk_split_pair_grid(long long n, int cus, int mode) {
+    if (n <= 0 || mode == 1) return 0;
+    const long long most = mode == 2 ? n : (n < trunk_pair_rest_max(cus) ? n : trunk_pair_rest_max(cus));
+    return (most + 1) / 2;
+}
+
 static inline bool at_multiple(const void* p, uintptr_t bytes) { return reinterpret_cast<uintptr_t>(p) % bytes == 0; }
 
 // conv.hip (table: x holds uint8 elements)
