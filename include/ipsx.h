@@ -108,7 +108,10 @@ extern "C" {
  *         ipsx_conv.w_packed_bf16, which precision 0 did not read before: a caller that left it NULL there is refused;
  *         ipsx_trunk_encode_parts_dedup (+ ipsx_trunk_parts_dedup_workspace_bytes) - ipsx_trunk_encode_parts with exact
  *         blank-patch dedup inside the counted launch (the minor number stays, as above: the tests of the earlier 3.06
- *         additions pin it) */
+ *         additions pin it);
+ *         ipsx_trunk_encode_parts_dedup_u8, ipsx_trunk_encode_parts_dedup_view, ipsx_trunk_encode_parts_dedup_view_u8 - that
+ *         dedup on the other three sources of the counted launch: uint8 patches, float32 images and uint8 images through a
+ *         patch view (additions only, the minor number stays for the same reason) */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -425,6 +428,30 @@ size_t ipsx_trunk_parts_dedup_workspace_bytes(const ipsx_trunk* t, int64_t n_ind
 int ipsx_trunk_encode_parts_dedup(const ipsx_trunk* t, const float* patches, const int32_t* index, int64_t n_index, float* emb,
                                   const int64_t* part_end, int n_parts, int32_t* done, const float* blank_emb, void* workspace,
                                   size_t workspace_bytes, int32_t* n_encoded, void* stream);
+
+/* ipsx_trunk_encode_parts_dedup on the other three sources of the counted launch.  patches / images / table / v mean what they
+ * mean for ipsx_trunk_encode_parts_u8, ipsx_trunk_encode_parts_view and ipsx_trunk_encode_parts_view_u8 (index: patch numbers,
+ * or grid patch numbers of the view), everything from blank_emb on what it means for ipsx_trunk_encode_parts_dedup, and emb is
+ * bit for bit what the entry without `_dedup` writes.  float32 images: a grid patch is blank when all its pixels are zero
+ * (-0.0 counts), blank_emb as above.  BYTES: an entry is blank when every byte of the patch is 0, and blank_emb is the
+ * embedding of such a patch - of a patch whose every pixel is table[c][0], which need NOT be 0.0f (a normalising table): the
+ * caller computes it with ipsx_trunk_encode_parts_u8 on one patch of zero bytes, once per weight state AND per table.  A patch
+ * of another byte whose table entry happens to be 0.0f is not blank by this rule; it is encoded, to the same bits.  The same
+ * trunk, alignments and limits as the entries without `_dedup`; anything else, a missing table or view among it: IPSX_EINVAL
+ * (workspace: IPSX_EWORKSPACE), nothing launched, no row and no counter written.  workspace:
+ * ipsx_trunk_parts_dedup_workspace_bytes(t, n_index) bytes, 8-byte aligned, for all four. */
+int ipsx_trunk_encode_parts_dedup_u8(const ipsx_trunk* t, const uint8_t* patches, const float* table, const int32_t* index,
+                                     int64_t n_index, float* emb, const int64_t* part_end, int n_parts, int32_t* done,
+                                     const float* blank_emb, void* workspace, size_t workspace_bytes, int32_t* n_encoded,
+                                     void* stream);
+int ipsx_trunk_encode_parts_dedup_view(const ipsx_trunk* t, const float* images, const ipsx_patch_view* v, const int32_t* index,
+                                       int64_t n_index, float* emb, const int64_t* part_end, int n_parts, int32_t* done,
+                                       const float* blank_emb, void* workspace, size_t workspace_bytes, int32_t* n_encoded,
+                                       void* stream);
+int ipsx_trunk_encode_parts_dedup_view_u8(const ipsx_trunk* t, const uint8_t* images, const float* table, const ipsx_patch_view* v,
+                                          const int32_t* index, int64_t n_index, float* emb, const int64_t* part_end, int n_parts,
+                                          int32_t* done, const float* blank_emb, void* workspace, size_t workspace_bytes,
+                                          int32_t* n_encoded, void* stream);
 
 /* ---------------------------------------------------------- image -> patches
  * The step that feeds ips(): replaces, for a whole batch on the device,

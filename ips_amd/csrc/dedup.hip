@@ -78,6 +78,8 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(const float4* __restr
 // ---- the same dedup inside the one counted launch (ipsx_trunk_encode_parts_dedup): no workspace of embeddings, no scatter
 //   blank_scan_parts_kernel     64 list entries per workgroup: blank or not (with an early exit), the blank entries' rows
 //                               written and counted into their parts, a mask and a count of the others
+//   blank_scan_parts_{u8,view,view_u8}_kernel   the same scan of uint8 patches (blank: every byte 0), of grid patches of
+//                               float32 images and of grid patches of uint8 images
 //   blank_compact_kernel        many workgroups: the ordered list of the entries to encode, and its length
 //   fused_trunk_parts_dedup_kernel (fused_trunk_eight.h)   encodes those, each to its own row, and counts them: the whole
 //                               rounds of the list, or all of it (trunk_split_n8 of the length, ipsx_internal.h)
@@ -86,6 +88,9 @@ constexpr int SCAN_ENT = 64;          // list entries per scan workgroup: 16 wav
 constexpr int PATCH_U4 = 256;         // a 1x32x32 float32 patch in 16-byte loads: 4 per lane
 
 __device__ __forceinline__ unsigned nonzero_bits(const uint4& v) { return (v.x | v.y | v.z | v.w) & 0x7FFFFFFFu; }   // -0.0 is zero
+__device__ __forceinline__ uint4 float4_bits(const float4& f) {
+    return uint4{__float_as_uint(f.x), __float_as_uint(f.y), __float_as_uint(f.z), __float_as_uint(f.w)};
+}
 __device__ __forceinline__ unsigned long long low_bits(int b) { return b >= 64 ? ~0ull : (1ull << b) - 1ull; }
 
 // List entry j is patch index[j].  A wavefront takes four entries: the first KiB of each (one 16-byte load per lane, the four
@@ -145,6 +150,126 @@ __global__ __launch_bounds__(1024) void blank_scan_parts_kernel(const float* __r
             }
         }
     }
+}
+
+// What the three scans below do with a wavefront's answer, step for step blank_scan_parts_kernel's (which keeps its own text:
+// its instruction stream is pinned): the rows of the blank ones among the wavefront's `valid` entries j0 .. (bit e of `bits`
+// clear) = blank_emb, then the workgroup's mask and count and the blank entries counted into their parts, by the same
+// hand-over.
+__device__ __forceinline__ void scan_hand_over(unsigned bits, int valid, int j0, int lo, int n, const float* __restrict__ blank_emb,
+                                               float* __restrict__ emb, const PartsArgs& pa,
+                                               unsigned long long* __restrict__ mask, int* __restrict__ cnt) {
+    __shared__ unsigned wbits[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float2 be = reinterpret_cast<const float2*>(blank_emb)[lane];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (e < valid && !(bits >> e & 1u)) reinterpret_cast<float2*>(emb + (size_t)(j0 + e) * 128)[lane] = be;   // wavefront-uniform
+    if (lane == 0) wbits[wave] = bits;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long m = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) m |= (unsigned long long)wbits[w] << (4 * w);
+        mask[blockIdx.x] = m;
+        cnt[blockIdx.x] = __popcll(m);
+        const unsigned long long blank = ~m & low_bits(n - lo);
+        if (blank) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            int begin = 0;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {                                // (constant indices: part_end stays in the kernel arguments)
+                if (k < pa.parts) {
+                    const int end = pa.part_end[k];
+                    const int b0 = begin - lo, b1 = end - lo;             // the part's entries in this workgroup: bits b0 .. b1 - 1
+                    const int c = b1 <= 0 || b0 >= SCAN_ENT ? 0 : __popcll(blank & low_bits(b1) & ~low_bits(b0 > 0 ? b0 : 0));
+                    if (c > 0) __hip_atomic_fetch_add(pa.done + k, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    begin = end;
+                }
+            }
+        }
+    }
+}
+
+// uint8 patches (table[c][byte] is their value): an entry is blank when every BYTE is 0 - its embedding is that of a patch of
+// table[c][0], the caller's blank_emb, whatever that float is.  A patch is 1,024 bytes: one 16-byte load per lane, the four
+// entries of a wavefront in flight together, nothing to exit early from.
+__global__ __launch_bounds__(1024) void blank_scan_parts_u8_kernel(const unsigned char* __restrict__ x, const int* __restrict__ index,
+                                                                   int n, const float* __restrict__ blank_emb,
+                                                                   float* __restrict__ emb, PartsArgs pa,
+                                                                   unsigned long long* __restrict__ mask, int* __restrict__ cnt) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lo = blockIdx.x * SCAN_ENT, j0 = lo + wave * 4;
+    uint4 v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        v[e] = j0 + e < n ? reinterpret_cast<const uint4*>(x + (size_t)index[j0 + e] * 1024)[lane] : uint4{0u, 0u, 0u, 0u};
+    unsigned bits = 0;                                                    // the wavefront's non-blank entries
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (__ballot((v[e].x | v[e].y | v[e].z | v[e].w) != 0u) != 0ull) bits |= 1u << e;
+    const int valid = n - j0 < 4 ? (n - j0 > 0 ? n - j0 : 0) : 4;
+    scan_hand_over(bits, valid, j0, lo, n, blank_emb, emb, pa, mask, cnt);   // (an entry beyond n: no bit, masked out there)
+}
+
+// A view of float32 images: list entry j is GRID patch index[j], its rows at pitch w in the image (view_base, view_load_32:
+// 16-byte loads where va.wide allows, dwords otherwise).  The float32 scan's order: the first KiB of the four entries (patch
+// rows 0 - 7) in flight together, the other three only where that was all zero; -0.0 is zero.
+__global__ __launch_bounds__(1024) void blank_scan_parts_view_kernel(const float* __restrict__ x, ViewArgs va,
+                                                                     const int* __restrict__ index, int n,
+                                                                     const float* __restrict__ blank_emb, float* __restrict__ emb,
+                                                                     PartsArgs pa, unsigned long long* __restrict__ mask,
+                                                                     int* __restrict__ cnt) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lo = blockIdx.x * SCAN_ENT, j0 = lo + wave * 4;
+    const int valid = n - j0 < 4 ? (n - j0 > 0 ? n - j0 : 0) : 4;
+    const float* p[4];
+    float4 v[4][1];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        p[e] = x + view_base(va, e < valid ? index[j0 + e] : 0);
+        if (e < valid) view_load_32<1>(p[e], va.v.w, va.wide, lane, 0, v[e]);
+        else v[e][0] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    unsigned bits = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (e >= valid) break;                                            // wavefront-uniform
+        unsigned any = nonzero_bits(float4_bits(v[e][0]));
+        if (__ballot(any != 0) == 0ull) {
+            float4 r[3];
+            view_load_32<3>(p[e], va.v.w, va.wide, lane, 1, r);
+            any = nonzero_bits(float4_bits(r[0])) | nonzero_bits(float4_bits(r[1])) | nonzero_bits(float4_bits(r[2]));
+        }
+        if (__ballot(any != 0) != 0ull) bits |= 1u << e;
+    }
+    scan_hand_over(bits, valid, j0, lo, n, blank_emb, emb, pa, mask, cnt);
+}
+
+// A view of uint8 images: a lane's 16 bytes are half a patch row, contiguous in the image (view_load_u8: 16, 4 or 1 bytes
+// per load by va.wide) - one such read per entry, the four of a wavefront in flight together; blank: every byte 0.
+__global__ __launch_bounds__(1024) void blank_scan_parts_view_u8_kernel(const unsigned char* __restrict__ x, ViewArgs va,
+                                                                        const int* __restrict__ index, int n,
+                                                                        const float* __restrict__ blank_emb, float* __restrict__ emb,
+                                                                        PartsArgs pa, unsigned long long* __restrict__ mask,
+                                                                        int* __restrict__ cnt) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lo = blockIdx.x * SCAN_ENT, j0 = lo + wave * 4;
+    const int valid = n - j0 < 4 ? (n - j0 > 0 ? n - j0 : 0) : 4;
+    unsigned w[4][4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (e < valid)
+            view_load_u8<4>(x + view_base(va, index[j0 + e]) + (long long)(lane >> 1) * va.v.w + 16 * (lane & 1), va.wide, w[e]);
+        else w[e][0] = w[e][1] = w[e][2] = w[e][3] = 0u;
+    }
+    unsigned bits = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (__ballot((w[e][0] | w[e][1] | w[e][2] | w[e][3]) != 0u) != 0ull) bits |= 1u << e;
+    scan_hand_over(bits, valid, j0, lo, n, blank_emb, emb, pa, mask, cnt);
 }
 
 // Ordered compaction with many workgroups: a workgroup takes four scan workgroups' masks (256 entries), sums the counts of the
@@ -281,30 +406,75 @@ IPSX_API size_t ipsx_trunk_parts_dedup_workspace_bytes(const ipsx_trunk* t, int6
     return parts_dedup_masks(n_index) * 12 + 256 + (size_t)n_index * 8 + 256;
 }
 
-IPSX_API int ipsx_trunk_encode_parts_dedup(const ipsx_trunk* t, const float* patches, const int32_t* index, int64_t n_index,
-                                           float* emb, const int64_t* part_end, int n_parts, int32_t* done,
-                                           const float* blank_emb, void* workspace, size_t workspace_bytes, int32_t* n_encoded,
-                                           void* stream) {
-    IPSX_REQUIRE(t && patches && index && emb && part_end && done && blank_emb, "trunk_encode_parts_dedup: null pointer");
-    IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_parts_dedup: only the fused 1x32x32 trunk is supported");
+// The four entries are one function of the source's kind.  Every refusal - the arguments, the trunk, the source (a byte
+// source without a table, misaligned bytes, a view the trunk does not read), the parts, the workspace - comes in front of the
+// scan: a refused call has written no row and no counter.
+static int encode_parts_dedup(const ipsx_trunk* t, const PatchSrc& src, bool u8, bool view, int64_t n_index, float* emb,
+                              const int64_t* part_end, int n_parts, int32_t* done, const float* blank_emb, void* workspace,
+                              size_t workspace_bytes, int32_t* n_encoded, void* stream, const char* what) {
+    IPSX_REQUIRE(t && src.base && src.index && emb && part_end && done && blank_emb && (!u8 || src.table) && (!view || src.view),
+                 "%s: null pointer", what);
+    IPSX_REQUIRE(fused_trunk_supported(t), "%s: only the fused 1x32x32 trunk is supported", what);
     IPSX_REQUIRE(t->precision == 0 && t->patch_dtype == 0 && t->c_in * t->h * t->w == PATCH_U4 * 4,
-                 "trunk_encode_parts_dedup: blank-patch detection reads float32 patches, on the exact fp32 trunk");
+                 "%s: blank-patch detection reads float32 or uint8 patches, on the exact fp32 trunk", what);
     PartsArgs pa;
-    IPSX_TRY(parts_args(pa, n_index, part_end, n_parts, done, "trunk_encode_parts_dedup"));
-    IPSX_TRY(parts_trunk_check(t, "trunk_encode_parts_dedup"));          // everything the trunk launch refuses: before the scan
+    IPSX_TRY(parts_args(pa, n_index, part_end, n_parts, done, what));
+    IPSX_TRY(parts_trunk_check(t, what));                                 // everything the trunk launch refuses: before the scan
+    if (u8 || view) IPSX_TRY(patch_src_check(t, src, n_index, true, what));
     const size_t need = ipsx_trunk_parts_dedup_workspace_bytes(t, n_index);
     if (!workspace || workspace_bytes < need || !at_multiple(workspace, 8))
-        return fail(IPSX_EWORKSPACE, "trunk_encode_parts_dedup: workspace %zu B < %zu B", workspace_bytes, need);
+        return fail(IPSX_EWORKSPACE, "%s: workspace %zu B < %zu B", what, workspace_bytes, need);
     hipStream_t s = as_stream(stream);
-    const int n_mask = (int)parts_dedup_masks(n_index);
+    const int n_mask = (int)parts_dedup_masks(n_index), n = (int)n_index;
     unsigned long long* mask = static_cast<unsigned long long*>(workspace);
     int* cnt = reinterpret_cast<int*>(mask + n_mask);
     int* count = reinterpret_cast<int*>(static_cast<unsigned char*>(workspace) + (((size_t)n_mask * 12 + 255) & ~(size_t)255));
     int2* clist = reinterpret_cast<int2*>(count + 64);
-    blank_scan_parts_kernel<<<dim3((unsigned)n_mask), dim3(1024), 0, s>>>(patches, index, (int)n_index, blank_emb, emb, pa, mask, cnt);
+    const dim3 grid((unsigned)n_mask), block(1024);
+    const unsigned char* bytes = static_cast<const unsigned char*>(src.base);
+    const float* floats = static_cast<const float*>(src.base);
+    // the scans' load widths are the eight-patch trunk kernel's: 16-byte loads or dwords (float32 images), 16 / 4 / 1 bytes
+    if (u8 && view)
+        blank_scan_parts_view_u8_kernel<<<grid, block, 0, s>>>(bytes, view_args(src, {16, 4, 1}), src.index, n, blank_emb, emb, pa,
+                                                               mask, cnt);
+    else if (u8) blank_scan_parts_u8_kernel<<<grid, block, 0, s>>>(bytes, src.index, n, blank_emb, emb, pa, mask, cnt);
+    else if (view)
+        blank_scan_parts_view_kernel<<<grid, block, 0, s>>>(floats, view_args(src, {16}), src.index, n, blank_emb, emb, pa, mask, cnt);
+    else blank_scan_parts_kernel<<<grid, block, 0, s>>>(floats, src.index, n, blank_emb, emb, pa, mask, cnt);
     IPSX_TRY(launched("blank_scan_parts"));
-    blank_compact_kernel<<<dim3((unsigned)cdiv(n_mask, 4)), dim3(256), 0, s>>>(mask, cnt, n_mask, index, clist, count, n_encoded);
+    blank_compact_kernel<<<dim3((unsigned)cdiv(n_mask, 4)), dim3(256), 0, s>>>(mask, cnt, n_mask, src.index, clist, count, n_encoded);
     IPSX_TRY(launched("blank_compact"));
-    return fused_trunk_encode_parts_compact(t, PatchSrc{patches, nullptr, nullptr, index, 0}, n_index, emb, part_end, n_parts, done,
-                                            clist, count, s);
+    return fused_trunk_encode_parts_compact(t, src, n_index, emb, part_end, n_parts, done, clist, count, s);
+}
+
+IPSX_API int ipsx_trunk_encode_parts_dedup(const ipsx_trunk* t, const float* patches, const int32_t* index, int64_t n_index,
+                                           float* emb, const int64_t* part_end, int n_parts, int32_t* done,
+                                           const float* blank_emb, void* workspace, size_t workspace_bytes, int32_t* n_encoded,
+                                           void* stream) {
+    return encode_parts_dedup(t, PatchSrc{patches, nullptr, nullptr, index, 0}, false, false, n_index, emb, part_end, n_parts, done,
+                              blank_emb, workspace, workspace_bytes, n_encoded, stream, "trunk_encode_parts_dedup");
+}
+
+IPSX_API int ipsx_trunk_encode_parts_dedup_u8(const ipsx_trunk* t, const uint8_t* patches, const float* table, const int32_t* index,
+                                              int64_t n_index, float* emb, const int64_t* part_end, int n_parts, int32_t* done,
+                                              const float* blank_emb, void* workspace, size_t workspace_bytes,
+                                              int32_t* n_encoded, void* stream) {
+    return encode_parts_dedup(t, PatchSrc{patches, table, nullptr, index, 0}, true, false, n_index, emb, part_end, n_parts, done,
+                              blank_emb, workspace, workspace_bytes, n_encoded, stream, "trunk_encode_parts_dedup_u8");
+}
+
+IPSX_API int ipsx_trunk_encode_parts_dedup_view(const ipsx_trunk* t, const float* images, const ipsx_patch_view* v,
+                                                const int32_t* index, int64_t n_index, float* emb, const int64_t* part_end,
+                                                int n_parts, int32_t* done, const float* blank_emb, void* workspace,
+                                                size_t workspace_bytes, int32_t* n_encoded, void* stream) {
+    return encode_parts_dedup(t, PatchSrc{images, nullptr, v, index, 0}, false, true, n_index, emb, part_end, n_parts, done,
+                              blank_emb, workspace, workspace_bytes, n_encoded, stream, "trunk_encode_parts_dedup_view");
+}
+
+IPSX_API int ipsx_trunk_encode_parts_dedup_view_u8(const ipsx_trunk* t, const uint8_t* images, const float* table,
+                                                   const ipsx_patch_view* v, const int32_t* index, int64_t n_index, float* emb,
+                                                   const int64_t* part_end, int n_parts, int32_t* done, const float* blank_emb,
+                                                   void* workspace, size_t workspace_bytes, int32_t* n_encoded, void* stream) {
+    return encode_parts_dedup(t, PatchSrc{images, table, v, index, 0}, true, true, n_index, emb, part_end, n_parts, done,
+                              blank_emb, workspace, workspace_bytes, n_encoded, stream, "trunk_encode_parts_dedup_view_u8");
 }

@@ -518,26 +518,7 @@ __device__ __forceinline__ void stage_u8_row16(const uint4 q, const float* tab, 
         for (int j = 0; j < 4; ++j) d[4 * k + j] = tab[(w[k] >> (8 * j)) & 0xFFu];
 }
 
-// patch-grid view: the NK float4 units k0 .. k0 + NK - 1 (unit k: pixels 4 (64 k + lane) .. + 3 of the 1x32x32 patch) that
-// this lane stages, read from the image rows at `src` (the patch's first pixel; row pitch w floats).  wide (launch-uniform):
-// 16-byte loads - src and every row start are 16-byte aligned - else four dword loads.
-template <int NK>
-__device__ __forceinline__ void view_load_32(const float* src, int w, int wide, int lane, int k0, float4 (&px)[NK]) {
-    if (wide) {
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            const int e = ((k0 + k) * 64 + lane) * 4;
-            px[k] = *reinterpret_cast<const float4*>(src + (long long)(e >> 5) * w + (e & 31));
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < NK; ++k) {
-            const int e = ((k0 + k) * 64 + lane) * 4;
-            const float* q = src + (long long)(e >> 5) * w + (e & 31);
-            px[k] = make_float4(q[0], q[1], q[2], q[3]);
-        }
-    }
-}
+// (patch-grid view: the float4 units a lane stages come through view_load_32, ipsx_common.h - the blank scan reads them too)
 
 // one patch by one wavefront on its own slab S: the input load and the stem + pool, whose output is left in the slab in
 // the 8x8 stage's layout, behind a workgroup barrier (layer1 reads every slab) - the front of fused_trunk_kernel
@@ -1024,6 +1005,9 @@ static void fused_lds_attrs() {
         {reinterpret_cast<const void*>(fused_trunk_parts_u8_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_parts_view_u8_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_parts_dedup_kernel), FUSED_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_parts_dedup_u8_kernel), FUSED_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_parts_dedup_view_kernel), FUSED_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_parts_dedup_view_u8_kernel), FUSED_LDS},
     };
     for (const auto& e : list) (void)hipFuncSetAttribute(e.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e.bytes);
     attr_set = true;
@@ -1167,21 +1151,36 @@ int fused_trunk_encode_parts(const ipsx_trunk* t, const PatchSrc& src, int64_t n
 // rounds through eight-patch workgroups, a remainder of up to half a round through pair workgroups, which are done with it
 // well before a started round would be (profiles/dedup_rounds_pair_table.txt).  The eight-patch grid is sized for a list
 // without a blank entry, the pair grid for the largest remainder the rule hands over; the workgroups beyond their share
-// return at once.  float32 patches through their index list only.
+// return at once.  src: any of the four kinds fused_trunk_encode_parts takes, through their index list (checked by the
+// entry, in front of the scan: patch_src_check) - the kernels differ in their last arguments only, as there.
 int fused_trunk_encode_parts_compact(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, const int64_t* part_end,
                                      int parts, int* done, const int2* clist, const int* count, hipStream_t s) {
     FusedArgs a;
     PartsArgs pa;
     IPSX_TRY(parts_launch_args(t, src, n, emb, part_end, parts, done, "trunk_encode_parts_dedup", a, pa));
-    if (src.table || src.view || !clist || !count)
-        return fail(IPSX_EINVAL, "trunk_encode_parts_dedup: float32 patches through an index list, with the scan's list and count");
+    if (!clist || !count) return fail(IPSX_EINVAL, "trunk_encode_parts_dedup: an index list, with the scan's list and count");
     a.count = count;
     const int cus = device_cus(), mode = g_pair_mode;
-    fused_trunk_parts_dedup_kernel<<<dim3((unsigned)cdiv(n, 8)), dim3(512), FUSED_LDS, s>>>(a, pa, clist, cus, mode);
+    const dim3 grid8((unsigned)cdiv(n, 8));
+    if (src.table && src.view)
+        fused_trunk_parts_dedup_view_u8_kernel<<<grid8, dim3(512), FUSED_LDS, s>>>(a, pa, clist, cus, mode, src.table,
+                                                                                  fused_view_args(src));
+    else if (src.table) fused_trunk_parts_dedup_u8_kernel<<<grid8, dim3(512), FUSED_LDS, s>>>(a, pa, clist, cus, mode, src.table);
+    else if (src.view)
+        fused_trunk_parts_dedup_view_kernel<<<grid8, dim3(512), FUSED_LDS, s>>>(a, pa, clist, cus, mode, fused_view_args(src));
+    else fused_trunk_parts_dedup_kernel<<<grid8, dim3(512), FUSED_LDS, s>>>(a, pa, clist, cus, mode);
     IPSX_TRY(launched("fused_trunk_parts_dedup"));
-    const int64_t grid2 = trunk_split_pair_grid(n, cus, mode);
-    if (grid2 == 0) return IPSX_OK;                                   // (mode 1: the eight-patch launch takes every entry)
-    fused_trunk_pair_parts_dedup_kernel<<<dim3((unsigned)grid2), dim3(256), (size_t)2 * SLAB * sizeof(float), s>>>(a, pa, clist, cus, mode);
+    const int64_t n2 = trunk_split_pair_grid(n, cus, mode);
+    if (n2 == 0) return IPSX_OK;                                      // (mode 1: the eight-patch launch takes every entry)
+    const dim3 grid2((unsigned)n2);
+    const size_t lds2 = (size_t)2 * SLAB * sizeof(float);
+    if (src.table && src.view)
+        fused_trunk_pair_parts_dedup_view_u8_kernel<<<grid2, dim3(256), lds2, s>>>(a, pa, clist, cus, mode, src.table,
+                                                                                  fused_view_args(src, 8));
+    else if (src.table) fused_trunk_pair_parts_dedup_u8_kernel<<<grid2, dim3(256), lds2, s>>>(a, pa, clist, cus, mode, src.table);
+    else if (src.view)
+        fused_trunk_pair_parts_dedup_view_kernel<<<grid2, dim3(256), lds2, s>>>(a, pa, clist, cus, mode, fused_view_args(src));
+    else fused_trunk_pair_parts_dedup_kernel<<<grid2, dim3(256), lds2, s>>>(a, pa, clist, cus, mode);
     return launched("fused_trunk_pair_parts_dedup");
 }
 

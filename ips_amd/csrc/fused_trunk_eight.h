@@ -795,3 +795,21 @@ __global__ __launch_bounds__(512, 1) void fused_trunk_parts_dedup_kernel(FusedAr
                                                                         int pair_mode) {
     fused_trunk_body<false, false, true, false, true>(a, nullptr, nullptr, &pa, nullptr, clist, cus, pair_mode);
 }
+
+// ... on uint8 patches, on a view of float32 images and on a view of uint8 images: clist[p].y is the patch - or GRID patch -
+// number as it stands (the COMPACT arm of fused_trunk_body never adds va->first), the input load is the kind's (trunk_front)
+__global__ __launch_bounds__(512, 1) void fused_trunk_parts_dedup_u8_kernel(FusedArgs a, PartsArgs pa, const int2* clist, int cus,
+                                                                           int pair_mode, const float* table) {
+    fused_trunk_body<false, true, true, false, true>(a, nullptr, table, &pa, nullptr, clist, cus, pair_mode);
+}
+
+__global__ __launch_bounds__(512, 1) void fused_trunk_parts_dedup_view_kernel(FusedArgs a, PartsArgs pa, const int2* clist, int cus,
+                                                                             int pair_mode, ViewArgs va) {
+    fused_trunk_body<false, false, true, true, true>(a, nullptr, nullptr, &pa, &va, clist, cus, pair_mode);
+}
+
+__global__ __launch_bounds__(512, 1) void fused_trunk_parts_dedup_view_u8_kernel(FusedArgs a, PartsArgs pa, const int2* clist,
+                                                                                int cus, int pair_mode, const float* table,
+                                                                                ViewArgs va) {
+    fused_trunk_body<false, true, true, true, true>(a, nullptr, table, &pa, &va, clist, cus, pair_mode);
+}

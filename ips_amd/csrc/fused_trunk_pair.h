@@ -430,6 +430,35 @@ __global__ __launch_bounds__(256, 2) void fused_trunk_pair_parts_dedup_kernel(Fu
     trunk_pair_tile<false, false, false, true>(a, p_first, lds, nullptr, nullptr, &pa, clist, n_list);
 }
 
+// ... on uint8 patches, on a view of float32 images and on a view of uint8 images (va.wide: the pair kernel's 8 / 4 / 1 bytes)
+__global__ __launch_bounds__(256, 2) void fused_trunk_pair_parts_dedup_u8_kernel(FusedArgs a, PartsArgs pa, const int2* clist,
+                                                                                int cus, int pair_mode, const float* table) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];          // 2 slabs
+    const long long n_list = *a.count;
+    const long long p_first = trunk_split_n8(n_list, cus, pair_mode) + (long long)blockIdx.x * 2;
+    if (p_first >= n_list) return;                                        // workgroup-uniform
+    trunk_pair_tile<false, true, false, true>(a, p_first, lds, table, nullptr, &pa, clist, n_list);
+}
+
+__global__ __launch_bounds__(256, 2) void fused_trunk_pair_parts_dedup_view_kernel(FusedArgs a, PartsArgs pa, const int2* clist,
+                                                                                  int cus, int pair_mode, ViewArgs va) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];          // 2 slabs
+    const long long n_list = *a.count;
+    const long long p_first = trunk_split_n8(n_list, cus, pair_mode) + (long long)blockIdx.x * 2;
+    if (p_first >= n_list) return;                                        // workgroup-uniform
+    trunk_pair_tile<false, false, true, true>(a, p_first, lds, nullptr, &va, &pa, clist, n_list);
+}
+
+__global__ __launch_bounds__(256, 2) void fused_trunk_pair_parts_dedup_view_u8_kernel(FusedArgs a, PartsArgs pa, const int2* clist,
+                                                                                     int cus, int pair_mode, const float* table,
+                                                                                     ViewArgs va) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];          // 2 slabs
+    const long long n_list = *a.count;
+    const long long p_first = trunk_split_n8(n_list, cus, pair_mode) + (long long)blockIdx.x * 2;
+    if (p_first >= n_list) return;                                        // workgroup-uniform
+    trunk_pair_tile<false, true, true, true>(a, p_first, lds, table, &va, &pa, clist, n_list);
+}
+
 // ------------------------------------------------------------------ one image as ONE persistent launch
 // A single image is not worth cutting into parts for the selection loop to run beside: the loop's
 // workgroup has to find a compute unit the trunk's workgroups leave free, and the last part's iterations are exposed.

@@ -80,6 +80,27 @@ __device__ __forceinline__ void view_load_u8(const unsigned char* q, int width, 
             w[k] = (unsigned)q[4 * k] | ((unsigned)q[4 * k + 1] << 8) | ((unsigned)q[4 * k + 2] << 16) | ((unsigned)q[4 * k + 3] << 24);
     }
 }
+
+// float32 images: the NK float4 units k0 .. k0 + NK - 1 (unit k: pixels 4 (64 k + lane) .. + 3 of the 1x32x32 patch) that
+// this lane stages, read from the image rows at `src` (the patch's first pixel; row pitch w floats).  wide (launch-uniform):
+// 16-byte loads - src and every row start are 16-byte aligned - else four dword loads.
+template <int NK>
+__device__ __forceinline__ void view_load_32(const float* src, int w, int wide, int lane, int k0, float4 (&px)[NK]) {
+    if (wide) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int e = ((k0 + k) * 64 + lane) * 4;
+            px[k] = *reinterpret_cast<const float4*>(src + (long long)(e >> 5) * w + (e & 31));
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const int e = ((k0 + k) * 64 + lane) * 4;
+            const float* q = src + (long long)(e >> 5) * w + (e & 31);
+            px[k] = make_float4(q[0], q[1], q[2], q[3]);
+        }
+    }
+}
 #endif
 
 }  // namespace ipsx

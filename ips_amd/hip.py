@@ -77,9 +77,10 @@ def dedup_blank():
 
 
 def dedup_auto():
-    """IPSX_DEDUP_BLANK unset (or ``auto``): exact blank-patch dedup inside the one counted launch, where that route runs on
-    a float32 patch tensor (``selection.parts_one_launch``, ``ipsx_trunk_encode_parts_dedup``); every other route runs as
-    under ``0`` and refuses nothing.  ``0``: no dedup anywhere."""
+    """IPSX_DEDUP_BLANK unset (or ``auto``): exact blank-patch dedup inside the one counted launch, wherever that route runs -
+    float32 or uint8 patches, float32 or uint8 images (``selection.parts_one_launch``, ``ipsx_trunk_encode_parts_dedup`` and
+    its ``_u8`` / ``_view`` / ``_view_u8`` twins); every other route runs as under ``0`` and refuses nothing.  ``0``: no
+    dedup anywhere."""
     return os.environ.get("IPSX_DEDUP_BLANK", "auto") == "auto"
 
 
@@ -355,6 +356,15 @@ _EXPORTS = {
     "ipsx_trunk_encode_parts_dedup": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
                                                 C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                 C.c_void_p, C.c_void_p]),
+    "ipsx_trunk_encode_parts_dedup_u8": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,
+                                                   C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                   C.c_void_p, C.c_void_p]),
+    "ipsx_trunk_encode_parts_dedup_view": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.POINTER(PatchViewStruct), C.c_void_p, C.c_int64,
+                                                     C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ipsx_trunk_encode_parts_dedup_view_u8": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.POINTER(PatchViewStruct),
+                                                        C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "ipsx_part_wait": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "ipsx_logits_if": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),

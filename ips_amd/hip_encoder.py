@@ -70,8 +70,8 @@ class EncoderPlan:
         self._ws = None
         self._ws_small = 0
         self._held = 0
-        self.blank_emb = None      # the fused fp32 trunk's embedding of an all-zero patch, for this weight state
-        self._blank_ready = None   # (the stream it was made on, the event behind its launch)
+        self.blank_emb = None      # the fused fp32 trunk's embedding of a blank patch that blank_embedding() returned last
+        self._blank = {}           # per kind "f32" | "u8": (the row, (stream it was made on, event behind its launch), table, its version)
         self.n_encoded = None      # device int32: what the last dedup call really encoded
         self.bf16 = False          # feature nets: the projector runs on the bf16 matrix pipe (IPSX_PRECISION=bf16)
 
@@ -180,6 +180,7 @@ class EncoderPlan:
     def _rebuild(self):
         self._keep = []
         self.blank_emb = None
+        self._blank = {}
         enc = self.encoder
         if self.is_image:
             mods = list(enc.children())
@@ -271,22 +272,34 @@ class EncoderPlan:
         return t
 
     def blank_embedding(self, src):
-        """(1, D) embedding of an all-zero patch of ``src``'s shape on the fused fp32 trunk, by the counted launch's own
-        kernel (``ipsx_trunk_encode_parts`` on one patch); kept until ``_refresh()`` sees the weights change (``_rebuild``
-        drops it).  One tiny launch per weight state, on the stream that is current then; a call on another stream waits for
-        that launch's event."""
-        if self.blank_emb is None or self.blank_emb.device != src.device:
-            dev = src.device
-            zero = torch.zeros((1,) + tuple(src.shape[-3:]), dtype=torch.float32, device=dev)
+        """(1, D) embedding of a blank patch of ``src``'s shape on the fused fp32 trunk, by the counted launch's own kernel
+        on one patch: all 0.0f through ``ipsx_trunk_encode_parts`` for float32 patches and images, all bytes 0 - every pixel
+        ``table[c][0]``, which need not be 0.0f - through ``ipsx_trunk_encode_parts_u8`` for uint8 ones.  A view shares its
+        tensor kind's row (held to the bit by tests/test_dedup_sources.py).  Kept per kind until ``_refresh()`` sees the
+        weights change (``_rebuild`` drops both), the bytes' also only while the table is the same tensor, unwritten
+        (the tensor is held here, so its address cannot come back as another table's).  One tiny launch per state, on the
+        stream that is current then; a call on another stream waits for that launch's event.  ``blank_emb`` is the row the
+        last call returned."""
+        dev, tab = src.device, src.table
+        kind = "f32" if tab is None else "u8"
+        held = self._blank.get(kind)
+        if held is not None and (held[0].device != dev or held[2] is not tab or (tab is not None and held[3] != tab._version)):
+            held = None
+        if held is None:
+            zero = torch.zeros((1,) + tuple(src.shape[-3:]), dtype=torch.float32 if tab is None else torch.uint8, device=dev)
             words = torch.zeros((2,), dtype=torch.int32, device=dev)       # the list [0] | the part's counter
             out = torch.empty((1, self.d_out), dtype=torch.float32, device=dev)
-            _ck(lib().ipsx_trunk_encode_parts(C.byref(self._describe(zero.shape, 0)), _p(zero), _p(words[0:1]), 1, _p(out),
-                                              (C.c_int64 * 1)(1), 1, _p(words[1:2]), _stream()), "ipsx_trunk_encode_parts")
-            self.blank_emb = out
-            self._blank_ready = (torch.cuda.current_stream(dev), torch.cuda.Event())
-            self._blank_ready[1].record()
-        elif torch.cuda.current_stream(src.device) != self._blank_ready[0]:
-            torch.cuda.current_stream(src.device).wait_event(self._blank_ready[1])   # made on another stream: behind its launch
+            tr, tail = C.byref(self._describe(zero.shape, 0)), (_p(words[0:1]), 1, _p(out), (C.c_int64 * 1)(1), 1, _p(words[1:2]), _stream())
+            if tab is None:
+                _ck(lib().ipsx_trunk_encode_parts(tr, _p(zero), *tail), "ipsx_trunk_encode_parts")
+            else:
+                _ck(lib().ipsx_trunk_encode_parts_u8(tr, _p(zero), _p(tab), *tail), "ipsx_trunk_encode_parts_u8")
+            ready = (torch.cuda.current_stream(dev), torch.cuda.Event())
+            ready[1].record()
+            held = self._blank[kind] = (out, ready, tab, None if tab is None else tab._version)
+        elif torch.cuda.current_stream(dev) != held[1][0]:
+            torch.cuda.current_stream(dev).wait_event(held[1][1])          # made on another stream: behind its launch
+        self.blank_emb = held[0]
         return self.blank_emb
 
     def encode_source(self, src, index=None, first=0, n=None, parts=None, out=None, dedup=False):
@@ -298,9 +311,10 @@ class EncoderPlan:
         ``parts`` = (part_end, done): ``index`` is the index lists of several parts one after the other, ending at the
         list entries ``part_end`` (ints), encoded as ONE launch that counts part k's finished patches into ``done[k]``
         (int32 on the GPU, zeroed by the caller on this stream) - float32 patches, uint8 patches with their table, or a view
-        of float32 or uint8 images, on the exact fp32 fused trunk.  ``dedup`` (with ``parts``, a float32 patch tensor): exact
-        blank-patch dedup inside that launch (``ipsx_trunk_encode_parts_dedup``) - the same bits, the all-zero entries'
-        rows written from ``blank_embedding``; ``n_encoded`` then holds the number of entries the trunk encoded."""
+        of float32 or uint8 images, on the exact fp32 fused trunk.  ``dedup`` (with ``parts``, any of those four): exact
+        blank-patch dedup inside that launch (``ipsx_trunk_encode_parts_dedup`` and its ``_u8`` / ``_view`` / ``_view_u8``
+        twins) - the same bits, the rows of the all-zero (bytes: all-zero-byte) entries written from ``blank_embedding``;
+        ``n_encoded`` then holds the number of entries the trunk encoded."""
         self._refresh()
         # the trunk struct describes THIS call's patches: nothing an earlier call or question left in it is read
         t, L = self._describe(src.shape, 0 if src.table is not None else _PATCH_DTYPES[src.dtype]), lib()
@@ -334,28 +348,23 @@ class EncoderPlan:
                 raise TypeError("parts=(part_end, done) take float32 patches, or uint8 patches with their table, and the "
                                 "parts' index lists")
             ends, done = (C.c_int64 * len(parts[0]))(*parts[0]), _p(parts[1])
-            if tab.value and vs is not None:               # whole uint8 images
-                _ck(L.ipsx_trunk_encode_parts_view_u8(tr, _p(base), tab, vs, _p(index), n, _p(out), ends, len(ends), done,
-                                                      _stream()), "ipsx_trunk_encode_parts_view_u8")
-            elif tab.value:
-                _ck(L.ipsx_trunk_encode_parts_u8(tr, _p(base), tab, _p(index), n, _p(out), ends, len(ends), done, _stream()),
-                    "ipsx_trunk_encode_parts_u8")
-            elif vs is not None:
-                _ck(L.ipsx_trunk_encode_parts_view(tr, _p(base), vs, _p(index), n, _p(out), ends, len(ends), done, _stream()),
-                    "ipsx_trunk_encode_parts_view")
-            elif dedup:
-                # exact blank-patch dedup inside the launch: the blank embedding of this weight state goes in front
+            # the four storage kinds differ in the export's suffix and in what follows the base pointer: the table, the view
+            kind = ("_view" if vs is not None else "") + ("_u8" if tab.value else "")
+            args = (tr, _p(base)) + ((tab,) if tab.value else ()) + ((vs,) if vs is not None else ()) + \
+                   (_p(index), n, _p(out), ends, len(ends), done)
+            if dedup:
+                # exact blank-patch dedup inside the launch: the blank embedding of this weight state (bytes: and of this
+                # table) goes in front
                 blank = self.blank_embedding(src)
                 self._describe(src.shape, 0)               # (blank_embedding described its own patch)
                 nb = L.ipsx_trunk_parts_dedup_workspace_bytes(tr, n)
                 if self.n_encoded is None or self.n_encoded.device != src.device:
                     self.n_encoded = torch.zeros((), dtype=torch.int32, device=src.device)
-                _ck(L.ipsx_trunk_encode_parts_dedup(tr, _p(base), _p(index), n, _p(out), ends, len(ends), done, _p(blank),
-                                                    _p(self._workspace(nb, src.device)), nb, _p(self.n_encoded), _stream()),
-                    "ipsx_trunk_encode_parts_dedup")
+                name = "ipsx_trunk_encode_parts_dedup" + kind
+                _ck(getattr(L, name)(*args, _p(blank), _p(self._workspace(nb, src.device)), nb, _p(self.n_encoded), _stream()), name)
             else:
-                _ck(L.ipsx_trunk_encode_parts(tr, _p(base), _p(index), n, _p(out), ends, len(ends), done, _stream()),
-                    "ipsx_trunk_encode_parts")
+                name = "ipsx_trunk_encode_parts" + kind
+                _ck(getattr(L, name)(*args, _stream()), name)
             return out
         if index is not None and vs is None:               # a patch tensor through an index list: the fused trunk
             if tab.value:

@@ -731,6 +731,15 @@ class Selection:
                 and vq.dtype == torch.float32 and src.count < (1 << 31) - 16
                 and _env_on("IPSX_ONE_LAUNCH") and hip.persistent_ok(src.device))
 
+    @staticmethod
+    def one_launch_dedup(src):
+        """Exact blank-patch dedup inside the counted launch of ``parts_one_launch``: with ``IPSX_DEDUP_BLANK`` unset (or
+        ``auto``), for every source that route takes - float32 or uint8 patches, a view of float32 or uint8 images (a blank
+        byte patch is all bytes 0: ``EncoderPlan.blank_embedding``).  ``0``: nowhere; ``1``: the explicit route's business
+        (``hip.dedup_blank``), which this route is not.  A function of the source's kind and the environment only."""
+        return (hip.dedup_auto() and src.dtype in (torch.float32, torch.uint8)
+                and (src.table is not None) == (src.dtype == torch.uint8))
+
     def parts_one_launch(self, src, every, edges, its, pos_enc, vq, R):
         """``parts_with_ranges`` without the trunk's launch boundaries: ``every`` is the parts' index lists
         joined.  The trunk launch goes to the main stream FIRST - a runtime that runs the two streams one after the other
@@ -758,10 +767,9 @@ class Selection:
         zeroed = torch.cuda.Event()
         zeroed.record(main)
         ends = self.part_ends(B, edges)
-        # float32 patch tensors: blank entries are found, written and counted in front of the trunk launch, which encodes
-        # the others only (same bits; the waits below see done[k] fill as before)
-        dedup = hip.dedup_auto() and src.dtype == torch.float32 and not src.is_view and src.table is None
-        emb_all = plan.encode_source(src, index=every, parts=(ends, done), dedup=dedup)
+        # blank entries are found, written and counted in front of the trunk launch, which encodes the others only (same
+        # bits; the waits below see done[k] fill as before)
+        emb_all = plan.encode_source(src, index=every, parts=(ends, done), dedup=self.one_launch_dedup(src))
         emb_all.record_stream(side)
         starts = [0] + ends[:-1]
         net._emb_parts = parts = [emb_all[starts[k]:ends[k]].view(B, edges[k + 1] - edges[k], -1) for k in range(P)]
