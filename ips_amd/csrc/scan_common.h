@@ -1060,6 +1060,8 @@ FastPlan scan_fast_plan(int m, int i, int h, int n_token);                 // sc
 int launch_scan_fast(const ScanCall& c, const FastPlan& fp);               // scan_fast.hip
 bool scan_cam_shape(int m, int i, int h, int n_token);                     // scan_cam.hip: BASELINE configs[3]'s shape
 int launch_scan_cam(const ScanCall& c);                                    // scan_cam.hip
+bool scan_mnist_shape(int m, int i, int h, int n_token);                   // scan_mnist.hip: BASELINE configs[1] / [2]'s shape
+int launch_scan_mnist(const ScanCall& c);                                  // scan_mnist.hip
 size_t scan_large_ws_per_image(int m, int i, int h, int n_token);          // scan_large.hip
 int launch_scan_large(const ScanCall& c);                                  // scan_large.hip
 int scan_large_team(int b, int m, int i, int h, int n_token);              // scan_large.hip: workgroups per image (1: no team)
@@ -1075,6 +1077,7 @@ extern bool g_scan_direct;             // diagnostic (ipsx_dbg_scan_direct)
 extern bool g_scan_team_trunc;         // diagnostic (ipsx_dbg_scan_team_trunc): 0 = the team's main workgroup always merges whole runs
 extern int g_scan_team;                // diagnostic (ipsx_dbg_scan_team): -1 the default, 0 one workgroup per image, 2 / 4 / 8
 extern bool g_scan_r8;                 // diagnostic (ipsx_dbg_scan_r8): 0 sends scan_cam_kernel's shape through scan_fast_kernel
+extern bool g_scan_mnist;              // diagnostic (ipsx_dbg_scan_mnist): 0 sends scan_mnist_kernel's shape through scan_fast_kernel
 extern unsigned long long* g_scan_stamps;      // diagnostic (ipsx_dbg_scan_stamps)
 unsigned long long* persist_log();     // device address of the resident loops' / the gate's log (scorer.hip: g_persist_log)
 

@@ -1,5 +1,5 @@
 // scorer.hip - the selection loop behind the C ABI: ipsx_scan* / ipsx_scan_persistent* / ipsx_scan_gate / ipsx_publish_rows
-// pick the kernel a shape takes (scan_fast.hip, scan_cam.hip, scan_large.hip) and own the process-wide switches.
+// pick the kernel a shape takes (scan_fast.hip, scan_cam.hip, scan_mnist.hip, scan_large.hip) and own the process-wide switches.
 // (Round 6: the logits live in logits.hip, scores / top-M in topm.hip, shared device code in scan_common.h.)
 //
 // Reference: MultiHeadCrossAttention.get_attn (architecture/transformer.py:71-83),
@@ -36,6 +36,7 @@ bool g_scan_team_trunc = true;      // diagnostic (ipsx_dbg_scan_team_trunc)
 int g_scan_team = -1;               // diagnostic (ipsx_dbg_scan_team): workgroups per image of scan_large_team_kernel (-1: default)
 bool g_scan_direct = true;          // diagnostic (ipsx_dbg_scan_direct): 0 = scan_large_kernel's five generic passes for every shape
 bool g_scan_r8 = true;              // diagnostic (ipsx_dbg_scan_r8): 0 sends the shape of scan_cam_kernel through scan_fast_kernel
+bool g_scan_mnist = true;           // diagnostic (ipsx_dbg_scan_mnist): 0 sends the shape of scan_mnist_kernel through scan_fast_kernel
 unsigned long long* g_scan_stamps = nullptr;   // diagnostic only (ipsx_dbg_scan_stamps)
 
 // Diagnostic (ipsx_dbg_persist_log; tools/soak.py): what the gate and the resident loops saw, on the 100 MHz clock -
@@ -249,6 +250,12 @@ static int scan_range_impl(const float* logits, int b, int64_t n, int m, int i, 
     if (!fp.ok || (g_scan_generic && !ready && !cond)) return launch_scan_large(c);
     // BASELINE configs[3] (8 heads, one token, M = I = 256): the specialised loop
     if (g_scan_r8 && scan_cam_shape(m, i, h, n_token)) return launch_scan_cam(c);
+    // BASELINE configs[1] / [2] (8 heads, 4 tokens, M = I = 64): the specialised loop - plain, conditional and persistent
+    // launches of one workgroup per image on contiguous logits; strided logits (ipsx_scan_range_strided) and the stamped
+    // diagnostic build stay on scan_fast_kernel
+    if (g_scan_mnist && scan_mnist_shape(m, i, h, n_token) && c.logits_bstride_rows == n && (workgroups <= 0 || workgroups >= b) &&
+        g_scan_stamps == nullptr)
+        return launch_scan_mnist(c);
     return launch_scan_fast(c, fp);
 }
 
@@ -287,3 +294,9 @@ extern "C" __attribute__((visibility("default"))) void ipsx_dbg_scan_team(int w)
 // Diagnostic: 0 = the team's ranking always from whole runs (the path taken when the runs' top halves are not provably enough)
 extern "C" __attribute__((visibility("default"))) void ipsx_dbg_scan_team_trunc(int on) { g_scan_team_trunc = on != 0; }
 extern "C" __attribute__((visibility("default"))) void ipsx_dbg_scan_r8(int on) { g_scan_r8 = on != 0; }
+// Diagnostic: 0 sends the shape of scan_mnist_kernel (8 heads, 4 tokens, M = I = 64) through scan_fast_kernel (tools/scan_compare.py,
+// tests/test_scan_mnist.py, the A/B measurements); ipsx_dbg_scan_mnist_shape is the dispatcher's shape predicate
+extern "C" __attribute__((visibility("default"))) void ipsx_dbg_scan_mnist(int on) { g_scan_mnist = on != 0; }
+extern "C" __attribute__((visibility("default"))) int ipsx_dbg_scan_mnist_shape(int m, int i, int h, int n_token) {
+    return scan_mnist_shape(m, i, h, n_token) ? 1 : 0;
+}

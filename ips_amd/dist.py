@@ -110,14 +110,23 @@ def default_units():
     return DEFAULT_UNITS
 
 
+# scan_mnist_kernel (8 heads x 4 tokens, M = I = 64), measured on 16 images x 2,500 patches, the loop alone: 3.39 us per
+# iteration over 39 iterations, launch included (2.73 us over the 156 of 10,000 patches; scan_fast_kernel: 5.86 / 4.98 us;
+# profiles/scan_mnist_loop.json)
+LOOP_US_MNIST = 3.4
+
+
 def loop_iteration_us(M, I, H, T):
-    """Rough duration of one iteration of the selection loop kernels: ~4 us at the CAMELYON shape and
-    6.7 us at the MNIST shape (both 4,096 logits per iteration), 92 us at 10,000 candidates of 8 logits."""
+    """Rough duration of one iteration of the selection loop kernels: ~4 us at the CAMELYON shape, 3.4 us
+    at the MNIST shape (both 4,096 logits per iteration; other shapes of 32 logits on scan_fast_kernel: 6.7 us), 92 us at
+    10,000 candidates of 8 logits."""
     L, R = M + I, H * T
     if L > 1024:
         return 92.0 * L * R / 80000.0
     if (M, I, H, T) == (256, 256, 8, 1):                  # scan_cam_kernel's shape
         return 4.2
+    if (M, I, H, T) == (64, 64, 8, 4):                    # scan_mnist_kernel's shape
+        return LOOP_US_MNIST
     return 2.5 + L * R / 1000.0
 
 

@@ -917,6 +917,21 @@ def scan_persistent_large(M, I, H, T):
             and M + I <= 16384 and H * T <= 256)
 
 
+def scan_mnist_shape(M, I, H, T):
+    """Is this the shape of ``scan_mnist_kernel`` (8 heads x 4 tokens, M = I = 64: the dispatcher's predicate)?"""
+    fn = lib().ipsx_dbg_scan_mnist_shape           # (diagnostic export, not in include/ipsx.h: bound here, not in _EXPORTS)
+    fn.restype, fn.argtypes = C.c_int, [C.c_int] * 4
+    return bool(fn(M, I, H, T))
+
+
+def dbg_scan_mnist(on):
+    """Diagnostic: ``False`` sends ``scan_mnist_kernel``'s shape through ``scan_fast_kernel`` (comparisons, A/B timing);
+    the default is on.  Process-wide: restore it in a ``finally``."""
+    fn = lib().ipsx_dbg_scan_mnist
+    fn.restype, fn.argtypes = None, [C.c_int]
+    fn(1 if on else 0)
+
+
 def scan_persistent_groupable(M, I, H, T):
     """Can fewer resident workgroups than images run this shape's persistent loops (``scan_persistent(workgroups=)``)?"""
     return bool(lib().ipsx_scan_persistent_groupable(M, I, H, T))
