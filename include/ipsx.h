@@ -111,7 +111,9 @@ extern "C" {
  *         additions pin it);
  *         ipsx_trunk_encode_parts_dedup_u8, ipsx_trunk_encode_parts_dedup_view, ipsx_trunk_encode_parts_dedup_view_u8 - that
  *         dedup on the other three sources of the counted launch: uint8 patches, float32 images and uint8 images through a
- *         patch view (additions only, the minor number stays for the same reason) */
+ *         patch view (additions only, the minor number stays for the same reason);
+ *         ipsx_scan_ragged - the selection loop over slides of different lengths packed into one logits table, one launch
+ *         (an addition, the minor number stays for the same reason) */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -663,6 +665,17 @@ int ipsx_scan_range(const float* logits, int b, int64_t n, int m, int i, int h, 
 int ipsx_scan_range_strided(const float* logits, int64_t logits_bstride_rows, int b, int64_t n, int m, int i, int h,
                             int n_token, int64_t it_begin, int64_t it_end, int64_t* mem_idx, float* mem_score,
                             int32_t* tie_flag, void* workspace, size_t workspace_bytes, void* stream);
+/* 3.06: ipsx_scan on b slides of DIFFERENT lengths in one launch.  The slides' logits lie one after the other in one packed
+ * (total, h * n_token) table; row_offsets (device, b + 1 int64, ascending from 0 to total) says where each starts.  Slide k is
+ * scanned as ipsx_scan scans a contiguous copy of its rows alone - its own n = row_offsets[k + 1] - row_offsets[k], its own
+ * ceil((n - m) / i) iterations and ragged last chunk - by one workgroup (plain launches only; never a team of workgroups):
+ * mem_idx (b, m) holds slide-LOCAL row numbers, mem_score and tie_flag are per slide as ipsx_scan leaves them.  No row at or
+ * behind row_offsets[k + 1] is read for slide k.  n_max (the longest slide) and total are the caller's host-side knowledge
+ * (dispatch, the < 2^31 checks); the caller guarantees that EVERY slide has more than m rows - a slide that has not, or
+ * whose offsets leave the table, is left untouched.  workspace: b times ipsx_scan_workspace_bytes(1, m, i, h, n_token). */
+int ipsx_scan_ragged(const float* logits, const int64_t* row_offsets, int b, int64_t n_max, int64_t total, int m, int i,
+                     int h, int n_token, int64_t* mem_idx, float* mem_score, int32_t* tie_flag, void* workspace,
+                     size_t workspace_bytes, void* stream);
 
 /* The whole loop as ONE launch that may start before any logits exist (overlap with the encoder without re-launching
  * per part): the kernel waits until *ready (device int32, written with ipsx_publish_rows on another stream after the

@@ -33,6 +33,7 @@ import torch
 from torch import nn
 
 from .. import hip
+from ..ragged import Ragged
 from ..shuffle import draw_shuffle, shuffle_batch, shuffle_instance
 from .resnet import load_torchvision_checkpoint, resnet18_trunk, resnet50_trunk
 from .transformer import Transformer, pos_enc_1d
@@ -117,6 +118,7 @@ class IPSNet(nn.Module):
         self._plan = None             # packed-weight cache of the HIP encoder
         self._emb_parts = None        # eval-mode embeddings of the last ips() call (see last_mem_emb)
         self._mem_emb = None
+        self._ragged_rows = None      # ips_ragged: (global rows (1, B * M) of its winners, the call's last_mem_idx)
         self._selection = None        # the HIP selection pipelines (ips_amd/selection.py), built on first use
         self._device_patches = None   # lazy loading: the device copy of the host tensor, when it is kept
         # uint8 patch storage (ips_amd/quant.py): the (n_chan, 256) float32 table of set_patch_table - a plain tensor
@@ -292,7 +294,12 @@ class IPSNet(nn.Module):
 
         uint8 image patches (after ``set_patch_table``): the same selection on a quarter of the bytes; ``mem_patch``
         comes back float32 - the selected bytes dequantised, bit for bit what the call returns for the expanded tensor.
+
+        A ``ips_amd.ragged.Ragged`` (slides of different lengths, e.g. from a loader with ``collate_ragged``) goes to
+        ``ips_ragged``.
         """
+        if isinstance(patches, Ragged):
+            return self.ips_ragged(patches)
         B, N = patches.shape[:2]
         u8 = patches.dtype == torch.uint8
         if u8:
@@ -302,6 +309,22 @@ class IPSNet(nn.Module):
             mem_patch = patches.to(self.device)
             return (self._dequant(mem_patch) if u8 else mem_patch), (self.pos_enc.expand(B, -1, -1) if self.use_pos else None)
         return self._call(patches)
+
+    @torch.no_grad()
+    def ips_ragged(self, slides):
+        """``ips()`` on slides of DIFFERENT lengths in one call: ``slides`` an ``ips_amd.ragged.Ragged`` or a
+        list of (N_b, F) | (N_b, C, h, w) tensors, on the device or on the host (copied whole)
+        -> (mem_patch (B, M, ...), mem_pos (B, M, D) | None).  Slide by slide and bit for bit what
+        ``for b in range(B): out[b] = net.ips(slides[b][None])`` returns and leaves behind - ``last_mem_idx`` (B, M), local
+        to each slide, ``last_mem_emb`` (B, M, D), ``last_shuffle`` the list of the B per-slide permutations (drawn slide by
+        slide, in slide order: torch's RNG streams end where that loop leaves them) -, positions restarting at 0 in every
+        slide.  On a ROCm device: one encoder pass over all rows, one packed logits table, ONE loop launch
+        (``ipsx_scan_ragged``), gathers over global rows; on a CPU device the loop itself.  Refused before the first launch:
+        a slide with N_b <= M (the reference returns N_b patches there: no rectangular result), ``use_pos`` with
+        N_b > conf.N (with 'instance' shuffling: N_b != conf.N, where ``ips()`` itself raises), an empty batch, uint8 rows,
+        ``IPSX_DEDUP_BLANK=1``."""
+        from ..ragged import ips_ragged
+        return ips_ragged(self, slides)
 
     @contextlib.contextmanager
     def _scoring(self):
@@ -501,7 +524,11 @@ class IPSNet(nn.Module):
         and skip the second encoder pass (SURVEY.md section 8 f, N-a).  Gathered on first use."""
         if self._mem_emb is None and self._emb_parts and self.last_mem_idx is not None:
             emb = self._emb_parts[0] if len(self._emb_parts) == 1 else torch.cat(self._emb_parts, dim=1)
-            self._mem_emb = self._take(emb, self.last_mem_idx)
+            if self._ragged_rows is not None and self._ragged_rows[1] is self.last_mem_idx:      # (ips_ragged: one packed table)
+                self._mem_emb = self._take(emb, self._ragged_rows[0]).view(*self.last_mem_idx.shape, -1)
+            else:
+                self._mem_emb = self._take(emb, self.last_mem_idx)
+            self._ragged_rows = None
             self._emb_parts = None
         return self._mem_emb
 

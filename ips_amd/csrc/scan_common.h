@@ -702,6 +702,26 @@ struct ScanArgs {
     long long lg_bs;       // rows between the images' logits: read by the STRIDED instantiations only (ipsx_scan_range_strided)
 };
 
+// RAGGED (ipsx_scan_ragged): workgroup b's slide out of the packed table - rows [row_off[b], row_off[b + 1]) of rows_total.
+// The argument blocks stay as they are (every other kernel compiles to the instructions it always did): a RAGGED launch is
+// never a stamped one, so the row offsets travel as the kernels' second argument (`stamps`), and rows_total as lg_bs, which
+// the STRIDED instantiations alone read.  The two offsets are workgroup-uniform and kept scalar; a slide the caller's
+// guarantee (more than m rows, inside the table) does not hold for is not touched (-> false).
+__device__ __forceinline__ bool ragged_slide(const long long* row_off, long long rows_total, int b, int m, int i,
+                                             long long* first, long long* n, long long* n_iter) {
+    const long long r0 = row_off[b], r1 = row_off[b + 1];
+    const long long lo = ((long long)__builtin_amdgcn_readfirstlane((int)(r0 >> 32)) << 32) |
+                         (unsigned int)__builtin_amdgcn_readfirstlane((int)r0);
+    const long long hi = ((long long)__builtin_amdgcn_readfirstlane((int)(r1 >> 32)) << 32) |
+                         (unsigned int)__builtin_amdgcn_readfirstlane((int)r1);
+    *first = lo;
+    *n = hi - lo;
+    if (!(lo >= 0 && hi <= rows_total && hi - lo > m && hi - lo < (1ll << 31))) return false;
+    // (n < 2^31: the division in 32 bits - it runs on the vector unit - and its quotient back into a scalar register)
+    *n_iter = (long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)((unsigned int)(hi - lo - m + i - 1) / (unsigned int)i));
+    return true;
+}
+
 // ipsx_scan_range_if: the recovery launch behind a persistent loop - every workgroup looks at the word the loop sets when
 // it gave up waiting and leaves at once when it is clear (workgroup-uniform).
 __device__ __forceinline__ bool scan_skipped(const int* cond, int mask) {
@@ -1048,6 +1068,8 @@ struct ScanCall {
     int32_t cond_mask;
     int ready_stride, workgroups;
     int64_t logits_bstride_rows;       // rows between the images' logits: n for every entry but ipsx_scan_range_strided
+    const int64_t* row_offsets;        // ipsx_scan_ragged alone: (b + 1) row offsets on the device into a packed table of
+                                       //   logits_bstride_rows rows in all; n is then the longest slide.  nullptr for every other entry
 };
 
 // Is this shape the LDS-resident loop's (scan_fast_kernel)?  Otherwise scan_large_kernel takes it (and needs a workspace).

@@ -11,7 +11,10 @@ namespace ipsx {
 
 // STRIDED: the images' logits lie a.lg_bs rows apart (ipsx_scan_range_strided) - an instantiation of its own, so that the
 // kernels every other entry launches are compiled from the code they always were
-template <int R, int T, int EPT, int LCH, bool STAMP, bool PERSIST, bool STRIDED = false>
+// RAGGED: the third mode of that kind (ipsx_scan_ragged) - workgroup b's rows, their number and its iteration count come
+// from row_off[b], row_off[b + 1] (ragged_slide, scan_common.h: the offsets arrive as `stamps`); behind that the loop is the
+// code below, unchanged
+template <int R, int T, int EPT, int LCH, bool STAMP, bool PERSIST, bool STRIDED = false, bool RAGGED = false>
 __global__ __launch_bounds__(SCAN_NT) void scan_fast_kernel(ScanArgs a, unsigned long long* stamps) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // prefetch registers per (prefetching) thread: 4, 5 for 32 rows x up to 512 candidates - the reference's shipped
@@ -54,7 +57,13 @@ __global__ __launch_bounds__(SCAN_NT) void scan_fast_kernel(ScanArgs a, unsigned
     float* eB = eA + (size_t)Lmax * ld;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x;
-    const float* lg = a.lg + (size_t)b * (STRIDED ? a.lg_bs : a.n) * R;
+    long long first_row = 0;
+    if constexpr (RAGGED) {
+        a.it0 = 0;
+        static_assert(!(RAGGED && (STAMP || PERSIST || STRIDED)), "scan_fast_kernel: RAGGED is a plain launch");
+        if (!ragged_slide(reinterpret_cast<const long long*>(stamps), a.lg_bs, b, a.m, a.i, &first_row, &a.n, &a.it1)) return;
+    }
+    const float* lg = RAGGED ? a.lg + (size_t)first_row * R : a.lg + (size_t)b * (STRIDED ? a.lg_bs : a.n) * R;
     const int r = tid & (R - 1), lrow0 = tid >> log2R;
     constexpr int lstep = SCAN_NT >> log2R;
 
@@ -439,9 +448,16 @@ int launch_scan_fast(const ScanCall& c, const FastPlan& fp) {
     const int ept = fp.ept, lch = fp.lch;
     unsigned long long* st = g_scan_stamps;
     const bool strided = c.logits_bstride_rows != c.n;
+    const bool ragged = c.row_offsets != nullptr;           // (plain launches only: scorer.hip ipsx_scan_ragged)
+    // (the row offsets in the place of the stamps, the table's rows in a.lg_bs: ragged_slide, scan_common.h)
+    unsigned long long* const row_off = reinterpret_cast<unsigned long long*>(const_cast<int64_t*>(c.row_offsets));
 #define IPSX_LAUNCH_FAST(RR, TT, E, C, S)                                                                           \
     do {                                                                                                            \
-        if (a.ready) {                                                                                              \
+        if (ragged) {                                                                                               \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_fast_kernel<RR, TT, E, C, false, false, false, true>), \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast);                       \
+            scan_fast_kernel<RR, TT, E, C, false, false, false, true><<<dim3((unsigned)b), dim3(SCAN_NT), fast, as_stream(stream)>>>(a, row_off); \
+        } else if (a.ready) {                                                                                       \
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_fast_kernel<RR, TT, E, C, false, true>),   \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast);                       \
             scan_fast_kernel<RR, TT, E, C, false, true><<<dim3((unsigned)b), dim3(SCAN_NT), fast, as_stream(stream)>>>(a, nullptr); \
@@ -478,8 +494,8 @@ int launch_scan_fast(const ScanCall& c, const FastPlan& fp) {
         scan_fast_kernel<8, 1, 4, 8, true, true><<<dim3((unsigned)b), dim3(SCAN_NT), fast, as_stream(stream)>>>(a, st);
         return launched("scan");
     }
-    if (st && R == 8 && n_token == 1 && ept == 4 && lch == 8) IPSX_LAUNCH_FAST(8, 1, 4, 8, true);
-    if (st && R == 32 && n_token == 4 && ept == 4 && lch == 2) IPSX_LAUNCH_FAST(32, 4, 4, 2, true);
+    if (st && !ragged && R == 8 && n_token == 1 && ept == 4 && lch == 8) IPSX_LAUNCH_FAST(8, 1, 4, 8, true);
+    if (st && !ragged && R == 32 && n_token == 4 && ept == 4 && lch == 2) IPSX_LAUNCH_FAST(32, 4, 4, 2, true);
     if (R == 8 && n_token == 1) IPSX_LAUNCH_FAST_E(8, 1);
     IPSX_LAUNCH_FAST_E(32, 4);
 #undef IPSX_LAUNCH_FAST_C

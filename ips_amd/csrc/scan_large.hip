@@ -331,7 +331,7 @@ constexpr int LARGE_U = 8;
         }                                                                          \
     } while (0)
 
-template <bool STAMP, bool STRIDED = false>      // (STRIDED: see scan_fast_kernel)
+template <bool STAMP, bool STRIDED = false, bool RAGGED = false>      // (STRIDED, RAGGED: see scan_fast_kernel)
 __global__ __launch_bounds__(LARGE_NT) void scan_large_kernel(LargeArgs a, unsigned long long* stamps) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int R = a.h * a.T, Lp = a.Lp, m = a.m;
@@ -341,7 +341,13 @@ __global__ __launch_bounds__(LARGE_NT) void scan_large_kernel(LargeArgs a, unsig
     const int tail = (a.n2 + (a.n2 >> 4)) * 8 + ((R + 1) & ~1) * 8;
     const int tid = threadIdx.x, b = blockIdx.x;
     constexpr int NW = LARGE_NT / 64;
-    const float* lg = a.lg + (size_t)b * (STRIDED ? a.lg_bs : a.n) * R;
+    long long first_row = 0;
+    if constexpr (RAGGED) {
+        a.it0 = 0;
+        static_assert(!(RAGGED && (STAMP || STRIDED)), "scan_large_kernel: RAGGED is a plain launch");
+        if (!ragged_slide(reinterpret_cast<const long long*>(stamps), a.lg_bs, b, m, a.i, &first_row, &a.n, &a.it1)) return;
+    }
+    const float* lg = RAGGED ? a.lg + (size_t)first_row * R : a.lg + (size_t)b * (STRIDED ? a.lg_bs : a.n) * R;
     long long* mem = a.mem_idx + (size_t)b * m;
     float* xT = reinterpret_cast<float*>(a.ws + (size_t)b * a.ws_per_image);
     int* lists = reinterpret_cast<int*>(xT + (size_t)R * Lp);
@@ -783,6 +789,14 @@ int launch_scan_large(const ScanCall& c) {
         const size_t lds = large_lds_bytes(n2, R);
         IPSX_REQUIRE(lds <= kLdsLimit, "scan: internal - %zu B of LDS", lds);
         // a team of workgroups per image (scan_large_team.h) - not the conditional recovery launch, which must not wait on anyone
+        if (c.row_offsets != nullptr) {                                // ipsx_scan_ragged: one workgroup per slide, never a team
+            IPSX_REQUIRE(!ready && !cond, "scan_ragged: plain launches only");
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_large_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            // (the row offsets in the place of the stamps, the table's rows - fewer than 2^31 - in la.lg_bs: ragged_slide, scan_common.h)
+            scan_large_kernel<false, false, true><<<dim3((unsigned)b), dim3(LARGE_NT), lds, as_stream(stream)>>>(
+                la, reinterpret_cast<unsigned long long*>(const_cast<int64_t*>(c.row_offsets)));
+            return launched("scan");
+        }
         const int W = cond ? 1 : scan_large_team(b, m, i, h, n_token);
         const bool strided = c.logits_bstride_rows != n && !ready && !cond;
         if (W > 1 && !(g_scan_stamps && n2 / (LARGE_NT * W) != 2)) {

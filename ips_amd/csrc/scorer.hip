@@ -96,6 +96,29 @@ IPSX_API int ipsx_scan_range_strided(const float* logits, int64_t logits_bstride
                            workspace, workspace_bytes, stream, nullptr, 0, 0, 0, logits_bstride_rows);
 }
 
+// ipsx_scan on slides of different lengths: slide k's logits are rows [row_offsets[k], row_offsets[k + 1]) of ONE packed
+// (total, R) table, the offsets b + 1 int64 on the device.  One plain launch of one workgroup per slide - the RAGGED
+// instantiation of the loop kernel the shape takes (never scan_mnist_kernel, never a team) -, each replaying the loop of
+// ipsx_scan for its slide alone: mem_idx (b, m) is slide-local.  n_max (the longest slide) and total are the caller's
+// host-side knowledge; every slide has more than m rows (a slide that has not, or that leaves the table, is left untouched).
+IPSX_API int ipsx_scan_ragged(const float* logits, const int64_t* row_offsets, int b, int64_t n_max, int64_t total, int m,
+                              int i, int h, int n_token, int64_t* mem_idx, float* mem_score, int32_t* tie_flag,
+                              void* workspace, size_t workspace_bytes, void* stream) {
+    IPSX_REQUIRE(logits && row_offsets && mem_idx, "scan_ragged: null pointer");
+    IPSX_REQUIRE(b > 0 && m > 0 && i > 0 && h > 0 && n_token > 0, "scan_ragged: bad sizes");
+    IPSX_REQUIRE(n_max > m, "scan_ragged: needs more patches per slide (longest: %lld) than memory slots (%d)", (long long)n_max, m);
+    IPSX_REQUIRE(total >= n_max && total <= (int64_t)b * n_max && total < ((int64_t)1 << 31),
+                 "scan_ragged: %lld rows in all (fewer than 2^31) for %d slides of at most %lld", (long long)total, b, (long long)n_max);
+    if (tie_flag && hipMemsetAsync(tie_flag, 0, sizeof(int32_t) * (size_t)b, as_stream(stream)) != hipSuccess)
+        return fail(IPSX_EHIP, "scan_ragged: memset failed");
+    const FastPlan fp = scan_fast_plan(m, i, h, n_token);
+    ScanCall c = {logits, b, n_max, m, i, h, n_token, 0, (n_max - m + i - 1) / i, mem_idx, mem_score, tie_flag, nullptr, nullptr,
+                  workspace, workspace_bytes, stream, nullptr, 0, 0, 0, total, row_offsets};
+    if (!fp.ok || g_scan_generic) return launch_scan_large(c);
+    if (g_scan_r8 && scan_cam_shape(m, i, h, n_token)) return launch_scan_cam(c);
+    return launch_scan_fast(c, fp);
+}
+
 IPSX_API size_t ipsx_scan_workspace_bytes(int b, int m, int i, int h, int n_token) {
     if (b <= 0 || m <= 0 || i <= 0 || h <= 0 || n_token <= 0) return 0;
     if (scan_fast_plan(m, i, h, n_token).ok && !g_scan_generic) return 0;

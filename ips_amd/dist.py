@@ -29,6 +29,7 @@ import torch
 import torch.distributed as dist
 
 from . import hip
+from .ragged import Ragged, refuse
 
 PARTS = 4
 DEFAULT_UNITS = 256            # compute units of an MI355X in SPX mode: what a plan assumes where no GPU is visible (CPU tests)
@@ -384,6 +385,8 @@ def ips_sharded(net, local_patches, N, group=None, timings=None, plan=None):
     ``timings`` (GPU path only): a list that receives one dict of HIP events per call - see ``phase_ms`` - so that a
     run can say where a rank's time went (encoder, exchange, loop, what of the loop stayed exposed).
     """
+    if isinstance(local_patches, Ragged):
+        refuse("dist.ips_sharded")
     if local_patches.dtype == torch.uint8:
         raise TypeError("sharded IPS reads float32 patches (uint8 patch storage: IPSNet.ips on one device)")
     world, rank = _world_rank(group)

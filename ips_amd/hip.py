@@ -327,6 +327,8 @@ _EXPORTS = {
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ipsx_scan_range_strided": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64,
                                           C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ipsx_scan_ragged": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ipsx_stream_commit": (C.c_int, [C.POINTER(StreamTable), C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                      C.c_void_p]),
     "ipsx_stream_commit_view": (C.c_int, [C.POINTER(StreamTable), C.c_int, C.c_void_p, C.POINTER(PatchViewStruct), C.c_int,
@@ -668,6 +670,36 @@ def scan_range_strided(lg, n, M, I, H, T, it_begin, it_end, mem_idx, tie, worksp
     _ck(lib().ipsx_scan_range_strided(_p(lg), cap, B, n, M, I, H, T, it_begin, it_end, _p(mem_idx), None, _p(tie),
                                       _p(ws), ws.numel() if ws is not None else 0, _stream()), "ipsx_scan_range_strided")
     return mem_idx
+
+
+def scan_ragged(lg, offsets, lengths, M, I, H, T, want_scores=False, workspace=None):
+    """The IPS chunk loop on slides of different lengths in ONE launch (``ipsx_scan_ragged``): ``lg`` the packed
+    (sum N_b, H*T) float32 logits, ``offsets`` the (B + 1,) int64 prefix sum of ``lengths`` on ``lg``'s device, ``lengths``
+    the host ints -> mem_idx (B, M) int64, slide-local (and the scores with ``want_scores``); the tie flags are left in
+    ``scan_ragged.last_tie``.  Every slide must have more than ``M`` rows: checked here, on the host lengths."""
+    lengths = [int(n) for n in lengths]
+    B, total = len(lengths), sum(lengths)
+    if B == 0:
+        raise ValueError("scan_ragged: no slides")
+    if lg.dtype != torch.float32 or lg.dim() != 2 or not lg.is_contiguous() or lg.shape != (total, H * T):
+        raise ValueError("scan_ragged needs a contiguous float32 ({}, {}) logits table, got {} {}".format(
+            total, H * T, lg.dtype, tuple(lg.shape)))
+    if offsets.dtype != torch.int64 or tuple(offsets.shape) != (B + 1,) or not offsets.is_contiguous() or offsets.device != lg.device:
+        raise ValueError("scan_ragged needs the ({},) int64 row offsets on the logits' device".format(B + 1))
+    for k, n in enumerate(lengths):
+        if n <= M:
+            raise ValueError("slide {} has {} rows: the loop needs more than M = {}".format(k, n, M))
+    mem_idx = torch.empty((B, M), dtype=torch.int64, device=lg.device)
+    sc = torch.empty((B, M), dtype=torch.float32, device=lg.device) if want_scores else None
+    tie = torch.empty((B,), dtype=torch.int32, device=lg.device)
+    ws = workspace
+    if ws is None:
+        nb = lib().ipsx_scan_workspace_bytes(1, M, I, H, T)
+        ws = torch.empty(B * nb, dtype=torch.uint8, device=lg.device) if nb else None
+    _ck(lib().ipsx_scan_ragged(_p(lg), _p(offsets), B, max(lengths), total, M, I, H, T, _p(mem_idx), _p(sc), _p(tie), _p(ws),
+                               ws.numel() if ws is not None else 0, _stream()), "ipsx_scan_ragged")
+    scan_ragged.last_tie = tie
+    return (mem_idx, sc) if want_scores else mem_idx
 
 
 def _stream_tables(tables, n_cand):

@@ -43,6 +43,7 @@ copies the kept patches out of it.  Everywhere else the piece is unfolded and ta
 import torch
 
 from . import hip
+from .ragged import Ragged, refuse
 
 
 class BandGeometry:
@@ -189,6 +190,8 @@ class IPSStream:
         """Take the next ``piece`` (B, n, ...) of every image.  Stream-ordered on the current stream: when the call
         returns, the caller may overwrite or free the piece with work on that stream.  Host pieces are copied to the
         device as they are."""
+        if isinstance(piece, Ragged):
+            refuse("ips_stream().feed()")
         if self._geom is not None:
             raise TypeError("this is a row stream (ips_stream(patch_size, patch_stride)): it takes feed_rows(band), not patches")
         self._check(piece)
@@ -267,6 +270,8 @@ class IPSStream:
         """Take the next pixel rows ``band`` (B, C, h, W) of every image - float32, or uint8 after ``set_patch_table``; on the
         device or on the host.  The patch rows the band completes are this feed's piece (none: nothing is launched).
         Stream-ordered like ``feed``: when the call returns, the caller may overwrite or free the band."""
+        if isinstance(band, Ragged):
+            refuse("ips_stream().feed_rows()")
         drop, rows, ny_w, carry, _ = self._check_rows(band)
         net = self.net
         (ph, pw), (sh, sw) = self._patch_size, self._patch_stride
