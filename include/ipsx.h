@@ -113,7 +113,9 @@ extern "C" {
  *         dedup on the other three sources of the counted launch: uint8 patches, float32 images and uint8 images through a
  *         patch view (additions only, the minor number stays for the same reason);
  *         ipsx_scan_ragged - the selection loop over slides of different lengths packed into one logits table, one launch
- *         (an addition, the minor number stays for the same reason) */
+ *         (an addition, the minor number stays for the same reason);
+ *         ipsx_ragged_finish - the end of a padded ragged call in one launch: selected rows of long slides, the rows of
+ *         short slides in the order given, zero padding, indices and global rows (an addition, the minor number stays) */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -768,6 +770,20 @@ int ipsx_ips_finish_indexed(const void* patches, int64_t patch_row_bytes, int64_
                             const void* pos, int64_t pos_row_bytes, int64_t pos_bstride_rows, const int64_t* mem_idx,
                             const int64_t* order, int64_t order_bstride, int b, int m, void* mem_patch, void* mem_pos,
                             int64_t* mem_idx_out, const int32_t* status, int32_t* status_host, void* stream);
+
+/* 3.06: the end of a PADDED ragged call (IPSNet.ips_ragged(pad=True)) in ONE launch, grid (m, b).  rows: the packed rows of
+ * all slides, (total, row_bytes); row_offsets: (b + 1) int64 on the device; mem_idx: (b, m) slide-local, as ipsx_scan_ragged
+ * leaves it (the rows of slides with no more than m rows are never read; NULL when no slide is longer); flat: (total) int32
+ * or NULL - packed row g is source row flat[g] of `rows` (a shuffle applied as an index); pos: the packed positional rows
+ * (total, pos_row_bytes) in packed numbering, or NULL.  Slide k has n = row_offsets[k + 1] - row_offsets[k] rows.
+ *   n > m:   slot j takes local row r = clamp(mem_idx[k][j], 0, n - 1);
+ *   n <= m:  slot j < n takes r = j; slots j >= n are WRITTEN as zeros (patch and positional row), index and row -1.
+ * mem_patch[k][j] = rows[flat ? clamp(flat[g], 0, total - 1) : g], mem_pos[k][j] = pos[g], mem_idx_out[k][j] = r,
+ * rows_out[k][j] = g = row_offsets[k] + r.  Nothing is read outside [0, total); a slide whose offsets leave the table is
+ * left untouched.  Rows are whole 16-byte units at 16-byte addresses, as ipsx_ips_finish asks. */
+int ipsx_ragged_finish(const void* rows, int64_t row_bytes, int64_t total, const int64_t* row_offsets,
+                       const int64_t* mem_idx, const int32_t* flat, const void* pos, int64_t pos_row_bytes, int b, int m,
+                       void* mem_patch, void* mem_pos, int64_t* mem_idx_out, int64_t* rows_out, void* stream);
 
 /* 3.06: the state update of a stream (IPSNet.ips_stream) as ONE launch, for up to four tables at once (patch rows,
  * embeddings, logits, global ids).  The n_cand candidates of a table are two segments that are never joined: its first

@@ -119,6 +119,7 @@ class IPSNet(nn.Module):
         self._emb_parts = None        # eval-mode embeddings of the last ips() call (see last_mem_emb)
         self._mem_emb = None
         self._ragged_rows = None      # ips_ragged: (global rows (1, B * M) of its winners, the call's last_mem_idx)
+        self._pad_state = None        # ips_ragged(pad=True): (the call's last_mem_idx, its last_mem_count, what makes its last_mem_emb)
         self._selection = None        # the HIP selection pipelines (ips_amd/selection.py), built on first use
         self._device_patches = None   # lazy loading: the device copy of the host tensor, when it is kept
         # uint8 patch storage (ips_amd/quant.py): the (n_chan, 256) float32 table of set_patch_table - a plain tensor
@@ -296,22 +297,22 @@ class IPSNet(nn.Module):
         comes back float32 - the selected bytes dequantised, bit for bit what the call returns for the expanded tensor.
 
         A ``ips_amd.ragged.Ragged`` (slides of different lengths, e.g. from a loader with ``collate_ragged``) goes to
-        ``ips_ragged``.
+        ``ips_ragged``, with its ``pad`` flag.
         """
         if isinstance(patches, Ragged):
-            return self.ips_ragged(patches)
+            return self.ips_ragged(patches, pad=patches.pad)
         B, N = patches.shape[:2]
         u8 = patches.dtype == torch.uint8
         if u8:
             self._check_u8(patches)
         if self.M >= N:  # nothing to select (:185-188)
-            self._emb_parts = self._mem_emb = self.last_shuffle = self.last_mem_idx = None
+            self._emb_parts = self._mem_emb = self.last_shuffle = self.last_mem_idx = self._pad_state = None
             mem_patch = patches.to(self.device)
             return (self._dequant(mem_patch) if u8 else mem_patch), (self.pos_enc.expand(B, -1, -1) if self.use_pos else None)
         return self._call(patches)
 
     @torch.no_grad()
-    def ips_ragged(self, slides):
+    def ips_ragged(self, slides, pad=False):
         """``ips()`` on slides of DIFFERENT lengths in one call: ``slides`` an ``ips_amd.ragged.Ragged`` or a
         list of (N_b, F) | (N_b, C, h, w) tensors, on the device or on the host (copied whole)
         -> (mem_patch (B, M, ...), mem_pos (B, M, D) | None).  Slide by slide and bit for bit what
@@ -322,9 +323,19 @@ class IPSNet(nn.Module):
         (``ipsx_scan_ragged``), gathers over global rows; on a CPU device the loop itself.  Refused before the first launch:
         a slide with N_b <= M (the reference returns N_b patches there: no rectangular result), ``use_pos`` with
         N_b > conf.N (with 'instance' shuffling: N_b != conf.N, where ``ips()`` itself raises), an empty batch, uint8 rows,
-        ``IPSX_DEDUP_BLANK=1``."""
+        ``IPSX_DEDUP_BLANK=1``.
+
+        ``pad=True`` takes slides with N_b <= M as well (an empty slide is refused) and returns the batch ``fill_batch`` of
+        training/iterative.py builds from the solo calls: a short slide's rows in the order given in slots [0, N_b) - never
+        shuffled, no random number drawn - and +0.0 behind them; ``mem_pos`` ``pos_enc[0, :N_b]`` then zeros;
+        ``last_mem_idx`` 0 .. N_b-1 then -1; ``last_mem_emb`` the eval-mode embeddings of its rows, the padding slots the
+        embedding of ONE all-zero row (what ``forward()`` in eval mode computes from the padding); its ``last_shuffle`` entry
+        None (``last_shuffle`` None when no slide is long).  ``last_mem_count`` holds the B host ints min(N_b, M); nothing
+        masks the padding - the reference attends to it as well.  Long slides are as without ``pad``.  On a ROCm device
+        the call ends in ONE launch (``ipsx_ragged_finish``) where the rows are whole 16-byte units; a batch of short slides
+        only encodes nothing until ``last_mem_emb`` is read."""
         from ..ragged import ips_ragged
-        return ips_ragged(self, slides)
+        return ips_ragged(self, slides, pad)
 
     @contextlib.contextmanager
     def _scoring(self):
@@ -349,7 +360,7 @@ class IPSNet(nn.Module):
         viewed = not torch.is_tensor(patches)
         u8 = patches.dtype == torch.uint8
         B = patches.shape[0]
-        self._emb_parts = self._mem_emb = None
+        self._emb_parts = self._mem_emb = self._pad_state = None
         self.last_shuffle = None
         with self._scoring():
             if self.use_pos:
@@ -530,7 +541,20 @@ class IPSNet(nn.Module):
                 self._mem_emb = self._take(emb, self.last_mem_idx)
             self._ragged_rows = None
             self._emb_parts = None
+        if self._mem_emb is None and self._padded() and self._pad_state[2] is not None:
+            self._mem_emb = self._pad_state[2]()
+            self._pad_state = self._pad_state[:2] + (None,)
         return self._mem_emb
+
+    def _padded(self):
+        """Was the last selection a ``ips_ragged(pad=True)`` call?  (Every selection leaves a ``last_mem_idx`` of its own.)"""
+        return self._pad_state is not None and self.last_mem_idx is not None and self._pad_state[0] is self.last_mem_idx
+
+    @property
+    def last_mem_count(self):
+        """After ``ips_ragged(slides, pad=True)``: the tuple of the B host ints min(N_b, M) - the slots of every slide that
+        hold rows of it, the rest being zero padding.  None after every other selection."""
+        return self._pad_state[1] if self._padded() else None
 
     # ---------------------------------------------------------------- aggregation
     def forward(self, mem_patch, mem_pos=None, mem_emb=None):

@@ -63,6 +63,69 @@ __global__ __launch_bounds__(256) void ips_finish_kernel(FinishArgs a) {
     }
 }
 
+// The end of a PADDED ragged call (IPSNet.ips_ragged(pad=True)) in ONE launch: workgroup (j, b) fills slot j of
+// slide b - patch row, positional row, slide-local index and global packed row.  The slide's length comes from the two row
+// offsets (workgroup-uniform, kept scalar as ragged_slide does).  A LONG slide (more than m rows) takes the loop's selection
+// idx[b][j], clamped into its own slide; a SHORT one is its rows in the order given - idx is not read for it, the loop left
+// that row unwritten - and zeros behind them: the padding is WRITTEN here (index and row -1), the output buffers need no
+// memset.  Packed row g is source row flat[g] of `rows` when a shuffle was applied as an index (the positional rows are in
+// packed numbering).  No read leaves [0, total); a slide whose offsets leave the table is left untouched.
+struct RaggedFinishArgs {
+    const uint4* rows; long long row_units, total;
+    const long long* row_off; const long long* idx; const int* flat;
+    const uint4* pos; long long pos_units;
+    uint4* out_patch; uint4* out_pos; long long* idx_out; long long* rows_out;
+    int m;
+};
+
+__global__ __launch_bounds__(256) void ragged_finish_kernel(RaggedFinishArgs a) {
+    const int j = blockIdx.x, b = blockIdx.y;
+    const long long r0 = a.row_off[b], r1 = a.row_off[b + 1];
+    const long long lo = ((long long)__builtin_amdgcn_readfirstlane((int)(r0 >> 32)) << 32) |
+                         (unsigned int)__builtin_amdgcn_readfirstlane((int)r0);
+    const long long hi = ((long long)__builtin_amdgcn_readfirstlane((int)(r1 >> 32)) << 32) |
+                         (unsigned int)__builtin_amdgcn_readfirstlane((int)r1);
+    if (!(lo >= 0 && hi >= lo && hi <= a.total)) return;
+    const long long n = hi - lo;
+    const size_t slot = (size_t)b * a.m + j;
+    uint4* d = a.out_patch + slot * a.row_units;
+    uint4* dp = a.pos ? a.out_pos + slot * a.pos_units : nullptr;
+    long long r;
+    if (n > a.m) {
+        if (!a.idx) return;                                     // (a batch of short slides only has no selection)
+        r = a.idx[slot];
+        r = r < 0 ? 0 : (r >= n ? n - 1 : r);                   // inside its OWN slide
+    } else if (j < n) {
+        r = j;
+    } else {                                                    // the padding of a short slide
+        const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+        for (long long i = threadIdx.x; i < a.row_units; i += 256) d[i] = zero;
+        if (dp)
+            for (long long i = threadIdx.x; i < a.pos_units; i += 256) dp[i] = zero;
+        if (threadIdx.x == 0) {
+            a.idx_out[slot] = -1;
+            a.rows_out[slot] = -1;
+        }
+        return;
+    }
+    const long long g = lo + r;                                 // in [lo, hi): inside the table
+    long long rs = g;
+    if (a.flat) {
+        rs = a.flat[g];
+        rs = rs < 0 ? 0 : (rs >= a.total ? a.total - 1 : rs);
+    }
+    const uint4* s = a.rows + (size_t)rs * a.row_units;
+    for (long long i = threadIdx.x; i < a.row_units; i += 256) d[i] = s[i];
+    if (dp) {
+        const uint4* sp = a.pos + (size_t)g * a.pos_units;
+        for (long long i = threadIdx.x; i < a.pos_units; i += 256) dp[i] = sp[i];
+    }
+    if (threadIdx.x == 0) {
+        a.idx_out[slot] = r;
+        a.rows_out[slot] = g;
+    }
+}
+
 }  // namespace ipsx
 
 using namespace ipsx;
@@ -108,6 +171,28 @@ IPSX_API int ipsx_ips_finish_indexed(const void* patches, int64_t patch_row_byte
     IPSX_REQUIRE(order && (order_bstride == 0 || order_bstride == n_rows), "ips_finish_indexed: order is (b or 1, n_rows)");
     return ips_finish_impl(patches, patch_row_bytes, patch_bstride_rows, n_rows, pos, pos_row_bytes, pos_bstride_rows, mem_idx, b, m,
                            mem_patch, mem_pos, mem_idx_out, status, status_host, order, order_bstride, stream);
+}
+
+// The end of IPSNet.ips_ragged(pad=True) in ONE launch (ragged_finish_kernel above): rows (total, row_bytes) the packed
+// rows, row_offsets (b + 1) int64 on the device, mem_idx (b, m) slide-local (rows of slides with at most m rows are never
+// read; NULL when no slide is longer), flat (total) int32 or NULL, pos (total, pos_row_bytes) or NULL.
+IPSX_API int ipsx_ragged_finish(const void* rows, int64_t row_bytes, int64_t total, const int64_t* row_offsets,
+                                const int64_t* mem_idx, const int32_t* flat, const void* pos, int64_t pos_row_bytes, int b, int m,
+                                void* mem_patch, void* mem_pos, int64_t* mem_idx_out, int64_t* rows_out, void* stream) {
+    IPSX_REQUIRE(rows && row_offsets && mem_patch && mem_idx_out && rows_out && b > 0 && b <= 65535 && m > 0 && total > 0,
+                 "ragged_finish: bad arguments");
+    IPSX_REQUIRE(row_bytes > 0 && row_bytes % 16 == 0 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0 &&
+                 (reinterpret_cast<uintptr_t>(mem_patch) & 15) == 0, "ragged_finish: rows of 16-byte units at 16-byte addresses");
+    IPSX_REQUIRE(!pos || (mem_pos && pos_row_bytes > 0 && pos_row_bytes % 16 == 0 && (reinterpret_cast<uintptr_t>(pos) & 15) == 0 &&
+                          (reinterpret_cast<uintptr_t>(mem_pos) & 15) == 0), "ragged_finish: positional rows of 16-byte units");
+    RaggedFinishArgs a;
+    a.rows = static_cast<const uint4*>(rows); a.row_units = row_bytes / 16; a.total = total;
+    a.row_off = reinterpret_cast<const long long*>(row_offsets); a.idx = reinterpret_cast<const long long*>(mem_idx); a.flat = flat;
+    a.pos = static_cast<const uint4*>(pos); a.pos_units = pos ? pos_row_bytes / 16 : 0;
+    a.out_patch = static_cast<uint4*>(mem_patch); a.out_pos = static_cast<uint4*>(mem_pos);
+    a.idx_out = reinterpret_cast<long long*>(mem_idx_out); a.rows_out = reinterpret_cast<long long*>(rows_out); a.m = m;
+    ragged_finish_kernel<<<dim3((unsigned)m, (unsigned)b), dim3(256), 0, as_stream(stream)>>>(a);
+    return launched("ragged_finish");
 }
 
 IPSX_API int ipsx_gather_rows(const void* src, const int64_t* idx, void* dst, int b, int64_t n_rows, int m,

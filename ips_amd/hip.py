@@ -393,6 +393,8 @@ _EXPORTS = {
     "ipsx_ips_finish_indexed": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                           C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    "ipsx_ragged_finish": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ipsx_aggregate_workspace_bytes": (C.c_size_t, [C.POINTER(Transf), C.c_int, C.c_int]),
     "ipsx_aggregate": (C.c_int, [C.POINTER(Transf), C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                  C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -672,11 +674,14 @@ def scan_range_strided(lg, n, M, I, H, T, it_begin, it_end, mem_idx, tie, worksp
     return mem_idx
 
 
-def scan_ragged(lg, offsets, lengths, M, I, H, T, want_scores=False, workspace=None):
+def scan_ragged(lg, offsets, lengths, M, I, H, T, want_scores=False, workspace=None, short_ok=False):
     """The IPS chunk loop on slides of different lengths in ONE launch (``ipsx_scan_ragged``): ``lg`` the packed
     (sum N_b, H*T) float32 logits, ``offsets`` the (B + 1,) int64 prefix sum of ``lengths`` on ``lg``'s device, ``lengths``
     the host ints -> mem_idx (B, M) int64, slide-local (and the scores with ``want_scores``); the tie flags are left in
-    ``scan_ragged.last_tie``.  Every slide must have more than ``M`` rows: checked here, on the host lengths."""
+    ``scan_ragged.last_tie``.  Every slide must have more than ``M`` rows: checked here, on the host lengths.
+    ``short_ok``: that check is skipped - the workgroup of a slide with no more than ``M`` rows returns before its first
+    read, so the ``mem_idx`` (and score) rows of such slides come back UNWRITTEN (``ragged_finish`` never reads them); one
+    slide must still be longer than ``M``."""
     lengths = [int(n) for n in lengths]
     B, total = len(lengths), sum(lengths)
     if B == 0:
@@ -687,8 +692,10 @@ def scan_ragged(lg, offsets, lengths, M, I, H, T, want_scores=False, workspace=N
     if offsets.dtype != torch.int64 or tuple(offsets.shape) != (B + 1,) or not offsets.is_contiguous() or offsets.device != lg.device:
         raise ValueError("scan_ragged needs the ({},) int64 row offsets on the logits' device".format(B + 1))
     for k, n in enumerate(lengths):
-        if n <= M:
+        if n <= M and not short_ok:
             raise ValueError("slide {} has {} rows: the loop needs more than M = {}".format(k, n, M))
+    if max(lengths) <= M:
+        raise ValueError("scan_ragged: no slide has more than M = {} rows".format(M))
     mem_idx = torch.empty((B, M), dtype=torch.int64, device=lg.device)
     sc = torch.empty((B, M), dtype=torch.float32, device=lg.device) if want_scores else None
     tie = torch.empty((B,), dtype=torch.int32, device=lg.device)
@@ -1104,6 +1111,54 @@ def ips_finish(src, pos, idx_buf, status, status_host, order=None):
     _ck(lib().ipsx_ips_finish(_p(src), row_bytes, N if src.shape[0] > 1 else 0, N, _p(pos), pos_bytes, pos_bs, _p(idx_buf), B, M,
                               _p(out), _p(out_pos), _p(idx), _p(status), _p(status_host), _stream()), "ipsx_ips_finish")
     return idx, out, out_pos
+
+
+def ragged_finish_supported(rows, pos):
+    """Can ``ragged_finish`` end a padded ragged call: packed device rows (total, ...) - and positional rows (total, D) -
+    that are whole 16-byte units at 16-byte addresses?"""
+    for t in (rows, pos):
+        if t is None:
+            continue
+        if not (on_device(t) and t.is_contiguous() and t.dim() >= 2 and t.shape[0] > 0):
+            return False
+        if (t[0].numel() * t.element_size()) % 16 or t.data_ptr() % 16:
+            return False
+    return rows is not None and (pos is None or (pos.dim() == 2 and pos.shape[0] == rows.shape[0] and pos.device == rows.device))
+
+
+def ragged_finish(rows, offsets, mem_idx, M, flat=None, pos=None, out=None):
+    """The end of ``IPSNet.ips_ragged(pad=True)``, ONE launch (``ipsx_ragged_finish``).  ``rows`` (total, ...) the packed rows
+    of the B slides, ``offsets`` (B + 1,) int64 on their device, ``mem_idx`` (B, M) int64 slide-local as ``scan_ragged``
+    leaves it (rows of slides with at most ``M`` rows are never read; None when no slide is longer), ``flat`` (total,) int32:
+    packed row g is source row ``flat[g]`` of ``rows``, ``pos`` (total, D) the packed positional rows.  A slide with more
+    than ``M`` rows gets its selected rows, a shorter one its rows in the order given and zeros behind them (written by the
+    kernel: nothing depends on what the buffers held) -> (mem_patch (B, M, ...), mem_pos (B, M, D) | None, mem_idx (B, M)
+    with -1 in the padding, rows (B, M): the packed row of every slot or -1).  ``out``: those four tensors (``mem_pos`` None
+    without ``pos``), written in place of fresh ones."""
+    if not ragged_finish_supported(rows, pos):
+        raise ValueError("ragged_finish needs packed device rows of whole 16-byte units at 16-byte addresses")
+    total, B = rows.shape[0], offsets.numel() - 1
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or B < 1 or not offsets.is_contiguous() or offsets.device != rows.device:
+        raise ValueError("ragged_finish needs the (B + 1,) int64 row offsets on the rows' device")
+    if mem_idx is not None and (mem_idx.dtype != torch.int64 or tuple(mem_idx.shape) != (B, M) or not mem_idx.is_contiguous()
+                                or mem_idx.device != rows.device):
+        raise ValueError("mem_idx must be a contiguous ({}, {}) int64 tensor on the rows' device".format(B, M))
+    if flat is not None and (flat.dtype != torch.int32 or tuple(flat.shape) != (total,) or not flat.is_contiguous()
+                             or flat.device != rows.device):
+        raise ValueError("flat must be a contiguous ({},) int32 tensor on the rows' device".format(total))
+    shapes = ((B, M) + tuple(rows.shape[1:]), rows.dtype), ((B, M, pos.shape[1]), pos.dtype) if pos is not None else None, \
+        ((B, M), torch.int64), ((B, M), torch.int64)
+    if out is None:
+        out = tuple(torch.empty(s[0], dtype=s[1], device=rows.device) if s is not None else None for s in shapes)
+    for t, s in zip(out, shapes):
+        if (t is None) != (s is None) or (t is not None and (tuple(t.shape) != s[0] or t.dtype != s[1] or not t.is_contiguous()
+                                                              or t.device != rows.device)):
+            raise ValueError("ragged_finish: out must be the four contiguous result tensors on the rows' device")
+    out, out_pos, idx, grow = out
+    _ck(lib().ipsx_ragged_finish(_p(rows), rows[0].numel() * rows.element_size(), total, _p(offsets), _p(mem_idx), _p(flat), _p(pos),
+                                 pos.shape[1] * pos.element_size() if pos is not None else 0, B, M, _p(out), _p(out_pos), _p(idx),
+                                 _p(grow), _stream()), "ipsx_ragged_finish")
+    return out, out_pos, idx, grow
 
 
 def order_index(order, B, N, out=None):

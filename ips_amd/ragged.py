@@ -10,6 +10,10 @@ them at once.  The contract is the solo calls': slide by slide and bit for bit w
 returns and leaves behind, with torch's RNG streams consumed as that loop consumes them.  On a ROCm device that is one
 encoder pass over all rows, one packed logits table, ONE selection-loop launch (``ipsx_scan_ragged``: the loop kernels on
 per-slide lengths) and the gathers over global rows; on a CPU device it is that loop.
+
+``pad=True`` takes slides with no more rows than the memory as well: the reference's ``ips()`` returns all N_b rows of such a
+slide, unshuffled, and ``fill_batch`` (training/iterative.py) writes them into zero-initialised (B, M, ...) buffers - that
+batch is what the padded call returns, its end ONE launch (``ipsx_ragged_finish``) that also writes the zero padding.
 """
 
 import os
@@ -22,9 +26,10 @@ from .shuffle import draw_shuffle
 
 class Ragged:
     """The slides of a call, one after the other: ``rows`` (sum N_b, F) | (sum N_b, C, h, w), contiguous; ``lengths`` the
-    host ints N_b.  ``offsets`` is their int64 prefix sum (B + 1,) on the rows' device, made once and kept."""
+    host ints N_b.  ``offsets`` is their int64 prefix sum (B + 1,) on the rows' device, made once and kept.  ``pad``: what
+    ``net.ips(ragged)`` hands to ``ips_ragged`` - slides with N_b <= M come back zero-padded to M rows."""
 
-    def __init__(self, rows, lengths):
+    def __init__(self, rows, lengths, pad=False):
         lengths = tuple(int(n) for n in lengths)
         if not torch.is_tensor(rows) or rows.dim() not in (2, 4):
             raise TypeError("Ragged rows are a (sum N_b, F) or (sum N_b, C, h, w) tensor")
@@ -32,6 +37,7 @@ class Ragged:
             raise ValueError("lengths {} do not add up to the {} rows".format(lengths, rows.shape[0]))
         self.rows = rows if rows.is_contiguous() else rows.contiguous()
         self.lengths = lengths
+        self.pad = bool(pad)
         starts = [0]
         for n in lengths:
             starts.append(starts[-1] + n)
@@ -39,17 +45,17 @@ class Ragged:
         self._cache = {}                                 # device -> [offsets, row_base]: shared with the copies ``to()`` makes
 
     @classmethod
-    def from_list(cls, slides):
+    def from_list(cls, slides, pad=False):
         """[(N_0, ...), (N_1, ...), ...] tensors of one row shape, dtype and device -> Ragged (the rows are joined once)."""
         slides = list(slides)
         if not slides:
-            return cls(torch.empty((0, 0)), ())
+            return cls(torch.empty((0, 0)), (), pad)
         first = slides[0]
         for k, s in enumerate(slides):
             if not torch.is_tensor(s) or s.dim() not in (2, 4) or s.shape[1:] != first.shape[1:] or s.dtype != first.dtype \
                     or s.device != first.device:
                 raise TypeError("slide {}: every slide is a (N_b, F) or (N_b, C, h, w) tensor of one row shape, dtype and device".format(k))
-        return cls(torch.cat(slides, 0), [s.shape[0] for s in slides])
+        return cls(torch.cat(slides, 0), [s.shape[0] for s in slides], pad)
 
     def __len__(self):
         return len(self.lengths)
@@ -86,7 +92,7 @@ class Ragged:
         if rows is self.rows:
             return self
         r = Ragged.__new__(Ragged)
-        r.rows, r.lengths, r.starts, r._cache = rows, self.lengths, self.starts, self._cache
+        r.rows, r.lengths, r.starts, r._cache, r.pad = rows, self.lengths, self.starts, self._cache, self.pad
         return r
 
     def to(self, *args, **kwargs):
@@ -106,16 +112,24 @@ class Ragged:
         return slot[1]
 
     def __repr__(self):
-        return "Ragged(rows={}, lengths={}, dtype={}, device={})".format(tuple(self.rows.shape), self.lengths, self.dtype, self.device)
+        return "Ragged(rows={}, lengths={}, dtype={}, device={}{})".format(tuple(self.rows.shape), self.lengths, self.dtype, self.device,
+                                                                           ", pad=True" if self.pad else "")
 
 
-def collate_ragged(samples):
+def collate_ragged(samples, pad=False):
     """A ``DataLoader`` ``collate_fn`` for the datasets' ``{'input': (N, ...), task: label}`` samples whose inputs differ in
     length: ``'input'`` becomes a ``Ragged``, everything else is collated as ``default_collate`` does."""
     from torch.utils.data import default_collate
     rest = default_collate([{k: v for k, v in s.items() if k != 'input'} for s in samples])
-    rest['input'] = Ragged.from_list([torch.as_tensor(s['input']) for s in samples])
+    rest['input'] = Ragged.from_list([torch.as_tensor(s['input']) for s in samples], pad)
     return rest
+
+
+def collate_ragged_padded(samples):
+    """``collate_ragged`` with ``pad=True``: slides with no more rows than the memory come back zero-padded to M rows, as
+    ``fill_batch`` leaves them in the (B, M, ...) buffers - the loops of training/iterative.py drive real CAMELYON batches
+    (many slides have fewer foreground tiles than M = 5000) unchanged."""
+    return collate_ragged(samples, pad=True)
 
 
 def refuse(what):
@@ -123,8 +137,10 @@ def refuse(what):
     raise TypeError("{} takes (B, N, ...) tensors: a Ragged batch goes through IPSNet.ips_ragged".format(what))
 
 
-def _check(net, slides):
-    """Everything ``ips_ragged`` refuses, before the first launch and before the first random number is drawn."""
+def _check(net, slides, pad=False):
+    """Everything ``ips_ragged`` refuses, before the first launch and before the first random number is drawn.  ``pad``:
+    slides with N_b <= M are taken (never shuffled, so 'instance' shuffling with positions does not refuse them); an empty
+    slide is not."""
     if len(slides) == 0:
         raise ValueError("ips_ragged: an empty batch")
     if slides.dtype == torch.uint8:
@@ -136,13 +152,15 @@ def _check(net, slides):
         raise TypeError("ips_ragged: {} rows for {}".format(tuple(slides.rows.shape), "an image encoder ((sum N_b, C, h, w))" if net.is_image
                                                             else "a feature net ((sum N_b, F))"))
     for b, n in enumerate(slides.lengths):
-        if n <= net.M:
+        if pad and n == 0:
+            raise ValueError("slide {} has no rows: nothing to pad".format(b))
+        if n <= net.M and not pad:
             raise ValueError("slide {} has {} rows and the memory M = {}: the reference returns all {} of them there, the "
                              "batch would not be rectangular (select such a slide with ips())".format(b, n, net.M, n))
         if net.use_pos and n > net.pos_enc.shape[1]:
             raise ValueError("slide {} has {} rows, the positional table conf.N = {}".format(b, n, net.pos_enc.shape[1]))
         if (net.use_pos and net.shuffle and net.shuffle_style == 'instance' and not net._shuffle_overridden()
-                and n != net.pos_enc.shape[1]):
+                and n > net.M and n != net.pos_enc.shape[1]):
             # (shuffle_instance gathers the WHOLE table with the slide's permutation: ips() on this slide alone raises)
             raise ValueError("slide {} has {} rows: shuffle_style 'instance' with use_pos needs slides of exactly conf.N = {} "
                              "rows, as ips() does".format(b, n, net.pos_enc.shape[1]))
@@ -166,24 +184,35 @@ def _solo_loop(net, slides):
     return torch.cat(patch, 0), (torch.cat(pos, 0) if net.use_pos else None)
 
 
-def _draw(net, slides):
+def _draw(net, slides, skip=()):
     """The permutations of a shuffled call, slide by slide in slide order, by the calls ``IPSNet._shuffle`` makes for a
     (1, N_b, ...) input on the device the slides were handed over on -> (perms | None, copies | None): ``perms`` the B
     (N_b,) permutations as drawn; an overridden ``do_shuffle`` is called as ever and returns shuffled COPIES
-    [(rows_b, pos_b)] instead (nothing is kept in ``last_shuffle`` then, as in ``ips()``)."""
+    [(rows_b, pos_b)] instead (nothing is kept in ``last_shuffle`` then, as in ``ips()``).  ``skip``: the slides of a padded
+    call that ``ips()`` returns before it shuffles (N_b <= M) - nothing is drawn for them, they stay in the order given."""
     if net._shuffle_overridden():
         copies = []
         for b in range(len(slides)):
+            if b in skip:
+                copies.append((slides[b], net.pos_enc[0, :slides.lengths[b]] if net.use_pos else None))
+                continue
             x, p = net.do_shuffle(slides[b].unsqueeze(0), net.pos_enc if net.use_pos else None)
             copies.append((x[0], p[0, :x.shape[1]] if torch.is_tensor(p) else None))
         return None, copies
     perms = []
     for b in range(len(slides)):
+        if b in skip:
+            perms.append(None)
+            continue
         perm = draw_shuffle(slides[b].unsqueeze(0), net.shuffle_style)
         if perm is None:                   # an unknown style: do_shuffle leaves everything as it is
             return None, None
         perms.append(perm.reshape(-1))
-    return perms, None
+    drawn = [p for p in perms if p is not None]
+    if not drawn:
+        return None, None
+    return [torch.arange(slides.lengths[b], dtype=torch.int64, device=drawn[0].device) if p is None else p
+            for b, p in enumerate(perms)], None
 
 
 def _index_ok(net, rows):
@@ -196,58 +225,75 @@ def _index_ok(net, rows):
     return rows.dtype == torch.float32 and bool(plan.index_list_supported(rows.shape))
 
 
+def _packed(net, slides, skip=(), encode=True):
+    """The front of a device call, inside ``net._scoring()``: the permutations drawn (none for the slides in ``skip``), the
+    slides on the device, ONE encoder pass over all rows (``encode``) and the packed positional rows
+    -> (dev, rows, flat, emb, pos): ``flat`` int32 (total,) - packed row j of the call is row flat[j] of ``rows`` - or None;
+    ``pos`` (1, total, D) or None.  Sets ``net.last_shuffle``."""
+    device, B = net.device, len(slides)
+    perms = copies = None
+    if net.shuffle:
+        # (drawn where the slides were handed over - a host-resident Ragged draws 'instance' permutations from the CPU
+        #  generator, as its solo calls do)
+        perms, copies = _draw(net, slides, skip)
+    dev = slides.to(device)                      # a host-resident Ragged is copied whole
+    rows = dev.rows
+    flat = None                               # int32 (total,): packed row j of the call is row flat[j] of ``rows``
+    local = None                              # int64 (total,): the position inside its slide of packed row j
+    if perms is not None:
+        local = torch.cat(perms).to(device)
+        flat = (local + dev.row_base()).to(torch.int32)
+        by_index = _index_ok(net, rows)
+        # (what the solo calls keep: the device copy where they select through the index, else the permutation as drawn)
+        net.last_shuffle = [None if b in skip else (local[dev.starts[b]:dev.starts[b + 1]] if by_index else perms[b]).unsqueeze(0)
+                            for b in range(B)]
+        if not by_index:
+            rows, flat = rows.index_select(0, flat), None
+    elif copies is not None:
+        rows = torch.cat([c[0] for c in copies], 0).to(device)
+    emb = None
+    if encode:                                # one encoder pass over all rows
+        if flat is None:
+            emb = net._embed(rows)
+        elif net.is_image:
+            emb = net.plan.encode_source(hip.PatchSource(rows, None), index=flat)
+        else:
+            emb = net.plan.encode(rows, index=flat)
+    pos = None
+    if net.use_pos:
+        if copies is not None:
+            pos = torch.cat([c[1] for c in copies], 0).to(device)
+        else:
+            if local is None:
+                local = torch.arange(dev.total, dtype=torch.int64, device=device) - dev.row_base()
+            pos = net.pos_enc[0].index_select(0, local)          # positions restart at 0 in every slide
+        pos = pos.unsqueeze(0)
+    return dev, rows, flat, emb, pos
+
+
 @torch.no_grad()
-def ips_ragged(net, slides):
+def ips_ragged(net, slides, pad=False):
     """``IPSNet.ips_ragged``: see there."""
+    pad = bool(pad)
     if not isinstance(slides, Ragged):
-        slides = Ragged.from_list(slides)
-    _check(net, slides)
+        slides = Ragged.from_list(slides, pad)
+    _check(net, slides, pad)
     device = net.device
+    net._pad_state = None
+    if pad:
+        return _ips_ragged_padded(net, slides)
     if not hip.on_device(device) or (net.encoder.training and not net.training):
         return _solo_loop(net, slides)
 
     B, M, D = len(slides), net.M, net.D
-    lengths, total = slides.lengths, slides.total
+    lengths = slides.lengths
     net._emb_parts = net._mem_emb = net.last_shuffle = net.last_mem_idx = net._ragged_rows = None
     with net._scoring():
-        perms = copies = None
-        if net.shuffle:
-            # (drawn where the slides were handed over - a host-resident Ragged draws 'instance' permutations from the CPU
-            #  generator, as its solo calls do)
-            perms, copies = _draw(net, slides)
-        dev = slides.to(device)                      # a host-resident Ragged is copied whole
-        rows, offsets = dev.rows, dev.offsets
         ca = net.transf.crs_attn
         vq, R = ca.folded_query(), ca.H * ca.n_token
         with net.plan.hold():
-            flat = None                               # int32 (total,): packed row j of the call is row flat[j] of ``rows``
-            local = None                              # int64 (total,): the position inside its slide of packed row j
-            if perms is not None:
-                local = torch.cat(perms).to(device)
-                flat = (local + dev.row_base()).to(torch.int32)
-                by_index = _index_ok(net, rows)
-                # (what the solo calls keep: the device copy where they select through the index, else the permutation as drawn)
-                net.last_shuffle = [(local[dev.starts[b]:dev.starts[b + 1]] if by_index else perms[b]).unsqueeze(0) for b in range(B)]
-                if not by_index:
-                    rows, flat = rows.index_select(0, flat), None
-            elif copies is not None:
-                rows = torch.cat([c[0] for c in copies], 0).to(device)
-            # one encoder pass over all rows
-            if flat is None:
-                emb = net._embed(rows)
-            elif net.is_image:
-                emb = net.plan.encode_source(hip.PatchSource(rows, None), index=flat)
-            else:
-                emb = net.plan.encode(rows, index=flat)
-            pos = None
-            if net.use_pos:
-                if copies is not None:
-                    pos = torch.cat([c[1] for c in copies], 0).to(device)
-                else:
-                    if local is None:
-                        local = torch.arange(total, dtype=torch.int64, device=device) - dev.row_base()
-                    pos = net.pos_enc[0].index_select(0, local)          # positions restart at 0 in every slide
-                pos = pos.unsqueeze(0)
+            dev, rows, flat, emb, pos = _packed(net, slides)
+            offsets = dev.offsets
             # one packed (total, R) logits table, ONE loop launch on per-slide lengths
             logits = hip.logits(emb.unsqueeze(0), pos, vq, R)[0]
             mem_idx = hip.scan_ragged(logits, offsets, lengths, M, net.I, ca.H, ca.n_token)
@@ -258,4 +304,133 @@ def ips_ragged(net, slides):
         mem_pos = hip.gather_rows(pos, grow).view(B, M, D) if net.use_pos else None
     net._emb_parts, net._ragged_rows = [emb.unsqueeze(0)], (grow, mem_idx)
     net.last_mem_idx = mem_idx
+    return mem_patch, mem_pos
+
+
+# ------------------------------------------------------------------ pad=True: short slides zero-padded to M rows
+def _pad_emb(net, long_emb, short_rows):
+    """``last_mem_emb`` of a padded call on the solo route, made on first use: the solo calls' embeddings for the long
+    slides; for a short one the eval-mode embeddings of its rows in [0, N_b) and, behind them, the embedding of ONE all-zero
+    row - what ``forward()`` in eval mode computes from the zero padding."""
+    if any(e is None for e in long_emb.values()):
+        return None
+    B, M = len(long_emb) + len(short_rows), net.M
+    out = zero = None
+    with torch.no_grad(), net._scoring():
+        for b in range(B):
+            if b in long_emb:
+                e = long_emb[b][0]
+            else:
+                rows = short_rows[b]
+                e = net._embed(rows)
+                if rows.shape[0] < M:
+                    if zero is None:
+                        zero = net._embed(torch.zeros((1,) + tuple(rows.shape[1:]), dtype=rows.dtype, device=rows.device))
+                    e = torch.cat((e, zero.expand(M - rows.shape[0], -1)), 0)
+            if out is None:
+                out = torch.empty((B, M, e.shape[-1]), dtype=e.dtype, device=e.device)
+            out[b] = e
+    return out
+
+
+def _padded_solo(net, slides):
+    """The padded call as the loop of solo calls plus the padding on ATen ops: a CPU device, and a ROCm device whose encoder
+    is in training mode inside an eval-mode net."""
+    B, M, D, device = len(slides), net.M, net.D, net.device
+    shape = tuple(slides.rows.shape[1:])
+    mem_patch = torch.zeros((B, M) + shape, dtype=slides.dtype, device=device)
+    mem_pos = torch.zeros((B, M, D), dtype=net.pos_enc.dtype, device=device) if net.use_pos else None
+    mem_idx = torch.full((B, M), -1, dtype=torch.int64, device=device)
+    long_emb, short_rows, shuf = {}, {}, []
+    for b, n in enumerate(slides.lengths):
+        if n > M:
+            p, q = net._call(slides[b].unsqueeze(0))
+            mem_patch[b] = p[0]
+            if net.use_pos:
+                mem_pos[b] = q[0]
+            mem_idx[b] = net.last_mem_idx[0]
+            long_emb[b] = net.last_mem_emb
+            shuf.append(net.last_shuffle)
+        else:                                  # what ips() returns before it shuffles, as fill_batch writes it
+            short_rows[b] = rows = slides[b].to(device)
+            mem_patch[b, :n] = rows
+            if net.use_pos:
+                mem_pos[b, :n] = net.pos_enc[0, :n]
+            mem_idx[b, :n] = torch.arange(n, dtype=torch.int64, device=device)
+            shuf.append(None)
+    net._emb_parts = net._mem_emb = net._ragged_rows = None
+    net.last_shuffle = shuf if net.shuffle and any(s is not None for s in shuf) else None
+    net.last_mem_idx = mem_idx
+    net._pad_state = (mem_idx, tuple(min(n, M) for n in slides.lengths), lambda: _pad_emb(net, long_emb, short_rows))
+    return mem_patch, mem_pos
+
+
+def _finish_aten(rows, offsets, lengths, mem_idx, M, flat, pos):
+    """``hip.ragged_finish`` for rows that are no whole 16-byte units: the ``gather_rows`` launches plus the padding on ATen
+    ops -> the same four tensors."""
+    B, device = len(lengths), rows.device
+    n = torch.tensor(lengths, dtype=torch.int64).to(device).unsqueeze(1)
+    slot = torch.arange(M, dtype=torch.int64, device=device).unsqueeze(0)
+    short = n <= M
+    valid = ~short | (slot < n)
+    local = torch.minimum(slot, n - 1).expand(B, M)
+    if mem_idx is not None:                    # (the rows of short slides come back unwritten from the loop)
+        local = torch.where(short, local, torch.minimum(mem_idx.clamp(min=0), n - 1))
+    grow = local + offsets[:-1].unsqueeze(1)
+    g = grow.reshape(1, B * M)
+    src = g if flat is None else flat.index_select(0, g[0]).to(torch.int64).unsqueeze(0)
+    mem_patch = hip.gather_rows(rows.unsqueeze(0), src).view(B, M, *rows.shape[1:])
+    mem_patch.masked_fill_(~valid.view(B, M, *(1,) * (rows.dim() - 1)), 0)
+    mem_pos = None
+    if pos is not None:
+        mem_pos = hip.gather_rows(pos.unsqueeze(0), g).view(B, M, -1)
+        mem_pos.masked_fill_(~valid.unsqueeze(-1), 0)
+    return mem_patch, mem_pos, torch.where(valid, local, -1), torch.where(valid, grow, -1)
+
+
+def _ips_ragged_padded(net, slides):
+    """``ips_ragged(pad=True)``: one encoder pass over all rows, one packed logits table, ONE loop launch (the workgroups of
+    short slides return before their first read) and ONE finish launch (``ipsx_ragged_finish``: selected rows, short
+    slides' rows in the order given, the zero padding, indices and global rows).  A batch of short slides only launches
+    no encoder, no logits and no loop."""
+    device = net.device
+    if not hip.on_device(device) or (net.encoder.training and not net.training):
+        return _padded_solo(net, slides)
+    B, M = len(slides), net.M
+    lengths = slides.lengths
+    short = frozenset(b for b, n in enumerate(lengths) if n <= M)
+    any_long = len(short) < B
+    net._emb_parts = net._mem_emb = net.last_shuffle = net.last_mem_idx = net._ragged_rows = None
+    with net._scoring():
+        ca = net.transf.crs_attn
+        with net.plan.hold():
+            dev, rows, flat, emb, pos = _packed(net, slides, skip=short, encode=any_long)
+            offsets = dev.offsets
+            mem_idx = None
+            if any_long:
+                logits = hip.logits(emb.unsqueeze(0), pos, ca.folded_query(), ca.H * ca.n_token)[0]
+                mem_idx = hip.scan_ragged(logits, offsets, lengths, M, net.I, ca.H, ca.n_token, short_ok=True)
+        pos2 = pos[0] if pos is not None else None
+        if hip.ragged_finish_supported(rows, pos2):
+            mem_patch, mem_pos, mem_idx, grow = hip.ragged_finish(rows, offsets, mem_idx, M, flat, pos2)
+        else:
+            mem_patch, mem_pos, mem_idx, grow = _finish_aten(rows, offsets, lengths, mem_idx, M, flat, pos2)
+    if net.last_shuffle is not None and all(s is None for s in net.last_shuffle):
+        net.last_shuffle = None
+
+    unencoded = rows if emb is None else None       # (a batch of short slides only: at most B * M rows, kept until they are read)
+    zero_row = (1,) + tuple(rows.shape[1:]), rows.dtype
+
+    def emb_of_slots():
+        """(B, M, D): the packed pass's rows (made now for a batch of short slides only); the padding holds the embedding
+        of ONE all-zero row."""
+        with torch.no_grad(), net._scoring(), net.plan.hold():
+            table = emb if emb is not None else net._embed(unencoded)
+            out = hip.gather_rows(table.unsqueeze(0), grow.clamp(min=0).view(1, B * M)).view(B, M, -1)
+            if any(lengths[b] < M for b in short):
+                zero = net._embed(torch.zeros(zero_row[0], dtype=zero_row[1], device=device))
+                out = torch.where((grow < 0).unsqueeze(-1), zero.view(1, 1, -1), out)
+        return out
+    net.last_mem_idx = mem_idx
+    net._pad_state = (mem_idx, tuple(min(n, M) for n in lengths), emb_of_slots)
     return mem_patch, mem_pos

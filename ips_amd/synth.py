@@ -291,3 +291,23 @@ def make_loader(conf, n_item, seed=0):
             item[task['name']] = lab
         items.append(item)
     return ListLoader(items)
+
+
+def make_slide_items(conf, lengths, seed=0):
+    """One seeded dataset sample per length: {'input': (N_k, ...), <task>: label} - slides of DIFFERENT lengths, as
+    ``CamelyonFeatures.__getitem__`` hands them out, for ``collate_ragged`` / ``collate_ragged_padded``; ``item['input'][None]``
+    with ``label[None]`` is the (B_seq = 1) loader item of the same slide."""
+    items = []
+    for k, n in enumerate(lengths):
+        g = _rng(seed, "labels%d" % k)
+        item = {'input': make_patches(conf, 1, seed=seed * 1000 + k, blank_frac=0.5, N=n)[0].contiguous()}
+        for task in conf.tasks.values():
+            if task['metric'] == 'multilabel_accuracy':
+                lab = torch.from_numpy((g.random((conf.n_class,)) < 0.3).astype(np.float32))
+            elif task['act_fn'] == 'sigmoid':
+                lab = torch.tensor(int(g.integers(0, 2)), dtype=torch.int64)
+            else:
+                lab = torch.tensor(int(g.integers(0, conf.n_class)), dtype=torch.int64)
+            item[task['name']] = lab
+        items.append(item)
+    return items
