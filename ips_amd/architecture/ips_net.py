@@ -113,13 +113,8 @@ class IPSNet(nn.Module):
         self.output_layers = self.get_output_layers(conf.tasks)
 
         # additions that do not change the drop-in surface
-        self.last_mem_idx = None      # (B, M) int64 indices chosen by the last ips() call
-        self.last_shuffle = None      # (B, N) | (1, N) int64 permutation of the last shuffled ips() call (see ips), or None
+        self._reset_last()            # what the last selection left behind: nothing yet
         self._plan = None             # packed-weight cache of the HIP encoder
-        self._emb_parts = None        # eval-mode embeddings of the last ips() call (see last_mem_emb)
-        self._mem_emb = None
-        self._ragged_rows = None      # ips_ragged: (global rows (1, B * M) of its winners, the call's last_mem_idx)
-        self._pad_state = None        # ips_ragged(pad=True): (the call's last_mem_idx, its last_mem_count, what makes its last_mem_emb)
         self._selection = None        # the HIP selection pipelines (ips_amd/selection.py), built on first use
         self._device_patches = None   # lazy loading: the device copy of the host tensor, when it is kept
         # uint8 patch storage (ips_amd/quant.py): the (n_chan, 256) float32 table of set_patch_table - a plain tensor
@@ -306,7 +301,7 @@ class IPSNet(nn.Module):
         if u8:
             self._check_u8(patches)
         if self.M >= N:  # nothing to select (:185-188)
-            self._emb_parts = self._mem_emb = self.last_shuffle = self.last_mem_idx = self._pad_state = None
+            self._reset_last()
             mem_patch = patches.to(self.device)
             return (self._dequant(mem_patch) if u8 else mem_patch), (self.pos_enc.expand(B, -1, -1) if self.use_pos else None)
         return self._call(patches)
@@ -320,7 +315,9 @@ class IPSNet(nn.Module):
         to each slide, ``last_mem_emb`` (B, M, D), ``last_shuffle`` the list of the B per-slide permutations (drawn slide by
         slide, in slide order: torch's RNG streams end where that loop leaves them) -, positions restarting at 0 in every
         slide.  On a ROCm device: one encoder pass over all rows, one packed logits table, ONE loop launch
-        (``ipsx_scan_ragged``), gathers over global rows; on a CPU device the loop itself.  Refused before the first launch:
+        (``ipsx_scan_ragged``) and ONE finish launch (``ipsx_ragged_finish``; ``gather_rows`` launches where the rows are not
+        whole 16-byte units), ``last_mem_emb`` gathered on first read; on a CPU device the loop itself.  With and without
+        ``pad`` the route is the same.  Refused before the first launch:
         a slide with N_b <= M (the reference returns N_b patches there: no rectangular result), ``use_pos`` with
         N_b > conf.N (with 'instance' shuffling: N_b != conf.N, where ``ips()`` itself raises), an empty batch, uint8 rows,
         ``IPSX_DEDUP_BLANK=1``.
@@ -331,11 +328,22 @@ class IPSNet(nn.Module):
         ``last_mem_idx`` 0 .. N_b-1 then -1; ``last_mem_emb`` the eval-mode embeddings of its rows, the padding slots the
         embedding of ONE all-zero row (what ``forward()`` in eval mode computes from the padding); its ``last_shuffle`` entry
         None (``last_shuffle`` None when no slide is long).  ``last_mem_count`` holds the B host ints min(N_b, M); nothing
-        masks the padding - the reference attends to it as well.  Long slides are as without ``pad``.  On a ROCm device
-        the call ends in ONE launch (``ipsx_ragged_finish``) where the rows are whole 16-byte units; a batch of short slides
-        only encodes nothing until ``last_mem_emb`` is read."""
+        masks the padding - the reference attends to it as well.  Long slides are as without ``pad``; the finish launch
+        writes the padding too, and a batch of short slides only encodes nothing until ``last_mem_emb`` is read."""
         from ..ragged import ips_ragged
         return ips_ragged(self, slides, pad)
+
+    def _reset_last(self):
+        """Forget the last selection.  Every entry point (``ips``, ``ips_image``, ``ips_ragged``, a stream's ``finish``, the
+        calls of ips_amd/dist.py) begins here, before it launches or draws anything, and then sets what it leaves itself:
+        nothing outlives its call.  A call that runs selections of its own inside (the host route of ``ips_ragged``,
+        ``dist.ips_tournament``) comes here once more behind them: what they left is theirs."""
+        self.last_mem_idx = None      # (B, M) int64 indices chosen by the last selection
+        self.last_shuffle = None      # (B, N) | (1, N) int64 permutation of the last shuffled ips() call (see ips), or None
+        self._emb_parts = None        # the producers' hand-off (selection.py): eval-mode embeddings of all patches, in parts
+        self._mem_emb = None          # (B, M, D): ``last_mem_emb``, once it is made
+        self._emb_make = None         # a call that gathers ``last_mem_emb`` another way: () -> (B, M, D) | None, run on first read
+        self._mem_count = None        # ``last_mem_count``
 
     @contextlib.contextmanager
     def _scoring(self):
@@ -360,8 +368,7 @@ class IPSNet(nn.Module):
         viewed = not torch.is_tensor(patches)
         u8 = patches.dtype == torch.uint8
         B = patches.shape[0]
-        self._emb_parts = self._mem_emb = self._pad_state = None
-        self.last_shuffle = None
+        self._reset_last()
         with self._scoring():
             if self.use_pos:
                 pos_enc = pos_enc.expand(B, -1, -1)
@@ -533,28 +540,19 @@ class IPSNet(nn.Module):
         ``encoder(mem_patch)`` in ``forward`` recomputes exactly these (reference :273 after :209/:227 with
         running BatchNorm statistics), so an eval loop can hand them back through ``forward(..., mem_emb=)``
         and skip the second encoder pass (SURVEY.md section 8 f, N-a).  Gathered on first use."""
-        if self._mem_emb is None and self._emb_parts and self.last_mem_idx is not None:
-            emb = self._emb_parts[0] if len(self._emb_parts) == 1 else torch.cat(self._emb_parts, dim=1)
-            if self._ragged_rows is not None and self._ragged_rows[1] is self.last_mem_idx:      # (ips_ragged: one packed table)
-                self._mem_emb = self._take(emb, self._ragged_rows[0]).view(*self.last_mem_idx.shape, -1)
-            else:
-                self._mem_emb = self._take(emb, self.last_mem_idx)
-            self._ragged_rows = None
-            self._emb_parts = None
-        if self._mem_emb is None and self._padded() and self._pad_state[2] is not None:
-            self._mem_emb = self._pad_state[2]()
-            self._pad_state = self._pad_state[:2] + (None,)
+        if self._mem_emb is None and self._emb_make is not None:
+            make, self._emb_make = self._emb_make, None
+            self._mem_emb = make()
+        elif self._mem_emb is None and self._emb_parts and self.last_mem_idx is not None:
+            parts, self._emb_parts = self._emb_parts, None
+            self._mem_emb = self._take(parts[0] if len(parts) == 1 else torch.cat(parts, dim=1), self.last_mem_idx)
         return self._mem_emb
-
-    def _padded(self):
-        """Was the last selection a ``ips_ragged(pad=True)`` call?  (Every selection leaves a ``last_mem_idx`` of its own.)"""
-        return self._pad_state is not None and self.last_mem_idx is not None and self._pad_state[0] is self.last_mem_idx
 
     @property
     def last_mem_count(self):
         """After ``ips_ragged(slides, pad=True)``: the tuple of the B host ints min(N_b, M) - the slots of every slide that
         hold rows of it, the rest being zero padding.  None after every other selection."""
-        return self._pad_state[1] if self._padded() else None
+        return self._mem_count
 
     # ---------------------------------------------------------------- aggregation
     def forward(self, mem_patch, mem_pos=None, mem_emb=None):

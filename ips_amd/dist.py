@@ -416,6 +416,7 @@ def ips_sharded(net, local_patches, N, group=None, timings=None, plan=None):
             raise RuntimeError("ips_sharded: the ranks disagree on the partition (different GPUs per rank?) - pass the same plan= everywhere")
         net.__dict__["_shard_plan_checked"] = (plan.signature(), world)
     dev = local_patches.device
+    net._reset_last()                  # (no last_mem_emb, no last_shuffle: both are None behind a sharded call)
     with net._scoring():
         ca = net.transf.crs_attn
         on_gpu = hip.on_device(dev)
@@ -632,11 +633,11 @@ def ips_tournament(net, local_patches, N, group=None):
     B, n_local = local_patches.shape[:2]
     assert n_local == hi - lo, "rank %d expects %d patches, got %d" % (rank, hi - lo, n_local)
     dev = local_patches.device
+    net._reset_last()
     with net._scoring():
         pos = net.pos_enc[:, lo:hi].expand(B, -1, -1) if net.use_pos else None
         k = min(M, n_local)                                      # a slab no larger than the memory keeps everything
         if n_local > M:
-            net._emb_parts = net._mem_emb = None
             loc = net._select_hip(local_patches, pos) if hip.on_device(dev) else net._select_aten(local_patches, pos)
             net.last_mem_idx = loc
             emb = net.last_mem_emb                               # (B, M, D) embeddings of the slab's winners
@@ -662,8 +663,8 @@ def ips_tournament(net, local_patches, N, group=None):
         mem_patch = mem_patch * owned.view(B, M, *(1,) * (mem_patch.dim() - 2)).to(mem_patch.dtype)
         mem_patch = _all_reduce(mem_patch, group)
         mem_pos = net._take(net.pos_enc, mem_idx) if net.use_pos else None
+    net._reset_last()                  # (the slab winners' embeddings are not the call's: nothing is kept)
     net.last_mem_idx = mem_idx
-    net._emb_parts = net._mem_emb = None
     return mem_patch, mem_pos, mem_idx
 
 

@@ -9,11 +9,12 @@ them at once.  The contract is the solo calls': slide by slide and bit for bit w
 
 returns and leaves behind, with torch's RNG streams consumed as that loop consumes them.  On a ROCm device that is one
 encoder pass over all rows, one packed logits table, ONE selection-loop launch (``ipsx_scan_ragged``: the loop kernels on
-per-slide lengths) and the gathers over global rows; on a CPU device it is that loop.
+per-slide lengths) and ONE finish launch (``ipsx_ragged_finish``); on a CPU device it is that loop.
 
 ``pad=True`` takes slides with no more rows than the memory as well: the reference's ``ips()`` returns all N_b rows of such a
 slide, unshuffled, and ``fill_batch`` (training/iterative.py) writes them into zero-initialised (B, M, ...) buffers - that
-batch is what the padded call returns, its end ONE launch (``ipsx_ragged_finish``) that also writes the zero padding.
+batch is what the padded call returns, by the same route: a call without ``pad`` is the padded call with no short slide,
+and the finish launch also writes the zero padding.
 """
 
 import os
@@ -166,24 +167,6 @@ def _check(net, slides, pad=False):
                              "rows, as ips() does".format(b, n, net.pos_enc.shape[1]))
 
 
-def _solo_loop(net, slides):
-    """The loop the contract names - the CPU plumbing path (``_select_aten`` per slide), and a ROCm device whose encoder is
-    in training mode inside an eval-mode net (batch statistics: no per-row function)."""
-    patch, pos, idx, emb, shuf = [], [], [], [], []
-    for b in range(len(slides)):
-        p, q = net._call(slides[b].unsqueeze(0))
-        patch.append(p)
-        pos.append(q)
-        idx.append(net.last_mem_idx)
-        emb.append(net.last_mem_emb)
-        shuf.append(net.last_shuffle)
-    net.last_mem_idx = torch.cat(idx, 0)
-    net._emb_parts, net._ragged_rows = None, None
-    net._mem_emb = torch.cat(emb, 0) if all(e is not None for e in emb) else None
-    net.last_shuffle = shuf if net.shuffle and any(s is not None for s in shuf) else None
-    return torch.cat(patch, 0), (torch.cat(pos, 0) if net.use_pos else None)
-
-
 def _draw(net, slides, skip=()):
     """The permutations of a shuffled call, slide by slide in slide order, by the calls ``IPSNet._shuffle`` makes for a
     (1, N_b, ...) input on the device the slides were handed over on -> (perms | None, copies | None): ``perms`` the B
@@ -273,45 +256,26 @@ def _packed(net, slides, skip=(), encode=True):
 
 @torch.no_grad()
 def ips_ragged(net, slides, pad=False):
-    """``IPSNet.ips_ragged``: see there."""
+    """``IPSNet.ips_ragged``: see there.  ``pad`` decides what ``_check`` refuses, whether the loop launch lets short slides
+    through, and whether the call leaves a ``last_mem_count`` - nothing else."""
     pad = bool(pad)
     if not isinstance(slides, Ragged):
         slides = Ragged.from_list(slides, pad)
     _check(net, slides, pad)
-    device = net.device
-    net._pad_state = None
-    if pad:
-        return _ips_ragged_padded(net, slides)
-    if not hip.on_device(device) or (net.encoder.training and not net.training):
-        return _solo_loop(net, slides)
-
-    B, M, D = len(slides), net.M, net.D
-    lengths = slides.lengths
-    net._emb_parts = net._mem_emb = net.last_shuffle = net.last_mem_idx = net._ragged_rows = None
-    with net._scoring():
-        ca = net.transf.crs_attn
-        vq, R = ca.folded_query(), ca.H * ca.n_token
-        with net.plan.hold():
-            dev, rows, flat, emb, pos = _packed(net, slides)
-            offsets = dev.offsets
-            # one packed (total, R) logits table, ONE loop launch on per-slide lengths
-            logits = hip.logits(emb.unsqueeze(0), pos, vq, R)[0]
-            mem_idx = hip.scan_ragged(logits, offsets, lengths, M, net.I, ca.H, ca.n_token)
-        # the gathers over global rows
-        grow = (mem_idx + offsets[:-1].unsqueeze(1)).reshape(1, B * M)
-        src_rows = grow if flat is None else flat.index_select(0, grow[0]).to(torch.int64).unsqueeze(0)
-        mem_patch = hip.gather_rows(rows.unsqueeze(0), src_rows).view(B, M, *rows.shape[1:])
-        mem_pos = hip.gather_rows(pos, grow).view(B, M, D) if net.use_pos else None
-    net._emb_parts, net._ragged_rows = [emb.unsqueeze(0)], (grow, mem_idx)
-    net.last_mem_idx = mem_idx
-    return mem_patch, mem_pos
+    net._reset_last()
+    if not hip.on_device(net.device) or (net.encoder.training and not net.training):
+        out = _host_route(net, slides)
+    else:
+        out = _device_route(net, slides, short_ok=pad)
+    net._mem_count = tuple(min(n, net.M) for n in slides.lengths) if pad else None
+    return out
 
 
-# ------------------------------------------------------------------ pad=True: short slides zero-padded to M rows
-def _pad_emb(net, long_emb, short_rows):
-    """``last_mem_emb`` of a padded call on the solo route, made on first use: the solo calls' embeddings for the long
-    slides; for a short one the eval-mode embeddings of its rows in [0, N_b) and, behind them, the embedding of ONE all-zero
-    row - what ``forward()`` in eval mode computes from the zero padding."""
+# ------------------------------------------------------------------ the host route
+def _host_emb(net, long_emb, short_rows):
+    """``last_mem_emb`` of a call on the host route, made on first use: the solo calls' embeddings for the long slides; for
+    a short one the eval-mode embeddings of its rows in [0, N_b) and, behind them, the embedding of ONE all-zero row - what
+    ``forward()`` in eval mode computes from the zero padding."""
     if any(e is None for e in long_emb.values()):
         return None
     B, M = len(long_emb) + len(short_rows), net.M
@@ -333,9 +297,10 @@ def _pad_emb(net, long_emb, short_rows):
     return out
 
 
-def _padded_solo(net, slides):
-    """The padded call as the loop of solo calls plus the padding on ATen ops: a CPU device, and a ROCm device whose encoder
-    is in training mode inside an eval-mode net."""
+def _host_route(net, slides):
+    """The loop the contract names, a solo call per long slide, plus the padding of the short ones on ATen ops - the CPU
+    plumbing path (``_select_aten`` per slide), and a ROCm device whose encoder is in training mode inside an eval-mode net
+    (batch statistics: no per-row function)."""
     B, M, D, device = len(slides), net.M, net.D, net.device
     shape = tuple(slides.rows.shape[1:])
     mem_patch = torch.zeros((B, M) + shape, dtype=slides.dtype, device=device)
@@ -358,49 +323,45 @@ def _padded_solo(net, slides):
                 mem_pos[b, :n] = net.pos_enc[0, :n]
             mem_idx[b, :n] = torch.arange(n, dtype=torch.int64, device=device)
             shuf.append(None)
-    net._emb_parts = net._mem_emb = net._ragged_rows = None
+    net._reset_last()                          # (what the last solo call left is that call's, not this one's)
     net.last_shuffle = shuf if net.shuffle and any(s is not None for s in shuf) else None
     net.last_mem_idx = mem_idx
-    net._pad_state = (mem_idx, tuple(min(n, M) for n in slides.lengths), lambda: _pad_emb(net, long_emb, short_rows))
+    net._emb_make = lambda: _host_emb(net, long_emb, short_rows)
     return mem_patch, mem_pos
 
 
+# ------------------------------------------------------------------ the device route
 def _finish_aten(rows, offsets, lengths, mem_idx, M, flat, pos):
-    """``hip.ragged_finish`` for rows that are no whole 16-byte units: the ``gather_rows`` launches plus the padding on ATen
-    ops -> the same four tensors."""
+    """``hip.ragged_finish`` for rows that are no whole 16-byte units: the ``gather_rows`` launches plus, where a slide is
+    short, the padding on ATen ops -> the same four tensors."""
     B, device = len(lengths), rows.device
     n = torch.tensor(lengths, dtype=torch.int64).to(device).unsqueeze(1)
     slot = torch.arange(M, dtype=torch.int64, device=device).unsqueeze(0)
-    short = n <= M
-    valid = ~short | (slot < n)
-    local = torch.minimum(slot, n - 1).expand(B, M)
+    local = torch.minimum(slot, n - 1).expand(B, M)             # a short slide: its rows in the order given
     if mem_idx is not None:                    # (the rows of short slides come back unwritten from the loop)
-        local = torch.where(short, local, torch.minimum(mem_idx.clamp(min=0), n - 1))
+        local = torch.where(n <= M, local, torch.minimum(mem_idx.clamp(min=0), n - 1))
     grow = local + offsets[:-1].unsqueeze(1)
     g = grow.reshape(1, B * M)
     src = g if flat is None else flat.index_select(0, g[0]).to(torch.int64).unsqueeze(0)
     mem_patch = hip.gather_rows(rows.unsqueeze(0), src).view(B, M, *rows.shape[1:])
+    mem_pos = hip.gather_rows(pos.unsqueeze(0), g).view(B, M, -1) if pos is not None else None
+    if min(lengths) >= M:                      # every slot holds a row
+        return mem_patch, mem_pos, local, grow
+    valid = slot < n
     mem_patch.masked_fill_(~valid.view(B, M, *(1,) * (rows.dim() - 1)), 0)
-    mem_pos = None
-    if pos is not None:
-        mem_pos = hip.gather_rows(pos.unsqueeze(0), g).view(B, M, -1)
+    if mem_pos is not None:
         mem_pos.masked_fill_(~valid.unsqueeze(-1), 0)
     return mem_patch, mem_pos, torch.where(valid, local, -1), torch.where(valid, grow, -1)
 
 
-def _ips_ragged_padded(net, slides):
-    """``ips_ragged(pad=True)``: one encoder pass over all rows, one packed logits table, ONE loop launch (the workgroups of
-    short slides return before their first read) and ONE finish launch (``ipsx_ragged_finish``: selected rows, short
-    slides' rows in the order given, the zero padding, indices and global rows).  A batch of short slides only launches
-    no encoder, no logits and no loop."""
-    device = net.device
-    if not hip.on_device(device) or (net.encoder.training and not net.training):
-        return _padded_solo(net, slides)
-    B, M = len(slides), net.M
+def _device_route(net, slides, short_ok):
+    """One encoder pass over all rows, one packed logits table, ONE loop launch (the workgroups of short slides return before
+    their first read) and ONE finish launch (``ipsx_ragged_finish``: selected rows, short slides' rows in the order given,
+    the zero padding, indices and global rows).  A batch of short slides only launches no encoder, no logits and no loop."""
+    B, M, device = len(slides), net.M, net.device
     lengths = slides.lengths
     short = frozenset(b for b, n in enumerate(lengths) if n <= M)
     any_long = len(short) < B
-    net._emb_parts = net._mem_emb = net.last_shuffle = net.last_mem_idx = net._ragged_rows = None
     with net._scoring():
         ca = net.transf.crs_attn
         with net.plan.hold():
@@ -409,7 +370,7 @@ def _ips_ragged_padded(net, slides):
             mem_idx = None
             if any_long:
                 logits = hip.logits(emb.unsqueeze(0), pos, ca.folded_query(), ca.H * ca.n_token)[0]
-                mem_idx = hip.scan_ragged(logits, offsets, lengths, M, net.I, ca.H, ca.n_token, short_ok=True)
+                mem_idx = hip.scan_ragged(logits, offsets, lengths, M, net.I, ca.H, ca.n_token, short_ok=short_ok)
         pos2 = pos[0] if pos is not None else None
         if hip.ragged_finish_supported(rows, pos2):
             mem_patch, mem_pos, mem_idx, grow = hip.ragged_finish(rows, offsets, mem_idx, M, flat, pos2)
@@ -420,17 +381,18 @@ def _ips_ragged_padded(net, slides):
 
     unencoded = rows if emb is None else None       # (a batch of short slides only: at most B * M rows, kept until they are read)
     zero_row = (1,) + tuple(rows.shape[1:]), rows.dtype
+    padded = any(lengths[b] < M for b in short)
 
     def emb_of_slots():
         """(B, M, D): the packed pass's rows (made now for a batch of short slides only); the padding holds the embedding
         of ONE all-zero row."""
         with torch.no_grad(), net._scoring(), net.plan.hold():
             table = emb if emb is not None else net._embed(unencoded)
-            out = hip.gather_rows(table.unsqueeze(0), grow.clamp(min=0).view(1, B * M)).view(B, M, -1)
-            if any(lengths[b] < M for b in short):
+            out = hip.gather_rows(table.unsqueeze(0), (grow.clamp(min=0) if padded else grow).view(1, B * M)).view(B, M, -1)
+            if padded:
                 zero = net._embed(torch.zeros(zero_row[0], dtype=zero_row[1], device=device))
                 out = torch.where((grow < 0).unsqueeze(-1), zero.view(1, 1, -1), out)
         return out
     net.last_mem_idx = mem_idx
-    net._pad_state = (mem_idx, tuple(min(n, M) for n in lengths), emb_of_slots)
+    net._emb_make = emb_of_slots
     return mem_patch, mem_pos

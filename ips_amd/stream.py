@@ -445,15 +445,13 @@ class IPSStream:
         if self._geom is not None and self.fed == 0:
             raise RuntimeError("the {} pixel rows fed complete no patch row of height {}".format(self.rows, self._patch_size[0]))
         M, B = net.M, self._B
-        net._emb_parts = net._mem_emb = None
-        net.last_shuffle = None
+        net._reset_last()
         u8 = self._dtype == torch.uint8
         if self.fed <= M:
             mem_patch = (self._sets[self._cur][0][:, :self.fed].clone() if self._on_device else
                          torch.cat((self._mem_patch, self._pending), dim=1) if self._mem_patch is not None else self._pending)
             mem_pos = net.pos_enc[:, :self.fed].expand(B, -1, -1) if net.use_pos else None
             self._close(None)
-            net.last_mem_idx = None
             return (net._dequant(mem_patch) if u8 else mem_patch), mem_pos
         with net._scoring():
             if self._on_device:

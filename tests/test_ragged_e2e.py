@@ -1,6 +1,6 @@
 """``IPSNet.ips_ragged`` on the device against the loop of solo ``net.ips(slide[None])`` calls it replaces - every output of
 the contract bit for bit (``mem_patch``, ``mem_pos``, ``last_mem_idx``, ``last_mem_emb``, ``last_shuffle``, both RNG
-streams): one encoder pass over all rows, one packed logits table, ONE ``ipsx_scan_ragged``, gathers over global rows."""
+streams): one encoder pass over all rows, one packed logits table, ONE ``ipsx_scan_ragged``, ONE ``ipsx_ragged_finish``."""
 
 import pytest
 import torch
@@ -90,3 +90,59 @@ def test_one_scan_launch_per_call(feature_nets, monkeypatch):
         monkeypatch.setattr(hip, name, lambda *a, _n=name, **k: seen.append(_n))
     net.ips_ragged(slides)
     assert seen == ["ragged"]
+
+
+# ------------------------------------------------------------------ the call without ``pad`` ends as the padded one does
+M8, I4 = 8, 4
+
+
+@pytest.fixture(scope="module")
+def small_cases():
+    """A feature net with M = 8, I = 4, four slides, and the solo loop's record for them: made once per configuration."""
+    made = {}
+
+    def get(shuffle, use_pos):
+        if (shuffle, use_pos) not in made:
+            conf = rc.feature_conf(M=M8, shuffle=shuffle, shuffle_style='batch', use_pos=use_pos).clone(I=I4)
+            net = rc.make_net(conf, DEV)
+            slides = _on_device(rc.make_slides(conf, (M8 + 1, 3 * M8, 3 * M8 + 5, 7 * M8)))
+            made[(shuffle, use_pos)] = (net, slides, rc.solo_loop(net, slides))
+        return made[(shuffle, use_pos)]
+    return get
+
+
+def test_launches_of_a_call_without_pad(small_cases, monkeypatch):
+    """On aligned rows: one encoder pass, one logits table, ONE ``ipsx_scan_ragged``, ONE ``ipsx_ragged_finish`` - and no
+    ``gather_rows`` launch until ``last_mem_emb`` is read."""
+    net, slides, want = small_cases(False, True)
+    seen = []
+
+    def counted(name, real):
+        def call(*a, **k):
+            seen.append(name)
+            return real(*a, **k)
+        return call
+    for name in ("scan_ragged", "ragged_finish", "gather_rows", "logits", "scan", "scan_range"):
+        monkeypatch.setattr(hip, name, counted(name, getattr(hip, name)))
+    plan = type(net.plan)                                      # (every eval-mode encoder pass on the device goes through the plan)
+    for name in ("encode", "encode_source"):
+        monkeypatch.setattr(plan, name, counted("encode", getattr(plan, name)))
+    net.ips_ragged(slides)
+    assert sorted(seen) == ["encode", "logits", "ragged_finish", "scan_ragged"]
+    assert net.last_mem_count is None
+    del seen[:]
+    assert rc._same(net.last_mem_emb.cpu(), want["mem_emb"])
+    assert seen == ["gather_rows"]
+
+
+@pytest.mark.parametrize("shuffle", [False, True])
+@pytest.mark.parametrize("use_pos", [False, True])
+def test_unaligned_rows_without_pad_equal_the_solo_loop(small_cases, monkeypatch, shuffle, use_pos):
+    """Rows that are no whole 16-byte units end in the ``gather_rows`` launches (``_finish_aten``)."""
+    net, slides, want = small_cases(shuffle, use_pos)
+    assert (want["shuffle"] is not None) == shuffle and (want["mem_pos"] is not None) == use_pos
+    monkeypatch.setattr(hip, "ragged_finish_supported", lambda rows, pos: False)
+    monkeypatch.setattr(hip, "ragged_finish", None)
+    got = rc.ragged_call(net, slides)
+    rc.assert_same_record(got, want)
+    assert net.last_mem_count is None and tuple(got["mem_idx"].shape) == (4, M8)

@@ -99,7 +99,10 @@ def main():
             for k, fn in legs.items():
                 torch.manual_seed(rep)
                 # (a net keeps the embeddings of its last call for last_mem_emb: dropped, so that a leg's peak is its own)
-                net._emb_parts = net._mem_emb = net._pad_state = None
+                if hasattr(net, "_reset_last"):
+                    net._reset_last()
+                else:             # (the parent commit: the baseline)
+                    net._emb_parts = net._mem_emb = net._pad_state = None
                 torch.cuda.synchronize()
                 torch.cuda.reset_peak_memory_stats(dev)
                 base = torch.cuda.memory_allocated(dev)
