@@ -1,7 +1,10 @@
 """``ipsx_scan_ragged`` on logits alone (no encoder): the RAGGED instantiations of scan_fast_kernel, scan_cam_kernel and
 scan_large_kernel on packed tables of B = 5 slides against ``ipsx_scan`` called on a contiguous copy of every slide alone -
 ``mem_idx`` and ``tie_flag`` equal, ``mem_score`` bit for bit (the criterion tests/test_scan_mnist.py uses between two loop
-kernels), in both tie orders, on tables that do tie: quantised logits, and a stretch of duplicated rows."""
+kernels), in both tie orders, on tables that do tie: quantised logits, and a stretch of duplicated rows.
+
+Every shape here has I = M.  Shapes with I != M, every instantiation class of the three kernels, and the oracle's loop as the
+criterion: tests/test_ragged_scan_lattice.py."""
 
 import numpy as np
 import pytest
