@@ -115,7 +115,10 @@ extern "C" {
  *         ipsx_scan_ragged - the selection loop over slides of different lengths packed into one logits table, one launch
  *         (an addition, the minor number stays for the same reason);
  *         ipsx_ragged_finish - the end of a padded ragged call in one launch: selected rows of long slides, the rows of
- *         short slides in the order given, zero padding, indices and global rows (an addition, the minor number stays) */
+ *         short slides in the order given, zero padding, indices and global rows (an addition, the minor number stays);
+ *         ipsx_scan_ragged_spans, ipsx_stream_commit_ragged - slides of different lengths fed in pieces
+ *         (IPSNet.ips_ragged_stream): ipsx_scan_ragged on slides that lie anywhere in one logits table, and ipsx_stream_commit
+ *         with per-slide numbers read from a device table (additions, the minor number stays) */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -678,6 +681,17 @@ int ipsx_scan_range_strided(const float* logits, int64_t logits_bstride_rows, in
 int ipsx_scan_ragged(const float* logits, const int64_t* row_offsets, int b, int64_t n_max, int64_t total, int m, int i,
                      int h, int n_token, int64_t* mem_idx, float* mem_score, int32_t* tie_flag, void* workspace,
                      size_t workspace_bytes, void* stream);
+/* 3.06: ipsx_scan_ragged on slides that lie ANYWHERE in one (rows_total, h * n_token) table.  spans (device, (b, 2) int64):
+ * the first row and the row count of slide k's candidates; the spans need not touch each other nor ascend.  Slide k is scanned
+ * as ipsx_scan_ragged scans a slide of that many rows - its own ceil((count - m) / i) iterations and ragged last chunk - by one
+ * workgroup (a plain launch; never a team, never the kernel specialised for 8 heads x 4 tokens): mem_idx holds row numbers
+ * inside the span.  A slide whose count is not above m, or whose span leaves [0, rows_total), is left untouched in all three
+ * outputs - tie_flag is only ever SET here, the caller clears it.  No row outside a span is read.  n_max: the caller's
+ * host-side bound on the counts (dispatch, the < 2^31 checks).  workspace: b times ipsx_scan_workspace_bytes(1, m, i, h,
+ * n_token). */
+int ipsx_scan_ragged_spans(const float* logits, const int64_t* spans, int b, int64_t n_max, int64_t rows_total, int m, int i,
+                           int h, int n_token, int64_t* mem_idx, float* mem_score, int32_t* tie_flag, void* workspace,
+                           size_t workspace_bytes, void* stream);
 
 /* The whole loop as ONE launch that may start before any logits exist (overlap with the encoder without re-launching
  * per part): the kernel waits until *ready (device int32, written with ipsx_publish_rows on another stream after the
@@ -819,6 +833,22 @@ int ipsx_stream_commit(const ipsx_stream_table* tables, int n_tables, const int6
 int ipsx_stream_commit_view(const ipsx_stream_table* tables, int n_tables, const void* images, const ipsx_patch_view* v,
                             int elem_size, const int64_t* sel, int b, int m, int64_t n_cand, int64_t tail_first, int* unit,
                             void* stream);
+/* 3.06: ipsx_stream_commit for slides that each have their own numbers (IPSNet.ips_ragged_stream), ONE launch, grid
+ * (rows_max, b, n_tables).  tables: as above with these differences - `piece` is ONE packed (piece_rows_total, row_bytes)
+ * tensor for all slides (piece_bstride_bytes 0), a table without a piece holds ALL of a slide's candidates in `held`, and
+ * held_rows is the number of rows per slide that may be READ from `held` (its capacity).  slides (device, (b, 6) int64), per
+ * slide: held rows, candidates, tail_first, the slide's first row in the packed piece, the mode, one reserved word.
+ *   mode 0 (idle):   nothing is read or written.
+ *   mode 1 (append): dst[k][held + r] = piece[first + r]; the rows in front stay as they are (tables without a piece: nothing).
+ *   mode 2 (select): dst[k][j] = cand[k][clamp(sel[k][j])] for j < m, dst[k][m + r] = cand[k][tail_first + r] behind them.
+ *   mode 3 (move):   dst[k][j] = cand[k][j] for every candidate.
+ * A workgroup beyond its slide's rows returns at once.  Whatever the device table says, nothing is read outside a table's
+ * held_rows or the packed piece and nothing is written outside dst_rows: a slide whose numbers contradict the capacities of
+ * ANY table of the launch (or that selects without sel, or selects / moves in a table whose dst is its held buffer) is left
+ * untouched in all of them.  Refused before the launch: what ipsx_stream_commit refuses that the host can know - a
+ * destination that overlaps the piece, or the held rows other than in place from the same address. */
+int ipsx_stream_commit_ragged(const ipsx_stream_table* tables, int n_tables, const int64_t* sel, const int64_t* slides, int b,
+                              int m, int64_t rows_max, int64_t piece_rows_total, void* stream);
 
 /* ONE IPSNet.ips call whose selection loop is resident (architecture/ips_net.py:169-262 for one image on the fused trunk,
  * or for feature slides through the projector), enqueued by ONE library call: fill of the control words, the loop on

@@ -466,6 +466,16 @@ class IPSNet(nn.Module):
         from ..stream import IPSStream
         return IPSStream(self, patch_size, patch_stride)
 
+    def ips_ragged_stream(self, pad=False):
+        """``ips_ragged()`` over slides whose rows arrive in pieces -> ``ips_amd.ragged_stream.RaggedIPSStream``:
+        ``feed(pieces)`` takes a ``Ragged`` or a list of B tensors (n_b, F) | (n_b, C, h, w) - the next rows of each slide,
+        n_b >= 0, on the device or the host -, ``feed_all(slides, slab_rows)`` walks a whole batch in slabs, and ``finish()``
+        returns and leaves behind what ``ips_ragged([torch.cat(pieces of slide b) for b], pad=pad)`` does with ``shuffle``
+        off, bit for bit.  The state is M + I - 1 rows per slide whatever the lengths turn out to be; a host batch goes over
+        slab by slab.  The stream never shuffles."""
+        from ..ragged_stream import RaggedIPSStream
+        return RaggedIPSStream(self, pad)
+
     def _chunks(self, N):
         """[0, M) then ceil((N-M)/I) chunks of I (last one ragged) - reference :206,217-221."""
         yield 0, self.M

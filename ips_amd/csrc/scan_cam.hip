@@ -99,7 +99,7 @@ __device__ __forceinline__ void search_run_u32_x2(const uint32_t* runA, uint32_t
     cB = (int)(loB + key_gt(lastB, mB));
 }
 
-template <bool STAMP, bool PERSIST, bool STRIDED = false, bool RAGGED = false>      // (STRIDED, RAGGED: see scan_fast_kernel)
+template <bool STAMP, bool PERSIST, bool STRIDED = false, bool RAGGED = false, bool SPANS = false>      // (STRIDED, RAGGED, SPANS: see scan_fast_kernel)
 __global__ __launch_bounds__(cam::NT) void scan_cam_kernel(ScanArgs a, unsigned long long* stamps) {
     using namespace cam;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(cam::NT) void scan_cam_kernel(ScanArgs a, unsigned 
     if constexpr (RAGGED) {                                      // (one workgroup per slide: the loop over b makes one trip)
         a.it0 = 0;
         static_assert(!(RAGGED && (STAMP || PERSIST || STRIDED)), "scan_cam_kernel: RAGGED is a plain launch");
-        if (!ragged_slide(reinterpret_cast<const long long*>(stamps), a.lg_bs, b, M, I, &first_row, &a.n, &a.it1)) return;
+        if (!slide_of<SPANS>(reinterpret_cast<const long long*>(stamps), a.lg_bs, b, M, I, &first_row, &a.n, &a.it1)) return;
     }
     const float* lg = RAGGED ? a.lg + (size_t)first_row * R : a.lg + (size_t)b * (STRIDED ? a.lg_bs : a.n) * R;
 #pragma unroll
@@ -540,6 +540,13 @@ int launch_scan_cam(const ScanCall& c) {
         scan_cam_kernel<S, P><<<dim3((unsigned)grid), dim3(cam::NT), cam::LDS_BYTES, as_stream(stream)>>>(a, st);   \
         return launched("scan");                                                                                    \
     } while (0)
+        if (c.row_offsets != nullptr && c.spans) {                // ipsx_scan_ragged_spans: as below, the slides looked up in pairs
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_cam_kernel<false, false, false, true, true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)cam::LDS_BYTES);
+            scan_cam_kernel<false, false, false, true, true><<<dim3((unsigned)b), dim3(cam::NT), cam::LDS_BYTES, as_stream(stream)>>>(
+                a, reinterpret_cast<unsigned long long*>(const_cast<int64_t*>(c.row_offsets)));
+            return launched("scan");
+        }
         if (c.row_offsets != nullptr) {                           // ipsx_scan_ragged: plain launches, one workgroup per slide
             // (the row offsets in the place of the stamps, the table's rows in a.lg_bs: ragged_slide, scan_common.h)
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_cam_kernel<false, false, false, true>),

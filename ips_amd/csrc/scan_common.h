@@ -722,6 +722,34 @@ __device__ __forceinline__ bool ragged_slide(const long long* row_off, long long
     return true;
 }
 
+// SPANS (ipsx_scan_ragged_spans): the RAGGED mode with another slide lookup - workgroup b's slide is the pair
+// spans[2 * b] (first row), spans[2 * b + 1] (rows) inside the table of rows_total rows; the spans need not touch each other
+// (the blocks of a stream's logits table, IPSNet.ips_ragged_stream).  Same hand-over as ragged_slide (the pairs as `stamps`,
+// rows_total as lg_bs), the two numbers workgroup-uniform and scalar; a slide whose count is not above m, or whose span
+// leaves the table, is not touched (-> false).
+__device__ __forceinline__ bool spans_slide(const long long* spans, long long rows_total, int b, int m, int i,
+                                            long long* first, long long* n, long long* n_iter) {
+    const long long r0 = spans[2 * (size_t)b], c0 = spans[2 * (size_t)b + 1];
+    const long long lo = ((long long)__builtin_amdgcn_readfirstlane((int)(r0 >> 32)) << 32) |
+                         (unsigned int)__builtin_amdgcn_readfirstlane((int)r0);
+    const long long cnt = ((long long)__builtin_amdgcn_readfirstlane((int)(c0 >> 32)) << 32) |
+                          (unsigned int)__builtin_amdgcn_readfirstlane((int)c0);
+    *first = lo;
+    *n = cnt;
+    // (cnt < 2^31 and lo <= rows_total first: lo + cnt cannot overflow behind them)
+    if (!(lo >= 0 && lo <= rows_total && cnt > m && cnt < (1ll << 31) && lo + cnt <= rows_total)) return false;
+    *n_iter = (long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)((unsigned int)(cnt - m + i - 1) / (unsigned int)i));
+    return true;
+}
+
+// the slide lookup of a RAGGED instantiation: row offsets, or (SPANS) pairs
+template <bool SPANS>
+__device__ __forceinline__ bool slide_of(const long long* table, long long rows_total, int b, int m, int i,
+                                         long long* first, long long* n, long long* n_iter) {
+    if constexpr (SPANS) return spans_slide(table, rows_total, b, m, i, first, n, n_iter);
+    else return ragged_slide(table, rows_total, b, m, i, first, n, n_iter);
+}
+
 // ipsx_scan_range_if: the recovery launch behind a persistent loop - every workgroup looks at the word the loop sets when
 // it gave up waiting and leaves at once when it is clear (workgroup-uniform).
 __device__ __forceinline__ bool scan_skipped(const int* cond, int mask) {
@@ -1070,6 +1098,7 @@ struct ScanCall {
     int64_t logits_bstride_rows;       // rows between the images' logits: n for every entry but ipsx_scan_range_strided
     const int64_t* row_offsets;        // ipsx_scan_ragged alone: (b + 1) row offsets on the device into a packed table of
                                        //   logits_bstride_rows rows in all; n is then the longest slide.  nullptr for every other entry
+    bool spans;                        // ipsx_scan_ragged_spans: row_offsets holds b (first row, rows) pairs instead (spans_slide)
 };
 
 // Is this shape the LDS-resident loop's (scan_fast_kernel)?  Otherwise scan_large_kernel takes it (and needs a workspace).

@@ -14,7 +14,8 @@ namespace ipsx {
 // RAGGED: the third mode of that kind (ipsx_scan_ragged) - workgroup b's rows, their number and its iteration count come
 // from row_off[b], row_off[b + 1] (ragged_slide, scan_common.h: the offsets arrive as `stamps`); behind that the loop is the
 // code below, unchanged
-template <int R, int T, int EPT, int LCH, bool STAMP, bool PERSIST, bool STRIDED = false, bool RAGGED = false>
+// SPANS (with RAGGED; ipsx_scan_ragged_spans): the slide is a (first row, rows) pair instead (spans_slide, scan_common.h)
+template <int R, int T, int EPT, int LCH, bool STAMP, bool PERSIST, bool STRIDED = false, bool RAGGED = false, bool SPANS = false>
 __global__ __launch_bounds__(SCAN_NT) void scan_fast_kernel(ScanArgs a, unsigned long long* stamps) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // prefetch registers per (prefetching) thread: 4, 5 for 32 rows x up to 512 candidates - the reference's shipped
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(SCAN_NT) void scan_fast_kernel(ScanArgs a, unsigned
     if constexpr (RAGGED) {
         a.it0 = 0;
         static_assert(!(RAGGED && (STAMP || PERSIST || STRIDED)), "scan_fast_kernel: RAGGED is a plain launch");
-        if (!ragged_slide(reinterpret_cast<const long long*>(stamps), a.lg_bs, b, a.m, a.i, &first_row, &a.n, &a.it1)) return;
+        if (!slide_of<SPANS>(reinterpret_cast<const long long*>(stamps), a.lg_bs, b, a.m, a.i, &first_row, &a.n, &a.it1)) return;
     }
     const float* lg = RAGGED ? a.lg + (size_t)first_row * R : a.lg + (size_t)b * (STRIDED ? a.lg_bs : a.n) * R;
     const int r = tid & (R - 1), lrow0 = tid >> log2R;
@@ -453,7 +454,11 @@ int launch_scan_fast(const ScanCall& c, const FastPlan& fp) {
     unsigned long long* const row_off = reinterpret_cast<unsigned long long*>(const_cast<int64_t*>(c.row_offsets));
 #define IPSX_LAUNCH_FAST(RR, TT, E, C, S)                                                                           \
     do {                                                                                                            \
-        if (ragged) {                                                                                               \
+        if (ragged && c.spans) {                                                                                    \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_fast_kernel<RR, TT, E, C, false, false, false, true, true>), \
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast);                       \
+            scan_fast_kernel<RR, TT, E, C, false, false, false, true, true><<<dim3((unsigned)b), dim3(SCAN_NT), fast, as_stream(stream)>>>(a, row_off); \
+        } else if (ragged) {                                                                                        \
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_fast_kernel<RR, TT, E, C, false, false, false, true>), \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast);                       \
             scan_fast_kernel<RR, TT, E, C, false, false, false, true><<<dim3((unsigned)b), dim3(SCAN_NT), fast, as_stream(stream)>>>(a, row_off); \

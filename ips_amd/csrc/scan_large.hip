@@ -331,7 +331,7 @@ constexpr int LARGE_U = 8;
         }                                                                          \
     } while (0)
 
-template <bool STAMP, bool STRIDED = false, bool RAGGED = false>      // (STRIDED, RAGGED: see scan_fast_kernel)
+template <bool STAMP, bool STRIDED = false, bool RAGGED = false, bool SPANS = false>      // (STRIDED, RAGGED, SPANS: see scan_fast_kernel)
 __global__ __launch_bounds__(LARGE_NT) void scan_large_kernel(LargeArgs a, unsigned long long* stamps) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int R = a.h * a.T, Lp = a.Lp, m = a.m;
@@ -345,7 +345,7 @@ __global__ __launch_bounds__(LARGE_NT) void scan_large_kernel(LargeArgs a, unsig
     if constexpr (RAGGED) {
         a.it0 = 0;
         static_assert(!(RAGGED && (STAMP || STRIDED)), "scan_large_kernel: RAGGED is a plain launch");
-        if (!ragged_slide(reinterpret_cast<const long long*>(stamps), a.lg_bs, b, m, a.i, &first_row, &a.n, &a.it1)) return;
+        if (!slide_of<SPANS>(reinterpret_cast<const long long*>(stamps), a.lg_bs, b, m, a.i, &first_row, &a.n, &a.it1)) return;
     }
     const float* lg = RAGGED ? a.lg + (size_t)first_row * R : a.lg + (size_t)b * (STRIDED ? a.lg_bs : a.n) * R;
     long long* mem = a.mem_idx + (size_t)b * m;
@@ -791,6 +791,12 @@ int launch_scan_large(const ScanCall& c) {
         // a team of workgroups per image (scan_large_team.h) - not the conditional recovery launch, which must not wait on anyone
         if (c.row_offsets != nullptr) {                                // ipsx_scan_ragged: one workgroup per slide, never a team
             IPSX_REQUIRE(!ready && !cond, "scan_ragged: plain launches only");
+            if (c.spans) {                                             // ipsx_scan_ragged_spans: the slides looked up in pairs (spans_slide)
+                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_large_kernel<false, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+                scan_large_kernel<false, false, true, true><<<dim3((unsigned)b), dim3(LARGE_NT), lds, as_stream(stream)>>>(
+                    la, reinterpret_cast<unsigned long long*>(const_cast<int64_t*>(c.row_offsets)));
+                return launched("scan");
+            }
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_large_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             // (the row offsets in the place of the stamps, the table's rows - fewer than 2^31 - in la.lg_bs: ragged_slide, scan_common.h)
             scan_large_kernel<false, false, true><<<dim3((unsigned)b), dim3(LARGE_NT), lds, as_stream(stream)>>>(

@@ -119,6 +119,27 @@ IPSX_API int ipsx_scan_ragged(const float* logits, const int64_t* row_offsets, i
     return launch_scan_fast(c, fp);
 }
 
+// ipsx_scan_ragged on slides that lie anywhere in ONE (rows_total, R) table: spans (b, 2) int64 on the device, slide k's first
+// row and row count (the blocks of a ragged stream's logits table, IPSNet.ips_ragged_stream: the counts change from feed to
+// feed, the blocks do not move).  The SPANS instantiation of the loop kernel the shape takes, one workgroup per slide; a
+// slide whose count is not above m, or whose span leaves the table, is left untouched in all three outputs - tie_flag
+// included, so nothing is cleared here.  n_max: the caller's bound on the counts (dispatch and the < 2^31 checks only).
+IPSX_API int ipsx_scan_ragged_spans(const float* logits, const int64_t* spans, int b, int64_t n_max, int64_t rows_total, int m,
+                                    int i, int h, int n_token, int64_t* mem_idx, float* mem_score, int32_t* tie_flag,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+    IPSX_REQUIRE(logits && spans && mem_idx, "scan_ragged_spans: null pointer");
+    IPSX_REQUIRE(b > 0 && m > 0 && i > 0 && h > 0 && n_token > 0, "scan_ragged_spans: bad sizes");
+    IPSX_REQUIRE(n_max > m, "scan_ragged_spans: needs more patches per slide (longest: %lld) than memory slots (%d)", (long long)n_max, m);
+    IPSX_REQUIRE(rows_total >= n_max && rows_total < ((int64_t)1 << 31),
+                 "scan_ragged_spans: a table of %lld rows (fewer than 2^31) for slides of at most %lld", (long long)rows_total, (long long)n_max);
+    const FastPlan fp = scan_fast_plan(m, i, h, n_token);
+    ScanCall c = {logits, b, n_max, m, i, h, n_token, 0, (n_max - m + i - 1) / i, mem_idx, mem_score, tie_flag, nullptr, nullptr,
+                  workspace, workspace_bytes, stream, nullptr, 0, 0, 0, rows_total, spans, true};
+    if (!fp.ok || g_scan_generic) return launch_scan_large(c);
+    if (g_scan_r8 && scan_cam_shape(m, i, h, n_token)) return launch_scan_cam(c);
+    return launch_scan_fast(c, fp);
+}
+
 IPSX_API size_t ipsx_scan_workspace_bytes(int b, int m, int i, int h, int n_token) {
     if (b <= 0 || m <= 0 || i <= 0 || h <= 0 || n_token <= 0) return 0;
     if (scan_fast_plan(m, i, h, n_token).ok && !g_scan_generic) return 0;

@@ -121,6 +121,81 @@ __global__ __launch_bounds__(256) void stream_commit_view_kernel(CommitViewArgs 
     else copy_units<unsigned char>(s, d, t.row_bytes);
 }
 
+// stream_commit_ragged_kernel (IPSNet.ips_ragged_stream): the update for slides that each have their own numbers.
+// Per slide six int64 words on the device - held rows, candidates, tail_first, the slide's first row in the packed piece,
+// the mode, one reserved - where stream_commit_kernel reads one n_cand and one tail_first for all images; the piece of a
+// table is ONE packed (piece_rows, row_bytes) tensor for all slides.  A table without a piece holds all of a slide's
+// candidates itself (the logits table behind the loop).
+constexpr long long COMMIT_APPEND = 1, COMMIT_SELECT = 2, COMMIT_MOVE = 3;      // (0, and anything else: idle)
+
+struct RaggedCommitTable {
+    const unsigned char* held; long long held_rows, held_bs;     // held_rows: rows per slide that may be read; held_bs: bytes between the slides
+    const unsigned char* piece;                                   // packed for all slides, or nullptr
+    unsigned char* dst; long long dst_rows, dst_bs;
+    long long row_bytes;
+    int unit;                                                     // 16, 4 or 1 bytes per lane
+    int in_place;                                                 // dst is the buffer `held` points into: append only
+};
+
+struct RaggedCommitArgs {
+    RaggedCommitTable t[COMMIT_MAX_TABLES];
+    const long long* sel;      // (b, m) candidate rows of the slides that select, or nullptr
+    const long long* slides;   // (b, 6)
+    int m, n_tables;
+    long long piece_rows;      // rows of the packed pieces
+};
+
+__device__ __forceinline__ long long uniform_ll(long long v) {
+    return ((long long)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned int)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+__global__ __launch_bounds__(256) void stream_commit_ragged_kernel(RaggedCommitArgs a) {
+    const long long j = blockIdx.x;
+    const int b = blockIdx.y;
+    const long long* w = a.slides + (size_t)b * 6;
+    const long long held = uniform_ll(w[0]), cand = uniform_ll(w[1]), tail_first = uniform_ll(w[2]), first = uniform_ll(w[3]),
+                    mode = uniform_ll(w[4]);
+    if (mode != COMMIT_APPEND && mode != COMMIT_SELECT && mode != COMMIT_MOVE) return;      // idle (and anything unknown)
+    // the slide's numbers against every table of the launch: one contradiction and the slide is not touched in any of them
+    const long long lim = 1ll << 40;                              // (sums below cannot overflow)
+    if (!(held >= 0 && cand >= held && cand > 0 && cand < lim && first >= 0 && first < lim)) return;
+    if (mode == COMMIT_SELECT && !(a.sel && tail_first >= 0 && tail_first <= cand)) return;
+    const long long rows = mode == COMMIT_APPEND ? cand - held : (mode == COMMIT_SELECT ? a.m + (cand - tail_first) : cand);
+    const long long last = mode == COMMIT_APPEND ? cand : rows;  // dst rows [.., last) are written
+    for (int k = 0; k < a.n_tables; ++k) {
+        const RaggedCommitTable& c = a.t[k];
+        const long long in_held = c.piece ? held : cand;          // candidates of this table that lie in its held rows
+        if (in_held > c.held_rows || last > c.dst_rows) return;
+        if (c.piece && first + (cand - held) > a.piece_rows) return;
+        if (c.in_place && mode != COMMIT_APPEND) return;
+    }
+    if (j >= rows) return;
+    const RaggedCommitTable& t = a.t[blockIdx.z];
+    long long r, out;                                             // candidate row read, row of dst written (workgroup-uniform)
+    if (mode == COMMIT_APPEND) {
+        if (!t.piece) return;                                     // (a table that holds its candidates has nothing to append)
+        r = held + j;
+        out = r;
+    } else if (mode == COMMIT_SELECT) {
+        if (j < a.m) {
+            r = a.sel[(size_t)b * a.m + j];
+            r = r < 0 ? 0 : (r >= cand ? cand - 1 : r);           // never read out of bounds
+        } else {
+            r = tail_first + (j - a.m);
+        }
+        out = j;
+    } else {
+        r = out = j;
+    }
+    const long long in_held = t.piece ? held : cand;
+    const unsigned char* s = r < in_held ? t.held + (size_t)b * t.held_bs + (size_t)r * t.row_bytes
+                                         : t.piece + (size_t)(first + (r - in_held)) * t.row_bytes;
+    unsigned char* d = t.dst + (size_t)b * t.dst_bs + (size_t)out * t.row_bytes;
+    if (t.unit == 16) copy_units<uint4>(s, d, t.row_bytes / 16);
+    else if (t.unit == 4) copy_units<uint32_t>(s, d, t.row_bytes / 4);
+    else copy_units<unsigned char>(s, d, t.row_bytes);
+}
+
 }  // namespace ipsx
 
 using namespace ipsx;
@@ -243,5 +318,59 @@ IPSX_API int ipsx_stream_commit_view(const ipsx_stream_table* tables, int n_tabl
     if (rows <= 0) return IPSX_OK;
     IPSX_REQUIRE(rows < ((int64_t)1 << 31) && b < 65536, "%s: %lld rows x %d images in one launch", what, rows, b);
     stream_commit_view_kernel<<<dim3((unsigned)rows, (unsigned)b, (unsigned)n_tables), dim3(256), 0, as_stream(stream)>>>(a);
+    return launched(what);
+}
+
+// The state update of a ragged stream (IPSNet.ips_ragged_stream) as ONE launch: see stream_commit_ragged_kernel.  What the host
+// can know is refused here; what only the device table says is checked per slide in the kernel.
+IPSX_API int ipsx_stream_commit_ragged(const ipsx_stream_table* tables, int n_tables, const int64_t* sel, const int64_t* slides,
+                                       int b, int m, int64_t rows_max, int64_t piece_rows_total, void* stream) {
+    const char* what = "stream_commit_ragged";
+    IPSX_REQUIRE(tables, "%s: null tables", what);
+    IPSX_REQUIRE(n_tables > 0 && n_tables <= COMMIT_MAX_TABLES, "%s: %d tables (1 .. %d in one launch)", what, n_tables, COMMIT_MAX_TABLES);
+    IPSX_REQUIRE(b > 0 && m > 0 && rows_max >= 0 && piece_rows_total >= 0, "%s: bad sizes (b = %d, m = %d, %lld rows, a piece of %lld)",
+                 what, b, m, (long long)rows_max, (long long)piece_rows_total);
+    IPSX_REQUIRE(slides, "%s: null slide table", what);
+    RaggedCommitArgs a;
+    a.sel = reinterpret_cast<const long long*>(sel); a.slides = reinterpret_cast<const long long*>(slides);
+    a.m = m; a.n_tables = n_tables; a.piece_rows = piece_rows_total;
+    for (int k = 0; k < n_tables; ++k) {
+        const ipsx_stream_table& s = tables[k];
+        RaggedCommitTable& t = a.t[k];
+        IPSX_REQUIRE(s.dst && s.row_bytes > 0, "%s: table %d has no destination or no row size", what, k);
+        IPSX_REQUIRE(s.held_rows >= 0 && (s.held_rows == 0 || (s.held && (b == 1 || s.held_bstride_rows >= s.held_rows))),
+                     "%s: table %d: the held rows are missing or overlap the next slide's", what, k);
+        IPSX_REQUIRE(s.piece || s.held_rows > 0, "%s: table %d has neither held rows nor a piece", what, k);
+        IPSX_REQUIRE(!s.piece || piece_rows_total > 0, "%s: table %d: a piece of no rows", what, k);
+        IPSX_REQUIRE(s.piece_bstride_bytes == 0, "%s: table %d: the piece is one packed tensor (batch stride 0)", what, k);
+        IPSX_REQUIRE(s.dst_rows > 0 && (b == 1 || s.dst_bstride_rows >= s.dst_rows),
+                     "%s: table %d: a destination of %lld rows, %lld between the slides", what, k, (long long)s.dst_rows,
+                     (long long)s.dst_bstride_rows);
+        const long long dst_span = ((long long)(b - 1) * s.dst_bstride_rows + s.dst_rows) * s.row_bytes;
+        t.in_place = 0;
+        if (s.held_rows > 0) {
+            // in place (append only: the kernel leaves a slide that selects or moves there untouched), or apart
+            if (s.held == s.dst && (b == 1 || s.held_bstride_rows == s.dst_bstride_rows)) t.in_place = 1;
+            else
+                IPSX_REQUIRE(!overlaps(s.dst, dst_span, s.held, ((long long)(b - 1) * s.held_bstride_rows + s.held_rows) * s.row_bytes),
+                             "%s: table %d: the destination overlaps the held rows (in place only from the same address)", what, k);
+        }
+        IPSX_REQUIRE(!s.piece || !overlaps(s.dst, dst_span, s.piece, piece_rows_total * s.row_bytes),
+                     "%s: table %d: the destination overlaps the piece", what, k);
+        t.held = static_cast<const unsigned char*>(s.held); t.held_rows = s.held_rows; t.held_bs = s.held_bstride_rows * s.row_bytes;
+        t.piece = static_cast<const unsigned char*>(s.piece);
+        t.dst = static_cast<unsigned char*>(s.dst); t.dst_rows = s.dst_rows; t.dst_bs = s.dst_bstride_rows * s.row_bytes;
+        t.row_bytes = s.row_bytes;
+        t.unit = 1;
+        for (long long u : {16ll, 4ll})
+            if (s.row_bytes % u == 0 && multiple_of(s.dst, u) && (!s.held || multiple_of(s.held, u)) && (!s.piece || multiple_of(s.piece, u))) {
+                t.unit = (int)u;
+                break;
+            }
+    }
+    for (int k = n_tables; k < COMMIT_MAX_TABLES; ++k) a.t[k] = a.t[0];
+    if (rows_max == 0) return IPSX_OK;
+    IPSX_REQUIRE(rows_max < ((int64_t)1 << 31) && b < 65536, "%s: %lld rows x %d slides in one launch", what, (long long)rows_max, b);
+    stream_commit_ragged_kernel<<<dim3((unsigned)rows_max, (unsigned)b, (unsigned)n_tables), dim3(256), 0, as_stream(stream)>>>(a);
     return launched(what);
 }

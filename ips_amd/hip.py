@@ -395,6 +395,10 @@ _EXPORTS = {
                                           C.c_void_p, C.c_void_p]),
     "ipsx_ragged_finish": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ipsx_scan_ragged_spans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ipsx_stream_commit_ragged": (C.c_int, [C.POINTER(StreamTable), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64,
+                                            C.c_int64, C.c_void_p]),
     "ipsx_aggregate_workspace_bytes": (C.c_size_t, [C.POINTER(Transf), C.c_int, C.c_int]),
     "ipsx_aggregate": (C.c_int, [C.POINTER(Transf), C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                  C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -707,6 +711,83 @@ def scan_ragged(lg, offsets, lengths, M, I, H, T, want_scores=False, workspace=N
                                ws.numel() if ws is not None else 0, _stream()), "ipsx_scan_ragged")
     scan_ragged.last_tie = tie
     return (mem_idx, sc) if want_scores else mem_idx
+
+
+def _on_gpu(what, *tensors):
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise ValueError("{}: every tensor lies on the GPU (got one on {})".format(what, t.device))
+
+
+def scan_ragged_spans(lg, spans, n_max, M, I, H, T, mem_idx, tie, mem_score=None, workspace=None):
+    """``scan_ragged`` on slides that lie anywhere in ONE (rows_total, H*T) float32 table (``ipsx_scan_ragged_spans``):
+    ``spans`` (B, 2) int64 on ``lg``'s device, first row and row count per slide; ``n_max`` the caller's host-side bound on
+    the counts.  ``mem_idx`` (B, M) int64 - row numbers inside the span -, ``mem_score`` (B, M) float32 or None and ``tie``
+    (B,) int32 are the caller's: a slide whose count is not above ``M``, or whose span leaves the table, is left untouched
+    in all three, and ``tie`` is only ever set (the caller clears it)."""
+    _on_gpu("scan_ragged_spans", lg, spans, mem_idx, tie, mem_score, workspace)
+    if lg.dtype != torch.float32 or lg.dim() != 2 or not lg.is_contiguous() or lg.shape[1] != H * T:
+        raise ValueError("scan_ragged_spans needs a contiguous float32 (rows, {}) logits table, got {} {}".format(
+            H * T, lg.dtype, tuple(lg.shape)))
+    B = spans.shape[0] if spans.dim() == 2 else 0
+    if spans.dtype != torch.int64 or tuple(spans.shape) != (B, 2) or B == 0 or not spans.is_contiguous() or spans.device != lg.device:
+        raise ValueError("scan_ragged_spans needs (B, 2) int64 spans on the logits' device")
+    if mem_idx.dtype != torch.int64 or tuple(mem_idx.shape) != (B, M) or not mem_idx.is_contiguous():
+        raise ValueError("mem_idx must be a contiguous ({}, {}) int64 tensor".format(B, M))
+    if tie.dtype != torch.int32 or tuple(tie.shape) != (B,) or not tie.is_contiguous():
+        raise ValueError("tie must be a contiguous ({},) int32 tensor".format(B))
+    if mem_score is not None and (mem_score.dtype != torch.float32 or tuple(mem_score.shape) != (B, M) or not mem_score.is_contiguous()):
+        raise ValueError("mem_score must be a contiguous ({}, {}) float32 tensor".format(B, M))
+    ws = workspace
+    if ws is None:
+        nb = lib().ipsx_scan_workspace_bytes(1, M, I, H, T)
+        ws = torch.empty(B * nb, dtype=torch.uint8, device=lg.device) if nb else None
+    _ck(lib().ipsx_scan_ragged_spans(_p(lg), _p(spans), B, int(n_max), lg.shape[0], M, I, H, T, _p(mem_idx), _p(mem_score), _p(tie),
+                                     _p(ws), ws.numel() if ws is not None else 0, _stream()), "ipsx_scan_ragged_spans")
+    return mem_idx
+
+
+COMMIT_IDLE, COMMIT_APPEND, COMMIT_SELECT, COMMIT_MOVE = 0, 1, 2, 3
+
+
+def stream_commit_ragged(tables, sel, slides, M, rows_max):
+    """The state update of a ragged stream, ONE launch (``ipsx_stream_commit_ragged``).  ``tables``: up to four ``(held, piece,
+    dst)`` - ``held`` (B, cap, ...) or None, all of whose rows may be read; ``piece`` (rows, ...) ONE packed tensor for all
+    slides, or None for a table that holds all candidates itself; ``dst`` (B, cap', ...) contiguous (``held`` itself: append in
+    place).  ``slides`` (B, 6) int64 on the device, per slide: held rows, candidates, tail_first, first row in the packed
+    piece, the mode (``COMMIT_IDLE / _APPEND / _SELECT / _MOVE``), 0.  ``sel`` (B, M) int64 candidate rows of the slides that
+    select, or None.  ``rows_max``: the most rows any slide writes (the grid)."""
+    flat = [t for tab in tables for t in tab]
+    _on_gpu("stream_commit_ragged", sel, slides, *flat)
+    arr = (StreamTable * max(1, len(tables)))()
+    B, piece_rows = None, 0
+    for k, (held, piece, dst) in enumerate(tables[:len(arr)]):
+        if dst.dim() < 2 or not dst.is_contiguous():
+            raise ValueError("table {}: the destination must be a contiguous (B, cap, ...) tensor".format(k))
+        B = dst.shape[0] if B is None else B
+        if dst.shape[0] != B:
+            raise ValueError("table {}: {} slides, the first table has {}".format(k, dst.shape[0], B))
+        t = arr[k]
+        t.dst, t.dst_rows, t.dst_bstride_rows = dst.data_ptr(), dst.shape[1], dst.shape[1]
+        t.row_bytes = dst[0, 0].numel() * dst.element_size()
+        if held is not None:
+            if not held.is_contiguous() or held.dtype != dst.dtype or held.shape[2:] != dst.shape[2:] or held.shape[0] != B \
+                    or held.device != dst.device:
+                raise ValueError("table {}: held rows must be a contiguous (B, cap, ...) tensor of the destination's kind".format(k))
+            t.held, t.held_rows, t.held_bstride_rows = held.data_ptr(), held.shape[1], held.shape[1]
+        if piece is not None:
+            if piece.dtype != dst.dtype or piece.shape[1:] != dst.shape[2:] or piece.device != dst.device or not piece.is_contiguous():
+                raise ValueError("table {}: the piece must be a contiguous packed (rows, ...) tensor of the destination's kind".format(k))
+            if piece_rows and piece.shape[0] != piece_rows:
+                raise ValueError("table {}: a piece of {} rows, another table's has {}".format(k, piece.shape[0], piece_rows))
+            piece_rows = piece.shape[0]
+            t.piece = piece.data_ptr()
+    if tuple(slides.shape) != (B, 6) or slides.dtype != torch.int64 or not slides.is_contiguous():
+        raise ValueError("slides must be a contiguous (B, 6) int64 tensor")
+    if sel is not None and (sel.dtype != torch.int64 or tuple(sel.shape) != (B, M) or not sel.is_contiguous()):
+        raise ValueError("sel must be a contiguous (B, M) int64 tensor")
+    _ck(lib().ipsx_stream_commit_ragged(arr, len(tables), _p(sel), _p(slides), B or 0, M, int(rows_max), piece_rows, _stream()),
+        "ipsx_stream_commit_ragged")
 
 
 def _stream_tables(tables, n_cand):

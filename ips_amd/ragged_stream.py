@@ -1,0 +1,420 @@
+"""``RaggedIPSStream``: slides of different lengths fed in pieces (``IPSNet.ips_ragged_stream()``).
+
+``ips_stream()`` bounds the memory of a selection but every image must receive the same number of rows in every feed;
+``ips_ragged()`` takes slides of different lengths but needs every row of every slide at once.  This stream does both:
+
+    s = net.ips_ragged_stream()                 # or pad=True
+    for pieces in source:                       # a Ragged, or a list of B tensors (n_b, F) | (n_b, C, h, w); n_b >= 0, sum n_b >= 1
+        s.feed(pieces)
+    mem_patch, mem_pos = s.finish()
+
+Every feed carries the next rows of each slide, as many or as few as the caller has - none for a slide that has ended or has
+nothing this time - and each slide's chunk loop runs as far as that slide's rows allow.  On a net whose ``shuffle`` is off
+``finish()`` returns and leaves behind, bit for bit, what ``net.ips_ragged([torch.cat(pieces of slide b) for b], pad=pad)``
+returns and leaves behind, wherever the pieces end.  Like ``IPSStream`` it never shuffles.
+
+On a ROCm device the state is that of ``IPSStream`` - two sets of four tables (B, M + I - 1, ...): patch rows, embeddings,
+global ids, logits (the logits table alone grows with the largest number of candidates a slide has had in a feed) - but
+every slide has its own numbers: rows held, rows fed, iterations this feed completes.  They are host ints; per feed they go
+to the device as ONE small int64 table, and nothing is read back.  A feed is one encoder pass and one ``hip.logits`` over
+its packed rows, one launch that puts the piece's logits behind each slide's held logits
+(``hip.stream_commit_ragged``, append), ONE loop launch in which slide b scans the first M + k_b * I rows of its block of
+the logits table (``hip.scan_ragged_spans``; a slide with k_b = 0 is not touched) and ONE commit launch for all four tables
+in which a slide selects, moves (it completed no chunk but the stream flips its buffer set) or idles.  A feed in which no
+slide completes a chunk is encoder, logits and one append launch for the four tables.
+
+On a CPU device, and where an encoder alone is in training mode inside an eval-mode net (the fall-back conditions of
+``ragged._host_route``), B solo ``IPSStream`` state machines run on ATen ops.
+"""
+
+import torch
+
+from . import hip
+from .ragged import Ragged, _host_emb
+from .stream import IPSStream
+
+
+class RaggedIPSStream:
+    """The state of one streamed ragged selection.  ``fed``: rows per slide so far; ``iterations``: completed iterations per
+    slide; ``mem_idx``: (B, M) int64 row numbers inside each slide, in the order of its last completed iteration (a row of
+    -1 for a slide that has not reached M rows; None before the first feed)."""
+
+    def __init__(self, net, pad=False):
+        self.net = net
+        self.pad = bool(pad)
+        self._finished = False
+        self._generation = hip.weights_generation()
+        self._B = self._row_shape = self._dtype = None
+        self._fed, self._iters, self._held = [], [], []
+        self._last_idx = None
+        self._solo = None            # the host route: B IPSStream on ATen ops
+        self._device_route = None    # decided by the first feed
+        # device state
+        self._sets = None            # [[patch, emb, ids, logits], [...]]: the two buffer sets
+        self._cur = 0
+        self._sel = self._tie = self._scan_ws = None
+        self._stage, self._stage_at = [], 0      # pinned (3, B, 6) staging buffers of the per-feed table, used in turn
+
+    # ------------------------------------------------------------------ observable state
+    @property
+    def fed(self):
+        return tuple(self._fed)
+
+    @property
+    def iterations(self):
+        return tuple(self._iters)
+
+    @property
+    def mem_idx(self):
+        if self._finished:
+            return self._last_idx
+        if self._B is None:
+            return None
+        M = self.net.M
+        if not self._device_route:
+            out = torch.full((self._B, M), -1, dtype=torch.int64, device=self.net.device)
+            for b, s in enumerate(self._solo):
+                if s.fed >= M:
+                    out[b] = s.mem_idx[0]
+            return out
+        reached = torch.tensor([n >= M for n in self._fed]).to(self.net.device)
+        return torch.where(reached.unsqueeze(1), self._sets[self._cur][2][:, :M], -1)
+
+    # ------------------------------------------------------------------ checks, before the first launch or allocation of a call
+    def _check(self):
+        if self._finished:
+            raise RuntimeError("this stream has finished (IPSNet.ips_ragged_stream() starts another)")
+        if hip.dedup_blank():
+            raise TypeError("blank-patch dedup needs the whole input (IPSX_DEDUP_BLANK=1 with ips_ragged_stream)")
+        if hip.weights_generation() != self._generation:
+            raise RuntimeError("the weights changed since this stream began (an optimizer step between feeds would mix "
+                               "embeddings of two weight sets)")
+
+    def _check_pieces(self, pieces):
+        """-> (lengths, row shape, dtype) of a feed, or the refusal."""
+        net = self.net
+        dim = 4 if net.is_image else 2
+        layout = "(n_b, C, h, w) patches of an image encoder" if net.is_image else "(n_b, F) feature rows"
+        if isinstance(pieces, Ragged):
+            if pieces.rows.dim() != dim:
+                raise ValueError("a feed is a Ragged, or a list of B tensors, of {}".format(layout))
+            lengths, shape, dtype = pieces.lengths, tuple(pieces.rows.shape[1:]), pieces.dtype
+        else:
+            if not isinstance(pieces, (list, tuple)) or not pieces or any(not torch.is_tensor(p) or p.dim() != dim for p in pieces):
+                raise ValueError("a feed is a Ragged, or a list of B tensors, of {}".format(layout))
+            shape, dtype = tuple(pieces[0].shape[1:]), pieces[0].dtype
+            for k, p in enumerate(pieces):
+                if tuple(p.shape[1:]) != shape or p.dtype != dtype:          # (each piece may lie on the host or on the device)
+                    raise ValueError("piece {}: the pieces of a feed have one row shape and dtype".format(k))
+            lengths = tuple(int(p.shape[0]) for p in pieces)
+        if len(lengths) == 0:
+            raise ValueError("a feed of no slides")
+        if dtype == torch.uint8:
+            raise TypeError("ips_ragged_stream reads float32 rows (float16 / bfloat16 where ips() takes them): uint8 patch storage "
+                            "goes through ips_stream() slide by slide")
+        if self._B is None:
+            if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+                raise TypeError("pieces are float32, or float16 / bfloat16 where ips() takes them; got {}".format(dtype))
+            if dtype != torch.float32 and self._routes_to_device():
+                # (what the encoder plan would refuse at its first launch: said here, before anything is allocated)
+                if hip.precision() == "fp32" or (not net.is_image and hip.precision() != "bf16"):
+                    raise TypeError("{} pieces need IPSX_PRECISION=bf16{}".format(dtype, " or fp32x3" if net.is_image else ""))
+        else:
+            if len(lengths) != self._B or shape != self._row_shape:
+                raise ValueError("a feed of {} slides with rows {} in a stream of B = {} slides with rows {}".format(
+                    len(lengths), shape, self._B, self._row_shape))
+            if dtype != self._dtype:
+                raise TypeError("a {} feed in a stream of {}".format(dtype, self._dtype))
+        if sum(lengths) == 0:
+            raise ValueError("a feed carries at least one row (every length is 0)")
+        if net.use_pos:
+            fed = self._fed or [0] * len(lengths)
+            for b, n in enumerate(lengths):
+                if fed[b] + n > net.pos_enc.shape[1]:
+                    raise ValueError("slide {} would have {} rows, the positional table conf.N = {}".format(
+                        b, fed[b] + n, net.pos_enc.shape[1]))
+        return lengths, shape, dtype
+
+    def _routes_to_device(self):
+        net = self.net
+        return hip.on_device(net.device) and not (net.encoder.training and not net.training)
+
+    # ------------------------------------------------------------------ feed
+    @torch.no_grad()
+    def feed(self, pieces):
+        """Take the next rows of every slide: a ``Ragged``, or a list of B tensors (n_b, ...) with n_b >= 0 and at least one
+        row in all; on the device or on the host (a host piece is copied to the device as it is, and only the piece).
+        Stream-ordered on the current stream, as ``IPSStream.feed``."""
+        self._check()
+        lengths, shape, dtype = self._check_pieces(pieces)
+        net = self.net
+        if self._B is None:
+            self._B, self._row_shape, self._dtype = len(lengths), shape, dtype
+            self._fed, self._iters, self._held = [0] * self._B, [0] * self._B, [0] * self._B
+            self._device_route = self._routes_to_device()
+            if not self._device_route:
+                self._solo = [IPSStream(net) for _ in range(self._B)]
+                for s in self._solo:
+                    s._on_device = False         # (the ATen state machine, also for device tensors)
+        if self._device_route:
+            with net._scoring():
+                self._feed_hip(pieces, lengths)
+        else:
+            for b, n in enumerate(lengths):
+                if n:
+                    self._solo[b].feed(pieces[b].unsqueeze(0))
+                    self._iters[b] = self._solo[b].iterations
+        for b, n in enumerate(lengths):
+            self._fed[b] += n
+        return self
+
+    def feed_all(self, slides, slab_rows):
+        """Walk ``slides`` (a ``Ragged`` or a list of (N_b, ...) tensors) in slabs of at most ``slab_rows`` packed rows - a slab
+        may end inside a slide - and feed each: the lazy route for a host batch,
+        ``net.ips_ragged_stream(pad=...).feed_all(batch, 65536).finish()``."""
+        slab_rows = int(slab_rows)
+        if slab_rows < 1:
+            raise ValueError("slabs of {} rows".format(slab_rows))
+        ragged = slides if isinstance(slides, Ragged) else None
+        lengths = ragged.lengths if ragged is not None else tuple(int(s.shape[0]) for s in slides)
+        starts = [0]
+        for n in lengths:
+            starts.append(starts[-1] + n)
+        total = starts[-1]
+        if total == 0:
+            self.feed(slides)                    # (refused there)
+        for lo in range(0, total, slab_rows):
+            hi = min(lo + slab_rows, total)
+            cut = [(min(max(lo, starts[b]), starts[b + 1]) - starts[b], min(max(hi, starts[b]), starts[b + 1]) - starts[b])
+                   for b in range(len(lengths))]
+            if ragged is not None:               # the slab's rows are one range of the packed rows
+                self.feed(Ragged(ragged.rows[lo:hi], [e - s for s, e in cut]))
+            else:
+                self.feed([slides[b][s:e] for b, (s, e) in enumerate(cut)])
+        return self
+
+    # ------------------------------------------------------------------ the ROCm device
+    def _allocate(self, dev):
+        net = self.net
+        B, cap = self._B, net.M + net.I - 1
+        ca = net.transf.crs_attn
+        self._R = ca.H * ca.n_token
+        self._sets = [[torch.empty((B, cap) + self._row_shape, dtype=self._dtype, device=dev),
+                       torch.empty((B, cap, net.D), dtype=torch.float32, device=dev),
+                       torch.empty((B, cap), dtype=torch.int64, device=dev),
+                       None] for _ in range(2)]
+        self._sel = torch.empty((B, net.M), dtype=torch.int64, device=dev)
+        self._tie = torch.zeros((B,), dtype=torch.int32, device=dev)
+        nb = hip.lib().ipsx_scan_workspace_bytes(1, net.M, net.I, ca.H, ca.n_token)
+        self._scan_ws = torch.empty(B * nb, dtype=torch.uint8, device=dev) if nb else None
+
+    def _numbers(self, planes, dev):
+        """Up to three (B, 6) planes of host ints -> ONE (3, B, 6) int64 tensor on the device, ONE copy.  The copy leaves from
+        pinned memory and does not wait for the device: a few staging buffers are used in turn, each with the event behind
+        its last copy."""
+        B = self._B
+        planes = planes + [[[0] * 6] * B] * (3 - len(planes))
+        host = torch.tensor(planes, dtype=torch.int64)
+        if not self._stage:
+            self._stage = [[torch.empty((3, B, 6), dtype=torch.int64).pin_memory(), None] for _ in range(4)]
+        slot = self._stage[self._stage_at % len(self._stage)]
+        self._stage_at += 1
+        if slot[1] is not None:
+            slot[1].synchronize()
+        slot[0].copy_(host)
+        out = slot[0].to(dev, non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record()
+        return out
+
+    def _logits_room(self, rows, dev):
+        """The logits tables hold a slide's held rows AND its piece's: they grow with the largest number of candidates."""
+        cur = self._sets[self._cur][3]
+        if cur is not None and cur.shape[1] >= rows:
+            return
+        new = [torch.empty((self._B, rows, self._R), dtype=torch.float32, device=dev) for _ in range(2)]
+        if cur is not None:
+            new[self._cur][:, :cur.shape[1]].copy_(cur)
+        for k in range(2):
+            self._sets[k][3] = new[k]
+
+    def _pack(self, pieces, lengths, dev):
+        """The feed's rows as ONE packed (sum n_b, ...) tensor on the device: a host piece goes over as it is."""
+        if isinstance(pieces, Ragged):
+            return pieces.rows.to(dev)
+        live = [p for p in pieces if p.shape[0]]
+        if len(live) == 1:
+            p = live[0].to(dev)
+            return p if p.is_contiguous() else p.contiguous()
+        packed = torch.empty((sum(lengths),) + self._row_shape, dtype=self._dtype, device=dev)
+        lo = 0
+        for p in live:
+            packed[lo:lo + p.shape[0]].copy_(p)
+            lo += p.shape[0]
+        return packed
+
+    def _scan(self, counts, lcap):
+        """ONE loop launch: slide b scans the first counts[b] rows of its block of the current logits table (0: not touched)."""
+        net = self.net
+        ca = net.transf.crs_attn
+        lg = self._sets[self._cur][3]
+        hip.scan_ragged_spans(lg.view(self._B * lcap, self._R), self._spans, max(counts), net.M, net.I, ca.H, ca.n_token,
+                              self._sel, self._tie, workspace=self._scan_ws)
+        hip.scan.last_tie = self._tie
+
+    def _feed_hip(self, pieces, lengths):
+        net = self.net
+        M, I, B, dev = net.M, net.I, self._B, net.device
+        held, fed = self._held, self._fed
+        total = [held[b] + lengths[b] for b in range(B)]
+        k = [(t - M) // I if t > M else 0 for t in total]
+        starts = [0]
+        for n in lengths:
+            starts.append(starts[-1] + n)
+        any_select = any(k)
+        if self._sets is None:
+            self._allocate(dev)
+        self._logits_room(max(total), dev)
+        lcap = self._sets[self._cur][3].shape[1]
+        # the per-slide numbers of every launch of this feed: ONE int64 table, ONE copy
+        A, S, V, E = hip.COMMIT_APPEND, hip.COMMIT_SELECT, hip.COMMIT_MOVE, hip.COMMIT_IDLE
+        append = [[held[b], total[b], 0, starts[b], A if lengths[b] else E, 0] for b in range(B)]
+        commit = [[held[b], total[b], M + k[b] * I if k[b] else 0, starts[b], S if k[b] else (V if total[b] else E), 0] for b in range(B)]
+        counts = [M + k[b] * I if k[b] else 0 for b in range(B)]
+        spans = [[b * lcap, counts[b], lengths[b], fed[b] - starts[b], 0, 0] for b in range(B)]
+        table = self._numbers([append, commit, spans], dev)
+        self._spans = table[2, :, :2].contiguous()
+
+        packed = self._pack(pieces, lengths, dev)
+        emb = net._embed(packed)                                          # ONE encoder pass over the packed rows
+        n_tot = starts[-1]
+        # the row number inside its slide of every packed row: fed_b + r (ids, and the rows of the positional table)
+        ids = torch.arange(n_tot, dtype=torch.int64, device=dev) + torch.repeat_interleave(table[2, :, 3], table[2, :, 2], output_size=n_tot)
+        pos = net.pos_enc[0].index_select(0, ids).unsqueeze(0) if net.use_pos else None
+        lg_piece = hip.logits(emb.unsqueeze(0), pos, net.transf.crs_attn.folded_query(), self._R)[0]
+        cur, dst = self._sets[self._cur], self._sets[self._cur ^ 1]
+        if not any_select:                   # no slide completes a chunk: everything goes behind the held rows, in place
+            hip.stream_commit_ragged([(cur[0], packed, cur[0]), (cur[1], emb, cur[1]), (cur[2], ids, cur[2]), (cur[3], lg_piece, cur[3])],
+                                     None, table[0], M, max(lengths))
+            self._held = total
+            return
+        hip.stream_commit_ragged([(cur[3], lg_piece, cur[3])], None, table[0], M, max(lengths))
+        self._scan(counts, lcap)
+        rows_max = max(total[b] - k[b] * I for b in range(B))
+        hip.stream_commit_ragged([(cur[0], packed, dst[0]), (cur[1], emb, dst[1]), (cur[2], ids, dst[2]), (cur[3], None, dst[3])],
+                                 self._sel, table[1], M, rows_max)
+        self._cur ^= 1
+        self._held = [total[b] - k[b] * I for b in range(B)]
+        for b in range(B):
+            self._iters[b] += k[b]
+
+    def _last_chunks(self):
+        """The ragged last chunk of every slide that holds more than M rows: one more iteration, no tail behind it."""
+        net = self.net
+        M, B, dev = net.M, self._B, net.device
+        held = self._held
+        if not any(h > M for h in held):
+            return
+        lcap = self._sets[self._cur][3].shape[1]
+        S, V, E = hip.COMMIT_SELECT, hip.COMMIT_MOVE, hip.COMMIT_IDLE
+        commit = [[held[b], held[b], held[b], 0, S if held[b] > M else (V if held[b] else E), 0] for b in range(B)]
+        counts = [held[b] if held[b] > M else 0 for b in range(B)]
+        spans = [[b * lcap, counts[b], 0, 0, 0, 0] for b in range(B)]
+        table = self._numbers([commit, spans], dev)
+        self._spans = table[1, :, :2].contiguous()
+        self._scan(counts, lcap)
+        cur, dst = self._sets[self._cur], self._sets[self._cur ^ 1]
+        hip.stream_commit_ragged([(cur[0], None, dst[0]), (cur[1], None, dst[1]), (cur[2], None, dst[2])], self._sel, table[0], M, M)
+        self._cur ^= 1
+        self._held = [min(h, M) for h in held]
+        for b in range(B):
+            self._iters[b] += 1 if held[b] > M else 0
+
+    # ------------------------------------------------------------------ finish
+    @torch.no_grad()
+    def finish(self):
+        """Run the ragged last chunk of every slide that has one -> (mem_patch (B, M, ...), mem_pos (B, M, D) | None), and
+        leave behind what ``ips_ragged`` leaves.  Without ``pad`` a slide with no more than M rows is refused, with ``pad``
+        a slide with no rows at all."""
+        self._check()
+        net = self.net
+        if self._B is None:
+            raise RuntimeError("nothing was fed")
+        M, B = net.M, self._B
+        for b, n in enumerate(self._fed):
+            if self.pad and n == 0:
+                raise ValueError("slide {} has no rows: nothing to pad".format(b))
+            if n <= M and not self.pad:
+                raise ValueError("slide {} has {} rows and the memory M = {}: the reference returns all {} of them there, the "
+                                 "batch would not be rectangular (select such a slide with ips())".format(b, n, M, n))
+        net._reset_last()
+        if self._device_route:
+            mem_patch, mem_pos = self._finish_hip()
+        else:
+            mem_patch, mem_pos = self._finish_aten()
+        net._mem_count = tuple(min(n, M) for n in self._fed) if self.pad else None
+        self._finished, self._last_idx = True, net.last_mem_idx
+        self._sets = self._sel = self._scan_ws = self._solo = None
+        self._stage = []
+        return mem_patch, mem_pos
+
+    def _finish_hip(self):
+        net = self.net
+        M, B, dev = net.M, self._B, net.device
+        with net._scoring():
+            self._last_chunks()
+            patch, emb, ids, _ = self._sets[self._cur]
+            mem_patch, mem_emb, mem_idx = patch[:, :M].clone(), emb[:, :M].clone(), ids[:, :M].clone()
+            padded = any(n < M for n in self._fed)
+            if padded:                       # rows, then +0.0; 0 .. N_b-1, then -1
+                n = torch.tensor(self._fed, dtype=torch.int64).to(dev).unsqueeze(1)
+                hole = torch.arange(M, dtype=torch.int64, device=dev).unsqueeze(0) >= n
+                mem_patch.masked_fill_(hole.view(B, M, *(1,) * (mem_patch.dim() - 2)), 0)
+                mem_idx.masked_fill_(hole, -1)
+            mem_pos = None
+            if net.use_pos:
+                mem_pos = net._take(net.pos_enc.expand(B, -1, -1), mem_idx.clamp(min=0) if padded else mem_idx)
+                if padded:
+                    mem_pos.masked_fill_(hole.unsqueeze(-1), 0)
+        net.last_mem_idx = mem_idx
+        if not padded:
+            net._mem_emb = mem_emb
+            return mem_patch, mem_pos
+        zero_row = (1,) + self._row_shape, self._dtype
+
+        def emb_of_slots():
+            """The padding holds the embedding of ONE all-zero row (made on first read, as ``ips_ragged`` makes it)."""
+            with torch.no_grad(), net._scoring():
+                zero = net._embed(torch.zeros(zero_row[0], dtype=zero_row[1], device=dev))
+                return torch.where(hole.unsqueeze(-1), zero.view(1, 1, -1), mem_emb)
+        net._emb_make = emb_of_slots
+        return mem_patch, mem_pos
+
+    def _finish_aten(self):
+        """What ``ragged._host_route`` builds, from the solo streams: a long slide's selection, a short slide's rows in the
+        order given and the zero padding behind them."""
+        net = self.net
+        M, B, D, device = net.M, self._B, net.D, net.device
+        mem_patch = torch.zeros((B, M) + self._row_shape, dtype=self._dtype, device=device)
+        mem_pos = torch.zeros((B, M, D), dtype=net.pos_enc.dtype, device=device) if net.use_pos else None
+        mem_idx = torch.full((B, M), -1, dtype=torch.int64, device=device)
+        long_emb, short_rows = {}, {}
+        for b, n in enumerate(self._fed):
+            p, q = self._solo[b].finish()
+            self._iters[b] = self._solo[b].iterations
+            if n > M:
+                mem_patch[b] = p[0]
+                if net.use_pos:
+                    mem_pos[b] = q[0]
+                mem_idx[b] = net.last_mem_idx[0]
+                long_emb[b] = net.last_mem_emb
+            else:                                  # the rows in arrival order, as fill_batch writes them
+                short_rows[b] = rows = p[0]
+                mem_patch[b, :n] = rows
+                if net.use_pos:
+                    mem_pos[b, :n] = net.pos_enc[0, :n]
+                mem_idx[b, :n] = torch.arange(n, dtype=torch.int64, device=device)
+        net._reset_last()                          # (what the last solo stream left is that stream's, not this one's)
+        net.last_mem_idx = mem_idx
+        net._emb_make = lambda: _host_emb(net, long_emb, short_rows)
+        return mem_patch, mem_pos
