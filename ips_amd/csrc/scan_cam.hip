@@ -99,8 +99,8 @@ __device__ __forceinline__ void search_run_u32_x2(const uint32_t* runA, uint32_t
     cB = (int)(loB + key_gt(lastB, mB));
 }
 
-template <bool STAMP, bool PERSIST, bool STRIDED = false, bool RAGGED = false, bool SPANS = false>      // (STRIDED, RAGGED, SPANS: see scan_fast_kernel)
-__global__ __launch_bounds__(cam::NT) void scan_cam_kernel(ScanArgs a, unsigned long long* stamps) {
+template <bool STAMP, bool PERSIST, Rows ROWS = Rows::Packed>      // (ROWS, aux: see scan_fast_kernel)
+__global__ __launch_bounds__(cam::NT) void scan_cam_kernel(ScanArgs a, ScanAux<ROWS> aux) {
     using namespace cam;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (!PERSIST && scan_skipped(a.cond, a.cond_mask)) return;
@@ -131,12 +131,11 @@ __global__ __launch_bounds__(cam::NT) void scan_cam_kernel(ScanArgs a, unsigned 
     // projector, so two resident loops follow 16 slides and the projector keeps the other 14 compute units.
     for (int b = blockIdx.x; b < a.slides; b += (int)gridDim.x) {
     long long first_row = 0;
-    if constexpr (RAGGED) {                                      // (one workgroup per slide: the loop over b makes one trip)
+    if constexpr (rows_per_slide(ROWS)) {
         a.it0 = 0;
-        static_assert(!(RAGGED && (STAMP || PERSIST || STRIDED)), "scan_cam_kernel: RAGGED is a plain launch");
-        if (!slide_of<SPANS>(reinterpret_cast<const long long*>(stamps), a.lg_bs, b, M, I, &first_row, &a.n, &a.it1)) return;
+        if (!slide_of<ROWS, !(STAMP || PERSIST)>(aux, a.table_rows, b, M, I, &first_row, &a.n, &a.it1)) return;
     }
-    const float* lg = RAGGED ? a.lg + (size_t)first_row * R : a.lg + (size_t)b * (STRIDED ? a.lg_bs : a.n) * R;
+    const float* lg = image_rows<ROWS, !(STAMP || PERSIST)>(a.lg, a.n, a.table_rows, first_row, b, R);
 #pragma unroll
     for (int k = 0; k < 8; ++k) tacc[k] = 0;
     if (STAMP) tlast = __builtin_amdgcn_s_memtime();
@@ -206,7 +205,7 @@ __global__ __launch_bounds__(cam::NT) void scan_cam_kernel(ScanArgs a, unsigned 
         uint32_t* const mkey_nx = pmax + 2 * R * (par ^ 1);     // ... and folded into by this iteration, for the next one
         // diagnostic (STAMP build): every wave's clock at 15 points of iterations 100..103 of image 0 (tools/scan_stamps.py camwaves)
         unsigned long long* const wlog = (STAMP && b == 0 && k_it >= 100 && k_it < 104)
-                                             ? stamps + 8 * gridDim.x + 2048 + (k_it - 100) * 256 + wave * 16 : nullptr;
+                                             ? stamps_of(aux) + 8 * gridDim.x + 2048 + (k_it - 100) * 256 + wave * 16 : nullptr;
 #define WSTAMP(k_) do { if (STAMP && wlog != nullptr && lane == 0) wlog[k_] = __builtin_amdgcn_s_memtime(); } while (0)
         const int lo1 = lo + I;
         const int cnt1 = k_it + 1 < n_it ? max(0, min(I, n_rows - lo1)) : 0;
@@ -488,8 +487,8 @@ __global__ __launch_bounds__(cam::NT) void scan_cam_kernel(ScanArgs a, unsigned 
         // diagnostic (STAMP build; tools/scan_stamps.py campipe): when this iteration ended (100 MHz clock) and how many rows
         // the loop knew to be published then - the timeline of a call, loop against producer
         if (STAMP && b == 0 && tid == 0 && k_it < 512) {
-            stamps[8 * gridDim.x + 4 * k_it + 2] = __builtin_amdgcn_s_memrealtime();
-            stamps[8 * gridDim.x + 4 * k_it + 3] = (unsigned long long)ready_known;
+            stamps_of(aux)[8 * gridDim.x + 4 * k_it + 2] = __builtin_amdgcn_s_memrealtime();
+            stamps_of(aux)[8 * gridDim.x + 4 * k_it + 3] = (unsigned long long)ready_known;
         }
 #undef WSTAMP
 #undef CAM_PREP
@@ -505,68 +504,33 @@ __global__ __launch_bounds__(cam::NT) void scan_cam_kernel(ScanArgs a, unsigned 
     }
     if (a.tie && tid == 0 && tie) a.tie[b] = 1;
     if (STAMP && tid == 0)
-        for (int k = 0; k < 8; ++k) stamps[(size_t)b * 8 + k] = tacc[k];
+        for (int k = 0; k < 8; ++k) stamps_of(aux)[(size_t)b * 8 + k] = tacc[k];
     lds_barrier();                                               // (the next slide starts on the same LDS)
     }
 }
 
 bool scan_cam_shape(int m, int i, int h, int n_token) { return h * n_token == cam::R && n_token == 1 && m == cam::M && i == cam::I; }
 
+// BASELINE configs[3] (8 heads, one token, M = I = 256): the specialised loop (scan_cam_kernel)
 int launch_scan_cam(const ScanCall& c) {
-    const int b = c.b;
-    void* const stream = c.stream;
+    static_assert(cam::LDS_BYTES <= 160 * 1024, "scan_cam_kernel: LDS");
     ScanArgs a;
-    a.plog = persist_log();
-    a.lg = c.logits; a.n = c.n; a.lg_bs = c.logits_bstride_rows; a.m = c.m; a.i = c.i; a.h = c.h; a.T = c.n_token; a.n2 = next_pow2(c.m + c.i);
-    a.it0 = c.it_begin; a.it1 = c.it_end;
-    a.mem_idx = reinterpret_cast<long long*>(c.mem_idx); a.mem_score = c.mem_score; a.tie = c.tie_flag;
-    a.ready = c.ready; a.status = c.status; a.ready_stride = c.ready_stride;
-    a.ready_words = c.ready ? (c.ready_stride ? std::min(c.b, 64) : 1) : 0;
-    a.wait_ticks = (unsigned long long)g_persist_wait_ms * 100000ull;
-    a.cond = c.cond; a.cond_mask = c.cond_mask;
-    a.slides = c.b;
-    a.tie_order = g_tie_order;
-    a.use_lds = 1;
-    unsigned long long* st = g_scan_stamps;
-    {
-        // BASELINE configs[3] (8 heads, one token, M = I = 256): the specialised loop (scan_cam_kernel)
-        static_assert(cam::LDS_BYTES <= 160 * 1024, "scan_cam_kernel: LDS");
-        a.stk_off = cam::OFF_STK;
-        const int grid = c.workgroups > 0 && c.workgroups < b ? c.workgroups : b;
-#define IPSX_LAUNCH_CAM(S, P)                                                                                       \
-    do {                                                                                                            \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_cam_kernel<S, P>),                             \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)cam::LDS_BYTES);                 \
-        scan_cam_kernel<S, P><<<dim3((unsigned)grid), dim3(cam::NT), cam::LDS_BYTES, as_stream(stream)>>>(a, st);   \
-        return launched("scan");                                                                                    \
-    } while (0)
-        if (c.row_offsets != nullptr && c.spans) {                // ipsx_scan_ragged_spans: as below, the slides looked up in pairs
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_cam_kernel<false, false, false, true, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)cam::LDS_BYTES);
-            scan_cam_kernel<false, false, false, true, true><<<dim3((unsigned)b), dim3(cam::NT), cam::LDS_BYTES, as_stream(stream)>>>(
-                a, reinterpret_cast<unsigned long long*>(const_cast<int64_t*>(c.row_offsets)));
-            return launched("scan");
-        }
-        if (c.row_offsets != nullptr) {                           // ipsx_scan_ragged: plain launches, one workgroup per slide
-            // (the row offsets in the place of the stamps, the table's rows in a.lg_bs: ragged_slide, scan_common.h)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_cam_kernel<false, false, false, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)cam::LDS_BYTES);
-            scan_cam_kernel<false, false, false, true><<<dim3((unsigned)b), dim3(cam::NT), cam::LDS_BYTES, as_stream(stream)>>>(
-                a, reinterpret_cast<unsigned long long*>(const_cast<int64_t*>(c.row_offsets)));
-            return launched("scan");
-        }
-        if (!a.ready && c.logits_bstride_rows != c.n) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_cam_kernel<false, false, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)cam::LDS_BYTES);
-            scan_cam_kernel<false, false, true><<<dim3((unsigned)grid), dim3(cam::NT), cam::LDS_BYTES, as_stream(stream)>>>(a, nullptr);
-            return launched("scan");
-        }
-        if (st && a.ready) IPSX_LAUNCH_CAM(true, true);
-        if (st) IPSX_LAUNCH_CAM(true, false);
-        if (a.ready) IPSX_LAUNCH_CAM(false, true);
-        IPSX_LAUNCH_CAM(false, false);
-#undef IPSX_LAUNCH_CAM
+    fill_scan_args(a, c);
+    a.stk_off = cam::OFF_STK;
+    unsigned long long* const st = g_scan_stamps;
+    const bool persist = c.ready != nullptr;
+    const dim3 grid((unsigned)(c.workgroups > 0 && c.workgroups < c.b ? c.workgroups : c.b)), block(cam::NT);    // (Offsets / Spans: always b)
+    switch (c.rows) {
+        case Rows::Offsets: launch_lds(scan_cam_kernel<false, false, Rows::Offsets>, grid, block, cam::LDS_BYTES, c.stream, a, slide_entries(c)); break;
+        case Rows::Spans: launch_lds(scan_cam_kernel<false, false, Rows::Spans>, grid, block, cam::LDS_BYTES, c.stream, a, slide_entries(c)); break;
+        case Rows::Strided: launch_lds(scan_cam_kernel<false, false, Rows::Strided>, grid, block, cam::LDS_BYTES, c.stream, a, nullptr); break;
+        case Rows::Packed:
+            launch_lds(st ? (persist ? scan_cam_kernel<true, true> : scan_cam_kernel<true, false>)               // diagnostic builds
+                          : (persist ? scan_cam_kernel<false, true> : scan_cam_kernel<false, false>),
+                       grid, block, cam::LDS_BYTES, c.stream, a, st);
+            break;
     }
+    return launched("scan");
 }
 
 }  // namespace ipsx

@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "ipsx_common.h"
 #include "ipsx_math.h"
@@ -699,55 +700,85 @@ struct ScanArgs {
     int slides;            // images of the call; a launch of fewer workgroups (scan_cam_kernel) gives workgroup w the
                            // images w, w + gridDim.x, ... one after the other
     unsigned long long* plog;   // the resident loops' log (scorer.hip g_persist_log; diagnostic: ipsx_dbg_persist_log)
-    long long lg_bs;       // rows between the images' logits: read by the STRIDED instantiations only (ipsx_scan_range_strided)
+    long long table_rows;  // Rows::Strided: rows between two images' logits; Rows::Offsets / Spans: rows of the one table the slides
+                           //   lie in; Rows::Packed: not read (the images lie n rows apart)
 };
 
-// RAGGED (ipsx_scan_ragged): workgroup b's slide out of the packed table - rows [row_off[b], row_off[b + 1]) of rows_total.
-// The argument blocks stay as they are (every other kernel compiles to the instructions it always did): a RAGGED launch is
-// never a stamped one, so the row offsets travel as the kernels' second argument (`stamps`), and rows_total as lg_bs, which
-// the STRIDED instantiations alone read.  The two offsets are workgroup-uniform and kept scalar; a slide the caller's
-// guarantee (more than m rows, inside the table) does not hold for is not touched (-> false).
-__device__ __forceinline__ bool ragged_slide(const long long* row_off, long long rows_total, int b, int m, int i,
-                                             long long* first, long long* n, long long* n_iter) {
-    const long long r0 = row_off[b], r1 = row_off[b + 1];
-    const long long lo = ((long long)__builtin_amdgcn_readfirstlane((int)(r0 >> 32)) << 32) |
-                         (unsigned int)__builtin_amdgcn_readfirstlane((int)r0);
-    const long long hi = ((long long)__builtin_amdgcn_readfirstlane((int)(r1 >> 32)) << 32) |
-                         (unsigned int)__builtin_amdgcn_readfirstlane((int)r1);
-    *first = lo;
-    *n = hi - lo;
-    if (!(lo >= 0 && hi <= rows_total && hi - lo > m && hi - lo < (1ll << 31))) return false;
-    // (n < 2^31: the division in 32 bits - it runs on the vector unit - and its quotient back into a scalar register)
-    *n_iter = (long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)((unsigned int)(hi - lo - m + i - 1) / (unsigned int)i));
-    return true;
+// Where image b's logit rows lie and how many there are - decided ONCE, where a ScanCall is made (scorer.hip), and compiled
+// into the loop kernels as a template argument, so every layout's kernel is the code it was before the next layout came:
+//   Packed   image b's n rows start b * n rows into the table (every entry point but the three below)
+//   Strided  ... b * table_rows rows into it (ipsx_scan_range_strided: a stream's candidate table of fixed capacity)
+//   Offsets  slide b is rows [table[b], table[b + 1]) of ONE table of table_rows rows (ipsx_scan_ragged)
+//   Spans    slide b is table[2 b + 1] rows from row table[2 b] on; spans need not touch (ipsx_scan_ragged_spans)
+// Only Packed logits are waited for (persistent), launched conditionally or stamped: scorer.hip refuses the rest.
+// (The enumerators' ORDER is part of the generated code: the compiler numbers the kernels of a translation unit by their
+//  sorted mangled names for the dynamic-LDS table of the functions they call, and this order keeps every kernel the number -
+//  an immediate in front of those calls - it had as <STRIDED, RAGGED, SPANS> booleans.  tools/asm_compare.py shows it.)
+enum class Rows : int { Packed, Offsets, Spans, Strided };
+constexpr bool rows_per_slide(Rows r) { return r == Rows::Offsets || r == Rows::Spans; }
+
+// The loop kernels' second parameter, typed by the layout: the slide table of an Offsets / Spans build - which is never a
+// stamped one -, the stamp buffer of the diagnostic builds (ignored by the others) else.  A plain pointer either way: the
+// kernels' argument layout, and the code of every instantiation, is what it was when this was `unsigned long long* stamps`
+// for all of them (what a union in its place, or one more member of ScanArgs, does to the kernels).
+template <Rows ROWS> using ScanAux = std::conditional_t<rows_per_slide(ROWS), const long long*, unsigned long long*>;
+__device__ __forceinline__ unsigned long long* stamps_of(unsigned long long* aux) { return aux; }
+__device__ __forceinline__ unsigned long long* stamps_of(const long long*) { return nullptr; }      // (a slide table: never stamped)
+
+// a workgroup-uniform 64-bit value into scalar registers, half by half
+__device__ __forceinline__ long long uniform_i64(long long v) {
+    return ((long long)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (unsigned int)__builtin_amdgcn_readfirstlane((int)v);
 }
 
-// SPANS (ipsx_scan_ragged_spans): the RAGGED mode with another slide lookup - workgroup b's slide is the pair
-// spans[2 * b] (first row), spans[2 * b + 1] (rows) inside the table of rows_total rows; the spans need not touch each other
-// (the blocks of a stream's logits table, IPSNet.ips_ragged_stream).  Same hand-over as ragged_slide (the pairs as `stamps`,
-// rows_total as lg_bs), the two numbers workgroup-uniform and scalar; a slide whose count is not above m, or whose span
-// leaves the table, is not touched (-> false).
-__device__ __forceinline__ bool spans_slide(const long long* spans, long long rows_total, int b, int m, int i,
-                                            long long* first, long long* n, long long* n_iter) {
-    const long long r0 = spans[2 * (size_t)b], c0 = spans[2 * (size_t)b + 1];
-    const long long lo = ((long long)__builtin_amdgcn_readfirstlane((int)(r0 >> 32)) << 32) |
-                         (unsigned int)__builtin_amdgcn_readfirstlane((int)r0);
-    const long long cnt = ((long long)__builtin_amdgcn_readfirstlane((int)(c0 >> 32)) << 32) |
-                          (unsigned int)__builtin_amdgcn_readfirstlane((int)c0);
-    *first = lo;
-    *n = cnt;
-    // (cnt < 2^31 and lo <= rows_total first: lo + cnt cannot overflow behind them)
-    if (!(lo >= 0 && lo <= rows_total && cnt > m && cnt < (1ll << 31) && lo + cnt <= rows_total)) return false;
-    *n_iter = (long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)((unsigned int)(cnt - m + i - 1) / (unsigned int)i));
-    return true;
+// iterations of a slide of n rows, m < n < 2^31: the division in 32 bits - it runs on the vector unit - and its quotient
+// back into a scalar register
+__device__ __forceinline__ long long slide_iterations(long long n, int m, int i) {
+    return (long long)(unsigned int)__builtin_amdgcn_readfirstlane((int)((unsigned int)(n - m + i - 1) / (unsigned int)i));
 }
 
-// the slide lookup of a RAGGED instantiation: row offsets, or (SPANS) pairs
-template <bool SPANS>
-__device__ __forceinline__ bool slide_of(const long long* table, long long rows_total, int b, int m, int i,
+// The front of every loop kernel, in two functions, because a kernel's argument block must not be handed to a function whole
+// (the argument loads of EVERY instantiation then compile differently) - values go in, and a kernel that takes
+// slides lends the two members the slide replaces:
+//     long long first_row = 0;
+//     if constexpr (rows_per_slide(ROWS)) {
+//         a.it0 = 0;
+//         if (!slide_of<ROWS, PLAIN>(aux, a.table_rows, b, m, i, &first_row, &a.n, &a.it1)) return;
+//     }
+//     const float* lg = image_rows<ROWS, PLAIN>(a.lg, a.n, a.table_rows, first_row, b, R);
+// PLAIN: the instantiation is neither stamped nor persistent.
+
+// Offsets / Spans: workgroup b's slide out of the one table - its first row, its rows and the iterations of its whole loop;
+// the two numbers of the table entry are workgroup-uniform and kept scalar.  A slide the caller's guarantee does not hold
+// for - Offsets: more than m rows, inside the table; Spans: a count above m, a span inside the table (the blocks of a stream's
+// logits table, IPSNet.ips_ragged_stream, need not touch each other) - is not touched (-> false).
+template <Rows ROWS, bool PLAIN>
+__device__ __forceinline__ bool slide_of(const long long* slides, long long table_rows, int b, int m, int i,
                                          long long* first, long long* n, long long* n_iter) {
-    if constexpr (SPANS) return spans_slide(table, rows_total, b, m, i, first, n, n_iter);
-    else return ragged_slide(table, rows_total, b, m, i, first, n, n_iter);
+    static_assert(rows_per_slide(ROWS) && PLAIN, "only packed logits are stamped or waited for");
+    if constexpr (ROWS == Rows::Spans) {
+        const long long r0 = slides[2 * (size_t)b], c0 = slides[2 * (size_t)b + 1];
+        const long long lo = uniform_i64(r0), cnt = uniform_i64(c0);
+        *first = lo;
+        *n = cnt;
+        // (cnt < 2^31 and lo <= table_rows first: lo + cnt cannot overflow behind them)
+        if (!(lo >= 0 && lo <= table_rows && cnt > m && cnt < (1ll << 31) && lo + cnt <= table_rows)) return false;
+        *n_iter = slide_iterations(cnt, m, i);
+    } else {
+        const long long r0 = slides[b], r1 = slides[b + 1];
+        const long long lo = uniform_i64(r0), hi = uniform_i64(r1);
+        *first = lo;
+        *n = hi - lo;
+        if (!(lo >= 0 && hi <= table_rows && hi - lo > m && hi - lo < (1ll << 31))) return false;
+        *n_iter = slide_iterations(hi - lo, m, i);
+    }
+    return true;
+}
+
+// image (slide) b's logits, R floats per row: n rows per image, table_rows between two images, or from the slide's first row on
+template <Rows ROWS, bool PLAIN, typename TR>
+__device__ __forceinline__ const float* image_rows(const float* table, long long n, TR table_rows, long long first_row, int b, int R) {
+    static_assert(ROWS == Rows::Packed || PLAIN, "only packed logits are stamped or waited for");
+    return rows_per_slide(ROWS) ? table + (size_t)first_row * R : table + (size_t)b * (ROWS == Rows::Strided ? table_rows : n) * R;
 }
 
 // ipsx_scan_range_if: the recovery launch behind a persistent loop - every workgroup looks at the word the loop sets when
@@ -1077,29 +1108,36 @@ struct TopmArgs {
     int* tie;
 };
 
-// one call of the selection loop as the C ABI hands it over (scorer.hip: scan_range_impl) to the unit whose kernel takes it
+// One call of the selection loop as the C ABI hands it over (scorer.hip: dispatch_scan) to the unit whose kernel takes it.
+// An entry point names the fields it has; what it does not name is zero / Packed.
 struct ScanCall {
-    const float* logits;
-    int b;
-    int64_t n;
-    int m, i, h, n_token;
-    int64_t it_begin, it_end;
-    int64_t* mem_idx;
-    float* mem_score;
-    int32_t* tie_flag;
-    const int32_t* ready;
-    int32_t* status;
-    void* workspace;
-    size_t workspace_bytes;
-    void* stream;
-    const int32_t* cond;
-    int32_t cond_mask;
-    int ready_stride, workgroups;
-    int64_t logits_bstride_rows;       // rows between the images' logits: n for every entry but ipsx_scan_range_strided
-    const int64_t* row_offsets;        // ipsx_scan_ragged alone: (b + 1) row offsets on the device into a packed table of
-                                       //   logits_bstride_rows rows in all; n is then the longest slide.  nullptr for every other entry
-    bool spans;                        // ipsx_scan_ragged_spans: row_offsets holds b (first row, rows) pairs instead (spans_slide)
+    const float* logits = nullptr;
+    int b = 0;
+    int64_t n = 0;                         // rows per image; Offsets / Spans: the longest slide
+    int m = 0, i = 0, h = 0, n_token = 0;
+    int64_t it_begin = 0, it_end = 0;
+    int64_t* mem_idx = nullptr;
+    float* mem_score = nullptr;
+    int32_t* tie_flag = nullptr;
+    const int32_t* ready = nullptr;        // persistent launch
+    int32_t* status = nullptr;
+    void* workspace = nullptr;
+    size_t workspace_bytes = 0;
+    void* stream = nullptr;
+    const int32_t* cond = nullptr;         // conditional launch
+    int32_t cond_mask = 0;
+    int ready_stride = 0, workgroups = 0;
+    Rows rows = Rows::Packed;              // where image b's logits lie (see Rows)
+    const int64_t* slide_table = nullptr;  // Offsets: b + 1 row offsets, Spans: b (first row, rows) pairs - on the device
+    int64_t table_rows = 0;                // Strided: rows between two images' logits; Offsets / Spans: rows of the one table
 };
+
+// the slide table as the kernels read it: the C ABI's int64_t is the kernels' `long long` (as mem_idx is) - the same 64 bits
+// under two names, converted here and nowhere else
+inline const long long* slide_entries(const ScanCall& c) {
+    static_assert(sizeof(long long) == sizeof(int64_t), "slide tables: 64-bit entries");
+    return static_cast<const long long*>(static_cast<const void*>(c.slide_table));
+}
 
 // Is this shape the LDS-resident loop's (scan_fast_kernel)?  Otherwise scan_large_kernel takes it (and needs a workspace).
 struct FastPlan {
@@ -1134,5 +1172,29 @@ unsigned long long* persist_log();     // device address of the resident loops' 
 
 inline int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 constexpr size_t kLdsLimit = 160 * 1024;
+
+// the argument block of the LDS-resident loops for this call; the launcher sets stk_off (its kernel's LDS layout) afterwards
+inline void fill_scan_args(ScanArgs& a, const ScanCall& c) {
+    a.plog = persist_log();
+    a.lg = c.logits; a.n = c.n; a.table_rows = c.table_rows; a.m = c.m; a.i = c.i; a.h = c.h; a.T = c.n_token; a.n2 = next_pow2(c.m + c.i);
+    a.it0 = c.it_begin; a.it1 = c.it_end;
+    a.mem_idx = reinterpret_cast<long long*>(c.mem_idx); a.mem_score = c.mem_score; a.tie = c.tie_flag;
+    a.ready = c.ready; a.status = c.status; a.ready_stride = c.ready_stride;
+    a.ready_words = c.ready ? (c.ready_stride ? std::min(c.b, 64) : 1) : 0;
+    a.wait_ticks = (unsigned long long)g_persist_wait_ms * 100000ull;
+    a.cond = c.cond; a.cond_mask = c.cond_mask;
+    a.slides = c.b;
+    a.tie_order = g_tie_order;
+    a.use_lds = 1;
+    a.stk_off = 0;
+}
+
+// a kernel with `lds` bytes of dynamic LDS (beyond the 64 KB a launch may ask for unannounced) onto `stream`
+template <typename T> struct as_declared { using type = T; };
+template <typename... A>
+inline void launch_lds(void (*kernel)(A...), dim3 grid, dim3 block, size_t lds, void* stream, typename as_declared<A>::type... args) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    kernel<<<grid, block, lds, as_stream(stream)>>>(args...);
+}
 
 }  // namespace ipsx

@@ -9,14 +9,11 @@
 
 namespace ipsx {
 
-// STRIDED: the images' logits lie a.lg_bs rows apart (ipsx_scan_range_strided) - an instantiation of its own, so that the
-// kernels every other entry launches are compiled from the code they always were
-// RAGGED: the third mode of that kind (ipsx_scan_ragged) - workgroup b's rows, their number and its iteration count come
-// from row_off[b], row_off[b + 1] (ragged_slide, scan_common.h: the offsets arrive as `stamps`); behind that the loop is the
-// code below, unchanged
-// SPANS (with RAGGED; ipsx_scan_ragged_spans): the slide is a (first row, rows) pair instead (spans_slide, scan_common.h)
-template <int R, int T, int EPT, int LCH, bool STAMP, bool PERSIST, bool STRIDED = false, bool RAGGED = false, bool SPANS = false>
-__global__ __launch_bounds__(SCAN_NT) void scan_fast_kernel(ScanArgs a, unsigned long long* stamps) {
+// ROWS: where image b's logits lie (Rows, scan_common.h) - an instantiation per layout, so that the kernels every other
+// entry launches are compiled from the code they always were; behind slide_rows() the loop is the code below for all of them.
+// aux: the stamp buffer (STAMP builds look at it), or the slide table of Rows::Offsets / Spans (ScanAux, scan_common.h).
+template <int R, int T, int EPT, int LCH, bool STAMP, bool PERSIST, Rows ROWS = Rows::Packed>
+__global__ __launch_bounds__(SCAN_NT) void scan_fast_kernel(ScanArgs a, ScanAux<ROWS> aux) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // prefetch registers per (prefetching) thread: 4, 5 for 32 rows x up to 512 candidates - the reference's shipped
     // Megapixel-MNIST sizes (M = I = 100, 4 tokens: a chunk is 3,200 logits for 704 prefetching threads)
@@ -59,12 +56,11 @@ __global__ __launch_bounds__(SCAN_NT) void scan_fast_kernel(ScanArgs a, unsigned
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x;
     long long first_row = 0;
-    if constexpr (RAGGED) {
+    if constexpr (rows_per_slide(ROWS)) {
         a.it0 = 0;
-        static_assert(!(RAGGED && (STAMP || PERSIST || STRIDED)), "scan_fast_kernel: RAGGED is a plain launch");
-        if (!slide_of<SPANS>(reinterpret_cast<const long long*>(stamps), a.lg_bs, b, a.m, a.i, &first_row, &a.n, &a.it1)) return;
+        if (!slide_of<ROWS, !(STAMP || PERSIST)>(aux, a.table_rows, b, a.m, a.i, &first_row, &a.n, &a.it1)) return;
     }
-    const float* lg = RAGGED ? a.lg + (size_t)first_row * R : a.lg + (size_t)b * (STRIDED ? a.lg_bs : a.n) * R;
+    const float* lg = image_rows<ROWS, !(STAMP || PERSIST)>(a.lg, a.n, a.table_rows, first_row, b, R);
     const int r = tid & (R - 1), lrow0 = tid >> log2R;
     constexpr int lstep = SCAN_NT >> log2R;
 
@@ -296,7 +292,7 @@ __global__ __launch_bounds__(SCAN_NT) void scan_fast_kernel(ScanArgs a, unsigned
             for (int j = tid; j < cnt1; j += SCAN_NT) cnew[a.m + j] = (int)(lo1 + j);
         }
         if (STAMP && tid == 0) tacc[7] += (unsigned long long)(Lr - a.m);
-        if (STAMP && PERSIST && tid == 0 && b == 0 && it < 512) stamps[8 * gridDim.x + 4 * it] = __builtin_amdgcn_s_memtime() - tlast;
+        if (STAMP && PERSIST && tid == 0 && b == 0 && it < 512) stamps_of(aux)[8 * gridDim.x + 4 * it] = __builtin_amdgcn_s_memtime() - tlast;
         FAST_STAMP(4);
         if (Lr <= 192) {                     // counting rank below the crossover of the two rankings (~200 keys)
             int P = 1;
@@ -350,11 +346,11 @@ __global__ __launch_bounds__(SCAN_NT) void scan_fast_kernel(ScanArgs a, unsigned
             const unsigned long long ts1 = STAMP ? __builtin_amdgcn_s_memtime() : 0;
             tie_order_slow(keyB, keyA, L, a.m, reinterpret_cast<int*>(smem + a.stk_off));
             if (STAMP && PERSIST && tid == 0 && b == 0) {
-                stamps[8 * gridDim.x + 2044] = ts1 - ts0;
-                stamps[8 * gridDim.x + 2045] = __builtin_amdgcn_s_memtime() - ts1;
+                stamps_of(aux)[8 * gridDim.x + 2044] = ts1 - ts0;
+                stamps_of(aux)[8 * gridDim.x + 2045] = __builtin_amdgcn_s_memtime() - ts1;
             }
         }
-        if (STAMP && PERSIST && tid == 0 && b == 0 && it < 512) { stamps[8 * gridDim.x + 4 * it + 1] = __builtin_amdgcn_s_memtime() - tlast; stamps[8 * gridDim.x + 4 * it + 2] = __builtin_amdgcn_s_memrealtime(); }
+        if (STAMP && PERSIST && tid == 0 && b == 0 && it < 512) { stamps_of(aux)[8 * gridDim.x + 4 * it + 1] = __builtin_amdgcn_s_memtime() - tlast; stamps_of(aux)[8 * gridDim.x + 4 * it + 2] = __builtin_amdgcn_s_memrealtime(); }
         FAST_STAMP(5);
         // the loads of the chunk after the next one, issued HERE - behind the ranking, not in the prep in front of it: the
         // ranking's searches reload a spilled register pair, the compiler therefore drains the vector-memory counter in
@@ -406,7 +402,7 @@ __global__ __launch_bounds__(SCAN_NT) void scan_fast_kernel(ScanArgs a, unsigned
     }
     if (a.tie && tid == 0 && tie) a.tie[b] = 1;
     if (STAMP && tid == 0)
-        for (int k = 0; k < 8; ++k) stamps[(size_t)b * 8 + k] = tacc[k];
+        for (int k = 0; k < 8; ++k) stamps_of(aux)[(size_t)b * 8 + k] = tacc[k];
 }
 
 FastPlan scan_fast_plan(int m, int i, int h, int n_token) {
@@ -425,87 +421,42 @@ FastPlan scan_fast_plan(int m, int i, int h, int n_token) {
     return p;
 }
 
-static void fill_scan_args(ScanArgs& a, const ScanCall& c) {
-    a.plog = persist_log();
-    a.lg = c.logits; a.n = c.n; a.lg_bs = c.logits_bstride_rows; a.m = c.m; a.i = c.i; a.h = c.h; a.T = c.n_token; a.n2 = next_pow2(c.m + c.i);
-    a.it0 = c.it_begin; a.it1 = c.it_end;
-    a.mem_idx = reinterpret_cast<long long*>(c.mem_idx); a.mem_score = c.mem_score; a.tie = c.tie_flag;
-    a.ready = c.ready; a.status = c.status; a.ready_stride = c.ready_stride;
-    a.ready_words = c.ready ? (c.ready_stride ? std::min(c.b, 64) : 1) : 0;
-    a.wait_ticks = (unsigned long long)g_persist_wait_ms * 100000ull;
-    a.cond = c.cond; a.cond_mask = c.cond_mask;
-    a.slides = c.b;
-    a.tie_order = g_tie_order;
-    a.use_lds = 1;
+// the five builds of one (R, T, EPT, LCH): on packed logits plain and persistent, and one per other layout (plain launches)
+template <int R, int T, int E, int C>
+static void launch_fast(const ScanCall& c, const ScanArgs& a, size_t lds, unsigned long long* st) {
+    const dim3 grid((unsigned)c.b), block(SCAN_NT);
+    switch (c.rows) {
+        case Rows::Offsets: return launch_lds(scan_fast_kernel<R, T, E, C, false, false, Rows::Offsets>, grid, block, lds, c.stream, a, slide_entries(c));
+        case Rows::Spans: return launch_lds(scan_fast_kernel<R, T, E, C, false, false, Rows::Spans>, grid, block, lds, c.stream, a, slide_entries(c));
+        case Rows::Strided: return launch_lds(scan_fast_kernel<R, T, E, C, false, false, Rows::Strided>, grid, block, lds, c.stream, a, nullptr);
+        case Rows::Packed: break;
+    }
+    launch_lds(c.ready ? scan_fast_kernel<R, T, E, C, false, true> : scan_fast_kernel<R, T, E, C, false, false>, grid, block, lds, c.stream, a, st);
 }
 
 int launch_scan_fast(const ScanCall& c, const FastPlan& fp) {
-    const int b = c.b, R = c.h * c.n_token, n_token = c.n_token;
-    void* const stream = c.stream;
+    const int R = c.h * c.n_token, ept = fp.ept, lch = fp.lch;
+    IPSX_REQUIRE(c.workgroups <= 0 || c.workgroups >= c.b, "scan_persistent_on: fewer workgroups than images only for the shapes of "
+                 "ipsx_scan_persistent_groupable");
     ScanArgs a;
     fill_scan_args(a, c);
     a.stk_off = (int)(fp.lds - STK_BYTES);
-    const size_t fast = fp.lds;
-    const int ept = fp.ept, lch = fp.lch;
-    unsigned long long* st = g_scan_stamps;
-    const bool strided = c.logits_bstride_rows != c.n;
-    const bool ragged = c.row_offsets != nullptr;           // (plain launches only: scorer.hip ipsx_scan_ragged)
-    // (the row offsets in the place of the stamps, the table's rows in a.lg_bs: ragged_slide, scan_common.h)
-    unsigned long long* const row_off = reinterpret_cast<unsigned long long*>(const_cast<int64_t*>(c.row_offsets));
-#define IPSX_LAUNCH_FAST(RR, TT, E, C, S)                                                                           \
-    do {                                                                                                            \
-        if (ragged && c.spans) {                                                                                    \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_fast_kernel<RR, TT, E, C, false, false, false, true, true>), \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast);                       \
-            scan_fast_kernel<RR, TT, E, C, false, false, false, true, true><<<dim3((unsigned)b), dim3(SCAN_NT), fast, as_stream(stream)>>>(a, row_off); \
-        } else if (ragged) {                                                                                        \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_fast_kernel<RR, TT, E, C, false, false, false, true>), \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast);                       \
-            scan_fast_kernel<RR, TT, E, C, false, false, false, true><<<dim3((unsigned)b), dim3(SCAN_NT), fast, as_stream(stream)>>>(a, row_off); \
-        } else if (a.ready) {                                                                                       \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_fast_kernel<RR, TT, E, C, false, true>),   \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast);                       \
-            scan_fast_kernel<RR, TT, E, C, false, true><<<dim3((unsigned)b), dim3(SCAN_NT), fast, as_stream(stream)>>>(a, nullptr); \
-        } else if (strided) {                                                                                       \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_fast_kernel<RR, TT, E, C, false, false, true>), \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast);                       \
-            scan_fast_kernel<RR, TT, E, C, false, false, true><<<dim3((unsigned)b), dim3(SCAN_NT), fast, as_stream(stream)>>>(a, nullptr); \
-        } else {                                                                                                    \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_fast_kernel<RR, TT, E, C, S, false>),      \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast);                       \
-            scan_fast_kernel<RR, TT, E, C, S, false><<<dim3((unsigned)b), dim3(SCAN_NT), fast, as_stream(stream)>>>(a, st); \
-        }                                                                                                           \
-        return launched("scan");                                                                                    \
-    } while (0)
-#define IPSX_LAUNCH_FAST_C(RR, TT, E)                                                                               \
-    do {                                                                                                            \
-        if (lch == 2) IPSX_LAUNCH_FAST(RR, TT, E, 2, false);                                                        \
-        else if (lch == 8) IPSX_LAUNCH_FAST(RR, TT, E, 8, false);                                                   \
-        else IPSX_LAUNCH_FAST(RR, TT, E, 16, false);                                                                \
-    } while (0)
-#define IPSX_LAUNCH_FAST_E(RR, TT)                                                                                  \
-    do {                                                                                                            \
-        if (ept == 1) IPSX_LAUNCH_FAST_C(RR, TT, 1);                                                                \
-        else if (ept == 2) IPSX_LAUNCH_FAST_C(RR, TT, 2);                                                           \
-        else if (ept == 4) IPSX_LAUNCH_FAST_C(RR, TT, 4);                                                           \
-        else IPSX_LAUNCH_FAST_C(RR, TT, 8);                                                                         \
-    } while (0)
-    IPSX_REQUIRE(c.workgroups <= 0 || c.workgroups >= b, "scan_persistent_on: fewer workgroups than images only for the shapes of "
-                 "ipsx_scan_persistent_groupable");
-    // the diagnostic (stamped) build exists for the two benchmark shapes
-    if (st && a.ready && R == 8 && n_token == 1 && ept == 4 && lch == 8) {      // stamped persistent loop (diagnostic)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_fast_kernel<8, 1, 4, 8, true, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast);
-        scan_fast_kernel<8, 1, 4, 8, true, true><<<dim3((unsigned)b), dim3(SCAN_NT), fast, as_stream(stream)>>>(a, st);
-        return launched("scan");
-    }
-    if (st && !ragged && R == 8 && n_token == 1 && ept == 4 && lch == 8) IPSX_LAUNCH_FAST(8, 1, 4, 8, true);
-    if (st && !ragged && R == 32 && n_token == 4 && ept == 4 && lch == 2) IPSX_LAUNCH_FAST(32, 4, 4, 2, true);
-    if (R == 8 && n_token == 1) IPSX_LAUNCH_FAST_E(8, 1);
-    IPSX_LAUNCH_FAST_E(32, 4);
-#undef IPSX_LAUNCH_FAST_C
-#undef IPSX_LAUNCH_FAST_E
-#undef IPSX_LAUNCH_FAST
+    unsigned long long* const st = g_scan_stamps;
+    const dim3 grid((unsigned)c.b), block(SCAN_NT);
+#define IPSX_FAST_C(RR, TT, E) (lch == 2 ? launch_fast<RR, TT, E, 2> : lch == 8 ? launch_fast<RR, TT, E, 8> : launch_fast<RR, TT, E, 16>)
+#define IPSX_FAST_E(RR, TT) \
+    (ept == 1 ? IPSX_FAST_C(RR, TT, 1) : ept == 2 ? IPSX_FAST_C(RR, TT, 2) : ept == 4 ? IPSX_FAST_C(RR, TT, 4) : IPSX_FAST_C(RR, TT, 8))
+    // the diagnostic (stamped) builds exist for the two benchmark shapes, on packed logits (stamps and any other layout: refused
+    // in scorer.hip); elsewhere the stamp buffer goes to a kernel that does not look at it
+    if (st && R == 8 && ept == 4 && lch == 8)
+        launch_lds(c.ready ? scan_fast_kernel<8, 1, 4, 8, true, true> : scan_fast_kernel<8, 1, 4, 8, true, false>, grid, block, fp.lds, c.stream, a, st);
+    else if (st && !c.ready && R == 32 && ept == 4 && lch == 2)
+        launch_lds(scan_fast_kernel<32, 4, 4, 2, true, false>, grid, block, fp.lds, c.stream, a, st);
+    else
+        (R == 8 ? IPSX_FAST_E(8, 1) : IPSX_FAST_E(32, 4))(c, a, fp.lds, st);           // (scan_fast_plan: the instantiated (R, T) pairs)
+#undef IPSX_FAST_C
+#undef IPSX_FAST_E
+    return launched("scan");
 }
 
 }  // namespace ipsx

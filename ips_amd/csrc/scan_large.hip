@@ -291,8 +291,8 @@ struct LargeArgs {
     int tie_order;
     int rstamp;            // 1: the replay's phase stamps are collected (ipsx_dbg_replay_stamps)
     int direct;            // 1: the register-resident passes for 8 heads x one token (diagnostic ipsx_dbg_scan_direct(0): off)
-    int lg_bs;             // rows between the images' logits, read by the STRIDED instantiations only (ScanArgs::lg_bs); it sits in
-                           // what was padding in front of `lg`: the struct's size and every other member's offset are unchanged
+    int table_rows;        // Rows::Strided: rows between two images' logits; Offsets / Spans: rows of the one table (fewer than 2^31
+                           // either way; ScanArgs::table_rows).  It sits in what was padding in front of `lg`
     const float* lg;       // (b, n, R)
     long long n;
     long long it0, it1;
@@ -331,8 +331,8 @@ constexpr int LARGE_U = 8;
         }                                                                          \
     } while (0)
 
-template <bool STAMP, bool STRIDED = false, bool RAGGED = false, bool SPANS = false>      // (STRIDED, RAGGED, SPANS: see scan_fast_kernel)
-__global__ __launch_bounds__(LARGE_NT) void scan_large_kernel(LargeArgs a, unsigned long long* stamps) {
+template <bool STAMP, Rows ROWS = Rows::Packed>      // (ROWS, aux: see scan_fast_kernel)
+__global__ __launch_bounds__(LARGE_NT) void scan_large_kernel(LargeArgs a, ScanAux<ROWS> aux) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int R = a.h * a.T, Lp = a.Lp, m = a.m;
     uint64_t* keys = reinterpret_cast<uint64_t*>(smem);
@@ -342,12 +342,11 @@ __global__ __launch_bounds__(LARGE_NT) void scan_large_kernel(LargeArgs a, unsig
     const int tid = threadIdx.x, b = blockIdx.x;
     constexpr int NW = LARGE_NT / 64;
     long long first_row = 0;
-    if constexpr (RAGGED) {
+    if constexpr (rows_per_slide(ROWS)) {
         a.it0 = 0;
-        static_assert(!(RAGGED && (STAMP || STRIDED)), "scan_large_kernel: RAGGED is a plain launch");
-        if (!slide_of<SPANS>(reinterpret_cast<const long long*>(stamps), a.lg_bs, b, m, a.i, &first_row, &a.n, &a.it1)) return;
+        if (!slide_of<ROWS, !STAMP>(aux, a.table_rows, b, m, a.i, &first_row, &a.n, &a.it1)) return;
     }
-    const float* lg = RAGGED ? a.lg + (size_t)first_row * R : a.lg + (size_t)b * (STRIDED ? a.lg_bs : a.n) * R;
+    const float* lg = image_rows<ROWS, !STAMP>(a.lg, a.n, a.table_rows, first_row, b, R);
     long long* mem = a.mem_idx + (size_t)b * m;
     float* xT = reinterpret_cast<float*>(a.ws + (size_t)b * a.ws_per_image);
     int* lists = reinterpret_cast<int*>(xT + (size_t)R * Lp);
@@ -686,7 +685,7 @@ __global__ __launch_bounds__(LARGE_NT) void scan_large_kernel(LargeArgs a, unsig
     }
     if (a.tie && tid == 0 && tie) a.tie[b] = 1;
     if (STAMP && tid == 0)
-        for (int k = 0; k < 8; ++k) stamps[(size_t)b * 8 + k] += tacc[k];
+        for (int k = 0; k < 8; ++k) stamps_of(aux)[(size_t)b * 8 + k] += tacc[k];
 }
 #undef LARGE_STAMP
 
@@ -750,116 +749,73 @@ int scan_large_team(int b, int m, int i, int h, int n_token) {
 int scan_large_max_l() { return LARGE_MAX_L; }
 size_t topm_large_ws_per_row(int l) { return ((size_t)2 * l * 4 + 255) & ~(size_t)255; }
 
+// the team's builds of one CPT: packed logits, strided logits, and (CPT = 2 alone: tools/scan_stamps.py largepipe) the stamped one
+template <int CPT>
+static void (*team_kernel(Rows rows, bool stamped))(LargeArgs, unsigned long long*) {
+    if constexpr (CPT == 2)
+        if (stamped) return scan_large_team_kernel<2, true>;
+    return rows == Rows::Strided ? scan_large_team_kernel<CPT, false, Rows::Strided> : scan_large_team_kernel<CPT, false>;
+}
+
 int launch_scan_large(const ScanCall& c) {
-    const float* const logits = c.logits;
-    const int b = c.b, m = c.m, i = c.i, h = c.h, n_token = c.n_token, ready_stride = c.ready_stride;
-    const int64_t n = c.n, it_begin = c.it_begin, it_end = c.it_end;
-    int64_t* const mem_idx = c.mem_idx;
-    float* const mem_score = c.mem_score;
-    int32_t* const tie_flag = c.tie_flag;
-    const int32_t* const ready = c.ready;
-    int32_t* const status = c.status;
-    void* const workspace = c.workspace;
-    const size_t workspace_bytes = c.workspace_bytes;
-    void* const stream = c.stream;
-    const int32_t* const cond = c.cond;
-    const int32_t cond_mask = c.cond_mask;
-    const int R = h * n_token, Lmax = m + i, n2 = std::max(64, next_pow2(Lmax));
-        IPSX_REQUIRE(!(ready && cond), "scan: a persistent launch is not conditional");
-        IPSX_REQUIRE(!ready || status, "scan_persistent: needs the status word");
-        IPSX_REQUIRE(Lmax <= LARGE_MAX_L, "scan: M+I = %d candidates - at most %d are supported", Lmax, LARGE_MAX_L);
-        IPSX_REQUIRE(R <= 256, "scan: H * n_token = %d > 256 not supported", R);
-        const size_t need = (size_t)b * scan_large_ws_per_image(m, i, h, n_token);
-        if (!workspace || workspace_bytes < need)
-            return fail(IPSX_EWORKSPACE, "scan: M=%d I=%d H=%d n_token=%d needs a workspace of %zu B (ipsx_scan_workspace_bytes), got %zu",
-                        m, i, h, n_token, need, workspace_bytes);
-        LargeArgs la;
-        la.plog = persist_log();
-        la.tie_order = g_tie_order;
-        la.direct = g_scan_direct ? 1 : 0;
-        la.rstamp = g_replay_stamps_on ? 1 : 0;
-        la.lg = logits; la.n = n; la.lg_bs = (int)c.logits_bstride_rows; la.it0 = it_begin; la.it1 = it_end;
-        la.m = m; la.i = i; la.h = h; la.T = n_token; la.n2 = n2; la.Lp = (Lmax + 63) & ~63;
-        la.mem_idx = reinterpret_cast<long long*>(mem_idx); la.mem_score = mem_score; la.tie = tie_flag;
-        la.ws = static_cast<unsigned char*>(workspace); la.ws_per_image = scan_large_ws_per_image(m, i, h, n_token);
-        la.ready = ready; la.status = status; la.ready_stride = ready_stride;
-        la.ready_words = ready ? (ready_stride ? std::min(b, 64) : 1) : 0;
-        la.wait_ticks = (unsigned long long)g_persist_wait_ms * 100000ull;
-        la.cond = cond; la.cond_mask = cond_mask;
-        const size_t lds = large_lds_bytes(n2, R);
-        IPSX_REQUIRE(lds <= kLdsLimit, "scan: internal - %zu B of LDS", lds);
-        // a team of workgroups per image (scan_large_team.h) - not the conditional recovery launch, which must not wait on anyone
-        if (c.row_offsets != nullptr) {                                // ipsx_scan_ragged: one workgroup per slide, never a team
-            IPSX_REQUIRE(!ready && !cond, "scan_ragged: plain launches only");
-            if (c.spans) {                                             // ipsx_scan_ragged_spans: the slides looked up in pairs (spans_slide)
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_large_kernel<false, false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                scan_large_kernel<false, false, true, true><<<dim3((unsigned)b), dim3(LARGE_NT), lds, as_stream(stream)>>>(
-                    la, reinterpret_cast<unsigned long long*>(const_cast<int64_t*>(c.row_offsets)));
-                return launched("scan");
-            }
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_large_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            // (the row offsets in the place of the stamps, the table's rows - fewer than 2^31 - in la.lg_bs: ragged_slide, scan_common.h)
-            scan_large_kernel<false, false, true><<<dim3((unsigned)b), dim3(LARGE_NT), lds, as_stream(stream)>>>(
-                la, reinterpret_cast<unsigned long long*>(const_cast<int64_t*>(c.row_offsets)));
-            return launched("scan");
+    const int R = c.h * c.n_token, Lmax = c.m + c.i, n2 = std::max(64, next_pow2(Lmax));
+    IPSX_REQUIRE(!(c.ready && c.cond), "scan: a persistent launch is not conditional");
+    IPSX_REQUIRE(!c.ready || c.status, "scan_persistent: needs the status word");
+    IPSX_REQUIRE(Lmax <= LARGE_MAX_L, "scan: M+I = %d candidates - at most %d are supported", Lmax, LARGE_MAX_L);
+    IPSX_REQUIRE(R <= 256, "scan: H * n_token = %d > 256 not supported", R);
+    const size_t need = (size_t)c.b * scan_large_ws_per_image(c.m, c.i, c.h, c.n_token);
+    if (!c.workspace || c.workspace_bytes < need)
+        return fail(IPSX_EWORKSPACE, "scan: M=%d I=%d H=%d n_token=%d needs a workspace of %zu B (ipsx_scan_workspace_bytes), got %zu",
+                    c.m, c.i, c.h, c.n_token, need, c.workspace_bytes);
+    LargeArgs la;
+    la.plog = persist_log();
+    la.tie_order = g_tie_order;
+    la.direct = g_scan_direct ? 1 : 0;
+    la.rstamp = g_replay_stamps_on ? 1 : 0;
+    la.lg = c.logits; la.n = c.n; la.table_rows = (int)c.table_rows; la.it0 = c.it_begin; la.it1 = c.it_end;
+    la.m = c.m; la.i = c.i; la.h = c.h; la.T = c.n_token; la.n2 = n2; la.Lp = (Lmax + 63) & ~63;
+    la.mem_idx = reinterpret_cast<long long*>(c.mem_idx); la.mem_score = c.mem_score; la.tie = c.tie_flag;
+    la.ws = static_cast<unsigned char*>(c.workspace); la.ws_per_image = scan_large_ws_per_image(c.m, c.i, c.h, c.n_token);
+    la.ready = c.ready; la.status = c.status; la.ready_stride = c.ready_stride;
+    la.ready_words = c.ready ? (c.ready_stride ? std::min(c.b, 64) : 1) : 0;
+    la.wait_ticks = (unsigned long long)g_persist_wait_ms * 100000ull;
+    la.cond = c.cond; la.cond_mask = c.cond_mask;
+    la.team_off = 0; la.team_ticks = 0; la.team_trunc = 0;
+    const size_t lds = large_lds_bytes(n2, R);
+    IPSX_REQUIRE(lds <= kLdsLimit, "scan: internal - %zu B of LDS", lds);
+    unsigned long long* const st = g_scan_stamps;
+    // a team of workgroups per image (scan_large_team.h) - not the conditional recovery launch, which must not wait on anyone,
+    // and not a workgroup per slide (Offsets / Spans)
+    const int W = c.cond || rows_per_slide(c.rows) ? 1 : scan_large_team(c.b, c.m, c.i, c.h, c.n_token);
+    if (W > 1 && !(st && n2 / (LARGE_NT * W) != 2)) {
+        la.team_off = large_ws_base(c.m, c.i, c.h, c.n_token);
+        la.team_ticks = la.wait_ticks * (c.ready ? 1ull : 20ull);
+        la.team_trunc = g_scan_team_trunc ? 1 : 0;
+        unsigned char* ctl0 = la.ws + la.team_off;
+        // (the counters, and the runs' words behind them: a key on its way carries its iteration's number - team_key_out)
+        if (hipMemset2DAsync(ctl0, la.ws_per_image, 0, (size_t)TEAM_CTL_INTS * 4 + (size_t)n2 * 8, (size_t)c.b, as_stream(c.stream)) != hipSuccess)
+            return fail(IPSX_EHIP, "scan: clearing the team counters: %s", hipGetErrorString(hipGetLastError()));
+        void (*k)(LargeArgs, unsigned long long*) = nullptr;
+        switch (n2 / (LARGE_NT * W)) {
+            case 1: k = team_kernel<1>(c.rows, st != nullptr); break;
+            case 2: k = team_kernel<2>(c.rows, st != nullptr); break;
+            case 4: k = team_kernel<4>(c.rows, st != nullptr); break;
+            case 8: k = team_kernel<8>(c.rows, st != nullptr); break;
+            default: return fail(IPSX_EINVAL, "scan: internal - team of %d workgroups for %d slots", W, n2);
         }
-        const int W = cond ? 1 : scan_large_team(b, m, i, h, n_token);
-        const bool strided = c.logits_bstride_rows != n && !ready && !cond;
-        if (W > 1 && !(g_scan_stamps && n2 / (LARGE_NT * W) != 2)) {
-            la.team_off = large_ws_base(m, i, h, n_token);
-            la.team_ticks = la.wait_ticks * (ready ? 1ull : 20ull);
-            la.team_trunc = g_scan_team_trunc ? 1 : 0;
-            unsigned char* ctl0 = la.ws + la.team_off;
-            // (the counters, and the runs' words behind them: a key on its way carries its iteration's number - team_key_out)
-            if (hipMemset2DAsync(ctl0, la.ws_per_image, 0, (size_t)TEAM_CTL_INTS * 4 + (size_t)n2 * 8, (size_t)b, as_stream(stream)) != hipSuccess)
-                return fail(IPSX_EHIP, "scan: clearing the team counters: %s", hipGetErrorString(hipGetLastError()));
-            const dim3 grid((unsigned)(b * W)), block(LARGE_NT);
-#define IPSX_TEAM_LAUNCH(CPT, ST)                                                                                              \
-    do {                                                                                                                        \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_large_team_kernel<CPT, ST>),                               \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                        \
-        scan_large_team_kernel<CPT, ST><<<grid, block, lds, as_stream(stream)>>>(la, ST ? g_scan_stamps : nullptr);             \
-    } while (0)
-#define IPSX_TEAM_LAUNCH_STRIDED(CPT)                                                                                          \
-    do {                                                                                                                        \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_large_team_kernel<CPT, false, true>),                      \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                        \
-        scan_large_team_kernel<CPT, false, true><<<grid, block, lds, as_stream(stream)>>>(la, nullptr);                         \
-    } while (0)
-            if (strided) {
-                switch (n2 / (LARGE_NT * W)) {
-                    case 1: IPSX_TEAM_LAUNCH_STRIDED(1); break;
-                    case 2: IPSX_TEAM_LAUNCH_STRIDED(2); break;
-                    case 4: IPSX_TEAM_LAUNCH_STRIDED(4); break;
-                    case 8: IPSX_TEAM_LAUNCH_STRIDED(8); break;
-                    default: return fail(IPSX_EINVAL, "scan: internal - team of %d workgroups for %d slots", W, n2);
-                }
-                return launched("scan");
-            }
-#undef IPSX_TEAM_LAUNCH_STRIDED
-            switch (n2 / (LARGE_NT * W)) {
-                case 1: IPSX_TEAM_LAUNCH(1, false); break;
-                case 2: if (g_scan_stamps) IPSX_TEAM_LAUNCH(2, true); else IPSX_TEAM_LAUNCH(2, false); break;
-                case 4: IPSX_TEAM_LAUNCH(4, false); break;
-                case 8: IPSX_TEAM_LAUNCH(8, false); break;
-                default: return fail(IPSX_EINVAL, "scan: internal - team of %d workgroups for %d slots", W, n2);
-            }
-#undef IPSX_TEAM_LAUNCH
-            return launched("scan");
-        }
-        if (strided) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_large_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            scan_large_kernel<false, true><<<dim3((unsigned)b), dim3(LARGE_NT), lds, as_stream(stream)>>>(la, nullptr);
-            return launched("scan");
-        }
-        if (g_scan_stamps) {                                           // diagnostic build (tools/scan_stamps.py large)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_large_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            scan_large_kernel<true><<<dim3((unsigned)b), dim3(LARGE_NT), lds, as_stream(stream)>>>(la, g_scan_stamps);
-        } else {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_large_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            scan_large_kernel<false><<<dim3((unsigned)b), dim3(LARGE_NT), lds, as_stream(stream)>>>(la, nullptr);
-        }
+        launch_lds(k, dim3((unsigned)(c.b * W)), dim3(LARGE_NT), lds, c.stream, la, st);
         return launched("scan");
+    }
+    const dim3 grid((unsigned)c.b), block(LARGE_NT);
+    switch (c.rows) {
+        case Rows::Offsets: launch_lds(scan_large_kernel<false, Rows::Offsets>, grid, block, lds, c.stream, la, slide_entries(c)); break;
+        case Rows::Spans: launch_lds(scan_large_kernel<false, Rows::Spans>, grid, block, lds, c.stream, la, slide_entries(c)); break;
+        case Rows::Strided: launch_lds(scan_large_kernel<false, Rows::Strided>, grid, block, lds, c.stream, la, nullptr); break;
+        case Rows::Packed:          // (stamped: the diagnostic build, tools/scan_stamps.py large)
+            launch_lds(st ? scan_large_kernel<true> : scan_large_kernel<false>, grid, block, lds, c.stream, la, st);
+            break;
+    }
+    return launched("scan");
 }
 
 int launch_topm_large(const TopmArgs& a, int b, void* workspace, size_t workspace_bytes, void* stream) {
@@ -868,9 +824,8 @@ int launch_topm_large(const TopmArgs& a, int b, void* workspace, size_t workspac
         return fail(IPSX_EWORKSPACE, "topm: %d candidates need a workspace of %zu B (ipsx_topm_workspace_bytes), got %zu",
                     a.L, need, workspace_bytes);
     const size_t big = large_key_bytes(a.n2) + LARGE_TAIL_BYTES;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(topm_large_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)big);
-    topm_large_kernel<<<dim3((unsigned)b), dim3(LARGE_NT), big, as_stream(stream)>>>(
-        a, static_cast<unsigned char*>(workspace), topm_large_ws_per_row(a.L));
+    launch_lds(topm_large_kernel, dim3((unsigned)b), dim3(LARGE_NT), big, stream, a, static_cast<unsigned char*>(workspace),
+               topm_large_ws_per_row(a.L));
     return launched("topm");
 }
 
@@ -878,9 +833,7 @@ int launch_topm_large(const TopmArgs& a, int b, void* workspace, size_t workspac
 
 using namespace ipsx;
 
-// Diagnostic entry point (not part of include/ipsx.h): 0 sends the shape of scan_cam_kernel (8 logits per candidate,
-// M = I = 256) through scan_fast_kernel instead - tools/scan_compare.py and tools/scan_stamps.py use it.
-// Diagnostic: read (and clear) the replay's phase stamps (g_replay_t) into out[10]
+// Diagnostic (not part of include/ipsx.h): read (and clear) the replay's phase stamps (g_replay_t) into out[10]
 extern "C" __attribute__((visibility("default"))) int ipsx_dbg_replay_stamps(unsigned long long* out) {
     unsigned long long zero[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     g_replay_stamps_on = out != nullptr;                                   // (null: off again)

@@ -305,8 +305,8 @@ __device__ __attribute__((noinline)) int team_redo(const LargeArgs& a, long long
 
 // CPT = candidates per thread: a workgroup's run is 1024 * CPT slots, the team W = n2 / (1024 * CPT) workgroups.
 // 8 heads, one token (R = 8) only - the shape scan_large_kernel's register-resident passes are written for.
-template <int CPT, bool STAMP, bool STRIDED = false>      // (STRIDED: see scan_fast_kernel)
-__global__ __launch_bounds__(LARGE_NT) void scan_large_team_kernel(LargeArgs a, unsigned long long* stamps) {
+template <int CPT, bool STAMP, Rows ROWS = Rows::Packed>      // (ROWS, aux: see scan_fast_kernel; a team never takes Offsets / Spans)
+__global__ __launch_bounds__(LARGE_NT) void scan_large_team_kernel(LargeArgs a, ScanAux<ROWS> aux) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int RUN = LARGE_NT * CPT;
     constexpr int NW = LARGE_NT / 64;
@@ -316,7 +316,8 @@ __global__ __launch_bounds__(LARGE_NT) void scan_large_team_kernel(LargeArgs a, 
     const int tail = (a.n2 + (a.n2 >> 4)) * 8 + 8 * 8;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int b = blockIdx.x / W, w = blockIdx.x - b * W;
-    const float* lg = a.lg + (size_t)b * (STRIDED ? a.lg_bs : a.n) * 8;
+    static_assert(!rows_per_slide(ROWS), "scan_large_team_kernel: a team per image, never per slide");
+    const float* lg = image_rows<ROWS, !STAMP>(a.lg, a.n, a.table_rows, 0, b, 8);
     long long* const mem_out = a.mem_idx + (size_t)b * m;
     unsigned char* wsb = a.ws + (size_t)b * a.ws_per_image;
     float* xT = reinterpret_cast<float*>(wsb);
@@ -341,7 +342,7 @@ __global__ __launch_bounds__(LARGE_NT) void scan_large_team_kernel(LargeArgs a, 
             }
         }
     }
-    if (STAMP && w == 0 && tid == 0) stamps[(size_t)gridDim.x / W * 8 + 127] = __builtin_amdgcn_s_memrealtime();
+    if (STAMP && w == 0 && tid == 0) stamps_of(aux)[(size_t)gridDim.x / W * 8 + 127] = __builtin_amdgcn_s_memrealtime();
     long long ready_known = 0;
     if (w == 0 && a.it0 == 0)
         for (int j = tid; j < m; j += LARGE_NT) mem_out[j] = j;      // (only the main workgroup's own redo reads it in iteration 0)
@@ -416,7 +417,7 @@ __global__ __launch_bounds__(LARGE_NT) void scan_large_team_kernel(LargeArgs a, 
             for (int u = 0; u < W; ++u) { pre[u] = run; run += team_count(L, u, W); }
             pre[W] = run;
             // (diagnostic build: when this iteration's rows were there, on the 100 MHz clock - tools/scan_stamps.py largepipe)
-            if (STAMP && w == 0 && it - a.it0 < 64) stamps[(size_t)gridDim.x / W * 8 + 2 * (it - a.it0)] = __builtin_amdgcn_s_memrealtime();
+            if (STAMP && w == 0 && it - a.it0 < 64) stamps_of(aux)[(size_t)gridDim.x / W * 8 + 2 * (it - a.it0)] = __builtin_amdgcn_s_memrealtime();
         }
         // ---- my candidates' 8 logits, once; row maxima of what I hold
         float4 v[CPT][2];
@@ -721,7 +722,7 @@ __global__ __launch_bounds__(LARGE_NT) void scan_large_team_kernel(LargeArgs a, 
         TEAM_STAMP(6);
         team_arrive(&ctl[TC_E]);
         TEAM_STAMP(7);
-        if (STAMP && w == 0 && tid == 0 && it - a.it0 < 64) stamps[(size_t)gridDim.x / W * 8 + 2 * (it - a.it0) + 1] = __builtin_amdgcn_s_memrealtime();
+        if (STAMP && w == 0 && tid == 0 && it - a.it0 < 64) stamps_of(aux)[(size_t)gridDim.x / W * 8 + 2 * (it - a.it0) + 1] = __builtin_amdgcn_s_memrealtime();
     }
     // ---- the end: the main workgroup sees the last iteration through (everybody's ranks written; redone if it was flagged)
     // and leaves the memory in the caller's buffer
@@ -740,7 +741,7 @@ __global__ __launch_bounds__(LARGE_NT) void scan_large_team_kernel(LargeArgs a, 
         }
     }
     if (STAMP && tid == 0)
-        for (int k = 0; k < 8; ++k) stamps[(size_t)b * 8 + k] += tacc[k];
+        for (int k = 0; k < 8; ++k) stamps_of(aux)[(size_t)b * 8 + k] += tacc[k];
 }
 #undef TEAM_STAMP
 #undef TEAM_WAIT

@@ -335,30 +335,12 @@ __global__ __launch_bounds__(mn::NT) void scan_mnist_kernel(ScanArgs a) {
 bool scan_mnist_shape(int m, int i, int h, int n_token) { return h == mn::H && n_token == mn::T && m == mn::M && i == mn::I; }
 
 int launch_scan_mnist(const ScanCall& c) {
-    IPSX_REQUIRE(scan_mnist_shape(c.m, c.i, c.h, c.n_token) && c.logits_bstride_rows == c.n && (c.workgroups <= 0 || c.workgroups >= c.b),
+    IPSX_REQUIRE(scan_mnist_shape(c.m, c.i, c.h, c.n_token) && c.rows == Rows::Packed && (c.workgroups <= 0 || c.workgroups >= c.b),
                  "scan_mnist_kernel: 8 heads x 4 tokens, M = I = 64, contiguous logits, one workgroup per image");
     ScanArgs a;
-    a.plog = persist_log();
-    a.lg = c.logits; a.n = c.n; a.lg_bs = c.logits_bstride_rows; a.m = c.m; a.i = c.i; a.h = c.h; a.T = c.n_token; a.n2 = next_pow2(c.m + c.i);
-    a.it0 = c.it_begin; a.it1 = c.it_end;
-    a.mem_idx = reinterpret_cast<long long*>(c.mem_idx); a.mem_score = c.mem_score; a.tie = c.tie_flag;
-    a.ready = c.ready; a.status = c.status; a.ready_stride = c.ready_stride;
-    a.ready_words = c.ready ? (c.ready_stride ? std::min(c.b, 64) : 1) : 0;
-    a.wait_ticks = (unsigned long long)g_persist_wait_ms * 100000ull;
-    a.cond = c.cond; a.cond_mask = c.cond_mask;
-    a.slides = c.b;
-    a.tie_order = g_tie_order;
-    a.use_lds = 1;
+    fill_scan_args(a, c);
     a.stk_off = mn::OFF_STK;
-    if (a.ready) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_mnist_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)mn::LDS_BYTES);
-        scan_mnist_kernel<true><<<dim3((unsigned)c.b), dim3(mn::NT), mn::LDS_BYTES, as_stream(c.stream)>>>(a);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(scan_mnist_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)mn::LDS_BYTES);
-        scan_mnist_kernel<false><<<dim3((unsigned)c.b), dim3(mn::NT), mn::LDS_BYTES, as_stream(c.stream)>>>(a);
-    }
+    launch_lds(c.ready ? scan_mnist_kernel<true> : scan_mnist_kernel<false>, dim3((unsigned)c.b), dim3(mn::NT), mn::LDS_BYTES, c.stream, a);
     return launched("scan");
 }
 

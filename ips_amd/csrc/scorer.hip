@@ -57,6 +57,57 @@ unsigned long long* persist_log() {
     return p[dev];
 }
 
+// What every entry point of the loop has, in the order the C ABI names it; what an entry has beyond that it names itself.
+static ScanCall scan_call(const float* logits, int b, int64_t n, int m, int i, int h, int n_token, int64_t* mem_idx,
+                          float* mem_score, int32_t* tie_flag, void* stream) {
+    ScanCall c;
+    c.logits = logits; c.b = b; c.n = n; c.m = m; c.i = i; c.h = h; c.n_token = n_token;
+    c.mem_idx = mem_idx; c.mem_score = mem_score; c.tie_flag = tie_flag; c.stream = stream;
+    return c;
+}
+
+// the whole loop over n rows (callers have checked n > m, i > 0)
+static void whole_loop(ScanCall& c) { c.it_begin = 0; c.it_end = (c.n - c.m + c.i - 1) / c.i; }
+
+// THE check of a call before any launcher sees it: the sizes and the iteration range, and the combinations no kernel is
+// built for - without this they would be served as if the logits were packed.  (No entry point builds one of those today.)
+static int validate_scan_call(const ScanCall& c) {
+    IPSX_REQUIRE(c.logits && c.mem_idx, "scan: null pointer");
+    IPSX_REQUIRE(c.b > 0 && c.m > 0 && c.i > 0 && c.h > 0 && c.n_token > 0, "scan: bad sizes");
+    IPSX_REQUIRE(c.n > c.m, "scan: needs more patches (%lld) than memory slots (%d)", (long long)c.n, c.m);
+    IPSX_REQUIRE(c.n < ((int64_t)1 << 31), "scan: too many patches");
+    IPSX_REQUIRE(c.it_begin >= 0 && c.it_begin <= c.it_end && c.it_end <= (c.n - c.m + c.i - 1) / c.i,
+                 "scan: iteration range [%lld, %lld) outside the loop", (long long)c.it_begin, (long long)c.it_end);
+    if (c.rows == Rows::Packed) return IPSX_OK;
+    IPSX_REQUIRE(!c.ready && !c.cond && !g_scan_stamps,
+                 "scan: only packed logits are waited for (persistent), launched conditionally or stamped");
+    IPSX_REQUIRE(c.table_rows > 0 && c.table_rows < ((int64_t)1 << 31), "scan: a table of %lld rows", (long long)c.table_rows);
+    if (rows_per_slide(c.rows)) {
+        IPSX_REQUIRE(c.slide_table, "scan: slides without their table");
+        IPSX_REQUIRE(c.workgroups <= 0 || c.workgroups >= c.b, "scan: slides of different lengths take a workgroup each");
+    }
+    return IPSX_OK;
+}
+
+// THE kernel choice of every entry point.
+static int dispatch_scan(const ScanCall& c) {
+    IPSX_TRY(validate_scan_call(c));
+    if (c.it_begin == c.it_end) return IPSX_OK;
+    const FastPlan fp = scan_fast_plan(c.m, c.i, c.h, c.n_token);
+    // every shape the LDS-resident loops do not cover - other head / token counts, candidate sets beyond the LDS (the
+    // reference's shipped CAMELYON configuration: M = I = 5000): scan_large_kernel (forced generic: plain launches only)
+    if (!fp.ok || (g_scan_generic && !c.ready && !c.cond)) return launch_scan_large(c);
+    // BASELINE configs[3] (8 heads, one token, M = I = 256): the specialised loop
+    if (g_scan_r8 && scan_cam_shape(c.m, c.i, c.h, c.n_token)) return launch_scan_cam(c);
+    // BASELINE configs[1] / [2] (8 heads, 4 tokens, M = I = 64): the specialised loop - plain, conditional and persistent
+    // launches of one workgroup per image on packed logits; every other layout (never a ragged call, then) and the stamped
+    // diagnostic build stay on scan_fast_kernel
+    if (g_scan_mnist && scan_mnist_shape(c.m, c.i, c.h, c.n_token) && c.rows == Rows::Packed &&
+        (c.workgroups <= 0 || c.workgroups >= c.b) && g_scan_stamps == nullptr)
+        return launch_scan_mnist(c);
+    return launch_scan_fast(c, fp);
+}
+
 }  // namespace ipsx
 
 using namespace ipsx;
@@ -71,17 +122,13 @@ IPSX_API int ipsx_scan(const float* logits, int b, int64_t n, int m, int i, int 
                            workspace, workspace_bytes, stream);
 }
 
-static int scan_range_impl(const float* logits, int b, int64_t n, int m, int i, int h, int n_token,
-                           int64_t it_begin, int64_t it_end, int64_t* mem_idx, float* mem_score,
-                           int32_t* tie_flag, const int32_t* ready, int32_t* status, void* workspace,
-                           size_t workspace_bytes, void* stream, const int32_t* cond = nullptr, int32_t cond_mask = 0,
-                           int ready_stride = 0, int workgroups = 0, int64_t logits_bstride_rows = -1);
-
 IPSX_API int ipsx_scan_range(const float* logits, int b, int64_t n, int m, int i, int h, int n_token,
                              int64_t it_begin, int64_t it_end, int64_t* mem_idx, float* mem_score,
                              int32_t* tie_flag, void* workspace, size_t workspace_bytes, void* stream) {
-    return scan_range_impl(logits, b, n, m, i, h, n_token, it_begin, it_end, mem_idx, mem_score, tie_flag, nullptr, nullptr,
-                           workspace, workspace_bytes, stream);
+    ScanCall c = scan_call(logits, b, n, m, i, h, n_token, mem_idx, mem_score, tie_flag, stream);
+    c.it_begin = it_begin; c.it_end = it_end;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    return dispatch_scan(c);
 }
 
 // ipsx_scan_range on logits that sit in a table of fixed capacity: image k's rows start k * logits_bstride_rows rows behind
@@ -92,12 +139,18 @@ IPSX_API int ipsx_scan_range_strided(const float* logits, int64_t logits_bstride
     IPSX_REQUIRE(logits_bstride_rows >= n && logits_bstride_rows < ((int64_t)1 << 31),
                  "scan_range_strided: %lld rows between the images hold %lld candidates (fewer than 2^31)",
                  (long long)logits_bstride_rows, (long long)n);
-    return scan_range_impl(logits, b, n, m, i, h, n_token, it_begin, it_end, mem_idx, mem_score, tie_flag, nullptr, nullptr,
-                           workspace, workspace_bytes, stream, nullptr, 0, 0, 0, logits_bstride_rows);
+    ScanCall c = scan_call(logits, b, n, m, i, h, n_token, mem_idx, mem_score, tie_flag, stream);
+    c.it_begin = it_begin; c.it_end = it_end;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    if (logits_bstride_rows != n) {                        // (a full table is packed logits: every kernel of ipsx_scan_range)
+        c.rows = Rows::Strided;
+        c.table_rows = logits_bstride_rows;
+    }
+    return dispatch_scan(c);
 }
 
 // ipsx_scan on slides of different lengths: slide k's logits are rows [row_offsets[k], row_offsets[k + 1]) of ONE packed
-// (total, R) table, the offsets b + 1 int64 on the device.  One plain launch of one workgroup per slide - the RAGGED
+// (total, R) table, the offsets b + 1 int64 on the device.  One plain launch of one workgroup per slide - the Rows::Offsets
 // instantiation of the loop kernel the shape takes (never scan_mnist_kernel, never a team) -, each replaying the loop of
 // ipsx_scan for its slide alone: mem_idx (b, m) is slide-local.  n_max (the longest slide) and total are the caller's
 // host-side knowledge; every slide has more than m rows (a slide that has not, or that leaves the table, is left untouched).
@@ -111,17 +164,16 @@ IPSX_API int ipsx_scan_ragged(const float* logits, const int64_t* row_offsets, i
                  "scan_ragged: %lld rows in all (fewer than 2^31) for %d slides of at most %lld", (long long)total, b, (long long)n_max);
     if (tie_flag && hipMemsetAsync(tie_flag, 0, sizeof(int32_t) * (size_t)b, as_stream(stream)) != hipSuccess)
         return fail(IPSX_EHIP, "scan_ragged: memset failed");
-    const FastPlan fp = scan_fast_plan(m, i, h, n_token);
-    ScanCall c = {logits, b, n_max, m, i, h, n_token, 0, (n_max - m + i - 1) / i, mem_idx, mem_score, tie_flag, nullptr, nullptr,
-                  workspace, workspace_bytes, stream, nullptr, 0, 0, 0, total, row_offsets};
-    if (!fp.ok || g_scan_generic) return launch_scan_large(c);
-    if (g_scan_r8 && scan_cam_shape(m, i, h, n_token)) return launch_scan_cam(c);
-    return launch_scan_fast(c, fp);
+    ScanCall c = scan_call(logits, b, n_max, m, i, h, n_token, mem_idx, mem_score, tie_flag, stream);
+    whole_loop(c);
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    c.rows = Rows::Offsets; c.slide_table = row_offsets; c.table_rows = total;
+    return dispatch_scan(c);
 }
 
 // ipsx_scan_ragged on slides that lie anywhere in ONE (rows_total, R) table: spans (b, 2) int64 on the device, slide k's first
 // row and row count (the blocks of a ragged stream's logits table, IPSNet.ips_ragged_stream: the counts change from feed to
-// feed, the blocks do not move).  The SPANS instantiation of the loop kernel the shape takes, one workgroup per slide; a
+// feed, the blocks do not move).  The Rows::Spans instantiation of the loop kernel the shape takes, one workgroup per slide; a
 // slide whose count is not above m, or whose span leaves the table, is left untouched in all three outputs - tie_flag
 // included, so nothing is cleared here.  n_max: the caller's bound on the counts (dispatch and the < 2^31 checks only).
 IPSX_API int ipsx_scan_ragged_spans(const float* logits, const int64_t* spans, int b, int64_t n_max, int64_t rows_total, int m,
@@ -132,12 +184,11 @@ IPSX_API int ipsx_scan_ragged_spans(const float* logits, const int64_t* spans, i
     IPSX_REQUIRE(n_max > m, "scan_ragged_spans: needs more patches per slide (longest: %lld) than memory slots (%d)", (long long)n_max, m);
     IPSX_REQUIRE(rows_total >= n_max && rows_total < ((int64_t)1 << 31),
                  "scan_ragged_spans: a table of %lld rows (fewer than 2^31) for slides of at most %lld", (long long)rows_total, (long long)n_max);
-    const FastPlan fp = scan_fast_plan(m, i, h, n_token);
-    ScanCall c = {logits, b, n_max, m, i, h, n_token, 0, (n_max - m + i - 1) / i, mem_idx, mem_score, tie_flag, nullptr, nullptr,
-                  workspace, workspace_bytes, stream, nullptr, 0, 0, 0, rows_total, spans, true};
-    if (!fp.ok || g_scan_generic) return launch_scan_large(c);
-    if (g_scan_r8 && scan_cam_shape(m, i, h, n_token)) return launch_scan_cam(c);
-    return launch_scan_fast(c, fp);
+    ScanCall c = scan_call(logits, b, n_max, m, i, h, n_token, mem_idx, mem_score, tie_flag, stream);
+    whole_loop(c);
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    c.rows = Rows::Spans; c.slide_table = spans; c.table_rows = rows_total;
+    return dispatch_scan(c);
 }
 
 IPSX_API size_t ipsx_scan_workspace_bytes(int b, int m, int i, int h, int n_token) {
@@ -167,8 +218,10 @@ IPSX_API int ipsx_scan_persistent(const float* logits, int b, int64_t n, int m, 
     IPSX_REQUIRE(ready && status, "scan_persistent: needs the progress word(s) and the status word");
     IPSX_REQUIRE(n > m && i > 0, "scan: needs more patches (%lld) than memory slots (%d)", (long long)n, m);
     IPSX_REQUIRE(ipsx_scan_persistent_supported(m, i, h, n_token), "scan_persistent: shape not covered (use ipsx_scan_range)");
-    return scan_range_impl(logits, b, n, m, i, h, n_token, 0, (n - m + i - 1) / i, mem_idx, mem_score, tie_flag, ready, status,
-                           nullptr, 0, stream, nullptr, 0, ready_per_image ? 1 : 0);
+    ScanCall c = scan_call(logits, b, n, m, i, h, n_token, mem_idx, mem_score, tie_flag, stream);
+    whole_loop(c);
+    c.ready = ready; c.ready_stride = ready_per_image ? 1 : 0; c.status = status;
+    return dispatch_scan(c);
 }
 
 IPSX_API int ipsx_scan_persistent_groupable(int m, int i, int h, int n_token) {
@@ -181,8 +234,11 @@ IPSX_API int ipsx_scan_persistent_on(const float* logits, int b, int64_t n, int 
     IPSX_REQUIRE(ready && status, "scan_persistent: needs the progress word(s) and the status word");
     IPSX_REQUIRE(n > m && i > 0, "scan: needs more patches (%lld) than memory slots (%d)", (long long)n, m);
     IPSX_REQUIRE(ipsx_scan_persistent_supported(m, i, h, n_token), "scan_persistent: shape not covered (use ipsx_scan_range)");
-    return scan_range_impl(logits, b, n, m, i, h, n_token, 0, (n - m + i - 1) / i, mem_idx, mem_score, tie_flag, ready, status,
-                           nullptr, 0, stream, nullptr, 0, ready_per_image ? 1 : 0, workgroups);
+    ScanCall c = scan_call(logits, b, n, m, i, h, n_token, mem_idx, mem_score, tie_flag, stream);
+    whole_loop(c);
+    c.ready = ready; c.ready_stride = ready_per_image ? 1 : 0; c.status = status;
+    c.workgroups = workgroups;
+    return dispatch_scan(c);
 }
 
 // The persistent loop for EVERY shape ipsx_scan covers - candidate sets beyond the LDS take the workspace of ipsx_scan
@@ -194,8 +250,12 @@ IPSX_API int ipsx_scan_persistent_ws(const float* logits, int b, int64_t n, int 
                                      size_t workspace_bytes, void* stream) {
     IPSX_REQUIRE(ready && status, "scan_persistent: needs the progress word(s) and the status word");
     IPSX_REQUIRE(n > m && i > 0, "scan: needs more patches (%lld) than memory slots (%d)", (long long)n, m);
-    return scan_range_impl(logits, b, n, m, i, h, n_token, 0, (n - m + i - 1) / i, mem_idx, mem_score, tie_flag, ready, status,
-                           workspace, workspace_bytes, stream, nullptr, 0, ready_per_image ? 1 : 0, workgroups);
+    ScanCall c = scan_call(logits, b, n, m, i, h, n_token, mem_idx, mem_score, tie_flag, stream);
+    whole_loop(c);
+    c.ready = ready; c.ready_stride = ready_per_image ? 1 : 0; c.status = status;
+    c.workgroups = workgroups;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    return dispatch_scan(c);
 }
 
 IPSX_API int ipsx_scan_range_if_ws(const float* logits, int b, int64_t n, int m, int i, int h, int n_token,
@@ -203,8 +263,11 @@ IPSX_API int ipsx_scan_range_if_ws(const float* logits, int b, int64_t n, int m,
                                    int32_t* tie_flag, const int32_t* cond, int32_t cond_mask, void* workspace,
                                    size_t workspace_bytes, void* stream) {
     IPSX_REQUIRE(cond && cond_mask, "scan_range_if: needs the condition word and a mask");
-    return scan_range_impl(logits, b, n, m, i, h, n_token, it_begin, it_end, mem_idx, mem_score, tie_flag, nullptr, nullptr,
-                           workspace, workspace_bytes, stream, cond, cond_mask);
+    ScanCall c = scan_call(logits, b, n, m, i, h, n_token, mem_idx, mem_score, tie_flag, stream);
+    c.it_begin = it_begin; c.it_end = it_end;
+    c.cond = cond; c.cond_mask = cond_mask;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes;
+    return dispatch_scan(c);
 }
 
 // one thread that holds its stream until every workgroup of the persistent scan is resident (bounded: ~0.5 s)
@@ -270,37 +333,10 @@ IPSX_API int ipsx_scan_range_if(const float* logits, int b, int64_t n, int m, in
                                 int32_t* tie_flag, const int32_t* cond, int32_t cond_mask, void* stream) {
     IPSX_REQUIRE(cond && cond_mask, "scan_range_if: needs the condition word and a mask");
     IPSX_REQUIRE(scan_fast_plan(m, i, h, n_token).ok, "scan_range_if: shapes of the LDS-resident loop only");
-    return scan_range_impl(logits, b, n, m, i, h, n_token, it_begin, it_end, mem_idx, mem_score, tie_flag, nullptr, nullptr,
-                           nullptr, 0, stream, cond, cond_mask);
-}
-
-static int scan_range_impl(const float* logits, int b, int64_t n, int m, int i, int h, int n_token,
-                           int64_t it_begin, int64_t it_end, int64_t* mem_idx, float* mem_score,
-                           int32_t* tie_flag, const int32_t* ready, int32_t* status, void* workspace,
-                           size_t workspace_bytes, void* stream, const int32_t* cond, int32_t cond_mask, int ready_stride,
-                           int workgroups, int64_t logits_bstride_rows) {
-    IPSX_REQUIRE(logits && mem_idx, "scan: null pointer");
-    IPSX_REQUIRE(b > 0 && m > 0 && i > 0 && h > 0 && n_token > 0, "scan: bad sizes");
-    IPSX_REQUIRE(n > m, "scan: needs more patches (%lld) than memory slots (%d)", (long long)n, m);
-    IPSX_REQUIRE(n < ((int64_t)1 << 31), "scan: too many patches");
-    IPSX_REQUIRE(it_begin >= 0 && it_begin <= it_end && it_end <= (n - m + i - 1) / i,
-                 "scan: iteration range [%lld, %lld) outside the loop", (long long)it_begin, (long long)it_end);
-    if (it_begin == it_end) return IPSX_OK;
-    const FastPlan fp = scan_fast_plan(m, i, h, n_token);
-    ScanCall c = {logits, b, n, m, i, h, n_token, it_begin, it_end, mem_idx, mem_score, tie_flag, ready, status, workspace,
-                  workspace_bytes, stream, cond, cond_mask, ready_stride, workgroups, logits_bstride_rows < 0 ? n : logits_bstride_rows};
-    // every shape the LDS-resident loops do not cover - other head / token counts, candidate sets beyond the LDS (the
-    // reference's shipped CAMELYON configuration: M = I = 5000): scan_large_kernel (forced generic: plain launches only)
-    if (!fp.ok || (g_scan_generic && !ready && !cond)) return launch_scan_large(c);
-    // BASELINE configs[3] (8 heads, one token, M = I = 256): the specialised loop
-    if (g_scan_r8 && scan_cam_shape(m, i, h, n_token)) return launch_scan_cam(c);
-    // BASELINE configs[1] / [2] (8 heads, 4 tokens, M = I = 64): the specialised loop - plain, conditional and persistent
-    // launches of one workgroup per image on contiguous logits; strided logits (ipsx_scan_range_strided) and the stamped
-    // diagnostic build stay on scan_fast_kernel
-    if (g_scan_mnist && scan_mnist_shape(m, i, h, n_token) && c.logits_bstride_rows == n && (workgroups <= 0 || workgroups >= b) &&
-        g_scan_stamps == nullptr)
-        return launch_scan_mnist(c);
-    return launch_scan_fast(c, fp);
+    ScanCall c = scan_call(logits, b, n, m, i, h, n_token, mem_idx, mem_score, tie_flag, stream);
+    c.it_begin = it_begin; c.it_end = it_end;
+    c.cond = cond; c.cond_mask = cond_mask;
+    return dispatch_scan(c);
 }
 
 IPSX_API int ipsx_set_persistent_wait_ms(int ms) {
@@ -315,8 +351,6 @@ IPSX_API int ipsx_set_tie_order(int mode) {
     return prev;
 }
 
-// Diagnostic entry point (not part of include/ipsx.h): when set to a device buffer of b*8 uint64, the next
-// resident scans accumulate per-phase s_memtime cycles there (tools/scan_stamps.py); NULL switches it off.
 // Diagnostic (not part of include/ipsx.h): copies g_persist_log to out8 (host memory) and clears it; synchronises the device
 extern "C" __attribute__((visibility("default"))) int ipsx_dbg_persist_log(unsigned long long* out8) {
     unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -324,6 +358,8 @@ extern "C" __attribute__((visibility("default"))) int ipsx_dbg_persist_log(unsig
     return hipMemcpyToSymbol(HIP_SYMBOL(ipsx::g_persist_log), zero, sizeof(zero)) == hipSuccess ? 0 : -1;
 }
 
+// Diagnostic entry point (not part of include/ipsx.h): when set to a device buffer of b*8 uint64, the next
+// resident scans accumulate per-phase s_memtime cycles there (tools/scan_stamps.py); NULL switches it off.
 extern "C" __attribute__((visibility("default"))) void ipsx_dbg_scan_stamps(unsigned long long* buf) {
     ipsx::g_scan_stamps = buf;
 }
@@ -337,6 +373,8 @@ extern "C" __attribute__((visibility("default"))) void ipsx_dbg_scan_direct(int 
 extern "C" __attribute__((visibility("default"))) void ipsx_dbg_scan_team(int w) { g_scan_team = w; }
 // Diagnostic: 0 = the team's ranking always from whole runs (the path taken when the runs' top halves are not provably enough)
 extern "C" __attribute__((visibility("default"))) void ipsx_dbg_scan_team_trunc(int on) { g_scan_team_trunc = on != 0; }
+// Diagnostic: 0 sends the shape of scan_cam_kernel (8 logits per candidate, M = I = 256) through scan_fast_kernel instead -
+// tools/scan_compare.py and tools/scan_stamps.py use it.
 extern "C" __attribute__((visibility("default"))) void ipsx_dbg_scan_r8(int on) { g_scan_r8 = on != 0; }
 // Diagnostic: 0 sends the shape of scan_mnist_kernel (8 heads, 4 tokens, M = I = 64) through scan_fast_kernel (tools/scan_compare.py,
 // tests/test_scan_mnist.py, the A/B measurements); ipsx_dbg_scan_mnist_shape is the dispatcher's shape predicate

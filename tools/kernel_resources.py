@@ -21,7 +21,14 @@ for src in sorted(f for f in os.listdir(CSRC) if f.endswith(".hip")):
                          r".*?\.sgpr_count:\s+(\d+).*?\.sgpr_spill_count:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", text, re.S):
         agpr, lds, name, scratch, sgpr, sspill, vgpr, vspill = m.groups()
         dem = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
-        dem = re.sub(r"\(.*", "", dem).replace("void ", "").replace("ipsx::", "")
+        # (the parameter list goes: the last top-level bracket - a template argument such as (ipsx::Rows)0 has brackets too)
+        depth, cut = 0, len(dem)
+        for k in range(len(dem) - 1, -1, -1):
+            depth += (dem[k] == ")") - (dem[k] == "(")
+            if depth == 0:
+                cut = k if dem[k] == "(" else len(dem)
+                break
+        dem = dem[:cut].replace("void ", "").replace("ipsx::", "")
         rows.append((src, dem, int(vgpr), int(agpr), int(vspill), int(scratch), int(sgpr), int(sspill), int(lds)))
 print("%-18s %-64s %5s %5s %7s %8s %5s %7s %7s" % ("file", "kernel", "vgpr", "agpr", "v-spill", "scratchB", "sgpr", "s-spill", "ldsB"))
 for r in rows:
