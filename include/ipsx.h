@@ -118,7 +118,11 @@ extern "C" {
  *         short slides in the order given, zero padding, indices and global rows (an addition, the minor number stays);
  *         ipsx_scan_ragged_spans, ipsx_stream_commit_ragged - slides of different lengths fed in pieces
  *         (IPSNet.ips_ragged_stream): ipsx_scan_ragged on slides that lie anywhere in one logits table, and ipsx_stream_commit
- *         with per-slide numbers read from a device table (additions, the minor number stays) */
+ *         with per-slide numbers read from a device table (additions, the minor number stays);
+ *         ipsx_image_entry, ipsx_ragged_view (structs), ipsx_ragged_view_fill, ipsx_ragged_view_offset,
+ *         ipsx_trunk_ragged_view_supported, ipsx_trunk_encode_ragged_view, ipsx_ragged_finish_view - whole images of
+ *         different sizes in one call (IPSNet.ips_image_ragged): the patch-grid view with where a patch lies and its
+ *         pitches read per patch from a table, and the end of such a call in one launch (additions, the minor number stays) */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -798,6 +802,60 @@ int ipsx_ips_finish_indexed(const void* patches, int64_t patch_row_bytes, int64_
 int ipsx_ragged_finish(const void* rows, int64_t row_bytes, int64_t total, const int64_t* row_offsets,
                        const int64_t* mem_idx, const int32_t* flat, const void* pos, int64_t pos_row_bytes, int b, int m,
                        void* mem_patch, void* mem_pos, int64_t* mem_idx_out, int64_t* rows_out, void* stream);
+
+/* 3.06: the RAGGED patch-grid view (IPSNet.ips_image_ragged).  Whole float32 images of DIFFERENT sizes, (c, h_k, w_k) each,
+ * packed into ONE buffer; the patches of all of them numbered one image after the other ("packed patches"), each image's
+ * grid in the order of ipsx_patch_view.  One table entry per image: elem_off its first element inside the buffer, first its
+ * first packed patch number, ny = (h - ph) / sh + 1, nx = (w - pw) / sw + 1.  Packed patch p belongs to the image k with the
+ * largest first <= p and is grid patch p - first of it: it starts at element elem_off + (py * sh) * w + px * sw, its row
+ * pitch is w, its channel pitch h * w. */
+typedef struct ipsx_image_entry {
+    int64_t elem_off;
+    int64_t first;
+    int32_t h, w, ny, nx;
+} ipsx_image_entry;
+
+typedef struct ipsx_ragged_view {
+    int b, c, ph, pw, sh, sw;
+    const ipsx_image_entry* images;      /* DEVICE: the table of b entries the kernels read */
+    const ipsx_image_entry* host;        /* HOST: the same table, as ipsx_ragged_view_fill left it - every entry point checks
+                                          * it again and takes the patch count and the launch's load width from it */
+} ipsx_ragged_view;
+
+/* host: fills table[0 .. b) from the images' (h[k], w[k], elem_off[k]) and checks it - every field positive (elem_off[0] >=
+ * 0), ph <= h, pw <= w, offsets increasing, no image reaching into the next (elem_off[k] + c * h * w <= elem_off[k + 1]),
+ * fewer than 2^31 patches in all.  Returns the total patch count, or -1 (ipsx_last_error says why; the table is then not to
+ * be used). */
+int64_t ipsx_ragged_view_fill(ipsx_image_entry* table, int b, int c, int ph, int pw, int sh, int sw, const int32_t* h,
+                              const int32_t* w, const int64_t* elem_off);
+/* host: element offset of packed patch p's (0, 0, 0) inside the packed buffer, its row pitch in *pitch and its channel pitch
+ * in *chan_pitch (either may be NULL); -1 for a p outside [0, total) or an invalid table.  `geometry`: the view (b, c, patch,
+ * stride; its table pointers are not read - `table` is).  The kernels compute their addresses by the same function. */
+int64_t ipsx_ragged_view_offset(const ipsx_image_entry* table, int b, const ipsx_ragged_view* geometry, int64_t p,
+                                int64_t* pitch, int64_t* chan_pitch);
+/* 1 when ipsx_trunk_encode_ragged_view takes this trunk and view: what ipsx_trunk_view_supported asks of the trunk and the
+ * patch shape, and a valid host table */
+int ipsx_trunk_ragged_view_supported(const ipsx_trunk* t, const ipsx_ragged_view* view);
+/* emb row j (j < n) = the embedding of packed patch index[j] (device int32), or of packed patch first + j when index is NULL:
+ * bit for bit ipsx_trunk_encode of those patches copied out of their images - the stems' staging code is the view's, only
+ * where a patch's first pixel lies and its two pitches are per patch.  A list entry that is no packed patch reads packed
+ * patch 0, never outside the buffer.  The load width is picked per launch from the HOST table: the kernel's wide load when
+ * `pixels`, every elem_off, every w and sw are multiples of it, dword loads otherwise.  Plain launches only (no counted
+ * launch, no dedup, no uint8).  workspace: as ipsx_trunk_encode. */
+int ipsx_trunk_encode_ragged_view(const ipsx_trunk* t, const float* pixels, const ipsx_ragged_view* view,
+                                  const int32_t* index /* NULL: packed patches first .. first+n-1 */, int64_t first, int64_t n,
+                                  float* emb, void* workspace, size_t workspace_bytes, void* stream);
+/* ipsx_ragged_finish with the source row replaced by a grid patch copied out of its image, grid (m, b).  row_offsets: (b + 1)
+ * int64 on the device, the packed patch numbers (entry k = images[k].first, entry b the total); mem_idx, flat, pos and the
+ * four outputs as there, mem_patch (b, m, c, ph, pw) float32.  Image k with n = ny * nx patches:
+ *   n > m:   slot j takes local patch r = clamp(mem_idx[k][j], 0, n - 1);
+ *   n <= m:  slot j < n takes r = j; slots j >= n are WRITTEN as zeros (patch and positional row), index and row -1.
+ * The patch copied is grid patch (flat ? flat[g] : g) - a packed number, clamped into [0, total) - with g = first + r;
+ * mem_pos[k][j] = pos[g], mem_idx_out[k][j] = r, rows_out[k][j] = g.  16-byte copies where pw, every w, sw and the addresses
+ * allow (the host table decides), dwords otherwise.  No read leaves the packed buffer. */
+int ipsx_ragged_finish_view(const float* pixels, const ipsx_ragged_view* view, const int64_t* row_offsets, const int64_t* mem_idx,
+                            int m, const int32_t* flat, const void* pos, int64_t pos_row_bytes, void* mem_patch, void* mem_pos,
+                            int64_t* mem_idx_out, int64_t* rows_out, void* stream);
 
 /* 3.06: the state update of a stream (IPSNet.ips_stream) as ONE launch, for up to four tables at once (patch rows,
  * embeddings, logits, global ids).  The n_cand candidates of a table are two segments that are never joined: its first

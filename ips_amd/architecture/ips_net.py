@@ -34,6 +34,7 @@ from torch import nn
 
 from .. import hip
 from ..ragged import Ragged
+from ..ragged_image import RaggedImages
 from ..shuffle import draw_shuffle, shuffle_batch, shuffle_instance
 from .resnet import load_torchvision_checkpoint, resnet18_trunk, resnet50_trunk
 from .transformer import Transformer, pos_enc_1d
@@ -436,7 +437,12 @@ class IPSNet(nn.Module):
         (B, N, C, ph, pw) tensor, a multiple of the images when patches overlap, is never made.  Where the view is not
         supported (other stems and precisions, blank-patch dedup, a CPU device, an encoder in training mode, an overridden
         ``do_shuffle``, other image types, M >= N) the patch tensor is materialised - uint8 images: as uint8 patches - and
-        ``ips()`` runs as ever, refusing what it refuses."""
+        ``ips()`` runs as ever, refusing what it refuses.
+
+        An ``ips_amd.ragged_image.RaggedImages`` (images of different sizes, e.g. from a loader with
+        ``collate_ragged_images``) goes to ``ips_image_ragged``, with its ``pad`` flag."""
+        if isinstance(images, RaggedImages):
+            return self.ips_image_ragged(images, patch_size, patch_stride, pad=images.pad)
         if not self.is_image or images.dim() != 4:
             raise TypeError("ips_image takes (B, C, H, W) images of an image encoder")
         table = self._table_for(images)    # (uint8 without a table: the error uint8 patches raise)
@@ -450,6 +456,28 @@ class IPSNet(nn.Module):
         if view is None:
             return self.ips(self._materialise(images, patch_size, patch_stride))
         return self._call(hip.PatchSource(images=images.to(self.device), view=view, table=table))
+
+    @torch.no_grad()
+    def ips_image_ragged(self, images, patch_size, patch_stride, pad=False):
+        """``ips_image()`` on whole images of DIFFERENT sizes in one call: ``images`` an
+        ``ips_amd.ragged_image.RaggedImages`` or a list of (C, H_b, W_b) float32 tensors, on the device or on the host (copied
+        whole) -> (mem_patch (B, M, C, ph, pw), mem_pos (B, M, D) | None).  Image by image and bit for bit what
+        ``for b in range(B): out[b] = net.ips_image(images[b][None], patch_size, patch_stride)`` returns and leaves behind,
+        which is what ``net.ips_ragged([patchify(images[b]) for b], pad=pad)`` returns and leaves behind: ``last_mem_idx``
+        (B, M) local to each image's grid, ``last_mem_emb``, ``last_shuffle`` the list of per-image permutations (drawn image
+        by image: torch's RNG streams end where that loop leaves them), positions restarting at 0 in every image; with
+        ``pad=True`` an image with ny_b * nx_b <= M comes back as ``ips_ragged(pad=True)`` returns a short slide, and
+        ``last_mem_count`` is set.  On a ROCm device, float32 images, an eval-mode encoder, no overridden ``do_shuffle``, at
+        least one image longer than M and a trunk whose stem reads a ragged view (``EncoderPlan.ragged_view_supported``: the
+        exact fp32 1x32x32, 1x50x50 and 3x100x100 trunks): ONE encoder pass over the grid patches of all images, read where
+        they lie - no patch tensor is made -, one packed logits table, ONE loop launch (``ipsx_scan_ragged``) and ONE finish
+        launch (``ipsx_ragged_finish_view``).  Everywhere else the per-image patch tensors are materialised and
+        ``ips_ragged(list, pad)`` runs unchanged, with its own refusals.  Refused before the first launch and before a random
+        number is drawn: everything ``ips_ragged`` refuses with "rows" read as grid patches, images whose channel counts
+        differ from each other or from the encoder's, a patch or stride that does not fit an image, uint8 images (TypeError:
+        they stay with solo ``ips_image()``), a feature net."""
+        from ..ragged_image import ips_image_ragged
+        return ips_image_ragged(self, images, patch_size, patch_stride, pad)
 
     def ips_stream(self, patch_size=None, patch_stride=None):
         """``ips()`` over patches that arrive in pieces -> ``ips_amd.stream.IPSStream``: ``feed(piece)`` takes

@@ -303,8 +303,9 @@ constexpr int SP_SLAB_U8 = SP_SLAB + 256;
 // ipsx_patch_view in `va`: the same float2 units off the image's rows (row pitch w; 8-byte loads when va->wide, else dwords)
 // U8 and VIEW: whole uint8 images.  The patch kernel's dwords cross row ends, which an image does not allow: the float view's
 // 1,250 two-pixel units instead, 2 bytes each (va->wide: one 2-byte load or two single bytes), through the table copy
-template <bool U8, bool VIEW = false>
-__device__ __forceinline__ void stem_pool50_body(const StemArgs& a, const float* table, const ViewArgs* va = nullptr) {
+// VA: what `va` points to - ViewArgs, or RaggedAt (ipsx_common.h: images of different sizes, the patch resolved by the kernel)
+template <bool U8, bool VIEW = false, class VA = ViewArgs>
+__device__ __forceinline__ void stem_pool50_body(const StemArgs& a, const float* table, const typename as_given<VA>::type* va = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, half = lane >> 5;
@@ -488,6 +489,14 @@ __global__ __launch_bounds__(256, 2) void stem_pool50_kernel(StemArgs a) { stem_
 __global__ __launch_bounds__(256, 2) void stem_pool50_u8_kernel(StemArgs a, const float* table) { stem_pool50_body<true>(a, table); }
 __global__ __launch_bounds__(256, 2) void stem_pool50_view_kernel(StemArgs a, ViewArgs va) { stem_pool50_body<false, true>(a, nullptr, &va); }
 __global__ __launch_bounds__(256, 2) void stem_pool50_view_u8_kernel(StemArgs a, const float* table, ViewArgs va) { stem_pool50_body<true, true>(a, table, &va); }
+// ... through a ragged view (a.patches: the packed buffer of images of different sizes): the wavefront resolves its patch
+// (the body's own number, tail included) on scalar registers, the body stages it as the view kernel does
+__global__ __launch_bounds__(256, 2) void stem_pool50_ragged_view_kernel(StemArgs a, RaggedViewArgs rv) {
+    long long p = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (p >= a.n) p = a.n - 1;
+    const RaggedAt at = ragged_at(rv, p);
+    stem_pool50_body<false, true, RaggedAt>(a, nullptr, &at);
+}
 
 // ------------------------------------------------------------------------------------------------ stem + max-pool, 3 x 100 px
 // The traffic-sign configuration's stem (config/traffic_config.yml: 3x100x100 patches -> 50x50x64 -> 25x25x64 pooled), same
@@ -521,8 +530,9 @@ constexpr int S3_FLOATS_U8 = S3_FLOATS + 3 * 256;
 // units off the image's planes (row pitch w, plane pitch h * w; 16-byte loads when va->wide, else dwords)
 // U8 and VIEW: whole uint8 images.  The patch kernel's 16-byte units cross row and plane ends: the float view's 7,500
 // four-pixel units instead, a dword each (va->wide: one dword load or four single bytes), through the channel's table copy
-template <bool U8, bool VIEW = false>
-__device__ __forceinline__ void stem_pool100x3_body(const Stem3Args& a, const float* table, const ViewArgs* va = nullptr) {
+// VA: as in stem_pool50_body
+template <bool U8, bool VIEW = false, class VA = ViewArgs>
+__device__ __forceinline__ void stem_pool100x3_body(const Stem3Args& a, const float* table, const typename as_given<VA>::type* va = nullptr) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 31, half = lane >> 5;
@@ -755,6 +765,11 @@ __global__ __launch_bounds__(256, 1) void stem_pool100x3_kernel(Stem3Args a) { s
 __global__ __launch_bounds__(256, 1) void stem_pool100x3_u8_kernel(Stem3Args a, const float* table) { stem_pool100x3_body<true>(a, table); }
 __global__ __launch_bounds__(256, 1) void stem_pool100x3_view_kernel(Stem3Args a, ViewArgs va) { stem_pool100x3_body<false, true>(a, nullptr, &va); }
 __global__ __launch_bounds__(256, 1) void stem_pool100x3_view_u8_kernel(Stem3Args a, const float* table, ViewArgs va) { stem_pool100x3_body<true, true>(a, table, &va); }
+// ... through a ragged view, as stem_pool50_ragged_view_kernel (workgroup = patch)
+__global__ __launch_bounds__(256, 1) void stem_pool100x3_ragged_view_kernel(Stem3Args a, RaggedViewArgs rv) {
+    const RaggedAt at = ragged_at(rv, (long long)blockIdx.x);
+    stem_pool100x3_body<false, true, RaggedAt>(a, nullptr, &at);
+}
 
 static bool stem_pool100x3_supported(const ipsx_trunk* t) {
     const char* e = getenv("IPSX_NO_FUSED");
@@ -795,12 +810,16 @@ int fused_stem_pool50(const ipsx_trunk* t, const PatchSrc& src, float* y, int64_
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S3_FLOATS * sizeof(float)));
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem_pool100x3_view_u8_kernel),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S3_FLOATS_U8 * sizeof(float)));
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem_pool100x3_ragged_view_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S3_FLOATS * sizeof(float)));
             attr3 = true;
         }
         const dim3 grid((unsigned)n), block(256);
         if (src.view && src.table)
             stem_pool100x3_view_u8_kernel<<<grid, block, S3_FLOATS_U8 * sizeof(float), s>>>(a3, src.table, view_args(src, {4, 1}));
         else if (src.view) stem_pool100x3_view_kernel<<<grid, block, S3_FLOATS * sizeof(float), s>>>(a3, view_args(src, {16}));
+        else if (src.ragged)
+            stem_pool100x3_ragged_view_kernel<<<grid, block, S3_FLOATS * sizeof(float), s>>>(a3, ragged_view_args(src, 16));
         else if (src.table) stem_pool100x3_u8_kernel<<<grid, block, S3_FLOATS_U8 * sizeof(float), s>>>(a3, src.table);
         else stem_pool100x3_kernel<<<grid, block, S3_FLOATS * sizeof(float), s>>>(a3);
         return launched("stem_pool100x3") == IPSX_OK ? 1 : -1;
@@ -814,6 +833,7 @@ int fused_stem_pool50(const ipsx_trunk* t, const PatchSrc& src, float* y, int64_
     if (src.view && src.table)
         stem_pool50_view_u8_kernel<<<grid, block, 4 * SP_SLAB_U8 * sizeof(float), s>>>(a, src.table, view_args(src, {2, 1}));
     else if (src.view) stem_pool50_view_kernel<<<grid, block, 4 * SP_SLAB * sizeof(float), s>>>(a, view_args(src, {8}));
+    else if (src.ragged) stem_pool50_ragged_view_kernel<<<grid, block, 4 * SP_SLAB * sizeof(float), s>>>(a, ragged_view_args(src, 8));
     else if (src.table) stem_pool50_u8_kernel<<<grid, block, 4 * SP_SLAB_U8 * sizeof(float), s>>>(a, src.table);
     else stem_pool50_kernel<<<grid, block, 4 * SP_SLAB * sizeof(float), s>>>(a);
     return launched("stem_pool50") == IPSX_OK ? 1 : -1;

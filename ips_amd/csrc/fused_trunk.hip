@@ -527,10 +527,11 @@ __device__ __forceinline__ void stage_u8_row16(const uint4 q, const float* tab, 
 // lane from the image's rows (row pitch w), staged in the same order
 // U8 and VIEW: whole uint8 images - the lane's 16 bytes are half a patch row, contiguous in the image too (va->wide: 16, 4 or 1
 // bytes per load), staged by stage_u8_row16 as the uint8 patch kernel's
-template <bool STAMP, int WPB, bool U8 = false, bool VIEW = false>
+// VA: what `va` points to - ViewArgs, or RaggedAt (ipsx_common.h: images of different sizes, the patch resolved by the kernel)
+template <bool STAMP, int WPB, bool U8 = false, bool VIEW = false, class VA = ViewArgs>
 __device__ __forceinline__ void trunk_front(const FusedArgs& a, long long pi, float* S, int lane, int wave,
                                             unsigned long long* stamps, const float* table = nullptr,
-                                            const ViewArgs* va = nullptr) {
+                                            const typename as_given<VA>::type* va = nullptr) {
     IPSX_STAMP(0);
 
     // ---- input patch -> slab as a zero-padded 38x38 image (coalesced 16 B global loads)
@@ -1000,6 +1001,7 @@ static void fused_lds_attrs() {
         {reinterpret_cast<const void*>(fused_trunk_u8_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_view_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_view_u8_kernel), FUSED_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_ragged_view_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_parts_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_parts_view_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_parts_u8_kernel), FUSED_LDS},
@@ -1017,7 +1019,7 @@ static void fused_lds_attrs() {
 // stamps, no device-side count.
 int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, hipStream_t s, const int* count,
                  unsigned long long* stamps) {
-    if ((src.table || src.view) && (stamps || count))
+    if ((src.table || src.view || src.ragged) && (stamps || count))
         return fail(IPSX_EINVAL, "fused trunk: uint8 patches and patch views go without stamps and device-side counts");
     FusedArgs a = fused_args(t, src, n, emb, true);
     a.count = count;
@@ -1073,6 +1075,13 @@ int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb
         if (n_full) fused_trunk_view_kernel<<<grid8, dim3(512), FUSED_LDS, s>>>(a, fused_view_args(src));
         if (rest) fused_trunk_pair_view_kernel<<<grid2, dim3(256), lds2, s>>>(b, fused_view_args(tail));
         return launched("fused_trunk_view");
+    }
+    if (src.ragged) {                                  // (the list travels with the table: the kernels resolve it themselves)
+        FusedArgs ar = a, br = b;
+        ar.index = nullptr; br.index = nullptr;
+        if (n_full) fused_trunk_ragged_view_kernel<<<grid8, dim3(512), FUSED_LDS, s>>>(ar, ragged_view_args(src, 16));
+        if (rest) fused_trunk_pair_ragged_view_kernel<<<grid2, dim3(256), lds2, s>>>(br, ragged_view_args(tail, 16));
+        return launched("fused_trunk_ragged_view");
     }
     if (stamps) fused_trunk_kernel<true><<<grid8, dim3(512), FUSED_LDS, s>>>(a, stamps);
     else if (n_full) fused_trunk_kernel<false><<<grid8, dim3(512), FUSED_LDS, s>>>(a, nullptr);

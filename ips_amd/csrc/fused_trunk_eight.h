@@ -668,9 +668,10 @@ __device__ __forceinline__ int* compact_rows() {
 // call's list.  clist[p] = (j, a.index[j]): patch .y -> emb row j = .x.  The rows are kept in LDS (32 bytes beside the slabs)
 // for the store and the count at the end, so that nothing there waits for memory again.  Only the first n8 entries are this
 // launch's (trunk_split_n8 of the count, ipsx_internal.h: whole rounds, or all of them); the pair launch behind takes the rest.
-template <bool STAMP, bool U8, bool PARTS = false, bool VIEW = false, bool COMPACT = false>
+// VA: as in trunk_front
+template <bool STAMP, bool U8, bool PARTS = false, bool VIEW = false, bool COMPACT = false, class VA = ViewArgs>
 __device__ __forceinline__ void fused_trunk_body(const FusedArgs& a, unsigned long long* stamps, const float* table,
-                                                 const PartsArgs* pa = nullptr, const ViewArgs* va = nullptr,
+                                                 const PartsArgs* pa = nullptr, const typename as_given<VA>::type* va = nullptr,
                                                  const int2* __restrict__ clist = nullptr, int cus = 0, int pair_mode = 0) {
     extern __shared__ __attribute__((aligned(16))) float lds[];          // 8 slabs of SLAB8
     constexpr int WPB = 8;
@@ -691,7 +692,7 @@ __device__ __forceinline__ void fused_trunk_body(const FusedArgs& a, unsigned lo
         pi = e.y;
     } else if (a.index) pi = a.index[pi];
     else if constexpr (VIEW) pi += va->first;
-    trunk_front<STAMP, WPB, U8, VIEW>(a, pi, lds + wave * SLAB8, lane, wave, stamps, table, va);
+    trunk_front<STAMP, WPB, U8, VIEW, VA>(a, pi, lds + wave * SLAB8, lane, wave, stamps, table, va);
     switch (__builtin_amdgcn_readfirstlane(Geo8::set_of_wave(wave))) {   // the wave's layer1 tile set, see Geo8
         case 0: layer1_p1<STAMP, 0>(a, lds, lane, wave, stamps); break;
         case 1: layer1_p1<STAMP, 1>(a, lds, lane, wave, stamps); break;
@@ -774,6 +775,16 @@ __global__ __launch_bounds__(512, 1) void fused_trunk_view_kernel(FusedArgs a, V
 // ... through a view of whole uint8 images (a.patches: bytes; table: 256 floats)
 __global__ __launch_bounds__(512, 1) void fused_trunk_view_u8_kernel(FusedArgs a, const float* table, ViewArgs va) {
     fused_trunk_body<false, true, false, true>(a, nullptr, table, nullptr, &va);
+}
+
+// ... through a ragged view (a.patches: the packed buffer of images of different sizes; the list travels in rv.index, a.index
+// and a.count are NULL): the wavefront (= patch) resolves its patch - the body's own number, tail included - on scalar
+// registers, the body stages it as the view kernel does
+__global__ __launch_bounds__(512, 1) void fused_trunk_ragged_view_kernel(FusedArgs a, RaggedViewArgs rv) {
+    long long j = (long long)blockIdx.x * 8 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (j >= a.n) j = a.n - 1;
+    const RaggedAt at = ragged_at(rv, j);
+    fused_trunk_body<false, false, false, true, false, RaggedAt>(a, nullptr, nullptr, nullptr, &at);
 }
 
 __global__ __launch_bounds__(512, 1) void fused_trunk_parts_view_kernel(FusedArgs a, PartsArgs pa, ViewArgs va) {

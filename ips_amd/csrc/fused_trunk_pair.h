@@ -230,9 +230,10 @@ __device__ __forceinline__ void store_l2_pair(float* lds, const f32x16& v, int l
 // COMPACT (fused_trunk_pair_parts_dedup_kernel only, as in fused_trunk_body): the two entries are clist[p_first], clist[p_first
 // + 1] below n_list, the list's device-side length; clist[p] = (j, a.index[j]): patch .y -> emb row j = .x, and the rows are
 // counted into their parts behind the stores (parts_count_compact<2>)
-template <bool KEEP, bool U8 = false, bool VIEW = false, bool COMPACT = false>
+// VA: as in trunk_front
+template <bool KEEP, bool U8 = false, bool VIEW = false, bool COMPACT = false, class VA = ViewArgs>
 __device__ __forceinline__ void trunk_pair_tile(const FusedArgs& a, long long p_first, float* lds, const float* table = nullptr,
-                                                const ViewArgs* va = nullptr, const PartsArgs* pa = nullptr,
+                                                const typename as_given<VA>::type* va = nullptr, const PartsArgs* pa = nullptr,
                                                 const int2* __restrict__ clist = nullptr, long long n_list = 0) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ps = wave >> 1, nh = wave & 1;                              // patch slot of the workgroup, n-tile of the pair
@@ -416,6 +417,15 @@ __global__ __launch_bounds__(256, 2) void fused_trunk_pair_view_kernel(FusedArgs
 __global__ __launch_bounds__(256, 2) void fused_trunk_pair_view_u8_kernel(FusedArgs a, const float* table, ViewArgs va) {
     extern __shared__ __attribute__((aligned(16))) float lds[];          // 2 slabs
     trunk_pair_tile<false, true, true>(a, (long long)blockIdx.x * 2, lds, table, &va);
+}
+
+// ... through a ragged view, as fused_trunk_ragged_view_kernel (two wavefronts per patch)
+__global__ __launch_bounds__(256, 2) void fused_trunk_pair_ragged_view_kernel(FusedArgs a, RaggedViewArgs rv) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];          // 2 slabs
+    long long j = (long long)blockIdx.x * 2 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 7));
+    if (j >= a.n) j = a.n - 1;
+    const RaggedAt at = ragged_at(rv, j);
+    trunk_pair_tile<false, false, true, false, RaggedAt>(a, (long long)blockIdx.x * 2, lds, nullptr, &at);
 }
 
 // the counted launch behind the blank scan, second half (dedup.hip; launched behind fused_trunk_parts_dedup_kernel on its

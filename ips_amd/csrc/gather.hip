@@ -3,7 +3,9 @@
 // (reference architecture/ips_net.py:245-250).  Pure HBM-bound copy: one workgroup
 // per selected row, 16 bytes per lane when the row allows it.
 
-#include "ipsx_common.h"
+#include <type_traits>
+
+#include "ipsx_internal.h"
 
 namespace ipsx {
 
@@ -126,6 +128,80 @@ __global__ __launch_bounds__(256) void ragged_finish_kernel(RaggedFinishArgs a) 
     }
 }
 
+// ragged_finish_kernel with the source row replaced by a grid patch copied out of its image (IPSNet.ips_image_ragged, DESIGN
+// 2.8): workgroup (j, k) fills slot j of image k.  The image's table entry and its two row offsets are workgroup-uniform and
+// kept scalar; an image whose offsets are not its entry's (first, first + ny * nx) is left untouched.  The patch copied is
+// packed patch flat[g] (or g), resolved through the table by the function the stems use (ragged_view_offset) - a number that
+// is no packed patch reads packed patch 0, so no read leaves the packed buffer.  VW: floats per copy (4: 16-byte copies - pw,
+// every w, sw and the addresses allow them, the host's decision - or 1).
+struct RaggedFinishViewArgs {
+    const float* pixels; const ipsx_image_entry* images; int b, c, ph, pw, sh, sw; long long total;
+    const long long* row_off; const long long* idx; const int* flat;
+    const uint4* pos; long long pos_units;
+    float* out_patch; uint4* out_pos; long long* idx_out; long long* rows_out;
+    int m;
+};
+
+template <int VW>
+__global__ __launch_bounds__(256) void ragged_finish_view_kernel(RaggedFinishViewArgs a) {
+    typedef typename std::conditional<VW == 4, float4, float>::type V;
+    const int j = blockIdx.x, k = blockIdx.y;
+    const long long r0 = a.row_off[k], r1 = a.row_off[k + 1];
+    const long long lo = ((long long)__builtin_amdgcn_readfirstlane((int)(r0 >> 32)) << 32) |
+                         (unsigned int)__builtin_amdgcn_readfirstlane((int)r0);
+    const long long hi = ((long long)__builtin_amdgcn_readfirstlane((int)(r1 >> 32)) << 32) |
+                         (unsigned int)__builtin_amdgcn_readfirstlane((int)r1);
+    const ipsx_image_entry e = a.images[k];
+    const long long n = (long long)e.ny * e.nx;
+    if (!(lo >= 0 && lo == e.first && hi - lo == n && hi <= a.total)) return;
+    const size_t slot = (size_t)k * a.m + j;
+    const int rowv = a.pw / VW, units = a.c * a.ph * rowv;
+    V* d = reinterpret_cast<V*>(a.out_patch + slot * ((size_t)a.c * a.ph * a.pw));
+    uint4* dp = a.pos ? a.out_pos + slot * a.pos_units : nullptr;
+    long long r;
+    if (n > a.m) {
+        if (!a.idx) return;                                     // (a batch of short images only has no selection)
+        r = a.idx[slot];
+        r = r < 0 ? 0 : (r >= n ? n - 1 : r);                   // inside its OWN image
+    } else if (j < n) {
+        r = j;
+    } else {                                                    // the padding of a short image
+        V zero;
+        if constexpr (VW == 4) zero = make_float4(0.f, 0.f, 0.f, 0.f); else zero = 0.f;
+        for (int i = threadIdx.x; i < units; i += 256) d[i] = zero;
+        if (dp)
+            for (long long i = threadIdx.x; i < a.pos_units; i += 256) dp[i] = make_uint4(0u, 0u, 0u, 0u);
+        if (threadIdx.x == 0) {
+            a.idx_out[slot] = -1;
+            a.rows_out[slot] = -1;
+        }
+        return;
+    }
+    const long long g = lo + r;                                 // in [lo, hi): inside the table
+    long long ps = g;
+    if (a.flat) {
+        ps = a.flat[g];
+        ps = ps < 0 ? 0 : (ps >= a.total ? a.total - 1 : ps);
+    }
+    ps = (long long)__builtin_amdgcn_readfirstlane((int)ps);    // (total < 2^31; workgroup-uniform: the table is read scalar)
+    int w = a.images[0].w, h = a.images[0].h;
+    long long off = ragged_view_offset(a.images, a.b, a.sh, a.sw, ps, &w, &h);
+    if (off < 0) off = a.images[0].elem_off;
+    const float* s = a.pixels + off;
+    for (int i = threadIdx.x; i < units; i += 256) {
+        const int xv = i % rowv, t = i / rowv, y = t % a.ph, ch = t / a.ph;
+        d[i] = *reinterpret_cast<const V*>(s + ((long long)ch * h + y) * w + xv * VW);
+    }
+    if (dp) {
+        const uint4* sp = a.pos + (size_t)g * a.pos_units;
+        for (long long i = threadIdx.x; i < a.pos_units; i += 256) dp[i] = sp[i];
+    }
+    if (threadIdx.x == 0) {
+        a.idx_out[slot] = r;
+        a.rows_out[slot] = g;
+    }
+}
+
 }  // namespace ipsx
 
 using namespace ipsx;
@@ -193,6 +269,33 @@ IPSX_API int ipsx_ragged_finish(const void* rows, int64_t row_bytes, int64_t tot
     a.idx_out = reinterpret_cast<long long*>(mem_idx_out); a.rows_out = reinterpret_cast<long long*>(rows_out); a.m = m;
     ragged_finish_kernel<<<dim3((unsigned)m, (unsigned)b), dim3(256), 0, as_stream(stream)>>>(a);
     return launched("ragged_finish");
+}
+
+// The end of IPSNet.ips_image_ragged in ONE launch (ragged_finish_view_kernel above): ipsx_ragged_finish on the patches of
+// images of different sizes, copied out of the packed buffer.  The view's host table is checked here, before the launch.
+IPSX_API int ipsx_ragged_finish_view(const float* pixels, const ipsx_ragged_view* view, const int64_t* row_offsets,
+                                     const int64_t* mem_idx, int m, const int32_t* flat, const void* pos, int64_t pos_row_bytes,
+                                     void* mem_patch, void* mem_pos, int64_t* mem_idx_out, int64_t* rows_out, void* stream) {
+    IPSX_REQUIRE(pixels && view && row_offsets && mem_patch && mem_idx_out && rows_out && m > 0, "ragged_finish_view: bad arguments");
+    const int64_t total = ragged_view_total(view, "ragged_finish_view");
+    if (total < 0) return IPSX_EINVAL;
+    IPSX_REQUIRE(view->images && view->b <= 65535 && total > 0, "ragged_finish_view: a device table of at most 65535 images");
+    IPSX_REQUIRE(at_multiple(pixels, 4) && at_multiple(mem_patch, 4), "ragged_finish_view: pixels and mem_patch at 4-byte addresses");
+    IPSX_REQUIRE(!pos || (mem_pos && pos_row_bytes > 0 && pos_row_bytes % 16 == 0 && at_multiple(pos, 16) && at_multiple(mem_pos, 16)),
+                 "ragged_finish_view: positional rows of 16-byte units");
+    RaggedFinishViewArgs a;
+    a.pixels = pixels; a.images = view->images; a.b = view->b; a.c = view->c; a.ph = view->ph; a.pw = view->pw;
+    a.sh = view->sh; a.sw = view->sw; a.total = total;
+    a.row_off = reinterpret_cast<const long long*>(row_offsets); a.idx = reinterpret_cast<const long long*>(mem_idx); a.flat = flat;
+    a.pos = static_cast<const uint4*>(pos); a.pos_units = pos ? pos_row_bytes / 16 : 0;
+    a.out_patch = static_cast<float*>(mem_patch); a.out_pos = static_cast<uint4*>(mem_pos);
+    a.idx_out = reinterpret_cast<long long*>(mem_idx_out); a.rows_out = reinterpret_cast<long long*>(rows_out); a.m = m;
+    const dim3 grid((unsigned)m, (unsigned)view->b);
+    if (view->pw % 4 == 0 && at_multiple(mem_patch, 16) && ragged_view_at_multiple(pixels, *view, 16))
+        ragged_finish_view_kernel<4><<<grid, dim3(256), 0, as_stream(stream)>>>(a);
+    else
+        ragged_finish_view_kernel<1><<<grid, dim3(256), 0, as_stream(stream)>>>(a);
+    return launched("ragged_finish_view");
 }
 
 IPSX_API int ipsx_gather_rows(const void* src, const int64_t* idx, void* dst, int b, int64_t n_rows, int m,

@@ -59,7 +59,72 @@ __device__ __forceinline__ long long view_base(const ViewArgs& va, long long p) 
     return off < 0 ? 0 : off;
 }
 
+// ---- ragged patch-grid view (ipsx_ragged_view): images of DIFFERENT sizes in one packed buffer, one table entry each
+// The image of packed patch p - the largest bi with images[bi].first <= p - by bisection, as patchify_sparse_kernel finds
+// the image of a non-zero.  0 <= p is the caller's; a p behind the last grid lands in the last image and fails its range test.
+__host__ __device__ inline int ragged_view_image(const ipsx_image_entry* im, int b, long long p) {
+    int lo = 0, hi = b;                               // im[lo].first <= p < im[hi].first
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (im[mid].first <= p) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// Element offset of packed patch p's (channel 0, row 0, column 0) inside the packed buffer, with the row pitch *w and the
+// image height *h of ITS image (channel pitch h * w); -1 - and nothing written - for a p outside [0, total).  ONE definition
+// for the host export ipsx_ragged_view_offset and the kernels' address arithmetic: elem_off of the image plus what
+// patch_view_offset gives for the image's own one-image view.
+__host__ __device__ inline long long ragged_view_offset(const ipsx_image_entry* im, int b, int sh, int sw, long long p, int* w, int* h) {
+    if (b <= 0 || p < 0) return -1;
+    const ipsx_image_entry e = im[ragged_view_image(im, b, p)];
+    const long long local = p - e.first;
+    if (local < 0 || e.nx <= 0 || local >= (long long)e.ny * e.nx) return -1;
+    const unsigned ul = (unsigned)local, py = ul / (unsigned)e.nx, px = ul - py * (unsigned)e.nx;
+    *w = e.w; *h = e.h;
+    return e.elem_off + ((long long)py * sh) * e.w + (long long)px * sw;
+}
+
+// what a ragged view kernel gets beside its usual arguments: the device table, and patch j of the launch is packed patch
+// index[j] (device int32) or first + j; wide as in ViewArgs, picked by the host that filled the table
+struct RaggedViewArgs {
+    const ipsx_image_entry* images;
+    int b, sh, sw;
+    const int* index;
+    long long first;
+    int wide;
+};
+
+// ... resolved for ONE patch: what the stems' staging code reads of a ViewArgs - the patch's first pixel in place of its
+// number (view_base below), the pitches of its image in v.w / v.h.  The bodies are templated on the type.
+struct RaggedAt {
+    struct { int h, w; } v;
+    const int* index;
+    long long first;
+    int wide;
+    long long off;
+};
+__device__ __forceinline__ long long view_base(const RaggedAt& at, long long) { return at.off; }
+
+// in a template's parameter list: the argument is not deduced from (the bodies' `va` defaults to nullptr)
+template <class T> struct as_given { using type = T; };
+
 #ifdef __HIPCC__
+// launch patch j (wave-uniform; the caller hands the same j to every lane) of a ragged view, on scalar registers: the packed
+// number is made uniform for the compiler, the bisection and the entry are scalar loads.  A number that is no packed patch
+// (a bad index list) reads packed patch 0: never outside the buffer.
+__device__ __forceinline__ RaggedAt ragged_at(const RaggedViewArgs& rv, long long j) {
+    const long long q = rv.index ? (long long)rv.index[j] : rv.first + j;
+    const long long p = (long long)__builtin_amdgcn_readfirstlane((int)q);       // (the host keeps first + n below 2^31)
+    RaggedAt at;
+    int w = rv.images[0].w, h = rv.images[0].h;
+    const long long off = ragged_view_offset(rv.images, rv.b, rv.sh, rv.sw, p, &w, &h);
+    at.off = off < 0 ? rv.images[0].elem_off : off;
+    at.v.w = w; at.v.h = h;
+    at.index = nullptr; at.first = 0; at.wide = rv.wide;
+    return at;
+}
+
 // uint8 images: the 4 NW consecutive bytes at q (inside one image row) as NW little-endian dwords, by loads of `width` bytes
 // (launch-uniform, every load naturally aligned): ONE load of 4 NW bytes, NW dwords, or 4 NW single bytes put together -
 // the same registers whatever the width, so a kernel's staging code has one form

@@ -12,6 +12,8 @@ namespace ipsx {
 //   the patch tensor at `base`: float32, t->patch_dtype (fused split trunks) or - with `table` - uint8 whose values are
 //   table[channel][byte]; or
 //   the grid of `view` over the whole images at `base`: float32, or - with `table` - uint8 through the table.
+//   the grids of `ragged` over float32 images of different sizes packed into the buffer at `base`: index and
+//   first count packed patches.
 // A tensor that is read from patch k on has its base moved (`first` stays 0); only a view counts in `first`.
 struct PatchSrc {
     const void* base;
@@ -19,12 +21,13 @@ struct PatchSrc {
     const ipsx_patch_view* view;
     const int* index;
     long long first;
+    const ipsx_ragged_view* ragged;
 };
 
 // the source of patches k .. of this source - the remainder of a launch, a chunk, the second half of a call
 static inline PatchSrc patch_src_from(const ipsx_trunk* t, PatchSrc s, int64_t k) {
     if (s.index) s.index += k;
-    else if (s.view) s.first += k;
+    else if (s.view || s.ragged) s.first += k;
     else s.base = static_cast<const unsigned char*>(s.base) +
                   (size_t)k * t->c_in * t->h * t->w * (s.table ? 1 : (t->patch_dtype ? 2 : sizeof(float)));
     return s;
@@ -45,6 +48,26 @@ static inline ViewArgs view_args(const PatchSrc& s, std::initializer_list<int> w
     va.v = *s.view; va.index = s.index; va.first = s.first;
     va.wide = view_load_width(s.base, *s.view, s.table ? 1 : sizeof(float), widths);
     return va;
+}
+
+// ---- the ragged view (trunk.hip).  The checked HOST table of a view -> its total patch count, or -1 with the message set
+// (`what`: the entry's name): what ipsx_ragged_view_fill accepts, asked again by every entry that is handed a view
+int64_t ragged_view_total(const ipsx_ragged_view* rv, const char* what);
+// can every patch row of the view be read by loads of `wd` bytes: the buffer, every image's offset and row pitch and the
+// patches' column stride are multiples of it (the host knows the table it uploaded)
+static inline bool ragged_view_at_multiple(const void* base, const ipsx_ragged_view& rv, int wd) {
+    if (reinterpret_cast<uintptr_t>(base) % wd != 0 || (rv.sw * sizeof(float)) % wd != 0) return false;
+    for (int k = 0; k < rv.b; ++k)
+        if ((rv.host[k].elem_off * (long long)sizeof(float)) % wd != 0 || (rv.host[k].w * sizeof(float)) % wd != 0) return false;
+    return true;
+}
+// what a ragged view kernel gets beside its usual arguments; wide: the kernel's one wide load (bytes), or 0 = dwords
+static inline RaggedViewArgs ragged_view_args(const PatchSrc& s, int widest) {
+    RaggedViewArgs rv;
+    rv.images = s.ragged->images; rv.b = s.ragged->b; rv.sh = s.ragged->sh; rv.sw = s.ragged->sw;
+    rv.index = s.index; rv.first = s.first;
+    rv.wide = ragged_view_at_multiple(s.base, *s.ragged, widest) ? widest : 0;
+    return rv;
 }
 
 // PARTS (ipsx_trunk_encode_parts): ONE launch encodes the index lists of every part of a call, one after the other, and says

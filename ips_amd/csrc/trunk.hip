@@ -136,7 +136,52 @@ int patch_src_check(const ipsx_trunk* t, const PatchSrc& src, int64_t n, bool fu
         IPSX_REQUIRE(src.index || src.first + n <= view_patches(*src.view), "%s: patches %lld .. %lld of a grid of %lld", what,
                      src.first, (long long)(src.first + n), (long long)view_patches(*src.view));
     }
+    if (src.ragged) {
+        IPSX_REQUIRE(!src.table && !src.view, "%s: a ragged view reads float32 images, and is no ipsx_patch_view", what);
+        IPSX_REQUIRE(at_multiple(src.base, 4), "%s: images must lie at a 4-byte address", what);
+        const int64_t total = ragged_view_total(src.ragged, what);
+        if (total < 0) return IPSX_EINVAL;
+        IPSX_REQUIRE(src.ragged->images, "%s: no device table", what);
+        IPSX_REQUIRE(ipsx_trunk_ragged_view_supported(t, src.ragged), "%s: the exact fp32 trunks whose stem stages its patch into "
+                     "LDS (1x32x32 fused, 1x50x50, 3x100x100) on a ragged view of their patch shape "
+                     "(ipsx_trunk_ragged_view_supported)", what);
+        IPSX_REQUIRE(src.index ? n <= 0x7FFFFFF0ll : src.first + n <= total, "%s: packed patches %lld .. %lld of %lld", what,
+                     src.first, (long long)(src.first + n), (long long)total);
+    }
     return IPSX_OK;
+}
+
+// The checked host table of a ragged view -> the total patch count, or -1
+int64_t ragged_view_total(const ipsx_ragged_view* rv, const char* what) {
+    if (!rv || !rv->host || rv->b <= 0 || rv->c <= 0 || rv->ph <= 0 || rv->pw <= 0 || rv->sh <= 0 || rv->sw <= 0) {
+        fail(IPSX_EINVAL, "%s: a ragged view needs a host table and positive b, c, patch and stride", what);
+        return -1;
+    }
+    int64_t total = 0, end = 0;                            // packed patches so far; the element behind the last image
+    for (int k = 0; k < rv->b; ++k) {
+        const ipsx_image_entry& e = rv->host[k];
+        if (e.h <= 0 || e.w <= 0 || rv->ph > e.h || rv->pw > e.w) {
+            fail(IPSX_EINVAL, "%s: image %d is %dx%d, the patch %dx%d", what, k, e.h, e.w, rv->ph, rv->pw);
+            return -1;
+        }
+        if (e.ny != (e.h - rv->ph) / rv->sh + 1 || e.nx != (e.w - rv->pw) / rv->sw + 1 || e.first != total) {
+            fail(IPSX_EINVAL, "%s: image %d: the entry's grid %dx%d from patch %lld is not the geometry's", what, k, e.ny, e.nx,
+                 (long long)e.first);
+            return -1;
+        }
+        if (e.elem_off < end) {
+            fail(IPSX_EINVAL, "%s: image %d at element %lld lies inside or in front of the image before it (ends at %lld)", what, k,
+                 (long long)e.elem_off, (long long)end);
+            return -1;
+        }
+        end = e.elem_off + (int64_t)rv->c * e.h * e.w;
+        total += (int64_t)e.ny * e.nx;
+        if (total > 0x7FFFFFFFll) {
+            fail(IPSX_EINVAL, "%s: more than 2^31 - 1 patches", what);
+            return -1;
+        }
+    }
+    return total;
 }
 
 }  // namespace ipsx
@@ -320,6 +365,60 @@ IPSX_API int ipsx_trunk_encode_view(const ipsx_trunk* t, const float* images, co
     IPSX_REQUIRE(t && images && v && emb && n >= 0 && first >= 0, "trunk_encode_view: bad arguments");
     return trunk_encode(t, PatchSrc{images, nullptr, v, index, index ? 0 : first}, n, emb, workspace, workspace_bytes, stream,
                         "trunk_encode_view");
+}
+
+// ---- the ragged patch-grid view: whole images of different sizes, packed
+IPSX_API int64_t ipsx_ragged_view_fill(ipsx_image_entry* table, int b, int c, int ph, int pw, int sh, int sw, const int32_t* h,
+                                       const int32_t* w, const int64_t* elem_off) {
+    if (!table || !h || !w || !elem_off || b <= 0 || c <= 0 || ph <= 0 || pw <= 0 || sh <= 0 || sw <= 0) {
+        fail(IPSX_EINVAL, "ragged_view_fill: bad arguments");
+        return -1;
+    }
+    int64_t first = 0;
+    for (int k = 0; k < b; ++k) {
+        if (h[k] <= 0 || w[k] <= 0 || ph > h[k] || pw > w[k]) {
+            fail(IPSX_EINVAL, "ragged_view_fill: image %d is %dx%d, the patch %dx%d", k, h[k], w[k], ph, pw);
+            return -1;
+        }
+        ipsx_image_entry& e = table[k];
+        e.elem_off = elem_off[k]; e.first = first; e.h = h[k]; e.w = w[k];
+        e.ny = (h[k] - ph) / sh + 1; e.nx = (w[k] - pw) / sw + 1;
+        first += (int64_t)e.ny * e.nx;
+        if (first > 0x7FFFFFFFll) {
+            fail(IPSX_EINVAL, "ragged_view_fill: more than 2^31 - 1 patches");
+            return -1;
+        }
+    }
+    const ipsx_ragged_view rv{b, c, ph, pw, sh, sw, nullptr, table};
+    return ragged_view_total(&rv, "ragged_view_fill");
+}
+
+IPSX_API int64_t ipsx_ragged_view_offset(const ipsx_image_entry* table, int b, const ipsx_ragged_view* geometry, int64_t p,
+                                         int64_t* pitch, int64_t* chan_pitch) {
+    if (!table || !geometry || b != geometry->b) return -1;
+    const ipsx_ragged_view rv{b, geometry->c, geometry->ph, geometry->pw, geometry->sh, geometry->sw, nullptr, table};
+    if (ragged_view_total(&rv, "ragged_view_offset") < 0) return -1;
+    int w = 0, h = 0;
+    const long long off = ragged_view_offset(table, b, rv.sh, rv.sw, p, &w, &h);
+    if (off < 0) return -1;
+    if (pitch) *pitch = w;
+    if (chan_pitch) *chan_pitch = (int64_t)h * w;
+    return off;
+}
+
+IPSX_API int ipsx_trunk_ragged_view_supported(const ipsx_trunk* t, const ipsx_ragged_view* view) {
+    if (!t || !view || ragged_view_total(view, "trunk_ragged_view_supported") < 0) return 0;
+    if (t->precision != 0 || t->patch_dtype != 0) return 0;
+    if (view->c != t->c_in || view->ph != t->h || view->pw != t->w) return 0;
+    return fused_trunk_supported(t) || fused_stem_pool50_covers(t) || fused_stem_pool100x3_covers(t) ? 1 : 0;
+}
+
+IPSX_API int ipsx_trunk_encode_ragged_view(const ipsx_trunk* t, const float* pixels, const ipsx_ragged_view* view,
+                                           const int32_t* index, int64_t first, int64_t n, float* emb, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    IPSX_REQUIRE(t && pixels && view && emb && n >= 0 && first >= 0, "trunk_encode_ragged_view: bad arguments");
+    return trunk_encode(t, PatchSrc{pixels, nullptr, nullptr, index, index ? 0 : first, view}, n, emb, workspace, workspace_bytes,
+                        stream, "trunk_encode_ragged_view");
 }
 
 IPSX_API int ipsx_trunk_encode_parts_view(const ipsx_trunk* t, const float* images, const ipsx_patch_view* v, const int32_t* index,

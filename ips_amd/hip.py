@@ -159,6 +159,18 @@ class PatchViewStruct(C.Structure):
                 ("ph", C.c_int), ("pw", C.c_int), ("sh", C.c_int), ("sw", C.c_int)]
 
 
+class ImageEntry(C.Structure):
+    """``ipsx_image_entry``: one image of a ragged view - where it lies in the packed buffer, its first packed patch, its grid."""
+    _fields_ = [("elem_off", C.c_int64), ("first", C.c_int64), ("h", C.c_int32), ("w", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32)]
+
+
+class RaggedViewStruct(C.Structure):
+    """``ipsx_ragged_view``: float32 images of different sizes in one packed buffer and the patch grids laid over them;
+    ``images`` the table on the device, ``host`` the same table on the host."""
+    _fields_ = [("b", C.c_int), ("c", C.c_int), ("ph", C.c_int), ("pw", C.c_int), ("sh", C.c_int), ("sw", C.c_int),
+                ("images", C.c_void_p), ("host", C.POINTER(ImageEntry))]
+
+
 class IpsCall(C.Structure):
     """include/ipsx.h ``ipsx_ips_call``: one ips() call with a resident loop, enqueued by ONE library call."""
     _fields_ = [("b", C.c_int), ("n", C.c_int64), ("m", C.c_int), ("i", C.c_int), ("h", C.c_int), ("n_token", C.c_int),
@@ -395,6 +407,15 @@ _EXPORTS = {
                                           C.c_void_p, C.c_void_p]),
     "ipsx_ragged_finish": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ipsx_ragged_view_fill": (C.c_int64, [C.POINTER(ImageEntry)] + [C.c_int] * 6 + [C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int64)]),
+    "ipsx_ragged_view_offset": (C.c_int64, [C.POINTER(ImageEntry), C.c_int, C.POINTER(RaggedViewStruct), C.c_int64,
+                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ipsx_trunk_ragged_view_supported": (C.c_int, [C.POINTER(Trunk), C.POINTER(RaggedViewStruct)]),
+    "ipsx_trunk_encode_ragged_view": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.POINTER(RaggedViewStruct), C.c_void_p, C.c_int64,
+                                                C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ipsx_ragged_finish_view": (C.c_int, [C.c_void_p, C.POINTER(RaggedViewStruct), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ipsx_scan_ragged_spans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ipsx_stream_commit_ragged": (C.c_int, [C.POINTER(StreamTable), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64,
@@ -1242,6 +1263,42 @@ def ragged_finish(rows, offsets, mem_idx, M, flat=None, pos=None, out=None):
     return out, out_pos, idx, grow
 
 
+def ragged_finish_view(pixels, rview, offsets, mem_idx, M, flat=None, pos=None, out=None):
+    """The end of ``IPSNet.ips_image_ragged``, ONE launch (``ipsx_ragged_finish_view``): ``ragged_finish`` with the source
+    row replaced by a grid patch copied out of its image.  ``pixels`` the packed 1-d float32 buffer, ``rview`` its
+    ``RaggedView``, ``offsets`` (B + 1,) int64 packed patch numbers on the device, ``mem_idx`` / ``flat`` / ``pos`` as there
+    -> (mem_patch (B, M, C, ph, pw), mem_pos | None, mem_idx with -1 in the padding, packed patch of every slot or -1).
+    ``out``: those four tensors (``mem_pos`` None without ``pos``), written in place of fresh ones - every slot is written,
+    nothing depends on what they held."""
+    B, total, dev = len(rview.sizes), rview.count, pixels.device
+    if pixels.dtype != torch.float32 or pixels.dim() != 1 or not pixels.is_contiguous() or not on_device(pixels):
+        raise ValueError("ragged_finish_view needs the packed 1-d float32 buffer on the GPU")
+    if offsets.dtype != torch.int64 or tuple(offsets.shape) != (B + 1,) or not offsets.is_contiguous() or offsets.device != dev:
+        raise ValueError("ragged_finish_view needs the (B + 1,) int64 patch offsets on the pixels' device")
+    if mem_idx is not None and (mem_idx.dtype != torch.int64 or tuple(mem_idx.shape) != (B, M) or not mem_idx.is_contiguous()
+                                or mem_idx.device != dev):
+        raise ValueError("mem_idx must be a contiguous ({}, {}) int64 tensor on the pixels' device".format(B, M))
+    if flat is not None and (flat.dtype != torch.int32 or tuple(flat.shape) != (total,) or not flat.is_contiguous() or flat.device != dev):
+        raise ValueError("flat must be a contiguous ({},) int32 tensor on the pixels' device".format(total))
+    if pos is not None and (pos.dim() != 2 or pos.shape[0] != total or not pos.is_contiguous() or pos.device != dev
+                            or (pos.shape[1] * pos.element_size()) % 16 or pos.data_ptr() % 16):
+        raise ValueError("pos must be ({}, D) contiguous rows of whole 16-byte units on the pixels' device".format(total))
+    rview.on(dev)
+    shapes = ((B, M) + rview.patch_shape, torch.float32), ((B, M, pos.shape[1]), pos.dtype) if pos is not None else None, \
+        ((B, M), torch.int64), ((B, M), torch.int64)
+    if out is None:
+        out = tuple(torch.empty(s[0], dtype=s[1], device=dev) if s is not None else None for s in shapes)
+    for t, s in zip(out, shapes):
+        if (t is None) != (s is None) or (t is not None and (tuple(t.shape) != s[0] or t.dtype != s[1] or not t.is_contiguous()
+                                                              or t.device != dev)):
+            raise ValueError("ragged_finish_view: out must be the four contiguous result tensors on the pixels' device")
+    out, out_pos, idx, grow = out
+    _ck(lib().ipsx_ragged_finish_view(_p(pixels), C.byref(rview.struct), _p(offsets), _p(mem_idx), M, _p(flat), _p(pos),
+                                      pos.shape[1] * pos.element_size() if pos is not None else 0, _p(out), _p(out_pos), _p(idx),
+                                      _p(grow), _stream()), "ipsx_ragged_finish_view")
+    return out, out_pos, idx, grow
+
+
 def order_index(order, B, N, out=None):
     """``order`` ((B or 1, N) int64, contiguous, on the device) -> (B, N) int32 flat row numbers
     ``b * N + clamp(order[b, j], 0, N - 1)`` - what the row-indexed producers read through - in ONE launch
@@ -1326,19 +1383,71 @@ class PatchView:
         return 0
 
 
+class RaggedView:
+    """The patch grids of whole images of DIFFERENT sizes that lie in one packed buffer, as addresses (``ipsx_ragged_view``,
+    DESIGN 2.8): packed patch ``p`` is grid patch ``p - first_b`` (``py * nx_b + px``, the order of the reference's
+    ``unfold``) of the image ``b`` with the largest ``first_b <= p``.  ``sizes`` the (H_b, W_b) pairs, ``elem_offsets`` the
+    element offset of every image inside the buffer.  The table is built and checked on the host
+    (``ipsx_ragged_view_fill``: a geometry it refuses raises ValueError) and uploaded by ``on(device)``, once per device."""
+
+    def __init__(self, channels, sizes, elem_offsets, patch_size, patch_stride):
+        sizes = [(int(h), int(w)) for h, w in sizes]
+        (ph, pw), (sh, sw) = (int(v) for v in patch_size), (int(v) for v in patch_stride)
+        B, Cc = len(sizes), int(channels)
+        self.table = (ImageEntry * max(B, 1))()
+        total = lib().ipsx_ragged_view_fill(self.table, B, Cc, ph, pw, sh, sw, (C.c_int32 * max(B, 1))(*[s[0] for s in sizes]),
+                                            (C.c_int32 * max(B, 1))(*[s[1] for s in sizes]),
+                                            (C.c_int64 * max(B, 1))(*[int(o) for o in elem_offsets]))
+        if total < 0:
+            raise ValueError("patch {}x{} / stride {}x{} on images {}: {}".format(ph, pw, sh, sw, sizes, lib().ipsx_last_error().decode()))
+        self.struct = RaggedViewStruct(B, Cc, ph, pw, sh, sw, None, self.table)
+        self.sizes, self.patch_size, self.patch_stride, self.patch_shape = tuple(sizes), (ph, pw), (sh, sw), (Cc, ph, pw)
+        self.grids = tuple((e.ny, e.nx) for e in self.table[:B])
+        self.lengths = tuple(ny * nx for ny, nx in self.grids)       # patches per image
+        self.firsts = tuple(e.first for e in self.table[:B])
+        self.count = int(total)
+        self._device = {}                                             # device -> the uploaded table (kept alive here)
+
+    def on(self, device):
+        """This view with its table on ``device`` (uploaded on first use) -> self."""
+        device = torch.device(device)
+        dev = self._device.get(device)
+        if dev is None:
+            host = torch.frombuffer(bytearray(bytes(self.table)), dtype=torch.uint8)
+            dev = self._device[device] = host.to(device)
+        self.struct.images = dev.data_ptr()
+        return self
+
+    def origin(self, p):
+        """(element offset of packed patch ``p``'s (0, 0, 0) inside the buffer, row pitch, channel pitch) - or (-1, 0, 0)
+        when ``p`` is no packed patch (``ipsx_ragged_view_offset``: the function the kernels address by)."""
+        pitch, chan = C.c_int64(0), C.c_int64(0)
+        off = lib().ipsx_ragged_view_offset(self.table, len(self.sizes), C.byref(self.struct), int(p), C.byref(pitch), C.byref(chan))
+        return int(off), int(pitch.value), int(chan.value)
+
+
 class PatchSource:
     """Where the patches of an image-encoder call lie - what ``EncoderPlan.encode_source`` reads.  Either a patch tensor
     ``PatchSource(patches, table=None)``: (P, C, h, w) or (B, N, C, h, w) on the GPU, float32, float16 / bfloat16 under
     IPSX_PRECISION=bf16 / fp32x3, or uint8 with its ``table`` (C, 256); or whole images read through a patch grid
     ``PatchSource(images=..., view=..., table=None)`` (``PatchView``, DESIGN 2.3: float32 images, or uint8 images with
-    their ``table``), whose patch tensor is never made.  Everything that
+    their ``table``), whose patch tensor is never made; or float32 images of different sizes in ONE packed 1-d buffer read
+    through their grids ``PatchSource(images=pixels, ragged=...)`` (``RaggedView``).  Everything that
     refuses a storage kind does so here, once, before the first launch; what is kept is contiguous.  ``shape`` is that of
     the patch tensor (for a view: the one ``patchify`` would make), ``count`` its number of patches."""
 
-    __slots__ = ("patches", "table", "images", "view", "shape", "dtype", "device", "count")
+    __slots__ = ("patches", "table", "images", "view", "shape", "dtype", "device", "count", "ragged")
 
-    def __init__(self, patches=None, table=None, images=None, view=None):
-        self.patches = self.table = self.images = self.view = None
+    def __init__(self, patches=None, table=None, images=None, view=None, ragged=None):
+        self.patches = self.table = self.images = self.view = self.ragged = None
+        if ragged is not None:
+            # float32 images of different sizes in one packed 1-d buffer, read through a ``RaggedView`` (DESIGN 2.8)
+            if table is not None or images.dtype != torch.float32 or images.dim() != 1 or not on_device(images):
+                raise TypeError("a ragged view reads a packed 1-d float32 buffer on the GPU")
+            self.images, self.ragged = images if images.is_contiguous() else images.contiguous(), ragged.on(images.device)
+            self.shape = torch.Size((ragged.count,) + ragged.patch_shape)
+            self.dtype, self.device, self.count = images.dtype, images.device, ragged.count
+            return
         if view is not None:
             self.images, self.view = view.check(images, table), view
             if table is not None:
@@ -1359,7 +1468,7 @@ class PatchSource:
     @property
     def base(self):
         """The tensor the kernels' base pointer points into."""
-        return self.images if self.view is not None else self.patches
+        return self.images if self.view is not None or self.ragged is not None else self.patches
 
 
 def gather_patches_view(images, view, idx, table=None):

@@ -314,7 +314,9 @@ class EncoderPlan:
         of float32 or uint8 images, on the exact fp32 fused trunk.  ``dedup`` (with ``parts``, any of those four): exact
         blank-patch dedup inside that launch (``ipsx_trunk_encode_parts_dedup`` and its ``_u8`` / ``_view`` / ``_view_u8``
         twins) - the same bits, the rows of the all-zero (bytes: all-zero-byte) entries written from ``blank_embedding``;
-        ``n_encoded`` then holds the number of entries the trunk encoded."""
+        ``n_encoded`` then holds the number of entries the trunk encoded.  A source with a ``hip.RaggedView`` (images of
+        different sizes in one packed buffer): ``index`` / ``first`` count packed patches, plain launches only
+        (``ipsx_trunk_encode_ragged_view``)."""
         self._refresh()
         # the trunk struct describes THIS call's patches: nothing an earlier call or question left in it is read
         t, L = self._describe(src.shape, 0 if src.table is not None else _PATCH_DTYPES[src.dtype]), lib()
@@ -322,6 +324,10 @@ class EncoderPlan:
             raise ValueError("patches have {} channels, encoder expects {}".format(src.shape[-3], t.c_in))
         if src.is_view and not L.ipsx_trunk_view_supported(C.byref(t), C.byref(src.view.struct)):
             raise ValueError("this encoder does not read patches through a view (EncoderPlan.view_supported)")
+        rv = C.byref(src.ragged.struct) if src.ragged is not None else None
+        if rv is not None and (parts is not None or not L.ipsx_trunk_ragged_view_supported(C.byref(t), rv)):
+            raise ValueError("this encoder does not read patches through a ragged view (EncoderPlan.ragged_view_supported; "
+                             "plain launches only)")
         if index is not None:
             if index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous() or index.device != src.device:
                 raise ValueError("index must be a contiguous 1-d int32 tensor on the patches' device")
@@ -334,7 +340,7 @@ class EncoderPlan:
             out = torch.empty((n, self.d_out), dtype=torch.float32, device=src.device)
         if n == 0:
             return out
-        if index is not None and not src.is_view and not L.ipsx_trunk_kernel(C.byref(t)).startswith(b"fused"):
+        if index is not None and not src.is_view and rv is None and not L.ipsx_trunk_kernel(C.byref(t)).startswith(b"fused"):
             # a layer-by-layer trunk: its LDS-staging stems take an index list through a view - the patch tensor as
             # src.count images of ONE patch each, grid patch p = patch p
             view = self._rows_view(src.shape)
@@ -366,19 +372,23 @@ class EncoderPlan:
                 name = "ipsx_trunk_encode_parts" + kind
                 _ck(getattr(L, name)(*args, _stream()), name)
             return out
-        if index is not None and vs is None:               # a patch tensor through an index list: the fused trunk
+        if index is not None and vs is None and rv is None:    # a patch tensor through an index list: the fused trunk
             if tab.value:
                 _ck(L.ipsx_trunk_encode_indexed_u8(tr, _p(base), tab, _p(index), n, _p(out), _stream()), "ipsx_trunk_encode_indexed_u8")
             else:
                 _ck(L.ipsx_trunk_encode_indexed(tr, _p(base), _p(index), n, _p(out), _stream()), "ipsx_trunk_encode_indexed")
             return out
-        flat = base if vs is not None else base.view(-1, *src.shape[-3:])
+        flat = base if vs is not None or rv is not None else base.view(-1, *src.shape[-3:])
 
         def run(lo, cnt, ws, nb):
             """Patches lo .. lo + cnt of the call - the library's own rule for "the source from patch lo on": the index is
             advanced, else the view's first patch, else the tensor."""
             outs = _p(out[lo:lo + cnt])
-            if vs is not None:
+            if rv is not None:                             # images of different sizes: index and first count packed patches
+                ix, lo1 = (_p(index[lo:]), 0) if index is not None else (None, first + lo)
+                _ck(L.ipsx_trunk_encode_ragged_view(tr, _p(flat), rv, ix, lo1, cnt, outs, _p(ws), nb, _stream()),
+                    "ipsx_trunk_encode_ragged_view")
+            elif vs is not None:
                 ix, lo1 = (_p(index[lo:]), 0) if index is not None else (None, first + lo)
                 if tab.value:                              # whole uint8 images
                     _ck(L.ipsx_trunk_encode_view_u8(tr, _p(flat), tab, vs, ix, lo1, cnt, outs, _p(ws), nb, _stream()),
@@ -460,6 +470,14 @@ class EncoderPlan:
             return False
         self._refresh()
         return bool(lib().ipsx_trunk_view_supported(C.byref(self._describe(view.patch_size)), C.byref(view.struct)))
+
+    def ragged_view_supported(self, rview):
+        """Can ``encode_source`` read the patches of this ``hip.RaggedView`` (images of different sizes)?  What
+        ``view_supported`` asks, of the view's patch shape (``ipsx_trunk_ragged_view_supported``)."""
+        if not self.is_image:
+            return False
+        self._refresh()
+        return bool(lib().ipsx_trunk_ragged_view_supported(C.byref(self._describe(rview.patch_size)), C.byref(rview.struct)))
 
     def view_kernel_name(self, view, u8=False):
         """The kernel that reads the images for this view (None: not supported); ``u8``: uint8 images."""
