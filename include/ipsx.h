@@ -999,7 +999,9 @@ int ipsx_bn_train_forward(const float* x, const float* residual, int64_t rows, i
                           const float* beta, float eps, float momentum, float* running_mean, float* running_var,
                           int relu, float* y, float* save_mean, float* save_invstd, float* workspace, void* stream);
 /* ipsx_bn_train_forward without its reduction pass: the per-slab partial sums come from the convolution that produced x
- * (ipsx_conv2d_lds_nhwc_stats), taken around `shift` (may alias running_mean: it is read before the update). */
+ * (ipsx_conv2d_lds_nhwc_stats), taken around `shift` (may alias running_mean: it is read before the update).  A channel
+ * whose shift proves more than 2 standard deviations from the batch mean, or not finite, is summed again over x on the
+ * device (fp64, deterministic): any shift gives statistics to float32 rounding, a near one gives them without that pass. */
 int ipsx_bn_train_forward_partials(const float* x, const float* residual, int64_t rows, int c, const float* gamma,
                                    const float* beta, float eps, float momentum, float* running_mean, float* running_var,
                                    int relu, float* y, float* save_mean, float* save_invstd, const float* partial,

@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256, 2) void conv_nhwc_kernel(NhwcArgs a) {
             }
     }
     if (NORM) {
-        // rows the statistics mark as centred (ipsx_rowstats.h: mean^2 / var > 64 - never on well-conditioned features): this
+        // rows the statistics mark as centred (ipsx_rowstats.h: mean^2 / var > 16, RM_RECENTRE = 17 - never on well-conditioned features): this
         // wave's columns of them again, as the chain over (x - mean) * w
         const unsigned mrow = m_base + lane;
         unsigned long long todo = __builtin_amdgcn_ballot_w64(mrow < a.m_total && reinterpret_cast<const float2*>(a.stats)[min(mrow, a.m_total - 1)].y < 0.0f);

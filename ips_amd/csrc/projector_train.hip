@@ -192,9 +192,12 @@ __global__ __launch_bounds__(256, 2) void projector_train_fwd_kernel(PtFwdArgs a
 
 // shift[o] = the mean of column o of z over its first k = min(n, PT_SHIFT_ROWS) rows: the value the column sums are taken
 // around.  bn_finalize_kernel takes any shift; the closer it is to the column mean, the less var = q / n - (s / n)^2
-// cancels.  Around row 0 alone (bn_reduce_kernel's rule) some column of 256 lies 3 sigma off, and the fp32 rounding of s
-// and q of a single slab came to 9e-7 of invstd at 65 rows, 6 x the stock error; around the mean of eight rows it lies
-// about 1 sigma off.  One wavefront per column, the lanes split F (coalesced reads of the row of W).
+// cancels.  Around row 0 alone some column of 256 lies 3 sigma off, and the fp32 rounding of s and q of a single slab
+// came to 9e-7 of invstd at 65 rows, 6 x the stock error; around the mean of eight rows it lies about 0.35 sigma off - if
+// the eight rows are typical.  Where they are not (eight rows of tissue in front of a slide of near-identical background:
+// sqrt(n / 8) sigma off, invstd to 2.7e-5) bn_finalize_kernel notices - a shift more than 2 sigma from the mean it led to
+// - and sums those columns of z again in fp64 (csrc/bn_train.hip; tests/test_bn_train_conditioning.py).
+// One wavefront per column, the lanes split F (coalesced reads of the row of W).
 constexpr int PT_SHIFT_ROWS = 8;
 
 template <typename T>

@@ -177,7 +177,13 @@ def _stats_shift(bn, x, weight, stride, pad, packs):
     E[d]^2 keeps its precision only while the shift is near the batch mean.  ``running_mean`` is not - 0 at
     initialisation, anything after loading foreign statistics (advisor, round 5) - so: the batch mean of this layer's
     PREVIOUS training step (the tensor that step returned, held by reference: no copy, no launch), and before there is one
-    the channel means of the convolution of the batch's first patch (one extra launch on 1 patch, once per layer)."""
+    the channel means of the convolution of the batch's first patch (one extra launch on 1 patch, once per layer).
+
+    Either is a guess made before the batch is seen, and nothing here looks at it (that would be a host synchronisation):
+    a first patch unlike the rest, a jump of the data between two steps, a previous step whose batch held a NaN - also
+    one that ``load_state_dict`` has since undone, or that came along through ``copy.deepcopy`` - are caught on the device,
+    where ``bn_finalize_kernel`` checks the shift against the mean it led to and, more than 2 sigma off or not finite,
+    discards the epilogue's sums and takes the channel's moments off the convolution's output again (csrc/bn_train.hip)."""
     prev = getattr(bn, "_ipsx_batch_mean", None)
     if prev is not None and prev.device == x.device and prev.shape == bn.running_mean.shape:
         return prev

@@ -327,12 +327,16 @@ def test_fused_encoder_matches_float64_autograd(conf_fn, patch):
     come out as +1 ulp in float32 and as -1e-9 in float64, which switches that element's gradient on or off.  The ReLU
     masks of both evaluations are compared first; a seed with such a flip (rare: ~0.4 M activations in the 2-stage
     trunk, 3 M in the 4-stage trunk on 64-px patches - where nine seeds of ten have one: BatchNorm centres every map on
-    zero) is held to a loose bound only, and at least ONE seed of at most ten must be free of flips and pass the tight
-    bound on every parameter gradient (float64 and these kernels are deterministic: the same seeds every run)."""
+    zero) is held to a loose bound only, and at least ONE seed of at most twenty must be free of flips and pass the tight
+    bound on every parameter gradient (float64 and these kernels are deterministic: the same seeds every run).  (Twenty,
+    not ten, since the BatchNorm statistics stopped shifting by row 0: which of a seed's activations land within an ulp of
+    zero moves with ANY change to the rounding of a mean - on the 64-px trunk seed 1 was the only flip-free one of ten,
+    now 11 and 18 are the flip-free ones of twenty, at 1.2e-5 and 1.1e-5 of the tight bound's 5e-5 - and a tenth of the
+    seeds being flip-free, ten of them come up empty one time in three.)"""
     dev = torch.device("cuda:0")
     conf = conf_fn(N=64, M=8, I=8, patch=patch)
     clean = 0
-    for seed in range(10):
+    for seed in range(20):
         if seed >= 3 and clean >= 1:
             break
         net_a = synth.fill_weights(IPSNet(dev, conf), 5 + seed).to(dev).train()
