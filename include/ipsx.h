@@ -122,7 +122,10 @@ extern "C" {
  *         ipsx_image_entry, ipsx_ragged_view (structs), ipsx_ragged_view_fill, ipsx_ragged_view_offset,
  *         ipsx_trunk_ragged_view_supported, ipsx_trunk_encode_ragged_view, ipsx_ragged_finish_view - whole images of
  *         different sizes in one call (IPSNet.ips_image_ragged): the patch-grid view with where a patch lies and its
- *         pitches read per patch from a table, and the end of such a call in one launch (additions, the minor number stays) */
+ *         pitches read per patch from a table, and the end of such a call in one launch (additions, the minor number stays);
+ *         ipsx_ragged_view_blank_flags, ipsx_trunk_encode_ragged_view_dedup (+ ipsx_trunk_ragged_view_dedup_workspace_bytes) -
+ *         exact blank-patch dedup on the ragged view: ipsx_trunk_encode_ragged_view encoding every non-blank entry and one
+ *         blank one (additions, the minor number stays) */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -841,7 +844,7 @@ int ipsx_trunk_ragged_view_supported(const ipsx_trunk* t, const ipsx_ragged_view
  * where a patch's first pixel lies and its two pitches are per patch.  A list entry that is no packed patch reads packed
  * patch 0, never outside the buffer.  The load width is picked per launch from the HOST table: the kernel's wide load when
  * `pixels`, every elem_off, every w and sw are multiples of it, dword loads otherwise.  Plain launches only (no counted
- * launch, no dedup, no uint8).  workspace: as ipsx_trunk_encode. */
+ * launch, no uint8; blank-patch dedup: ipsx_trunk_encode_ragged_view_dedup below).  workspace: as ipsx_trunk_encode. */
 int ipsx_trunk_encode_ragged_view(const ipsx_trunk* t, const float* pixels, const ipsx_ragged_view* view,
                                   const int32_t* index /* NULL: packed patches first .. first+n-1 */, int64_t first, int64_t n,
                                   float* emb, void* workspace, size_t workspace_bytes, void* stream);
@@ -856,6 +859,29 @@ int ipsx_trunk_encode_ragged_view(const ipsx_trunk* t, const float* pixels, cons
 int ipsx_ragged_finish_view(const float* pixels, const ipsx_ragged_view* view, const int64_t* row_offsets, const int64_t* mem_idx,
                             int m, const int32_t* flat, const void* pos, int64_t pos_row_bytes, void* mem_patch, void* mem_pos,
                             int64_t* mem_idx_out, int64_t* rows_out, void* stream);
+
+/* 3.06: exact blank-patch dedup on the ragged view (ipsx_trunk_encode_dedup for images of different sizes).  The fused
+ * 1x32x32 trunk at precision 0 on float32 images only; every entry checks the view's HOST table again before it launches.
+ * nonblank[j] (device int32, n entries) = 1 when entry j's patch - packed patch index[j], or first + j when index is NULL -
+ * has a non-zero element (-0.0 is zero, a denormal is not), 0 otherwise.  An entry that is no packed patch is flagged as
+ * packed patch 0, the patch the encoder reads for it.  Nothing outside the patch windows is read. */
+int ipsx_ragged_view_blank_flags(const float* pixels, const ipsx_ragged_view* view, const int32_t* index,
+                                 int64_t first, int64_t n, int32_t* nonblank, void* stream);
+/* bytes of device workspace ipsx_trunk_encode_ragged_view_dedup needs for n entries (0 for n <= 0): the flags, the list, the
+ * slots (n int32 each), the list's length and the compacted embeddings (n + 1 rows of 128 floats) */
+size_t ipsx_trunk_ragged_view_dedup_workspace_bytes(const ipsx_trunk* t, int64_t n);
+/* ipsx_trunk_encode_ragged_view, bit for bit, encoding every non-blank entry and ONE blank one.  On one stream, no host
+ * synchronisation: the flags (above); the ordered list of the entries to encode - the non-blank ones in list order, then the
+ * FIRST blank one - as packed patch numbers, its length and every entry's slot in it, all on the device (sums of integers:
+ * the list depends on the data only); the trunk launched for n entries, its workgroups beyond the device-side length
+ * returning before they read the list; emb[j] = the row of entry j's slot.  *n_encoded (device int32, may be NULL) = the
+ * list's length: the non-blank entries, plus 1 if any entry is blank.  workspace: device memory at a 16-byte address,
+ * ipsx_trunk_ragged_view_dedup_workspace_bytes(t, n) bytes (IPSX_EWORKSPACE otherwise).  n = 0 returns IPSX_OK; n >= 2^31, a
+ * null pointer and any other trunk are refused (IPSX_EINVAL) before the first launch. */
+int ipsx_trunk_encode_ragged_view_dedup(const ipsx_trunk* t, const float* pixels, const ipsx_ragged_view* view,
+                                        const int32_t* index /* NULL: packed patches first .. first+n-1 */, int64_t first,
+                                        int64_t n, float* emb, void* workspace, size_t workspace_bytes, int32_t* n_encoded,
+                                        void* stream);
 
 /* 3.06: the state update of a stream (IPSNet.ips_stream) as ONE launch, for up to four tables at once (patch rows,
  * embeddings, logits, global ids).  The n_cand candidates of a table are two segments that are never joined: its first

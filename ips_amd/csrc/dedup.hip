@@ -13,6 +13,9 @@
 //                        blank), its length, and for every patch the slot of its representative
 //   fused trunk          launched for the worst case, workgroups beyond the device-side count exit at once
 //   scatter_rows_kernel  emb[j] = emb_unique[slot[j]]
+// The explicit route's shape also runs on a ragged view - whole images of different sizes, the grid patches read where they
+// lie (ipsx_trunk_encode_ragged_view_dedup, the default of IPSNet.ips_image_ragged on the fused trunk): its scan and its
+// many-workgroup compaction stand behind the counted launch's kernels below.
 
 #include "ipsx_internal.h"
 
@@ -304,6 +307,84 @@ __global__ __launch_bounds__(256) void blank_compact_kernel(const unsigned long 
     }
 }
 
+// ---- the explicit route on a ragged view (ipsx_trunk_encode_ragged_view_dedup): images of different sizes, DESIGN 2.8
+//   blank_flags_ragged_view_kernel   one wavefront per list entry: its patch resolved as the ragged stems resolve it, read
+//                                    where it lies in its image
+//   ragged_compact_kernel            many workgroups: the ordered list of the entries to encode as PACKED PATCH NUMBERS (the
+//                                    non-blank ones, then the first blank one), its length, every entry's slot
+//   fused_trunk_ragged_view_counted_kernel (fused_trunk_eight.h) over that list, then scatter_rows_kernel
+// One wavefront per list entry j (wave-uniform: readfirstlane), the bisection, the table entry and the offset on scalar
+// registers (ragged_at); an entry that is no packed patch is packed patch 0, as in the encoder.  The 1x32x32 window at its
+// image's row pitch: the first KiB (patch rows 0 - 7), the other three only where that is all zero; 16-byte loads where
+// rv.wide allows, dwords otherwise (view_load_32) - nothing outside the window is read.
+__global__ __launch_bounds__(256) void blank_flags_ragged_view_kernel(const float* __restrict__ x, RaggedViewArgs rv, long long n,
+                                                                      int* __restrict__ nonblank) {
+    const int lane = threadIdx.x & 63;
+    const long long j = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (j >= n) return;                                                   // wavefront-uniform
+    const RaggedAt at = ragged_at(rv, j);
+    const float* p = x + at.off;
+    float4 v[1];
+    view_load_32<1>(p, at.v.w, at.wide, lane, 0, v);
+    unsigned any = nonzero_bits(float4_bits(v[0]));
+    if (__ballot(any != 0) == 0ull) {
+        float4 r[3];
+        view_load_32<3>(p, at.v.w, at.wide, lane, 1, r);
+        any = nonzero_bits(float4_bits(r[0])) | nonzero_bits(float4_bits(r[1])) | nonzero_bits(float4_bits(r[2]));
+    }
+    const unsigned long long b = __ballot(any != 0);
+    if (lane == 0) nonblank[j] = b != 0ull;
+}
+
+// Ordered compaction with many workgroups: a workgroup takes 1,024 entries.  It counts the non-blank entries in front of its
+// own and in the whole list and finds the first blank one by reading ALL flags (n / 1,024 workgroups x n flags out of the L2:
+// 35 us at 118 k entries, profiles/ips_image_ragged_dedup_trace.txt - 0.8 % of encoding a seventh of them), then writes list[slot] = the packed patch
+// number of its non-blank entries - index[j], or first + j - and slot[j] of every entry; the blank entries' slot is the one
+// behind the non-blank ones, where workgroup 0 puts the first blank entry, and the length.  Sums and a minimum of integers:
+// the list depends on the data only, never on timing.
+__global__ __launch_bounds__(1024) void ragged_compact_kernel(const int* __restrict__ nonblank, int n, const int* __restrict__ index,
+                                                              long long first, int* __restrict__ list, int* __restrict__ slot,
+                                                              int* __restrict__ count) {
+    __shared__ int s_before[16], s_total[16], s_blank[16], s_own[16];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned lo = blockIdx.x * 1024u;
+    int before = 0, total = 0, blank = 0x7FFFFFFF;
+    for (unsigned i = tid; i < (unsigned)n; i += 1024u) {
+        const int f = nonblank[i] != 0;
+        total += f;
+        before += f & (i < lo);
+        if (!f && blank == 0x7FFFFFFF) blank = (int)i;                    // (i grows: the thread's first blank entry)
+    }
+#pragma unroll
+    for (int o = 32; o; o >>= 1) {
+        before += __shfl_xor(before, o);
+        total += __shfl_xor(total, o);
+        const int other = __shfl_xor(blank, o);
+        blank = other < blank ? other : blank;
+    }
+    const unsigned j = lo + tid;
+    const int f = j < (unsigned)n ? nonblank[j] != 0 : 0;
+    const unsigned long long m = __ballot(f != 0);
+    if (lane == 0) { s_before[wave] = before; s_total[wave] = total; s_blank[wave] = blank; s_own[wave] = __popcll(m); }
+    __syncthreads();
+    int pos = 0, nb = 0, fb = 0x7FFFFFFF;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) {
+        pos += s_before[w] + (w < wave ? s_own[w] : 0);
+        nb += s_total[w];
+        fb = s_blank[w] < fb ? s_blank[w] : fb;
+    }
+    pos += __popcll(m & ((1ull << lane) - 1ull));
+    if (j < (unsigned)n) {
+        if (f) list[pos] = index ? index[j] : (int)(first + j);
+        slot[j] = f ? pos : nb;
+    }
+    if (blockIdx.x == 0 && tid == 0) {
+        if (fb != 0x7FFFFFFF) list[nb] = index ? index[fb] : (int)(first + fb);
+        *count = nb + (fb != 0x7FFFFFFF ? 1 : 0);
+    }
+}
+
 }  // namespace ipsx
 
 using namespace ipsx;
@@ -477,4 +558,74 @@ IPSX_API int ipsx_trunk_encode_parts_dedup_view_u8(const ipsx_trunk* t, const ui
                                                    void* workspace, size_t workspace_bytes, int32_t* n_encoded, void* stream) {
     return encode_parts_dedup(t, PatchSrc{images, table, v, index, 0}, true, true, n_index, emb, part_end, n_parts, done,
                               blank_emb, workspace, workspace_bytes, n_encoded, stream, "trunk_encode_parts_dedup_view_u8");
+}
+
+// ---- exact blank-patch dedup on a ragged view: the explicit route's shape on plain launches
+IPSX_API size_t ipsx_trunk_ragged_view_dedup_workspace_bytes(const ipsx_trunk* t, int64_t n) {
+    return ipsx_trunk_dedup_workspace_bytes(t, n);     // the same parts: flags, list, slots, the length, n + 1 compacted rows
+}
+
+// what both entries ask of the view and the list: a valid host table (checked again), a device table, 1x32x32 windows on
+// float32 pixels, the entries inside the packed patches (an index list: any int32 number, resolved to packed patch 0)
+static int ragged_dedup_list_check(const float* pixels, const ipsx_ragged_view* view, const int32_t* index, int64_t first,
+                                   int64_t n, const char* what) {
+    IPSX_REQUIRE(pixels && view && n >= 0 && first >= 0, "%s: bad arguments", what);
+    IPSX_REQUIRE(n < ((int64_t)1 << 31), "%s: too many entries", what);
+    const int64_t total = ragged_view_total(view, what);
+    if (total < 0) return IPSX_EINVAL;
+    IPSX_REQUIRE(view->images, "%s: no device table", what);
+    IPSX_REQUIRE(view->c == 1 && view->ph == 32 && view->pw == 32, "%s: blank-patch detection reads the 1x32x32 patches of the "
+                 "fused trunk, the view's are %dx%dx%d", what, view->c, view->ph, view->pw);
+    IPSX_REQUIRE(at_multiple(pixels, 4), "%s: images must lie at a 4-byte address", what);
+    IPSX_REQUIRE(index ? n <= 0x7FFFFFF0ll : first + n <= total, "%s: packed patches %lld .. %lld of %lld", what,
+                 (long long)first, (long long)(first + n), (long long)total);
+    return IPSX_OK;
+}
+
+static int ragged_blank_flags(const PatchSrc& src, int64_t n, int32_t* nonblank, hipStream_t s) {
+    blank_flags_ragged_view_kernel<<<dim3((unsigned)cdiv(n, 4)), dim3(256), 0, s>>>(static_cast<const float*>(src.base),
+                                                                                    ragged_view_args(src, 16), n, nonblank);
+    return launched("blank_flags_ragged_view");
+}
+
+IPSX_API int ipsx_ragged_view_blank_flags(const float* pixels, const ipsx_ragged_view* view, const int32_t* index,
+                                          int64_t first, int64_t n, int32_t* nonblank, void* stream) {
+    IPSX_TRY(ragged_dedup_list_check(pixels, view, index, first, n, "ragged_view_blank_flags"));
+    IPSX_REQUIRE(nonblank || n == 0, "ragged_view_blank_flags: no flags");
+    if (n == 0) return IPSX_OK;
+    return ragged_blank_flags(PatchSrc{pixels, nullptr, nullptr, index, index ? 0 : first, view}, n, nonblank, as_stream(stream));
+}
+
+IPSX_API int ipsx_trunk_encode_ragged_view_dedup(const ipsx_trunk* t, const float* pixels, const ipsx_ragged_view* view,
+                                                 const int32_t* index, int64_t first, int64_t n, float* emb, void* workspace,
+                                                 size_t workspace_bytes, int32_t* n_encoded, void* stream) {
+    const char* what = "trunk_encode_ragged_view_dedup";
+    IPSX_REQUIRE(t && emb, "%s: null pointer", what);
+    IPSX_TRY(ragged_dedup_list_check(pixels, view, index, first, n, what));
+    IPSX_REQUIRE(fused_trunk_supported(t) && t->precision == 0 && t->patch_dtype == 0 && t->c_in * t->h * t->w == PATCH_U4 * 4,
+                 "%s: the exact fp32 fused 1x32x32 trunk only", what);
+    const PatchSrc src{pixels, nullptr, nullptr, index, index ? 0 : first, view};
+    IPSX_TRY(patch_src_check(t, src, n, true, what));
+    IPSX_TRY(parts_trunk_check(t, what));                                 // what the trunk launch refuses: before the scan
+    if (n == 0) return IPSX_OK;
+    const size_t need = ipsx_trunk_ragged_view_dedup_workspace_bytes(t, n);
+    if (!workspace || workspace_bytes < need || !at_multiple(workspace, 16))
+        return fail(IPSX_EWORKSPACE, "%s: workspace %zu B < %zu B (at a 16-byte address)", what, workspace_bytes, need);
+    hipStream_t s = as_stream(stream);
+    int* nonblank = static_cast<int*>(workspace);
+    int* list = nonblank + n;
+    int* slot = list + n;
+    int* count = slot + n;
+    float* emb_u = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + (((size_t)n * 12 + 4 + 255) & ~(size_t)255));
+    IPSX_TRY(ragged_blank_flags(src, n, nonblank, s));
+    ragged_compact_kernel<<<dim3((unsigned)cdiv(n, 1024)), dim3(1024), 0, s>>>(nonblank, (int)n, index, src.first, list, slot, count);
+    IPSX_TRY(launched("ragged_compact"));
+    // the list holds packed patch numbers: the trunk reads it as an index list of up to n entries, *count of them written
+    IPSX_TRY(fused_launch(t, PatchSrc{pixels, nullptr, nullptr, list, 0, view}, n, emb_u, s, count));
+    scatter_rows_kernel<<<dim3((unsigned)cdiv(n * 32, 256)), dim3(256), 0, s>>>(
+        reinterpret_cast<const float4*>(emb_u), slot, reinterpret_cast<float4*>(emb), n, 32);
+    IPSX_TRY(launched("scatter_rows"));
+    if (n_encoded && hipMemcpyAsync(n_encoded, count, sizeof(int), hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return fail(IPSX_EHIP, "%s: count copy failed", what);
+    return IPSX_OK;
 }

@@ -1002,6 +1002,7 @@ static void fused_lds_attrs() {
         {reinterpret_cast<const void*>(fused_trunk_view_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_view_u8_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_ragged_view_kernel), FUSED_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_ragged_view_counted_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_parts_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_parts_view_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_parts_u8_kernel), FUSED_LDS},
@@ -1016,10 +1017,10 @@ static void fused_lds_attrs() {
 }
 
 // `n` patches of `src` (checked by the entry: patch_src_check) -> emb.  A table or a view: the exact fp32 trunk only, no
-// stamps, no device-side count.
+// stamps, no device-side count - but for a ragged view, which takes a count (ipsx_trunk_encode_ragged_view_dedup).
 int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, hipStream_t s, const int* count,
                  unsigned long long* stamps) {
-    if ((src.table || src.view || src.ragged) && (stamps || count))
+    if (((src.table || src.view) && (stamps || count)) || (src.ragged && stamps))
         return fail(IPSX_EINVAL, "fused trunk: uint8 patches and patch views go without stamps and device-side counts");
     FusedArgs a = fused_args(t, src, n, emb, true);
     a.count = count;
@@ -1079,7 +1080,8 @@ int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb
     if (src.ragged) {                                  // (the list travels with the table: the kernels resolve it themselves)
         FusedArgs ar = a, br = b;
         ar.index = nullptr; br.index = nullptr;
-        if (n_full) fused_trunk_ragged_view_kernel<<<grid8, dim3(512), FUSED_LDS, s>>>(ar, ragged_view_args(src, 16));
+        if (count) fused_trunk_ragged_view_counted_kernel<<<grid8, dim3(512), FUSED_LDS, s>>>(ar, ragged_view_args(src, 16));
+        else if (n_full) fused_trunk_ragged_view_kernel<<<grid8, dim3(512), FUSED_LDS, s>>>(ar, ragged_view_args(src, 16));
         if (rest) fused_trunk_pair_ragged_view_kernel<<<grid2, dim3(256), lds2, s>>>(br, ragged_view_args(tail, 16));
         return launched("fused_trunk_ragged_view");
     }

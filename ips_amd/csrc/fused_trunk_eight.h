@@ -787,6 +787,18 @@ __global__ __launch_bounds__(512, 1) void fused_trunk_ragged_view_kernel(FusedAr
     fused_trunk_body<false, false, false, true, false, RaggedAt>(a, nullptr, nullptr, nullptr, &at);
 }
 
+// ... behind the blank scan of a ragged view (ipsx_trunk_encode_ragged_view_dedup, dedup.hip): rv.index is the compacted list,
+// of which only the first *a.count entries are written - a workgroup beyond the count returns BEFORE it resolves a patch, so
+// nothing reads the list's tail; the body reads the same count for its own tail rule
+__global__ __launch_bounds__(512, 1) void fused_trunk_ragged_view_counted_kernel(FusedArgs a, RaggedViewArgs rv) {
+    const long long n_valid = *a.count;
+    if ((long long)blockIdx.x * 8 >= n_valid) return;                     // workgroup-uniform
+    long long j = (long long)blockIdx.x * 8 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (j >= n_valid) j = n_valid - 1;
+    const RaggedAt at = ragged_at(rv, j);
+    fused_trunk_body<false, false, false, true, false, RaggedAt>(a, nullptr, nullptr, nullptr, &at);
+}
+
 __global__ __launch_bounds__(512, 1) void fused_trunk_parts_view_kernel(FusedArgs a, PartsArgs pa, ViewArgs va) {
     fused_trunk_body<false, false, true, true>(a, nullptr, nullptr, &pa, &va);
 }

@@ -79,8 +79,9 @@ def dedup_blank():
 def dedup_auto():
     """IPSX_DEDUP_BLANK unset (or ``auto``): exact blank-patch dedup inside the one counted launch, wherever that route runs -
     float32 or uint8 patches, float32 or uint8 images (``selection.parts_one_launch``, ``ipsx_trunk_encode_parts_dedup`` and
-    its ``_u8`` / ``_view`` / ``_view_u8`` twins); every other route runs as under ``0`` and refuses nothing.  ``0``: no
-    dedup anywhere."""
+    its ``_u8`` / ``_view`` / ``_view_u8`` twins), and in the packed encoder pass of ``ips_image_ragged`` on the fused trunk
+    (``ragged_image.ragged_dedup``, ``ipsx_trunk_encode_ragged_view_dedup``); every other route runs as under ``0`` and
+    refuses nothing.  ``0``: no dedup anywhere."""
     return os.environ.get("IPSX_DEDUP_BLANK", "auto") == "auto"
 
 
@@ -416,6 +417,11 @@ _EXPORTS = {
                                                 C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ipsx_ragged_finish_view": (C.c_int, [C.c_void_p, C.POINTER(RaggedViewStruct), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ipsx_ragged_view_blank_flags": (C.c_int, [C.c_void_p, C.POINTER(RaggedViewStruct), C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                               C.c_void_p]),
+    "ipsx_trunk_ragged_view_dedup_workspace_bytes": (C.c_size_t, [C.POINTER(Trunk), C.c_int64]),
+    "ipsx_trunk_encode_ragged_view_dedup": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.POINTER(RaggedViewStruct), C.c_void_p, C.c_int64,
+                                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "ipsx_scan_ragged_spans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ipsx_stream_commit_ragged": (C.c_int, [C.POINTER(StreamTable), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64,
@@ -1297,6 +1303,29 @@ def ragged_finish_view(pixels, rview, offsets, mem_idx, M, flat=None, pos=None, 
                                       pos.shape[1] * pos.element_size() if pos is not None else 0, _p(out), _p(out_pos), _p(idx),
                                       _p(grow), _stream()), "ipsx_ragged_finish_view")
     return out, out_pos, idx, grow
+
+
+def ragged_blank_flags(pixels, rview, index=None, first=0, n=None):
+    """Which entries of a list of packed patches of a ragged view hold a non-zero pixel (``ipsx_ragged_view_blank_flags``)?
+    ``pixels`` the packed 1-d float32 buffer on the GPU, ``rview`` its ``RaggedView`` (1x32x32 patches); the entries are
+    packed patches ``index`` ((n,) int32 on the device; a number that is no packed patch reads packed patch 0) or
+    ``first .. first + n - 1`` (default: all from ``first`` on) -> (n,) int32, 1 = non-blank (-0.0 is zero, a denormal is
+    not): the rule of the exact blank-patch dedup, read where the patches lie."""
+    if pixels.dtype != torch.float32 or pixels.dim() != 1 or not pixels.is_contiguous() or not on_device(pixels):
+        raise ValueError("ragged_blank_flags needs the packed 1-d float32 buffer on the GPU")
+    if index is not None:
+        if index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous() or index.device != pixels.device:
+            raise ValueError("index must be a contiguous 1-d int32 tensor on the pixels' device")
+        first, n = 0, index.numel()
+    elif n is None:
+        n = rview.count - first
+    if first < 0 or n < 0 or (index is None and first + n > rview.count):
+        raise ValueError("patches {} .. {} of a view of {}".format(first, first + n, rview.count))
+    rview.on(pixels.device)
+    out = torch.empty((n,), dtype=torch.int32, device=pixels.device)
+    _ck(lib().ipsx_ragged_view_blank_flags(_p(pixels), C.byref(rview.struct), _p(index), first, n, _p(out), _stream()),
+        "ipsx_ragged_view_blank_flags")
+    return out
 
 
 def order_index(order, B, N, out=None):

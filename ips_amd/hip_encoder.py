@@ -315,8 +315,10 @@ class EncoderPlan:
         blank-patch dedup inside that launch (``ipsx_trunk_encode_parts_dedup`` and its ``_u8`` / ``_view`` / ``_view_u8``
         twins) - the same bits, the rows of the all-zero (bytes: all-zero-byte) entries written from ``blank_embedding``;
         ``n_encoded`` then holds the number of entries the trunk encoded.  A source with a ``hip.RaggedView`` (images of
-        different sizes in one packed buffer): ``index`` / ``first`` count packed patches, plain launches only
-        (``ipsx_trunk_encode_ragged_view``)."""
+        different sizes in one packed buffer): ``index`` / ``first`` count packed patches, no ``parts``
+        (``ipsx_trunk_encode_ragged_view``); ``dedup`` there, on the fused 1x32x32 trunk only (ValueError on any other): the
+        explicit route on plain launches - blank scan through the view, ordered compaction, the trunk over the non-blank
+        entries and ONE blank one, scatter (``ipsx_trunk_encode_ragged_view_dedup``) - the same bits, and ``n_encoded`` is set."""
         self._refresh()
         # the trunk struct describes THIS call's patches: nothing an earlier call or question left in it is read
         t, L = self._describe(src.shape, 0 if src.table is not None else _PATCH_DTYPES[src.dtype]), lib()
@@ -327,7 +329,9 @@ class EncoderPlan:
         rv = C.byref(src.ragged.struct) if src.ragged is not None else None
         if rv is not None and (parts is not None or not L.ipsx_trunk_ragged_view_supported(C.byref(t), rv)):
             raise ValueError("this encoder does not read patches through a ragged view (EncoderPlan.ragged_view_supported; "
-                             "plain launches only)")
+                             "no parts)")
+        if rv is not None and dedup and not L.ipsx_trunk_kernel(C.byref(t)).startswith(b"fused"):
+            raise ValueError("blank-patch dedup on a ragged view runs on the fused 1x32x32 trunk only (EncoderPlan.fused)")
         if index is not None:
             if index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous() or index.device != src.device:
                 raise ValueError("index must be a contiguous 1-d int32 tensor on the patches' device")
@@ -377,6 +381,14 @@ class EncoderPlan:
                 _ck(L.ipsx_trunk_encode_indexed_u8(tr, _p(base), tab, _p(index), n, _p(out), _stream()), "ipsx_trunk_encode_indexed_u8")
             else:
                 _ck(L.ipsx_trunk_encode_indexed(tr, _p(base), _p(index), n, _p(out), _stream()), "ipsx_trunk_encode_indexed")
+            return out
+        if rv is not None and dedup:                           # the explicit dedup route through the ragged view
+            nb = L.ipsx_trunk_ragged_view_dedup_workspace_bytes(tr, n)
+            if self.n_encoded is None or self.n_encoded.device != src.device:
+                self.n_encoded = torch.zeros((), dtype=torch.int32, device=src.device)
+            _ck(L.ipsx_trunk_encode_ragged_view_dedup(tr, _p(base), rv, _p(index), first, n, _p(out),
+                                                      _p(self._workspace(nb, src.device)), nb, _p(self.n_encoded), _stream()),
+                "ipsx_trunk_encode_ragged_view_dedup")
             return out
         flat = base if vs is not None or rv is not None else base.view(-1, *src.shape[-3:])
 

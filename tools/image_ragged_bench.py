@@ -12,8 +12,10 @@ baseline - the baseline is never the code under test:
 
 Legs on the head: ``solo`` (the loop of ips_image(image[None]) calls), ``patches`` (hip.patchify per image, then
 ips_ragged(list): the materialised route, its patch tensors made inside the timed call) and ``image_ragged``
-(ips_image_ragged on the packed RaggedImages).  Nothing is accepted or refused here.  Peak memory is the allocator's peak
-above what is allocated when the leg starts (the resident input: the images as a list and as one packed buffer)."""
+(ips_image_ragged on the packed RaggedImages, the environment as it is: the default), and, where the tree has the exact
+blank-patch dedup on the ragged view, ``image_ragged_plain`` (the same call under IPSX_DEDUP_BLANK=0: plain launches).  With
+``--parent`` the parent's ``solo`` and ``image_ragged`` legs are the baselines (profiles/ips_image_ragged_dedup.json).  Nothing
+is accepted or refused here.  Peak memory is the allocator's peak above what is allocated when the leg starts (the resident input: the images as a list and as one packed buffer)."""
 import argparse
 import json
 import os
@@ -77,6 +79,17 @@ def main():
             packed = RaggedImages.from_list(images)
             legs["patches"] = lambda: net.ips_ragged([hip.patchify(im[None], patch, stride)[0] for im in images])
             legs["image_ragged"] = lambda: net.ips_image_ragged(packed, patch, stride)
+            from ips_amd import ragged_image
+            if hasattr(ragged_image, "ragged_dedup"):
+                def under(key, value):
+                    def leg():
+                        os.environ[key] = value
+                        try:
+                            return net.ips_image_ragged(packed, patch, stride)
+                        finally:
+                            del os.environ[key]
+                    return leg
+                legs["image_ragged_plain"] = under("IPSX_DEDUP_BLANK", "0")
         times = {k: [] for k in legs}
         peaks = {}
         for rep in range(args.warmup + args.repeats):
@@ -104,6 +117,13 @@ def main():
             rec["parent_solo"] = ps
             for k in rec["legs"]:
                 rec["legs"][k]["over_parent_solo"] = rec["legs"][k]["median_ms"] / ps["median_ms"]
+            pr = parent[name]["legs"].get("image_ragged")
+            if pr is not None and "image_ragged" in rec["legs"]:
+                rec["parent_image_ragged"] = pr
+                for k in rec["legs"]:
+                    if k.startswith("image_ragged"):
+                        rec["legs"][k]["within_parent_image_ragged_spread"] = bool(rec["legs"][k]["median_ms"] <= pr["median_ms"] + pr["spread_ms"])
+                        rec["legs"][k]["within_parent_solo_spread"] = bool(rec["legs"][k]["median_ms"] <= ps["median_ms"] + ps["spread_ms"])
             if "image_ragged" in rec["legs"]:
                 rec["image_ragged_within_parent_spread"] = bool(rec["legs"]["image_ragged"]["median_ms"] <= ps["median_ms"] + ps["spread_ms"])
                 rec["image_ragged_peak_below_patches"] = bool(rec["legs"]["image_ragged"]["peak_bytes_above_input"] <
