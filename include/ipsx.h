@@ -245,7 +245,8 @@ int ipsx_conv2d_affine(const ipsx_conv* cv, const float* x, const float* residua
 int ipsx_conv2d_affine_to_nhwc(const ipsx_conv* cv, const float* x, const float* residual,
                                float* y, int64_t n, int h, int w, int relu, void* stream);
 /* the same on channels-last activations: x (n,h,w,c_in), residual / y (n,ho,wo,c_out); C_in % 32 == 0.
- * This is the fast layer-by-layer path (16-byte operand loads); a Linear over rows is h = w = 1. */
+ * This is the fast layer-by-layer path (16-byte operand loads); a Linear over rows is h = w = 1.
+ * Alignment: x, residual, y and w_packed at 16-byte addresses (no scalar route; not tested here - the caller's duty). */
 int ipsx_conv2d_affine_nhwc(const ipsx_conv* cv, const float* x, const float* residual,
                             float* y, int64_t n, int h, int w, int relu, void* stream);
 /* The same on the bf16 matrix pipe (3.03; the layer-by-layer trunk at precision 1): x, residual and y are bfloat16,
@@ -275,7 +276,8 @@ int ipsx_stem7x7s2_nhwc(const ipsx_conv* conv, const float* x, float* y, int64_t
 /* The data gradient of the 32-px trunk's strided convolution (64 -> 128 channels, 3x3 / 2, 8x8 -> 4x4 maps; the arguments of
  * _supported describe that FORWARD convolution): dy (n, 4, 4, 128) -> dx (n, 8, 8, 64), channels-last, taken by parity class
  * of the input pixel - nine taps instead of the thirty-six of a stride-1 convolution over dy spread on a zero map.
- * w_packed_dgrad: ipsx_pack_conv_weight_strided of the weights rotated by 180 degrees and transposed (128 -> 64, 3x3). */
+ * w_packed_dgrad: ipsx_pack_conv_weight_strided of the weights rotated by 180 degrees and transposed (128 -> 64, 3x3).
+ * Alignment: w_packed_dgrad, dy and dx at 16-byte addresses (float4 loads and stores, no scalar route). */
 int ipsx_conv2d_dgrad_s2_lds_nhwc_supported(int c_in, int c_out, int k, int stride, int pad, int h, int w);
 int ipsx_conv2d_dgrad_s2_lds_nhwc(const float* w_packed_dgrad, int k, const float* dy, float* dx, int64_t n, void* stream);
                                   /* k = 3 (pad 1), or k = 1: the 1x1 / 2 projection beside it (pad 0; three of four input pixels
@@ -295,6 +297,8 @@ int ipsx_conv2d_wgrad_nhwc_supported(int c_in, int c_out, int kh, int kw, int st
 size_t ipsx_conv2d_wgrad_nhwc_workspace_bytes(int64_t n, int c_in, int c_out, int kh, int kw);
 int ipsx_conv2d_wgrad_nhwc(const float* x, const float* dy, int64_t n, int h, int w, int c_in, int c_out, int kh, int kw,
                            int stride, int pad, float* dw, void* workspace, size_t workspace_bytes, void* stream);
+/* (x and y at 16-byte addresses, c % 4 == 0: float4 along the channels, no scalar route; the same holds for x, dy and dx of
+ * the backward pass below) */
 int ipsx_maxpool_3x3s2_nhwc(const float* x, float* y, int64_t n, int c, int h, int w, void* stream);
 /* Its backward pass for the training step (16 x 16 maps, C % 32 == 0): dx (n, 16, 16, C) from x and dy (n, 8, 8, C), the
  * gradient of a window to its first maximum in row-major order - ATen's max_pool2d_with_indices_backward bit for bit, without
@@ -481,7 +485,8 @@ int ipsx_patchify(const float* img, int b, int c, int h, int w, int ph, int pw, 
  * canvas (the reference's _img_shape), value its pixel.  patches is zeroed and filled; nonblank
  * (b*ny*nx int32, or NULL) is set to 1 for every patch that received a non-zero value.  Indices
  * outside the canvas are skipped (the host validates them before upload; numpy would raise).
- * offsets, index and value are device pointers; nnz = offsets[b].                                  */
+ * offsets, index and value are device pointers; nnz = offsets[b] - and no entry at or past nnz is read, whatever
+ * offsets[b] holds: nnz is what index and value are known to hold.  Element-sized loads only (any aligned int64 / float). */
 int ipsx_patchify_sparse(const int64_t* index, const float* value, const int64_t* offsets, int64_t nnz,
                          int b, int c, int h, int w, int ph, int pw, int sh, int sw,
                          float* patches, int32_t* nonblank, void* stream);
@@ -601,7 +606,12 @@ int ipsx_query_proj(const float* q, const float* wq, float temperature,
  * H*Dk*D, so the kernel is bound by reading the embeddings.
  * emb (b,n,d) with batch stride emb_bstride (floats); pos (b|1,n,d) or NULL, pos_bstride = 0 broadcasts one
  * (n,d) table over the batch; wk_packed = ipsx_pack_conv_weight of k_w.weight viewed as (H*Dk, D, 1, 1);
- * v_packed: ipsx_folded_query_elems(h, n_token, d) floats; r = h * n_token; logits (b,n,r).            */
+ * v_packed: ipsx_folded_query_elems(h, n_token, d) floats; r = h * n_token; logits (b,n,r).
+ * Alignment: v_packed at a 16-byte address, always; with d % 8 == 0 the rows of emb and pos are read with 16-byte loads
+ * and there is no scalar route - emb, pos at 16-byte addresses, emb_bstride and pos_bstride multiples of 4 floats (d % 8 != 0
+ * takes 4-byte loads).  logits is written with 4-byte stores: any row range of a longer table.  The same holds for
+ * ipsx_logits_if, ipsx_logits_stats (stats_out: 8-byte stores), x of ipsx_scores and x of ipsx_aggregate*.  None of this is
+ * tested by the entry points: ips_amd/hip.py copies a read-only view that misses it. */
 size_t ipsx_folded_query_elems(int h, int n_token, int d);
 int ipsx_fold_query(const float* qs, const float* wk_packed, int h, int dk, int n_token, int d,
                     float* v_packed, void* stream);
@@ -647,7 +657,10 @@ int ipsx_set_tie_order(int mode);
  * mem_idx (b,m) int64 = selected patch indices in final score order;
  * mem_score (b,m) or NULL; tie_flag (b) int32 or NULL: set when two candidates
  * straddling a top-m boundary had bit-equal scores (the reference's own order is
- * then implementation-defined, ips_net.py:199).                               */
+ * then implementation-defined, ips_net.py:199).
+ * Alignment (every ipsx_scan* entry point): logits at a 16-byte address - the loops
+ * for candidate sets beyond the LDS and the 8-row shapes load rows as float4 and
+ * have no scalar route; mem_idx 8, mem_score / tie_flag / the int32 words 4.     */
 int ipsx_scan(const float* logits, int b, int64_t n, int m, int i, int h, int n_token,
               int64_t* mem_idx, float* mem_score, int32_t* tie_flag,
               void* workspace, size_t workspace_bytes, void* stream);
@@ -1018,7 +1031,10 @@ int ipsx_head(const float* emb, int b, int n_token, int d, int token,
  *   backward: g = dy masked by y > 0 (when relu); dbeta = sum g; dgamma = sum g * xhat;
  *             dx = gamma * invstd * (g - dbeta / rows - xhat * dgamma / rows); dresidual = g (when not NULL).
  * c / 4 must be a power of two <= 256 (ipsx_bn_train_supported); workspace: ipsx_bn_train_workspace_floats floats.
- * fp32 results to rounding of torch.nn.functional.batch_norm (another summation order), deterministic.          */
+ * fp32 results to rounding of torch.nn.functional.batch_norm (another summation order), deterministic.
+ * Alignment: x, residual, y, dy, dx, dresidual, gamma, beta, save_mean, save_invstd, dgamma, dbeta, partial and the workspace
+ * at 16-byte addresses (whole float4, no scalar route; c % 4 == 0 keeps the rows there); running_mean, running_var and
+ * shift are read and written one float per channel: any float address, e.g. a slice of a longer buffer.        */
 int ipsx_bn_train_supported(int64_t rows, int c);
 size_t ipsx_bn_train_workspace_floats(int64_t rows, int c);
 int ipsx_bn_train_forward(const float* x, const float* residual, int64_t rows, int c, const float* gamma,
@@ -1073,7 +1089,8 @@ int ipsx_projector_wgrad(const void* x, int dtype, const float* dz, const float*
  * go through per-workgroup blocks in the workspace, added in ascending (b, row) order: the same bits every call, and an
  * image's Z, P and dx do not depend on the rest of the batch.  R 1 .. 32, D a multiple of 32 up to 1024
  * (ipsx_attn_pool_supported), any M >= 1, B <= 65535.  workspace: ipsx_attn_pool_workspace_bytes(B, M, R, D), either
- * direction.  No allocation, no host synchronisation (graph-capturable). */
+ * direction.  No allocation, no host synchronisation (graph-capturable).  Alignment: x, A, dZ, Z, dx and dA at 16-byte
+ * addresses (rows of D % 32 == 0 floats read and written as float4, no scalar route). */
 int ipsx_attn_pool_supported(int R, int D);
 size_t ipsx_attn_pool_workspace_bytes(int64_t B, int64_t M, int R, int D);
 int ipsx_attn_pool_forward(const float* x, const float* A, const float* keep, int64_t B, int64_t M, int R, int D, float* Z,

@@ -95,10 +95,10 @@ __global__ __launch_bounds__(256) void gather_patches_view_u8_kernel(const unsig
 // one thread per non-zero; the image of a non-zero is found by bisection of the (B+1) offsets
 __global__ __launch_bounds__(256) void patchify_sparse_kernel(const long long* __restrict__ index,
                                                               const float* __restrict__ value,
-                                                              const long long* __restrict__ offsets, int b, PatchGeom g,
-                                                              float* __restrict__ out, int* __restrict__ nonblank) {
+                                                              const long long* __restrict__ offsets, long long nnz, int b,
+                                                              PatchGeom g, float* __restrict__ out, int* __restrict__ nonblank) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= offsets[b]) return;
+    if (e >= nnz || e >= offsets[b]) return;          // (nnz: what index / value hold - offsets[b] is device data the host never saw)
     int lo = 0, hi = b;                               // offsets[lo] <= e < offsets[hi]
     while (hi - lo > 1) {
         const int mid = (lo + hi) >> 1;
@@ -176,7 +176,7 @@ IPSX_API int ipsx_patchify_sparse(const int64_t* index, const float* value, cons
         return fail(IPSX_EHIP, "patchify_sparse: memset failed");
     if (nnz == 0) return IPSX_OK;
     patchify_sparse_kernel<<<dim3((unsigned)cdiv(nnz, 256)), dim3(256), 0, s>>>(
-        reinterpret_cast<const long long*>(index), value, reinterpret_cast<const long long*>(offsets), b, g, patches,
+        reinterpret_cast<const long long*>(index), value, reinterpret_cast<const long long*>(offsets), (long long)nnz, b, g, patches,
         reinterpret_cast<int*>(nonblank));
     return launched("patchify_sparse");
 }

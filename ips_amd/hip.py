@@ -134,7 +134,13 @@ def on_device(x):
         dev = x.device
     else:
         dev = torch.device(x)
-    return dev.type == "cuda" and backend() == "hip"
+    return _gpu_device(dev) and backend() == "hip"
+
+
+def _gpu_device(dev):
+    """Is ``dev`` a GPU?  THE device test of ``on_device`` and of every wrapper's arguments (``_one_gpu``): a test without
+    a GPU switches it here."""
+    return dev.type == "cuda"
 
 
 # ------------------------------------------------------------------ C structs
@@ -524,6 +530,63 @@ def _f32(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+# The argument contract of every wrapper below and in hip_train.py: three helpers, attribute comparisons
+# only - nothing that synchronises, allocates or launches while the arguments are valid.
+def _same_gpu(what, names, *tensors):
+    """Every tensor of a call (None: absent) lies on ONE GPU -> that device.  (``names``: of ``tensors``, for the message - the
+    positional form of ``_one_gpu`` for the wrappers a selection calls many times.)"""
+    dev = None
+    for t in tensors:
+        if t is not None:
+            d = t.device
+            if dev is None:
+                if not _gpu_device(d):
+                    raise ValueError("{}: {} lies on {}, the kernels read and write GPU memory".format(
+                        what, [n for n, u in zip(names, tensors) if u is t][0], d))
+                dev = d
+            elif d != dev:
+                raise ValueError("{}: {} lies on {}, the call's other tensors on {}".format(
+                    what, [n for n, u in zip(names, tensors) if u is t][0], d, dev))
+    return dev
+
+
+def _one_gpu(what, **tensors):
+    """Every tensor of a call (None: absent) lies on ONE GPU -> that device."""
+    return _same_gpu(what, tuple(tensors), *tensors.values())
+
+
+def _rd(what, name, t, dtype=torch.float32, dim=None, align=16, cl=False):
+    """A tensor the kernel only READS, as the kernel takes it.  Another dtype or rank is refused (an index tensor is never
+    converted); another layout - transposed, strided, sliced, expanded, channels-first where ``cl`` asks for channels-last -
+    is copied, and so is a tensor whose address is no multiple of ``align`` (a fresh allocation is)."""
+    if t.dtype != dtype:
+        raise TypeError("{}: {} must be {}, got {}".format(what, name, dtype, t.dtype))
+    if dim is not None and t.dim() != dim:
+        raise ValueError("{}: {} must have {} dimensions, got {}".format(what, name, dim, tuple(t.shape)))
+    if cl:
+        if not t.is_contiguous(memory_format=torch.channels_last):
+            return t.contiguous(memory_format=torch.channels_last)
+    elif not t.is_contiguous():
+        return t.contiguous()
+    return t.clone() if t.data_ptr() % align else t
+
+
+def _wr(what, name, t, dtype, shape=None, align=1, cl=False):
+    """A tensor the kernel WRITES (outputs, loop state, workspaces, flags): handed over where it lies, never copied - so
+    another dtype, shape, layout or an address that is no multiple of ``align`` is refused."""
+    if t.dtype != dtype or (shape is not None and tuple(t.shape) != tuple(shape)) or t.data_ptr() % align or \
+            not (t.is_contiguous(memory_format=torch.channels_last) if cl else t.is_contiguous()):
+        raise ValueError("{}: {} must be a {}{} {} tensor{}, got {} {} with strides {} at an address {} mod 16".format(
+            what, name, "channels-last" if cl else "contiguous", " " + str(tuple(shape)) if shape is not None else "", dtype,
+            " at a {}-byte address".format(align) if align > 1 else "", t.dtype, tuple(t.shape), t.stride(), t.data_ptr() % 16))
+    return t
+
+
+def _workspace(what, ws):
+    """A caller's workspace: contiguous uint8 bytes (None: the wrapper allocates)."""
+    return _wr(what, "workspace", ws, torch.uint8, align=16) if ws is not None else None
+
+
 _PATCH_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
 
@@ -562,7 +625,10 @@ def _patches(t, table=None):
 # ------------------------------------------------------------------ scorer
 def query_proj(q, wq, temperature):
     """(T, D) queries, (H*Dk, D) weight -> (T, H*Dk) = (q @ wq.T) / temperature."""
-    q, wq = _f32(q.detach()), _f32(wq.detach())
+    _one_gpu("query_proj", q=q, wq=wq)
+    q, wq = _rd("query_proj", "q", q.detach(), dim=2, align=4), _rd("query_proj", "wq", wq.detach(), dim=2, align=4)
+    if q.shape[1] != wq.shape[1]:
+        raise ValueError("query_proj: q has {} features, wq takes {}".format(q.shape[1], wq.shape[1]))
     out = torch.empty((q.shape[0], wq.shape[0]), dtype=torch.float32, device=q.device)
     _ck(lib().ipsx_query_proj(_p(q), _p(wq), C.c_float(temperature), q.shape[0], q.shape[1],
                               wq.shape[0], _p(out), _stream()), "ipsx_query_proj")
@@ -572,24 +638,38 @@ def query_proj(q, wq, temperature):
 def pack_linear(weight):
     """nn.Linear weight (out, in) -> MFMA B-operand stream (a 1x1 convolution)."""
     w = weight.detach()
+    if w.dim() != 2:
+        raise ValueError("pack_linear: weight must be (out, in), got {}".format(tuple(w.shape)))
     return _pack_conv(w.reshape(w.shape[0], w.shape[1], 1, 1))
+
+
+def _fold_args(what, qs, wk_weight, H, Dk, T):
+    """(T, H*Dk) scaled query and (H*Dk, D) key weight on one GPU -> qs as the kernel reads it, D."""
+    _one_gpu(what, qs=qs, wk_weight=wk_weight)
+    qs = _rd(what, "qs", qs.detach(), dim=2, align=4)          # (fold_query_kernel: 4-byte loads)
+    if wk_weight.dtype != torch.float32 or wk_weight.dim() != 2:
+        raise TypeError("{}: wk_weight must be a float32 (H*Dk, D) matrix, got {} {}".format(what, wk_weight.dtype, tuple(wk_weight.shape)))
+    if tuple(qs.shape) != (T, H * Dk) or wk_weight.shape[0] != H * Dk:
+        raise ValueError("{}: qs must be ({}, {}) and wk_weight ({}, D), got {} and {}".format(
+            what, T, H * Dk, H * Dk, tuple(qs.shape), tuple(wk_weight.shape)))
+    return qs, wk_weight.shape[1]
 
 
 def fold_query(qs, wk_weight, H, Dk, T):
     """Scaled query (T, H*Dk) folded into the key weights k_w.weight (H*Dk, D) -> packed (H*T, D) operand of
     ``logits`` (ipsx_fold_query): logit = x . V[h*T + t],  V[h*T + t] = sum_j qs[t][h, j] k_w[h*Dk + j]."""
-    D = wk_weight.shape[1]
+    qs, D = _fold_args("fold_query", qs, wk_weight, H, Dk, T)
     out = torch.empty(lib().ipsx_folded_query_elems(H, T, D), dtype=torch.float32, device=qs.device)
-    _ck(lib().ipsx_fold_query(_p(_f32(qs)), _p(pack_linear(wk_weight)), H, Dk, T, D, _p(out), _stream()), "ipsx_fold_query")
+    _ck(lib().ipsx_fold_query(_p(qs), _p(pack_linear(wk_weight)), H, Dk, T, D, _p(out), _stream()), "ipsx_fold_query")
     return out
 
 
 def fold_query_bf16(qs, wk_weight, H, Dk, T):
     """The folded query rounded to bfloat16 in the operand layout of ``ipsx_logits_bf16`` (a uint8 tensor: that dtype is
     how ``logits`` tells the two apart)."""
-    D = wk_weight.shape[1]
+    qs, D = _fold_args("fold_query_bf16", qs, wk_weight, H, Dk, T)
     out = torch.empty(lib().ipsx_folded_query_bf16_bytes(H, T, D), dtype=torch.uint8, device=qs.device)
-    _ck(lib().ipsx_fold_query_bf16(_p(_f32(qs)), _p(pack_linear(wk_weight)), H, Dk, T, D, _p(out), _stream()),
+    _ck(lib().ipsx_fold_query_bf16(_p(qs), _p(pack_linear(wk_weight)), H, Dk, T, D, _p(out), _stream()),
         "ipsx_fold_query_bf16")
     return out
 
@@ -598,17 +678,8 @@ def logits(emb, pos, vq, R, out=None, cond=None, mask=1):
     """Per-patch attention logits (B, n, R = H*T) from the folded query ``vq``; ``out`` may be a column slice of
     (B, N, R).  A bfloat16 folded query (``fold_query_bf16``) selects the bf16 matrix pipe.  ``cond`` (int32 device
     scalar; fp32 folded query only): a conditional launch that does nothing unless a bit of ``mask`` is set in it."""
+    emb, pos, pos_bs, out = _logits_args("logits", emb, pos, vq, R, out, cond)
     B, n, D = emb.shape
-    emb = _f32(emb)
-    if out is None:
-        out = torch.empty((B, n, R), dtype=torch.float32, device=emb.device)
-    if out.stride(2) != 1 or out.stride(1) != R:
-        raise ValueError("logits output must be row-contiguous")
-    pos_bs = 0
-    if pos is not None:
-        if pos.stride(2) != 1 or pos.stride(1) != D:
-            pos = pos.contiguous()
-        pos_bs = pos.stride(0) if pos.shape[0] > 1 else 0
     if vq.dtype == torch.uint8:
         if cond is not None:
             raise ValueError("conditional logits: fp32 folded query only")
@@ -624,28 +695,94 @@ def logits(emb, pos, vq, R, out=None, cond=None, mask=1):
     return out
 
 
+_VQ_SIZE = {}
+
+
+def _logits_args(what, emb, pos, vq, R, out, cond):
+    """The arguments of the logits kernels, checked -> (emb, pos, pos_bstride, out) as the kernel takes them.  ``emb`` /
+    ``pos`` are read with 16-byte loads when D % 8 == 0 (csrc/logits.hip ``logits_wave``: no scalar route at that D), so a
+    view at another address or with rows that are not D apart is copied; ``out`` is written with 4-byte stores, row by row.
+    (Called ten times per ``ips()``: plain comparisons, written out.)"""
+    _same_gpu(what, _LOGITS_NAMES, emb, pos, vq, out, cond)
+    shape = emb.shape
+    if emb.dtype != torch.float32:
+        raise TypeError("{}: emb must be float32, got {}".format(what, emb.dtype))
+    if len(shape) != 3:
+        raise ValueError("{}: emb must be (B, n, D), got {}".format(what, tuple(shape)))
+    B, n, D = shape
+    align = 4 if D & 7 else 16
+    if not emb.is_contiguous():
+        emb = emb.contiguous()
+    elif emb.data_ptr() % align:
+        emb = emb.clone()
+    size = _VQ_SIZE.get((vq.dtype, R, D))
+    if size is None:
+        if vq.dtype == torch.float32:
+            size = lib().ipsx_folded_query_elems(R, 1, D)
+        elif vq.dtype == torch.uint8:
+            size = lib().ipsx_folded_query_bf16_bytes(R, 1, D)
+        else:
+            raise TypeError("{}: vq must be a folded query (float32, or uint8 bytes of bfloat16), got {}".format(what, vq.dtype))
+        _VQ_SIZE[(vq.dtype, R, D)] = size
+    if vq.numel() != size or vq.data_ptr() & 15 or not vq.is_contiguous():
+        raise ValueError("{}: vq must be the contiguous folded query of R = {}, D = {} ({} elements at a 16-byte address), got {}".format(
+            what, R, D, size, tuple(vq.shape)))
+    if out is None:
+        out = torch.empty((B, n, R), dtype=torch.float32, device=emb.device)
+    else:
+        st = out.stride()
+        if out.dtype != torch.float32 or out.shape != (B, n, R) or st[2] != 1 or st[1] != R or (B > 1 and st[0] < n * R):
+            raise ValueError("{}: out must be float32 ({}, {}, {}) with contiguous rows (a row range of a longer table), got {} {} "
+                             "with strides {}".format(what, B, n, R, out.dtype, tuple(out.shape), st))
+    pos_bs = 0
+    if pos is not None:
+        ps = pos.shape
+        if pos.dtype != torch.float32:
+            raise TypeError("{}: pos must be float32, got {}".format(what, pos.dtype))
+        if len(ps) != 3 or ps[1] != n or ps[2] != D or (ps[0] != B and ps[0] != 1):
+            raise ValueError("{}: pos must be ({} or 1, {}, {}), got {}".format(what, B, n, D, tuple(ps)))
+        st = pos.stride()
+        pos_bs = st[0] if ps[0] > 1 else 0
+        if st[2] != 1 or st[1] != D or pos_bs < 0 or pos.data_ptr() % align or (pos_bs * 4) % align:
+            pos = pos.clone() if pos.is_contiguous() else pos.contiguous()
+            pos_bs = pos.stride(0) if ps[0] > 1 else 0
+    if cond is not None:
+        _word(what, "cond", cond)
+    return emb, pos, pos_bs, out
+
+
+_LOGITS_NAMES = ("emb", "pos", "vq", "out", "cond")
+
+
+def _word(what, name, t, n=1):
+    """An int32 flag / counter the kernels poll or set: ``n`` contiguous words on the GPU."""
+    if t.dtype != torch.int32 or t.numel() != n or not t.is_contiguous():
+        raise ValueError("{}: {} must hold {} contiguous int32 word(s), got {} {}".format(what, name, n, t.dtype, tuple(t.shape)))
+    return t
+
+
 def part_wait(done, want, status, bit=1):
     """Hold the current stream until the counter ``done`` (int32 device scalar, a part of ``EncoderPlan.encode_indexed``'s
     one launch) has reached ``want``; a wait without progress for ``persistent_wait_ms`` sets ``bit`` in ``status``."""
+    _same_gpu("part_wait", ("done", "status"), done, status)
+    _word("part_wait", "done", done)
+    _word("part_wait", "status", status)
     _ck(lib().ipsx_part_wait(_p(done), int(want), _p(status), int(bit), _stream()), "ipsx_part_wait")
 
 
 def logits_stats(emb, pos, vq, R, out, stats_x, stats_out, ln_eps):
     """``logits(emb, pos, vq, R, out)`` and, in the same launch, the LayerNorm row moments of ``stats_x`` (P, F) into
     ``stats_out`` (P, 2).  fp32 folded query only."""
-    B, n, D = emb.shape
-    emb = _f32(emb)
-    if out.stride(2) != 1 or out.stride(1) != R:
-        raise ValueError("logits output must be row-contiguous")
-    pos_bs = 0
-    if pos is not None:
-        if pos.stride(2) != 1 or pos.stride(1) != D:
-            pos = pos.contiguous()
-        pos_bs = pos.stride(0) if pos.shape[0] > 1 else 0
-    stats_x = _f32(stats_x)
+    _same_gpu("logits_stats", ("emb", "stats_x", "stats_out"), emb, stats_x, stats_out)
+    if vq.dtype != torch.float32:
+        raise TypeError("logits_stats: vq must be the float32 folded query, got {}".format(vq.dtype))
+    if out is None:
+        raise ValueError("logits_stats: out must be given")
+    stats_x = _rd("logits_stats", "stats_x", stats_x, dim=2)
     sn, sf = stats_x.shape
-    if tuple(stats_out.shape) != (sn, 2) or stats_out.dtype != torch.float32 or not stats_out.is_contiguous():
-        raise ValueError("stats_out must be a contiguous (P, 2) float32 tensor")
+    _wr("logits_stats", "stats_out", stats_out, torch.float32, (sn, 2), align=8)
+    emb, pos, pos_bs, out = _logits_args("logits_stats", emb, pos, vq, R, out, None)
+    B, n, D = emb.shape
     _ck(lib().ipsx_logits_stats(_p(emb), n * D, _p(pos), pos_bs, _p(vq), B, n, D, R, _p(out), out.stride(0),
                                 _p(stats_x), sn, sf, C.c_float(ln_eps), _p(stats_out), _stream()), "ipsx_logits_stats")
     return out
@@ -664,10 +801,40 @@ def scan_workgroups_per_image(B, M, I, H, T):
     return max(1, int(lib().ipsx_scan_workgroups_per_image(B, M, I, H, T)))
 
 
+def _scan_args(what, lg, M, I, H, T, mem_idx=None, tie=None, workspace=None, copy=True, words=()):
+    """The arguments of a selection loop on a (B, N, H*T) float32 logits table, checked -> (lg, B, N).  The loops read
+    ``lg`` rows with 16-byte loads (csrc/scan_large.hip, scan_cam.hip): a view is copied where the loop only reads a
+    finished table (``copy``) and refused where producers still write it; ``mem_idx`` (B, M) int64 and ``tie`` (B,) int32
+    are loop state, ``words`` int32 flags: handed over where they lie."""
+    _same_gpu(what, _SCAN_NAMES, lg, mem_idx, tie, workspace, *words)
+    shape = lg.shape
+    if len(shape) != 3 or shape[2] != H * T:
+        raise ValueError("{}: lg must be (B, N, H*T = {}), got {}".format(what, H * T, tuple(shape)))
+    B, N = shape[0], shape[1]
+    if N <= M:
+        raise ValueError("{}: lg has N = {} rows per image, the loop needs more than M = {}".format(what, N, M))
+    if lg.dtype != torch.float32:
+        raise TypeError("{}: lg must be float32, got {}".format(what, lg.dtype))
+    if not lg.is_contiguous() or lg.data_ptr() & 15:
+        if not copy:
+            raise ValueError("{}: lg must be the whole contiguous (B, N, H*T) table at a 16-byte address (it is read where it "
+                             "lies), got strides {}".format(what, lg.stride()))
+        lg = lg.clone() if lg.is_contiguous() else lg.contiguous()
+    if mem_idx is not None and (mem_idx.dtype != torch.int64 or mem_idx.shape != (B, M) or not mem_idx.is_contiguous()):
+        raise ValueError("{}: mem_idx must be a contiguous ({}, {}) int64 tensor, got {} {}".format(what, B, M, mem_idx.dtype, tuple(mem_idx.shape)))
+    if tie is not None and (tie.dtype != torch.int32 or tie.shape != (B,) or not tie.is_contiguous()):
+        raise ValueError("{}: tie must be a contiguous ({},) int32 tensor, got {} {}".format(what, B, tie.dtype, tuple(tie.shape)))
+    if workspace is not None:
+        _workspace(what, workspace)
+    return lg, B, N
+
+
+_SCAN_NAMES = ("lg", "mem_idx", "tie", "workspace", "cond / ready", "status")
+
+
 def scan(lg, M, I, H, T, want_scores=False):
     """The IPS chunk loop on cached logits (B, N, H*T) -> mem_idx (B, M) int64."""
-    lg = _f32(lg)
-    B, N = lg.shape[:2]
+    lg, B, N = _scan_args("scan", lg, M, I, H, T)
     mem_idx = torch.empty((B, M), dtype=torch.int64, device=lg.device)
     sc = torch.empty((B, M), dtype=torch.float32, device=lg.device) if want_scores else None
     tie = torch.zeros((B,), dtype=torch.int32, device=lg.device)
@@ -681,9 +848,7 @@ def scan(lg, M, I, H, T, want_scores=False):
 def scan_range(lg, M, I, H, T, it_begin, it_end, mem_idx, tie, workspace=None):
     """Iterations [it_begin, it_end) of the loop, state carried in ``mem_idx`` (B, M) int64 / ``tie`` (B,) int32.
     ``workspace``: ``scan_workspace(...)`` kept by the caller; allocated here (on the current stream) when missing."""
-    B, N = lg.shape[:2]
-    if not lg.is_contiguous():
-        raise ValueError("scan_range needs the full contiguous (B, N, H*T) logits buffer")
+    lg, B, N = _scan_args("scan_range", lg, M, I, H, T, mem_idx, tie, workspace)
     ws = workspace if workspace is not None else scan_workspace(B, M, I, H, T, lg.device)
     _ck(lib().ipsx_scan_range(_p(lg), B, N, M, I, H, T, it_begin, it_end, _p(mem_idx), None, _p(tie),
                               _p(ws), ws.numel() if ws is not None else 0, _stream()), "ipsx_scan_range")
@@ -697,8 +862,14 @@ def scan_range_strided(lg, n, M, I, H, T, it_begin, it_end, mem_idx, tie, worksp
     B, cap = lg.shape[:2]
     if lg.dtype != torch.float32 or lg.dim() != 3 or lg.stride(2) != 1 or lg.stride(1) != lg.shape[2] or (B > 1 and lg.stride(0) != cap * lg.shape[2]):
         raise ValueError("scan_range_strided needs a row-contiguous float32 (B, cap, H*T) logits table")
+    if lg.shape[2] != H * T or lg.data_ptr() % 16:
+        raise ValueError("scan_range_strided: lg must have H*T = {} columns and lie at a 16-byte address, got {}".format(H * T, tuple(lg.shape)))
     if not 0 < n <= cap:
         raise ValueError("{} candidates in a table of {} rows".format(n, cap))
+    _one_gpu("scan_range_strided", lg=lg, mem_idx=mem_idx, tie=tie, workspace=workspace)
+    _wr("scan_range_strided", "mem_idx", mem_idx, torch.int64, (B, M))
+    _wr("scan_range_strided", "tie", tie, torch.int32, (B,))
+    _workspace("scan_range_strided", workspace)
     ws = workspace if workspace is not None else scan_workspace(B, M, I, H, T, lg.device)
     _ck(lib().ipsx_scan_range_strided(_p(lg), cap, B, n, M, I, H, T, it_begin, it_end, _p(mem_idx), None, _p(tie),
                                       _p(ws), ws.numel() if ws is not None else 0, _stream()), "ipsx_scan_range_strided")
@@ -717,6 +888,10 @@ def scan_ragged(lg, offsets, lengths, M, I, H, T, want_scores=False, workspace=N
     B, total = len(lengths), sum(lengths)
     if B == 0:
         raise ValueError("scan_ragged: no slides")
+    _one_gpu("scan_ragged", lg=lg, offsets=offsets, workspace=workspace)
+    _workspace("scan_ragged", workspace)
+    if lg.data_ptr() % 16:
+        raise ValueError("scan_ragged: lg must lie at a 16-byte address")
     if lg.dtype != torch.float32 or lg.dim() != 2 or not lg.is_contiguous() or lg.shape != (total, H * T):
         raise ValueError("scan_ragged needs a contiguous float32 ({}, {}) logits table, got {} {}".format(
             total, H * T, lg.dtype, tuple(lg.shape)))
@@ -741,9 +916,13 @@ def scan_ragged(lg, offsets, lengths, M, I, H, T, want_scores=False, workspace=N
 
 
 def _on_gpu(what, *tensors):
+    dev = None
     for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise ValueError("{}: every tensor lies on the GPU (got one on {})".format(what, t.device))
+        if t is None:
+            continue
+        if not _gpu_device(t.device) or (dev is not None and t.device != dev):
+            raise ValueError("{}: every tensor lies on the GPU, all on the same one (got one on {})".format(what, t.device))
+        dev = t.device
 
 
 def scan_ragged_spans(lg, spans, n_max, M, I, H, T, mem_idx, tie, mem_score=None, workspace=None):
@@ -753,9 +932,10 @@ def scan_ragged_spans(lg, spans, n_max, M, I, H, T, mem_idx, tie, mem_score=None
     (B,) int32 are the caller's: a slide whose count is not above ``M``, or whose span leaves the table, is left untouched
     in all three, and ``tie`` is only ever set (the caller clears it)."""
     _on_gpu("scan_ragged_spans", lg, spans, mem_idx, tie, mem_score, workspace)
-    if lg.dtype != torch.float32 or lg.dim() != 2 or not lg.is_contiguous() or lg.shape[1] != H * T:
-        raise ValueError("scan_ragged_spans needs a contiguous float32 (rows, {}) logits table, got {} {}".format(
+    if lg.dtype != torch.float32 or lg.dim() != 2 or not lg.is_contiguous() or lg.shape[1] != H * T or lg.data_ptr() % 16:
+        raise ValueError("scan_ragged_spans needs a contiguous float32 (rows, {}) logits table at a 16-byte address, got {} {}".format(
             H * T, lg.dtype, tuple(lg.shape)))
+    _workspace("scan_ragged_spans", workspace)
     B = spans.shape[0] if spans.dim() == 2 else 0
     if spans.dtype != torch.int64 or tuple(spans.shape) != (B, 2) or B == 0 or not spans.is_contiguous() or spans.device != lg.device:
         raise ValueError("scan_ragged_spans needs (B, 2) int64 spans on the logits' device")
@@ -820,6 +1000,8 @@ def stream_commit_ragged(tables, sel, slides, M, rows_max):
 def _stream_tables(tables, n_cand):
     """``(held, held_rows, piece, dst)`` tuples -> (the ``ipsx_stream_table`` array, B); the checks a tensor allows before
     the library's own."""
+    if len(tables) > 4:
+        raise ValueError("{} tables: a commit moves at most four".format(len(tables)))
     arr = (StreamTable * max(1, len(tables)))()
     B = None
     for k, (held, held_rows, piece, dst) in enumerate(tables[:len(arr)]):
@@ -867,7 +1049,8 @@ def stream_commit(tables, sel, M, n_cand, tail_first=0):
     arr, B = _stream_tables(tables, n_cand)
     if sel is not None and (sel.dtype != torch.int64 or tuple(sel.shape) != (B, M) or not sel.is_contiguous()):
         raise ValueError("sel must be a contiguous (B, M) int64 tensor")
-    st = _stream() if len(tables) and tables[0][3].is_cuda else None       # (host tensors: refused by the library's own checks)
+    _on_gpu("stream_commit", sel, *[t for tab in tables for t in (tab[0], tab[2], tab[3])])
+    st = _stream() if len(tables) else None
     _ck(lib().ipsx_stream_commit(arr, len(tables), _p(sel), B or 0, M, n_cand, tail_first, st), "ipsx_stream_commit")
 
 
@@ -896,7 +1079,8 @@ def stream_commit_view(tables, images, view, sel, M, n_cand, tail_first=0):
     if sel is not None and (sel.dtype != torch.int64 or tuple(sel.shape) != (B, M) or not sel.is_contiguous()):
         raise ValueError("sel must be a contiguous (B, M) int64 tensor")
     unit = C.c_int(0)
-    st = _stream() if images.is_cuda else None               # (host tensors: refused by the library's own checks)
+    _on_gpu("stream_commit_view", images, sel, *[t for tab in tables for t in (tab[0], tab[2], tab[3])])
+    st = _stream()
     _ck(lib().ipsx_stream_commit_view(arr, len(tables), _p(images), C.byref(view.struct), images.element_size(), _p(sel), B or 0,
                                       M, n_cand, tail_first, C.byref(unit), st), "ipsx_stream_commit_view")
     return unit.value
@@ -905,7 +1089,8 @@ def stream_commit_view(tables, images, view, sel, M, n_cand, tail_first=0):
 def scan_range_if(lg, M, I, H, T, it_begin, it_end, mem_idx, tie, cond, mask=1, workspace=None):
     """``scan_range`` that every workgroup abandons at once unless ``cond`` (int32 device scalar) has a bit of ``mask``
     set: the in-call recovery of a persistent loop that gave up waiting (its status word, bit 0)."""
-    B, N = lg.shape[:2]
+    lg, B, N = _scan_args("scan_range_if", lg, M, I, H, T, mem_idx, tie, workspace, False, (cond,))
+    _word("scan_range_if", "cond", cond)
     if workspace is not None:
         _ck(lib().ipsx_scan_range_if_ws(_p(lg), B, N, M, I, H, T, it_begin, it_end, _p(mem_idx), None, _p(tie), _p(cond), mask,
                                         _p(workspace), workspace.numel(), _stream()), "ipsx_scan_range_if_ws")
@@ -1089,11 +1274,11 @@ def scan_persistent(lg, M, I, H, T, mem_idx, tie, ready, status, workgroups=0, w
     ``publish_rows`` on the producing stream; or one word per image - ``ready.numel() == B`` > 1 - when the producer works
     through the images one after the other) before it reads rows; see include/ipsx.h.  ``workgroups`` in (0, B): that
     many resident loops, each taking its images one after the other (``scan_persistent_groupable`` shapes)."""
-    B, N = lg.shape[:2]
-    if not lg.is_contiguous():
-        raise ValueError("scan_persistent needs the full contiguous (B, N, H*T) logits buffer")
+    lg, B, N = _scan_args("scan_persistent", lg, M, I, H, T, mem_idx, tie, workspace, False, (ready, status))
+    _wr("scan_persistent", "ready", ready, torch.int32)
     if ready.numel() not in (1, B):
         raise ValueError("ready: one word, or one per image")
+    _word("scan_persistent", "status", status)
     st = C.c_void_p(stream.cuda_stream) if stream is not None else _stream()     # (``stream``: launch there without
     if workspace is not None:          # a candidate set beyond the LDS             #  making it the current stream)
         _ck(lib().ipsx_scan_persistent_ws(_p(lg), B, N, M, I, H, T, _p(mem_idx), None, _p(tie), _p(ready),
@@ -1108,16 +1293,26 @@ def scan_persistent(lg, M, I, H, T, mem_idx, tie, ready, status, workgroups=0, w
 
 def scan_gate(status):
     """Hold the current stream until the persistent scan owning ``status`` is resident (bounded wait)."""
+    _same_gpu("scan_gate", ("status",), status)
+    _word("scan_gate", "status", status)
     _ck(lib().ipsx_scan_gate(_p(status), _stream()), "ipsx_scan_gate")
 
 
 def publish_rows(ready, n_rows):
+    """Advance the progress word ``ready`` (one int32 on the GPU) to ``n_rows`` on the current stream."""
+    _same_gpu("publish_rows", ("ready",), ready)
+    _word("publish_rows", "ready", ready)
     _ck(lib().ipsx_publish_rows(_p(ready), int(n_rows), _stream()), "ipsx_publish_rows")
 
 
 def _scores_impl(x, qs, wk, H, Dk, T, want_attn):
-    x = _f32(x)
+    what = "attn_map" if want_attn else "scores"
+    _one_gpu(what, x=x, qs=qs, wk=wk)
+    x = _rd(what, "x", x, dim=3)           # (read by the logits kernel: 16-byte loads when D % 8 == 0)
     B, L, D = x.shape
+    qs, Dw = _fold_args(what, qs, wk, H, Dk, T)
+    if Dw != D:
+        raise ValueError("{}: x has {} features, wk takes {}".format(what, D, Dw))
     sc = torch.empty((B, L), dtype=torch.float32, device=x.device)
     attn = torch.empty((B, H, T, L), dtype=torch.float32, device=x.device) if want_attn else None
     nb = lib().ipsx_scores_workspace_bytes(B, L, D, H, T)
@@ -1137,8 +1332,11 @@ def attn_map(x, qs, wk, H, Dk, T):
 
 
 def topm(sc, M):
-    sc = _f32(sc)
+    _one_gpu("topm", sc=sc)
+    sc = _rd("topm", "sc", sc, dim=2, align=4)
     B, L = sc.shape
+    if not 0 < M <= L:
+        raise ValueError("topm: M = {} of L = {} candidates".format(M, L))
     top = torch.empty((B, M), dtype=torch.int64, device=sc.device)
     tie = torch.zeros((B,), dtype=torch.int32, device=sc.device)
     nb = lib().ipsx_topm_workspace_bytes(B, L, M)
@@ -1149,7 +1347,12 @@ def topm(sc, M):
 
 def gather_rows(src, idx):
     """src (B|1, N, ...) on the GPU, idx (B, M) int64 -> (B, M, ...)."""
+    _same_gpu("gather_rows", ("src", "idx"), src, idx)
+    if idx.dtype != torch.int64 or idx.dim() != 2:
+        raise TypeError("gather_rows: idx must be a (B, M) int64 tensor, got {} {}".format(idx.dtype, tuple(idx.shape)))
     B, M = idx.shape
+    if src.dim() < 2 or src.shape[0] not in (1, B):
+        raise ValueError("gather_rows: src must be ({} or 1, N, ...) for idx {}, got {}".format(B, tuple(idx.shape), tuple(src.shape)))
     if src.stride(0) == 0 and src.shape[0] > 1:      # expanded broadcast table
         src = src[:1]
     src = src if src.is_contiguous() else src.contiguous()
@@ -1168,6 +1371,7 @@ def dequant_patches(q, table):
     ``ips_amd.quant.patch_table``).  For the M patches a selection keeps: what leaves ``ips()`` is float32."""
     if q.dtype != torch.uint8 or q.dim() < 3:
         raise TypeError("expected uint8 (..., C, h, w) patches, got {} {}".format(q.dtype, tuple(q.shape)))
+    _one_gpu("dequant_patches", q=q, table=table)
     table = _patch_table(table, q.shape[-3], q.device)
     q = q if q.is_contiguous() else q.contiguous()
     out = torch.empty(q.shape, dtype=torch.float32, device=q.device)
@@ -1197,8 +1401,22 @@ def ips_finish(src, pos, idx_buf, status, status_host, order=None):
     ``order`` ((B or 1, N) int64, contiguous, on the device): the loop ran on shuffled numbering - the patch rows are
     ``src[b, order[b, idx[b, m]]]`` of the UNSHUFFLED ``src`` (``ipsx_ips_finish_indexed``), ``pos`` and the indices as before.
     -> (mem_idx, mem_patch, mem_pos)"""
+    _same_gpu("ips_finish", ("src", "pos", "idx_buf", "status", "order"), src, pos, idx_buf, status, order)
+    if idx_buf.dim() != 2:
+        raise ValueError("ips_finish: idx_buf must be (B, M), got {}".format(tuple(idx_buf.shape)))
     B, M = idx_buf.shape
+    _wr("ips_finish", "idx_buf", idx_buf, torch.int64)
+    _word("ips_finish", "status", status)
+    # status_host is THE host argument of this module: the pinned mirror the kernel writes the status word to
+    if status_host.device.type != "cpu" or status_host.dtype != torch.int32 or status_host.numel() < 1:
+        raise ValueError("ips_finish: status_host must be the pinned host mirror (int32, on the CPU), got {} on {}".format(
+            status_host.dtype, status_host.device))
+    if not ips_finish_supported(src, pos) or src.shape[0] not in (1, B):
+        raise ValueError("ips_finish: src ({} or 1, N, ...) / pos must be contiguous device rows of whole 16-byte units at 16-byte "
+                         "addresses (ips_finish_supported)".format(B))
     N = src.shape[1]
+    if pos is not None and (pos.shape[0] not in (1, B) or pos.shape[1] < N):         # (a longer table: its first N rows)
+        raise ValueError("ips_finish: pos must be ({} or 1, >= {}, D), got {}".format(B, N, tuple(pos.shape)))
     row_bytes = src[0, 0].numel() * src.element_size()
     out = torch.empty((B, M) + tuple(src.shape[2:]), dtype=src.dtype, device=src.device)
     idx = torch.empty_like(idx_buf)
@@ -1333,7 +1551,7 @@ def order_index(order, B, N, out=None):
     ``b * N + clamp(order[b, j], 0, N - 1)`` - what the row-indexed producers read through - in ONE launch
     (``ipsx_order_index``); ``out``: B * N int32 on the same device."""
     if order.dtype != torch.int64 or order.dim() != 2 or order.shape[1] != N or order.shape[0] not in (1, B) or \
-            not order.is_contiguous() or not order.is_cuda:
+            not order.is_contiguous() or not _gpu_device(order.device):
         raise ValueError("order must be a contiguous (B or 1, N) int64 tensor on the device")
     if out is None:
         out = torch.empty((B, N), dtype=torch.int32, device=order.device)
@@ -1347,7 +1565,8 @@ def order_index(order, B, N, out=None):
 def patchify(img, patch_size, patch_stride):
     """img (B, C, H, W) float32 on the GPU -> (B, N, C, ph, pw): unfold + permute + reshape of the reference's
     datasets (data/megapixel_mnist/mnist_dataset.py:44-51, data/traffic/traffic_dataset.py:336-343), batched."""
-    img = _f32(img)
+    _one_gpu("patchify", img=img)
+    img = _rd("patchify", "img", img, dim=4, align=4)      # (ipsx_patchify takes its scalar route off 16-byte addresses)
     B, Cc, H, W = img.shape
     (ph, pw), (sh, sw) = patch_size, patch_stride
     n = lib().ipsx_patchify_count(H, W, ph, pw, sh, sw)
@@ -1504,6 +1723,7 @@ def gather_patches_view(images, view, idx, table=None):
     """images (B, C, H, W) float32 on the GPU, idx (B, M) int64 patch numbers inside each image (py * nx + px) ->
     (B, M, C, ph, pw): ``patchify(images, ...)[b, idx[b, m]]`` copied straight out of the images.  uint8 images with
     their ``table`` (C, 256): float32 all the same, ``table[c][byte]``."""
+    _one_gpu("gather_patches_view", images=images, idx=idx, table=table)
     images = view.check(images, table)
     if idx.dtype != torch.int64 or idx.dim() != 2 or idx.shape[0] != view.image_shape[0] or idx.device != images.device:
         raise ValueError("idx must be a (B, M) int64 tensor on the images' device")
@@ -1531,6 +1751,11 @@ def patchify_sparse(index, value, offsets, canvas, patch_size, patch_stride, fla
     B = offsets.numel() - 1
     if index.dtype != torch.int64 or offsets.dtype != torch.int64 or value.dtype != torch.float32:
         raise TypeError("index / offsets must be int64 and value float32")
+    _one_gpu("patchify_sparse", index=index, value=value, offsets=offsets)
+    if index.dim() != 1 or value.dim() != 1 or offsets.dim() != 1 or index.numel() != value.numel():
+        raise ValueError("patchify_sparse: index and value must be 1-d of one length, offsets 1-d, got {}, {} and {} (the kernel "
+                         "reads no entry past that length, whatever offsets[-1] says)".format(
+                             tuple(index.shape), tuple(value.shape), tuple(offsets.shape)))
     n = lib().ipsx_patchify_count(H, W, ph, pw, sh, sw)
     if n <= 0 or B <= 0:
         raise ValueError("bad geometry")
@@ -1547,15 +1772,17 @@ def conv2d_nhwc_bf16(x, weight, alpha, shift, stride, pad, residual=None, relu=T
     """One convolution of the bf16 layer-by-layer trunk (conv_nhwc_bf16_kernel): ``x`` (n, h, w, C_in) bfloat16, OIHW float32
     ``weight`` (rounded to bf16 by the packing), float32 ``alpha`` / ``shift`` (C_out,) or None, ``residual``
     (n, ho, wo, C_out) bfloat16 or None  ->  (n, ho, wo, C_out) bfloat16 (written into ``out`` where one is given)."""
+    _one_gpu("conv2d_nhwc_bf16", x=x, weight=weight, alpha=alpha, shift=shift, residual=residual, out=out)
     if x.dim() != 4 or x.dtype != torch.bfloat16 or not x.is_contiguous():
         raise ValueError("expected a contiguous bfloat16 (n, h, w, C) tensor")
     w = _f32(weight.detach())
     co, ci, kh, kw = w.shape
     n, h, wd, _ = x.shape
-    half = torch.empty(lib().ipsx_packed_conv_weight_bf16_bytes(co, ci, kh, kw), dtype=torch.uint8, device=x.device)
-    _ck(lib().ipsx_pack_conv_weight_bf16(_p(w), co, ci, kh, kw, _p(half), _stream()), "ipsx_pack_conv_weight_bf16")
     alpha, shift = (_f32(alpha) if alpha is not None else None), (_f32(shift) if shift is not None else None)
-    cv = Conv(ci, co, kh, kw, stride, pad, None, _p(alpha), _p(shift), _p(half))
+    for name, t in (("alpha", alpha), ("shift", shift)):
+        if t is not None and tuple(t.shape) != (co,):
+            raise ValueError("conv2d_nhwc_bf16: {} must be ({},), got {}".format(name, co, tuple(t.shape)))
+    cv = Conv(ci, co, kh, kw, stride, pad, None, _p(alpha), _p(shift), None)
     if x.shape[3] != ci or not lib().ipsx_conv2d_affine_nhwc_bf16_supported(C.byref(cv)):
         raise ValueError("the bf16 convolution needs C_in % 16 == 0 and C_out % 8 == 0, got {} -> {}".format(ci, co))
     ho, wo = (h + 2 * pad - kh) // stride + 1, (wd + 2 * pad - kw) // stride + 1
@@ -1565,6 +1792,10 @@ def conv2d_nhwc_bf16(x, weight, alpha, shift, stride, pad, residual=None, relu=T
     if out is not None and (out.dtype != torch.bfloat16 or tuple(out.shape) != (n, ho, wo, co) or not out.is_contiguous() or
                             out.device != x.device):
         raise ValueError("out must be a contiguous bfloat16 (n, ho, wo, C_out) tensor on the device of x")
+    # (every refusal stands in front of the packing launch)
+    half = torch.empty(lib().ipsx_packed_conv_weight_bf16_bytes(co, ci, kh, kw), dtype=torch.uint8, device=x.device)
+    _ck(lib().ipsx_pack_conv_weight_bf16(_p(w), co, ci, kh, kw, _p(half), _stream()), "ipsx_pack_conv_weight_bf16")
+    cv.w_packed_bf16 = half.data_ptr()
     y = out if out is not None else torch.empty((n, ho, wo, co), dtype=torch.bfloat16, device=x.device)
     _ck(lib().ipsx_conv2d_affine_nhwc_bf16(C.byref(cv), _p(x), _p(residual), _p(y), n, h, wd, int(bool(relu)), _stream()),
         "ipsx_conv2d_affine_nhwc_bf16")
@@ -1575,6 +1806,7 @@ def avgpool_nhwc_bf16(x):
     """(n, h, w, C) bfloat16 -> (n, C) float32: the fp32 sum over the pixels in memory order, divided by their number."""
     if x.dim() != 4 or x.dtype != torch.bfloat16 or not x.is_contiguous():
         raise ValueError("expected a contiguous bfloat16 (n, h, w, C) tensor")
+    _one_gpu("avgpool_nhwc_bf16", x=x)
     n, h, w, c = x.shape
     y = torch.empty((n, c), dtype=torch.float32, device=x.device)
     _ck(lib().ipsx_avgpool_nhwc_bf16(_p(x), _p(y), n, c, h * w, _stream()), "ipsx_avgpool_nhwc_bf16")
@@ -1585,8 +1817,11 @@ def avgpool_nhwc_bf16(x):
 def aggregate(transf, x):
     """Transformer.forward in eval / no-grad mode: x (B, M, D) -> (B, n_token, D)."""
     ca, mlp = transf.crs_attn, transf.mlp
-    x = _f32(x)
+    _one_gpu("aggregate", x=x, weights=ca.k_w.weight)
+    x = _rd("aggregate", "x", x, dim=3)          # (its logits pass reads rows with 16-byte loads)
     B, M, D = x.shape
+    if ca.k_w.weight.shape[1] != D or ca.v_w.weight.shape[1] != D:
+        raise ValueError("aggregate: x has {} features, the attention's weights take {}".format(D, ca.k_w.weight.shape[1]))
     t = Transf()
     t.n_token, t.h, t.d, t.dk, t.dv, t.d_inner = ca.n_token, ca.H, D, ca.D_k, ca.D_v, mlp.w_1.out_features
     keep = []
@@ -1614,9 +1849,13 @@ def aggregate(transf, x):
 
 def head(emb, token, linear, act):
     """act(Linear(emb[:, token])) with act in {'softmax', 'sigmoid'}: (B, T, D) -> (B, n_class)."""
-    emb = _f32(emb)
+    _one_gpu("head", emb=emb, weight=linear.weight, bias=linear.bias)
+    emb = _rd("head", "emb", emb, dim=3, align=4)          # (head_kernel: 4-byte loads only)
     B, T, D = emb.shape
-    w, b = _f32(linear.weight.detach()), _f32(linear.bias.detach())
+    w, b = _rd("head", "linear.weight", linear.weight.detach(), dim=2, align=4), _rd("head", "linear.bias", linear.bias.detach(), dim=1, align=4)
+    if w.shape[1] != D or b.shape[0] != w.shape[0] or not 0 <= token < T or act not in ("softmax", "sigmoid"):
+        raise ValueError("head: emb {} with token {}, act {!r} and a Linear of weight {} / bias {}".format(
+            tuple(emb.shape), token, act, tuple(w.shape), tuple(b.shape)))
     out = torch.empty((B, w.shape[0]), dtype=torch.float32, device=emb.device)
     _ck(lib().ipsx_head(_p(emb), B, T, D, token, _p(w), _p(b), w.shape[0],
                         {"softmax": 0, "sigmoid": 1}[act], _p(out), _stream()), "ipsx_head")

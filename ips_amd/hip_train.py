@@ -10,7 +10,7 @@ import os
 
 import torch
 
-from .hip import (lib, _ck, _p, _f32, _stream, _PATCH_DTYPES, Conv)
+from .hip import (lib, _ck, _p, _f32, _stream, _PATCH_DTYPES, Conv, _gpu_device, _one_gpu, _rd, _wr)
 from .hip_encoder import _pack_conv
 
 
@@ -37,6 +37,7 @@ def conv_train_supported(conv):
 def _pack_conv_view(weight, dgrad=False):
     """``_pack_conv`` of a weight tensor as it lies in memory (any strides: no contiguous copy) - or, ``dgrad``, of the
     weights rotated by 180 degrees and transposed: -> (packed, C_out, C_in) of the convolution they describe."""
+    _conv_weight("pack_conv_view", weight)
     co, ci, kh, kw = weight.shape
     s_co, s_ci, s_kh, s_kw = weight.stride()
     if dgrad:
@@ -49,6 +50,13 @@ def _pack_conv_view(weight, dgrad=False):
     _ck(lib().ipsx_pack_conv_weight_strided(_p(weight), base, n_out, n_in, kh, kw, sn, sc, sky, skx, _p(packed), _stream()),
         "ipsx_pack_conv_weight_strided")
     return packed, n_out, n_in
+
+
+def _conv_weight(what, weight, dev=None):
+    """An OIHW float32 weight on the GPU (``dev``: on that one), read where it lies - any strides, 4-byte loads."""
+    if weight.dim() != 4 or weight.dtype != torch.float32 or not _gpu_device(weight.device) or (dev is not None and weight.device != dev):
+        raise ValueError("{}: weight must be a float32 OIHW tensor on the call's GPU, got {} {} on {}".format(
+            what, weight.dtype, tuple(weight.shape), weight.device))
 
 
 class PackJob(C.Structure):
@@ -67,6 +75,8 @@ def pack_conv_views(views):
         return []
     dev = views[0][0].device
     sizes = []
+    for weight, dgrad in views:
+        _conv_weight("pack_conv_views", weight, dev)
     for weight, dgrad in views:
         co, ci, kh, kw = weight.shape
         n_out, n_in = (ci, co) if dgrad else (co, ci)
@@ -108,20 +118,37 @@ def conv_lds_supported(conv, h, w):
                 and lib().ipsx_conv2d_lds_nhwc_supported(conv.in_channels, conv.out_channels, kh, conv.stride[0], conv.padding[0], h, w))
 
 
+def _activation(what, name, x, shape=None):
+    """A saved activation: float32 channels-last (P, C, H, W) at a 16-byte address (the kernels' 16-byte buffer loads),
+    handed over where it lies - anything else is refused, never copied."""
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous(memory_format=_CL) or x.data_ptr() % 16 or \
+            (shape is not None and tuple(x.shape) != tuple(shape)):
+        raise ValueError("{}: {} - expected a float32 channels-last (P, C, H, W){} tensor at a 16-byte address, got {} {} with "
+                         "strides {}".format(what, name, " = " + str(tuple(shape)) if shape is not None else "", x.dtype, tuple(x.shape),
+                                             x.stride()))
+    return x
+
+
 def conv2d_nhwc(x, weight, stride, pad, dgrad_weights=False, packed=None, stats_shift=None):
     """Plain convolution of a channels-last (P, C_in, h, w) tensor with an OIHW ``weight`` on the fp32 matrix cores
     (conv_nhwc_kernel): -> channels-last (P, C_out, ho, wo).  ``packed``: the weight already packed for this direction
     (``pack_conv_views``).  ``stats_shift`` (a (C_out,) tensor; only where ``conv_lds_supported``): -> (y, partial, slabs),
     the output's per-slab sums around that shift for ``bn_train_forward_partials``."""
-    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous(memory_format=_CL):
-        raise ValueError("expected a float32 channels-last (P, C, H, W) tensor")
+    _one_gpu("conv2d_nhwc", x=x, weight=weight, packed=packed, stats_shift=stats_shift)
+    _activation("conv2d_nhwc", "x", x)
+    _conv_weight("conv2d_nhwc", weight)
     kh, kw = weight.shape[2:]
     n, _, h, w = x.shape
     ho, wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
+    co, ci = (weight.shape[1], weight.shape[0]) if dgrad_weights else (weight.shape[0], weight.shape[1])
+    if x.shape[1] != ci:
+        raise ValueError("conv2d_nhwc: x has {} channels, weight takes {}".format(x.shape[1], ci))
+    if packed is not None:
+        _wr("conv2d_nhwc", "packed", packed, torch.float32, align=16)
+    if stats_shift is not None:
+        _wr("conv2d_nhwc", "stats_shift", stats_shift, torch.float32, (co,))
     if packed is None:
-        packed, co, ci = _pack_conv_view(weight.detach(), dgrad_weights)
-    else:
-        co, ci = (weight.shape[1], weight.shape[0]) if dgrad_weights else (weight.shape[0], weight.shape[1])
+        packed = _pack_conv_view(weight.detach(), dgrad_weights)[0]
     cv = Conv(ci, co, kh, kw, stride, pad, _p(packed), None, None, None)
     y = torch.empty((n, co, ho, wo), dtype=torch.float32, device=x.device, memory_format=_CL)
     if n == 0:                                  # (an empty batch: nothing to launch)
@@ -151,16 +178,21 @@ def conv2d_nhwc(x, weight, stride, pad, dgrad_weights=False, packed=None, stats_
 def conv2d_nhwc_dgrad(dy, weight, stride, pad, in_hw, packed=None):
     """Data gradient of ``conv2d_nhwc``: the same kernel on dy with the weights rotated by 180 degrees and transposed; a
     strided layer first spreads dy over a zero map of the input's size (needs kernel - 1 = 2 pad)."""
+    _one_gpu("conv2d_nhwc_dgrad", dy=dy, weight=weight, packed=packed)
+    _conv_weight("conv2d_nhwc_dgrad", weight)
     co, ci, kh, kw = weight.shape
+    ho, wo = (in_hw[0] + 2 * pad - kh) // stride + 1, (in_hw[1] + 2 * pad - kw) // stride + 1
+    if dy.dim() != 4 or tuple(dy.shape[1:]) != (co, ho, wo):
+        raise ValueError("conv2d_nhwc_dgrad: dy - expected float32 (P, %d, %d, %d), got %s" % (co, ho, wo, tuple(dy.shape)))
+    dy = _rd("conv2d_nhwc_dgrad", "dy", dy, cl=True)          # (a gradient is read only: any layout, copied to channels-last)
+    if packed is not None:
+        _wr("conv2d_nhwc_dgrad", "packed", packed, torch.float32, align=16)
     if (stride > 1 and kh == kw and os.environ.get("IPSX_TRAIN_DGRAD_S2", "1") != "0"
             and lib().ipsx_conv2d_dgrad_s2_lds_nhwc_supported(ci, co, kh, stride, pad, in_hw[0], in_hw[1])):
         # the 32-px trunk's strided layer by parity class of the input pixel: no spread map (csrc/dgrad_s2.hip)
         if packed is None:
             packed = _pack_conv_view(weight.detach(), True)[0]
         n = dy.shape[0]
-        if dy.dtype != torch.float32 or tuple(dy.shape[1:]) != (co, in_hw[0] // 2, in_hw[1] // 2):
-            raise ValueError("dy: expected float32 (P, %d, %d, %d)" % (co, in_hw[0] // 2, in_hw[1] // 2))
-        dy = dy.contiguous(memory_format=_CL)
         dx = torch.empty((n, ci, in_hw[0], in_hw[1]), dtype=torch.float32, device=dy.device, memory_format=_CL)
         _ck(lib().ipsx_conv2d_dgrad_s2_lds_nhwc(_p(packed), kh, _p(dy), _p(dx), n, _stream()), "ipsx_conv2d_dgrad_s2_lds_nhwc")
         return dx
@@ -181,10 +213,15 @@ def conv2d_nhwc_wgrad(x, dy, weight_shape, stride, pad):
     """Weight gradient of ``conv2d_nhwc`` -> (C_out, C_in, kh, kw) in channels-last memory order (ipsx_conv2d_wgrad_nhwc).
     Activations of 2 GiB and more (the kernel's buffer range) are taken in slices of whole images, the slices' gradients
     added in slice order (deterministic; the forward kernel slices per launch in the same way)."""
+    _one_gpu("conv2d_nhwc_wgrad", x=x, dy=dy)
     co, ci, kh, kw = weight_shape
+    _activation("conv2d_nhwc_wgrad", "x", x)          # (the saved activation: refused as conv2d_nhwc refuses it)
     n, _, h, w = x.shape
-    dy = dy.contiguous(memory_format=_CL)
-    ho, wo = dy.shape[2:]
+    ho, wo = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
+    if x.shape[1] != ci or dy.dim() != 4 or tuple(dy.shape) != (n, co, ho, wo):
+        raise ValueError("conv2d_nhwc_wgrad: x {} and dy {} - expected ({}, {}, {}, {}) and ({}, {}, {}, {})".format(
+            tuple(x.shape), tuple(dy.shape), n, ci, h, w, n, co, ho, wo))
+    dy = _rd("conv2d_nhwc_wgrad", "dy", dy, cl=True)
     per_image = 4 * max(h * w * ci, ho * wo * co)
     step = max(1, min(n, _WGRAD_MAX_BYTES // per_image))
     dw = torch.empty((co, ci, kh, kw), dtype=torch.float32, device=x.device, memory_format=_CL)
@@ -202,13 +239,33 @@ def conv2d_nhwc_wgrad(x, dy, weight_shape, stride, pad):
     return dw
 
 
-def _rows_cl(t):
-    """(P, C, H, W) channels-last tensor, or (rows, C) rows as they lie (BatchNorm1d) -> (rows, C) of its memory."""
+def _rows_cl(t, name="x"):
+    """(P, C, H, W) channels-last tensor, or (rows, C) rows as they lie (BatchNorm1d) -> (rows, C) of its memory.  The
+    BatchNorm kernels read and write whole float4 (csrc/bn_train.hip): the address is a multiple of 16."""
+    if t.data_ptr() % 16:
+        raise ValueError("{}: expected a tensor at a 16-byte address".format(name))
     if t.dim() == 2 and t.dtype == torch.float32 and t.is_contiguous():
         return t.shape[0], t.shape[1]
     if t.dim() != 4 or t.dtype != torch.float32 or not t.is_contiguous(memory_format=torch.channels_last):
-        raise ValueError("expected a float32 channels-last (P, C, H, W) tensor")
+        raise ValueError("{}: expected a float32 channels-last (P, C, H, W) tensor, got {} {}".format(name, t.dtype, tuple(t.shape)))
     return t.shape[0] * t.shape[2] * t.shape[3], t.shape[1]
+
+
+def _bn_args(what, x, residual, gamma, beta, running_mean, running_var, **more):
+    """The arguments the two BatchNorm forwards share, checked -> (rows, c, gamma, beta): ``gamma`` / ``beta`` (C,) are read
+    as float4 (copied where they are strided or off a 16-byte address); ``running_mean`` / ``running_var`` (C,) are updated
+    in place with 4-byte stores: handed over where they lie."""
+    _one_gpu(what, x=x, residual=residual, gamma=gamma, beta=beta, running_mean=running_mean, running_var=running_var, **more)
+    rows, c = _rows_cl(x)
+    if residual is not None and (_rows_cl(residual, "residual") != (rows, c) or residual.shape != x.shape):
+        raise ValueError("{}: residual {} beside x {}".format(what, tuple(residual.shape), tuple(x.shape)))
+    gamma, beta = _rd(what, "gamma", gamma.detach(), dim=1), _rd(what, "beta", beta.detach(), dim=1)
+    if gamma.shape[0] != c or beta.shape[0] != c:
+        raise ValueError("{}: gamma {} / beta {} for {} channels".format(what, tuple(gamma.shape), tuple(beta.shape), c))
+    for name, t in (("running_mean", running_mean), ("running_var", running_var)):
+        if t is not None:
+            _wr(what, name, t, torch.float32, (c,))
+    return rows, c, gamma, beta
 
 
 def bn_train_supported(rows, c):
@@ -218,16 +275,14 @@ def bn_train_supported(rows, c):
 def bn_train_forward(x, residual, gamma, beta, eps, momentum, running_mean, running_var, relu):
     """Batch-statistics BatchNorm2d (+ residual) (+ ReLU) of a channels-last activation; updates the running
     statistics in place.  Returns y (channels-last), mean, invstd."""
-    rows, c = _rows_cl(x)
-    if residual is not None and _rows_cl(residual) != (rows, c):
-        raise ValueError("residual shape")
+    rows, c, gamma, beta = _bn_args("bn_train_forward", x, residual, gamma, beta, running_mean, running_var)
     y = torch.empty_like(x)                        # (preserves channels-last)
     # mean | invstd are saved for backward, so they are an allocation of their own (2 C floats): carved out of the
     # workspace they would keep its ~4 KB x C alive until backward, per BatchNorm (~20 MB per ResNet-18 step)
     stat = torch.empty(2 * c, dtype=torch.float32, device=x.device)
     mean, invstd = stat[:c], stat[c:]
     ws = torch.empty(max(1, _bn_workspace_floats(rows, c)), dtype=torch.float32, device=x.device)
-    _ck(lib().ipsx_bn_train_forward(_p(x), _p(residual), rows, c, _p(_f32(gamma)), _p(_f32(beta)), eps, momentum,
+    _ck(lib().ipsx_bn_train_forward(_p(x), _p(residual), rows, c, _p(gamma), _p(beta), eps, momentum,
                                     _p(running_mean), _p(running_var), int(relu), _p(y), _p(mean), _p(invstd),
                                     _p(ws), _stream()), "ipsx_bn_train_forward")
     return y, mean, invstd
@@ -242,7 +297,8 @@ def maxpool_train_supported(x):
 
 def maxpool_3x3s2_nhwc(x):
     """nn.MaxPool2d(3, 2, 1) of a channels-last (P, C, h, w) activation -> channels-last (P, C, ho, wo)."""
-    x = x.contiguous(memory_format=_CL)
+    _one_gpu("maxpool_3x3s2_nhwc", x=x)
+    x = _rd("maxpool_3x3s2_nhwc", "x", x, dim=4, cl=True)         # (float4 loads along the channels)
     n, c, h, w = x.shape
     y = torch.empty((n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=torch.float32, device=x.device, memory_format=_CL)
     _ck(lib().ipsx_maxpool_3x3s2_nhwc(_p(x), _p(y), n, c, h, w, _stream()), "ipsx_maxpool_3x3s2_nhwc")
@@ -251,9 +307,12 @@ def maxpool_3x3s2_nhwc(x):
 
 def maxpool_3x3s2_bwd_nhwc(x, dy):
     """The gradient of ``maxpool_3x3s2_nhwc`` w.r.t. x (ATen's rule: a window's gradient goes to its first maximum)."""
-    x = x.contiguous(memory_format=_CL)
-    dy = dy.contiguous(memory_format=_CL)
+    _one_gpu("maxpool_3x3s2_bwd_nhwc", x=x, dy=dy)
+    x = _rd("maxpool_3x3s2_bwd_nhwc", "x", x, dim=4, cl=True)
     n, c, h, w = x.shape
+    if dy.dim() != 4 or tuple(dy.shape) != (n, c, (h - 1) // 2 + 1, (w - 1) // 2 + 1):
+        raise ValueError("maxpool_3x3s2_bwd_nhwc: dy {} is not the pooled map of x {}".format(tuple(dy.shape), tuple(x.shape)))
+    dy = _rd("maxpool_3x3s2_bwd_nhwc", "dy", dy, cl=True)
     dx = torch.empty_like(x)
     _ck(lib().ipsx_maxpool_3x3s2_bwd_nhwc(_p(x), _p(dy), _p(dx), n, c, h, w, _stream()), "ipsx_maxpool_3x3s2_bwd_nhwc")
     return dx
@@ -262,13 +321,17 @@ def maxpool_3x3s2_bwd_nhwc(x, dy):
 def bn_train_forward_partials(x, residual, gamma, beta, eps, momentum, running_mean, running_var, relu, partial, slabs, shift):
     """``bn_train_forward`` without its reduction pass: ``partial`` (slabs, 2, C) are the sums ``conv2d_nhwc(..., stats_shift=
     shift)`` took off its accumulators (``shift`` may be ``running_mean`` itself)."""
-    rows, c = _rows_cl(x)
-    if residual is not None and _rows_cl(residual) != (rows, c):
-        raise ValueError("residual shape")
+    rows, c, gamma, beta = _bn_args("bn_train_forward_partials", x, residual, gamma, beta, running_mean, running_var,
+                                    partial=partial, shift=shift)
+    # (partial: the producer's hand-over, shift: may BE running_mean - both taken where they lie)
+    _wr("bn_train_forward_partials", "partial", partial, torch.float32, align=16)
+    if partial.dim() != 3 or tuple(partial.shape[1:]) != (2, c) or not 0 <= slabs <= partial.shape[0]:
+        raise ValueError("bn_train_forward_partials: partial must be (>= slabs = {}, 2, {}), got {}".format(slabs, c, tuple(partial.shape)))
+    _wr("bn_train_forward_partials", "shift", shift, torch.float32, (c,))
     y = torch.empty_like(x)
     stat = torch.empty(2 * c, dtype=torch.float32, device=x.device)
     mean, invstd = stat[:c], stat[c:]
-    _ck(lib().ipsx_bn_train_forward_partials(_p(x), _p(residual), rows, c, _p(_f32(gamma)), _p(_f32(beta)), eps, momentum,
+    _ck(lib().ipsx_bn_train_forward_partials(_p(x), _p(residual), rows, c, _p(gamma), _p(beta), eps, momentum,
                                              _p(running_mean), _p(running_var), int(relu), _p(y), _p(mean), _p(invstd),
                                              _p(partial), slabs, _p(shift), _stream()), "ipsx_bn_train_forward_partials")
     return y, mean, invstd
@@ -289,15 +352,22 @@ def _bn_workspace_floats(rows, c):
 
 def bn_train_backward(dy, y, x, gamma, mean, invstd, relu, want_residual):
     """-> dx, dresidual | None, dgamma, dbeta."""
+    _one_gpu("bn_train_backward", dy=dy, y=y, x=x, gamma=gamma, mean=mean, invstd=invstd)
     rows, c = _rows_cl(x)
-    if _rows_cl(dy) != (rows, c):
-        raise ValueError("dy shape")
+    if _rows_cl(dy, "dy") != (rows, c) or dy.shape != x.shape:
+        raise ValueError("bn_train_backward: dy {} beside x {}".format(tuple(dy.shape), tuple(x.shape)))
+    if y is not None and (_rows_cl(y, "y") != (rows, c) or y.shape != x.shape):
+        raise ValueError("bn_train_backward: y {} beside x {}".format(tuple(y.shape), tuple(x.shape)))
+    gamma, mean, invstd = (_rd("bn_train_backward", name, t.detach(), dim=1) for name, t in
+                           (("gamma", gamma), ("mean", mean), ("invstd", invstd)))
+    if not gamma.shape[0] == mean.shape[0] == invstd.shape[0] == c:
+        raise ValueError("bn_train_backward: gamma / mean / invstd must be ({},)".format(c))
     dx = torch.empty_like(x)
     dres = torch.empty_like(x) if want_residual else None
     dgamma = torch.empty(c, dtype=torch.float32, device=x.device)
     dbeta = torch.empty_like(dgamma)
     ws = torch.empty(max(1, _bn_workspace_floats(rows, c)), dtype=torch.float32, device=x.device)
-    _ck(lib().ipsx_bn_train_backward(_p(dy), _p(y), _p(x), rows, c, _p(_f32(gamma)), _p(mean), _p(invstd), int(relu),
+    _ck(lib().ipsx_bn_train_backward(_p(dy), _p(y), _p(x), rows, c, _p(gamma), _p(mean), _p(invstd), int(relu),
                                      _p(dx), _p(dres), _p(dgamma), _p(dbeta), _p(ws), _stream()),
         "ipsx_bn_train_backward")
     return dx, dres, dgamma, dbeta
@@ -311,7 +381,7 @@ def projector_train_supported(f, d):
 
 
 def _feature_rows(x, f):
-    if x.dim() != 2 or x.shape[1] != f or x.dtype not in _PATCH_DTYPES or not x.is_cuda:
+    if x.dim() != 2 or x.shape[1] != f or x.dtype not in _PATCH_DTYPES or not _gpu_device(x.device):
         raise ValueError("expected (rows, {}) float32 / bfloat16 / float16 feature rows on the GPU, got {} {}".format(
             f, tuple(x.shape), x.dtype))
     if x.shape[0] == 0:
@@ -324,6 +394,9 @@ def projector_train_forward(x, weight, bias, ln_eps):
     the (D, F) ``weight`` and ``bias``, for the BatchNorm1d behind it in batch-statistics mode:
     -> (z, stats, partial, slabs, shift) - ``stats`` (rows, 2) the rows' (mean, rstd), all that backward needs of the
     LayerNorm; ``partial`` (slabs, 2, D) the column sums of z around ``shift`` for ``bn_train_forward_partials``."""
+    _one_gpu("projector_train_forward", x=x, weight=weight, bias=bias)
+    if weight.dim() != 2 or bias.dim() != 1 or bias.shape[0] != weight.shape[0]:
+        raise ValueError("projector_train_forward: weight (D, F) and bias (D,), got {} and {}".format(tuple(weight.shape), tuple(bias.shape)))
     d, f = weight.shape
     if not projector_train_supported(f, d):
         raise ValueError("the training projector takes F % 32 == 0 and D a power of two in 32 .. 1024, got F = {}, D = {}".format(f, d))
@@ -360,11 +433,15 @@ def projector_wgrad(x, dz, stats):
     """The gradient of ``projector_train_forward``'s z w.r.t. weight and bias -> (dw (D, F), db (D,)): dw = sum over the rows
     of (dz |rstd|)^T (x - mean), on the fp32 matrix cores from the raw rows.  Activations of 2 GiB and more go in slices of
     whole rows, each call adding its chunks onto the result in order: the bits of one call (csrc/projector_train.hip)."""
+    _one_gpu("projector_wgrad", x=x, dz=dz, stats=stats)
+    if dz.dim() != 2 or x.dim() != 2:
+        raise ValueError("projector_wgrad: x (rows, F) and dz (rows, D), got {} and {}".format(tuple(x.shape), tuple(dz.shape)))
     n, d = dz.shape
     f = x.shape[1]
     x = _feature_rows(x, f)
-    if dz.dtype != torch.float32 or x.shape[0] != n or tuple(stats.shape) != (n, 2):
+    if dz.dtype != torch.float32 or x.shape[0] != n or tuple(stats.shape) != (n, 2) or stats.dtype != torch.float32:
         raise ValueError("dz: expected float32 ({}, D), statistics of the same rows".format(x.shape[0]))
+    stats = _rd("projector_wgrad", "stats", stats, align=8)          # ((mean, rstd) pairs: 8-byte loads)
     if not projector_train_supported(f, d):
         raise ValueError("the training projector takes F % 32 == 0 and D a power of two in 32 .. 1024, got F = {}, D = {}".format(f, d))
     dz = dz if dz.is_contiguous() else dz.contiguous()
@@ -392,10 +469,10 @@ def _attn_pool_args(x, A, keep):
     for name, t in (("x", x), ("A", A), ("keep", keep)):
         if t is None:
             continue
-        if t.dtype != torch.float32 or not t.is_cuda:
-            raise ValueError("{}: expected float32 on the GPU, got {} on {}".format(name, t.dtype, t.device))
-        if not t.is_contiguous():
-            raise ValueError("{}: expected a contiguous tensor".format(name))
+        if t.dtype != torch.float32 or not _gpu_device(t.device) or t.device != x.device:
+            raise ValueError("{}: expected float32 on the call's GPU, got {} on {}".format(name, t.dtype, t.device))
+        if not t.is_contiguous() or (name != "keep" and t.data_ptr() % 16):         # (keep: rows of M, read float by float)
+            raise ValueError("{}: expected a contiguous tensor at a 16-byte address (the kernels' float4 loads)".format(name))
     if x.dim() != 3 or A.dim() != 2 or A.shape[1] != x.shape[2]:
         raise ValueError("expected x (B, M, D) and A (R, D), got {} and {}".format(tuple(x.shape), tuple(A.shape)))
     B, M, D = x.shape
@@ -432,10 +509,10 @@ def attn_pool_backward(x, A, keep, P, Z, dZ, want_dx=True):
     returned for the same ``x``, ``A``, ``keep``."""
     B, M, D, R = _attn_pool_args(x, A, keep)
     for name, t, shape in (("P", P, (B, R, M)), ("Z", Z, (B, R, D)), ("dZ", dZ, (B, R, D))):
-        if t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != shape:
-            raise ValueError("{}: expected float32 {} on the GPU, got {} {}".format(name, shape, t.dtype, tuple(t.shape)))
-        if not t.is_contiguous():
-            raise ValueError("{}: expected a contiguous tensor".format(name))
+        if t.dtype != torch.float32 or not _gpu_device(t.device) or t.device != x.device or tuple(t.shape) != shape:
+            raise ValueError("{}: expected float32 {} on the call's GPU, got {} {}".format(name, shape, t.dtype, tuple(t.shape)))
+        if not t.is_contiguous() or (name != "P" and t.data_ptr() % 16):            # (P: rows of M, read float by float)
+            raise ValueError("{}: expected a contiguous tensor at a 16-byte address".format(name))
     dx = torch.empty_like(x) if want_dx else None
     dA = torch.empty((R, D), dtype=torch.float32, device=x.device)
     ws, nb = _attn_pool_workspace(B, M, R, D, x.device)

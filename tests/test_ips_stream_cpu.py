@@ -244,7 +244,7 @@ def test_stream_commit_refuses_bad_arguments_before_any_launch():
     with pytest.raises(RuntimeError, match="null tables"):
         hip.stream_commit(None, None, 4, 4)
     t = torch.zeros((1, 8, 4))
-    with pytest.raises(RuntimeError, match="tables"):
+    with pytest.raises(ValueError, match="5 tables"):         # (the wrapper's own count, in front of its device check)
         hip.stream_commit([(t, 2, t[:, :2], t)] * 5, None, 4, 4)
     with pytest.raises(ValueError, match="piece of 3 rows"):
         hip.stream_commit([(t, 2, t[:, :3], t)], None, 4, 4)
