@@ -125,7 +125,10 @@ extern "C" {
  *         pitches read per patch from a table, and the end of such a call in one launch (additions, the minor number stays);
  *         ipsx_ragged_view_blank_flags, ipsx_trunk_encode_ragged_view_dedup (+ ipsx_trunk_ragged_view_dedup_workspace_bytes) -
  *         exact blank-patch dedup on the ragged view: ipsx_trunk_encode_ragged_view encoding every non-blank entry and one
- *         blank one (additions, the minor number stays) */
+ *         blank one (additions, the minor number stays);
+ *         ipsx_trunk_encode_ragged_view_u8, ipsx_ragged_finish_view_u8, ipsx_ragged_view_blank_flags_u8,
+ *         ipsx_trunk_encode_ragged_view_dedup_u8 - the ragged view over whole uint8 images with their table: the four ragged
+ *         entries with the bytes' staging of ipsx_trunk_encode_view_u8 (additions, the minor number stays) */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -819,8 +822,9 @@ int ipsx_ragged_finish(const void* rows, int64_t row_bytes, int64_t total, const
                        const int64_t* mem_idx, const int32_t* flat, const void* pos, int64_t pos_row_bytes, int b, int m,
                        void* mem_patch, void* mem_pos, int64_t* mem_idx_out, int64_t* rows_out, void* stream);
 
-/* 3.06: the RAGGED patch-grid view (IPSNet.ips_image_ragged).  Whole float32 images of DIFFERENT sizes, (c, h_k, w_k) each,
- * packed into ONE buffer; the patches of all of them numbered one image after the other ("packed patches"), each image's
+/* 3.06: the RAGGED patch-grid view (IPSNet.ips_image_ragged).  Whole images of DIFFERENT sizes, (c, h_k, w_k) each - float32,
+ * or uint8 with their table through the _u8 entries at the end of this group, where an element is a byte -, packed into ONE
+ * buffer; the patches of all of them numbered one image after the other ("packed patches"), each image's
  * grid in the order of ipsx_patch_view.  One table entry per image: elem_off its first element inside the buffer, first its
  * first packed patch number, ny = (h - ph) / sh + 1, nx = (w - pw) / sw + 1.  Packed patch p belongs to the image k with the
  * largest first <= p and is grid patch p - first of it: it starts at element elem_off + (py * sh) * w + px * sw, its row
@@ -857,7 +861,8 @@ int ipsx_trunk_ragged_view_supported(const ipsx_trunk* t, const ipsx_ragged_view
  * where a patch's first pixel lies and its two pitches are per patch.  A list entry that is no packed patch reads packed
  * patch 0, never outside the buffer.  The load width is picked per launch from the HOST table: the kernel's wide load when
  * `pixels`, every elem_off, every w and sw are multiples of it, dword loads otherwise.  Plain launches only (no counted
- * launch, no uint8; blank-patch dedup: ipsx_trunk_encode_ragged_view_dedup below).  workspace: as ipsx_trunk_encode. */
+ * launch; uint8 images: ipsx_trunk_encode_ragged_view_u8, blank-patch dedup: ipsx_trunk_encode_ragged_view_dedup, both below).
+ * workspace: as ipsx_trunk_encode. */
 int ipsx_trunk_encode_ragged_view(const ipsx_trunk* t, const float* pixels, const ipsx_ragged_view* view,
                                   const int32_t* index /* NULL: packed patches first .. first+n-1 */, int64_t first, int64_t n,
                                   float* emb, void* workspace, size_t workspace_bytes, void* stream);
@@ -874,7 +879,7 @@ int ipsx_ragged_finish_view(const float* pixels, const ipsx_ragged_view* view, c
                             int64_t* mem_idx_out, int64_t* rows_out, void* stream);
 
 /* 3.06: exact blank-patch dedup on the ragged view (ipsx_trunk_encode_dedup for images of different sizes).  The fused
- * 1x32x32 trunk at precision 0 on float32 images only; every entry checks the view's HOST table again before it launches.
+ * 1x32x32 trunk at precision 0 on float32 images (uint8 images: the _u8 twins below); every entry checks the view's HOST table again before it launches.
  * nonblank[j] (device int32, n entries) = 1 when entry j's patch - packed patch index[j], or first + j when index is NULL -
  * has a non-zero element (-0.0 is zero, a denormal is not), 0 otherwise.  An entry that is no packed patch is flagged as
  * packed patch 0, the patch the encoder reads for it.  Nothing outside the patch windows is read. */
@@ -895,6 +900,31 @@ int ipsx_trunk_encode_ragged_view_dedup(const ipsx_trunk* t, const float* pixels
                                         const int32_t* index /* NULL: packed patches first .. first+n-1 */, int64_t first,
                                         int64_t n, float* emb, void* workspace, size_t workspace_bytes, int32_t* n_encoded,
                                         void* stream);
+
+/* 3.06: the ragged view over whole uint8 images.  `pixels` holds the packed images as bytes, `table` (c x 256 floats, device,
+ * at a 16-byte address) the float32 value of every byte per channel, as in ipsx_trunk_encode_view_u8; ipsx_image_entry.elem_off
+ * stays an element offset - for bytes an element is a byte - and ipsx_trunk_ragged_view_supported answers for bytes as for
+ * floats.  Every entry is, bit for bit, its float32 twin on the expanded buffer table[channel][byte] (which is never made);
+ * the exact fp32 trunks only (precision 0, patch_dtype 0).  The load width is picked per launch from the HOST table, the widest
+ * of the kernel's own list at which `pixels`, every image's byte offset, every w and sw are multiples: 1x32x32 fused 16 / 4 /
+ * 1 bytes (its pair kernel 8 / 4 / 1), 1x50x50 2 / 1, 3x100x100 4 / 1 - single bytes always fit, so any address is taken. */
+int ipsx_trunk_encode_ragged_view_u8(const ipsx_trunk* t, const uint8_t* pixels, const float* table, const ipsx_ragged_view* view,
+                                     const int32_t* index /* NULL: packed patches first .. first+n-1 */, int64_t first, int64_t n,
+                                     float* emb, void* workspace, size_t workspace_bytes, void* stream);
+/* ipsx_ragged_finish_view on bytes: mem_patch (b, m, c, ph, pw) is FLOAT32 table[channel][byte] of the copied patch; the
+ * padding slots of a short image are written as float +0.0 (not table[channel][0]).  Everything else as there. */
+int ipsx_ragged_finish_view_u8(const uint8_t* pixels, const float* table, const ipsx_ragged_view* view, const int64_t* row_offsets,
+                               const int64_t* mem_idx, int m, const int32_t* flat, const void* pos, int64_t pos_row_bytes,
+                               void* mem_patch, void* mem_pos, int64_t* mem_idx_out, int64_t* rows_out, void* stream);
+/* ipsx_ragged_view_blank_flags on bytes: blank means every byte of the 1x32x32 window is 0 (whatever the table makes of 0) */
+int ipsx_ragged_view_blank_flags_u8(const uint8_t* pixels, const ipsx_ragged_view* view, const int32_t* index, int64_t first,
+                                    int64_t n, int32_t* nonblank, void* stream);
+/* ipsx_trunk_encode_ragged_view_u8, bit for bit, by the four steps and the workspace of ipsx_trunk_encode_ragged_view_dedup
+ * (ipsx_trunk_ragged_view_dedup_workspace_bytes).  The ONE blank entry is encoded from its image like any other - every pixel
+ * table[0] -, so no blank embedding is handed in. */
+int ipsx_trunk_encode_ragged_view_dedup_u8(const ipsx_trunk* t, const uint8_t* pixels, const float* table,
+                                           const ipsx_ragged_view* view, const int32_t* index, int64_t first, int64_t n, float* emb,
+                                           void* workspace, size_t workspace_bytes, int32_t* n_encoded, void* stream);
 
 /* 3.06: the state update of a stream (IPSNet.ips_stream) as ONE launch, for up to four tables at once (patch rows,
  * embeddings, logits, global ids).  The n_cand candidates of a table are two segments that are never joined: its first

@@ -320,14 +320,21 @@ class IPSNet(nn.Module):
         whole 16-byte units), ``last_mem_emb`` gathered on first read; on a CPU device the loop itself.  With and without
         ``pad`` the route is the same.  Refused before the first launch:
         a slide with N_b <= M (the reference returns N_b patches there: no rectangular result), ``use_pos`` with
-        N_b > conf.N (with 'instance' shuffling: N_b != conf.N, where ``ips()`` itself raises), an empty batch, uint8 rows,
+        N_b > conf.N (with 'instance' shuffling: N_b != conf.N, where ``ips()`` itself raises), an empty batch,
         ``IPSX_DEDUP_BLANK=1``.
+
+        uint8 (N_b, C, h, w) patch slides of an image net (after ``set_patch_table``): the same call on a quarter of the
+        bytes - everything returned and left behind is, bit for bit, that of the float32 slides ``patch_table[c][byte]``,
+        ``mem_patch`` float32 (the finish runs on the byte rows, then ``hip.dequant_patches``).  Refused as ``ips()`` refuses
+        them: no table, a table whose rows differ from the channel count, ``IPSX_PRECISION`` other than ``fp32`` on a ROCm
+        device, a feature net (``TypeError``).
 
         ``pad=True`` takes slides with N_b <= M as well (an empty slide is refused) and returns the batch ``fill_batch`` of
         training/iterative.py builds from the solo calls: a short slide's rows in the order given in slots [0, N_b) - never
         shuffled, no random number drawn - and +0.0 behind them; ``mem_pos`` ``pos_enc[0, :N_b]`` then zeros;
         ``last_mem_idx`` 0 .. N_b-1 then -1; ``last_mem_emb`` the eval-mode embeddings of its rows, the padding slots the
-        embedding of ONE all-zero row (what ``forward()`` in eval mode computes from the padding); its ``last_shuffle`` entry
+        embedding of ONE all-zero row (what ``forward()`` in eval mode computes from the padding; uint8 slides: float32
+        ``+0.0`` and the all-zero FLOAT patch's embedding, not ``patch_table[c][0]``); its ``last_shuffle`` entry
         None (``last_shuffle`` None when no slide is long).  ``last_mem_count`` holds the B host ints min(N_b, M); nothing
         masks the padding - the reference attends to it as well.  Long slides are as without ``pad``; the finish launch
         writes the padding too, and a batch of short slides only encodes nothing until ``last_mem_emb`` is read."""
@@ -460,22 +467,26 @@ class IPSNet(nn.Module):
     @torch.no_grad()
     def ips_image_ragged(self, images, patch_size, patch_stride, pad=False):
         """``ips_image()`` on whole images of DIFFERENT sizes in one call: ``images`` an
-        ``ips_amd.ragged_image.RaggedImages`` or a list of (C, H_b, W_b) float32 tensors, on the device or on the host (copied
-        whole) -> (mem_patch (B, M, C, ph, pw), mem_pos (B, M, D) | None).  Image by image and bit for bit what
+        ``ips_amd.ragged_image.RaggedImages`` or a list of (C, H_b, W_b) float32 tensors - or uint8 ones after
+        ``set_patch_table``, the bytes a dataset stores: everything below as for the float32 images ``patch_table[c][byte]``,
+        which are never made, ``mem_patch`` float32 -, on the device or on the host (copied whole, as stored) -> (mem_patch (B, M, C, ph, pw), mem_pos (B, M, D) | None).  Image by image and bit for bit what
         ``for b in range(B): out[b] = net.ips_image(images[b][None], patch_size, patch_stride)`` returns and leaves behind,
         which is what ``net.ips_ragged([patchify(images[b]) for b], pad=pad)`` returns and leaves behind: ``last_mem_idx``
         (B, M) local to each image's grid, ``last_mem_emb``, ``last_shuffle`` the list of per-image permutations (drawn image
         by image: torch's RNG streams end where that loop leaves them), positions restarting at 0 in every image; with
         ``pad=True`` an image with ny_b * nx_b <= M comes back as ``ips_ragged(pad=True)`` returns a short slide, and
-        ``last_mem_count`` is set.  On a ROCm device, float32 images, an eval-mode encoder, no overridden ``do_shuffle``, at
+        ``last_mem_count`` is set.  On a ROCm device, float32 or uint8 images, an eval-mode encoder, no overridden ``do_shuffle``, at
         least one image longer than M and a trunk whose stem reads a ragged view (``EncoderPlan.ragged_view_supported``: the
         exact fp32 1x32x32, 1x50x50 and 3x100x100 trunks): ONE encoder pass over the grid patches of all images, read where
         they lie - no patch tensor is made -, one packed logits table, ONE loop launch (``ipsx_scan_ragged``) and ONE finish
-        launch (``ipsx_ragged_finish_view``).  Everywhere else the per-image patch tensors are materialised and
+        launch (``ipsx_ragged_finish_view``; bytes: the ``_u8`` exports, the load width picked per launch from the images'
+        byte offsets and widths).  Everywhere else the per-image patch tensors are materialised - uint8 images: as uint8
+        patches - and
         ``ips_ragged(list, pad)`` runs unchanged, with its own refusals.  Refused before the first launch and before a random
         number is drawn: everything ``ips_ragged`` refuses with "rows" read as grid patches, images whose channel counts
-        differ from each other or from the encoder's, a patch or stride that does not fit an image, uint8 images (TypeError:
-        they stay with solo ``ips_image()``), a feature net."""
+        differ from each other or from the encoder's, a patch or stride that does not fit an image, uint8 images without a table
+        (TypeError), with a table whose rows differ from the channel count or - on a ROCm device - under ``IPSX_PRECISION``
+        other than ``fp32``, a feature net."""
         from ..ragged_image import ips_image_ragged
         return ips_image_ragged(self, images, patch_size, patch_stride, pad)
 

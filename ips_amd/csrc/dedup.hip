@@ -336,6 +336,20 @@ __global__ __launch_bounds__(256) void blank_flags_ragged_view_kernel(const floa
     if (lane == 0) nonblank[j] = b != 0ull;
 }
 
+// ... of whole uint8 images: blank means every byte of the window 0.  A lane's 16 bytes are half a patch row, contiguous in
+// its image (view_load_u8: 16, 4 or 1 bytes per load by rv.wide) - the whole KiB in one read, as blank_scan_parts_view_u8_kernel
+__global__ __launch_bounds__(256) void blank_flags_ragged_view_u8_kernel(const unsigned char* __restrict__ x, RaggedViewArgs rv,
+                                                                         long long n, int* __restrict__ nonblank) {
+    const int lane = threadIdx.x & 63;
+    const long long j = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (j >= n) return;                                                   // wavefront-uniform
+    const RaggedAt at = ragged_at(rv, j);
+    unsigned w[4];
+    view_load_u8<4>(x + at.off + (long long)(lane >> 1) * at.v.w + 16 * (lane & 1), at.wide, w);
+    const unsigned long long b = __ballot((w[0] | w[1] | w[2] | w[3]) != 0u);
+    if (lane == 0) nonblank[j] = b != 0ull;
+}
+
 // Ordered compaction with many workgroups: a workgroup takes 1,024 entries.  It counts the non-blank entries in front of its
 // own and in the whole list and finds the first blank one by reading ALL flags (n / 1,024 workgroups x n flags out of the L2:
 // 35 us at 118 k entries, profiles/ips_image_ragged_dedup_trace.txt - 0.8 % of encoding a seventh of them), then writes list[slot] = the packed patch
@@ -565,9 +579,10 @@ IPSX_API size_t ipsx_trunk_ragged_view_dedup_workspace_bytes(const ipsx_trunk* t
     return ipsx_trunk_dedup_workspace_bytes(t, n);     // the same parts: flags, list, slots, the length, n + 1 compacted rows
 }
 
-// what both entries ask of the view and the list: a valid host table (checked again), a device table, 1x32x32 windows on
-// float32 pixels, the entries inside the packed patches (an index list: any int32 number, resolved to packed patch 0)
-static int ragged_dedup_list_check(const float* pixels, const ipsx_ragged_view* view, const int32_t* index, int64_t first,
+// what every entry asks of the view and the list: a valid host table (checked again), a device table, 1x32x32 windows on
+// float32 pixels - or bytes (u8) -, the entries inside the packed patches (an index list: any int32 number, resolved to
+// packed patch 0)
+static int ragged_dedup_list_check(const void* pixels, bool u8, const ipsx_ragged_view* view, const int32_t* index, int64_t first,
                                    int64_t n, const char* what) {
     IPSX_REQUIRE(pixels && view && n >= 0 && first >= 0, "%s: bad arguments", what);
     IPSX_REQUIRE(n < ((int64_t)1 << 31), "%s: too many entries", what);
@@ -576,13 +591,21 @@ static int ragged_dedup_list_check(const float* pixels, const ipsx_ragged_view* 
     IPSX_REQUIRE(view->images, "%s: no device table", what);
     IPSX_REQUIRE(view->c == 1 && view->ph == 32 && view->pw == 32, "%s: blank-patch detection reads the 1x32x32 patches of the "
                  "fused trunk, the view's are %dx%dx%d", what, view->c, view->ph, view->pw);
-    IPSX_REQUIRE(at_multiple(pixels, 4), "%s: images must lie at a 4-byte address", what);
+    IPSX_REQUIRE(u8 || at_multiple(pixels, 4), "%s: images must lie at a 4-byte address", what);
     IPSX_REQUIRE(index ? n <= 0x7FFFFFF0ll : first + n <= total, "%s: packed patches %lld .. %lld of %lld", what,
                  (long long)first, (long long)(first + n), (long long)total);
     return IPSX_OK;
 }
 
-static int ragged_blank_flags(const PatchSrc& src, int64_t n, int32_t* nonblank, hipStream_t s) {
+// (u8: src.base holds bytes - the scan needs no table, so src.table does not say it)
+static int ragged_blank_flags(const PatchSrc& src, bool u8, int64_t n, int32_t* nonblank, hipStream_t s) {
+    if (u8) {
+        RaggedViewArgs rv = ragged_view_args(src, {1});
+        rv.wide = ragged_view_load_width(src.base, *src.ragged, 1, {16, 4, 1});
+        blank_flags_ragged_view_u8_kernel<<<dim3((unsigned)cdiv(n, 4)), dim3(256), 0, s>>>(static_cast<const unsigned char*>(src.base),
+                                                                                           rv, n, nonblank);
+        return launched("blank_flags_ragged_view_u8");
+    }
     blank_flags_ragged_view_kernel<<<dim3((unsigned)cdiv(n, 4)), dim3(256), 0, s>>>(static_cast<const float*>(src.base),
                                                                                     ragged_view_args(src, 16), n, nonblank);
     return launched("blank_flags_ragged_view");
@@ -590,21 +613,29 @@ static int ragged_blank_flags(const PatchSrc& src, int64_t n, int32_t* nonblank,
 
 IPSX_API int ipsx_ragged_view_blank_flags(const float* pixels, const ipsx_ragged_view* view, const int32_t* index,
                                           int64_t first, int64_t n, int32_t* nonblank, void* stream) {
-    IPSX_TRY(ragged_dedup_list_check(pixels, view, index, first, n, "ragged_view_blank_flags"));
+    IPSX_TRY(ragged_dedup_list_check(pixels, false, view, index, first, n, "ragged_view_blank_flags"));
     IPSX_REQUIRE(nonblank || n == 0, "ragged_view_blank_flags: no flags");
     if (n == 0) return IPSX_OK;
-    return ragged_blank_flags(PatchSrc{pixels, nullptr, nullptr, index, index ? 0 : first, view}, n, nonblank, as_stream(stream));
+    return ragged_blank_flags(PatchSrc{pixels, nullptr, nullptr, index, index ? 0 : first, view}, false, n, nonblank, as_stream(stream));
 }
 
-IPSX_API int ipsx_trunk_encode_ragged_view_dedup(const ipsx_trunk* t, const float* pixels, const ipsx_ragged_view* view,
-                                                 const int32_t* index, int64_t first, int64_t n, float* emb, void* workspace,
-                                                 size_t workspace_bytes, int32_t* n_encoded, void* stream) {
-    const char* what = "trunk_encode_ragged_view_dedup";
+IPSX_API int ipsx_ragged_view_blank_flags_u8(const uint8_t* pixels, const ipsx_ragged_view* view, const int32_t* index,
+                                             int64_t first, int64_t n, int32_t* nonblank, void* stream) {
+    IPSX_TRY(ragged_dedup_list_check(pixels, true, view, index, first, n, "ragged_view_blank_flags_u8"));
+    IPSX_REQUIRE(nonblank || n == 0, "ragged_view_blank_flags_u8: no flags");
+    if (n == 0) return IPSX_OK;
+    return ragged_blank_flags(PatchSrc{pixels, nullptr, nullptr, index, index ? 0 : first, view}, true, n, nonblank, as_stream(stream));
+}
+
+// the four steps behind both entries; table: the pixels are bytes
+static int encode_ragged_view_dedup(const ipsx_trunk* t, const void* pixels, const float* table, const ipsx_ragged_view* view,
+                                    const int32_t* index, int64_t first, int64_t n, float* emb, void* workspace,
+                                    size_t workspace_bytes, int32_t* n_encoded, void* stream, const char* what) {
     IPSX_REQUIRE(t && emb, "%s: null pointer", what);
-    IPSX_TRY(ragged_dedup_list_check(pixels, view, index, first, n, what));
+    IPSX_TRY(ragged_dedup_list_check(pixels, table != nullptr, view, index, first, n, what));
     IPSX_REQUIRE(fused_trunk_supported(t) && t->precision == 0 && t->patch_dtype == 0 && t->c_in * t->h * t->w == PATCH_U4 * 4,
                  "%s: the exact fp32 fused 1x32x32 trunk only", what);
-    const PatchSrc src{pixels, nullptr, nullptr, index, index ? 0 : first, view};
+    const PatchSrc src{pixels, table, nullptr, index, index ? 0 : first, view};
     IPSX_TRY(patch_src_check(t, src, n, true, what));
     IPSX_TRY(parts_trunk_check(t, what));                                 // what the trunk launch refuses: before the scan
     if (n == 0) return IPSX_OK;
@@ -617,15 +648,33 @@ IPSX_API int ipsx_trunk_encode_ragged_view_dedup(const ipsx_trunk* t, const floa
     int* slot = list + n;
     int* count = slot + n;
     float* emb_u = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + (((size_t)n * 12 + 4 + 255) & ~(size_t)255));
-    IPSX_TRY(ragged_blank_flags(src, n, nonblank, s));
+    IPSX_TRY(ragged_blank_flags(src, table != nullptr, n, nonblank, s));
     ragged_compact_kernel<<<dim3((unsigned)cdiv(n, 1024)), dim3(1024), 0, s>>>(nonblank, (int)n, index, src.first, list, slot, count);
     IPSX_TRY(launched("ragged_compact"));
     // the list holds packed patch numbers: the trunk reads it as an index list of up to n entries, *count of them written
-    IPSX_TRY(fused_launch(t, PatchSrc{pixels, nullptr, nullptr, list, 0, view}, n, emb_u, s, count));
+    IPSX_TRY(fused_launch(t, PatchSrc{pixels, table, nullptr, list, 0, view}, n, emb_u, s, count));
     scatter_rows_kernel<<<dim3((unsigned)cdiv(n * 32, 256)), dim3(256), 0, s>>>(
         reinterpret_cast<const float4*>(emb_u), slot, reinterpret_cast<float4*>(emb), n, 32);
     IPSX_TRY(launched("scatter_rows"));
     if (n_encoded && hipMemcpyAsync(n_encoded, count, sizeof(int), hipMemcpyDeviceToDevice, s) != hipSuccess)
         return fail(IPSX_EHIP, "%s: count copy failed", what);
     return IPSX_OK;
+}
+
+IPSX_API int ipsx_trunk_encode_ragged_view_dedup(const ipsx_trunk* t, const float* pixels, const ipsx_ragged_view* view,
+                                                 const int32_t* index, int64_t first, int64_t n, float* emb, void* workspace,
+                                                 size_t workspace_bytes, int32_t* n_encoded, void* stream) {
+    return encode_ragged_view_dedup(t, pixels, nullptr, view, index, first, n, emb, workspace, workspace_bytes, n_encoded, stream,
+                                    "trunk_encode_ragged_view_dedup");
+}
+
+// ... on whole uint8 images: the ONE blank entry is encoded from its image like any other (every pixel table[0]), so no
+// blank embedding comes in from outside
+IPSX_API int ipsx_trunk_encode_ragged_view_dedup_u8(const ipsx_trunk* t, const uint8_t* pixels, const float* table,
+                                                    const ipsx_ragged_view* view, const int32_t* index, int64_t first, int64_t n,
+                                                    float* emb, void* workspace, size_t workspace_bytes, int32_t* n_encoded,
+                                                    void* stream) {
+    IPSX_REQUIRE(table, "trunk_encode_ragged_view_dedup_u8: no table");
+    return encode_ragged_view_dedup(t, pixels, table, view, index, first, n, emb, workspace, workspace_bytes, n_encoded, stream,
+                                    "trunk_encode_ragged_view_dedup_u8");
 }

@@ -497,6 +497,13 @@ __global__ __launch_bounds__(256, 2) void stem_pool50_ragged_view_kernel(StemArg
     const RaggedAt at = ragged_at(rv, p);
     stem_pool50_body<false, true, RaggedAt>(a, nullptr, &at);
 }
+// ... of whole uint8 images (table: 256 floats; rv.wide: 2 bytes per load, or 1), staged as stem_pool50_view_u8_kernel does
+__global__ __launch_bounds__(256, 2) void stem_pool50_ragged_view_u8_kernel(StemArgs a, const float* table, RaggedViewArgs rv) {
+    long long p = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (p >= a.n) p = a.n - 1;
+    const RaggedAt at = ragged_at(rv, p);
+    stem_pool50_body<true, true, RaggedAt>(a, table, &at);
+}
 
 // ------------------------------------------------------------------------------------------------ stem + max-pool, 3 x 100 px
 // The traffic-sign configuration's stem (config/traffic_config.yml: 3x100x100 patches -> 50x50x64 -> 25x25x64 pooled), same
@@ -770,6 +777,11 @@ __global__ __launch_bounds__(256, 1) void stem_pool100x3_ragged_view_kernel(Stem
     const RaggedAt at = ragged_at(rv, (long long)blockIdx.x);
     stem_pool100x3_body<false, true, RaggedAt>(a, nullptr, &at);
 }
+// ... of whole uint8 images (table: 3 x 256 floats; rv.wide: 4 bytes per load, or 1), staged as stem_pool100x3_view_u8_kernel does
+__global__ __launch_bounds__(256, 1) void stem_pool100x3_ragged_view_u8_kernel(Stem3Args a, const float* table, RaggedViewArgs rv) {
+    const RaggedAt at = ragged_at(rv, (long long)blockIdx.x);
+    stem_pool100x3_body<true, true, RaggedAt>(a, table, &at);
+}
 
 static bool stem_pool100x3_supported(const ipsx_trunk* t) {
     const char* e = getenv("IPSX_NO_FUSED");
@@ -812,12 +824,17 @@ int fused_stem_pool50(const ipsx_trunk* t, const PatchSrc& src, float* y, int64_
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S3_FLOATS_U8 * sizeof(float)));
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem_pool100x3_ragged_view_kernel),
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S3_FLOATS * sizeof(float)));
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(stem_pool100x3_ragged_view_u8_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(S3_FLOATS_U8 * sizeof(float)));
             attr3 = true;
         }
         const dim3 grid((unsigned)n), block(256);
         if (src.view && src.table)
             stem_pool100x3_view_u8_kernel<<<grid, block, S3_FLOATS_U8 * sizeof(float), s>>>(a3, src.table, view_args(src, {4, 1}));
         else if (src.view) stem_pool100x3_view_kernel<<<grid, block, S3_FLOATS * sizeof(float), s>>>(a3, view_args(src, {16}));
+        else if (src.ragged && src.table)
+            stem_pool100x3_ragged_view_u8_kernel<<<grid, block, S3_FLOATS_U8 * sizeof(float), s>>>(a3, src.table,
+                                                                                                  ragged_view_args(src, {4, 1}));
         else if (src.ragged)
             stem_pool100x3_ragged_view_kernel<<<grid, block, S3_FLOATS * sizeof(float), s>>>(a3, ragged_view_args(src, 16));
         else if (src.table) stem_pool100x3_u8_kernel<<<grid, block, S3_FLOATS_U8 * sizeof(float), s>>>(a3, src.table);
@@ -833,6 +850,8 @@ int fused_stem_pool50(const ipsx_trunk* t, const PatchSrc& src, float* y, int64_
     if (src.view && src.table)
         stem_pool50_view_u8_kernel<<<grid, block, 4 * SP_SLAB_U8 * sizeof(float), s>>>(a, src.table, view_args(src, {2, 1}));
     else if (src.view) stem_pool50_view_kernel<<<grid, block, 4 * SP_SLAB * sizeof(float), s>>>(a, view_args(src, {8}));
+    else if (src.ragged && src.table)
+        stem_pool50_ragged_view_u8_kernel<<<grid, block, 4 * SP_SLAB_U8 * sizeof(float), s>>>(a, src.table, ragged_view_args(src, {2, 1}));
     else if (src.ragged) stem_pool50_ragged_view_kernel<<<grid, block, 4 * SP_SLAB * sizeof(float), s>>>(a, ragged_view_args(src, 8));
     else if (src.table) stem_pool50_u8_kernel<<<grid, block, 4 * SP_SLAB_U8 * sizeof(float), s>>>(a, src.table);
     else stem_pool50_kernel<<<grid, block, 4 * SP_SLAB * sizeof(float), s>>>(a);

@@ -1003,6 +1003,8 @@ static void fused_lds_attrs() {
         {reinterpret_cast<const void*>(fused_trunk_view_u8_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_ragged_view_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_ragged_view_counted_kernel), FUSED_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_ragged_view_u8_kernel), FUSED_LDS},
+        {reinterpret_cast<const void*>(fused_trunk_ragged_view_counted_u8_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_parts_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_parts_view_kernel), FUSED_LDS},
         {reinterpret_cast<const void*>(fused_trunk_parts_u8_kernel), FUSED_LDS},
@@ -1017,10 +1019,11 @@ static void fused_lds_attrs() {
 }
 
 // `n` patches of `src` (checked by the entry: patch_src_check) -> emb.  A table or a view: the exact fp32 trunk only, no
-// stamps, no device-side count - but for a ragged view, which takes a count (ipsx_trunk_encode_ragged_view_dedup).
+// stamps, no device-side count - but for a ragged view, of float32 or uint8 images, which takes a count
+// (ipsx_trunk_encode_ragged_view_dedup, _dedup_u8).
 int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb, hipStream_t s, const int* count,
                  unsigned long long* stamps) {
-    if (((src.table || src.view) && (stamps || count)) || (src.ragged && stamps))
+    if (((src.table || src.view) && !src.ragged && (stamps || count)) || (src.ragged && stamps))
         return fail(IPSX_EINVAL, "fused trunk: uint8 patches and patch views go without stamps and device-side counts");
     FusedArgs a = fused_args(t, src, n, emb, true);
     a.count = count;
@@ -1062,6 +1065,16 @@ int fused_launch(const ipsx_trunk* t, const PatchSrc& src, int64_t n, float* emb
     const FusedArgs b = fused_args(t, tail, rest, emb + (size_t)n_full * 128, true);
     const dim3 grid8((unsigned)cdiv(stamps ? n : n_full, 8)), grid2((unsigned)cdiv(rest, 2));
     const size_t lds2 = (size_t)2 * SLAB * sizeof(float);
+    if (src.table && src.ragged) {                     // whole uint8 images of different sizes: the byte tiers of the uint8 view
+        FusedArgs ar = a, br = b;
+        ar.index = nullptr; br.index = nullptr;
+        if (count)
+            fused_trunk_ragged_view_counted_u8_kernel<<<grid8, dim3(512), FUSED_LDS, s>>>(ar, src.table, ragged_view_args(src, {16, 4, 1}));
+        else if (n_full)
+            fused_trunk_ragged_view_u8_kernel<<<grid8, dim3(512), FUSED_LDS, s>>>(ar, src.table, ragged_view_args(src, {16, 4, 1}));
+        if (rest) fused_trunk_pair_ragged_view_u8_kernel<<<grid2, dim3(256), lds2, s>>>(br, src.table, ragged_view_args(tail, {8, 4, 1}));
+        return launched("fused_trunk_ragged_view_u8");
+    }
     if (src.table && src.view) {
         if (n_full) fused_trunk_view_u8_kernel<<<grid8, dim3(512), FUSED_LDS, s>>>(a, src.table, fused_view_args(src));
         if (rest) fused_trunk_pair_view_u8_kernel<<<grid2, dim3(256), lds2, s>>>(b, src.table, fused_view_args(tail, 8));

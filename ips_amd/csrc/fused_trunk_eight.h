@@ -799,6 +799,27 @@ __global__ __launch_bounds__(512, 1) void fused_trunk_ragged_view_counted_kernel
     fused_trunk_body<false, false, false, true, false, RaggedAt>(a, nullptr, nullptr, nullptr, &at);
 }
 
+// ... through a ragged view of whole uint8 images (a.patches: the packed bytes; table: 256 floats): the patch resolved as in
+// fused_trunk_ragged_view_kernel, staged as in fused_trunk_view_u8_kernel (rv.wide: 16, 4 or 1 bytes per load)
+__global__ __launch_bounds__(512, 1) void fused_trunk_ragged_view_u8_kernel(FusedArgs a, const float* table, RaggedViewArgs rv) {
+    long long j = (long long)blockIdx.x * 8 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (j >= a.n) j = a.n - 1;
+    const RaggedAt at = ragged_at(rv, j);
+    fused_trunk_body<false, true, false, true, false, RaggedAt>(a, nullptr, table, nullptr, &at);
+}
+
+// ... behind the blank scan of a ragged view of uint8 images (ipsx_trunk_encode_ragged_view_dedup_u8), as
+// fused_trunk_ragged_view_counted_kernel: nothing reads the list beyond *a.count
+__global__ __launch_bounds__(512, 1) void fused_trunk_ragged_view_counted_u8_kernel(FusedArgs a, const float* table,
+                                                                                   RaggedViewArgs rv) {
+    const long long n_valid = *a.count;
+    if ((long long)blockIdx.x * 8 >= n_valid) return;                     // workgroup-uniform
+    long long j = (long long)blockIdx.x * 8 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (j >= n_valid) j = n_valid - 1;
+    const RaggedAt at = ragged_at(rv, j);
+    fused_trunk_body<false, true, false, true, false, RaggedAt>(a, nullptr, table, nullptr, &at);
+}
+
 __global__ __launch_bounds__(512, 1) void fused_trunk_parts_view_kernel(FusedArgs a, PartsArgs pa, ViewArgs va) {
     fused_trunk_body<false, false, true, true>(a, nullptr, nullptr, &pa, &va);
 }

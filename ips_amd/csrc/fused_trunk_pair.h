@@ -428,6 +428,15 @@ __global__ __launch_bounds__(256, 2) void fused_trunk_pair_ragged_view_kernel(Fu
     trunk_pair_tile<false, false, true, false, RaggedAt>(a, (long long)blockIdx.x * 2, lds, nullptr, &at);
 }
 
+// ... through a ragged view of whole uint8 images (table: 256 floats; rv.wide: 8, 4 or 1 bytes per load)
+__global__ __launch_bounds__(256, 2) void fused_trunk_pair_ragged_view_u8_kernel(FusedArgs a, const float* table, RaggedViewArgs rv) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];          // 2 slabs
+    long long j = (long long)blockIdx.x * 2 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 7));
+    if (j >= a.n) j = a.n - 1;
+    const RaggedAt at = ragged_at(rv, j);
+    trunk_pair_tile<false, true, true, false, RaggedAt>(a, (long long)blockIdx.x * 2, lds, table, &at);
+}
+
 // the counted launch behind the blank scan, second half (dedup.hip; launched behind fused_trunk_parts_dedup_kernel on its
 // stream): the entries clist[n8 .. *a.count) that the eight-patch workgroups leave - trunk_split_n8 of the count, as there -
 // two per workgroup, each to its own row, counted into their parts

@@ -202,6 +202,78 @@ __global__ __launch_bounds__(256) void ragged_finish_view_kernel(RaggedFinishVie
     }
 }
 
+// ragged_finish_view_kernel on whole uint8 images (ipsx_ragged_finish_view_u8): a.pixels holds bytes, mem_patch is float32
+// table[channel][byte] - what ipsx_dequant_patches makes of the copied bytes - and the padding of a short image float +0.0,
+// not table[channel][0].  VW: pixels per thread and step (4: one dword load and one 16-byte store - pw, every w, sw and the
+// addresses allow them, the host's decision - or 1).  The table (c x 256 floats) is read where it lies: L2-resident, and the
+// launch is the call's last one, not its hot one.
+template <int VW>
+__global__ __launch_bounds__(256) void ragged_finish_view_u8_kernel(RaggedFinishViewArgs a, const float* __restrict__ table) {
+    typedef typename std::conditional<VW == 4, float4, float>::type V;
+    const int j = blockIdx.x, k = blockIdx.y;
+    const long long r0 = a.row_off[k], r1 = a.row_off[k + 1];
+    const long long lo = ((long long)__builtin_amdgcn_readfirstlane((int)(r0 >> 32)) << 32) |
+                         (unsigned int)__builtin_amdgcn_readfirstlane((int)r0);
+    const long long hi = ((long long)__builtin_amdgcn_readfirstlane((int)(r1 >> 32)) << 32) |
+                         (unsigned int)__builtin_amdgcn_readfirstlane((int)r1);
+    const ipsx_image_entry e = a.images[k];
+    const long long n = (long long)e.ny * e.nx;
+    if (!(lo >= 0 && lo == e.first && hi - lo == n && hi <= a.total)) return;
+    const size_t slot = (size_t)k * a.m + j;
+    const int rowv = a.pw / VW, units = a.c * a.ph * rowv;
+    V* d = reinterpret_cast<V*>(a.out_patch + slot * ((size_t)a.c * a.ph * a.pw));
+    uint4* dp = a.pos ? a.out_pos + slot * a.pos_units : nullptr;
+    long long r;
+    if (n > a.m) {
+        if (!a.idx) return;                                     // (a batch of short images only has no selection)
+        r = a.idx[slot];
+        r = r < 0 ? 0 : (r >= n ? n - 1 : r);                   // inside its OWN image
+    } else if (j < n) {
+        r = j;
+    } else {                                                    // the padding of a short image: float zeros
+        V zero;
+        if constexpr (VW == 4) zero = make_float4(0.f, 0.f, 0.f, 0.f); else zero = 0.f;
+        for (int i = threadIdx.x; i < units; i += 256) d[i] = zero;
+        if (dp)
+            for (long long i = threadIdx.x; i < a.pos_units; i += 256) dp[i] = make_uint4(0u, 0u, 0u, 0u);
+        if (threadIdx.x == 0) {
+            a.idx_out[slot] = -1;
+            a.rows_out[slot] = -1;
+        }
+        return;
+    }
+    const long long g = lo + r;                                 // in [lo, hi): inside the table
+    long long ps = g;
+    if (a.flat) {
+        ps = a.flat[g];
+        ps = ps < 0 ? 0 : (ps >= a.total ? a.total - 1 : ps);
+    }
+    ps = (long long)__builtin_amdgcn_readfirstlane((int)ps);    // (total < 2^31; workgroup-uniform: the table is read scalar)
+    int w = a.images[0].w, h = a.images[0].h;
+    long long off = ragged_view_offset(a.images, a.b, a.sh, a.sw, ps, &w, &h);
+    if (off < 0) off = a.images[0].elem_off;
+    const unsigned char* s = reinterpret_cast<const unsigned char*>(a.pixels) + off;
+    for (int i = threadIdx.x; i < units; i += 256) {
+        const int xv = i % rowv, t = i / rowv, y = t % a.ph, ch = t / a.ph;
+        const unsigned char* q = s + ((long long)ch * h + y) * w + xv * VW;
+        const float* tc = table + 256 * ch;
+        if constexpr (VW == 4) {
+            const unsigned v = *reinterpret_cast<const unsigned*>(q);
+            d[i] = make_float4(tc[v & 0xFFu], tc[(v >> 8) & 0xFFu], tc[(v >> 16) & 0xFFu], tc[v >> 24]);
+        } else {
+            d[i] = tc[q[0]];
+        }
+    }
+    if (dp) {
+        const uint4* sp = a.pos + (size_t)g * a.pos_units;
+        for (long long i = threadIdx.x; i < a.pos_units; i += 256) dp[i] = sp[i];
+    }
+    if (threadIdx.x == 0) {
+        a.idx_out[slot] = r;
+        a.rows_out[slot] = g;
+    }
+}
+
 }  // namespace ipsx
 
 using namespace ipsx;
@@ -273,29 +345,54 @@ IPSX_API int ipsx_ragged_finish(const void* rows, int64_t row_bytes, int64_t tot
 
 // The end of IPSNet.ips_image_ragged in ONE launch (ragged_finish_view_kernel above): ipsx_ragged_finish on the patches of
 // images of different sizes, copied out of the packed buffer.  The view's host table is checked here, before the launch.
-IPSX_API int ipsx_ragged_finish_view(const float* pixels, const ipsx_ragged_view* view, const int64_t* row_offsets,
-                                     const int64_t* mem_idx, int m, const int32_t* flat, const void* pos, int64_t pos_row_bytes,
-                                     void* mem_patch, void* mem_pos, int64_t* mem_idx_out, int64_t* rows_out, void* stream) {
+// (table: the pixels are bytes, mem_patch their float32 values - ipsx_ragged_finish_view_u8)
+static int ragged_finish_view_impl(const void* pixels, const float* table, const ipsx_ragged_view* view, const int64_t* row_offsets,
+                                   const int64_t* mem_idx, int m, const int32_t* flat, const void* pos, int64_t pos_row_bytes,
+                                   void* mem_patch, void* mem_pos, int64_t* mem_idx_out, int64_t* rows_out, void* stream) {
     IPSX_REQUIRE(pixels && view && row_offsets && mem_patch && mem_idx_out && rows_out && m > 0, "ragged_finish_view: bad arguments");
     const int64_t total = ragged_view_total(view, "ragged_finish_view");
     if (total < 0) return IPSX_EINVAL;
     IPSX_REQUIRE(view->images && view->b <= 65535 && total > 0, "ragged_finish_view: a device table of at most 65535 images");
-    IPSX_REQUIRE(at_multiple(pixels, 4) && at_multiple(mem_patch, 4), "ragged_finish_view: pixels and mem_patch at 4-byte addresses");
+    IPSX_REQUIRE((table || at_multiple(pixels, 4)) && at_multiple(mem_patch, 4), "ragged_finish_view: pixels and mem_patch at 4-byte addresses");
     IPSX_REQUIRE(!pos || (mem_pos && pos_row_bytes > 0 && pos_row_bytes % 16 == 0 && at_multiple(pos, 16) && at_multiple(mem_pos, 16)),
                  "ragged_finish_view: positional rows of 16-byte units");
     RaggedFinishViewArgs a;
-    a.pixels = pixels; a.images = view->images; a.b = view->b; a.c = view->c; a.ph = view->ph; a.pw = view->pw;
+    a.pixels = static_cast<const float*>(pixels); a.images = view->images; a.b = view->b; a.c = view->c; a.ph = view->ph; a.pw = view->pw;
     a.sh = view->sh; a.sw = view->sw; a.total = total;
     a.row_off = reinterpret_cast<const long long*>(row_offsets); a.idx = reinterpret_cast<const long long*>(mem_idx); a.flat = flat;
     a.pos = static_cast<const uint4*>(pos); a.pos_units = pos ? pos_row_bytes / 16 : 0;
     a.out_patch = static_cast<float*>(mem_patch); a.out_pos = static_cast<uint4*>(mem_pos);
     a.idx_out = reinterpret_cast<long long*>(mem_idx_out); a.rows_out = reinterpret_cast<long long*>(rows_out); a.m = m;
     const dim3 grid((unsigned)m, (unsigned)view->b);
+    if (table) {                                           // bytes: dword loads where the view allows them, else single bytes
+        if (view->pw % 4 == 0 && at_multiple(mem_patch, 16) && ragged_view_at_multiple(pixels, *view, 4, 1))
+            ragged_finish_view_u8_kernel<4><<<grid, dim3(256), 0, as_stream(stream)>>>(a, table);
+        else
+            ragged_finish_view_u8_kernel<1><<<grid, dim3(256), 0, as_stream(stream)>>>(a, table);
+        return launched("ragged_finish_view_u8");
+    }
     if (view->pw % 4 == 0 && at_multiple(mem_patch, 16) && ragged_view_at_multiple(pixels, *view, 16))
         ragged_finish_view_kernel<4><<<grid, dim3(256), 0, as_stream(stream)>>>(a);
     else
         ragged_finish_view_kernel<1><<<grid, dim3(256), 0, as_stream(stream)>>>(a);
     return launched("ragged_finish_view");
+}
+
+IPSX_API int ipsx_ragged_finish_view(const float* pixels, const ipsx_ragged_view* view, const int64_t* row_offsets,
+                                     const int64_t* mem_idx, int m, const int32_t* flat, const void* pos, int64_t pos_row_bytes,
+                                     void* mem_patch, void* mem_pos, int64_t* mem_idx_out, int64_t* rows_out, void* stream) {
+    return ragged_finish_view_impl(pixels, nullptr, view, row_offsets, mem_idx, m, flat, pos, pos_row_bytes, mem_patch, mem_pos,
+                                   mem_idx_out, rows_out, stream);
+}
+
+// ... on whole uint8 images: mem_patch (b, m, c, ph, pw) float32 = table[channel][byte], the padding float +0.0
+IPSX_API int ipsx_ragged_finish_view_u8(const uint8_t* pixels, const float* table, const ipsx_ragged_view* view,
+                                        const int64_t* row_offsets, const int64_t* mem_idx, int m, const int32_t* flat,
+                                        const void* pos, int64_t pos_row_bytes, void* mem_patch, void* mem_pos,
+                                        int64_t* mem_idx_out, int64_t* rows_out, void* stream) {
+    IPSX_REQUIRE(table, "ragged_finish_view_u8: no table");
+    return ragged_finish_view_impl(pixels, table, view, row_offsets, mem_idx, m, flat, pos, pos_row_bytes, mem_patch, mem_pos,
+                                   mem_idx_out, rows_out, stream);
 }
 
 IPSX_API int ipsx_gather_rows(const void* src, const int64_t* idx, void* dst, int b, int64_t n_rows, int m,

@@ -12,8 +12,8 @@ namespace ipsx {
 //   the patch tensor at `base`: float32, t->patch_dtype (fused split trunks) or - with `table` - uint8 whose values are
 //   table[channel][byte]; or
 //   the grid of `view` over the whole images at `base`: float32, or - with `table` - uint8 through the table.
-//   the grids of `ragged` over float32 images of different sizes packed into the buffer at `base`: index and
-//   first count packed patches.
+//   the grids of `ragged` over images of different sizes packed into the buffer at `base`: float32, or - with
+//   `table` - uint8 through the table; index and first count packed patches.
 // A tensor that is read from patch k on has its base moved (`first` stays 0); only a view counts in `first`.
 struct PatchSrc {
     const void* base;
@@ -54,21 +54,31 @@ static inline ViewArgs view_args(const PatchSrc& s, std::initializer_list<int> w
 // (`what`: the entry's name): what ipsx_ragged_view_fill accepts, asked again by every entry that is handed a view
 int64_t ragged_view_total(const ipsx_ragged_view* rv, const char* what);
 // can every patch row of the view be read by loads of `wd` bytes: the buffer, every image's offset and row pitch and the
-// patches' column stride are multiples of it (the host knows the table it uploaded)
-static inline bool ragged_view_at_multiple(const void* base, const ipsx_ragged_view& rv, int wd) {
-    if (reinterpret_cast<uintptr_t>(base) % wd != 0 || (rv.sw * sizeof(float)) % wd != 0) return false;
+// patches' column stride are multiples of it (the host knows the table it uploaded).  elem: bytes per pixel (4, or 1 for
+// uint8 images - elem_off counts pixels, so a byte image's offset is its byte offset)
+static inline bool ragged_view_at_multiple(const void* base, const ipsx_ragged_view& rv, int wd, size_t elem = sizeof(float)) {
+    if (reinterpret_cast<uintptr_t>(base) % wd != 0 || (rv.sw * elem) % wd != 0) return false;
     for (int k = 0; k < rv.b; ++k)
-        if ((rv.host[k].elem_off * (long long)sizeof(float)) % wd != 0 || (rv.host[k].w * sizeof(float)) % wd != 0) return false;
+        if ((rv.host[k].elem_off * (long long)elem) % wd != 0 || (rv.host[k].w * elem) % wd != 0) return false;
     return true;
 }
-// what a ragged view kernel gets beside its usual arguments; wide: the kernel's one wide load (bytes), or 0 = dwords
-static inline RaggedViewArgs ragged_view_args(const PatchSrc& s, int widest) {
+// the widest of `widths` (bytes per load, widest first) at which every patch row of the ragged view starts; 0 when none does
+static inline int ragged_view_load_width(const void* base, const ipsx_ragged_view& rv, size_t elem, std::initializer_list<int> widths) {
+    for (const int wd : widths)
+        if (ragged_view_at_multiple(base, rv, wd, elem)) return wd;
+    return 0;
+}
+// what a ragged view kernel gets beside its usual arguments, made by the launcher that knows its kernel's load widths (bytes,
+// widest first), as view_args: float32 images the one wide load, else 0 = dwords; uint8 images (s.table) a list that ends on
+// 1, which always fits
+static inline RaggedViewArgs ragged_view_args(const PatchSrc& s, std::initializer_list<int> widths) {
     RaggedViewArgs rv;
     rv.images = s.ragged->images; rv.b = s.ragged->b; rv.sh = s.ragged->sh; rv.sw = s.ragged->sw;
     rv.index = s.index; rv.first = s.first;
-    rv.wide = ragged_view_at_multiple(s.base, *s.ragged, widest) ? widest : 0;
+    rv.wide = ragged_view_load_width(s.base, *s.ragged, s.table ? 1 : sizeof(float), widths);
     return rv;
 }
+static inline RaggedViewArgs ragged_view_args(const PatchSrc& s, int widest) { return ragged_view_args(s, {widest}); }
 
 // PARTS (ipsx_trunk_encode_parts): ONE launch encodes the index lists of every part of a call, one after the other, and says
 // how far each part has come - done[k] counts the patches of part k whose embeddings are written AND visible to the whole

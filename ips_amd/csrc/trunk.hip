@@ -111,8 +111,9 @@ int patch_src_check(const ipsx_trunk* t, const PatchSrc& src, int64_t n, bool fu
     IPSX_REQUIRE(t->patch_dtype == 0 || (fused && t->precision != 0), "%s: the stem kernels of the layer-by-layer trunk "
                  "(stem_pool50_kernel, stem_pool100x3_kernel, conv_any_kernel) read float32 patches; half-precision patch storage "
                  "exists for the fused 1x32x32 trunk at precision 1 (bf16) / 2 (fp32x3) only", what);
-    if (src.table && src.view) {
-        // whole uint8 images: the byte tier of the view kernels takes any image address (view_args), the table copy is 16-byte loads
+    if (src.table && (src.view || src.ragged)) {
+        // whole uint8 images: the byte tier of the view kernels takes any image address (view_args, ragged_view_args), the table
+        // copy is 16-byte loads
         IPSX_REQUIRE(t->precision == 0 && t->patch_dtype == 0, "%s: uint8 images go with the exact fp32 trunk only (precision 0, "
                      "patch_dtype 0), got precision %d, patch_dtype %d", what, t->precision, t->patch_dtype);
         IPSX_REQUIRE(at_multiple(src.table, 16), "%s: the table of uint8 images must lie at a 16-byte address", what);
@@ -137,8 +138,8 @@ int patch_src_check(const ipsx_trunk* t, const PatchSrc& src, int64_t n, bool fu
                      src.first, (long long)(src.first + n), (long long)view_patches(*src.view));
     }
     if (src.ragged) {
-        IPSX_REQUIRE(!src.table && !src.view, "%s: a ragged view reads float32 images, and is no ipsx_patch_view", what);
-        IPSX_REQUIRE(at_multiple(src.base, 4), "%s: images must lie at a 4-byte address", what);
+        IPSX_REQUIRE(!src.view, "%s: a ragged view is no ipsx_patch_view", what);
+        IPSX_REQUIRE(src.table || at_multiple(src.base, 4), "%s: images must lie at a 4-byte address", what);
         const int64_t total = ragged_view_total(src.ragged, what);
         if (total < 0) return IPSX_EINVAL;
         IPSX_REQUIRE(src.ragged->images, "%s: no device table", what);
@@ -419,6 +420,14 @@ IPSX_API int ipsx_trunk_encode_ragged_view(const ipsx_trunk* t, const float* pix
     IPSX_REQUIRE(t && pixels && view && emb && n >= 0 && first >= 0, "trunk_encode_ragged_view: bad arguments");
     return trunk_encode(t, PatchSrc{pixels, nullptr, nullptr, index, index ? 0 : first, view}, n, emb, workspace, workspace_bytes,
                         stream, "trunk_encode_ragged_view");
+}
+
+IPSX_API int ipsx_trunk_encode_ragged_view_u8(const ipsx_trunk* t, const uint8_t* pixels, const float* table,
+                                              const ipsx_ragged_view* view, const int32_t* index, int64_t first, int64_t n,
+                                              float* emb, void* workspace, size_t workspace_bytes, void* stream) {
+    IPSX_REQUIRE(t && pixels && table && view && emb && n >= 0 && first >= 0, "trunk_encode_ragged_view_u8: bad arguments");
+    return trunk_encode(t, PatchSrc{pixels, table, nullptr, index, index ? 0 : first, view}, n, emb, workspace, workspace_bytes,
+                        stream, "trunk_encode_ragged_view_u8");
 }
 
 IPSX_API int ipsx_trunk_encode_parts_view(const ipsx_trunk* t, const float* images, const ipsx_patch_view* v, const int32_t* index,

@@ -80,7 +80,7 @@ def dedup_auto():
     """IPSX_DEDUP_BLANK unset (or ``auto``): exact blank-patch dedup inside the one counted launch, wherever that route runs -
     float32 or uint8 patches, float32 or uint8 images (``selection.parts_one_launch``, ``ipsx_trunk_encode_parts_dedup`` and
     its ``_u8`` / ``_view`` / ``_view_u8`` twins), and in the packed encoder pass of ``ips_image_ragged`` on the fused trunk
-    (``ragged_image.ragged_dedup``, ``ipsx_trunk_encode_ragged_view_dedup``); every other route runs as under ``0`` and
+    (``ragged_image.ragged_dedup``, ``ipsx_trunk_encode_ragged_view_dedup``, uint8 images: ``_dedup_u8``); every other route runs as under ``0`` and
     refuses nothing.  ``0``: no dedup anywhere."""
     return os.environ.get("IPSX_DEDUP_BLANK", "auto") == "auto"
 
@@ -428,6 +428,16 @@ _EXPORTS = {
     "ipsx_trunk_ragged_view_dedup_workspace_bytes": (C.c_size_t, [C.POINTER(Trunk), C.c_int64]),
     "ipsx_trunk_encode_ragged_view_dedup": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.POINTER(RaggedViewStruct), C.c_void_p, C.c_int64,
                                                       C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "ipsx_trunk_encode_ragged_view_u8": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.POINTER(RaggedViewStruct), C.c_void_p,
+                                                   C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ipsx_ragged_finish_view_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RaggedViewStruct), C.c_void_p, C.c_void_p, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "ipsx_ragged_view_blank_flags_u8": (C.c_int, [C.c_void_p, C.POINTER(RaggedViewStruct), C.c_void_p, C.c_int64, C.c_int64,
+                                                  C.c_void_p, C.c_void_p]),
+    "ipsx_trunk_encode_ragged_view_dedup_u8": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.POINTER(RaggedViewStruct),
+                                                         C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                         C.c_void_p, C.c_void_p]),
     "ipsx_scan_ragged_spans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ipsx_stream_commit_ragged": (C.c_int, [C.POINTER(StreamTable), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64,
@@ -1487,15 +1497,21 @@ def ragged_finish(rows, offsets, mem_idx, M, flat=None, pos=None, out=None):
     return out, out_pos, idx, grow
 
 
-def ragged_finish_view(pixels, rview, offsets, mem_idx, M, flat=None, pos=None, out=None):
+def ragged_finish_view(pixels, rview, offsets, mem_idx, M, flat=None, pos=None, out=None, table=None):
     """The end of ``IPSNet.ips_image_ragged``, ONE launch (``ipsx_ragged_finish_view``): ``ragged_finish`` with the source
     row replaced by a grid patch copied out of its image.  ``pixels`` the packed 1-d float32 buffer, ``rview`` its
     ``RaggedView``, ``offsets`` (B + 1,) int64 packed patch numbers on the device, ``mem_idx`` / ``flat`` / ``pos`` as there
     -> (mem_patch (B, M, C, ph, pw), mem_pos | None, mem_idx with -1 in the padding, packed patch of every slot or -1).
     ``out``: those four tensors (``mem_pos`` None without ``pos``), written in place of fresh ones - every slot is written,
-    nothing depends on what they held."""
+    nothing depends on what they held.  ``table`` (C, 256): ``pixels`` is the packed uint8 buffer and ``mem_patch`` comes
+    back float32, ``table[c][byte]``, its padding float +0.0 (``ipsx_ragged_finish_view_u8``), as ``gather_patches_view``
+    dispatches on its table."""
     B, total, dev = len(rview.sizes), rview.count, pixels.device
-    if pixels.dtype != torch.float32 or pixels.dim() != 1 or not pixels.is_contiguous() or not on_device(pixels):
+    if table is not None:
+        if pixels.dtype != torch.uint8 or pixels.dim() != 1 or not pixels.is_contiguous() or not on_device(pixels):
+            raise ValueError("ragged_finish_view with a table needs the packed 1-d uint8 buffer on the GPU")
+        table = _patch_table(table, rview.patch_shape[0], dev)
+    elif pixels.dtype != torch.float32 or pixels.dim() != 1 or not pixels.is_contiguous() or not on_device(pixels):
         raise ValueError("ragged_finish_view needs the packed 1-d float32 buffer on the GPU")
     if offsets.dtype != torch.int64 or tuple(offsets.shape) != (B + 1,) or not offsets.is_contiguous() or offsets.device != dev:
         raise ValueError("ragged_finish_view needs the (B + 1,) int64 patch offsets on the pixels' device")
@@ -1517,6 +1533,11 @@ def ragged_finish_view(pixels, rview, offsets, mem_idx, M, flat=None, pos=None, 
                                                               or t.device != dev)):
             raise ValueError("ragged_finish_view: out must be the four contiguous result tensors on the pixels' device")
     out, out_pos, idx, grow = out
+    if table is not None:
+        _ck(lib().ipsx_ragged_finish_view_u8(_p(pixels), _p(table), C.byref(rview.struct), _p(offsets), _p(mem_idx), M, _p(flat),
+                                             _p(pos), pos.shape[1] * pos.element_size() if pos is not None else 0, _p(out),
+                                             _p(out_pos), _p(idx), _p(grow), _stream()), "ipsx_ragged_finish_view_u8")
+        return out, out_pos, idx, grow
     _ck(lib().ipsx_ragged_finish_view(_p(pixels), C.byref(rview.struct), _p(offsets), _p(mem_idx), M, _p(flat), _p(pos),
                                       pos.shape[1] * pos.element_size() if pos is not None else 0, _p(out), _p(out_pos), _p(idx),
                                       _p(grow), _stream()), "ipsx_ragged_finish_view")
@@ -1528,9 +1549,11 @@ def ragged_blank_flags(pixels, rview, index=None, first=0, n=None):
     ``pixels`` the packed 1-d float32 buffer on the GPU, ``rview`` its ``RaggedView`` (1x32x32 patches); the entries are
     packed patches ``index`` ((n,) int32 on the device; a number that is no packed patch reads packed patch 0) or
     ``first .. first + n - 1`` (default: all from ``first`` on) -> (n,) int32, 1 = non-blank (-0.0 is zero, a denormal is
-    not): the rule of the exact blank-patch dedup, read where the patches lie."""
-    if pixels.dtype != torch.float32 or pixels.dim() != 1 or not pixels.is_contiguous() or not on_device(pixels):
-        raise ValueError("ragged_blank_flags needs the packed 1-d float32 buffer on the GPU")
+    not): the rule of the exact blank-patch dedup, read where the patches lie.  A packed uint8 buffer: non-blank is any
+    byte of the window other than 0 (``ipsx_ragged_view_blank_flags_u8``; no table: the rule reads bytes)."""
+    u8 = pixels.dtype == torch.uint8
+    if not (u8 or pixels.dtype == torch.float32) or pixels.dim() != 1 or not pixels.is_contiguous() or not on_device(pixels):
+        raise ValueError("ragged_blank_flags needs the packed 1-d float32 (or uint8) buffer on the GPU")
     if index is not None:
         if index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous() or index.device != pixels.device:
             raise ValueError("index must be a contiguous 1-d int32 tensor on the pixels' device")
@@ -1541,6 +1564,10 @@ def ragged_blank_flags(pixels, rview, index=None, first=0, n=None):
         raise ValueError("patches {} .. {} of a view of {}".format(first, first + n, rview.count))
     rview.on(pixels.device)
     out = torch.empty((n,), dtype=torch.int32, device=pixels.device)
+    if u8:
+        _ck(lib().ipsx_ragged_view_blank_flags_u8(_p(pixels), C.byref(rview.struct), _p(index), first, n, _p(out), _stream()),
+            "ipsx_ragged_view_blank_flags_u8")
+        return out
     _ck(lib().ipsx_ragged_view_blank_flags(_p(pixels), C.byref(rview.struct), _p(index), first, n, _p(out), _stream()),
         "ipsx_ragged_view_blank_flags")
     return out
@@ -1635,7 +1662,8 @@ class RaggedView:
     """The patch grids of whole images of DIFFERENT sizes that lie in one packed buffer, as addresses (``ipsx_ragged_view``,
     DESIGN 2.8): packed patch ``p`` is grid patch ``p - first_b`` (``py * nx_b + px``, the order of the reference's
     ``unfold``) of the image ``b`` with the largest ``first_b <= p``.  ``sizes`` the (H_b, W_b) pairs, ``elem_offsets`` the
-    element offset of every image inside the buffer.  The table is built and checked on the host
+    element offset of every image inside the buffer - the pixels are float32, or uint8 read through a table
+    (``PatchSource(images=, ragged=, table=)``), for which an element is a byte.  The table is built and checked on the host
     (``ipsx_ragged_view_fill``: a geometry it refuses raises ValueError) and uploaded by ``on(device)``, once per device."""
 
     def __init__(self, channels, sizes, elem_offsets, patch_size, patch_stride):
@@ -1653,6 +1681,7 @@ class RaggedView:
         self.grids = tuple((e.ny, e.nx) for e in self.table[:B])
         self.lengths = tuple(ny * nx for ny, nx in self.grids)       # patches per image
         self.firsts = tuple(e.first for e in self.table[:B])
+        self.elem_offsets = tuple(e.elem_off for e in self.table[:B])
         self.count = int(total)
         self._device = {}                                             # device -> the uploaded table (kept alive here)
 
@@ -1665,6 +1694,19 @@ class RaggedView:
             dev = self._device[device] = host.to(device)
         self.struct.images = dev.data_ptr()
         return self
+
+    def load_width(self, pixels, widths):
+        """The launcher's rule for a ragged view kernel's load width (``ragged_view_args``, csrc/ipsx_internal.h), a pure host
+        function: the first of ``widths`` (bytes, widest first) of which the address of ``pixels`` (the packed 1-d buffer,
+        float32 or uint8), every image's byte offset, every row pitch ``W_b`` in bytes and the patches' column stride in
+        bytes are all multiples; 0 when none is.  The lists are ``PatchView.load_bytes``': fused 1x32x32 float32 (16,),
+        uint8 (16, 4, 1), its pair kernel (8, 4, 1); 1x50x50 (8,) / (2, 1); 3x100x100 (16,) / (4, 1)."""
+        e = pixels.element_size()
+        for wd in widths:
+            if pixels.data_ptr() % wd == 0 and self.patch_stride[1] * e % wd == 0 and \
+                    all(o * e % wd == 0 and w * e % wd == 0 for o, (_, w) in zip(self.elem_offsets, self.sizes)):
+                return wd
+        return 0
 
     def origin(self, p):
         """(element offset of packed patch ``p``'s (0, 0, 0) inside the buffer, row pitch, channel pitch) - or (-1, 0, 0)
@@ -1679,8 +1721,9 @@ class PatchSource:
     ``PatchSource(patches, table=None)``: (P, C, h, w) or (B, N, C, h, w) on the GPU, float32, float16 / bfloat16 under
     IPSX_PRECISION=bf16 / fp32x3, or uint8 with its ``table`` (C, 256); or whole images read through a patch grid
     ``PatchSource(images=..., view=..., table=None)`` (``PatchView``, DESIGN 2.3: float32 images, or uint8 images with
-    their ``table``), whose patch tensor is never made; or float32 images of different sizes in ONE packed 1-d buffer read
-    through their grids ``PatchSource(images=pixels, ragged=...)`` (``RaggedView``).  Everything that
+    their ``table``), whose patch tensor is never made; or images of different sizes in ONE packed 1-d buffer read
+    through their grids ``PatchSource(images=pixels, ragged=..., table=None)`` (``RaggedView``, DESIGN 2.8: float32 pixels,
+    or uint8 pixels with their ``table``).  Everything that
     refuses a storage kind does so here, once, before the first launch; what is kept is contiguous.  ``shape`` is that of
     the patch tensor (for a view: the one ``patchify`` would make), ``count`` its number of patches."""
 
@@ -1689,9 +1732,19 @@ class PatchSource:
     def __init__(self, patches=None, table=None, images=None, view=None, ragged=None):
         self.patches = self.table = self.images = self.view = self.ragged = None
         if ragged is not None:
-            # float32 images of different sizes in one packed 1-d buffer, read through a ``RaggedView``
-            if table is not None or images.dtype != torch.float32 or images.dim() != 1 or not on_device(images):
-                raise TypeError("a ragged view reads a packed 1-d float32 buffer on the GPU")
+            # images of different sizes in one packed 1-d buffer, read through a ``RaggedView``: float32, or
+            # uint8 with their table - refused where uint8 patches are (``_patches``)
+            if images.dim() != 1 or not on_device(images) or (images.dtype != torch.uint8 and (table is not None or
+                                                                                               images.dtype != torch.float32)):
+                raise TypeError("a ragged view reads a packed 1-d float32 buffer on the GPU, or a uint8 one with its table")
+            if images.dtype == torch.uint8:
+                if table is None:
+                    raise TypeError("uint8 images need a dequantisation table: IPSNet.set_patch_table(ips_amd.quant.patch_table(...))")
+                if precision() != "fp32":
+                    raise TypeError("uint8 images go with the exact trunk (IPSX_PRECISION=fp32), not {}".format(precision()))
+                if dedup_blank():
+                    raise TypeError("blank-patch dedup reads float32 patches (IPSX_DEDUP_BLANK=1 with uint8 images)")
+                self.table = _patch_table(table, ragged.patch_shape[0], images.device)
             self.images, self.ragged = images if images.is_contiguous() else images.contiguous(), ragged.on(images.device)
             self.shape = torch.Size((ragged.count,) + ragged.patch_shape)
             self.dtype, self.device, self.count = images.dtype, images.device, ragged.count

@@ -315,7 +315,8 @@ class EncoderPlan:
         blank-patch dedup inside that launch (``ipsx_trunk_encode_parts_dedup`` and its ``_u8`` / ``_view`` / ``_view_u8``
         twins) - the same bits, the rows of the all-zero (bytes: all-zero-byte) entries written from ``blank_embedding``;
         ``n_encoded`` then holds the number of entries the trunk encoded.  A source with a ``hip.RaggedView`` (images of
-        different sizes in one packed buffer): ``index`` / ``first`` count packed patches, no ``parts``
+        different sizes in one packed buffer; float32 pixels, or uint8 pixels with their table - the ``_u8``
+        exports, the bits of the float32 expansion ``table[c][byte]``): ``index`` / ``first`` count packed patches, no ``parts``
         (``ipsx_trunk_encode_ragged_view``); ``dedup`` there, on the fused 1x32x32 trunk only (ValueError on any other): the
         explicit route on plain launches - blank scan through the view, ordered compaction, the trunk over the non-blank
         entries and ONE blank one, scatter (``ipsx_trunk_encode_ragged_view_dedup``) - the same bits, and ``n_encoded`` is set."""
@@ -386,9 +387,11 @@ class EncoderPlan:
             nb = L.ipsx_trunk_ragged_view_dedup_workspace_bytes(tr, n)
             if self.n_encoded is None or self.n_encoded.device != src.device:
                 self.n_encoded = torch.zeros((), dtype=torch.int32, device=src.device)
-            _ck(L.ipsx_trunk_encode_ragged_view_dedup(tr, _p(base), rv, _p(index), first, n, _p(out),
-                                                      _p(self._workspace(nb, src.device)), nb, _p(self.n_encoded), _stream()),
-                "ipsx_trunk_encode_ragged_view_dedup")
+            tail = (rv, _p(index), first, n, _p(out), _p(self._workspace(nb, src.device)), nb, _p(self.n_encoded), _stream())
+            if tab.value:                                  # whole uint8 images: the ONE blank entry is read from its image
+                _ck(L.ipsx_trunk_encode_ragged_view_dedup_u8(tr, _p(base), tab, *tail), "ipsx_trunk_encode_ragged_view_dedup_u8")
+            else:
+                _ck(L.ipsx_trunk_encode_ragged_view_dedup(tr, _p(base), *tail), "ipsx_trunk_encode_ragged_view_dedup")
             return out
         flat = base if vs is not None or rv is not None else base.view(-1, *src.shape[-3:])
 
@@ -398,8 +401,12 @@ class EncoderPlan:
             outs = _p(out[lo:lo + cnt])
             if rv is not None:                             # images of different sizes: index and first count packed patches
                 ix, lo1 = (_p(index[lo:]), 0) if index is not None else (None, first + lo)
-                _ck(L.ipsx_trunk_encode_ragged_view(tr, _p(flat), rv, ix, lo1, cnt, outs, _p(ws), nb, _stream()),
-                    "ipsx_trunk_encode_ragged_view")
+                if tab.value:                              # whole uint8 images
+                    _ck(L.ipsx_trunk_encode_ragged_view_u8(tr, _p(flat), tab, rv, ix, lo1, cnt, outs, _p(ws), nb, _stream()),
+                        "ipsx_trunk_encode_ragged_view_u8")
+                else:
+                    _ck(L.ipsx_trunk_encode_ragged_view(tr, _p(flat), rv, ix, lo1, cnt, outs, _p(ws), nb, _stream()),
+                        "ipsx_trunk_encode_ragged_view")
             elif vs is not None:
                 ix, lo1 = (_p(index[lo:]), 0) if index is not None else (None, first + lo)
                 if tab.value:                              # whole uint8 images

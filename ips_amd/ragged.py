@@ -144,10 +144,18 @@ def _check(net, slides, pad=False):
     slide is not."""
     if len(slides) == 0:
         raise ValueError("ips_ragged: an empty batch")
-    if slides.dtype == torch.uint8:
-        raise TypeError("ips_ragged reads float32 rows (float16 / bfloat16 where ips() takes them): uint8 patch storage goes "
-                        "through ips() slide by slide")
-    if hip.dedup_blank():                      # (as streams do: whatever the device)
+    if slides.dtype == torch.uint8:            # what IPSNet._check_u8 asks of the solo calls' (1, N_b, C, h, w) patches
+        if not net.is_image or slides.rows.dim() != 4:
+            raise TypeError("uint8 rows go with the (sum N_b, C, h, w) patches of an image encoder (set_patch_table), "
+                            "a feature net reads float rows")
+        table = net._table_for(slides)
+        channels = getattr(slides, "channels", None)
+        channels = slides.rows.shape[1] if channels is None else channels
+        if table.shape[0] != channels:
+            raise ValueError("the patch table has {} rows, the patches {} channels".format(table.shape[0], channels))
+        if hip.on_device(net.device) and hip.precision() != "fp32":
+            raise TypeError("uint8 patches go with the exact trunk (IPSX_PRECISION=fp32), not {}".format(hip.precision()))
+    if hip.dedup_blank():                     # (as streams do: whatever the device)
         raise TypeError("blank-patch dedup needs batches of one length (IPSX_DEDUP_BLANK=1 with ips_ragged)")
     if slides.rows.dim() != (4 if net.is_image else 2):
         raise TypeError("ips_ragged: {} rows for {}".format(tuple(slides.rows.shape), "an image encoder ((sum N_b, C, h, w))" if net.is_image
@@ -205,7 +213,8 @@ def _index_ok(net, rows):
     if not net.is_image:
         return rows.dtype in (torch.float32, torch.float16, torch.bfloat16)
     plan = net.plan
-    return rows.dtype == torch.float32 and bool(plan.index_list_supported(rows.shape))
+    # (uint8 rows come with their table - ``_check`` saw to it - and the list addresses bytes as it addresses floats)
+    return rows.dtype in (torch.float32, torch.uint8) and bool(plan.index_list_supported(rows.shape))
 
 
 def _packed(net, slides, skip=(), encode=True):
@@ -239,7 +248,7 @@ def _packed(net, slides, skip=(), encode=True):
         if flat is None:
             emb = net._embed(rows)
         elif net.is_image:
-            emb = net.plan.encode_source(hip.PatchSource(rows, None), index=flat)
+            emb = net.plan.encode_source(hip.PatchSource(rows, net._table_for(rows)), index=flat)
         else:
             emb = net.plan.encode(rows, index=flat)
     pos = None
@@ -288,8 +297,9 @@ def _host_emb(net, long_emb, short_rows):
                 rows = short_rows[b]
                 e = net._embed(rows)
                 if rows.shape[0] < M:
-                    if zero is None:
-                        zero = net._embed(torch.zeros((1,) + tuple(rows.shape[1:]), dtype=rows.dtype, device=rows.device))
+                    if zero is None:           # (uint8 rows: the padding of mem_patch is float32 +0.0, not byte 0)
+                        zero = net._embed(torch.zeros((1,) + tuple(rows.shape[1:]), device=rows.device,
+                                                      dtype=torch.float32 if rows.dtype == torch.uint8 else rows.dtype))
                     e = torch.cat((e, zero.expand(M - rows.shape[0], -1)), 0)
             if out is None:
                 out = torch.empty((B, M, e.shape[-1]), dtype=e.dtype, device=e.device)
@@ -303,7 +313,8 @@ def _host_route(net, slides):
     (batch statistics: no per-row function)."""
     B, M, D, device = len(slides), net.M, net.D, net.device
     shape = tuple(slides.rows.shape[1:])
-    mem_patch = torch.zeros((B, M) + shape, dtype=slides.dtype, device=device)
+    u8 = slides.dtype == torch.uint8           # (the solo calls return the selected bytes dequantised: the buffer is float32)
+    mem_patch = torch.zeros((B, M) + shape, dtype=torch.float32 if u8 else slides.dtype, device=device)
     mem_pos = torch.zeros((B, M, D), dtype=net.pos_enc.dtype, device=device) if net.use_pos else None
     mem_idx = torch.full((B, M), -1, dtype=torch.int64, device=device)
     long_emb, short_rows, shuf = {}, {}, []
@@ -318,7 +329,7 @@ def _host_route(net, slides):
             shuf.append(net.last_shuffle)
         else:                                  # what ips() returns before it shuffles, as fill_batch writes it
             short_rows[b] = rows = slides[b].to(device)
-            mem_patch[b, :n] = rows
+            mem_patch[b, :n] = net._dequant(rows) if u8 else rows
             if net.use_pos:
                 mem_pos[b, :n] = net.pos_enc[0, :n]
             mem_idx[b, :n] = torch.arange(n, dtype=torch.int64, device=device)
@@ -376,11 +387,17 @@ def _device_route(net, slides, short_ok):
             mem_patch, mem_pos, mem_idx, grow = hip.ragged_finish(rows, offsets, mem_idx, M, flat, pos2)
         else:
             mem_patch, mem_pos, mem_idx, grow = _finish_aten(rows, offsets, lengths, mem_idx, M, flat, pos2)
+        if rows.dtype == torch.uint8:
+            # the (B, M) selected byte rows leave as float32 table[c][byte]; the padding behind a short slide's rows is
+            # float32 +0.0 (what fill_batch's zero-initialised buffers hold), not table[c][0]
+            mem_patch = hip.dequant_patches(mem_patch, net._table_for(rows))
+            if any(lengths[b] < M for b in short):
+                mem_patch.masked_fill_((mem_idx < 0).view(B, M, 1, 1, 1), 0)
     if net.last_shuffle is not None and all(s is None for s in net.last_shuffle):
         net.last_shuffle = None
 
     unencoded = rows if emb is None else None       # (a batch of short slides only: at most B * M rows, kept until they are read)
-    zero_row = (1,) + tuple(rows.shape[1:]), rows.dtype
+    zero_row = (1,) + tuple(rows.shape[1:]), torch.float32 if rows.dtype == torch.uint8 else rows.dtype
     padded = any(lengths[b] < M for b in short)
 
     def emb_of_slots():

@@ -12,6 +12,10 @@ with torch's RNG streams consumed as that loop consumes them.  On a ROCm device 
 encoder pass over the grid patches of all images, read where they lie through a ragged view (``hip.RaggedView``: no patch
 tensor is made), one packed logits table, ONE selection-loop launch (``ipsx_scan_ragged``) and ONE finish launch
 (``ipsx_ragged_finish_view``); everywhere else the patch tensors are materialised and ``ips_ragged`` runs unchanged.
+
+uint8 images (after ``net.set_patch_table``): the same call on a quarter of the bytes - the stems, the blank scan and the
+finish launch read the bytes where they lie through the table (the ``_u8`` exports); everything returned and left behind is,
+bit for bit, that of the float32 images ``table[c][byte]``, which are never made, and ``mem_patch`` is float32.
 """
 
 import os
@@ -146,8 +150,8 @@ class _Grids:
             return 4
         shape = ("sum ny_b nx_b", "C", "ph", "pw")
 
-    def __init__(self, lengths, dtype):
-        self.lengths, self.dtype, self.rows = tuple(lengths), dtype, self._Rows()
+    def __init__(self, lengths, dtype, channels):
+        self.lengths, self.dtype, self.channels, self.rows = tuple(lengths), dtype, channels, self._Rows()
 
     def __len__(self):
         return len(self.lengths)
@@ -208,18 +212,16 @@ def ips_image_ragged(net, images, patch_size, patch_stride, pad=False):
         images = RaggedImages.from_list(images, pad)
     if len(images) == 0:
         raise ValueError("ips_image_ragged: an empty batch")
-    if images.dtype == torch.uint8:
-        raise TypeError("ips_image_ragged reads float32 images: uint8 images go through ips_image() image by image")
     c_in = _encoder_channels(net)
     if c_in is not None and images.channels != c_in:
         raise ValueError("images have {} channels, the encoder expects {}".format(images.channels, c_in))
     grids = images.grids(patch_size, patch_stride)
     lengths = tuple(ny * nx for ny, nx in grids)
-    _check(net, _Grids(lengths, images.dtype), pad)
+    _check(net, _Grids(lengths, images.dtype, images.channels), pad)   # (uint8: a table of C rows, the exact trunk)
     net._reset_last()
 
     rview = None
-    if (hip.on_device(net.device) and images.dtype == torch.float32
+    if (hip.on_device(net.device) and images.dtype in (torch.float32, torch.uint8)
             and not (net.encoder.training and not net.training)           # (the selection itself puts a training NET into eval mode)
             and not (net.shuffle and net._shuffle_overridden())
             and any(n > net.M for n in lengths)
@@ -257,7 +259,8 @@ def _viewed_route(net, images, rview, short_ok):
                 by_index = os.environ.get("IPSX_SHUFFLE", "index") != "copy"
                 net.last_shuffle = [None if b in short else (local[rview.firsts[b]:rview.firsts[b] + lengths[b]] if by_index else perms[b]).unsqueeze(0)
                                     for b in range(B)]
-            src = hip.PatchSource(images=dev.pixels, ragged=rview)
+            table = net._table_for(dev)                  # (uint8 pixels: read through the table, never expanded)
+            src = hip.PatchSource(images=dev.pixels, ragged=rview, table=table)
             # ONE encoder pass over all grid patches (the fused trunk: blank ones encoded once, the same bits)
             emb = net.plan.encode_source(src, index=flat, dedup=ragged_dedup(os.environ, net.plan, rview))
             pos = None
@@ -267,7 +270,7 @@ def _viewed_route(net, images, rview, short_ok):
                 pos = net.pos_enc[0].index_select(0, local)          # positions restart at 0 in every image
             logits = hip.logits(emb.unsqueeze(0), pos.unsqueeze(0) if pos is not None else None, ca.folded_query(), ca.H * ca.n_token)[0]
             mem_idx = hip.scan_ragged(logits, offsets, lengths, M, net.I, ca.H, ca.n_token, short_ok=short_ok)
-        mem_patch, mem_pos, mem_idx, grow = hip.ragged_finish_view(dev.pixels, rview, offsets, mem_idx, M, flat, pos)
+        mem_patch, mem_pos, mem_idx, grow = hip.ragged_finish_view(dev.pixels, rview, offsets, mem_idx, M, flat, pos, table=table)
     if net.last_shuffle is not None and all(s is None for s in net.last_shuffle):
         net.last_shuffle = None
 
