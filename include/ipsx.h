@@ -128,7 +128,10 @@ extern "C" {
  *         blank one (additions, the minor number stays);
  *         ipsx_trunk_encode_ragged_view_u8, ipsx_ragged_finish_view_u8, ipsx_ragged_view_blank_flags_u8,
  *         ipsx_trunk_encode_ragged_view_dedup_u8 - the ragged view over whole uint8 images with their table: the four ragged
- *         entries with the bytes' staging of ipsx_trunk_encode_view_u8 (additions, the minor number stays) */
+ *         entries with the bytes' staging of ipsx_trunk_encode_view_u8 (additions, the minor number stays);
+ *         ipsx_stream_commit_ragged_view - row bands of whole images of different sizes (IPSNet.ips_ragged_stream with a
+ *         patch size): ipsx_stream_commit_ragged whose patch table reads its piece out of the packed pixel windows of a feed
+ *         through an ipsx_ragged_view, no patch tensor exists (an addition, the minor number stays) */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -976,6 +979,23 @@ int ipsx_stream_commit_view(const ipsx_stream_table* tables, int n_tables, const
  * destination that overlaps the piece, or the held rows other than in place from the same address. */
 int ipsx_stream_commit_ragged(const ipsx_stream_table* tables, int n_tables, const int64_t* sel, const int64_t* slides, int b,
                               int m, int64_t rows_max, int64_t piece_rows_total, void* stream);
+/* 3.06: ipsx_stream_commit_ragged for a ragged stream fed pixel-row bands (RaggedIPSStream.feed_rows).  tables[0] is the patch
+ * table and has no `piece` pointer: candidate held + r of slide k is packed patch first_k + r of `view` over `pixels` (the
+ * packed 1-d buffer of the feed's windows, elem_size 4: float32 | 1: uint8) - word 3 of the slide's row counts packed patches
+ * of the view as it counts rows of the packed pieces of tables[1 ..], which keep them.  The patch's image is resolved by the
+ * bisection of the ragged stems, once per workgroup; the patch is copied raw, c * ph segments of pw elements with row pitch w
+ * and channel pitch h * w of ITS image (bytes stay bytes); row_bytes of table 0 is c * ph * pw * elem_size.  The view may
+ * have fewer entries than the launch has slides.  Table 0 is copied 16 / 4 / 1 bytes per lane, ONE width for the launch: the
+ * widest of which pixels, every entry's byte offset, every w, sw and pw in bytes, dst and held are all multiples - decided
+ * from the view's HOST table (*unit, when given, says which); no load touches a byte outside a patch row.  Whatever the
+ * device tables say, nothing is read outside the pixel buffer (its extent is the host table's) or a table's held_rows and
+ * nothing is written outside dst_rows; a slide whose numbers contradict any table of the launch - first + (cand - held)
+ * beyond the view's patch count included - is left untouched in all of them.  Refused before the launch: what
+ * ipsx_stream_commit_ragged refuses, a view whose host table is invalid or that has no device table, table 0 with a piece
+ * pointer or another row_bytes, another elem_size, a destination of table 0 that overlaps the pixels. */
+int ipsx_stream_commit_ragged_view(const ipsx_stream_table* tables, int n_tables, const void* pixels, const ipsx_ragged_view* view,
+                                   int elem_size, const int64_t* sel, const int64_t* slides, int b, int m, int64_t rows_max,
+                                   int64_t piece_rows_total, int* unit, void* stream);
 
 /* ONE IPSNet.ips call whose selection loop is resident (architecture/ips_net.py:169-262 for one image on the fused trunk,
  * or for feature slides through the projector), enqueued by ONE library call: fill of the control words, the loop on

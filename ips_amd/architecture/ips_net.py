@@ -505,15 +505,23 @@ class IPSNet(nn.Module):
         from ..stream import IPSStream
         return IPSStream(self, patch_size, patch_stride)
 
-    def ips_ragged_stream(self, pad=False):
+    def ips_ragged_stream(self, pad=False, patch_size=None, patch_stride=None):
         """``ips_ragged()`` over slides whose rows arrive in pieces -> ``ips_amd.ragged_stream.RaggedIPSStream``:
         ``feed(pieces)`` takes a ``Ragged`` or a list of B tensors (n_b, F) | (n_b, C, h, w) - the next rows of each slide,
         n_b >= 0, on the device or the host -, ``feed_all(slides, slab_rows)`` walks a whole batch in slabs, and ``finish()``
         returns and leaves behind what ``ips_ragged([torch.cat(pieces of slide b) for b], pad=pad)`` does with ``shuffle``
         off, bit for bit.  The state is M + I - 1 rows per slide whatever the lengths turn out to be; a host batch goes over
-        slab by slab.  The stream never shuffles."""
+        slab by slab.  The stream never shuffles.
+
+        With ``patch_size`` (ph, pw) and ``patch_stride`` (sh, sw) - both, as ``ips_stream`` takes them - the stream is a
+        ragged ROW stream: ``feed_rows(bands)`` takes a list of B entries, the next pixel rows (C, h_b, W_b) of
+        whole images of different sizes - float32, or uint8 after ``set_patch_table``; h_b >= 0 or None, on the device or the
+        host -, ``feed_rows_all(images, band_rows)`` walks a ``RaggedImages`` or a list of images in bands, and ``finish()``
+        returns and leaves behind what ``ips_image_ragged([torch.cat(bands of image b, 1) for b], patch_size, patch_stride,
+        pad=pad)`` does with ``shuffle`` off, bit for bit, wherever the bands end.  Each image carries the fewer than ph rows
+        a patch row straddling two bands needs; where ``ips_image_ragged`` reads a ragged view no patch tensor is made."""
         from ..ragged_stream import RaggedIPSStream
-        return RaggedIPSStream(self, pad)
+        return RaggedIPSStream(self, pad, patch_size, patch_stride)
 
     def _chunks(self, N):
         """[0, M) then ceil((N-M)/I) chunks of I (last one ragged) - reference :206,217-221."""

@@ -442,6 +442,9 @@ _EXPORTS = {
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ipsx_stream_commit_ragged": (C.c_int, [C.POINTER(StreamTable), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64,
                                             C.c_int64, C.c_void_p]),
+    "ipsx_stream_commit_ragged_view": (C.c_int, [C.POINTER(StreamTable), C.c_int, C.c_void_p, C.POINTER(RaggedViewStruct), C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int64, C.POINTER(C.c_int),
+                                                 C.c_void_p]),
     "ipsx_aggregate_workspace_bytes": (C.c_size_t, [C.POINTER(Transf), C.c_int, C.c_int]),
     "ipsx_aggregate": (C.c_int, [C.POINTER(Transf), C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                  C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -967,15 +970,38 @@ def scan_ragged_spans(lg, spans, n_max, M, I, H, T, mem_idx, tie, mem_score=None
 COMMIT_IDLE, COMMIT_APPEND, COMMIT_SELECT, COMMIT_MOVE = 0, 1, 2, 3
 
 
-def stream_commit_ragged(tables, sel, slides, M, rows_max):
+def stream_commit_ragged(tables, sel, slides, M, rows_max, pixels=None, view=None):
     """The state update of a ragged stream, ONE launch (``ipsx_stream_commit_ragged``).  ``tables``: up to four ``(held, piece,
     dst)`` - ``held`` (B, cap, ...) or None, all of whose rows may be read; ``piece`` (rows, ...) ONE packed tensor for all
     slides, or None for a table that holds all candidates itself; ``dst`` (B, cap', ...) contiguous (``held`` itself: append in
     place).  ``slides`` (B, 6) int64 on the device, per slide: held rows, candidates, tail_first, first row in the packed
     piece, the mode (``COMMIT_IDLE / _APPEND / _SELECT / _MOVE``), 0.  ``sel`` (B, M) int64 candidate rows of the slides that
-    select, or None.  ``rows_max``: the most rows any slide writes (the grid)."""
+    select, or None.  ``rows_max``: the most rows any slide writes (the grid).
+
+    ``pixels`` and ``view`` (both, or neither): the stream is fed pixel-row bands (``ipsx_stream_commit_ragged_view``, DESIGN
+    2.10).  ``tables[0]`` is the patch table ``(held, None, dst)`` with rows (C, ph, pw) of the pixels' dtype: candidate
+    held + r of slide k is packed patch first_k + r of ``view`` (a ``RaggedView``) over ``pixels``, the packed 1-d float32 |
+    uint8 buffer of the feed's windows, copied where it lies - bytes as bytes.  A strided ``pixels`` is copied, another dtype or
+    rank refused.  -> the bytes per lane the patch table was copied with (16, 4 or 1); None without a view."""
+    what = "stream_commit_ragged"
+    if (pixels is None) != (view is None):
+        raise ValueError("{}: pixels and view go together".format(what))
     flat = [t for tab in tables for t in tab]
-    _on_gpu("stream_commit_ragged", sel, slides, *flat)
+    _on_gpu(what, sel, slides, pixels, *flat)
+    if view is not None:
+        if pixels.dtype not in (torch.float32, torch.uint8):
+            raise TypeError("{}: a ragged view reads float32 or uint8 pixels, got {}".format(what, pixels.dtype))
+        pixels = _rd(what, "pixels", pixels, dtype=pixels.dtype, dim=1, align=1)
+        if not tables or tables[0][1] is not None:
+            raise ValueError("{}: table 0 is the patch table: its piece is the view (pass None)".format(what))
+        dst0 = tables[0][2]
+        if dst0.dtype != pixels.dtype or tuple(dst0.shape[2:]) != view.patch_shape:
+            raise ValueError("{}: table 0: rows of {} {}, the view's patches are {} {}".format(
+                what, dst0.dtype, tuple(dst0.shape[2:]), pixels.dtype, view.patch_shape))
+        e = view.table[len(view.sizes) - 1]
+        if e.elem_off + view.patch_shape[0] * e.h * e.w > pixels.numel():
+            raise ValueError("{}: the view's images end at element {}, the pixels hold {}".format(
+                what, e.elem_off + view.patch_shape[0] * e.h * e.w, pixels.numel()))
     arr = (StreamTable * max(1, len(tables)))()
     B, piece_rows = None, 0
     for k, (held, piece, dst) in enumerate(tables[:len(arr)]):
@@ -1003,8 +1029,15 @@ def stream_commit_ragged(tables, sel, slides, M, rows_max):
         raise ValueError("slides must be a contiguous (B, 6) int64 tensor")
     if sel is not None and (sel.dtype != torch.int64 or tuple(sel.shape) != (B, M) or not sel.is_contiguous()):
         raise ValueError("sel must be a contiguous (B, M) int64 tensor")
-    _ck(lib().ipsx_stream_commit_ragged(arr, len(tables), _p(sel), _p(slides), B or 0, M, int(rows_max), piece_rows, _stream()),
-        "ipsx_stream_commit_ragged")
+    if view is None:
+        _ck(lib().ipsx_stream_commit_ragged(arr, len(tables), _p(sel), _p(slides), B or 0, M, int(rows_max), piece_rows, _stream()),
+            "ipsx_stream_commit_ragged")
+        return None
+    unit = C.c_int(0)
+    _ck(lib().ipsx_stream_commit_ragged_view(arr, len(tables), _p(pixels), C.byref(view.on(pixels.device).struct), pixels.element_size(),
+                                             _p(sel), _p(slides), B or 0, M, int(rows_max), piece_rows, C.byref(unit), _stream()),
+        "ipsx_stream_commit_ragged_view")
+    return unit.value
 
 
 def _stream_tables(tables, n_cand):
@@ -1685,9 +1718,14 @@ class RaggedView:
         self.count = int(total)
         self._device = {}                                             # device -> the uploaded table (kept alive here)
 
-    def on(self, device):
-        """This view with its table on ``device`` (uploaded on first use) -> self."""
+    def on(self, device, uploaded=None):
+        """This view with its table on ``device`` (uploaded on first use) -> self.  ``uploaded``: the caller's own upload of
+        ``bytes(self.table)`` to that device - a stream that makes a view per feed sends it with its other numbers."""
         device = torch.device(device)
+        if uploaded is not None:
+            if uploaded.device != device or uploaded.numel() * uploaded.element_size() < C.sizeof(ImageEntry) * len(self.sizes):
+                raise ValueError("the uploaded table lies on {} with {} bytes".format(uploaded.device, uploaded.numel() * uploaded.element_size()))
+            self._device[device] = uploaded
         dev = self._device.get(device)
         if dev is None:
             host = torch.frombuffer(bytearray(bytes(self.table)), dtype=torch.uint8)

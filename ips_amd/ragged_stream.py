@@ -25,23 +25,56 @@ slide completes a chunk is encoder, logits and one append launch for the four ta
 
 On a CPU device, and where an encoder alone is in training mode inside an eval-mode net (the fall-back conditions of
 ``ragged._host_route``), B solo ``IPSStream`` state machines run on ATen ops.
+
+A ragged ROW stream (``net.ips_ragged_stream(pad, patch_size, patch_stride)``) takes the pixel rows of whole
+images of different sizes instead:
+
+    s = net.ips_ragged_stream(patch_size=(32, 32), patch_stride=(16, 16))
+    for bands in reader:                        # a list of B entries: (C, h_b, W_b) with h_b >= 0, or None; sum h_b >= 1
+        s.feed_rows(bands)
+    mem_patch, mem_pos = s.finish()
+
+and returns and leaves behind what ``net.ips_image_ragged([torch.cat(bands of image b, 1) for b], patch_size, patch_stride,
+pad=pad)`` does, wherever the bands end.  Every image has its own ``BandGeometry`` and carried rows (fewer than ``ph``); a feed
+packs the carried rows and the bands into ONE window buffer, and where the encoder reads a ``hip.RaggedView`` the patches the
+windows complete are never unfolded: the stems read the window, and ``hip.stream_commit_ragged(..., pixels=, view=)`` copies
+the kept patches out of it.  Everywhere else the live patch rows are unfolded and take ``feed()``'s path, or (the ATen
+route) B solo row streams run.
 """
+
+import os
 
 import torch
 
 from . import hip
 from .ragged import Ragged, _host_emb
-from .stream import IPSStream
+from .ragged_image import RaggedImages, ragged_dedup
+from .stream import BandGeometry, IPSStream
 
 
 class RaggedIPSStream:
     """The state of one streamed ragged selection.  ``fed``: rows per slide so far; ``iterations``: completed iterations per
     slide; ``mem_idx``: (B, M) int64 row numbers inside each slide, in the order of its last completed iteration (a row of
-    -1 for a slide that has not reached M rows; None before the first feed)."""
+    -1 for a slide that has not reached M rows; None before the first feed).  A row stream (``patch_size`` / ``patch_stride``
+    given) takes ``feed_rows(bands)`` instead of ``feed``; ``rows``: pixel rows per image so far, ``fed``:
+    complete patch rows times ``nx_b``; ``view_feeds``: feeds whose piece was read through a ragged view (no patch tensor)."""
 
-    def __init__(self, net, pad=False):
+    def __init__(self, net, pad=False, patch_size=None, patch_stride=None):
         self.net = net
         self.pad = bool(pad)
+        self._patch_size = self._patch_stride = None
+        if patch_size is not None or patch_stride is not None:
+            if patch_size is None or patch_stride is None:
+                raise ValueError("a row stream needs both patch_size and patch_stride")
+            if not net.is_image:
+                raise TypeError("a row stream takes bands of whole images: it goes with an image encoder")
+            (ph, pw), (sh, sw) = (int(v) for v in patch_size), (int(v) for v in patch_stride)
+            if min(ph, pw, sh, sw) <= 0:
+                raise ValueError("patch {}x{} / stride {}x{}".format(ph, pw, sh, sw))
+            self._patch_size, self._patch_stride = (ph, pw), (sh, sw)
+            self._geoms = self._carry = self._widths = self._nx = None   # per image, made by the first feed
+            self._view_ok = False        # does the encoder read a ragged view of this patch shape (decided by the first feed)
+        self.view_feeds = 0
         self._finished = False
         self._generation = hip.weights_generation()
         self._B = self._row_shape = self._dtype = None
@@ -56,6 +89,13 @@ class RaggedIPSStream:
         self._stage, self._stage_at = [], 0      # pinned (3, B, 6) staging buffers of the per-feed table, used in turn
 
     # ------------------------------------------------------------------ observable state
+    @property
+    def rows(self):
+        """Pixel rows taken per image so far (a row stream; None before the first feed)."""
+        if self._patch_size is None or self._geoms is None:
+            return None
+        return tuple(g.rows for g in self._geoms)
+
     @property
     def fed(self):
         return tuple(self._fed)
@@ -77,6 +117,8 @@ class RaggedIPSStream:
                 if s.fed >= M:
                     out[b] = s.mem_idx[0]
             return out
+        if self._sets is None:               # (a row stream whose bands have completed no patch row yet)
+            return torch.full((self._B, M), -1, dtype=torch.int64, device=self.net.device)
         reached = torch.tensor([n >= M for n in self._fed]).to(self.net.device)
         return torch.where(reached.unsqueeze(1), self._sets[self._cur][2][:, :M], -1)
 
@@ -145,6 +187,8 @@ class RaggedIPSStream:
         """Take the next rows of every slide: a ``Ragged``, or a list of B tensors (n_b, ...) with n_b >= 0 and at least one
         row in all; on the device or on the host (a host piece is copied to the device as it is, and only the piece).
         Stream-ordered on the current stream, as ``IPSStream.feed``."""
+        if self._patch_size is not None:
+            raise TypeError("this is a row stream (ips_ragged_stream(patch_size=, patch_stride=)): it takes feed_rows(bands), not patches")
         self._check()
         lengths, shape, dtype = self._check_pieces(pieces)
         net = self.net
@@ -193,6 +237,176 @@ class RaggedIPSStream:
                 self.feed([slides[b][s:e] for b, (s, e) in enumerate(cut)])
         return self
 
+    # ------------------------------------------------------------------ feed_rows
+    def _check_bands(self, bands):
+        """Everything that refuses a feed of bands, before the first launch or allocation of the call and before the stream's
+        state changes -> (dtype, channels, widths, plans): ``plans[b]`` is ``BandGeometry.plan`` of image b's band, None for an
+        image without rows this time; ``widths[b]`` the image's width once a non-empty band has fixed it."""
+        net = self.net
+        (ph, pw), (sh, sw) = self._patch_size, self._patch_stride
+        layout = "a feed is a list of B entries: (C, h_b, W_b) bands - the next h_b >= 0 pixel rows of image b - or None"
+        if isinstance(bands, (Ragged, RaggedImages)):
+            raise TypeError("feed_rows takes a list of bands; a RaggedImages of whole images goes through feed_rows_all")
+        if not isinstance(bands, (list, tuple)) or not bands:
+            raise ValueError(layout)
+        if self._B is not None and len(bands) != self._B:
+            raise ValueError("a feed of {} entries in a stream of B = {} images".format(len(bands), self._B))
+        B = len(bands)
+        dtype, chans = self._dtype, (self._row_shape[0] if self._row_shape else None)
+        widths = list(self._widths) if self._widths else [None] * B
+        geoms = self._geoms or [BandGeometry(ph, sh)] * B             # (plan() reads, it takes nothing)
+        fed = self._fed or [0] * B
+        plans, any_row = [None] * B, False
+        for b, band in enumerate(bands):
+            if band is None:
+                continue
+            if not torch.is_tensor(band) or band.dim() != 3 or band.shape[0] < 1 or band.shape[2] < 1:
+                raise ValueError("entry {}: {}".format(b, layout))
+            Cc, h, W = band.shape
+            if dtype is None:                    # the stream's first band: what every later one must look like
+                if band.dtype == torch.uint8:
+                    table = net._table_for(band)
+                    if table.shape[0] != Cc:
+                        raise ValueError("the patch table has {} rows, the band {} channels".format(table.shape[0], Cc))
+                    if hip.on_device(net.device) and hip.precision() != "fp32":
+                        raise TypeError("uint8 bands go with the exact trunk (IPSX_PRECISION=fp32), not {}".format(hip.precision()))
+                elif band.dtype != torch.float32:
+                    raise TypeError("bands are float32, or uint8 after set_patch_table; got {}".format(band.dtype))
+                want = next(net.encoder.children()).in_channels
+                if Cc != want:
+                    raise ValueError("a band of {} channels, the encoder expects {}".format(Cc, want))
+                dtype, chans = band.dtype, Cc
+            elif band.dtype != dtype:
+                raise TypeError("entry {}: a {} band in a stream of {}".format(b, band.dtype, dtype))
+            elif Cc != chans:
+                raise ValueError("entry {}: a band of {} channels in a stream of {}".format(b, Cc, chans))
+            if widths[b] is not None and W != widths[b]:
+                raise ValueError("entry {}: a band {} pixels wide, image {} is {} wide".format(b, W, b, widths[b]))
+            if h == 0:
+                continue
+            if widths[b] is None:
+                if pw > W:
+                    raise ValueError("entry {}: patches of width {} do not fit rows of {} pixels".format(b, pw, W))
+                widths[b] = W
+            plans[b] = geoms[b].plan(h)
+            any_row = True
+            n = fed[b] + plans[b][2] * ((W - pw) // sw + 1)
+            if net.use_pos and n > net.pos_enc.shape[1]:
+                raise ValueError("image {} would have {} patches, the positional table conf.N = {}".format(b, n, net.pos_enc.shape[1]))
+        if not any_row:
+            raise ValueError("a feed carries at least one pixel row (every entry is None or has no rows)")
+        return dtype, chans, widths, plans
+
+    @torch.no_grad()
+    def feed_rows(self, bands):
+        """Take the next pixel rows of every image: a list of B entries, ``(C, h_b, W_b)`` float32 - or uint8 after
+        ``set_patch_table`` - with h_b >= 0, or None for an image that has ended or has nothing this time; at least one pixel
+        row in all; each band on the device or on the host.  Image b's width is that of its first non-empty band.  The patch
+        rows a feed completes are its piece (none: nothing is launched).  Stream-ordered like ``feed``: when the call returns,
+        the caller may overwrite or free the bands."""
+        if self._patch_size is None:
+            raise TypeError("this is a patch stream: feed_rows() goes with ips_ragged_stream(patch_size=, patch_stride=)")
+        if isinstance(bands, (Ragged, RaggedImages)):
+            raise TypeError("feed_rows takes a list of bands; a RaggedImages of whole images goes through feed_rows_all")
+        self._check()
+        dtype, chans, widths, plans = self._check_bands(bands)
+        net = self.net
+        (ph, pw), (sh, sw) = self._patch_size, self._patch_stride
+        if self._B is None:
+            B = self._B = len(bands)
+            self._row_shape, self._dtype = (chans, ph, pw), dtype
+            self._fed, self._iters, self._held = [0] * B, [0] * B, [0] * B
+            self._geoms, self._carry = [BandGeometry(ph, sh) for _ in range(B)], [None] * B
+            self._device_route = self._routes_to_device()
+            if self._device_route:
+                # (asked of the smallest view of this patch shape: the answer depends on the trunk and the patch alone)
+                self._view_ok = bool(net.plan.ragged_view_supported(hip.RaggedView(chans, [(ph, pw)], [0], (ph, pw), (sh, sw))))
+            else:
+                self._solo = [IPSStream(net, self._patch_size, self._patch_stride) for _ in range(B)]
+                for s in self._solo:
+                    s._on_device = False         # (the ATen state machine, also for device tensors)
+        self._widths = widths
+        self._nx = [0 if W is None else (W - pw) // sw + 1 for W in widths]
+        if self._device_route:
+            self._feed_rows_hip(bands, plans)
+        else:
+            for b, plan in enumerate(plans):
+                if plan is not None:
+                    self._solo[b].feed_rows(bands[b].unsqueeze(0))
+                    self._iters[b] = self._solo[b].iterations
+        for b, plan in enumerate(plans):
+            if plan is not None:
+                self._geoms[b].take(bands[b].shape[1])
+                self._fed[b] += plan[2] * self._nx[b]
+        return self
+
+    def feed_rows_all(self, images, band_rows):
+        """Walk ``images`` (a ``RaggedImages`` or a list of (C, H_b, W_b) tensors) in bands of at most ``band_rows`` pixel rows
+        per image and feed each; an image that has run out drops out of the later feeds.  The lazy route for a host batch,
+        ``net.ips_ragged_stream(patch_size=..., patch_stride=...).feed_rows_all(batch, 256).finish()``."""
+        band_rows = int(band_rows)
+        if band_rows < 1:
+            raise ValueError("bands of {} rows".format(band_rows))
+        images = list(images)
+        if not images or any(not torch.is_tensor(im) or im.dim() != 3 for im in images):
+            raise ValueError("feed_rows_all takes a RaggedImages or a list of (C, H_b, W_b) images")
+        tallest = max(im.shape[1] for im in images)
+        if tallest == 0:
+            self.feed_rows(images)               # (refused there)
+        for lo in range(0, tallest, band_rows):
+            self.feed_rows([im[:, lo:lo + band_rows] if lo < im.shape[1] else None for im in images])
+        return self
+
+    def _feed_rows_hip(self, bands, plans):
+        """One feed of bands on the device: ONE packed window buffer - per image with rows the carried rows, then the band's,
+        as (C, rows_b, W_b) at a 16-byte offset: the only pixel copy of the feed, a host band lands in it -, the selection on
+        the patch rows the windows complete (``_feed_hip``: through a ragged view over the LIVE images where the encoder
+        reads one, as patch tensors elsewhere), then each image's rows behind its last complete patch row kept as a copy."""
+        net = self.net
+        (ph, pw), (sh, sw) = self._patch_size, self._patch_stride
+        B, dev, Cc = self._B, net.device, self._row_shape[0]
+        unit = max(16 // torch.empty((), dtype=self._dtype).element_size(), 1)
+        have = [b for b in range(B) if plans[b] is not None and plans[b][1] > 0]
+        if not have:                             # every row of the feed lies between two patch rows
+            return
+        offs, end = {}, 0
+        for b in have:
+            offs[b] = (end + unit - 1) // unit * unit
+            end = offs[b] + Cc * plans[b][1] * self._widths[b]
+        window = torch.empty((end,), dtype=self._dtype, device=dev)
+        wins = {}
+        for b in have:
+            drop, rows = plans[b][:2]
+            band, W = bands[b], self._widths[b]
+            carry = rows - (band.shape[1] - drop)
+            win = wins[b] = window[offs[b]:offs[b] + Cc * rows * W].view(Cc, rows, W)
+            if carry:
+                win[:, :carry].copy_(self._carry[b])
+            if band.shape[1] > drop:
+                src, dst = band[:, drop:], win[:, carry:]
+                if src.device == window.device or (src.is_contiguous() and dst.is_contiguous()):
+                    dst.copy_(src)
+                else:                            # host rows into a strided window: plane by plane, each transfer contiguous at both ends
+                    for c in range(Cc):
+                        dst[c].copy_(src[c])
+        live = [b for b in have if plans[b][2] > 0]
+        if live:
+            lengths = [plans[b][2] * self._nx[b] if plans[b] is not None and plans[b][1] > 0 else 0 for b in range(B)]
+            with net._scoring():
+                if self._view_ok:
+                    view = hip.RaggedView(Cc, [(plans[b][1], self._widths[b]) for b in live], [offs[b] for b in live],
+                                          self._patch_size, self._patch_stride)
+                    self._feed_hip(None, lengths, window, view)
+                    self.view_feeds += 1
+                else:                            # the pieces as patch tensors, through feed()'s path
+                    empty = torch.empty((0,) + self._row_shape, dtype=self._dtype, device=dev)
+                    pieces = [net._materialise(wins[b][None, :, :(plans[b][2] - 1) * sh + ph], self._patch_size, self._patch_stride)[0]
+                              if lengths[b] else empty for b in range(B)]
+                    self._feed_hip(pieces, lengths)
+        for b in have:                           # (copies: the window itself is released)
+            rows, keep = plans[b][1], plans[b][3]
+            self._carry[b] = wins[b][:, rows - keep:].clone() if keep else None
+
     # ------------------------------------------------------------------ the ROCm device
     def _allocate(self, dev):
         net = self.net
@@ -208,24 +422,30 @@ class RaggedIPSStream:
         nb = hip.lib().ipsx_scan_workspace_bytes(1, net.M, net.I, ca.H, ca.n_token)
         self._scan_ws = torch.empty(B * nb, dtype=torch.uint8, device=dev) if nb else None
 
-    def _numbers(self, planes, dev):
+    def _numbers(self, planes, dev, view=None):
         """Up to three (B, 6) planes of host ints -> ONE (3, B, 6) int64 tensor on the device, ONE copy.  The copy leaves from
         pinned memory and does not wait for the device: a few staging buffers are used in turn, each with the event behind
-        its last copy."""
+        its last copy.  ``view``: a feed's ``hip.RaggedView`` - its entry table (at most B entries of four words) rides behind
+        the planes in the same copy and the view is told where it lies."""
         B = self._B
         planes = planes + [[[0] * 6] * B] * (3 - len(planes))
         host = torch.tensor(planes, dtype=torch.int64)
         if not self._stage:
-            self._stage = [[torch.empty((3, B, 6), dtype=torch.int64).pin_memory(), None] for _ in range(4)]
+            self._stage = [[torch.empty((22 * B,), dtype=torch.int64).pin_memory(), None] for _ in range(4)]
         slot = self._stage[self._stage_at % len(self._stage)]
         self._stage_at += 1
         if slot[1] is not None:
             slot[1].synchronize()
-        slot[0].copy_(host)
+        slot[0][:18 * B].copy_(host.view(-1))
+        if view is not None:
+            entries = torch.frombuffer(bytearray(bytes(view.table)), dtype=torch.int64)
+            slot[0][18 * B:18 * B + entries.numel()].copy_(entries)
         out = slot[0].to(dev, non_blocking=True)
         slot[1] = torch.cuda.Event()
         slot[1].record()
-        return out
+        if view is not None:
+            view.on(out.device, out[18 * B:])
+        return out[:18 * B].view(3, B, 6)
 
     def _logits_room(self, rows, dev):
         """The logits tables hold a slide's held rows AND its piece's: they grow with the largest number of candidates."""
@@ -262,7 +482,10 @@ class RaggedIPSStream:
                               self._sel, self._tie, workspace=self._scan_ws)
         hip.scan.last_tie = self._tie
 
-    def _feed_hip(self, pieces, lengths):
+    def _feed_hip(self, pieces, lengths, window=None, view=None):
+        """One feed on the device.  ``view``: the feed's patches are those of a ``hip.RaggedView`` over ``window``, the packed
+        pixel windows of a row stream's live images - encoded and committed where they lie, no patch tensor; slide b's first
+        packed patch is ``starts[b]``, in the view as in the packed embeddings, ids and logits."""
         net = self.net
         M, I, B, dev = net.M, net.I, self._B, net.device
         held, fed = self._held, self._fed
@@ -282,11 +505,16 @@ class RaggedIPSStream:
         commit = [[held[b], total[b], M + k[b] * I if k[b] else 0, starts[b], S if k[b] else (V if total[b] else E), 0] for b in range(B)]
         counts = [M + k[b] * I if k[b] else 0 for b in range(B)]
         spans = [[b * lcap, counts[b], lengths[b], fed[b] - starts[b], 0, 0] for b in range(B)]
-        table = self._numbers([append, commit, spans], dev)
+        table = self._numbers([append, commit, spans], dev, view)
         self._spans = table[2, :, :2].contiguous()
 
-        packed = self._pack(pieces, lengths, dev)
-        emb = net._embed(packed)                                          # ONE encoder pass over the packed rows
+        if view is None:
+            packed, piece = self._pack(pieces, lengths, dev), {}
+            emb = net._embed(packed)                                      # ONE encoder pass over the packed rows
+        else:                                                             # ... over the packed patches of the view
+            packed, piece = None, dict(pixels=window, view=view)
+            src = hip.PatchSource(images=window, ragged=view, table=net._table_for(window))
+            emb = net.plan.encode_source(src, dedup=ragged_dedup(os.environ, net.plan, view))
         n_tot = starts[-1]
         # the row number inside its slide of every packed row: fed_b + r (ids, and the rows of the positional table)
         ids = torch.arange(n_tot, dtype=torch.int64, device=dev) + torch.repeat_interleave(table[2, :, 3], table[2, :, 2], output_size=n_tot)
@@ -295,14 +523,14 @@ class RaggedIPSStream:
         cur, dst = self._sets[self._cur], self._sets[self._cur ^ 1]
         if not any_select:                   # no slide completes a chunk: everything goes behind the held rows, in place
             hip.stream_commit_ragged([(cur[0], packed, cur[0]), (cur[1], emb, cur[1]), (cur[2], ids, cur[2]), (cur[3], lg_piece, cur[3])],
-                                     None, table[0], M, max(lengths))
+                                     None, table[0], M, max(lengths), **piece)
             self._held = total
             return
         hip.stream_commit_ragged([(cur[3], lg_piece, cur[3])], None, table[0], M, max(lengths))
         self._scan(counts, lcap)
         rows_max = max(total[b] - k[b] * I for b in range(B))
         hip.stream_commit_ragged([(cur[0], packed, dst[0]), (cur[1], emb, dst[1]), (cur[2], ids, dst[2]), (cur[3], None, dst[3])],
-                                 self._sel, table[1], M, rows_max)
+                                 self._sel, table[1], M, rows_max, **piece)
         self._cur ^= 1
         self._held = [total[b] - k[b] * I for b in range(B)]
         for b in range(B):
@@ -341,6 +569,11 @@ class RaggedIPSStream:
         if self._B is None:
             raise RuntimeError("nothing was fed")
         M, B = net.M, self._B
+        if self._patch_size is not None:
+            for b, g in enumerate(self._geoms):
+                if g.patch_rows == 0:        # (ips_image_ragged refuses a patch that does not fit its image)
+                    raise ValueError("image {}: the {} pixel rows fed complete no patch row of height {}".format(
+                        b, g.rows, self._patch_size[0]))
         for b, n in enumerate(self._fed):
             if self.pad and n == 0:
                 raise ValueError("slide {} has no rows: nothing to pad".format(b))
@@ -356,6 +589,8 @@ class RaggedIPSStream:
         self._finished, self._last_idx = True, net.last_mem_idx
         self._sets = self._sel = self._scan_ws = self._solo = None
         self._stage = []
+        if self._patch_size is not None:
+            self._carry = None
         return mem_patch, mem_pos
 
     def _finish_hip(self):
@@ -365,6 +600,9 @@ class RaggedIPSStream:
             self._last_chunks()
             patch, emb, ids, _ = self._sets[self._cur]
             mem_patch, mem_emb, mem_idx = patch[:, :M].clone(), emb[:, :M].clone(), ids[:, :M].clone()
+            u8 = self._dtype == torch.uint8
+            if u8:                           # a row stream's byte patch table: the M slots leave as float32, the padding as +0.0
+                mem_patch = net._dequant(mem_patch)
             padded = any(n < M for n in self._fed)
             if padded:                       # rows, then +0.0; 0 .. N_b-1, then -1
                 n = torch.tensor(self._fed, dtype=torch.int64).to(dev).unsqueeze(1)
@@ -380,7 +618,7 @@ class RaggedIPSStream:
         if not padded:
             net._mem_emb = mem_emb
             return mem_patch, mem_pos
-        zero_row = (1,) + self._row_shape, self._dtype
+        zero_row = (1,) + self._row_shape, torch.float32 if u8 else self._dtype
 
         def emb_of_slots():
             """The padding holds the embedding of ONE all-zero row (made on first read, as ``ips_ragged`` makes it)."""
@@ -395,7 +633,8 @@ class RaggedIPSStream:
         order given and the zero padding behind them."""
         net = self.net
         M, B, D, device = net.M, self._B, net.D, net.device
-        mem_patch = torch.zeros((B, M) + self._row_shape, dtype=self._dtype, device=device)
+        u8 = self._dtype == torch.uint8      # (a row stream's bytes: the solo streams return them dequantised)
+        mem_patch = torch.zeros((B, M) + self._row_shape, dtype=torch.float32 if u8 else self._dtype, device=device)
         mem_pos = torch.zeros((B, M, D), dtype=net.pos_enc.dtype, device=device) if net.use_pos else None
         mem_idx = torch.full((B, M), -1, dtype=torch.int64, device=device)
         long_emb, short_rows = {}, {}
