@@ -131,7 +131,10 @@ extern "C" {
  *         entries with the bytes' staging of ipsx_trunk_encode_view_u8 (additions, the minor number stays);
  *         ipsx_stream_commit_ragged_view - row bands of whole images of different sizes (IPSNet.ips_ragged_stream with a
  *         patch size): ipsx_stream_commit_ragged whose patch table reads its piece out of the packed pixel windows of a feed
- *         through an ipsx_ragged_view, no patch tensor exists (an addition, the minor number stays) */
+ *         through an ipsx_ragged_view, no patch tensor exists (an addition, the minor number stays);
+ *         ipsx_scan_range_logits, ipsx_scan_logits_check (+ struct ipsx_logits_part) - a range of the selection loop whose
+ *         launch computes its own logits in a prologue (8 heads x 4 tokens, m = i = 64), and the conditional redo of a counted
+ *         call inside its last part's launch (additions, the minor number stays) */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -762,6 +765,30 @@ int ipsx_set_persistent_wait_ms(int ms);
 int ipsx_scan_range_if(const float* logits, int b, int64_t n, int m, int i, int h, int n_token,
                        int64_t it_begin, int64_t it_end, int64_t* mem_idx, float* mem_score,
                        int32_t* tie_flag, const int32_t* cond, int32_t cond_mask, void* stream);
+/* A range of the loop whose launch computes its own logits: ipsx_logits of the parts [part_begin, part_end) and ipsx_scan_range
+ * of the iterations [it_begin, it_end) in ONE launch, bit for bit.  Workgroup k of the loop reads image k's logits alone, and
+ * a patch's logits depend on that patch alone, so in front of its first iteration it writes image k's rows of those parts
+ * into `logits` (b, n, r) itself - no logits launch, no dependency between workgroups.  The embeddings of a call lie
+ * part-major: parts[j] = {emb: (b, rows, d) float32 at a 16-byte address, rows per image, first row of the part in an
+ * image}, n_parts <= 16, in order and tiling [0, n); pos (b | 1, n, d) of whole images or NULL, pos_bstride 0 broadcasts.
+ * The rows the iterations read end inside part part_end - 1 at the latest; those in front of part_begin are in `logits`
+ * (part_begin == part_end: all of them - the launch computes no rows unless it redoes the call).
+ * redo (device int32, or NULL with mask 0): with (*redo & redo_mask) != 0 - a part wait of the call gave up (ipsx_part_wait)
+ * - the launch computes ALL parts and runs the iterations [0, it_end): the conditional redo of ipsx_logits_if /
+ * ipsx_scan_range_if, in the launch of the call's last part.
+ * Shape: 8 heads x 4 tokens, m = i = 64 (r = 32), d % 8 == 0; anything else: IPSX_EINVAL, nothing launched.
+ * ipsx_scan_logits_check: the arithmetic of the part table and the two ranges alone, on the host (no device needed). */
+typedef struct ipsx_logits_part {
+    const float* emb;
+    int64_t rows;
+    int64_t first;
+} ipsx_logits_part;
+int ipsx_scan_logits_check(const ipsx_logits_part* parts, int n_parts, int part_begin, int part_end, int64_t n, int m, int i,
+                           int64_t it_begin, int64_t it_end);
+int ipsx_scan_range_logits(float* logits, int b, int64_t n, int m, int i, int h, int n_token, int64_t it_begin, int64_t it_end,
+                           int64_t* mem_idx, float* mem_score, int32_t* tie_flag, const ipsx_logits_part* parts, int n_parts,
+                           int part_begin, int part_end, int d, const float* pos, int64_t pos_bstride, const float* v_packed,
+                           const int32_t* redo, int32_t redo_mask, void* stream);
 /* ipsx_logits for rows [0, n) and, in the SAME launch, the LayerNorm row moments (ipsx_projector_stats) of stats_n rows
  * of stats_x - the next slab the projector is about to take: two short latency-bound launches of a slab-by-slab producer
  * of ipsx_scan_persistent as one. */

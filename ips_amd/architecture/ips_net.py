@@ -387,7 +387,11 @@ class IPSNet(nn.Module):
 
             if hip.on_device(device):
                 with self.plan.hold():            # weights cannot change inside a no-grad call: check them once
-                    mem_idx = self._select_hip(patches, pos_enc, order)
+                    self.selection.caller_finishes = True       # (this call ends in finish / take_unfinished + after_call below)
+                    try:
+                        mem_idx = self._select_hip(patches, pos_enc, order)
+                    finally:
+                        self.selection.caller_finishes = False
             else:
                 mem_idx = self._select_aten(patches, pos_enc)
 

@@ -1132,6 +1132,20 @@ struct ScanCall {
     int64_t table_rows = 0;                // Strided: rows between two images' logits; Offsets / Spans: rows of the one table
 };
 
+// What scan_mnist_kernel's logits prologue reads (its second kernel parameter).  The embeddings of a call are part-major -
+// part k is one (b, rows, d) block for the rows first .. first + rows of every image -, so the table of the parts travels
+// in the kernel arguments: no pointer the prologue would have to chase.
+constexpr int SCAN_LOGITS_PARTS = 16;
+struct LogitsPart { const float* emb; int rows, first; };
+struct ScanLogits {
+    LogitsPart part[SCAN_LOGITS_PARTS];
+    const float* pos; long long pos_bs;    // (b | 1, n, d) positional table of WHOLE images (pos_bs 0: one for all), or nullptr
+    const float* vp;                       // the packed folded query (ipsx_fold_query)
+    float* out;                            // the (b, n, R) logits the loop reads
+    const int* redo; int redo_mask;        // (*redo & redo_mask) != 0: all parts, the loop from iteration 0; or nullptr
+    int d, kgs, n_parts, part0, part1;     // the parts of this launch: [part0, part1)
+};
+
 // the slide table as the kernels read it: the C ABI's int64_t is the kernels' `long long` (as mem_idx is) - the same 64 bits
 // under two names, converted here and nowhere else
 inline const long long* slide_entries(const ScanCall& c) {
@@ -1151,6 +1165,7 @@ bool scan_cam_shape(int m, int i, int h, int n_token);                     // sc
 int launch_scan_cam(const ScanCall& c);                                    // scan_cam.hip
 bool scan_mnist_shape(int m, int i, int h, int n_token);                   // scan_mnist.hip: BASELINE configs[1] / [2]'s shape
 int launch_scan_mnist(const ScanCall& c);                                  // scan_mnist.hip
+int launch_scan_mnist_logits(const ScanCall& c, const ScanLogits& p);      // scan_mnist.hip: the same with the logits prologue
 size_t scan_large_ws_per_image(int m, int i, int h, int n_token);          // scan_large.hip
 int launch_scan_large(const ScanCall& c);                                  // scan_large.hip
 int scan_large_team(int b, int m, int i, int h, int n_token);              // scan_large.hip: workgroups per image (1: no team)
@@ -1167,6 +1182,7 @@ extern bool g_scan_team_trunc;         // diagnostic (ipsx_dbg_scan_team_trunc):
 extern int g_scan_team;                // diagnostic (ipsx_dbg_scan_team): -1 the default, 0 one workgroup per image, 2 / 4 / 8
 extern bool g_scan_r8;                 // diagnostic (ipsx_dbg_scan_r8): 0 sends scan_cam_kernel's shape through scan_fast_kernel
 extern bool g_scan_mnist;              // diagnostic (ipsx_dbg_scan_mnist): 0 sends scan_mnist_kernel's shape through scan_fast_kernel
+extern bool g_scan_logits;             // diagnostic (ipsx_dbg_scan_logits): 0 = ipsx_scan_range_logits enqueues logits launches and loop launches
 extern unsigned long long* g_scan_stamps;      // diagnostic (ipsx_dbg_scan_stamps)
 unsigned long long* persist_log();     // device address of the resident loops' / the gate's log (scorer.hip: g_persist_log)
 

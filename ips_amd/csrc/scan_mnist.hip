@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "logits_wave.h"
 #include "scan_common.h"
 
 namespace ipsx {
@@ -59,11 +60,46 @@ __device__ __forceinline__ float quad_bcast(float v) {
     return as_float((uint32_t)__builtin_amdgcn_update_dpp(0, (int)as_u32(v), K * 0x55, 0xF, 0xF, false));
 }
 
-template <bool PERSIST>
-__global__ __launch_bounds__(mn::NT) void scan_mnist_kernel(ScanArgs a) {
+// PRO: the launch computes its image's logits itself, in a prologue in front of the first iteration of its range.  A patch's
+// logits depend on that patch alone, and workgroup b reads image b's logits alone - so workgroup b writes the rows of image b
+// that its range adds (the parts [part0, part1) of the call, ScanLogits) into the (b, n, R) table logits_kernel<1> fills
+// otherwise, with logits_wave's arithmetic (the 32-row tiles of a part dealt to the 16 wavefronts; four k-groups of loads in
+// flight instead of eight: 128 registers), and a barrier with a workgroup-scope release / acquire around it hands them to
+// the loop: no logits launch in front of the loop's, no dependency between workgroups, no wait.  With the word `redo` set
+// (a part wait of the call gave up: rows may have been computed from embeddings that were not there yet) it computes ALL
+// parts and runs the loop from iteration 0 - what three conditional logits launches and a conditional loop launch did.
+// The arguments of the prologue are a second kernel parameter that only a PRO instantiation has (P...): the others keep
+// their one-parameter shape and their code (tools/asm_compare.py; PRO in front keeps the order of their mangled names).
+template <bool PRO, bool PERSIST, typename... P>
+__global__ __launch_bounds__(mn::NT) void scan_mnist_kernel(ScanArgs a, P... p) {
     using namespace mn;
+    static_assert(sizeof...(P) == (PRO ? 1 : 0) && !(PRO && PERSIST), "scan_mnist_kernel: the prologue's arguments, plain launches only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (!PERSIST && scan_skipped(a.cond, a.cond_mask)) return;
+    if constexpr (PRO) {
+        const ScanLogits& q = (p, ...);
+        int k0 = q.part0, k1 = q.part1;
+        // (the word is the same for every lane: through readfirstlane, so that it0 and everything the iterations derive from it
+        //  stay in scalar registers as in the other instantiations)
+        int redo = 0;
+        if (q.redo != nullptr)
+            redo = __builtin_amdgcn_readfirstlane(__hip_atomic_load(q.redo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & q.redo_mask);
+        if (redo != 0) { k0 = 0; k1 = q.n_parts; a.it0 = 0; }
+#pragma unroll 1
+        for (int k = k0; k < k1; ++k) {
+            LogitsArgs la;                                        // part k: (b, rows, d) embeddings of the rows first .. first + rows
+            la.emb = q.part[k].emb; la.emb_bs = (long long)q.part[k].rows * q.d;
+            la.pos = q.pos ? q.pos + (size_t)q.part[k].first * q.d : nullptr; la.pos_bs = q.pos_bs;
+            la.vp = q.vp; la.n = q.part[k].rows; la.d = q.d; la.R = R; la.kgs = q.kgs;
+            la.out = q.out + (size_t)q.part[k].first * R; la.out_bs = a.n * R;
+            if (q.pos) {                                          // (workgroup-uniform, known in front of the loads)
+                for (unsigned bx = 0; (long long)bx * (NT / 2) < la.n; ++bx) logits_wave<1, 4, NT / 64, 1>(la, bx, (int)blockIdx.x);
+            } else {
+                for (unsigned bx = 0; (long long)bx * (NT / 2) < la.n; ++bx) logits_wave<1, 4, NT / 64, -1>(la, bx, (int)blockIdx.x);
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // every row is written before the barrier below ...
+    }
     __builtin_amdgcn_s_setprio(3);
     if (PERSIST) {
         asm volatile("v_mov_b32 v127, 0" ::: "v127");               // (the whole register file of the compute unit: see scan_fast_kernel)
@@ -87,6 +123,7 @@ __global__ __launch_bounds__(mn::NT) void scan_mnist_kernel(ScanArgs a) {
     if (tid < 4 * R) pmax[tid] = 0u;
     if (tid < 2) ccount[2 + tid] = 0;
     lds_barrier();
+    if constexpr (PRO) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");      // ... and read behind it
     SCAN_WAIT_ROWS(std::min<long long>(a.n, a.it0 * (long long)I + M + I));
     {
         float* const x0 = reinterpret_cast<float*>(smem + OFF_X);
@@ -340,8 +377,20 @@ int launch_scan_mnist(const ScanCall& c) {
     ScanArgs a;
     fill_scan_args(a, c);
     a.stk_off = mn::OFF_STK;
-    launch_lds(c.ready ? scan_mnist_kernel<true> : scan_mnist_kernel<false>, dim3((unsigned)c.b), dim3(mn::NT), mn::LDS_BYTES, c.stream, a);
+    launch_lds(c.ready ? scan_mnist_kernel<false, true> : scan_mnist_kernel<false, false>, dim3((unsigned)c.b), dim3(mn::NT), mn::LDS_BYTES,
+               c.stream, a);
     return launched("scan");
+}
+
+// the loop's range with the logits prologue (scorer.hip has checked the part table: ipsx_scan_logits_check)
+int launch_scan_mnist_logits(const ScanCall& c, const ScanLogits& p) {
+    IPSX_REQUIRE(scan_mnist_shape(c.m, c.i, c.h, c.n_token) && c.rows == Rows::Packed && !c.ready && !c.cond && c.workgroups <= 0,
+                 "scan_mnist_kernel with logits: 8 heads x 4 tokens, M = I = 64, packed logits, a plain launch of one workgroup per image");
+    ScanArgs a;
+    fill_scan_args(a, c);
+    a.stk_off = mn::OFF_STK;
+    launch_lds(scan_mnist_kernel<true, false, ScanLogits>, dim3((unsigned)c.b), dim3(mn::NT), mn::LDS_BYTES, c.stream, a, p);
+    return launched("scan_logits");
 }
 
 }  // namespace ipsx

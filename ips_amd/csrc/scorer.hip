@@ -37,6 +37,7 @@ int g_scan_team = -1;               // diagnostic (ipsx_dbg_scan_team): workgrou
 bool g_scan_direct = true;          // diagnostic (ipsx_dbg_scan_direct): 0 = scan_large_kernel's five generic passes for every shape
 bool g_scan_r8 = true;              // diagnostic (ipsx_dbg_scan_r8): 0 sends the shape of scan_cam_kernel through scan_fast_kernel
 bool g_scan_mnist = true;           // diagnostic (ipsx_dbg_scan_mnist): 0 sends the shape of scan_mnist_kernel through scan_fast_kernel
+bool g_scan_logits = true;          // diagnostic (ipsx_dbg_scan_logits): 0 = ipsx_scan_range_logits enqueues logits launches and loop launches
 unsigned long long* g_scan_stamps = nullptr;   // diagnostic only (ipsx_dbg_scan_stamps)
 
 // Diagnostic (ipsx_dbg_persist_log; tools/soak.py): what the gate and the resident loops saw, on the 100 MHz clock -
@@ -339,6 +340,74 @@ IPSX_API int ipsx_scan_range_if(const float* logits, int b, int64_t n, int m, in
     return dispatch_scan(c);
 }
 
+// ---- ipsx_scan_range_logits: a range of the loop whose launch computes its own logits (scan_mnist_kernel's prologue)
+// The part table's arithmetic, on the host, before anything is launched: parts [0, n_parts) tile the rows [0, n) of an image in
+// order (first[k] = rows[0] + ... + rows[k - 1]), the launch's parts [part_begin, part_end) are among them - none of them
+// (part_begin == part_end) when the rows are an earlier launch's and the launch is there for its redo -, and the rows its
+// iterations [it_begin, it_end) read - up to min(n, m + it_end * i) - end where part part_end - 1 ends at the latest (the
+// rows in front of part_begin are an earlier launch's).
+IPSX_API int ipsx_scan_logits_check(const ipsx_logits_part* parts, int n_parts, int part_begin, int part_end, int64_t n, int m,
+                                    int i, int64_t it_begin, int64_t it_end) {
+    IPSX_REQUIRE(parts && n_parts >= 1 && n_parts <= SCAN_LOGITS_PARTS, "scan_range_logits: 1 to %d parts (got %d)", SCAN_LOGITS_PARTS, n_parts);
+    IPSX_REQUIRE(part_begin >= 0 && part_begin <= part_end && part_end <= n_parts, "scan_range_logits: parts [%d, %d) of %d", part_begin,
+                 part_end, n_parts);
+    IPSX_REQUIRE(m > 0 && i > 0 && n > m && n < ((int64_t)1 << 31), "scan_range_logits: more patches (%lld, fewer than 2^31) than memory slots (%d)",
+                 (long long)n, m);
+    int64_t at = 0;
+    for (int k = 0; k < n_parts; ++k) {
+        IPSX_REQUIRE(parts[k].rows > 0 && parts[k].rows <= n, "scan_range_logits: part %d has %lld rows per image", k, (long long)parts[k].rows);
+        IPSX_REQUIRE(parts[k].first == at, "scan_range_logits: part %d starts at row %lld, the parts in front of it end at %lld", k,
+                     (long long)parts[k].first, (long long)at);
+        at += parts[k].rows;
+    }
+    IPSX_REQUIRE(at == n, "scan_range_logits: the parts hold %lld rows per image, an image has %lld", (long long)at, (long long)n);
+    IPSX_REQUIRE(it_begin >= 0 && it_begin < it_end && it_end <= (n - m + i - 1) / i, "scan_range_logits: iteration range [%lld, %lld) outside the loop",
+                 (long long)it_begin, (long long)it_end);
+    const int64_t read_end = std::min<int64_t>(n, (int64_t)m + it_end * i);
+    const int64_t have_end = part_end > 0 ? parts[part_end - 1].first + parts[part_end - 1].rows : 0;
+    IPSX_REQUIRE(read_end <= have_end, "scan_range_logits: iterations up to %lld read rows up to %lld, the parts in front of part %d end at %lld",
+                 (long long)it_end, (long long)read_end, part_end, (long long)have_end);
+    return IPSX_OK;
+}
+
+IPSX_API int ipsx_scan_range_logits(float* logits, int b, int64_t n, int m, int i, int h, int n_token, int64_t it_begin, int64_t it_end,
+                                    int64_t* mem_idx, float* mem_score, int32_t* tie_flag, const ipsx_logits_part* parts, int n_parts,
+                                    int part_begin, int part_end, int d, const float* pos, int64_t pos_bstride, const float* v_packed,
+                                    const int32_t* redo, int32_t redo_mask, void* stream) {
+    IPSX_REQUIRE(logits && mem_idx && v_packed && b > 0, "scan_range_logits: null pointer");
+    IPSX_REQUIRE(scan_mnist_shape(m, i, h, n_token), "scan_range_logits: 8 heads x 4 tokens, M = I = 64 (scan_mnist_kernel) only");
+    IPSX_REQUIRE(d > 0 && d % 8 == 0, "scan_range_logits: embeddings of whole 8-float groups (d = %d)", d);
+    IPSX_REQUIRE(!redo == !redo_mask, "scan_range_logits: the redo word and its mask go together");
+    IPSX_TRY(ipsx_scan_logits_check(parts, n_parts, part_begin, part_end, n, m, i, it_begin, it_end));
+    for (int k = 0; k < n_parts; ++k)
+        IPSX_REQUIRE(parts[k].emb && (reinterpret_cast<uintptr_t>(parts[k].emb) & 15) == 0, "scan_range_logits: part %d's embeddings at a 16-byte address", k);
+    IPSX_REQUIRE((reinterpret_cast<uintptr_t>(v_packed) & 15) == 0 && (reinterpret_cast<uintptr_t>(pos) & 15) == 0 && pos_bstride >= 0 &&
+                 pos_bstride % 4 == 0, "scan_range_logits: the folded query and the positional table at 16-byte addresses");
+    const int r = h * n_token;
+    if (!g_scan_logits) {
+        // the launches this entry point replaces, one by one (tests, A/B): the parts' logits and the range; with a redo word,
+        // the conditional logits of the other parts and the conditional loop from iteration 0 behind them
+        for (int k = part_begin; k < part_end; ++k)
+            IPSX_TRY(ipsx_logits(parts[k].emb, parts[k].rows * d, pos ? pos + parts[k].first * d : nullptr, pos_bstride, v_packed, b, parts[k].rows, d, r,
+                                 logits + parts[k].first * r, n * r, stream));
+        IPSX_TRY(ipsx_scan_range(logits, b, n, m, i, h, n_token, it_begin, it_end, mem_idx, mem_score, tie_flag, nullptr, 0, stream));
+        if (!redo) return IPSX_OK;
+        for (int k = 0; k < n_parts; ++k)
+            if (k < part_begin || k >= part_end)
+                IPSX_TRY(ipsx_logits_if(parts[k].emb, parts[k].rows * d, pos ? pos + parts[k].first * d : nullptr, pos_bstride, v_packed, b, parts[k].rows,
+                                        d, r, logits + parts[k].first * r, n * r, redo, redo_mask, stream));
+        return ipsx_scan_range_if(logits, b, n, m, i, h, n_token, 0, it_end, mem_idx, mem_score, tie_flag, redo, redo_mask, stream);
+    }
+    ScanCall c = scan_call(logits, b, n, m, i, h, n_token, mem_idx, mem_score, tie_flag, stream);
+    c.it_begin = it_begin; c.it_end = it_end;
+    IPSX_TRY(validate_scan_call(c));
+    ScanLogits p = {};
+    for (int k = 0; k < n_parts; ++k) { p.part[k].emb = parts[k].emb; p.part[k].rows = (int)parts[k].rows; p.part[k].first = (int)parts[k].first; }
+    p.pos = pos; p.pos_bs = pos_bstride; p.vp = v_packed; p.out = logits; p.redo = redo; p.redo_mask = redo_mask;
+    p.d = d; p.kgs = d / 8; p.n_parts = n_parts; p.part0 = part_begin; p.part1 = part_end;
+    return launch_scan_mnist_logits(c, p);
+}
+
 IPSX_API int ipsx_set_persistent_wait_ms(int ms) {
     const int prev = g_persist_wait_ms;
     if (ms > 0) g_persist_wait_ms = ms > 20000 ? 20000 : ms;
@@ -379,6 +448,14 @@ extern "C" __attribute__((visibility("default"))) void ipsx_dbg_scan_r8(int on) 
 // Diagnostic: 0 sends the shape of scan_mnist_kernel (8 heads, 4 tokens, M = I = 64) through scan_fast_kernel (tools/scan_compare.py,
 // tests/test_scan_mnist.py, the A/B measurements); ipsx_dbg_scan_mnist_shape is the dispatcher's shape predicate
 extern "C" __attribute__((visibility("default"))) void ipsx_dbg_scan_mnist(int on) { g_scan_mnist = on != 0; }
+// Diagnostic: 0 = ipsx_scan_range_logits enqueues the launches it replaces (logits_kernel<1> per part, the loop's range, the
+// conditional redo) instead of the one launch with the logits prologue (tests/test_scan_logits.py, the A/B measurements);
+// -1 only queries.  -> the previous setting
+extern "C" __attribute__((visibility("default"))) int ipsx_dbg_scan_logits(int on) {
+    const int prev = g_scan_logits ? 1 : 0;
+    if (on >= 0) g_scan_logits = on != 0;
+    return prev;
+}
 extern "C" __attribute__((visibility("default"))) int ipsx_dbg_scan_mnist_shape(int m, int i, int h, int n_token) {
     return scan_mnist_shape(m, i, h, n_token) ? 1 : 0;
 }

@@ -387,6 +387,10 @@ _EXPORTS = {
                                                         C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64), C.c_int, C.c_void_p,
                                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "ipsx_part_wait": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ipsx_scan_logits_check": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64]),
+    "ipsx_scan_range_logits": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "ipsx_logits_if": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
     "ipsx_trunk_encode_u8": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
@@ -511,6 +515,9 @@ def lib():
         if os.environ.get("IPSX_SCAN_R8", "1") == "0":      # diagnostic: the 8-row loop shapes through scan_fast_kernel
             L.ipsx_dbg_scan_r8.argtypes = [C.c_int]
             L.ipsx_dbg_scan_r8(0)
+        if os.environ.get("IPSX_SCAN_LOGITS", "1") == "0":  # diagnostic: logits launches in front of scan_mnist_kernel's ranges
+            L.ipsx_dbg_scan_logits.restype, L.ipsx_dbg_scan_logits.argtypes = C.c_int, [C.c_int]
+            L.ipsx_dbg_scan_logits(0)
         _LIB = L
     return _LIB
 
@@ -866,6 +873,73 @@ def scan_range(lg, M, I, H, T, it_begin, it_end, mem_idx, tie, workspace=None):
     _ck(lib().ipsx_scan_range(_p(lg), B, N, M, I, H, T, it_begin, it_end, _p(mem_idx), None, _p(tie),
                               _p(ws), ws.numel() if ws is not None else 0, _stream()), "ipsx_scan_range")
     return mem_idx
+
+
+class LogitsPartStruct(C.Structure):
+    """``ipsx_logits_part`` (include/ipsx.h): a part's (B, rows, D) embeddings, its rows per image, its first row in an image."""
+    _fields_ = [("emb", C.c_void_p), ("rows", C.c_int64), ("first", C.c_int64)]
+
+
+class LogitsParts:
+    """The part table of ``ipsx_scan_range_logits`` and its launch (``scan_range``): the parts' embeddings ``embs[k]``
+    (B, rows_k, D) float32, one after the other along the patch axis - part k holds the rows ``first[k] = rows_0 + ... + rows_(k-1)`` onwards of every image.  Made once
+    per call; keeps the tensors it points to.  ``rows`` alone (ints) makes the table's arithmetic without tensors."""
+
+    def __init__(self, embs=None, rows=None):
+        if embs is not None:
+            rows = [int(e.shape[1]) for e in embs]
+        self.embs, self.rows = embs, [int(r) for r in rows]
+        self.first = [sum(self.rows[:k]) for k in range(len(self.rows))]
+        self.n = sum(self.rows)
+        self.array = (LogitsPartStruct * max(1, len(self.rows)))()
+        for k, r in enumerate(self.rows):
+            self.array[k].emb = embs[k].data_ptr() if embs is not None else None
+            self.array[k].rows, self.array[k].first = r, self.first[k]
+
+    def __len__(self):
+        return len(self.rows)
+
+    def check(self, part_begin, part_end, M, I, it_begin, it_end):
+        """The host-side check of ``ipsx_scan_range_logits`` on this table (``ipsx_scan_logits_check``; no device needed):
+        raises RuntimeError with the library's message when the ranges do not fit the parts."""
+        _ck(lib().ipsx_scan_logits_check(self.array, len(self), part_begin, part_end, self.n, M, I, it_begin, it_end),
+            "ipsx_scan_logits_check")
+
+    def scan_range(self, logits, M, I, H, T, it_begin, it_end, mem_idx, tie, part_begin, part_end, pos, vq, redo=None, mask=1):
+        """``logits(self.embs[k], pos rows of part k, vq)`` for k in [part_begin, part_end) into the (B, N, H*T) table ``logits``
+        and ``scan_range(logits, ..., it_begin, it_end, ...)`` as ONE launch, bit for bit (``ipsx_scan_range_logits``:
+        ``scan_mnist_kernel``'s shape only - ``scan_mnist_shape`` - and D % 8 == 0).  ``pos``: (B or 1, >= N, D) positional rows of
+        WHOLE images, or None.  ``redo`` (int32 device scalar): with a bit of ``mask`` set in it, all parts and the iterations
+        [0, it_end) - the call's conditional redo inside this launch.  ``dbg_scan_logits(False)`` makes the library enqueue the
+        launches this replaces instead."""
+        _same_gpu("scan_range_logits", ("logits", "mem_idx", "tie", "pos", "vq", "redo") + ("emb",) * len(self), logits, mem_idx, tie, pos, vq,
+                  redo, *self.embs)
+        lg, B, N = _scan_args("scan_range_logits", logits, M, I, H, T, mem_idx, tie, None, False)
+        D = self.embs[0].shape[2]
+        for k, e in enumerate(self.embs):
+            if e.dtype != torch.float32 or e.dim() != 3 or tuple(e.shape) != (B, self.rows[k], D) or not e.is_contiguous() or e.data_ptr() & 15:
+                raise ValueError("scan_range_logits: part {} must be a contiguous float32 ({}, {}, {}) block at a 16-byte address, got {} {}".format(
+                    k, B, self.rows[k], D, e.dtype, tuple(e.shape)))
+        if self.n != N:
+            raise ValueError("scan_range_logits: the parts hold {} rows per image, the logits table {}".format(self.n, N))
+        size = lib().ipsx_folded_query_elems(H * T, 1, D)
+        if vq.dtype != torch.float32 or vq.numel() != size or vq.data_ptr() & 15 or not vq.is_contiguous():
+            raise ValueError("scan_range_logits: vq must be the contiguous float32 folded query of R = {}, D = {} at a 16-byte address".format(H * T, D))
+        pos_bs = 0
+        if pos is not None:
+            ps, st = pos.shape, pos.stride()
+            if pos.dtype != torch.float32 or len(ps) != 3 or ps[1] < N or ps[2] != D or ps[0] not in (1, B):
+                raise ValueError("scan_range_logits: pos must be float32 ({} or 1, >= {}, {}), got {} {}".format(B, N, D, pos.dtype, tuple(ps)))
+            pos_bs = st[0] if ps[0] > 1 else 0
+            if st[2] != 1 or st[1] != D or pos_bs < 0 or pos.data_ptr() & 15 or pos_bs & 3:
+                pos = pos.contiguous()
+                pos_bs = pos.stride(0) if ps[0] > 1 else 0
+        if redo is not None:
+            _word("scan_range_logits", "redo", redo)
+        _ck(lib().ipsx_scan_range_logits(_p(lg), B, N, M, I, H, T, it_begin, it_end, _p(mem_idx), None, _p(tie), self.array, len(self),
+                                         part_begin, part_end, D, _p(pos), pos_bs, _p(vq), _p(redo), mask if redo is not None else 0,
+                                         _stream()), "ipsx_scan_range_logits")
+        return mem_idx
 
 
 def scan_range_strided(lg, n, M, I, H, T, it_begin, it_end, mem_idx, tie, workspace=None):
@@ -1305,6 +1379,21 @@ def dbg_scan_mnist(on):
     fn = lib().ipsx_dbg_scan_mnist
     fn.restype, fn.argtypes = None, [C.c_int]
     fn(1 if on else 0)
+
+
+def dbg_scan_logits(on):
+    """Diagnostic: ``False`` makes ``LogitsParts.scan_range`` enqueue the launches it replaces - ``logits_kernel<1>`` per part, the
+    loop's range, the conditional redo - and ``Selection.parts_one_launch`` take its earlier launch chain (comparisons, A/B
+    timing); ``None`` only asks.  The default is on; ``IPSX_SCAN_LOGITS=0`` in the environment switches it off when the
+    library is loaded.  Process-wide: restore it in a ``finally``.  -> the previous setting"""
+    fn = lib().ipsx_dbg_scan_logits                # (diagnostic export, not in include/ipsx.h: bound here, not in _EXPORTS)
+    fn.restype, fn.argtypes = C.c_int, [C.c_int]
+    return bool(fn(-1 if on is None else (1 if on else 0)))
+
+
+def scan_logits_on():
+    """Does ``LogitsParts.scan_range`` run as one launch (``dbg_scan_logits``, ``IPSX_SCAN_LOGITS``)?"""
+    return dbg_scan_logits(None)
 
 
 def scan_persistent_groupable(M, I, H, T):

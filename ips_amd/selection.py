@@ -63,6 +63,13 @@ def _env_on(name):
 # profiles/shuffle_routes_native_order_ab.json) - not the margin that was asked of it
 NATIVE_ORDER_DEFAULT = "0"
 
+# IPSX_SCAN_LOGITS_ROWS when the environment does not set it: the most rows per image of a part whose logits the loop's launch
+# computes itself (``Selection.parts_loop_logits``); a longer part gets a logits launch in front of the loop's.  One workgroup
+# per image computes such rows on ONE compute unit, ~4.3 us per 100 rows measured, where a launch across the device costs its
+# floor of ~5 us and little more: level at ~150 rows, measured to pay at 125 (19.0 -> 18.0 us) and to lose at 375 (43.1 -> 49.7 us;
+# DESIGN 5.4, profiles/scan_logits_trace.txt).  128 = one 32-row tile per SIMD of the workgroup's compute unit.
+SCAN_LOGITS_ROWS_DEFAULT = "128"
+
 # IPSX_ONE_LAUNCH_U8 when the environment does not set it.  Off: the rule was "faster than the parent's uint8 median by more
 # than the parent's own max - min on all three shapes".  16 x 1600x1600 uint8 images met it twice (stride 32: 0.48 / 0.49 ms
 # against 0.11 / 0.13; stride 16: 0.93 / 0.85 against 0.44 / 0.23); 16 x 2,500 uint8 patches missed it in the first of two
@@ -84,6 +91,7 @@ class Selection:
     allocating afresh in every call sends a host that runs ahead of the GPU back to the driver)."""
 
     OVERLAP_PARTS = 4
+    SCAN_LOGITS_ROWS = int(os.environ.get("IPSX_SCAN_LOGITS_ROWS", SCAN_LOGITS_ROWS_DEFAULT))    # (read once, not per call)
     LAZY_SLAB_BYTES = 48 << 20
 
     def __init__(self, net, owned=False):
@@ -97,6 +105,7 @@ class Selection:
         self.scan_status_host = None
         self._mirror_pending = None
         self._unfinished = None
+        self.caller_finishes = False               # IPSNet._call: the call ends in ``finish`` / ``take_unfinished`` + ``after_call``
         self._done = None                          # (mem_idx, mem_patch, mem_pos) of a call the library enqueued whole
         self._calls = {}                           # hip.IpsCall structures, per pipeline
         self.timing_hook = None                    # callable(rows) -> slot of a library-owned event pair around the producer, or None
@@ -746,7 +755,9 @@ class Selection:
         then finds every counter full - and for each part but the last the side stream gets a wait on the part's counter,
         the part's logits and its iterations.  A wait that gave up (no progress for hip.persistent_wait_ms) sets the status
         word; the conditional launches at the end then redo the early parts' logits and the whole loop in this call, and
-        the host, which reads the word one call later, counts the event as the persistent pipelines do."""
+        the host, which reads the word one call later, counts the event as the persistent pipelines do.
+        At ``scan_mnist_kernel``'s shape (``scan_logits_ok``) what follows the trunk launch is ``parts_loop_logits`` instead:
+        the same launches per part, the redo inside the last part's launch, the end of the call in one launch."""
         net, plan = self.net, self.plan()
         N = edges[-1]
         B = every.numel() // N
@@ -773,6 +784,9 @@ class Selection:
         emb_all.record_stream(side)
         starts = [0] + ends[:-1]
         net._emb_parts = parts = [emb_all[starts[k]:ends[k]].view(B, edges[k + 1] - edges[k], -1) for k in range(P)]
+        if self.scan_logits_ok(vq, M, I, ca, net.D):
+            return self.parts_loop_logits(src, parts, its, pos_enc if net.use_pos else None, vq, logits, mem_idx_buf, tie, done, status,
+                                          [ends[k] - starts[k] for k in range(P)], zeroed, scan_ws)
         pos = [pos_enc[:, edges[k]:edges[k + 1]] if net.use_pos else None for k in range(P)]
         with torch.cuda.stream(side):
             side.wait_event(zeroed)                # (previous readers of the buffers are done, the counters are zero)
@@ -791,6 +805,59 @@ class Selection:
         self._mirror_pending = status              # (copied to the host by after_call: behind the call's gathers)
         hip.scan.last_tie = tie
         return mem_idx_buf.clone()                 # the buffer is overwritten by the next call
+
+    @staticmethod
+    def scan_logits_ok(vq, M, I, ca, D):
+        """The counted route without logits launches (``parts_loop_logits``): ``scan_mnist_kernel``'s shape on float32 logits,
+        embeddings of whole 8-float groups, and not switched off (``hip.dbg_scan_logits``, ``IPSX_SCAN_LOGITS=0``)."""
+        return (vq.dtype == torch.float32 and D % 8 == 0 and hip.scan_mnist_shape(M, I, ca.H, ca.n_token) and hip.scan_logits_on())
+
+    def parts_loop_logits(self, src, parts, its, pos, vq, logits, mem_idx_buf, tie, done, status, counts, zeroed, scan_ws=None):
+        """What ``parts_one_launch`` enqueues behind the trunk launch at ``scan_mnist_kernel``'s shape: per part
+        a wait, the part's logits and its iterations on the side stream, as before - a part of at most ``SCAN_LOGITS_ROWS``
+        rows per image without a logits launch: workgroup b of the loop's launch writes image b's logits of the part itself
+        (``hip.LogitsParts.scan_range``).  The last part's launch, on the main stream, takes the status word: clear, it does the
+        last part; set by a wait that gave up, every workgroup recomputes every row of its image and runs the whole loop -
+        the redo of the call, in the launch that was due anyway, so no launch does nothing on the clean path.  The call's
+        end is ``finish``'s one launch where ``IPSNet._call`` asks for it and the patches are a tensor it takes."""
+        net = self.net
+        M, I = net.M, net.I
+        ca = net.transf.crs_attn
+        P = len(its) - 1
+        side, main = self.streams(logits.device)
+        table = hip.LogitsParts(parts)
+        limit = self.SCAN_LOGITS_ROWS
+        R = ca.H * ca.n_token
+
+        def part(k, redo=None):
+            if table.rows[k] <= limit:
+                table.scan_range(logits, M, I, ca.H, ca.n_token, its[k], its[k + 1], mem_idx_buf, tie, k, k + 1, pos, vq, redo=redo)
+                return
+            # a long part: its logits on the whole device, then the loop's launch - the plain one (the kernels of the chain
+            # this replaces), or, where it carries the redo, the prologue's instance with no rows of its own
+            lo = table.first[k]
+            hip.logits(parts[k], pos[:, lo:lo + table.rows[k]] if pos is not None else None, vq, R, out=logits[:, lo:lo + table.rows[k]])
+            if redo is None:
+                hip.scan_range(logits, M, I, ca.H, ca.n_token, its[k], its[k + 1], mem_idx_buf, tie, scan_ws)
+            else:
+                table.scan_range(logits, M, I, ca.H, ca.n_token, its[k], its[k + 1], mem_idx_buf, tie, k + 1, k + 1, pos, vq, redo=redo)
+
+        with torch.cuda.stream(side):
+            side.wait_event(zeroed)                # (previous readers of the buffers are done, the counters are zero)
+            for k in range(P - 1):
+                hip.part_wait(done[k:k + 1], counts[k], status)
+                part(k)
+        main.wait_stream(side)
+        # behind the trunk launch every embedding is there: what the redo reads
+        part(P - 1, redo=status)
+        self._mirror_pending = status              # (copied to the host by finish's launch, or by after_call behind the gathers)
+        hip.scan.last_tie = tie
+        # (whole images: the patches are gathered through the view; a caller that does not end in ``finish`` / ``take_unfinished``
+        #  - dist.py - gets its own copy, as before)
+        if src.is_view or not self.caller_finishes:
+            return mem_idx_buf.clone()
+        self._unfinished = mem_idx_buf             # ``finish`` - one launch - or ``take_unfinished`` + the gathers is the caller's next step
+        return mem_idx_buf
 
     # ------------------------------------------------------------------ pipeline: parts, the loop in ranges beside them
     def parts_with_ranges(self, patches, pos_enc):
