@@ -1076,33 +1076,10 @@ def stream_commit_ragged(tables, sel, slides, M, rows_max, pixels=None, view=Non
         if e.elem_off + view.patch_shape[0] * e.h * e.w > pixels.numel():
             raise ValueError("{}: the view's images end at element {}, the pixels hold {}".format(
                 what, e.elem_off + view.patch_shape[0] * e.h * e.w, pixels.numel()))
-    arr = (StreamTable * max(1, len(tables)))()
-    B, piece_rows = None, 0
-    for k, (held, piece, dst) in enumerate(tables[:len(arr)]):
-        if dst.dim() < 2 or not dst.is_contiguous():
-            raise ValueError("table {}: the destination must be a contiguous (B, cap, ...) tensor".format(k))
-        B = dst.shape[0] if B is None else B
-        if dst.shape[0] != B:
-            raise ValueError("table {}: {} slides, the first table has {}".format(k, dst.shape[0], B))
-        t = arr[k]
-        t.dst, t.dst_rows, t.dst_bstride_rows = dst.data_ptr(), dst.shape[1], dst.shape[1]
-        t.row_bytes = dst[0, 0].numel() * dst.element_size()
-        if held is not None:
-            if not held.is_contiguous() or held.dtype != dst.dtype or held.shape[2:] != dst.shape[2:] or held.shape[0] != B \
-                    or held.device != dst.device:
-                raise ValueError("table {}: held rows must be a contiguous (B, cap, ...) tensor of the destination's kind".format(k))
-            t.held, t.held_rows, t.held_bstride_rows = held.data_ptr(), held.shape[1], held.shape[1]
-        if piece is not None:
-            if piece.dtype != dst.dtype or piece.shape[1:] != dst.shape[2:] or piece.device != dst.device or not piece.is_contiguous():
-                raise ValueError("table {}: the piece must be a contiguous packed (rows, ...) tensor of the destination's kind".format(k))
-            if piece_rows and piece.shape[0] != piece_rows:
-                raise ValueError("table {}: a piece of {} rows, another table's has {}".format(k, piece.shape[0], piece_rows))
-            piece_rows = piece.shape[0]
-            t.piece = piece.data_ptr()
+    arr, B, piece_rows = _stream_tables(tables, packed=True)
     if tuple(slides.shape) != (B, 6) or slides.dtype != torch.int64 or not slides.is_contiguous():
         raise ValueError("slides must be a contiguous (B, 6) int64 tensor")
-    if sel is not None and (sel.dtype != torch.int64 or tuple(sel.shape) != (B, M) or not sel.is_contiguous()):
-        raise ValueError("sel must be a contiguous (B, M) int64 tensor")
+    _check_sel(sel, B, M)
     if view is None:
         _ck(lib().ipsx_stream_commit_ragged(arr, len(tables), _p(sel), _p(slides), B or 0, M, int(rows_max), piece_rows, _stream()),
             "ipsx_stream_commit_ragged")
@@ -1114,44 +1091,63 @@ def stream_commit_ragged(tables, sel, slides, M, rows_max, pixels=None, view=Non
     return unit.value
 
 
-def _stream_tables(tables, n_cand):
-    """``(held, held_rows, piece, dst)`` tuples -> (the ``ipsx_stream_table`` array, B); the checks a tensor allows before
-    the library's own."""
-    if len(tables) > 4:
+def _stream_tables(tables, n_cand=None, packed=False):
+    """The tables of a commit -> (the ``ipsx_stream_table`` array, B, rows of the packed pieces); the checks a tensor allows
+    before the library's own.  ``tables``: ``(held, held_rows, piece, dst)`` with ``piece`` (B or 1, n_cand - held_rows, ...)
+    read where it lies, at most four; or, ``packed`` (the ragged call form): ``(held, piece, dst)`` - all rows of ``held`` may
+    be read, and ``piece`` is ONE packed (rows, ...) tensor for all slides, of as many rows in every table."""
+    if not packed and len(tables) > 4:
         raise ValueError("{} tables: a commit moves at most four".format(len(tables)))
     arr = (StreamTable * max(1, len(tables)))()
-    B = None
-    for k, (held, held_rows, piece, dst) in enumerate(tables[:len(arr)]):
-        row_bytes = dst[0, 0].numel() * dst.element_size()
-        if not dst.is_contiguous():
-            raise ValueError("table {}: the destination must be contiguous".format(k))
+    B, piece_rows = None, 0
+    for k, tab in enumerate(tables[:len(arr)]):
+        held, held_rows, piece, dst = (tab[0], None, tab[1], tab[2]) if packed else tab
+        if (packed and dst.dim() < 2) or not dst.is_contiguous():
+            raise ValueError("table {}: the destination must be {}".format(k, "a contiguous (B, cap, ...) tensor" if packed else "contiguous"))
         B = dst.shape[0] if B is None else B
         if dst.shape[0] != B:
-            raise ValueError("table {}: {} images, the first table has {}".format(k, dst.shape[0], B))
+            raise ValueError("table {}: {} {}, the first table has {}".format(k, dst.shape[0], "slides" if packed else "images", B))
         t = arr[k]
-        t.dst, t.dst_rows, t.dst_bstride_rows, t.row_bytes = dst.data_ptr(), dst.shape[1], dst.shape[1], row_bytes
-        t.held_rows = held_rows
+        t.dst, t.dst_rows, t.dst_bstride_rows = dst.data_ptr(), dst.shape[1], dst.shape[1]
+        t.row_bytes = dst[0, 0].numel() * dst.element_size()
         if held is not None:
             if not held.is_contiguous() or held.dtype != dst.dtype or held.shape[2:] != dst.shape[2:] or held.shape[0] != B \
                     or held.device != dst.device:
                 raise ValueError("table {}: held rows must be a contiguous (B, cap, ...) tensor of the destination's kind".format(k))
-            if held_rows > held.shape[1]:
+            if packed:
+                held_rows = held.shape[1]
+            elif held_rows > held.shape[1]:
                 raise ValueError("table {}: {} held rows in a buffer of {}".format(k, held_rows, held.shape[1]))
             t.held, t.held_bstride_rows = held.data_ptr(), held.shape[1]
         elif held_rows:
             raise ValueError("table {}: {} held rows but no buffer".format(k, held_rows))
-        if piece is not None:
-            if piece.dtype != dst.dtype or piece.shape[2:] != dst.shape[2:] or piece.shape[0] not in (1, B) or piece.device != dst.device:
-                raise ValueError("table {}: the piece must be a (B or 1, n, ...) tensor of the destination's kind".format(k))
-            if piece.shape[1] != n_cand - held_rows:
-                raise ValueError("table {}: a piece of {} rows behind {} held rows, {} candidates".format(k, piece.shape[1], held_rows, n_cand))
-            if piece.shape[1] and not piece[0].is_contiguous():
-                raise ValueError("table {}: the piece's rows must be contiguous inside an image".format(k))
-            bs = piece.stride(0) if piece.shape[0] > 1 else 0
-            if bs < 0:
-                raise ValueError("table {}: negative batch stride".format(k))
-            t.piece, t.piece_bstride_bytes = piece.data_ptr(), bs * piece.element_size()
-    return arr, B
+        t.held_rows = held_rows or 0
+        if piece is None:
+            continue
+        if packed:
+            if piece.dtype != dst.dtype or piece.shape[1:] != dst.shape[2:] or piece.device != dst.device or not piece.is_contiguous():
+                raise ValueError("table {}: the piece must be a contiguous packed (rows, ...) tensor of the destination's kind".format(k))
+            if piece_rows and piece.shape[0] != piece_rows:
+                raise ValueError("table {}: a piece of {} rows, another table's has {}".format(k, piece.shape[0], piece_rows))
+            piece_rows = piece.shape[0]
+            t.piece = piece.data_ptr()
+            continue
+        if piece.dtype != dst.dtype or piece.shape[2:] != dst.shape[2:] or piece.shape[0] not in (1, B) or piece.device != dst.device:
+            raise ValueError("table {}: the piece must be a (B or 1, n, ...) tensor of the destination's kind".format(k))
+        if piece.shape[1] != n_cand - held_rows:
+            raise ValueError("table {}: a piece of {} rows behind {} held rows, {} candidates".format(k, piece.shape[1], held_rows, n_cand))
+        if piece.shape[1] and not piece[0].is_contiguous():
+            raise ValueError("table {}: the piece's rows must be contiguous inside an image".format(k))
+        bs = piece.stride(0) if piece.shape[0] > 1 else 0
+        if bs < 0:
+            raise ValueError("table {}: negative batch stride".format(k))
+        t.piece, t.piece_bstride_bytes = piece.data_ptr(), bs * piece.element_size()
+    return arr, B, piece_rows
+
+
+def _check_sel(sel, B, M):
+    if sel is not None and (sel.dtype != torch.int64 or tuple(sel.shape) != (B, M) or not sel.is_contiguous()):
+        raise ValueError("sel must be a contiguous (B, M) int64 tensor")
 
 
 def stream_commit(tables, sel, M, n_cand, tail_first=0):
@@ -1163,9 +1159,8 @@ def stream_commit(tables, sel, M, n_cand, tail_first=0):
     front stay as they are).  Everything is checked before the launch."""
     if tables is None:
         _ck(lib().ipsx_stream_commit(None, 0, None, 0, M, n_cand, tail_first, None), "ipsx_stream_commit")
-    arr, B = _stream_tables(tables, n_cand)
-    if sel is not None and (sel.dtype != torch.int64 or tuple(sel.shape) != (B, M) or not sel.is_contiguous()):
-        raise ValueError("sel must be a contiguous (B, M) int64 tensor")
+    arr, B, _ = _stream_tables(tables, n_cand)
+    _check_sel(sel, B, M)
     _on_gpu("stream_commit", sel, *[t for tab in tables for t in (tab[0], tab[2], tab[3])])
     st = _stream() if len(tables) else None
     _ck(lib().ipsx_stream_commit(arr, len(tables), _p(sel), B or 0, M, n_cand, tail_first, st), "ipsx_stream_commit")
@@ -1192,9 +1187,8 @@ def stream_commit_view(tables, images, view, sel, M, n_cand, tail_first=0):
         if dst.dtype != images.dtype or tuple(dst.shape[2:]) != view.patch_shape or dst.device != images.device:
             raise ValueError("table 0: rows of {} {}, the view's patches are {} {}".format(
                 dst.dtype, tuple(dst.shape[2:]), images.dtype, view.patch_shape))
-    arr, B = _stream_tables(tables, n_cand)
-    if sel is not None and (sel.dtype != torch.int64 or tuple(sel.shape) != (B, M) or not sel.is_contiguous()):
-        raise ValueError("sel must be a contiguous (B, M) int64 tensor")
+    arr, B, _ = _stream_tables(tables, n_cand)
+    _check_sel(sel, B, M)
     unit = C.c_int(0)
     _on_gpu("stream_commit_view", images, sel, *[t for tab in tables for t in (tab[0], tab[2], tab[3])])
     st = _stream()

@@ -49,43 +49,28 @@ import torch
 from . import hip
 from .ragged import Ragged, _host_emb
 from .ragged_image import RaggedImages, ragged_dedup
-from .stream import BandGeometry, IPSStream
+from .stream import BandGeometry, IPSStream, StreamState
 
 
-class RaggedIPSStream:
+class RaggedIPSStream(StreamState):
     """The state of one streamed ragged selection.  ``fed``: rows per slide so far; ``iterations``: completed iterations per
     slide; ``mem_idx``: (B, M) int64 row numbers inside each slide, in the order of its last completed iteration (a row of
     -1 for a slide that has not reached M rows; None before the first feed).  A row stream (``patch_size`` / ``patch_stride``
     given) takes ``feed_rows(bands)`` instead of ``feed``; ``rows``: pixel rows per image so far, ``fed``:
     complete patch rows times ``nx_b``; ``view_feeds``: feeds whose piece was read through a ragged view (no patch tensor)."""
 
+    entry = "ips_ragged_stream"
+
     def __init__(self, net, pad=False, patch_size=None, patch_stride=None):
-        self.net = net
+        super().__init__(net, patch_size, patch_stride)
         self.pad = bool(pad)
-        self._patch_size = self._patch_stride = None
-        if patch_size is not None or patch_stride is not None:
-            if patch_size is None or patch_stride is None:
-                raise ValueError("a row stream needs both patch_size and patch_stride")
-            if not net.is_image:
-                raise TypeError("a row stream takes bands of whole images: it goes with an image encoder")
-            (ph, pw), (sh, sw) = (int(v) for v in patch_size), (int(v) for v in patch_stride)
-            if min(ph, pw, sh, sw) <= 0:
-                raise ValueError("patch {}x{} / stride {}x{}".format(ph, pw, sh, sw))
-            self._patch_size, self._patch_stride = (ph, pw), (sh, sw)
+        if self._patch_size is not None:
             self._geoms = self._carry = self._widths = self._nx = None   # per image, made by the first feed
             self._view_ok = False        # does the encoder read a ragged view of this patch shape (decided by the first feed)
-        self.view_feeds = 0
-        self._finished = False
-        self._generation = hip.weights_generation()
-        self._B = self._row_shape = self._dtype = None
         self._fed, self._iters, self._held = [], [], []
         self._last_idx = None
         self._solo = None            # the host route: B IPSStream on ATen ops
         self._device_route = None    # decided by the first feed
-        # device state
-        self._sets = None            # [[patch, emb, ids, logits], [...]]: the two buffer sets
-        self._cur = 0
-        self._sel = self._tie = self._scan_ws = None
         self._stage, self._stage_at = [], 0      # pinned (3, B, 6) staging buffers of the per-feed table, used in turn
 
     # ------------------------------------------------------------------ observable state
@@ -123,15 +108,6 @@ class RaggedIPSStream:
         return torch.where(reached.unsqueeze(1), self._sets[self._cur][2][:, :M], -1)
 
     # ------------------------------------------------------------------ checks, before the first launch or allocation of a call
-    def _check(self):
-        if self._finished:
-            raise RuntimeError("this stream has finished (IPSNet.ips_ragged_stream() starts another)")
-        if hip.dedup_blank():
-            raise TypeError("blank-patch dedup needs the whole input (IPSX_DEDUP_BLANK=1 with ips_ragged_stream)")
-        if hip.weights_generation() != self._generation:
-            raise RuntimeError("the weights changed since this stream began (an optimizer step between feeds would mix "
-                               "embeddings of two weight sets)")
-
     def _check_pieces(self, pieces):
         """-> (lengths, row shape, dtype) of a feed, or the refusal."""
         net = self.net
@@ -189,7 +165,7 @@ class RaggedIPSStream:
         Stream-ordered on the current stream, as ``IPSStream.feed``."""
         if self._patch_size is not None:
             raise TypeError("this is a row stream (ips_ragged_stream(patch_size=, patch_stride=)): it takes feed_rows(bands), not patches")
-        self._check()
+        self._check_open()
         lengths, shape, dtype = self._check_pieces(pieces)
         net = self.net
         if self._B is None:
@@ -263,18 +239,8 @@ class RaggedIPSStream:
             if not torch.is_tensor(band) or band.dim() != 3 or band.shape[0] < 1 or band.shape[2] < 1:
                 raise ValueError("entry {}: {}".format(b, layout))
             Cc, h, W = band.shape
-            if dtype is None:                    # the stream's first band: what every later one must look like
-                if band.dtype == torch.uint8:
-                    table = net._table_for(band)
-                    if table.shape[0] != Cc:
-                        raise ValueError("the patch table has {} rows, the band {} channels".format(table.shape[0], Cc))
-                    if hip.on_device(net.device) and hip.precision() != "fp32":
-                        raise TypeError("uint8 bands go with the exact trunk (IPSX_PRECISION=fp32), not {}".format(hip.precision()))
-                elif band.dtype != torch.float32:
-                    raise TypeError("bands are float32, or uint8 after set_patch_table; got {}".format(band.dtype))
-                want = next(net.encoder.children()).in_channels
-                if Cc != want:
-                    raise ValueError("a band of {} channels, the encoder expects {}".format(Cc, want))
+            if dtype is None:                    # the stream's first band
+                self._check_first_band(band, Cc, hip.on_device(net.device))
                 dtype, chans = band.dtype, Cc
             elif band.dtype != dtype:
                 raise TypeError("entry {}: a {} band in a stream of {}".format(b, band.dtype, dtype))
@@ -285,8 +251,7 @@ class RaggedIPSStream:
             if h == 0:
                 continue
             if widths[b] is None:
-                if pw > W:
-                    raise ValueError("entry {}: patches of width {} do not fit rows of {} pixels".format(b, pw, W))
+                self._check_patch_fits(W, "entry {}: ".format(b))
                 widths[b] = W
             plans[b] = geoms[b].plan(h)
             any_row = True
@@ -308,7 +273,7 @@ class RaggedIPSStream:
             raise TypeError("this is a patch stream: feed_rows() goes with ips_ragged_stream(patch_size=, patch_stride=)")
         if isinstance(bands, (Ragged, RaggedImages)):
             raise TypeError("feed_rows takes a list of bands; a RaggedImages of whole images goes through feed_rows_all")
-        self._check()
+        self._check_open()
         dtype, chans, widths, plans = self._check_bands(bands)
         net = self.net
         (ph, pw), (sh, sw) = self._patch_size, self._patch_stride
@@ -377,18 +342,9 @@ class RaggedIPSStream:
         wins = {}
         for b in have:
             drop, rows = plans[b][:2]
-            band, W = bands[b], self._widths[b]
-            carry = rows - (band.shape[1] - drop)
+            W = self._widths[b]
             win = wins[b] = window[offs[b]:offs[b] + Cc * rows * W].view(Cc, rows, W)
-            if carry:
-                win[:, :carry].copy_(self._carry[b])
-            if band.shape[1] > drop:
-                src, dst = band[:, drop:], win[:, carry:]
-                if src.device == window.device or (src.is_contiguous() and dst.is_contiguous()):
-                    dst.copy_(src)
-                else:                            # host rows into a strided window: plane by plane, each transfer contiguous at both ends
-                    for c in range(Cc):
-                        dst[c].copy_(src[c])
+            self._fill_window(win, self._carry[b], bands[b][:, drop:])
         live = [b for b in have if plans[b][2] > 0]
         if live:
             lengths = [plans[b][2] * self._nx[b] if plans[b] is not None and plans[b][1] > 0 else 0 for b in range(B)]
@@ -408,19 +364,12 @@ class RaggedIPSStream:
             self._carry[b] = wins[b][:, rows - keep:].clone() if keep else None
 
     # ------------------------------------------------------------------ the ROCm device
-    def _allocate(self, dev):
+    def _scan_workspace(self, dev):
+        """(every slide scans its own span: B times what one image needs)"""
         net = self.net
-        B, cap = self._B, net.M + net.I - 1
         ca = net.transf.crs_attn
-        self._R = ca.H * ca.n_token
-        self._sets = [[torch.empty((B, cap) + self._row_shape, dtype=self._dtype, device=dev),
-                       torch.empty((B, cap, net.D), dtype=torch.float32, device=dev),
-                       torch.empty((B, cap), dtype=torch.int64, device=dev),
-                       None] for _ in range(2)]
-        self._sel = torch.empty((B, net.M), dtype=torch.int64, device=dev)
-        self._tie = torch.zeros((B,), dtype=torch.int32, device=dev)
         nb = hip.lib().ipsx_scan_workspace_bytes(1, net.M, net.I, ca.H, ca.n_token)
-        self._scan_ws = torch.empty(B * nb, dtype=torch.uint8, device=dev) if nb else None
+        return torch.empty(self._B * nb, dtype=torch.uint8, device=dev) if nb else None
 
     def _numbers(self, planes, dev, view=None):
         """Up to three (B, 6) planes of host ints -> ONE (3, B, 6) int64 tensor on the device, ONE copy.  The copy leaves from
@@ -446,17 +395,6 @@ class RaggedIPSStream:
         if view is not None:
             view.on(out.device, out[18 * B:])
         return out[:18 * B].view(3, B, 6)
-
-    def _logits_room(self, rows, dev):
-        """The logits tables hold a slide's held rows AND its piece's: they grow with the largest number of candidates."""
-        cur = self._sets[self._cur][3]
-        if cur is not None and cur.shape[1] >= rows:
-            return
-        new = [torch.empty((self._B, rows, self._R), dtype=torch.float32, device=dev) for _ in range(2)]
-        if cur is not None:
-            new[self._cur][:, :cur.shape[1]].copy_(cur)
-        for k in range(2):
-            self._sets[k][3] = new[k]
 
     def _pack(self, pieces, lengths, dev):
         """The feed's rows as ONE packed (sum n_b, ...) tensor on the device: a host piece goes over as it is."""
@@ -564,7 +502,7 @@ class RaggedIPSStream:
         """Run the ragged last chunk of every slide that has one -> (mem_patch (B, M, ...), mem_pos (B, M, D) | None), and
         leave behind what ``ips_ragged`` leaves.  Without ``pad`` a slide with no more than M rows is refused, with ``pad``
         a slide with no rows at all."""
-        self._check()
+        self._check_open()
         net = self.net
         if self._B is None:
             raise RuntimeError("nothing was fed")
@@ -586,11 +524,9 @@ class RaggedIPSStream:
         else:
             mem_patch, mem_pos = self._finish_aten()
         net._mem_count = tuple(min(n, M) for n in self._fed) if self.pad else None
-        self._finished, self._last_idx = True, net.last_mem_idx
-        self._sets = self._sel = self._scan_ws = self._solo = None
-        self._stage = []
-        if self._patch_size is not None:
-            self._carry = None
+        self._last_idx = net.last_mem_idx
+        self._release()
+        self._solo, self._stage = None, []
         return mem_patch, mem_pos
 
     def _finish_hip(self):

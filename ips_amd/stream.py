@@ -40,6 +40,8 @@ encoder reads a ``hip.PatchView`` that piece is never unfolded: the stems read t
 copies the kept patches out of it.  Everywhere else the piece is unfolded and takes ``feed()``'s path.
 """
 
+import itertools
+
 import torch
 
 from . import hip
@@ -87,16 +89,16 @@ class BandGeometry:
         return out
 
 
-class IPSStream:
-    """The state of one streamed selection.  ``fed``: patches per image so far; ``iterations``: completed iterations;
-    ``mem_idx``: (B, M) int64 global patch numbers in the order of the last completed iteration (None until M patches
-    have arrived).  A row stream (``patch_size`` / ``patch_stride`` given) takes ``feed_rows(band)`` instead of ``feed``;
-    ``rows``: pixel rows taken so far, ``fed``: complete patch rows times ``nx``; ``view_feeds``: feeds whose piece was read
-    through a patch view (no patch tensor)."""
+class StreamState:
+    """What ``IPSStream`` and ``RaggedIPSStream`` share: how a row stream is asked for, the checks of an open stream and of a
+    row stream's first band, the device buffers (two sets of four tables, the scan's buffers), and the copy that puts
+    carried pixel rows and a band into a window.  ``entry``: the ``IPSNet`` method a stream was made by, for the messages."""
 
-    def __init__(self, net, patch_size=None, patch_stride=None):
+    entry = None
+
+    def __init__(self, net, patch_size, patch_stride):
         self.net = net
-        self._geom = None
+        self._patch_size = self._patch_stride = None          # ((ph, pw), (sh, sw)) of a row stream
         if patch_size is not None or patch_stride is not None:
             if patch_size is None or patch_stride is None:
                 raise ValueError("a row stream needs both patch_size and patch_stride")
@@ -106,22 +108,117 @@ class IPSStream:
             if min(ph, pw, sh, sw) <= 0:
                 raise ValueError("patch {}x{} / stride {}x{}".format(ph, pw, sh, sw))
             self._patch_size, self._patch_stride = (ph, pw), (sh, sw)
-            self._geom = BandGeometry(ph, sh)
-            self._carry = None           # (B, C, carry, W) on net.device: the window before the next band
-            self._band_shape = None      # (B, C, W) of the first band
-            self._nx = 0
         self.view_feeds = 0
-        self.fed = 0
-        self.iterations = 0
         self._finished = False
         self._generation = hip.weights_generation()
         self._B = self._row_shape = self._dtype = None
-        self._on_device = hip.on_device(net.device)
         # device state
         self._sets = None            # [[patch, emb, ids, logits], [...]]: the two buffer sets
         self._cur = 0
-        self._held = 0               # valid rows per image in the current set
         self._sel = self._tie = self._scan_ws = None
+
+    # ------------------------------------------------------------------ checks, before the first launch of a call
+    def _check_open(self):
+        if self._finished:
+            raise RuntimeError("this stream has finished (IPSNet.{}() starts another)".format(self.entry))
+        if hip.dedup_blank():
+            raise TypeError("blank-patch dedup needs the whole input (IPSX_DEDUP_BLANK=1 with {})".format(self.entry))
+        if hip.weights_generation() != self._generation:
+            raise RuntimeError("the weights changed since this stream began (an optimizer step between feeds would mix "
+                               "embeddings of two weight sets)")
+
+    def _check_first_band(self, band, chans, on_device):
+        """The first band of a row stream, ``chans`` channels: what every later one must look like."""
+        net = self.net
+        if band.dtype == torch.uint8:
+            table = net._table_for(band)
+            if table.shape[0] != chans:
+                raise ValueError("the patch table has {} rows, the band {} channels".format(table.shape[0], chans))
+            if on_device and hip.precision() != "fp32":
+                raise TypeError("uint8 bands go with the exact trunk (IPSX_PRECISION=fp32), not {}".format(hip.precision()))
+        elif band.dtype != torch.float32:
+            raise TypeError("bands are float32, or uint8 after set_patch_table; got {}".format(band.dtype))
+        want = next(net.encoder.children()).in_channels
+        if chans != want:
+            raise ValueError("a band of {} channels, the encoder expects {}".format(chans, want))
+
+    def _check_patch_fits(self, W, label=""):
+        """``label``: which entry of a feed the rows are, in front of the message."""
+        if self._patch_size[1] > W:
+            raise ValueError("{}patches of width {} do not fit rows of {} pixels".format(label, self._patch_size[1], W))
+
+    # ------------------------------------------------------------------ the ROCm device
+    def _allocate(self, dev):
+        net = self.net
+        B, cap = self._B, net.M + net.I - 1
+        ca = net.transf.crs_attn
+        self._R = ca.H * ca.n_token
+        self._sets = [[torch.empty((B, cap) + self._row_shape, dtype=self._dtype, device=dev),
+                       torch.empty((B, cap, net.D), dtype=torch.float32, device=dev),
+                       torch.empty((B, cap), dtype=torch.int64, device=dev),
+                       None] for _ in range(2)]
+        self._sel = torch.empty((B, net.M), dtype=torch.int64, device=dev)
+        self._tie = torch.zeros((B,), dtype=torch.int32, device=dev)
+        self._scan_ws = self._scan_workspace(dev)
+
+    def _logits_room(self, rows, dev, keep=None):
+        """The logits tables hold the held rows AND the piece's: they grow with the largest number of candidates (R floats per
+        row).  ``keep``: the rows per image of the current table that go over (None: the whole table)."""
+        cur = self._sets[self._cur][3]
+        if cur is not None and cur.shape[1] >= rows:
+            return
+        new = [torch.empty((self._B, rows, self._R), dtype=torch.float32, device=dev) for _ in range(2)]
+        if cur is not None and keep is None:
+            new[self._cur][:, :cur.shape[1]].copy_(cur)
+        elif cur is not None and keep:
+            new[self._cur][:, :keep].copy_(cur[:, :keep])
+        for k in range(2):
+            self._sets[k][3] = new[k]
+
+    @staticmethod
+    def _fill_window(window, carried, src):
+        """``window`` (..., rows, W) <- the ``carried`` rows (None: none), then ``src`` (..., h, W), the band's rows: the only
+        copy of pixels a feed makes - a host band's transfer lands in the window."""
+        carry = window.shape[-2] - src.shape[-2]
+        if carry:
+            window[..., :carry, :].copy_(carried)
+        if src.shape[-2]:
+            dst = window[..., carry:, :]
+            if src.device == window.device or (src.is_contiguous() and dst.is_contiguous()):
+                dst.copy_(src)
+            else:                        # host rows into a strided window: plane by plane, each transfer contiguous at both ends
+                for at in itertools.product(*(range(n) for n in dst.shape[:-2])):
+                    dst[at].copy_(src[at])
+
+    def _release(self):
+        """The end of the stream: its buffers go."""
+        self._finished = True
+        self._sets = self._sel = self._scan_ws = None
+        if self._patch_size is not None:
+            self._carry = None
+
+
+class IPSStream(StreamState):
+    """The state of one streamed selection.  ``fed``: patches per image so far; ``iterations``: completed iterations;
+    ``mem_idx``: (B, M) int64 global patch numbers in the order of the last completed iteration (None until M patches
+    have arrived).  A row stream (``patch_size`` / ``patch_stride`` given) takes ``feed_rows(band)`` instead of ``feed``;
+    ``rows``: pixel rows taken so far, ``fed``: complete patch rows times ``nx``; ``view_feeds``: feeds whose piece was read
+    through a patch view (no patch tensor)."""
+
+    entry = "ips_stream"
+
+    def __init__(self, net, patch_size=None, patch_stride=None):
+        super().__init__(net, patch_size, patch_stride)
+        self._geom = None
+        if self._patch_size is not None:
+            self._geom = BandGeometry(self._patch_size[0], self._patch_stride[0])
+            self._carry = None           # (B, C, carry, W) on net.device: the window before the next band
+            self._band_shape = None      # (B, C, W) of the first band
+            self._nx = 0
+        self.fed = 0
+        self.iterations = 0
+        self._on_device = hip.on_device(net.device)
+        self._held = 0               # valid rows per image in the current set
         # ATen state
         self._mem_patch = self._mem_emb = self._mem_ids = None
         self._pending = None         # (B, t, ...) rows no iteration has consumed
@@ -144,13 +241,7 @@ class IPSStream:
     # ------------------------------------------------------------------ checks, before the first launch of a call
     def _check(self, piece=None):
         net = self.net
-        if self._finished:
-            raise RuntimeError("this stream has finished (IPSNet.ips_stream() starts another)")
-        if hip.dedup_blank():
-            raise TypeError("blank-patch dedup needs the whole input (IPSX_DEDUP_BLANK=1 with ips_stream)")
-        if hip.weights_generation() != self._generation:
-            raise RuntimeError("the weights changed since this stream began (an optimizer step between feeds would mix "
-                               "embeddings of two weight sets)")
+        self._check_open()
         if piece is None:
             return
         if not torch.is_tensor(piece) or piece.dim() != (5 if net.is_image else 3) or piece.shape[1] < 1 or piece.shape[0] < 1:
@@ -227,19 +318,8 @@ class IPSStream:
         (ph, pw), (sh, sw) = self._patch_size, self._patch_stride
         B, Cc, h, W = band.shape
         if self._band_shape is None:
-            if band.dtype == torch.uint8:
-                table = net._table_for(band)
-                if table.shape[0] != Cc:
-                    raise ValueError("the patch table has {} rows, the band {} channels".format(table.shape[0], Cc))
-                if self._on_device and hip.precision() != "fp32":
-                    raise TypeError("uint8 bands go with the exact trunk (IPSX_PRECISION=fp32), not {}".format(hip.precision()))
-            elif band.dtype != torch.float32:
-                raise TypeError("bands are float32, or uint8 after set_patch_table; got {}".format(band.dtype))
-            want = next(net.encoder.children()).in_channels
-            if Cc != want:
-                raise ValueError("a band of {} channels, the encoder expects {}".format(Cc, want))
-            if pw > W:
-                raise ValueError("patches of width {} do not fit rows of {} pixels".format(pw, W))
+            self._check_first_band(band, Cc, self._on_device)
+            self._check_patch_fits(W)
         else:
             self._check_like_first("band", band, (B, Cc, W) == self._band_shape,
                                    lambda: "B = {}, C = {}, h, W = {}".format(*self._band_shape))
@@ -248,21 +328,10 @@ class IPSStream:
         return plan
 
     def _window(self, band, drop, rows):
-        """The carried rows and the band's rows from ``drop`` on as ONE (B, C, rows, W) tensor on the net's device: the only
-        copy of pixels a feed makes - a host band's transfer lands in it."""
-        B, Cc, h, W = band.shape
-        carry = rows - (h - drop)
+        """The carried rows and the band's rows from ``drop`` on as ONE (B, C, rows, W) tensor on the net's device."""
+        B, Cc, _, W = band.shape
         window = torch.empty((B, Cc, rows, W), dtype=band.dtype, device=self.net.device)
-        if carry:
-            window[:, :, :carry].copy_(self._carry)
-        if h > drop:
-            src, dst = band[:, :, drop:], window[:, :, carry:]
-            if src.device == window.device or (src.is_contiguous() and dst.is_contiguous()):
-                dst.copy_(src)
-            else:                        # host rows into a strided window: plane by plane, each transfer contiguous at both ends
-                for b in range(B):
-                    for c in range(Cc):
-                        dst[b, c].copy_(src[b, c])
+        self._fill_window(window, self._carry, band[:, :, drop:])
         return window
 
     @torch.no_grad()
@@ -301,30 +370,10 @@ class IPSStream:
         return self
 
     # ------------------------------------------------------------------ the ROCm device
-    def _allocate(self, piece):
+    def _scan_workspace(self, dev):
         net = self.net
-        B, dev, cap = self._B, piece.device, net.M + net.I - 1
         ca = net.transf.crs_attn
-        R = ca.H * ca.n_token
-        self._sets = [[torch.empty((B, cap) + self._row_shape, dtype=self._dtype, device=dev),
-                       torch.empty((B, cap, net.D), dtype=torch.float32, device=dev),
-                       torch.empty((B, cap), dtype=torch.int64, device=dev),
-                       None] for _ in range(2)]
-        self._sel = torch.empty((B, net.M), dtype=torch.int64, device=dev)
-        self._tie = torch.zeros((B,), dtype=torch.int32, device=dev)
-        self._scan_ws = hip.scan_workspace(B, net.M, net.I, ca.H, ca.n_token, dev)
-        self._R = R
-
-    def _logits_room(self, rows, dev):
-        """The logits tables hold the held rows AND the piece's: they grow with the largest piece (R floats per row)."""
-        cur = self._sets[self._cur][3]
-        if cur is not None and cur.shape[1] >= rows:
-            return
-        new = [torch.empty((self._B, rows, self._R), dtype=torch.float32, device=dev) for _ in range(2)]
-        if cur is not None and self._held:
-            new[self._cur][:, :self._held].copy_(cur[:, :self._held])
-        for k in range(2):
-            self._sets[k][3] = new[k]
+        return hip.scan_workspace(self._B, net.M, net.I, ca.H, ca.n_token, dev)
 
     def _encode(self, piece):
         """(B, n, ...) -> (B, n, D) float32, the piece read where it lies: one launch for a contiguous piece, one per image
@@ -359,8 +408,8 @@ class IPSStream:
         M, I = net.M, net.I
         n_k, held = piece.shape[1] if view is None else view.per_image, self._held
         if self._sets is None:
-            self._allocate(piece)
-        self._logits_room(held + n_k, piece.device)
+            self._allocate(piece.device)
+        self._logits_room(held + n_k, piece.device, keep=held)       # (only the held rows of the table hold logits)
         if view is None:
             emb_k = self._encode(piece)
         else:                        # (the view numbers image-major: one launch for all images)
@@ -471,8 +520,6 @@ class IPSStream:
         return mem_patch, mem_pos
 
     def _close(self, mem_idx):
-        self._finished, self._last_idx = True, mem_idx
-        self._sets = self._sel = self._scan_ws = None
+        self._last_idx = mem_idx
+        self._release()
         self._mem_patch = self._mem_emb = self._mem_ids = self._pending = None
-        if self._geom is not None:
-            self._carry = None

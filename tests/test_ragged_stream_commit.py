@@ -131,3 +131,55 @@ def test_select_without_sel_and_numbers_out_of_range_write_nothing():
     slides[0] = [5, 10, 11, 3, SELECT, 0]        # the tail starts behind the candidates
     got = launch(tables, slides, SEL, 8)
     assert all((dst == SENTINEL).all() for _, dst in got)
+
+
+@pytest.mark.parametrize("clamp", [False, True])
+@pytest.mark.parametrize("dtype,width", [(torch.float32, 4), (torch.float32, 3), (torch.uint8, 3)])        # rows of 16, 12, 3 bytes
+def test_uniform_and_ragged_commit_write_the_same_bytes(dtype, width, clamp):
+    """Where the contracts of ``hip.stream_commit`` and ``hip.stream_commit_ragged`` overlap - every slide has the uniform
+    call's numbers, the pieces are contiguous - the two kernel families share their body and must write byte-identical
+    destinations: an append, then a selection with a tail.  B = 2, M = 4, 5 held rows, a piece of 3 rows (the uniform call
+    takes it as (B, 3, ...), the ragged one the same rows packed as (6, ...)), tail_first = 6; ``clamp``: one ``sel`` entry
+    of -1 and one of n_cand.  Sources and destinations are filled with distinct values, and the bytes neither call may
+    touch - the rows in front of an append, the rows behind what is written - are compared with the rest."""
+    B, held_rows, piece_rows, tail_first, cap = 2, 5, 3, 6, 12
+    n_cand = held_rows + piece_rows
+    numel = B * cap * width
+
+    def values(first, shape):           # first, first + 1, ...: no value twice in held and piece together, none is the filler
+        return torch.arange(first, first + torch.Size(shape).numel()).to(dtype).view(shape).to(DEV)
+
+    held = values(1, (B, cap, width))
+    piece = values(1 + numel, (B, piece_rows, width))
+    assert numel + piece.numel() < 251       # (a uint8 holds them)
+    sel = torch.tensor([[7, 0, 5, 2], [3, 3, 6, 1]], dtype=torch.int64, device=DEV)
+    if clamp:
+        sel[0, 1], sel[1, 2] = -1, n_cand
+
+    def fresh():
+        return torch.full((B, cap, width), 251, dtype=dtype, device=DEV) if dtype == torch.uint8 else \
+            torch.full((B, cap, width), -7.0, dtype=dtype, device=DEV)
+
+    # append: the piece's rows go behind the held ones; the uniform call needs no candidates in front of them in dst
+    dst_u, dst_r = fresh(), fresh()
+    hip.stream_commit([(held, held_rows, piece, dst_u)], None, M, n_cand)
+    slides = torch.tensor([[held_rows, n_cand, 0, b * piece_rows, APPEND, 0] for b in range(B)], dtype=torch.int64, device=DEV)
+    hip.stream_commit_ragged([(held, piece.reshape(B * piece_rows, width), dst_r)], None, slides, M, piece_rows)
+    torch.cuda.synchronize()
+    assert torch.equal(dst_u.view(torch.uint8), dst_r.view(torch.uint8))
+    assert torch.equal(dst_u[:, held_rows:n_cand], piece) and torch.equal(dst_u[:, :held_rows], fresh()[:, :held_rows]) \
+        and torch.equal(dst_u[:, n_cand:], fresh()[:, n_cand:])
+
+    # select with a tail: M winners, then candidates [tail_first, n_cand)
+    dst_u, dst_r = fresh(), fresh()
+    hip.stream_commit([(held, held_rows, piece, dst_u)], sel, M, n_cand, tail_first)
+    slides = torch.tensor([[held_rows, n_cand, tail_first, b * piece_rows, SELECT, 0] for b in range(B)], dtype=torch.int64, device=DEV)
+    hip.stream_commit_ragged([(held, piece.reshape(B * piece_rows, width), dst_r)], sel, slides, M, M + n_cand - tail_first)
+    torch.cuda.synchronize()
+    assert torch.equal(dst_u.view(torch.uint8), dst_r.view(torch.uint8))
+    cand = torch.cat((held[:, :held_rows], piece), dim=1)
+    rows = torch.cat((sel.clamp(0, n_cand - 1), torch.arange(tail_first, n_cand, device=DEV).expand(B, -1)), dim=1)
+    want = fresh()
+    want[:, :rows.shape[1]] = torch.gather(cand, 1, rows.unsqueeze(-1).expand(-1, -1, width))
+    assert torch.equal(dst_u, want)
+    assert torch.equal(held, values(1, (B, cap, width))) and torch.equal(piece, values(1 + numel, (B, piece_rows, width)))
