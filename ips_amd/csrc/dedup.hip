@@ -96,6 +96,26 @@ __device__ __forceinline__ uint4 float4_bits(const float4& f) {
 }
 __device__ __forceinline__ unsigned long long low_bits(int b) { return b >= 64 ? ~0ull : (1ull << b) - 1ull; }
 
+// Does the 1x32x32 float32 window at p (its image's row pitch w floats) hold a non-zero bit?  A wavefront's question: v0 is
+// the lane's share of the first KiB (patch rows 0 - 7, view_load_32 unit 0), loaded by the caller - so that several windows'
+// first reads can be in flight together -, the other three are read only where that is all zero; -0.0 is zero.
+__device__ __forceinline__ bool window_nonzero(const float* p, int w, int wide, int lane, const float4& v0) {
+    unsigned any = nonzero_bits(float4_bits(v0));
+    if (__ballot(any != 0) == 0ull) {
+        float4 r[3];
+        view_load_32<3>(p, w, wide, lane, 1, r);
+        any = nonzero_bits(float4_bits(r[0])) | nonzero_bits(float4_bits(r[1])) | nonzero_bits(float4_bits(r[2]));
+    }
+    return __ballot(any != 0) != 0ull;
+}
+// ... of uint8 pixels: blank means every byte 0.  A lane's 16 bytes are half a patch row, contiguous in the image
+// (view_load_u8: 16, 4 or 1 bytes per load by `wide`) - the whole KiB in one read per lane, nothing to exit early from
+__device__ __forceinline__ void window_load_u8(const unsigned char* p, int w, int wide, unsigned (&d)[4]) {
+    const int lane = threadIdx.x & 63;
+    view_load_u8<4>(p + (long long)(lane >> 1) * w + 16 * (lane & 1), wide, d);
+}
+__device__ __forceinline__ bool window_nonzero_u8(const unsigned (&d)[4]) { return __ballot((d[0] | d[1] | d[2] | d[3]) != 0u) != 0ull; }
+
 // List entry j is patch index[j].  A wavefront takes four entries: the first KiB of each (one 16-byte load per lane, the four
 // in flight together) and, only where that is all zero, the other three.  On data without blank patches a KiB per patch is
 // read.  Blank entry j: emb row j = blank_emb.  The hand-over of those rows is parts_count's (fused_trunk_eight.h): every
@@ -218,8 +238,8 @@ __global__ __launch_bounds__(1024) void blank_scan_parts_u8_kernel(const unsigne
 }
 
 // A view of float32 images: list entry j is GRID patch index[j], its rows at pitch w in the image (view_base, view_load_32:
-// 16-byte loads where va.wide allows, dwords otherwise).  The float32 scan's order: the first KiB of the four entries (patch
-// rows 0 - 7) in flight together, the other three only where that was all zero; -0.0 is zero.
+// 16-byte loads where va.wide allows, dwords otherwise).  The float32 scan's order: the first KiB of the four entries in
+// flight together, then window_nonzero.
 __global__ __launch_bounds__(1024) void blank_scan_parts_view_kernel(const float* __restrict__ x, ViewArgs va,
                                                                      const int* __restrict__ index, int n,
                                                                      const float* __restrict__ blank_emb, float* __restrict__ emb,
@@ -240,38 +260,30 @@ __global__ __launch_bounds__(1024) void blank_scan_parts_view_kernel(const float
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         if (e >= valid) break;                                            // wavefront-uniform
-        unsigned any = nonzero_bits(float4_bits(v[e][0]));
-        if (__ballot(any != 0) == 0ull) {
-            float4 r[3];
-            view_load_32<3>(p[e], va.v.w, va.wide, lane, 1, r);
-            any = nonzero_bits(float4_bits(r[0])) | nonzero_bits(float4_bits(r[1])) | nonzero_bits(float4_bits(r[2]));
-        }
-        if (__ballot(any != 0) != 0ull) bits |= 1u << e;
+        if (window_nonzero(p[e], va.v.w, va.wide, lane, v[e][0])) bits |= 1u << e;
     }
     scan_hand_over(bits, valid, j0, lo, n, blank_emb, emb, pa, mask, cnt);
 }
 
-// A view of uint8 images: a lane's 16 bytes are half a patch row, contiguous in the image (view_load_u8: 16, 4 or 1 bytes
-// per load by va.wide) - one such read per entry, the four of a wavefront in flight together; blank: every byte 0.
+// A view of uint8 images: one window_load_u8 per entry, the four of a wavefront in flight together.
 __global__ __launch_bounds__(1024) void blank_scan_parts_view_u8_kernel(const unsigned char* __restrict__ x, ViewArgs va,
                                                                         const int* __restrict__ index, int n,
                                                                         const float* __restrict__ blank_emb, float* __restrict__ emb,
                                                                         PartsArgs pa, unsigned long long* __restrict__ mask,
                                                                         int* __restrict__ cnt) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wave = threadIdx.x >> 6;
     const int lo = blockIdx.x * SCAN_ENT, j0 = lo + wave * 4;
     const int valid = n - j0 < 4 ? (n - j0 > 0 ? n - j0 : 0) : 4;
     unsigned w[4][4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        if (e < valid)
-            view_load_u8<4>(x + view_base(va, index[j0 + e]) + (long long)(lane >> 1) * va.v.w + 16 * (lane & 1), va.wide, w[e]);
+        if (e < valid) window_load_u8(x + view_base(va, index[j0 + e]), va.v.w, va.wide, w[e]);
         else w[e][0] = w[e][1] = w[e][2] = w[e][3] = 0u;
     }
     unsigned bits = 0;
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-        if (__ballot((w[e][0] | w[e][1] | w[e][2] | w[e][3]) != 0u) != 0ull) bits |= 1u << e;
+        if (window_nonzero_u8(w[e])) bits |= 1u << e;
     scan_hand_over(bits, valid, j0, lo, n, blank_emb, emb, pa, mask, cnt);
 }
 
@@ -315,39 +327,27 @@ __global__ __launch_bounds__(256) void blank_compact_kernel(const unsigned long 
 //   fused_trunk_ragged_view_counted_kernel (fused_trunk_eight.h) over that list, then scatter_rows_kernel
 // One wavefront per list entry j (wave-uniform: readfirstlane), the bisection, the table entry and the offset on scalar
 // registers (ragged_at); an entry that is no packed patch is packed patch 0, as in the encoder.  The 1x32x32 window at its
-// image's row pitch: the first KiB (patch rows 0 - 7), the other three only where that is all zero; 16-byte loads where
-// rv.wide allows, dwords otherwise (view_load_32) - nothing outside the window is read.
-__global__ __launch_bounds__(256) void blank_flags_ragged_view_kernel(const float* __restrict__ x, RaggedViewArgs rv, long long n,
+// image's row pitch, asked as the counted launch's view scans ask it (window_nonzero; U8: whole uint8 images,
+// window_nonzero_u8) - nothing outside the window is read.
+template <bool U8>
+__global__ __launch_bounds__(256) void blank_flags_ragged_view_kernel(const void* __restrict__ x, RaggedViewArgs rv, long long n,
                                                                       int* __restrict__ nonblank) {
     const int lane = threadIdx.x & 63;
     const long long j = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (j >= n) return;                                                   // wavefront-uniform
     const RaggedAt at = ragged_at(rv, j);
-    const float* p = x + at.off;
-    float4 v[1];
-    view_load_32<1>(p, at.v.w, at.wide, lane, 0, v);
-    unsigned any = nonzero_bits(float4_bits(v[0]));
-    if (__ballot(any != 0) == 0ull) {
-        float4 r[3];
-        view_load_32<3>(p, at.v.w, at.wide, lane, 1, r);
-        any = nonzero_bits(float4_bits(r[0])) | nonzero_bits(float4_bits(r[1])) | nonzero_bits(float4_bits(r[2]));
+    bool any;
+    if constexpr (U8) {
+        unsigned w[4];
+        window_load_u8(static_cast<const unsigned char*>(x) + at.off, at.v.w, at.wide, w);
+        any = window_nonzero_u8(w);
+    } else {
+        const float* p = static_cast<const float*>(x) + at.off;
+        float4 v[1];
+        view_load_32<1>(p, at.v.w, at.wide, lane, 0, v);
+        any = window_nonzero(p, at.v.w, at.wide, lane, v[0]);
     }
-    const unsigned long long b = __ballot(any != 0);
-    if (lane == 0) nonblank[j] = b != 0ull;
-}
-
-// ... of whole uint8 images: blank means every byte of the window 0.  A lane's 16 bytes are half a patch row, contiguous in
-// its image (view_load_u8: 16, 4 or 1 bytes per load by rv.wide) - the whole KiB in one read, as blank_scan_parts_view_u8_kernel
-__global__ __launch_bounds__(256) void blank_flags_ragged_view_u8_kernel(const unsigned char* __restrict__ x, RaggedViewArgs rv,
-                                                                         long long n, int* __restrict__ nonblank) {
-    const int lane = threadIdx.x & 63;
-    const long long j = (long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    if (j >= n) return;                                                   // wavefront-uniform
-    const RaggedAt at = ragged_at(rv, j);
-    unsigned w[4];
-    view_load_u8<4>(x + at.off + (long long)(lane >> 1) * at.v.w + 16 * (lane & 1), at.wide, w);
-    const unsigned long long b = __ballot((w[0] | w[1] | w[2] | w[3]) != 0u);
-    if (lane == 0) nonblank[j] = b != 0ull;
+    if (lane == 0) nonblank[j] = any;
 }
 
 // Ordered compaction with many workgroups: a workgroup takes 1,024 entries.  It counts the non-blank entries in front of its
@@ -399,114 +399,80 @@ __global__ __launch_bounds__(1024) void ragged_compact_kernel(const int* __restr
     }
 }
 
-}  // namespace ipsx
+// ---- the host side.  The ipsx_trunk_encode* exports themselves stand in trunk.hip, each a call of one of these.
 
-using namespace ipsx;
-
-IPSX_API int ipsx_trunk_encode_indexed(const ipsx_trunk* t, const float* patches, const int32_t* index,
-                                       int64_t n_index, float* emb, void* stream) {
-    IPSX_REQUIRE(t && patches && index && emb && n_index >= 0, "trunk_encode_indexed: bad arguments");
-    IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_indexed: only the fused 1x32x32 trunk is supported");
-    const PatchSrc src{patches, nullptr, nullptr, index, 0};
-    IPSX_TRY(patch_src_check(t, src, n_index, true, "trunk_encode_indexed"));
-    if (n_index == 0) return IPSX_OK;
-    return fused_launch(t, src, n_index, emb, as_stream(stream));
+// The workspace of the two explicit routes, in ONE place: flags, list and slots (n ints each) and the length, then - at the
+// next 256-byte boundary - the n + 1 compacted rows of 128 floats.  -> the bytes the workspace exports report (they cover it:
+// the rows start at most 259 bytes behind the ints, 512 are allowed for)
+struct DedupWork {
+    int *flags, *list, *slot, *count;
+    float* rows;
+};
+static size_t dedup_layout(int64_t n, void* workspace, DedupWork* w) {
+    if (w) {
+        w->flags = static_cast<int*>(workspace); w->list = w->flags + n; w->slot = w->list + n; w->count = w->slot + n;
+        w->rows = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + (((size_t)n * 12 + 4 + 255) & ~(size_t)255));
+    }
+    return (size_t)n * 12 + 256 + (size_t)(n + 1) * 128 * sizeof(float) + 256;
 }
 
-IPSX_API int ipsx_trunk_encode_parts(const ipsx_trunk* t, const float* patches, const int32_t* index, int64_t n_index,
-                                     float* emb, const int64_t* part_end, int n_parts, int32_t* done, void* stream) {
-    IPSX_REQUIRE(t && patches && index && emb && part_end && done, "trunk_encode_parts: null pointer");
-    IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_parts: only the fused 1x32x32 trunk is supported");
-    return fused_trunk_encode_parts(t, PatchSrc{patches, nullptr, nullptr, index, 0}, n_index, emb, part_end, n_parts, done,
-                                    as_stream(stream));
+// The explicit route behind its entry's refusals: the flags (flags(w): made into w.flags, or the caller's own), the route's
+// compaction (compact(w): list, slots and length), the trunk over the list - patch numbers of `src`, read as an index list of
+// up to n entries, *count of them written -, the scatter and the copy of the length.
+template <class Flags, class Compact>
+static int dedup_explicit(const ipsx_trunk* t, PatchSrc src, int64_t n, float* emb, void* workspace, int32_t* n_encoded, hipStream_t s,
+                          const char* what, Flags flags, Compact compact) {
+    DedupWork w;
+    dedup_layout(n, workspace, &w);
+    IPSX_TRY(flags(w));
+    IPSX_TRY(compact(w));
+    src.index = w.list; src.first = 0;
+    IPSX_TRY(fused_launch(t, src, n, w.rows, s, w.count));
+    scatter_rows_kernel<<<dim3((unsigned)cdiv(n * 32, 256)), dim3(256), 0, s>>>(
+        reinterpret_cast<const float4*>(w.rows), w.slot, reinterpret_cast<float4*>(emb), n, 32);
+    IPSX_TRY(launched("scatter_rows"));
+    if (n_encoded && hipMemcpyAsync(n_encoded, w.count, sizeof(int), hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return fail(IPSX_EHIP, "%s: count copy failed", what);
+    return IPSX_OK;
 }
 
-IPSX_API int ipsx_trunk_encode_parts_u8(const ipsx_trunk* t, const uint8_t* patches, const float* table, const int32_t* index,
-                                        int64_t n_index, float* emb, const int64_t* part_end, int n_parts, int32_t* done,
-                                        void* stream) {
-    IPSX_REQUIRE(t && patches && table && index && emb && part_end && done, "trunk_encode_parts_u8: null pointer");
-    IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_parts_u8: only the fused 1x32x32 trunk is supported");
-    const PatchSrc src{patches, table, nullptr, index, 0};
-    IPSX_TRY(patch_src_check(t, src, n_index, true, "trunk_encode_parts_u8"));
-    return fused_trunk_encode_parts(t, src, n_index, emb, part_end, n_parts, done, as_stream(stream));
-}
-
-IPSX_API size_t ipsx_trunk_dedup_workspace_bytes(const ipsx_trunk* t, int64_t n_patch) {
-    if (!t || n_patch <= 0) return 0;
-    // nonblank, index, slot (n ints each) + count + the compacted embeddings (n+1 rows of 128 floats)
-    return (size_t)n_patch * 12 + 256 + (size_t)(n_patch + 1) * 128 * sizeof(float) + 256;
-}
-
-static int encode_dedup(const ipsx_trunk* t, const float* patches, int64_t n_patch, const int32_t* flags, float* emb,
-                        void* workspace, size_t workspace_bytes, int32_t* n_encoded, void* stream) {
-    IPSX_REQUIRE(t && patches && emb && n_patch >= 0, "trunk_encode_dedup: bad arguments");
+// ipsx_trunk_encode_dedup (flags: NULL) and _flagged (flagged: the caller's flags, which must be there)
+int encode_dedup(const ipsx_trunk* t, const PatchSrc& src, int64_t n_patch, const int32_t* flags, bool flagged, float* emb,
+                 void* workspace, size_t workspace_bytes, int32_t* n_encoded, void* stream) {
+    IPSX_REQUIRE(!flagged || flags, "trunk_encode_dedup_flagged: no flags");
+    IPSX_REQUIRE(t && t->patch_dtype == 0, "trunk_encode_dedup: blank-patch detection reads float32 patches");
+    IPSX_REQUIRE(t && src.base && emb && n_patch >= 0, "trunk_encode_dedup: bad arguments");
     IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_dedup: only the fused 1x32x32 trunk is supported");
     IPSX_REQUIRE(n_patch < ((int64_t)1 << 31), "trunk_encode_dedup: too many patches");
-    IPSX_TRY(patch_src_check(t, PatchSrc{patches, nullptr, nullptr, nullptr, 0}, n_patch, true, "trunk_encode_dedup"));
+    IPSX_TRY(patch_src_check(t, src, n_patch, true, "trunk_encode_dedup"));
     if (n_patch == 0) return IPSX_OK;
     const size_t need = ipsx_trunk_dedup_workspace_bytes(t, n_patch);
     if (!workspace || workspace_bytes < need)
         return fail(IPSX_EWORKSPACE, "trunk_encode_dedup: workspace %zu B < %zu B", workspace_bytes, need);
     hipStream_t s = as_stream(stream);
-    int* nonblank = static_cast<int*>(workspace);
-    int* index = nonblank + n_patch;
-    int* slot = index + n_patch;
-    int* count = slot + n_patch;
-    float* emb_u = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(workspace) +
-                                            (((size_t)n_patch * 12 + 4 + 255) & ~(size_t)255));
-    const int elems4 = t->c_in * t->h * t->w / 4;
-    if (!flags) {
-        blank_flags_kernel<<<dim3((unsigned)cdiv(n_patch, 4)), dim3(256), 0, s>>>(patches, n_patch, elems4, nonblank);
-        IPSX_TRY(launched("blank_flags"));
-    }
-    compact_kernel<<<dim3(1), dim3(1024), 0, s>>>(flags ? reinterpret_cast<const int*>(flags) : nonblank, (int)n_patch,
-                                                  index, slot, count);
-    IPSX_TRY(launched("compact"));
-    IPSX_TRY(fused_launch(t, PatchSrc{patches, nullptr, nullptr, index, 0}, n_patch, emb_u, s, count));
-    scatter_rows_kernel<<<dim3((unsigned)cdiv(n_patch * 32, 256)), dim3(256), 0, s>>>(
-        reinterpret_cast<const float4*>(emb_u), slot, reinterpret_cast<float4*>(emb), n_patch, 32);
-    IPSX_TRY(launched("scatter_rows"));
-    if (n_encoded) {
-        if (hipMemcpyAsync(n_encoded, count, sizeof(int), hipMemcpyDeviceToDevice, s) != hipSuccess)
-            return fail(IPSX_EHIP, "trunk_encode_dedup: count copy failed");
-    }
-    return IPSX_OK;
-}
-
-static int dedup_needs_f32(const ipsx_trunk* t) {
-    IPSX_REQUIRE(t && t->patch_dtype == 0, "trunk_encode_dedup: blank-patch detection reads float32 patches");
-    return IPSX_OK;
-}
-
-IPSX_API int ipsx_trunk_encode_dedup(const ipsx_trunk* t, const float* patches, int64_t n_patch, float* emb,
-                                     void* workspace, size_t workspace_bytes, int32_t* n_encoded, void* stream) {
-    IPSX_TRY(dedup_needs_f32(t));
-    return encode_dedup(t, patches, n_patch, nullptr, emb, workspace, workspace_bytes, n_encoded, stream);
-}
-
-IPSX_API int ipsx_trunk_encode_dedup_flagged(const ipsx_trunk* t, const float* patches, int64_t n_patch,
-                                             const int32_t* nonblank, float* emb, void* workspace,
-                                             size_t workspace_bytes, int32_t* n_encoded, void* stream) {
-    IPSX_REQUIRE(nonblank, "trunk_encode_dedup_flagged: no flags");
-    IPSX_TRY(dedup_needs_f32(t));
-    return encode_dedup(t, patches, n_patch, nonblank, emb, workspace, workspace_bytes, n_encoded, stream);
+    return dedup_explicit(t, src, n_patch, emb, workspace, n_encoded, s, "trunk_encode_dedup",
+        [&](const DedupWork& w) {
+            if (flags) return (int)IPSX_OK;
+            blank_flags_kernel<<<dim3((unsigned)cdiv(n_patch, 4)), dim3(256), 0, s>>>(static_cast<const float*>(src.base), n_patch,
+                                                                                      t->c_in * t->h * t->w / 4, w.flags);
+            return launched("blank_flags");
+        },
+        [&](const DedupWork& w) {
+            compact_kernel<<<dim3(1), dim3(1024), 0, s>>>(flags ? reinterpret_cast<const int*>(flags) : w.flags, (int)n_patch, w.list,
+                                                          w.slot, w.count);
+            return launched("compact");
+        });
 }
 
 // ---- exact blank-patch dedup inside the one counted launch
 static size_t parts_dedup_masks(int64_t n_index) { return (size_t)cdiv(n_index, (int64_t)SCAN_ENT); }
 
-IPSX_API size_t ipsx_trunk_parts_dedup_workspace_bytes(const ipsx_trunk* t, int64_t n_index) {
-    if (!t || n_index <= 0) return 0;
-    // the scan workgroups' masks (8 B) and counts, the length, the list of the entries to encode (8 B each)
-    return parts_dedup_masks(n_index) * 12 + 256 + (size_t)n_index * 8 + 256;
-}
-
 // The four entries are one function of the source's kind.  Every refusal - the arguments, the trunk, the source (a byte
 // source without a table, misaligned bytes, a view the trunk does not read), the parts, the workspace - comes in front of the
 // scan: a refused call has written no row and no counter.
-static int encode_parts_dedup(const ipsx_trunk* t, const PatchSrc& src, bool u8, bool view, int64_t n_index, float* emb,
-                              const int64_t* part_end, int n_parts, int32_t* done, const float* blank_emb, void* workspace,
-                              size_t workspace_bytes, int32_t* n_encoded, void* stream, const char* what) {
+int encode_parts_dedup(const ipsx_trunk* t, const PatchSrc& src, bool u8, bool view, int64_t n_index, float* emb,
+                       const int64_t* part_end, int n_parts, int32_t* done, const float* blank_emb, void* workspace,
+                       size_t workspace_bytes, int32_t* n_encoded, void* stream, const char* what) {
     IPSX_REQUIRE(t && src.base && src.index && emb && part_end && done && blank_emb && (!u8 || src.table) && (!view || src.view),
                  "%s: null pointer", what);
     IPSX_REQUIRE(fused_trunk_supported(t), "%s: only the fused 1x32x32 trunk is supported", what);
@@ -542,43 +508,7 @@ static int encode_parts_dedup(const ipsx_trunk* t, const PatchSrc& src, bool u8,
     return fused_trunk_encode_parts_compact(t, src, n_index, emb, part_end, n_parts, done, clist, count, s);
 }
 
-IPSX_API int ipsx_trunk_encode_parts_dedup(const ipsx_trunk* t, const float* patches, const int32_t* index, int64_t n_index,
-                                           float* emb, const int64_t* part_end, int n_parts, int32_t* done,
-                                           const float* blank_emb, void* workspace, size_t workspace_bytes, int32_t* n_encoded,
-                                           void* stream) {
-    return encode_parts_dedup(t, PatchSrc{patches, nullptr, nullptr, index, 0}, false, false, n_index, emb, part_end, n_parts, done,
-                              blank_emb, workspace, workspace_bytes, n_encoded, stream, "trunk_encode_parts_dedup");
-}
-
-IPSX_API int ipsx_trunk_encode_parts_dedup_u8(const ipsx_trunk* t, const uint8_t* patches, const float* table, const int32_t* index,
-                                              int64_t n_index, float* emb, const int64_t* part_end, int n_parts, int32_t* done,
-                                              const float* blank_emb, void* workspace, size_t workspace_bytes,
-                                              int32_t* n_encoded, void* stream) {
-    return encode_parts_dedup(t, PatchSrc{patches, table, nullptr, index, 0}, true, false, n_index, emb, part_end, n_parts, done,
-                              blank_emb, workspace, workspace_bytes, n_encoded, stream, "trunk_encode_parts_dedup_u8");
-}
-
-IPSX_API int ipsx_trunk_encode_parts_dedup_view(const ipsx_trunk* t, const float* images, const ipsx_patch_view* v,
-                                                const int32_t* index, int64_t n_index, float* emb, const int64_t* part_end,
-                                                int n_parts, int32_t* done, const float* blank_emb, void* workspace,
-                                                size_t workspace_bytes, int32_t* n_encoded, void* stream) {
-    return encode_parts_dedup(t, PatchSrc{images, nullptr, v, index, 0}, false, true, n_index, emb, part_end, n_parts, done,
-                              blank_emb, workspace, workspace_bytes, n_encoded, stream, "trunk_encode_parts_dedup_view");
-}
-
-IPSX_API int ipsx_trunk_encode_parts_dedup_view_u8(const ipsx_trunk* t, const uint8_t* images, const float* table,
-                                                   const ipsx_patch_view* v, const int32_t* index, int64_t n_index, float* emb,
-                                                   const int64_t* part_end, int n_parts, int32_t* done, const float* blank_emb,
-                                                   void* workspace, size_t workspace_bytes, int32_t* n_encoded, void* stream) {
-    return encode_parts_dedup(t, PatchSrc{images, table, v, index, 0}, true, true, n_index, emb, part_end, n_parts, done,
-                              blank_emb, workspace, workspace_bytes, n_encoded, stream, "trunk_encode_parts_dedup_view_u8");
-}
-
 // ---- exact blank-patch dedup on a ragged view: the explicit route's shape on plain launches
-IPSX_API size_t ipsx_trunk_ragged_view_dedup_workspace_bytes(const ipsx_trunk* t, int64_t n) {
-    return ipsx_trunk_dedup_workspace_bytes(t, n);     // the same parts: flags, list, slots, the length, n + 1 compacted rows
-}
-
 // what every entry asks of the view and the list: a valid host table (checked again), a device table, 1x32x32 windows on
 // float32 pixels - or bytes (u8) -, the entries inside the packed patches (an index list: any int32 number, resolved to
 // packed patch 0)
@@ -599,40 +529,31 @@ static int ragged_dedup_list_check(const void* pixels, bool u8, const ipsx_ragge
 
 // (u8: src.base holds bytes - the scan needs no table, so src.table does not say it)
 static int ragged_blank_flags(const PatchSrc& src, bool u8, int64_t n, int32_t* nonblank, hipStream_t s) {
-    if (u8) {
-        RaggedViewArgs rv = ragged_view_args(src, {1});
-        rv.wide = ragged_view_load_width(src.base, *src.ragged, 1, {16, 4, 1});
-        blank_flags_ragged_view_u8_kernel<<<dim3((unsigned)cdiv(n, 4)), dim3(256), 0, s>>>(static_cast<const unsigned char*>(src.base),
-                                                                                           rv, n, nonblank);
-        return launched("blank_flags_ragged_view_u8");
-    }
-    blank_flags_ragged_view_kernel<<<dim3((unsigned)cdiv(n, 4)), dim3(256), 0, s>>>(static_cast<const float*>(src.base),
-                                                                                    ragged_view_args(src, 16), n, nonblank);
-    return launched("blank_flags_ragged_view");
+    RaggedViewArgs rv = ragged_view_args(src, 16);
+    if (u8) rv.wide = ragged_view_load_width(src.base, *src.ragged, 1, {16, 4, 1});
+    const dim3 grid((unsigned)cdiv(n, 4)), block(256);
+    if (u8) blank_flags_ragged_view_kernel<true><<<grid, block, 0, s>>>(src.base, rv, n, nonblank);
+    else blank_flags_ragged_view_kernel<false><<<grid, block, 0, s>>>(src.base, rv, n, nonblank);
+    return launched(u8 ? "blank_flags_ragged_view_u8" : "blank_flags_ragged_view");
 }
 
-IPSX_API int ipsx_ragged_view_blank_flags(const float* pixels, const ipsx_ragged_view* view, const int32_t* index,
-                                          int64_t first, int64_t n, int32_t* nonblank, void* stream) {
-    IPSX_TRY(ragged_dedup_list_check(pixels, false, view, index, first, n, "ragged_view_blank_flags"));
-    IPSX_REQUIRE(nonblank || n == 0, "ragged_view_blank_flags: no flags");
+// ipsx_ragged_view_blank_flags and _u8
+static int ragged_view_blank_flags(const void* pixels, bool u8, const ipsx_ragged_view* view, const int32_t* index, int64_t first,
+                                   int64_t n, int32_t* nonblank, void* stream, const char* what) {
+    IPSX_TRY(ragged_dedup_list_check(pixels, u8, view, index, first, n, what));
+    IPSX_REQUIRE(nonblank || n == 0, "%s: no flags", what);
     if (n == 0) return IPSX_OK;
-    return ragged_blank_flags(PatchSrc{pixels, nullptr, nullptr, index, index ? 0 : first, view}, false, n, nonblank, as_stream(stream));
+    return ragged_blank_flags(PatchSrc{pixels, nullptr, nullptr, index, index ? 0 : first, view}, u8, n, nonblank, as_stream(stream));
 }
 
-IPSX_API int ipsx_ragged_view_blank_flags_u8(const uint8_t* pixels, const ipsx_ragged_view* view, const int32_t* index,
-                                             int64_t first, int64_t n, int32_t* nonblank, void* stream) {
-    IPSX_TRY(ragged_dedup_list_check(pixels, true, view, index, first, n, "ragged_view_blank_flags_u8"));
-    IPSX_REQUIRE(nonblank || n == 0, "ragged_view_blank_flags_u8: no flags");
-    if (n == 0) return IPSX_OK;
-    return ragged_blank_flags(PatchSrc{pixels, nullptr, nullptr, index, index ? 0 : first, view}, true, n, nonblank, as_stream(stream));
-}
-
-// the four steps behind both entries; table: the pixels are bytes
-static int encode_ragged_view_dedup(const ipsx_trunk* t, const void* pixels, const float* table, const ipsx_ragged_view* view,
-                                    const int32_t* index, int64_t first, int64_t n, float* emb, void* workspace,
-                                    size_t workspace_bytes, int32_t* n_encoded, void* stream, const char* what) {
+// ipsx_trunk_encode_ragged_view_dedup and _u8 (u8: the pixels are bytes and the table must be there.  The ONE blank entry is
+// encoded from its image like any other - every pixel table[0] -, so no blank embedding comes in from outside)
+int encode_ragged_view_dedup(const ipsx_trunk* t, const void* pixels, const float* table, bool u8, const ipsx_ragged_view* view,
+                             const int32_t* index, int64_t first, int64_t n, float* emb, void* workspace, size_t workspace_bytes,
+                             int32_t* n_encoded, void* stream, const char* what) {
+    IPSX_REQUIRE(!u8 || table, "%s: no table", what);
     IPSX_REQUIRE(t && emb, "%s: null pointer", what);
-    IPSX_TRY(ragged_dedup_list_check(pixels, table != nullptr, view, index, first, n, what));
+    IPSX_TRY(ragged_dedup_list_check(pixels, u8, view, index, first, n, what));
     IPSX_REQUIRE(fused_trunk_supported(t) && t->precision == 0 && t->patch_dtype == 0 && t->c_in * t->h * t->w == PATCH_U4 * 4,
                  "%s: the exact fp32 fused 1x32x32 trunk only", what);
     const PatchSrc src{pixels, table, nullptr, index, index ? 0 : first, view};
@@ -643,38 +564,39 @@ static int encode_ragged_view_dedup(const ipsx_trunk* t, const void* pixels, con
     if (!workspace || workspace_bytes < need || !at_multiple(workspace, 16))
         return fail(IPSX_EWORKSPACE, "%s: workspace %zu B < %zu B (at a 16-byte address)", what, workspace_bytes, need);
     hipStream_t s = as_stream(stream);
-    int* nonblank = static_cast<int*>(workspace);
-    int* list = nonblank + n;
-    int* slot = list + n;
-    int* count = slot + n;
-    float* emb_u = reinterpret_cast<float*>(static_cast<unsigned char*>(workspace) + (((size_t)n * 12 + 4 + 255) & ~(size_t)255));
-    IPSX_TRY(ragged_blank_flags(src, table != nullptr, n, nonblank, s));
-    ragged_compact_kernel<<<dim3((unsigned)cdiv(n, 1024)), dim3(1024), 0, s>>>(nonblank, (int)n, index, src.first, list, slot, count);
-    IPSX_TRY(launched("ragged_compact"));
-    // the list holds packed patch numbers: the trunk reads it as an index list of up to n entries, *count of them written
-    IPSX_TRY(fused_launch(t, PatchSrc{pixels, table, nullptr, list, 0, view}, n, emb_u, s, count));
-    scatter_rows_kernel<<<dim3((unsigned)cdiv(n * 32, 256)), dim3(256), 0, s>>>(
-        reinterpret_cast<const float4*>(emb_u), slot, reinterpret_cast<float4*>(emb), n, 32);
-    IPSX_TRY(launched("scatter_rows"));
-    if (n_encoded && hipMemcpyAsync(n_encoded, count, sizeof(int), hipMemcpyDeviceToDevice, s) != hipSuccess)
-        return fail(IPSX_EHIP, "%s: count copy failed", what);
-    return IPSX_OK;
+    return dedup_explicit(t, src, n, emb, workspace, n_encoded, s, what,
+        [&](const DedupWork& w) { return ragged_blank_flags(src, u8, n, w.flags, s); },
+        [&](const DedupWork& w) {
+            ragged_compact_kernel<<<dim3((unsigned)cdiv(n, 1024)), dim3(1024), 0, s>>>(w.flags, (int)n, src.index, src.first, w.list,
+                                                                                       w.slot, w.count);
+            return launched("ragged_compact");
+        });
 }
 
-IPSX_API int ipsx_trunk_encode_ragged_view_dedup(const ipsx_trunk* t, const float* pixels, const ipsx_ragged_view* view,
-                                                 const int32_t* index, int64_t first, int64_t n, float* emb, void* workspace,
-                                                 size_t workspace_bytes, int32_t* n_encoded, void* stream) {
-    return encode_ragged_view_dedup(t, pixels, nullptr, view, index, first, n, emb, workspace, workspace_bytes, n_encoded, stream,
-                                    "trunk_encode_ragged_view_dedup");
+}  // namespace ipsx
+
+using namespace ipsx;
+
+IPSX_API size_t ipsx_trunk_dedup_workspace_bytes(const ipsx_trunk* t, int64_t n_patch) {
+    return t && n_patch > 0 ? dedup_layout(n_patch, nullptr, nullptr) : 0;
 }
 
-// ... on whole uint8 images: the ONE blank entry is encoded from its image like any other (every pixel table[0]), so no
-// blank embedding comes in from outside
-IPSX_API int ipsx_trunk_encode_ragged_view_dedup_u8(const ipsx_trunk* t, const uint8_t* pixels, const float* table,
-                                                    const ipsx_ragged_view* view, const int32_t* index, int64_t first, int64_t n,
-                                                    float* emb, void* workspace, size_t workspace_bytes, int32_t* n_encoded,
-                                                    void* stream) {
-    IPSX_REQUIRE(table, "trunk_encode_ragged_view_dedup_u8: no table");
-    return encode_ragged_view_dedup(t, pixels, table, view, index, first, n, emb, workspace, workspace_bytes, n_encoded, stream,
-                                    "trunk_encode_ragged_view_dedup_u8");
+IPSX_API size_t ipsx_trunk_ragged_view_dedup_workspace_bytes(const ipsx_trunk* t, int64_t n) {
+    return ipsx_trunk_dedup_workspace_bytes(t, n);     // the same route, the same parts
+}
+
+IPSX_API size_t ipsx_trunk_parts_dedup_workspace_bytes(const ipsx_trunk* t, int64_t n_index) {
+    if (!t || n_index <= 0) return 0;
+    // the scan workgroups' masks (8 B) and counts, the length, the list of the entries to encode (8 B each)
+    return parts_dedup_masks(n_index) * 12 + 256 + (size_t)n_index * 8 + 256;
+}
+
+IPSX_API int ipsx_ragged_view_blank_flags(const float* pixels, const ipsx_ragged_view* view, const int32_t* index,
+                                          int64_t first, int64_t n, int32_t* nonblank, void* stream) {
+    return ragged_view_blank_flags(pixels, false, view, index, first, n, nonblank, stream, "ragged_view_blank_flags");
+}
+
+IPSX_API int ipsx_ragged_view_blank_flags_u8(const uint8_t* pixels, const ipsx_ragged_view* view, const int32_t* index,
+                                             int64_t first, int64_t n, int32_t* nonblank, void* stream) {
+    return ragged_view_blank_flags(pixels, true, view, index, first, n, nonblank, stream, "ragged_view_blank_flags_u8");
 }

@@ -3,8 +3,6 @@
 // (reference architecture/ips_net.py:245-250).  Pure HBM-bound copy: one workgroup
 // per selected row, 16 bytes per lane when the row allows it.
 
-#include <type_traits>
-
 #include "ipsx_internal.h"
 
 namespace ipsx {
@@ -65,13 +63,15 @@ __global__ __launch_bounds__(256) void ips_finish_kernel(FinishArgs a) {
     }
 }
 
-// The end of a PADDED ragged call (IPSNet.ips_ragged(pad=True)) in ONE launch: workgroup (j, b) fills slot j of
-// slide b - patch row, positional row, slide-local index and global packed row.  The slide's length comes from the two row
-// offsets (workgroup-uniform, kept scalar as ragged_slide does).  A LONG slide (more than m rows) takes the loop's selection
-// idx[b][j], clamped into its own slide; a SHORT one is its rows in the order given - idx is not read for it, the loop left
-// that row unwritten - and zeros behind them: the padding is WRITTEN here (index and row -1), the output buffers need no
-// memset.  Packed row g is source row flat[g] of `rows` when a shuffle was applied as an index (the positional rows are in
-// packed numbering).  No read leaves [0, total); a slide whose offsets leave the table is left untouched.
+// The end of a PADDED ragged call (IPSNet.ips_ragged(pad=True), IPSNet.ips_image_ragged) in ONE launch: workgroup
+// (j, b) fills slot j of slide - or image - b: patch row, positional row, local index and global packed row.  The slot rule
+// is ragged_finish_slot below, written ONCE for the three sources (packed rows, a float32 ragged view, a uint8 one); a source
+// supplies what differs:
+//   guard(b, lo, hi, &n)   are the two row offsets this slide's, and its length n
+//   dst(slot)              where slot's row of mem_patch lies
+//   zero(d)                the padding of mem_patch
+//   copy(d, ps)            packed row / packed patch ps into mem_patch
+// The argument structs share the names the rule reads (row_off, idx, flat, total, pos, pos_units, out_pos, idx_out, rows_out, m).
 struct RaggedFinishArgs {
     const uint4* rows; long long row_units, total;
     const long long* row_off; const long long* idx; const int* flat;
@@ -80,17 +80,33 @@ struct RaggedFinishArgs {
     int m;
 };
 
-__global__ __launch_bounds__(256) void ragged_finish_kernel(RaggedFinishArgs a) {
+// ... of whole images: the source row is a grid patch copied out of its image
+struct RaggedFinishViewArgs {
+    const float* pixels; const ipsx_image_entry* images; int b, c, ph, pw, sh, sw; long long total;
+    const long long* row_off; const long long* idx; const int* flat;
+    const uint4* pos; long long pos_units;
+    float* out_patch; uint4* out_pos; long long* idx_out; long long* rows_out;
+    int m;
+};
+
+// The slide's length comes from the two row offsets (workgroup-uniform, kept scalar as ragged_slide does).  A LONG slide (more
+// than m rows) takes the loop's selection idx[b][j], clamped into its own slide; a SHORT one is its rows in the order given -
+// idx is not read for it, the loop left that row unwritten - and zeros behind them: the padding is WRITTEN here (index and
+// row -1), the output buffers need no memset.  Packed row g is source row flat[g] when a shuffle was applied as an index (the
+// positional rows are in packed numbering).  No read leaves [0, total); a slide the source's guard refuses is left untouched.
+template <class S>
+__device__ __forceinline__ void ragged_finish_slot(const S& src) {
+    const auto& a = src.a;
     const int j = blockIdx.x, b = blockIdx.y;
     const long long r0 = a.row_off[b], r1 = a.row_off[b + 1];
     const long long lo = ((long long)__builtin_amdgcn_readfirstlane((int)(r0 >> 32)) << 32) |
                          (unsigned int)__builtin_amdgcn_readfirstlane((int)r0);
     const long long hi = ((long long)__builtin_amdgcn_readfirstlane((int)(r1 >> 32)) << 32) |
                          (unsigned int)__builtin_amdgcn_readfirstlane((int)r1);
-    if (!(lo >= 0 && hi >= lo && hi <= a.total)) return;
-    const long long n = hi - lo;
+    long long n;
+    if (!src.guard(b, lo, hi, &n)) return;
     const size_t slot = (size_t)b * a.m + j;
-    uint4* d = a.out_patch + slot * a.row_units;
+    const auto d = src.dst(slot);
     uint4* dp = a.pos ? a.out_pos + slot * a.pos_units : nullptr;
     long long r;
     if (n > a.m) {
@@ -100,10 +116,9 @@ __global__ __launch_bounds__(256) void ragged_finish_kernel(RaggedFinishArgs a) 
     } else if (j < n) {
         r = j;
     } else {                                                    // the padding of a short slide
-        const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
-        for (long long i = threadIdx.x; i < a.row_units; i += 256) d[i] = zero;
+        src.zero(d);
         if (dp)
-            for (long long i = threadIdx.x; i < a.pos_units; i += 256) dp[i] = zero;
+            for (long long i = threadIdx.x; i < a.pos_units; i += 256) dp[i] = make_uint4(0u, 0u, 0u, 0u);
         if (threadIdx.x == 0) {
             a.idx_out[slot] = -1;
             a.rows_out[slot] = -1;
@@ -111,13 +126,12 @@ __global__ __launch_bounds__(256) void ragged_finish_kernel(RaggedFinishArgs a) 
         return;
     }
     const long long g = lo + r;                                 // in [lo, hi): inside the table
-    long long rs = g;
+    long long ps = g;
     if (a.flat) {
-        rs = a.flat[g];
-        rs = rs < 0 ? 0 : (rs >= a.total ? a.total - 1 : rs);
+        ps = a.flat[g];
+        ps = ps < 0 ? 0 : (ps >= a.total ? a.total - 1 : ps);
     }
-    const uint4* s = a.rows + (size_t)rs * a.row_units;
-    for (long long i = threadIdx.x; i < a.row_units; i += 256) d[i] = s[i];
+    src.copy(d, ps);
     if (dp) {
         const uint4* sp = a.pos + (size_t)g * a.pos_units;
         for (long long i = threadIdx.x; i < a.pos_units; i += 256) dp[i] = sp[i];
@@ -128,150 +142,72 @@ __global__ __launch_bounds__(256) void ragged_finish_kernel(RaggedFinishArgs a) 
     }
 }
 
-// ragged_finish_kernel with the source row replaced by a grid patch copied out of its image (IPSNet.ips_image_ragged, DESIGN
-// 2.8): workgroup (j, k) fills slot j of image k.  The image's table entry and its two row offsets are workgroup-uniform and
-// kept scalar; an image whose offsets are not its entry's (first, first + ny * nx) is left untouched.  The patch copied is
-// packed patch flat[g] (or g), resolved through the table by the function the stems use (ragged_view_offset) - a number that
-// is no packed patch reads packed patch 0, so no read leaves the packed buffer.  VW: floats per copy (4: 16-byte copies - pw,
-// every w, sw and the addresses allow them, the host's decision - or 1).
-struct RaggedFinishViewArgs {
-    const float* pixels; const ipsx_image_entry* images; int b, c, ph, pw, sh, sw; long long total;
-    const long long* row_off; const long long* idx; const int* flat;
-    const uint4* pos; long long pos_units;
-    float* out_patch; uint4* out_pos; long long* idx_out; long long* rows_out;
-    int m;
+// packed rows of 16-byte units: offsets that leave the table are refused
+struct FinishRows {
+    const RaggedFinishArgs& a;
+    __device__ __forceinline__ bool guard(int, long long lo, long long hi, long long* n) const {
+        if (!(lo >= 0 && hi >= lo && hi <= a.total)) return false;
+        *n = hi - lo;
+        return true;
+    }
+    __device__ __forceinline__ uint4* dst(size_t slot) const { return a.out_patch + slot * a.row_units; }
+    __device__ __forceinline__ void zero(uint4* d) const {
+        for (long long i = threadIdx.x; i < a.row_units; i += 256) d[i] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    __device__ __forceinline__ void copy(uint4* d, long long rs) const {
+        const uint4* s = a.rows + (size_t)rs * a.row_units;
+        for (long long i = threadIdx.x; i < a.row_units; i += 256) d[i] = s[i];
+    }
 };
 
-template <int VW>
-__global__ __launch_bounds__(256) void ragged_finish_view_kernel(RaggedFinishViewArgs a) {
-    typedef typename std::conditional<VW == 4, float4, float>::type V;
-    const int j = blockIdx.x, k = blockIdx.y;
-    const long long r0 = a.row_off[k], r1 = a.row_off[k + 1];
-    const long long lo = ((long long)__builtin_amdgcn_readfirstlane((int)(r0 >> 32)) << 32) |
-                         (unsigned int)__builtin_amdgcn_readfirstlane((int)r0);
-    const long long hi = ((long long)__builtin_amdgcn_readfirstlane((int)(r1 >> 32)) << 32) |
-                         (unsigned int)__builtin_amdgcn_readfirstlane((int)r1);
-    const ipsx_image_entry e = a.images[k];
-    const long long n = (long long)e.ny * e.nx;
-    if (!(lo >= 0 && lo == e.first && hi - lo == n && hi <= a.total)) return;
-    const size_t slot = (size_t)k * a.m + j;
-    const int rowv = a.pw / VW, units = a.c * a.ph * rowv;
-    V* d = reinterpret_cast<V*>(a.out_patch + slot * ((size_t)a.c * a.ph * a.pw));
-    uint4* dp = a.pos ? a.out_pos + slot * a.pos_units : nullptr;
-    long long r;
-    if (n > a.m) {
-        if (!a.idx) return;                                     // (a batch of short images only has no selection)
-        r = a.idx[slot];
-        r = r < 0 ? 0 : (r >= n ? n - 1 : r);                   // inside its OWN image
-    } else if (j < n) {
-        r = j;
-    } else {                                                    // the padding of a short image
+// A ragged view: the image's table entry is workgroup-uniform and kept scalar; an image whose offsets are not its entry's
+// (first, first + ny * nx) is refused.  The patch copied is packed patch ps, resolved through the table by the function the
+// stems use (ragged_view_offset) - a number that is no packed patch reads packed patch 0, so no read leaves the packed buffer.
+// VW: pixels per thread and step (4: 16-byte stores, and 16-byte or - bytes - dword loads: pw, every w, sw and the addresses
+// allow them, the host's decision - or 1).  U8: a.pixels holds bytes and mem_patch is float32 table[channel][byte] - what
+// ipsx_dequant_patches makes of the copied bytes -, the padding float +0.0, not table[channel][0]; the table (c x 256 floats)
+// is read where it lies: L2-resident, and the launch is the call's last one, not its hot one.
+template <int VW, bool U8>
+struct FinishView {
+    typedef typename TableFloats<VW>::type V;
+    const RaggedFinishViewArgs& a;
+    const float* __restrict__ table;
+    struct Dst { V* d; int rowv, units; };                           // the slot's row in units of V, rowv to a patch row
+    __device__ __forceinline__ Dst dst(size_t slot) const {
+        const int rowv = a.pw / VW;
+        return Dst{reinterpret_cast<V*>(a.out_patch + slot * ((size_t)a.c * a.ph * a.pw)), rowv, a.c * a.ph * rowv};
+    }
+    __device__ __forceinline__ bool guard(int k, long long lo, long long hi, long long* n) const {
+        const ipsx_image_entry e = a.images[k];
+        const long long len = (long long)e.ny * e.nx;
+        if (!(lo >= 0 && lo == e.first && hi - lo == len && hi <= a.total)) return false;
+        *n = len;
+        return true;
+    }
+    __device__ __forceinline__ void zero(const Dst& t) const {
         V zero;
         if constexpr (VW == 4) zero = make_float4(0.f, 0.f, 0.f, 0.f); else zero = 0.f;
-        for (int i = threadIdx.x; i < units; i += 256) d[i] = zero;
-        if (dp)
-            for (long long i = threadIdx.x; i < a.pos_units; i += 256) dp[i] = make_uint4(0u, 0u, 0u, 0u);
-        if (threadIdx.x == 0) {
-            a.idx_out[slot] = -1;
-            a.rows_out[slot] = -1;
+        for (int i = threadIdx.x; i < t.units; i += 256) t.d[i] = zero;
+    }
+    __device__ __forceinline__ void copy(const Dst& t, long long ps) const {
+        ps = (long long)__builtin_amdgcn_readfirstlane((int)ps);    // (total < 2^31; workgroup-uniform: the table is read scalar)
+        int w = a.images[0].w, h = a.images[0].h;
+        long long off = ragged_view_offset(a.images, a.b, a.sh, a.sw, ps, &w, &h);
+        if (off < 0) off = a.images[0].elem_off;
+        for (int i = threadIdx.x; i < t.units; i += 256) {
+            const int xv = i % t.rowv, u = i / t.rowv, y = u % a.ph, ch = u / a.ph;
+            const long long at = off + ((long long)ch * h + y) * w + xv * VW;
+            if constexpr (U8) t.d[i] = table_floats<VW>(table + 256 * ch, reinterpret_cast<const unsigned char*>(a.pixels) + at);
+            else t.d[i] = *reinterpret_cast<const V*>(a.pixels + at);
         }
-        return;
     }
-    const long long g = lo + r;                                 // in [lo, hi): inside the table
-    long long ps = g;
-    if (a.flat) {
-        ps = a.flat[g];
-        ps = ps < 0 ? 0 : (ps >= a.total ? a.total - 1 : ps);
-    }
-    ps = (long long)__builtin_amdgcn_readfirstlane((int)ps);    // (total < 2^31; workgroup-uniform: the table is read scalar)
-    int w = a.images[0].w, h = a.images[0].h;
-    long long off = ragged_view_offset(a.images, a.b, a.sh, a.sw, ps, &w, &h);
-    if (off < 0) off = a.images[0].elem_off;
-    const float* s = a.pixels + off;
-    for (int i = threadIdx.x; i < units; i += 256) {
-        const int xv = i % rowv, t = i / rowv, y = t % a.ph, ch = t / a.ph;
-        d[i] = *reinterpret_cast<const V*>(s + ((long long)ch * h + y) * w + xv * VW);
-    }
-    if (dp) {
-        const uint4* sp = a.pos + (size_t)g * a.pos_units;
-        for (long long i = threadIdx.x; i < a.pos_units; i += 256) dp[i] = sp[i];
-    }
-    if (threadIdx.x == 0) {
-        a.idx_out[slot] = r;
-        a.rows_out[slot] = g;
-    }
-}
+};
 
-// ragged_finish_view_kernel on whole uint8 images (ipsx_ragged_finish_view_u8): a.pixels holds bytes, mem_patch is float32
-// table[channel][byte] - what ipsx_dequant_patches makes of the copied bytes - and the padding of a short image float +0.0,
-// not table[channel][0].  VW: pixels per thread and step (4: one dword load and one 16-byte store - pw, every w, sw and the
-// addresses allow them, the host's decision - or 1).  The table (c x 256 floats) is read where it lies: L2-resident, and the
-// launch is the call's last one, not its hot one.
-template <int VW>
-__global__ __launch_bounds__(256) void ragged_finish_view_u8_kernel(RaggedFinishViewArgs a, const float* __restrict__ table) {
-    typedef typename std::conditional<VW == 4, float4, float>::type V;
-    const int j = blockIdx.x, k = blockIdx.y;
-    const long long r0 = a.row_off[k], r1 = a.row_off[k + 1];
-    const long long lo = ((long long)__builtin_amdgcn_readfirstlane((int)(r0 >> 32)) << 32) |
-                         (unsigned int)__builtin_amdgcn_readfirstlane((int)r0);
-    const long long hi = ((long long)__builtin_amdgcn_readfirstlane((int)(r1 >> 32)) << 32) |
-                         (unsigned int)__builtin_amdgcn_readfirstlane((int)r1);
-    const ipsx_image_entry e = a.images[k];
-    const long long n = (long long)e.ny * e.nx;
-    if (!(lo >= 0 && lo == e.first && hi - lo == n && hi <= a.total)) return;
-    const size_t slot = (size_t)k * a.m + j;
-    const int rowv = a.pw / VW, units = a.c * a.ph * rowv;
-    V* d = reinterpret_cast<V*>(a.out_patch + slot * ((size_t)a.c * a.ph * a.pw));
-    uint4* dp = a.pos ? a.out_pos + slot * a.pos_units : nullptr;
-    long long r;
-    if (n > a.m) {
-        if (!a.idx) return;                                     // (a batch of short images only has no selection)
-        r = a.idx[slot];
-        r = r < 0 ? 0 : (r >= n ? n - 1 : r);                   // inside its OWN image
-    } else if (j < n) {
-        r = j;
-    } else {                                                    // the padding of a short image: float zeros
-        V zero;
-        if constexpr (VW == 4) zero = make_float4(0.f, 0.f, 0.f, 0.f); else zero = 0.f;
-        for (int i = threadIdx.x; i < units; i += 256) d[i] = zero;
-        if (dp)
-            for (long long i = threadIdx.x; i < a.pos_units; i += 256) dp[i] = make_uint4(0u, 0u, 0u, 0u);
-        if (threadIdx.x == 0) {
-            a.idx_out[slot] = -1;
-            a.rows_out[slot] = -1;
-        }
-        return;
-    }
-    const long long g = lo + r;                                 // in [lo, hi): inside the table
-    long long ps = g;
-    if (a.flat) {
-        ps = a.flat[g];
-        ps = ps < 0 ? 0 : (ps >= a.total ? a.total - 1 : ps);
-    }
-    ps = (long long)__builtin_amdgcn_readfirstlane((int)ps);    // (total < 2^31; workgroup-uniform: the table is read scalar)
-    int w = a.images[0].w, h = a.images[0].h;
-    long long off = ragged_view_offset(a.images, a.b, a.sh, a.sw, ps, &w, &h);
-    if (off < 0) off = a.images[0].elem_off;
-    const unsigned char* s = reinterpret_cast<const unsigned char*>(a.pixels) + off;
-    for (int i = threadIdx.x; i < units; i += 256) {
-        const int xv = i % rowv, t = i / rowv, y = t % a.ph, ch = t / a.ph;
-        const unsigned char* q = s + ((long long)ch * h + y) * w + xv * VW;
-        const float* tc = table + 256 * ch;
-        if constexpr (VW == 4) {
-            const unsigned v = *reinterpret_cast<const unsigned*>(q);
-            d[i] = make_float4(tc[v & 0xFFu], tc[(v >> 8) & 0xFFu], tc[(v >> 16) & 0xFFu], tc[v >> 24]);
-        } else {
-            d[i] = tc[q[0]];
-        }
-    }
-    if (dp) {
-        const uint4* sp = a.pos + (size_t)g * a.pos_units;
-        for (long long i = threadIdx.x; i < a.pos_units; i += 256) dp[i] = sp[i];
-    }
-    if (threadIdx.x == 0) {
-        a.idx_out[slot] = r;
-        a.rows_out[slot] = g;
-    }
+__global__ __launch_bounds__(256) void ragged_finish_kernel(RaggedFinishArgs a) { ragged_finish_slot(FinishRows{a}); }
+
+template <int VW, bool U8>
+__global__ __launch_bounds__(256) void ragged_finish_view_kernel(RaggedFinishViewArgs a, const float* __restrict__ table) {
+    ragged_finish_slot(FinishView<VW, U8>{a, table});
 }
 
 }  // namespace ipsx
@@ -366,15 +302,15 @@ static int ragged_finish_view_impl(const void* pixels, const float* table, const
     const dim3 grid((unsigned)m, (unsigned)view->b);
     if (table) {                                           // bytes: dword loads where the view allows them, else single bytes
         if (view->pw % 4 == 0 && at_multiple(mem_patch, 16) && ragged_view_at_multiple(pixels, *view, 4, 1))
-            ragged_finish_view_u8_kernel<4><<<grid, dim3(256), 0, as_stream(stream)>>>(a, table);
+            ragged_finish_view_kernel<4, true><<<grid, dim3(256), 0, as_stream(stream)>>>(a, table);
         else
-            ragged_finish_view_u8_kernel<1><<<grid, dim3(256), 0, as_stream(stream)>>>(a, table);
+            ragged_finish_view_kernel<1, true><<<grid, dim3(256), 0, as_stream(stream)>>>(a, table);
         return launched("ragged_finish_view_u8");
     }
     if (view->pw % 4 == 0 && at_multiple(mem_patch, 16) && ragged_view_at_multiple(pixels, *view, 16))
-        ragged_finish_view_kernel<4><<<grid, dim3(256), 0, as_stream(stream)>>>(a);
+        ragged_finish_view_kernel<4, false><<<grid, dim3(256), 0, as_stream(stream)>>>(a, nullptr);
     else
-        ragged_finish_view_kernel<1><<<grid, dim3(256), 0, as_stream(stream)>>>(a);
+        ragged_finish_view_kernel<1, false><<<grid, dim3(256), 0, as_stream(stream)>>>(a, nullptr);
     return launched("ragged_finish_view");
 }
 

@@ -125,6 +125,20 @@ __device__ __forceinline__ RaggedAt ragged_at(const RaggedViewArgs& rv, long lon
     return at;
 }
 
+// uint8 pixels as float32 through their table, for the copies that hand patches back (gather.hip, patchify.hip): the VW (1
+// or 4) bytes at q - 4: one naturally aligned dword load - are tc[byte], tc = table + 256 * channel
+template <int VW> struct TableFloats { typedef float type; };
+template <> struct TableFloats<4> { typedef float4 type; };
+template <int VW>
+__device__ __forceinline__ typename TableFloats<VW>::type table_floats(const float* tc, const unsigned char* q) {
+    if constexpr (VW == 4) {
+        const unsigned v = *reinterpret_cast<const unsigned*>(q);
+        return make_float4(tc[v & 0xFFu], tc[(v >> 8) & 0xFFu], tc[(v >> 16) & 0xFFu], tc[v >> 24]);
+    } else {
+        return tc[q[0]];
+    }
+}
+
 // uint8 images: the 4 NW consecutive bytes at q (inside one image row) as NW little-endian dwords, by loads of `width` bytes
 // (launch-uniform, every load naturally aligned): ONE load of 4 NW bytes, NW dwords, or 4 NW single bytes put together -
 // the same registers whatever the width, so a kernel's staging code has one form

@@ -17,11 +17,11 @@ namespace ipsx {
 // A tensor that is read from patch k on has its base moved (`first` stays 0); only a view counts in `first`.
 struct PatchSrc {
     const void* base;
-    const float* table;
-    const ipsx_patch_view* view;
-    const int* index;
-    long long first;
-    const ipsx_ragged_view* ragged;
+    const float* table = nullptr;
+    const ipsx_patch_view* view = nullptr;
+    const int* index = nullptr;
+    long long first = 0;
+    const ipsx_ragged_view* ragged = nullptr;
 };
 
 // the source of patches k .. of this source - the remainder of a launch, a chunk, the second half of a call
@@ -150,6 +150,15 @@ int fused_trunk_encode_parts_compact(const ipsx_trunk* t, const PatchSrc& src, i
 int fused_trunk_stream(const ipsx_trunk* t, const float* patches, int64_t n, float* emb, const float* pos, const float* v_packed,
                        int r, float* logits, int32_t* ctl, int32_t* ready, int workgroups, int quad_pulls, hipStream_t s,
                        const int32_t* index = nullptr);
+// dedup.hip: what stands behind the dedup exports among the ipsx_trunk_encode* family (trunk.hip); `what`: the entry's name
+int encode_dedup(const ipsx_trunk* t, const PatchSrc& src, int64_t n_patch, const int32_t* flags, bool flagged, float* emb,
+                 void* workspace, size_t workspace_bytes, int32_t* n_encoded, void* stream);
+int encode_parts_dedup(const ipsx_trunk* t, const PatchSrc& src, bool u8, bool view, int64_t n_index, float* emb,
+                       const int64_t* part_end, int n_parts, int32_t* done, const float* blank_emb, void* workspace,
+                       size_t workspace_bytes, int32_t* n_encoded, void* stream, const char* what);
+int encode_ragged_view_dedup(const ipsx_trunk* t, const void* pixels, const float* table, bool u8, const ipsx_ragged_view* view,
+                             const int32_t* index, int64_t first, int64_t n, float* emb, void* workspace, size_t workspace_bytes,
+                             int32_t* n_encoded, void* stream, const char* what);
 // trunk.hip: a source of `n` patches against a trunk, once per entry (`what`: the entry's name in the message; `fused`:
 // fused_trunk_supported(t))
 int patch_src_check(const ipsx_trunk* t, const PatchSrc& src, int64_t n, bool fused, const char* what);

@@ -40,56 +40,41 @@ __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__
     out[e] = *reinterpret_cast<const V*>(img + src);
 }
 
-// ipsx_gather_patches_view: out[bi][j] = patch idx[bi][j] of image bi, copied out of the images - one thread per V (float or
-// float4) of the output; a patch number outside the image's grid reads patch 0
-template <typename V, int VW>
-__global__ __launch_bounds__(256) void gather_patches_view_kernel(const float* __restrict__ img, ipsx_patch_view v, int m,
-                                                                  const long long* __restrict__ idx, long long total,
-                                                                  V* __restrict__ out) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= total) return;
-    const int rowv = v.pw / VW;
-    long long r = e;
-    const int xv = (int)(r % rowv); r /= rowv;
-    const int y = (int)(r % v.ph); r /= v.ph;
-    const int c = (int)(r % v.c); r /= v.c;          // r = bi * m + j
-    const long long bi = r / m;
-    const long long per = (long long)((v.h - v.ph) / v.sh + 1) * ((v.w - v.pw) / v.sw + 1);
-    long long q = idx[r];
-    if (q < 0 || q >= per) q = 0;
-    long long off = patch_view_offset(v, bi * per + q);
-    if (off < 0) off = 0;
-    out[e] = *reinterpret_cast<const V*>(img + off + ((long long)c * v.h + y) * v.w + (long long)xv * VW);
-}
-
-// ipsx_gather_patches_view_u8: the same out of uint8 images, written as float32 through the per-channel table
-// (out = table[c][byte]) - one thread per VW bytes of a patch row (4: one dword load, 16 bytes stored; 1: any address)
-template <int VW>
-__global__ __launch_bounds__(256) void gather_patches_view_u8_kernel(const unsigned char* __restrict__ img,
-                                                                     const float* __restrict__ table, ipsx_patch_view v, int m,
-                                                                     const long long* __restrict__ idx, long long total,
-                                                                     float* __restrict__ out) {
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= total) return;
-    const int rowv = v.pw / VW;
-    long long r = e;
-    const int xv = (int)(r % rowv); r /= rowv;
-    const int y = (int)(r % v.ph); r /= v.ph;
-    const int c = (int)(r % v.c); r /= v.c;          // r = bi * m + j
-    const long long bi = r / m;
-    const long long per = (long long)((v.h - v.ph) / v.sh + 1) * ((v.w - v.pw) / v.sw + 1);
-    long long q = idx[r];
-    if (q < 0 || q >= per) q = 0;
-    long long off = patch_view_offset(v, bi * per + q);
-    if (off < 0) off = 0;
-    const unsigned char* src = img + off + ((long long)c * v.h + y) * v.w + (long long)xv * VW;
-    const float* tc = table + 256 * c;
-    if constexpr (VW == 4) {
-        const unsigned w = *reinterpret_cast<const unsigned*>(src);
-        reinterpret_cast<float4*>(out)[e] = make_float4(tc[w & 0xFFu], tc[(w >> 8) & 0xFFu], tc[(w >> 16) & 0xFFu], tc[w >> 24]);
-    } else {
-        out[e] = tc[*src];
+// ipsx_gather_patches_view / _u8: out[bi][j] = patch idx[bi][j] of image bi, copied out of the images - one thread per VW (1
+// or 4) pixels of a patch row of the output; a patch number outside the image's grid reads patch 0.  The images supply the
+// load: float32 pixels as they are (4: one 16-byte load), uint8 pixels as float32 through the per-channel table (out =
+// table[c][byte]; 4: one dword load, 16 bytes stored; 1: any address).
+struct FloatImages {
+    const float* __restrict__ px;
+    template <int VW> __device__ __forceinline__ typename TableFloats<VW>::type load(long long off, int) const {
+        return *reinterpret_cast<const typename TableFloats<VW>::type*>(px + off);
     }
+};
+struct ByteImages {
+    const unsigned char* __restrict__ px;
+    const float* __restrict__ table;
+    template <int VW> __device__ __forceinline__ typename TableFloats<VW>::type load(long long off, int c) const {
+        return table_floats<VW>(table + 256 * c, px + off);
+    }
+};
+
+template <int VW, class Images>
+__global__ __launch_bounds__(256) void gather_patches_view_kernel(Images img, ipsx_patch_view v, int m, const long long* __restrict__ idx,
+                                                                  long long total, typename TableFloats<VW>::type* __restrict__ out) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int rowv = v.pw / VW;
+    long long r = e;
+    const int xv = (int)(r % rowv); r /= rowv;
+    const int y = (int)(r % v.ph); r /= v.ph;
+    const int c = (int)(r % v.c); r /= v.c;          // r = bi * m + j
+    const long long bi = r / m;
+    const long long per = (long long)((v.h - v.ph) / v.sh + 1) * ((v.w - v.pw) / v.sw + 1);
+    long long q = idx[r];
+    if (q < 0 || q >= per) q = 0;
+    long long off = patch_view_offset(v, bi * per + q);
+    if (off < 0) off = 0;
+    out[e] = img.template load<VW>(off + ((long long)c * v.h + y) * v.w + (long long)xv * VW, c);
 }
 
 // one thread per non-zero; the image of a non-zero is found by bisection of the (B+1) offsets
@@ -181,6 +166,22 @@ IPSX_API int ipsx_patchify_sparse(const int64_t* index, const float* value, cons
     return launched("patchify_sparse");
 }
 
+// what both exports do behind their own refusals; images_at: the address multiple `images` needs for VW = 4
+template <class Images>
+static int gather_patches_view(Images img, size_t images_at, const ipsx_patch_view* v, const int64_t* idx, int m, float* out, void* stream,
+                               const char* what) {
+    const long long elems = (long long)v->b * m * v->c * v->ph * v->pw;
+    if (elems == 0) return IPSX_OK;
+    const bool v4 = v->pw % 4 == 0 && v->w % 4 == 0 && v->sw % 4 == 0 && reinterpret_cast<uintptr_t>(img.px) % images_at == 0 &&
+                    (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+    const long long* ix = reinterpret_cast<const long long*>(idx);
+    const long long total = v4 ? elems / 4 : elems;
+    const dim3 grid((unsigned)cdiv(total, 256)), block(256);
+    if (v4) gather_patches_view_kernel<4><<<grid, block, 0, as_stream(stream)>>>(img, *v, m, ix, total, reinterpret_cast<float4*>(out));
+    else gather_patches_view_kernel<1><<<grid, block, 0, as_stream(stream)>>>(img, *v, m, ix, total, out);
+    return launched(what);
+}
+
 IPSX_API int ipsx_gather_patches_view(const float* images, const ipsx_patch_view* v, const int64_t* idx, int m, float* out,
                                       void* stream) {
     IPSX_REQUIRE(images && v && idx && out && m >= 0, "gather_patches_view: bad arguments");
@@ -188,20 +189,7 @@ IPSX_API int ipsx_gather_patches_view(const float* images, const ipsx_patch_view
                  v->h, v->w, v->ph, v->pw, v->sh, v->sw);
     IPSX_REQUIRE(reinterpret_cast<uintptr_t>(images) % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0,
                  "gather_patches_view: images and out must lie at 4-byte addresses");
-    const long long elems = (long long)v->b * m * v->c * v->ph * v->pw;
-    if (elems == 0) return IPSX_OK;
-    const bool v4 = v->pw % 4 == 0 && v->w % 4 == 0 && v->sw % 4 == 0 && (reinterpret_cast<uintptr_t>(images) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-    const long long* ix = reinterpret_cast<const long long*>(idx);
-    if (v4) {
-        const long long total = elems / 4;
-        gather_patches_view_kernel<float4, 4><<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, as_stream(stream)>>>(
-            images, *v, m, ix, total, reinterpret_cast<float4*>(out));
-    } else {
-        gather_patches_view_kernel<float, 1><<<dim3((unsigned)cdiv(elems, 256)), dim3(256), 0, as_stream(stream)>>>(
-            images, *v, m, ix, elems, out);
-    }
-    return launched("gather_patches_view");
+    return gather_patches_view(FloatImages{images}, 16, v, idx, m, out, stream, "gather_patches_view");
 }
 
 IPSX_API int ipsx_gather_patches_view_u8(const uint8_t* images, const float* table, const ipsx_patch_view* v, const int64_t* idx,
@@ -211,18 +199,5 @@ IPSX_API int ipsx_gather_patches_view_u8(const uint8_t* images, const float* tab
                  v->h, v->w, v->ph, v->pw, v->sh, v->sw);
     IPSX_REQUIRE(reinterpret_cast<uintptr_t>(table) % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0,
                  "gather_patches_view_u8: table and out must lie at 4-byte addresses");
-    const long long elems = (long long)v->b * m * v->c * v->ph * v->pw;
-    if (elems == 0) return IPSX_OK;
-    const bool v4 = v->pw % 4 == 0 && v->w % 4 == 0 && v->sw % 4 == 0 && (reinterpret_cast<uintptr_t>(images) & 3) == 0 &&
-                    (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-    const long long* ix = reinterpret_cast<const long long*>(idx);
-    if (v4) {
-        const long long total = elems / 4;
-        gather_patches_view_u8_kernel<4><<<dim3((unsigned)cdiv(total, 256)), dim3(256), 0, as_stream(stream)>>>(
-            images, table, *v, m, ix, total, out);
-    } else {
-        gather_patches_view_u8_kernel<1><<<dim3((unsigned)cdiv(elems, 256)), dim3(256), 0, as_stream(stream)>>>(
-            images, table, *v, m, ix, elems, out);
-    }
-    return launched("gather_patches_view_u8");
+    return gather_patches_view(ByteImages{images, table}, 4, v, idx, m, out, stream, "gather_patches_view_u8");
 }

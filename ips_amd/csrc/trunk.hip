@@ -212,9 +212,17 @@ IPSX_API const char* ipsx_trunk_kernel(const ipsx_trunk* t) {
     return "conv_nhwc_kernel (layer by layer)";
 }
 
-// The one path behind ipsx_trunk_encode, _u8, _view and _view_u8: `n_patch` patches of `src` -> emb; only the stem's load differs
+// an export's own first refusal, where it has one: "<its name>: <text>" unless ok
+struct Need {
+    bool ok = true;
+    const char* text = "";
+};
+
+// The one path behind ipsx_trunk_encode, _view, _ragged_view and their _u8 twins: `n_patch` patches of `src` -> emb; only the
+// stem's load differs
 static int trunk_encode(const ipsx_trunk* t, const PatchSrc& src, int64_t n_patch, float* emb, void* workspace,
-                        size_t workspace_bytes, void* stream, const char* what) {
+                        size_t workspace_bytes, void* stream, const char* what, Need need = Need()) {
+    IPSX_REQUIRE(need.ok, "%s: %s", what, need.text);
     TrunkGeom g;
     IPSX_TRY(trunk_geom(t, &g));
     IPSX_REQUIRE(src.base && emb && n_patch >= 0, "%s: bad arguments", what);
@@ -328,27 +336,163 @@ static int trunk_encode(const ipsx_trunk* t, const PatchSrc& src, int64_t n_patc
     return IPSX_OK;
 }
 
+// An index list into a patch tensor, one launch of the fused trunk (ipsx_trunk_encode_indexed, _u8: the table must be there)
+static int trunk_encode_indexed(const ipsx_trunk* t, const PatchSrc& src, bool u8, int64_t n_index, float* emb, void* stream,
+                                const char* what) {
+    IPSX_REQUIRE(t && src.base && (!u8 || src.table) && src.index && emb && n_index >= 0, "%s: bad arguments", what);
+    IPSX_REQUIRE(fused_trunk_supported(t), "%s: only the fused 1x32x32 trunk is supported", what);
+    IPSX_TRY(patch_src_check(t, src, n_index, true, what));
+    if (n_index == 0) return IPSX_OK;
+    return fused_launch(t, src, n_index, emb, as_stream(stream));
+}
+
+// The counted launch (ipsx_trunk_encode_parts and its _u8 / _view / _view_u8 twins), shaped like encode_parts_dedup.  Float32
+// patches are checked by the launch alone; the view entries say more of a trunk that is not the fused one.
+static int trunk_encode_parts(const ipsx_trunk* t, const PatchSrc& src, bool u8, bool view, int64_t n_index, float* emb,
+                              const int64_t* part_end, int n_parts, int32_t* done, void* stream, const char* what) {
+    IPSX_REQUIRE(t && src.base && (!u8 || src.table) && (!view || src.view) && src.index && emb && part_end && done,
+                 "%s: null pointer", what);
+    IPSX_REQUIRE(fused_trunk_supported(t), view ? "%s: the fused fp32 1x32x32 trunk on a valid view of 1x32x32 patches only"
+                                                : "%s: only the fused 1x32x32 trunk is supported", what);
+    if (u8 || view) IPSX_TRY(patch_src_check(t, src, n_index, true, what));
+    return fused_trunk_encode_parts(t, src, n_index, emb, part_end, n_parts, done, as_stream(stream));
+}
+
+// ---- the ipsx_trunk_encode* exports, all twenty: a source and one call each.  Behind them stand trunk_encode,
+// trunk_encode_indexed and trunk_encode_parts above and, in dedup.hip, encode_parts_dedup, encode_dedup and
+// encode_ragged_view_dedup.  A view's `first` counts only without an index list.
 IPSX_API int ipsx_trunk_encode(const ipsx_trunk* t, const float* patches, int64_t n_patch, float* emb,
                                void* workspace, size_t workspace_bytes, void* stream) {
-    return trunk_encode(t, PatchSrc{patches, nullptr, nullptr, nullptr, 0}, n_patch, emb, workspace, workspace_bytes, stream,
-                        "trunk_encode");
+    return trunk_encode(t, PatchSrc{patches}, n_patch, emb, workspace, workspace_bytes, stream, "trunk_encode");
 }
 
 IPSX_API int ipsx_trunk_encode_u8(const ipsx_trunk* t, const uint8_t* patches, const float* table, int64_t n_patch, float* emb,
                                   void* workspace, size_t workspace_bytes, void* stream) {
-    IPSX_REQUIRE(table, "trunk_encode_u8: no table");
-    return trunk_encode(t, PatchSrc{patches, table, nullptr, nullptr, 0}, n_patch, emb, workspace, workspace_bytes, stream,
-                        "trunk_encode_u8");
+    return trunk_encode(t, PatchSrc{patches, table}, n_patch, emb, workspace, workspace_bytes, stream, "trunk_encode_u8",
+                        Need{table != nullptr, "no table"});
+}
+
+IPSX_API int ipsx_trunk_encode_view(const ipsx_trunk* t, const float* images, const ipsx_patch_view* v, const int32_t* index,
+                                    int64_t first, int64_t n, float* emb, void* workspace, size_t workspace_bytes, void* stream) {
+    return trunk_encode(t, PatchSrc{images, nullptr, v, index, index ? 0 : first}, n, emb, workspace, workspace_bytes, stream,
+                        "trunk_encode_view", Need{t && images && v && emb && n >= 0 && first >= 0, "bad arguments"});
+}
+
+IPSX_API int ipsx_trunk_encode_view_u8(const ipsx_trunk* t, const uint8_t* images, const float* table, const ipsx_patch_view* v,
+                                       const int32_t* index, int64_t first, int64_t n, float* emb, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    return trunk_encode(t, PatchSrc{images, table, v, index, index ? 0 : first}, n, emb, workspace, workspace_bytes, stream,
+                        "trunk_encode_view_u8", Need{t && images && table && v && emb && n >= 0 && first >= 0, "bad arguments"});
+}
+
+IPSX_API int ipsx_trunk_encode_ragged_view(const ipsx_trunk* t, const float* pixels, const ipsx_ragged_view* view,
+                                           const int32_t* index, int64_t first, int64_t n, float* emb, void* workspace,
+                                           size_t workspace_bytes, void* stream) {
+    return trunk_encode(t, PatchSrc{pixels, nullptr, nullptr, index, index ? 0 : first, view}, n, emb, workspace, workspace_bytes,
+                        stream, "trunk_encode_ragged_view", Need{t && pixels && view && emb && n >= 0 && first >= 0, "bad arguments"});
+}
+
+IPSX_API int ipsx_trunk_encode_ragged_view_u8(const ipsx_trunk* t, const uint8_t* pixels, const float* table,
+                                              const ipsx_ragged_view* view, const int32_t* index, int64_t first, int64_t n,
+                                              float* emb, void* workspace, size_t workspace_bytes, void* stream) {
+    return trunk_encode(t, PatchSrc{pixels, table, nullptr, index, index ? 0 : first, view}, n, emb, workspace, workspace_bytes,
+                        stream, "trunk_encode_ragged_view_u8",
+                        Need{t && pixels && table && view && emb && n >= 0 && first >= 0, "bad arguments"});
+}
+
+IPSX_API int ipsx_trunk_encode_indexed(const ipsx_trunk* t, const float* patches, const int32_t* index,
+                                       int64_t n_index, float* emb, void* stream) {
+    return trunk_encode_indexed(t, PatchSrc{patches, nullptr, nullptr, index}, false, n_index, emb, stream, "trunk_encode_indexed");
 }
 
 IPSX_API int ipsx_trunk_encode_indexed_u8(const ipsx_trunk* t, const uint8_t* patches, const float* table, const int32_t* index,
                                           int64_t n_index, float* emb, void* stream) {
-    IPSX_REQUIRE(t && patches && table && index && emb && n_index >= 0, "trunk_encode_indexed_u8: bad arguments");
-    IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_indexed_u8: only the fused 1x32x32 trunk is supported");
-    const PatchSrc src{patches, table, nullptr, index, 0};
-    IPSX_TRY(patch_src_check(t, src, n_index, true, "trunk_encode_indexed_u8"));
-    if (n_index == 0) return IPSX_OK;
-    return fused_launch(t, src, n_index, emb, as_stream(stream));
+    return trunk_encode_indexed(t, PatchSrc{patches, table, nullptr, index}, true, n_index, emb, stream, "trunk_encode_indexed_u8");
+}
+
+IPSX_API int ipsx_trunk_encode_parts(const ipsx_trunk* t, const float* patches, const int32_t* index, int64_t n_index,
+                                     float* emb, const int64_t* part_end, int n_parts, int32_t* done, void* stream) {
+    return trunk_encode_parts(t, PatchSrc{patches, nullptr, nullptr, index}, false, false, n_index, emb, part_end, n_parts, done,
+                              stream, "trunk_encode_parts");
+}
+
+IPSX_API int ipsx_trunk_encode_parts_u8(const ipsx_trunk* t, const uint8_t* patches, const float* table, const int32_t* index,
+                                        int64_t n_index, float* emb, const int64_t* part_end, int n_parts, int32_t* done,
+                                        void* stream) {
+    return trunk_encode_parts(t, PatchSrc{patches, table, nullptr, index}, true, false, n_index, emb, part_end, n_parts, done, stream,
+                              "trunk_encode_parts_u8");
+}
+
+IPSX_API int ipsx_trunk_encode_parts_view(const ipsx_trunk* t, const float* images, const ipsx_patch_view* v, const int32_t* index,
+                                          int64_t n_index, float* emb, const int64_t* part_end, int n_parts, int32_t* done,
+                                          void* stream) {
+    return trunk_encode_parts(t, PatchSrc{images, nullptr, v, index}, false, true, n_index, emb, part_end, n_parts, done, stream,
+                              "trunk_encode_parts_view");
+}
+
+IPSX_API int ipsx_trunk_encode_parts_view_u8(const ipsx_trunk* t, const uint8_t* images, const float* table,
+                                             const ipsx_patch_view* v, const int32_t* index, int64_t n_index, float* emb,
+                                             const int64_t* part_end, int n_parts, int32_t* done, void* stream) {
+    return trunk_encode_parts(t, PatchSrc{images, table, v, index}, true, true, n_index, emb, part_end, n_parts, done, stream,
+                              "trunk_encode_parts_view_u8");
+}
+
+IPSX_API int ipsx_trunk_encode_parts_dedup(const ipsx_trunk* t, const float* patches, const int32_t* index, int64_t n_index,
+                                           float* emb, const int64_t* part_end, int n_parts, int32_t* done,
+                                           const float* blank_emb, void* workspace, size_t workspace_bytes, int32_t* n_encoded,
+                                           void* stream) {
+    return encode_parts_dedup(t, PatchSrc{patches, nullptr, nullptr, index}, false, false, n_index, emb, part_end, n_parts, done,
+                              blank_emb, workspace, workspace_bytes, n_encoded, stream, "trunk_encode_parts_dedup");
+}
+
+IPSX_API int ipsx_trunk_encode_parts_dedup_u8(const ipsx_trunk* t, const uint8_t* patches, const float* table, const int32_t* index,
+                                              int64_t n_index, float* emb, const int64_t* part_end, int n_parts, int32_t* done,
+                                              const float* blank_emb, void* workspace, size_t workspace_bytes,
+                                              int32_t* n_encoded, void* stream) {
+    return encode_parts_dedup(t, PatchSrc{patches, table, nullptr, index}, true, false, n_index, emb, part_end, n_parts, done,
+                              blank_emb, workspace, workspace_bytes, n_encoded, stream, "trunk_encode_parts_dedup_u8");
+}
+
+IPSX_API int ipsx_trunk_encode_parts_dedup_view(const ipsx_trunk* t, const float* images, const ipsx_patch_view* v,
+                                                const int32_t* index, int64_t n_index, float* emb, const int64_t* part_end,
+                                                int n_parts, int32_t* done, const float* blank_emb, void* workspace,
+                                                size_t workspace_bytes, int32_t* n_encoded, void* stream) {
+    return encode_parts_dedup(t, PatchSrc{images, nullptr, v, index}, false, true, n_index, emb, part_end, n_parts, done,
+                              blank_emb, workspace, workspace_bytes, n_encoded, stream, "trunk_encode_parts_dedup_view");
+}
+
+IPSX_API int ipsx_trunk_encode_parts_dedup_view_u8(const ipsx_trunk* t, const uint8_t* images, const float* table,
+                                                   const ipsx_patch_view* v, const int32_t* index, int64_t n_index, float* emb,
+                                                   const int64_t* part_end, int n_parts, int32_t* done, const float* blank_emb,
+                                                   void* workspace, size_t workspace_bytes, int32_t* n_encoded, void* stream) {
+    return encode_parts_dedup(t, PatchSrc{images, table, v, index}, true, true, n_index, emb, part_end, n_parts, done,
+                              blank_emb, workspace, workspace_bytes, n_encoded, stream, "trunk_encode_parts_dedup_view_u8");
+}
+
+IPSX_API int ipsx_trunk_encode_dedup(const ipsx_trunk* t, const float* patches, int64_t n_patch, float* emb,
+                                     void* workspace, size_t workspace_bytes, int32_t* n_encoded, void* stream) {
+    return encode_dedup(t, PatchSrc{patches}, n_patch, nullptr, false, emb, workspace, workspace_bytes, n_encoded, stream);
+}
+
+IPSX_API int ipsx_trunk_encode_dedup_flagged(const ipsx_trunk* t, const float* patches, int64_t n_patch,
+                                             const int32_t* nonblank, float* emb, void* workspace,
+                                             size_t workspace_bytes, int32_t* n_encoded, void* stream) {
+    return encode_dedup(t, PatchSrc{patches}, n_patch, nonblank, true, emb, workspace, workspace_bytes, n_encoded, stream);
+}
+
+IPSX_API int ipsx_trunk_encode_ragged_view_dedup(const ipsx_trunk* t, const float* pixels, const ipsx_ragged_view* view,
+                                                 const int32_t* index, int64_t first, int64_t n, float* emb, void* workspace,
+                                                 size_t workspace_bytes, int32_t* n_encoded, void* stream) {
+    return encode_ragged_view_dedup(t, pixels, nullptr, false, view, index, first, n, emb, workspace, workspace_bytes, n_encoded,
+                                    stream, "trunk_encode_ragged_view_dedup");
+}
+
+IPSX_API int ipsx_trunk_encode_ragged_view_dedup_u8(const ipsx_trunk* t, const uint8_t* pixels, const float* table,
+                                                    const ipsx_ragged_view* view, const int32_t* index, int64_t first, int64_t n,
+                                                    float* emb, void* workspace, size_t workspace_bytes, int32_t* n_encoded,
+                                                    void* stream) {
+    return encode_ragged_view_dedup(t, pixels, table, true, view, index, first, n, emb, workspace, workspace_bytes, n_encoded, stream,
+                                    "trunk_encode_ragged_view_dedup_u8");
 }
 
 // ---- the patch-grid view (3.06): whole images in place of the patch tensor
@@ -359,13 +503,6 @@ IPSX_API int ipsx_trunk_view_supported(const ipsx_trunk* t, const ipsx_patch_vie
     if (t->precision != 0 || t->patch_dtype != 0) return 0;
     if (v->c != t->c_in || v->ph != t->h || v->pw != t->w) return 0;
     return fused_trunk_supported(t) || fused_stem_pool50_covers(t) || fused_stem_pool100x3_covers(t) ? 1 : 0;
-}
-
-IPSX_API int ipsx_trunk_encode_view(const ipsx_trunk* t, const float* images, const ipsx_patch_view* v, const int32_t* index,
-                                    int64_t first, int64_t n, float* emb, void* workspace, size_t workspace_bytes, void* stream) {
-    IPSX_REQUIRE(t && images && v && emb && n >= 0 && first >= 0, "trunk_encode_view: bad arguments");
-    return trunk_encode(t, PatchSrc{images, nullptr, v, index, index ? 0 : first}, n, emb, workspace, workspace_bytes, stream,
-                        "trunk_encode_view");
 }
 
 // ---- the ragged patch-grid view: whole images of different sizes, packed
@@ -412,50 +549,6 @@ IPSX_API int ipsx_trunk_ragged_view_supported(const ipsx_trunk* t, const ipsx_ra
     if (t->precision != 0 || t->patch_dtype != 0) return 0;
     if (view->c != t->c_in || view->ph != t->h || view->pw != t->w) return 0;
     return fused_trunk_supported(t) || fused_stem_pool50_covers(t) || fused_stem_pool100x3_covers(t) ? 1 : 0;
-}
-
-IPSX_API int ipsx_trunk_encode_ragged_view(const ipsx_trunk* t, const float* pixels, const ipsx_ragged_view* view,
-                                           const int32_t* index, int64_t first, int64_t n, float* emb, void* workspace,
-                                           size_t workspace_bytes, void* stream) {
-    IPSX_REQUIRE(t && pixels && view && emb && n >= 0 && first >= 0, "trunk_encode_ragged_view: bad arguments");
-    return trunk_encode(t, PatchSrc{pixels, nullptr, nullptr, index, index ? 0 : first, view}, n, emb, workspace, workspace_bytes,
-                        stream, "trunk_encode_ragged_view");
-}
-
-IPSX_API int ipsx_trunk_encode_ragged_view_u8(const ipsx_trunk* t, const uint8_t* pixels, const float* table,
-                                              const ipsx_ragged_view* view, const int32_t* index, int64_t first, int64_t n,
-                                              float* emb, void* workspace, size_t workspace_bytes, void* stream) {
-    IPSX_REQUIRE(t && pixels && table && view && emb && n >= 0 && first >= 0, "trunk_encode_ragged_view_u8: bad arguments");
-    return trunk_encode(t, PatchSrc{pixels, table, nullptr, index, index ? 0 : first, view}, n, emb, workspace, workspace_bytes,
-                        stream, "trunk_encode_ragged_view_u8");
-}
-
-IPSX_API int ipsx_trunk_encode_parts_view(const ipsx_trunk* t, const float* images, const ipsx_patch_view* v, const int32_t* index,
-                                          int64_t n_index, float* emb, const int64_t* part_end, int n_parts, int32_t* done,
-                                          void* stream) {
-    IPSX_REQUIRE(t && images && v && index && emb && part_end && done, "trunk_encode_parts_view: null pointer");
-    IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_parts_view: the fused fp32 1x32x32 trunk on a valid view of 1x32x32 patches only");
-    const PatchSrc src{images, nullptr, v, index, 0};
-    IPSX_TRY(patch_src_check(t, src, n_index, true, "trunk_encode_parts_view"));
-    return fused_trunk_encode_parts(t, src, n_index, emb, part_end, n_parts, done, as_stream(stream));
-}
-
-IPSX_API int ipsx_trunk_encode_parts_view_u8(const ipsx_trunk* t, const uint8_t* images, const float* table,
-                                             const ipsx_patch_view* v, const int32_t* index, int64_t n_index, float* emb,
-                                             const int64_t* part_end, int n_parts, int32_t* done, void* stream) {
-    IPSX_REQUIRE(t && images && table && v && index && emb && part_end && done, "trunk_encode_parts_view_u8: null pointer");
-    IPSX_REQUIRE(fused_trunk_supported(t), "trunk_encode_parts_view_u8: the fused fp32 1x32x32 trunk on a valid view of 1x32x32 patches only");
-    const PatchSrc src{images, table, v, index, 0};
-    IPSX_TRY(patch_src_check(t, src, n_index, true, "trunk_encode_parts_view_u8"));
-    return fused_trunk_encode_parts(t, src, n_index, emb, part_end, n_parts, done, as_stream(stream));
-}
-
-IPSX_API int ipsx_trunk_encode_view_u8(const ipsx_trunk* t, const uint8_t* images, const float* table, const ipsx_patch_view* v,
-                                       const int32_t* index, int64_t first, int64_t n, float* emb, void* workspace,
-                                       size_t workspace_bytes, void* stream) {
-    IPSX_REQUIRE(t && images && table && v && emb && n >= 0 && first >= 0, "trunk_encode_view_u8: bad arguments");
-    return trunk_encode(t, PatchSrc{images, table, v, index, index ? 0 : first}, n, emb, workspace, workspace_bytes, stream,
-                        "trunk_encode_view_u8");
 }
 
 // One image: trunk AND logits of its patches as ONE persistent launch that feeds ipsx_scan_persistent patch by patch

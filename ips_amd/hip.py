@@ -619,6 +619,15 @@ def _patch_table(table, n_chan, device):
     return table if table.is_contiguous() else table.contiguous()
 
 
+def _call_twin(name, head, table, tail, u8=None):
+    """The one rule of the float32 / uint8 twin exports: ``name(*head, *tail)`` on float32 storage, and on uint8 storage
+    (``u8``; default: there is a ``table``) the ``_u8`` twin, whose ``table`` - where it takes one - stands behind the base
+    pointer, the last of ``head``."""
+    if (table is not None) if u8 is None else u8:
+        name, head = name + "_u8", head + ((_p(table),) if table is not None else ())
+    _ck(getattr(lib(), name)(*head, *tail), name)
+
+
 def _patches(t, table=None):
     """Patch tensors may be stored in bfloat16 / float16 (BASELINE configs[4]); only the reduced-precision fused trunks
     read those (the exact path's contract is float32 in).  uint8 patches go with a ``table`` (n_chan, 256) on the exact
@@ -1578,6 +1587,30 @@ def ragged_finish_supported(rows, pos):
     return rows is not None and (pos is None or (pos.dim() == 2 and pos.shape[0] == rows.shape[0] and pos.device == rows.device))
 
 
+def _finish_args(name, what, unit, dev, offsets, B, M, total, mem_idx, flat, pos, pos_refusal, patch, out):
+    """What ``ragged_finish`` and ``ragged_finish_view`` (``name``) ask alike of the (B + 1,) ``offsets`` (``unit``: "row",
+    "patch"), ``mem_idx``, ``flat`` and ``out`` on the device ``dev`` of the ``what`` ("rows", "pixels"); ``pos_refusal``: what
+    the caller has against ``pos``, said in its place; ``patch`` = (shape, dtype) of ``mem_patch`` -> the four result
+    tensors, ``out`` or fresh ones."""
+    if offsets.dtype != torch.int64 or tuple(offsets.shape) != (B + 1,) or B < 1 or not offsets.is_contiguous() or offsets.device != dev:
+        raise ValueError("{} needs the (B + 1,) int64 {} offsets on the {}' device".format(name, unit, what))
+    if mem_idx is not None and (mem_idx.dtype != torch.int64 or tuple(mem_idx.shape) != (B, M) or not mem_idx.is_contiguous()
+                                or mem_idx.device != dev):
+        raise ValueError("mem_idx must be a contiguous ({}, {}) int64 tensor on the {}' device".format(B, M, what))
+    if flat is not None and (flat.dtype != torch.int32 or tuple(flat.shape) != (total,) or not flat.is_contiguous() or flat.device != dev):
+        raise ValueError("flat must be a contiguous ({},) int32 tensor on the {}' device".format(total, what))
+    if pos_refusal is not None:
+        raise ValueError(pos_refusal)
+    shapes = patch, ((B, M, pos.shape[1]), pos.dtype) if pos is not None else None, ((B, M), torch.int64), ((B, M), torch.int64)
+    if out is None:
+        return tuple(torch.empty(s[0], dtype=s[1], device=dev) if s is not None else None for s in shapes)
+    for t, s in zip(out, shapes):
+        if (t is None) != (s is None) or (t is not None and (tuple(t.shape) != s[0] or t.dtype != s[1] or not t.is_contiguous()
+                                                              or t.device != dev)):
+            raise ValueError("{}: out must be the four contiguous result tensors on the {}' device".format(name, what))
+    return out
+
+
 def ragged_finish(rows, offsets, mem_idx, M, flat=None, pos=None, out=None):
     """The end of ``IPSNet.ips_ragged(pad=True)``, ONE launch (``ipsx_ragged_finish``).  ``rows`` (total, ...) the packed rows
     of the B slides, ``offsets`` (B + 1,) int64 on their device, ``mem_idx`` (B, M) int64 slide-local as ``scan_ragged``
@@ -1590,23 +1623,8 @@ def ragged_finish(rows, offsets, mem_idx, M, flat=None, pos=None, out=None):
     if not ragged_finish_supported(rows, pos):
         raise ValueError("ragged_finish needs packed device rows of whole 16-byte units at 16-byte addresses")
     total, B = rows.shape[0], offsets.numel() - 1
-    if offsets.dtype != torch.int64 or offsets.dim() != 1 or B < 1 or not offsets.is_contiguous() or offsets.device != rows.device:
-        raise ValueError("ragged_finish needs the (B + 1,) int64 row offsets on the rows' device")
-    if mem_idx is not None and (mem_idx.dtype != torch.int64 or tuple(mem_idx.shape) != (B, M) or not mem_idx.is_contiguous()
-                                or mem_idx.device != rows.device):
-        raise ValueError("mem_idx must be a contiguous ({}, {}) int64 tensor on the rows' device".format(B, M))
-    if flat is not None and (flat.dtype != torch.int32 or tuple(flat.shape) != (total,) or not flat.is_contiguous()
-                             or flat.device != rows.device):
-        raise ValueError("flat must be a contiguous ({},) int32 tensor on the rows' device".format(total))
-    shapes = ((B, M) + tuple(rows.shape[1:]), rows.dtype), ((B, M, pos.shape[1]), pos.dtype) if pos is not None else None, \
-        ((B, M), torch.int64), ((B, M), torch.int64)
-    if out is None:
-        out = tuple(torch.empty(s[0], dtype=s[1], device=rows.device) if s is not None else None for s in shapes)
-    for t, s in zip(out, shapes):
-        if (t is None) != (s is None) or (t is not None and (tuple(t.shape) != s[0] or t.dtype != s[1] or not t.is_contiguous()
-                                                              or t.device != rows.device)):
-            raise ValueError("ragged_finish: out must be the four contiguous result tensors on the rows' device")
-    out, out_pos, idx, grow = out
+    out, out_pos, idx, grow = _finish_args("ragged_finish", "rows", "row", rows.device, offsets, B, M, total, mem_idx, flat, pos, None,
+                                           ((B, M) + tuple(rows.shape[1:]), rows.dtype), out)
     _ck(lib().ipsx_ragged_finish(_p(rows), rows[0].numel() * rows.element_size(), total, _p(offsets), _p(mem_idx), _p(flat), _p(pos),
                                  pos.shape[1] * pos.element_size() if pos is not None else 0, B, M, _p(out), _p(out_pos), _p(idx),
                                  _p(grow), _stream()), "ipsx_ragged_finish")
@@ -1629,34 +1647,16 @@ def ragged_finish_view(pixels, rview, offsets, mem_idx, M, flat=None, pos=None, 
         table = _patch_table(table, rview.patch_shape[0], dev)
     elif pixels.dtype != torch.float32 or pixels.dim() != 1 or not pixels.is_contiguous() or not on_device(pixels):
         raise ValueError("ragged_finish_view needs the packed 1-d float32 buffer on the GPU")
-    if offsets.dtype != torch.int64 or tuple(offsets.shape) != (B + 1,) or not offsets.is_contiguous() or offsets.device != dev:
-        raise ValueError("ragged_finish_view needs the (B + 1,) int64 patch offsets on the pixels' device")
-    if mem_idx is not None and (mem_idx.dtype != torch.int64 or tuple(mem_idx.shape) != (B, M) or not mem_idx.is_contiguous()
-                                or mem_idx.device != dev):
-        raise ValueError("mem_idx must be a contiguous ({}, {}) int64 tensor on the pixels' device".format(B, M))
-    if flat is not None and (flat.dtype != torch.int32 or tuple(flat.shape) != (total,) or not flat.is_contiguous() or flat.device != dev):
-        raise ValueError("flat must be a contiguous ({},) int32 tensor on the pixels' device".format(total))
-    if pos is not None and (pos.dim() != 2 or pos.shape[0] != total or not pos.is_contiguous() or pos.device != dev
-                            or (pos.shape[1] * pos.element_size()) % 16 or pos.data_ptr() % 16):
-        raise ValueError("pos must be ({}, D) contiguous rows of whole 16-byte units on the pixels' device".format(total))
+    bad_pos = pos is not None and (pos.dim() != 2 or pos.shape[0] != total or not pos.is_contiguous() or pos.device != dev
+                                   or (pos.shape[1] * pos.element_size()) % 16 or pos.data_ptr() % 16)
+    out, out_pos, idx, grow = _finish_args(
+        "ragged_finish_view", "pixels", "patch", dev, offsets, B, M, total, mem_idx, flat, pos,
+        "pos must be ({}, D) contiguous rows of whole 16-byte units on the pixels' device".format(total) if bad_pos else None,
+        ((B, M) + rview.patch_shape, torch.float32), out)
     rview.on(dev)
-    shapes = ((B, M) + rview.patch_shape, torch.float32), ((B, M, pos.shape[1]), pos.dtype) if pos is not None else None, \
-        ((B, M), torch.int64), ((B, M), torch.int64)
-    if out is None:
-        out = tuple(torch.empty(s[0], dtype=s[1], device=dev) if s is not None else None for s in shapes)
-    for t, s in zip(out, shapes):
-        if (t is None) != (s is None) or (t is not None and (tuple(t.shape) != s[0] or t.dtype != s[1] or not t.is_contiguous()
-                                                              or t.device != dev)):
-            raise ValueError("ragged_finish_view: out must be the four contiguous result tensors on the pixels' device")
-    out, out_pos, idx, grow = out
-    if table is not None:
-        _ck(lib().ipsx_ragged_finish_view_u8(_p(pixels), _p(table), C.byref(rview.struct), _p(offsets), _p(mem_idx), M, _p(flat),
-                                             _p(pos), pos.shape[1] * pos.element_size() if pos is not None else 0, _p(out),
-                                             _p(out_pos), _p(idx), _p(grow), _stream()), "ipsx_ragged_finish_view_u8")
-        return out, out_pos, idx, grow
-    _ck(lib().ipsx_ragged_finish_view(_p(pixels), C.byref(rview.struct), _p(offsets), _p(mem_idx), M, _p(flat), _p(pos),
-                                      pos.shape[1] * pos.element_size() if pos is not None else 0, _p(out), _p(out_pos), _p(idx),
-                                      _p(grow), _stream()), "ipsx_ragged_finish_view")
+    _call_twin("ipsx_ragged_finish_view", (_p(pixels),), table,
+               (C.byref(rview.struct), _p(offsets), _p(mem_idx), M, _p(flat), _p(pos),
+                pos.shape[1] * pos.element_size() if pos is not None else 0, _p(out), _p(out_pos), _p(idx), _p(grow), _stream()))
     return out, out_pos, idx, grow
 
 
@@ -1680,12 +1680,8 @@ def ragged_blank_flags(pixels, rview, index=None, first=0, n=None):
         raise ValueError("patches {} .. {} of a view of {}".format(first, first + n, rview.count))
     rview.on(pixels.device)
     out = torch.empty((n,), dtype=torch.int32, device=pixels.device)
-    if u8:
-        _ck(lib().ipsx_ragged_view_blank_flags_u8(_p(pixels), C.byref(rview.struct), _p(index), first, n, _p(out), _stream()),
-            "ipsx_ragged_view_blank_flags_u8")
-        return out
-    _ck(lib().ipsx_ragged_view_blank_flags(_p(pixels), C.byref(rview.struct), _p(index), first, n, _p(out), _stream()),
-        "ipsx_ragged_view_blank_flags")
+    _call_twin("ipsx_ragged_view_blank_flags", (_p(pixels),), None, (C.byref(rview.struct), _p(index), first, n, _p(out), _stream()),
+               u8=u8)                                   # (no table: the rule reads bytes)
     return out
 
 
@@ -1906,11 +1902,7 @@ def gather_patches_view(images, view, idx, table=None):
     out = torch.empty((idx.shape[0], M) + view.patch_shape, dtype=torch.float32, device=images.device)
     if table is not None:
         table = _patch_table(table, images.shape[-3], images.device)
-        _ck(lib().ipsx_gather_patches_view_u8(_p(images), _p(table), C.byref(view.struct), _p(idx), M, _p(out), _stream()),
-            "ipsx_gather_patches_view_u8")
-        return out
-    _ck(lib().ipsx_gather_patches_view(_p(images), C.byref(view.struct), _p(idx), M, _p(out), _stream()),
-        "ipsx_gather_patches_view")
+    _call_twin("ipsx_gather_patches_view", (_p(images),), table, (C.byref(view.struct), _p(idx), M, _p(out), _stream()))
     return out
 
 

@@ -9,7 +9,7 @@ import os
 
 import torch
 
-from .hip import (lib, _ck, _p, _f32, _stream, _patches, PatchSource, PatchView, _PATCH_DTYPES, Conv, Block, Trunk, precision, dedup_blank, weights_generation)
+from .hip import (lib, _ck, _call_twin, _p, _f32, _stream, _patches, PatchSource, PatchView, _PATCH_DTYPES, Conv, Block, Trunk, precision, dedup_blank, weights_generation)
 
 
 # ------------------------------------------------------------------ encoder plan
@@ -290,10 +290,7 @@ class EncoderPlan:
             words = torch.zeros((2,), dtype=torch.int32, device=dev)       # the list [0] | the part's counter
             out = torch.empty((1, self.d_out), dtype=torch.float32, device=dev)
             tr, tail = C.byref(self._describe(zero.shape, 0)), (_p(words[0:1]), 1, _p(out), (C.c_int64 * 1)(1), 1, _p(words[1:2]), _stream())
-            if tab is None:
-                _ck(lib().ipsx_trunk_encode_parts(tr, _p(zero), *tail), "ipsx_trunk_encode_parts")
-            else:
-                _ck(lib().ipsx_trunk_encode_parts_u8(tr, _p(zero), _p(tab), *tail), "ipsx_trunk_encode_parts_u8")
+            _call_twin("ipsx_trunk_encode_parts", (tr, _p(zero)), tab, tail)
             ready = (torch.cuda.current_stream(dev), torch.cuda.Event())
             ready[1].record()
             held = self._blank[kind] = (out, ready, tab, None if tab is None else tab._version)
@@ -353,16 +350,16 @@ class EncoderPlan:
                 raise ValueError("this encoder's stem takes no index list (EncoderPlan.index_list_supported)")
             src = PatchSource(images=src.patches.view(-1, *src.shape[-3:]), view=view, table=src.table)
         tr, vs = C.byref(t), C.byref(src.view.struct) if src.is_view else None
-        tab, base = _p(src.table), src.base
+        # Every export of the family is name(trunk, base, [table,] ...): the storage's rule (_call_twin) picks the _u8 twin and
+        # puts the table behind the base pointer; the view's struct, where there is one, leads what follows
+        tab, base = src.table, src.base
         if parts is not None:
-            if index is None or not (src.dtype == torch.float32 or (src.dtype == torch.uint8 and tab.value)):
+            if index is None or not (src.dtype == torch.float32 or (src.dtype == torch.uint8 and tab is not None)):
                 raise TypeError("parts=(part_end, done) take float32 patches, or uint8 patches with their table, and the "
                                 "parts' index lists")
             ends, done = (C.c_int64 * len(parts[0]))(*parts[0]), _p(parts[1])
-            # the four storage kinds differ in the export's suffix and in what follows the base pointer: the table, the view
-            kind = ("_view" if vs is not None else "") + ("_u8" if tab.value else "")
-            args = (tr, _p(base)) + ((tab,) if tab.value else ()) + ((vs,) if vs is not None else ()) + \
-                   (_p(index), n, _p(out), ends, len(ends), done)
+            kind = "_view" if vs is not None else ""
+            args = ((vs,) if vs is not None else ()) + (_p(index), n, _p(out), ends, len(ends), done)
             if dedup:
                 # exact blank-patch dedup inside the launch: the blank embedding of this weight state (bytes: and of this
                 # table) goes in front
@@ -371,54 +368,34 @@ class EncoderPlan:
                 nb = L.ipsx_trunk_parts_dedup_workspace_bytes(tr, n)
                 if self.n_encoded is None or self.n_encoded.device != src.device:
                     self.n_encoded = torch.zeros((), dtype=torch.int32, device=src.device)
-                name = "ipsx_trunk_encode_parts_dedup" + kind
-                _ck(getattr(L, name)(*args, _p(blank), _p(self._workspace(nb, src.device)), nb, _p(self.n_encoded), _stream()), name)
+                _call_twin("ipsx_trunk_encode_parts_dedup" + kind, (tr, _p(base)), tab,
+                           args + (_p(blank), _p(self._workspace(nb, src.device)), nb, _p(self.n_encoded), _stream()))
             else:
-                name = "ipsx_trunk_encode_parts" + kind
-                _ck(getattr(L, name)(*args, _stream()), name)
+                _call_twin("ipsx_trunk_encode_parts" + kind, (tr, _p(base)), tab, args + (_stream(),))
             return out
         if index is not None and vs is None and rv is None:    # a patch tensor through an index list: the fused trunk
-            if tab.value:
-                _ck(L.ipsx_trunk_encode_indexed_u8(tr, _p(base), tab, _p(index), n, _p(out), _stream()), "ipsx_trunk_encode_indexed_u8")
-            else:
-                _ck(L.ipsx_trunk_encode_indexed(tr, _p(base), _p(index), n, _p(out), _stream()), "ipsx_trunk_encode_indexed")
+            _call_twin("ipsx_trunk_encode_indexed", (tr, _p(base)), tab, (_p(index), n, _p(out), _stream()))
             return out
         if rv is not None and dedup:                           # the explicit dedup route through the ragged view
             nb = L.ipsx_trunk_ragged_view_dedup_workspace_bytes(tr, n)
             if self.n_encoded is None or self.n_encoded.device != src.device:
                 self.n_encoded = torch.zeros((), dtype=torch.int32, device=src.device)
-            tail = (rv, _p(index), first, n, _p(out), _p(self._workspace(nb, src.device)), nb, _p(self.n_encoded), _stream())
-            if tab.value:                                  # whole uint8 images: the ONE blank entry is read from its image
-                _ck(L.ipsx_trunk_encode_ragged_view_dedup_u8(tr, _p(base), tab, *tail), "ipsx_trunk_encode_ragged_view_dedup_u8")
-            else:
-                _ck(L.ipsx_trunk_encode_ragged_view_dedup(tr, _p(base), *tail), "ipsx_trunk_encode_ragged_view_dedup")
+            # (whole uint8 images: the ONE blank entry is read from its image)
+            _call_twin("ipsx_trunk_encode_ragged_view_dedup", (tr, _p(base)), tab,
+                       (rv, _p(index), first, n, _p(out), _p(self._workspace(nb, src.device)), nb, _p(self.n_encoded), _stream()))
             return out
         flat = base if vs is not None or rv is not None else base.view(-1, *src.shape[-3:])
 
         def run(lo, cnt, ws, nb):
             """Patches lo .. lo + cnt of the call - the library's own rule for "the source from patch lo on": the index is
             advanced, else the view's first patch, else the tensor."""
-            outs = _p(out[lo:lo + cnt])
-            if rv is not None:                             # images of different sizes: index and first count packed patches
+            tail = (cnt, _p(out[lo:lo + cnt]), _p(ws), nb, _stream())
+            if rv is not None or vs is not None:           # whole images (of different sizes: index and first count packed patches)
                 ix, lo1 = (_p(index[lo:]), 0) if index is not None else (None, first + lo)
-                if tab.value:                              # whole uint8 images
-                    _ck(L.ipsx_trunk_encode_ragged_view_u8(tr, _p(flat), tab, rv, ix, lo1, cnt, outs, _p(ws), nb, _stream()),
-                        "ipsx_trunk_encode_ragged_view_u8")
-                else:
-                    _ck(L.ipsx_trunk_encode_ragged_view(tr, _p(flat), rv, ix, lo1, cnt, outs, _p(ws), nb, _stream()),
-                        "ipsx_trunk_encode_ragged_view")
-            elif vs is not None:
-                ix, lo1 = (_p(index[lo:]), 0) if index is not None else (None, first + lo)
-                if tab.value:                              # whole uint8 images
-                    _ck(L.ipsx_trunk_encode_view_u8(tr, _p(flat), tab, vs, ix, lo1, cnt, outs, _p(ws), nb, _stream()),
-                        "ipsx_trunk_encode_view_u8")
-                else:
-                    _ck(L.ipsx_trunk_encode_view(tr, _p(flat), vs, ix, lo1, cnt, outs, _p(ws), nb, _stream()),
-                        "ipsx_trunk_encode_view")
-            elif tab.value:
-                _ck(L.ipsx_trunk_encode_u8(tr, _p(flat[first + lo:]), tab, cnt, outs, _p(ws), nb, _stream()), "ipsx_trunk_encode_u8")
+                name, grid = ("ipsx_trunk_encode_ragged_view", rv) if rv is not None else ("ipsx_trunk_encode_view", vs)
+                _call_twin(name, (tr, _p(flat)), tab, (grid, ix, lo1) + tail)
             else:
-                _ck(L.ipsx_trunk_encode(tr, _p(flat[first + lo:]), cnt, outs, _p(ws), nb, _stream()), "ipsx_trunk_encode")
+                _call_twin("ipsx_trunk_encode", (tr, _p(flat[first + lo:])), tab, tail)
 
         # Layer-by-layer trunks: the batch goes through in two halves on two streams.  The stem and the max-pool are
         # HBM-bound (together 11-13 % of the trunk's time for 1 % of its arithmetic), the residual stages MFMA-bound:
