@@ -134,7 +134,10 @@ extern "C" {
  *         through an ipsx_ragged_view, no patch tensor exists (an addition, the minor number stays);
  *         ipsx_scan_range_logits, ipsx_scan_logits_check (+ struct ipsx_logits_part) - a range of the selection loop whose
  *         launch computes its own logits in a prologue (8 heads x 4 tokens, m = i = 64), and the conditional redo of a counted
- *         call inside its last part's launch (additions, the minor number stays) */
+ *         call inside its last part's launch (additions, the minor number stays);
+ *         ipsx_scan_range_logits_gate - ipsx_scan_range_logits handed over on the device between two streams: a word per
+ *         image published at a launch's end and waited for behind the next launch's prologue, the result in a buffer of its
+ *         own (an addition, the minor number stays) */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -789,6 +792,23 @@ int ipsx_scan_range_logits(float* logits, int b, int64_t n, int m, int i, int h,
                            int64_t* mem_idx, float* mem_score, int32_t* tie_flag, const ipsx_logits_part* parts, int n_parts,
                            int part_begin, int part_end, int d, const float* pos, int64_t pos_bstride, const float* v_packed,
                            const int32_t* redo, int32_t redo_mask, void* stream);
+/* ipsx_scan_range_logits between two launches on DIFFERENT streams with no stream wait between them: the same arguments, and
+ *   gate_publish (b int32, or NULL): at its very end workgroup k stores it_end to gate_publish[k], behind its stores of
+ *            mem_idx / mem_score / tie_flag (an agent-scope release in front of the word);
+ *   gate, gate_target (b int32 zeroed by the caller before either launch, or NULL and 0): behind its prologue - the rows of its
+ *            parts, which need nothing of the other stream - workgroup k waits until gate[k] >= gate_target (it_begin or later),
+ *            then runs its iterations.  A wait that sees no progress of its word for ipsx_set_persistent_wait_ms sets status_bit
+ *            in *status and does in its workgroup what redo does: every part's rows, the iterations [0, it_end).  With redo set
+ *            on entry the (bounded) wait comes first;
+ *   mem_out  (b, m) int64 other than mem_idx, or NULL: the final indices go there and mem_idx is only read - a launch that
+ *            gave up may have a late launch of the other stream writing mem_idx behind it.
+ * A gate without its target, or without status and status_bit: IPSX_EINVAL.  Always the one launch (ipsx_dbg_scan_logits is
+ * not consulted). */
+int ipsx_scan_range_logits_gate(float* logits, int b, int64_t n, int m, int i, int h, int n_token, int64_t it_begin, int64_t it_end,
+                                int64_t* mem_idx, float* mem_score, int32_t* tie_flag, const ipsx_logits_part* parts, int n_parts,
+                                int part_begin, int part_end, int d, const float* pos, int64_t pos_bstride, const float* v_packed,
+                                const int32_t* redo, int32_t redo_mask, const int32_t* gate, int32_t gate_target,
+                                int32_t* gate_publish, int32_t* status, int32_t status_bit, int64_t* mem_out, void* stream);
 /* ipsx_logits for rows [0, n) and, in the SAME launch, the LayerNorm row moments (ipsx_projector_stats) of stats_n rows
  * of stats_x - the next slab the projector is about to take: two short latency-bound launches of a slab-by-slab producer
  * of ipsx_scan_persistent as one. */

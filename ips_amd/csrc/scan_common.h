@@ -1146,6 +1146,16 @@ struct ScanLogits {
     int d, kgs, n_parts, part0, part1;     // the parts of this launch: [part0, part1)
 };
 
+// The hand-over between two launches of scan_mnist_kernel on different streams (its third kernel parameter; see the kernel).
+// Every member may be null / zero on its own: a launch that only publishes, one that only waits, one that does neither.
+struct ScanGate {
+    const int* wait; int target;           // poll wait[b] until it has reached `target` (the iteration the loop resumes from), or nullptr
+    int* publish;                          // publish[b] = it1 behind the workgroup's last stores, or nullptr
+    int* status; int bit;                  // a wait that gave up sets `bit` in *status (and redoes the call in its workgroup)
+    long long* out;                        // (b, m): the final memory indices go here instead of mem_idx, or nullptr
+    unsigned long long wait_ticks;         // longest wait WITHOUT progress of the word, in 100 MHz ticks (ipsx_set_persistent_wait_ms)
+};
+
 // the slide table as the kernels read it: the C ABI's int64_t is the kernels' `long long` (as mem_idx is) - the same 64 bits
 // under two names, converted here and nowhere else
 inline const long long* slide_entries(const ScanCall& c) {
@@ -1166,6 +1176,7 @@ int launch_scan_cam(const ScanCall& c);                                    // sc
 bool scan_mnist_shape(int m, int i, int h, int n_token);                   // scan_mnist.hip: BASELINE configs[1] / [2]'s shape
 int launch_scan_mnist(const ScanCall& c);                                  // scan_mnist.hip
 int launch_scan_mnist_logits(const ScanCall& c, const ScanLogits& p);      // scan_mnist.hip: the same with the logits prologue
+int launch_scan_mnist_gate(const ScanCall& c, const ScanLogits& p, const ScanGate& g);   // scan_mnist.hip: ... and a gate
 size_t scan_large_ws_per_image(int m, int i, int h, int n_token);          // scan_large.hip
 int launch_scan_large(const ScanCall& c);                                  // scan_large.hip
 int scan_large_team(int b, int m, int i, int h, int n_token);              // scan_large.hip: workgroups per image (1: no team)

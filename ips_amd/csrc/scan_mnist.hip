@@ -70,14 +70,68 @@ __device__ __forceinline__ float quad_bcast(float v) {
 // parts and runs the loop from iteration 0 - what three conditional logits launches and a conditional loop launch did.
 // The arguments of the prologue are a second kernel parameter that only a PRO instantiation has (P...): the others keep
 // their one-parameter shape and their code (tools/asm_compare.py; PRO in front keeps the order of their mangled names).
+//
+// GATE (a third parameter, ScanGate, behind the prologue's): the two ends of a hand-over between two launches of one call
+// that lie on different streams with no stream wait between them (Selection.parts_loop_logits).
+//   publish  the launch in front - the side stream's last - stores the iteration it reached, it1, to publish[b] at its very
+//            end, behind its workgroup's stores of mem_idx / mem_score / tie: parts_count's hand-over (fused_trunk_eight.h).
+//   wait     the launch behind - the call's last, enqueued on the main stream directly behind the trunk - writes its parts'
+//            rows FIRST, beside the other launch's last iterations, and only then polls wait[b] until it has reached `target`
+//            (relaxed agent-scope loads, a sleep between them, one agent-scope acquire behind the barrier that tells the
+//            workgroup): stream order makes the one word per image enough - when the side's last launch has ended for image
+//            b, every earlier side-stream kernel of the call has ended.  A wait that sees no progress of its word for
+//            wait_ticks gives up: it sets `bit` in *status, as a part wait does, and does what `redo` makes it do - every
+//            part's rows, the loop from iteration 0.
+//   out      the final memory indices go here instead of mem_idx: a launch that gave up may still have a late side-stream
+//            launch writing the working buffer behind it.
+// Without the prologue (scan_mnist_kernel<false, false, ScanGate>) the parameter is the kernel's second and only `publish` is
+// looked at: the side stream's last loop launch behind a long part's logits launch, at the plain instance's registers.
+// With `redo` set on entry the wait comes FIRST (still bounded): the rows a side-stream launch wrote from embeddings that
+// were not there yet must not land behind the ones this launch writes.  (A part wait cannot give up after the trunk's end -
+// its counter is full by then, and a wait that starts later passes at once - so the word this launch reads at its start,
+// behind the trunk in stream order, is final as far as part waits go.)
+// The wait side of ScanGate (see scan_mnist_kernel), by the whole workgroup: wave 0 polls wait[b] until it has reached the target -
+// part_wait_kernel's form: relaxed agent-scope loads, a sleep between them, bounded WITHOUT PROGRESS of the word -, a barrier
+// tells the others, ONE agent-scope acquire orders every wave's loads behind the poll.  -> reached (workgroup-uniform, scalar).
+__device__ __forceinline__ bool gate_reached(const ScanGate& g, int b, int* flag) {
+    if (threadIdx.x < 64) {
+        unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+        int last = __hip_atomic_load(g.wait + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        int ok = 1;
+        while (last < g.target) {
+            __builtin_amdgcn_s_sleep(8);
+            const int v = __hip_atomic_load(g.wait + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const unsigned long long t = __builtin_amdgcn_s_memrealtime();
+            if (v != last) { last = v; t0 = t; }
+            else if (t - t0 > g.wait_ticks) { ok = 0; break; }
+        }
+        if (threadIdx.x == 0) *flag = ok;
+    }
+    lds_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    const int ok = __builtin_amdgcn_readfirstlane(*flag);
+    lds_barrier();                                               // (the flag is read before anybody writes it again)
+    return ok != 0;
+}
+
+template <typename A, typename... B>
+__device__ __forceinline__ const A& first_of(const A& a0, const B&...) { return a0; }
+
+template <typename A>
+__device__ __forceinline__ const A& last_of(const A& a0) { return a0; }
+template <typename A, typename... B>
+__device__ __forceinline__ const auto& last_of(const A&, const B&... rest) { return last_of(rest...); }
+
 template <bool PRO, bool PERSIST, typename... P>
 __global__ __launch_bounds__(mn::NT) void scan_mnist_kernel(ScanArgs a, P... p) {
     using namespace mn;
-    static_assert(sizeof...(P) == (PRO ? 1 : 0) && !(PRO && PERSIST), "scan_mnist_kernel: the prologue's arguments, plain launches only");
+    constexpr bool GATE = sizeof...(P) == (PRO ? 2 : 1);        // (without the prologue: a launch that publishes, and nothing else)
+    static_assert((sizeof...(P) == (PRO ? 1 : 0) || GATE) && !((PRO || GATE) && PERSIST),
+                  "scan_mnist_kernel: the prologue's arguments (and the gate's behind them), plain launches only");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     if (!PERSIST && scan_skipped(a.cond, a.cond_mask)) return;
     if constexpr (PRO) {
-        const ScanLogits& q = (p, ...);
+        const ScanLogits& q = first_of(p...);
         int k0 = q.part0, k1 = q.part1;
         // (the word is the same for every lane: through readfirstlane, so that it0 and everything the iterations derive from it
         //  stay in scalar registers as in the other instantiations)
@@ -85,18 +139,37 @@ __global__ __launch_bounds__(mn::NT) void scan_mnist_kernel(ScanArgs a, P... p) 
         if (q.redo != nullptr)
             redo = __builtin_amdgcn_readfirstlane(__hip_atomic_load(q.redo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & q.redo_mask);
         if (redo != 0) { k0 = 0; k1 = q.n_parts; a.it0 = 0; }
+        int s0 = 0, s1 = 0;                                       // GATE: the parts whose rows are written already (second pass)
+        if constexpr (GATE) {
+            const ScanGate& g = last_of(p...);
+            if (g.wait != nullptr && redo != 0 && !gate_reached(g, (int)blockIdx.x, reinterpret_cast<int*>(smem + OFF_CNT)) && threadIdx.x == 0)
+                __hip_atomic_fetch_or(g.status, g.bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        for (;;) {                                                // (GATE: a second pass when the wait gave up)
 #pragma unroll 1
-        for (int k = k0; k < k1; ++k) {
-            LogitsArgs la;                                        // part k: (b, rows, d) embeddings of the rows first .. first + rows
-            la.emb = q.part[k].emb; la.emb_bs = (long long)q.part[k].rows * q.d;
-            la.pos = q.pos ? q.pos + (size_t)q.part[k].first * q.d : nullptr; la.pos_bs = q.pos_bs;
-            la.vp = q.vp; la.n = q.part[k].rows; la.d = q.d; la.R = R; la.kgs = q.kgs;
-            la.out = q.out + (size_t)q.part[k].first * R; la.out_bs = a.n * R;
-            if (q.pos) {                                          // (workgroup-uniform, known in front of the loads)
-                for (unsigned bx = 0; (long long)bx * (NT / 2) < la.n; ++bx) logits_wave<1, 4, NT / 64, 1>(la, bx, (int)blockIdx.x);
-            } else {
-                for (unsigned bx = 0; (long long)bx * (NT / 2) < la.n; ++bx) logits_wave<1, 4, NT / 64, -1>(la, bx, (int)blockIdx.x);
+            for (int k = k0; k < k1; ++k) {
+                if (GATE && k >= s0 && k < s1) continue;
+                LogitsArgs la;                                    // part k: (b, rows, d) embeddings of the rows first .. first + rows
+                la.emb = q.part[k].emb; la.emb_bs = (long long)q.part[k].rows * q.d;
+                la.pos = q.pos ? q.pos + (size_t)q.part[k].first * q.d : nullptr; la.pos_bs = q.pos_bs;
+                la.vp = q.vp; la.n = q.part[k].rows; la.d = q.d; la.R = R; la.kgs = q.kgs;
+                la.out = q.out + (size_t)q.part[k].first * R; la.out_bs = a.n * R;
+                if (q.pos) {                                      // (workgroup-uniform, known in front of the loads)
+                    for (unsigned bx = 0; (long long)bx * (NT / 2) < la.n; ++bx) logits_wave<1, 4, NT / 64, 1>(la, bx, (int)blockIdx.x);
+                } else {
+                    for (unsigned bx = 0; (long long)bx * (NT / 2) < la.n; ++bx) logits_wave<1, 4, NT / 64, -1>(la, bx, (int)blockIdx.x);
+                }
             }
+            if constexpr (GATE) {
+                const ScanGate& g = last_of(p...);
+                if (g.wait != nullptr && redo == 0 && !gate_reached(g, (int)blockIdx.x, reinterpret_cast<int*>(smem + OFF_CNT))) {
+                    // gave up: the redo, in this workgroup alone (workgroup-uniform): the other parts' rows, the loop from 0
+                    if (threadIdx.x == 0) __hip_atomic_fetch_or(g.status, g.bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    redo = 1; s0 = k0; s1 = k1; k0 = 0; k1 = q.n_parts; a.it0 = 0;
+                    continue;
+                }
+            }
+            break;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");  // every row is written before the barrier below ...
     }
@@ -361,12 +434,31 @@ __global__ __launch_bounds__(mn::NT) void scan_mnist_kernel(ScanArgs a, P... p) 
     {
         const int parn = (int)(n_iter & 1);                       // the set the last iteration wrote
         const int* const cand = reinterpret_cast<const int*>(smem + OFF_CAND) + parn * L;
+        long long* dst = a.mem_idx;
+        if constexpr (GATE) {
+            const ScanGate& g = last_of(p...);
+            if (g.out != nullptr) dst = g.out;
+        }
         if (tid < M) {
-            a.mem_idx[(size_t)b * M + tid] = cand[tid];
+            dst[(size_t)b * M + tid] = cand[tid];
             if (a.mem_score) a.mem_score[(size_t)b * M + tid] = n_iter > 0 ? key_score(sorted[tid]) : 0.0f;
         }
     }
     if (a.tie && tid == 0 && tie) a.tie[b] = 1;
+    if constexpr (GATE) {
+        const ScanGate& g = last_of(p...);
+        if (g.publish != nullptr) {
+            // parts_count's hand-over: the storing wavefronts drain their stores, the workgroup meets, one thread releases at
+            // agent scope, waits for the write-back, and only then stores the word
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            if (tid == 0) {
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __hip_atomic_store(g.publish + b, (int)a.it1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
 }
 
 bool scan_mnist_shape(int m, int i, int h, int n_token) { return h == mn::H && n_token == mn::T && m == mn::M && i == mn::I; }
@@ -391,6 +483,23 @@ int launch_scan_mnist_logits(const ScanCall& c, const ScanLogits& p) {
     a.stk_off = mn::OFF_STK;
     launch_lds(scan_mnist_kernel<true, false, ScanLogits>, dim3((unsigned)c.b), dim3(mn::NT), mn::LDS_BYTES, c.stream, a, p);
     return launched("scan_logits");
+}
+
+// ... and with the gate's arguments (scorer.hip: ipsx_scan_range_logits_gate has checked them)
+int launch_scan_mnist_gate(const ScanCall& c, const ScanLogits& p, const ScanGate& g) {
+    IPSX_REQUIRE(scan_mnist_shape(c.m, c.i, c.h, c.n_token) && c.rows == Rows::Packed && !c.ready && !c.cond && c.workgroups <= 0,
+                 "scan_mnist_kernel with logits: 8 heads x 4 tokens, M = I = 64, packed logits, a plain launch of one workgroup per image");
+    ScanArgs a;
+    fill_scan_args(a, c);
+    a.stk_off = mn::OFF_STK;
+    // a launch that only publishes - no rows of its own, no redo, no wait, no buffer of its own: the side stream's last loop launch
+    // behind a long part's logits launch - is the plain instance with the gate's parameter: none of the prologue's registers
+    // (tools/scan_loop_time.py: the loop alone at the plain instance's time per iteration)
+    if (p.part0 == p.part1 && !p.redo && !g.wait && !g.out)
+        launch_lds(scan_mnist_kernel<false, false, ScanGate>, dim3((unsigned)c.b), dim3(mn::NT), mn::LDS_BYTES, c.stream, a, g);
+    else
+        launch_lds(scan_mnist_kernel<true, false, ScanLogits, ScanGate>, dim3((unsigned)c.b), dim3(mn::NT), mn::LDS_BYTES, c.stream, a, p, g);
+    return launched("scan_logits_gate");
 }
 
 }  // namespace ipsx

@@ -370,10 +370,10 @@ IPSX_API int ipsx_scan_logits_check(const ipsx_logits_part* parts, int n_parts, 
     return IPSX_OK;
 }
 
-IPSX_API int ipsx_scan_range_logits(float* logits, int b, int64_t n, int m, int i, int h, int n_token, int64_t it_begin, int64_t it_end,
-                                    int64_t* mem_idx, float* mem_score, int32_t* tie_flag, const ipsx_logits_part* parts, int n_parts,
-                                    int part_begin, int part_end, int d, const float* pos, int64_t pos_bstride, const float* v_packed,
-                                    const int32_t* redo, int32_t redo_mask, void* stream) {
+// the checks the two entry points share: the tensors, the shape, the part table and the two ranges
+static int scan_logits_checked(float* logits, int b, int64_t n, int m, int i, int h, int n_token, int64_t it_begin, int64_t it_end,
+                               int64_t* mem_idx, const ipsx_logits_part* parts, int n_parts, int part_begin, int part_end, int d,
+                               const float* pos, int64_t pos_bstride, const float* v_packed, const int32_t* redo, int32_t redo_mask) {
     IPSX_REQUIRE(logits && mem_idx && v_packed && b > 0, "scan_range_logits: null pointer");
     IPSX_REQUIRE(scan_mnist_shape(m, i, h, n_token), "scan_range_logits: 8 heads x 4 tokens, M = I = 64 (scan_mnist_kernel) only");
     IPSX_REQUIRE(d > 0 && d % 8 == 0, "scan_range_logits: embeddings of whole 8-float groups (d = %d)", d);
@@ -383,6 +383,25 @@ IPSX_API int ipsx_scan_range_logits(float* logits, int b, int64_t n, int m, int 
         IPSX_REQUIRE(parts[k].emb && (reinterpret_cast<uintptr_t>(parts[k].emb) & 15) == 0, "scan_range_logits: part %d's embeddings at a 16-byte address", k);
     IPSX_REQUIRE((reinterpret_cast<uintptr_t>(v_packed) & 15) == 0 && (reinterpret_cast<uintptr_t>(pos) & 15) == 0 && pos_bstride >= 0 &&
                  pos_bstride % 4 == 0, "scan_range_logits: the folded query and the positional table at 16-byte addresses");
+    return IPSX_OK;
+}
+
+// the prologue's arguments of a checked call
+static ScanLogits scan_logits_table(float* logits, const ipsx_logits_part* parts, int n_parts, int part_begin, int part_end, int d,
+                                    const float* pos, int64_t pos_bstride, const float* v_packed, const int32_t* redo, int32_t redo_mask) {
+    ScanLogits p = {};
+    for (int k = 0; k < n_parts; ++k) { p.part[k].emb = parts[k].emb; p.part[k].rows = (int)parts[k].rows; p.part[k].first = (int)parts[k].first; }
+    p.pos = pos; p.pos_bs = pos_bstride; p.vp = v_packed; p.out = logits; p.redo = redo; p.redo_mask = redo_mask;
+    p.d = d; p.kgs = d / 8; p.n_parts = n_parts; p.part0 = part_begin; p.part1 = part_end;
+    return p;
+}
+
+IPSX_API int ipsx_scan_range_logits(float* logits, int b, int64_t n, int m, int i, int h, int n_token, int64_t it_begin, int64_t it_end,
+                                    int64_t* mem_idx, float* mem_score, int32_t* tie_flag, const ipsx_logits_part* parts, int n_parts,
+                                    int part_begin, int part_end, int d, const float* pos, int64_t pos_bstride, const float* v_packed,
+                                    const int32_t* redo, int32_t redo_mask, void* stream) {
+    IPSX_TRY(scan_logits_checked(logits, b, n, m, i, h, n_token, it_begin, it_end, mem_idx, parts, n_parts, part_begin, part_end, d, pos,
+                                 pos_bstride, v_packed, redo, redo_mask));
     const int r = h * n_token;
     if (!g_scan_logits) {
         // the launches this entry point replaces, one by one (tests, A/B): the parts' logits and the range; with a redo word,
@@ -401,11 +420,36 @@ IPSX_API int ipsx_scan_range_logits(float* logits, int b, int64_t n, int m, int 
     ScanCall c = scan_call(logits, b, n, m, i, h, n_token, mem_idx, mem_score, tie_flag, stream);
     c.it_begin = it_begin; c.it_end = it_end;
     IPSX_TRY(validate_scan_call(c));
-    ScanLogits p = {};
-    for (int k = 0; k < n_parts; ++k) { p.part[k].emb = parts[k].emb; p.part[k].rows = (int)parts[k].rows; p.part[k].first = (int)parts[k].first; }
-    p.pos = pos; p.pos_bs = pos_bstride; p.vp = v_packed; p.out = logits; p.redo = redo; p.redo_mask = redo_mask;
-    p.d = d; p.kgs = d / 8; p.n_parts = n_parts; p.part0 = part_begin; p.part1 = part_end;
-    return launch_scan_mnist_logits(c, p);
+    return launch_scan_mnist_logits(c, scan_logits_table(logits, parts, n_parts, part_begin, part_end, d, pos, pos_bstride, v_packed, redo, redo_mask));
+}
+
+// ipsx_scan_range_logits with the hand-over between two launches on different streams (ScanGate, scan_mnist.hip): the launch
+// waits on the device for gate[k] >= gate_target behind its prologue, stores it_end to gate_publish[k] at its end, writes
+// its final indices to mem_out - each of the three on its own or not at all.  Always scan_mnist_kernel's one launch: the
+// launches ipsx_dbg_scan_logits(0) puts in its place have no such hand-over.
+IPSX_API int ipsx_scan_range_logits_gate(float* logits, int b, int64_t n, int m, int i, int h, int n_token, int64_t it_begin,
+                                         int64_t it_end, int64_t* mem_idx, float* mem_score, int32_t* tie_flag,
+                                         const ipsx_logits_part* parts, int n_parts, int part_begin, int part_end, int d, const float* pos,
+                                         int64_t pos_bstride, const float* v_packed, const int32_t* redo, int32_t redo_mask,
+                                         const int32_t* gate, int32_t gate_target, int32_t* gate_publish, int32_t* status,
+                                         int32_t status_bit, int64_t* mem_out, void* stream) {
+    IPSX_TRY(scan_logits_checked(logits, b, n, m, i, h, n_token, it_begin, it_end, mem_idx, parts, n_parts, part_begin, part_end, d, pos,
+                                 pos_bstride, v_packed, redo, redo_mask));
+    IPSX_REQUIRE(gate ? gate_target > 0 && gate_target >= it_begin : gate_target == 0,
+                 "scan_range_logits_gate: a gate goes with its target, the iteration the range resumes from or a later one (target %d, range from %lld)",
+                 (int)gate_target, (long long)it_begin);
+    IPSX_REQUIRE(gate ? status && status_bit : !status == !status_bit,
+                 "scan_range_logits_gate: a gate needs the status word and a bit for a wait that gives up");
+    IPSX_REQUIRE(it_end < ((int64_t)1 << 31), "scan_range_logits_gate: the iteration published is a 32-bit word");
+    IPSX_REQUIRE(!mem_out || mem_out != mem_idx, "scan_range_logits_gate: mem_out is a buffer of its own");
+    ScanCall c = scan_call(logits, b, n, m, i, h, n_token, mem_idx, mem_score, tie_flag, stream);
+    c.it_begin = it_begin; c.it_end = it_end;
+    IPSX_TRY(validate_scan_call(c));
+    ScanGate g = {};
+    g.wait = gate; g.target = gate_target; g.publish = gate_publish; g.status = status; g.bit = status_bit;
+    g.out = reinterpret_cast<long long*>(mem_out);
+    g.wait_ticks = (unsigned long long)g_persist_wait_ms * 100000ull;
+    return launch_scan_mnist_gate(c, scan_logits_table(logits, parts, n_parts, part_begin, part_end, d, pos, pos_bstride, v_packed, redo, redo_mask), g);
 }
 
 IPSX_API int ipsx_set_persistent_wait_ms(int ms) {

@@ -391,6 +391,10 @@ _EXPORTS = {
     "ipsx_scan_range_logits": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ipsx_scan_range_logits_gate": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                              C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                              C.c_int32, C.c_void_p, C.c_void_p]),
     "ipsx_logits_if": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int,
                                  C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]),
     "ipsx_trunk_encode_u8": (C.c_int, [C.POINTER(Trunk), C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
@@ -914,15 +918,22 @@ class LogitsParts:
         _ck(lib().ipsx_scan_logits_check(self.array, len(self), part_begin, part_end, self.n, M, I, it_begin, it_end),
             "ipsx_scan_logits_check")
 
-    def scan_range(self, logits, M, I, H, T, it_begin, it_end, mem_idx, tie, part_begin, part_end, pos, vq, redo=None, mask=1):
+    def scan_range(self, logits, M, I, H, T, it_begin, it_end, mem_idx, tie, part_begin, part_end, pos, vq, redo=None, mask=1,
+                   gate=None, gate_publish=None, status=None, out=None):
         """``logits(self.embs[k], pos rows of part k, vq)`` for k in [part_begin, part_end) into the (B, N, H*T) table ``logits``
         and ``scan_range(logits, ..., it_begin, it_end, ...)`` as ONE launch, bit for bit (``ipsx_scan_range_logits``:
         ``scan_mnist_kernel``'s shape only - ``scan_mnist_shape`` - and D % 8 == 0).  ``pos``: (B or 1, >= N, D) positional rows of
         WHOLE images, or None.  ``redo`` (int32 device scalar): with a bit of ``mask`` set in it, all parts and the iterations
         [0, it_end) - the call's conditional redo inside this launch.  ``dbg_scan_logits(False)`` makes the library enqueue the
-        launches this replaces instead."""
-        _same_gpu("scan_range_logits", ("logits", "mem_idx", "tie", "pos", "vq", "redo") + ("emb",) * len(self), logits, mem_idx, tie, pos, vq,
-                  redo, *self.embs)
+        launches this replaces instead.
+
+        The hand-over between two such launches on different streams (``ipsx_scan_range_logits_gate``), each on its own or
+        together: ``gate_publish`` (B int32 words): workgroup b stores ``it_end`` there at its end; ``gate`` (the same words,
+        zeroed before either launch) with ``status`` (int32 device scalar): behind its prologue workgroup b waits on the device
+        until ``gate[b] >= it_begin`` - a wait without progress for ``persistent_wait_ms`` sets bit ``mask`` in ``status`` and
+        redoes the call in that workgroup; ``out`` (B, M) int64: the final indices go there, ``mem_idx`` is only read."""
+        _same_gpu("scan_range_logits", ("logits", "mem_idx", "tie", "pos", "vq", "redo", "gate", "gate_publish", "status", "out") +
+                  ("emb",) * len(self), logits, mem_idx, tie, pos, vq, redo, gate, gate_publish, status, out, *self.embs)
         lg, B, N = _scan_args("scan_range_logits", logits, M, I, H, T, mem_idx, tie, None, False)
         D = self.embs[0].shape[2]
         for k, e in enumerate(self.embs):
@@ -945,10 +956,24 @@ class LogitsParts:
                 pos_bs = pos.stride(0) if ps[0] > 1 else 0
         if redo is not None:
             _word("scan_range_logits", "redo", redo)
-        _ck(lib().ipsx_scan_range_logits(_p(lg), B, N, M, I, H, T, it_begin, it_end, _p(mem_idx), None, _p(tie), self.array, len(self),
-                                         part_begin, part_end, D, _p(pos), pos_bs, _p(vq), _p(redo), mask if redo is not None else 0,
-                                         _stream()), "ipsx_scan_range_logits")
-        return mem_idx
+        if gate is None and gate_publish is None and status is None and out is None:
+            _ck(lib().ipsx_scan_range_logits(_p(lg), B, N, M, I, H, T, it_begin, it_end, _p(mem_idx), None, _p(tie), self.array, len(self),
+                                             part_begin, part_end, D, _p(pos), pos_bs, _p(vq), _p(redo), mask if redo is not None else 0,
+                                             _stream()), "ipsx_scan_range_logits")
+            return mem_idx
+        for name, t in (("gate", gate), ("gate_publish", gate_publish)):
+            if t is not None:
+                _word("scan_range_logits", name, t, B)
+        if status is not None:
+            _word("scan_range_logits", "status", status)
+        if out is not None and (out.dtype != torch.int64 or out.shape != (B, M) or not out.is_contiguous() or out.data_ptr() == mem_idx.data_ptr()):
+            raise ValueError("scan_range_logits: out must be a contiguous ({}, {}) int64 tensor other than mem_idx, got {} {}".format(
+                B, M, out.dtype, tuple(out.shape)))
+        _ck(lib().ipsx_scan_range_logits_gate(_p(lg), B, N, M, I, H, T, it_begin, it_end, _p(mem_idx), None, _p(tie), self.array, len(self),
+                                              part_begin, part_end, D, _p(pos), pos_bs, _p(vq), _p(redo), mask if redo is not None else 0,
+                                              _p(gate), it_begin if gate is not None else 0, _p(gate_publish), _p(status),
+                                              mask if status is not None else 0, _p(out), _stream()), "ipsx_scan_range_logits_gate")
+        return mem_idx if out is None else out
 
 
 def scan_range_strided(lg, n, M, I, H, T, it_begin, it_end, mem_idx, tie, workspace=None):

@@ -69,6 +69,11 @@ NATIVE_ORDER_DEFAULT = "0"
 # floor of ~5 us and little more: level at ~150 rows, measured to pay at 125 (19.0 -> 18.0 us) and to lose at 375 (43.1 -> 49.7 us;
 # DESIGN 5.4, profiles/scan_logits_trace.txt).  128 = one 32-row tile per SIMD of the workgroup's compute unit.
 SCAN_LOGITS_ROWS_DEFAULT = "128"
+# IPSX_SCAN_TAIL_ROWS when the environment does not set it: the most rows per image the trailing parts of a counted call may
+# hold together to go into ONE last launch behind the trunk's, let go by a device-side gate (``Selection.parts_loop_logits``,
+# DESIGN 5.4).  Its prologue - 4.3 us per 100 rows - runs beside the side stream's last iterations and has to end before they
+# do.  IPSX_SCAN_TAIL=0: the chain as it was.
+SCAN_TAIL_ROWS_DEFAULT = "512"
 
 # IPSX_ONE_LAUNCH_U8 when the environment does not set it.  Off: the rule was "faster than the parent's uint8 median by more
 # than the parent's own max - min on all three shapes".  16 x 1600x1600 uint8 images met it twice (stride 32: 0.48 / 0.49 ms
@@ -105,6 +110,7 @@ class Selection:
         self.scan_status_host = None
         self._mirror_pending = None
         self._unfinished = None
+        self._side_pending = self._side_event = None     # the event behind the last counted call's side-stream kernels, while no main-stream wait has covered them
         self.caller_finishes = False               # IPSNet._call: the call ends in ``finish`` / ``take_unfinished`` + ``after_call``
         self._done = None                          # (mem_idx, mem_patch, mem_pos) of a call the library enqueued whole
         self._calls = {}                           # hip.IpsCall structures, per pipeline
@@ -161,6 +167,7 @@ class Selection:
     def streams(self, dev):
         if self._side is None or self._side.device != torch.device(dev):
             self._side = hip.side_stream(dev)      # (one per device and process, high priority: hip.side_stream)
+            self._side_pending = self._side_event = None
         return self._side, torch.cuda.current_stream(dev)
 
     def buffers(self, name, key, make):
@@ -771,9 +778,17 @@ class Selection:
             "parts1", (B, N, M, I, R, P, str(dev)),
             lambda: (torch.empty((B, N, R), dtype=torch.float32, device=dev),
                      torch.empty((B, M), dtype=torch.int64, device=dev),
-                     torch.zeros((-(-(B + P + 1) // 4) * 4,), dtype=torch.int32, device=dev),   # tie flags | counters | status
+                     torch.zeros((-(-(2 * B + P + 1) // 4) * 4,), dtype=torch.int32, device=dev),   # tie flags | counters | status | gate
                      hip.scan_workspace(B, M, I, ca.H, ca.n_token, dev)))
-        tie, done, status = words[:B], words[B:B + P], words[B + P:B + P + 1]
+        tie, done, status, gate = words[:B], words[B:B + P], words[B + P:B + P + 1], words[B + P + 1:2 * B + P + 1]
+        if self._side_pending is not None:
+            # the last call's final launch did not wait for the side stream (``parts_loop_logits``: a device-side gate instead):
+            # its side-stream kernels come in front of this fill.  They are long done when the caller has synchronised in
+            # between - the host sees that, and no hand-over between the two queues (measured: 20 - 30 us in front of the fill)
+            # is enqueued; calls back to back wait for the event, beside the last call's end
+            if not self._side_pending.query():
+                main.wait_event(self._side_pending)
+            self._side_pending = None
         words.zero_()
         zeroed = torch.cuda.Event()
         zeroed.record(main)
@@ -786,7 +801,7 @@ class Selection:
         net._emb_parts = parts = [emb_all[starts[k]:ends[k]].view(B, edges[k + 1] - edges[k], -1) for k in range(P)]
         if self.scan_logits_ok(vq, M, I, ca, net.D):
             return self.parts_loop_logits(src, parts, its, pos_enc if net.use_pos else None, vq, logits, mem_idx_buf, tie, done, status,
-                                          [ends[k] - starts[k] for k in range(P)], zeroed, scan_ws)
+                                          [ends[k] - starts[k] for k in range(P)], zeroed, scan_ws, gate)
         pos = [pos_enc[:, edges[k]:edges[k + 1]] if net.use_pos else None for k in range(P)]
         with torch.cuda.stream(side):
             side.wait_event(zeroed)                # (previous readers of the buffers are done, the counters are zero)
@@ -812,7 +827,7 @@ class Selection:
         embeddings of whole 8-float groups, and not switched off (``hip.dbg_scan_logits``, ``IPSX_SCAN_LOGITS=0``)."""
         return (vq.dtype == torch.float32 and D % 8 == 0 and hip.scan_mnist_shape(M, I, ca.H, ca.n_token) and hip.scan_logits_on())
 
-    def parts_loop_logits(self, src, parts, its, pos, vq, logits, mem_idx_buf, tie, done, status, counts, zeroed, scan_ws=None):
+    def parts_loop_logits(self, src, parts, its, pos, vq, logits, mem_idx_buf, tie, done, status, counts, zeroed, scan_ws=None, gate=None):
         """What ``parts_one_launch`` enqueues behind the trunk launch at ``scan_mnist_kernel``'s shape: per part
         a wait, the part's logits and its iterations on the side stream, as before - a part of at most ``SCAN_LOGITS_ROWS``
         rows per image without a logits launch: workgroup b of the loop's launch writes image b's logits of the part itself
@@ -829,35 +844,76 @@ class Selection:
         limit = self.SCAN_LOGITS_ROWS
         R = ca.H * ca.n_token
 
-        def part(k, redo=None):
+        def part(k, redo=None, publish=None):
             if table.rows[k] <= limit:
-                table.scan_range(logits, M, I, ca.H, ca.n_token, its[k], its[k + 1], mem_idx_buf, tie, k, k + 1, pos, vq, redo=redo)
+                table.scan_range(logits, M, I, ca.H, ca.n_token, its[k], its[k + 1], mem_idx_buf, tie, k, k + 1, pos, vq, redo=redo,
+                                 gate_publish=publish)
                 return
             # a long part: its logits on the whole device, then the loop's launch - the plain one (the kernels of the chain
             # this replaces), or, where it carries the redo, the prologue's instance with no rows of its own
             lo = table.first[k]
             hip.logits(parts[k], pos[:, lo:lo + table.rows[k]] if pos is not None else None, vq, R, out=logits[:, lo:lo + table.rows[k]])
-            if redo is None:
+            if redo is None and publish is None:
                 hip.scan_range(logits, M, I, ca.H, ca.n_token, its[k], its[k + 1], mem_idx_buf, tie, scan_ws)
             else:
-                table.scan_range(logits, M, I, ca.H, ca.n_token, its[k], its[k + 1], mem_idx_buf, tie, k + 1, k + 1, pos, vq, redo=redo)
+                table.scan_range(logits, M, I, ca.H, ca.n_token, its[k], its[k + 1], mem_idx_buf, tie, k + 1, k + 1, pos, vq, redo=redo,
+                                 gate_publish=publish)
 
+        k_tail = P
+        if gate is not None and self.scan_tail_on(logits.shape[0] * logits.shape[1], logits.device):
+            k_tail = self.tail_parts(table.rows, int(os.environ.get("IPSX_SCAN_TAIL_ROWS", SCAN_TAIL_ROWS_DEFAULT)))
         with torch.cuda.stream(side):
             side.wait_event(zeroed)                # (previous readers of the buffers are done, the counters are zero)
-            for k in range(P - 1):
+            for k in range(min(k_tail, P - 1)):
                 hip.part_wait(done[k:k + 1], counts[k], status)
-                part(k)
-        main.wait_stream(side)
-        # behind the trunk launch every embedding is there: what the redo reads
-        part(P - 1, redo=status)
+                part(k, publish=gate if k == k_tail - 1 else None)
+        result = mem_idx_buf
+        if k_tail < P:
+            # The trailing parts [k_tail, P) as ONE launch directly behind the trunk's, no stream wait in front of it (enqueued
+            # AFTER the side stream's launches all the same: a runtime that runs kernels in submission order meets the side's
+            # work first): rows first - every embedding is there behind the trunk -, then the device-side gate lets the
+            # iterations go when image b's side-stream loop has published its[k_tail], and the result goes to a buffer of its
+            # own.  The next call's fill is ordered behind this call's side-stream kernels in ``parts_one_launch``.
+            result = self.buffers("parts1_out", (tuple(mem_idx_buf.shape), str(mem_idx_buf.device)), lambda: (torch.empty_like(mem_idx_buf),))[0]
+            table.scan_range(logits, M, I, ca.H, ca.n_token, its[k_tail], its[P], mem_idx_buf, tie, k_tail, P, pos, vq, redo=status,
+                             gate=gate, status=status, out=result)
+            if self._side_event is None:
+                self._side_event = torch.cuda.Event()
+            self._side_event.record(side)
+            self._side_pending = self._side_event
+        else:
+            main.wait_stream(side)
+            # behind the trunk launch every embedding is there: what the redo reads
+            part(P - 1, redo=status)
         self._mirror_pending = status              # (copied to the host by finish's launch, or by after_call behind the gathers)
         hip.scan.last_tie = tie
         # (whole images: the patches are gathered through the view; a caller that does not end in ``finish`` / ``take_unfinished``
         #  - dist.py - gets its own copy, as before)
         if src.is_view or not self.caller_finishes:
-            return mem_idx_buf.clone()
-        self._unfinished = mem_idx_buf             # ``finish`` - one launch - or ``take_unfinished`` + the gathers is the caller's next step
-        return mem_idx_buf
+            return result.clone()
+        self._unfinished = result                  # ``finish`` - one launch - or ``take_unfinished`` + the gathers is the caller's next step
+        return result
+
+    def scan_tail_on(self, patches, dev):
+        """The gated last launch of ``parts_loop_logits``: ``IPSX_SCAN_TAIL=0`` nowhere, ``=1`` on every call of the route, unset
+        on calls of at least ``small_batch_limit`` patches.  That is every image batch the route gets by itself - a smaller
+        one comes here only with 100 iterations or more per image (not measured with the gate), or from a test that lifts the
+        limit to look at the route's launches one by one (tests/test_scan_logits.py counts them).  The limit is written out
+        below and NOT asked of ``small_batch_limit``, deliberately and in this one place: that test lifts the method itself,
+        and the launches it counts are the chain's."""
+        mode = os.environ.get("IPSX_SCAN_TAIL", "auto")
+        return mode != "0" and (mode == "1" or patches >= 16 * self.round_patches(dev))
+
+    @staticmethod
+    def tail_parts(rows, limit):
+        """``k_tail`` of ``parts_loop_logits``: the first part such that the parts ``k_tail .. P - 1`` together hold at most
+        ``limit`` rows per image - those go into the call's last launch.  At least one part stays on the side stream (there
+        is nothing to gate on otherwise); ``P``: no trailing part fits, the chain as it was."""
+        P, k, held = len(rows), len(rows), 0
+        while k > 1 and held + rows[k - 1] <= limit:
+            k -= 1
+            held += rows[k]
+        return k
 
     # ------------------------------------------------------------------ pipeline: parts, the loop in ranges beside them
     def parts_with_ranges(self, patches, pos_enc):

@@ -4,6 +4,8 @@
     plain       the instantiation without the logits prologue (hip.scan_range over the whole loop)
     prologue    the instantiation WITH it, launched with no part of its own (part_begin == part_end): the same iterations
                 through the other instantiation's code - the prologue is outside the iterations, so the two must agree
+    publish     the instantiation with the prologue AND the gate's parameter, publishing the iteration it reached per image at
+                its end (gate_publish=): what the side stream's last loop launch of a gated call runs
     *_slope     (time of all iterations - time of the first half) / the other half: microseconds per iteration without what a
                 launch costs once (kernel arguments, the empty prologue, the loop's own set-up); *_per_launch: that remainder
     python tools/scan_loop_time.py [out.json]"""
@@ -48,10 +50,16 @@ for N in (2500, 10000):
     def prologue(n):
         return lambda: parts.scan_range(lg, M, I, H, T, 0, n, mem, tie, 1, 1, None, vq)
 
+    words = torch.zeros((B,), dtype=torch.int32, device=DEV)
+
+    def publish(n):
+        return lambda: parts.scan_range(lg, M, I, H, T, 0, n, mem, tie, 1, 1, None, vq, gate_publish=words)
+
     half = n_iter // 2
-    res = {"plain": [], "prologue": [], "plain_slope": [], "prologue_slope": [], "plain_per_launch": [], "prologue_per_launch": []}
+    variants = (("plain", plain), ("prologue", prologue), ("publish", publish))
+    res = {k + suffix: [] for k, _ in variants for suffix in ("", "_slope", "_per_launch")}
     for _ in range(3):
-        for k, fn in (("plain", plain), ("prologue", prologue)):
+        for k, fn in variants:
             whole, part = timed(fn(n_iter)), timed(fn(half))
             slope = (whole - part) / (n_iter - half)                 # us per iteration WITHOUT what a launch costs once
             res[k].append(round(whole / n_iter, 3))
