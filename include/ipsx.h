@@ -137,7 +137,10 @@ extern "C" {
  *         call inside its last part's launch (additions, the minor number stays);
  *         ipsx_scan_range_logits_gate - ipsx_scan_range_logits handed over on the device between two streams: a word per
  *         image published at a launch's end and waited for behind the next launch's prologue, the result in a buffer of its
- *         own (an addition, the minor number stays) */
+ *         own (an addition, the minor number stays);
+ *         ipsx_aggregate_counted, ipsx_attn_pool_forward_counted, ipsx_attn_pool_backward_counted - the masked aggregator:
+ *         image b of a zero-padded batch (IPSNet.ips_ragged(pad=True)) attends to its first count[b] slots only, in the
+ *         eval aggregation and in the training step's attention pool (additions, the minor number stays) */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -1114,6 +1117,15 @@ int ipsx_aggregate(const ipsx_transf* t, const float* x, int b, int m, float* ou
  * workspace, as ipsx_aggregate does).  Saves four small launches per call in an evaluation loop. */
 int ipsx_aggregate_packed(const ipsx_transf* t, const float* vq_packed, const float* wv_packed, const float* x, int b,
                           int m, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* 3.06: ipsx_aggregate_packed on a zero-padded batch.  count (b int32, device): image k attends to its slots 0 .. count[k] - 1
+ * only - the softmax of every head and token runs over those slots, the others have probability +0.0 and add nothing to the
+ * context, and what they hold cannot reach `out`.  The values are read on the device and clamped into 1 .. m there (the
+ * host cannot see them); count NULL is refused with IPSX_EINVAL.  The same launches over the same rows, the same refusals
+ * and the same workspace (ipsx_aggregate_workspace_bytes) as ipsx_aggregate_packed; out[k] has the bits of
+ * ipsx_aggregate_packed on the first count[k] rows of image k alone. */
+int ipsx_aggregate_counted(const ipsx_transf* t, const float* vq_packed, const float* wv_packed, const float* x,
+                           const int32_t* count, int b, int m, float* out, void* workspace, size_t workspace_bytes,
+                           void* stream);
 /* out[b][c] = act(w[c,:] . emb[b][token,:] + bias[c]); act 0 = softmax, 1 = sigmoid */
 int ipsx_head(const float* emb, int b, int n_token, int d, int token,
               const float* w, const float* bias, int n_class, int act,
@@ -1195,6 +1207,17 @@ int ipsx_attn_pool_forward(const float* x, const float* A, const float* keep, in
 int ipsx_attn_pool_backward(const float* x, const float* A, const float* keep, const float* P, const float* Z, const float* dZ,
                             int64_t B, int64_t M, int R, int D, float* dx, float* dA, void* workspace, size_t workspace_bytes,
                             void* stream);
+/* 3.06: the two calls above on a zero-padded batch.  count (B int32, device; clamped into 1 .. M on the device; NULL is
+ * refused): the rows of image b are 0 .. count[b] - 1 where they are 0 .. M - 1 above, the row pitch of x, keep, P and dx
+ * stays M.  P[b, r, m >= count[b]] is written +0.0 and dx[b, m >= count[b], :] is written 0; the rows of x beyond count[b]
+ * are never read, so nothing they hold reaches Z, P, dx or dA.  Z[b], P[b, :, :count[b]] and dx[b, :count[b]] have the bits
+ * of the unmasked calls on x[b, :count[b]] alone (up to the sign of a zero).  The same number of launches, the same
+ * workspace and the same refusals as the unmasked calls. */
+int ipsx_attn_pool_forward_counted(const float* x, const float* A, const float* keep, const int32_t* count, int64_t B, int64_t M,
+                                   int R, int D, float* Z, float* P, void* workspace, size_t workspace_bytes, void* stream);
+int ipsx_attn_pool_backward_counted(const float* x, const float* A, const float* keep, const int32_t* count, const float* P,
+                                    const float* Z, const float* dZ, int64_t B, int64_t M, int R, int D, float* dx, float* dA,
+                                    void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -616,8 +616,14 @@ class IPSNet(nn.Module):
         return self._mem_count
 
     # ---------------------------------------------------------------- aggregation
-    def forward(self, mem_patch, mem_pos=None, mem_emb=None):
+    def forward(self, mem_patch, mem_pos=None, mem_emb=None, mem_count=None):
         """Embed the M selected patches, aggregate, classify (reference :264-283).
+
+        ``mem_count`` (optional, not in the reference): the filled slots of every slide of a zero-padded buffer - after a
+        ``pad=True`` selection ``net(mem_patch, mem_pos, mem_count=net.last_mem_count)``.  Handed to the aggregator
+        (``Transformer.forward(x, count=)``): slide b is classified from its first mem_count[b] slots only, as the solo call
+        on them would classify it; the padding is still embedded, but nothing of it reaches the prediction.  None (the
+        default; ``last_mem_count`` is never read here): every slot is attended to, as in the reference.
 
         ``mem_emb`` (optional, not in the reference): embeddings of ``mem_patch`` already computed by ``ips()``
         in eval mode (``last_mem_emb``); used instead of a second encoder pass when the encoder is in eval
@@ -627,4 +633,6 @@ class IPSNet(nn.Module):
             mem_emb = self._embed(mem_patch.reshape(-1, *mem_patch.shape[2:])).view(B, M, -1)
         if torch.is_tensor(mem_pos):
             mem_emb = mem_emb + mem_pos
+        if mem_count is not None:
+            return self.get_preds(self.transf(mem_emb, count=mem_count))
         return self.get_preds(self.transf(mem_emb))

@@ -14,6 +14,9 @@ Three execution paths live behind that interface:
   autograd node (``ips_amd/training/fused_aggregator.py``, csrc/attn_pool_train.hip), the R-row rest on stock ops.
 * everything else (CPU tensors, ``get_scores`` / ``get_attn`` under autograd, ``IPSX_TRAIN_AGGREGATOR=0``)
   ->  stock ATen ops, which is what the reference itself dispatches.
+
+``Transformer.forward(x, count=)`` (not in the reference) masks the zero padding of a ``pad=True`` batch on
+each of the three paths; ``count=None`` is the code above, unchanged.
 """
 
 import math
@@ -59,13 +62,19 @@ class ScaledDotProductAttention(nn.Module):
         self.temperature = temperature
         self.dropout = nn.Dropout(attn_dropout)
 
-    def compute_attn(self, q, k):
+    def compute_attn(self, q, k, count=None):
+        """``count`` (not in the reference; an integer tensor (B,) on k's device, None = every slot): slide b attends to its
+        slots 0 .. count[b] - 1 only - the others are filled with -inf in front of the softmax, so their probability is
+        exactly +0.0 and their gradient exactly 0.  This is the definition the masked kernels are held to."""
         # the division is applied to q BEFORE the contraction (reference :31)
         logits = torch.matmul(q / self.temperature, k.transpose(2, 3))
+        if count is not None:
+            beyond = torch.arange(k.shape[2], device=k.device)[None, :] >= count.to(k.device)[:, None]          # (B, M)
+            logits = logits.masked_fill(beyond[:, None, None, :], float("-inf"))
         return self.dropout(torch.softmax(logits, dim=-1))
 
-    def forward(self, q, k, v):
-        return torch.matmul(self.compute_attn(q, k), v)
+    def forward(self, q, k, v, count=None):
+        return torch.matmul(self.compute_attn(q, k, count), v)
 
 
 class MultiHeadCrossAttention(nn.Module):
@@ -139,12 +148,12 @@ class MultiHeadCrossAttention(nn.Module):
     def _drops(self):
         return self.training and (self.dropout.p > 0 or self.attention.dropout.p > 0)
 
-    def forward(self, x):
+    def forward(self, x, count=None):
         b = x.shape[0]
         q = self._heads(self.q_w, self.q, self.D_k)
         k = self._heads(self.k_w, x, self.D_k)
         v = self._heads(self.v_w, x, self.D_v)
-        ctx = self.attention(q, k, v)                        # (B, H, n_token, D_v)
+        ctx = self.attention(q, k, v) if count is None else self.attention(q, k, v, count)          # (B, H, n_token, D_v)
         ctx = ctx.transpose(1, 2).contiguous().view(b, self.n_token, -1)
         out = self.dropout(self.fc(ctx))
         out += self.q                                        # residual on the learned queries
@@ -184,11 +193,21 @@ class Transformer(nn.Module):
         attn = ca.get_attn(x)
         return attn.mean(dim=1).transpose(1, 2).mean(-1)
 
-    def forward(self, x):
-        """Aggregate ``x`` (B, M, D) into ``(B, n_token, D)``."""
-        ca = self.crs_attn
+    def forward(self, x, count=None):
+        """Aggregate ``x`` (B, M, D) into ``(B, n_token, D)``.
+
+        ``count`` (not in the reference; B ints or an integer tensor (B,), ``IPSNet.last_mem_count`` after a ``pad=True``
+        selection; None = today's code on every route): slide b is aggregated from its slots 0 .. count[b] - 1 only, as
+        ``self(x[b:b + 1, :count[b]])`` would - on every route, chosen as without it.  Host counts outside 1 .. M or of
+        another length than B raise ValueError; a tensor on the GPU is not read back (``hip.slot_counts``)."""
+        masked = {}
+        if count is not None:
+            if x.dim() != 3:
+                raise ValueError("count needs x (B, M, D), got {}".format(tuple(x.shape)))
+            # (ONE int32 tensor on x's device, checked once; the calls below get it as a keyword the unmasked ones never see)
+            masked["count"] = hip.slot_counts("Transformer.forward", count, x.shape[0], x.shape[1], x.device)
         if _use_hip(x, *self.parameters()) and not self.training:
-            return hip.aggregate(self, x)
+            return hip.aggregate(self, x, **masked)
         if (x.is_cuda and x.dim() == 3 and x.dtype == torch.float32 and torch.is_grad_enabled() and hip.backend() == "hip"
                 and (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
             # training step (reference training/iterative.py:158-163): the (B, M) part as one node on folded queries
@@ -197,5 +216,5 @@ class Transformer(nn.Module):
                 if getattr(self, "_fused_train_ok", None) is None:        # (the module tree does not change after construction)
                     self._fused_train_ok = fused_aggregator.supported(self)
                 if self._fused_train_ok:
-                    return fused_aggregator.forward(self, x)
-        return self.mlp(self.crs_attn(x))
+                    return fused_aggregator.forward(self, x, **masked)
+        return self.mlp(self.crs_attn(x, **masked))

@@ -91,8 +91,13 @@ struct CtxArgs {
     const float* v;     // (b, m, h*dv)
     float* ctx;         // (b, T, h*dv)
     int m, h, T, dv;
+    const int32_t* count;   // COUNTED: (b,) filled slots per image, clamped into 1 .. m here; the row pitch stays m
 };
 
+// COUNTED (ipsx_aggregate_counted): image b attends to its slots l < count[b] only - the row maximum, the denominator and
+// the context run over that bound through the same chains, so the bits are those of the unmasked kernel on the image's
+// first count[b] rows alone; the slots beyond are never read.
+template <bool COUNTED>
 __global__ __launch_bounds__(256) void attn_ctx_kernel(CtxArgs a) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int R = a.h * a.T, hdv = a.h * a.dv;
@@ -100,12 +105,14 @@ __global__ __launch_bounds__(256) void attn_ctx_kernel(CtxArgs a) {
     float* rden = sm + R;
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* lg = a.lg + (size_t)b * a.m * R;
+    int rows = a.m;
+    if constexpr (COUNTED) rows = min(max(a.count[b], 1), a.m);
     for (int r = wave; r < R; r += 4) {
         float mx = -__builtin_huge_valf();
-        for (int i = lane; i < a.m; i += 64) mx = nanmax(mx, lg[(size_t)i * R + r]);
+        for (int i = lane; i < rows; i += 64) mx = nanmax(mx, lg[(size_t)i * R + r]);
         mx = wave_max(mx);
         float s = 0.0f;
-        for (int i = lane; i < a.m; i += 64) s = s + det_expf(lg[(size_t)i * R + r] - mx);
+        for (int i = lane; i < rows; i += 64) s = s + det_expf(lg[(size_t)i * R + r] - mx);
         s = wave_butterfly_sum(s);
         if (lane == 0) { rmax[r] = mx; rden[r] = 1.0f / s; }         // (the reciprocal: oracle orc_scores_from_logits)
     }
@@ -116,7 +123,7 @@ __global__ __launch_bounds__(256) void attn_ctx_kernel(CtxArgs a) {
         const int r = hh * a.T + t;
         const float mx = rmax[r], den = rden[r];
         float acc = 0.0f;
-        for (int l = 0; l < a.m; ++l) {
+        for (int l = 0; l < rows; ++l) {
             const float w = det_expf(lg[(size_t)l * R + r] - mx) * den;
             acc = __builtin_fmaf(w, v[(size_t)l * hdv + col], acc);
         }
@@ -303,8 +310,10 @@ IPSX_API int ipsx_aggregate(const ipsx_transf* t, const float* x, int b, int m, 
     return ipsx_aggregate_packed(t, nullptr, nullptr, x, b, m, out, workspace, workspace_bytes, stream);
 }
 
-IPSX_API int ipsx_aggregate_packed(const ipsx_transf* t, const float* vq_packed, const float* wv_packed, const float* x, int b,
-                                   int m, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+// ipsx_aggregate_packed, and with ``count`` ipsx_aggregate_counted: the same launches over the same rows, the context
+// kernel bounded by count[b]
+static int aggregate_impl(const ipsx_transf* t, const float* vq_packed, const float* wv_packed, const float* x, const int32_t* count,
+                          int b, int m, float* out, void* workspace, size_t workspace_bytes, void* stream) {
     IPSX_REQUIRE(t && x && out && b > 0 && m > 0, "aggregate: bad arguments");
     IPSX_REQUIRE(t->q && t->wq && t->wk && t->wv && t->fc && t->ln1_g && t->ln1_b && t->w1 && t->b1 && t->w2 &&
                      t->b2 && t->ln2_g && t->ln2_b, "aggregate: missing weights");
@@ -346,8 +355,9 @@ IPSX_API int ipsx_aggregate_packed(const ipsx_transf* t, const float* vq_packed,
     IPSX_TRY(ipsx_conv2d_affine_nhwc(&vproj, x, nullptr, v, (int64_t)b * m, 1, 1, 0, stream));
 
     CtxArgs c;
-    c.lg = lg; c.v = v; c.ctx = ctx; c.m = m; c.h = t->h; c.T = t->n_token; c.dv = t->dv;
-    attn_ctx_kernel<<<dim3((unsigned)b), dim3(256), (size_t)R * 8, s>>>(c);
+    c.lg = lg; c.v = v; c.ctx = ctx; c.m = m; c.h = t->h; c.T = t->n_token; c.dv = t->dv; c.count = count;
+    if (count) attn_ctx_kernel<true><<<dim3((unsigned)b), dim3(256), (size_t)R * 8, s>>>(c);
+    else attn_ctx_kernel<false><<<dim3((unsigned)b), dim3(256), (size_t)R * 8, s>>>(c);
     IPSX_TRY(launched("attn_ctx"));
 
     TailArgs ta;
@@ -356,6 +366,18 @@ IPSX_API int ipsx_aggregate_packed(const ipsx_transf* t, const float* vq_packed,
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(transf_tail_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     transf_tail_kernel<<<dim3((unsigned)b), dim3(256), lds, s>>>(ta);
     return launched("transf_tail");
+}
+
+IPSX_API int ipsx_aggregate_packed(const ipsx_transf* t, const float* vq_packed, const float* wv_packed, const float* x, int b,
+                                   int m, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    return aggregate_impl(t, vq_packed, wv_packed, x, nullptr, b, m, out, workspace, workspace_bytes, stream);
+}
+
+IPSX_API int ipsx_aggregate_counted(const ipsx_transf* t, const float* vq_packed, const float* wv_packed, const float* x,
+                                    const int32_t* count, int b, int m, float* out, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+    IPSX_REQUIRE(count, "aggregate_counted: count is null (ipsx_aggregate_packed is the unmasked call)");
+    return aggregate_impl(t, vq_packed, wv_packed, x, count, b, m, out, workspace, workspace_bytes, stream);
 }
 
 IPSX_API int ipsx_head(const float* emb, int b, int n_token, int d, int token, const float* w, const float* bias,

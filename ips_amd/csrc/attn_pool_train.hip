@@ -23,6 +23,13 @@
 // written once.  Z and dA are sums over workgroups: every workgroup stores its block, attn_pool_sum_kernel adds the blocks
 // in ascending (b, chunk) order - no float atomics, the same bits every run, and an image's Z / P / dx do not depend on
 // what else is in the batch (the chunk is a constant: the tree of additions depends on M alone).
+//
+// COUNTED (the _counted exports, a zero-padded batch): image b's row bound is count[b] (device int32, clamped into 1 .. M)
+// where it is M above; the row pitch stays M.  The mask is that bound and nothing else - no row at or beyond count[b] is
+// read, so whatever the padding holds cannot reach an output - and since the trees depend on the row count alone, Z[b],
+// P[b, :, :count[b]] and dx[b, :count[b]] have the bits of the unmasked kernels on x[b, :count[b]].  A workgroup whose
+// chunk starts at or beyond count[b] does no arithmetic: it stores a zero block (attn_pool_sum_kernel is unchanged; a
+// trailing +0.0 can only turn a -0.0 sum into +0.0) and, in the backward, zeros into its rows of dx.
 
 #include "ipsx_common.h"
 #include "ipsx_math.h"
@@ -37,6 +44,13 @@ typedef float ap_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int AP_CHUNK = 128;          // rows of x per workgroup: 4 wavefronts x 32
 constexpr int AP_PITCH = 33;           // floats per [m] row of the LDS images
 constexpr int AP_MAX_R = 32, AP_MAX_D = 1024;
+
+// the row bound of image b
+template <bool COUNTED>
+__device__ __forceinline__ int ap_rows(const int32_t* __restrict__ count, int b, int M) {
+    if constexpr (COUNTED) return min(max(count[b], 1), M);
+    else return M;
+}
 
 // row of accumulator register q in lane half h (the 32x32 C/D map)
 __device__ __forceinline__ int ap_row(int q, int half) { return (q & 3) + 8 * (q >> 2) + 4 * half; }
@@ -145,40 +159,69 @@ __device__ __forceinline__ void ap_store_block(float* __restrict__ out, const ap
     }
 }
 
+// a block of zeros in its place: a workgroup whose chunk lies beyond the image's rows (COUNTED)
+template <int GPW>
+__device__ __forceinline__ void ap_store_zero_block(float* __restrict__ out, int R, int D, int wave, int lane) {
+    ap_f32x16 acc[GPW][4];
+#pragma unroll
+    for (int g = 0; g < GPW; ++g)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int q = 0; q < 16; ++q) acc[g][j][q] = 0.0f;
+    ap_store_block<GPW>(out, acc, R, D, wave, lane);
+}
+
+// dx[ml, :] = 0 for the chunk's rows ml = from .. to - 1 (COUNTED: the rows beyond the image's count), the wavefront's columns
+template <int GPW>
+__device__ __forceinline__ void ap_zero_dx_rows(float* __restrict__ dxb, int from, int to, int D, int wave, int lane) {
+    const int half = lane >> 5, i = lane & 31;
+#pragma unroll
+    for (int g = 0; g < GPW; ++g) {
+        const int col = (wave + 4 * g) * 128 + 4 * i;
+        if (col >= D) continue;
+        for (int ml = from + half; ml < to; ml += 2) *reinterpret_cast<ap_f32x4*>(dxb + (size_t)ml * D + col) = ap_f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    }
+}
+
 // ------------------------------------------------------------------ forward 1: raw logits into P
+template <bool COUNTED>
 __global__ __launch_bounds__(256) void attn_pool_logits_kernel(const float* __restrict__ x, const float* __restrict__ A, float* __restrict__ P,
-                                                               int M, int R, int D) {
+                                                               const int32_t* __restrict__ count, int M, int R, int D) {
     const int lane = threadIdx.x & 63, half = lane >> 5, i = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.y, m0 = blockIdx.x * AP_CHUNK + wave * 32;
-    if (m0 >= M) return;                                            // wave-uniform; no barrier below
+    const int rows = ap_rows<COUNTED>(count, b, M);
+    if (m0 >= rows) return;                                         // wave-uniform; no barrier below
     const float* xb = x + (size_t)b * M * D;
-    const ap_f32x16 acc = ap_dot_tile(xb, A, m0, M, R, D, lane);
+    const ap_f32x16 acc = ap_dot_tile(xb, A, m0, rows, R, D, lane);
     if (i >= R) return;
     float* pr = P + ((size_t)b * R + i) * M;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
         const int m = m0 + ap_row(q, half);
-        if (m < M) pr[m] = acc[q];
+        if (m < rows) pr[m] = acc[q];
     }
 }
 
 // ------------------------------------------------------------------ forward 2: P[b, r, :] = softmax of its logits, in place
 // One workgroup per row; maximum and sum through a fixed tree (thread-strided chains, xor butterfly, the four wavefronts
-// in order).
-__global__ __launch_bounds__(256) void attn_pool_softmax_kernel(float* __restrict__ P, int M) {
+// in order).  COUNTED: over the image's count[b] slots; the slots beyond (which the logits kernel left unwritten) get +0.0.
+template <bool COUNTED>
+__global__ __launch_bounds__(256) void attn_pool_softmax_kernel(float* __restrict__ P, const int32_t* __restrict__ count, int M, int R) {
     __shared__ float red[4];
     float* row = P + (size_t)blockIdx.x * M;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int rows = ap_rows<COUNTED>(count, (int)(blockIdx.x / (unsigned)R), M);
     float mx = -INFINITY;
-    for (int m = t; m < M; m += 256) mx = nanmax(mx, row[m]);
+    for (int m = t; m < rows; m += 256) mx = nanmax(mx, row[m]);
     mx = wave_max(mx);
     if (lane == 0) red[wave] = mx;
     __syncthreads();
     mx = nanmax(nanmax(red[0], red[1]), nanmax(red[2], red[3]));
     __syncthreads();
     float s = 0.0f;
-    for (int m = t; m < M; m += 256) {
+    for (int m = t; m < rows; m += 256) {
         const float e = expf(row[m] - mx);
         row[m] = e;
         s = s + e;
@@ -188,19 +231,28 @@ __global__ __launch_bounds__(256) void attn_pool_softmax_kernel(float* __restric
     if (lane == 0) red[wave] = s;
     __syncthreads();
     s = (red[0] + red[1]) + (red[2] + red[3]);
-    for (int m = t; m < M; m += 256) row[m] = row[m] / s;
+    for (int m = t; m < rows; m += 256) row[m] = row[m] / s;
+    if constexpr (COUNTED)
+        for (int m = rows + t; m < M; m += 256) row[m] = 0.0f;
 }
 
 // ------------------------------------------------------------------ forward 3: this chunk's block of Z
-template <int GPW>
+template <int GPW, bool COUNTED>
 __global__ __launch_bounds__(256) void attn_pool_pool_kernel(const float* __restrict__ x, const float* __restrict__ P,
-                                                             const float* __restrict__ keep, float* __restrict__ part, int M, int R, int D,
-                                                             int chunks) {
+                                                             const float* __restrict__ keep, const int32_t* __restrict__ count,
+                                                             float* __restrict__ part, int M, int R, int D, int chunks) {
     __shared__ float wl[AP_CHUNK * AP_PITCH];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.y, m0 = blockIdx.x * AP_CHUNK;
-    const int nrows = min(AP_CHUNK, M - m0);
+    const int rows = ap_rows<COUNTED>(count, b, M);
+    const int nrows = min(AP_CHUNK, rows - m0);
+    if constexpr (COUNTED) {
+        if (nrows <= 0) {                                           // (the whole workgroup: no barrier is skipped by a part of it)
+            if (wave * 128 < D) ap_store_zero_block<GPW>(part + ((size_t)b * chunks + blockIdx.x) * R * D, R, D, wave, lane);
+            return;
+        }
+    }
     for (int e = threadIdx.x; e < AP_CHUNK * 32; e += 256) {        // e = r * 128 + m: a row of P per 128 threads' loads
         const int r = e >> 7, ml = e & (AP_CHUNK - 1);
         float v = 0.0f;
@@ -220,7 +272,7 @@ __global__ __launch_bounds__(256) void attn_pool_pool_kernel(const float* __rest
         for (int j = 0; j < 4; ++j)
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[g][j][q] = 0.0f;
-    ap_pool_chunk<GPW>(x + (size_t)b * M * D, wl, m0, nrows, M, D, wave, lane, acc);
+    ap_pool_chunk<GPW>(x + (size_t)b * M * D, wl, m0, nrows, rows, D, wave, lane, acc);
     ap_store_block<GPW>(part + ((size_t)b * chunks + blockIdx.x) * R * D, acc, R, D, wave, lane);
 }
 
@@ -260,9 +312,10 @@ struct ApBwdArgs {
     const float *x, *A, *keep, *P, *dZ, *c;
     float *dx, *part;          // dx may be null
     int M, R, D, chunks;
+    const int32_t* count;      // COUNTED only
 };
 
-template <int GPW>
+template <int GPW, bool COUNTED>
 __global__ __launch_bounds__(256) void attn_pool_bwd_kernel(ApBwdArgs a) {
     __shared__ float wp[AP_CHUNK * AP_PITCH];      // P'[m][r]
     __shared__ float wd[AP_CHUNK * AP_PITCH];      // dL[m][r]
@@ -270,16 +323,25 @@ __global__ __launch_bounds__(256) void attn_pool_bwd_kernel(ApBwdArgs a) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int b = blockIdx.y, m0 = blockIdx.x * AP_CHUNK;
     const int M = a.M, R = a.R, D = a.D;
-    const int nrows = min(AP_CHUNK, M - m0);
+    const int rows = ap_rows<COUNTED>(a.count, b, M);
+    const int nrows = min(AP_CHUNK, rows - m0);
     const float* xb = a.x + (size_t)b * M * D;
     const float* dzb = a.dZ + (size_t)b * R * D;
+    if constexpr (COUNTED) {
+        if (nrows <= 0) {                          // (the whole workgroup, in front of the barrier)
+            if (wave * 128 >= D) return;
+            ap_store_zero_block<GPW>(a.part + ((size_t)b * a.chunks + blockIdx.x) * R * D, R, D, wave, lane);
+            if (a.dx) ap_zero_dx_rows<GPW>(a.dx + ((size_t)b * M + m0) * D, 0, min(AP_CHUNK, M - m0), D, wave, lane);
+            return;
+        }
+    }
     {
         // dP' of this wavefront's 32 rows (a tile beyond M: zeros into the images, no arithmetic)
         const int t0 = wave * 32;
         ap_f32x16 acc;
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc[q] = 0.0f;
-        if (t0 < nrows) acc = ap_dot_tile(xb, dzb, m0 + t0, M, R, D, lane);
+        if (t0 < nrows) acc = ap_dot_tile(xb, dzb, m0 + t0, rows, R, D, lane);
         const float c = a.c[(size_t)b * AP_MAX_R + i];
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
@@ -305,13 +367,14 @@ __global__ __launch_bounds__(256) void attn_pool_bwd_kernel(ApBwdArgs a) {
             for (int j = 0; j < 4; ++j)
 #pragma unroll
                 for (int q = 0; q < 16; ++q) acc[g][j][q] = 0.0f;
-        ap_pool_chunk<GPW>(xb, wd, m0, nrows, M, D, wave, lane, acc);
+        ap_pool_chunk<GPW>(xb, wd, m0, nrows, rows, D, wave, lane, acc);
         ap_store_block<GPW>(a.part + ((size_t)b * a.chunks + blockIdx.x) * R * D, acc, R, D, wave, lane);
     }
     if (!a.dx) return;
     // dx[m, d] = sum_r P'[m, r] dZ[r, d] + dL[m, r] A[r, d]: 32 rows x 128 columns at a time, k = r in pairs
     const int ksteps = (R + 1) >> 1;
     float* dxb = a.dx + ((size_t)b * M + m0) * D;
+    if constexpr (COUNTED) ap_zero_dx_rows<GPW>(dxb, nrows, min(AP_CHUNK, M - m0), D, wave, lane);          // (the chunk straddles count[b])
 #pragma unroll 1
     for (int g = 0; g < GPW; ++g) {
         const int col = (wave + 4 * g) * 128 + 4 * i;
@@ -366,8 +429,10 @@ IPSX_API size_t ipsx_attn_pool_workspace_bytes(int64_t B, int64_t M, int R, int 
     return ((size_t)B * (size_t)cdiv(M, AP_CHUNK) * R * D + (size_t)B * AP_MAX_R) * sizeof(float);
 }
 
-IPSX_API int ipsx_attn_pool_forward(const float* x, const float* A, const float* keep, int64_t B, int64_t M, int R, int D, float* Z,
-                                    float* P, void* workspace, size_t workspace_bytes, void* stream) {
+// the forward and the backward behind their two exports each: count NULL = the unmasked kernels, as before
+template <bool COUNTED>
+static int ap_forward(const float* x, const float* A, const float* keep, const int32_t* count, int64_t B, int64_t M, int R, int D, float* Z,
+                      float* P, void* workspace, size_t workspace_bytes, void* stream) {
     IPSX_REQUIRE(x && A && Z && P, "attn_pool_forward: bad arguments");
     IPSX_REQUIRE(ap_shape(R, D), "attn_pool_forward: R = %d (1 .. 32), D = %d (a multiple of 32, 32 .. 1024)", R, D);
     IPSX_REQUIRE(ap_sizes(B, M), "attn_pool_forward: B = %lld (1 .. 65535), M = %lld (1 .. 2^30)", (long long)B, (long long)M);
@@ -377,21 +442,22 @@ IPSX_API int ipsx_attn_pool_forward(const float* x, const float* A, const float*
     const int chunks = (int)cdiv(M, AP_CHUNK);
     const dim3 grid((unsigned)chunks, (unsigned)B), block(256);
     float* part = static_cast<float*>(workspace);
-    attn_pool_logits_kernel<<<grid, block, 0, s>>>(x, A, P, (int)M, R, D);
+    attn_pool_logits_kernel<COUNTED><<<grid, block, 0, s>>>(x, A, P, count, (int)M, R, D);
     IPSX_TRY(launched("attn_pool_forward (logits)"));
-    attn_pool_softmax_kernel<<<dim3((unsigned)(B * R)), block, 0, s>>>(P, (int)M);
+    attn_pool_softmax_kernel<COUNTED><<<dim3((unsigned)(B * R)), block, 0, s>>>(P, count, (int)M, R);
     IPSX_TRY(launched("attn_pool_forward (softmax)"));
-    if (D <= 512) attn_pool_pool_kernel<1><<<grid, block, 0, s>>>(x, P, keep, part, (int)M, R, D, chunks);
-    else attn_pool_pool_kernel<2><<<grid, block, 0, s>>>(x, P, keep, part, (int)M, R, D, chunks);
+    if (D <= 512) attn_pool_pool_kernel<1, COUNTED><<<grid, block, 0, s>>>(x, P, keep, count, part, (int)M, R, D, chunks);
+    else attn_pool_pool_kernel<2, COUNTED><<<grid, block, 0, s>>>(x, P, keep, count, part, (int)M, R, D, chunks);
     IPSX_TRY(launched("attn_pool_forward (pool)"));
     const int total = R * D;
     attn_pool_sum_kernel<<<dim3((unsigned)cdiv(total, 256), (unsigned)B), block, 0, s>>>(part, chunks, total, Z);
     return launched("attn_pool_forward (sum)");
 }
 
-IPSX_API int ipsx_attn_pool_backward(const float* x, const float* A, const float* keep, const float* P, const float* Z, const float* dZ,
-                                     int64_t B, int64_t M, int R, int D, float* dx, float* dA, void* workspace, size_t workspace_bytes,
-                                     void* stream) {
+template <bool COUNTED>
+static int ap_backward(const float* x, const float* A, const float* keep, const int32_t* count, const float* P, const float* Z,
+                       const float* dZ, int64_t B, int64_t M, int R, int D, float* dx, float* dA, void* workspace, size_t workspace_bytes,
+                       void* stream) {
     IPSX_REQUIRE(x && A && P && Z && dZ && dA, "attn_pool_backward: bad arguments");
     IPSX_REQUIRE(ap_shape(R, D), "attn_pool_backward: R = %d (1 .. 32), D = %d (a multiple of 32, 32 .. 1024)", R, D);
     IPSX_REQUIRE(ap_sizes(B, M), "attn_pool_backward: B = %lld (1 .. 65535), M = %lld (1 .. 2^30)", (long long)B, (long long)M);
@@ -400,7 +466,7 @@ IPSX_API int ipsx_attn_pool_backward(const float* x, const float* A, const float
     hipStream_t s = as_stream(stream);
     const int chunks = (int)cdiv(M, AP_CHUNK);
     ApBwdArgs a;
-    a.x = x; a.A = A; a.keep = keep; a.P = P; a.dZ = dZ;
+    a.x = x; a.A = A; a.keep = keep; a.P = P; a.dZ = dZ; a.count = count;
     a.dx = dx; a.part = static_cast<float*>(workspace);
     float* c = a.part + (size_t)B * chunks * R * D;
     a.c = c;
@@ -408,12 +474,36 @@ IPSX_API int ipsx_attn_pool_backward(const float* x, const float* A, const float
     IPSX_TRY(launched("attn_pool_backward (row constants)"));
     a.M = (int)M; a.R = R; a.D = D; a.chunks = chunks;
     const dim3 grid((unsigned)chunks, (unsigned)B), block(256);
-    if (D <= 512) attn_pool_bwd_kernel<1><<<grid, block, 0, s>>>(a);
-    else attn_pool_bwd_kernel<2><<<grid, block, 0, s>>>(a);
+    if (D <= 512) attn_pool_bwd_kernel<1, COUNTED><<<grid, block, 0, s>>>(a);
+    else attn_pool_bwd_kernel<2, COUNTED><<<grid, block, 0, s>>>(a);
     IPSX_TRY(launched("attn_pool_backward"));
     const int total = R * D;
     const int64_t n = B * chunks;
     IPSX_REQUIRE(n < ((int64_t)1 << 31), "attn_pool_backward: %lld partial blocks", (long long)n);
     attn_pool_sum_kernel<<<dim3((unsigned)cdiv(total, 256), 1), block, 0, s>>>(a.part, (int)n, total, dA);
     return launched("attn_pool_backward (sum)");
+}
+
+IPSX_API int ipsx_attn_pool_forward(const float* x, const float* A, const float* keep, int64_t B, int64_t M, int R, int D, float* Z,
+                                    float* P, void* workspace, size_t workspace_bytes, void* stream) {
+    return ap_forward<false>(x, A, keep, nullptr, B, M, R, D, Z, P, workspace, workspace_bytes, stream);
+}
+
+IPSX_API int ipsx_attn_pool_forward_counted(const float* x, const float* A, const float* keep, const int32_t* count, int64_t B, int64_t M,
+                                            int R, int D, float* Z, float* P, void* workspace, size_t workspace_bytes, void* stream) {
+    IPSX_REQUIRE(count, "attn_pool_forward_counted: count is null (ipsx_attn_pool_forward is the unmasked call)");
+    return ap_forward<true>(x, A, keep, count, B, M, R, D, Z, P, workspace, workspace_bytes, stream);
+}
+
+IPSX_API int ipsx_attn_pool_backward(const float* x, const float* A, const float* keep, const float* P, const float* Z, const float* dZ,
+                                     int64_t B, int64_t M, int R, int D, float* dx, float* dA, void* workspace, size_t workspace_bytes,
+                                     void* stream) {
+    return ap_backward<false>(x, A, keep, nullptr, P, Z, dZ, B, M, R, D, dx, dA, workspace, workspace_bytes, stream);
+}
+
+IPSX_API int ipsx_attn_pool_backward_counted(const float* x, const float* A, const float* keep, const int32_t* count, const float* P,
+                                             const float* Z, const float* dZ, int64_t B, int64_t M, int R, int D, float* dx, float* dA,
+                                             void* workspace, size_t workspace_bytes, void* stream) {
+    IPSX_REQUIRE(count, "attn_pool_backward_counted: count is null (ipsx_attn_pool_backward is the unmasked call)");
+    return ap_backward<true>(x, A, keep, count, P, Z, dZ, B, M, R, D, dx, dA, workspace, workspace_bytes, stream);
 }

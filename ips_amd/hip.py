@@ -12,6 +12,7 @@ call returns an error code, a RuntimeError is raised.  ``IPSX_BACKEND=aten``
 
 import collections
 import ctypes as C
+import operator
 import os
 import subprocess
 
@@ -458,6 +459,8 @@ _EXPORTS = {
                                  C.c_void_p, C.c_size_t, C.c_void_p]),
     "ipsx_aggregate_packed": (C.c_int, [C.POINTER(Transf), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ipsx_aggregate_counted": (C.c_int, [C.POINTER(Transf), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ipsx_head": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                             C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "ipsx_bn_train_supported": (C.c_int, [C.c_int64, C.c_int]),
@@ -483,6 +486,11 @@ _EXPORTS = {
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ipsx_attn_pool_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                                           C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ipsx_attn_pool_forward_counted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ipsx_attn_pool_backward_counted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                  C.c_void_p]),
 }
 
 
@@ -609,6 +617,32 @@ def _wr(what, name, t, dtype, shape=None, align=1, cl=False):
 def _workspace(what, ws):
     """A caller's workspace: contiguous uint8 bytes (None: the wrapper allocates)."""
     return _wr(what, "workspace", ws, torch.uint8, align=16) if ws is not None else None
+
+
+def slot_counts(what, count, B, M, device):
+    """The filled slots of a zero-padded batch (``IPSNet.last_mem_count``) as the masked aggregator takes them: -> ONE int32
+    tensor of shape (B,) on ``device``.  ``count``: a sequence of B ints, or an integer tensor of shape (B,) on any device.
+    What lies on the host is checked here, before anything is launched or allocated: a wrong length or an entry outside
+    1 .. M raises ValueError.  A tensor that already lies on a GPU is NOT read back (that would synchronise): its shape and
+    dtype are checked, its entries are not - the kernels clamp them into 1 .. M."""
+    if torch.is_tensor(count):
+        if count.is_floating_point() or count.is_complex() or count.dtype == torch.bool:
+            raise TypeError("{}: count must hold integers, got {}".format(what, count.dtype))
+        if tuple(count.shape) != (B,):
+            raise ValueError("{}: count must have shape ({},) - one entry per image - got {}".format(what, B, tuple(count.shape)))
+        if count.device.type != "cpu":
+            return count.to(device=device, dtype=torch.int32).contiguous()
+        count = count.tolist()
+    try:
+        seq = [operator.index(c) for c in count]
+    except TypeError:
+        raise TypeError("{}: count must be a sequence of ints or an integer tensor, got {!r}".format(what, count)) from None
+    if len(seq) != B:
+        raise ValueError("{}: count has {} entries for a batch of {}".format(what, len(seq), B))
+    bad = [c for c in seq if not 1 <= c <= M]
+    if bad:
+        raise ValueError("{}: count entries must lie in 1 .. M = {}, got {}".format(what, M, bad[0]))
+    return torch.tensor(seq, dtype=torch.int32, device=device)
 
 
 _PATCH_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
@@ -2005,10 +2039,15 @@ def avgpool_nhwc_bf16(x):
 
 
 # ------------------------------------------------------------------ aggregation
-def aggregate(transf, x):
-    """Transformer.forward in eval / no-grad mode: x (B, M, D) -> (B, n_token, D)."""
+def aggregate(transf, x, count=None):
+    """Transformer.forward in eval / no-grad mode: x (B, M, D) -> (B, n_token, D).  ``count`` (``slot_counts``: B ints or an
+    integer tensor (B,); None = every slot): image b attends to its slots 0 .. count[b] - 1 only (ipsx_aggregate_counted) -
+    out[b] has the bits of ``aggregate(transf, x[b:b + 1, :count[b]])``.  Host counts are checked here; a tensor on the GPU
+    is not read back, the kernel clamps its entries into 1 .. M."""
     ca, mlp = transf.crs_attn, transf.mlp
     _one_gpu("aggregate", x=x, weights=ca.k_w.weight)
+    if count is not None and x.dim() == 3:          # (in front of every allocation and launch)
+        count = slot_counts("aggregate", count, x.shape[0], x.shape[1], x.device)
     x = _rd("aggregate", "x", x, dim=3)          # (its logits pass reads rows with 16-byte loads)
     B, M, D = x.shape
     if ca.k_w.weight.shape[1] != D or ca.v_w.weight.shape[1] != D:
@@ -2033,6 +2072,10 @@ def aggregate(transf, x):
     if vq is not None and vq.dtype != torch.float32:       # (bf16 logits operand: the aggregation folds its own fp32 one)
         vq = None
     wvp = ca.packed_v() if hasattr(ca, "packed_v") else None
+    if count is not None:
+        _ck(lib().ipsx_aggregate_counted(C.byref(t), _p(vq), _p(wvp), _p(x), _p(count), B, M, _p(out), _p(ws), nb, _stream()),
+            "ipsx_aggregate_counted")
+        return out
     _ck(lib().ipsx_aggregate_packed(C.byref(t), _p(vq), _p(wvp), _p(x), B, M, _p(out), _p(ws), nb, _stream()),
         "ipsx_aggregate_packed")
     return out

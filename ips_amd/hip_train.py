@@ -10,7 +10,7 @@ import os
 
 import torch
 
-from .hip import (lib, _ck, _p, _f32, _stream, _PATCH_DTYPES, Conv, _gpu_device, _one_gpu, _rd, _wr)
+from .hip import (lib, _ck, _p, _f32, _stream, _PATCH_DTYPES, Conv, _gpu_device, _one_gpu, _rd, _wr, slot_counts)
 from .hip_encoder import _pack_conv
 
 
@@ -464,8 +464,9 @@ def attn_pool_supported(R, D):
     return bool(lib().ipsx_attn_pool_supported(int(R), int(D)))
 
 
-def _attn_pool_args(x, A, keep):
-    """Checks (x (B, M, D), A (R, D), keep (B, R, M) | None) -> B, M, D, R."""
+def _attn_pool_args(x, A, keep, count=None):
+    """Checks (x (B, M, D), A (R, D), keep (B, R, M) | None, count | None) -> B, M, D, R, count (``slot_counts``: an int32
+    (B,) tensor on x's device, or None)."""
     for name, t in (("x", x), ("A", A), ("keep", keep)):
         if t is None:
             continue
@@ -483,7 +484,9 @@ def _attn_pool_args(x, A, keep):
         raise ValueError("the attention pool takes R = H * n_token in 1 .. 32 and D a multiple of 32 up to 1024, got R = {}, D = {}".format(R, D))
     if keep is not None and tuple(keep.shape) != (B, R, M):
         raise ValueError("keep: expected {}, got {}".format((B, R, M), tuple(keep.shape)))
-    return B, M, D, R
+    if count is not None:
+        count = slot_counts("attn_pool", count, B, M, x.device)
+    return B, M, D, R, count
 
 
 def _attn_pool_workspace(B, M, R, D, device):
@@ -493,21 +496,28 @@ def _attn_pool_workspace(B, M, R, D, device):
     return torch.empty(nb, dtype=torch.uint8, device=device), nb
 
 
-def attn_pool_forward(x, A, keep=None):
+def attn_pool_forward(x, A, keep=None, count=None):
     """Z[b, r] = sum_m P'[b, r, m] x[b, m] with P = softmax_m(x . A[r]), P' = P * keep, of float32 embeddings ``x`` (B, M, D),
-    the folded query ``A`` (R, D) and attention-dropout factors ``keep`` (B, R, M) or None: -> (Z (B, R, D), P (B, R, M))."""
-    B, M, D, R = _attn_pool_args(x, A, keep)
+    the folded query ``A`` (R, D) and attention-dropout factors ``keep`` (B, R, M) or None: -> (Z (B, R, D), P (B, R, M)).
+    ``count`` (B ints or an integer tensor (B,); None = all M): image b's rows are its first count[b] ones - the softmax runs
+    over them, P[b, :, count[b]:] is +0.0, the rows beyond are never read (ipsx_attn_pool_forward_counted).  Host counts are
+    checked before any launch (ValueError); a tensor on the GPU is not read back, the kernels clamp its entries into 1 .. M."""
+    B, M, D, R, count = _attn_pool_args(x, A, keep, count)
     Z = torch.empty((B, R, D), dtype=torch.float32, device=x.device)
     P = torch.empty((B, R, M), dtype=torch.float32, device=x.device)
     ws, nb = _attn_pool_workspace(B, M, R, D, x.device)
+    if count is not None:
+        _ck(lib().ipsx_attn_pool_forward_counted(_p(x), _p(A), _p(keep), _p(count), B, M, R, D, _p(Z), _p(P), _p(ws), nb, _stream()),
+            "ipsx_attn_pool_forward_counted")
+        return Z, P
     _ck(lib().ipsx_attn_pool_forward(_p(x), _p(A), _p(keep), B, M, R, D, _p(Z), _p(P), _p(ws), nb, _stream()), "ipsx_attn_pool_forward")
     return Z, P
 
 
-def attn_pool_backward(x, A, keep, P, Z, dZ, want_dx=True):
+def attn_pool_backward(x, A, keep, P, Z, dZ, want_dx=True, count=None):
     """The gradients of ``attn_pool_forward``'s Z: -> (dx (B, M, D) | None, dA (R, D)); ``P``, ``Z`` are what the forward
-    returned for the same ``x``, ``A``, ``keep``."""
-    B, M, D, R = _attn_pool_args(x, A, keep)
+    returned for the same ``x``, ``A``, ``keep``, ``count``.  With ``count``, dx[b, count[b]:] is exactly zero."""
+    B, M, D, R, count = _attn_pool_args(x, A, keep, count)
     for name, t, shape in (("P", P, (B, R, M)), ("Z", Z, (B, R, D)), ("dZ", dZ, (B, R, D))):
         if t.dtype != torch.float32 or not _gpu_device(t.device) or t.device != x.device or tuple(t.shape) != shape:
             raise ValueError("{}: expected float32 {} on the call's GPU, got {} {}".format(name, shape, t.dtype, tuple(t.shape)))
@@ -516,6 +526,10 @@ def attn_pool_backward(x, A, keep, P, Z, dZ, want_dx=True):
     dx = torch.empty_like(x) if want_dx else None
     dA = torch.empty((R, D), dtype=torch.float32, device=x.device)
     ws, nb = _attn_pool_workspace(B, M, R, D, x.device)
+    if count is not None:
+        _ck(lib().ipsx_attn_pool_backward_counted(_p(x), _p(A), _p(keep), _p(count), _p(P), _p(Z), _p(dZ), B, M, R, D, _p(dx), _p(dA), _p(ws),
+                                                  nb, _stream()), "ipsx_attn_pool_backward_counted")
+        return dx, dA
     _ck(lib().ipsx_attn_pool_backward(_p(x), _p(A), _p(keep), _p(P), _p(Z), _p(dZ), B, M, R, D, _p(dx), _p(dA), _p(ws), nb, _stream()),
         "ipsx_attn_pool_backward")
     return dx, dA

@@ -56,38 +56,47 @@ def supported(transf):
     return hip.attn_pool_supported(ca.H * ca.n_token, D)
 
 
-def aten_pool(x, A, keep=None):
-    """The pool in ATen ops (any device and dtype): what ``_AttnPool`` computes, and the definition of its backward."""
-    P = torch.softmax(torch.matmul(x, A.t()), dim=1).transpose(1, 2)          # (B, R, M)
+def aten_pool(x, A, keep=None, count=None):
+    """The pool in ATen ops (any device and dtype): what ``_AttnPool`` computes, and the definition of its backward.
+    ``count`` (an integer tensor (B,), or B ints): image b's softmax runs over its rows m < count[b]; the others are filled
+    with -inf first, so they get probability +0.0, add nothing to Z and receive gradient 0."""
+    L = torch.matmul(x, A.t())                                                # (B, M, R)
+    if count is not None:
+        beyond = torch.arange(x.shape[1], device=x.device)[None, :] >= torch.as_tensor(count, device=x.device)[:, None]
+        L = L.masked_fill(beyond[:, :, None], float("-inf"))
+    P = torch.softmax(L, dim=1).transpose(1, 2)                               # (B, R, M)
     if keep is not None:
         P = P * keep
     return torch.matmul(P, x)
 
 
 class _AttnPool(torch.autograd.Function):
-    """Z = pool(x, A, keep) as ONE node.  Saved: x by reference, A, keep, P (B, R, M), Z."""
+    """Z = pool(x, A, keep, count) as ONE node.  Saved: x by reference, A, keep, count, P (B, R, M), Z."""
 
     @staticmethod
-    def forward(ctx, x, A, keep):
-        Z, P = hip.attn_pool_forward(x, A, keep)
-        ctx.save_for_backward(x, A, keep, P, Z)
+    def forward(ctx, x, A, keep, count=None):
+        if count is not None:          # (checked once, on the way in: the backward gets the device tensor)
+            count = hip.slot_counts("attn_pool", count, x.shape[0], x.shape[1], x.device)
+        Z, P = hip.attn_pool_forward(x, A, keep, count)
+        ctx.save_for_backward(x, A, keep, count, P, Z)
         return Z
 
     @staticmethod
     def backward(ctx, dZ):
-        x, A, keep, P, Z = ctx.saved_tensors
-        dx, dA = hip.attn_pool_backward(x, A, keep, P, Z, dZ.contiguous(), want_dx=ctx.needs_input_grad[0])
-        return dx, dA if ctx.needs_input_grad[1] else None, None
+        x, A, keep, count, P, Z = ctx.saved_tensors
+        dx, dA = hip.attn_pool_backward(x, A, keep, P, Z, dZ.contiguous(), want_dx=ctx.needs_input_grad[0], count=count)
+        return dx, dA if ctx.needs_input_grad[1] else None, None, None
 
 
-def hip_pool(x, A, keep=None):
-    return _AttnPool.apply(x if x.is_contiguous() else x.contiguous(), A.contiguous(), keep)
+def hip_pool(x, A, keep=None, count=None):
+    return _AttnPool.apply(x if x.is_contiguous() else x.contiguous(), A.contiguous(), keep, count)
 
 
-def forward(transf, x, keep=None, pool=None):
+def forward(transf, x, keep=None, pool=None, count=None):
     """``transf.mlp(transf.crs_attn(x))`` of (B, M, D) embeddings -> (B, n_token, D), the (B, M) part as one node.
     ``keep``: the attention-dropout factors (B, H * n_token, M); drawn here when the attention dropout is active.
-    ``pool``: another evaluation of ``aten_pool`` (default: the HIP node)."""
+    ``pool``: another evaluation of ``aten_pool`` (default: the HIP node).
+    ``count``: the filled slots per image (``aten_pool``); handed to ``pool`` as its fourth argument when given."""
     ca = transf.crs_attn
     B, M, D = x.shape
     H, T = ca.H, ca.n_token
@@ -96,7 +105,8 @@ def forward(transf, x, keep=None, pool=None):
     drop = ca.attention.dropout
     if keep is None and drop.training and drop.p > 0:
         keep = F.dropout(torch.ones((B, H * T, M), dtype=x.dtype, device=x.device), drop.p, True)
-    Z = (hip_pool if pool is None else pool)(x, A, keep)
+    pool = hip_pool if pool is None else pool
+    Z = pool(x, A, keep) if count is None else pool(x, A, keep, count)
     ctx = torch.matmul(Z.view(B, H, T, D), ca.v_w.weight.view(H, ca.D_v, D).transpose(1, 2))          # (B, H, T, D_v)
     ctx = ctx.transpose(1, 2).contiguous().view(B, T, -1)
     out = ca.dropout(ca.fc(ctx))

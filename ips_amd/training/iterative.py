@@ -63,7 +63,11 @@ def compute_loss(net, mem_patch, mem_pos_enc, criterions, labels, conf, mem_emb=
     """Predictions, mean of the task losses, and [losses, predictions, labels] per task for the log [65-103].
 
     softmax heads: NLL of log(p + eps); sigmoid heads: BCE on flattened probabilities."""
-    preds = net(mem_patch, mem_pos_enc) if mem_emb is None else net(mem_patch, mem_pos_enc, mem_emb=mem_emb)
+    more = {} if mem_emb is None else {'mem_emb': mem_emb}
+    # conf.mask_padding (not in the reference): after a pad=True selection the aggregator attends to the filled slots only
+    if getattr(conf, 'mask_padding', False) and getattr(net, 'last_mem_count', None) is not None:
+        more['mem_count'] = net.last_mem_count
+    preds = net(mem_patch, mem_pos_enc, **more)
     tasks = list(conf.tasks.values())
     loss, per_task, shown = 0, [], []
     for task in tasks:
