@@ -140,7 +140,10 @@ extern "C" {
  *         own (an addition, the minor number stays);
  *         ipsx_aggregate_counted, ipsx_attn_pool_forward_counted, ipsx_attn_pool_backward_counted - the masked aggregator:
  *         image b of a zero-padded batch (IPSNet.ips_ragged(pad=True)) attends to its first count[b] slots only, in the
- *         eval aggregation and in the training step's attention pool (additions, the minor number stays) */
+ *         eval aggregation and in the training step's attention pool (additions, the minor number stays);
+ *         ipsx_projector_train_forward_indexed, ipsx_projector_wgrad_indexed - the masked encoder pass: the training step's
+ *         projector reads the filled rows of a zero-padded batch where they lie, through a row index, every intermediate
+ *         packed (additions, the minor number stays) */
 #define IPSX_VERSION 306
 
 #define IPSX_OK            0
@@ -1186,6 +1189,19 @@ int64_t ipsx_projector_wgrad_max_rows(int f, int d, int dtype);
 size_t ipsx_projector_wgrad_workspace_bytes(int64_t n, int f, int d);
 int ipsx_projector_wgrad(const void* x, int dtype, const float* dz, const float* stats, int64_t n, int f, int d, float* dw,
                          float* db, int accumulate, void* workspace, size_t workspace_bytes, void* stream);
+/* The row-indexed forms (the masked encoder pass): packed row j of stats / z / partial / dz is computed from source row
+ * index[j] of the (src_rows, F) tensor x; index holds n flat int32 row numbers, one outside [0, src_rows) is clamped into it
+ * (the rule of ipsx_projector_stats_indexed, whose statistics these calls take).  Slabs (64 packed rows), chunks, k order and
+ * every tree of additions are those of the packed rows: z, shift, partial, dw and db are the bits of the plain calls on the
+ * gathered tensor x[index], and no source row outside index is read.  A weight-gradient slice takes the matching n entries
+ * of index with the WHOLE source.  The kernels address the source with 32-bit buffer offsets: src_rows * F * element size
+ * must stay below 2 GiB - 64 KiB, a larger source is refused (IPSX_EINVAL) - gather the rows and take the plain calls. */
+int ipsx_projector_train_forward_indexed(const ipsx_conv* lin, const float* weight, const void* x, int dtype, const int32_t* index,
+                                         int64_t src_rows, int64_t n, const float* stats, float* z, float* shift, float* partial,
+                                         void* stream);
+int ipsx_projector_wgrad_indexed(const void* x, int dtype, const int32_t* index, int64_t src_rows, const float* dz,
+                                 const float* stats, int64_t n, int f, int d, float* dw, float* db, int accumulate, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 
 /* The cross-attention aggregator of the training step on folded queries (architecture/transformer.py:43-109 under
  * autograd).  x: (B, M, D) float32 embeddings; A: (R, D) the scaled query folded into k_w, R = H * n_token rows in the order

@@ -116,6 +116,7 @@ class IPSNet(nn.Module):
         # additions that do not change the drop-in surface
         self._reset_last()            # what the last selection left behind: nothing yet
         self._plan = None             # packed-weight cache of the HIP encoder
+        self._filled_rows = None      # forward(mask_encoder=True): (key, (int64 rows, int32 rows)) of the last counts (_filled_index)
         self._selection = None        # the HIP selection pipelines (ips_amd/selection.py), built on first use
         self._device_patches = None   # lazy loading: the device copy of the host tensor, when it is kept
         # uint8 patch storage (ips_amd/quant.py): the (n_chan, 256) float32 table of set_patch_table - a plain tensor
@@ -253,8 +254,29 @@ class IPSNet(nn.Module):
                 preds[task['name']] = layer(embeddings[:, task['id']])
         return preds
 
-    def _embed(self, x):
-        """(P, C, h, w) | (P, F)  ->  (P, D) with the encoder's CURRENT mode."""
+    def _fused_projector(self, x, n):
+        """Does the with-grad pass over ``n`` rows of the features ``x`` run on the fused projector node
+        (training/fused_projector.py)?  ROCm device, a feature net's encoder in training mode, grad enabled, a projector the
+        kernels take, 2-d features that need no gradient, more than one row."""
+        if not (hip.on_device(x) and self.encoder.training and not self.is_image and torch.is_grad_enabled()):
+            return False
+        from ..training import fused_projector
+        if getattr(self, "_fused_train_ok", None) is None:
+            self._fused_train_ok = fused_projector.supported(self.encoder)
+        return self._fused_train_ok and fused_projector.enabled() and x.dim() == 2 and n > 1 and not x.requires_grad
+
+    def _embed(self, x, rows=None):
+        """(P, C, h, w) | (P, F)  ->  (P, D) with the encoder's CURRENT mode.  ``rows`` (the pair of ``_filled_index``: the same
+        row numbers into ``x`` as int64 and as int32; the masked encoder pass of ``forward(mask_encoder=True)``):
+        -> (n_fill, D), the encoder on ``x[rows]`` alone - through the fused projector's row index where that node runs,
+        everywhere else on the gathered copy."""
+        if rows is not None:
+            rows64, rows32 = rows
+            if self._fused_projector(x, rows32.numel()):
+                from ..training import fused_projector
+                if fused_projector.rows_supported(x, rows32):
+                    return fused_projector.encode(self.encoder, x, rows=rows32)
+            x = x.index_select(0, rows64)
         if hip.on_device(x) and not self.encoder.training and not (
                 torch.is_grad_enabled() and any(p.requires_grad for p in self.encoder.parameters())):
             return self.plan.encode(x, table=self._table_for(x))
@@ -268,13 +290,10 @@ class IPSNet(nn.Module):
                 self._fused_train_ok = fused_encoder.supported(self.encoder)
             if self._fused_train_ok and fused_encoder.enabled():
                 return fused_encoder.encode(self.encoder, x)
-        if hip.on_device(x) and self.encoder.training and not self.is_image and torch.is_grad_enabled():
+        if self._fused_projector(x, x.shape[0]):
             # the same step of a feature net: LayerNorm + Linear + BatchNorm1d + ReLU as one node, half-stored rows read typed
             from ..training import fused_projector
-            if getattr(self, "_fused_train_ok", None) is None:
-                self._fused_train_ok = fused_projector.supported(self.encoder)
-            if self._fused_train_ok and fused_projector.enabled() and x.dim() == 2 and x.shape[0] > 1 and not x.requires_grad:
-                return fused_projector.encode(self.encoder, x)
+            return fused_projector.encode(self.encoder, x)
         if not self.is_image and x.dtype in (torch.float16, torch.bfloat16):
             x = x.float()      # half-stored features (IPSX_PRECISION=bf16): the stock modules compute on the exact widening
         return self.encoder(x).flatten(1)
@@ -616,21 +635,70 @@ class IPSNet(nn.Module):
         return self._mem_count
 
     # ---------------------------------------------------------------- aggregation
-    def forward(self, mem_patch, mem_pos=None, mem_emb=None, mem_count=None):
+    def _filled_counts(self, mem_count, B, M):
+        """The checked counts of ``forward(mask_encoder=True)`` -> a tuple of B host ints; nothing is launched or put on a
+        device.  Refuses: no counts, a count tensor on a GPU (the packed sizes are host numbers; reading it back would
+        synchronise), another length than B, an entry outside 1 .. M, one filled row in all under an encoder in training mode."""
+        if mem_count is None:
+            raise ValueError("mask_encoder=True needs mem_count: the filled slots of every slide")
+        if torch.is_tensor(mem_count) and mem_count.device.type != "cpu":
+            raise ValueError("mask_encoder=True needs mem_count on the host (a sequence of ints or a CPU tensor): the packed "
+                             "sizes are host numbers, and reading a device tensor back would synchronise")
+        counts = tuple(hip.slot_counts("forward(mask_encoder=True)", mem_count, B, M, torch.device("cpu")).tolist())
+        if sum(counts) == 1 and self.encoder.training:
+            raise ValueError("Expected more than 1 value per channel when training, got ONE filled row in the batch "
+                             "(mask_encoder=True: BatchNorm's batch statistics are taken over the filled rows)")
+        return counts
+
+    def _filled_index(self, counts, M, device):
+        """-> (rows64, rows32): the flat row numbers ``cat_b(range(b * M, b * M + counts[b]))`` on ``device``, as int64 for ATen
+        and as int32 for the fused projector.  Built once per (counts, M, device) and kept."""
+        key = (counts, M, torch.device(device))
+        kept = self._filled_rows
+        if kept is None or kept[0] != key:
+            rows = torch.cat([torch.arange(b * M, b * M + c, dtype=torch.int64) for b, c in enumerate(counts)]).to(device)
+            kept = self._filled_rows = (key, (rows, rows.to(torch.int32)))
+        return kept[1]
+
+    def _embed_filled(self, flat, rows):
+        """The masked encoder pass: the encoder, in its current mode, on the filled rows of ``flat`` only (``rows``: the pair of
+        ``_filled_index``) -> (B * M, D) with the padding slots exactly +0.0 (ATen ``index_copy`` into zeros: its backward
+        gathers the filled rows' gradient, the padding's is exactly 0)."""
+        packed = self._embed(flat, rows)
+        return packed.new_zeros((flat.shape[0], packed.shape[1])).index_copy(0, rows[0], packed)
+
+    def forward(self, mem_patch, mem_pos=None, mem_emb=None, mem_count=None, mask_encoder=False):
         """Embed the M selected patches, aggregate, classify (reference :264-283).
 
         ``mem_count`` (optional, not in the reference): the filled slots of every slide of a zero-padded buffer - after a
         ``pad=True`` selection ``net(mem_patch, mem_pos, mem_count=net.last_mem_count)``.  Handed to the aggregator
         (``Transformer.forward(x, count=)``): slide b is classified from its first mem_count[b] slots only, as the solo call
-        on them would classify it; the padding is still embedded, but nothing of it reaches the prediction.  None (the
+        on them would classify it; the padding is still embedded (with the encoder in training mode it takes part in the
+        BatchNorm batch statistics, the running-statistics update and the weight gradients: ``mask_encoder``).  None (the
         default; ``last_mem_count`` is never read here): every slot is attended to, as in the reference.
+
+        ``mask_encoder`` (optional, not in the reference; needs ``mem_count`` as B host integers): the encoder pass runs on
+        the filled rows only - ``emb = zeros(B * M, D); emb[rows] = _embed(flat[rows])`` with
+        ``rows = cat_b(range(b * M, b * M + mem_count[b]))``.  In training mode the batch statistics, the ``running_*``
+        update, ``num_batches_tracked`` and every parameter gradient are those of the encoder on the sum(mem_count) filled rows;
+        nothing at or beyond ``mem_count[b]`` is read, whatever it holds; the padding slots of the embedding are exactly
+        +0.0.  Refused before anything is launched (ValueError): no ``mem_count``, counts on a GPU, of another length than B
+        or outside 1 .. M, and ONE filled row in all with the encoder in training mode (BatchNorm's batch statistics need
+        more than one value per channel).  With ``mem_emb`` and the encoder in eval mode there is no encoder pass and the flag
+        has nothing to do.  False (the default): every route runs as without the argument.
 
         ``mem_emb`` (optional, not in the reference): embeddings of ``mem_patch`` already computed by ``ips()``
         in eval mode (``last_mem_emb``); used instead of a second encoder pass when the encoder is in eval
         mode, ignored in train mode where BatchNorm uses batch statistics and the pass carries gradients."""
         B, M = mem_patch.shape[:2]
+        counts = self._filled_counts(mem_count, B, M) if mask_encoder else None
         if mem_emb is None or self.encoder.training:
-            mem_emb = self._embed(mem_patch.reshape(-1, *mem_patch.shape[2:])).view(B, M, -1)
+            flat = mem_patch.reshape(-1, *mem_patch.shape[2:])
+            if counts is None:
+                mem_emb = self._embed(flat)
+            else:           # (the index is built here: with mem_emb handed to an eval-mode encoder the flag has nothing to do)
+                mem_emb = self._embed_filled(flat, self._filled_index(counts, M, mem_patch.device))
+            mem_emb = mem_emb.view(B, M, -1)
         if torch.is_tensor(mem_pos):
             mem_emb = mem_emb + mem_pos
         if mem_count is not None:

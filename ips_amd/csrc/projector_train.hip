@@ -19,6 +19,12 @@
 // sign marks the rows the no-grad path centres).
 //
 // Rows stored as float16 / bfloat16 are widened exactly in the operand load: the bits of the same values passed as float32.
+//
+// INDEXED instantiations (ipsx_projector_train_forward_indexed, ipsx_projector_wgrad_indexed): packed row j of
+// stats / z / dz is computed from source row index[j] of x - the filled slots of a zero-padded batch, read where they lie.
+// Slabs, chunks, k order and every tree of additions are those of the packed rows, so the results are the bits of the plain
+// kernels on the gathered copy x[index].  Only the x operand's address changes; the `false` instantiations are the plain
+// kernels.  The source is addressed with 32-bit buffer offsets: a source of 2 GiB or more is refused.
 
 #include <algorithm>
 
@@ -87,17 +93,22 @@ struct PtFwdArgs {
     const float* shift;        // c_out: the column sums are taken around it
     float* z;                  // (n, c_out)
     float* partial;            // this launch's first slab of [slabs][2][c_out]
+    const int32_t* index;      // INDEXED: the source row of this launch's every row (x: the whole source, x_bytes its size)
+    unsigned src_rows;
     unsigned n;
     unsigned x_bytes, w_bytes;
     int c_in, c_out, kgs;
 };
+
+// source row of an index entry: a number outside [0, src_rows) is clamped into it (the rule of ipsx_projector_stats_indexed)
+__device__ __forceinline__ unsigned pt_src_row(int32_t ix, unsigned src_rows) { return min((unsigned)max(ix, 0), src_rows - 1u); }
 
 template <int NTW>
 struct PtStage {
     pt_f32x4 a0, a1, b[NTW];
 };
 
-template <typename T, int NTW>
+template <typename T, int NTW, bool INDEXED>
 __global__ __launch_bounds__(256, 2) void projector_train_fwd_kernel(PtFwdArgs a) {
     const int lane = threadIdx.x & 63, half = lane >> 5, i = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -109,8 +120,13 @@ __global__ __launch_bounds__(256, 2) void projector_train_fwd_kernel(PtFwdArgs a
     const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.wp), 0, (int)a.w_bytes, 0x00020000);
     const unsigned r0 = m_base + (unsigned)i, r1 = r0 + 32u;
     const bool ok0 = r0 < a.n, ok1 = r1 < a.n;
-    const unsigned pv0 = ok0 ? (r0 * (unsigned)a.c_in + 4u * half) * (unsigned)sizeof(T) : kPtOob;
-    const unsigned pv1 = ok1 ? (r1 * (unsigned)a.c_in + 4u * half) * (unsigned)sizeof(T) : kPtOob;
+    unsigned x0 = r0, x1 = r1;                                      // where the lane's two rows lie in x
+    if constexpr (INDEXED) {                                        // resolved once, in front of the k-loop
+        x0 = ok0 ? pt_src_row(a.index[r0], a.src_rows) : 0u;
+        x1 = ok1 ? pt_src_row(a.index[r1], a.src_rows) : 0u;
+    }
+    const unsigned pv0 = ok0 ? (x0 * (unsigned)a.c_in + 4u * half) * (unsigned)sizeof(T) : kPtOob;
+    const unsigned pv1 = ok1 ? (x1 * (unsigned)a.c_in + 4u * half) * (unsigned)sizeof(T) : kPtOob;
     const float mean0 = ok0 ? a.stats[r0].x : 0.0f, mean1 = ok1 ? a.stats[r1].x : 0.0f;      // (a row that is not there: 0 - 0)
     const unsigned lb = lane * 16u;
     unsigned wb[NTW];                                               // a tile beyond C_out re-reads the last real one,
@@ -200,10 +216,11 @@ __global__ __launch_bounds__(256, 2) void projector_train_fwd_kernel(PtFwdArgs a
 // One wavefront per column, the lanes split F (coalesced reads of the row of W).
 constexpr int PT_SHIFT_ROWS = 8;
 
-template <typename T>
+template <typename T, bool INDEXED>
 __global__ __launch_bounds__(256) void projector_train_shift_kernel(const T* __restrict__ x, const float* __restrict__ w,
                                                                     const float* __restrict__ bias, const float2* __restrict__ stats, int k,
-                                                                    int c_in, int c_out, float* __restrict__ shift) {
+                                                                    int c_in, int c_out, float* __restrict__ shift,
+                                                                    const int32_t* __restrict__ index, unsigned src_rows) {
     const int lane = threadIdx.x & 63;
     const int o = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
     if (o >= c_out) return;                                         // wave-uniform; no barrier below
@@ -213,7 +230,7 @@ __global__ __launch_bounds__(256) void projector_train_shift_kernel(const T* __r
     for (int u = 0; u < PT_SHIFT_ROWS; ++u) {                       // (a row that is not there repeats the last one; not added)
         const int r = min(u, k - 1);
         mean[u] = stats[r].x;
-        xr[u] = x + (size_t)r * c_in;
+        xr[u] = x + (size_t)(INDEXED ? pt_src_row(index[r], src_rows) : (unsigned)r) * c_in;
         acc[u] = 0.0f;
     }
     const float* wr = w + (size_t)o * c_in;
@@ -253,14 +270,17 @@ struct PtWgArgs {
     long long n;
     int f, d;
     int f_regions, regions;    // regions = o_regions * f_regions
+    const int32_t* index;      // INDEXED: the source row of every row of dz / stats (x: the whole source, x_bytes its size)
+    unsigned src_rows, x_bytes;
 };
 
 struct PtWgStage {
     float a0, a1, b0, b1;
     float2 st;
+    int32_t ix;                // INDEXED: the index entry of the row this slot loads NEXT (requested one ring turn ahead)
 };
 
-template <typename T>
+template <typename T, bool INDEXED>
 __global__ __launch_bounds__(PW_WAVES * 64) void projector_wgrad_kernel(PtWgArgs a) {
     const int lane = threadIdx.x & 63, half = lane >> 5, i = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -272,8 +292,13 @@ __global__ __launch_bounds__(PW_WAVES * 64) void projector_wgrad_kernel(PtWgArgs
     const long long left = a.n - row_lo;
     const unsigned rows = (unsigned)(left < PW_CHUNK ? left : PW_CHUNK);
     // the chunk's rows as buffers of their own: what lies beyond them - the next chunk's rows - reads as zeros
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
+    // (INDEXED: x is the whole source, a row's base comes from the index, itself a buffer bounded to the chunk)
+    const __amdgpu_buffer_rsrc_t rx = INDEXED
+        ? __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.x), 0, (int)a.x_bytes, 0x00020000)
+        : __builtin_amdgcn_make_buffer_rsrc(
         const_cast<T*>(static_cast<const T*>(a.x) + (size_t)row_lo * a.f), 0, (int)(rows * (unsigned)a.f * (unsigned)sizeof(T)), 0x00020000);
+    __amdgpu_buffer_rsrc_t ri = rx;                                  // (the plain kernel has no index: never read there)
+    if constexpr (INDEXED) ri = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(a.index + row_lo), 0, (int)(rows * 4u), 0x00020000);
     const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.dz + (size_t)row_lo * a.d), 0,
                                                                         (int)(rows * (unsigned)a.d * 4u), 0x00020000);
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2*>(a.stats + row_lo), 0, (int)(rows * 8u), 0x00020000);
@@ -296,11 +321,29 @@ __global__ __launch_bounds__(PW_WAVES * 64) void projector_wgrad_kernel(PtWgArgs
     // chains of a quarter of the length round less than one, at the same instruction count
     float db0[4] = {0.0f, 0.0f, 0.0f, 0.0f}, db1[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 
+    // INDEXED: this lane's row of the pair being issued (its half's), and where the index of the pair one ring turn on lies
+    unsigned prow = (unsigned)half, soffi = 0u;
+    const unsigned vi = (unsigned)half * 4u, xrow = (unsigned)a.f * (unsigned)sizeof(T);
+    const unsigned cx0 = (unsigned)(f0 + i) * (unsigned)sizeof(T), cx1 = cx0 + 32u * (unsigned)sizeof(T);
+    const unsigned out1 = f0 + 32 + i < a.f ? 0u : kPtOob;
     auto issue = [&](PtWgStage& s) {
         s.a0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ry, (int)vy0, (int)soffy, 0));
         s.a1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ry, (int)vy1, (int)soffy, 0));
-        s.b0 = pt_load1<T>(rx, vx0, soffx);
-        s.b1 = pt_load1<T>(rx, vx1, soffx);
+        if constexpr (INDEXED) {
+            // a row beyond the chunk must read zeros as it does in the plain kernel: its index entry reads as 0, which is
+            // a real source row (0 * NaN is not 0), so the lane goes to the out-of-range offset instead
+            // (the source is below 2 GiB: OR-ing the marker's bit in is the select, and stays straight-line code)
+            const unsigned out = prow < rows ? 0u : kPtOob;
+            const unsigned base = pt_src_row(s.ix, a.src_rows) * xrow;
+            s.b0 = pt_load1<T>(rx, (base + cx0) | out, 0u);
+            s.b1 = pt_load1<T>(rx, (base + cx1) | out | out1, 0u);
+            s.ix = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(ri, (int)vi, (int)(soffi + 32u), 0);      // (4 pairs x 8 bytes on)
+            prow += 2u;
+            soffi += 8u;
+        } else {
+            s.b0 = pt_load1<T>(rx, vx0, soffx);
+            s.b1 = pt_load1<T>(rx, vx1, soffx);
+        }
         const pt_u32x2 u = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)vs, (int)soffs, 0);
         s.st = make_float2(__uint_as_float(u[0]), __uint_as_float(u[1]));
         soffy += ystride;
@@ -320,6 +363,12 @@ __global__ __launch_bounds__(PW_WAVES * 64) void projector_wgrad_kernel(PtWgArgs
     };
     const int steps = (int)((rows + 1u) >> 1);
     PtWgStage s0, s1, s2, s3;
+    if constexpr (INDEXED) {                                        // the first ring turn's index entries
+        s0.ix = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(ri, (int)vi, 0, 0);
+        s1.ix = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(ri, (int)vi, 8, 0);
+        s2.ix = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(ri, (int)vi, 16, 0);
+        s3.ix = (int32_t)__builtin_amdgcn_raw_buffer_load_b32(ri, (int)vi, 24, 0);
+    }
     issue(s0);
     issue(s1);
     issue(s2);
@@ -395,51 +444,88 @@ IPSX_API int ipsx_projector_train_supported(int f, int d) { return pt_shape(f, d
 
 IPSX_API int64_t ipsx_projector_train_slabs(int64_t n) { return n > 0 ? cdiv(n, 64) : 0; }
 
-IPSX_API int ipsx_projector_train_forward(const ipsx_conv* lin, const float* weight, const void* x, int dtype, int64_t n,
-                                          const float* stats, float* z, float* shift, float* partial, void* stream) {
-    IPSX_REQUIRE(lin && lin->w_packed && lin->shift && weight && x && stats && z && shift && partial && n > 0,
-                 "projector_train_forward: bad arguments");
+// a source the INDEXED kernels address with 32-bit buffer offsets: below 2 GiB (less the margin of pt_rows_per_launch)
+static bool pt_source_fits(int64_t src_rows, int f, int esize) {
+    return src_rows > 0 && src_rows < ((int64_t)1 << 31) && src_rows * f * esize <= ((int64_t)1 << 31) - 65536;
+}
+
+template <typename T, bool INDEXED>
+static void pt_launch_shift(const void* x, const float* weight, const ipsx_conv* lin, const float2* st2, int k, float* shift, const int32_t* index,
+                            int64_t src_rows, hipStream_t s) {
+    projector_train_shift_kernel<T, INDEXED><<<dim3((unsigned)cdiv(lin->c_out, 4)), dim3(256), 0, s>>>(
+        static_cast<const T*>(x), weight, lin->shift, st2, k, lin->c_in, lin->c_out, shift, index, (unsigned)src_rows);
+}
+
+template <typename T, bool INDEXED>
+static void pt_launch_fwd(const PtFwdArgs& a, hipStream_t s) {
+    const unsigned mt = (unsigned)cdiv((int64_t)a.n, 64);
+    if (a.c_out >= 512) projector_train_fwd_kernel<T, 4, INDEXED><<<dim3(mt, (unsigned)cdiv(a.c_out, 512)), dim3(256), 0, s>>>(a);
+    else projector_train_fwd_kernel<T, 2, INDEXED><<<dim3(mt, (unsigned)cdiv(a.c_out, 256)), dim3(256), 0, s>>>(a);
+}
+
+// FN<T, INDEXED>(...) for the call's dtype and index
+#define PT_DISPATCH(FN, ...)                                    \
+    do {                                                        \
+        if (index) {                                            \
+            if (dtype == 0) FN<float, true>(__VA_ARGS__);       \
+            else if (dtype == 1) FN<__bf16, true>(__VA_ARGS__); \
+            else FN<_Float16, true>(__VA_ARGS__);               \
+        } else {                                                \
+            if (dtype == 0) FN<float, false>(__VA_ARGS__);      \
+            else if (dtype == 1) FN<__bf16, false>(__VA_ARGS__);\
+            else FN<_Float16, false>(__VA_ARGS__);              \
+        }                                                       \
+    } while (0)
+
+// the one host path of ipsx_projector_train_forward (index NULL) and ipsx_projector_train_forward_indexed
+static int pt_forward(const char* what, const ipsx_conv* lin, const float* weight, const void* x, int dtype, const int32_t* index,
+                      int64_t src_rows, int64_t n, const float* stats, float* z, float* shift, float* partial, void* stream) {
+    IPSX_REQUIRE(lin && lin->w_packed && lin->shift && weight && x && stats && z && shift && partial && n > 0, "%s: bad arguments", what);
     IPSX_REQUIRE(lin->kh == 1 && lin->kw == 1 && lin->stride == 1 && lin->pad == 0 && !lin->alpha,
-                 "projector_train_forward: lin is a Linear with its bias in `shift` and no affine");
-    IPSX_REQUIRE(dtype >= 0 && dtype <= 2, "projector_train_forward: dtype %d (0 float32, 1 bfloat16, 2 float16)", dtype);
+                 "%s: lin is a Linear with its bias in `shift` and no affine", what);
+    IPSX_REQUIRE(dtype >= 0 && dtype <= 2, "%s: dtype %d (0 float32, 1 bfloat16, 2 float16)", what, dtype);
     const int f = lin->c_in, d = lin->c_out;
-    IPSX_REQUIRE(pt_shape(f, d), "projector_train_forward: F = %d (a multiple of 32), D = %d (a power of two, 32 .. 1024)", f, d);
+    IPSX_REQUIRE(pt_shape(f, d), "%s: F = %d (a multiple of 32), D = %d (a power of two, 32 .. 1024)", what, f, d);
     const int esize = dtype == 0 ? 4 : 2;
+    IPSX_REQUIRE(!index || pt_source_fits(src_rows, f, esize),
+                 "%s: a source of %lld rows is not below 2 GiB (32-bit buffer offsets): gather the rows and take the plain call", what,
+                 (long long)src_rows);
     hipStream_t s = as_stream(stream);
     const float2* st2 = reinterpret_cast<const float2*>(stats);
-    const dim3 sg((unsigned)cdiv(d, 4)), sb(256);
     const int k = (int)std::min<int64_t>(n, PT_SHIFT_ROWS);
-    if (dtype == 0) projector_train_shift_kernel<float><<<sg, sb, 0, s>>>(static_cast<const float*>(x), weight, lin->shift, st2, k, f, d, shift);
-    else if (dtype == 1) projector_train_shift_kernel<__bf16><<<sg, sb, 0, s>>>(static_cast<const __bf16*>(x), weight, lin->shift, st2, k, f, d, shift);
-    else projector_train_shift_kernel<_Float16><<<sg, sb, 0, s>>>(static_cast<const _Float16*>(x), weight, lin->shift, st2, k, f, d, shift);
-    IPSX_TRY(launched("projector_train_forward (shift)"));
+    PT_DISPATCH(pt_launch_shift, x, weight, lin, st2, k, shift, index, src_rows, s);
+    IPSX_TRY(launched(what));
+    // (packed rows per launch: z below 2 GiB, and the plain call's x)
     const int64_t per = pt_rows_per_launch(f, d, esize, 64);
     for (int64_t i0 = 0; i0 < n; i0 += per) {
         const int64_t cnt = std::min(per, n - i0);
         PtFwdArgs a;
-        a.x = static_cast<const char*>(x) + (size_t)i0 * f * esize;
+        a.x = index ? x : static_cast<const char*>(x) + (size_t)i0 * f * esize;
         a.wp = lin->w_packed; a.bias = lin->shift; a.stats = st2 + i0; a.shift = shift;
         a.z = z + (size_t)i0 * d;
         a.partial = partial + (size_t)(i0 / 64) * 2 * d;
+        a.index = index ? index + i0 : nullptr;
+        a.src_rows = index ? (unsigned)src_rows : 0u;
         a.n = (unsigned)cnt;
-        a.x_bytes = (unsigned)(cnt * f * esize);
+        a.x_bytes = (unsigned)((index ? src_rows : cnt) * f * esize);
         a.w_bytes = (unsigned)(cdiv(d, 32) * (int64_t)(f / 8) * 1024);
         a.c_in = f; a.c_out = d; a.kgs = f / 8;
-        const unsigned mt = (unsigned)cdiv(cnt, 64);
-        if (d >= 512) {
-            const dim3 grid(mt, (unsigned)cdiv(d, 512));
-            if (dtype == 0) projector_train_fwd_kernel<float, 4><<<grid, dim3(256), 0, s>>>(a);
-            else if (dtype == 1) projector_train_fwd_kernel<__bf16, 4><<<grid, dim3(256), 0, s>>>(a);
-            else projector_train_fwd_kernel<_Float16, 4><<<grid, dim3(256), 0, s>>>(a);
-        } else {
-            const dim3 grid(mt, (unsigned)cdiv(d, 256));
-            if (dtype == 0) projector_train_fwd_kernel<float, 2><<<grid, dim3(256), 0, s>>>(a);
-            else if (dtype == 1) projector_train_fwd_kernel<__bf16, 2><<<grid, dim3(256), 0, s>>>(a);
-            else projector_train_fwd_kernel<_Float16, 2><<<grid, dim3(256), 0, s>>>(a);
-        }
-        IPSX_TRY(launched("projector_train_forward"));
+        PT_DISPATCH(pt_launch_fwd, a, s);
+        IPSX_TRY(launched(what));
     }
     return IPSX_OK;
+}
+
+IPSX_API int ipsx_projector_train_forward(const ipsx_conv* lin, const float* weight, const void* x, int dtype, int64_t n,
+                                          const float* stats, float* z, float* shift, float* partial, void* stream) {
+    return pt_forward("projector_train_forward", lin, weight, x, dtype, nullptr, 0, n, stats, z, shift, partial, stream);
+}
+
+IPSX_API int ipsx_projector_train_forward_indexed(const ipsx_conv* lin, const float* weight, const void* x, int dtype, const int32_t* index,
+                                                  int64_t src_rows, int64_t n, const float* stats, float* z, float* shift, float* partial,
+                                                  void* stream) {
+    IPSX_REQUIRE(index, "projector_train_forward_indexed: bad arguments");
+    return pt_forward("projector_train_forward_indexed", lin, weight, x, dtype, index, src_rows, n, stats, z, shift, partial, stream);
 }
 
 IPSX_API int64_t ipsx_projector_wgrad_chunk_rows(void) { return PW_CHUNK; }
@@ -454,31 +540,54 @@ IPSX_API size_t ipsx_projector_wgrad_workspace_bytes(int64_t n, int f, int d) {
     return (size_t)cdiv(n, PW_CHUNK) * ((size_t)d * f + d) * sizeof(float);
 }
 
-IPSX_API int ipsx_projector_wgrad(const void* x, int dtype, const float* dz, const float* stats, int64_t n, int f, int d, float* dw,
-                                  float* db, int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
-    IPSX_REQUIRE(x && dz && stats && dw && db && n > 0, "projector_wgrad: bad arguments");
-    IPSX_REQUIRE(dtype >= 0 && dtype <= 2, "projector_wgrad: dtype %d (0 float32, 1 bfloat16, 2 float16)", dtype);
-    IPSX_REQUIRE(pt_shape(f, d), "projector_wgrad: F = %d (a multiple of 32), D = %d (a power of two, 32 .. 1024)", f, d);
+template <typename T, bool INDEXED>
+static void pt_launch_wgrad(const PtWgArgs& a, dim3 grid, dim3 block, hipStream_t s) {
+    projector_wgrad_kernel<T, INDEXED><<<grid, block, 0, s>>>(a);
+}
+
+// the one host path of ipsx_projector_wgrad (index NULL) and ipsx_projector_wgrad_indexed
+static int pt_wgrad(const char* what, const void* x, int dtype, const int32_t* index, int64_t src_rows, const float* dz, const float* stats,
+                    int64_t n, int f, int d, float* dw, float* db, int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+    IPSX_REQUIRE(x && dz && stats && dw && db && n > 0, "%s: bad arguments", what);
+    IPSX_REQUIRE(dtype >= 0 && dtype <= 2, "%s: dtype %d (0 float32, 1 bfloat16, 2 float16)", what, dtype);
+    IPSX_REQUIRE(pt_shape(f, d), "%s: F = %d (a multiple of 32), D = %d (a power of two, 32 .. 1024)", what, f, d);
     IPSX_REQUIRE(n <= ipsx_projector_wgrad_max_rows(f, d, dtype),
-                 "projector_wgrad: %lld rows exceed one 2 GiB buffer - call per slice of whole chunks (ipsx_projector_wgrad_max_rows) with "
-                 "accumulate = 1", (long long)n);
+                 "%s: %lld rows exceed one 2 GiB buffer - call per slice of whole chunks (ipsx_projector_wgrad_max_rows) with "
+                 "accumulate = 1", what, (long long)n);
+    const int esize = dtype == 0 ? 4 : 2;
+    IPSX_REQUIRE(!index || pt_source_fits(src_rows, f, esize),
+                 "%s: a source of %lld rows is not below 2 GiB (32-bit buffer offsets): gather the rows and take the plain call", what,
+                 (long long)src_rows);
     const size_t need = ipsx_projector_wgrad_workspace_bytes(n, f, d);
-    if (!workspace || workspace_bytes < need)
-        return fail(IPSX_EWORKSPACE, "projector_wgrad: workspace %zu B < %zu B", workspace_bytes, need);
+    if (!workspace || workspace_bytes < need) return fail(IPSX_EWORKSPACE, "%s: workspace %zu B < %zu B", what, workspace_bytes, need);
     PtWgArgs a;
     a.x = x; a.dz = dz; a.stats = reinterpret_cast<const float2*>(stats); a.partial = static_cast<float*>(workspace);
     a.n = n; a.f = f; a.d = d;
     a.f_regions = (int)cdiv(f, PW_BF);
     a.regions = a.f_regions * (int)cdiv(d, PW_BO);
+    a.index = index;
+    a.src_rows = index ? (unsigned)src_rows : 0u;
+    a.x_bytes = index ? (unsigned)(src_rows * f * esize) : 0u;
     const int chunks = (int)cdiv(n, PW_CHUNK);
     hipStream_t s = as_stream(stream);
     const dim3 grid((unsigned)(a.regions * chunks)), block(PW_WAVES * 64);
-    if (dtype == 0) projector_wgrad_kernel<float><<<grid, block, 0, s>>>(a);
-    else if (dtype == 1) projector_wgrad_kernel<__bf16><<<grid, block, 0, s>>>(a);
-    else projector_wgrad_kernel<_Float16><<<grid, block, 0, s>>>(a);
-    IPSX_TRY(launched("projector_wgrad"));
+    PT_DISPATCH(pt_launch_wgrad, a, grid, block, s);
+    IPSX_TRY(launched(what));
     const size_t dw_elems = (size_t)d * f, total = dw_elems + d;
     projector_wgrad_reduce_kernel<<<dim3((unsigned)cdiv((int64_t)total, 256)), dim3(256), 0, s>>>(a.partial, chunks, total, dw_elems, dw, db,
                                                                                                   accumulate ? 1 : 0);
-    return launched("projector_wgrad reduce");
+    return launched(what);
+}
+
+IPSX_API int ipsx_projector_wgrad(const void* x, int dtype, const float* dz, const float* stats, int64_t n, int f, int d, float* dw,
+                                  float* db, int accumulate, void* workspace, size_t workspace_bytes, void* stream) {
+    return pt_wgrad("projector_wgrad", x, dtype, nullptr, 0, dz, stats, n, f, d, dw, db, accumulate, workspace, workspace_bytes, stream);
+}
+
+IPSX_API int ipsx_projector_wgrad_indexed(const void* x, int dtype, const int32_t* index, int64_t src_rows, const float* dz,
+                                          const float* stats, int64_t n, int f, int d, float* dw, float* db, int accumulate, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    IPSX_REQUIRE(index, "projector_wgrad_indexed: bad arguments");
+    return pt_wgrad("projector_wgrad_indexed", x, dtype, index, src_rows, dz, stats, n, f, d, dw, db, accumulate, workspace, workspace_bytes,
+                    stream);
 }

@@ -480,6 +480,10 @@ _EXPORTS = {
     "ipsx_projector_wgrad_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
     "ipsx_projector_wgrad": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "ipsx_projector_train_forward_indexed": (C.c_int, [C.POINTER(Conv), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ipsx_projector_wgrad_indexed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                               C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "ipsx_attn_pool_supported": (C.c_int, [C.c_int, C.c_int]),
     "ipsx_attn_pool_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int, C.c_int]),
     "ipsx_attn_pool_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p,
@@ -2099,4 +2103,4 @@ def head(emb, token, linear, act):
 # ------------------------------------------------------------------ the encoder plan and the training step's kernels
 # (modules of their own since round 6; every name stays reachable as ``hip.<name>``)
 from .hip_encoder import (EncoderPlan, _PlanHold, _bn_affine, _pack_conv, encoder_kernel_name)          # noqa: E402,F401
-from .hip_train import (attn_pool_backward, attn_pool_forward, attn_pool_supported, PackJob, _BN_MAX_SLABS, _BN_WS_FLOATS, _CL, _PACK_BATCH_MAX, _WGRAD_MAX_BYTES, _bn_workspace_floats, _pack_conv_view, _rows_cl, bn_train_backward, bn_train_forward, bn_train_forward_partials, bn_train_supported, conv2d_nhwc, conv2d_nhwc_dgrad, conv2d_nhwc_wgrad, conv_lds_supported, conv_train_supported, maxpool_3x3s2_bwd_nhwc, maxpool_3x3s2_nhwc, maxpool_train_supported, pack_conv_views, projector_train_forward, projector_train_supported, projector_wgrad)          # noqa: E402,F401
+from .hip_train import (attn_pool_backward, attn_pool_forward, attn_pool_supported, PackJob, _BN_MAX_SLABS, _BN_WS_FLOATS, _CL, _PACK_BATCH_MAX, _WGRAD_MAX_BYTES, _bn_workspace_floats, _pack_conv_view, _rows_cl, bn_train_backward, bn_train_forward, bn_train_forward_partials, bn_train_supported, conv2d_nhwc, conv2d_nhwc_dgrad, conv2d_nhwc_wgrad, conv_lds_supported, conv_train_supported, maxpool_3x3s2_bwd_nhwc, maxpool_3x3s2_nhwc, maxpool_train_supported, pack_conv_views, projector_train_forward, projector_train_index_supported, projector_train_supported, projector_wgrad)          # noqa: E402,F401

@@ -389,11 +389,44 @@ def _feature_rows(x, f):
     return x if x.is_contiguous() else x.contiguous()
 
 
-def projector_train_forward(x, weight, bias, ln_eps):
+_PT_INDEX_SOURCE_BYTES = (1 << 31) - 65536        # what the indexed kernels address with 32-bit buffer offsets (include/ipsx.h)
+
+
+def projector_train_index_supported(x):
+    """Do ``projector_train_forward`` / ``projector_wgrad`` take ``x`` as the SOURCE of a row index - below 2 GiB?  (A larger
+    source goes through a gathered copy and the plain calls.)"""
+    return x.numel() * x.element_size() <= _PT_INDEX_SOURCE_BYTES
+
+
+def _row_index(what, index, x):
+    """The row index of the projector's indexed calls: int32, 1-D, at least one entry.  An index that lies on
+    the HOST is a host-built one: its entries are checked here against ``x``'s rows, then it is copied to ``x``'s device.  An
+    index on ``x``'s GPU is taken where it lies, its entries unread (the kernels clamp them); another device is refused."""
+    if not torch.is_tensor(index) or index.dtype != torch.int32:
+        raise TypeError("{}: index must be an int32 tensor, got {}".format(what, index.dtype if torch.is_tensor(index) else type(index)))
+    if index.dim() != 1 or index.numel() == 0:
+        raise ValueError("{}: index must be 1-d with at least one entry, got {}".format(what, tuple(index.shape)))
+    if not projector_train_index_supported(x):
+        raise ValueError("{}: a source of {} rows is not below 2 GiB - gather the rows and take the plain call".format(what, x.shape[0]))
+    if index.device.type == "cpu":
+        lo, hi = int(index.min()), int(index.max())
+        if lo < 0 or hi >= x.shape[0]:
+            raise ValueError("{}: index entries must lie in [0, {}), got {}".format(what, x.shape[0], lo if lo < 0 else hi))
+        return index.to(x.device).contiguous()
+    if index.device != x.device:
+        raise ValueError("{}: index lies on {}, the rows on {}".format(what, index.device, x.device))
+    return index if index.is_contiguous() else index.contiguous()
+
+
+def projector_train_forward(x, weight, bias, ln_eps, index=None):
     """z = Linear(LayerNorm(x)) of (rows, F) feature rows (float32, or float16 / bfloat16 widened in the operand load) with
     the (D, F) ``weight`` and ``bias``, for the BatchNorm1d behind it in batch-statistics mode:
     -> (z, stats, partial, slabs, shift) - ``stats`` (rows, 2) the rows' (mean, rstd), all that backward needs of the
-    LayerNorm; ``partial`` (slabs, 2, D) the column sums of z around ``shift`` for ``bn_train_forward_partials``."""
+    LayerNorm; ``partial`` (slabs, 2, D) the column sums of z around ``shift`` for ``bn_train_forward_partials``.
+
+    ``index`` (int32, 1-d; ``_row_index``): row j of every result is computed from row ``index[j]`` of ``x``, read where it
+    lies - the bits of ``projector_train_forward(x[index], ...)`` without the copy (``ipsx_projector_stats_indexed``,
+    ``ipsx_projector_train_forward_indexed``); rows of ``x`` outside the index are not read."""
     _one_gpu("projector_train_forward", x=x, weight=weight, bias=bias)
     if weight.dim() != 2 or bias.dim() != 1 or bias.shape[0] != weight.shape[0]:
         raise ValueError("projector_train_forward: weight (D, F) and bias (D,), got {} and {}".format(tuple(weight.shape), tuple(bias.shape)))
@@ -401,20 +434,31 @@ def projector_train_forward(x, weight, bias, ln_eps):
     if not projector_train_supported(f, d):
         raise ValueError("the training projector takes F % 32 == 0 and D a power of two in 32 .. 1024, got F = {}, D = {}".format(f, d))
     x = _feature_rows(x, f)
-    n = x.shape[0]
+    if index is not None:
+        index = _row_index("projector_train_forward", index, x)
+    n = x.shape[0] if index is None else index.numel()
     w = _f32(weight.detach())
     b = _f32(bias.detach())
     packed = _pack_conv(w.view(d, f, 1, 1))
     lin = Conv(f, d, 1, 1, 1, 0, _p(packed), None, _p(b), None, None)
     stats = torch.empty((n, 2), dtype=torch.float32, device=x.device)
-    _ck(lib().ipsx_projector_stats_typed(_p(x), _PATCH_DTYPES[x.dtype], n, f, C.c_float(ln_eps), _p(stats), _stream()),
-        "ipsx_projector_stats_typed")
+    if index is None:
+        _ck(lib().ipsx_projector_stats_typed(_p(x), _PATCH_DTYPES[x.dtype], n, f, C.c_float(ln_eps), _p(stats), _stream()),
+            "ipsx_projector_stats_typed")
+    else:
+        _ck(lib().ipsx_projector_stats_indexed(_p(x), _PATCH_DTYPES[x.dtype], _p(index), x.shape[0], n, f, C.c_float(ln_eps), _p(stats),
+                                               _stream()), "ipsx_projector_stats_indexed")
     slabs = int(lib().ipsx_projector_train_slabs(n))
     z = torch.empty((n, d), dtype=torch.float32, device=x.device)
     partial = torch.empty((slabs, 2, d), dtype=torch.float32, device=x.device)
     shift = torch.empty(d, dtype=torch.float32, device=x.device)
-    _ck(lib().ipsx_projector_train_forward(C.byref(lin), _p(w), _p(x), _PATCH_DTYPES[x.dtype], n, _p(stats), _p(z), _p(shift),
-                                           _p(partial), _stream()), "ipsx_projector_train_forward")
+    if index is None:
+        _ck(lib().ipsx_projector_train_forward(C.byref(lin), _p(w), _p(x), _PATCH_DTYPES[x.dtype], n, _p(stats), _p(z), _p(shift),
+                                               _p(partial), _stream()), "ipsx_projector_train_forward")
+    else:
+        _ck(lib().ipsx_projector_train_forward_indexed(C.byref(lin), _p(w), _p(x), _PATCH_DTYPES[x.dtype], _p(index), x.shape[0], n,
+                                                       _p(stats), _p(z), _p(shift), _p(partial), _stream()),
+            "ipsx_projector_train_forward_indexed")
     return z, stats, partial, slabs, shift
 
 
@@ -429,18 +473,25 @@ def _projector_wgrad_slice_rows(f, d, dtype):
     return step
 
 
-def projector_wgrad(x, dz, stats):
+def projector_wgrad(x, dz, stats, index=None):
     """The gradient of ``projector_train_forward``'s z w.r.t. weight and bias -> (dw (D, F), db (D,)): dw = sum over the rows
     of (dz |rstd|)^T (x - mean), on the fp32 matrix cores from the raw rows.  Activations of 2 GiB and more go in slices of
-    whole rows, each call adding its chunks onto the result in order: the bits of one call (csrc/projector_train.hip)."""
+    whole rows, each call adding its chunks onto the result in order: the bits of one call (csrc/projector_train.hip).
+
+    ``index`` (as ``projector_train_forward`` takes it): ``dz`` and ``stats`` are packed - row j goes with row ``index[j]`` of
+    ``x`` - and the result is the bits of ``projector_wgrad(x[index], dz, stats)`` (``ipsx_projector_wgrad_indexed``; a slice
+    takes the matching slice of the index)."""
     _one_gpu("projector_wgrad", x=x, dz=dz, stats=stats)
     if dz.dim() != 2 or x.dim() != 2:
         raise ValueError("projector_wgrad: x (rows, F) and dz (rows, D), got {} and {}".format(tuple(x.shape), tuple(dz.shape)))
     n, d = dz.shape
     f = x.shape[1]
     x = _feature_rows(x, f)
-    if dz.dtype != torch.float32 or x.shape[0] != n or tuple(stats.shape) != (n, 2) or stats.dtype != torch.float32:
-        raise ValueError("dz: expected float32 ({}, D), statistics of the same rows".format(x.shape[0]))
+    if index is not None:
+        index = _row_index("projector_wgrad", index, x)
+    rows = x.shape[0] if index is None else index.numel()
+    if dz.dtype != torch.float32 or rows != n or tuple(stats.shape) != (n, 2) or stats.dtype != torch.float32:
+        raise ValueError("dz: expected float32 ({}, D), statistics of the same rows".format(rows))
     stats = _rd("projector_wgrad", "stats", stats, align=8)          # ((mean, rstd) pairs: 8-byte loads)
     if not projector_train_supported(f, d):
         raise ValueError("the training projector takes F % 32 == 0 and D a power of two in 32 .. 1024, got F = {}, D = {}".format(f, d))
@@ -452,8 +503,13 @@ def projector_wgrad(x, dz, stats):
     ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
     for i0 in range(0, n, step):
         cnt = min(step, n - i0)
-        _ck(lib().ipsx_projector_wgrad(_p(x[i0:i0 + cnt]), _PATCH_DTYPES[x.dtype], _p(dz[i0:i0 + cnt]), _p(stats[i0:i0 + cnt]), cnt, f, d,
-                                       _p(dw), _p(db), int(i0 > 0), _p(ws), nb, _stream()), "ipsx_projector_wgrad")
+        if index is None:
+            _ck(lib().ipsx_projector_wgrad(_p(x[i0:i0 + cnt]), _PATCH_DTYPES[x.dtype], _p(dz[i0:i0 + cnt]), _p(stats[i0:i0 + cnt]), cnt, f,
+                                           d, _p(dw), _p(db), int(i0 > 0), _p(ws), nb, _stream()), "ipsx_projector_wgrad")
+        else:
+            _ck(lib().ipsx_projector_wgrad_indexed(_p(x), _PATCH_DTYPES[x.dtype], _p(index[i0:i0 + cnt]), x.shape[0], _p(dz[i0:i0 + cnt]),
+                                                   _p(stats[i0:i0 + cnt]), cnt, f, d, _p(dw), _p(db), int(i0 > 0), _p(ws), nb, _stream()),
+                "ipsx_projector_wgrad_indexed")
     return dw, db
 
 

@@ -18,6 +18,10 @@ batch statistics cost no pass; BatchNorm + ReLU and their backward are ``ipsx_bn
 
 Results equal the stock path to fp32 rounding (another summation order): tests/test_train_projector.py.
 ``IPSX_TRAIN_PROJECTOR=0`` switches it off.
+
+``encode(encoder, x, rows=)`` is the masked encoder pass: the node on the rows ``x[rows]`` alone - the filled
+slots of a zero-padded batch - read where they lie through the int32 index, every intermediate packed at ``rows.numel()``
+rows; the bits of ``encode(encoder, x[rows])`` without the gathered copy.
 """
 import os
 
@@ -54,11 +58,12 @@ class _Projector(torch.autograd.Function):
     reference, (mean, rstd) per row, z, y and the BatchNorm's batch statistics."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, gamma, beta, ln_eps, bn):
-        z, stats, partial, slabs, shift = hip.projector_train_forward(x, weight, bias, ln_eps)
+    def forward(ctx, x, weight, bias, gamma, beta, ln_eps, bn, rows):
+        z, stats, partial, slabs, shift = hip.projector_train_forward(x, weight, bias, ln_eps, index=rows)
         y, mean, invstd = hip.bn_train_forward_partials(z, None, gamma, beta, bn.eps, bn.momentum, bn.running_mean,
                                                         bn.running_var, True, partial, slabs, shift)
         ctx.save_for_backward(x, stats, z, y, gamma, mean, invstd)
+        ctx.rows = rows                  # (an index, not an activation: kept by reference like x)
         return y
 
     @staticmethod
@@ -68,17 +73,28 @@ class _Projector(torch.autograd.Function):
         dz, _, dgamma, dbeta = hip.bn_train_backward(dy, y, z, gamma, mean, invstd, True, False)
         dw = db = None
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dw, db = hip.projector_wgrad(x, dz, stats)
+            dw, db = hip.projector_wgrad(x, dz, stats, index=ctx.rows)
         return (None, dw if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None,
-                dgamma if ctx.needs_input_grad[3] else None, dbeta if ctx.needs_input_grad[4] else None, None, None)
+                dgamma if ctx.needs_input_grad[3] else None, dbeta if ctx.needs_input_grad[4] else None, None, None, None)
 
 
-def encode(encoder, x):
+def rows_supported(x, rows):
+    """Does ``encode(encoder, x, rows=rows)`` take this source and index?  More than one row (the BatchNorm's batch statistics
+    need two values per channel) of a source the indexed kernels can address (below 2 GiB)."""
+    return rows.numel() > 1 and hip.projector_train_index_supported(x)
+
+
+def encode(encoder, x, rows=None):
     """(P, F) feature rows (float32 / float16 / bfloat16) -> (P, D) embeddings; same value as ``encoder(x.float())`` in
-    train mode, with the same in-place update of the BatchNorm's running statistics and ``num_batches_tracked``."""
+    train mode, with the same in-place update of the BatchNorm's running statistics and ``num_batches_tracked``.
+
+    ``rows`` (int32, 1-d, on ``x``'s device, entries in [0, P)): -> the packed (rows.numel(), D) embeddings of ``x[rows]``, the
+    batch statistics, the running-statistics update and every gradient those of these rows alone; no other row of ``x`` is
+    read.  The caller scatters the packed result where it wants it (``IPSNet._embed_filled``: ATen ``index_copy`` into
+    zeros, whose backward gathers the packed ``dy``)."""
     ln, lin, bn, _ = encoder.children()
     if x.requires_grad:
         raise ValueError("the fused projector has no data gradient: the features must not require grad")
-    y = _Projector.apply(x, lin.weight, lin.bias, bn.weight, bn.bias, ln.eps, bn)
+    y = _Projector.apply(x, lin.weight, lin.bias, bn.weight, bn.bias, ln.eps, bn, rows)
     bn.num_batches_tracked += 1
     return y

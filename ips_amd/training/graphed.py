@@ -8,7 +8,10 @@ arithmetic and its order are exactly the eager ones (same kernels, same argument
 
 What capture needs and how it is met:
   * static inputs: the (B, M, ...) patch buffer, positional buffer and label buffers of ``init_batch`` are copied into
-    graph-owned tensors before each replay (a partial last batch - ``shrink_batch`` - falls back to the eager step);
+    graph-owned tensors before each replay (a partial last batch - ``shrink_batch`` - falls back to the eager step, and
+    so does a batch under ``mask_padding: 'encoder'`` whose selection left a count: the masked encoder pass is packed at
+    the filled rows, a size that changes from batch to batch.  ``mask_padding: True`` is NOT honoured by a replayed step:
+    the capture calls ``net(patches, pos)`` without a count, so only the eager fallbacks mask the aggregator);
   * an optimizer whose step does not read host scalars: ``AdamW(capturable=True)`` with the learning rate in a device
     tensor, refreshed from the value ``adjust_learning_rate`` wrote (reference utils/utils.py:14-31);
   * warm-up iterations on a side stream before capture: parameters, BatchNorm statistics, optimizer state and the RNG
@@ -120,7 +123,9 @@ class GraphedStep:
     # ------------------------------------------------------------------ the step
     def __call__(self, mem_patch, mem_pos_enc, labels):
         conf = self.conf
-        if not (mem_patch.is_cuda and mem_patch.shape[0] == conf.B):     # CPU, or the shrunk last batch of an epoch
+        packed = getattr(conf, 'mask_padding', False) == 'encoder' and getattr(self.net, 'last_mem_count', None) is not None
+        if packed or not (mem_patch.is_cuda and mem_patch.shape[0] == conf.B):     # CPU, the shrunk last batch of an epoch, or
+            # the masked encoder pass (its packed size is this batch's own)
             self._sync_lr()
             return self._eager(mem_patch, mem_pos_enc, labels)
         key = (tuple(mem_patch.shape), torch.is_tensor(mem_pos_enc), tuple(sorted(labels)))

@@ -64,9 +64,12 @@ def compute_loss(net, mem_patch, mem_pos_enc, criterions, labels, conf, mem_emb=
 
     softmax heads: NLL of log(p + eps); sigmoid heads: BCE on flattened probabilities."""
     more = {} if mem_emb is None else {'mem_emb': mem_emb}
-    # conf.mask_padding (not in the reference): after a pad=True selection the aggregator attends to the filled slots only
+    # conf.mask_padding (not in the reference): after a pad=True selection the aggregator attends to the filled slots only;
+    # 'encoder': the encoder pass runs on the filled rows only as well (BatchNorm statistics, weight gradients: DESIGN 2.6.2)
     if getattr(conf, 'mask_padding', False) and getattr(net, 'last_mem_count', None) is not None:
         more['mem_count'] = net.last_mem_count
+        if conf.mask_padding == 'encoder':
+            more['mask_encoder'] = True
     preds = net(mem_patch, mem_pos_enc, **more)
     tasks = list(conf.tasks.values())
     loss, per_task, shown = 0, [], []
