@@ -22,7 +22,7 @@ import os
 import torch
 
 from . import hip
-from .shuffle import draw_shuffle
+from .shuffle import draw_shuffle_for
 
 
 class Ragged:
@@ -138,34 +138,48 @@ def refuse(what):
     raise TypeError("{} takes (B, N, ...) tensors: a Ragged batch goes through IPSNet.ips_ragged".format(what))
 
 
+def _refuse_short(b, n, M, pad):
+    """The slide ``b`` of ``n`` rows that no ragged call - ``ips_ragged``, ``ips_image_ragged``, a ragged stream's
+    ``finish`` - makes a rectangular batch with: no more rows than the memory without ``pad``, no rows at all with it."""
+    if pad and n == 0:
+        raise ValueError("slide {} has no rows: nothing to pad".format(b))
+    if n <= M and not pad:
+        raise ValueError("slide {} has {} rows and the memory M = {}: the reference returns all {} of them there, the "
+                         "batch would not be rectangular (select such a slide with ips())".format(b, n, M, n))
+
+
+def _leave_count(net, lengths, pad):
+    """``last_mem_count`` of a ragged call: the filled slots of every slide after ``pad``, else None."""
+    net._mem_count = tuple(min(n, net.M) for n in lengths) if pad else None
+
+
 def _check(net, slides, pad=False):
-    """Everything ``ips_ragged`` refuses, before the first launch and before the first random number is drawn.  ``pad``:
-    slides with N_b <= M are taken (never shuffled, so 'instance' shuffling with positions does not refuse them); an empty
-    slide is not."""
-    if len(slides) == 0:
+    _check_facts(net, slides.lengths, slides.dtype, tuple(slides.rows.shape), pad)
+
+
+def _check_facts(net, lengths, dtype, rows_shape, pad):
+    """Everything ``ips_ragged`` refuses, before the first launch and before the first random number is drawn, asked of
+    the slides' ``lengths``, the ``dtype`` and the shape of the packed rows (``ips_image_ragged``: of the grid patches).
+    ``pad``: slides with N_b <= M are taken (never shuffled, so 'instance' shuffling with positions does not refuse them);
+    an empty slide is not."""
+    if len(lengths) == 0:
         raise ValueError("ips_ragged: an empty batch")
-    if slides.dtype == torch.uint8:            # what IPSNet._check_u8 asks of the solo calls' (1, N_b, C, h, w) patches
-        if not net.is_image or slides.rows.dim() != 4:
+    if dtype == torch.uint8:                   # what IPSNet._check_u8 asks of the solo calls' (1, N_b, C, h, w) patches
+        if not net.is_image or len(rows_shape) != 4:
             raise TypeError("uint8 rows go with the (sum N_b, C, h, w) patches of an image encoder (set_patch_table), "
                             "a feature net reads float rows")
-        table = net._table_for(slides)
-        channels = getattr(slides, "channels", None)
-        channels = slides.rows.shape[1] if channels is None else channels
-        if table.shape[0] != channels:
-            raise ValueError("the patch table has {} rows, the patches {} channels".format(table.shape[0], channels))
+        table = net._table_for(torch.empty(0, dtype=dtype))
+        if table.shape[0] != rows_shape[1]:
+            raise ValueError("the patch table has {} rows, the patches {} channels".format(table.shape[0], rows_shape[1]))
         if hip.on_device(net.device) and hip.precision() != "fp32":
             raise TypeError("uint8 patches go with the exact trunk (IPSX_PRECISION=fp32), not {}".format(hip.precision()))
     if hip.dedup_blank():                     # (as streams do: whatever the device)
         raise TypeError("blank-patch dedup needs batches of one length (IPSX_DEDUP_BLANK=1 with ips_ragged)")
-    if slides.rows.dim() != (4 if net.is_image else 2):
-        raise TypeError("ips_ragged: {} rows for {}".format(tuple(slides.rows.shape), "an image encoder ((sum N_b, C, h, w))" if net.is_image
+    if len(rows_shape) != (4 if net.is_image else 2):
+        raise TypeError("ips_ragged: {} rows for {}".format(rows_shape, "an image encoder ((sum N_b, C, h, w))" if net.is_image
                                                             else "a feature net ((sum N_b, F))"))
-    for b, n in enumerate(slides.lengths):
-        if pad and n == 0:
-            raise ValueError("slide {} has no rows: nothing to pad".format(b))
-        if n <= net.M and not pad:
-            raise ValueError("slide {} has {} rows and the memory M = {}: the reference returns all {} of them there, the "
-                             "batch would not be rectangular (select such a slide with ips())".format(b, n, net.M, n))
+    for b, n in enumerate(lengths):
+        _refuse_short(b, n, net.M, pad)
         if net.use_pos and n > net.pos_enc.shape[1]:
             raise ValueError("slide {} has {} rows, the positional table conf.N = {}".format(b, n, net.pos_enc.shape[1]))
         if (net.use_pos and net.shuffle and net.shuffle_style == 'instance' and not net._shuffle_overridden()
@@ -173,94 +187,6 @@ def _check(net, slides, pad=False):
             # (shuffle_instance gathers the WHOLE table with the slide's permutation: ips() on this slide alone raises)
             raise ValueError("slide {} has {} rows: shuffle_style 'instance' with use_pos needs slides of exactly conf.N = {} "
                              "rows, as ips() does".format(b, n, net.pos_enc.shape[1]))
-
-
-def _draw(net, slides, skip=()):
-    """The permutations of a shuffled call, slide by slide in slide order, by the calls ``IPSNet._shuffle`` makes for a
-    (1, N_b, ...) input on the device the slides were handed over on -> (perms | None, copies | None): ``perms`` the B
-    (N_b,) permutations as drawn; an overridden ``do_shuffle`` is called as ever and returns shuffled COPIES
-    [(rows_b, pos_b)] instead (nothing is kept in ``last_shuffle`` then, as in ``ips()``).  ``skip``: the slides of a padded
-    call that ``ips()`` returns before it shuffles (N_b <= M) - nothing is drawn for them, they stay in the order given."""
-    if net._shuffle_overridden():
-        copies = []
-        for b in range(len(slides)):
-            if b in skip:
-                copies.append((slides[b], net.pos_enc[0, :slides.lengths[b]] if net.use_pos else None))
-                continue
-            x, p = net.do_shuffle(slides[b].unsqueeze(0), net.pos_enc if net.use_pos else None)
-            copies.append((x[0], p[0, :x.shape[1]] if torch.is_tensor(p) else None))
-        return None, copies
-    perms = []
-    for b in range(len(slides)):
-        if b in skip:
-            perms.append(None)
-            continue
-        perm = draw_shuffle(slides[b].unsqueeze(0), net.shuffle_style)
-        if perm is None:                   # an unknown style: do_shuffle leaves everything as it is
-            return None, None
-        perms.append(perm.reshape(-1))
-    drawn = [p for p in perms if p is not None]
-    if not drawn:
-        return None, None
-    return [torch.arange(slides.lengths[b], dtype=torch.int64, device=drawn[0].device) if p is None else p
-            for b, p in enumerate(perms)], None
-
-
-def _index_ok(net, rows):
-    """May the encoder read the packed rows through an int32 index (``Selection.index_supported`` for one piece)?"""
-    if os.environ.get("IPSX_SHUFFLE", "index") == "copy":
-        return False
-    if not net.is_image:
-        return rows.dtype in (torch.float32, torch.float16, torch.bfloat16)
-    plan = net.plan
-    # (uint8 rows come with their table - ``_check`` saw to it - and the list addresses bytes as it addresses floats)
-    return rows.dtype in (torch.float32, torch.uint8) and bool(plan.index_list_supported(rows.shape))
-
-
-def _packed(net, slides, skip=(), encode=True):
-    """The front of a device call, inside ``net._scoring()``: the permutations drawn (none for the slides in ``skip``), the
-    slides on the device, ONE encoder pass over all rows (``encode``) and the packed positional rows
-    -> (dev, rows, flat, emb, pos): ``flat`` int32 (total,) - packed row j of the call is row flat[j] of ``rows`` - or None;
-    ``pos`` (1, total, D) or None.  Sets ``net.last_shuffle``."""
-    device, B = net.device, len(slides)
-    perms = copies = None
-    if net.shuffle:
-        # (drawn where the slides were handed over - a host-resident Ragged draws 'instance' permutations from the CPU
-        #  generator, as its solo calls do)
-        perms, copies = _draw(net, slides, skip)
-    dev = slides.to(device)                      # a host-resident Ragged is copied whole
-    rows = dev.rows
-    flat = None                               # int32 (total,): packed row j of the call is row flat[j] of ``rows``
-    local = None                              # int64 (total,): the position inside its slide of packed row j
-    if perms is not None:
-        local = torch.cat(perms).to(device)
-        flat = (local + dev.row_base()).to(torch.int32)
-        by_index = _index_ok(net, rows)
-        # (what the solo calls keep: the device copy where they select through the index, else the permutation as drawn)
-        net.last_shuffle = [None if b in skip else (local[dev.starts[b]:dev.starts[b + 1]] if by_index else perms[b]).unsqueeze(0)
-                            for b in range(B)]
-        if not by_index:
-            rows, flat = rows.index_select(0, flat), None
-    elif copies is not None:
-        rows = torch.cat([c[0] for c in copies], 0).to(device)
-    emb = None
-    if encode:                                # one encoder pass over all rows
-        if flat is None:
-            emb = net._embed(rows)
-        elif net.is_image:
-            emb = net.plan.encode_source(hip.PatchSource(rows, net._table_for(rows)), index=flat)
-        else:
-            emb = net.plan.encode(rows, index=flat)
-    pos = None
-    if net.use_pos:
-        if copies is not None:
-            pos = torch.cat([c[1] for c in copies], 0).to(device)
-        else:
-            if local is None:
-                local = torch.arange(dev.total, dtype=torch.int64, device=device) - dev.row_base()
-            pos = net.pos_enc[0].index_select(0, local)          # positions restart at 0 in every slide
-        pos = pos.unsqueeze(0)
-    return dev, rows, flat, emb, pos
 
 
 @torch.no_grad()
@@ -275,73 +201,173 @@ def ips_ragged(net, slides, pad=False):
     if not hip.on_device(net.device) or (net.encoder.training and not net.training):
         out = _host_route(net, slides)
     else:
-        out = _device_route(net, slides, short_ok=pad)
-    net._mem_count = tuple(min(n, net.M) for n in slides.lengths) if pad else None
+        out = _device_route(net, _RowsSource(net, slides), short_ok=pad)
+    _leave_count(net, slides.lengths, pad)
     return out
+
+
+# ------------------------------------------------------------------ the padding of last_mem_emb
+def _zero_emb(net, row_shape, dtype):
+    """(1, D): the embedding of ONE all-zero row (rows stored as uint8: the padding of ``mem_patch`` is float32 +0.0, not byte 0)."""
+    return net._embed(torch.zeros((1,) + tuple(row_shape), device=net.device, dtype=torch.float32 if dtype == torch.uint8 else dtype))
+
+
+def _pad_emb(net, emb, hole, row_shape, dtype):
+    """``last_mem_emb`` of a padded device call: ``emb`` (B, M, D) with ``_zero_emb`` in the empty slots ``hole`` (B, M) - what
+    ``forward()`` in eval mode computes from the zero padding."""
+    with torch.no_grad(), net._scoring(), net.plan.hold():
+        zero = _zero_emb(net, row_shape, dtype)
+    return torch.where(hole.unsqueeze(-1), zero.view(1, 1, -1), emb)
 
 
 # ------------------------------------------------------------------ the host route
 def _host_emb(net, long_emb, short_rows):
     """``last_mem_emb`` of a call on the host route, made on first use: the solo calls' embeddings for the long slides; for
-    a short one the eval-mode embeddings of its rows in [0, N_b) and, behind them, the embedding of ONE all-zero row - what
-    ``forward()`` in eval mode computes from the zero padding."""
+    a short one the eval-mode embeddings of its rows in [0, N_b) and, behind them, ``_zero_emb``."""
     if any(e is None for e in long_emb.values()):
         return None
-    B, M = len(long_emb) + len(short_rows), net.M
-    out = zero = None
+    embs, zero = [], None
     with torch.no_grad(), net._scoring():
-        for b in range(B):
+        for b in range(len(long_emb) + len(short_rows)):
             if b in long_emb:
-                e = long_emb[b][0]
-            else:
-                rows = short_rows[b]
-                e = net._embed(rows)
-                if rows.shape[0] < M:
-                    if zero is None:           # (uint8 rows: the padding of mem_patch is float32 +0.0, not byte 0)
-                        zero = net._embed(torch.zeros((1,) + tuple(rows.shape[1:]), device=rows.device,
-                                                      dtype=torch.float32 if rows.dtype == torch.uint8 else rows.dtype))
-                    e = torch.cat((e, zero.expand(M - rows.shape[0], -1)), 0)
-            if out is None:
-                out = torch.empty((B, M, e.shape[-1]), dtype=e.dtype, device=e.device)
-            out[b] = e
-    return out
+                embs.append(long_emb[b][0])
+                continue
+            rows = short_rows[b]
+            e = net._embed(rows)
+            if rows.shape[0] < net.M:
+                zero = _zero_emb(net, rows.shape[1:], rows.dtype) if zero is None else zero
+                e = torch.cat((e, zero.expand(net.M - rows.shape[0], -1)), 0)
+            embs.append(e)
+    return torch.stack(embs)
+
+
+def _host_fill(net, lengths, row_shape, dtype, solo):
+    """The (B, M, ...) batch of a host route from what ``solo`` yields slide by slide: ``(mem_patch, mem_pos, mem_idx,
+    mem_emb)`` of the solo selection in a slide of more than M rows, else the slide's rows on the device (stored bytes
+    dequantised) - written in the order given, as ``fill_batch`` writes them, zeros and indices of -1 behind them.  Leaves
+    ``last_mem_idx`` and a lazy ``last_mem_emb``; what the solo selections left is theirs, not this call's."""
+    B, M, D, device = len(lengths), net.M, net.D, net.device
+    mem_patch = torch.zeros((B, M) + tuple(row_shape), dtype=torch.float32 if dtype == torch.uint8 else dtype, device=device)
+    mem_pos = torch.zeros((B, M, D), dtype=net.pos_enc.dtype, device=device) if net.use_pos else None
+    mem_idx = torch.full((B, M), -1, dtype=torch.int64, device=device)
+    long_emb, short_rows = {}, {}
+    for b, (n, got) in enumerate(zip(lengths, solo)):
+        if n > M:
+            p, q, idx, long_emb[b] = got
+            mem_patch[b] = p[0]
+            if net.use_pos:
+                mem_pos[b] = q[0]
+            mem_idx[b] = idx[0]
+        else:
+            short_rows[b] = got
+            mem_patch[b, :n] = got
+            if net.use_pos:
+                mem_pos[b, :n] = net.pos_enc[0, :n]
+            mem_idx[b, :n] = torch.arange(n, dtype=torch.int64, device=device)
+    net._reset_last()
+    net.last_mem_idx = mem_idx
+    net._emb_make = lambda: _host_emb(net, long_emb, short_rows)
+    return mem_patch, mem_pos
 
 
 def _host_route(net, slides):
     """The loop the contract names, a solo call per long slide, plus the padding of the short ones on ATen ops - the CPU
     plumbing path (``_select_aten`` per slide), and a ROCm device whose encoder is in training mode inside an eval-mode net
     (batch statistics: no per-row function)."""
-    B, M, D, device = len(slides), net.M, net.D, net.device
-    shape = tuple(slides.rows.shape[1:])
-    u8 = slides.dtype == torch.uint8           # (the solo calls return the selected bytes dequantised: the buffer is float32)
-    mem_patch = torch.zeros((B, M) + shape, dtype=torch.float32 if u8 else slides.dtype, device=device)
-    mem_pos = torch.zeros((B, M, D), dtype=net.pos_enc.dtype, device=device) if net.use_pos else None
-    mem_idx = torch.full((B, M), -1, dtype=torch.int64, device=device)
-    long_emb, short_rows, shuf = {}, {}, []
-    for b, n in enumerate(slides.lengths):
-        if n > M:
-            p, q = net._call(slides[b].unsqueeze(0))
-            mem_patch[b] = p[0]
-            if net.use_pos:
-                mem_pos[b] = q[0]
-            mem_idx[b] = net.last_mem_idx[0]
-            long_emb[b] = net.last_mem_emb
-            shuf.append(net.last_shuffle)
-        else:                                  # what ips() returns before it shuffles, as fill_batch writes it
-            short_rows[b] = rows = slides[b].to(device)
-            mem_patch[b, :n] = net._dequant(rows) if u8 else rows
-            if net.use_pos:
-                mem_pos[b, :n] = net.pos_enc[0, :n]
-            mem_idx[b, :n] = torch.arange(n, dtype=torch.int64, device=device)
-            shuf.append(None)
-    net._reset_last()                          # (what the last solo call left is that call's, not this one's)
+    u8, shuf = slides.dtype == torch.uint8, []
+
+    def solo():
+        for b, n in enumerate(slides.lengths):
+            if n > net.M:
+                p, q = net._call(slides[b].unsqueeze(0))
+                shuf.append(net.last_shuffle)
+                yield p, q, net.last_mem_idx, net.last_mem_emb
+            else:                              # what ips() returns before it shuffles (uint8: the bytes dequantised)
+                rows = slides[b].to(net.device)
+                shuf.append(None)
+                yield net._dequant(rows) if u8 else rows
+    out = _host_fill(net, slides.lengths, slides.rows.shape[1:], slides.dtype, solo())
     net.last_shuffle = shuf if net.shuffle and any(s is not None for s in shuf) else None
-    net.last_mem_idx = mem_idx
-    net._emb_make = lambda: _host_emb(net, long_emb, short_rows)
-    return mem_patch, mem_pos
+    return out
 
 
 # ------------------------------------------------------------------ the device route
+def _draw(net, lengths, device, skip):
+    """The permutations of a shuffled call, slide by slide in slide order, by the calls ``IPSNet._shuffle`` makes for a
+    (1, N_b, ...) input on ``device`` -> the B (N_b,) permutations as drawn, or None.  ``skip``: the slides of a padded call
+    that ``ips()`` returns before it shuffles (N_b <= M) - nothing is drawn for them, they stay in the order given."""
+    perms = [None if b in skip else draw_shuffle_for(1, n, device, net.shuffle_style) for b, n in enumerate(lengths)]
+    drawn = [p for p in perms if p is not None]
+    if not drawn:                              # (no long slide, or an unknown style: do_shuffle leaves everything as it is)
+        return None
+    return [torch.arange(n, dtype=torch.int64, device=drawn[0].device) if p is None else p.reshape(-1) for n, p in zip(lengths, perms)]
+
+
+class _RowsSource:
+    """What ``_device_route`` selects in, for ``ips_ragged``: the packed rows of a ``Ragged``.  ``ragged_image._ViewSource``
+    answers the same questions for whole images; ``rows`` (there None) are the packed rows where they exist as a tensor."""
+
+    def __init__(self, net, slides):
+        # (drawn where the slides were handed over - a host-resident Ragged draws 'instance' permutations from the CPU
+        #  generator, as its solo calls do)
+        self.net, self.given, self.draw_device = net, slides, slides.device
+        dev = slides.to(net.device)                  # a host-resident Ragged is copied whole
+        self.rows, self.lengths, self.starts, self.offsets, self.row_base = dev.rows, dev.lengths, dev.starts, dev.offsets, dev.row_base
+        self.row_shape, self.dtype = tuple(dev.rows.shape[1:]), dev.dtype
+
+    def shuffled_copies(self, skip):
+        """An overridden ``do_shuffle``, called as ever on the slides as given (not on those in ``skip``): its shuffled COPIES
+        become the rows -> their packed positional rows | None.  Nothing is kept in ``last_shuffle``, as in ``ips()``."""
+        net, rows, pos = self.net, [], []
+        for b, n in enumerate(self.lengths):
+            x, p = self.given[b], net.pos_enc[0, :n] if net.use_pos else None
+            if b not in skip:
+                x, p = net.do_shuffle(x.unsqueeze(0), net.pos_enc if net.use_pos else None)
+                x, p = x[0], p[0, :x.shape[1]] if torch.is_tensor(p) else None
+            rows.append(x)
+            pos.append(p)
+        self.rows = torch.cat(rows, 0).to(net.device)
+        return torch.cat(pos, 0).to(net.device) if net.use_pos else None
+
+    def through_index(self, flat):
+        """-> (may the encoder read the rows through the int32 ``flat`` (``Selection.index_supported`` for one piece)?, the
+        index it reads through): where it may not, the rows become the permuted copy."""
+        net, rows = self.net, self.rows
+        if os.environ.get("IPSX_SHUFFLE", "index") == "copy":
+            ok = False
+        elif not net.is_image:
+            ok = rows.dtype in (torch.float32, torch.float16, torch.bfloat16)
+        else:   # (uint8 rows come with their table - ``_check`` saw to it - and the list addresses bytes as it addresses floats)
+            ok = rows.dtype in (torch.float32, torch.uint8) and bool(net.plan.index_list_supported(rows.shape))
+        if ok:
+            return True, flat
+        self.rows = rows.index_select(0, flat)
+        return False, None
+
+    def encode(self, flat):
+        net, rows = self.net, self.rows
+        if flat is None:
+            return net._embed(rows)
+        if net.is_image:
+            return net.plan.encode_source(hip.PatchSource(rows, net._table_for(rows)), index=flat)
+        return net.plan.encode(rows, index=flat)
+
+    def finish(self, offsets, mem_idx, flat, pos):
+        """ONE launch: ``ipsx_ragged_finish``, or ``_finish_aten`` for rows that are no whole 16-byte units."""
+        net, rows, M = self.net, self.rows, self.net.M
+        if hip.ragged_finish_supported(rows, pos):
+            mem_patch, mem_pos, mem_idx, grow = hip.ragged_finish(rows, offsets, mem_idx, M, flat, pos)
+        else:
+            mem_patch, mem_pos, mem_idx, grow = _finish_aten(rows, offsets, self.lengths, mem_idx, M, flat, pos)
+        if rows.dtype == torch.uint8:
+            # the (B, M) selected byte rows leave as float32 table[c][byte]; the padding behind a short slide's rows is
+            # float32 +0.0 (what fill_batch's zero-initialised buffers hold), not table[c][0]
+            mem_patch = hip.dequant_patches(mem_patch, net._table_for(rows))
+            if min(self.lengths) < M:
+                mem_patch.masked_fill_((mem_idx < 0).view(len(self.lengths), M, 1, 1, 1), 0)
+        return mem_patch, mem_pos, mem_idx, grow
+
+
 def _finish_aten(rows, offsets, lengths, mem_idx, M, flat, pos):
     """``hip.ragged_finish`` for rows that are no whole 16-byte units: the ``gather_rows`` launches plus, where a slide is
     short, the padding on ATen ops -> the same four tensors."""
@@ -365,51 +391,52 @@ def _finish_aten(rows, offsets, lengths, mem_idx, M, flat, pos):
     return mem_patch, mem_pos, torch.where(valid, local, -1), torch.where(valid, grow, -1)
 
 
-def _device_route(net, slides, short_ok):
-    """One encoder pass over all rows, one packed logits table, ONE loop launch (the workgroups of short slides return before
-    their first read) and ONE finish launch (``ipsx_ragged_finish``: selected rows, short slides' rows in the order given,
-    the zero padding, indices and global rows).  A batch of short slides only launches no encoder, no logits and no loop."""
-    B, M, device = len(slides), net.M, net.device
-    lengths = slides.lengths
+def _device_route(net, source, short_ok):
+    """A ragged call on a ROCm device: one encoder pass over all rows of the source, one packed logits table, ONE loop launch
+    (the workgroups of short slides return before their first read) and ONE finish launch (selected rows, short slides' rows
+    in the order given, the zero padding).  A batch of short slides only launches no encoder, no logits and no loop."""
+    M, device, lengths, starts = net.M, net.device, source.lengths, source.starts
+    B = len(lengths)
     short = frozenset(b for b, n in enumerate(lengths) if n <= M)
-    any_long = len(short) < B
     with net._scoring():
         ca = net.transf.crs_attn
         with net.plan.hold():
-            dev, rows, flat, emb, pos = _packed(net, slides, skip=short, encode=any_long)
-            offsets = dev.offsets
+            offsets = source.offsets
+            flat = None                        # int32 (total,): packed row j of the call is row flat[j] of the source
+            local = None                       # int64 (total,): the position inside its slide of packed row j
+            pos = None
+            copied = net.shuffle and net._shuffle_overridden()      # (rows only: ips_image_ragged materialises the patches then)
+            if copied:
+                pos = source.shuffled_copies(short)
+            elif net.shuffle:
+                perms = _draw(net, lengths, source.draw_device, short)
+                if perms is not None:
+                    local = torch.cat(perms).to(device)
+                    by_index, flat = source.through_index((local + source.row_base()).to(torch.int32))
+                    # (what the solo calls keep: the device copy where they select through the index, else the permutation as
+                    #  drawn; a drawn call has a long slide, so the list is never all None)
+                    net.last_shuffle = [None if b in short else (local[starts[b]:starts[b + 1]] if by_index else perms[b]).unsqueeze(0)
+                                        for b in range(B)]
+            emb = source.encode(flat) if len(short) < B else None
+            if net.use_pos and not copied:
+                if local is None:
+                    local = torch.arange(starts[-1], dtype=torch.int64, device=device) - source.row_base()
+                pos = net.pos_enc[0].index_select(0, local)          # positions restart at 0 in every slide
             mem_idx = None
-            if any_long:
-                logits = hip.logits(emb.unsqueeze(0), pos, ca.folded_query(), ca.H * ca.n_token)[0]
+            if emb is not None:
+                logits = hip.logits(emb.unsqueeze(0), pos.unsqueeze(0) if pos is not None else None, ca.folded_query(), ca.H * ca.n_token)[0]
                 mem_idx = hip.scan_ragged(logits, offsets, lengths, M, net.I, ca.H, ca.n_token, short_ok=short_ok)
-        pos2 = pos[0] if pos is not None else None
-        if hip.ragged_finish_supported(rows, pos2):
-            mem_patch, mem_pos, mem_idx, grow = hip.ragged_finish(rows, offsets, mem_idx, M, flat, pos2)
-        else:
-            mem_patch, mem_pos, mem_idx, grow = _finish_aten(rows, offsets, lengths, mem_idx, M, flat, pos2)
-        if rows.dtype == torch.uint8:
-            # the (B, M) selected byte rows leave as float32 table[c][byte]; the padding behind a short slide's rows is
-            # float32 +0.0 (what fill_batch's zero-initialised buffers hold), not table[c][0]
-            mem_patch = hip.dequant_patches(mem_patch, net._table_for(rows))
-            if any(lengths[b] < M for b in short):
-                mem_patch.masked_fill_((mem_idx < 0).view(B, M, 1, 1, 1), 0)
-    if net.last_shuffle is not None and all(s is None for s in net.last_shuffle):
-        net.last_shuffle = None
+        mem_patch, mem_pos, mem_idx, grow = source.finish(offsets, mem_idx, flat, pos)
 
-    unencoded = rows if emb is None else None       # (a batch of short slides only: at most B * M rows, kept until they are read)
-    zero_row = (1,) + tuple(rows.shape[1:]), torch.float32 if rows.dtype == torch.uint8 else rows.dtype
-    padded = any(lengths[b] < M for b in short)
+    unencoded = source.rows if emb is None else None      # (a batch of short slides only: at most B * M rows, kept until they are read)
+    padded, row_shape, dtype = min(lengths) < M, source.row_shape, source.dtype
 
     def emb_of_slots():
-        """(B, M, D): the packed pass's rows (made now for a batch of short slides only); the padding holds the embedding
-        of ONE all-zero row."""
+        """(B, M, D): the packed pass's rows (made now for a batch of short slides only), the padding by ``_pad_emb``."""
         with torch.no_grad(), net._scoring(), net.plan.hold():
             table = emb if emb is not None else net._embed(unencoded)
             out = hip.gather_rows(table.unsqueeze(0), (grow.clamp(min=0) if padded else grow).view(1, B * M)).view(B, M, -1)
-            if padded:
-                zero = net._embed(torch.zeros(zero_row[0], dtype=zero_row[1], device=device))
-                out = torch.where((grow < 0).unsqueeze(-1), zero.view(1, 1, -1), out)
-        return out
+        return _pad_emb(net, out, grow < 0, row_shape, dtype) if padded else out
     net.last_mem_idx = mem_idx
     net._emb_make = emb_of_slots
     return mem_patch, mem_pos

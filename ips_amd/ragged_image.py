@@ -18,14 +18,14 @@ finish launch read the bytes where they lie through the table (the ``_u8`` expor
 bit for bit, that of the float32 images ``table[c][byte]``, which are never made, and ``mem_patch`` is float32.
 """
 
+import functools
 import os
 
 import torch
 from torch import nn
 
 from . import hip
-from .ragged import _check, ips_ragged
-from .shuffle import draw_shuffle
+from .ragged import _check_facts, _device_route, _leave_count, ips_ragged
 
 
 class RaggedImages:
@@ -141,29 +141,6 @@ def collate_ragged_images(samples, pad=False):
     return rest
 
 
-class _Grids:
-    """The grids of a call as ``ragged._check`` reads slides: "rows" are grid patches."""
-
-    class _Rows:
-        @staticmethod
-        def dim():
-            return 4
-        shape = ("sum ny_b nx_b", "C", "ph", "pw")
-
-    def __init__(self, lengths, dtype, channels):
-        self.lengths, self.dtype, self.channels, self.rows = tuple(lengths), dtype, channels, self._Rows()
-
-    def __len__(self):
-        return len(self.lengths)
-
-
-class _Drawn:
-    """What ``draw_shuffle`` reads of the (1, N_b, ...) patches of an image: their shape and device."""
-
-    def __init__(self, n, device):
-        self.shape, self.device = (1, n), device
-
-
 def _encoder_channels(net):
     for m in net.encoder.modules():
         if isinstance(m, nn.Conv2d):
@@ -171,27 +148,8 @@ def _encoder_channels(net):
     return None
 
 
-def _draw(net, lengths, device, skip):
-    """The permutations of a shuffled call, image by image in image order, by the calls ``IPSNet._shuffle`` makes for the
-    (1, N_b, ...) patches of one image on ``device`` -> [(N_b,) permutation as drawn] | None (``ragged._draw`` on grids:
-    nothing is drawn for the images in ``skip``, they stay in grid order)."""
-    perms = []
-    for b, n in enumerate(lengths):
-        if b in skip:
-            perms.append(None)
-            continue
-        perm = draw_shuffle(_Drawn(n, device), net.shuffle_style)
-        if perm is None:                   # an unknown style: do_shuffle leaves everything as it is
-            return None
-        perms.append(perm.reshape(-1))
-    drawn = [p for p in perms if p is not None]
-    if not drawn:
-        return None
-    return [torch.arange(lengths[b], dtype=torch.int64, device=drawn[0].device) if p is None else p for b, p in enumerate(perms)]
-
-
 def ragged_dedup(env, plan, rview):
-    """Does the packed encoder pass of ``_viewed_route`` take the exact blank-patch dedup (``encode_source(dedup=True)``,
+    """Does the packed encoder pass of ``_ViewSource`` take the exact blank-patch dedup (``encode_source(dedup=True)``,
     DESIGN 2.8)?  A function of the environment (a mapping), the net's ``EncoderPlan`` and the call's ``hip.RaggedView``
     alone: under ``IPSX_DEDUP_BLANK`` unset or ``auto`` (``0``: plain launches; ``1`` never gets here, ``ragged._check``
     refuses it), and only where the plan's trunk for the view's patch shape is the fused 1x32x32 one - the layered trunks
@@ -217,7 +175,8 @@ def ips_image_ragged(net, images, patch_size, patch_stride, pad=False):
         raise ValueError("images have {} channels, the encoder expects {}".format(images.channels, c_in))
     grids = images.grids(patch_size, patch_stride)
     lengths = tuple(ny * nx for ny, nx in grids)
-    _check(net, _Grids(lengths, images.dtype, images.channels), pad)   # (uint8: a table of C rows, the exact trunk)
+    # ("rows" are grid patches; uint8: a table of C rows, the exact trunk)
+    _check_facts(net, lengths, images.dtype, (sum(lengths), images.channels) + tuple(int(v) for v in patch_size), pad)
     net._reset_last()
 
     rview = None
@@ -231,60 +190,41 @@ def ips_image_ragged(net, images, patch_size, patch_stride, pad=False):
             rview = None
     if rview is None:
         # the patch tensors, image by image, and the ragged call unchanged: it refuses what it refuses
-        out = ips_ragged(net, [net._materialise(images[b].unsqueeze(0), patch_size, patch_stride)[0] for b in range(len(images))], pad)
-    else:
-        out = _viewed_route(net, images, rview, short_ok=pad)
-    net._mem_count = tuple(min(n, net.M) for n in lengths) if pad else None
+        return ips_ragged(net, [net._materialise(images[b].unsqueeze(0), patch_size, patch_stride)[0] for b in range(len(images))], pad)
+    out = _device_route(net, _ViewSource(net, images.to(net.device).pixels, rview), short_ok=pad)   # (a host-resident batch is copied whole)
+    _leave_count(net, lengths, pad)
     return out
 
 
-def _viewed_route(net, images, rview, short_ok):
-    """``ragged._device_route`` with the packed rows replaced by the packed grid patches of a ragged view: the encoder pass
-    and the finish launch read the images where they lie."""
-    B, M, device = len(images), net.M, net.device
-    lengths = rview.lengths
-    short = frozenset(b for b, n in enumerate(lengths) if n <= M)
-    with net._scoring():
-        ca = net.transf.crs_attn
-        with net.plan.hold():
-            dev = images.to(device)                      # a host-resident batch is copied whole
-            # (drawn where the solo ips_image() calls draw: on the device the images are selected on)
-            perms = _draw(net, lengths, device, short) if net.shuffle else None
-            offsets = torch.tensor(rview.firsts + (rview.count,), dtype=torch.int64).to(device)
-            base = torch.repeat_interleave(offsets[:-1], torch.tensor(lengths, dtype=torch.int64).to(device), output_size=rview.count)
-            flat = local = None
-            if perms is not None:
-                local = torch.cat([p.to(device) for p in perms])
-                flat = (local + base).to(torch.int32)    # packed grid numbers first_b + perm_b[j]
-                by_index = os.environ.get("IPSX_SHUFFLE", "index") != "copy"
-                net.last_shuffle = [None if b in short else (local[rview.firsts[b]:rview.firsts[b] + lengths[b]] if by_index else perms[b]).unsqueeze(0)
-                                    for b in range(B)]
-            table = net._table_for(dev)                  # (uint8 pixels: read through the table, never expanded)
-            src = hip.PatchSource(images=dev.pixels, ragged=rview, table=table)
-            # ONE encoder pass over all grid patches (the fused trunk: blank ones encoded once, the same bits)
-            emb = net.plan.encode_source(src, index=flat, dedup=ragged_dedup(os.environ, net.plan, rview))
-            pos = None
-            if net.use_pos:
-                if local is None:
-                    local = torch.arange(rview.count, dtype=torch.int64, device=device) - base
-                pos = net.pos_enc[0].index_select(0, local)          # positions restart at 0 in every image
-            logits = hip.logits(emb.unsqueeze(0), pos.unsqueeze(0) if pos is not None else None, ca.folded_query(), ca.H * ca.n_token)[0]
-            mem_idx = hip.scan_ragged(logits, offsets, lengths, M, net.I, ca.H, ca.n_token, short_ok=short_ok)
-        mem_patch, mem_pos, mem_idx, grow = hip.ragged_finish_view(dev.pixels, rview, offsets, mem_idx, M, flat, pos, table=table)
-    if net.last_shuffle is not None and all(s is None for s in net.last_shuffle):
-        net.last_shuffle = None
+class _ViewSource:
+    """What ``ragged._device_route`` selects in, for ``ips_image_ragged``: the grid patches of the images in ``pixels`` (on the
+    device) through their ``hip.RaggedView``, read where they lie - no patch tensor is made, so ``rows`` is None."""
+    rows = None
 
-    padded = any(lengths[b] < M for b in short)
-    zero_shape = (1,) + rview.patch_shape
+    def __init__(self, net, pixels, rview):
+        self.net, self.pixels, self.rview = net, pixels, rview
+        self.draw_device = net.device                        # (where the solo ips_image() calls draw)
+        self.lengths, self.starts = rview.lengths, rview.firsts + (rview.count,)
+        self.row_shape, self.dtype = rview.patch_shape, pixels.dtype
 
-    def emb_of_slots():
-        """(B, M, D): the packed pass's rows; the padding holds the embedding of ONE all-zero patch."""
-        with torch.no_grad(), net._scoring(), net.plan.hold():
-            out = hip.gather_rows(emb.unsqueeze(0), (grow.clamp(min=0) if padded else grow).view(1, B * M)).view(B, M, -1)
-            if padded:
-                zero = net._embed(torch.zeros(zero_shape, dtype=torch.float32, device=device))
-                out = torch.where((grow < 0).unsqueeze(-1), zero.view(1, 1, -1), out)
-        return out
-    net.last_mem_idx = mem_idx
-    net._emb_make = emb_of_slots
-    return mem_patch, mem_pos
+    @functools.cached_property
+    def offsets(self):
+        return torch.tensor(self.starts, dtype=torch.int64).to(self.net.device)
+
+    def row_base(self):
+        return torch.repeat_interleave(self.offsets[:-1], torch.tensor(self.lengths, dtype=torch.int64).to(self.net.device),
+                                       output_size=self.rview.count)
+
+    def through_index(self, flat):
+        """A view is always read through the index; ``IPSX_SHUFFLE=copy`` decides only what ``last_shuffle`` keeps."""
+        return os.environ.get("IPSX_SHUFFLE", "index") != "copy", flat
+
+    def encode(self, flat=None):
+        """ONE encoder pass over all grid patches (uint8: through the table, never expanded), or over the patches ``flat``; on
+        the fused trunk blank ones are encoded once, the same bits."""
+        src = hip.PatchSource(images=self.pixels, ragged=self.rview, table=self.net._table_for(self.pixels))
+        return self.net.plan.encode_source(src, index=flat, dedup=ragged_dedup(os.environ, self.net.plan, self.rview))
+
+    def finish(self, offsets, mem_idx, flat, pos):
+        """ONE launch (``ipsx_ragged_finish_view``): the kept patches are copied out of their images."""
+        return hip.ragged_finish_view(self.pixels, self.rview, offsets, mem_idx, self.net.M, flat, pos, table=self.net._table_for(self.pixels))

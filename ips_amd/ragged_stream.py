@@ -42,13 +42,11 @@ the kept patches out of it.  Everywhere else the live patch rows are unfolded an
 route) B solo row streams run.
 """
 
-import os
-
 import torch
 
 from . import hip
-from .ragged import Ragged, _host_emb
-from .ragged_image import RaggedImages, ragged_dedup
+from .ragged import Ragged, _host_fill, _leave_count, _pad_emb, _refuse_short
+from .ragged_image import RaggedImages, _ViewSource
 from .stream import BandGeometry, IPSStream, StreamState
 
 
@@ -451,8 +449,7 @@ class RaggedIPSStream(StreamState):
             emb = net._embed(packed)                                      # ONE encoder pass over the packed rows
         else:                                                             # ... over the packed patches of the view
             packed, piece = None, dict(pixels=window, view=view)
-            src = hip.PatchSource(images=window, ragged=view, table=net._table_for(window))
-            emb = net.plan.encode_source(src, dedup=ragged_dedup(os.environ, net.plan, view))
+            emb = _ViewSource(net, window, view).encode()
         n_tot = starts[-1]
         # the row number inside its slide of every packed row: fed_b + r (ids, and the rows of the positional table)
         ids = torch.arange(n_tot, dtype=torch.int64, device=dev) + torch.repeat_interleave(table[2, :, 3], table[2, :, 2], output_size=n_tot)
@@ -506,24 +503,19 @@ class RaggedIPSStream(StreamState):
         net = self.net
         if self._B is None:
             raise RuntimeError("nothing was fed")
-        M, B = net.M, self._B
         if self._patch_size is not None:
             for b, g in enumerate(self._geoms):
                 if g.patch_rows == 0:        # (ips_image_ragged refuses a patch that does not fit its image)
                     raise ValueError("image {}: the {} pixel rows fed complete no patch row of height {}".format(
                         b, g.rows, self._patch_size[0]))
         for b, n in enumerate(self._fed):
-            if self.pad and n == 0:
-                raise ValueError("slide {} has no rows: nothing to pad".format(b))
-            if n <= M and not self.pad:
-                raise ValueError("slide {} has {} rows and the memory M = {}: the reference returns all {} of them there, the "
-                                 "batch would not be rectangular (select such a slide with ips())".format(b, n, M, n))
+            _refuse_short(b, n, net.M, self.pad)
         net._reset_last()
         if self._device_route:
             mem_patch, mem_pos = self._finish_hip()
         else:
             mem_patch, mem_pos = self._finish_aten()
-        net._mem_count = tuple(min(n, M) for n in self._fed) if self.pad else None
+        _leave_count(net, self._fed, self.pad)
         self._last_idx = net.last_mem_idx
         self._release()
         self._solo, self._stage = None, []
@@ -554,42 +546,19 @@ class RaggedIPSStream(StreamState):
         if not padded:
             net._mem_emb = mem_emb
             return mem_patch, mem_pos
-        zero_row = (1,) + self._row_shape, torch.float32 if u8 else self._dtype
-
-        def emb_of_slots():
-            """The padding holds the embedding of ONE all-zero row (made on first read, as ``ips_ragged`` makes it)."""
-            with torch.no_grad(), net._scoring():
-                zero = net._embed(torch.zeros(zero_row[0], dtype=zero_row[1], device=dev))
-                return torch.where(hole.unsqueeze(-1), zero.view(1, 1, -1), mem_emb)
-        net._emb_make = emb_of_slots
+        row_shape, dtype = self._row_shape, self._dtype
+        # (the padding holds the embedding of ONE all-zero row, made on first read, as ``ips_ragged`` makes it)
+        net._emb_make = lambda: _pad_emb(net, mem_emb, hole, row_shape, dtype)
         return mem_patch, mem_pos
 
     def _finish_aten(self):
         """What ``ragged._host_route`` builds, from the solo streams: a long slide's selection, a short slide's rows in the
         order given and the zero padding behind them."""
         net = self.net
-        M, B, D, device = net.M, self._B, net.D, net.device
-        u8 = self._dtype == torch.uint8      # (a row stream's bytes: the solo streams return them dequantised)
-        mem_patch = torch.zeros((B, M) + self._row_shape, dtype=torch.float32 if u8 else self._dtype, device=device)
-        mem_pos = torch.zeros((B, M, D), dtype=net.pos_enc.dtype, device=device) if net.use_pos else None
-        mem_idx = torch.full((B, M), -1, dtype=torch.int64, device=device)
-        long_emb, short_rows = {}, {}
-        for b, n in enumerate(self._fed):
-            p, q = self._solo[b].finish()
-            self._iters[b] = self._solo[b].iterations
-            if n > M:
-                mem_patch[b] = p[0]
-                if net.use_pos:
-                    mem_pos[b] = q[0]
-                mem_idx[b] = net.last_mem_idx[0]
-                long_emb[b] = net.last_mem_emb
-            else:                                  # the rows in arrival order, as fill_batch writes them
-                short_rows[b] = rows = p[0]
-                mem_patch[b, :n] = rows
-                if net.use_pos:
-                    mem_pos[b, :n] = net.pos_enc[0, :n]
-                mem_idx[b, :n] = torch.arange(n, dtype=torch.int64, device=device)
-        net._reset_last()                          # (what the last solo stream left is that stream's, not this one's)
-        net.last_mem_idx = mem_idx
-        net._emb_make = lambda: _host_emb(net, long_emb, short_rows)
-        return mem_patch, mem_pos
+
+        def solo():                          # (a row stream's bytes: the solo streams return them dequantised)
+            for b, n in enumerate(self._fed):
+                p, q = self._solo[b].finish()
+                self._iters[b] = self._solo[b].iterations
+                yield (p, q, net.last_mem_idx, net.last_mem_emb) if n > net.M else p[0]
+        return _host_fill(net, self._fed, self._row_shape, self._dtype, solo())

@@ -33,8 +33,14 @@ def draw_shuffle(patches, style):
     streams are consumed identically and ``x[:, perm]`` / ``x.gather(1, perm...)`` is their result.  ``'batch'``: (N,)
     on the host (the CPU generator); ``'instance'``: (B, N) on the patches' device; any other style: None, as
     ``do_shuffle`` leaves the patches alone.  Lets ``IPSNet.ips`` select through an index instead of a permuted copy."""
+    return draw_shuffle_for(patches.shape[0], patches.shape[1], patches.device, style)
+
+
+def draw_shuffle_for(B, N, device, style):
+    """``draw_shuffle`` for (B, N, ...) patches on ``device`` that need not exist: a ragged call draws for the grid patches
+    of an image it never unfolds."""
     if style == 'batch':
-        return torch.randperm(patches.shape[1])
+        return torch.randperm(N)
     if style == 'instance':
-        return torch.rand(patches.shape[:2], device=patches.device).argsort(1)
+        return torch.rand((B, N), device=device).argsort(1)
     return None

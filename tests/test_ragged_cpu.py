@@ -145,6 +145,35 @@ def test_blank_dedup_is_refused_as_streams_refuse_it(monkeypatch):
     net.ips_ragged(slides)
 
 
+@pytest.mark.parametrize("pad, lengths", [(False, (4, 7)), (True, (0, 7))], ids=["short", "empty"])
+def test_the_call_and_the_stream_refuse_short_and_empty_slides_in_the_same_words(pad, lengths):
+    """M = 4: a slide of M rows without ``pad``, a slide of no rows with it - one ``ValueError`` text from ``ips_ragged`` and
+    from ``RaggedIPSStream.finish()``."""
+    conf = rc.feature_conf(M=4)
+    net = rc.make_net(conf, CPU)
+    slides = [torch.zeros(n, conf.n_chan_in) for n in lengths]
+    with pytest.raises(ValueError) as call:
+        net.ips_ragged(slides, pad=pad)
+    with pytest.raises(ValueError) as stream:
+        net.ips_ragged_stream(pad=pad).feed(slides).finish()
+    assert str(call.value) == str(stream.value) and "slide 0" in str(call.value)
+
+
+@pytest.mark.parametrize("B", [1, 3])
+@pytest.mark.parametrize("style", ["batch", "instance"])
+def test_the_draw_by_shape_consumes_the_rng_as_the_draw_on_a_tensor(style, B):
+    from ips_amd.shuffle import draw_shuffle, draw_shuffle_for
+    N = 7
+    torch.manual_seed(23)
+    want = draw_shuffle(torch.zeros(B, N, 5), style)
+    want_next = torch.rand(1), torch.randperm(2)
+    torch.manual_seed(23)
+    got = draw_shuffle_for(B, N, CPU, style)
+    assert got.dtype == want.dtype and torch.equal(got, want)
+    assert torch.equal(torch.rand(1), want_next[0]) and torch.equal(torch.randperm(2), want_next[1])
+    assert draw_shuffle_for(B, N, CPU, "none") is None and draw_shuffle(torch.zeros(B, N), "none") is None
+
+
 # ------------------------------------------------------------------ the contract on CPU
 @pytest.fixture(scope="module")
 def nets():
